@@ -226,6 +226,26 @@ class Buffers:
         self.rew = torch.zeros(B, device=device); self.rst = torch.zeros(B, dtype=torch.uint8, device=device); self.to = torch.zeros(B, device=device)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the timed path handed its caller in its last timed step, one float32 DIR/<name>.npy per array (all arrays share the
+    env axis 0).  The inputs are seeded, so two builds compare output for output.  Above 64 MB in all, a fixed seeded sample of envs is written
+    (their indices in env_index.npy)."""
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    n = next(iter(host.values())).shape[0]
+    row_bytes = sum(a.nbytes // n for a in host.values())
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - 4096 * (len(host) + 1)) // (row_bytes + 8)            # room for the .npy headers and the float64 index
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        host = {k: a[idx] for k, a in host.items()}
+        host["env_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+
+
 def timed_run(sim, actions, first, n, buf, stream):
     """n un-instrumented steps (actions[first .. first+n)), bracketed by device synchronisation -> seconds."""
     torch.cuda.synchronize()
@@ -407,6 +427,8 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile-pass", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip steady_state / action_sets / curriculum_live / workloads / ref_protocol_fps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the env-step outputs of the last timed step (rank 0's shard) as float32 DIR/<name>.npy (e.g. bench_outputs/)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -522,6 +544,12 @@ def main():
         tt = torch.tensor([elapsed], device=coll_device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        rew_out, done_out = rew, rst
+        if storage is not None and policy is None:                       # sharded job: rewards / done flags of the step landed in the storage
+            t_last = (W + K - 1) % ROLLOUT_LEN
+            rew_out, done_out = storage.rewards[t_last], storage.dones[t_last]
+        dump_outputs(args.dump_outputs, {"obs": obs, "priv_obs": priv, "rew": rew_out, "done": done_out, "time_out": to})
     errno = sim.check_errno()
     using_graph, graph_fallbacks = sim.graph_status()
     total_envs = B * world

@@ -11,6 +11,8 @@ from go2_sim2real_locomotion_rl_amd.capi import REPO_ROOT
 from go2_sim2real_locomotion_rl_amd.model_blob import MODEL_JSON, load_model_json, pack_model
 
 # URDF facts (genesis/assets/urdf/go2/urdf/go2.urdf)
+# the compiler's inputs: the reference's plane / go2 / anymal_c URDF data files, stored with their asset-relative paths
+ASSETS = os.path.join(REPO_ROOT, "tests", "golden", "assets")
 LINK_ORDER = ["planeLink", "base", "FL_hip", "FR_hip", "RL_hip", "RR_hip", "FL_thigh", "FR_thigh", "RL_thigh", "RR_thigh", "FL_calf",
               "FR_calf", "RL_calf", "RR_calf"]
 
@@ -85,19 +87,16 @@ def test_blob_layout():
 
 
 def test_committed_json_matches_generator():
-    """tests/golden/go2_model.sha256 pins the committed tables; when the reference assets are present the generator is
-    re-run and must reproduce the committed JSON bit for bit."""
+    """tests/golden/go2_model.sha256 pins the committed tables; the generator, re-run on the stored URDF files
+    (tests/golden/assets), must reproduce the committed JSON bit for bit."""
     txt = open(MODEL_JSON).read()
     sha = hashlib.sha256(txt.encode()).hexdigest()
     pin = open(os.path.join(REPO_ROOT, "tests", "golden", "go2_model.sha256")).read().split()[0]
     assert sha == pin
-    assets = "/root/reference/genesis/assets"
-    if not os.path.isdir(assets):
-        pytest.skip("reference assets not present (GPU box)")
     spec = importlib.util.spec_from_file_location("compile_go2_model", os.path.join(REPO_ROOT, "tools", "compile_go2_model.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    regenerated = json.dumps(mod.build_model(assets), indent=1, sort_keys=True) + "\n"
+    regenerated = json.dumps(mod.build_model(ASSETS), indent=1, sort_keys=True) + "\n"
     assert regenerated == txt
 
 
@@ -149,14 +148,13 @@ def test_anymal_c_stands_on_the_oracle(oracle_lib):
     assert (z > 0.55).all() and (z < 0.70).all()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/genesis/assets"), reason="the URDF assets exist in the build container only")
 def test_anymal_c_model_is_what_the_compiler_produces():
     import importlib.util
     import json
 
     spec = importlib.util.spec_from_file_location("compile_model", os.path.join(os.path.dirname(ANYMAL_JSON), "..", "..", "tools", "compile_go2_model.py"))
     mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
-    model = mod.build_model("/root/reference/genesis/assets", base_init_pos=mod.ROBOTS["anymal_c"]["base_init_pos"], robot="anymal_c")
+    model = mod.build_model(ASSETS, base_init_pos=mod.ROBOTS["anymal_c"]["base_init_pos"], robot="anymal_c")
     assert json.loads(json.dumps(model, sort_keys=True)) == json.load(open(ANYMAL_JSON))
 
 

@@ -21,7 +21,6 @@ from go2_sim2real_locomotion_rl_amd.configs import build_stair_terrain, flatten_
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = ["base_jump", "base_crouch", "walk", "walk_delay1", "walk_delay2", "stairs"]
-REF_DIR = "/root/reference/examples/locomotion/final"
 
 
 def load_fixture(case, physics="strict"):
@@ -131,19 +130,38 @@ def test_hip_env_matches_the_reference_env_files(hip_lib, blob, case):
     replay_and_compare(hip_lib, blob, case, gpu=True, physics="strict" if os.environ.get("GO2SIM_TEST_STRICT") == "1" else "fast")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DIR), reason="the reference tree exists in the build container only")
-@pytest.mark.parametrize("case", CASES)
-def test_fixtures_are_what_the_reference_files_produce(oracle_lib, case):
-    """Re-runs the reference's env file for the first steps of the tape and compares with the committed fixture bit for bit: the fixtures are
-    reproducible from the committed script, and the reference's go2_env_base / walk / stair.py import, build, reset() and step on the genesis
-    alias with their real call shapes (set_mass_shift([s], [0]), set_COM_shift([[x, y, z]], [0]), force [B, 3] for one link ...)."""
+def fixture_generator():
+    """tools/make_ref_env_fixtures.py: the script that recorded the fixtures."""
     import sys
 
     sys.path.insert(0, os.path.join(os.path.dirname(GOLDEN), "..", "tools"))
     import make_ref_env_fixtures as M
 
+    return M
+
+
+def check_generator_inputs(M, case, cfgs_of_script):
+    """Both fixtures of `case` (strict and fast physics) hold the cfg dicts and the action tape the committed script produces."""
+    for physics in ("strict", "fast"):
+        z, cfgs, meta = load_fixture(case, physics)
+        assert json.loads(json.dumps(cfgs_of_script)) == cfgs, f"{case} ({physics}): cfg dicts"
+        tape = M.action_tape(meta["steps"], meta["n_envs"], z["actions"].shape[2], meta["seed"])
+        assert np.array_equal(tape, z["actions"]), f"{case} ({physics}): action tape"
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_fixtures_are_what_the_reference_files_produce(oracle_lib, case):
+    """The fixtures are reproducible from the committed script: the cfg dicts it pins and the action tape it draws are the ones stored in both
+    fixtures of the case.  With GO2SIM_REFERENCE_DIR set to a checkout of the reference project, the reference's env file is also re-run for the
+    first steps of the tape and compared with the committed fixture bit for bit: the reference's go2_env_base / walk / stair.py import, build,
+    reset() and step on the genesis alias with their real call shapes (set_mass_shift([s], [0]), set_COM_shift([[x, y, z]], [0]), force [B, 3]
+    for one link ...)."""
+    M = fixture_generator()
+    check_generator_inputs(M, case, M.pinned_cfgs(case))
+    if M.REF_DIR is None:
+        return
+    assert os.path.isdir(M.REF_DIR), f"GO2SIM_REFERENCE_DIR holds no {os.path.relpath(M.REF_DIR, M.REF_ROOT)}"
     z, cfgs, meta = load_fixture(case, "fast")
-    assert json.loads(json.dumps(M.pinned_cfgs(case))) == cfgs
     out, _ = M.run_case(case, B=meta["n_envs"], T=meta["steps"], seed=meta["seed"], n_run=30, physics="fast")
     for key in ("obs", "priv", "rew", "rew_terms", "done", "time_outs", "ctrl_pos", "ctrl_force", "commands", "base_pos", "episode_length"):
         assert np.array_equal(out[key], z[key][:30]), key

@@ -21,7 +21,7 @@ import os
 import numpy as np
 import pytest
 
-from test_ref_env_fixtures import REF_DIR, GOLDEN, load_fixture, replay_and_compare
+from test_ref_env_fixtures import check_generator_inputs, fixture_generator, load_fixture, replay_and_compare
 
 RNG_CASES = ["walk_rng", "walk_rng_axis", "stairs_rng", "base_jump_rng"]
 
@@ -72,16 +72,16 @@ def test_hip_env_matches_the_reference_env_files_with_scheduled_draws(blob, case
     replay_and_compare(lib, blob, case, gpu=True, physics="fast")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DIR), reason="the reference tree exists in the build container only")
 @pytest.mark.parametrize("case", RNG_CASES)
 def test_rng_fixtures_are_what_the_reference_files_produce(case):
-    import sys
-
-    sys.path.insert(0, os.path.join(os.path.dirname(GOLDEN), "..", "tools"))
-    import make_ref_env_fixtures as M
-
+    """As test_ref_env_fixtures.test_fixtures_are_what_the_reference_files_produce, with the scheduled draws: the committed script's cfg dicts and
+    action tape are the stored ones; with GO2SIM_REFERENCE_DIR set, the reference's env file is re-run for the first 30 steps as well."""
+    M = fixture_generator()
+    check_generator_inputs(M, case, M.rng_cfgs(case))
+    if M.REF_DIR is None:
+        return
+    assert os.path.isdir(M.REF_DIR), f"GO2SIM_REFERENCE_DIR holds no {os.path.relpath(M.REF_DIR, M.REF_ROOT)}"
     z, cfgs, meta = load_fixture(case, "fast")
-    assert json.loads(json.dumps(M.rng_cfgs(case))) == cfgs
     out, _ = M.run_case(case, B=meta["n_envs"], T=meta["steps"], seed=meta["seed"], n_run=30, physics="fast")
     for key in ("obs", "priv", "rew", "rew_terms", "done", "time_outs", "ctrl_pos", "ctrl_force", "commands", "base_pos", "episode_length", "terrain_row"):
         assert np.array_equal(out[key], z[key][:30]), key

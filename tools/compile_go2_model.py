@@ -20,9 +20,8 @@ urdfpy + MuJoCo + trimesh for exactly two assets (plane.urdf, go2.urdf):
                                                                     ** parity unpinned **
   * links/dofs invweight and meaninertia at qpos0      (rigid_solver.py:529-682, abd/misc.py:103-123)
 
-Input : the two URDF data files under /root/reference/genesis/assets (read as data only).
-Output: go2_sim2real_locomotion_rl_amd/model/go2_model.json (committed; the GPU box never sees
-        /root/reference).
+Input : the URDF data files of the reference's genesis/assets, stored under tests/golden/assets (read as data only).
+Output: go2_sim2real_locomotion_rl_amd/model/go2_model.json (committed).
 
 Run:  python tools/compile_go2_model.py [--assets DIR] [--out FILE]
 """
@@ -828,8 +827,8 @@ def build_model(assets_dir, base_init_pos=(0.0, 0.0, 0.42), base_init_quat=(1.0,
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--assets", default="/root/reference/genesis/assets")
     here = os.path.dirname(os.path.abspath(__file__))
+    ap.add_argument("--assets", default=os.path.join(here, "..", "tests", "golden", "assets"))   # the URDF data files, stored as test fixtures
     ap.add_argument("--robot", choices=sorted(ROBOTS) + sorted(SHAPE_ROBOTS), default="go2")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()

@@ -1,5 +1,5 @@
-import sys, time, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, time, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from go2_sim2real_locomotion_rl_amd.capi import load_hip_lib
 side = torch.cuda.Stream()

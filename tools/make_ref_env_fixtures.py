@@ -1,6 +1,6 @@
-"""Golden fixtures from the reference's OWN Go2Env files (build container only; nothing of /root/reference travels).
+"""Golden fixtures from the reference's OWN Go2Env files (needs a checkout of the reference project; nothing of it is stored here).
 
-    python tools/make_ref_env_fixtures.py            # writes tests/golden/ref_env_<case>.npz
+    GO2SIM_REFERENCE_DIR=<reference checkout> python tools/make_ref_env_fixtures.py      # writes tests/golden/ref_env_<case>.npz
 
 The reference's env classes (examples/locomotion/final/go2_env_{base,walk,stair}.py) import only torch, math, numpy, `genesis` and
 `genesis.utils.geom`.  The repo's `genesis/` alias package resolves those two imports to go2_sim2real_locomotion_rl_amd.genesis_shim, which
@@ -37,7 +37,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-REF_DIR = "/root/reference/examples/locomotion/final"
+REF_ROOT = os.environ.get("GO2SIM_REFERENCE_DIR")                    # a checkout of the reference project: needed to (re)run its env files
+REF_DIR = os.path.join(REF_ROOT, "examples", "locomotion", "final") if REF_ROOT else None
 OUT_DIR = os.path.join(ROOT, "tests", "golden")
 
 
@@ -279,8 +280,8 @@ def run_case(case, B=8, T=96, seed=11, n_run=None, physics="strict"):
 
 
 def main():
-    if not os.path.isdir(REF_DIR):
-        raise SystemExit("the reference tree is not present: fixtures can only be regenerated in the build container")
+    if REF_DIR is None or not os.path.isdir(REF_DIR):
+        raise SystemExit("set GO2SIM_REFERENCE_DIR to a checkout of the reference project: the fixtures are recorded from its env files")
     from go2_sim2real_locomotion_rl_amd import build
 
     build.build_oracle()
