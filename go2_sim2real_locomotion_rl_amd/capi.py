@@ -67,6 +67,7 @@ class EnvGlobals(ctypes.Structure):
         ("last_reset_count", ctypes.c_int), ("last_episode_rew", ctypes.c_float * 32),
         ("n_reset_now", ctypes.c_int), ("ep_acc", ctypes.c_float * 32), ("terrain_mean_row", ctypes.c_float), ("terrain_row_sum", ctypes.c_int),
         ("lock_terrain_rows", ctypes.c_int), ("sync_calls", ctypes.c_int), ("shard_counters", ctypes.c_double * 5),
+        ("engine_kp", ctypes.c_float), ("engine_kd", ctypes.c_float),
     ]
 
     def as_dict(self):

@@ -9,7 +9,7 @@ import math
 
 import numpy as np
 
-from .capi import C
+from .capi import C, Go2SimError
 from .model_blob import load_model_json
 
 REWARD_IDS = {
@@ -24,9 +24,11 @@ REWARD_IDS = {
 }
 
 
-def get_walk_cfgs():
-    """go2_train_walk.py:68-372 (values transcribed; comments there explain the choices)."""
+def get_walk_cfgs(pls_enable=True):
+    """go2_train_walk.py:68-372 (values transcribed; comments there explain the choices).  `pls_enable` is the script's switch (:77): off, the
+    policy has no per-leg stiffness actions (12 actions, 45 / 100 observations, :83-84, :305-309) and the motors run on the nominal gains."""
     kp_nominal, kd_nominal = 60.0, 2.0
+    num_actions = 12 + (4 if pls_enable else 0)
     curriculum_cfg = {
         "enabled": True, "level_init": 0.10, "level_min": 0.0, "level_max": 1.0, "ema_alpha": 0.03,
         "ready_timeout_rate": 0.80, "ready_tracking": 0.75, "ready_fall_rate": 0.15, "ready_streak": 4,
@@ -39,7 +41,7 @@ def get_walk_cfgs():
         "push_interval_easy_s": 10.0, "delay_easy_max_steps": 0, "global_dr_update_interval": 200,
     }
     env_cfg = {
-        "num_actions": 16, "num_pos_actions": 12, "pls_enable": True, "pls_kp_range": [10.0, 70.0], "pls_kp_default": 40.0,
+        "num_actions": num_actions, "num_pos_actions": 12, "pls_enable": bool(pls_enable), "pls_kp_range": [10.0, 70.0], "pls_kp_default": 40.0,
         "pls_kp_action_scale": 20.0, "kp": kp_nominal, "kd": kd_nominal, "torque_limits": [23.7, 23.7, 45.0] * 4,
         "simulate_action_latency": True, "foot_names": ["FR_calf", "FL_calf", "RR_calf", "RL_calf"],
         "foot_contact_threshold": 3.0,
@@ -62,7 +64,7 @@ def get_walk_cfgs():
         "com_shift_range": [-0.03, 0.03], "leg_mass_shift_range": [-0.5, 0.5], "gravity_offset_range": [-1.0, 1.0],
         "motor_strength_range": [0.9, 1.1], "min_delay_steps": 0, "max_delay_steps": 1,
     }
-    num_obs = 3 + 3 + 3 + 12 + 12 + 16
+    num_obs = 3 + 3 + 3 + 12 + 12 + num_actions
     obs_cfg = {"num_obs": num_obs, "num_privileged_obs": num_obs + 3 + 1 + 12 + 12 + 12 + 1 + 3 + 4 + 3 + 3 + 1,
                "obs_scales": {"lin_vel": 2.0, "ang_vel": 0.25, "dof_pos": 1.0, "dof_vel": 0.05}}
     reward_cfg = {
@@ -77,6 +79,25 @@ def get_walk_cfgs():
     command_cfg = {"num_commands": 3, "lin_vel_x_range": [-1.0, 1.0], "lin_vel_y_range": [-0.3, 0.3], "ang_vel_range": [-1.0, 1.0],
                    "cmd_curriculum": True, "cmd_curriculum_start_frac": 0.1, "compound_commands": True, "rel_standing_envs": 0.1}
     return env_cfg, obs_cfg, reward_cfg, command_cfg
+
+
+def _check_batch_gain_ranges(num_envs, f, i, F, I):
+    """The exact-sum argument of k_env_engine_gains (go2sim.hip): every effective gain base x factor is a float32 in [2^0, 2^7) and the batch holds at
+    most 2^23 / 12 envs, so the float64 sum of all of them is exact in any order."""
+    if num_envs * 12 > 1 << 23:
+        raise ValueError(f"the engine-PD batch gain sums 12 gains per env exactly in float64 for at most {(1 << 23) // 12} envs")
+
+    def span(base, flag=None):
+        if flag is not None and not i[I(flag)]:
+            return 1.0, 1.0
+        vals = [f[F(base + s)] for s in ("_EASY_LO", "_EASY_HI", "_HARD_LO", "_HARD_HI")]
+        return min(vals), max(vals)
+
+    for gain, fac, flag in (("KPR", "KPF", "HAS_KPF_DR"), ("KDR", "KDF", "HAS_KDF_DR")):
+        (blo, bhi), (flo, fhi) = span(gain), span(fac, flag)
+        if not (blo * flo >= 1.0 and bhi * fhi * (1.0 + 2.0 ** -20) < 128.0):
+            raise ValueError(f"the engine-PD batch gain needs every effective {'kp' if gain == 'KPR' else 'kd'} (range x factor) in [1, 128); got "
+                             f"[{blo * flo}, {bhi * fhi}]")
 
 
 def _name_maps(model):
@@ -169,8 +190,6 @@ def flatten_walk_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg, *, mod
     rng("HAS_LEGM_DR", "leg_mass_shift_range", [-0.1, 0.1], "leg_mass_shift_easy", "LEGM")
     rng("HAS_GOFF_DR", "gravity_offset_range", [-0.2, 0.2], "gravity_offset_easy", "GOFF")
     rng("HAS_MSTR_DR", "motor_strength_range", [0.97, 1.03], "motor_strength_easy", "MSTR")
-    if not pls and "kp_range" in env_cfg:
-        raise NotImplementedError("non-PLS per-env kp/kd ranges are not wired yet (reference configs use PLS)")
 
     on = env_cfg.get("obs_noise", None)
     i[I("HAS_OBS_NOISE")] = int(on is not None)
@@ -214,9 +233,15 @@ def flatten_walk_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg, *, mod
     i[I("NUM_ACTIONS")], i[I("NUM_POS_ACTIONS")] = env_cfg["num_actions"], npos
     i[I("NUM_OBS")], i[I("NUM_PRIV_OBS")] = obs_cfg["num_obs"], obs_cfg.get("num_privileged_obs") or obs_cfg["num_obs"]
     i[I("PLS_ENABLE")] = int(pls)
+    # PLS off (go2_env_walk.py:519, 758-801, 1007-1021): manual PD with per-env base x factor gains when kp_factor_range is set (mode A), else engine PD
+    # (control_dofs_position) whose motor gains are the batch mean of the gains drawn at each reset when kp_range is set (mode B), or env_cfg kp / kd (mode C)
     i[I("MANUAL_PD")] = int(pls or ("kp_factor_range" in env_cfg))
-    if not i[I("MANUAL_PD")]:
-        raise NotImplementedError("engine-PD control path (control_dofs_position) is the base env; not wired in the walk env yet")
+    i[I("ENGINE_BATCH_GAIN")] = int(not i[I("MANUAL_PD")] and "kp_range" in env_cfg)
+    if i[I("ENGINE_BATCH_GAIN")]:
+        if shared_globals:
+            raise Go2SimError("the engine-PD batch gain (pls_enable=False, kp_range set, no kp_factor_range) is one mean over the whole batch; "
+                              "sharding it over ranks (shared_globals=True) is not supported")
+        _check_batch_gain_ranges(num_envs, f, i, F, I)
     i[I("SUBSTEPS")] = 2
     i[I("MAX_EPISODE_LENGTH")] = math.ceil(env_cfg["episode_length_s"] / dt)
     i[I("RESAMPLE_STEPS")] = int(env_cfg["resampling_time_s"] / dt)
@@ -448,10 +473,11 @@ def build_stair_terrain(terrain_cfg):
     return hf, info
 
 
-def get_stair_cfgs():
+def get_stair_cfgs(pls_enable=True):
     """go2_train_stair.py:84-372 (values transcribed): the walk configuration plus the stair terrain, the terrain-relative rewards, the
-    two-phase DR schedule and the 182-wide privileged observation (49 + 55 + terrain row + 77 height-scan points)."""
-    env_cfg, obs_cfg, reward_cfg, command_cfg = get_walk_cfgs()
+    two-phase DR schedule and the 182-wide privileged observation (49 + 55 + terrain row + 77 height-scan points; 45 + ... = 178 with
+    `pls_enable` off, go2_train_stair.py:72)."""
+    env_cfg, obs_cfg, reward_cfg, command_cfg = get_walk_cfgs(pls_enable)
     terrain = get_stair_terrain_cfg()
     terrain["height_scan"] = {"num_x": 11, "num_y": 7, "x_range": [-0.5, 0.5], "y_range": [-0.3, 0.3]}
     env_cfg["curriculum"].update({"level_init": 0.65, "ready_timeout_rate": 0.60, "ready_tracking": 0.45, "ready_fall_rate": 0.35, "ready_streak": 5,

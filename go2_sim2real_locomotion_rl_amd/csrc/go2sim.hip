@@ -500,7 +500,8 @@ constexpr int MODELS_LDS_BYTES = lds_dma_bytes((int)sizeof(ModelS));
   X(e_dof_pos, NM) X(e_dof_vel, NM) X(last_dof_vel, NM) X(torque, NM) X(base_pos, 3) X(base_quat, 4) X(base_lin_vel, 3) \
   X(base_ang_vel, 3) X(projected_gravity, 3) X(base_euler, 3) X(commands, 3) X(time_out, 1) X(kp_factors, NM)          \
   X(kd_factors, NM) X(motor_strength, NM) X(gravity_offset, 3) X(current_push_force, 3) X(push_stored_force, 3)       \
-  X(feet_air_time, 4) X(base_vel_world, 3) X(last_base_pos_x, 1) X(episode_sums, NREW) X(rew_terms, NREW) X(rew, 1) X(obs, NOBS_MAX) X(priv, NPRIV_MAX)
+  X(feet_air_time, 4) X(base_vel_world, 3) X(last_base_pos_x, 1) X(episode_sums, NREW) X(rew_terms, NREW) X(rew, 1) X(obs, NOBS_MAX) X(priv, NPRIV_MAX) \
+  X(base_kp, 1) X(base_kd, 1)
 
 #define GO2SIM_INT_FIELDS(X)                                                                                         \
   X(n_contacts, 1) X(n_con, 1) X(err, 1) X(is_warmstart, 1) X(first_time, 1) X(n_broad, 1) X(solver_iters, 1) X(ctrl_mode, ND) \
@@ -611,7 +612,7 @@ struct E {
   FA(actions) FA(last_actions) FA(applied_actions) FA2(action_history, NA) FA(target_dof_pos) FA(e_dof_pos) FA(e_dof_vel) FA(last_dof_vel)
   FA(torque) FA(base_pos) FA(base_quat) FA(base_lin_vel) FA(base_ang_vel) FA(projected_gravity) FA(base_euler) FA(commands) FA(time_out)
   FA(kp_factors) FA(kd_factors) FA(motor_strength) FA(gravity_offset) FA(current_push_force) FA(push_stored_force) FA(feet_air_time) FA(base_vel_world) FA(last_base_pos_x)
-  FA(episode_sums) FA(rew_terms) FA(rew) FA(obs) FA(priv)
+  FA(episode_sums) FA(rew_terms) FA(rew) FA(obs) FA(priv) FA(base_kp) FA(base_kd)
   IA(n_contacts) IA(n_con) IA(err) IA(is_warmstart) IA(first_time) IA(n_broad) IA(solver_iters) IA(ctrl_mode)
   IA(gjk_fallback) IA(delay_steps) IA(episode_length) IA(reset_buf) IA(push_remaining) IA(foot_contact) IA(last_foot_contact) IA(terrain_row) IA(terrain_key)
   AA(acc) AA(qacc_ws) AA(force) AA(qf_smooth) AA(acc_smooth) AA(qfrc_constraint) AA3(cdof_ang) AA3(cdof_vel) AA3(cdofd_ang)
@@ -4398,7 +4399,7 @@ struct DCfg { double d[GO2SIM_FC_N_HOST]; float f[GO2SIM_FC_COUNT]; int i[GO2SIM
 struct Acc { double timeouts, tracking, ep[NREW]; int n_reset_now; int done; };   // done: workgroups of k_env_post_a that have finished
 typedef go2sim_env_globals_t Glob;
 
-enum { RNG_ACTION_NOISE = 1, RNG_PUSH = 2, RNG_CMD = 3, RNG_OBS_NOISE = 4, RNG_RESET_DR = 5, RNG_GLOBAL_DR = 6, RNG_RESET_CMD = 7, RNG_RESET_POSE = 8, RNG_TERRAIN_ROW = 9, RNG_TERRAIN_PERM = 10 };
+enum { RNG_ACTION_NOISE = 1, RNG_PUSH = 2, RNG_CMD = 3, RNG_OBS_NOISE = 4, RNG_RESET_DR = 5, RNG_GLOBAL_DR = 6, RNG_RESET_CMD = 7, RNG_RESET_POSE = 8, RNG_TERRAIN_ROW = 9, RNG_TERRAIN_PERM = 10, RNG_RESET_KPKD = 11 };
 __host__ __device__ inline dm_u4 rng4(uint64_t seed, uint32_t purpose, uint32_t env, uint32_t step, uint32_t idx) {
 #ifdef GO2SIM_RNG_CONST   // diagnostic build (include/go2sim_detmath.h): every word of a draw is its stream key
   dm_u4 o; o.v[0] = o.v[1] = o.v[2] = o.v[3] = step; (void)purpose; (void)env; (void)idx; (void)seed; return o;
@@ -4579,6 +4580,8 @@ __global__ __launch_bounds__(WG) void k_env_pre(Pool P, const Model* __restrict_
   float kpf[NM], kdf[NM], mst[NM], dp[NM], dv[NM];
 #pragma unroll
   for (int i = 0; i < NM; ++i) { kpf[i] = kp_factors[i]; kdf[i] = kd_factors[i]; mst[i] = motor_strength[i]; dp[i] = dof_pos[i]; dv[i] = dof_vel[i]; }
+  float bkp = c.f[GO2SIM_FC_KP], bkd = c.f[GO2SIM_FC_KD];             // PLS off: the per-env kp_val / kd_val of the last reset when kp_range is set
+  if (manual_pd && !pls && c.i[GO2SIM_IC_HAS_KP_RANGE]) { bkp = e.base_kp()[0]; bkd = e.base_kd()[0]; }
   float psf_[3] = {psf[0], psf[1], psf[2]}; int rem0 = prem[0];
   V3 pl_pos = e.l_pos()[pl], pl_com = e.root_com()[pl];
   float ext_[6];
@@ -4636,7 +4639,7 @@ __global__ __launch_bounds__(WG) void k_env_pre(Pool P, const Model* __restrict_
       eff_kp = kp_leg * kpf[i] * mst[i];
       eff_kd = kd_j * kdf[i];
     } else {
-      eff_kp = c.f[GO2SIM_FC_KP] * kpf[i]; eff_kd = c.f[GO2SIM_FC_KD] * kdf[i];
+      eff_kp = bkp * kpf[i]; eff_kd = bkd * kdf[i];                   // _effective_kp / kd = base x factor (go2_env_walk.py:794-795)
     }
     float pos_error = target[i] - dp[i];
     float torque = eff_kp * pos_error - eff_kd * dv[i];
@@ -4709,6 +4712,8 @@ __global__ __launch_bounds__(64) void k_pre_dynamics_team(Pool P, const ModelS* 
   const float h_ = base_env ? e.last_actions()[ia] : hist[read_idx][ia];
   const float kpf = e.kp_factors()[im], kdf = e.kd_factors()[im], mst = e.motor_strength()[im], dp = e.e_dof_pos()[im], dv = e.e_dof_vel()[im];
   const bool manual_pd = c.i[GO2SIM_IC_MANUAL_PD] != 0, pls = c.i[GO2SIM_IC_PLS_ENABLE] != 0;
+  const bool base_gains = manual_pd && !pls && c.i[GO2SIM_IC_HAS_KP_RANGE];   // PLS off: the per-env kp_val / kd_val of the last reset
+  const float bkp = base_gains ? e.base_kp()[0] : c.f[GO2SIM_FC_KP], bkd = base_gains ? e.base_kd()[0] : c.f[GO2SIM_FC_KD];
   const bool push_on = c.i[GO2SIM_IC_HAS_PUSH] && g.push_enable;
   const int pl = c.i[GO2SIM_IC_PUSH_LINK];
   auto psf = e.push_stored_force(); auto prem = e.push_remaining(); auto cpf = e.current_push_force(); auto ext = e.ext();
@@ -4768,7 +4773,7 @@ __global__ __launch_bounds__(64) void k_pre_dynamics_team(Pool P, const ModelS* 
           eff_kp = kp_leg * kpf * mst;
           eff_kd = kd_j * kdf;
         } else {
-          eff_kp = c.f[GO2SIM_FC_KP] * kpf; eff_kd = c.f[GO2SIM_FC_KD] * kdf;
+          eff_kp = bkp * kpf; eff_kd = bkd * kdf;                        // _effective_kp / kd = base x factor (go2_env_walk.py:794-795)
         }
         const float pos_error = target - dp;
         float torque = eff_kp * pos_error - eff_kd * dv;
@@ -5427,6 +5432,11 @@ DEV void env_reset_one(const Model& m, const DCfg& c, const Glob& g, const E& e,
   if (c.i[GO2SIM_IC_HAS_MSTR_DR])
     for (int blk = 0; blk < 3; ++blk) { dm_u4 r = rng4(seed, RNG_RESET_DR, b, rc, 7 + blk); for (int k = 0; k < 4; ++k) motor_strength[4 * blk + k] = rand_float(lerp_lo(c, GO2SIM_FC_MSTR_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_MSTR_EASY_LO, ts), r.v[k]); }
   }
+  if (!c.i[GO2SIM_IC_PLS_ENABLE] && c.i[GO2SIM_IC_HAS_KP_RANGE]) {   // _randomize_kp_kd with PLS off (go2_env_walk.py:776-781): kp_val, then kd_val, one per env;
+    dm_u4 r = rng4(seed, RNG_RESET_KPKD, b, rc, 0);                   // a stream of its own, so that no draw of a PLS-on configuration moves
+    e.base_kp()[0] = rand_float(lerp_lo(c, GO2SIM_FC_KPR_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_KPR_EASY_LO, ts), r.v[0]);
+    e.base_kd()[0] = rand_float(lerp_lo(c, GO2SIM_FC_KDR_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_KDR_EASY_LO, ts), r.v[1]);
+  }
   if (c.i[GO2SIM_IC_PER_ENV_GLOBAL_DR]) {   // extension (BASELINE configs[4], not in the reference): the friction / base-mass scalars are drawn per env
     dm_u4 r = pre ? pre->per_env : rng4(seed, RNG_RESET_DR, b, rc, 10);
     if (c.i[GO2SIM_IC_HAS_FRICTION_DR]) {
@@ -5551,6 +5561,48 @@ __global__ __launch_bounds__(WG) void k_env_reset_tail(Pool P, const Model* __re
   if (b >= P.B) return;
   E e(P, b);
   reset_tail(*mp, *cp, *gp, e, b, seed);
+}
+
+// GO2SIM_IC_ENGINE_BATCH_GAIN (PLS off, no kp_factor_range, kp_range set; go2_env_walk.py:797-801): after the resets of a reset call, the engine gains of
+// the 12 motor dofs become float(effective_kp[envs_idx].mean()) and float(effective_kd[envs_idx].mean()) -- set_dofs_kp / set_dofs_kv change the
+// solver's dof table, so the mean is written where every launch form of the dynamics, the solve and the control-force rewards reads kp / kv (the model
+// tables h->dm and h->dms), and kept in Glob for the host.  Launched after the kernels that reset (k_env_post_b_team, k_env_reset_tail), so the new
+// gains drive the physics from the next step on, as in the reference (reset_idx runs after scene.step).
+// Exactness: every effective gain is a float32 in [2^0, 2^7) (configs.flatten_walk_cfg asserts the ranges), hence a multiple of 2^-23, and a batch
+// holds at most 2^23 / 12 envs (asserted too), so the sum of all of them is below 2^30: at most 53 significant bits, exact in float64 whatever the
+// order of the additions.  The quotient by the count is rounded to float64 and then to float32; with 53 >= 2 x 24 + 2 bits that double rounding
+// equals the correctly rounded float32 quotient, so the result is the correctly rounded mean, independent of the grid and of the thread order.
+constexpr int GAIN_WG = 256;
+constexpr int P_B_MAX_GAIN = (1 << 23) / NM;
+__global__ __launch_bounds__(GAIN_WG) void k_env_engine_gains(Pool P, Model* __restrict__ mp, ModelS* __restrict__ msp, const DCfg* __restrict__ cp, Glob* gp) {
+  const DCfg& c = *cp; Glob& g = *gp;
+  if (g.n_reset_now <= 0) return;
+  __shared__ double s_kp[GAIN_WG], s_kd[GAIN_WG];
+  __shared__ int s_n[GAIN_WG];
+  double kp = 0.0, kd = 0.0;
+  int n = 0;
+  for (int b = threadIdx.x; b < P.B; b += GAIN_WG) {
+    E e(P, b);
+    if (!e.reset_buf()[0]) continue;
+    const float bkp = e.base_kp()[0], bkd = e.base_kd()[0];
+    auto kpf = e.kp_factors(); auto kdf = e.kd_factors();
+    for (int k = 0; k < NM; ++k) { kp += (double)(bkp * kpf[k]); kd += (double)(bkd * kdf[k]); }
+    n += 1;
+  }
+  s_kp[threadIdx.x] = kp; s_kd[threadIdx.x] = kd; s_n[threadIdx.x] = n;
+  __syncthreads();
+  for (int w = GAIN_WG / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) { s_kp[threadIdx.x] += s_kp[threadIdx.x + w]; s_kd[threadIdx.x] += s_kd[threadIdx.x + w]; s_n[threadIdx.x] += s_n[threadIdx.x + w]; }
+    __syncthreads();
+  }
+  if (threadIdx.x != 0 || s_n[0] == 0) return;
+  const double cnt = (double)(NM * s_n[0]);
+  const float mkp = (float)(s_kp[0] / cnt), mkd = (float)(s_kd[0] / cnt);
+  g.engine_kp = mkp; g.engine_kd = mkd;
+  for (int k = 0; k < NM; ++k) {
+    const int d = c.i[GO2SIM_IC_MOTOR_DOF0 + k];
+    mp->dofs[d].kp = mkp; mp->dofs[d].kv = mkd; msp->dofs[d].kp = mkp; msp->dofs[d].kv = mkd;
+  }
 }
 
 // Go2Env.step post-physics part B: reset_idx tail + observations (go2_env_walk.py:1080-1141)
@@ -5811,6 +5863,7 @@ __global__ __launch_bounds__(WG) void k_env_init_buffers(Pool P, const DCfg* __r
   E e(P, b);
   auto kpf = e.kp_factors(); auto kdf = e.kd_factors(); auto mst = e.motor_strength();
   for (int k = 0; k < NM; ++k) { kpf[k] = 1.0f; kdf[k] = 1.0f; mst[k] = 1.0f; }
+  e.base_kp()[0] = c.f[GO2SIM_FC_KP]; e.base_kd()[0] = c.f[GO2SIM_FC_KD];
   e.delay_steps()[0] = 1; e.reset_buf()[0] = 1;
   if (c.i[GO2SIM_IC_MANUAL_PD]) for (int k = 0; k < NM; ++k) e.ctrl_mode()[c.i[GO2SIM_IC_MOTOR_DOF0 + k]] = CTRL_FORCE;
 }
@@ -6186,6 +6239,9 @@ static bool step_graph_build(go2sim* h, const float* actions, float* obs, float*
   if (!ok) return false;
   g.a_pb_step = (uint32_t*)sl[6];
   g.a_obs = (float**)sl[7]; g.a_priv = (float**)sl[8]; g.a_rew = (float**)sl[9]; g.a_reset = (uint8_t**)sl[10]; g.a_timeout = (float**)sl[11];
+  if (h->hcfg.i[GO2SIM_IC_ENGINE_BATCH_GAIN] &&
+      !graph_add_kernel(h, last, k_env_engine_gains, dim3(1), dim3(GAIN_WG), nullptr, nullptr, nullptr, h->P, h->dm, h->dms, h->dcfg, h->dglob))
+    return false;
   if (hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0) != hipSuccess) return false;
   g.valid = true;
   return true;
@@ -6355,6 +6411,8 @@ static int field_lookup(int field, int* k, int* is_int, int* off, int* is_aos = 
     case GO2SIM_F_CTRL_POS: kk = ND; oo = FO(ctrl_pos); break;
     case GO2SIM_F_CTRL_VEL: kk = ND; oo = FO(ctrl_vel); break;
     case GO2SIM_F_DOF_POS: kk = ND; oo = FO(dof_pos); break;
+    case GO2SIM_F_BASE_KP: kk = 1; oo = FO(base_kp); break;
+    case GO2SIM_F_BASE_KD: kk = 1; oo = FO(base_kd); break;
     case GO2SIM_I_N_CONTACTS: kk = 1; ii = 1; oo = IO(n_contacts); break;
     case GO2SIM_I_CONTACT_GEOMS: kk = 2 * MAXC; ii = 1; oo = AIO(c_geom); aa = 1; break;
     case GO2SIM_I_N_CONSTRAINTS: kk = 1; ii = 1; oo = IO(n_con); break;
@@ -6510,6 +6568,8 @@ int go2sim_env_configure(go2sim_t* h, const double* f, int nf, const int* i, int
     for (int k = 0; k < 4; ++k) { int l = c.i[GO2SIM_IC_FOOT_LINK0 + k], l2 = c.i[GO2SIM_IC_HIP_LINK0 + k]; if (l < 0 || l >= NL || l2 < 0 || l2 >= NL) return GO2SIM_E_BADARG; }
     if (c.i[GO2SIM_IC_PUSH_LINK] < 0 || c.i[GO2SIM_IC_PUSH_LINK] >= NL || c.i[GO2SIM_IC_BASE_LINK] < 0 || c.i[GO2SIM_IC_BASE_LINK] >= NL) return GO2SIM_E_BADARG;
     for (int k = 0; k < c.i[GO2SIM_IC_N_REWARDS]; ++k) { int id = c.i[GO2SIM_IC_REWARD_ID0 + k]; if (id < 0 || id >= GO2SIM_R_COUNT) return GO2SIM_E_BADARG; }
+    if (c.i[GO2SIM_IC_ENGINE_BATCH_GAIN] && (c.i[GO2SIM_IC_ENV_KIND] != 0 || c.i[GO2SIM_IC_MANUAL_PD] || c.i[GO2SIM_IC_SHARED_GLOBALS] || P_B_MAX_GAIN < h->B))
+      return GO2SIM_E_BADARG;                                             // (one batch gain: not sharded; k_env_engine_gains: exact float64 sum up to 2^23 / 12 envs)
     step_graph_destroy(h);   // the configuration is baked into the kernel arguments of the step graph
     h->hcfg = c;
   }
@@ -6577,6 +6637,7 @@ int go2sim_env_step(go2sim_t* h, const float* actions, float* obs, float* priv, 
     hipLaunchKernelGGL(k_env_post_a, g, dim3(WG * POST_A_WAVES), 0, s, h->P, h->dm, h->hcfg, h->dglob, h->dacc, h->seed, h->step_count);
     if (h->hcfg.i[GO2SIM_IC_USE_TERRAIN]) hipLaunchKernelGGL(k_env_terrain_rows, dim3((h->B + 255) / 256), dim3(256), 0, s, h->P, h->dcfg, h->dglob, h->seed);
     hipLaunchKernelGGL(k_env_post_b_team<16>, dim3((h->B + 3) / 4), dim3(128), 0, s, h->P, h->dm, h->dms, h->dcfg, h->dglob, h->seed, h->step_count, obs, priv, rew, reset, timeout);
+    if (h->hcfg.i[GO2SIM_IC_ENGINE_BATCH_GAIN]) hipLaunchKernelGGL(k_env_engine_gains, dim3(1), dim3(GAIN_WG), 0, s, h->P, h->dm, h->dms, h->dcfg, h->dglob);
   }
   HIPCHK(hipGetLastError());
   h->action_write_idx = (h->action_write_idx + 1) % (h->hcfg.i[GO2SIM_IC_MAX_DELAY] + 1);
@@ -6593,6 +6654,7 @@ int go2sim_env_reset(go2sim_t* h, void* stream) {
   hipLaunchKernelGGL(k_env_globals, dim3(1), dim3(1), 0, s, h->dcfg, h->dglob, h->dacc, h->seed, 0);
   if (h->hcfg.i[GO2SIM_IC_USE_TERRAIN]) hipLaunchKernelGGL(k_env_terrain_rows, dim3((h->B + 255) / 256), dim3(256), 0, s, h->P, h->dcfg, h->dglob, h->seed);
   hipLaunchKernelGGL(k_env_reset_tail, g, b, 0, s, h->P, h->dm, h->dcfg, h->dglob, h->seed);
+  if (h->hcfg.i[GO2SIM_IC_ENGINE_BATCH_GAIN]) hipLaunchKernelGGL(k_env_engine_gains, dim3(1), dim3(GAIN_WG), 0, s, h->P, h->dm, h->dms, h->dcfg, h->dglob);
   launch_fk_team(h, s, 1, &h->dglob->n_reset_now);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;
@@ -6609,6 +6671,7 @@ int go2sim_env_reset_idx(go2sim_t* h, const int* envs_idx, int n_sel, void* stre
   hipLaunchKernelGGL(k_env_globals, dim3(1), dim3(1), 0, s, h->dcfg, h->dglob, h->dacc, h->seed, 0);
   if (h->hcfg.i[GO2SIM_IC_USE_TERRAIN]) hipLaunchKernelGGL(k_env_terrain_rows, dim3((h->B + 255) / 256), dim3(256), 0, s, h->P, h->dcfg, h->dglob, h->seed);
   hipLaunchKernelGGL(k_env_reset_tail, g, b, 0, s, h->P, h->dm, h->dcfg, h->dglob, h->seed);
+  if (h->hcfg.i[GO2SIM_IC_ENGINE_BATCH_GAIN]) hipLaunchKernelGGL(k_env_engine_gains, dim3(1), dim3(GAIN_WG), 0, s, h->P, h->dm, h->dms, h->dcfg, h->dglob);
   launch_fk_team(h, s, 1, &h->dglob->n_reset_now);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;

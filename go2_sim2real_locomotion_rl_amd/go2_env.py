@@ -63,6 +63,12 @@ def _as_device_tensor(ptr, shape, dtype, device):
     return torch.as_tensor(_Mem(), device=device)
 
 
+def is_base_env_cfg(env_cfg, obs_cfg):
+    """True for the cfg dicts of go2_env_base.py (crouch / jump: 12 actions, 45 observations, neither `pls_enable` nor `num_privileged_obs`)."""
+    walk_family = "pls_enable" in env_cfg or obs_cfg.get("num_privileged_obs") is not None
+    return not walk_family and obs_cfg["num_obs"] == 45 and env_cfg["num_actions"] == 12
+
+
 class Go2Env:
     def __init__(self, num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg, show_viewer=False, *, seed=None, device=None,
                  freeze_curriculum=False, log_extras=True, errno_poll_every=5, shared_globals=False):
@@ -84,17 +90,23 @@ class Go2Env:
 
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self._sim = Go2Sim(load_hip_lib(), pack_model(), num_envs, dev_index, _SEED if seed is None else int(seed))
-        # the two env families of the reference: walk (go2_env_walk.py: 16 actions, 49 / 104 obs) and base (go2_env_base.py: 12 / 45)
-        self.is_base_env = self.num_obs == 45 and self.num_actions == 12
+        # the two env families of the reference: walk / stairs (go2_env_walk.py / go2_env_stair.py: 16 actions and 49 / 104 / 182 obs with per-leg
+        # stiffness, 12 and 45 / 100 / 178 without) and base (go2_env_base.py: 12 / 45).  The walk family's train scripts set `pls_enable` and
+        # `num_privileged_obs`, the base env's set neither (go2_train_crouch.py / go2_train_jump.py)
+        self.is_base_env = is_base_env_cfg(env_cfg, obs_cfg)
         if self.is_base_env:
             fcfg, icfg, self._reward_names = flatten_base_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg)
             self.num_privileged_obs = None
         else:
             fcfg, icfg, self._reward_names = flatten_walk_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg,
                                                               freeze_curriculum=freeze_curriculum, shared_globals=shared_globals)
-            if self.num_obs != 49 or self.num_privileged_obs not in (None, 104, 182) or self.num_actions != 16:
+            layouts = {(16, 49): (None, 104, 182)}
+            if not env_cfg.get("pls_enable", False):
+                layouts[(12, 45)] = (None, 100, 178)
+            if self.num_privileged_obs not in layouts.get((self.num_actions, self.num_obs), ()):
                 raise Go2SimError("go2sim implements the walk layout (16 actions, 49 / 104 obs; go2_train_walk.py:300-320), the stair layout "
-                                  "(49 / 182 obs; go2_train_stair.py:282-300) and the base layout (12 actions, 45 obs; go2_train_crouch.py / "
+                                  "(49 / 182 obs; go2_train_stair.py:282-300), both with pls_enable=False (12 actions, 45 / 100 and 45 / 178 obs) "
+                                  "and the base layout (12 actions, 45 obs; go2_train_crouch.py / "
                                   "go2_train_jump.py)")
             terrain_cfg = env_cfg.get("terrain", None)
             if terrain_cfg is not None and terrain_cfg.get("enabled", False):     # go2_env_stair.py:352-433: gs.morphs.Terrain instead of the plane
@@ -105,7 +117,7 @@ class Go2Env:
 
         B, dev = num_envs, self.device
         self.obs_buf = torch.zeros(B, self.num_obs, device=dev)
-        self.privileged_obs_buf = torch.zeros(B, 45 if self.is_base_env else (self.num_privileged_obs or 104), device=dev)
+        self.privileged_obs_buf = torch.zeros(B, 45 if self.is_base_env else (self.num_privileged_obs or self.num_obs + 55), device=dev)
         self.rew_buf = torch.zeros(B, device=dev)
         self.reset_buf = torch.zeros(B, dtype=torch.uint8, device=dev)
         self._time_outs = torch.zeros(B, device=dev)
@@ -134,7 +146,7 @@ class Go2Env:
 
     # ---- reference API -------------------------------------------------------------------------
     def step(self, actions):
-        """go2_env_walk.py:985-1109.  ``actions`` [num_envs, 16] float32 on ``self.device``.
+        """go2_env_walk.py:985-1109.  ``actions`` [num_envs, num_actions] float32 on ``self.device``.
 
         Like the reference (``self.obs_buf = torch.cat(...)``, go2_env_walk.py:1084 / go2_env_base.py:175), every step returns NEW
         observation tensors: rsl_rl's PPO keeps ``transition.observations = obs`` by reference across ``env.step`` and copies it afterwards,
@@ -299,6 +311,21 @@ class Go2Env:
         """Eval scripts overwrite ``env.commands`` (go2_eval_walk.py); here through the setter of the C ABI."""
         v = commands.to(device=self.device, dtype=torch.float32).contiguous()
         self._sim.env_set_commands(v, torch.cuda.current_stream(self.device).cuda_stream)
+
+    @property
+    def base_gains(self):
+        """(kp_val, kd_val) [num_envs] float32 drawn at each env's last reset (pls_enable=False with kp_range; go2_env_walk.py:776-781)."""
+        out = torch.zeros(2, self.num_envs, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._sim.get_field(C["GO2SIM_F_BASE_KP"], out[0], stream)
+        self._sim.get_field(C["GO2SIM_F_BASE_KD"], out[1], stream)
+        return out[0], out[1]
+
+    @property
+    def engine_gains(self):
+        """(kp, kv) the motor dofs' engine PD runs with after the last reset call when the batch gain is on (pls_enable=False, kp_range set, no
+        kp_factor_range: the mean effective gains, go2_env_walk.py:797-801); float32 scalars on the device, no synchronisation."""
+        return self._glob_f32[self._goff["engine_kp"]], self._glob_f32[self._goff["engine_kd"]]
 
     @property
     def curriculum_level(self):

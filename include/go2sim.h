@@ -113,6 +113,8 @@ enum go2sim_field {
   GO2SIM_F_CTRL_POS = 26,     /* f32 k=18  dofs_state.ctrl_pos (control_dofs_position)    */
   GO2SIM_F_CTRL_VEL = 27,     /* f32 k=18  dofs_state.ctrl_vel                          */
   GO2SIM_F_DOF_POS = 28,      /* f32 k=18  dofs_state.pos (qpos - qpos0 per dof; FK output) */
+  GO2SIM_F_BASE_KP = 29,      /* f32 k=1   kp_val of the last reset (go2_env_walk.py:778; PLS off, kp_range set) */
+  GO2SIM_F_BASE_KD = 30,      /* f32 k=1   kd_val of the last reset (:780)                                      */
   /* int32 fields */
   GO2SIM_I_N_CONTACTS = 64,   /* i32 k=1   collider_state.n_contacts                    */
   GO2SIM_I_CONTACT_GEOMS = 65,/* i32 k=300 contact_data.geom_a, geom_b (150 + 150)      */
@@ -215,6 +217,8 @@ enum go2sim_icfg {
   GO2SIM_IC_SHARED_GLOBALS,    /* 1 = this handle is one shard of a larger batch (one process per GPU): the curriculum counters are only
                                   accumulated, and neither the curriculum update nor the "global" DR draws run inside env_step; the host combines the
                                   shards with go2sim_env_sync_counters / _sync_apply / _set_global_dr (distributed.sync_env_globals) */
+  GO2SIM_IC_ENGINE_BATCH_GAIN, /* walk / stair env with PLS off, no kp_factor_range, kp_range set (go2_env_walk.py:797-801): engine PD whose
+                                  motor-dof kp / kv become the mean of the effective gains drawn in each reset call (go2sim_env_globals_t.engine_kp / _kd) */
   GO2SIM_IC_COUNT
 };
 /* reward terms of go2_env_walk.py:1251-1366 */
@@ -287,6 +291,8 @@ typedef struct go2sim_env_globals {
   int   sync_calls;            /* GO2SIM_IC_SHARED_GLOBALS: number of go2sim_env_sync_apply calls (keys the global-DR draws) */
   double shard_counters[5];    /* GO2SIM_IC_SHARED_GLOBALS: this shard's increments since the last go2sim_env_sync_counters:
                                   episodes, time-outs, tracking sum, tracking n (go2_env_walk.py:460-463, 712-715), resets counted for the friction throttle (:744) */
+  float engine_kp, engine_kd;  /* GO2SIM_IC_ENGINE_BATCH_GAIN: the motor-dof gains of the last reset call, float(mean of effective_kp / kd over the reset
+                                  envs) (go2_env_walk.py:797-801); 0 in every other configuration */
 } go2sim_env_globals_t;
 
 typedef struct go2sim go2sim_t;

@@ -22,6 +22,14 @@ global `torch` is replaced by `ScheduledTorch`, which forwards everything except
 four-entry constant schedule of include/go2sim_detmath.h (GO2SIM_RNG_CONST), keyed like the C ABI's Philox stream (the env step for per-step
 draws, the reset-call number inside reset_idx).  The counterpart on the C-ABI side is the diagnostic -DGO2SIM_RNG_CONST build of the oracle and
 of the HIP library (build.ORACLE_VARIANTS / HIP_VARIANTS); the product build is untouched.  These cases keep the reference's shipped ranges.
+
+The `*_nopls*` cases are the same recipes with the train scripts' `pls_enable` switch off (go2_train_walk.py:77, go2_train_stair.py:72): 12 actions,
+45 observations.  `walk_nopls` / `stairs_nopls` keep kp_factor_range (manual PD on per-env base x factor gains, go2_env_walk.py:776-795), `*_engine*`
+drop the factor ranges (engine PD whose motor gains become the mean effective gain of each reset call, :797-801, 1020-1021) and `walk_nopls_static`
+drops kp_range / kd_range too (engine PD on env_cfg kp / kd).  They also record, per step, the gains the env handed to set_dofs_kp / set_dofs_kv
+(`engine_gains`); for the engine cases the script asserts at record time that each of them is the correctly rounded float64 mean of the effective
+gains of the reset envs, which is what the C ABI computes (torch's float32 mean() could differ from it in the last bit).  The oracle's own env layer
+has no PLS-off path: these fixtures are replayed on the HIP library only (tests/test_pls_off_gpu.py).
 """
 import copy
 import importlib.util
@@ -42,9 +50,32 @@ REF_DIR = os.path.join(REF_ROOT, "examples", "locomotion", "final") if REF_ROOT 
 OUT_DIR = os.path.join(ROOT, "tests", "golden")
 
 
+def pls_off(env_cfg, case):
+    """The PLS-off variants of a walk / stair cfg (module docstring): mode A keeps the factor ranges, `_engine` drops them, `_static` drops the gain
+    ranges as well."""
+    if "_engine" in case or "_static" in case:
+        env_cfg.pop("kp_factor_range"); env_cfg.pop("kd_factor_range")
+    if "_static" in case:
+        env_cfg.pop("kp_range"); env_cfg.pop("kd_range")
+    return env_cfg
+
+
 def pinned_cfgs(case):
     """The reference's configuration of the task with every random range collapsed to one value (see the module docstring)."""
     from go2_sim2real_locomotion_rl_amd.configs import get_crouch_cfgs, get_jump_cfgs, get_stair_cfgs, get_walk_cfgs
+
+    if "_nopls" in case:
+        base = case[:case.index("_nopls")]
+        env_cfg, obs_cfg, reward_cfg, command_cfg = pinned_cfgs(base)
+        with_pls = get_stair_cfgs if base == "stairs" else get_walk_cfgs
+        _, obs_off, _, _ = with_pls(pls_enable=False)
+        env_cfg.update({"pls_enable": False, "num_actions": 12})
+        obs_cfg.update({"num_obs": obs_off["num_obs"], "num_privileged_obs": obs_off["num_privileged_obs"]})
+        pls_off(env_cfg, case)
+        if "_engine" in case:       # dyadic gains: every mean of them is exact in float32 too, so torch's mean() is the correctly rounded one
+            env_cfg.update({"kp_range": [56.0, 56.0], "kd_range": [2.0, 2.0]})
+            env_cfg["curriculum"].update({"kp_easy": [56.0, 56.0], "kd_easy": [2.0, 2.0]})
+        return env_cfg, obs_cfg, reward_cfg, command_cfg
 
     if case in ("base_jump", "base_crouch"):
         env_cfg, obs_cfg, reward_cfg, command_cfg = copy.deepcopy(get_jump_cfgs() if case == "base_jump" else get_crouch_cfgs())
@@ -122,8 +153,13 @@ def rng_cfgs(case):
         command_cfg.update({"lin_vel_x_range": [-0.4, 0.8], "lin_vel_y_range": [-0.3, 0.1], "ang_vel_range": [-0.5, 0.25]})   # the shipped ranges are [0, 0]
         env_cfg["resampling_time_s"] = 0.3
         return env_cfg, obs_cfg, reward_cfg, command_cfg
-    env_cfg, obs_cfg, reward_cfg, command_cfg = copy.deepcopy(get_stair_cfgs() if case.startswith("stairs") else get_walk_cfgs())
+    pls = "_nopls" not in case
+    env_cfg, obs_cfg, reward_cfg, command_cfg = copy.deepcopy(get_stair_cfgs(pls) if case.startswith("stairs") else get_walk_cfgs(pls))
     cur = env_cfg["curriculum"]
+    if not pls:
+        pls_off(env_cfg, case)
+    if "_engine" in case:           # the shipped ranges as easy AND hard ranges: the draws stay dyadic (module docstring: the record-time mean check)
+        cur.update({"kp_easy": list(env_cfg["kp_range"]), "kd_easy": list(env_cfg["kd_range"])})
     env_cfg.update({"episode_length_s": 0.9, "resampling_time_s": 0.3, "termination_if_roll_greater_than": 25, "termination_if_pitch_greater_than": 25,
                     "push_interval_s": 0.5, "min_delay_steps": 0, "max_delay_steps": 2})
     cur.update({"update_every_episodes": 6, "global_dr_update_interval": 4, "push_interval_easy_s": 0.6, "mix_prob_current": 0.6, "level_init": 0.30,
@@ -136,6 +172,8 @@ def rng_cfgs(case):
 
 
 RNG_CASES = ["walk_rng", "walk_rng_axis", "stairs_rng", "base_jump_rng"]
+NOPLS_CASES = ["walk_nopls", "walk_nopls_engine", "walk_nopls_static", "stairs_nopls"]
+NOPLS_RNG_CASES = ["walk_nopls_rng", "walk_nopls_engine_rng"]
 
 
 def action_tape(T, B, n_act, seed):
@@ -190,6 +228,7 @@ def run_case(case, B=8, T=96, seed=11, n_run=None, physics="strict"):
     # physics underneath the reference's env code: the strict oracle (reference CPU summation order) or its FAST ORDER build (the arithmetic of the
     # HIP product); the env layer that is being pinned is the same reference code either way
     rng_case = case.endswith("_rng") or "_rng_" in case
+    nopls = "_nopls" in case
     if rng_case:
         from go2_sim2real_locomotion_rl_amd import build
         from go2_sim2real_locomotion_rl_amd.capi import Go2SimLib
@@ -224,8 +263,26 @@ def run_case(case, B=8, T=96, seed=11, n_run=None, physics="strict"):
                 sched.reset_key += 1
 
         env.reset_idx = reset_idx
+    engine = env.robot._scene._gains                                    # the shim's record of the dof gains set through set_dofs_kp / set_dofs_kv
+    motors_l = [int(d) for d in torch.as_tensor(env.motors_dof_idx).tolist()]
+    gain_checks = []
+    if nopls and not getattr(env, "_use_manual_pd", True):
+        inner_kpkd = env._randomize_kp_kd
+
+        def randomize_kp_kd(envs_idx, t_sample):                          # the set_dofs_kp / kv values against the correctly rounded float64 mean
+            inner_kpkd(envs_idx, t_sample)
+            if "kp_range" not in env.env_cfg:
+                return
+            for which, eff in enumerate((env._effective_kp, env._effective_kd)):
+                vals = eff[envs_idx].numpy().astype(np.float64)
+                exact, got = np.float32(vals.sum() / vals.size), np.float32(engine[motors_l[0]][which])
+                assert all(np.float32(engine[d][which]) == got for d in motors_l)
+                assert got == exact, f"{case}: set_dofs_{'kp' if which == 0 else 'kv'}({got!r}) is not the correctly rounded mean {exact!r}"
+                gain_checks.append(int(vals.size))
+
+        env._randomize_kp_kd = randomize_kp_kd
     rows = None
-    if case == "stairs":
+    if case == "stairs" or case == "stairs_nopls":
         rows = np.array([(3 * b + 1) % 13 for b in range(B)], np.int64)
         env._lock_terrain_rows = True
         env._env_terrain_row[:] = torch.from_numpy(rows)
@@ -248,8 +305,12 @@ def run_case(case, B=8, T=96, seed=11, n_run=None, physics="strict"):
     motors = torch.as_tensor(env.motors_dof_idx)
     rec = {k: [] for k in ("obs", "priv", "rew", "rew_terms", "done", "time_outs", "ctrl_pos", "ctrl_force", "base_pos", "commands", "episode_length", "level",
                            "delay_steps", "push_force", "terrain_row")}
+    if nopls:
+        rec["engine_gains"] = []
     has_priv = getattr(env, "num_privileged_obs", None) is not None
     n_run = T if n_run is None else n_run
+    if nopls:
+        engine_at_reset = np.array([[engine[d][0], engine[d][1]] for d in motors_l], np.float32)   # after the constructor's reset()
     for s in range(n_run):
         if sched is not None:
             sched.step_key = s
@@ -267,13 +328,17 @@ def run_case(case, B=8, T=96, seed=11, n_run=None, physics="strict"):
         rec["delay_steps"].append(env._delay_steps.numpy().astype(np.int32).copy() if hasattr(env, "_delay_steps") else np.zeros(B, np.int32))
         rec["push_force"].append(env._current_push_force.numpy().copy() if hasattr(env, "_current_push_force") else np.zeros((B, 3), np.float32))
         rec["terrain_row"].append(env._env_terrain_row.numpy().astype(np.int32).copy() if hasattr(env, "_env_terrain_row") else np.zeros(B, np.int32))
+        if nopls:                                                          # [12 motors, (kp, kv)] after the step (its reset call included)
+            rec["engine_gains"].append(np.array([[engine[d][0], engine[d][1]] for d in motors_l], np.float32))
     out = {k: np.stack(v) if k != "level" else np.asarray(v, np.float64) for k, v in rec.items()}
     out["actions"] = acts[:n_run]
+    if nopls:
+        out["engine_gains_at_reset"] = engine_at_reset
     done, to = out["done"].astype(bool), out["time_outs"] > 0
     meta = {"case": case, "reference_file": f"examples/locomotion/final/{stem}.py", "physics": physics, "n_envs": B, "steps": n_run, "seed": seed, "reward_names": names,
             "n_time_out_resets": int((done & to).sum()), "n_fall_resets": int((done & ~to).sum()),
             "terrain_rows": None if rows is None else rows.tolist(), "rng_calls": None if sched is None else dict(sched.calls),
-            "reset_calls": None if sched is None else sched.reset_key}
+            "reset_calls": None if sched is None else sched.reset_key, "gain_mean_checks": len(gain_checks)}
     out["cfgs_json"] = np.array(cfg_json)
     out["meta_json"] = np.array(json.dumps(meta))
     return out, meta
@@ -286,9 +351,9 @@ def main():
 
     build.build_oracle()
     os.makedirs(OUT_DIR, exist_ok=True)
-    for case in sys.argv[1:] or ["base_jump", "base_crouch", "walk", "walk_delay1", "walk_delay2", "stairs"] + RNG_CASES:
+    for case in sys.argv[1:] or ["base_jump", "base_crouch", "walk", "walk_delay1", "walk_delay2", "stairs"] + RNG_CASES + NOPLS_CASES + NOPLS_RNG_CASES:
         for physics in ("strict", "fast"):
-            out, meta = run_case(case, B=16 if case in RNG_CASES else 8, physics=physics)
+            out, meta = run_case(case, B=16 if case in RNG_CASES + NOPLS_RNG_CASES else 8, physics=physics)
             path = fixture_path(case, physics)
             np.savez_compressed(path, **out)
             print(f"{path}: {meta['n_time_out_resets']} time-out resets, {meta['n_fall_resets']} fall resets, {os.path.getsize(path) // 1024} KiB"
