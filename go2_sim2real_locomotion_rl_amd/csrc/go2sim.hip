@@ -396,6 +396,7 @@ struct LinkS {
 struct GeomS { int type, link; V3 pos; Q4 quat; };
 struct JLim { int q_start, dof_start; float lo, hi; };   // revolute joints; q_start = -1 for the others (add_joint_limit_constraints, solver.py:1088-1143)
 constexpr int NTRI = ND * (ND + 1) / 2;
+constexpr int LEG_K = 4, LEG_D = 3;   // leg form: four serial chains of three one-dof links hanging from a free-joint root (a quadruped)
 struct alignas(16) ModelS {
   int n_levels, iterations, ls_iterations, arrow_mode;
   float substep_dt; V3 gravity; float eps, tolerance, ls_tolerance, meaninertia;
@@ -407,10 +408,56 @@ struct alignas(16) ModelS {
   Joint joints[NJ]; Dof dofs[ND]; GeomS geoms[NG]; Entity entities[2];
   float qpos0[NQ]; unsigned mass_mask_bits[ND];
   int level_start[NL + 1], level_links[NL], child_start[NL + 1], child_list[NL], dof_link[ND];
+  // leg form of the tree (build_leg_form): links of leg l at leg_links[LEG_D * l + 0 .. LEG_D - 1], root -> leaf, legs in the child_list order of
+  // the root; leg_form = 0 when the tree does not have that shape.  (Bytes: the table fills the tail of the last 16-byte granule.)
+  unsigned char leg_links[LEG_K * LEG_D], leg_root, leg_form;
 };
 constexpr int SOLVER_BLOCK_BYTES = (int)(sizeof(LinkS) * NL + 2 * (NTRI + 1) + sizeof(JLim) * NJ);
 static_assert(sizeof(ModelS) % 16 == 0 && (2 * (NTRI + 1)) % 4 == 0 && offsetof(ModelS, links) % 16 == 0 && offsetof(ModelS, jlim) == offsetof(ModelS, links) + sizeof(LinkS) * NL + 2 * (NTRI + 1), "ModelS is copied in 16-byte granules");
 
+// The leg form: one root link with a single free joint, from which LEG_K serial chains of LEG_D links hang, every chain link with one revolute
+// joint of one dof; any other root is a fixed link without joints or children (the ground).  The kinematics and dynamics walk such a tree one lane
+// per leg in registers (tk_kinematics / tk_dynamics) instead of level by level through LDS.  GO2SIM_NO_LEG_FORM=1 (read when the model is built):
+// diagnostic switch, keeps the level walk under test.
+static bool build_leg_form(const Model& m, ModelS& o) {
+  if (getenv("GO2SIM_NO_LEG_FORM") && atoi(getenv("GO2SIM_NO_LEG_FORM")) != 0) return false;
+  if (NL > 255) return false;
+  auto n_children = [&](int i) { return m.child_start[i + 1] - m.child_start[i]; };
+  auto one_revolute = [&](const Link& L) {
+    if (L.joint_end - L.joint_start != 1) return false;
+    const Joint& J = m.joints[L.joint_start];
+    return J.type == JOINT_REVOLUTE && J.dof_end - J.dof_start == 1 && L.dof_start == J.dof_start && L.dof_end == J.dof_end &&
+           L.q_end - L.q_start == 1 && J.q_start == L.q_start;
+  };
+  int root = -1, n_links = 0;
+  for (int i = 0; i < NL; ++i) {
+    const Link& L = m.links[i];
+    if (L.parent != -1) continue;
+    const bool free_root = !L.is_fixed && L.joint_end - L.joint_start == 1 && m.joints[L.joint_start].type == JOINT_FREE && L.n_dofs == 6;
+    if (free_root) {
+      if (root >= 0) return false;
+      root = i;
+    } else if (!(L.is_fixed && L.joint_end == L.joint_start && L.n_dofs == 0 && n_children(i) == 0)) {
+      return false;
+    } else {
+      n_links++;
+    }
+  }
+  if (root < 0 || n_children(root) != LEG_K) return false;
+  n_links++;
+  for (int l = 0; l < LEG_K; ++l) {
+    int i = m.child_list[m.child_start[root] + l];
+    for (int d = 0; d < LEG_D; ++d) {
+      if (!one_revolute(m.links[i]) || n_children(i) != (d + 1 < LEG_D ? 1 : 0)) return false;
+      o.leg_links[LEG_D * l + d] = (unsigned char)i;
+      n_links++;
+      if (d + 1 < LEG_D) i = m.child_list[m.child_start[i]];
+    }
+  }
+  if (n_links != NL) return false;
+  o.leg_root = (unsigned char)root;
+  return true;
+}
 bool build_model_s(const Model& m, ModelS& o) {
   memset(&o, 0, sizeof(o));
   o.n_levels = m.n_levels; o.iterations = m.iterations; o.ls_iterations = m.ls_iterations; o.arrow_mode = m.arrow_mode;
@@ -445,6 +492,7 @@ bool build_model_s(const Model& m, ModelS& o) {
     o.jlim[i].q_start = rev ? J.q_start : -1; o.jlim[i].dof_start = J.dof_start;
     o.jlim[i].lo = rev ? m.dofs[J.dof_start].limit[0] : 0.0f; o.jlim[i].hi = rev ? m.dofs[J.dof_start].limit[1] : 0.0f;
   }
+  o.leg_form = build_leg_form(m, o) ? 1 : 0;
   return true;
 }
 DEV float mass_mask(const ModelS& m, int i, int j) { return (float)((m.mass_mask_bits[i] >> j) & 1u); }
@@ -452,21 +500,23 @@ DEV void tri_index(const ModelS& m, int idx, int& i, int& j) { i = m.tri_i[idx];
 
 // View used by the team kernels: scalars come from the global copy through uniform (scalar) loads and live in SGPRs, tables point into LDS
 struct ModelView {
-  int n_levels, iterations, ls_iterations, arrow_mode; float substep_dt; V3 gravity; float eps, tolerance, ls_tolerance, meaninertia;
+  int n_levels, iterations, ls_iterations, arrow_mode, leg_form; float substep_dt; V3 gravity; float eps, tolerance, ls_tolerance, meaninertia;
   const LinkS* links; const Joint* joints; const Dof* dofs; const GeomS* geoms; const Entity* entities; const float* qpos0;
   const unsigned* mass_mask_bits; const int *level_start, *level_links, *child_start, *child_list, *dof_link; const unsigned char *tri_i, *tri_j;
+  const unsigned char* leg_links; int leg_root;
   DEV ModelView(const ModelS* t, const ModelS* __restrict__ g)
-      : n_levels(g->n_levels), iterations(g->iterations), ls_iterations(g->ls_iterations), arrow_mode(g->arrow_mode), substep_dt(g->substep_dt), gravity(g->gravity), eps(g->eps),
+      : n_levels(g->n_levels), iterations(g->iterations), ls_iterations(g->ls_iterations), arrow_mode(g->arrow_mode), leg_form(g->leg_form), substep_dt(g->substep_dt), gravity(g->gravity), eps(g->eps),
         tolerance(g->tolerance), ls_tolerance(g->ls_tolerance), meaninertia(g->meaninertia), links(t->links), joints(t->joints), dofs(t->dofs),
         geoms(t->geoms), entities(t->entities), qpos0(t->qpos0), mass_mask_bits(t->mass_mask_bits), level_start(t->level_start),
-        level_links(t->level_links), child_start(t->child_start), child_list(t->child_list), dof_link(t->dof_link), tri_i(t->tri_i), tri_j(t->tri_j) {}
+        level_links(t->level_links), child_start(t->child_start), child_list(t->child_list), dof_link(t->dof_link), tri_i(t->tri_i), tri_j(t->tri_j),
+        leg_links(t->leg_links), leg_root(g->leg_root) {}
   // solver flavour: only the link table and the triangle LUT are staged in LDS; joint / dof constants are read with uniform indices and stay
   // behind scalar loads of the global model
   DEV ModelView(const LinkS* lds_links, const unsigned char* lds_tri_i, const unsigned char* lds_tri_j, const Model* __restrict__ g)
-      : n_levels(g->n_levels), iterations(g->iterations), ls_iterations(g->ls_iterations), arrow_mode(g->arrow_mode), substep_dt(g->substep_dt), gravity(g->gravity), eps(g->eps),
+      : n_levels(g->n_levels), iterations(g->iterations), ls_iterations(g->ls_iterations), arrow_mode(g->arrow_mode), leg_form(0), substep_dt(g->substep_dt), gravity(g->gravity), eps(g->eps),
         tolerance(g->tolerance), ls_tolerance(g->ls_tolerance), meaninertia(g->meaninertia), links(lds_links), joints(g->joints), dofs(g->dofs),
         geoms(nullptr), entities(g->entities), qpos0(g->qpos0), mass_mask_bits(nullptr), level_start(nullptr), level_links(nullptr), child_start(nullptr),
-        child_list(nullptr), dof_link(nullptr), tri_i(lds_tri_i), tri_j(lds_tri_j) {}
+        child_list(nullptr), dof_link(nullptr), tri_i(lds_tri_i), tri_j(lds_tri_j), leg_links(nullptr), leg_root(-1) {}
 };
 DEV float mass_mask(const ModelView& m, int i, int j) { return (float)((m.mass_mask_bits[i] >> j) & 1u); }
 DEV void tri_index(const ModelView& m, int idx, int& i, int& j) { i = m.tri_i[idx]; j = m.tri_j[idx]; }
@@ -742,7 +792,8 @@ enum { SI_LS_IT = 0, SI_LS_RESULT, SI_IMPROVED };
 
 // ---------------------------------------------------------------------------------------------
 // Team kinematics / dynamics: T lanes per environment, link tree processed level by level
-// (Go2: base | 4 hips | 4 thighs | 4 calves), independent links / dofs / matrix entries spread over the lanes, every
+// (Go2: base | 4 hips | 4 thighs | 4 calves; in the leg form -- build_leg_form, teams of 32 / 64 -- one lane per leg walks its chain in
+// registers instead), independent links / dofs / matrix entries spread over the lanes, every
 // chained sum evaluated in the serial order of the reference.
 // ---------------------------------------------------------------------------------------------
 DEV V3 ld3(const float* p, int i) { return v3(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
@@ -993,7 +1044,69 @@ template <int T, class MT>
 DEV void tk_kinematics(const MT& m, const E& e, KinData* s, int tl, bool force_update_fixed, DynData* dk = nullptr) {
   // s->l_pos / s->l_quat hold the current link poses (tk_stage_links, issued with the kernel's other staging loads)
   PH_BEGIN                                                             // (profiling builds: 18 = link poses by level, 19 = COM / inertia / cdof / geoms, 55 = velocities by level)
-  for (int lev = 0; lev < m.n_levels; ++lev) {
+  const bool legs = (T == 32 || T == 64) && m.leg_form;
+  if (legs) {
+    // leg form: every lane evaluates the root pose (redundantly: the same operations, no LDS round trip), lane l < LEG_K then walks leg l root -> leaf
+    // in registers.  The joint-local terms (dp, the local rotation) do not depend on the parent: they are formed before the walk, side by side on
+    // LEG_K * LEG_D lanes.  Per link the operations and their order are those of the level walk below.
+    const int r = m.leg_root;
+    const int rq = m.joints[m.links[r].joint_start].q_start;
+    const V3 rpos = v3(s->qpos[rq], s->qpos[rq + 1], s->qpos[rq + 2]);
+    Q4 rquat = q4(s->qpos[rq + 3], s->qpos[rq + 4], s->qpos[rq + 5], s->qpos[rq + 6]);
+    const float rn = dm_sqrt(norm_sqr(rquat));
+    rquat = q4(rquat.w / rn, rquat.x / rn, rquat.y / rn, rquat.z / rn);
+    if (tl == 0) {
+      const auto& L = m.links[r];
+      const int i_j = L.joint_start, ds = m.joints[i_j].dof_start;
+      st3(s->xanchor, i_j, rpos);
+      st3(s->xaxis, i_j, v3(0, 0, 1));
+      gstore(e, FO(dof_pos), ds + 0, rpos.x); gstore(e, FO(dof_pos), ds + 1, rpos.y); gstore(e, FO(dof_pos), ds + 2, rpos.z);
+      if (dk) { dk->out[ds] = rpos.x; dk->out[ds + 1] = rpos.y; dk->out[ds + 2] = rpos.z; }
+      st3(s->l_pos, r, rpos); st4(s->l_quat, r, rquat); e.l_pos()[r] = rpos; e.l_quat()[r] = rquat;
+    }
+    // the joint-local rotations, one lane per chain link (lane LEG_D * l + d: link d of leg l), handed to the leg lanes by a cross-lane read
+    Q4 ql = q4(0, 0, 0, 0);
+    if (tl < LEG_K * LEG_D) {
+      const Joint& J = m.joints[m.links[m.leg_links[tl]].joint_start];
+      const float dp = s->qpos[J.q_start] - m.qpos0[J.q_start];
+      gstore(e, FO(dof_pos), J.dof_start, dp);
+      if (dk) dk->out[J.dof_start] = dp;
+      ql = rotvec_to_quat(m.dofs[J.dof_start].motion_ang * dp, m.eps);
+    }
+    Q4 qloc[LEG_D];
+#pragma unroll
+    for (int d = 0; d < LEG_D; ++d) {
+      const int src = tl < LEG_K ? LEG_D * tl + d : 0;
+      qloc[d] = q4(__shfl(ql.w, src, T), __shfl(ql.x, src, T), __shfl(ql.y, src, T), __shfl(ql.z, src, T));
+    }
+    if (tl < LEG_K) {
+      int lk[LEG_D], jk[LEG_D];
+      V3 lpos[LEG_D], jpos[LEG_D], axis[LEG_D]; Q4 lquat[LEG_D];
+#pragma unroll
+      for (int d = 0; d < LEG_D; ++d) {
+        lk[d] = m.leg_links[LEG_D * tl + d];
+        const auto& L = m.links[lk[d]];
+        jk[d] = L.joint_start;
+        const Joint& J = m.joints[jk[d]];
+        lpos[d] = L.pos; lquat[d] = L.quat; jpos[d] = J.pos; axis[d] = m.dofs[J.dof_start].motion_ang;
+      }
+      V3 pos = rpos; Q4 quat = rquat;
+#pragma unroll
+      for (int d = 0; d < LEG_D; ++d) {
+        const Q4 pq = quat;
+        pos = pos + transform_by_quat(lpos[d], pq);
+        quat = transform_quat_by_quat(lquat[d], pq);
+        const V3 anchor = transform_by_quat(jpos[d], quat) + pos;
+        st3(s->xanchor, jk[d], anchor);
+        st3(s->xaxis, jk[d], transform_by_quat(axis[d], quat));
+        quat = transform_quat_by_quat(qloc[d], quat);
+        pos = anchor - transform_by_quat(jpos[d], quat);
+        st3(s->l_pos, lk[d], pos); st4(s->l_quat, lk[d], quat); e.l_pos()[lk[d]] = pos; e.l_quat()[lk[d]] = quat;
+      }
+    }
+    team_sync();
+  }
+  for (int lev = 0; lev < (legs ? 0 : m.n_levels); ++lev) {
     for (int k = m.level_start[lev] + tl; k < m.level_start[lev + 1]; k += T) {
       int i_l = m.level_links[k];
       const auto& L = m.links[i_l];
@@ -1114,7 +1227,64 @@ DEV void tk_kinematics(const MT& m, const E& e, KinData* s, int tl, bool force_u
   team_sync();
   PH(19)
   // forward velocity
-  for (int lev = 0; lev < m.n_levels; ++lev) {
+  if (legs) {
+    // leg form: the root's velocity on every lane (redundantly), then lane l < LEG_K carries it down leg l in registers; the other roots (fixed,
+    // without joints) are at rest
+    const int r = m.leg_root, ds = m.links[r].dof_start;
+    float v[6]; V3 ca[6], cv[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) { v[i] = s->vel[ds + i]; ca[i] = ld3(s->cdof_ang, ds + i); cv[i] = ld3(s->cdof_vel, ds + i); }
+    V3 cvel_vel = v3(0, 0, 0), cvel_ang = v3(0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { cvel_vel = cvel_vel + cv[i] * v[i]; cvel_ang = cvel_ang + ca[i] * v[i]; }
+    if (tl == 0) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        if (!dk) { e.cdofd_ang()[ds + i] = v3(0, 0, 0); e.cdofd_vel()[ds + i] = v3(0, 0, 0); }
+        if (dk) { st3(dk->cdofd_ang, ds + i, v3(0, 0, 0)); st3(dk->cdofd_vel, ds + i, v3(0, 0, 0)); }
+        V3 oa, ov;
+        motion_cross_motion(cvel_ang, cvel_vel, ca[i + 3], cv[i + 3], oa, ov);
+        if (!dk) { e.cdofd_ang()[ds + i + 3] = oa; e.cdofd_vel()[ds + i + 3] = ov; }
+        if (dk) { st3(dk->cdofd_ang, ds + i + 3, oa); st3(dk->cdofd_vel, ds + i + 3, ov); }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { cvel_vel = cvel_vel + cv[i + 3] * v[i + 3]; cvel_ang = cvel_ang + ca[i + 3] * v[i + 3]; }
+    if (tl == 0) {
+      st3(s->cd_vel, r, cvel_vel); st3(s->cd_ang, r, cvel_ang);
+      if (!dk) { e.cd_vel()[r] = cvel_vel; e.cd_ang()[r] = cvel_ang; }
+      if (dk) { st3(dk->cd_vel, r, cvel_vel); st3(dk->cd_ang, r, cvel_ang); }
+    }
+    for (int i_l = tl; i_l < NL; i_l += T) {
+      if (m.links[i_l].parent != -1 || i_l == r) continue;
+      st3(s->cd_vel, i_l, v3(0, 0, 0)); st3(s->cd_ang, i_l, v3(0, 0, 0));
+      if (!dk) { e.cd_vel()[i_l] = v3(0, 0, 0); e.cd_ang()[i_l] = v3(0, 0, 0); }
+      if (dk) { st3(dk->cd_vel, i_l, v3(0, 0, 0)); st3(dk->cd_ang, i_l, v3(0, 0, 0)); }
+    }
+    if (tl < LEG_K) {
+      int lk[LEG_D], dd[LEG_D]; float lv[LEG_D]; V3 la[LEG_D], lc[LEG_D];
+#pragma unroll
+      for (int d = 0; d < LEG_D; ++d) {
+        lk[d] = m.leg_links[LEG_D * tl + d];
+        dd[d] = m.links[lk[d]].dof_start;
+        lv[d] = s->vel[dd[d]]; la[d] = ld3(s->cdof_ang, dd[d]); lc[d] = ld3(s->cdof_vel, dd[d]);
+      }
+#pragma unroll
+      for (int d = 0; d < LEG_D; ++d) {
+        V3 oa, ov;
+        motion_cross_motion(cvel_ang, cvel_vel, la[d], lc[d], oa, ov);
+        if (!dk) { e.cdofd_ang()[dd[d]] = oa; e.cdofd_vel()[dd[d]] = ov; }
+        if (dk) { st3(dk->cdofd_ang, dd[d], oa); st3(dk->cdofd_vel, dd[d], ov); }
+        cvel_vel = cvel_vel + lc[d] * lv[d];
+        cvel_ang = cvel_ang + la[d] * lv[d];
+        st3(s->cd_vel, lk[d], cvel_vel); st3(s->cd_ang, lk[d], cvel_ang);
+        if (!dk) { e.cd_vel()[lk[d]] = cvel_vel; e.cd_ang()[lk[d]] = cvel_ang; }
+        if (dk) { st3(dk->cd_vel, lk[d], cvel_vel); st3(dk->cd_ang, lk[d], cvel_ang); }
+      }
+    }
+    team_sync();
+  }
+  for (int lev = 0; lev < (legs ? 0 : m.n_levels); ++lev) {
     for (int k = m.level_start[lev] + tl; k < m.level_start[lev + 1]; k += T) {
       int i_l = m.level_links[k];
       const auto& L = m.links[i_l];
@@ -1270,8 +1440,32 @@ __global__ __launch_bounds__(64) void k_fk_team(Pool P, const ModelS* __restrict
 template <int T, class MT>
 DEV void tk_dynamics(const MT& m, const E& e, DynData* s, int tl, bool env_valid) {
   PH_BEGIN
+  const bool legs = (T == 32 || T == 64) && m.leg_form;
   // ---- composite rigid bodies, leaf -> root ----
-  for (int lev = m.n_levels - 2; lev >= 0; --lev) {
+  if (legs) {
+    // leg form: lane c < 13 owns component c of every link; per leg the one-child sums leaf -> root in registers, then the root's LEG_K-child sum in
+    // child_list order (the legs' order) -- the additions of the level walk below, in its order
+    for (int c = tl; c < 13; c += T) {
+      auto at = [&](int i_l) -> float* { return (c < 9) ? &s->crb_I[9 * i_l + c] : ((c < 12) ? &s->crb_pos[3 * i_l + c - 9] : &s->crb_mass[i_l]); };
+      const int r = m.leg_root;
+      float x[LEG_K][LEG_D];
+#pragma unroll
+      for (int l = 0; l < LEG_K; ++l)
+#pragma unroll
+        for (int d = 0; d < LEG_D; ++d) x[l][d] = *at(m.leg_links[LEG_D * l + d]);
+      float a = *at(r);
+#pragma unroll
+      for (int l = 0; l < LEG_K; ++l) {
+#pragma unroll
+        for (int d = LEG_D - 2; d >= 0; --d) { x[l][d] = x[l][d] + x[l][d + 1]; *at(m.leg_links[LEG_D * l + d]) = x[l][d]; }
+      }
+#pragma unroll
+      for (int l = 0; l < LEG_K; ++l) a = a + x[l][0];
+      *at(r) = a;
+    }
+    team_sync();
+  }
+  for (int lev = (legs ? -1 : m.n_levels - 2); lev >= 0; --lev) {
     int n_par = m.level_start[lev + 1] - m.level_start[lev];
     for (int w = tl; w < n_par * 13; w += T) {
       int i_p = m.level_links[m.level_start[lev] + w / 13], comp = w % 13;
@@ -1399,7 +1593,40 @@ DEV void tk_dynamics(const MT& m, const E& e, DynData* s, int tl, bool env_valid
     s->qf_passive[i_d] = qp;
   }
   // ---- bias forces: accelerations root -> leaf ----
-  for (int lev = 0; lev < m.n_levels; ++lev) {
+  if (legs) {
+    // leg form: lane (l, c) = (tl / 6, tl % 6) < (LEG_K, 6) carries component c (vel xyz, ang xyz: the sums are component-wise) from the root down
+    // leg l; the lanes of leg 0 write the root, the first lanes the other roots (fixed, without dofs)
+    const int r = m.leg_root;
+    if (tl < 6 * LEG_K) {
+      const int l = tl / 6, c = tl % 6;
+      const float* src = (c < 3) ? s->cdofd_vel : s->cdofd_ang;
+      const int cc = (c < 3) ? c : c - 3;
+      const V3 g0 = -m.gravity * (1.0f - 0.0f);                       // (formed before the component is picked: no dynamic index into m)
+      const int ds = m.links[r].dof_start;
+      float vr[6], xr[6], vl[LEG_D], xl[LEG_D]; int lk[LEG_D];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) { vr[i] = s->vel[ds + i]; xr[i] = src[3 * (ds + i) + cc]; }
+#pragma unroll
+      for (int d = 0; d < LEG_D; ++d) {
+        lk[d] = m.leg_links[LEG_D * l + d];
+        const int i_d = m.links[lk[d]].dof_start;
+        vl[d] = s->vel[i_d]; xl[d] = src[3 * i_d + cc];
+      }
+      float* dst = (c < 3) ? s->cdd_vel : s->cdd_ang;
+      float a = (c < 3) ? ((cc == 0) ? g0.x : ((cc == 1) ? g0.y : g0.z)) : 0.0f;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) a = a + xr[i] * vr[i];
+      if (l == 0) dst[3 * r + cc] = a;
+#pragma unroll
+      for (int d = 0; d < LEG_D; ++d) { a = a + xl[d] * vl[d]; dst[3 * lk[d] + cc] = a; }
+    }
+    for (int i_l = tl; i_l < NL; i_l += T) {
+      if (m.links[i_l].parent != -1 || i_l == r) continue;
+      st3(s->cdd_vel, i_l, -m.gravity * (1.0f - 0.0f)); st3(s->cdd_ang, i_l, v3(0, 0, 0));
+    }
+    team_sync();
+  }
+  for (int lev = 0; lev < (legs ? 0 : m.n_levels); ++lev) {
     for (int k = m.level_start[lev] + tl; k < m.level_start[lev + 1]; k += T) {
       int i_l = m.level_links[k];
       const auto& L = m.links[i_l];
@@ -1429,7 +1656,29 @@ DEV void tk_dynamics(const MT& m, const E& e, DynData* s, int tl, bool env_valid
     st3(s->cfrc_ang, i_l, f1_ang + f3_ang + ext_ang + v3(0, 0, 0));
   }
   team_sync();
-  for (int lev = m.n_levels - 2; lev >= 0; --lev) {
+  if (legs) {
+    // leg form: lane c < 6 owns component c of every link, as for the composite rigid bodies above
+    for (int c = tl; c < 6; c += T) {
+      auto at = [&](int i_l) -> float* { return (c < 3) ? &s->cfrc_vel[3 * i_l + c] : &s->cfrc_ang[3 * i_l + c - 3]; };
+      const int r = m.leg_root;
+      float x[LEG_K][LEG_D];
+#pragma unroll
+      for (int l = 0; l < LEG_K; ++l)
+#pragma unroll
+        for (int d = 0; d < LEG_D; ++d) x[l][d] = *at(m.leg_links[LEG_D * l + d]);
+      float a = *at(r);
+#pragma unroll
+      for (int l = 0; l < LEG_K; ++l) {
+#pragma unroll
+        for (int d = LEG_D - 2; d >= 0; --d) { x[l][d] = x[l][d] + x[l][d + 1]; *at(m.leg_links[LEG_D * l + d]) = x[l][d]; }
+      }
+#pragma unroll
+      for (int l = 0; l < LEG_K; ++l) a = a + x[l][0];
+      *at(r) = a;
+    }
+    team_sync();
+  }
+  for (int lev = (legs ? -1 : m.n_levels - 2); lev >= 0; --lev) {
     int n_par = m.level_start[lev + 1] - m.level_start[lev];
     for (int w = tl; w < n_par * 6; w += T) {
       int i_p = m.level_links[m.level_start[lev] + w / 6], comp = w % 6;

@@ -1,0 +1,38 @@
+"""The leg form of the team kinematics / dynamics (csrc/go2sim.hip build_leg_form: one lane per leg walks hip -> thigh -> calf in registers) against
+the level-by-level walk it replaces, selected with GO2SIM_NO_LEG_FORM=1 (read when the model is built).  Both must give the same bits: the leg form
+changes where values wait, not the arithmetic."""
+import numpy as np
+import pytest
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("task", ["walk", "stairs"])
+@pytest.mark.parametrize("knob", [{}, {"GO2SIM_DYN_TEAM": "64", "GO2SIM_FK_TEAM": "64"}, {"GO2SIM_FK_TEAM": "32"}])
+def test_leg_form_env_step_bits(hip_lib, blob, task, knob, monkeypatch):
+    from go2_sim2real_locomotion_rl_amd.configs import get_stair_cfgs, get_walk_cfgs
+    from util import GpuEnv, bits_equal, make_actions
+
+    n_envs, steps = 128, 20
+    for k, v in knob.items():
+        monkeypatch.setenv(k, v)
+    env_l = GpuEnv(hip_lib, blob, n_envs, seed=5, task=task)                 # leg form (the default)
+    monkeypatch.setenv("GO2SIM_NO_LEG_FORM", "1")
+    env_w = GpuEnv(hip_lib, blob, n_envs, seed=5, task=task)                 # level walk
+    monkeypatch.delenv("GO2SIM_NO_LEG_FORM")
+    env_l.reset(); env_w.reset()
+    cfg = (get_stair_cfgs if task == "stairs" else get_walk_cfgs)()[0]
+    max_ep = int(np.ceil(cfg["episode_length_s"] / 0.02))
+    ep = env_w.torch.from_numpy((max_ep - 15 + np.arange(n_envs) % 16).astype(np.int32)).to(env_w.dev)   # staggered time-outs: the in-step reset FK
+    env_l.sim.env_set_episode_length(ep); env_w.sim.env_set_episode_length(ep)
+    acts = make_actions(steps, n_envs, seed=5, kind="mixed", n_act=env_w.n_act)
+    resets = 0
+    for s, a in enumerate(acts):
+        out_l, out_w = env_l.step(a), env_w.step(a)
+        bad = [n for n, x, y in zip(("obs", "priv", "rew", "reset", "timeout"), out_l, out_w) if not bits_equal(x, y)]
+        assert not bad, f"{task} {knob} step {s}: {bad} differ between the leg form and the level walk"
+        resets += int(out_w[3].sum())
+    for name in ("F_QPOS", "F_VEL", "F_ACC", "F_EFC_FORCE", "F_LINK_POS", "F_LINK_QUAT", "F_LINK_CDVEL", "F_LINK_CDANG",
+                 "F_DOF_POS", "F_MASS_MAT", "F_FORCE", "F_ACC_SMOOTH", "I_N_CONTACTS"):
+        assert bits_equal(env_l.field(name), env_w.field(name)), f"{task} {knob}: {name} after {steps} steps"
+    assert resets >= n_envs // 2, "the run went through the reset path"
+    assert env_l.sim.check_errno() == 0 and env_w.sim.check_errno() == 0
