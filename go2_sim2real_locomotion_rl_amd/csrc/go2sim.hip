@@ -37,7 +37,7 @@ namespace {
 constexpr int NL = GO2SIM_NL, ND = GO2SIM_ND, NQ = GO2SIM_NQ, NG = GO2SIM_NG, NJ = GO2SIM_NJ;
 constexpr int NPAIR = GO2SIM_NPAIR_MAX, MAXC = GO2SIM_MAX_CONTACTS, MAXB = GO2SIM_MAX_BROAD, MAXR = GO2SIM_MAX_ROWS;
 constexpr int JOINT_FIXED = 0, JOINT_REVOLUTE = 1, JOINT_FREE = 4;
-constexpr int GEOM_SPHERE = 1, GEOM_CYLINDER = 3, GEOM_BOX = 5, GEOM_TERRAIN = 7;
+constexpr int GEOM_PLANE = 0, GEOM_SPHERE = 1, GEOM_CYLINDER = 3, GEOM_BOX = 5, GEOM_TERRAIN = 7;   // GEOM_PLANE: geom 0 only (with_plane_ground)
 constexpr int TERRAIN_CB = 4;   // vertices per side of a block of the coarse maximum map of the heightfield
 constexpr int CTRL_FORCE = 0, CTRL_VELOCITY = 1, CTRL_POSITION = 2;
 constexpr int NA = 16, NM = 12, NOBS_MAX = 64, NPRIV_MAX = 192, NREW = 32;
@@ -334,6 +334,10 @@ bool parse_model(const void* blob, size_t nbytes, Model& m) {
   }
   for (int i = 0; i < NJ; ++i, p += 5) { Joint& j = m.joints[i]; j.type = p[0]; j.link = p[1]; j.q_start = p[2]; j.dof_start = p[3]; j.dof_end = p[4]; }
   for (int i = 0; i < NG; ++i, p += 3) { m.geoms[i].type = p[0]; m.geoms[i].link = p[1]; m.geoms[i].is_convex = p[2]; }
+  for (int i = 0; i < NG; ++i) {                  // the collider's geom types; a plane (with_plane_ground) can only be the ground, geom 0
+    const int t = m.geoms[i].type;
+    if (!(t == GEOM_SPHERE || t == GEOM_CYLINDER || t == GEOM_BOX || (t == GEOM_PLANE && i == 0))) return false;
+  }
   for (int i = 0; i < 2; ++i, p += 6) {
     Entity& e = m.entities[i];
     e.link_start = p[0]; e.link_end = p[1]; e.dof_start = p[2]; e.dof_end = p[3]; e.geom_start = p[4]; e.geom_end = p[5];
@@ -1932,11 +1936,12 @@ DEV V3 support_driver(const Model& m, V3 direction, int i_g, const GeomLite& gl,
     V3 v_ = v3((d_box.x < 0.0f ? -1.0f : 1.0f) * gl.d0 * 0.5f, (d_box.y < 0.0f ? -1.0f : 1.0f) * gl.d1 * 0.5f,
                (d_box.z < 0.0f ? -1.0f : 1.0f) * gl.d2 * 0.5f);
     return rot_apply(rot, v_) + pos;
-  } else {
+  } else if (gl.type == GEOM_CYLINDER) {
     V3 d_mesh = rot_apply_inv(rot, direction);
     V3 v_ = support_cylinder_local(m, m.geoms[i_g], d_mesh);
     return rot_apply(rot, v_) + pos;
   }
+  return pos;   // a plane has no support point: its pairs never reach MPR or GJK (plane_contact, plane_box_contact_staged)
 }
 struct Pair { int i_ga, i_gb; V3 pos_a; Q4 quat_a; V3 pos_b; Q4 quat_b; const V3* prism; GeomLite ga, gb; Rot ra, rb; };   // ra / rb = make_rot(quat_a / quat_b)
 DEV void pair_set_rots(Pair& pr) { pr.ra = make_rot(pr.quat_a); pr.rb = make_rot(pr.quat_b); }
@@ -1962,13 +1967,15 @@ DEV V3 gjk_support_driver(const Model& m, V3 direction, int i_g, const GeomLite&
                (d_box.z < 0.0f ? -1.0f : 1.0f) * gl.d2 * 0.5f);
     vid = (v_.x > 0.0f) * 1 + (v_.y > 0.0f) * 2 + (v_.z > 0.0f) * 4 + 64 * i_g;
     return rot_apply(rot, v_) + pos;
-  } else {
+  } else if (gl.type == GEOM_CYLINDER) {
     V3 d_mesh = rot_apply_inv(rot, direction);
     int k = 0;
     V3 v_ = support_cylinder_local(m, m.geoms[i_g], d_mesh, &k);
     vid = k + 64 * i_g;
     return rot_apply(rot, v_) + pos;
   }
+  vid = -1;     // a plane never reaches GJK / EPA (see support_driver)
+  return pos;
 }
 #include "go2sim_gjk_dev.h"   // device-side safe GJK + EPA (templated on the polytope store: LDS slot or full-capacity global record)
 
@@ -2196,6 +2203,7 @@ DEV void mpr_contact(const Model& m, const Pair& pr, V3 normal_ws, bool& is_col,
 // func_compute_tolerance, contact.py:264-283
 DEV float compute_tolerance(const Model& m, int i_ga, int i_gb, float tolerance) {
   float size_b = norm(m.geoms[i_gb].aabb[7] - m.geoms[i_gb].aabb[0]);
+  if (m.geoms[i_ga].type == GEOM_PLANE) return 0.5f * tolerance * size_b;   // the plane's (finite) box does not count
   float size_a = norm(m.geoms[i_ga].aabb[7] - m.geoms[i_ga].aabb[0]);
   return 0.5f * tolerance * fmn(size_a, size_b);
 }
@@ -2203,7 +2211,7 @@ DEV float compute_tolerance(const Model& m, int i_ga, int i_gb, float tolerance)
 DEV void contact_orthogonals(const Model& m, const E& e, int i_ga, int i_gb, V3 normal, V3& axis_0, V3& axis_1) {
   V3 size_ga = m.geoms[i_ga].aabb[7], size_gb = m.geoms[i_gb].aabb[7];
   float volume_ga = size_ga.x * size_ga.y * size_ga.z, volume_gb = size_gb.x * size_gb.y * size_gb.z;
-  int i_g = (volume_ga < volume_gb) ? i_ga : i_gb;
+  int i_g = (volume_ga < volume_gb && m.geoms[i_ga].type != GEOM_PLANE) ? i_ga : i_gb;   // against a plane, b is the reference geometry
   int i_l = m.geoms[i_g].link;
   M3 rot = quat_to_R(e.i_quat()[i_l], m.eps);
   int axis_idx = 0; float axis_angle_max = 0.0f;
@@ -2226,6 +2234,16 @@ DEV void rotate_frame(V3 pos, Q4 quat, V3 contact_pos, Q4 qrot, V3& new_pos, Q4&
   new_pos = pos - vec;
 }
 
+// The plane branch of func_convex_convex_contact (narrowphase.py:659-678): geom a is the plane (data[0:3] = its normal in the geom frame), b a
+// sphere or cylinder; one support point of b along the inward normal, no MPR and no GJK.  Runs for detection 0 and for every perturbed detection.
+DEV void plane_contact(const Model& m, const Pair& pr, bool& is_col, V3& normal, float& penetration, V3& pos) {
+  const V3 plane_dir = transform_by_quat(v3(pr.ga.d0, pr.ga.d1, pr.ga.d2), pr.quat_a);
+  normal = -normalized(plane_dir);
+  const V3 v1 = support_driver(m, normal, pr.i_gb, pr.gb, pr.pos_b, pr.rb);
+  penetration = dot(normal, v1 - pr.pos_a);
+  pos = v1 - 0.5f * penetration * normal;
+  is_col = penetration > 0.0f;
+}
 // ---------------------------------------------------------------------------------------------
 // Team collision detection: T lanes per environment.
 //   * AABBs: one lane per geom.
@@ -2274,6 +2292,35 @@ DEV void stage_contact(ContactStage& cs, V3 normal, V3 pos, float pen) {
   cs.n++;
 }
 
+// func_plane_box_contact, box_contact.py:25-93 (func_narrow_phase_convex_specializations): the deepest corner of the box, then its corners in vertex
+// order while the pair has fewer than n_contacts_per_pair contacts; a corner is kept if it penetrates and lies more than `tolerance` from the first
+// contact.  The box's vertices are its init-AABB corners (same order: x slowest, z fastest).  No perturbation, no cache.
+DEV void plane_box_contact_staged(const Model& m, const E& e, int i_ga, int i_gb, ContactStage& cs) {
+  const V3 ga_pos = e.g_pos()[i_ga], gb_pos = e.g_pos()[i_gb];
+  const Q4 ga_quat = e.g_quat()[i_ga], gb_quat = e.g_quat()[i_gb];
+  const Geom& A = m.geoms[i_ga]; const Geom& Bg = m.geoms[i_gb];
+  const V3 normal = -normalized(transform_by_quat(v3(A.data[0], A.data[1], A.data[2]), ga_quat));
+  const V3 d_box = inv_transform_by_quat(normal, gb_quat);                            // _func_support_box, support_field.py:286-306
+  const V3 v_ = v3((d_box.x < 0.0f ? -1.0f : 1.0f) * Bg.data[0] * 0.5f, (d_box.y < 0.0f ? -1.0f : 1.0f) * Bg.data[1] * 0.5f,
+                   (d_box.z < 0.0f ? -1.0f : 1.0f) * Bg.data[2] * 0.5f);
+  const V3 v1 = transform_by_trans_quat(v_, gb_pos, gb_quat);
+  const float pen0 = dot(normal, v1 - ga_pos);
+  if (!(pen0 > 0.0f)) return;
+  const V3 contact_pos_0 = v1 - 0.5f * pen0 * normal;
+  stage_contact(cs, normal, contact_pos_0, pen0);
+  const float tolerance = compute_tolerance(m, i_ga, i_gb, m.mc_tolerance);
+  const int n_max = imn(m.n_contacts_per_pair, 5);                                    // 5 = the staging slots of a lane
+  for (int c = 0; c < 8; ++c) {
+    if (cs.n >= n_max) break;
+    const V3 corner = transform_by_trans_quat(Bg.aabb[c], gb_pos, gb_quat);
+    const float pen = dot(normal, corner - ga_pos);
+    if (pen > 0.0f) {
+      const V3 cpos = corner - 0.5f * pen * normal;
+      if (norm(cpos - contact_pos_0) > tolerance) stage_contact(cs, normal, cpos, pen);
+    }
+  }
+}
+
 // func_convex_convex_contact (CCD_ALGORITHM_CODE.MPR branch), narrowphase.py:514-961; contacts go to the lane's staging buffer.
 // The function is cut in three so that the GJK / EPA fallback of the unperturbed detection -- the one the landing robots need -- can be answered
 // by the whole team between the pieces (k_collide_team, T = 16):  cc_detect0 = pair set-up + MPR (+ cold retry) + "prefer GJK" decision;
@@ -2317,6 +2364,11 @@ DEV void cc_detect0(const Model& m, const E& e, int i_ga, int i_gb, unsigned* nc
   pair_set_rots(pr);
   c.is_col = false; c.penetration = 0.0f; c.normal = v3(0, 0, 0); c.contact_pos = v3(0, 0, 0);
   c.i_pair = (i_ga > i_gb) ? m.pair_idx[i_gb][i_ga] : m.pair_idx[i_ga][i_gb];
+  if (c.type_a == GEOM_PLANE) {                                  // plane pairs never vote for GJK / EPA
+    plane_contact(m, pr, c.is_col, c.normal, c.penetration, c.contact_pos);
+    c.want_gjk = false;
+    return;
+  }
   bool guess_available;
   cc_mpr_with_retry(m, c, 0, ncv, e.normal_cache(), guess_available);
   c.want_gjk = cc_prefer_gjk(m, c, guess_available);
@@ -2358,9 +2410,13 @@ DEV void cc_rest(const Model& m, const E& e, CcState& c, ContactStage& cs, GjkSt
       rotate_frame(c.ga_pos_o, c.ga_quat_o, contact_pos_0, qrot, pr.pos_a, pr.quat_a);
       rotate_frame(c.gb_pos_o, c.gb_quat_o, contact_pos_0, inv_quat(qrot), pr.pos_b, pr.quat_b);
       pair_set_rots(pr);
-      bool guess_available;
-      cc_mpr_with_retry(m, c, i_detection, ncv, normal_cache, guess_available);
-      if (cc_prefer_gjk(m, c, guess_available)) cc_gjk_lane(m, e, c, gjk_slots, gjk_slot_mask, gjk_full);
+      if (c.type_a == GEOM_PLANE) {
+        plane_contact(m, pr, is_col, normal, penetration, contact_pos);
+      } else {
+        bool guess_available;
+        cc_mpr_with_retry(m, c, i_detection, ncv, normal_cache, guess_available);
+        if (cc_prefer_gjk(m, c, guess_available)) cc_gjk_lane(m, e, c, gjk_slots, gjk_slot_mask, gjk_full);
+      }
     }
     if (i_detection == 0) {
       is_col_0 = is_col; normal_0 = normal; contact_pos_0 = contact_pos;
@@ -2679,17 +2735,45 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
   //      pair, ordered compaction; the terrain pass appends after all convex-convex contacts, as the two reference kernels do ----
   int nc_run = 0;
   const int n_np_iter = (n_broad + T - 1) / T;
+  // the staged contacts of a round of T pairs go to the list in pair order (func_add_contact, contact.py:165-199)
+  auto append_staged = [&](const ContactStage& cs, int i_ga, int i_gb) {
+    s->cnt[tl] = cs.n;
+    team_sync();
+    int off = 0, tot = 0;
+    for (int l = 0; l < T; ++l) { int c = s->cnt[l]; off += (l < tl) ? c : 0; tot += c; }
+    for (int k = 0; k < cs.n; ++k) {
+      int i_c = nc_run + off + k;
+      if (i_c < m.max_contact_pairs) {
+        const float* p = cs.st + 7 * k;
+        float friction_a = e.geom_friction()[i_ga] * e.friction_ratio()[i_ga];
+        float friction_b = e.geom_friction()[i_gb] * e.friction_ratio()[i_gb];
+        e.c_geom()[i_c] = i_ga; e.c_geom()[MAXC + i_c] = i_gb;
+        e.c_normal()[i_c] = v3(p[0], p[1], p[2]); e.c_pos()[i_c] = v3(p[3], p[4], p[5]); e.c_pen()[i_c] = p[6];
+        e.c_friction()[i_c] = fmx(fmx(friction_a, friction_b), 1e-2f);
+        auto sol = e.c_sol()[i_c];
+        for (int q = 0; q < 7; ++q) sol[q] = 0.5f * (m.geoms[i_ga].sol_params[q] + m.geoms[i_gb].sol_params[q]);
+        e.c_link()[i_c] = m.geoms[i_ga].link; e.c_link()[MAXC + i_c] = m.geoms[i_gb].link;
+      } else {
+        atomicOr(&e.err()[0], GO2SIM_ERR_OVERFLOW_COLLISION_PAIRS);
+      }
+    }
+    nc_run += tot;
+    team_sync();
+  };
+  bool any_plane_box = false;                                          // team-uniform: a plane-box pair is in the broad-phase list
   for (int it = 0; it < n_np_iter; ++it) {
     int ip = it * T + tl;
     ContactStage cs; cs.st = &s->stage[tl][0][0]; cs.n = 0;
     int i_ga = 0, i_gb = 0;
-    bool convex_pair = false;
+    bool convex_pair = false, plane_box = false;
     if (ip < n_broad) {
       int pk = s->pair_sorted[ip];
       i_ga = pk & 0xff; i_gb = pk >> 8;
       if (m.geoms[i_ga].type > m.geoms[i_gb].type) { int t = i_ga; i_ga = i_gb; i_gb = t; }
-      convex_pair = m.geoms[i_gb].type != GEOM_TERRAIN;
+      plane_box = m.geoms[i_ga].type == GEOM_PLANE && m.geoms[i_gb].type == GEOM_BOX;   // skipped here (narrowphase.py:1040), own pass below
+      convex_pair = m.geoms[i_gb].type != GEOM_TERRAIN && !plane_box;
     }
+    any_plane_box |= team_ballot<T>(plane_box) != 0ull;
 #ifndef GO2SIM_GJK_SERIAL
     if constexpr (T == 16) {
       // MPR of every pair on its own lane; then the pairs whose MPR answer has to be replaced by safe GJK + EPA (narrowphase.py:727-845) are
@@ -2738,28 +2822,23 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
     } else
 #endif
     if (convex_pair) convex_convex_contact_staged(m, e, i_ga, i_gb, cs, s->gjk, &s->gjk_slot_mask, &gjk_scratch[(size_t)b * T + tl], s->ncv);
-    s->cnt[tl] = cs.n;
-    team_sync();
-    int off = 0, tot = 0;
-    for (int l = 0; l < T; ++l) { int c = s->cnt[l]; off += (l < tl) ? c : 0; tot += c; }
-    for (int k = 0; k < cs.n; ++k) {                                   // func_add_contact, contact.py:165-199
-      int i_c = nc_run + off + k;
-      if (i_c < m.max_contact_pairs) {
-        const float* p = cs.st + 7 * k;
-        float friction_a = e.geom_friction()[i_ga] * e.friction_ratio()[i_ga];
-        float friction_b = e.geom_friction()[i_gb] * e.friction_ratio()[i_gb];
-        e.c_geom()[i_c] = i_ga; e.c_geom()[MAXC + i_c] = i_gb;
-        e.c_normal()[i_c] = v3(p[0], p[1], p[2]); e.c_pos()[i_c] = v3(p[3], p[4], p[5]); e.c_pen()[i_c] = p[6];
-        e.c_friction()[i_c] = fmx(fmx(friction_a, friction_b), 1e-2f);
-        auto sol = e.c_sol()[i_c];
-        for (int q = 0; q < 7; ++q) sol[q] = 0.5f * (m.geoms[i_ga].sol_params[q] + m.geoms[i_gb].sol_params[q]);
-        e.c_link()[i_c] = m.geoms[i_ga].link; e.c_link()[MAXC + i_c] = m.geoms[i_gb].link;
-      } else {
-        atomicOr(&e.err()[0], GO2SIM_ERR_OVERFLOW_COLLISION_PAIRS);
+    append_staged(cs, i_ga, i_gb);
+  }
+  // ---- func_narrow_phase_convex_specializations (narrowphase.py:1146-1170; collider.py:486-498): plane-box pairs, after all convex-convex
+  //      contacts and before the terrain pass; one lane per pair, same ordered compaction ----
+  if (any_plane_box) {
+    for (int it = 0; it < n_np_iter; ++it) {
+      int ip = it * T + tl;
+      ContactStage cs; cs.st = &s->stage[tl][0][0]; cs.n = 0;
+      int i_ga = 0, i_gb = 0;
+      if (ip < n_broad) {
+        int pk = s->pair_sorted[ip];
+        i_ga = pk & 0xff; i_gb = pk >> 8;
+        if (m.geoms[i_ga].type > m.geoms[i_gb].type) { int t = i_ga; i_ga = i_gb; i_gb = t; }
+        if (m.geoms[i_ga].type == GEOM_PLANE && m.geoms[i_gb].type == GEOM_BOX) plane_box_contact_staged(m, e, i_ga, i_gb, cs);
       }
+      append_staged(cs, i_ga, i_gb);
     }
-    nc_run += tot;
-    team_sync();
   }
   // ---- func_narrow_phase_any_vs_terrain (narrowphase.py:1197-1244): appended after all convex-convex contacts.  One lane per heightfield
   //      prism: the pairs enumerate the prisms their geom can reach, the MPR queries run T at a time, and the accept / dedupe / cap logic of

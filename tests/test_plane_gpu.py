@@ -1,0 +1,280 @@
+"""The infinite ground plane (gs.morphs.Plane, model_blob.with_plane_ground) on the HIP collider.
+
+1. Contact sets: Go2 on the plane at several hundred seeded poses (feet through the plane, tilted and sunk bases, calves and thighs touching; the default
+   plane and a tilted, shifted one).  Per pose: F_QPOS, forward kinematics, the link poses read back, one substep; the contact list of the substep
+   against tests/plane_ref.py (float64) evaluated on the poses that were read back.  Poses on which some keep / drop decision lies within 1e-4 of its
+   threshold are redrawn (float32 and float64 would be allowed to decide differently there; the tilted plane pairs every geom, so few of its draws
+   survive).  Measured on one MI355X, 293 poses (279 + 14): largest deviation 6.5e-8 m in position, 1.1e-7 in the unit normal and 1.0e-7 m in
+   penetration (bounds 1e-5).
+2. Known answers: the cube of the reference's test_contact_forces (tests/test_rigid_physics.py:1749-1800) on a gs.morphs.Plane, |net contact force -
+   weight| <= 1e-5 after 50 steps; the same cube on a plane tilted by 10 degrees with mu = 1 stays put.
+3. Go2 standing from qpos0 on the plane and on the plane.urdf box agree.
+4. The scheduling knobs of the collision launch are bit-equal to the default build on a plane scene.
+5. The reference's `go2` and `anymal` benchmark bodies (tests/test_rigid_benchmarks.py:316-412) run through `import genesis as gs` on gs.morphs.Plane."""
+import os
+
+import numpy as np
+import pytest
+
+from go2_sim2real_locomotion_rl_amd.capi import Go2Sim
+from go2_sim2real_locomotion_rl_amd.model_blob import MODEL_JSON, load_model_json, pack_model, with_plane_ground
+from plane_ref import PlaneRef
+from util import F, GpuEnv, bits_equal, make_actions
+
+MODEL_DIR = os.path.dirname(MODEL_JSON)
+PLANES = [dict(), dict(pos=(0.3, -0.2, 0.05), normal=(np.sin(0.15), -np.sin(0.1), 1.0))]
+
+
+class Scene:
+    """scene-level handle on the HIP library (numpy in / out)"""
+
+    def __init__(self, lib, model, n_envs, seed=1):
+        import torch
+
+        self.torch, self.dev, self.B = torch, torch.device("cuda:0"), n_envs
+        self.sim = Go2Sim(lib, pack_model(model), n_envs, 0, seed)
+
+    def get(self, name):
+        k, is_int = self.sim.field_size(F(name))
+        t = self.torch.zeros(k, self.B, dtype=self.torch.int32 if is_int else self.torch.float32, device=self.dev)
+        self.sim.get_field(F(name), t)
+        self.torch.cuda.synchronize()
+        return t.cpu().numpy()
+
+    def put(self, name, a):
+        self.sim.set_field(F(name), self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev))
+        self.torch.cuda.synchronize()
+
+
+def draw_qpos(model, rng, B):
+    """Base 0.08-0.4 m above the plane's origin, tilted up to 0.7 rad, any yaw; joints anywhere inside their limits."""
+    q = np.tile(np.asarray(model["qpos0"], np.float64)[:, None], (1, B))
+    q[0:2] = rng.uniform(-0.3, 0.3, (2, B))
+    q[2] = rng.uniform(0.08, 0.4, B)
+    ax = rng.normal(size=(3, B)); ax /= np.linalg.norm(ax, axis=0)
+    ang = rng.uniform(-0.7, 0.7, B) * np.where(rng.random(B) < 0.3, 0.2, 1.0)
+    qt = np.concatenate([np.cos(0.5 * ang)[None], np.sin(0.5 * ang) * ax])
+    yaw = rng.uniform(-np.pi, np.pi, B)
+    qy = np.stack([np.cos(0.5 * yaw), 0 * yaw, 0 * yaw, np.sin(0.5 * yaw)])
+    w1, x1, y1, z1 = qt; w2, x2, y2, z2 = qy
+    q[3:7] = [w1 * w2 - z1 * z2, x1 * w2 + y1 * z2, y1 * w2 - x1 * z2, w1 * z2 + z1 * w2]
+    lim = np.array([d["limit"] for d in model["dofs"]])[6:]
+    q[7:] = lim[:, :1] + (lim[:, 1:] - lim[:, :1]) * rng.random((len(lim), B))
+    return q.astype(np.float32)
+
+
+@pytest.mark.gpu
+def test_contact_sets_against_reference(hip_lib):
+    B, need, margin_min = 256, 200, 1e-4
+    base = load_model_json()
+    stats = dict(pos=0.0, normal=0.0, pen=0.0)
+    accepted = 0
+    for k, kw in enumerate(PLANES):
+        model = with_plane_ground(base, **kw)
+        ref = PlaneRef(model)
+        robot_geoms = [i for i in range(1, len(model["geoms"])) if model["collision_pair_idx"][i] >= 0]   # geoms paired with the ground (row 0)
+        s = Scene(hip_lib, model, B, seed=5 + k)
+        acc_here = 0
+        for rnd in range(8):
+            s.put("F_QPOS", draw_qpos(base, np.random.default_rng(100 * k + rnd), B))
+            s.put("F_VEL", np.zeros((18, B), np.float32))
+            s.sim.reset_caches(None, 0); s.sim.forward_kinematics()
+            lp, lq = s.get("F_LINK_POS").reshape(-1, 3, B), s.get("F_LINK_QUAT").reshape(-1, 4, B)
+            s.sim.substep()
+            nc, cg = s.get("I_N_CONTACTS")[0], s.get("I_CONTACT_GEOMS")
+            cpos, cnor, cpen = s.get("F_CONTACT_POS").reshape(-1, 3, B), s.get("F_CONTACT_NORMAL").reshape(-1, 3, B), s.get("F_CONTACT_PEN")
+            maxc = cpen.shape[0]
+            for b in range(B):
+                want = ref.contacts(lp[:, :, b].astype(np.float64), lq[:, :, b].astype(np.float64), robot_geoms)
+                if ref.margin < margin_min or not want:
+                    continue
+                got = [c for c in range(nc[b]) if cg[c, b] == 0]                      # contacts with the plane, in list order (self-contacts aside)
+                n_self = nc[b] - len(got)
+                assert nc[b] == len(want) + n_self, (k, b, nc[b], len(want), n_self)
+                assert [(int(cg[c, b]), int(cg[maxc + c, b])) for c in got] == [(a, g) for a, g, *_ in want], (k, b)
+                if n_self == 0:
+                    assert got == list(range(len(want)))
+                for c, (_, _, n, p, d) in zip(got, want):
+                    stats["pos"] = max(stats["pos"], np.abs(cpos[c, :, b] - p).max())
+                    stats["normal"] = max(stats["normal"], np.abs(cnor[c, :, b] - n).max())
+                    stats["pen"] = max(stats["pen"], abs(cpen[c, b] - d))
+                acc_here += 1
+        print(f"plane {k}: {acc_here} of {8 * B} drawn poses compared")
+        accepted += acc_here
+        assert s.sim.check_errno() == 0
+    print(f"plane contact sets: {accepted} poses, max deviation pos {stats['pos']:.2e} m, normal {stats['normal']:.2e}, pen {stats['pen']:.2e} m")
+    assert accepted >= need, accepted
+    assert stats["pos"] <= 1e-5 and stats["normal"] <= 1e-5 and stats["pen"] <= 1e-5, stats
+
+
+@pytest.fixture(scope="module")
+def box_lib():
+    from go2_sim2real_locomotion_rl_amd import build
+    from go2_sim2real_locomotion_rl_amd.capi import Go2SimLib
+
+    _, so = build.build_shape_variant("box", hip=True, verbose=False)
+    return Go2SimLib(os.path.abspath(so), "go2sim_")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", ["box", "box01"])
+def test_cube_contact_force_on_plane(box_lib, shape):
+    """test_contact_forces (test_rigid_physics.py:1749-1800): after 50 steps the cube's net contact force is its weight, atol 1e-5."""
+    m = with_plane_ground(load_model_json(os.path.join(MODEL_DIR, f"{shape}_model.json")))
+    B = 8
+    s = Scene(box_lib, m, B)
+    weight = -m["gravity"][2] * m["links"][1]["inertial_mass"]
+    for _ in range(50):
+        s.sim.scene_step(1)
+    f = s.get("F_CONTACT_FORCE").reshape(-1, 3, B)
+    err = np.abs(f[1] - np.array([[0.0], [0.0], [weight]])).max()
+    print(f"{shape} on the plane: |net contact force - weight| = {err:.2e} N (weight {weight:.4e} N), contacts {s.get('I_N_CONTACTS')[0].tolist()}")
+    assert err <= 1e-5, (f[1, :, 0], weight)
+    assert np.array_equal(f[0], -f[1])
+    assert int(s.get("I_N_CONTACTS").min()) == 4, "the four bottom corners"
+    assert s.sim.check_errno() == 0
+
+
+@pytest.mark.gpu
+def test_cube_on_tilted_plane_sticks(box_lib):
+    th = np.deg2rad(10.0)
+    m = with_plane_ground(load_model_json(os.path.join(MODEL_DIR, "box_model.json")), normal=(np.sin(th), 0.0, np.cos(th)))
+    B = 4
+    s = Scene(box_lib, m, B)
+    s.sim.set_friction(1.0)
+    a = 0.5 * m["geoms"][1]["data"][2]
+    q = np.zeros((7, B), np.float32)
+    q[0:3] = (np.array([np.sin(th), 0.0, np.cos(th)]) * (a + 1e-4))[:, None]     # resting on the plane through the origin, turned with it
+    q[3], q[5] = np.cos(0.5 * th), np.sin(0.5 * th)
+    s.put("F_QPOS", q); s.put("F_VEL", np.zeros((6, B), np.float32))
+    s.sim.reset_caches(None, 0); s.sim.forward_kinematics()
+    for _ in range(100):
+        s.sim.scene_step(1)
+    p0 = s.get("F_QPOS")[:3].copy()
+    for _ in range(100):
+        s.sim.scene_step(1)
+    v = s.get("F_VEL")
+    drift = np.abs(s.get("F_QPOS")[:3] - p0).max()
+    speed = np.linalg.norm(v[:3], axis=0).max()
+    print(f"cube on a 10 degree plane, mu = 1: speed {speed:.2e} m/s, drift over 1 s {drift:.2e} m")
+    # one MI355X: 8.9e-4 m/s and 8.7e-4 m over the second second -- the slow creep of the soft friction rows, just inside the bound
+    assert speed < 1e-3 and drift < 1e-3
+    assert s.sim.check_errno() == 0
+
+
+STAND = [0.0, 0.0, 0.0, 0.0, 0.8, 0.8, 1.0, 1.0, -1.5, -1.5, -1.5, -1.5]      # the standing pose of the reference's go2 benchmark (:341-345)
+
+
+def stand(lib, model, B=16, steps=200):
+    """qpos0 with the standing joint angles, held by engine PD control (kp 100, kv 10); `steps` scene steps of 2 substeps."""
+    s = Scene(lib, model, B)
+    for d in range(6, 18):
+        s.sim.set_dof_gains(d, 100.0, 10.0, -model["dofs"][d]["force_range"][1], model["dofs"][d]["force_range"][1])
+    q = np.tile(np.asarray(model["qpos0"], np.float32)[:, None], (1, B)); q[7:] = np.asarray(STAND, np.float32)[:, None]
+    ctrl = np.zeros((18, B), np.float32); ctrl[6:] = q[7:]
+    mode = np.zeros((18, B), np.int32); mode[6:] = 2
+    s.put("F_QPOS", q); s.put("F_VEL", np.zeros((18, B), np.float32)); s.put("F_CTRL_POS", ctrl); s.put("I_CTRL_MODE", mode)
+    s.sim.reset_caches(None, 0); s.sim.forward_kinematics()
+    for _ in range(steps):
+        s.sim.scene_step(2)
+    assert s.sim.check_errno() == 0
+    feet = [g["link"] for g in model["geoms"] if g["type"] == 1 and g["link"] > 1]       # the foot spheres (link 1 is the base)
+    return s.get("F_QPOS"), s.get("F_CONTACT_FORCE").reshape(-1, 3, B)[feet]
+
+
+@pytest.mark.gpu
+def test_go2_stands_alike_on_plane_and_box(hip_lib):
+    """Go2 standing from qpos0 (standing joint angles) for 200 scene steps.  Bound: 1e-5 m in base height, 1e-4 rad in joint angle, 1e-3 of the robot's
+    weight per foot -- about a hundred times what one MI355X measured (8.9e-8 m, 1.2e-6 rad, 2.0e-5), room for the run-to-run freedom of MPR's answers.  The two grounds put the same plane under the robot; the
+    box ground is met by MPR (+ perturbed detections) instead of the support point, whose contact points differ by the MPR tolerance."""
+    base = load_model_json()
+    qp, fp = stand(hip_lib, with_plane_ground(base))
+    qb, fb = stand(hip_lib, base)
+    w = -base["gravity"][2] * sum(l["inertial_mass"] for l in base["links"][1:])
+    dh, dq, df = np.abs(qp[2] - qb[2]).max(), np.abs(qp[7:] - qb[7:]).max(), np.abs(fp - fb).max() / w
+    print(f"Go2 standing 200 steps, plane vs plane.urdf: base height {dh:.2e} m, joints {dq:.2e} rad, foot force {df:.2e} x weight; height {qp[2].mean():.4f} m")
+    assert qp[2].min() > 0.2, "standing"
+    assert dh <= 1e-5 and dq <= 1e-4 and df <= 1e-3
+
+
+KNOBS = ["GO2SIM_COLLIDE_TEAM=32", "GO2SIM_COLLIDE_TEAM=64", "GO2SIM_NO_GRAPH=1", "GO2SIM_NO_FUSE=1"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("knob", KNOBS)
+def test_plane_scheduling_knobs_bit_equal(hip_lib, knob, monkeypatch):
+    blob = pack_model(with_plane_ground(load_model_json()))
+    n_envs, steps = 128, 20
+    k, v = knob.split("=")
+    monkeypatch.setenv(k, v)
+    env_k = GpuEnv(hip_lib, blob, n_envs, seed=3)
+    monkeypatch.delenv(k)
+    env_d = GpuEnv(hip_lib, blob, n_envs, seed=3)
+    env_k.reset(); env_d.reset()
+    for s, a in enumerate(make_actions(steps, n_envs, seed=3, kind="mixed", n_act=env_d.n_act)):
+        out_k, out_d = env_k.step(a), env_d.step(a)
+        bad = [n for n, x, y in zip(("obs", "priv", "rew", "reset", "timeout"), out_k, out_d) if not bits_equal(x, y)]
+        assert not bad, f"{knob} step {s}: {bad} differ from the default build"
+    for name in ("F_QPOS", "F_VEL", "F_CONTACT_POS", "F_CONTACT_PEN", "I_N_CONTACTS", "I_CONTACT_GEOMS"):
+        assert bits_equal(env_k.field(name), env_d.field(name)), f"{knob}: {name} after {steps} steps"
+    assert int(env_d.field("I_N_CONTACTS").max()) > 0
+    assert env_k.sim.check_errno() == 0 and env_d.sim.check_errno() == 0
+
+
+def protocol(robot, n_envs=4096, warm=100, ground="plane"):
+    """tests/test_rigid_benchmarks.py `go2` (:316-374) and `anymal` (:378-412) bodies; dt 0.01, one substep (the reference's SimOptions defaults)."""
+    import torch
+
+    import genesis as gs
+
+    gs.init(backend=gs.gpu)
+    scene = gs.Scene(sim_options=gs.options.SimOptions(dt=0.01, substeps=1), rigid_options=gs.options.RigidOptions(dt=0.01), show_viewer=False)
+    scene.add_entity(gs.morphs.Plane() if ground == "plane" else gs.morphs.URDF(file="urdf/plane/plane.urdf", fixed=True))
+    if robot == "go2":
+        robot_e = scene.add_entity(gs.morphs.URDF(file="urdf/go2/urdf/go2.urdf"), vis_mode="collision")
+        scene.build(n_envs=n_envs)
+        ctrl_pos = torch.tensor([0.0, 0.0, 0.0, 0.0, 0.8, 0.8, 1.0, 1.0, -1.5, -1.5, -1.5, -1.5], dtype=gs.tc_float, device=gs.device)
+        robot_e.control_dofs_position(ctrl_pos, dofs_idx_local=slice(6, None))
+        init_qpos = torch.tensor([[0.0, 0.0, 0.42, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.8, 0.8, 1.0, 1.0, -1.5, -1.5, -1.5, -1.5]],
+                                 dtype=gs.tc_float, device=gs.device).repeat((scene.n_envs, 1))
+        lo, hi = robot_e.get_dofs_limit()
+        init_qpos[:, 7:] = lo[6:] + (hi[6:] - lo[6:]) * torch.rand((scene.n_envs, robot_e.n_dofs - 6), dtype=gs.tc_float, device=gs.device)
+        robot_e.set_qpos(init_qpos)
+    else:
+        robot_e = scene.add_entity(gs.morphs.URDF(file="urdf/anymal_c/urdf/anymal_c.urdf", pos=(0, 0, 0.8)))
+        scene.build(n_envs=n_envs)
+        robot_e.set_dofs_kp(1000.0, slice(6, None))
+        robot_e.control_dofs_position(0.0, slice(6, None))
+    for _ in range(warm):                                                # step-counted warm-up
+        scene.step()
+    torch.cuda.synchronize()
+    return scene, robot_e
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("robot", ["go2", "anymal_c"])
+def test_reference_protocol_on_plane(robot):
+    """500 steps after the warm-up: errno 0, finite state, the robots upright.  The go2 body drops every robot from 0.42 m with its joints drawn anywhere
+    inside their limits, and some land on their side or back whatever the ground (one MI355X: 77.42 % upright on the plane, 77.44 % on the plane.urdf
+    box, same torch seed); so the share that stays upright on the plane must match the box's within 1 %, and every ANYmal stays upright."""
+    import torch
+
+    upright = {}
+    for ground in ("plane", "plane_urdf"):
+        torch.manual_seed(0)
+        scene, r = protocol(robot, ground=ground)
+        for _ in range(500):
+            scene.step()
+        torch.cuda.synchronize()
+        assert scene._sim.check_errno() == 0
+        q, quat, h = r.get_dofs_position(), r.get_quat(), r.get_pos()[:, 2]
+        assert torch.isfinite(q).all() and torch.isfinite(quat).all() and torch.isfinite(h).all()
+        up = 1.0 - 2.0 * (quat[:, 1] ** 2 + quat[:, 2] ** 2)             # z component of the base's z axis
+        upright[ground] = ((up > 0.5) & (h > 0.1)).float().mean().item()
+        if ground == "plane":
+            assert scene._model["geoms"][0]["type"] != 0, "the scene's model stays the box ground; the plane goes in at build()"
+        del scene
+    print(f"{robot} protocol, 500 steps: upright on gs.morphs.Plane {upright['plane']:.4f}, on plane.urdf {upright['plane_urdf']:.4f}")
+    assert upright["plane"] >= 0.7 and abs(upright["plane"] - upright["plane_urdf"]) <= 0.01, upright
+    if robot == "anymal_c":
+        assert upright["plane"] == 1.0
