@@ -690,15 +690,11 @@ struct E {
 // completed (s_waitcnt) -- a workgroup-scope release / acquire fence pair around a wave barrier.  No s_barrier: teams of one wavefront reach
 // these points under team-divergent control flow (different Newton / line-search trip counts, early exits), where a hardware barrier would be
 // undefined behaviour.
-#ifdef GO2SIM_TEAM_SYNC_SBARRIER
-DEV void team_sync() { __syncthreads(); }
-#else
 DEV void team_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
-#endif
 DEV float gload(const E& e, int off, int k) { return e.f[(size_t)(off + k) * e.B]; }
 DEV void gstore(const E& e, int off, int k, float v) { e.f[(size_t)(off + k) * e.B] = v; }
 DEV float aload(const E& e, int off, int k) { return e.fa[off + k]; }              // AoS record word
@@ -786,10 +782,6 @@ struct StampScope {
 #endif
 enum { STK_PRE_DYN = 0, STK_COLLIDE, STK_SOLVE, STK_INT_FK_DYN, STK_INT_FK, STK_POST_A, STK_POST_B, STK_OTHER };
 
-// -DGO2SIM_REPEAT_PHASE=k (profiling builds, tools/repeat_probe.py): phase k runs twice; every such phase is idempotent, so the results
-// are unchanged and the time difference prices the phase.  Solver: 0 stage, 1 rows (13 contact rows, 14 joint-limit rows), 3 Hessian +
-// factorisation, 4 Hessian, 5 gradient, 6 line search, 11 commit.  Collision: 30 AABBs, 31 endpoint sort, 32 candidate pairs, 34 GJK / EPA
-// query, 35 MPR query.
 // scalar slots
 enum { SV_COST = 0, SV_PREV_COST, SV_GAUSS, SV_QG0, SV_QG1, SV_QG2, SV_GTOL };
 enum { SI_LS_IT = 0, SI_LS_RESULT, SI_IMPROVED };
@@ -817,9 +809,6 @@ DEV void st9(float* p, int i, const M3& r) {
 // the whole line for 4 or 8 of its bytes and writes it back piecemeal.  Logical block ids are handed out so that the workgroups of one XCD cover one
 // contiguous range of envs (speed only: any placement gives the same results).
 DEV int xcd_block() {
-#ifdef GO2SIM_NO_XCD_REMAP
-  return (int)blockIdx.x;
-#endif
   const int n = (int)gridDim.x, q = n >> 3, r = n & 7, x = (int)blockIdx.x & 7, i = (int)blockIdx.x >> 3;
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
 }
@@ -847,14 +836,9 @@ DEV void lpt_file(int* __restrict__ rec, int cap, int L, int B, int epw_s, int n
 // env of (workgroup, slot) in the solver grid; B (= no env) past the end of the XCD's list
 DEV int lpt_take(const int* __restrict__ rec, int cap, int B, int epw, int slot) {
   const int ident = xcd_block() * epw + slot;
-#ifdef GO2SIM_NO_XCD_REMAP
-  return ident;
-#endif
   if (rec == nullptr) return ident;
   const int n = (int)gridDim.x, q = n >> 3, r = n & 7, x = (int)blockIdx.x & 7;
-  const int start = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q), nblk = q + (x < r ? 1 : 0);
-  (void)start;
-  const int expected = nblk;                                             // blocks of this XCD
+  const int expected = q + (x < r ? 1 : 0);                              // blocks of this XCD
   const int local = (int)blockIdx.x >> 3;
   int total = 0, cls = -1, off = 0;
 #pragma unroll
@@ -881,9 +865,6 @@ struct KinData {
 #ifndef GO2SIM_FAST_ORDER
 #define GO2SIM_FAST_ORDER 1
 #endif
-#ifndef REBUILD_FLIPS
-#define REBUILD_FLIPS 1
-#endif
 template <int CTRL>
 DEV float dpp_perm(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true)); }
 #if GO2SIM_FAST_ORDER
@@ -905,7 +886,6 @@ DEV float dpp_perm(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(
 // the reverse LDL^T of the strict build).  The FAST ORDER oracle mirrors the arithmetic operation for operation (arrow_factor / arrow_solve in
 // oracle/go2sim_cpu.cpp).
 constexpr bool ARROW_SHAPE = (ND == 18);
-constexpr bool ARROW_SOLVER = ARROW_SHAPE && (REBUILD_FLIPS <= 1);    // (rank-1 updates of the Newton factor exist for the row form only)
 DEV float leg_sum4(float x) {                                          // (x_l + x_(l^2)) + (x_(l^1) + x_(l^3)) over the four 8-lane groups of 32 lanes
   const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
   const float p = __uint_as_float(r[0]) + __uint_as_float(r[1]);     // lane ^ 16
@@ -1032,6 +1012,9 @@ struct DynData {
   float M[ND * ND], L[ND * ND];
   int ctrl_mode[ND];
 };
+#if GO2SIM_FAST_ORDER
+static_assert(!ARROW_SHAPE || (offsetof(DynData, Dinv) % 8 == 0 && sizeof(DynData) % 8 == 0), "arrow_solve reads DynData::Dinv with 8-byte LDS loads");
+#endif
 
 template <int T>
 DEV void tk_stage_links(const E& e, KinData* s, int tl) {
@@ -2341,9 +2324,6 @@ DEV void cc_mpr_with_retry(const Model& m, CcState& c, int i_detection, unsigned
     }
     if (!is_mpr_updated) {
       PHD_BEGIN
-#if defined(GO2SIM_REPEAT_PHASE) && GO2SIM_REPEAT_PHASE == 35
-      mpr_contact(m, c.pr, normal_ws, c.is_col, c.normal, c.penetration, c.contact_pos);
-#endif
       mpr_contact(m, c.pr, normal_ws, c.is_col, c.normal, c.penetration, c.contact_pos);
       PHD(36)
       is_mpr_updated = true;
@@ -2381,9 +2361,6 @@ DEV void cc_gjk_lane(const Model& m, const E& e, CcState& c, GjkStoreLds* gjk_sl
   dp.m = &m; dp.i_ga = pr.i_ga; dp.i_gb = pr.i_gb; dp.pos_a = pr.pos_a; dp.quat_a = pr.quat_a; dp.pos_b = pr.pos_b; dp.quat_b = pr.quat_b;   // path, `pr` stays in registers
   dp.ga = pr.ga; dp.gb = pr.gb; dp.ra = pr.ra; dp.rb = pr.rb;
   dp.discrete = c.type_a == GEOM_BOX && c.type_b == GEOM_BOX;     // func_is_discrete_geoms, collider/utils.py:105-126
-#if defined(GO2SIM_REPEAT_PHASE) && GO2SIM_REPEAT_PHASE == 34
-  { const DgResult g0 = gjk_query(dp, gjk_slots, gjk_slot_mask, gjk_full, m.eps); if (g0.penetration == 12345.0f) c.penetration = 0.0f; }
-#endif
   PHD_BEGIN
   const DgResult gr = gjk_query(dp, gjk_slots, gjk_slot_mask, gjk_full, m.eps);
   PHD(34)
@@ -2565,11 +2542,10 @@ DEV bool terrain_prism_contact(const Model& m, const E& e, const TP& t, int i_gb
   return is_col;
 }
 
-// EPW = environments per wavefront: 64 / T fills the wavefront; fewer leave the upper lanes idle (the teams of a wavefront run in lockstep, so a
-// team pays for the longest query loop and for every branch direction of its neighbours)
-template <int T, int EPW = 64 / T>
+template <int T>
 __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __restrict__ mp, GjkStoreFull* __restrict__ gjk_scratch, int* __restrict__ lpt_rec, int lpt_cap, int solver_epw) {
   STAMP(STK_COLLIDE)
+  constexpr int EPW = 64 / T;                                           // environments per wavefront
   __shared__ CollideData<T> lds[EPW];
   const int tl = threadIdx.x % T, slot = threadIdx.x / T;
   const int b = xcd_block() * EPW + slot;
@@ -2594,9 +2570,6 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
     for (int it = 0; it < NPI; ++it) { int pidx = it * T + tl; int v = m.pair_list[pidx < NPAIR ? pidx : NPAIR - 1]; packed_[it] = (pidx < n_pairs) ? v : -1; }
   }
   // ---- kernel_update_geom_aabbs, forward_kinematics.py:1171-1193 (out-of-range lanes redo the last geom: no branch between the loads) ----
-#if defined(GO2SIM_REPEAT_PHASE) && GO2SIM_REPEAT_PHASE == 30
-  for (int rep = 0; rep < 2; ++rep)
-#endif
 #pragma unroll
   for (int g0 = 0; g0 < NG; g0 += T) {
     const int i_g = (g0 + tl < NG) ? g0 + tl : NG - 1;
@@ -2618,10 +2591,6 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
   team_sync();
   PH(30)
   // ---- func_broad_phase, broadphase.py:141-396: endpoint refresh + stable sort ----
-#if defined(GO2SIM_REPEAT_PHASE) && GO2SIM_REPEAT_PHASE == 31
-  for (int rep = 0; rep < 2; ++rep) {
-  team_sync();
-#endif
   for (int i = tl; i < n2; i += T) {
     // first step: endpoints in (link, geom) order: geoms are stored link-major, so buffer slot i/2 holds geom i/2
     int sg = first ? ((i >> 1) | ((i & 1) ? 0x100 : 0)) : s->bp.sig[i];
@@ -2662,17 +2631,11 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
       }
     }
   }
-#if defined(GO2SIM_REPEAT_PHASE) && GO2SIM_REPEAT_PHASE == 31
-  }
-#endif
   if (tl == 0 && first) e.first_time()[0] = 0;
   team_sync();
   PH(31)
   // ---- candidate pairs: every valid geom pair is tested by one lane ----
   int n_cand = 0;
-#if defined(GO2SIM_REPEAT_PHASE) && GO2SIM_REPEAT_PHASE == 32
-  for (int rep = 0; rep < 2; ++rep) { n_cand = 0; team_sync();
-#endif
   // the pair table is fetched for all rounds up front and every LDS operand of a test is read unconditionally, so that the reads of a
   // round are in flight together; only the ballot compaction is sequential
   unsigned cmask = 0; int key_[NPI];
@@ -2714,9 +2677,6 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
       if (cmask & (1u << it)) { if (pos < MAXB) { s->bp.cand_key[pos] = key_[it]; s->bp.cand_pair[pos] = packed_[it]; } pos++; }
     n_cand = tot;
   }
-#if defined(GO2SIM_REPEAT_PHASE) && GO2SIM_REPEAT_PHASE == 32
-  }
-#endif
   // the serial sweep stops appending at max_broad_pairs (broadphase.py:330-338): all candidates are ranked by the sweep key first, the list is
   // clipped afterwards, so the pairs that survive are the ones the sweep reaches first
   if (n_cand > m.max_broad_pairs && tl == 0) atomicOr(&e.err()[0], GO2SIM_ERR_OVERFLOW_CANDIDATE_CONTACTS);
@@ -2774,7 +2734,6 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
       convex_pair = m.geoms[i_gb].type != GEOM_TERRAIN && !plane_box;
     }
     any_plane_box |= team_ballot<T>(plane_box) != 0ull;
-#ifndef GO2SIM_GJK_SERIAL
     if constexpr (T == 16) {
       // MPR of every pair on its own lane; then the pairs whose MPR answer has to be replaced by safe GJK + EPA (narrowphase.py:727-845) are
       // answered by QUADS: the four quads of the team take four flagged pairs at a time (the four feet of a landing robot), the four lanes of a
@@ -2819,9 +2778,7 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
         if (cst.is_col) { cst.normal = v3(o[2], o[3], o[4]); cst.contact_pos = v3(o[5], o[6], o[7]); }
       }
       if (convex_pair) cc_rest(m, e, cst, cs, nullptr, &s->gjk_slot_mask, &gjk_scratch[(size_t)b * T + tl], s->ncv);
-    } else
-#endif
-    if (convex_pair) convex_convex_contact_staged(m, e, i_ga, i_gb, cs, s->gjk, &s->gjk_slot_mask, &gjk_scratch[(size_t)b * T + tl], s->ncv);
+    } else if (convex_pair) convex_convex_contact_staged(m, e, i_ga, i_gb, cs, s->gjk, &s->gjk_slot_mask, &gjk_scratch[(size_t)b * T + tl], s->ncv);
     append_staged(cs, i_ga, i_gb);
   }
   // ---- func_narrow_phase_convex_specializations (narrowphase.py:1146-1170; collider.py:486-498): plane-box pairs, after all convex-convex
@@ -3023,12 +2980,8 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
 // ---------------------------------------------------------------------------------------------
 // ---- exact line search helpers, solver.py:1888-2417 ----
 struct LsPoint { float alpha, cost, grad, hess; };
-#ifndef GO2SIM_BRACKET_INLINE
-#define GO2SIM_BRACKET_ATTR DEVN
-#else
-#define GO2SIM_BRACKET_ATTR DEV
-#endif
-GO2SIM_BRACKET_ATTR int update_bracket(LsPoint& p, const float alphas[3], const float costs[3], const float grads[3], const float hess[3], float& p_next_alpha) {
+// the inlined bracket step of the -DGO2SIM_BRACKET_INLINE build (tests/test_bracket_inline.py); the product calls update_bracket_v below
+DEV int update_bracket(LsPoint& p, const float alphas[3], const float costs[3], const float grads[3], const float hess[3], float& p_next_alpha) {
   int flag = 0;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
@@ -3042,7 +2995,7 @@ GO2SIM_BRACKET_ATTR int update_bracket(LsPoint& p, const float alphas[3], const 
 
 // The out-of-line form of the product: everything travels BY VALUE (arguments and the result in vector registers under the AMDGPU calling convention),
 // so keeping the bracket step out of line no longer costs a round trip through private memory per call (round 3: LsPoint& and four array pointers,
-// 35 memory instructions for 53 vector ones).  -DGO2SIM_BRACKET_BYREF restores the by-reference form for A / B runs.
+// 35 memory instructions for 53 vector ones).
 struct BrOut { float alpha, cost, grad, hess, next_alpha; int flag; };
 DEVN BrOut update_bracket_v(float pa, float pc, float pg, float ph, float a0, float a1, float a2, float c0, float c1, float c2, float g0, float g1, float g2,
                             float h0, float h1, float h2) {
@@ -3156,11 +3109,10 @@ DEV void team_serial_sum(const float (&x)[NQ], const float (&base)[NQ], int tl, 
 //     row of 16 lanes (xor 1, xor 2, mirror in 8, mirror in 16) and one add per pair of rows -- instead of a 16..32-step dependent chain;
 //   * triangular solves: reciprocal diagonal (18 divisions side by side instead of 36 in sequence; the reference's LDL^T path stores D_inv the same
 //     way, forward_dynamics.py:545-687), column-oriented with one lane per row;
-//   * rank-1 Cholesky rotations: 1 / r = r * (1 / tmp) with the division issued beside the square root, c = r * (1 / L_kk), s = v_k * (1 / L_kk) with the
-//     reciprocal diagonal carried from update to update.
+//   * a change of the active set: the Hessian is summed and factorised afresh instead of updating the factor by rank-1 rotations (ts_cholesky_incremental).
 // The FAST ORDER build of the CPU oracle (oracle/go2sim_cpu.cpp with -DGO2SIM_FAST_ORDER) mirrors this arithmetic operation for operation (tolerance 0 in the GPU
 // parity tests); tests/test_fast_order.py bounds fast against strict.
-// (GO2SIM_FAST_ORDER / REBUILD_FLIPS defaults and dpp_perm: defined with the arrow-form helpers above the dynamics)
+// (GO2SIM_FAST_ORDER default and dpp_perm: defined with the arrow-form helpers above the dynamics)
 // butterfly sum over the T lanes of a team (every lane ends with the total); `x` = the lane's own partial sum
 template <int T, int NQ>
 DEV void team_tree_sum(const float (&x)[NQ], float (&total)[NQ]) {
@@ -3182,15 +3134,10 @@ DEV void team_tree_sum(const float (&x)[NQ], float (&total)[NQ]) {
   // team_bcast(a, 0) + team_bcast(a, 16) (IEEE addition commutes), hence the same bits.  Measured: solver 0.1421 -> 0.1370 ms per step in the window.
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
-#ifndef GO2SIM_TREE_SUM_READLANE
     const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a[q]), __float_as_uint(a[q]), false, false);
     const float pair = __uint_as_float(r[0]) + __uint_as_float(r[1]);                       // rows 0 + 1 (lanes 0..31), rows 2 + 3 (lanes 32..63)
     if constexpr (T == 32) total[q] = pair;
     else { const auto h = __builtin_amdgcn_permlane32_swap(__float_as_uint(pair), __float_as_uint(pair), false, false); total[q] = __uint_as_float(h[0]) + __uint_as_float(h[1]); }
-#else
-    if constexpr (T == 32) total[q] = team_bcast<T>(a[q], 0) + team_bcast<T>(a[q], 16);
-    else total[q] = (team_bcast<T>(a[q], 0) + team_bcast<T>(a[q], 16)) + (team_bcast<T>(a[q], 32) + team_bcast<T>(a[q], 48));
-#endif
   }
 }
 template <int T>
@@ -3486,9 +3433,6 @@ DEV bool ts_cholesky_incremental_reg(const MT& m, S* s, int tl, int n_con) {
   float Lr[ND];
 #pragma unroll
   for (int k = 0; k < ND; ++k) Lr[k] = s->H[row * DS + k];
-#if GO2SIM_FAST_ORDER
-  float invL = 1.0f / s->H[row * DS + row];                            // reciprocal of my diagonal element, carried through the updates
-#endif
   // The rows whose activity flipped are found T at a time (lane c tests row c) and collected in a bit mask per team; the teams of a wavefront
   // then walk their own lists in step: pass f updates every team's f-th flipped row at once.  (A common loop over the row index would run the
   // rank-1 update once per flipped row of EITHER team, with the other team masked off.)
@@ -3513,18 +3457,9 @@ DEV bool ts_cholesky_incremental_reg(const MT& m, S* s, int tl, int n_con) {
           const float tmp = Lkk * Lkk + sign * (vk * vk);
           if (tmp < m.eps) { degenerated = true; break; }
           const float r = dm_sqrt(tmp);
-#if GO2SIM_FAST_ORDER
-          const float invLkk = team_bcast<T>(invL, k);
-          const float rinv = r * (1.0f / tmp);                           // the division does not wait for the square root
-          const float cc = r * invLkk;
-          const float cinv = Lkk * rinv;
-          const float sk = vk * invLkk;
-          if (row == k) invL = rinv;
-#else
           const float cc = r / Lkk;
           const float cinv = 1.0f / cc;
           const float sk = vk / Lkk;
-#endif
           if (row == k) Lr[k] = r;
           else if (row > k) {
             const float hik = (Lr[k] + sk * v * sign) * cinv;
@@ -3551,91 +3486,6 @@ DEV bool ts_cholesky_incremental_reg(const MT& m, S* s, int tl, int n_con) {
 // divisions of ALL pairs of the step are one instruction stream, lanes side by side -- then every pair's rotation is handed from its lane k to
 // the rows below it.  Each matrix / vector element sees exactly the operations of the serial algorithm in the same order, so the result is
 // bit-identical; the "degenerated" verdict is the same too (any pair degenerating makes the caller rebuild the factor from scratch).
-#if GO2SIM_FAST_ORDER && defined(GO2SIM_PIPELINE_REG)
-// Register form of the pipeline (-DGO2SIM_PIPELINE_REG, FAST ORDER builds; measured equal to the LDS form below: solver 0.223 vs 0.217 ms per step in the
-// landing window, so the smaller LDS form is the default): lane i keeps row i of the factor and its update-vector elements in registers for the whole call,
-// the time loop is unrolled so that the column of every slot is a compile-time index, and the rotation (c, 1/c, s) of column k travels from lane k by
-// v_readlane -- no LDS round trip and no barrier inside a time step (the LDS form below pays two per step).  Same operations per element, same order.
-template <int T, int FMAX, class S, class MT>
-DEV bool ts_cholesky_incremental_pipelined(const MT& m, S* s, int tl, int n_con) {
-  static_assert(T >= ND && (T == 32 || T == 64), "one lane per row of the factor");
-  bool degenerated = false;
-  const int row = tl < ND ? tl : ND - 1;
-  const bool own = tl < ND;
-  const unsigned urow = own ? (unsigned)row : 0u;                       // "column k lies left of my row" is (unsigned)k < urow (never true for spare lanes)
-  float Lr[ND];
-#pragma unroll
-  for (int k = 0; k < ND; ++k) Lr[k] = s->H[row * DS + k];
-  float Ld = s->H[row * DS + row];                                     // my diagonal element ...
-  float invLd = 1.0f / Ld;                                             // ... and its reciprocal, carried through the updates
-  for (int base = 0; base < n_con && !degenerated; base += T) {
-    const int c_me = base + tl;
-    const bool flip = c_me < n_con && ((s->active[c_me] != 0) != (s->prev_active[c_me] != 0));
-    const unsigned long long bal = __ballot(flip);
-    unsigned long long mask = (T == 64) ? bal : ((bal >> ((threadIdx.x / T) * T)) & ((1ull << (T & 63)) - 1ull));
-    while (mask != 0ull && !degenerated) {                              // batches of up to FMAX flipped rows, in row order
-      float W[FMAX], sg[FMAX]; int nb = 0;                              // update vectors (my element), sign of each update (0 = slot unused)
-#pragma unroll
-      for (int f = 0; f < FMAX; ++f) {
-        W[f] = 0.0f; sg[f] = 0.0f;
-        if (mask != 0ull) {
-          const int c = base + __ffsll((long long)mask) - 1;
-          mask &= mask - 1ull;
-          W[f] = s->J[c * DS + row] * dm_sqrt(s->efc_D[c]);
-          sg[f] = (s->active[c] != 0) ? 1.0f : -1.0f;
-          nb = f + 1;
-        }
-      }
-      const int nb_wave = __builtin_amdgcn_readfirstlane(imx(__shfl(nb, 0), __shfl(nb, T == 64 ? 0 : 32)));   // both teams (nb is team-uniform)
-      PHC(52, 1) PHC(53, nb_wave) PHC(54, ND - 1 + nb_wave)
-#pragma unroll
-      for (int t = 0; t < ND - 1 + FMAX; ++t) {
-        if (t >= ND - 1 + nb_wave) break;
-        // ---- my pair of this step: row f_me at my own column ----
-        const int f_me = t - row;
-        float dv = 0.0f, sg_me = 0.0f;
-#pragma unroll
-        for (int f = 0; f < FMAX; ++f) { dv = (f_me == f) ? W[f] : dv; sg_me = (f_me == f) ? sg[f] : sg_me; }
-        const bool rot = own && sg_me != 0.0f && dm_abs(dv) > m.eps;     // (sg_me == 0: no pair at my column in this step)
-        const float tmp = Ld * Ld + sg_me * (dv * dv);
-        const bool deg = rot && tmp < m.eps;
-        const float r = dm_sqrt(tmp);
-        const float rinv = r * (1.0f / tmp);                             // the division does not wait for the square root
-        const float cc = r * invLd;
-        float cinv = Ld * rinv;
-        const float sk = dv * invLd;
-        cinv = rot ? cinv : 0.0f;                                        // 0 marks "no rotation for this pair" (L_kk / r is never 0)
-        {
-          const unsigned long long dbal = __ballot(deg);
-          const unsigned long long mine = (T == 64) ? dbal : ((dbal >> ((threadIdx.x / T) * T)) & ((1ull << (T & 63)) - 1ull));
-          if (mine != 0ull) { degenerated = true; break; }
-        }
-        if (rot) { Ld = r; invLd = rinv; }
-        // ---- every pair's rotation goes from the lane of its column to the rows below it ----
-#pragma unroll
-        for (int f = 0; f < FMAX; ++f) {
-          const int k = t - f;                                           // compile-time after unrolling
-          if (k < 0 || k > ND - 2) continue;
-          const float c_k = team_bcast<T>(cc, k), ci_k = team_bcast<T>(cinv, k), s_k = team_bcast<T>(sk, k);
-          const bool on = (unsigned)k < urow && sg[f] != 0.0f && ci_k != 0.0f;   // left of my row, slot in use, pair rotates
-          const float hik = (Lr[k] + s_k * W[f] * sg[f]) * ci_k;
-          const float wn = W[f] * c_k - s_k * hik;
-          Lr[k] = on ? hik : Lr[k];
-          W[f] = on ? wn : W[f];
-        }
-      }
-    }
-  }
-  if (!degenerated && own) {                                            // a degenerated factor is rebuilt from scratch by the caller
-#pragma unroll
-    for (int k = 0; k < ND; ++k)
-      if (k < row) { s->H[row * DS + k] = Lr[k]; s->H[k * DS + row] = Lr[k]; }   // (the strict upper triangle mirrors the lower one)
-    s->H[row * DS + row] = Ld;
-  }
-  team_sync();
-  return degenerated;
-}
-#else
 template <int T, int FMAX, class S, class MT>
 DEV bool ts_cholesky_incremental_pipelined(const MT& m, S* s, int tl, int n_con) {
   static_assert(T >= ND && (T == 32 || T == 64), "one lane per row of the factor");
@@ -3644,9 +3494,6 @@ DEV bool ts_cholesky_incremental_pipelined(const MT& m, S* s, int tl, int n_con)
   const bool own = tl < ND;
   const unsigned urow = own ? (unsigned)row : 0u;                       // "column k lies left of my row" is (unsigned)k < urow (never true for spare lanes)
   float Ld = s->H[row * DS + row];                                     // my diagonal element
-#if GO2SIM_FAST_ORDER
-  float invLd = 1.0f / Ld;                                             // ... and its reciprocal, carried through the updates
-#endif
   for (int base = 0; base < n_con && !degenerated; base += T) {
     const int c_me = base + tl;
     const bool flip = c_me < n_con && ((s->active[c_me] != 0) != (s->prev_active[c_me] != 0));
@@ -3681,17 +3528,9 @@ DEV bool ts_cholesky_incremental_pipelined(const MT& m, S* s, int tl, int n_con)
         const float tmp = Ld * Ld + sg_me * (dv * dv);
         const bool deg = rot && tmp < m.eps;
         const float r = dm_sqrt(tmp);
-#if GO2SIM_FAST_ORDER
-        const float rinv = r * (1.0f / tmp);                             // the division does not wait for the square root
-        const float cc = r * invLd;
-        float cinv = Ld * rinv;
-        const float sk = dv * invLd;
-        if (rot) invLd = rinv;
-#else
         const float cc = r / Ld;
         float cinv = 1.0f / cc;
         const float sk = dv / Ld;
-#endif
         cinv = rot ? cinv : 0.0f;                                        // 0 marks "no rotation for this pair" (1 / cc is never 0)
         {
           const unsigned long long dbal = __ballot(deg);
@@ -3731,31 +3570,23 @@ DEV bool ts_cholesky_incremental_pipelined(const MT& m, S* s, int tl, int n_con)
   }
   return degenerated;
 }
-#endif
 template <int T, class S, class MT>
 DEV bool ts_cholesky_incremental(const MT& m, S* s, int tl, int n_con) {
   if constexpr (T >= ND && (T == 32 || T == 64)) {   // (the register / pipelined forms shuffle across teams of 32 or 64 lanes)
 #if GO2SIM_FAST_ORDER
-    // FAST ORDER: an env with REBUILD_FLIPS (default 1: any) or more flipped rows has its Hessian summed and factorised afresh -- the caller's rebuild
-    // path, which the reference takes for a degenerated factor -- instead of one rank-1 pass of the factor per flipped row.  With the block-form
-    // Hessian and the row-form factorisation above the rebuild is the cheaper instruction stream even for a single flipped row (measured, driver
-    // window / default run / stairs, M env-steps/s: never 8.67 / 14.07 / 6.04, >= 4 rows 8.85 / 14.08 / 6.43, >= 2 rows 9.21 / 14.12 / 6.63, always
-    // 9.49 / 14.51 / 6.67), it depends on the env alone, and it does not accumulate the rounding of the rank-1 passes.  (First: the teams that stay
-    // are then alone in the wave-level votes below.)
-    {
-      int n_exact = 0;
-      for (int base = 0; base < n_con; base += T) {
-        const int c = base + tl;
-        n_exact += __popcll(team_ballot<T>(c < n_con && ((s->active[c] != 0) != (s->prev_active[c] != 0))));
-      }
-      if (n_exact >= REBUILD_FLIPS) return true;
-      if (n_exact == 0) return false;                                   // nothing flipped: the factor stands
+    // FAST ORDER: an env with any flipped row has its Hessian summed and factorised afresh -- the caller's rebuild path, which the reference takes for
+    // a degenerated factor -- instead of one rank-1 pass of the factor per flipped row.  With the block-form Hessian and the row-form factorisation
+    // above the rebuild is the cheaper instruction stream even for a single flipped row (measured, driver window / default run / stairs, M env-steps/s:
+    // never 8.67 / 14.07 / 6.04, >= 4 rows 8.85 / 14.08 / 6.43, >= 2 rows 9.21 / 14.12 / 6.63, always 9.49 / 14.51 / 6.67), it depends on the env
+    // alone, and it does not accumulate the rounding of the rank-1 passes.  The rank-1 forms above are the strict build's.
+    int n_exact = 0;
+    for (int base = 0; base < n_con; base += T) {
+      const int c = base + tl;
+      n_exact += __popcll(team_ballot<T>(c < n_con && ((s->active[c] != 0) != (s->prev_active[c] != 0))));
     }
-#if REBUILD_FLIPS <= 1
-    return false;                                                       // (not reached: every change of the active set is a rebuild)
-#endif
-#endif
-#if !defined(GO2SIM_NO_PIPELINED_RANK1) && !(GO2SIM_FAST_ORDER && REBUILD_FLIPS <= 2)   // (REBUILD_FLIPS <= 2: an env that stays has at most one flipped row)
+    if (n_exact >= 1) return true;
+    return false;                                                       // no flipped row: the factor stands
+#else
     // how many rows flipped (the larger count of the teams in this wavefront): one -> the register-resident serial form is the cheaper
     // instruction stream; several -> the pipelined form is 17 + n steps long instead of 18 n
     int n_flip = 0;
@@ -3778,8 +3609,8 @@ DEV bool ts_cholesky_incremental(const MT& m, S* s, int tl, int n_con) {
       if (n_wave <= 6) return ts_cholesky_incremental_pipelined<T, 6>(m, s, tl, n_con);
       return ts_cholesky_incremental_pipelined<T, 8>(m, s, tl, n_con);
     }
-#endif
     return ts_cholesky_incremental_reg<T>(m, s, tl, n_con);
+#endif
   }
   bool degenerated = false;
   for (int c = 0; c < n_con && !degenerated; ++c) {
@@ -3939,13 +3770,8 @@ DEV LsPoint ts_ls_point(const MT& m, S* s, int tl, int n_con, int nseg, const Ls
   return p;
 }
 // func_ls_point_fn_3alphas_opt, solver.py:2080-2209
-#ifdef GO2SIM_LS3_NOINLINE
-#define GO2SIM_LS3_ATTR DEVN
-#else
-#define GO2SIM_LS3_ATTR DEV
-#endif
 template <int T, class S, class MT>
-GO2SIM_LS3_ATTR void ts_ls_point3(const MT& m, S* s, int tl, int n_con, int nseg, const LsRow& rw, const float a[3], float qg0, float qg1, float qg2, float costs[3], float grads[3],
+DEV void ts_ls_point3(const MT& m, S* s, int tl, int n_con, int nseg, const LsRow& rw, const float a[3], float qg0, float qg1, float qg2, float costs[3], float grads[3],
                       float hess[3]) {
   float b0 = qg0 + 0.0f, b1 = qg1 + 0.0f, b2 = qg2 + 0.0f;
   float t[3][3] = {{b0, b1, b2}, {b0, b1, b2}, {b0, b1, b2}};
@@ -4002,12 +3828,6 @@ GO2SIM_LS3_ATTR void ts_ls_point3(const MT& m, S* s, int tl, int n_con, int nseg
   }
 }
 
-#ifdef GO2SIM_BRACKET_DEBUG   // investigation build (tools/repro_bracket): every bracket step of the first 4 envs is logged (40 floats per record)
-constexpr int BRLOG_ENVS = 4, BRLOG_CAP = 8192, BRLOG_W = 40;
-__device__ float g_brlog[BRLOG_ENVS * BRLOG_CAP * BRLOG_W];
-__device__ int g_brcnt[BRLOG_ENVS];
-__device__ int g_brenv_of_wg[65536];
-#endif
 #if defined(GO2SIM_PHASE_PROFILE) && GO2SIM_FAST_ORDER   // where a line search spends its cycles: 50 set-up (mv, jv, coefficients, p0), 51 the 1-D Newton steps (52: their number),
 #define LS_TIMER unsigned long long ls_t0 = __builtin_readcyclecounter();   // 53 the bracket refinement (54: its rounds of three points)
 #define LS_MARK(id) { const unsigned long long ls_n = __builtin_readcyclecounter(); PHC(id, ls_n - ls_t0) ls_t0 = ls_n; }
@@ -4052,10 +3872,7 @@ DEV float ts_linesearch_tail(const MT& m, S* s, int tl, int n_con, int nseg, con
       if (dm_abs(grads[i]) < gtol && (!best_found || costs[i] < best_cost)) { best_alpha = al[i]; best_cost = costs[i]; best_found = true; }
     PHC(54, 1)
     if (best_found) { LS_MARK(53) return best_alpha; }
-#ifdef GO2SIM_BRACKET_DEBUG
-    const LsPoint p1_in = p1, p2_in = p2;
-#endif
-#if !defined(GO2SIM_BRACKET_INLINE) && !defined(GO2SIM_BRACKET_BYREF)
+#ifndef GO2SIM_BRACKET_INLINE
     const BrOut o1 = update_bracket_v(p1.alpha, p1.cost, p1.grad, p1.hess, al[0], al[1], al[2], costs[0], costs[1], costs[2], grads[0], grads[1], grads[2], hess[0], hess[1], hess[2]);
     p1.alpha = o1.alpha; p1.cost = o1.cost; p1.grad = o1.grad; p1.hess = o1.hess; p1_next_alpha = o1.next_alpha;
     const int b1 = o1.flag;
@@ -4064,36 +3881,7 @@ DEV float ts_linesearch_tail(const MT& m, S* s, int tl, int n_con, int nseg, con
     const int b2 = o2.flag;
 #else
     int b1 = update_bracket(p1, al, costs, grads, hess, p1_next_alpha);
-#ifdef GO2SIM_BRACKET_FENCE   // investigation builds (tools/repro_bracket/README.md): value barriers around the inlined bracket step
-    asm volatile("" : "+v"(p1.alpha), "+v"(p1.cost), "+v"(p1.grad), "+v"(p1.hess), "+v"(p1_next_alpha), "+v"(b1));
-#endif
     int b2 = update_bracket(p2, al, costs, grads, hess, p2_next_alpha);
-#ifdef GO2SIM_BRACKET_FENCE
-    asm volatile("" : "+v"(p2.alpha), "+v"(p2.cost), "+v"(p2.grad), "+v"(p2.hess), "+v"(p2_next_alpha), "+v"(b2));
-#endif
-#endif
-#ifdef GO2SIM_BRACKET_DEBUG
-    {
-      const int env = g_brenv_of_wg[blockIdx.x] + (int)(threadIdx.x / T);
-      if (tl == 0 && env < BRLOG_ENVS) {
-        const int k = g_brcnt[env];
-        if (k < BRLOG_CAP) {
-          float* o = &g_brlog[((size_t)env * BRLOG_CAP + k) * BRLOG_W];
-          int q = 0;
-          o[q++] = (float)ls_it; o[q++] = gtol;
-          for (int i = 0; i < 3; ++i) o[q++] = al[i];
-          for (int i = 0; i < 3; ++i) o[q++] = costs[i];
-          for (int i = 0; i < 3; ++i) o[q++] = grads[i];
-          for (int i = 0; i < 3; ++i) o[q++] = hess[i];
-          o[q++] = p1_in.alpha; o[q++] = p1_in.cost; o[q++] = p1_in.grad; o[q++] = p1_in.hess;
-          o[q++] = p2_in.alpha; o[q++] = p2_in.cost; o[q++] = p2_in.grad; o[q++] = p2_in.hess;
-          o[q++] = p1.alpha; o[q++] = p1.cost; o[q++] = p1.grad; o[q++] = p1.hess;
-          o[q++] = p2.alpha; o[q++] = p2.cost; o[q++] = p2.grad; o[q++] = p2.hess;
-          o[q++] = p1_next_alpha; o[q++] = p2_next_alpha; o[q++] = (float)b1; o[q++] = (float)b2;
-          g_brcnt[env] = k + 1;
-        }
-      }
-    }
 #endif
     if (b1 == 0 && b2 == 0) { LS_MARK(53) return al[2]; }
     al[0] = p1_next_alpha; al[1] = p2_next_alpha; al[2] = (p1.alpha + p2.alpha) * 0.5f;
@@ -4280,9 +4068,6 @@ DEV float ts_linesearch(const MT& m, S* s, int tl, int n_con, float gauss) {
 template <int T, class S, class MT>
 DEV int ts_solve(const MT& m, const E& e, S* s, int tl, int nc, int n_con, unsigned lim_mask, int ws_flag) {
   PH_BEGIN
-#ifdef GO2SIM_REPEAT_PHASE      // profiling builds: run one idempotent phase twice, the time difference is that phase's cost
-  for (int rep_stage = 0; rep_stage < (GO2SIM_REPEAT_PHASE == 0 ? 2 : 1); ++rep_stage) {
-#endif
   // ---- stage inputs (branch-free: all loads of the stage are in flight together) ----
   const bool ws = (n_con > 0) && ws_flag;
   team_stage<NTRI, T>(tl, [&](int k) { return aload(e, AO(mass_mat), k); }, [&](int k, float v) { int i, j; tri_index(m, k, i, j); s->M[i * DS + j] = v; s->M[j * DS + i] = v; });   // packed lower triangle
@@ -4296,16 +4081,9 @@ DEV int ts_solve(const MT& m, const E& e, S* s, int tl, int nc, int n_con, unsig
   team_sync();
   if (!ws) team_for<ND, T>(tl, [&](int d) { s->qacc[d] = s->acc_smooth[d]; });
   team_sync();
-#ifdef GO2SIM_REPEAT_PHASE
-  }
-  for (int rep_rows = 0; rep_rows < (GO2SIM_REPEAT_PHASE == 1 ? 2 : 1); ++rep_rows) {
-#endif
   PH(0)
   bool rows_coupled = false;                                           // does a contact row of this lane join two legs? (arrow form of the Newton Hessian)
   // ---- contact rows: one lane per row ----
-#if defined(GO2SIM_REPEAT_PHASE) && GO2SIM_REPEAT_PHASE == 13
-  for (int rep_c = 0; rep_c < 2; ++rep_c)
-#endif
   for (int r = tl; r < 4 * nc; r += T) {
     int i_col = r >> 2, i = r & 3;
     int link_a = e.c_link()[i_col], link_b = e.c_link()[MAXC + i_col];
@@ -4355,9 +4133,6 @@ DEV int ts_solve(const MT& m, const E& e, S* s, int tl, int nc, int n_con, unsig
     rows_coupled = rows_coupled || (legs & (legs - 1u)) != 0u;
   }
   // ---- joint-limit rows: one lane per joint, ordered compaction ----
-#if defined(GO2SIM_REPEAT_PHASE) && GO2SIM_REPEAT_PHASE == 14
-  for (int rep_c = 0; rep_c < 2; ++rep_c)
-#endif
   for (int i_j = tl; i_j < NJ; i_j += T) {
     if (!((lim_mask >> i_j) & 1u)) continue;                           // joints past a limit, found by the kernel prologue
     const Joint& Jt = m.joints[i_j];
@@ -4381,9 +4156,6 @@ DEV int ts_solve(const MT& m, const E& e, S* s, int tl, int nc, int n_con, unsig
     }
   }
   team_sync();
-#ifdef GO2SIM_REPEAT_PHASE
-  }
-#endif
   PH(1)
   // ---- func_solve_init ----
   {
@@ -4413,22 +4185,15 @@ DEV int ts_solve(const MT& m, const E& e, S* s, int tl, int nc, int n_con, unsig
     bool need_full = true;
     [[maybe_unused]] bool arrow = false;                               // which form the factor of this solve has
 #if GO2SIM_FAST_ORDER
-    if constexpr (ARROW_SOLVER && (T == 32 || T == 64)) arrow = m.arrow_mode != 0 && team_ballot<T>(rows_coupled) == 0ull;
+    if constexpr (ARROW_SHAPE && (T == 32 || T == 64)) arrow = m.arrow_mode != 0 && team_ballot<T>(rows_coupled) == 0ull;
 #endif
     for (int it = 0;; ++it) {
       if (need_full) {                       // single call site of the direct Hessian + factorisation (init and degenerate rebuild)
-#if defined(GO2SIM_REPEAT_PHASE) && GO2SIM_REPEAT_PHASE == 3
-        ts_hessian_direct<T>(m, s, tl, n_con);
-        ts_cholesky_factor<T>(m, s, tl);
-#endif
-#if defined(GO2SIM_REPEAT_PHASE) && GO2SIM_REPEAT_PHASE == 4
-        ts_hessian_direct<T>(m, s, tl, n_con);
-#endif
 #if GO2SIM_FAST_ORDER
         if constexpr (T >= 21) { if (it == 0) ts_hessian_direct<T>(m, s, tl, n_con); else ts_hessian_update<T>(m, s, tl, n_con); }
         else ts_hessian_direct<T>(m, s, tl, n_con);
         PH(3)
-        if constexpr (ARROW_SOLVER && (T == 32 || T == 64)) { if (arrow) ts_cholesky_factor_arrow<T>(m, s, tl); else ts_cholesky_factor<T>(m, s, tl); }
+        if constexpr (ARROW_SHAPE && (T == 32 || T == 64)) { if (arrow) ts_cholesky_factor_arrow<T>(m, s, tl); else ts_cholesky_factor<T>(m, s, tl); }
         else ts_cholesky_factor<T>(m, s, tl);
 #else
         ts_hessian_direct<T>(m, s, tl, n_con);
@@ -4437,12 +4202,9 @@ DEV int ts_solve(const MT& m, const E& e, S* s, int tl, int nc, int n_con, unsig
 #endif
         PH(4)
       }
-#if defined(GO2SIM_REPEAT_PHASE) && GO2SIM_REPEAT_PHASE == 5
-      ts_update_gradient<T>(s, tl);
-#endif
 #if GO2SIM_FAST_ORDER
       [[maybe_unused]] float grad_sq_arrow = 0.0f;
-      if constexpr (ARROW_SOLVER && (T == 32 || T == 64)) { if (arrow) grad_sq_arrow = ts_update_gradient_arrow<T>(m, s, tl); else ts_update_gradient<T>(s, tl); }
+      if constexpr (ARROW_SHAPE && (T == 32 || T == 64)) { if (arrow) grad_sq_arrow = ts_update_gradient_arrow<T>(m, s, tl); else ts_update_gradient<T>(s, tl); }
       else ts_update_gradient<T>(s, tl);
 #else
       ts_update_gradient<T>(s, tl);
@@ -4454,7 +4216,7 @@ DEV int ts_solve(const MT& m, const E& e, S* s, int tl, int nc, int n_con, unsig
         if constexpr (T >= 32) {
           const float g = s->grad[tl < ND ? tl : ND - 1];
 #if GO2SIM_FAST_ORDER
-          if (ARROW_SOLVER && (T == 32 || T == 64) && arrow) grad_norm = grad_sq_arrow;
+          if (ARROW_SHAPE && (T == 32 || T == 64) && arrow) grad_norm = grad_sq_arrow;
           else grad_norm = team_tree_sum1<T>(tl < ND ? g * g : 0.0f);
 #else
           const float xq[1] = {tl < ND ? g * g : 0.0f}, zero[1] = {0.0f};
@@ -4473,9 +4235,6 @@ DEV int ts_solve(const MT& m, const E& e, S* s, int tl, int nc, int n_con, unsig
       if (it == m.iterations) break;
       for (int d = tl; d < ND; d += T) s->search[d] = -s->Mgrad[d];
       team_sync();
-#if defined(GO2SIM_REPEAT_PHASE) && GO2SIM_REPEAT_PHASE == 6
-      { float alpha0 = ts_linesearch<T>(m, s, tl, n_con, gauss); if (alpha0 == 12345.0f) s->search[0] = 0.0f; team_sync(); }
-#endif
       float alpha = ts_linesearch<T>(m, s, tl, n_con, gauss);
       PH(6)
       iters++;
@@ -4581,9 +4340,6 @@ DEV void solve_body(const Pool& P, const Model* __restrict__ gm, const ModelS* _
   if (lpt_next && blockIdx.x == 0) for (int i = threadIdx.x; i < 8 * LPT_CLS; i += 64) lpt_next[i] = 0;   // the record of the next collide / solve pair
   const bool env_valid = b < P.B;
   b_out = b; resident_out = false;
-#ifdef GO2SIM_BRACKET_DEBUG
-  if (threadIdx.x == 0) g_brenv_of_wg[blockIdx.x] = b - slot;
-#endif
   E e(P, env_valid ? b : P.B - 1);
   const int nc = e.n_contacts()[0];
   const int ws_flag = e.is_warmstart()[0];
@@ -4602,10 +4358,6 @@ DEV void solve_body(const Pool& P, const Model* __restrict__ gm, const ModelS* _
     resident_out = true;
     int iters = ts_solve<T>(m, e, s, tl, nc, n_con, lim_mask, ws_flag);
     PH(10)                                                               // (resets the timer: the phases of ts_solve are accounted inside it)
-#if defined(GO2SIM_REPEAT_PHASE) && GO2SIM_REPEAT_PHASE == 11
-    ts_commit<T>(m, e, s, tl, nc, n_con, iters);
-    team_sync();
-#endif
     ts_commit<T>(m, e, s, tl, nc, n_con, iters);
     PH(11)
   } else {
@@ -5330,16 +5082,14 @@ DEV float reward_term(const Model& m, const DCfg& c, RewState& rs, int id, const
 // One lane per env; the kernel is a single wave per 64 envs, so its duration is its dependency chain: every input is loaded before the
 // first store (one memory round trip instead of one per reward term) and the per-term episode sums sit in LDS for the dynamic term loop.
 DEV void env_globals_body(const DCfg& c, Glob& g, Acc* acc, uint64_t seed, int count_push);
-// Lane per env; the workgroup is POST_A_WAVES wavefronts over the SAME 64 envs.  Every wave loads the state and forms the shared quantities (base frame
+// Lane per env; the workgroup is POST_A_NWAVES wavefronts over the SAME 64 envs.  Every wave loads the state and forms the shared quantities (base frame
 // velocities, Euler angles, foot contacts, command gates) redundantly; the reward TERMS -- the long serial part: 19 independent functions of that state --
 // are dealt to the waves (term k runs on one wave, its value goes to LDS), and wave 0 then adds them in the reference's order and makes every store.
 // The three terms that touch env state beyond their own value (feet_air_time writes and feet_stance reads _feet_air_time, go2_env_walk.py:1303-1314;
 // forward_progress moves _last_base_pos_x) stay together on wave 0, in order.  Same operations per value and the same sum order: results unchanged.
-#ifndef GO2SIM_POST_A_WAVES
-#define GO2SIM_POST_A_WAVES 4
-#endif
-constexpr int POST_A_WAVES = GO2SIM_POST_A_WAVES;   // (<= 8: the workgroup has to fit one CU at two wavefronts per SIMD)
-__global__ __launch_bounds__(WG * POST_A_WAVES) void k_env_post_a(Pool P, const Model* __restrict__ mp, const DCfg cv, Glob* gp,
+// (Eight wavefronts measured slower: two 215-register wavefronts per SIMD get in each other's way.)
+constexpr int POST_A_NWAVES = 4;
+__global__ __launch_bounds__(WG * POST_A_NWAVES) void k_env_post_a(Pool P, const Model* __restrict__ mp, const DCfg cv, Glob* gp,
                                                    Acc* acc, uint64_t seed, uint32_t step_count) {
   STAMP(STK_POST_A)
   __shared__ float s_es[NREW][WG], s_r[NREW][WG];
@@ -5457,7 +5207,7 @@ __global__ __launch_bounds__(WG * POST_A_WAVES) void k_env_post_a(Pool P, const 
       const int id = id_next; const float scale = scale_next;
       { const int kn = (k + 1 < NREW) ? k + 1 : k; id_next = c.i[GO2SIM_IC_REWARD_ID0 + kn]; scale_next = c.f[GO2SIM_FC_REWARD_SCALE0 + kn]; }   // the table reads of the next term overlap this one
       const bool stateful = id == GO2SIM_R_FEET_AIR_TIME || id == GO2SIM_R_FEET_STANCE || id == GO2SIM_R_FORWARD_PROGRESS;
-      const int owner = stateful ? 0 : (POST_A_WAVES > 4 ? 1 + j % (POST_A_WAVES - 1) : (1 + j) % POST_A_WAVES);
+      const int owner = stateful ? 0 : (1 + j) % POST_A_NWAVES;
       j += stateful ? 0 : 1;
       if (wv == owner) s_r[k][ln] = reward_term(m, c, rs, id, rc, gates) * scale;
     }
@@ -6285,7 +6035,7 @@ struct go2sim {
   GjkStoreFull* gjk_scratch = nullptr;      // full-capacity polytope records of the GJK / EPA fallback (queries that outgrow their LDS slot) and
                                             // prism descriptors of the terrain pass: one block per (env, narrow-phase lane)
   SolverData<MAXR>* solver_ovf = nullptr;   // per-env global scratch for solves that do not fit in LDS (> RL rows)
-  int* lpt = nullptr; int lpt_cap = 0; int lpt_parity = 0; bool use_lpt = true, lpt_flat = false;   // heaviest-first dispatch records of the solver (two, alternating)
+  int* lpt = nullptr; int lpt_cap = 0; int lpt_parity = 0; bool use_lpt = true;   // heaviest-first dispatch records of the solver (two, alternating)
   // One env step = 11 dependent kernel launches (12 with terrain).  Issued one by one they cost the host ~20 us each -- close to the GPU time of
   // the step -- so the sequence is kept as an instantiated hipGraph: per step the three step-dependent kernel nodes get their new arguments
   // (actions pointer, step counter, ring index) and the graph is launched with one call.  GO2SIM_NO_GRAPH=1 (or timing mode) uses plain launches.
@@ -6311,7 +6061,6 @@ struct go2sim {
   int dyn_team = 32;                        // lanes per environment in k_dynamics_team
   int fk_team = 16;                         // lanes per environment in k_integrate_fk_team / k_fk_team
   int collide_team = 16;                    // lanes per environment in k_collide_team
-  int collide_epw = 0;                      // environments per wavefront in k_collide_team<16> (0 = 4, a full wavefront; GO2SIM_COLLIDE_EPW = 1 / 2 leave lanes idle)
   int solver_team = 32;                     // lanes per environment in k_constraint_solve_team
   int terrain_solver_team = 64;             // ... on heightfield terrain (96 LDS rows)
   uint32_t step_count = 0; int action_write_idx = 0;
@@ -6366,16 +6115,11 @@ static void launch_dynamics(go2sim* h, hipStream_t s, const float* actions = nul
   else if (T == 32) hipLaunchKernelGGL(k_dynamics_team<32>, gd, b, 0, s, h->P, h->dms);
   else hipLaunchKernelGGL(k_dynamics_team<64>, gd, b, 0, s, h->P, h->dms);
 }
-static int collide_epw(const go2sim* h) { return (h->collide_team == 16 && h->collide_epw > 0) ? h->collide_epw : 64 / h->collide_team; }
 static int solver_epw(const go2sim* h) { return 64 / (h->hm.terrain_enabled ? h->terrain_solver_team : h->solver_team); }
-// the envs of a solver block must sit in one collision wavefront (their contact counts meet there).  On flat ground (two envs per solver wavefront, one
-// residency round) the sorted order measured 1-3 % SLOWER than the identity order, with single envs as well as with adjacent pairs as the sorted unit
-// (the record lookup delays every workgroup's first loads; there is no second round to win it back): off unless GO2SIM_LPT_FLAT=1
-static bool lpt_enabled(const go2sim* h) {
-  const int epw_c = collide_epw(h), epw_s = solver_epw(h);
-  if (!h->use_lpt || epw_s > epw_c || epw_c % epw_s != 0) return false;
-  return epw_s == 1 || h->lpt_flat;
-}
+// heaviest-first dispatch where a solver wavefront holds one env.  On flat ground (two envs per solver wavefront, one residency round) the sorted order
+// measured 1-3 % SLOWER than the identity order, with single envs as well as with adjacent pairs as the sorted unit (the record lookup delays every
+// workgroup's first loads; there is no second round to win it back)
+static bool lpt_enabled(const go2sim* h) { return h->use_lpt && solver_epw(h) == 1; }
 static size_t lpt_record_ints(const go2sim* h) { return (size_t)8 * LPT_CLS * (1 + h->lpt_cap); }
 // flat ground, 32-lane teams in solver and dynamics: the solve and the kinematics (+ next dynamics) that follow it share a launch (k_solve_integrate_team);
 // GO2SIM_NO_FUSE_SOLVE=1 keeps the two launches
@@ -6391,11 +6135,9 @@ static void launch_collide_solve(go2sim* h, hipStream_t s, int fuse_mode = 0) {
   {
     ScopedTimer t(h, s, T_COLLIDE);
     const int T = h->collide_team;
-    const int epw_c = collide_epw(h);
+    const int epw_c = 64 / T;
     dim3 gc((h->B + epw_c - 1) / epw_c);
-    if (T == 16 && epw_c == 2) hipLaunchKernelGGL((k_collide_team<16, 2>), gc, b, 0, s, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s);
-    else if (T == 16 && epw_c == 1) hipLaunchKernelGGL((k_collide_team<16, 1>), gc, b, 0, s, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s);
-    else if (T == 16) hipLaunchKernelGGL(k_collide_team<16>, gc, b, 0, s, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s);
+    if (T == 16) hipLaunchKernelGGL(k_collide_team<16>, gc, b, 0, s, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s);
     else if (T == 32) hipLaunchKernelGGL(k_collide_team<32>, gc, b, 0, s, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s);
     else hipLaunchKernelGGL(k_collide_team<64>, gc, b, 0, s, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s);
   }
@@ -6527,10 +6269,8 @@ static bool step_graph_build(go2sim* h, const float* actions, float* obs, float*
     // leave.  Tried and measured slower: off unless GO2SIM_PAR_PRE=1 (go2sim::par_pre).
     hipGraphNode_t pre_node = nullptr;
     if (i == 0 && fuse_pre(h) && h->par_pre) { pre_node = last; last = nullptr; }
-    { const int T = h->collide_team; const int epw_c = collide_epw(h); const dim3 gc((h->B + epw_c - 1) / epw_c);
-      ok = T == 16 && epw_c == 2 ? graph_add_kernel(h, last, k_collide_team<16, 2>, gc, b64, nullptr, nullptr, nullptr, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s)
-         : T == 16 && epw_c == 1 ? graph_add_kernel(h, last, k_collide_team<16, 1>, gc, b64, nullptr, nullptr, nullptr, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s)
-         : T == 16 ? graph_add_kernel(h, last, k_collide_team<16>, gc, b64, nullptr, nullptr, nullptr, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s)
+    { const int T = h->collide_team; const int epw_c = 64 / T; const dim3 gc((h->B + epw_c - 1) / epw_c);
+      ok = T == 16 ? graph_add_kernel(h, last, k_collide_team<16>, gc, b64, nullptr, nullptr, nullptr, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s)
          : T == 32 ? graph_add_kernel(h, last, k_collide_team<32>, gc, b64, nullptr, nullptr, nullptr, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s)
                    : graph_add_kernel(h, last, k_collide_team<64>, gc, b64, nullptr, nullptr, nullptr, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s); }
     if (!ok) break;
@@ -6555,7 +6295,7 @@ static bool step_graph_build(go2sim* h, const float* actions, float* obs, float*
     else { ok = add_integrate(); if (ok && i + 1 < substeps) ok = add_dynamics(); }
   }
   if (!ok) return false;
-  ok = graph_add_kernel(h, last, k_env_post_a, ge, dim3(WG * POST_A_WAVES), &g.n_post_a, &g.p_post_a, &sl, h->P, h->dm, h->hcfg, h->dglob, h->dacc, h->seed, h->step_count);
+  ok = graph_add_kernel(h, last, k_env_post_a, ge, dim3(WG * POST_A_NWAVES), &g.n_post_a, &g.p_post_a, &sl, h->P, h->dm, h->hcfg, h->dglob, h->dacc, h->seed, h->step_count);
   if (!ok) return false;
   g.a_pa_step = (uint32_t*)sl[6];
   if (h->hcfg.i[GO2SIM_IC_USE_TERRAIN]) {
@@ -6638,12 +6378,10 @@ int go2sim_create(const void* blob, size_t nbytes, int n_envs, int device, uint6
     if (const char* t = getenv("GO2SIM_NO_FUSE_SOLVE")) { if (atoi(t) != 0) h->fuse_solve_int = false; }
     if (const char* t = getenv("GO2SIM_FK_TEAM")) { int v = atoi(t); if (v == 16 || v == 32 || v == 64) h->fk_team = v; }
     if (const char* t = getenv("GO2SIM_COLLIDE_TEAM")) { int v = atoi(t); if (v == 16 || v == 32 || v == 64) h->collide_team = v; }
-    if (const char* t = getenv("GO2SIM_COLLIDE_EPW")) { int v = atoi(t); if (v == 1 || v == 2) h->collide_epw = v; }
     CK(hipMalloc((void**)&h->gjk_scratch, (size_t)n_envs * h->collide_team * sizeof(GjkStoreFull)));   // ~20 KB per narrow-phase lane
     if (const char* t = getenv("GO2SIM_SOLVER_TEAM")) { int v = atoi(t); if (v == 16 || v == 32 || v == 64) h->solver_team = v; }
     if (const char* t = getenv("GO2SIM_TERRAIN_SOLVER_TEAM")) { int v = atoi(t); if (v == 32 || v == 64) h->terrain_solver_team = v; }
     if (const char* t = getenv("GO2SIM_NO_LPT")) { if (atoi(t) != 0) h->use_lpt = false; }
-    if (const char* t = getenv("GO2SIM_LPT_FLAT")) { h->lpt_flat = atoi(t) != 0; }
     h->lpt_cap = n_envs / 8 + 72;
     CK(hipMalloc((void**)&h->lpt, 2 * lpt_record_ints(h) * sizeof(int)));
     CK(hipMemset(h->lpt, 0, 2 * lpt_record_ints(h) * sizeof(int)));
@@ -6962,7 +6700,7 @@ int go2sim_env_step(go2sim_t* h, const float* actions, float* obs, float* priv, 
   launch_substeps(h, s, h->hcfg.i[GO2SIM_IC_SUBSTEPS], fuse_pre(h) ? actions : nullptr);
   {
     ScopedTimer t(h, s, T_ENV_POST);
-    hipLaunchKernelGGL(k_env_post_a, g, dim3(WG * POST_A_WAVES), 0, s, h->P, h->dm, h->hcfg, h->dglob, h->dacc, h->seed, h->step_count);
+    hipLaunchKernelGGL(k_env_post_a, g, dim3(WG * POST_A_NWAVES), 0, s, h->P, h->dm, h->hcfg, h->dglob, h->dacc, h->seed, h->step_count);
     if (h->hcfg.i[GO2SIM_IC_USE_TERRAIN]) hipLaunchKernelGGL(k_env_terrain_rows, dim3((h->B + 255) / 256), dim3(256), 0, s, h->P, h->dcfg, h->dglob, h->seed);
     hipLaunchKernelGGL(k_env_post_b_team<16>, dim3((h->B + 3) / 4), dim3(128), 0, s, h->P, h->dm, h->dms, h->dcfg, h->dglob, h->seed, h->step_count, obs, priv, rew, reset, timeout);
     if (h->hcfg.i[GO2SIM_IC_ENGINE_BATCH_GAIN]) hipLaunchKernelGGL(k_env_engine_gains, dim3(1), dim3(GAIN_WG), 0, s, h->P, h->dm, h->dms, h->dcfg, h->dglob);
@@ -7238,15 +6976,6 @@ int go2sim_debug_narrowphase(go2sim_t* h, int which, int i_ga, int i_gb, const f
   return GO2SIM_E_OK;
 }
 
-#ifdef GO2SIM_BRACKET_DEBUG
-int go2sim_debug_brlog(go2sim_t* h, float* out, int* cnt) {
-  if (!h || !out || !cnt) return GO2SIM_E_BADARG;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_brlog), sizeof(float) * BRLOG_ENVS * BRLOG_CAP * BRLOG_W));
-  HIPCHK(hipMemcpyFromSymbol(cnt, HIP_SYMBOL(g_brcnt), sizeof(int) * BRLOG_ENVS));
-  return GO2SIM_E_OK;
-}
-#endif
 /* development/test aid (not declared in include/go2sim.h): device address of ANY pool field by name */
 #ifdef GO2SIM_STAMP
 int go2sim_debug_stamps(go2sim_t* h, unsigned long long* stamps, unsigned* counts) {   // [ST_KINDS][ST_MAX_WG][ST_DEPTH][2], [ST_KINDS][ST_MAX_WG]

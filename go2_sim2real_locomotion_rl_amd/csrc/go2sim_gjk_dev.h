@@ -21,16 +21,9 @@
 #ifndef GO2SIM_GJK_DEV_H
 #define GO2SIM_GJK_DEV_H
 
-// Two code shapes, same arithmetic: the default inlines and unrolls (fastest measured: 107 k cycles per query at the landing peak); with
-// -DGO2SIM_GJK_COMPACT the support evaluation / face attachment are single out-of-line copies and the loops stay rolled (4 k instead of 15 k
-// instructions, but 164 k cycles per query: the call frames and rolled loops cost more than the instruction fetch they save).
-#ifdef GO2SIM_GJK_COMPACT
-#define DG_OUTLINE DEVN
-#define DG_NOUNROLL _Pragma("nounroll")
-#else
-#define DG_OUTLINE DEV
-#define DG_NOUNROLL
-#endif
+// The support evaluation and the face attachment are inlined and the loops unrolled (107 k cycles per query at the landing peak).  Single
+// out-of-line copies with rolled loops were measured too: 4 k instead of 15 k instructions, but 164 k cycles per query (the call frames and
+// rolled loops cost more than the instruction fetch they save).
 constexpr int DG_GJK_MAX_IT = 50, DG_EPA_MAX_IT = 50;                 // gjk.py:53-54
 constexpr int DG_MAX_FACES = 6 * DG_EPA_MAX_IT;                        // gjk.py:56 (polytope_max_faces)
 constexpr int DG_MAX_VERTS = 5 + DG_EPA_MAX_IT;                        // array_class.py:744
@@ -58,7 +51,7 @@ struct DgResult { bool is_col, overflow; float penetration; V3 normal, pos; };
 struct DgPair {
   const Model* m; int i_ga, i_gb; V3 pos_a; Q4 quat_a; V3 pos_b; Q4 quat_b; bool discrete; GeomLite ga, gb; Rot ra, rb;   // type / size of the two geoms and the rotation coefficients of their poses, set up once
   DEV V3 support_one(V3 d, int i_g, const GeomLite& gl, V3 pos, const Rot& rot, int& vid) const { return gjk_support_driver(*m, d, i_g, gl, pos, rot, vid); }
-  DG_OUTLINE void support_into(V3 d, DgVert* out) const {                   // the one copy of the support code of a query
+  DEV void support_into(V3 d, DgVert* out) const {                   // the one copy of the support code of a query
     PHD_BEGIN
     DgVert r;
     r.o1 = support_one(d, i_ga, ga, pos_a, ra, r.id1);
@@ -74,7 +67,7 @@ struct DgPair {
     V3 db = rot_apply_inv(rot, d);
     return 1 << ((db.x == 0.0f) + (db.y == 0.0f) + (db.z == 0.0f));
   }
-  DG_OUTLINE int count(V3 d) const { return count_one(d, ga, ra) * count_one(-d, gb, rb); }
+  DEV int count(V3 d) const { return count_one(d, ga, ra) * count_one(-d, gb, rb); }
   // func_get_discrete_geom_vertex (BOX), gjk.py:1666-1700
   DEV void box_vertex(bool second, int i_v, V3& obj, int& id) const {
     const int i_g = second ? i_gb : i_ga;
@@ -119,7 +112,6 @@ DEV bool dg_valid(const S& st, int ns, const DgVert& w) { return !dg_duplicate(s
 template <class S>
 DEV DgVert dg_safe_support(const DgPair& pr, const S& st, int ns, V3 dir, float eps) {
   DgVert w; w.o1 = v3(0, 0, 0); w.o2 = v3(0, 0, 0); w.mk = v3(0, 0, 0); w.id1 = -1; w.id2 = -1;
-DG_NOUNROLL
   for (int i = 0; i < 9; ++i) {
     V3 nd = dir;
     if (i > 0) {
@@ -144,7 +136,6 @@ template <class S>
 DEV bool dg_search_vertex(const DgPair& pr, const S& st, GjkCtl& c, DgVert& w, float eps) {
   w.o1 = v3(0, 0, 0); w.o2 = v3(0, 0, 0); w.mk = v3(0, 0, 0); w.id1 = -1; w.id2 = -1;
   if (pr.discrete) {                                                    // box - box: walk the 8 x 8 vertex pairs from where the last search stopped
-DG_NOUNROLL
     for (int k = 0; k < 64; ++k) {
       const int mth = (k + c.last_searched) % 64;
       pr.box_vertex(false, mth / 8, w.o1, w.id1);
@@ -158,7 +149,6 @@ DG_NOUNROLL
     V3 a = st.v[0].mk, b = st.v[1].mk, cc = st.v[2].mk;
     V3 nrm = cross(cc - a, b - a);
     V3 dir = nrm / norm(nrm);
-DG_NOUNROLL
     for (int i = 0; i < 2; ++i) {
       w = dg_safe_support(pr, st, c.ns, (i == 0) ? dir : -dir, eps);
       if (dg_valid(st, c.ns, w)) return true;
@@ -174,7 +164,6 @@ template <class S>
 DEV bool dg_gjk(const DgPair& pr, S& st, GjkCtl& c, float eps) {
   c.ns = 0;
   V3 best_n = v3(0, 0, 0);
-DG_NOUNROLL
   for (int step = 0; step < 4 + DG_GJK_MAX_IT; ++step) {
     const bool init = step < 4;
     V3 dir = best_n;
@@ -185,7 +174,6 @@ DG_NOUNROLL
     } else {
       // outward normal and signed distance (origin inside => positive) of the four faces; face j is opposite to vertex j
       float best_sd = 0.0f; int best = 0;
-DG_NOUNROLL
       for (int j = 0; j < 4; ++j) {
         const int a = (j == 0) ? 2 : ((j == 1) ? 0 : ((j == 2) ? 1 : 0));
         const int b = (j == 0) ? 1 : ((j == 1) ? 2 : ((j == 2) ? 0 : 1));
@@ -235,7 +223,7 @@ DEV bool dg_plane_normal(V3 p1, V3 p2, V3 p3, V3& nrm) {
 // func_safe_attach_face_to_polytope, epa.py:1298-1380; the caller has checked the capacity
 // (the face index and the vertex count are explicit so that several lanes can attach different faces of one polytope side by side)
 template <class S>
-DG_OUTLINE bool dg_attach_face_at(S& st, int nv, int n, int v1, int v2, int v3_, int a1, int a2, int a3) {
+DEV bool dg_attach_face_at(S& st, int nv, int n, int v1, int v2, int v3_, int a1, int a2, int a3) {
   DgFace& F = st.f[n];
   F.v[0] = (short)v1; F.v[1] = (short)v2; F.v[2] = (short)v3_; F.adj[0] = (short)a1; F.adj[1] = (short)a2; F.adj[2] = (short)a3;
   V3 p1 = st.v[v1].mk, p2 = st.v[v2].mk, p3 = st.v[v3_].mk, nrm;
@@ -360,7 +348,6 @@ DEV float dg_epa(const DgPair& pr, S& st, GjkCtl& c, float eps, V3& w1, V3& w2, 
   has_witness = false;
   // polytope = the GJK tetrahedron (its vertices already sit in v[0..3])
   c.nv = 4; c.nf = 0; c.nmap = 0; c.hz_n = 0;
-DG_NOUNROLL
   for (int i = 0; i < 4; ++i) {                                          // (vertices | neighbours) of the four faces, 3 bits per index
     const unsigned code = (i == 0) ? 0210u | (0231u << 9) : ((i == 1) ? 0130u | (0032u << 9) : ((i == 2) ? 0320u | (0130u << 9) : 0123u | (0102u << 9)));
     dg_attach_face(st, c, (int)(code & 7u), (int)((code >> 3) & 7u), (int)((code >> 6) & 7u), (int)((code >> 9) & 7u), (int)((code >> 12) & 7u), (int)((code >> 15) & 7u));

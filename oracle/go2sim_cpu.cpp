@@ -1454,14 +1454,11 @@ void add_joint_limit_constraints(const Model& m, Env& e) {
 // reference's CPU (serial) variants; north_star allows a float32 tolerance on floats, and the HIP product uses it for the reductions that sit on
 // the critical path of the Newton solve: sums over constraint rows / dofs are lane-parallel butterfly trees instead of first-to-last chains,
 // the triangular solves multiply by a stored reciprocal diagonal (as the reference's own LDL^T path does for the mass matrix,
-// forward_dynamics.py:545-687) and run column-oriented, and the rank-1 Cholesky rotations use reciprocals that are formed off the critical
-// path.  This build mirrors that arithmetic operation for operation, so that HIP == libgo2sim_cpu_fast.so bit for bit;
+// forward_dynamics.py:545-687) and run column-oriented, and a change of the active set refactorises the Hessian instead of updating the factor
+// by rank-1 rotations.  This build mirrors that arithmetic operation for operation, so that HIP == libgo2sim_cpu_fast.so bit for bit;
 // tests/test_fast_order.py bounds fast vs strict.
 // ---------------------------------------------------------------------------------------------
 #ifdef GO2SIM_FAST_ORDER
-#ifndef GO2SIM_REBUILD_FLIPS
-#define GO2SIM_REBUILD_FLIPS 1
-#endif
 inline int fast_team(const Model& m) { return m.terrain_enabled ? 64 : 32; }   // lanes per env of k_constraint_solve_team (flat: 32, heightfield: 64)
 // sum of `n` terms spread over the W lanes of a team: lane l adds its terms l, l + W, ... first to last, then a butterfly over the lanes
 // (xor 1, xor 2, mirror in 8, mirror in 16 inside rows of 16 lanes; the rows are added pairwise)
@@ -1535,9 +1532,6 @@ void hessian_update(const Model& m, Env& e) {
 // reciprocal pivots sqrt(e) * (1 / e) and fused multiply-adds
 bool rows_uncoupled(const Model& m, const Env& e) {                 // no contact joins links of two different legs (the link chains a contact row walks up, ts_solve)
   if (ND != 18 || m.arrow_mode == 0) return false;
-#if GO2SIM_REBUILD_FLIPS > 1
-  return false;
-#endif
   for (int i_c = 0; i_c < e.n_contacts; ++i_c) {
     unsigned legs = 0u;
     for (int i_ab = 0; i_ab < 2; ++i_ab)
@@ -1580,16 +1574,13 @@ void cholesky_factor_direct(const Model& m, Env& e) {
 }
 // func_hessian_and_cholesky_factor_incremental_dense_batch, solver.py:1632-1675
 bool cholesky_incremental(const Model& m, Env& e) {
-  bool is_degenerated = false;
 #ifdef GO2SIM_FAST_ORDER
-  {                                                                // ts_cholesky_incremental: REBUILD_FLIPS or more flipped rows -> the caller's rebuild path
-    int n_flip = 0;
-    for (int i_c = 0; i_c < e.n_con; ++i_c) n_flip += ((e.active[i_c] != 0) != (e.prev_active[i_c] != 0)) ? 1 : 0;
-    if (n_flip >= GO2SIM_REBUILD_FLIPS) return true;
-  }
-  real invd[ND];                                                   // reciprocal diagonal of the factor, carried through the updates
-  for (int k = 0; k < ND; ++k) invd[k] = 1.0f / e.H[k][k];
+  // ts_cholesky_incremental: any flipped row -> the caller's rebuild path; none -> the factor stands
+  for (int i_c = 0; i_c < e.n_con; ++i_c)
+    if ((e.active[i_c] != 0) != (e.prev_active[i_c] != 0)) return true;
+  return false;
 #endif
+  bool is_degenerated = false;
   for (int i_c = 0; i_c < e.n_con; ++i_c) {
     bool is_active = e.active[i_c] != 0, is_active_prev = e.prev_active[i_c] != 0;
     if (is_active ^ is_active_prev) {
@@ -1602,17 +1593,9 @@ bool cholesky_incremental(const Model& m, Env& e) {
           real tmp = Lkk * Lkk + sign * (e.nt_vec[k] * e.nt_vec[k]);
           if (tmp < m.eps) { is_degenerated = true; break; }
           real r = dm_sqrt(tmp);
-#ifdef GO2SIM_FAST_ORDER
-          real rinv = r * (1.0f / tmp);                              // 1 / r without a division after the square root
-          real c = r * invd[k];
-          real cinv = Lkk * rinv;
-          real s = e.nt_vec[k] * invd[k];
-          invd[k] = rinv;
-#else
           real c = r / Lkk;
           real cinv = 1.0f / c;
           real s = e.nt_vec[k] / Lkk;
-#endif
           e.H[k][k] = r;
           for (int i = k + 1; i < ND; ++i) e.H[i][k] = (e.H[i][k] + s * e.nt_vec[i] * sign) * cinv;
           for (int i = k + 1; i < ND; ++i) e.nt_vec[i] = e.nt_vec[i] * c - s * e.H[i][k];

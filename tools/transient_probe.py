@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel ms/step in the landing window (steps W..W+K after the reset) for one or more builds of the library.
-usage: transient_probe.py [--warm 5] [--steps 20] [--kind C] lib1.so [lib2.so ...]   (profiling builds: -DGO2SIM_REPEAT_PHASE=k)"""
+usage: transient_probe.py [--warm 5] [--steps 20] [--kind C] lib1.so [lib2.so ...]   (any builds, e.g. build.build_hip_variant(name, flags))"""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
