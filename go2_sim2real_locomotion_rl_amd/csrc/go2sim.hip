@@ -39,6 +39,7 @@ constexpr int NPAIR = GO2SIM_NPAIR_MAX, MAXC = GO2SIM_MAX_CONTACTS, MAXB = GO2SI
 constexpr int JOINT_FIXED = 0, JOINT_REVOLUTE = 1, JOINT_FREE = 4;
 constexpr int GEOM_PLANE = 0, GEOM_SPHERE = 1, GEOM_CYLINDER = 3, GEOM_BOX = 5, GEOM_TERRAIN = 7;   // GEOM_PLANE: geom 0 only (with_plane_ground)
 constexpr int TERRAIN_CB = 4;   // vertices per side of a block of the coarse maximum map of the heightfield
+constexpr int MAX_CONTACTS_PER_PAIR = 5;   // largest n_contacts_per_pair a model may ask for (parse_model)
 constexpr int CTRL_FORCE = 0, CTRL_VELOCITY = 1, CTRL_POSITION = 2;
 constexpr int NA = 16, NM = 12, NOBS_MAX = 64, NPRIV_MAX = 192, NREW = 32;
 constexpr int WG = 64;  // one wavefront per workgroup
@@ -290,6 +291,7 @@ bool parse_model(const void* blob, size_t nbytes, Model& m) {
   int nf = H[18], ni = H[19];
   if (m.n_links != NL || m.n_joints != NJ || m.n_dofs != ND || m.n_qs != NQ || m.n_geoms != NG || m.n_entities != 2) return false;
   if (m.n_pairs > NPAIR || m.max_contact_pairs > MAXC || m.max_broad_pairs > MAXB || m.support_res != 180 || H[17] != 32) return false;
+  if (m.n_contacts_per_pair > MAX_CONTACTS_PER_PAIR) return false;   // the staging slots of a lane and the terrain replay hold five contacts per pair
   if (nbytes < 128 + (size_t)4 * (nf + ni)) return false;
   const float* F = (const float*)((const char*)blob + 128);
   const int32_t* I = (const int32_t*)(F + nf);
@@ -2500,6 +2502,26 @@ DEV bool terrain_pair_setup(const Model& m, const E& e, int i_ga, int i_gb, TP& 
 }
 // height of the k-th vertex of the strip of row r (vertex order of func_add_prism_vert: (c, i) with i fastest)
 DEV float terrain_strip_z(const Model& m, int r, int c_min, int k) { return m.terrain_hf[(size_t)(r + (k & 1)) * m.terrain_cols + c_min + (k >> 1)]; }
+// Prism descriptor of k_collide_team: pair slot | cell index within the pair << 5.  The cell `local` of a pair is the prism after vertex
+// k = 2 + local % nkk of row r = r_min + local / nkk: relative to the pair, so that any row or column of the heightfield is encoded (a pair's bounding
+// box covers fewer than 2^26 prisms).
+static_assert(NG - 1 <= 32, "five bits of pair slot: at most 32 geoms besides the heightfield");
+// the cell index of terrain_desc has 26 bits: a pair's bounding box spans at most (D / hs + 2) rows and columns for a geom of init-AABB diagonal D,
+// 2 (D / hs + 2)^2 prisms; go2sim_set_terrain refuses a cell size at which some geom could cover more (the oracle applies the same test)
+inline bool terrain_cells_fit(const Model& m, float hs) {
+  for (int i = 0; i < NG; ++i) {
+    const double dx = m.geoms[i].aabb[7].x - m.geoms[i].aabb[0].x, dy = m.geoms[i].aabb[7].y - m.geoms[i].aabb[0].y, dz = m.geoms[i].aabb[7].z - m.geoms[i].aabb[0].z;
+    const double n = std::sqrt(dx * dx + dy * dy + dz * dz) / (double)hs + 2.0;
+    if (i > 0 && 2.0 * n * n >= (double)(1 << 26)) return false;
+  }
+  return true;
+}
+DEV int terrain_desc(int p, int local) { return p | (local << 5); }
+template <class TP>
+DEV void terrain_desc_cell(const TP& t, int local, int& r, int& k) {
+  const int nkk = 2 * (t.c_max - t.c_min + 1) - 2;
+  r = t.r_min + local / nkk; k = 2 + local % nkk;
+}
 // (2) the prism that exists after the k-th vertex of row r was pushed (k >= 2) is tested iff one of its top vertices reaches the geom: evaluated one
 //     cell per lane in k_collide_team
 // (3) MPR of the geom against that prism; the contact is returned in world coordinates
@@ -2837,128 +2859,136 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
     }
     team_sync();
     PH(26)
-    int* items = (int*)&gjk_scratch[(size_t)b * T];                     // prism descriptors p | r << 5 | k << 18 (the GJK scratch is idle in this pass)
+    int* items = (int*)&gjk_scratch[(size_t)b * T];                     // prism descriptors, terrain_desc (the GJK scratch is idle in this pass)
+    constexpr int TU = 4;
     const int items_cap = (int)(sizeof(GjkStoreFull) * T / sizeof(int));
+    static_assert(sizeof(GjkStoreFull) / sizeof(int) >= TU, "a chunk of descriptors holds a batch of cells");
+    static_assert(sizeof(GjkStoreFull) * 16 / sizeof(int) <= 100000, "test_terrain_gpu.py::test_descriptors_beyond_one_chunk sizes its field for > 1 chunk");
     int n_cells = 0;
     for (int p = 0; p < n_tp; ++p) n_cells += s->tr.tp[p].n_items;
     team_sync();
     { int off = 0; for (int p = 0; p < n_tp; ++p) { int c = s->tr.tp[p].n_items; if (tl == 0) s->tr.tp[p].item_off = off; off += c; } }   // first cell of the pair
     team_sync();
-    // One lane per cell, TU cells per lane in flight (the heights come from L2 / HBM: the loads of a batch are issued together).  A cell is a
-    // descriptor iff one of the three top vertices of its prism reaches the geom (narrowphase.py:430-436); the descriptors are compacted in
-    // (pair, row, vertex) order, the order in which the serial loop meets them.
-    int n_items = 0;
-    {
-      constexpr int TU = 4;
-      int p_cur = 0, p_end = n_tp > 0 ? s->tr.tp[0].n_items : 0;        // cells [.., p_end) belong to pairs <= p_cur (per-lane cursor: a lane's cells ascend)
-      for (int base = 0; base < n_cells; base += T * TU) {
+    int cur_p = -1, n_con = 0;                                          // replay state (identical on every lane), carried from chunk to chunk
+    float tolerance = 0.0f;
+    V3 acc[5];                                                          // contacts already accepted for the current terrain pair (dedupe); team-uniform
+#pragma unroll
+    for (int j = 0; j < 5; ++j) acc[j] = v3(0, 0, 0);
+    // The cells are visited in chunks whose descriptors fit the scratch (items_cap, ~79 k at T = 16); a chunk is culled and replayed before the
+    // next one is enumerated, so a heightfield too fine for one chunk still gives the serial loop's contact list.  One chunk in the benchmarks.
+    int p_cur = 0, p_end = n_tp > 0 ? s->tr.tp[0].n_items : 0;          // cells [.., p_end) belong to pairs <= p_cur (per-lane cursor: a lane's cells ascend)
+    for (int cell_base = 0; cell_base < n_cells;) {
+      // One lane per cell, TU cells per lane in flight (the heights come from L2 / HBM: the loads of a batch are issued together).  A cell is a
+      // descriptor iff one of the three top vertices of its prism reaches the geom (narrowphase.py:430-436); the descriptors are compacted in
+      // (pair, row, vertex) order, the order in which the serial loop meets them.
+      int n_items = 0;
+      for (; cell_base < n_cells && n_items <= items_cap - T * TU; cell_base += T * TU) {
         int desc[TU]; bool el[TU];
 #pragma unroll
         for (int u = 0; u < TU; ++u) {
-          const int ci = base + u * T + tl;
+          const int ci = cell_base + u * T + tl;
           el[u] = false; desc[u] = 0;
           if (ci < n_cells) {
             while (ci >= p_end) { ++p_cur; p_end += s->tr.tp[p_cur].n_items; }
             const auto& t = s->tr.tp[p_cur];
-            const int nkk = 2 * (t.c_max - t.c_min + 1) - 2;
             const int local = ci - (p_end - t.n_items);
-            const int r = t.r_min + local / nkk, k = 2 + local % nkk;
+            int r, k;
+            terrain_desc_cell(t, local, r, k);
             const float z0 = terrain_strip_z(m, r, t.c_min, k - 2), z1 = terrain_strip_z(m, r, t.c_min, k - 1), z2 = terrain_strip_z(m, r, t.c_min, k);
             el[u] = (z0 >= t.zmin) | (z1 >= t.zmin) | (z2 >= t.zmin);
-            desc[u] = p_cur | (r << 5) | (k << 18);
+            desc[u] = terrain_desc(p_cur, local);
           }
         }
 #pragma unroll
         for (int u = 0; u < TU; ++u) {
           const unsigned long long mk = team_ballot<T>(el[u]);
-          if (el[u]) { const int q = n_items + __popcll(mk & ((1ull << tl) - 1ull)); if (q < items_cap) items[q] = desc[u]; }
+          if (el[u]) items[n_items + __popcll(mk & ((1ull << tl) - 1ull))] = desc[u];
           n_items += __popcll(mk);
         }
       }
-    }
-    if (n_items > items_cap) n_items = items_cap;
-    team_sync();
-    // About half of the queries end at the first support point of the portal search (the prism lies beside the geom).  That step is evaluated for
-    // every descriptor here, and only the survivors are distributed for the full query (compacted in place, in order: the write position never
-    // passes the read position).  A dropped descriptor is one whose query returns "no contact", so the contact list does not change.
-    {
-      int n_keep = 0;
+      team_sync();
+      // About half of the queries end at the first support point of the portal search (the prism lies beside the geom).  That step is evaluated for
+      // every descriptor here, and only the survivors are distributed for the full query (compacted in place, in order: the write position never
+      // passes the read position).  A dropped descriptor is one whose query returns "no contact", so the contact list does not change.
+      {
+        int n_keep = 0;
+        for (int base = 0; base < n_items; base += T) {
+          const int q = base + tl;
+          int d = 0; bool keep = false;
+          if (q < n_items) {
+            d = items[q];
+            const auto& t = s->tr.tp[d & 31];
+            int r, k;
+            terrain_desc_cell(t, d >> 5, r, k);
+            keep = !terrain_prism_separated_at_once(m, t, i_terrain, r, k);
+          }
+          const unsigned long long mk = team_ballot<T>(keep);
+          if (keep) items[n_keep + __popcll(mk & ((1ull << tl) - 1ull))] = d;
+          n_keep += __popcll(mk);
+          team_sync();
+        }
+        n_items = n_keep;
+      }
+      PH(27)
       for (int base = 0; base < n_items; base += T) {
         const int q = base + tl;
-        int d = 0; bool keep = false;
+        float* st = &s->stage[tl][0][0];
+        int has = 0;
         if (q < n_items) {
-          d = items[q];
-          keep = !terrain_prism_separated_at_once(m, s->tr.tp[d & 31], i_terrain, (d >> 5) & 0x1fff, d >> 18);
+          int d = items[q];
+          const auto& t = s->tr.tp[d & 31];
+          V3 normal, cpos; float pen;
+          int r, k;
+          terrain_desc_cell(t, d >> 5, r, k);
+          if (terrain_prism_contact(m, e, t, i_terrain, r, k, normal, cpos, pen)) {
+            has = 1 + (d & 31);
+            st[0] = normal.x; st[1] = normal.y; st[2] = normal.z; st[3] = cpos.x; st[4] = cpos.y; st[5] = cpos.z; st[6] = pen;
+          }
         }
-        const unsigned long long mk = team_ballot<T>(keep);
-        if (keep) items[n_keep + __popcll(mk & ((1ull << tl) - 1ull))] = d;
-        n_keep += __popcll(mk);
+        s->cnt[tl] = has;                                                  // 0 = no contact, else 1 + pair slot
         team_sync();
-      }
-      n_items = n_keep;
-    }
-    PH(27)
-    int cur_p = -1, n_con = 0;                                          // replay state (identical on every lane)
-    float tolerance = 0.0f;
-    V3 acc[5];                                                          // contacts already accepted for the current terrain pair (dedupe); team-uniform
+        PH(28)
+        // replay of the serial accept / dedupe / cap logic over the prisms of this round that produced a contact (team-uniform: every lane reads the
+        // same staged values); the j-th accepted contact of the round is then written out by lane j
+        unsigned long long hm = team_ballot<T>(has != 0);
+        int n_acc = 0, my_l = -1, my_ic = 0;
+        while (hm) {
+          const int l = __ffsll((long long)hm) - 1;
+          hm &= hm - 1ull;
+          const int p = s->cnt[l] - 1;
+          if (p != cur_p) { cur_p = p; n_con = 0; tolerance = s->tr.tp[p].tol; }
+          if (n_con >= m.n_contacts_per_pair) continue;
+          const float* pc = &s->stage[l][0][0];
+          const V3 cpos = v3(pc[3], pc[4], pc[5]);
+          bool valid = true;
 #pragma unroll
-    for (int j = 0; j < 5; ++j) acc[j] = v3(0, 0, 0);
-    for (int base = 0; base < n_items; base += T) {
-      const int q = base + tl;
-      float* st = &s->stage[tl][0][0];
-      int has = 0;
-      if (q < n_items) {
-        int d = items[q];
-        const auto& t = s->tr.tp[d & 31];
-        V3 normal, cpos; float pen;
-        if (terrain_prism_contact(m, e, t, i_terrain, (d >> 5) & 0x1fff, d >> 18, normal, cpos, pen)) {
-          has = 1 + (d & 31);
-          st[0] = normal.x; st[1] = normal.y; st[2] = normal.z; st[3] = cpos.x; st[4] = cpos.y; st[5] = cpos.z; st[6] = pen;
+          for (int jj = 0; jj < 5; ++jj)                                  // acc[jj] is contact nc_run - n_con + jj of the list
+            if (jj < n_con && nc_run - n_con + jj < m.max_contact_pairs && norm(cpos - acc[jj]) < tolerance) valid = false;
+          if (!valid) continue;
+#pragma unroll
+          for (int jj = 0; jj < 5; ++jj) if (jj == n_con) acc[jj] = cpos;
+          if (tl == n_acc) { my_l = l; my_ic = nc_run; }
+          n_acc++; nc_run++; n_con++;
         }
-      }
-      s->cnt[tl] = has;                                                  // 0 = no contact, else 1 + pair slot
-      team_sync();
-      PH(28)
-      // replay of the serial accept / dedupe / cap logic over the prisms of this round that produced a contact (team-uniform: every lane reads the
-      // same staged values); the j-th accepted contact of the round is then written out by lane j
-      unsigned long long hm = team_ballot<T>(has != 0);
-      int n_acc = 0, my_l = -1, my_ic = 0;
-      while (hm) {
-        const int l = __ffsll((long long)hm) - 1;
-        hm &= hm - 1ull;
-        const int p = s->cnt[l] - 1;
-        if (p != cur_p) { cur_p = p; n_con = 0; tolerance = s->tr.tp[p].tol; }
-        if (n_con >= m.n_contacts_per_pair) continue;
-        const float* pc = &s->stage[l][0][0];
-        const V3 cpos = v3(pc[3], pc[4], pc[5]);
-        bool valid = true;
-#pragma unroll
-        for (int jj = 0; jj < 5; ++jj)                                  // acc[jj] is contact nc_run - n_con + jj of the list
-          if (jj < n_con && nc_run - n_con + jj < m.max_contact_pairs && norm(cpos - acc[jj]) < tolerance) valid = false;
-        if (!valid) continue;
-#pragma unroll
-        for (int jj = 0; jj < 5; ++jj) if (jj == n_con) acc[jj] = cpos;
-        if (tl == n_acc) { my_l = l; my_ic = nc_run; }
-        n_acc++; nc_run++; n_con++;
-      }
-      if (my_l >= 0) {
-        if (my_ic < m.max_contact_pairs) {                               // func_add_contact, contact.py:165-199
-          const float* pc = &s->stage[my_l][0][0];
-          const int i_ga = s->tr.tp[s->cnt[my_l] - 1].i_ga, i_c = my_ic;
-          float friction_a = e.geom_friction()[i_ga] * e.friction_ratio()[i_ga];
-          float friction_b = e.geom_friction()[i_terrain] * e.friction_ratio()[i_terrain];
-          e.c_geom()[i_c] = i_ga; e.c_geom()[MAXC + i_c] = i_terrain;
-          e.c_normal()[i_c] = v3(pc[0], pc[1], pc[2]); e.c_pos()[i_c] = v3(pc[3], pc[4], pc[5]); e.c_pen()[i_c] = pc[6];
-          e.c_friction()[i_c] = fmx(fmx(friction_a, friction_b), 1e-2f);
-          auto sol = e.c_sol()[i_c];
-          for (int qq = 0; qq < 7; ++qq) sol[qq] = 0.5f * (m.geoms[i_ga].sol_params[qq] + m.geoms[i_terrain].sol_params[qq]);
-          e.c_link()[i_c] = m.geoms[i_ga].link; e.c_link()[MAXC + i_c] = m.geoms[i_terrain].link;
-        } else {
-          atomicOr(&e.err()[0], GO2SIM_ERR_OVERFLOW_COLLISION_PAIRS);
+        if (my_l >= 0) {
+          if (my_ic < m.max_contact_pairs) {                               // func_add_contact, contact.py:165-199
+            const float* pc = &s->stage[my_l][0][0];
+            const int i_ga = s->tr.tp[s->cnt[my_l] - 1].i_ga, i_c = my_ic;
+            float friction_a = e.geom_friction()[i_ga] * e.friction_ratio()[i_ga];
+            float friction_b = e.geom_friction()[i_terrain] * e.friction_ratio()[i_terrain];
+            e.c_geom()[i_c] = i_ga; e.c_geom()[MAXC + i_c] = i_terrain;
+            e.c_normal()[i_c] = v3(pc[0], pc[1], pc[2]); e.c_pos()[i_c] = v3(pc[3], pc[4], pc[5]); e.c_pen()[i_c] = pc[6];
+            e.c_friction()[i_c] = fmx(fmx(friction_a, friction_b), 1e-2f);
+            auto sol = e.c_sol()[i_c];
+            for (int qq = 0; qq < 7; ++qq) sol[qq] = 0.5f * (m.geoms[i_ga].sol_params[qq] + m.geoms[i_terrain].sol_params[qq]);
+            e.c_link()[i_c] = m.geoms[i_ga].link; e.c_link()[MAXC + i_c] = m.geoms[i_terrain].link;
+          } else {
+            atomicOr(&e.err()[0], GO2SIM_ERR_OVERFLOW_COLLISION_PAIRS);
+          }
         }
+        team_sync();                                                       // stage / cnt / items are rewritten by the next round or chunk
+        PH(29)
       }
-      team_sync();                                                       // stage / cnt are rewritten by the next round
-      PH(29)
     }
   }
   if (tl == 0) {
@@ -6565,6 +6595,7 @@ __global__ void k_set_link0_pose(Pool P, V3 pos) {
 }
 int go2sim_set_terrain(go2sim_t* h, const int16_t* hf, int rows, int cols, float horizontal_scale, float vertical_scale, const float* origin, void* stream) {
   if (!h || !hf || rows < 2 || cols < 2 || !origin || !(horizontal_scale > 0.0f)) return GO2SIM_E_BADARG;
+  if (!terrain_cells_fit(h->hm, horizontal_scale)) return GO2SIM_E_BADARG;
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(hipStreamSynchronize(s));
   step_graph_destroy(h);   // the solver kernel of the step graph depends on the terrain flag

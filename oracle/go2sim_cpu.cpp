@@ -245,6 +245,7 @@ bool parse_model(const void* blob, size_t nbytes, Model& m) {
   int nf = H[18], ni = H[19];
   if (m.n_links != NL || m.n_joints != NJ || m.n_dofs != ND || m.n_qs != NQ || m.n_geoms != NG || m.n_entities != 2) return false;
   if (m.n_pairs > NPAIR || m.max_contact_pairs > MAXC || m.max_broad_pairs > MAXB || m.support_res != 180 || H[17] != 32) return false;
+  if (m.n_contacts_per_pair > 5) return false;   // the HIP library stages at most five contacts per pair; both libraries accept the same models
   if (nbytes < 128 + (size_t)4 * (nf + ni)) return false;
   const float* F = (const float*)((const char*)blob + 128);
   const int32_t* I = (const int32_t*)(F + nf);
@@ -3204,6 +3205,12 @@ int go2sim_cpu_read_timing(go2sim*, float*, int*, int) { return GO2SIM_E_BADARG;
 // Terrain morph (rigid_entity.py:505-552, utils/terrain.py:228-330, collider.py:374-394): the ground slab becomes a heightfield geom
 int go2sim_cpu_set_terrain(go2sim* h, const int16_t* hf, int rows, int cols, float horizontal_scale, float vertical_scale, const float* origin, void*) {
   if (!h || !hf || rows < 2 || cols < 2 || !origin || !(horizontal_scale > 0.0f)) return GO2SIM_E_BADARG;
+  for (int i = 1; i < NG; ++i) {                       // the HIP library's prism descriptors index at most 2^26 prisms per pair: refuse the same fields
+    const Geom& g = h->m.geoms[i];
+    const double dx = g.aabb[7].x - g.aabb[0].x, dy = g.aabb[7].y - g.aabb[0].y, dz = g.aabb[7].z - g.aabb[0].z;
+    const double n = std::sqrt(dx * dx + dy * dy + dz * dz) / (double)horizontal_scale + 2.0;
+    if (2.0 * n * n >= (double)(1 << 26)) return GO2SIM_E_BADARG;
+  }
   Model& m = h->m;
   m.terrain_enabled = 1; m.terrain_rows = rows; m.terrain_cols = cols; m.terrain_hs = horizontal_scale;
   m.terrain_hf.resize((size_t)rows * cols);

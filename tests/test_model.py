@@ -181,3 +181,27 @@ def test_anymal_c_scene_step_hip_equals_oracle(oracle_lib, hip_lib):
             t = torch.zeros(k, B, device=dev); gpu.get_field(C["GO2SIM_" + name], t); torch.cuda.synchronize()
             assert np.array_equal(t.cpu().numpy().view(np.int32), cpu.get_field_np(C["GO2SIM_" + name]).view(np.int32)), f"step {s}: {name}"
     assert gpu.check_errno() == 0
+
+
+@pytest.mark.parametrize("n", [5, 6])
+def test_contacts_per_pair_above_five_is_rejected(oracle_lib, n):
+    """The HIP collider stages at most five contacts per pair (plane-box pass, terrain replay); both libraries refuse a model asking for more."""
+    from go2_sim2real_locomotion_rl_amd.capi import Go2Sim, Go2SimError
+
+    m = load_model_json()
+    m["collider"]["n_contacts_per_pair"] = n
+    if n <= 5:
+        Go2Sim(oracle_lib, pack_model(m), 2)
+        return
+    with pytest.raises(Go2SimError):
+        Go2Sim(oracle_lib, pack_model(m), 2)
+
+
+@pytest.mark.gpu
+def test_contacts_per_pair_above_five_is_rejected_on_the_gpu(hip_lib):
+    from go2_sim2real_locomotion_rl_amd.capi import Go2Sim, Go2SimError
+
+    m = load_model_json()
+    m["collider"]["n_contacts_per_pair"] = 6
+    with pytest.raises(Go2SimError):
+        Go2Sim(hip_lib, pack_model(m), 2)

@@ -1,0 +1,136 @@
+"""Heightfield contacts on the HIP collider beyond the stair field: GPU vs the FAST ORDER oracle, tolerance 0.
+
+1. Scene steps on the fields of tests/test_terrain_ref.py (random heights with negative values, a ramp, single tall spikes next to the coarse maximum
+   map's blocks, a small field with the robot across its four borders).
+2. A field of more than 8192 rows with the robots above rows >= 8192: the prism descriptors of k_collide_team once kept the absolute row in 13 bits,
+   and a geom there read the prisms of row r mod 8192.
+3. A 1 mm field under robots lying on it: more eligible prisms than one chunk of descriptors holds (items_cap, the GJK scratch of the team), so
+   the terrain pass runs in several chunks; the oracle has no such limit.
+4. GO2SIM_COLLIDE_TEAM=16 / 32 / 64 give the same bits on a heightfield scene."""
+import numpy as np
+import pytest
+
+from go2_sim2real_locomotion_rl_amd.capi import Go2SimError
+from go2_sim2real_locomotion_rl_amd.model_blob import load_model_json, pack_model
+from test_parity_gpu import FIELDS as STATE_FIELDS
+from test_terrain_ref import FIELDS, STAND, draw_qpos, robot_geoms
+from terrain_ref import TerrainRef
+from util import CpuEnv, GpuEnv, F, bits_equal
+
+
+def run_pair(oracle_lib, hip_lib, field, q, steps, B, seed=2, contact_x=False):
+    """Scene steps on the oracle and the GPU from qpos `q` with random joint torques; every state field bit-equal after every step."""
+    blob = pack_model()
+    cpu, gpu = CpuEnv(oracle_lib, blob, B, seed=seed), GpuEnv(hip_lib, blob, B, seed=seed)
+    for e in (cpu, gpu):
+        e.sim.set_terrain(*field[:4])
+    rng = np.random.default_rng(seed)
+    v = (0.3 * rng.standard_normal((18, B))).astype(np.float32)
+    ctrl = np.zeros((18, B), np.float32); ctrl[6:] = 4.0 * rng.standard_normal((12, B))
+    for name, arr in (("F_QPOS", q.astype(np.float32)), ("F_VEL", v), ("F_CTRL_FORCE", ctrl)):
+        cpu.sim.set_field_np(F(name), arr); gpu.set_field(name, arr)
+    for e in (cpu, gpu):
+        e.sim.reset_caches(); e.sim.forward_kinematics()
+    total, xs = 0, []
+    for s in range(steps):
+        cpu.sim.scene_step(2); gpu.sim.scene_step(2)
+        for fn in STATE_FIELDS:
+            assert bits_equal(cpu.field(fn), gpu.field(fn)), f"scene step {s}: field {fn} differs"
+        nc, cg, cp = cpu.field("I_N_CONTACTS")[0], cpu.field("I_CONTACT_GEOMS"), cpu.field("F_CONTACT_POS").reshape(-1, 3, B)
+        total += int(nc.sum())
+        xs += [float(cp[c, 0, b]) - field[3][0] for b in range(B) for c in range(nc[b]) if cg[cp.shape[0] + c, b] == 0]   # heightfield contacts
+    assert cpu.sim.check_errno() == 0 and gpu.sim.check_errno() == 0
+    return (total, xs) if contact_x else total
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", [n for n in FIELDS if n != "stairs"])
+def test_fields_scene_step_bit_exact(oracle_lib, hip_lib, name):
+    B = 48
+    q = draw_qpos(load_model_json(), FIELDS[name], np.random.default_rng(5), B)
+    total = run_pair(oracle_lib, hip_lib, FIELDS[name], q, 20, B)
+    print(f"{name}: {total} contacts over 20 scene steps")
+    assert total > 20 * B
+
+
+def tall_field():
+    """8600 x 64 cells of 5 mm: a 0.3 m block over rows < 8192, low random bumps beyond (rows 8192 and up lie at x >= 40.96 m)."""
+    rng = np.random.default_rng(3)
+    hf = np.full((8600, 64), 60, np.int16)
+    hf[8192:] = rng.integers(0, 5, (8600 - 8192, 64))
+    return hf, 0.005, 0.005, (0.0, -0.16, 0.0)
+
+
+@pytest.mark.gpu
+def test_rows_beyond_8192(oracle_lib, hip_lib):
+    B = 16
+    field = tall_field()
+    q = np.tile(np.asarray(load_model_json()["qpos0"], np.float32)[:, None], (1, B))
+    rng = np.random.default_rng(4)
+    q[0] = rng.uniform(41.8, 41.9, B); q[1] = rng.uniform(-0.02, 0.02, B); q[2] = rng.uniform(0.26, 0.32, B)
+    q[7:] = (STAND[:, None] + 0.1 * rng.standard_normal((12, B))).astype(np.float32)
+    total, pos = run_pair(oracle_lib, hip_lib, field, q, 10, B, contact_x=True)
+    print(f"rows >= 8192: {total} contacts over 10 scene steps, contact x in [{min(pos):.3f}, {max(pos):.3f}] m")
+    assert total > 10 * B and min(pos) >= 8192 * field[1], "the contacts lie on rows >= 8192"
+
+
+def fine_field():
+    """A flat field of 1 mm cells, 900 x 900."""
+    return np.zeros((900, 900), np.int16), 0.001, 0.005, (-0.45, -0.45, 0.0)
+
+
+@pytest.mark.gpu
+def test_descriptors_beyond_one_chunk(oracle_lib, hip_lib):
+    """Go2 lying on its belly on a 1 mm field: ~155 k eligible prisms per env (the restatement's count), about twice what one chunk holds at the
+    default team of 16 lanes (items_cap = sizeof(GjkStoreFull) * 16 / 4, about 79 k)."""
+    B = 4
+    model = load_model_json()
+    field = fine_field()
+    q = np.tile(np.asarray(model["qpos0"], np.float32)[:, None], (1, B))
+    q[0] = [0.0, 0.01, -0.01, 0.02]; q[1] = [0.0, 0.01, 0.02, -0.01]; q[2] = 0.05
+    q[7:] = np.array([0.0, 0.0, 0.0, 0.0, 1.5, 1.5, 1.5, 1.5, -2.6, -2.6, -2.6, -2.6], np.float32)[:, None]
+    from go2_sim2real_locomotion_rl_amd.capi import Go2Sim, load_cpu_oracle_lib
+
+    probe = Go2Sim(load_cpu_oracle_lib(fast=True), pack_model(model), B, 0, 1)
+    probe.set_terrain(*field)
+    probe.set_field_np(F("F_QPOS"), q); probe.reset_caches(); probe.forward_kinematics()
+    lp, lq = probe.get_field_np(F("F_LINK_POS")).reshape(-1, 3, B), probe.get_field_np(F("F_LINK_QUAT")).reshape(-1, 4, B)
+    ref = TerrainRef(model, *field)
+    n_desc = [ref.eligible_total(lp[:, :, b].astype(np.float64), lq[:, :, b].astype(np.float64), robot_geoms(model)) for b in range(B)]
+    print(f"eligible prisms per env: {n_desc}")
+    assert min(n_desc) > 150000, n_desc
+    total = run_pair(oracle_lib, hip_lib, field, q, 3, B)
+    assert total > 0
+
+
+@pytest.mark.gpu
+def test_cell_size_with_too_many_prisms_per_pair_is_refused(hip_lib):
+    from go2_sim2real_locomotion_rl_amd.capi import Go2Sim
+
+    sim = Go2Sim(hip_lib, pack_model(), 1, 0, 1)
+    with pytest.raises(Go2SimError):
+        sim.set_terrain(np.zeros((64, 64), np.int16), 5e-5, 0.005, (0.0, 0.0, 0.0))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("team", ["32", "64"])
+def test_collide_team_bit_equal_on_heightfields(hip_lib, team, monkeypatch):
+    B = 64
+    blob = pack_model()
+    for name in ("random", "spikes"):
+        field = FIELDS[name]
+        q = draw_qpos(load_model_json(), field, np.random.default_rng(9), B)
+        monkeypatch.setenv("GO2SIM_COLLIDE_TEAM", team)
+        env_k = GpuEnv(hip_lib, blob, B, seed=3)
+        monkeypatch.delenv("GO2SIM_COLLIDE_TEAM")
+        env_d = GpuEnv(hip_lib, blob, B, seed=3)
+        for e in (env_k, env_d):
+            e.sim.set_terrain(*field[:4])
+            e.set_field("F_QPOS", q); e.set_field("F_VEL", np.zeros((18, B), np.float32))
+            e.sim.reset_caches(); e.sim.forward_kinematics()
+        for s in range(10):
+            env_k.sim.scene_step(2); env_d.sim.scene_step(2)
+            for fn in ("F_QPOS", "F_VEL", "F_CONTACT_POS", "F_CONTACT_PEN", "I_N_CONTACTS", "I_CONTACT_GEOMS"):
+                assert bits_equal(env_k.field(fn), env_d.field(fn)), f"team {team}, {name}, step {s}: {fn}"
+        assert int(env_d.field("I_N_CONTACTS").max()) > 0
+        assert env_k.sim.check_errno() == 0 and env_d.sim.check_errno() == 0
