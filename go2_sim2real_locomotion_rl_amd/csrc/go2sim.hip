@@ -6049,6 +6049,36 @@ __global__ void k_scatter(const void* __restrict__ src, void* __restrict__ dst, 
 enum { T_DYN = 0, T_COLLIDE, T_SOLVE, T_INTEGRATE, T_ENV_PRE, T_ENV_POST, T_MISC, T_TOTAL, T_N };
 constexpr int TIMING_RING = 2048;
 
+// One kernel launch of a step, as both executors need it (run_plain: hipLaunchKernel; step_graph_build: one kernel node)
+struct Launch {
+  void* func; dim3 grid, block;
+  int cat;                                        // timing class (T_DYN ... T_ENV_POST)
+  bool join;                                      // step graph: this node also waits for the node in front of its predecessor, which starts as a second root
+  std::vector<void*> args;                        // the stored argument values (add_launch)
+};
+struct LaunchList {
+  std::vector<Launch> v;
+  std::vector<void*> owned;                       // argument storage of all entries (malloc'ed)
+  // entries of an env step whose arguments change per step: actions pointer, step counter and ring index | step counter | step counter and the output
+  // pointers, so the caller may hand over fresh observation tensors per step (the reference allocates a new obs tensor each step, go2_env_walk.py:1084)
+  int pre = -1, post_a = -1, post_b = -1;
+  hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; std::vector<hipGraphNode_t> nodes;   // the list as a graph (node i = entry i)
+  LaunchList() = default;
+  LaunchList(const LaunchList&) = delete;
+  LaunchList& operator=(const LaunchList&) = delete;
+  ~LaunchList() { clear(); }
+  void drop_graph() {
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (graph) (void)hipGraphDestroy(graph);
+    exec = nullptr; graph = nullptr; nodes.clear();
+  }
+  void clear() {
+    drop_graph();
+    for (void* p : owned) free(p);
+    owned.clear(); v.clear(); pre = post_a = post_b = -1;
+  }
+};
+
 struct go2sim {
   int B = 0, device = 0;
   uint64_t seed = 0;
@@ -6066,21 +6096,10 @@ struct go2sim {
                                             // prism descriptors of the terrain pass: one block per (env, narrow-phase lane)
   SolverData<MAXR>* solver_ovf = nullptr;   // per-env global scratch for solves that do not fit in LDS (> RL rows)
   int* lpt = nullptr; int lpt_cap = 0; int lpt_parity = 0; bool use_lpt = true;   // heaviest-first dispatch records of the solver (two, alternating)
-  // One env step = 11 dependent kernel launches (12 with terrain).  Issued one by one they cost the host ~20 us each -- close to the GPU time of
-  // the step -- so the sequence is kept as an instantiated hipGraph: per step the three step-dependent kernel nodes get their new arguments
-  // (actions pointer, step counter, ring index) and the graph is launched with one call.  GO2SIM_NO_GRAPH=1 (or timing mode) uses plain launches.
-  struct StepGraph {
-    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-    hipGraphNode_t n_pre = nullptr, n_post_a = nullptr, n_post_b = nullptr;
-    hipGraphNode_t extra_dep = nullptr;             // graph_add_kernel: second parent of the next node (consumed by that call)
-    hipKernelNodeParams p_pre{}, p_post_a{}, p_post_b{};
-    std::vector<void*> owned;                       // argument storage of all nodes (malloc'ed)
-    const float** a_actions = nullptr; uint32_t* a_pre_step = nullptr; int* a_pre_widx = nullptr; uint32_t* a_pa_step = nullptr; uint32_t* a_pb_step = nullptr;
-    // output pointers of the step (k_env_post_b_team): rewritten every step like the step counter, so the caller may hand over fresh
-    // observation tensors per step (the reference allocates a new obs tensor each step, go2_env_walk.py:1084) without a graph rebuild
-    float** a_obs = nullptr; float** a_priv = nullptr; float** a_rew = nullptr; uint8_t** a_reset = nullptr; float** a_timeout = nullptr;
-    bool valid = false;
-  } sg;
+  // The kernel launches of one env step (which, and how many: build_launch_list), built once per configuration.  Issued one by one they cost the host
+  // ~20 us each -- close to the GPU time of the step -- so the list is also kept as an instantiated hipGraph: per step the three step-dependent
+  // entries get their new arguments (step_list_patch) and the graph is launched with one call.  GO2SIM_NO_GRAPH=1 (or timing mode) uses plain launches.
+  LaunchList step;
   bool use_graph = true;
   int graph_fallbacks = 0;                  // times the graph path was abandoned for plain launches (go2sim_graph_status)
   bool fuse_fk_dyn = true;                  // k_integrate_fk_dynamics_team between the substeps of a scene step (GO2SIM_NO_FUSE=1: separate launches)
@@ -6122,29 +6141,30 @@ struct ScopedTimer {
   ~ScopedTimer() { if (idx >= 0) (void)hipEventRecord(h->ev1[idx], s); }
 };
 
+// ---- team kernels: the instantiation for a runtime team size (lanes per environment) ---------------------------------------------------------
+static dim3 team_grid(const go2sim* h, int T) { return dim3((h->B + 64 / T - 1) / (64 / T)); }   // one wavefront per workgroup, 64 / T envs in it
+// (the kernels appear in the code object in the order in which these helpers name their instantiations)
+static auto fk_kernel(int T) { if (T == 16) return k_fk_team<16>; if (T == 32) return k_fk_team<32>; return k_fk_team<64>; }
+static auto pre_dynamics_kernel(int T) { return T == 32 ? k_pre_dynamics_team<32> : k_pre_dynamics_team<64>; }
+static auto dynamics_kernel(int T) { if (T == 16) return k_dynamics_team<16>; if (T == 32) return k_dynamics_team<32>; return k_dynamics_team<64>; }
+static auto collide_kernel(int T) { if (T == 16) return k_collide_team<16>; if (T == 32) return k_collide_team<32>; return k_collide_team<64>; }
+// flat ground: 32 lanes per env and 32 LDS rows; heightfield terrain (many more contacts): one env per wavefront with 96 LDS rows.
+// fuse_mode: 0 = the solve alone; 1 = + integrate / kinematics / next dynamics; 2 = + integrate / kinematics (last substep), both for teams of 32 only
+static auto solve_kernel(bool terrain, int T, int fuse_mode) {
+  if (terrain) return T == 32 ? k_constraint_solve_team<32, RL_TERRAIN> : k_constraint_solve_team<64, RL_TERRAIN>;
+  if (T == 16) return k_constraint_solve_team<16, RL>;
+  if (fuse_mode) return fuse_mode == 1 ? k_solve_integrate_team<32, RL, true> : k_solve_integrate_team<32, RL, false>;
+  return T == 32 ? k_constraint_solve_team<32, RL> : k_constraint_solve_team<64, RL>;
+}
+static auto integrate_kernel(int T) { if (T == 16) return k_integrate_fk_team<16>; if (T == 32) return k_integrate_fk_team<32>; return k_integrate_fk_team<64>; }
+static auto integrate_dynamics_kernel(int T) { return T == 32 ? k_integrate_fk_dynamics_team<32> : k_integrate_fk_dynamics_team<64>; }
+
 static void launch_fk_team(go2sim* h, hipStream_t s, int force_update_fixed, const int* cond) {
-  const int T = h->fk_team;
-  dim3 gd((h->B + 64 / T - 1) / (64 / T)), b(64);
-  if (T == 16) hipLaunchKernelGGL(k_fk_team<16>, gd, b, 0, s, h->P, h->dms, force_update_fixed, cond);
-  else if (T == 32) hipLaunchKernelGGL(k_fk_team<32>, gd, b, 0, s, h->P, h->dms, force_update_fixed, cond);
-  else hipLaunchKernelGGL(k_fk_team<64>, gd, b, 0, s, h->P, h->dms, force_update_fixed, cond);
+  hipLaunchKernelGGL(fk_kernel(h->fk_team), team_grid(h, h->fk_team), dim3(64), 0, s, h->P, h->dms, force_update_fixed, cond);
 }
 
-// `actions` != nullptr: the first dynamics launch of an env step, with the pre-physics part of the step in the same kernel (k_pre_dynamics_team)
+// the first dynamics launch of an env step carries the pre-physics part of the step (k_pre_dynamics_team)
 static bool fuse_pre(const go2sim* h) { return h->fuse_fk_dyn && h->dyn_team >= 32; }
-static void launch_dynamics(go2sim* h, hipStream_t s, const float* actions = nullptr) {
-  ScopedTimer t(h, s, T_DYN);
-  const int T = h->dyn_team;
-  dim3 gd((h->B + 64 / T - 1) / (64 / T)), b(WG);
-  if (actions) {
-    if (T == 32) hipLaunchKernelGGL(k_pre_dynamics_team<32>, gd, b, 0, s, h->P, h->dms, h->hcfg, h->dglob, actions, h->seed, h->step_count, h->action_write_idx);
-    else hipLaunchKernelGGL(k_pre_dynamics_team<64>, gd, b, 0, s, h->P, h->dms, h->hcfg, h->dglob, actions, h->seed, h->step_count, h->action_write_idx);
-    return;
-  }
-  if (T == 16) hipLaunchKernelGGL(k_dynamics_team<16>, gd, b, 0, s, h->P, h->dms);
-  else if (T == 32) hipLaunchKernelGGL(k_dynamics_team<32>, gd, b, 0, s, h->P, h->dms);
-  else hipLaunchKernelGGL(k_dynamics_team<64>, gd, b, 0, s, h->P, h->dms);
-}
 static int solver_epw(const go2sim* h) { return 64 / (h->hm.terrain_enabled ? h->terrain_solver_team : h->solver_team); }
 // heaviest-first dispatch where a solver wavefront holds one env.  On flat ground (two envs per solver wavefront, one residency round) the sorted order
 // measured 1-3 % SLOWER than the identity order, with single envs as well as with adjacent pairs as the sorted unit (the record lookup delays every
@@ -6154,202 +6174,122 @@ static size_t lpt_record_ints(const go2sim* h) { return (size_t)8 * LPT_CLS * (1
 // flat ground, 32-lane teams in solver and dynamics: the solve and the kinematics (+ next dynamics) that follow it share a launch (k_solve_integrate_team);
 // GO2SIM_NO_FUSE_SOLVE=1 keeps the two launches
 static bool fuse_solve(const go2sim* h) { return h->fuse_solve_int && h->fuse_fk_dyn && !h->hm.terrain_enabled && h->solver_team == 32 && h->dyn_team == 32; }
-// fuse_mode: 0 = the solve alone; 1 = + integrate / kinematics / next dynamics; 2 = + integrate / kinematics (last substep)
-static void launch_collide_solve(go2sim* h, hipStream_t s, int fuse_mode = 0) {
-  dim3 b(WG);
-  const bool lpt_on = lpt_enabled(h);
-  int* lpt_cur = lpt_on ? h->lpt + h->lpt_parity * lpt_record_ints(h) : nullptr;
-  int* lpt_next = lpt_on ? h->lpt + (1 - h->lpt_parity) * lpt_record_ints(h) : nullptr;
-  h->lpt_parity ^= 1;
-  const int epw_s = solver_epw(h);
-  {
-    ScopedTimer t(h, s, T_COLLIDE);
-    const int T = h->collide_team;
-    const int epw_c = 64 / T;
-    dim3 gc((h->B + epw_c - 1) / epw_c);
-    if (T == 16) hipLaunchKernelGGL(k_collide_team<16>, gc, b, 0, s, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s);
-    else if (T == 32) hipLaunchKernelGGL(k_collide_team<32>, gc, b, 0, s, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s);
-    else hipLaunchKernelGGL(k_collide_team<64>, gc, b, 0, s, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s);
-  }
-  {
-    ScopedTimer t(h, s, T_SOLVE);
-    // flat ground: 32 lanes per env and 32 LDS rows; heightfield terrain (many more contacts): one env per wavefront with 96 LDS rows
-    if (h->hm.terrain_enabled) {
-      if (h->terrain_solver_team == 32) hipLaunchKernelGGL((k_constraint_solve_team<32, RL_TERRAIN>), dim3((h->B + 1) / 2), b, 0, s, h->P, h->dm, h->dms, h->solver_ovf, (const int*)lpt_cur, lpt_next, h->lpt_cap);
-      else hipLaunchKernelGGL((k_constraint_solve_team<64, RL_TERRAIN>), dim3(h->B), b, 0, s, h->P, h->dm, h->dms, h->solver_ovf, (const int*)lpt_cur, lpt_next, h->lpt_cap);
-    } else {
-      const int T = h->solver_team;
-      dim3 gs((h->B + 64 / T - 1) / (64 / T));
-      if (T == 16) hipLaunchKernelGGL((k_constraint_solve_team<16, RL>), gs, b, 0, s, h->P, h->dm, h->dms, h->solver_ovf, (const int*)lpt_cur, lpt_next, h->lpt_cap);
-      else if (T == 32 && fuse_mode == 1) hipLaunchKernelGGL((k_solve_integrate_team<32, RL, true>), gs, b, 0, s, h->P, h->dm, h->dms, h->solver_ovf, (const int*)lpt_cur, lpt_next, h->lpt_cap);
-      else if (T == 32 && fuse_mode == 2) hipLaunchKernelGGL((k_solve_integrate_team<32, RL, false>), gs, b, 0, s, h->P, h->dm, h->dms, h->solver_ovf, (const int*)lpt_cur, lpt_next, h->lpt_cap);
-      else if (T == 32) hipLaunchKernelGGL((k_constraint_solve_team<32, RL>), gs, b, 0, s, h->P, h->dm, h->dms, h->solver_ovf, (const int*)lpt_cur, lpt_next, h->lpt_cap);
-      else hipLaunchKernelGGL((k_constraint_solve_team<64, RL>), gs, b, 0, s, h->P, h->dm, h->dms, h->solver_ovf, (const int*)lpt_cur, lpt_next, h->lpt_cap);
-    }
-  }
-}
-static void launch_integrate(go2sim* h, hipStream_t s) {
-  ScopedTimer t(h, s, T_INTEGRATE);
-  const int T = h->fk_team;
-  dim3 gd((h->B + 64 / T - 1) / (64 / T)), b(WG);
-  if (T == 16) hipLaunchKernelGGL(k_integrate_fk_team<16>, gd, b, 0, s, h->P, h->dms);
-  else if (T == 32) hipLaunchKernelGGL(k_integrate_fk_team<32>, gd, b, 0, s, h->P, h->dms);
-  else hipLaunchKernelGGL(k_integrate_fk_team<64>, gd, b, 0, s, h->P, h->dms);
-}
-// integrate + FK of one substep and the forward dynamics of the next one in a single launch (accounted with the integrate class)
-static void launch_integrate_dynamics(go2sim* h, hipStream_t s) {
-  ScopedTimer t(h, s, T_INTEGRATE);
-  const int T = h->dyn_team == 64 ? 64 : 32;
-  dim3 gd((h->B + 64 / T - 1) / (64 / T)), b(WG);
-  if (T == 32) hipLaunchKernelGGL(k_integrate_fk_dynamics_team<32>, gd, b, 0, s, h->P, h->dms);
-  else hipLaunchKernelGGL(k_integrate_fk_dynamics_team<64>, gd, b, 0, s, h->P, h->dms);
-}
-// n substeps of RigidSolver.substep (rigid_solver.py:1116-1184): dynamics | collide, solve | integrate+FK, where the integrate of substep i and the
-// dynamics of substep i + 1 share a launch
-static int launch_substeps(go2sim* h, hipStream_t s, int n, const float* pre_actions = nullptr) {
-  launch_dynamics(h, s, pre_actions);
-  for (int i = 0; i < n; ++i) {
-    if (fuse_solve(h)) { launch_collide_solve(h, s, i + 1 < n ? 1 : 2); continue; }
-    launch_collide_solve(h, s);
-    if (i + 1 < n && h->fuse_fk_dyn) launch_integrate_dynamics(h, s);
-    else { launch_integrate(h, s); if (i + 1 < n) launch_dynamics(h, s); }
-  }
-  return GO2SIM_E_OK;
-}
-static int launch_substep(go2sim* h, hipStream_t s) { return launch_substeps(h, s, 1); }
 
-// ---- hipGraph of one env step -----------------------------------------------------------------------------------------------------
-static void step_graph_destroy(go2sim* h) {
-  auto& g = h->sg;
-  if (g.exec) (void)hipGraphExecDestroy(g.exec);
-  if (g.graph) (void)hipGraphDestroy(g.graph);
-  for (void* p : g.owned) free(p);
-  g = go2sim::StepGraph();
-}
-// appends one kernel node after `last`; the argument values are copied into storage owned by the graph record, laid out with the kernel's
-// own parameter types (P...), and *slots receives the addresses of the stored arguments
+// ---- the launch list of a step ---------------------------------------------------------------------------------------------------------------
+// appends one launch; the argument values are copied into storage owned by the list, laid out with the kernel's own parameter types (P...)
 template <class... P, class... A>
-static bool graph_add_kernel(go2sim* h, hipGraphNode_t& last, void (*kernel)(P...), dim3 grid, dim3 block, hipGraphNode_t* node_out, hipKernelNodeParams* params_out,
-                             void*** slots, A... a) {
+static void add_launch(LaunchList& L, int cat, void (*kernel)(P...), dim3 grid, dim3 block, A... a) {
   static_assert(sizeof...(P) == sizeof...(A), "argument count");
-  auto& g = h->sg;
-  void** ptrs = (void**)malloc(sizeof(void*) * sizeof...(P));
-  g.owned.push_back(ptrs);
-  int i = 0;
-  auto store = [&](auto typed) { using T = decltype(typed); T* m = (T*)malloc(sizeof(T)); memcpy((void*)m, (const void*)&typed, sizeof(T)); g.owned.push_back((void*)m); ptrs[i++] = (void*)m; };
+  Launch e{(void*)kernel, grid, block, cat, false, {}};
+  auto store = [&](auto typed) { using T = decltype(typed); T* m = (T*)malloc(sizeof(T)); memcpy((void*)m, (const void*)&typed, sizeof(T)); L.owned.push_back((void*)m); e.args.push_back((void*)m); };
   (store(static_cast<P>(a)), ...);
-  hipKernelNodeParams kp{};
-  kp.func = (void*)kernel; kp.gridDim = grid; kp.blockDim = block; kp.sharedMemBytes = 0; kp.kernelParams = ptrs; kp.extra = nullptr;
-  hipGraphNode_t node = nullptr;
-  hipGraphNode_t deps[2] = {last, g.extra_dep};                       // (extra_dep: the second parent of a join node, set by the caller for one call)
-  const int n_deps = (last ? 1 : 0) + ((last && g.extra_dep) ? 1 : 0);
-  g.extra_dep = nullptr;
-  if (hipGraphAddKernelNode(&node, g.graph, n_deps ? deps : nullptr, n_deps, &kp) != hipSuccess) return false;
-  last = node;
-  if (node_out) *node_out = node;
-  if (params_out) *params_out = kp;
-  if (slots) *slots = ptrs;
-  return true;
+  L.v.push_back(std::move(e));
 }
-template <int T> struct TeamTag {};
-// the launch sequence of go2sim_env_step, as graph nodes (kept next to it: both must list the same kernels in the same order)
-static bool step_graph_build(go2sim* h, const float* actions, float* obs, float* priv, float* rew, uint8_t* reset, float* timeout) {
-  step_graph_destroy(h);
-  auto& g = h->sg;
-  if (hipGraphCreate(&g.graph, 0) != hipSuccess) return false;
-  hipGraphNode_t last = nullptr;
-  const dim3 ge = grid_for(h->B), be(WG), b64(64);
-  void** sl = nullptr;
-  auto team_grid = [&](int T) { return dim3((h->B + 64 / T - 1) / (64 / T)); };
-  // first node: the pre-physics part, alone (k_env_pre) or in front of the first dynamics (k_pre_dynamics_team); same per-step argument slots
-  bool ok;
-  if (!fuse_pre(h)) ok = graph_add_kernel(h, last, k_env_pre, ge, be, &g.n_pre, &g.p_pre, &sl, h->P, h->dm, h->hcfg, h->dglob, actions, h->seed, h->step_count, h->action_write_idx);
-  else if (h->dyn_team == 32) ok = graph_add_kernel(h, last, k_pre_dynamics_team<32>, team_grid(32), b64, &g.n_pre, &g.p_pre, &sl, h->P, h->dms, h->hcfg, h->dglob, actions, h->seed, h->step_count, h->action_write_idx);
-  else ok = graph_add_kernel(h, last, k_pre_dynamics_team<64>, team_grid(64), b64, &g.n_pre, &g.p_pre, &sl, h->P, h->dms, h->hcfg, h->dglob, actions, h->seed, h->step_count, h->action_write_idx);
-  if (!ok) return false;
-  g.a_actions = (const float**)sl[4]; g.a_pre_step = (uint32_t*)sl[6]; g.a_pre_widx = (int*)sl[7];
-  const int substeps = h->hcfg.i[GO2SIM_IC_SUBSTEPS];
-  auto add_dynamics = [&]() {
-    const int T = h->dyn_team; const dim3 gd = team_grid(T);
-    return T == 16 ? graph_add_kernel(h, last, k_dynamics_team<16>, gd, b64, nullptr, nullptr, nullptr, h->P, h->dms)
-         : T == 32 ? graph_add_kernel(h, last, k_dynamics_team<32>, gd, b64, nullptr, nullptr, nullptr, h->P, h->dms)
-                   : graph_add_kernel(h, last, k_dynamics_team<64>, gd, b64, nullptr, nullptr, nullptr, h->P, h->dms);
-  };
-  auto add_integrate = [&]() {
-    const int T = h->fk_team; const dim3 gd = team_grid(T);
-    return T == 16 ? graph_add_kernel(h, last, k_integrate_fk_team<16>, gd, b64, nullptr, nullptr, nullptr, h->P, h->dms)
-         : T == 32 ? graph_add_kernel(h, last, k_integrate_fk_team<32>, gd, b64, nullptr, nullptr, nullptr, h->P, h->dms)
-                   : graph_add_kernel(h, last, k_integrate_fk_team<64>, gd, b64, nullptr, nullptr, nullptr, h->P, h->dms);
-  };
-  auto add_integrate_dynamics = [&]() {
-    const int T = h->dyn_team == 64 ? 64 : 32; const dim3 gd = team_grid(T);
-    return T == 32 ? graph_add_kernel(h, last, k_integrate_fk_dynamics_team<32>, gd, b64, nullptr, nullptr, nullptr, h->P, h->dms)
-                   : graph_add_kernel(h, last, k_integrate_fk_dynamics_team<64>, gd, b64, nullptr, nullptr, nullptr, h->P, h->dms);
-  };
-  if (!fuse_pre(h)) ok = add_dynamics();
-  for (int i = 0; i < substeps && ok; ++i) {                               // same order as launch_substeps
-    // heaviest-first records: substep i uses record i & 1 and clears the other one (an odd substep count would leave record 0 uncleared: no records then)
-    const bool lpt_on = lpt_enabled(h) && (substeps % 2 == 0);
-    int* lpt_cur = lpt_on ? h->lpt + (i & 1) * lpt_record_ints(h) : nullptr;
-    int* lpt_next = lpt_on ? h->lpt + (1 - (i & 1)) * lpt_record_ints(h) : nullptr;
-    const int epw_s = solver_epw(h);
+struct StepIO { const float* actions; float *obs, *priv, *rew; uint8_t* reset; float* timeout; };   // what go2sim_env_step is handed per step
+// n substeps of RigidSolver.substep (rigid_solver.py:1116-1184): dynamics | collide, solve | integrate+FK, where the integrate of substep i and the
+// dynamics of substep i + 1 share a launch.  With `io` the list is the whole env step: the pre-physics part in front (alone, k_env_pre, or inside the
+// first dynamics launch), the post-physics launches behind.  This is the one place that says which kernels a step runs, in which shape and order.
+static void build_launch_list(const go2sim* h, LaunchList& L, int n, const StepIO* io) {
+  const dim3 ge = grid_for(h->B), b(WG);
+  const bool terrain = h->hm.terrain_enabled != 0;
+  auto add_dynamics = [&]() { add_launch(L, T_DYN, dynamics_kernel(h->dyn_team), team_grid(h, h->dyn_team), b, h->P, h->dms); };
+  if (io) L.pre = 0;
+  if (io && fuse_pre(h)) {
+    add_launch(L, T_DYN, pre_dynamics_kernel(h->dyn_team), team_grid(h, h->dyn_team), b, h->P, h->dms, h->hcfg, h->dglob, io->actions, h->seed, h->step_count, h->action_write_idx);
+  } else {
+    if (io) add_launch(L, T_ENV_PRE, k_env_pre, ge, b, h->P, h->dm, h->hcfg, h->dglob, io->actions, h->seed, h->step_count, h->action_write_idx);
+    add_dynamics();
+  }
+  // heaviest-first records: a substep files and reads one record and clears the other one for the next substep.  The env step's list is built once and
+  // starts at record 0 (an odd substep count would leave record 0 uncleared: no records then); a list built per call continues from h->lpt_parity.
+  const bool lpt_on = lpt_enabled(h) && !(io && n % 2);
+  const int lpt0 = io ? 0 : h->lpt_parity;
+  for (int i = 0; i < n; ++i) {
+    const bool more = i + 1 < n;
+    int* lpt_cur = lpt_on ? h->lpt + ((lpt0 + i) & 1) * lpt_record_ints(h) : nullptr;
+    int* lpt_next = lpt_on ? h->lpt + ((lpt0 + i + 1) & 1) * lpt_record_ints(h) : nullptr;
+    add_launch(L, T_COLLIDE, collide_kernel(h->collide_team), team_grid(h, h->collide_team), b, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, solver_epw(h));
+    const int Ts = terrain ? h->terrain_solver_team : h->solver_team;
+    add_launch(L, T_SOLVE, solve_kernel(terrain, Ts, fuse_solve(h) ? (more ? 1 : 2) : 0), team_grid(h, Ts), b, h->P, h->dm, h->dms, h->solver_ovf, lpt_cur, lpt_next, h->lpt_cap);
     // The first collision pass reads nothing the pre-physics / dynamics launch writes (geom poses, sort buffers and the normal cache come from the end of the
-    // previous step): it is a second ROOT of the graph, and the first solve joins the two.  The collision launch is as long as its slowest workgroup
+    // previous step): it can be a second ROOT of the graph, and the first solve joins the two.  The collision launch is as long as its slowest workgroup
     // (landing window: mean 42 us, span 66 us, one wave per SIMD with the whole register file); the dynamics wavefronts take the SIMDs its early finishers
     // leave.  Tried and measured slower: off unless GO2SIM_PAR_PRE=1 (go2sim::par_pre).
-    hipGraphNode_t pre_node = nullptr;
-    if (i == 0 && fuse_pre(h) && h->par_pre) { pre_node = last; last = nullptr; }
-    { const int T = h->collide_team; const int epw_c = 64 / T; const dim3 gc((h->B + epw_c - 1) / epw_c);
-      ok = T == 16 ? graph_add_kernel(h, last, k_collide_team<16>, gc, b64, nullptr, nullptr, nullptr, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s)
-         : T == 32 ? graph_add_kernel(h, last, k_collide_team<32>, gc, b64, nullptr, nullptr, nullptr, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s)
-                   : graph_add_kernel(h, last, k_collide_team<64>, gc, b64, nullptr, nullptr, nullptr, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, epw_s); }
-    if (!ok) break;
-    g.extra_dep = pre_node;                                            // the solve waits for the collision pass AND (first substep) for the dynamics
-    if (h->hm.terrain_enabled) {
-      if (h->terrain_solver_team == 32) ok = graph_add_kernel(h, last, k_constraint_solve_team<32, RL_TERRAIN>, dim3((h->B + 1) / 2), b64, nullptr, nullptr, nullptr, h->P, h->dm, h->dms, h->solver_ovf, (const int*)lpt_cur, lpt_next, h->lpt_cap);
-      else ok = graph_add_kernel(h, last, k_constraint_solve_team<64, RL_TERRAIN>, dim3(h->B), b64, nullptr, nullptr, nullptr, h->P, h->dm, h->dms, h->solver_ovf, (const int*)lpt_cur, lpt_next, h->lpt_cap);
+    L.v.back().join = io && i == 0 && fuse_pre(h) && h->par_pre;
+    if (fuse_solve(h)) continue;
+    if (more && h->fuse_fk_dyn) {                 // (accounted with the integrate class)
+      const int Td = h->dyn_team == 64 ? 64 : 32;
+      add_launch(L, T_INTEGRATE, integrate_dynamics_kernel(Td), team_grid(h, Td), b, h->P, h->dms);
     } else {
-      const int T = h->solver_team; const dim3 gs = team_grid(T);
-      if (fuse_solve(h)) {                                               // solve + integrate / kinematics (+ next dynamics) in one launch
-        ok = (i + 1 < substeps) ? graph_add_kernel(h, last, k_solve_integrate_team<32, RL, true>, gs, b64, nullptr, nullptr, nullptr, h->P, h->dm, h->dms, h->solver_ovf, (const int*)lpt_cur, lpt_next, h->lpt_cap)
-                                : graph_add_kernel(h, last, k_solve_integrate_team<32, RL, false>, gs, b64, nullptr, nullptr, nullptr, h->P, h->dm, h->dms, h->solver_ovf, (const int*)lpt_cur, lpt_next, h->lpt_cap);
-        if (!ok) break;
-        continue;
-      }
-      ok = T == 16 ? graph_add_kernel(h, last, k_constraint_solve_team<16, RL>, gs, b64, nullptr, nullptr, nullptr, h->P, h->dm, h->dms, h->solver_ovf, (const int*)lpt_cur, lpt_next, h->lpt_cap)
-         : T == 32 ? graph_add_kernel(h, last, k_constraint_solve_team<32, RL>, gs, b64, nullptr, nullptr, nullptr, h->P, h->dm, h->dms, h->solver_ovf, (const int*)lpt_cur, lpt_next, h->lpt_cap)
-                   : graph_add_kernel(h, last, k_constraint_solve_team<64, RL>, gs, b64, nullptr, nullptr, nullptr, h->P, h->dm, h->dms, h->solver_ovf, (const int*)lpt_cur, lpt_next, h->lpt_cap);
+      add_launch(L, T_INTEGRATE, integrate_kernel(h->fk_team), team_grid(h, h->fk_team), b, h->P, h->dms);
+      if (more) add_dynamics();
     }
-    if (!ok) break;
-    if (i + 1 < substeps && h->fuse_fk_dyn) ok = add_integrate_dynamics();
-    else { ok = add_integrate(); if (ok && i + 1 < substeps) ok = add_dynamics(); }
   }
-  if (!ok) return false;
-  ok = graph_add_kernel(h, last, k_env_post_a, ge, dim3(WG * POST_A_NWAVES), &g.n_post_a, &g.p_post_a, &sl, h->P, h->dm, h->hcfg, h->dglob, h->dacc, h->seed, h->step_count);
-  if (!ok) return false;
-  g.a_pa_step = (uint32_t*)sl[6];
-  if (h->hcfg.i[GO2SIM_IC_USE_TERRAIN]) {
-    ok = graph_add_kernel(h, last, k_env_terrain_rows, dim3((h->B + 255) / 256), dim3(256), nullptr, nullptr, nullptr, h->P, h->dcfg, h->dglob, h->seed);
-    if (!ok) return false;
+  if (!io) return;
+  L.post_a = (int)L.v.size();
+  add_launch(L, T_ENV_POST, k_env_post_a, ge, dim3(WG * POST_A_NWAVES), h->P, h->dm, h->hcfg, h->dglob, h->dacc, h->seed, h->step_count);
+  if (h->hcfg.i[GO2SIM_IC_USE_TERRAIN]) add_launch(L, T_ENV_POST, k_env_terrain_rows, dim3((h->B + 255) / 256), dim3(256), h->P, h->dcfg, h->dglob, h->seed);
+  L.post_b = (int)L.v.size();
+  add_launch(L, T_ENV_POST, k_env_post_b_team<16>, dim3((h->B + 3) / 4), dim3(128), h->P, h->dm, h->dms, h->dcfg, h->dglob, h->seed, h->step_count, io->obs, io->priv, io->rew, io->reset, io->timeout);
+  if (h->hcfg.i[GO2SIM_IC_ENGINE_BATCH_GAIN]) add_launch(L, T_ENV_POST, k_env_engine_gains, dim3(1), dim3(GAIN_WG), h->P, h->dm, h->dms, h->dcfg, h->dglob);
+}
+// the per-step arguments of the env step's list (argument positions: k_env_pre / k_pre_dynamics_team, k_env_post_a, k_env_post_b_team)
+template <class T> static void set_arg(Launch& e, int k, T value) { *(T*)e.args[k] = value; }
+static void step_list_patch(go2sim* h, const StepIO& io) {
+  Launch &pre = h->step.v[h->step.pre], &pa = h->step.v[h->step.post_a], &pb = h->step.v[h->step.post_b];
+  set_arg(pre, 4, io.actions); set_arg(pre, 6, h->step_count); set_arg(pre, 7, h->action_write_idx);
+  set_arg(pa, 6, h->step_count);
+  set_arg(pb, 6, h->step_count); set_arg(pb, 7, io.obs); set_arg(pb, 8, io.priv); set_arg(pb, 9, io.rew); set_arg(pb, 10, io.reset); set_arg(pb, 11, io.timeout);
+}
+
+// executor 1: plain launches.  Consecutive entries of one timing class are one timed scope
+static void run_plain(go2sim* h, hipStream_t s, const LaunchList& L) {
+  for (size_t i = 0; i < L.v.size();) {
+    const int cat = L.v[i].cat;
+    ScopedTimer t(h, s, cat);
+    for (; i < L.v.size() && L.v[i].cat == cat; ++i) (void)hipLaunchKernel(L.v[i].func, L.v[i].grid, L.v[i].block, (void**)L.v[i].args.data(), 0, s);
   }
-  ok = graph_add_kernel(h, last, k_env_post_b_team<16>, dim3((h->B + 3) / 4), dim3(128), &g.n_post_b, &g.p_post_b, &sl, h->P, h->dm, h->dms, h->dcfg, h->dglob, h->seed, h->step_count,
-                        obs, priv, rew, reset, timeout);
-  if (!ok) return false;
-  g.a_pb_step = (uint32_t*)sl[6];
-  g.a_obs = (float**)sl[7]; g.a_priv = (float**)sl[8]; g.a_rew = (float**)sl[9]; g.a_reset = (uint8_t**)sl[10]; g.a_timeout = (float**)sl[11];
-  if (h->hcfg.i[GO2SIM_IC_ENGINE_BATCH_GAIN] &&
-      !graph_add_kernel(h, last, k_env_engine_gains, dim3(1), dim3(GAIN_WG), nullptr, nullptr, nullptr, h->P, h->dm, h->dms, h->dcfg, h->dglob))
-    return false;
-  if (hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0) != hipSuccess) return false;
-  g.valid = true;
-  return true;
+}
+static void run_substeps(go2sim* h, hipStream_t s, int n) {
+  LaunchList L;
+  build_launch_list(h, L, n, nullptr);
+  run_plain(h, s, L);
+  h->lpt_parity ^= n & 1;
+}
+
+// executor 2: the list as an explicitly built hipGraph, a chain in list order (but see Launch::join)
+static hipKernelNodeParams node_params(const Launch& e) {
+  hipKernelNodeParams kp{};
+  kp.func = e.func; kp.gridDim = e.grid; kp.blockDim = e.block; kp.sharedMemBytes = 0; kp.kernelParams = (void**)e.args.data(); kp.extra = nullptr;
+  return kp;
+}
+static bool step_graph_build(LaunchList& L) {
+  if (hipGraphCreate(&L.graph, 0) != hipSuccess) return false;
+  L.nodes.assign(L.v.size(), nullptr);
+  hipGraphNode_t last = nullptr, side = nullptr;
+  for (size_t i = 0; i < L.v.size(); ++i) {
+    if (i + 1 < L.v.size() && L.v[i + 1].join) { side = last; last = nullptr; }
+    hipGraphNode_t deps[2] = {last, L.v[i].join ? side : nullptr};
+    const int n_deps = (last ? 1 : 0) + ((last && deps[1]) ? 1 : 0);
+    const hipKernelNodeParams kp = node_params(L.v[i]);
+    if (hipGraphAddKernelNode(&L.nodes[i], L.graph, n_deps ? deps : nullptr, n_deps, &kp) != hipSuccess) return false;
+    last = L.nodes[i];
+  }
+  return hipGraphInstantiate(&L.exec, L.graph, nullptr, nullptr, 0) == hipSuccess;
+}
+static bool step_graph_launch(LaunchList& L, hipStream_t s) {
+  for (int i : {L.pre, L.post_a, L.post_b}) {
+    const hipKernelNodeParams kp = node_params(L.v[i]);
+    if (hipGraphExecKernelNodeSetParams(L.exec, L.nodes[i], &kp) != hipSuccess) return false;
+  }
+  return hipGraphLaunch(L.exec, s) == hipSuccess;
 }
 
 extern "C" {
 
 // releases everything a handle owns (hipFree(nullptr) is a no-op): shared by go2sim_destroy and the error paths of go2sim_create
 static void handle_release(go2sim* h) {
-  step_graph_destroy(h);
+  h->step.clear();
   if (h->ev_created) for (int i = 0; i < TIMING_RING; ++i) { (void)hipEventDestroy(h->ev0[i]); (void)hipEventDestroy(h->ev1[i]); }
   (void)hipFree(h->P.f); (void)hipFree(h->P.i); (void)hipFree(h->P.fa); (void)hipFree(h->P.ia); (void)hipFree(h->dm); (void)hipFree(h->dcfg);
   (void)hipFree(h->dglob); (void)hipFree(h->dacc); (void)hipFree(h->derr); (void)hipFree(h->solver_ovf); (void)hipFree(h->gjk_scratch); (void)hipFree(h->lpt);
@@ -6357,6 +6297,22 @@ static void handle_release(go2sim* h) {
   if (h->herr_pinned) (void)hipHostFree(h->herr_pinned);
   if (h->ev_errno) (void)hipEventDestroy(h->ev_errno);
   delete h;
+}
+
+// the GO2SIM_* environment knobs of a handle (README.md); an unset or unaccepted value leaves the default
+static int env_int(const char* name, int unset) { const char* t = getenv(name); return t ? atoi(t) : unset; }
+static void read_knobs(go2sim* h) {
+  auto team = [](const char* name, int smallest, int* v) { const int t = env_int(name, *v); if ((t == 16 && smallest == 16) || t == 32 || t == 64) *v = t; };
+  team("GO2SIM_DYN_TEAM", 16, &h->dyn_team);
+  team("GO2SIM_FK_TEAM", 16, &h->fk_team);
+  team("GO2SIM_COLLIDE_TEAM", 16, &h->collide_team);
+  team("GO2SIM_SOLVER_TEAM", 16, &h->solver_team);
+  team("GO2SIM_TERRAIN_SOLVER_TEAM", 32, &h->terrain_solver_team);
+  if (env_int("GO2SIM_NO_GRAPH", 0)) h->use_graph = false;
+  if (env_int("GO2SIM_NO_FUSE", 0)) h->fuse_fk_dyn = false;
+  if (env_int("GO2SIM_NO_FUSE_SOLVE", 0)) h->fuse_solve_int = false;
+  if (env_int("GO2SIM_PAR_PRE", 0)) h->par_pre = true;
+  if (env_int("GO2SIM_NO_LPT", 0)) h->use_lpt = false;
 }
 
 int go2sim_create(const void* blob, size_t nbytes, int n_envs, int device, uint64_t seed, go2sim_t** out) {
@@ -6401,17 +6357,8 @@ int go2sim_create(const void* blob, size_t nbytes, int n_envs, int device, uint6
     h->herr_pinned[0] = h->herr_pinned[1] = 0;
     CK(hipEventCreateWithFlags(&h->ev_errno, hipEventDisableTiming));
     CK(hipMalloc((void**)&h->solver_ovf, (size_t)n_envs * sizeof(SolverData<MAXR>)));
-    if (const char* t = getenv("GO2SIM_DYN_TEAM")) { int v = atoi(t); if (v == 16 || v == 32 || v == 64) h->dyn_team = v; }
-    if (const char* t = getenv("GO2SIM_NO_GRAPH")) { if (atoi(t) != 0) h->use_graph = false; }
-    if (const char* t = getenv("GO2SIM_NO_FUSE")) { if (atoi(t) != 0) h->fuse_fk_dyn = false; }
-    if (const char* t = getenv("GO2SIM_PAR_PRE")) { if (atoi(t) != 0) h->par_pre = true; }
-    if (const char* t = getenv("GO2SIM_NO_FUSE_SOLVE")) { if (atoi(t) != 0) h->fuse_solve_int = false; }
-    if (const char* t = getenv("GO2SIM_FK_TEAM")) { int v = atoi(t); if (v == 16 || v == 32 || v == 64) h->fk_team = v; }
-    if (const char* t = getenv("GO2SIM_COLLIDE_TEAM")) { int v = atoi(t); if (v == 16 || v == 32 || v == 64) h->collide_team = v; }
-    CK(hipMalloc((void**)&h->gjk_scratch, (size_t)n_envs * h->collide_team * sizeof(GjkStoreFull)));   // ~20 KB per narrow-phase lane
-    if (const char* t = getenv("GO2SIM_SOLVER_TEAM")) { int v = atoi(t); if (v == 16 || v == 32 || v == 64) h->solver_team = v; }
-    if (const char* t = getenv("GO2SIM_TERRAIN_SOLVER_TEAM")) { int v = atoi(t); if (v == 32 || v == 64) h->terrain_solver_team = v; }
-    if (const char* t = getenv("GO2SIM_NO_LPT")) { if (atoi(t) != 0) h->use_lpt = false; }
+    read_knobs(h);
+    CK(hipMalloc((void**)&h->gjk_scratch, (size_t)n_envs * h->collide_team * sizeof(GjkStoreFull)));   // ~20 KB per narrow-phase lane (after GO2SIM_COLLIDE_TEAM)
     h->lpt_cap = n_envs / 8 + 72;
     CK(hipMalloc((void**)&h->lpt, 2 * lpt_record_ints(h) * sizeof(int)));
     CK(hipMemset(h->lpt, 0, 2 * lpt_record_ints(h) * sizeof(int)));
@@ -6453,14 +6400,14 @@ int go2sim_scene_reset(go2sim_t* h, void* stream) {
 }
 int go2sim_substep(go2sim_t* h, void* stream) {
   if (!h) return GO2SIM_E_BADARG;
-  launch_substep(h, (hipStream_t)stream);
+  run_substeps(h, (hipStream_t)stream, 1);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;
 }
 int go2sim_scene_step(go2sim_t* h, int substeps, void* stream) {
   if (!h || substeps <= 0) return GO2SIM_E_BADARG;
   hipStream_t s = (hipStream_t)stream;
-  launch_substeps(h, s, substeps);
+  run_substeps(h, s, substeps);
   { ScopedTimer t(h, s, T_MISC); hipLaunchKernelGGL(k_clear_ext, grid_for(h->B), dim3(WG), 0, s, h->P); }
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;
@@ -6598,7 +6545,7 @@ int go2sim_set_terrain(go2sim_t* h, const int16_t* hf, int rows, int cols, float
   if (!terrain_cells_fit(h->hm, horizontal_scale)) return GO2SIM_E_BADARG;
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(hipStreamSynchronize(s));
-  step_graph_destroy(h);   // the solver kernel of the step graph depends on the terrain flag
+  h->step.clear();         // the solver kernel of the env step's list depends on the terrain flag
   Model& m = h->hm;
   std::vector<float> hfm((size_t)rows * cols);
   float hmax = -1e30f, hmin = 1e30f;
@@ -6667,7 +6614,7 @@ int go2sim_env_configure(go2sim_t* h, const double* f, int nf, const int* i, int
     for (int k = 0; k < c.i[GO2SIM_IC_N_REWARDS]; ++k) { int id = c.i[GO2SIM_IC_REWARD_ID0 + k]; if (id < 0 || id >= GO2SIM_R_COUNT) return GO2SIM_E_BADARG; }
     if (c.i[GO2SIM_IC_ENGINE_BATCH_GAIN] && (c.i[GO2SIM_IC_ENV_KIND] != 0 || c.i[GO2SIM_IC_MANUAL_PD] || c.i[GO2SIM_IC_SHARED_GLOBALS] || P_B_MAX_GAIN < h->B))
       return GO2SIM_E_BADARG;                                             // (one batch gain: not sharded; k_env_engine_gains: exact float64 sum up to 2^23 / 12 envs)
-    step_graph_destroy(h);   // the configuration is baked into the kernel arguments of the step graph
+    h->step.clear();         // the configuration is baked into the kernel arguments of the env step's list
     h->hcfg = c;
   }
   const DCfg& c = h->hcfg;
@@ -6698,61 +6645,47 @@ int go2sim_env_configure(go2sim_t* h, const double* f, int nf, const int* i, int
 int go2sim_env_step(go2sim_t* h, const float* actions, float* obs, float* priv, float* rew, uint8_t* reset, float* timeout, void* stream) {
   if (!h || !h->cfg_set || !actions) return GO2SIM_E_BADARG;
   hipStream_t s = (hipStream_t)stream;
-  dim3 g = grid_for(h->B), b(WG);
+  LaunchList& L = h->step;
+  const StepIO io{actions, obs, priv, rew, reset, timeout};
+  if (L.v.empty()) build_launch_list(h, L, h->hcfg.i[GO2SIM_IC_SUBSTEPS], &io);
+  step_list_patch(h, io);
+  bool launched = false;
   if (h->use_graph && !h->timing) {
-    auto& sg = h->sg;
-    if (!sg.valid) {
-      if (!step_graph_build(h, actions, obs, priv, rew, reset, timeout)) {
-        (void)hipGetLastError();
-        fprintf(stderr, "go2sim: hipGraph build failed, falling back to plain kernel launches\n");
-        step_graph_destroy(h); h->use_graph = false; h->graph_fallbacks += 1;
-      }
+    const char* failed = (!L.exec && !step_graph_build(L)) ? "build" : !step_graph_launch(L, s) ? "launch" : nullptr;
+    if (failed) {                           // nothing of this step was enqueued: drop the graph and continue with plain launches
+      (void)hipGetLastError();
+      fprintf(stderr, "go2sim: hipGraph %s failed, falling back to plain kernel launches\n", failed);
+      L.drop_graph(); h->use_graph = false; h->graph_fallbacks += 1;
     }
-    if (h->use_graph) {
-      *sg.a_actions = actions; *sg.a_pre_step = h->step_count; *sg.a_pre_widx = h->action_write_idx; *sg.a_pa_step = h->step_count; *sg.a_pb_step = h->step_count;
-      *sg.a_obs = obs; *sg.a_priv = priv; *sg.a_rew = rew; *sg.a_reset = reset; *sg.a_timeout = timeout;
-      const bool launched = hipGraphExecKernelNodeSetParams(sg.exec, sg.n_pre, &sg.p_pre) == hipSuccess &&
-                            hipGraphExecKernelNodeSetParams(sg.exec, sg.n_post_a, &sg.p_post_a) == hipSuccess &&
-                            hipGraphExecKernelNodeSetParams(sg.exec, sg.n_post_b, &sg.p_post_b) == hipSuccess && hipGraphLaunch(sg.exec, s) == hipSuccess;
-      if (launched) {
-        h->action_write_idx = (h->action_write_idx + 1) % (h->hcfg.i[GO2SIM_IC_MAX_DELAY] + 1);
-        h->step_count += 1;
-        h->lpt_parity = 0;                // (the graph leaves record 0 cleared)
-        return GO2SIM_E_OK;
-      }
-      (void)hipGetLastError();            // nothing of this step was enqueued: drop the graph and continue with plain launches
-      fprintf(stderr, "go2sim: hipGraph launch failed, falling back to plain kernel launches\n");
-      step_graph_destroy(h); h->use_graph = false; h->graph_fallbacks += 1;
-    }
+    launched = !failed;
   }
-  if (h->timing && h->ev_n + 64 > TIMING_RING) timing_flush(h);   // all pending events belong to completed launches
-  ScopedTimer total(h, s, T_TOTAL);
-  if (!fuse_pre(h)) { ScopedTimer t(h, s, T_ENV_PRE); hipLaunchKernelGGL(k_env_pre, g, b, 0, s, h->P, h->dm, h->hcfg, h->dglob, actions, h->seed, h->step_count, h->action_write_idx); }
-  launch_substeps(h, s, h->hcfg.i[GO2SIM_IC_SUBSTEPS], fuse_pre(h) ? actions : nullptr);
-  {
-    ScopedTimer t(h, s, T_ENV_POST);
-    hipLaunchKernelGGL(k_env_post_a, g, dim3(WG * POST_A_NWAVES), 0, s, h->P, h->dm, h->hcfg, h->dglob, h->dacc, h->seed, h->step_count);
-    if (h->hcfg.i[GO2SIM_IC_USE_TERRAIN]) hipLaunchKernelGGL(k_env_terrain_rows, dim3((h->B + 255) / 256), dim3(256), 0, s, h->P, h->dcfg, h->dglob, h->seed);
-    hipLaunchKernelGGL(k_env_post_b_team<16>, dim3((h->B + 3) / 4), dim3(128), 0, s, h->P, h->dm, h->dms, h->dcfg, h->dglob, h->seed, h->step_count, obs, priv, rew, reset, timeout);
-    if (h->hcfg.i[GO2SIM_IC_ENGINE_BATCH_GAIN]) hipLaunchKernelGGL(k_env_engine_gains, dim3(1), dim3(GAIN_WG), 0, s, h->P, h->dm, h->dms, h->dcfg, h->dglob);
+  if (!launched) {
+    if (h->timing && h->ev_n + 64 > TIMING_RING) timing_flush(h);   // all pending events belong to completed launches
+    ScopedTimer total(h, s, T_TOTAL);
+    run_plain(h, s, L);
+    HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipGetLastError());
   h->action_write_idx = (h->action_write_idx + 1) % (h->hcfg.i[GO2SIM_IC_MAX_DELAY] + 1);
   h->step_count += 1;
+  h->lpt_parity = 0;                        // (an env step leaves record 0 cleared)
   return GO2SIM_E_OK;
 }
-int go2sim_env_reset(go2sim_t* h, void* stream) {
-  if (!h || !h->cfg_set) return GO2SIM_E_BADARG;
-  hipStream_t s = (hipStream_t)stream;
-  dim3 g = grid_for(h->B), b(WG);
-  ScopedTimer t(h, s, T_MISC);
-  HIPCHK(hipMemsetAsync(h->dacc, 0, sizeof(Acc), s));
-  hipLaunchKernelGGL(k_env_mark_all, g, b, 0, s, h->P, h->dcfg, h->dacc);
+// what go2sim_env_reset and go2sim_env_reset_idx share after their marking kernels
+static void launch_reset_marked(go2sim* h, hipStream_t s) {
+  const dim3 g = grid_for(h->B), b(WG);
   hipLaunchKernelGGL(k_env_globals, dim3(1), dim3(1), 0, s, h->dcfg, h->dglob, h->dacc, h->seed, 0);
   if (h->hcfg.i[GO2SIM_IC_USE_TERRAIN]) hipLaunchKernelGGL(k_env_terrain_rows, dim3((h->B + 255) / 256), dim3(256), 0, s, h->P, h->dcfg, h->dglob, h->seed);
   hipLaunchKernelGGL(k_env_reset_tail, g, b, 0, s, h->P, h->dm, h->dcfg, h->dglob, h->seed);
   if (h->hcfg.i[GO2SIM_IC_ENGINE_BATCH_GAIN]) hipLaunchKernelGGL(k_env_engine_gains, dim3(1), dim3(GAIN_WG), 0, s, h->P, h->dm, h->dms, h->dcfg, h->dglob);
   launch_fk_team(h, s, 1, &h->dglob->n_reset_now);
+}
+int go2sim_env_reset(go2sim_t* h, void* stream) {
+  if (!h || !h->cfg_set) return GO2SIM_E_BADARG;
+  hipStream_t s = (hipStream_t)stream;
+  ScopedTimer t(h, s, T_MISC);
+  HIPCHK(hipMemsetAsync(h->dacc, 0, sizeof(Acc), s));
+  hipLaunchKernelGGL(k_env_mark_all, grid_for(h->B), dim3(WG), 0, s, h->P, h->dcfg, h->dacc);
+  launch_reset_marked(h, s);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;
 }
@@ -6760,16 +6693,11 @@ int go2sim_env_reset_idx(go2sim_t* h, const int* envs_idx, int n_sel, void* stre
   if (!h || !h->cfg_set || (n_sel > 0 && !envs_idx) || n_sel < 0) return GO2SIM_E_BADARG;
   if (n_sel == 0) return GO2SIM_E_OK;                                  // `if len(envs_idx) == 0: return`, go2_env_walk.py:1157
   hipStream_t s = (hipStream_t)stream;
-  dim3 g = grid_for(h->B), b(WG);
   ScopedTimer t(h, s, T_MISC);
   HIPCHK(hipMemsetAsync(h->dacc, 0, sizeof(Acc), s));
-  hipLaunchKernelGGL(k_env_unmark_all, g, b, 0, s, h->P);
-  hipLaunchKernelGGL(k_env_mark_idx, grid_for(n_sel), b, 0, s, h->P, h->dcfg, h->dacc, envs_idx, n_sel);
-  hipLaunchKernelGGL(k_env_globals, dim3(1), dim3(1), 0, s, h->dcfg, h->dglob, h->dacc, h->seed, 0);
-  if (h->hcfg.i[GO2SIM_IC_USE_TERRAIN]) hipLaunchKernelGGL(k_env_terrain_rows, dim3((h->B + 255) / 256), dim3(256), 0, s, h->P, h->dcfg, h->dglob, h->seed);
-  hipLaunchKernelGGL(k_env_reset_tail, g, b, 0, s, h->P, h->dm, h->dcfg, h->dglob, h->seed);
-  if (h->hcfg.i[GO2SIM_IC_ENGINE_BATCH_GAIN]) hipLaunchKernelGGL(k_env_engine_gains, dim3(1), dim3(GAIN_WG), 0, s, h->P, h->dm, h->dms, h->dcfg, h->dglob);
-  launch_fk_team(h, s, 1, &h->dglob->n_reset_now);
+  hipLaunchKernelGGL(k_env_unmark_all, grid_for(h->B), dim3(WG), 0, s, h->P);
+  hipLaunchKernelGGL(k_env_mark_idx, grid_for(n_sel), dim3(WG), 0, s, h->P, h->dcfg, h->dacc, envs_idx, n_sel);
+  launch_reset_marked(h, s);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;
 }

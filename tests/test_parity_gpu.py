@@ -91,9 +91,32 @@ def test_live_curriculum_long_run_bit_exact(oracle_lib, hip_lib, blob):
     assert max(levels) > 0.4 and min(levels) < 0.05, "the level was meant to rise and fall"
 
 
+# timed scopes per env step of 2 substeps in timing mode, by class (DYN, COLLIDE, SOLVE, INTEGRATE, ENV_PRE, ENV_POST, MISC, TOTAL): bench.py divides the
+# class milliseconds by these counts (roofline_of).  A run of consecutive launches of one class is one scope: the post-physics launches are one ENV_POST.
+TIMING_COUNTS = {
+    "flat": (1, 2, 2, 0, 0, 1, 0, 1),         # k_pre_dynamics_team | 2 x (k_collide_team, k_solve_integrate_team) | post
+    "heightfield": (1, 2, 2, 2, 0, 1, 0, 1),  # ... the solve alone, then k_integrate_fk_dynamics_team / k_integrate_fk_team
+    "no_fuse": (2, 2, 2, 2, 1, 1, 0, 1),      # k_env_pre | k_dynamics_team | 2 x (collide, solve, k_integrate_fk_team [, k_dynamics_team]) | post
+}
+
+
+def _timed_env(hip_lib, blob, n_envs, seed, **kw):
+    t = GpuEnv(hip_lib, blob, n_envs, seed=seed, **kw)
+    t.sim.enable_timing(True)
+    return t
+
+
+def _assert_timing_counts(t, steps, row):
+    t.torch.cuda.synchronize()
+    _, cnt = t.sim.read_timing(reset=True)
+    print(f"timing counts over {steps} steps ({row}): {cnt}")
+    assert tuple(cnt) == tuple(steps * c for c in TIMING_COUNTS[row]), (row, steps, cnt)
+
+
 def test_graph_and_plain_launch_paths_agree(hip_lib, blob, monkeypatch):
     """go2sim_env_step launches its kernel sequence as one hipGraph (default) or kernel by kernel (GO2SIM_NO_GRAPH=1, timing mode): same bits.
-    Also covers a change of the output buffers between steps (the graph is rebuilt) and of the action buffer (a node parameter)."""
+    Also covers a change of the output buffers between steps (new arguments of a graph node) and of the action buffer (a node parameter), and the
+    number of timed scopes per step that timing mode accounts."""
     import torch
 
     n_envs, steps = 70, 60
@@ -101,15 +124,41 @@ def test_graph_and_plain_launch_paths_agree(hip_lib, blob, monkeypatch):
     monkeypatch.setenv("GO2SIM_NO_GRAPH", "1")
     p = GpuEnv(hip_lib, blob, n_envs, seed=4)
     monkeypatch.delenv("GO2SIM_NO_GRAPH")
-    g.reset(); p.reset()
+    t = _timed_env(hip_lib, blob, n_envs, 4)
+    g.reset(); p.reset(); t.reset()
+    t.sim.read_timing(reset=True)                                  # (the reset is a MISC scope)
     acts = make_actions(steps, n_envs, seed=9, kind="mixed")
     for s_, a in enumerate(acts):
-        if s_ == 20:                                               # new output tensors -> new graph
+        if s_ == 20:                                               # new output tensors
             g.obs = torch.zeros_like(g.obs); g.priv = torch.zeros_like(g.priv)
         og, pg, rg, dg, tg = g.step(a)
-        op, pp, rp, dp, tp = p.step(a)
-        assert bits_equal(og, op) and bits_equal(pg, pp) and bits_equal(rg, rp) and np.array_equal(dg, dp) and bits_equal(tg, tp), f"step {s_}"
+        for o in (p, t):
+            op, pp, rp, dp, tp = o.step(a)
+            assert bits_equal(og, op) and bits_equal(pg, pp) and bits_equal(rg, rp) and np.array_equal(dg, dp) and bits_equal(tg, tp), f"step {s_}"
     _compare_fields(g, p, "final")
+    _compare_fields(g, t, "final (timing mode)")
+    _assert_timing_counts(t, steps, "flat")
+    assert g.sim.graph_status() == (True, 0)
+
+
+@pytest.mark.parametrize("row,task,knob", [("heightfield", "stairs", None), ("no_fuse", "walk", "GO2SIM_NO_FUSE")])
+def test_timing_mode_agrees_with_graph(hip_lib, blob, monkeypatch, row, task, knob):
+    """Timing mode (plain launches bracketed by events, what bench.py's roofline pass runs) against the step graph on the heightfield task and with
+    GO2SIM_NO_FUSE=1: same bits, and the timed scopes per step of TIMING_COUNTS."""
+    n_envs, steps = 70, 12
+    if knob:
+        monkeypatch.setenv(knob, "1")
+    g = GpuEnv(hip_lib, blob, n_envs, seed=6, task=task)
+    t = _timed_env(hip_lib, blob, n_envs, 6, task=task)
+    g.reset(); t.reset()
+    t.sim.read_timing(reset=True)
+    for s_, a in enumerate(make_actions(steps, n_envs, seed=3, kind="0.5", n_act=g.n_act)):
+        og, pg, rg, dg, tg = g.step(a)
+        ot, pt, rt, dt, tt = t.step(a)
+        assert bits_equal(og, ot) and bits_equal(pg, pt) and bits_equal(rg, rt) and np.array_equal(dg, dt) and bits_equal(tg, tt), f"step {s_}"
+    _compare_fields(g, t, "final")
+    _assert_timing_counts(t, steps, row)
+    assert g.sim.graph_status() == (True, 0)
 
 
 def test_scene_step_bit_exact_with_uploaded_state(oracle_lib, hip_lib, blob):
