@@ -1740,11 +1740,187 @@ DEV void tk_dynamics(const MT& m, const E& e, DynData* s, int tl, bool env_valid
   PH(25)
 }
 
+// ---------------------------------------------------------------------------------------------
+// Collision broad phase, run by the team of the forward dynamics.
+// Every collision launch is preceded by exactly one forward-dynamics pass on the same state (build_launch_list), and the two do not depend on
+// each other: the broad phase (geom AABBs, func_collision_clear, the persistent sweep-and-prune sort, the candidate pair list) runs at the end of
+// that pass -- 32 lanes per env and two waves per SIMD -- instead of at the head of k_collide_team (16 lanes, one wave per SIMD), which starts at the
+// narrow phase and reads the pair list from e.broad().  Parallel form of the serial sweep: see "collision detection" below.  Same expressions and
+// the same values in sort_value / sort_ig / broad / n_broad / ncache_valid for every team size.
+// ---------------------------------------------------------------------------------------------
+// the lanes of my team that pass p (bit l = lane l of the team)
+template <int T> DEV unsigned long long team_ballot(bool p) {
+  const unsigned long long b = __ballot(p);
+  if constexpr (T == 64) return b;
+  else return (b >> (threadIdx.x & (64 - T))) & ((1ull << T) - 1ull);
+}
 template <int T>
-__global__ __launch_bounds__(64) void k_dynamics_team(Pool P, const ModelS* __restrict__ mp) {
+struct BroadData {
+  alignas(16) float amin[NG * 4], amax[NG * 4];     // xyz + pad: one 128-bit LDS read per corner
+  alignas(16) unsigned long long skey[2 * NG];      // (order-preserving integer image of the endpoint value) << 8 | position before the sort
+  alignas(8) int rank_mm[NG * 2];                   // (rank of the min endpoint, rank of the max endpoint) per geom
+  int cand_key[MAXB], cand_pair[MAXB];
+  unsigned short pair_sorted[MAXB];                 // geom a | geom b << 8
+};
+// The working set is laid over the env's dynamics record, all of which is dead once tk_dynamics has stored its results: the dynamics kernels keep
+// their LDS footprint (8 workgroups per CU).  The records of a workgroup are packed (sizeof(DynData) is not a multiple of 16), so the overlay starts
+// at the first 16-byte boundary inside the record; shape variants whose record is too small for it get a block of their own.
+constexpr int BROAD_PAD = 12;
+template <int T> constexpr bool BROAD_OVERLAY = sizeof(BroadData<T>) + BROAD_PAD <= sizeof(DynData);
+template <bool OVERLAY, int T> struct BroadSeparate { BroadData<T> k[64 / T]; DEV BroadData<T>* at(int slot, DynData*) { return &k[slot]; } };
+template <int T> struct BroadSeparate<true, T> {
+  DEV BroadData<T>* at(int slot, DynData* d) {      // d = record `slot` of a 16-byte aligned array
+    static_assert(sizeof(BroadData<T>) + BROAD_PAD <= sizeof(DynData) && sizeof(DynData) % 4 == 0 && alignof(BroadData<T>) == 16, "BroadData overlay");
+    return (BroadData<T>*)((char*)d + (16 - (slot * (int)sizeof(DynData)) % 16) % 16);
+  }
+};
+static_assert((BROAD_OVERLAY<16> && BROAD_OVERLAY<32> && BROAD_OVERLAY<64>) || NG != 28 || ND != 18, "the Go2 shape keeps the dynamics kernels' LDS size");
+
+// profiling builds: 30 = loads + AABBs, 31 = endpoint sort, 32 = candidate pairs, pair list, stores + clear (the ids these phases had in k_collide_team)
+template <int T>
+DEV void tk_broadphase(const Model& m, const E& e, BroadData<T>* s, int tl) {
+  const float inf = dm_bits2f(0x7f800000u);
+  PH_BEGIN
+  // ---- loads first (into registers): previous contact count, first-step flag, normal-cache mask, the persistent sort order, the pair table of the
+  //      candidate test for all rounds, geom poses and corners.  They are in flight while the last stores of the dynamics drain. ----
+  const int nc_old = e.n_contacts()[0];
+  const bool first = e.first_time()[0] != 0;
+  const unsigned ncv_old = (unsigned)e.ncache_valid()[tl < NCV ? tl : NCV - 1];
+  constexpr int n2 = 2 * NG, NK = (2 * NG + T - 1) / T, NPI = (NPAIR + T - 1) / T, NGR = (NG + T - 1) / T;
+  int sig_[NK];                                                         // my (up to) NK endpoints: i = tl + q * T (out-of-range lanes redo the last one)
+#pragma unroll
+  for (int q = 0; q < NK; ++q) { const int i = tl + q * T; sig_[q] = e.sort_ig()[i < n2 ? i : n2 - 1]; }
+  int packed_[NPI];
+  {
+    const int n_pairs = m.n_pairs;
+#pragma unroll
+    for (int it = 0; it < NPI; ++it) { int pidx = it * T + tl; int v = m.pair_list[pidx < NPAIR ? pidx : NPAIR - 1]; packed_[it] = (pidx < n_pairs) ? v : -1; }
+  }
+  // ---- kernel_update_geom_aabbs, forward_kinematics.py:1171-1193 (out-of-range lanes redo the last geom: no branch between the loads) ----
+  V3 lower_[NGR], upper_[NGR];
+#pragma unroll
+  for (int g = 0; g < NGR; ++g) {
+    const int i_g = (g * T + tl < NG) ? g * T + tl : NG - 1;
+    V3 lower = v3(inf, inf, inf), upper = v3(-inf, -inf, -inf);
+    V3 gp = e.g_pos()[i_g]; Q4 gq = e.g_quat()[i_g];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      V3 corner = transform_by_trans_quat(m.geoms[i_g].aabb[c], gp, gq);
+      lower = vmin(lower, corner); upper = vmax(upper, corner);
+    }
+    lower_[g] = lower; upper_[g] = upper;
+  }
+  team_sync();                                                          // the dynamics are done with the record under the overlay
+#pragma unroll
+  for (int g = 0; g < NGR; ++g) {
+    const int i_g = (g * T + tl < NG) ? g * T + tl : NG - 1;
+    *(float4*)&s->amin[4 * i_g] = make_float4(lower_[g].x, lower_[g].y, lower_[g].z, 0.0f);
+    *(float4*)&s->amax[4 * i_g] = make_float4(upper_[g].x, upper_[g].y, upper_[g].z, 0.0f);
+  }
+  team_sync();
+  PH(30)
+  // ---- func_broad_phase, broadphase.py:141-396: endpoint refresh + stable sort ----
+  int r[NK]; float sorted_v[NK]; int sorted_sg[NK];                     // my endpoints after the sort: rank, value, geom | is_max << 8 (stored at the end)
+  unsigned long long key[NK];
+#pragma unroll
+  for (int q = 0; q < NK; ++q) {
+    const int i = (tl + q * T < n2) ? tl + q * T : n2 - 1;
+    // first step: endpoints in (link, geom) order: geoms are stored link-major, so buffer slot i/2 holds geom i/2
+    const int sg = first ? ((i >> 1) | ((i & 1) ? 0x100 : 0)) : sig_[q];
+    const int g = sg & 0xff;
+    const float v = (sg & 0x100) ? s->amax[4 * g] : s->amin[4 * g];
+    // rank of endpoint i = #{j : w_j < v  or  (w_j == v and j < i)}  =  #{j : key_j < key_i} with key = (image(value), position): one 64-bit
+    // compare per pair instead of two float compares and the tie logic.  image() is monotone on the non-NaN floats and maps -0 and +0 to one value
+    // (v + 0.0f), like the float compares it replaces.
+    unsigned u = (unsigned)__float_as_int(v + 0.0f);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    key[q] = ((unsigned long long)u << 8) | (unsigned long long)i;
+    s->skey[i] = key[q];
+    sorted_v[q] = v; sorted_sg[q] = sg; r[q] = 0;
+  }
+  team_sync();
+  // a lane ranks its (up to) NK endpoints at once: every key is read once (the same address for all lanes of the team) and compared with all of them,
+  // instead of one pass over the keys per endpoint
+#pragma unroll
+  for (int j = 0; j < 2 * NG; ++j) {
+    const unsigned long long kj = s->skey[j];
+#pragma unroll
+    for (int q = 0; q < NK; ++q) r[q] += (kj < key[q]) ? 1 : 0;
+  }
+#pragma unroll
+  for (int q = 0; q < NK; ++q)
+    if (tl + q * T < n2) s->rank_mm[2 * (sorted_sg[q] & 0xff) + ((sorted_sg[q] & 0x100) ? 1 : 0)] = r[q];
+  team_sync();
+  PH(31)
+  // ---- candidate pairs: every valid geom pair is tested by one lane ----
+  // the pair table is fetched for all rounds up front and every LDS operand of a test is read unconditionally, so that the reads of a
+  // round are in flight together.  The verdicts of a round are collected with ballots: the candidates are compacted in (round, lane) order (the
+  // list is sorted by key below, so its order is free), and
+  // normal_cache[pidx] := 0 for every separated pair: pair pidx = it * T + tl is bit pidx of the mask, lane w gathers word w (instead of one
+  // LDS atomic per pair)
+  int n_cand = 0;
+  unsigned ncv_clear = 0u;
+  static_assert(NCV <= T, "one lane per word of the normal-cache mask");
+#pragma unroll
+  for (int it = 0; it < NPI; ++it) {
+    const int packed = packed_[it];
+    const int a = (packed < 0) ? 0 : (packed & 0xff), bg = (packed < 0) ? 0 : (packed >> 8);
+    const int2 rka = *(const int2*)&s->rank_mm[2 * a], rkb = *(const int2*)&s->rank_mm[2 * bg];
+    const float4 amn = *(const float4*)&s->amin[4 * a], amx = *(const float4*)&s->amax[4 * a], bmn = *(const float4*)&s->amin[4 * bg], bmx = *(const float4*)&s->amax[4 * bg];
+    const int ra = rka.x, rb = rkb.x;
+    const int rs = (ra < rb) ? rb : ra, rf = (ra < rb) ? ra : rb;
+    const int rmax_first = (ra < rb) ? rka.y : rkb.y;
+    const bool swept = packed >= 0 && rs < rmax_first;
+    const bool any1 = (amx.x <= bmn.x) || (amx.y <= bmn.y) || (amx.z <= bmn.z);
+    const bool any2 = (amn.x >= bmx.x) || (amn.y >= bmx.y) || (amn.z >= bmx.z);
+    const bool cand = swept && !(any1 || any2);
+    const unsigned long long cb = team_ballot<T>(cand);
+    if (cand) {
+      const int pos = n_cand + __popcll(cb & ((1ull << tl) - 1ull));
+      if (pos < MAXB) { s->cand_key[pos] = rs * 64 + rf; s->cand_pair[pos] = packed; }
+    }
+    n_cand += __popcll(cb);
+    const unsigned long long sep = team_ballot<T>(swept && (any1 || any2));
+    if constexpr (T < 32) { if (tl == ((it * T) >> 5)) ncv_clear |= (unsigned)(sep << ((it * T) & 31)); }
+    else if constexpr (T == 32) { if (tl == it) ncv_clear |= (unsigned)sep; }
+    else { if (tl == 2 * it) ncv_clear |= (unsigned)sep; if (tl == 2 * it + 1) ncv_clear |= (unsigned)(sep >> 32); }
+  }
+  // the serial sweep stops appending at max_broad_pairs (broadphase.py:330-338): all candidates are ranked by the sweep key first, the list is
+  // clipped afterwards, so the pairs that survive are the ones the sweep reaches first
+  const bool overflow = n_cand > m.max_broad_pairs;
+  n_cand = imn(n_cand, MAXB);
+  team_sync();
+  for (int c = tl; c < n_cand; c += T) {
+    const int ck = s->cand_key[c]; int cr = 0;
+    for (int j = 0; j < n_cand; ++j) cr += s->cand_key[j] < ck;
+    s->pair_sorted[cr] = (unsigned short)s->cand_pair[c];
+  }
+  const int n_broad = imn(n_cand, m.max_broad_pairs);
+  team_sync();
+  // ---- everything the broad phase writes to the env's records, after the last ordering point: none of the stores is waited for ----
+  for (int c = tl; c < n_broad; c += T) { int pk = s->pair_sorted[c]; e.broad()[2 * c] = pk & 0xff; e.broad()[2 * c + 1] = pk >> 8; }
+#pragma unroll
+  for (int q = 0; q < NK; ++q) if (tl + q * T < n2) { e.sort_value()[r[q]] = sorted_v[q]; e.sort_ig()[r[q]] = sorted_sg[q]; }
+  if (tl < NCV && ncv_clear != 0u) e.ncache_valid()[tl] = (int)(ncv_old & ~ncv_clear);
+  if (tl == 0) {
+    e.n_broad()[0] = n_broad;
+    if (first) e.first_time()[0] = 0;
+    if (overflow) atomicOr(&e.err()[0], GO2SIM_ERR_OVERFLOW_CANDIDATE_CONTACTS);
+  }
+  // func_collision_clear, broadphase.py:73-138
+  for (int i_c = tl; i_c < nc_old; i_c += T) {
+    e.c_link()[i_c] = -1; e.c_link()[MAXC + i_c] = -1; e.c_geom()[i_c] = -1; e.c_geom()[MAXC + i_c] = -1;
+    e.c_pen()[i_c] = 0.0f; e.c_pos()[i_c] = v3(0, 0, 0); e.c_normal()[i_c] = v3(0, 0, 0); e.c_force()[i_c] = v3(0, 0, 0);
+  }
+  PH(32)
+}
+
+template <int T>
+__global__ __launch_bounds__(64) void k_dynamics_team(Pool P, const ModelS* __restrict__ mp, const Model* __restrict__ gm) {
   constexpr int EPW = 64 / T;
-  __shared__ DynData lds[EPW];
+  __shared__ alignas(16) DynData lds[EPW];
   __shared__ alignas(16) char ms_raw[MODELS_LDS_BYTES];
+  __shared__ BroadSeparate<BROAD_OVERLAY<T>, T> lds_b;
   const ModelS& ms = *(const ModelS*)ms_raw;
   wg_dma_to_lds<(int)sizeof(ModelS)>(ms_raw, mp);
   {  // ---- stage the SoA inputs cooperatively (adjacent lanes = adjacent envs), before any lane retires ----
@@ -1780,6 +1956,7 @@ __global__ __launch_bounds__(64) void k_dynamics_team(Pool P, const ModelS* __re
   team_sync();
   PH(20)
   tk_dynamics<T>(m, e, s, tl, env_valid);
+  if (env_valid) tk_broadphase<T>(*gm, e, lds_b.at(slot, s), tl);       // for the collision launch that follows
 }
 
 
@@ -1793,12 +1970,15 @@ template <int EPW> struct KinSeparate<true, EPW> { DEV KinData* at(int, void* ov
 // the top of the kernel.
 constexpr bool KIN_OVERLAY = sizeof(KinData) <= 2 * sizeof(float) * ND * ND;         // (shape variants with few dofs: the kinematics set gets its own LDS block)
 template <int T>
-DEV void integrate_fk_dynamics_body(const Pool& P, const ModelS* __restrict__ mp, int b, DynData* lds_d, char* ms_raw, KinSeparate<KIN_OVERLAY, 64 / T>& lds_k,
-                                    bool pre, float pre_vel, float pre_acc) {
+DEV void integrate_fk_dynamics_body(const Pool& P, const ModelS* __restrict__ mp, const Model* __restrict__ gm, int b, DynData* lds_d, char* ms_raw,
+                                    KinSeparate<KIN_OVERLAY, 64 / T>& lds_k, BroadSeparate<BROAD_OVERLAY<T>, T>& lds_b, bool pre, float pre_vel, float pre_acc) {
   const ModelS& ms = *(const ModelS*)ms_raw;
   wg_dma_to_lds<(int)sizeof(ModelS)>(ms_raw, mp);
   const int tl = threadIdx.x % T, slot = threadIdx.x / T;
   const ModelView m(&ms, mp);
+  // (k_solve_integrate_team: the env's record pointers are formed anew from an opaque copy of b.  Shared with the solve in front, they stay live across
+  //  it and are spilled there -- 8 VGPRs to scratch, 10 with the broad phase at the end of this function -- where forming them costs a few integer operations)
+  asm volatile("" : "+v"(b));
   E e(P, b < P.B ? b : P.B - 1);
   DynData* d = &lds_d[slot];
   // the kinematics working set lives in the M | L words of the dynamics record, which the dynamics only start writing (mass matrix, then its factor)
@@ -1831,15 +2011,17 @@ DEV void integrate_fk_dynamics_body(const Pool& P, const ModelS* __restrict__ mp
   team_sync();
   PH(41)
   tk_dynamics<T>(m, e, d, tl, true);
+  tk_broadphase<T>(*gm, e, lds_b.at(slot, d), tl);                      // of the geom poses the kinematics above have just written, for the next collision launch
 }
 template <int T>
-__global__ __launch_bounds__(64) void k_integrate_fk_dynamics_team(Pool P, const ModelS* __restrict__ mp) {
+__global__ __launch_bounds__(64) void k_integrate_fk_dynamics_team(Pool P, const ModelS* __restrict__ mp, const Model* __restrict__ gm) {
   STAMP(STK_INT_FK_DYN)
   constexpr int EPW = 64 / T;
-  __shared__ DynData lds_d[EPW];
+  __shared__ alignas(16) DynData lds_d[EPW];
   __shared__ alignas(16) char ms_raw[MODELS_LDS_BYTES];
   __shared__ KinSeparate<KIN_OVERLAY, EPW> lds_k;
-  integrate_fk_dynamics_body<T>(P, mp, xcd_block() * EPW + (int)threadIdx.x / T, lds_d, ms_raw, lds_k, false, 0.0f, 0.0f);
+  __shared__ BroadSeparate<BROAD_OVERLAY<T>, T> lds_b;
+  integrate_fk_dynamics_body<T>(P, mp, gm, xcd_block() * EPW + (int)threadIdx.x / T, lds_d, ms_raw, lds_k, lds_b, false, 0.0f, 0.0f);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1888,12 +2070,6 @@ DEV V3 support_cylinder_local(const Model& m, const Geom& G, V3 d_mesh, int* vid
 }
 // support_driver, collider/mpr.py:146-176
 // _func_support_prism, support_field.py:262-280: the terrain geom is represented by the current 6-vertex prism
-// the lanes of my team that pass p (bit l = lane l of the team)
-template <int T> DEV unsigned long long team_ballot(bool p) {
-  const unsigned long long b = __ballot(p);
-  if constexpr (T == 64) return b;
-  else return (b >> (threadIdx.x & (64 - T))) & ((1ull << T) - 1ull);
-}
 DEV V3 vsel(bool c, V3 a, V3 b) { return v3(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z); }
 DEV V3 support_prism(const V3* prism, V3 d) {
   // the bottom (0..2) or top (3..5) triangle, then the first vertex with the largest projection; written with value selects and constant
@@ -2242,27 +2418,18 @@ DEV void plane_contact(const Model& m, const Pair& pr, bool& is_col, V3& normal,
 constexpr int GJK_SLOTS = GJK_SLOTS_MAX;
 template <int T>
 struct CollideData {
-  // the three phases of the kernel use disjoint working sets, laid over each other: broad phase -> (barrier) -> convex narrow phase (GJK / EPA
-  // polytopes of the lanes that fall back from MPR) -> (barrier) -> terrain pass
-  struct Broad {
-    alignas(16) float amin[NG * 4], amax[NG * 4];   // xyz + pad: one 128-bit LDS read per corner
-    float sval[2 * NG], sval_sorted[2 * NG];
-    alignas(16) unsigned long long skey[2 * NG];      // (order-preserving integer image of the endpoint value) << 8 | position before the sort
-    int sig[2 * NG], sig_sorted[2 * NG];
-    alignas(8) int rank_mm[NG * 2];                  // (rank of the min endpoint, rank of the max endpoint) per geom
-    int cand_key[MAXB], cand_pair[MAXB];
-  };
+  // the two phases of the kernel use disjoint working sets, laid over each other: convex narrow phase (GJK / EPA polytopes of the lanes that fall
+  // back from MPR) -> (barrier) -> terrain pass.  (The broad phase runs in the dynamics launch in front of this kernel: tk_broadphase.)
   // terrain pass: one slot per (geom, terrain) pair of the broad-phase list
   struct TPair { int i_ga, r_min, r_max, c_min, c_max, n_items, item_off; float zmin, tol; V3 pos_a; Q4 quat_a; V3 center_a; };
   struct Terrain {
     TPair tp[NG];
   };
   union alignas(16) {
-    Broad bp;
     GjkStoreLds gjk[GJK_SLOTS];
     Terrain tr;
   };
-  unsigned short pair_sorted[MAXB];                   // geom a | geom b << 8
+  unsigned short pair_sorted[MAXB];                   // the broad-phase list of this env (e.broad()): geom a | geom b << 8
   float stage[T][5][7];
   int cnt[T];
   unsigned gjk_slot_mask;                             // bit i set = gjk[i] is taken
@@ -2575,150 +2742,32 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
   const Model& m = *mp;
   E e(P, b);
   CollideData<T>* s = &lds[slot];
-  const float inf = dm_bits2f(0x7f800000u);
-  if (tl == 0) s->gjk_slot_mask = 0u;                                   // made visible by the barriers of the broad phase
+  if (tl == 0) s->gjk_slot_mask = 0u;                                   // made visible by the barrier behind the pair-list load
   for (int i = tl; i < NCV; i += T) s->ncv[i] = (unsigned)e.ncache_valid()[i];
   PH_BEGIN
-  // ---- loads of the prologue first: previous contact count, first-step flag, the persistent sort order, geom poses ----
-  const int nc_old = e.n_contacts()[0];
-  const bool first = e.first_time()[0] != 0;
-  const int n2 = 2 * NG;
-  team_stage<2 * NG, T>(tl, [&](int i) { return __int_as_float(e.sort_ig()[i]); }, [&](int i, float v) { s->bp.sig[i] = __float_as_int(v); });
-  constexpr int NPI = (NPAIR + T - 1) / T;                            // the pair table of the candidate test, fetched for all rounds up front
-  int packed_[NPI];
-  {
-    const int n_pairs = m.n_pairs;
-#pragma unroll
-    for (int it = 0; it < NPI; ++it) { int pidx = it * T + tl; int v = m.pair_list[pidx < NPAIR ? pidx : NPAIR - 1]; packed_[it] = (pidx < n_pairs) ? v : -1; }
-  }
-  // ---- kernel_update_geom_aabbs, forward_kinematics.py:1171-1193 (out-of-range lanes redo the last geom: no branch between the loads) ----
-#pragma unroll
-  for (int g0 = 0; g0 < NG; g0 += T) {
-    const int i_g = (g0 + tl < NG) ? g0 + tl : NG - 1;
-    V3 lower = v3(inf, inf, inf), upper = v3(-inf, -inf, -inf);
-    V3 gp = e.g_pos()[i_g]; Q4 gq = e.g_quat()[i_g];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      V3 corner = transform_by_trans_quat(m.geoms[i_g].aabb[c], gp, gq);
-      lower = vmin(lower, corner); upper = vmax(upper, corner);
-    }
-    *(float4*)&s->bp.amin[4 * i_g] = make_float4(lower.x, lower.y, lower.z, 0.0f);
-    *(float4*)&s->bp.amax[4 * i_g] = make_float4(upper.x, upper.y, upper.z, 0.0f);
-  }
-  // ---- func_collision_clear, broadphase.py:73-138 ----
-  for (int i_c = tl; i_c < nc_old; i_c += T) {
-    e.c_link()[i_c] = -1; e.c_link()[MAXC + i_c] = -1; e.c_geom()[i_c] = -1; e.c_geom()[MAXC + i_c] = -1;
-    e.c_pen()[i_c] = 0.0f; e.c_pos()[i_c] = v3(0, 0, 0); e.c_normal()[i_c] = v3(0, 0, 0); e.c_force()[i_c] = v3(0, 0, 0);
-  }
+  // ---- the pair list of the broad phase (tk_broadphase, run by the dynamics launch in front of this one) ----
+  const int n_broad = imn(imx(e.n_broad()[0], 0), MAXB);
+  for (int c = tl; c < n_broad; c += T) s->pair_sorted[c] = (unsigned short)(e.broad()[2 * c] | (e.broad()[2 * c + 1] << 8));
   team_sync();
-  PH(30)
-  // ---- func_broad_phase, broadphase.py:141-396: endpoint refresh + stable sort ----
-  for (int i = tl; i < n2; i += T) {
-    // first step: endpoints in (link, geom) order: geoms are stored link-major, so buffer slot i/2 holds geom i/2
-    int sg = first ? ((i >> 1) | ((i & 1) ? 0x100 : 0)) : s->bp.sig[i];
-    int g = sg & 0xff;
-    s->bp.sig[i] = sg;
-    const float v = (sg & 0x100) ? s->bp.amax[4 * g] : s->bp.amin[4 * g];
-    s->bp.sval[i] = v;
-    // rank of endpoint i = #{j : w_j < v  or  (w_j == v and j < i)}  =  #{j : key_j < key_i} with key = (image(value), position): one 64-bit
-    // compare per pair instead of two float compares and the tie logic.  image() is monotone on the non-NaN floats and maps -0 and +0 to one value
-    // (v + 0.0f), like the float compares it replaces.
-    unsigned u = (unsigned)__float_as_int(v + 0.0f);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    s->bp.skey[i] = ((unsigned long long)u << 8) | (unsigned long long)i;
-  }
-  team_sync();
-  {
-    // a lane ranks its (up to) NK endpoints at once: every key is read once (the same address for all lanes of the team) and compared with all of them,
-    // instead of one pass over the keys per endpoint
-    constexpr int NK = (2 * NG + T - 1) / T;
-    unsigned long long key[NK]; int r[NK];
-#pragma unroll
-    for (int q = 0; q < NK; ++q) { const int i = tl + q * T; key[q] = s->bp.skey[i < n2 ? i : n2 - 1]; r[q] = 0; }
-#pragma unroll
-    for (int j = 0; j < 2 * NG; ++j) {
-      const unsigned long long kj = s->bp.skey[j];
-#pragma unroll
-      for (int q = 0; q < NK; ++q) r[q] += (kj < key[q]) ? 1 : 0;
-    }
-#pragma unroll
-    for (int q = 0; q < NK; ++q) {
-      const int i = tl + q * T;
-      if (i < n2) {
-        const float v = s->bp.sval[i];
-        const int sg = s->bp.sig[i];
-        s->bp.sval_sorted[r[q]] = v; s->bp.sig_sorted[r[q]] = sg;
-        s->bp.rank_mm[2 * (sg & 0xff) + ((sg & 0x100) ? 1 : 0)] = r[q];
-        e.sort_value()[r[q]] = v; e.sort_ig()[r[q]] = sg;
-      }
-    }
-  }
-  if (tl == 0 && first) e.first_time()[0] = 0;
-  team_sync();
-  PH(31)
-  // ---- candidate pairs: every valid geom pair is tested by one lane ----
-  int n_cand = 0;
-  // the pair table is fetched for all rounds up front and every LDS operand of a test is read unconditionally, so that the reads of a
-  // round are in flight together; only the ballot compaction is sequential
-  unsigned cmask = 0; int key_[NPI];
-  // normal_cache[pidx] := 0 for every separated pair: the lanes' verdicts of a round are collected with one ballot (pair pidx = it * T + tl is bit pidx of the
-  // mask) and lane w gathers word w, instead of one LDS atomic per pair (16 lanes of a team on one word)
-  unsigned ncv_clear = 0u;
-  static_assert(NCV <= T, "one lane per word of the normal-cache mask");
-#pragma unroll
-  for (int it = 0; it < NPI; ++it) {                                   // the rounds are independent: candidates are only marked here
-    const int pidx = it * T + tl;
-    const int packed = packed_[it];
-    const int a = (packed < 0) ? 0 : (packed & 0xff), bg = (packed < 0) ? 0 : (packed >> 8);
-    const int2 rka = *(const int2*)&s->bp.rank_mm[2 * a], rkb = *(const int2*)&s->bp.rank_mm[2 * bg];
-    const float4 amn = *(const float4*)&s->bp.amin[4 * a], amx = *(const float4*)&s->bp.amax[4 * a], bmn = *(const float4*)&s->bp.amin[4 * bg], bmx = *(const float4*)&s->bp.amax[4 * bg];
-    const int ra = rka.x, rb = rkb.x;
-    const int rs = (ra < rb) ? rb : ra, rf = (ra < rb) ? ra : rb;
-    const int rmax_first = (ra < rb) ? rka.y : rkb.y;
-    key_[it] = rs * 64 + rf;
-    const bool swept = packed >= 0 && rs < rmax_first;
-    const bool any1 = (amx.x <= bmn.x) || (amx.y <= bmn.y) || (amx.z <= bmn.z);
-    const bool any2 = (amn.x >= bmx.x) || (amn.y >= bmx.y) || (amn.z >= bmx.z);
-    if (swept && !(any1 || any2)) cmask |= 1u << it;
-    const unsigned long long sep = team_ballot<T>(swept && (any1 || any2));
-    (void)pidx;
-    if constexpr (T < 32) { if (tl == ((it * T) >> 5)) ncv_clear |= (unsigned)(sep << ((it * T) & 31)); }
-    else if constexpr (T == 32) { if (tl == it) ncv_clear |= (unsigned)sep; }
-    else { if (tl == 2 * it) ncv_clear |= (unsigned)sep; if (tl == 2 * it + 1) ncv_clear |= (unsigned)(sep >> 32); }
-  }
-  if (tl < NCV) s->ncv[tl] &= ~ncv_clear;
-  {                                                                    // compaction; the list is sorted by key below, so its order is free
-    const int mine = __popc(cmask);
-    s->cnt[tl] = mine;
-    team_sync();
-    int pos = 0, tot = 0;
-    for (int l = 0; l < T; ++l) { int c = s->cnt[l]; pos += (l < tl) ? c : 0; tot += c; }
-    team_sync();
-#pragma unroll
-    for (int it = 0; it < NPI; ++it)
-      if (cmask & (1u << it)) { if (pos < MAXB) { s->bp.cand_key[pos] = key_[it]; s->bp.cand_pair[pos] = packed_[it]; } pos++; }
-    n_cand = tot;
-  }
-  // the serial sweep stops appending at max_broad_pairs (broadphase.py:330-338): all candidates are ranked by the sweep key first, the list is
-  // clipped afterwards, so the pairs that survive are the ones the sweep reaches first
-  if (n_cand > m.max_broad_pairs && tl == 0) atomicOr(&e.err()[0], GO2SIM_ERR_OVERFLOW_CANDIDATE_CONTACTS);
-  n_cand = imn(n_cand, MAXB);
-  team_sync();
-  for (int c = tl; c < n_cand; c += T) {
-    int key = s->bp.cand_key[c], r = 0;
-    for (int j = 0; j < n_cand; ++j) r += s->bp.cand_key[j] < key;
-    s->pair_sorted[r] = (unsigned short)s->bp.cand_pair[c];
-  }
-  const int n_broad = imn(n_cand, m.max_broad_pairs);
-  team_sync();
-  for (int c = tl; c < n_broad; c += T) { int pk = s->pair_sorted[c]; e.broad()[2 * c] = pk & 0xff; e.broad()[2 * c + 1] = pk >> 8; }
-  PH(32)
   // ---- func_narrow_phase_convex_vs_convex (narrowphase.py:964-1068), then func_narrow_phase_any_vs_terrain (:1197-1244): one lane per
   //      pair, ordered compaction; the terrain pass appends after all convex-convex contacts, as the two reference kernels do ----
   int nc_run = 0;
   const int n_np_iter = (n_broad + T - 1) / T;
   // the staged contacts of a round of T pairs go to the list in pair order (func_add_contact, contact.py:165-199)
-  auto append_staged = [&](const ContactStage& cs, int i_ga, int i_gb) {
+  // what a contact of the pair (i_ga, i_gb) takes from the model and the env's geom records: requested BEFORE the pair's narrow-phase query, so the
+  // append behind the query does not start with a memory round trip (one wave per SIMD: nothing else would cover it)
+  struct PairConst { float friction, sol[7]; int link_a, link_b; };
+  auto load_pair_const = [&](int i_ga, int i_gb) {
+    PairConst pc;
+    float friction_a = e.geom_friction()[i_ga] * e.friction_ratio()[i_ga];
+    float friction_b = e.geom_friction()[i_gb] * e.friction_ratio()[i_gb];
+    pc.friction = fmx(fmx(friction_a, friction_b), 1e-2f);
+#pragma unroll
+    for (int q = 0; q < 7; ++q) pc.sol[q] = 0.5f * (m.geoms[i_ga].sol_params[q] + m.geoms[i_gb].sol_params[q]);
+    pc.link_a = m.geoms[i_ga].link; pc.link_b = m.geoms[i_gb].link;
+    return pc;
+  };
+  auto append_staged = [&](const ContactStage& cs, int i_ga, int i_gb, const PairConst& pc) {
     s->cnt[tl] = cs.n;
     team_sync();
     int off = 0, tot = 0;
@@ -2727,14 +2776,13 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
       int i_c = nc_run + off + k;
       if (i_c < m.max_contact_pairs) {
         const float* p = cs.st + 7 * k;
-        float friction_a = e.geom_friction()[i_ga] * e.friction_ratio()[i_ga];
-        float friction_b = e.geom_friction()[i_gb] * e.friction_ratio()[i_gb];
         e.c_geom()[i_c] = i_ga; e.c_geom()[MAXC + i_c] = i_gb;
         e.c_normal()[i_c] = v3(p[0], p[1], p[2]); e.c_pos()[i_c] = v3(p[3], p[4], p[5]); e.c_pen()[i_c] = p[6];
-        e.c_friction()[i_c] = fmx(fmx(friction_a, friction_b), 1e-2f);
+        e.c_friction()[i_c] = pc.friction;
         auto sol = e.c_sol()[i_c];
-        for (int q = 0; q < 7; ++q) sol[q] = 0.5f * (m.geoms[i_ga].sol_params[q] + m.geoms[i_gb].sol_params[q]);
-        e.c_link()[i_c] = m.geoms[i_ga].link; e.c_link()[MAXC + i_c] = m.geoms[i_gb].link;
+#pragma unroll
+        for (int q = 0; q < 7; ++q) sol[q] = pc.sol[q];
+        e.c_link()[i_c] = pc.link_a; e.c_link()[MAXC + i_c] = pc.link_b;
       } else {
         atomicOr(&e.err()[0], GO2SIM_ERR_OVERFLOW_COLLISION_PAIRS);
       }
@@ -2756,6 +2804,7 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
       convex_pair = m.geoms[i_gb].type != GEOM_TERRAIN && !plane_box;
     }
     any_plane_box |= team_ballot<T>(plane_box) != 0ull;
+    const PairConst pc = load_pair_const(i_ga, i_gb);
     if constexpr (T == 16) {
       // MPR of every pair on its own lane; then the pairs whose MPR answer has to be replaced by safe GJK + EPA (narrowphase.py:727-845) are
       // answered by QUADS: the four quads of the team take four flagged pairs at a time (the four feet of a landing robot), the four lanes of a
@@ -2801,7 +2850,7 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
       }
       if (convex_pair) cc_rest(m, e, cst, cs, nullptr, &s->gjk_slot_mask, &gjk_scratch[(size_t)b * T + tl], s->ncv);
     } else if (convex_pair) convex_convex_contact_staged(m, e, i_ga, i_gb, cs, s->gjk, &s->gjk_slot_mask, &gjk_scratch[(size_t)b * T + tl], s->ncv);
-    append_staged(cs, i_ga, i_gb);
+    append_staged(cs, i_ga, i_gb, pc);
   }
   // ---- func_narrow_phase_convex_specializations (narrowphase.py:1146-1170; collider.py:486-498): plane-box pairs, after all convex-convex
   //      contacts and before the terrain pass; one lane per pair, same ordered compaction ----
@@ -2816,7 +2865,7 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
         if (m.geoms[i_ga].type > m.geoms[i_gb].type) { int t = i_ga; i_ga = i_gb; i_gb = t; }
         if (m.geoms[i_ga].type == GEOM_PLANE && m.geoms[i_gb].type == GEOM_BOX) plane_box_contact_staged(m, e, i_ga, i_gb, cs);
       }
-      append_staged(cs, i_ga, i_gb);
+      append_staged(cs, i_ga, i_gb, load_pair_const(i_ga, i_gb));
     }
   }
   // ---- func_narrow_phase_any_vs_terrain (narrowphase.py:1197-1244): appended after all convex-convex contacts.  One lane per heightfield
@@ -2992,7 +3041,7 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
     }
   }
   if (tl == 0) {
-    e.n_broad()[0] = n_broad; e.n_contacts()[0] = imn(nc_run, m.max_contact_pairs);
+    e.n_contacts()[0] = imn(nc_run, m.max_contact_pairs);
     s->cnt[0] = imn(nc_run, m.max_contact_pairs);
   }
   team_sync();
@@ -4420,7 +4469,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   constexpr int EPW = 64 / T;
   constexpr size_t SOLVE_OFF = (sizeof(SolverData<RLN>) * EPW + 15) / 16 * 16, DYN_OFF = (sizeof(DynData) * EPW + 15) / 16 * 16, KIN_OFF = (sizeof(KinData) * EPW + 15) / 16 * 16;   // the DMA targets behind the blocks: 16-byte aligned
   constexpr size_t SOLVE_BYTES = SOLVE_OFF + lds_dma_bytes(SOLVER_BLOCK_BYTES);
-  constexpr size_t DYN_BYTES = DYN_OFF + MODELS_LDS_BYTES + sizeof(KinSeparate<KIN_OVERLAY, EPW>);
+  constexpr size_t KSEP_OFF = (sizeof(KinSeparate<KIN_OVERLAY, EPW>) + 15) / 16 * 16;
+  constexpr size_t DYN_BYTES = DYN_OFF + MODELS_LDS_BYTES + (BROAD_OVERLAY<T> ? sizeof(KinSeparate<KIN_OVERLAY, EPW>) : KSEP_OFF + sizeof(BroadSeparate<false, T>));
   constexpr size_t KIN_BYTES = KIN_OFF + MODELS_LDS_BYTES;
   __shared__ alignas(16) char raw[cmax(SOLVE_BYTES, WITH_DYN ? DYN_BYTES : KIN_BYTES)];
   const int tl = threadIdx.x % T, slot = threadIdx.x / T;
@@ -4438,7 +4488,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     DynData* lds_d = (DynData*)raw;
     char* ms_raw = raw + DYN_OFF;
     auto& lds_k = *(KinSeparate<KIN_OVERLAY, EPW>*)(ms_raw + MODELS_LDS_BYTES);
-    integrate_fk_dynamics_body<T>(P, mp, b, lds_d, ms_raw, lds_k, pre, pre_vel, pre_acc);
+    auto& lds_b = *(BroadSeparate<BROAD_OVERLAY<T>, T>*)(ms_raw + MODELS_LDS_BYTES + KSEP_OFF);   // (an empty struct when the working set is overlaid)
+    integrate_fk_dynamics_body<T>(P, mp, gm, b, lds_d, ms_raw, lds_k, lds_b, pre, pre_vel, pre_acc);
   } else {
     integrate_fk_body<T>(P, mp, b, (KinData*)raw, raw + KIN_OFF, pre, pre_vel, pre_acc);
   }
@@ -4787,12 +4838,14 @@ __global__ __launch_bounds__(WG) void k_env_pre(Pool P, const Model* __restrict_
 // Same arithmetic per element as k_env_pre (go2_env_walk.py:985-1023, _apply_push :872-906).
 template <int T>
 __global__ __launch_bounds__(64) void k_pre_dynamics_team(Pool P, const ModelS* __restrict__ mp, const DCfg cv, const Glob* __restrict__ gp,
-                                                          const float* __restrict__ actions_in, uint64_t seed, uint32_t step_count, int write_idx) {
+                                                          const float* __restrict__ actions_in, uint64_t seed, uint32_t step_count, int write_idx,
+                                                          const Model* __restrict__ gm) {
   STAMP(STK_PRE_DYN)
   static_assert(T >= NA, "one lane per action");
   constexpr int EPW = 64 / T;
-  __shared__ DynData lds[EPW];
+  __shared__ alignas(16) DynData lds[EPW];
   __shared__ alignas(16) char ms_raw[MODELS_LDS_BYTES];
+  __shared__ BroadSeparate<BROAD_OVERLAY<T>, T> lds_b;
   const ModelS& ms = *(const ModelS*)ms_raw;
   wg_dma_to_lds<(int)sizeof(ModelS)>(ms_raw, mp);
   {
@@ -4921,6 +4974,7 @@ __global__ __launch_bounds__(64) void k_pre_dynamics_team(Pool P, const ModelS* 
   team_sync();
   PH(20)
   tk_dynamics<T>(m, e, s, tl, env_valid);
+  if (env_valid) tk_broadphase<T>(*gm, e, lds_b.at(slot, s), tl);       // for the collision launch that follows
 }
 
 struct RewCtx { float link_vel_xy[8], foot_z[4], foot_xy[8]; float vel_world[3]; int was_reset; };
@@ -6053,7 +6107,6 @@ constexpr int TIMING_RING = 2048;
 struct Launch {
   void* func; dim3 grid, block;
   int cat;                                        // timing class (T_DYN ... T_ENV_POST)
-  bool join;                                      // step graph: this node also waits for the node in front of its predecessor, which starts as a second root
   std::vector<void*> args;                        // the stored argument values (add_launch)
 };
 struct LaunchList {
@@ -6104,9 +6157,6 @@ struct go2sim {
   int graph_fallbacks = 0;                  // times the graph path was abandoned for plain launches (go2sim_graph_status)
   bool fuse_fk_dyn = true;                  // k_integrate_fk_dynamics_team between the substeps of a scene step (GO2SIM_NO_FUSE=1: separate launches)
   bool fuse_solve_int = true;               // k_solve_integrate_team: the solve and the kinematics (+ next dynamics) after it in one launch (GO2SIM_NO_FUSE_SOLVE=1: separate)
-  bool par_pre = false;                     // step graph: the first collision pass as a second root beside the pre-physics / dynamics launch (GO2SIM_PAR_PRE=1).
-                                            // Measured slower than the chain (window 10.26 vs 10.40 M, default run 14.84 vs 15.24 M, stairs 7.51 vs 7.61 M env-steps/s):
-                                            // the dynamics wavefronts take SIMDs from the collision pass instead of waiting for its early finishers
   int dyn_team = 32;                        // lanes per environment in k_dynamics_team
   int fk_team = 16;                         // lanes per environment in k_integrate_fk_team / k_fk_team
   int collide_team = 16;                    // lanes per environment in k_collide_team
@@ -6180,7 +6230,7 @@ static bool fuse_solve(const go2sim* h) { return h->fuse_solve_int && h->fuse_fk
 template <class... P, class... A>
 static void add_launch(LaunchList& L, int cat, void (*kernel)(P...), dim3 grid, dim3 block, A... a) {
   static_assert(sizeof...(P) == sizeof...(A), "argument count");
-  Launch e{(void*)kernel, grid, block, cat, false, {}};
+  Launch e{(void*)kernel, grid, block, cat, {}};
   auto store = [&](auto typed) { using T = decltype(typed); T* m = (T*)malloc(sizeof(T)); memcpy((void*)m, (const void*)&typed, sizeof(T)); L.owned.push_back((void*)m); e.args.push_back((void*)m); };
   (store(static_cast<P>(a)), ...);
   L.v.push_back(std::move(e));
@@ -6189,13 +6239,17 @@ struct StepIO { const float* actions; float *obs, *priv, *rew; uint8_t* reset; f
 // n substeps of RigidSolver.substep (rigid_solver.py:1116-1184): dynamics | collide, solve | integrate+FK, where the integrate of substep i and the
 // dynamics of substep i + 1 share a launch.  With `io` the list is the whole env step: the pre-physics part in front (alone, k_env_pre, or inside the
 // first dynamics launch), the post-physics launches behind.  This is the one place that says which kernels a step runs, in which shape and order.
+// The collision pass is split over two launches: every dynamics pass (k_pre_dynamics_team / k_dynamics_team, the dynamics tail of
+// k_solve_integrate_team<.., true> / k_integrate_fk_dynamics_team) ends with the broad phase of the state it works on (tk_broadphase: AABBs, clearing
+// of the old contacts, the persistent sort, the pair list in e.broad()), and the k_collide_team that follows it -- every collision launch has exactly
+// one dynamics pass in front -- is the narrow phase on that list.  So the list is a strict chain: no launch may run beside its predecessor.
 static void build_launch_list(const go2sim* h, LaunchList& L, int n, const StepIO* io) {
   const dim3 ge = grid_for(h->B), b(WG);
   const bool terrain = h->hm.terrain_enabled != 0;
-  auto add_dynamics = [&]() { add_launch(L, T_DYN, dynamics_kernel(h->dyn_team), team_grid(h, h->dyn_team), b, h->P, h->dms); };
+  auto add_dynamics = [&]() { add_launch(L, T_DYN, dynamics_kernel(h->dyn_team), team_grid(h, h->dyn_team), b, h->P, h->dms, h->dm); };
   if (io) L.pre = 0;
   if (io && fuse_pre(h)) {
-    add_launch(L, T_DYN, pre_dynamics_kernel(h->dyn_team), team_grid(h, h->dyn_team), b, h->P, h->dms, h->hcfg, h->dglob, io->actions, h->seed, h->step_count, h->action_write_idx);
+    add_launch(L, T_DYN, pre_dynamics_kernel(h->dyn_team), team_grid(h, h->dyn_team), b, h->P, h->dms, h->hcfg, h->dglob, io->actions, h->seed, h->step_count, h->action_write_idx, h->dm);
   } else {
     if (io) add_launch(L, T_ENV_PRE, k_env_pre, ge, b, h->P, h->dm, h->hcfg, h->dglob, io->actions, h->seed, h->step_count, h->action_write_idx);
     add_dynamics();
@@ -6211,15 +6265,10 @@ static void build_launch_list(const go2sim* h, LaunchList& L, int n, const StepI
     add_launch(L, T_COLLIDE, collide_kernel(h->collide_team), team_grid(h, h->collide_team), b, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, solver_epw(h));
     const int Ts = terrain ? h->terrain_solver_team : h->solver_team;
     add_launch(L, T_SOLVE, solve_kernel(terrain, Ts, fuse_solve(h) ? (more ? 1 : 2) : 0), team_grid(h, Ts), b, h->P, h->dm, h->dms, h->solver_ovf, lpt_cur, lpt_next, h->lpt_cap);
-    // The first collision pass reads nothing the pre-physics / dynamics launch writes (geom poses, sort buffers and the normal cache come from the end of the
-    // previous step): it can be a second ROOT of the graph, and the first solve joins the two.  The collision launch is as long as its slowest workgroup
-    // (landing window: mean 42 us, span 66 us, one wave per SIMD with the whole register file); the dynamics wavefronts take the SIMDs its early finishers
-    // leave.  Tried and measured slower: off unless GO2SIM_PAR_PRE=1 (go2sim::par_pre).
-    L.v.back().join = io && i == 0 && fuse_pre(h) && h->par_pre;
     if (fuse_solve(h)) continue;
     if (more && h->fuse_fk_dyn) {                 // (accounted with the integrate class)
       const int Td = h->dyn_team == 64 ? 64 : 32;
-      add_launch(L, T_INTEGRATE, integrate_dynamics_kernel(Td), team_grid(h, Td), b, h->P, h->dms);
+      add_launch(L, T_INTEGRATE, integrate_dynamics_kernel(Td), team_grid(h, Td), b, h->P, h->dms, h->dm);
     } else {
       add_launch(L, T_INTEGRATE, integrate_kernel(h->fk_team), team_grid(h, h->fk_team), b, h->P, h->dms);
       if (more) add_dynamics();
@@ -6257,7 +6306,7 @@ static void run_substeps(go2sim* h, hipStream_t s, int n) {
   h->lpt_parity ^= n & 1;
 }
 
-// executor 2: the list as an explicitly built hipGraph, a chain in list order (but see Launch::join)
+// executor 2: the list as an explicitly built hipGraph, a chain in list order
 static hipKernelNodeParams node_params(const Launch& e) {
   hipKernelNodeParams kp{};
   kp.func = e.func; kp.gridDim = e.grid; kp.blockDim = e.block; kp.sharedMemBytes = 0; kp.kernelParams = (void**)e.args.data(); kp.extra = nullptr;
@@ -6266,13 +6315,10 @@ static hipKernelNodeParams node_params(const Launch& e) {
 static bool step_graph_build(LaunchList& L) {
   if (hipGraphCreate(&L.graph, 0) != hipSuccess) return false;
   L.nodes.assign(L.v.size(), nullptr);
-  hipGraphNode_t last = nullptr, side = nullptr;
+  hipGraphNode_t last = nullptr;
   for (size_t i = 0; i < L.v.size(); ++i) {
-    if (i + 1 < L.v.size() && L.v[i + 1].join) { side = last; last = nullptr; }
-    hipGraphNode_t deps[2] = {last, L.v[i].join ? side : nullptr};
-    const int n_deps = (last ? 1 : 0) + ((last && deps[1]) ? 1 : 0);
     const hipKernelNodeParams kp = node_params(L.v[i]);
-    if (hipGraphAddKernelNode(&L.nodes[i], L.graph, n_deps ? deps : nullptr, n_deps, &kp) != hipSuccess) return false;
+    if (hipGraphAddKernelNode(&L.nodes[i], L.graph, last ? &last : nullptr, last ? 1 : 0, &kp) != hipSuccess) return false;
     last = L.nodes[i];
   }
   return hipGraphInstantiate(&L.exec, L.graph, nullptr, nullptr, 0) == hipSuccess;
@@ -6311,7 +6357,6 @@ static void read_knobs(go2sim* h) {
   if (env_int("GO2SIM_NO_GRAPH", 0)) h->use_graph = false;
   if (env_int("GO2SIM_NO_FUSE", 0)) h->fuse_fk_dyn = false;
   if (env_int("GO2SIM_NO_FUSE_SOLVE", 0)) h->fuse_solve_int = false;
-  if (env_int("GO2SIM_PAR_PRE", 0)) h->par_pre = true;
   if (env_int("GO2SIM_NO_LPT", 0)) h->use_lpt = false;
 }
 
