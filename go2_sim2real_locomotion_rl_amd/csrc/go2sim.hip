@@ -19,6 +19,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -743,17 +745,21 @@ DEV void wg_load(const Pool& P, int b0, int off, F put) {
 constexpr int PH_MAX_WG = 8192;
 __device__ unsigned long long g_phase_cycles[PH_MAX_WG * 64];
 #define PH_BEGIN unsigned long long ph_t = __builtin_readcyclecounter();
-#define PH(i) { __builtin_amdgcn_s_waitcnt(0); unsigned long long ph_n = __builtin_readcyclecounter(); if (threadIdx.x == 0 && blockIdx.x < PH_MAX_WG) g_phase_cycles[blockIdx.x * 64 + (i)] += ph_n - ph_t; ph_t = __builtin_readcyclecounter(); }
+#define PH(i) { __builtin_amdgcn_s_waitcnt(0); unsigned long long ph_n = __builtin_readcyclecounter(); if (threadIdx.x == 0 && blockIdx.x < PH_MAX_WG / 2) g_phase_cycles[blockIdx.x * 64 + (i)] += ph_n - ph_t; ph_t = __builtin_readcyclecounter(); }
 // the same inside lane-divergent code: the first active lane of the wavefront accounts the section (all active lanes run it together)
 #define PHD_BEGIN unsigned long long phd_t = __builtin_readcyclecounter();
-#define PHD(i) { unsigned long long phd_n = __builtin_readcyclecounter(); const unsigned long long phd_a = __ballot(1); if ((int)threadIdx.x == __ffsll((long long)phd_a) - 1 && blockIdx.x < PH_MAX_WG) { atomicAdd(&g_phase_cycles[blockIdx.x * 64 + (i)], phd_n - phd_t); atomicAdd(&g_phase_cycles[blockIdx.x * 64 + (i) + 1], 1ull); } phd_t = __builtin_readcyclecounter(); }
-#define PHC(i, n) { if (threadIdx.x == 0 && blockIdx.x < PH_MAX_WG) g_phase_cycles[blockIdx.x * 64 + (i)] += (unsigned long long)(n); }   // event counter
+#define PHD(i) { unsigned long long phd_n = __builtin_readcyclecounter(); const unsigned long long phd_a = __ballot(1); if ((int)threadIdx.x == __ffsll((long long)phd_a) - 1 && blockIdx.x < PH_MAX_WG / 2) { atomicAdd(&g_phase_cycles[blockIdx.x * 64 + (i)], phd_n - phd_t); atomicAdd(&g_phase_cycles[blockIdx.x * 64 + (i) + 1], 1ull); } phd_t = __builtin_readcyclecounter(); }
+#define PHC(i, n) { if (threadIdx.x == 0 && blockIdx.x < PH_MAX_WG / 2) g_phase_cycles[blockIdx.x * 64 + (i)] += (unsigned long long)(n); }   // event counter
+// k_env_post_b_team: the 64 ids of a row are taken, so its marks go to the upper half of the rows (workgroup w: row PH_MAX_WG / 2 + w, ids from 0);
+// PH / PHD / PHC of the other kernels are confined to the lower half (they use at most 2048 rows at 4096 envs)
+#define PHB(i) { __builtin_amdgcn_s_waitcnt(0); unsigned long long ph_n = __builtin_readcyclecounter(); if (threadIdx.x == 0 && blockIdx.x < PH_MAX_WG / 2) g_phase_cycles[(PH_MAX_WG / 2 + blockIdx.x) * 64 + (i)] += ph_n - ph_t; ph_t = __builtin_readcyclecounter(); }
 #else
 #define PH_BEGIN
 #define PH(i)
 #define PHD_BEGIN
 #define PHD(i)
 #define PHC(i, n)
+#define PHB(i)
 #endif
 
 // ---- optional wall-clock stamps per workgroup (build with -DGO2SIM_STAMP; tools/launch_overhead.py): every workgroup of the step kernels records
@@ -5021,21 +5027,36 @@ DEV RewGates reward_gates(const RewState& rs) {
   g.moving = (dm_sqrt(c0 * c0 + c1 * c1) > 0.1f) ? 1.0f : 0.0f;
   return g;
 }
-DEV float reward_term(const Model& m, const DCfg& c, RewState& rs, int id, const RewCtx& rc, const RewGates& gt) {
-  const float dt = c.f[GO2SIM_FC_DT];
+// The configuration words the walk / stairs terms read, fetched in one batch ahead of the term loop (load_rew_k): inside the loop every one of them
+// was a scalar round trip of its own -- the twelve force ranges two dependent ones (motor dof index, then the model's dof record).
+struct RewK { float dt, sigma, lin_vel_z_deadzone, base_height_target, feet_air_time_target, feet_height_target; float def[NM], force_lo[NM], force_hi[NM]; int na, use_terrain; };
+DEV RewK load_rew_k(const Model& m, const DCfg& c) {
+  RewK K;
+  K.dt = c.f[GO2SIM_FC_DT]; K.sigma = c.f[GO2SIM_FC_TRACKING_SIGMA]; K.lin_vel_z_deadzone = c.f[GO2SIM_FC_LIN_VEL_Z_DEADZONE];
+  K.base_height_target = c.f[GO2SIM_FC_BASE_HEIGHT_TARGET]; K.feet_air_time_target = c.f[GO2SIM_FC_FEET_AIR_TIME_TARGET]; K.feet_height_target = c.f[GO2SIM_FC_FEET_HEIGHT_TARGET];
+  K.na = c.i[GO2SIM_IC_NUM_ACTIONS]; K.use_terrain = c.i[GO2SIM_IC_USE_TERRAIN];
+#pragma unroll
+  for (int i = 0; i < NM; ++i) {
+    const int d = c.i[GO2SIM_IC_MOTOR_DOF0 + i];
+    K.def[i] = c.f[GO2SIM_FC_DEFAULT_DOF_POS0 + i]; K.force_lo[i] = m.dofs[d].force_range[0]; K.force_hi[i] = m.dofs[d].force_range[1];
+  }
+  return K;
+}
+DEV float reward_term(const Model& m, const DCfg& c, const RewK& K, RewState& rs, int id, const RewCtx& rc, const RewGates& gt) {
+  const float dt = K.dt;
   const float* cmd = rs.cmd; const float* blv = rs.blv; const float* bav = rs.bav; const float* dof_pos = rs.dof_pos; const float* dof_vel = rs.dof_vel;
   float c0 = cmd[0], c1 = cmd[1], c2 = cmd[2];
   const float still = gt.still, moving = gt.moving;
   switch (id) {
-    case GO2SIM_R_TRACKING_LIN_VEL: { float d0 = c0 - blv[0], d1 = c1 - blv[1]; return dm_exp(-(d0 * d0 + d1 * d1) / c.f[GO2SIM_FC_TRACKING_SIGMA]); }
-    case GO2SIM_R_TRACKING_ANG_VEL: { float d = c2 - bav[2]; return dm_exp(-(d * d) / c.f[GO2SIM_FC_TRACKING_SIGMA]); }
+    case GO2SIM_R_TRACKING_LIN_VEL: { float d0 = c0 - blv[0], d1 = c1 - blv[1]; return dm_exp(-(d0 * d0 + d1 * d1) / K.sigma); }
+    case GO2SIM_R_TRACKING_ANG_VEL: { float d = c2 - bav[2]; return dm_exp(-(d * d) / K.sigma); }
     case GO2SIM_R_LIN_VEL_Z: {                                       // go2_env_stair.py:1615-1626 (deadzone 0 = walk env)
-      float v = blv[2], dz = c.f[GO2SIM_FC_LIN_VEL_Z_DEADZONE];
+      float v = blv[2], dz = K.lin_vel_z_deadzone;
       if (dz > 0.0f) { float ex = fmx(dm_abs(v) - dz, 0.0f); return ex * ex; }
       return v * v;
     }
     case GO2SIM_R_ACTION_RATE: {
-      float s = 0.0f; const int na = c.i[GO2SIM_IC_NUM_ACTIONS];
+      float s = 0.0f; const int na = K.na;
 #pragma unroll
       for (int i = 0; i < NA; ++i) if (i < na) { float d = rs.last_actions[i] - rs.actions[i]; s = s + d * d; }
       return s;
@@ -5043,13 +5064,13 @@ DEV float reward_term(const Model& m, const DCfg& c, RewState& rs, int id, const
     case GO2SIM_R_SIMILAR_TO_DEFAULT: {
       float s = 0.0f;
 #pragma unroll
-      for (int i = 0; i < NM; ++i) s = s + dm_abs(dof_pos[i] - c.f[GO2SIM_FC_DEFAULT_DOF_POS0 + i]);
+      for (int i = 0; i < NM; ++i) s = s + dm_abs(dof_pos[i] - K.def[i]);
       return s;
     }
     case GO2SIM_R_BASE_HEIGHT: {                                     // go2_env_stair.py:1634-1648: height above the local terrain
       float hgt = rs.base_pos[2];
-      if (c.i[GO2SIM_IC_USE_TERRAIN]) hgt = rs.base_pos[2] - terrain_height(m, c, rs.base_pos[0], rs.base_pos[1]);
-      float d = hgt - c.f[GO2SIM_FC_BASE_HEIGHT_TARGET]; return d * d;
+      if (K.use_terrain) hgt = rs.base_pos[2] - terrain_height(m, c, rs.base_pos[0], rs.base_pos[1]);
+      float d = hgt - K.base_height_target; return d * d;
     }
     case GO2SIM_R_DOF_ACC: {
       float s = 0.0f;
@@ -5068,7 +5089,7 @@ DEV float reward_term(const Model& m, const DCfg& c, RewState& rs, int id, const
     case GO2SIM_R_STAND_STILL: {
       float s = 0.0f;
 #pragma unroll
-      for (int i = 0; i < NM; ++i) s = s + dm_abs(dof_pos[i] - c.f[GO2SIM_FC_DEFAULT_DOF_POS0 + i]);
+      for (int i = 0; i < NM; ++i) s = s + dm_abs(dof_pos[i] - K.def[i]);
       return s * still;
     }
     case GO2SIM_R_STAND_STILL_VEL: { float a = blv[0], b2 = blv[1], w = bav[2]; float lin = a * a + b2 * b2; float ang = w * w; return (lin + 0.5f * ang) * still; }
@@ -5084,7 +5105,7 @@ DEV float reward_term(const Model& m, const DCfg& c, RewState& rs, int id, const
       for (int i = 0; i < 4; ++i) { float a = rs.fat[i]; int ct = rs.fc[i]; first[i] = (a > 0.0f && ct) ? 1.0f : 0.0f; a = a + dt; a = a * (ct ? 0.0f : 1.0f); rs.fat[i] = a; at[i] = a; }
       float s = 0.0f;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) s = s + (at[i] - c.f[GO2SIM_FC_FEET_AIR_TIME_TARGET]) * first[i];
+      for (int i = 0; i < 4; ++i) s = s + (at[i] - K.feet_air_time_target) * first[i];
       return s * moving;
     }
     case GO2SIM_R_FOOT_SLIP: {
@@ -5100,8 +5121,8 @@ DEV float reward_term(const Model& m, const DCfg& c, RewState& rs, int id, const
         float vx = rc.link_vel_xy[2 * i], vy = rc.link_vel_xy[2 * i + 1];
         float vn = dm_sqrt(vx * vx + vy * vy);
         float fz = rc.foot_z[i];
-        if (c.i[GO2SIM_IC_USE_TERRAIN]) fz = rc.foot_z[i] - terrain_height(m, c, rc.foot_xy[2 * i], rc.foot_xy[2 * i + 1]);   // go2_env_stair.py:1742-1747
-        float he = c.f[GO2SIM_FC_FEET_HEIGHT_TARGET] - fz; he = he * he;
+        if (K.use_terrain) fz = rc.foot_z[i] - terrain_height(m, c, rc.foot_xy[2 * i], rc.foot_xy[2 * i + 1]);   // go2_env_stair.py:1742-1747
+        float he = K.feet_height_target - fz; he = he * he;
         pen = pen + (rs.fc[i] ? 0.0f : 1.0f) * he * vn;
       }
       return pen * moving;
@@ -5116,8 +5137,7 @@ DEV float reward_term(const Model& m, const DCfg& c, RewState& rs, int id, const
       float s = 0.0f;
 #pragma unroll
       for (int i = 0; i < NM; ++i) {
-        int d = c.i[GO2SIM_IC_MOTOR_DOF0 + i];
-        float tau = clampf(rs.ctrl_force[i], m.dofs[d].force_range[0], m.dofs[d].force_range[1]);
+        float tau = clampf(rs.ctrl_force[i], K.force_lo[i], K.force_hi[i]);
         s = s + ((id == GO2SIM_R_ENERGY) ? dm_abs(tau * dof_vel[i]) : dm_abs(tau));
       }
       return s;
@@ -5171,10 +5191,17 @@ DEV void env_globals_body(const DCfg& c, Glob& g, Acc* acc, uint64_t seed, int c
 // are dealt to the waves (term k runs on one wave, its value goes to LDS), and wave 0 then adds them in the reference's order and makes every store.
 // The three terms that touch env state beyond their own value (feet_air_time writes and feet_stance reads _feet_air_time, go2_env_walk.py:1303-1314;
 // forward_progress moves _last_base_pos_x) stay together on wave 0, in order.  Same operations per value and the same sum order: results unchanged.
-// (Eight wavefronts measured slower: two 215-register wavefronts per SIMD get in each other's way.)
+// Which wave runs a term is decided on the host, once per configuration (deal_terms): wave 0 -- the wave that also makes every store and the sum -- keeps
+// only the stateful terms; the others go to the worker waves heaviest first, each to the least loaded worker, by the instruction counts of reward_term_cost.
+// (A wave runs its terms once, on cold code: what a term costs is roughly its length.  The former round-robin `(1 + j) % POST_A_NWAVES` gave wave 0 of the
+// walk's 19 terms dof_acc, foot_clearance, stand_still and base_height on top of its own two.)
+// (Wave count: eight wavefronts measured slower with the round-robin deal -- two 215-register wavefronts per SIMD get in each other's way; four, six and
+// eight were measured again with the deal by cost: DESIGN.md, round 7, profiles/r07_post_a_waves.txt.)
 constexpr int POST_A_NWAVES = 4;
+struct TermDeal { uint32_t w[NREW / 8]; uint32_t tracking; };       // owner wave of term k: four bits each; bit k of `tracking`: term k is a tracking term
+static_assert(NREW == 32 && POST_A_NWAVES >= 2 && POST_A_NWAVES <= 16, "TermDeal holds four bits per term");
 __global__ __launch_bounds__(WG * POST_A_NWAVES) void k_env_post_a(Pool P, const Model* __restrict__ mp, const DCfg cv, Glob* gp,
-                                                   Acc* acc, uint64_t seed, uint32_t step_count) {
+                                                   Acc* acc, uint64_t seed, uint32_t step_count, const TermDeal deal) {
   STAMP(STK_POST_A)
   __shared__ float s_es[NREW][WG], s_r[NREW][WG];
   const int ln = threadIdx.x % WG, wv = threadIdx.x / WG;
@@ -5284,23 +5311,19 @@ __global__ __launch_bounds__(WG * POST_A_NWAVES) void k_env_post_a(Pool P, const
   const float fat0[4] = {rs.fat[0], rs.fat[1], rs.fat[2], rs.fat[3]};
   const float last_x0 = rs.last_x;
   const RewGates gates = reward_gates(rs);
-  if (!base_env) {                                                   // the terms, dealt to the waves: stateful ones on wave 0, the others round-robin
-    int id_next = c.i[GO2SIM_IC_REWARD_ID0]; float scale_next = c.f[GO2SIM_FC_REWARD_SCALE0];
-    int j = 0;
+  if (!base_env) {                                                   // the terms, dealt to the waves (deal_terms): stateful ones on wave 0, in list order
+    const RewK K = load_rew_k(m, c);
+    const uint32_t dw[NREW / 8] = {deal.w[0], deal.w[1], deal.w[2], deal.w[3]};
     for (int k = 0; k < nrew; ++k) {
-      const int id = id_next; const float scale = scale_next;
-      { const int kn = (k + 1 < NREW) ? k + 1 : k; id_next = c.i[GO2SIM_IC_REWARD_ID0 + kn]; scale_next = c.f[GO2SIM_FC_REWARD_SCALE0 + kn]; }   // the table reads of the next term overlap this one
-      const bool stateful = id == GO2SIM_R_FEET_AIR_TIME || id == GO2SIM_R_FEET_STANCE || id == GO2SIM_R_FORWARD_PROGRESS;
-      const int owner = stateful ? 0 : (1 + j) % POST_A_NWAVES;
-      j += stateful ? 0 : 1;
-      if (wv == owner) s_r[k][ln] = reward_term(m, c, rs, id, rc, gates) * scale;
+      const uint32_t word = (k < 16) ? ((k < 8) ? dw[0] : dw[1]) : ((k < 24) ? dw[2] : dw[3]);
+      if (wv != (int)((word >> ((k & 7) * 4)) & 15u)) continue;       // (a wave reads the table entries of its own terms only)
+      s_r[k][ln] = reward_term(m, c, K, rs, c.i[GO2SIM_IC_REWARD_ID0 + k], rc, gates) * c.f[GO2SIM_FC_REWARD_SCALE0 + k];
     }
   }
   __syncthreads();
   PH(14)
   if (!w0) return;                                                   // the rest is wave 0's: the sum in the reference's order, the statistics, the stores
   for (int k = 0; k < nrew; ++k) {
-    const int id = c.i[GO2SIM_IC_REWARD_ID0 + k];
     float es = s_es[k][ln];
     if (!base_env) {
       const float r = s_r[k][ln];
@@ -5308,7 +5331,7 @@ __global__ __launch_bounds__(WG * POST_A_NWAVES) void k_env_post_a(Pool P, const
       es = es + r;
       s_es[k][ln] = es;
     }
-    if (id == GO2SIM_R_TRACKING_LIN_VEL || id == GO2SIM_R_TRACKING_ANG_VEL) tracking_int = tracking_int + es;
+    if ((deal.tracking >> k) & 1u) tracking_int = tracking_int + es;   // tracking_lin_vel / tracking_ang_vel (deal_terms)
   }
   if (rst) {
     float ep_steps = fmx((float)ep_len, 1.0f);
@@ -5324,16 +5347,10 @@ __global__ __launch_bounds__(WG * POST_A_NWAVES) void k_env_post_a(Pool P, const
   __threadfence();
   __builtin_amdgcn_wave_barrier();                                   // (only wave 0 is left: its lanes are the workgroup's 64 envs)
   PH(16)
-  if (threadIdx.x == 0) {
-    const int ticket = atomicAdd(&acc->done, 1);
-    if (ticket == (int)gridDim.x - 1) {
-      __threadfence();
-      acc->done = 0;
-      env_globals_body(c, *gp, acc, seed, 1);
-    }
-  }
-  PH(17)
-  // the per-term outputs go out last: nothing in this kernel reads them back, and the fence above then only waits for the statistics
+  int ticket = 0;
+  if (threadIdx.x == 0) ticket = atomicAdd(&acc->done, 1);
+  // the per-term outputs go out last: nothing in this kernel reads them back, the fence above then only waits for the statistics, and they are issued
+  // while the ticket is on its way
   if (!base_env) {
     e.rew()[0] = rew;
     auto rew_terms = e.rew_terms(); auto episode_sums = e.episode_sums();
@@ -5343,6 +5360,12 @@ __global__ __launch_bounds__(WG * POST_A_NWAVES) void k_env_post_a(Pool P, const
     for (int i = 0; i < 4; ++i) if (rs.fat[i] != fat0[i]) fat[i] = rs.fat[i];
     if (rs.last_x != last_x0) e.last_base_pos_x()[0] = rs.last_x;
   }
+  if (threadIdx.x == 0 && ticket == (int)gridDim.x - 1) {
+    __threadfence();
+    acc->done = 0;
+    env_globals_body(c, *gp, acc, seed, 1);
+  }
+  PH(17)
 }
 
 // Go2Env.reset: mark every env for reset + statistics (go2_env_walk.py:1242-1245)
@@ -5772,7 +5795,13 @@ __global__ __launch_bounds__(GAIN_WG) void k_env_engine_gains(Pool P, Model* __r
 // copies.  Team kernel: T lanes per env.  The reset (rare, serial) runs on lane 0; the 49 observations are produced four per lane (one
 // Philox block of noise each), the privileged tail one entry per lane, and the [n_envs, k] outputs are written with coalesced rows.
 // sources of the walk-layout observation vectors, staged into LDS in one batch (k_env_post_b_team)
-enum { PB_BAV = 0, PB_PG = 3, PB_GOFF = 6, PB_CMD = 9, PB_DP = 12, PB_DV = 24, PB_ACT = 36, PB_BLV = 52, PB_KP = 55, PB_KD = 67, PB_MS = 79, PB_PUSH = 91, PB_N = 94 };
+// (PB_DEF: the default pose of the configuration; PB_GLOB: friction, mass_shift, com_shift[3], leg_mass_shift[4] of Glob -- fetched in the same batch, so the
+// assembly reads every operand from LDS)
+enum { PB_BAV = 0, PB_PG = 3, PB_GOFF = 6, PB_CMD = 9, PB_DP = 12, PB_DV = 24, PB_ACT = 36, PB_BLV = 52, PB_KP = 55, PB_KD = 67, PB_MS = 79, PB_PUSH = 91,
+       PB_REW = 94, PB_TIMEOUT = 95, PB_ACTIONS = 96, PB_POOL_N = 112, PB_DEF = 112, PB_GLOB = 124, PB_N = 133 };
+static_assert(offsetof(Glob, mass_shift) - offsetof(Glob, friction) == 1 * sizeof(float) && offsetof(Glob, com_shift) - offsetof(Glob, friction) == 2 * sizeof(float) &&
+              offsetof(Glob, leg_mass_shift) - offsetof(Glob, friction) == 5 * sizeof(float) && sizeof(((Glob*)nullptr)->com_shift) == 3 * sizeof(float) &&
+              sizeof(((Glob*)nullptr)->leg_mass_shift) == 4 * sizeof(float), "PB_GLOB: friction, mass_shift, com_shift[3], leg_mass_shift[4] of Glob, contiguous and in this order");
 DEV int post_b_src_off(int k) {
   int off = FO(base_ang_vel) + k;
   off = (k >= PB_PG) ? FO(projected_gravity) + k - PB_PG : off;
@@ -5786,6 +5815,9 @@ DEV int post_b_src_off(int k) {
   off = (k >= PB_KD) ? FO(kd_factors) + k - PB_KD : off;
   off = (k >= PB_MS) ? FO(motor_strength) + k - PB_MS : off;
   off = (k >= PB_PUSH) ? FO(current_push_force) + k - PB_PUSH : off;
+  off = (k >= PB_REW) ? FO(rew) : off;                                 // what the copies at the end of the kernel read
+  off = (k >= PB_TIMEOUT) ? FO(time_out) : off;
+  off = (k >= PB_ACTIONS) ? FO(actions) + k - PB_ACTIONS : off;
   return off;
 }
 // Two wavefronts per workgroup over the SAME 64 / T envs: wavefront 0 resets the flagged envs and writes the observations; wavefront 1 exists for the steps on
@@ -5804,6 +5836,8 @@ __global__ __launch_bounds__(128) void k_env_post_b_team(Pool P, const Model* __
   __shared__ KinData fk_lds[EPW];
   __shared__ alignas(16) char ms_raw[MODELS_LDS_BYTES];
   const bool fk_needed = gp->n_reset_now > 0;
+  // the configuration words of the common path, requested with the reset count (one scalar round trip, not one per use)
+  const int na = cp->i[GO2SIM_IC_NUM_ACTIONS], nobs = cp->i[GO2SIM_IC_NUM_OBS], npriv = cp->i[GO2SIM_IC_NUM_PRIV_OBS], env_kind = cp->i[GO2SIM_IC_ENV_KIND];
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
   if (wave == 1) {
     if (!fk_needed) return;
@@ -5826,6 +5860,7 @@ __global__ __launch_bounds__(128) void k_env_post_b_team(Pool P, const Model* __
     return;
   }
   const bool valid = b < P.B;                                          // (lanes beyond the batch stay with their wavefront up to its ONE barrier)
+  PH_BEGIN                                                             // (profiling builds: wavefront 0's sections 0 reset, 1 staging + draws, 2 observations, 3 privileged tail, 4 copies)
   const Model& m = *mp; const DCfg& c = *cp; const Glob& g = *gp;
   E e(P, valid ? b : P.B - 1);
   auto fk_refresh = [&]() {};                                          // (done by wavefront 1)
@@ -5846,9 +5881,9 @@ __global__ __launch_bounds__(128) void k_env_post_b_team(Pool P, const Model* __
     team_sync();
   }
   if (fk_needed) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __syncthreads(); }   // hand the reset state over to the FK wavefront
+  PHB(0)
   if (!valid) return;
-  const int na = c.i[GO2SIM_IC_NUM_ACTIONS], nobs = c.i[GO2SIM_IC_NUM_OBS], npriv = c.i[GO2SIM_IC_NUM_PRIV_OBS];
-  if (c.i[GO2SIM_IC_ENV_KIND] == 1) {                                  // go2_env_base.py:165-196: rewards after the reset, 45 observations
+  if (env_kind == 1) {                                                 // go2_env_base.py:165-196: rewards after the reset, 45 observations
     if (tl == 0) {
       RewCtx rc; rc.was_reset = was_reset;
       auto bvw = e.base_vel_world();
@@ -5863,9 +5898,10 @@ __global__ __launch_bounds__(128) void k_env_post_b_team(Pool P, const Model* __
       }
       float rew = 0.0f;
       const RewGates gates = reward_gates(rs);
+      const RewK K = load_rew_k(m, c);
       auto rew_terms = e.rew_terms(); auto episode_sums = e.episode_sums();
       for (int k = 0; k < c.i[GO2SIM_IC_N_REWARDS]; ++k) {
-        float r = reward_term(m, c, rs, c.i[GO2SIM_IC_REWARD_ID0 + k], rc, gates) * c.f[GO2SIM_FC_REWARD_SCALE0 + k];
+        float r = reward_term(m, c, K, rs, c.i[GO2SIM_IC_REWARD_ID0 + k], rc, gates) * c.f[GO2SIM_FC_REWARD_SCALE0 + k];
         rew_terms[k] = r;
         rew = rew + r;
         episode_sums[k] = episode_sums[k] + r;
@@ -5896,16 +5932,40 @@ __global__ __launch_bounds__(128) void k_env_post_b_team(Pool P, const Model* __
     fk_refresh();
     return;
   }
-  // every source of the two observation vectors is fetched in one batch (the assembly below would otherwise pay a memory round trip per entry)
+  // every source of the two observation vectors is fetched in one batch (the assembly below would otherwise pay a memory round trip per entry): the env's
+  // buffers, the default pose and the DR words of Glob.  The loads are issued first; the constants of the assembly and the noise draws of this lane's block
+  // (functions of seed, env, step and block alone) are formed while they are in flight, then the values go to LDS.
   __shared__ float pb_src[EPW][PB_N + 2];
   float* src = pb_src[slot];
-  team_stage<PB_N, T>(tl, [&](int k) { return gload(e, post_b_src_off(k), 0); }, [&](int k, float v) { src[k] = v; });
-  team_sync();
+  constexpr int PB_ROUNDS = (PB_N + T - 1) / T;
+  float stg[PB_ROUNDS];
+#pragma unroll
+  for (int r = 0; r < PB_ROUNDS; ++r) {
+    int k = r * T + tl; k = k < PB_N ? k : PB_N - 1;
+    const float* p = (k < PB_POOL_N) ? e.f + (size_t)post_b_src_off(k) * e.B : (k < PB_GLOB) ? &c.f[GO2SIM_FC_DEFAULT_DOF_POS0 + k - PB_DEF] : (const float*)((const char*)&g + offsetof(Glob, friction)) + (k - PB_GLOB);
+    stg[r] = *p;
+  }
+  const int delay_steps = e.delay_steps()[0];          // (privileged entry 54; with the batch, not in a round trip of its own)
   const bool noisy = c.i[GO2SIM_IC_HAS_OBS_NOISE] && c.d[GO2SIM_FC_OBS_NOISE_LEVEL_MAX] > 0.0;
   const double lvl = g.obs_noise_level_cur;          // python-float products, rounded on assignment into the float32 noise vector
+  const float s_ang = c.f[GO2SIM_FC_OBS_SCALE_ANG_VEL], s_lin = c.f[GO2SIM_FC_OBS_SCALE_LIN_VEL], s_dp = c.f[GO2SIM_FC_OBS_SCALE_DOF_POS], s_dv = c.f[GO2SIM_FC_OBS_SCALE_DOF_VEL];
+  const float nv_ang = (float)(c.d[GO2SIM_FC_OBS_NOISE_ANG_VEL] * c.d[GO2SIM_FC_OBS_SCALE_ANG_VEL] * lvl), nv_grav = (float)(c.d[GO2SIM_FC_OBS_NOISE_GRAVITY] * lvl);
+  const float nv_dp = (float)(c.d[GO2SIM_FC_OBS_NOISE_DOF_POS] * c.d[GO2SIM_FC_OBS_SCALE_DOF_POS] * lvl), nv_dv = (float)(c.d[GO2SIM_FC_OBS_NOISE_DOF_VEL] * c.d[GO2SIM_FC_OBS_SCALE_DOF_VEL] * lvl);
+  const bool per_env_dr = c.i[GO2SIM_IC_PER_ENV_GLOBAL_DR] != 0;
+  float n0[4] = {0.0f, 0.0f, 0.0f, 0.0f};              // the draws of block `tl` (the only block of this lane unless nobs > 4 T)
+  if (noisy && tl * 4 < nobs) {
+    dm_u4 r = rng4(seed, RNG_OBS_NOISE, b, step_count, tl);
+    dm_normal2(r.v[0], r.v[1], &n0[0], &n0[1]); dm_normal2(r.v[2], r.v[3], &n0[2], &n0[3]);
+  }
+#pragma unroll
+  for (int r = 0; r < PB_ROUNDS; ++r) { int k = r * T + tl; k = k < PB_N ? k : PB_N - 1; src[k] = stg[r]; }
+  team_sync();
+  PHB(1)
+  // No branch per group: the source slot, the scale and the noise scale of an entry are selected from its index (in registers; no descriptor table is kept), and the value is formed
+  // by the group's own expression ((a - d) * s, a + b, a * s or a copy: `x - 0` and `x + 0` are not neutral for -0, so the forms stay apart).
   for (int blk = tl; blk * 4 < nobs; blk += T) {
-    float n[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (noisy) {
+    float n[4] = {n0[0], n0[1], n0[2], n0[3]};
+    if (noisy && blk != tl) {
       dm_u4 r = rng4(seed, RNG_OBS_NOISE, b, step_count, blk);
       dm_normal2(r.v[0], r.v[1], &n[0], &n[1]); dm_normal2(r.v[2], r.v[3], &n[2], &n[3]);
     }
@@ -5914,11 +5974,15 @@ __global__ __launch_bounds__(128) void k_env_post_b_team(Pool P, const Model* __
       int i = 4 * blk + k;
       if (i < nobs) {
         float v, nv = 0.0f;
-        if (i < 3) { v = src[PB_BAV + i] * c.f[GO2SIM_FC_OBS_SCALE_ANG_VEL]; nv = (float)(c.d[GO2SIM_FC_OBS_NOISE_ANG_VEL] * c.d[GO2SIM_FC_OBS_SCALE_ANG_VEL] * lvl); }
-        else if (i < 6) { v = src[PB_PG + i - 3] + src[PB_GOFF + i - 3]; nv = (float)(c.d[GO2SIM_FC_OBS_NOISE_GRAVITY] * lvl); }
-        else if (i < 9) { v = src[PB_CMD + i - 6] * ((i - 6 < 2) ? c.f[GO2SIM_FC_OBS_SCALE_LIN_VEL] : c.f[GO2SIM_FC_OBS_SCALE_ANG_VEL]); nv = 0.0f; }
-        else if (i < 21) { v = (src[PB_DP + i - 9] - c.f[GO2SIM_FC_DEFAULT_DOF_POS0 + i - 9]) * c.f[GO2SIM_FC_OBS_SCALE_DOF_POS]; nv = (float)(c.d[GO2SIM_FC_OBS_NOISE_DOF_POS] * c.d[GO2SIM_FC_OBS_SCALE_DOF_POS] * lvl); }
-        else if (i < 33) { v = src[PB_DV + i - 21] * c.f[GO2SIM_FC_OBS_SCALE_DOF_VEL]; nv = (float)(c.d[GO2SIM_FC_OBS_NOISE_DOF_VEL] * c.d[GO2SIM_FC_OBS_SCALE_DOF_VEL] * lvl); }
+        if (i < 33) {
+          const int a = (i < 3) ? PB_BAV + i : (i < 6) ? PB_PG + i - 3 : (i < 9) ? PB_CMD + i - 6 : (i < 21) ? PB_DP + i - 9 : PB_DV + i - 21;
+          const float x = src[a];
+          const float s = (i < 3) ? s_ang : (i < 8) ? s_lin : (i < 9) ? s_ang : (i < 21) ? s_dp : s_dv;
+          nv = (i < 3) ? nv_ang : (i < 6) ? nv_grav : (i < 9) ? 0.0f : (i < 21) ? nv_dp : nv_dv;
+          if (i >= 3 && i < 6) v = x + src[PB_GOFF + i - 3];
+          else if (i >= 9 && i < 21) v = (x - src[PB_DEF + i - 9]) * s;
+          else v = x * s;
+        }
         else { v = (i - 33 < na) ? src[PB_ACT + i - 33] : gload(e, FO(obs), i); }
         if (noisy) v = v + n[k] * nv;
         gstore(e, FO(obs), i, v); gstore(e, FO(priv), i, v);
@@ -5927,23 +5991,23 @@ __global__ __launch_bounds__(128) void k_env_post_b_team(Pool P, const Model* __
       }
     }
   }
-  // privileged tail (go2_env_walk.py:1115-1143)
+  PHB(2)
+  // privileged tail (go2_env_walk.py:1115-1143): entries 0..53 are copies of staged words (the first three scaled); the configuration words of the loop are read ahead of it
+  const int max_delay = c.i[GO2SIM_IC_MAX_DELAY], base_link = c.i[GO2SIM_IC_BASE_LINK], use_terrain = c.i[GO2SIM_IC_USE_TERRAIN], scan_n = c.i[GO2SIM_IC_SCAN_N], n_terrain_rows = c.i[GO2SIM_IC_N_TERRAIN_ROWS];
   for (int i = nobs + tl; i < npriv; i += T) {
     int j = i - nobs;
     float v; bool write = true;
-    if (j < 3) v = src[PB_BLV + j] * c.f[GO2SIM_FC_OBS_SCALE_LIN_VEL];
-    else if (j < 4) v = c.i[GO2SIM_IC_PER_ENV_GLOBAL_DR] ? gload(e, FO(geom_friction), NG - 1) : g.friction;
-    else if (j < 16) v = src[PB_KP + j - 4];
-    else if (j < 28) v = src[PB_KD + j - 16];
-    else if (j < 40) v = src[PB_MS + j - 28];
-    else if (j < 41) v = c.i[GO2SIM_IC_PER_ENV_GLOBAL_DR] ? gload(e, FO(mass_shift), c.i[GO2SIM_IC_BASE_LINK]) : g.mass_shift;
-    else if (j < 44) v = g.com_shift[j - 41];
-    else if (j < 48) v = g.leg_mass_shift[j - 44];
-    else if (j < 51) v = src[PB_GOFF + j - 48];
-    else if (j < 54) v = src[PB_PUSH + j - 51];
-    else if (j < 55) { write = c.i[GO2SIM_IC_MAX_DELAY] > 0; v = write ? (float)e.delay_steps()[0] / (float)c.i[GO2SIM_IC_MAX_DELAY] : gload(e, FO(priv), i); }
-    else if (c.i[GO2SIM_IC_USE_TERRAIN] && j == 55) v = (float)e.terrain_row()[0] / (float)imx(1, c.i[GO2SIM_IC_N_TERRAIN_ROWS] - 1);   // go2_env_stair.py:1466-1472
-    else if (c.i[GO2SIM_IC_USE_TERRAIN] && j - 56 < c.i[GO2SIM_IC_SCAN_N] && 56 + c.i[GO2SIM_IC_SCAN_N] <= npriv - nobs) {        // _compute_height_scan :772-803
+    if (j < 54) {
+      const int a = (j < 3) ? PB_BLV + j : (j < 4) ? PB_GLOB : (j < 16) ? PB_KP + j - 4 : (j < 28) ? PB_KD + j - 16 : (j < 40) ? PB_MS + j - 28
+                  : (j < 48) ? PB_GLOB + 1 + j - 40 : (j < 51) ? PB_GOFF + j - 48 : PB_PUSH + j - 51;   // 40: mass_shift, 41..43: com_shift, 44..47: leg_mass_shift
+      const float x = src[a];
+      v = (j < 3) ? x * s_lin : x;
+      if (per_env_dr && j == 3) v = gload(e, FO(geom_friction), NG - 1);
+      if (per_env_dr && j == 40) v = gload(e, FO(mass_shift), base_link);
+    }
+    else if (j < 55) { write = max_delay > 0; v = write ? (float)delay_steps / (float)max_delay : gload(e, FO(priv), i); }
+    else if (use_terrain && j == 55) v = (float)e.terrain_row()[0] / (float)imx(1, n_terrain_rows - 1);   // go2_env_stair.py:1466-1472
+    else if (use_terrain && j - 56 < scan_n && 56 + scan_n <= npriv - nobs) {        // _compute_height_scan :772-803
       auto bq = e.base_quat(); auto bp = e.base_pos();
       float qw = bq[0], qx = bq[1], qy = bq[2], qz = bq[3];
       float yaw = dm_atan2(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz));
@@ -5958,14 +6022,16 @@ __global__ __launch_bounds__(128) void k_env_post_b_team(Pool P, const Model* __
     if (write) gstore(e, FO(priv), i, v);
     if (priv_out) priv_out[(size_t)b * npriv + i] = v;
   }
-  for (int i = tl; i < na; i += T) gstore(e, FO(last_actions), i, gload(e, FO(actions), i));
+  PHB(3)
+  for (int i = tl; i < na; i += T) gstore(e, FO(last_actions), i, src[PB_ACTIONS + i]);
   for (int i = tl; i < NM; i += T) gstore(e, FO(last_dof_vel), i, src[PB_DV + i]);
   if (tl == 0) {
-    if (rew_out) rew_out[b] = e.rew()[0];
+    if (rew_out) rew_out[b] = src[PB_REW];
     if (reset_out) reset_out[b] = (uint8_t)was_reset;
-    if (timeout_out) timeout_out[b] = e.time_out()[0];
+    if (timeout_out) timeout_out[b] = src[PB_TIMEOUT];
   }
   fk_refresh();
+  PHB(4)
 }
 
 __global__ __launch_bounds__(WG) void k_init_state(Pool P, const Model* __restrict__ mp, int keep_dr) {
@@ -6235,6 +6301,52 @@ static void add_launch(LaunchList& L, int cat, void (*kernel)(P...), dim3 grid, 
   (store(static_cast<P>(a)), ...);
   L.v.push_back(std::move(e));
 }
+// ---- which wave of k_env_post_a runs which reward term -----------------------------------------------------------------------------------------
+// Vector instructions of a term as reward_term writes it (counted from the source: an IEEE division ~12, a square root ~10, dm_exp ~25, a height lookup on
+// the heightfield ~150; the twelve-motor loops 3-5 per motor).  Only the proportions matter, and only for speed: no result depends on the deal.  Estimates, not
+// measured cycles; a term added to reward_term needs its line here (an id without one is taken as a handful of operations).
+static int reward_term_cost(int id, bool terrain) {
+  switch (id) {
+    case GO2SIM_R_TRACKING_LIN_VEL: return 45;
+    case GO2SIM_R_TRACKING_ANG_VEL: return 40;
+    case GO2SIM_R_LIN_VEL_Z: return 6;
+    case GO2SIM_R_BASE_HEIGHT: return terrain ? 160 : 6;
+    case GO2SIM_R_ACTION_RATE: return 50;
+    case GO2SIM_R_SIMILAR_TO_DEFAULT: case GO2SIM_R_STAND_STILL: case GO2SIM_R_JOINT_TRACKING: return 40;
+    case GO2SIM_R_DOF_ACC: return 200;                               // twelve divisions
+    case GO2SIM_R_DOF_VEL: return 25;
+    case GO2SIM_R_FOOT_SLIP: return 25;
+    case GO2SIM_R_FOOT_CLEARANCE: return terrain ? 700 : 90;         // four square roots (+ four height lookups)
+    case GO2SIM_R_ENERGY: return 65;
+    case GO2SIM_R_TORQUE_LOAD: return 50;
+    case GO2SIM_R_STAND_STILL_VEL: return 10;
+    default: return 5;                                               // a handful of operations
+  }
+}
+// Stateful terms (feet_air_time, feet_stance, forward_progress: they read or move env state that another of them reads) stay on wave 0, which runs its
+// terms in list order.  The others: heaviest first (ties: list order), each to the worker wave 1 .. POST_A_NWAVES - 1 with the least work so far (ties:
+// the lowest wave).  Every term computes the same value on any wave, and wave 0 adds them in list order: the deal does not enter a result.
+static TermDeal deal_terms(const DCfg& c) {
+  TermDeal d = {{0, 0, 0, 0}, 0};
+  const int n = c.i[GO2SIM_IC_N_REWARDS] < NREW ? c.i[GO2SIM_IC_N_REWARDS] : NREW;
+  const bool terrain = c.i[GO2SIM_IC_USE_TERRAIN] != 0;
+  int order[NREW], cost[NREW], m = 0, load[POST_A_NWAVES] = {0};
+  for (int k = 0; k < n; ++k) {
+    const int id = c.i[GO2SIM_IC_REWARD_ID0 + k];
+    if (id == GO2SIM_R_TRACKING_LIN_VEL || id == GO2SIM_R_TRACKING_ANG_VEL) d.tracking |= 1u << k;
+    if (id == GO2SIM_R_FEET_AIR_TIME || id == GO2SIM_R_FEET_STANCE || id == GO2SIM_R_FORWARD_PROGRESS) continue;   // owner 0
+    cost[k] = reward_term_cost(id, terrain);
+    order[m++] = k;
+  }
+  std::stable_sort(order, order + m, [&](int a, int b) { return cost[a] > cost[b]; });
+  for (int t = 0; t < m; ++t) {
+    int w = 1;
+    for (int v = 2; v < POST_A_NWAVES; ++v) if (load[v] < load[w]) w = v;
+    load[w] += cost[order[t]];
+    d.w[order[t] >> 3] |= (uint32_t)w << ((order[t] & 7) * 4);
+  }
+  return d;
+}
 struct StepIO { const float* actions; float *obs, *priv, *rew; uint8_t* reset; float* timeout; };   // what go2sim_env_step is handed per step
 // n substeps of RigidSolver.substep (rigid_solver.py:1116-1184): dynamics | collide, solve | integrate+FK, where the integrate of substep i and the
 // dynamics of substep i + 1 share a launch.  With `io` the list is the whole env step: the pre-physics part in front (alone, k_env_pre, or inside the
@@ -6276,7 +6388,7 @@ static void build_launch_list(const go2sim* h, LaunchList& L, int n, const StepI
   }
   if (!io) return;
   L.post_a = (int)L.v.size();
-  add_launch(L, T_ENV_POST, k_env_post_a, ge, dim3(WG * POST_A_NWAVES), h->P, h->dm, h->hcfg, h->dglob, h->dacc, h->seed, h->step_count);
+  add_launch(L, T_ENV_POST, k_env_post_a, ge, dim3(WG * POST_A_NWAVES), h->P, h->dm, h->hcfg, h->dglob, h->dacc, h->seed, h->step_count, deal_terms(h->hcfg));
   if (h->hcfg.i[GO2SIM_IC_USE_TERRAIN]) add_launch(L, T_ENV_POST, k_env_terrain_rows, dim3((h->B + 255) / 256), dim3(256), h->P, h->dcfg, h->dglob, h->seed);
   L.post_b = (int)L.v.size();
   add_launch(L, T_ENV_POST, k_env_post_b_team<16>, dim3((h->B + 3) / 4), dim3(128), h->P, h->dm, h->dms, h->dcfg, h->dglob, h->seed, h->step_count, io->obs, io->priv, io->rew, io->reset, io->timeout);
@@ -6355,6 +6467,7 @@ static void read_knobs(go2sim* h) {
   team("GO2SIM_SOLVER_TEAM", 16, &h->solver_team);
   team("GO2SIM_TERRAIN_SOLVER_TEAM", 32, &h->terrain_solver_team);
   if (env_int("GO2SIM_NO_GRAPH", 0)) h->use_graph = false;
+  { const int g = env_int("GO2SIM_GRAPH", -1); if (g == 0) h->use_graph = false; else if (g == 1) h->use_graph = true; }   // names the executor outright (1: the step graph, 0: plain launches), whatever the default
   if (env_int("GO2SIM_NO_FUSE", 0)) h->fuse_fk_dyn = false;
   if (env_int("GO2SIM_NO_FUSE_SOLVE", 0)) h->fuse_solve_int = false;
   if (env_int("GO2SIM_NO_LPT", 0)) h->use_lpt = false;

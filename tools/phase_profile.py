@@ -71,14 +71,23 @@ if len(sys.argv) > 3 and sys.argv[3] == "decouple":
     print(f"  collide + solver only    : sum of slowest workgroups {S2_all.mean():9.0f}   longest per-env chain {C2_all.mean():9.0f}   gap {100 * (1 - C2_all.mean() / S2_all.mean()):5.1f} %")
     print("  (integrate_fk: the T = 16 launch of the second substep is attributed with the T = 32 map; it is constant-time, so the gap is unaffected)")
     raise SystemExit(0)
+POST_B = [0, 1, 2, 3, 4]     # k_env_post_b_team keeps its own rows (the upper half, PHB in csrc/go2sim.hip): 0 reset, 1 staging + draws, 2 observations, 3 privileged tail, 4 copies
 if len(sys.argv) > 3 and sys.argv[3] == "each":
     # one read-out per env step: what a single launch waits for is its slowest workgroup, which per-run sums average away
-    rows = {g: [] for g in GROUPS_}
-    worst = {g: None for g in GROUPS_}
+    rows = {g: [] for g in list(GROUPS_) + ["post_b"]}
+    worst = {g: None for g in list(GROUPS_) + ["post_b"]}
     for s in range(W, W + N):
         sim.env_step(act[s], obs, priv, rew, rst, to)
         lib.lib.go2sim_debug_phases(sim.h, out, 1)
         a = np.frombuffer(out, dtype=np.uint64).reshape(PH_MAX_WG, 64).astype(np.float64)
+        ab, a = a[PH_MAX_WG // 2:], a[:PH_MAX_WG // 2]
+        tot = ab[:, POST_B].sum(1)
+        if (tot > 0).any():
+            srt = np.sort(tot[tot > 0])
+            rows["post_b"].append((srt.mean(), srt[int(0.99 * len(srt))], srt[int(0.999 * len(srt))], srt[-1]))
+            i = int(np.argmax(tot))
+            if worst["post_b"] is None or tot[i] > worst["post_b"][0]:
+                worst["post_b"] = (tot[i], {k: ab[i, k] for k in POST_B}, {})
         for g, ids in GROUPS_.items():
             tot = a[:, ids].sum(1) / (1 if g == "post_a" else 2)                                  # two launches per env step (fused kernels: their phases land in both groups)
             used = tot > 0
