@@ -337,16 +337,146 @@ class RigidRef:
             dirs.append(dirn)
         return np.array(rows), np.array(dirs)
 
-    def limit_rows(self, qpos):
-        """Rows of the violated joint limits in joint order: +1 below the lower limit, -1 above the upper one."""
+    def limit_rows(self, qpos, limit=None):
+        """Rows of the violated joint limits in joint order: +1 below the lower limit, -1 above the upper one (limit: other bounds than the
+        model's float64 ones, e.g. the float32 numbers the library stores)."""
         rows = []
+        limit = self.limit if limit is None else limit
         for J in self.joints:
             if J["type"] != JOINT_REVOLUTE:
                 continue
             d, q = J["dof_start"], qpos[J["q_start"]]
-            lo, hi = q - self.limit[d, 0], self.limit[d, 1] - q
+            lo, hi = q - limit[d, 0], limit[d, 1] - q
             if min(lo, hi) < 0:
                 r = np.zeros(self.nd)
                 r[d] = 1.0 if lo < hi else -1.0
                 rows.append(r)
         return np.array(rows).reshape(-1, self.nd)
+
+    def inverse_weights(self):
+        """Inverse weights at qpos0 with M = inertia + armature (no damping term): per link the means of the translational and of the rotational
+        diagonal of J M^-1 J^T (J at the link's centre of mass), per dof the diagonal of M^-1 (a free joint: averaged over its three translations
+        and over its three rotations), and the mean inertia trace(M) / nd."""
+        k = self.fk(self.qpos0)
+        M = self.mass_matrix(k, implicit=False)
+        Minv = np.linalg.inv(M)
+        link = np.zeros((self.nl, 2))
+        for l in range(self.nl):
+            Jv, Jw = self.jac(k, l, k["c"][l])
+            link[l] = np.diag(Jv @ Minv @ Jv.T).mean(), np.diag(Jw @ Minv @ Jw.T).mean()
+        dof = np.diag(Minv).copy()
+        for J in self.joints:
+            if J["type"] == JOINT_FREE:
+                ds = J["dof_start"]
+                dof[ds:ds + 3] = dof[ds:ds + 3].mean()
+                dof[ds + 3:ds + 6] = dof[ds + 3:ds + 6].mean()
+        return link, dof, np.trace(M) / self.nd
+
+    def contact_params(self, geom_a, geom_b, friction, ratio):
+        """(mu, the seven solver parameters, inverse weight) of a contact between two geoms.  friction, ratio: per-geom arrays of one env.
+        mu = max(friction_a ratio_a, friction_b ratio_b, 0.01); the solver parameters are the mean of the two geoms'; the inverse weight is the
+        sum of the two links' translational inverse weights (a fixed link such as the ground has none).  The model's values are taken as the
+        float32 numbers the library stores."""
+        ga, gb = self.m["geoms"][geom_a], self.m["geoms"][geom_b]
+        mu = max(float(friction[geom_a]) * float(ratio[geom_a]), float(friction[geom_b]) * float(ratio[geom_b]), 0.01)
+        sol = 0.5 * (_f32(ga["sol_params"]) + _f32(gb["sol_params"]))
+        w = sum(float(_f32(self.links[g["link"]]["invweight"][0])) for g in (ga, gb) if not self.links[g["link"]]["is_fixed"])
+        return mu, sol, w
+
+    def constraint_problem(self, k, qpos, vel, contacts, friction, ratio):
+        """The constraint rows of one env at the start of a substep.  k: fk() of the state, qpos / vel: the state (vel: the velocity the substep
+        starts from), contacts: a list of (geom_a, geom_b, pos, normal, penetration) in the library's order, friction / ratio: per-geom arrays.
+        Rows: four per contact in contact order, then one per violated joint limit in joint order.  Returns a dict with J (n x nd), aref, D = 1 / diag,
+        imp, branch (BRANCH_*), and is_limit per row."""
+        eps = float(_f32(self.m["eps"]))
+        vel = np.asarray(vel, np.float64)
+        J, aref, D, imp, branch, is_limit = [], [], [], [], [], []
+        for ga, gb, pos, normal, pen in contacts:
+            mu, sol, w = self.contact_params(ga, gb, friction, ratio)
+            rows, _ = self.contact_rows(k, self.m["geoms"][ga]["link"], self.m["geoms"][gb]["link"], pos, normal, mu)
+            for r in rows:
+                im, ar, br = imp_aref(sol, -float(pen), r @ vel)
+                J.append(r); aref.append(ar); imp.append(im); branch.append(br); is_limit.append(False)
+                D.append(1.0 / max((w + mu * mu * w) * 2.0 * mu * mu * (1.0 - im) / im, eps))
+        lim32 = _f32(self.limit)
+        for r in self.limit_rows(qpos, lim32):
+            d = int(np.flatnonzero(r)[0])
+            joint = next(Jn for Jn in self.joints if Jn["dof_start"] == d)
+            q = float(qpos[joint["q_start"]])
+            delta = min(q - lim32[d, 0], lim32[d, 1] - q)
+            im, ar, br = imp_aref(_f32(joint["sol_params"]), delta, r @ vel)
+            J.append(r); aref.append(ar); imp.append(im); branch.append(br); is_limit.append(True)
+            D.append(1.0 / max(float(_f32(self.dofs[d]["invweight"])) * (1.0 - im) / im, eps))
+        return dict(J=np.array(J).reshape(-1, self.nd), aref=np.array(aref), D=np.array(D), imp=np.array(imp), branch=np.array(branch, int),
+                    is_limit=np.array(is_limit, bool))
+
+
+def _f32(x):
+    """x as the library holds it: rounded to float32, returned in float64."""
+    return np.asarray(x, np.float32).astype(np.float64)
+
+
+# ---------------------------------------------------------------------------------------------------- the constraint law
+BRANCH_LOW, BRANCH_HIGH, BRANCH_SAT = 0, 1, 2      # x = |pos| / width below mid, between mid and 1, beyond 1
+
+
+def impedance(sol, pos):
+    """(impedance, branch) at the constraint position pos (contacts: minus the penetration, limits: the violation) from the solver parameters
+    (timeconst, dampratio, dmin, dmax, width, mid, power): with x = |pos| / width and the unit curve y(x) = x^p / mid^(p-1) below mid,
+    1 - (1 - x)^p / (1 - mid)^(p-1) from mid to 1, the impedance is dmin + y (dmax - dmin) kept within [dmin, dmax], and dmax beyond x = 1."""
+    _, _, dmin, dmax, width, mid, power = (float(v) for v in sol)
+    x = abs(float(pos)) / width
+    if x > 1.0:
+        return dmax, BRANCH_SAT
+    if x < mid:
+        y, branch = x ** power / mid ** (power - 1.0), BRANCH_LOW
+    else:
+        y, branch = 1.0 - (1.0 - x) ** power / (1.0 - mid) ** (power - 1.0), BRANCH_HIGH
+    return min(max(dmin + y * (dmax - dmin), dmin), dmax), branch
+
+
+def imp_aref(sol, pos, vel):
+    """(impedance, reference acceleration, branch) of one row: aref = -b vel - k imp pos, the critically-scaled spring-damper with
+    b = 2 / (dmax timeconst) and k = 1 / (dmax timeconst dampratio)^2."""
+    timeconst, dampratio, _, dmax = (float(v) for v in sol[:4])
+    imp, branch = impedance(sol, pos)
+    b = 2.0 / (dmax * timeconst)
+    kk = 1.0 / (dmax * timeconst * dampratio) ** 2
+    return imp, -b * float(vel) - kk * imp * float(pos), branch
+
+
+def constraint_cost(M, a0, J, aref, D, a):
+    """1/2 (a - a0)^T M (a - a0) + 1/2 sum_i D_i min(0, (J a - aref)_i)^2."""
+    r = np.minimum(J @ a - aref, 0.0)
+    return 0.5 * (a - a0) @ M @ (a - a0) + 0.5 * (D * r) @ r
+
+
+def constraint_force(J, aref, D, a):
+    """The force of every row at the acceleration a: D_i max(0, -(J a - aref)_i)."""
+    return D * np.maximum(0.0, -(J @ a - aref))
+
+
+def solve_constraints(M, a0, J, aref, D, rtol=1e-10, max_iter=200):
+    """The minimiser of constraint_cost, a strictly convex piecewise quadratic: Newton on the active set (J a - aref)_i < 0 with a backtracking line
+    search, until the gradient is below rtol of the force scale max(|M| |a0| + |J|^T D (|J| |a0| + |aref|)).  Returns (a, cost, active set,
+    max |gradient| / force scale)."""
+    a = np.array(a0, np.float64)
+    fscale = (np.abs(M) @ np.abs(a0) + np.abs(J).T @ (D * (np.abs(J) @ np.abs(a0) + np.abs(aref)))).max() + 1e-300
+    cost = constraint_cost(M, a0, J, aref, D, a)
+    for _ in range(max_iter):
+        active = J @ a - aref < 0.0
+        g = M @ (a - a0) - J.T @ constraint_force(J, aref, D, a)
+        if np.abs(g).max() <= rtol * fscale:
+            break
+        Ja = J[active]
+        step = -np.linalg.solve(M + Ja.T @ (D[active, None] * Ja), g)
+        t = 1.0
+        while True:
+            c1 = constraint_cost(M, a0, J, aref, D, a + t * step)
+            if c1 <= cost + 1e-4 * t * (g @ step) or t < 1e-12:
+                break
+            t *= 0.5
+        a, cost = a + t * step, c1
+    else:
+        raise RuntimeError("solve_constraints: no convergence")
+    return a, cost, active, np.abs(g).max() / fscale

@@ -61,6 +61,24 @@ def test_invweight_sanity():
     assert 2.0 < m["meaninertia"] < 3.5
 
 
+MODEL_DIR = os.path.dirname(MODEL_JSON)
+
+
+@pytest.mark.parametrize("fname", sorted(f for f in os.listdir(MODEL_DIR) if f.endswith("_model.json")))
+def test_invweight_and_meaninertia_against_the_rigid_reference(fname):
+    """Every committed model: the link and dof inverse weights and the mean inertia equal those of tests/rigid_ref.py at qpos0 (world-frame point
+    Jacobians and M = sum m Jv^T Jv + Jw^T I Jw, not the compiler's COM-frame composite-body pass).  Both sides are float64: 1e-9 relative."""
+    from rigid_ref import RigidRef
+
+    m = load_model_json(os.path.join(MODEL_DIR, fname))
+    ref = RigidRef(m)
+    link, dof, meaninertia = ref.inverse_weights()
+    assert np.array([l["invweight"] for l in m["links"]]) == pytest.approx(link, rel=1e-9, abs=1e-300)
+    assert np.array([d["invweight"] for d in m["dofs"]]) == pytest.approx(dof, rel=1e-9)
+    assert m["meaninertia"] == pytest.approx(meaninertia, rel=1e-9)
+    assert all(w > 0 for l, L in zip(m["links"], ref.links) for w in l["invweight"] if not L["is_fixed"]), "every moving link has inverse weights"
+
+
 def test_collision_pairs():
     m = load_model_json()
     ng = 28

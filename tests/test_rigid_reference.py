@@ -5,10 +5,14 @@ algorithm to physics.  Each batch draws every state from its own seed: base quat
 non-unit stored quaternion), joint angles across and slightly outside the limits, realistic and large velocities (base |w| up to about 20 rad/s)
 and mass / COM shifts at and beyond the configured DR ranges.  Compared: (a) kinematics and COM-frame velocities, (b) the mass matrix, (c) the
 smooth force in force mode, in position mode with saturating PD and with an external wrench, (d) the smooth acceleration (arrow and row form),
-(e) the integrator, (f) the constraint force transpose and the KKT identity with contacts (flat ground and stairs) and joint limits.
+(e) the integrator, (f) the constraint phase with contacts (flat ground, stairs, and a batch of sub-millimetre penetrations and limit violations that
+reaches both polynomial branches of the impedance curve) and joint limits: the constraint force transpose and the KKT identity, the constraint LAW
+(every row's force is D max(0, -(J a - aref)) with aref, impedance, regulariser, friction / solver-parameter mixing and inverse weights rebuilt in
+float64 from the reference project's formulas) and the OPTIMUM (the acceleration is the minimiser of the convex constraint problem, found by an
+independent float64 Newton solve), cold and warm-started.
 
 The reference is first pinned by closed forms of its own (kinetic energy, a rigidly spinning robot, the double pendulum's Lagrangian, momentum
-and energy conservation along an accurate integration).
+and energy conservation along an accurate integration, the impedance curve at its knots, a unit mass on one constraint row).
 
 `-m gpu`: the same cases on the HIP library, bit-equal to the FAST ORDER oracle at default settings, and under every launch-shape knob
 (GO2SIM_{DYN,FK,COLLIDE,SOLVER}_TEAM, GO2SIM_TERRAIN_SOLVER_TEAM, GO2SIM_NO_LPT, GO2SIM_NO_FUSE, GO2SIM_NO_FUSE_SOLVE, GO2SIM_PAR_PRE).
@@ -20,7 +24,8 @@ import pytest
 
 from go2_sim2real_locomotion_rl_amd.capi import Go2Sim
 from go2_sim2real_locomotion_rl_amd.model_blob import load_model_json, pack_model
-from rigid_ref import RigidRef, mat_to_quat
+from rigid_ref import (BRANCH_HIGH, BRANCH_LOW, BRANCH_SAT, RigidRef, constraint_cost, constraint_force, imp_aref, impedance, mat_to_quat,
+                       solve_constraints)
 from util import F, install_stairs
 
 MODEL_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "go2_sim2real_locomotion_rl_amd", "model")
@@ -143,6 +148,105 @@ def test_ref_free_floating_conservation(name):
         assert abs(E(k2) - E(k0)) <= 1e-8 * E0
 
 
+SOLS = [(0.02, 1.0, 0.9, 0.95, 0.001, 0.5, 2.0), (0.05, 0.7, 0.2, 0.8, 0.01, 0.3, 3.0), (0.01, 1.3, 0.5, 0.99, 0.002, 0.8, 1.0)]
+
+
+@pytest.mark.parametrize("sol", SOLS)
+def test_ref_impedance_closed_forms(sol):
+    """The impedance is dmin at 0, dmax at and beyond the width, dmin + mid (dmax - dmin) at mid (the unit curve passes through (mid, mid)); it
+    is even in the position, continuous across mid and across the width, and monotone; each stretch reports its branch."""
+    _, _, dmin, dmax, width, mid, power = sol
+    assert impedance(sol, 0.0) == (dmin, BRANCH_LOW)
+    for x in (1.0, 1.0 + 1e-9, 3.0, 1e3):
+        imp, br = impedance(sol, -x * width)
+        assert imp == pytest.approx(dmax, rel=1e-14) and br == (BRANCH_HIGH if x == 1.0 else BRANCH_SAT)
+    imp_mid, br = impedance(sol, mid * width)
+    assert imp_mid == pytest.approx(dmin + mid * (dmax - dmin), rel=1e-14) and br == BRANCH_HIGH
+    h = 1e-9
+    below, above = impedance(sol, (mid - h) * width), impedance(sol, (mid + h) * width)
+    assert below[1] == BRANCH_LOW and above[1] == BRANCH_HIGH
+    assert abs(below[0] - imp_mid) <= 10 * h and abs(above[0] - imp_mid) <= 10 * h          # (slope of the unit curve at mid: power <= 3)
+    xs = np.linspace(0.0, 1.5, 301)
+    imps = np.array([impedance(sol, x * width)[0] for x in xs])
+    assert (np.diff(imps) >= 0).all() and imps[0] == dmin and imps[-1] == dmax
+    assert (np.diff(imps[xs < 1.0]) > 0).all(), "strictly increasing up to the width"
+    assert all(impedance(sol, x * width) == impedance(sol, -x * width) for x in xs)
+    if power == 2.0:                                                 # the two parabolas written out
+        assert impedance(sol, 0.25 * mid * width)[0] == pytest.approx(dmin + (dmax - dmin) * 0.0625 * mid, rel=1e-14)
+        x = 0.5 * (1 + mid)
+        assert impedance(sol, x * width)[0] == pytest.approx(dmin + (dmax - dmin) * (1 - 0.25 * (1 - mid)), rel=1e-14)
+
+
+@pytest.mark.parametrize("sol", SOLS)
+def test_ref_unit_mass_on_one_row(sol):
+    """A unit mass (inverse weight 1) on one limit-type row, diag = (1 - imp) / imp: the reference acceleration is the spring-damper
+    aref = -2 v / (dmax T) - imp pos / (dmax T zeta)^2, and where the row is active the minimiser of 1/2 (a - a0)^2 + 1/2 D (a - aref)^2 is
+    a = (1 - imp) a0 + imp aref -- the impedance is the fraction of the way from the free to the reference acceleration; where a0 >= aref the
+    row is inactive and a = a0."""
+    T, zeta, _, dmax = sol[:4]
+    rng = np.random.default_rng(5)
+    for x in (0.1, 0.45, 0.7, 0.99, 2.5):
+        pos, vel, a0 = -x * sol[4], rng.standard_normal() * 0.05, -9.81
+        imp, aref, _ = imp_aref(sol, pos, vel)
+        assert aref == pytest.approx(-2.0 * vel / (dmax * T) - imp * pos / (dmax * T * zeta) ** 2, rel=1e-14)
+        D = imp / (1.0 - imp)
+        M, J = np.eye(1), np.ones((1, 1))
+        a, cost, active, res = solve_constraints(M, np.array([a0]), J, np.array([aref]), np.array([D]))
+        assert aref > a0 and active[0] and res <= 1e-10
+        assert a[0] == pytest.approx((1 - imp) * a0 + imp * aref, rel=1e-12)
+        assert cost == pytest.approx(0.5 * imp * (aref - a0) ** 2, rel=1e-12)       # 1/2 (1 / (1 + 1 / D)) (aref - a0)^2
+        assert constraint_force(J, np.array([aref]), np.array([D]), a)[0] == pytest.approx(a[0] - a0, rel=1e-12)   # M (a - a0) = J^T force
+        a, cost, active, _ = solve_constraints(M, np.array([aref + 1.0]), J, np.array([aref]), np.array([D]))
+        assert a[0] == aref + 1.0 and cost == 0.0 and not active[0]
+
+
+def test_ref_contact_params():
+    """Friction is the larger of the two geoms' friction x ratio and at least 0.01; the solver parameters are the mean of the two geoms'; the
+    inverse weight is the sum of the two links' translational ones, the ground's link having none."""
+    import copy
+
+    m = copy.deepcopy(_model("go2"))
+    m["geoms"][15]["sol_params"] = [0.04, 0.5, 0.5, 0.75, 0.003, 0.25, 3.0]
+    ref = RigidRef(m)
+    ng = len(m["geoms"])
+    fric, ratio = np.linspace(0.5, 1.5, ng), np.ones(ng)
+    ratio[15], ratio[19] = 0.25, 2.0
+    w = lambda g: float(np.float32(m["links"][m["geoms"][g]["link"]]["invweight"][0]))   # noqa: E731
+    mu, sol, wt = ref.contact_params(0, 15, fric, ratio)
+    assert mu == max(fric[0], 0.25 * fric[15]) == 0.5 and wt == w(15) > 0
+    assert np.allclose(sol, [0.03, 0.75, 0.7, 0.85, 0.002, 0.375, 2.5], rtol=1e-7, atol=0)
+    mu, sol, wt = ref.contact_params(15, 19, fric, ratio)
+    assert mu == 2.0 * fric[19] and wt == w(15) + w(19)
+    assert ref.contact_params(0, 15, 0.001 * fric, ratio)[0] == 0.01
+    q = ref.qpos0.copy()
+    q[7:] += STAND_LEVEL                                              # (within every joint limit)
+    k = ref.fk(q)
+    contact = [(0, 15, k["p"][10], np.array([0.0, 0.0, 1.0]), 0.0005)]
+    P = ref.constraint_problem(k, q, np.zeros(ref.nd), contact, fric, ratio)
+    sol_mix = ref.contact_params(0, 15, fric, ratio)[1]
+    imp = impedance(sol_mix, -0.0005)[0]
+    assert P["J"].shape == (4, ref.nd) and (P["imp"] == imp).all() and (P["branch"] == BRANCH_LOW).all() and not P["is_limit"].any()
+    assert P["D"] == pytest.approx(1.0 / ((w(15) + 0.25 * w(15)) * 2 * 0.25 * (1 - imp) / imp), rel=1e-14)
+    assert P["aref"] == pytest.approx(imp * 0.0005 / (sol_mix[3] * sol_mix[0] * sol_mix[1]) ** 2, rel=1e-14)     # at rest: the spring term alone
+
+
+def test_ref_constraint_solver_on_random_problems():
+    """solve_constraints on random strictly convex problems with rows that switch during the solve: the returned point has a vanishing gradient
+    M (a - a0) = J^T force(a), and no point around it has a lower cost."""
+    rng = np.random.default_rng(6)
+    for n, nr in ((3, 2), (6, 9), (18, 40)):
+        A = rng.standard_normal((n, n))
+        M = A @ A.T + 0.1 * np.eye(n)
+        J, aref, D, a0 = rng.standard_normal((nr, n)), rng.standard_normal(nr) * 3, rng.uniform(0.1, 50.0, nr), rng.standard_normal(n) * 3
+        a, cost, active, res = solve_constraints(M, a0, J, aref, D)
+        force = constraint_force(J, aref, D, a)
+        assert res <= 1e-10 and 0 < active.sum() < nr and np.array_equal(active, force > 0)
+        assert np.abs(M @ (a - a0) - J.T @ force).max() <= 1e-9 * (np.abs(M) @ np.abs(a0)).max()
+        assert cost == pytest.approx(constraint_cost(M, a0, J, aref, D, a), rel=1e-14)
+        for _ in range(20):
+            assert constraint_cost(M, a0, J, aref, D, a + 1e-3 * rng.standard_normal(n)) > cost
+
+
 # ---------------------------------------------------------------------------------------------------- states and library access
 class Handle:
     """One simulator handle with numpy access to its fields, on the CPU oracle (numpy) or the HIP library (torch, cuda:0)."""
@@ -230,6 +334,49 @@ def _stand(ref):
     if ref.m.get("robot") == "go2":
         return [0, 0, 0, 0, 0.8, 0.8, 1.0, 1.0, -1.5, -1.5, -1.5, -1.5]
     return [0.0] * (ref.nd - 6)
+
+
+STAND_LEVEL = [0, 0, 0, 0, 0.9, 0.9, 0.9, 0.9, -1.5, -1.5, -1.5, -1.5]    # front and rear thighs alike: the four feet of a level go2 at one height
+SHALLOW_DEPTHS = (0.2e-3, 0.7e-3, 0.4e-3, 0.95e-3)                         # of the lowest foot sphere; the contact width of the impedance curve is 1 mm
+SHALLOW_LIMIT = (2e-4, 7e-4)                                                # rad past a limit; the width of the joints' curve is 1e-3 rad
+FOOT_RADIUS = 0.022
+
+
+def make_shallow_states(ref, B, seed):
+    """States of a robot standing level on flat ground at sub-millimetre penetrations, where the impedance is on its polynomial branches (a contact
+    deeper than the 1 mm width or a limit violation above 1e-3 rad takes the saturated value).  In periods of eight envs: the depth of the lowest
+    foot sphere is SHALLOW_DEPTHS[b % 4] (two below the midpoint of the curve, two above); envs 2, 3, 6, 7 have 0.05 rad of joint noise (one foot
+    down), the others none (several feet at one depth); envs 4-7 have one hip or calf joint SHALLOW_LIMIT[b % 2] past a limit.  The base height
+    comes from the reference's kinematics; velocities are small."""
+    assert ref.m.get("robot") == "go2"
+    nl, nd, nq = ref.nl, ref.nd, ref.nq
+    qpos = np.zeros((nq, B), np.float32); vel = np.zeros((nd, B)); ms = np.zeros((nl, B)); cs = np.zeros((nl, 3, B))
+    lim = ref.limit.astype(np.float32).astype(np.float64)[6:]
+    feet = [g for g in ref.m["geoms"] if g["type"] == 1 and g["data"][0] == FOOT_RADIUS]
+    assert len(feet) == 4
+    limit_joints = [(j, side) for j in (0, 1, 2, 3, 8, 9, 10, 11) for side in ((0, 1) if j < 4 else (1,))]   # hips both ways, calves at the upper (straight) end
+    for b in range(B):
+        rng = np.random.default_rng(seed + b)
+        q = ref.qpos0.copy()
+        q[7:] += STAND_LEVEL
+        if b % 4 >= 2:
+            q[7:] += 0.05 * rng.standard_normal(nd - 6)
+        q = q.astype(np.float32)
+        if b % 8 >= 4:
+            j, side = limit_joints[(b // 8 + b % 4 * 3) % len(limit_joints)]
+            over = SHALLOW_LIMIT[b % 2]
+            q[7 + j] = lim[j, 1] + over if side else lim[j, 0] - over
+        q[0:2] = rng.uniform(-0.5, 0.5, 2)
+        q[2] = 0.0
+        k = ref.fk(q.astype(np.float64))
+        lowest = min((k["p"][g["link"]] + k["R"][g["link"]] @ np.asarray(g["pos"]))[2] for g in feet) - FOOT_RADIUS
+        q[2] = -lowest - SHALLOW_DEPTHS[b % 4]                         # the ground's top face is z = 0
+        qpos[:, b] = q
+        vel[:, b] = rng.standard_normal(nd) * np.concatenate([[0.01] * 3, [0.03] * 3, [0.05] * (nd - 6)])
+        ms[1, b] = rng.uniform(-1.0, 3.0)
+        ms[2:, b] = rng.uniform(-0.1, 0.1, nl - 2)
+        cs[1:, :, b] = rng.uniform(-0.01, 0.01, (nl - 1, 3))
+    return dict(F_QPOS=qpos, F_VEL=vel.astype(np.float32), F_MASS_SHIFT=ms.astype(np.float32), F_COM_SHIFT=cs.reshape(nl * 3, B).astype(np.float32))
 
 
 def load_states(h, st):
@@ -374,9 +521,16 @@ def _check(errs, tol, what):
     assert not bad, f"{what}: error / tolerance {bad} (all: {errs})"
 
 
-def case_constraints(h, ref, st, seed, n_chk, ratios=True):
-    """(f) the constraint phase of one substep from states in contact: qfrc_constraint = sum row^T efc_force, M_ref a - f = qfrc_constraint, the
-    per-link contact forces, efc_force >= 0."""
+def _leg_of(ref, l):
+    """The child of the root link that carries link l (None for the root, the ground and l = -1)."""
+    leg = None
+    while l > -1 and l != ref.root:
+        leg, l = l, ref.links[l]["parent"]
+    return leg if l == ref.root else None
+
+
+def con_setup(h, ref, seed, ratios=True):
+    """Controls off, per-geom friction ratios drawn from the seed.  Returns (ratios, geom friction) as the library holds them."""
     rng = np.random.default_rng(seed)
     _controls(h, ref, "force", rng)
     ng = len(ref.m["geoms"])
@@ -384,25 +538,36 @@ def case_constraints(h, ref, st, seed, n_chk, ratios=True):
     if ratios:
         fr = rng.choice([0.3, 0.7, 1.0, 1.6], (ng, h.B)).astype(np.float32)
     h.set("F_FRICTION_RATIO", fr)
-    gfric = h.get("F_GEOM_FRICTION").astype(np.float64)
-    h.sim.substep(); h.sync()
+    return fr, h.get("F_GEOM_FRICTION").astype(np.float64)
+
+
+def con_check(h, ref, st, fr, gfric, n_chk):
+    """(f) the constraint phase of the substep just run from the states st: qfrc_constraint = sum row^T efc_force, M_ref a - f = qfrc_constraint, the
+    per-link contact forces, efc_force >= 0; `law`: every row's force is the one the constraint law prescribes at the library's own acceleration;
+    `opt`: that acceleration is the minimiser of the float64 constraint problem (M, smooth force, rows, aref and D all from the reference).
+    Returns the largest errors and, under `n_...`, what the batch covered."""
     nc, ncon = h.get("I_N_CONTACTS")[0], h.get("I_N_CONSTRAINTS")[0]
     cpos, cnrm = h.get("F_CONTACT_POS").reshape(-1, 3, h.B), h.get("F_CONTACT_NORMAL").reshape(-1, 3, h.B)
+    cpen = h.get("F_CONTACT_PEN")
     geoms = h.get("I_CONTACT_GEOMS")
     maxc = geoms.shape[0] // 2
     efc, qfrc, f, acc = h.get("F_EFC_FORCE"), h.get("F_QFRC_CONSTRAINT"), h.get("F_FORCE"), h.get("F_ACC")
     cf = h.get("F_CONTACT_FORCE").reshape(ref.nl, 3, h.B)
+    iters = h.get("I_SOLVER_ITERS")[0]
     s = _f64(st)
-    e = dict(qfrc=[], kkt=[], cforce=[], efc_min=[], rows=[])
+    e = dict(qfrc=[], kkt=[], cforce=[], efc_min=[], rows=[], law=[], opt=[], opt_cost=[])
+    n_branch = np.zeros((2, 3), int)                                   # [contact rows, limit rows] x [low, high, saturated]
+    n_coupled = n_active = n_inactive = 0
     for b in range(n_chk):
         k = ref_kin(ref, st, b)
-        rows, dirs, links = [], [], []
+        rows, dirs, links, contacts = [], [], [], []
         for i in range(nc[b]):
             ga, gb = geoms[i, b], geoms[maxc + i, b]
             la, lb = ref.m["geoms"][ga]["link"], ref.m["geoms"][gb]["link"]
             mu = max(gfric[ga, b] * fr[ga, b], gfric[gb, b] * fr[gb, b], 0.01)
             r, d = ref.contact_rows(k, la, lb, cpos[i, :, b].astype(np.float64), cnrm[i, :, b].astype(np.float64), mu)
             rows.append(r); dirs.append(d); links.append((la, lb))
+            contacts.append((ga, gb, cpos[i, :, b].astype(np.float64), cnrm[i, :, b].astype(np.float64), float(cpen[i, b])))
         lim = ref.limit_rows(s["F_QPOS"][:, b])
         J = np.concatenate(rows + [lim]) if rows else lim
         e["rows"].append(float(abs(J.shape[0] - ncon[b])))
@@ -412,17 +577,68 @@ def case_constraints(h, ref, st, seed, n_chk, ratios=True):
         qscale = (np.abs(J).T @ np.abs(lam)).max() + 1e-3
         e["qfrc"].append(np.abs(qr - qfrc[:, b]).max() / qscale)
         Mr = ref.mass_matrix(k, np.zeros(ref.nd))
-        kkt = Mr @ acc[:, b].astype(np.float64) - f[:, b]
-        kscale = (np.abs(Mr) @ np.abs(acc[:, b].astype(np.float64))).max() + np.abs(f[:, b]).max() + qscale
+        a = acc[:, b].astype(np.float64)
+        kkt = Mr @ a - f[:, b]
+        kscale = (np.abs(Mr) @ np.abs(a)).max() + np.abs(f[:, b]).max() + qscale
         e["kkt"].append(np.abs(kkt - qfrc[:, b]).max() / kscale)
         cref = np.zeros((ref.nl, 3))
         for i, (la, lb) in enumerate(links):
             force = dirs[i].T @ lam[4 * i:4 * i + 4]
             cref[la] -= force; cref[lb] += force
         e["cforce"].append(np.abs(cref - cf[:, :, b]).max() / (np.abs(cref).max() + 1e-3))
-    assert nc.sum() >= 2 * h.B, "the batch exercised the contact constraints"
-    assert sum(len(ref.limit_rows(s["F_QPOS"][:, b])) for b in range(h.B)) >= h.B, "... and the joint limits"
-    return {n: _worst(v) for n, v in e.items()}
+        # the constraint law and the optimum
+        P = ref.constraint_problem(k, s["F_QPOS"][:, b], s["F_VEL"][:, b], contacts, gfric[:, b], fr[:, b])
+        Jp, aref, D = P["J"], P["aref"], P["D"]
+        if Jp.shape[0] != ncon[b]:
+            e["law"].append(np.inf); e["opt"].append(np.inf)
+            continue
+        lscale = (D * (np.abs(Jp) @ np.abs(a) + np.abs(aref))).max() if len(D) else 1.0
+        e["law"].append(np.abs(constraint_force(Jp, aref, D, a) - lam).max() / lscale if len(D) else 0.0)
+        q, v = s["F_QPOS"][:, b], s["F_VEL"][:, b]
+        a0 = np.linalg.solve(Mr, -ref.bias(k) + ref.passive(q, v))                     # (controls off: no actuator force)
+        a_opt, cost_opt, active, _ = solve_constraints(Mr, a0, Jp, aref, D)
+        e["opt"].append(np.abs(a - a_opt).max() / np.abs(a_opt).max())
+        cost_scale = 0.5 * a0 @ Mr @ a0 + 0.5 * (D * aref) @ aref
+        e["opt_cost"].append(max(0.0, cost_opt - constraint_cost(Mr, a0, Jp, aref, D, a)) / cost_scale)
+        for lim_row in (0, 1):
+            n_branch[lim_row] += np.bincount(P["branch"][P["is_limit"] == bool(lim_row)], minlength=3)
+        n_coupled += any(None not in (_leg_of(ref, la), _leg_of(ref, lb)) and _leg_of(ref, la) != _leg_of(ref, lb) for la, lb in links)
+        n_active += int(active.sum()); n_inactive += int((~active).sum())
+    out = {n: _worst(v) for n, v in e.items()}
+    out["at_cap"] = float((iters >= ref.m["solver"]["iterations"]).sum())
+    out["n_iters"] = int(iters.max())
+    out.update(n_low=n_branch[0, 0], n_high=n_branch[0, 1], n_sat=n_branch[0, 2], n_limit_low=n_branch[1, 0], n_limit_high=n_branch[1, 1],
+               n_limit_sat=n_branch[1, 2], n_coupled=n_coupled, n_uncoupled=n_chk - n_coupled, n_active=n_active, n_inactive=n_inactive,
+               n_contacts=int(nc.sum()), n_limits=sum(len(ref.limit_rows(s["F_QPOS"][:, b])) for b in range(h.B)))
+    return out
+
+
+def case_constraints(h, ref, st, seed, n_chk, case="flat"):
+    """One substep from states in contact, checked by con_check; asserts what the batch has to cover.  Returns the errors and what con_setup set."""
+    fr, gfric = con_setup(h, ref, seed)
+    h.sim.substep(); h.sync()
+    errs = con_check(h, ref, st, fr, gfric, n_chk)
+    if case == "shallow":
+        assert errs["n_contacts"] >= h.B, "every env of the batch touches the ground"
+        # ... at the depth it was placed at: the deepest foot-ground contact is the lowest foot sphere (1e-6 m: the float32 kinematics are within
+        # 3e-7 m of the reference's, TOL_KIN)
+        pen, geoms, nc = h.get("F_CONTACT_PEN"), h.get("I_CONTACT_GEOMS"), h.get("I_N_CONTACTS")[0]
+        for b in range(h.B):
+            ga, gb = geoms[:nc[b], b], geoms[geoms.shape[0] // 2:geoms.shape[0] // 2 + nc[b], b]
+            foot = [i for i in range(nc[b]) if ref.links[ref.m["geoms"][min(ga[i], gb[i])]["link"]]["is_fixed"]
+                    and ref.m["geoms"][max(ga[i], gb[i])]["data"][0] == FOOT_RADIUS]
+            assert foot and abs(pen[foot, b].max() - SHALLOW_DEPTHS[b % 4]) <= 1e-6, (b, pen[:nc[b], b])
+    else:
+        assert errs["n_contacts"] >= 2 * h.B, "the batch exercised the contact constraints"
+        assert errs["n_limits"] >= h.B, "... and the joint limits"
+    if n_chk == h.B:
+        if case == "shallow":          # both polynomial branches of the impedance, for contacts and for limits
+            assert errs["n_low"] >= 8 and errs["n_high"] >= 8 and errs["n_limit_low"] >= 1 and errs["n_limit_high"] >= 1, errs
+        else:                          # the saturated value; both factorisations of the Newton Hessian (a contact between two legs couples their blocks)
+            assert errs["n_sat"] >= 8 and errs["n_limit_sat"] >= 1, errs
+            assert errs["n_coupled"] >= 1 and errs["n_uncoupled"] >= 1, errs
+        assert errs["n_active"] >= 8 and errs["n_inactive"] >= 1, errs
+    return errs, (fr, gfric)
 
 
 TOL_CON = dict(
@@ -432,6 +648,22 @@ TOL_CON = dict(
     kkt=5e-5,          # relative to max |M| |a| + max |f| + the qfrc scale; measured <= 1.3e-6 (oracles, HIP default and every knob but
     #                    GO2SIM_TERRAIN_SOLVER_TEAM=32, see TOL_CON_EARLY_STOP).  M a - f - qfrc is the Newton gradient at the solver's last iterate
     cforce=5e-5,       # relative to max |contact force|; measured <= 1.0e-6 (stairs)
+    # law and opt: ten times the worst value measured on the strict and the fast oracle at 8 and at 128 envs over flat, stairs and shallow; the margin is
+    # for other sum orders (16- and 64-lane teams) and other seeds.  The HIP default build is bit-equal to the fast oracle; HIP under the knobs at
+    # 128 envs: law <= 8.9e-7, opt <= 1.7e-5 (GO2SIM_TERRAIN_SOLVER_TEAM=32 on stairs, the early stop again; every other knob <= 3.8e-6),
+    # warm_law <= 8.4e-7 and warm_opt <= 1.8e-5 (GO2SIM_NO_ARROW=1 on flat ground)
+    law=9e-6,          # |efc_force - D max(0, -(J a - aref))| at the library's F_ACC, relative to max D (|J| |a| + |aref|); measured <= 8.7e-7 (stairs;
+    #                    flat 2.0e-7, shallow 2.4e-7)
+    opt=2e-4,          # max |F_ACC - a*| / max |a*| with a* the float64 minimiser; measured <= 1.7e-5 (strict oracle, stairs at 128 envs: a solve that
+    #                    stops an iteration early, see TOL_CON_EARLY_STOP; otherwise stairs 5.0e-6, shallow 3.0e-6, flat 7.1e-7)
+    opt_cost=1e-9,     # cost(a*) - cost(F_ACC), both in float64, relative to 1/2 a0^T M a0 + 1/2 sum D aref^2: a* is the minimiser up to a gradient of
+    #                    1e-10 of the force scale, so by convexity the cost at any other point is above its by all but ~1e-10 x |F_ACC - a*| / |a*| of it
+    at_cap=0,          # number of envs whose solve stopped at the model's iteration cap (50); measured: at most 10 iterations
+    # the same after a following warm-started substep (its float32 Jaref has been carried through the previous solve's line searches as well)
+    warm_law=4e-5,     # measured <= 3.7e-6 (stairs; flat 9.0e-7, shallow 8.0e-7)
+    warm_opt=2e-4,     # measured <= 1.6e-5 (flat and stairs alike; shallow 1.4e-6)
+    warm_opt_cost=1e-9,
+    warm_at_cap=0,     # measured: at most 8 iterations
 )
 # GO2SIM_TERRAIN_SOLVER_TEAM=32 on stairs: the KKT residual is not a rounding error but the Newton gradient left when the solve stops on
 # `improvement < meaninertia * ND * tolerance`; with the 32-lane sum order some stairs solves stop an iteration earlier and leave 5.6e-5 of the
@@ -459,19 +691,20 @@ SNAP = {
     "kin": ["F_LINK_POS", "F_LINK_QUAT", "F_LINK_CDVEL", "F_LINK_CDANG", "F_ROOT_COM", "F_DOF_POS"],
     "dyn": ["F_MASS_MAT", "F_FORCE", "F_ACC_SMOOTH", "F_ACC", "F_QPOS", "F_VEL"],
     "con": ["F_FORCE", "F_ACC", "F_QPOS", "F_VEL", "F_EFC_FORCE", "F_QFRC_CONSTRAINT", "F_CONTACT_FORCE", "F_CONTACT_POS", "F_CONTACT_NORMAL",
-            "I_N_CONTACTS", "I_N_CONSTRAINTS", "I_CONTACT_GEOMS", "I_SOLVER_ITERS"],
+            "F_CONTACT_PEN", "I_N_CONTACTS", "I_N_CONSTRAINTS", "I_CONTACT_GEOMS", "I_SOLVER_ITERS"],
 }
-CASES = {"kin": "kin", "force": "dyn", "position": "dyn", "ext": "dyn", "flat": "con", "stairs": "con"}
+CASES = {"kin": "kin", "force": "dyn", "position": "dyn", "ext": "dyn", "flat": "con", "stairs": "con", "shallow": "con"}
 
 
 MULTI = ["F_QPOS", "F_VEL", "F_ACC", "F_ACC_SMOOTH", "F_FORCE", "F_MASS_MAT", "F_LINK_POS", "F_LINK_QUAT", "F_LINK_CDVEL", "F_LINK_CDANG",
-         "F_EFC_FORCE", "F_QFRC_CONSTRAINT", "F_CONTACT_FORCE", "I_N_CONTACTS", "I_N_CONSTRAINTS", "I_SOLVER_ITERS"]
+         "F_EFC_FORCE", "F_QFRC_CONSTRAINT", "F_CONTACT_FORCE", "I_N_CONTACTS", "I_N_CONSTRAINTS", "I_SOLVER_ITERS", "I_IS_WARMSTART"]
 
 
 def run_case(lib, name, case, n_envs, gpu=False, env=None, monkeypatch=None, check=True, more_substeps=0):
     """Loads the case's states into a fresh handle (env: knobs set while the handle is created), runs it, checks nothing.  Returns (errors against
     the reference -- empty with check=False --, the library's fields of the case).  more_substeps > 0: then one scene_step of that many substeps
-    (the multi-substep launch sequence: fused solve + integrate + next dynamics, or the separate launches), whose fields join the snapshot."""
+    (the multi-substep launch sequence: fused solve + integrate + next dynamics, or the separate launches), whose fields join the snapshot.  For a
+    constraint case more_substeps = 1 also checks that warm-started substep against the reference (errors under warm_...)."""
     model = MODELS[name]()
     ref = RigidRef(model)
     for k, v in (env or {}).items():
@@ -489,15 +722,21 @@ def run_case(lib, name, case, n_envs, gpu=False, env=None, monkeypatch=None, che
         load_states(h, st)
         errs, _ = case_dynamics(h, ref, st, case, seed=7, n_chk=n_chk)
     else:
-        st = make_states(ref, n_envs, seed=400, contact=True)
+        st = make_shallow_states(ref, n_envs, seed=500) if case == "shallow" else make_states(ref, n_envs, seed=400, contact=True)
         if case == "stairs":
             _place_on_stairs(h, st)
         load_states(h, st)
-        errs = case_constraints(h, ref, st, seed=9, n_chk=n_chk)
+        errs, con = case_constraints(h, ref, st, seed=9, n_chk=n_chk, case=case)
     snap = {n: h.get(n) for n in SNAP[CASES[case]]}
     if more_substeps:
         h.sim.scene_step(more_substeps); h.sync()
         snap.update({"after %d substeps: %s" % (more_substeps, n): h.get(n) for n in MULTI})
+        if CASES[case] == "con" and more_substeps == 1 and check:
+            # the solve of that substep started from the previous acceleration; its problem is rebuilt from the state read back before it
+            assert (snap["after 1 substeps: I_IS_WARMSTART"] == 1).all()
+            w = con_check(h, ref, dict(st, F_QPOS=snap["F_QPOS"], F_VEL=snap["F_VEL"]), *con, n_chk)
+            assert w["n_contacts"] >= n_envs and w["n_active"] >= 8, w
+            errs.update({"warm_" + n: v for n, v in w.items()})
     return errs, snap
 
 
@@ -510,9 +749,13 @@ def cpu_lib(request, oracle_strict_lib, oracle_fast_lib):
     return oracle_strict_lib if request.param == "strict" else oracle_fast_lib
 
 
-@pytest.mark.parametrize("case,name", [(c, n) for c in ("kin", "force", "position", "ext") for n in ("go2", "anymal_c")] + [("flat", "go2"), ("stairs", "go2")])
+CON_CASES = [("flat", "go2"), ("stairs", "go2"), ("shallow", "go2")]
+
+
+@pytest.mark.parametrize("case,name", [(c, n) for c in ("kin", "force", "position", "ext") for n in ("go2", "anymal_c")] + CON_CASES)
 def test_oracle_against_reference(cpu_lib, case, name):
-    errs, _ = run_case(cpu_lib, name, case, B)
+    errs, _ = run_case(cpu_lib, name, case, B, more_substeps=int(CASES[case] == "con"))
+    print(f"oracle {name} {case}:", {n: float("%.2e" % v) for n, v in errs.items()})
     _check(errs, TOL[CASES[case]], f"{name} {case}")
 
 
@@ -523,9 +766,16 @@ def test_oracle_row_form_against_reference(cpu_lib, name, monkeypatch):
     _check(errs, TOL_DYN, f"{name} row form")
 
 
+@pytest.mark.parametrize("case", ["flat", "shallow"])
+def test_oracle_row_form_contacts_against_reference(oracle_fast_lib, case, monkeypatch):
+    """(f) with GO2SIM_NO_ARROW=1 on the FAST ORDER oracle (the strict build has no arrow form): every env's Newton Hessian in row form."""
+    errs, _ = run_case(oracle_fast_lib, "go2", case, B, env={"GO2SIM_NO_ARROW": "1"}, monkeypatch=monkeypatch, more_substeps=1)
+    _check(errs, TOL_CON, f"go2 {case} row form")
+
+
 # ---------------------------------------------------------------------------------------------------- GPU: the HIP library and its knobs
 B_GPU = 128
-GPU_CASES = [(c, n) for c in ("kin", "force", "position", "ext") for n in ("go2", "anymal_c")] + [("flat", "go2"), ("stairs", "go2")]
+GPU_CASES = [(c, n) for c in ("kin", "force", "position", "ext") for n in ("go2", "anymal_c")] + CON_CASES
 
 
 def _bits_equal_snaps(a, b):
@@ -539,10 +789,11 @@ def _bits_equal_snaps(a, b):
 def test_hip_against_reference_and_oracle(hip_lib, oracle_fast_lib, case, name):
     """(a)-(f) on the HIP library at default settings: within the float64 tolerances, and bit-equal to the FAST ORDER oracle on the same states
     (states the env never reaches: base |w| up to 20 rad/s, DR shifts beyond their ranges)."""
-    errs, snap = run_case(hip_lib, name, case, B_GPU, gpu=True)
+    more = int(CASES[case] == "con")                       # (the constraint cases: then a warm-started substep)
+    errs, snap = run_case(hip_lib, name, case, B_GPU, gpu=True, more_substeps=more)
     print(f"hip default {name} {case}:", {n: float("%.2e" % v) for n, v in errs.items()})
     _check(errs, TOL[CASES[case]], f"hip {name} {case}")
-    _, ref_snap = run_case(oracle_fast_lib, name, case, B_GPU)
+    _, ref_snap = run_case(oracle_fast_lib, name, case, B_GPU, check=False, more_substeps=more)
     assert not _bits_equal_snaps(snap, ref_snap), f"HIP vs fast oracle differ in {_bits_equal_snaps(snap, ref_snap)}"
 
 
@@ -557,6 +808,19 @@ def test_hip_row_form_against_reference_and_oracle(hip_lib, oracle_fast_lib, nam
     assert not _bits_equal_snaps(snap, ref_snap), f"HIP vs fast oracle differ in {_bits_equal_snaps(snap, ref_snap)}"
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["flat", "shallow"])
+def test_hip_row_form_contacts_against_reference_and_oracle(hip_lib, oracle_fast_lib, case, monkeypatch):
+    """GO2SIM_NO_ARROW=1 with contacts: the row-form factorisation of the Newton Hessian in every env (by default only envs with a contact between two
+    legs take it), against the float64 constraint law and optimum, cold and warm-started, and bit-equal to the oracle under the same switch."""
+    env = {"GO2SIM_NO_ARROW": "1"}
+    errs, snap = run_case(hip_lib, "go2", case, B_GPU, gpu=True, env=env, monkeypatch=monkeypatch, more_substeps=1)
+    print(f"hip NO_ARROW go2 {case}:", {n: float("%.2e" % v) for n, v in errs.items()})
+    _check(errs, TOL_CON, f"hip go2 {case} row form")
+    _, ref_snap = run_case(oracle_fast_lib, "go2", case, B_GPU, env=env, monkeypatch=monkeypatch, check=False, more_substeps=1)
+    assert not _bits_equal_snaps(snap, ref_snap), f"HIP vs fast oracle differ in {_bits_equal_snaps(snap, ref_snap)}"
+
+
 # knob -> (cases, rule[, tolerances of the constraint case]).  "bits": the knob changes the launch shape only (which kernel, how many envs per
 # workgroup, dispatch order); the arithmetic of every env is that of the default build -> bit equality with it, after the single substep AND after
 # a following scene_step of MORE_SUBSTEPS substeps (what selects the fused solve + integrate + next-dynamics launch, the k_integrate_fk_dynamics_team
@@ -564,7 +828,7 @@ def test_hip_row_form_against_reference_and_oracle(hip_lib, oracle_fast_lib, nam
 # the step graph with GO2SIM_PAR_PRE) are covered by test_hip_knob_env_step.  "solver": the team width of the Newton solve sets the butterfly-tree
 # order of its row / dof sums (README: a 16-lane team gives other last bits) -> float64 tolerances, and F_ACC within the test_fast_order.py bound
 # of the default build.  "tol": the float64 tolerances.
-FLAT = ("force", "position", "ext", "flat")
+FLAT = ("force", "position", "ext", "flat", "shallow")
 MORE_SUBSTEPS = 3
 KNOBS = {
     "GO2SIM_DYN_TEAM=16": (FLAT, "tol"),              # row-form mass factorisation (the arrow form needs 32 / 64 lanes): other last bits
