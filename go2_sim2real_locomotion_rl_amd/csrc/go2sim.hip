@@ -263,6 +263,11 @@ struct Joint { int type, link, q_start, dof_start, dof_end; V3 pos; float sol_pa
 struct Dof { V3 motion_ang, motion_vel; float limit[2], invweight, armature, damping, stiffness, frictionloss, kp, kv, force_range[2]; };
 struct Geom { int type, link, is_convex; V3 pos; Q4 quat; float data[7], friction, sol_params[7]; V3 center; V3 aabb[8]; float rim[32][2]; };
 struct Entity { int link_start, link_end, dof_start, dof_end, geom_start, geom_end; };
+// What the narrow phase reads of a geom, 25 words instead of the 464 bytes of a Geom: a table of its own in device memory, written by k_build_geomk
+// after every upload of the model (upload_model) and copied into LDS at the head of k_collide_team.  aabb_mid / aabb_size / aabb_diag are the per-geom
+// terms of guess_geoms_center and compute_tolerance, formed once with the same device operations.
+struct GeomK { int type, link; float data[3], sol_params[7]; V3 center, aabb7, aabb_mid, aabb_size; float aabb_diag; };
+static_assert(sizeof(GeomK) == 25 * 4, "GeomK: 25 words");
 struct Model {
   int n_links, n_joints, n_dofs, n_qs, n_geoms, n_entities, n_pairs, max_collision_pairs, max_contact_pairs, max_broad_pairs,
       n_contacts_per_pair, iterations, ls_iterations, ccd_iterations, support_res;
@@ -279,11 +284,12 @@ struct Model {
   // reference's leaf->root loops add them to the parent), link of every dof
   int n_levels, level_start[NL + 1], level_links[NL], child_start[NL + 1], child_list[NL], dof_link[ND];
   int arrow_mode;   // derived: numbering of the four leg chains (dm_arrow_mode; 0 = the Hessian has no arrow form)
+  const GeomK* gk;  // derived: the compact geom table of the narrow phase (device pointer, NG records; upload_model)
 };
 
 bool parse_model(const void* blob, size_t nbytes, Model& m) {
   m.terrain_enabled = 0; m.terrain_rows = m.terrain_cols = 0; m.terrain_hs = 0.0f; m.terrain_hf = nullptr;
-  m.terrain_cmax = nullptr; m.terrain_crows = m.terrain_ccols = 0;
+  m.terrain_cmax = nullptr; m.terrain_crows = m.terrain_ccols = 0; m.gk = nullptr;
   if (nbytes < 128) return false;
   const int32_t* H = (const int32_t*)blob;
   if (H[0] != GO2SIM_MODEL_MAGIC || H[1] != GO2SIM_MODEL_VERSION) return false;
@@ -541,6 +547,7 @@ DEV void wg_dma_to_lds(void* lds_dst, const void* __restrict__ src, int lane = (
                                      (__attribute__((address_space(3))) void*)((char*)lds_dst + k * 1024), 16, 0, 0);
 }
 constexpr int MODELS_LDS_BYTES = lds_dma_bytes((int)sizeof(ModelS));
+constexpr int GEOMK_BYTES = NG * (int)sizeof(GeomK), GEOMK_LDS_BYTES = lds_dma_bytes(GEOMK_BYTES);   // the geom table of the narrow phase (k_collide_team)
 
 // ---------------------------------------------------------------------------------------------
 // SoA state pool.  X(name, floats_per_env).  Order of the first group matches enum go2sim_field so
@@ -698,6 +705,12 @@ DEV void team_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+// The same for LDS alone: what the lanes of the team exchange through LDS is ordered, stores to global memory stay in flight.
+DEV void team_sync_lds() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 DEV float gload(const E& e, int off, int k) { return e.f[(size_t)(off + k) * e.B]; }
 DEV void gstore(const E& e, int off, int k, float v) { e.f[(size_t)(off + k) * e.B] = v; }
@@ -1766,8 +1779,12 @@ struct BroadData {
   alignas(16) unsigned long long skey[2 * NG];      // (order-preserving integer image of the endpoint value) << 8 | position before the sort
   alignas(8) int rank_mm[NG * 2];                   // (rank of the min endpoint, rank of the max endpoint) per geom
   int cand_key[MAXB], cand_pair[MAXB];
-  unsigned short pair_sorted[MAXB];                 // geom a | geom b << 8
+  unsigned pair_sorted[MAXB];                       // geom a | geom b << 8 | pair index << 16 (broad_word)
 };
+// One word per pair of the broad-phase list, as e.broad() holds it: the candidate test of pair pidx meets pair_list[pidx] = a | b << 8, and pidx IS
+// m.pair_idx[a][b] (parse_model), so the narrow phase gets the index of the pair's normal-cache entry with the pair instead of looking it up.
+static_assert(NPAIR <= (1 << 16) && NG <= (1 << 8), "broad_word: 8 bits per geom, 16 bits of pair index");
+DEV unsigned broad_word(int packed, int pidx) { return (unsigned)packed | ((unsigned)pidx << 16); }
 // The working set is laid over the env's dynamics record, all of which is dead once tk_dynamics has stored its results: the dynamics kernels keep
 // their LDS footprint (8 workgroups per CU).  The records of a workgroup are packed (sizeof(DynData) is not a multiple of 16), so the overlay starts
 // at the first 16-byte boundary inside the record; shape variants whose record is too small for it get a block of their own.
@@ -1883,7 +1900,7 @@ DEV void tk_broadphase(const Model& m, const E& e, BroadData<T>* s, int tl) {
     const unsigned long long cb = team_ballot<T>(cand);
     if (cand) {
       const int pos = n_cand + __popcll(cb & ((1ull << tl) - 1ull));
-      if (pos < MAXB) { s->cand_key[pos] = rs * 64 + rf; s->cand_pair[pos] = packed; }
+      if (pos < MAXB) { s->cand_key[pos] = rs * 64 + rf; s->cand_pair[pos] = (int)broad_word(packed, it * T + tl); }
     }
     n_cand += __popcll(cb);
     const unsigned long long sep = team_ballot<T>(swept && (any1 || any2));
@@ -1899,12 +1916,12 @@ DEV void tk_broadphase(const Model& m, const E& e, BroadData<T>* s, int tl) {
   for (int c = tl; c < n_cand; c += T) {
     const int ck = s->cand_key[c]; int cr = 0;
     for (int j = 0; j < n_cand; ++j) cr += s->cand_key[j] < ck;
-    s->pair_sorted[cr] = (unsigned short)s->cand_pair[c];
+    s->pair_sorted[cr] = (unsigned)s->cand_pair[c];
   }
   const int n_broad = imn(n_cand, m.max_broad_pairs);
   team_sync();
   // ---- everything the broad phase writes to the env's records, after the last ordering point: none of the stores is waited for ----
-  for (int c = tl; c < n_broad; c += T) { int pk = s->pair_sorted[c]; e.broad()[2 * c] = pk & 0xff; e.broad()[2 * c + 1] = pk >> 8; }
+  for (int c = tl; c < n_broad; c += T) e.broad()[c] = (int)s->pair_sorted[c];
 #pragma unroll
   for (int q = 0; q < NK; ++q) if (tl + q * T < n2) { e.sort_value()[r[q]] = sorted_v[q]; e.sort_ig()[r[q]] = sorted_sg[q]; }
   if (tl < NCV && ncv_clear != 0u) e.ncache_valid()[tl] = (int)(ncv_old & ~ncv_clear);
@@ -2093,7 +2110,7 @@ DEV V3 support_prism(const V3* prism, V3 d) {
 }
 // type and size of a geom, read once per pair so that the MPR iterations do not go back to the model in global memory
 struct GeomLite { int type; float d0, d1, d2; };
-DEV GeomLite geom_lite(const Model& m, int i_g) { const Geom& G = m.geoms[i_g]; GeomLite r = {G.type, G.data[0], G.data[1], G.data[2]}; return r; }
+DEV GeomLite geom_lite(const GeomK* gk, int i_g) { const GeomK& G = gk[i_g]; GeomLite r = {G.type, G.data[0], G.data[1], G.data[2]}; return r; }   // gk: the geom table, in LDS (k_collide_team) or global (m.gk)
 DEV V3 support_driver(const Model& m, V3 direction, int i_g, const GeomLite& gl, V3 pos, const Rot& rot, const V3* prism = nullptr) {
   if (gl.type == GEOM_TERRAIN) return support_prism(prism, direction);
   if (gl.type == GEOM_SPHERE) {
@@ -2319,14 +2336,14 @@ DEV void mpr_find_penetration(const Model& m, Simplex& s, const Pair& pr, bool& 
   }
 }
 // guess_geoms_center, mpr.py:601-683
-DEV void guess_geoms_center(const Model& m, const Pair& pr, V3 normal_ws, V3& center_a, V3& center_b) {
-  const Geom& A = m.geoms[pr.i_ga]; const Geom& Bg = m.geoms[pr.i_gb];
+DEV void guess_geoms_center(const Model& m, const GeomK* gk, const Pair& pr, V3 normal_ws, V3& center_a, V3& center_b) {
+  const GeomK& A = gk[pr.i_ga]; const GeomK& Bg = gk[pr.i_gb];
   center_a = transform_by_trans_quat(A.center, pr.pos_a, pr.quat_a);
   center_b = transform_by_trans_quat(Bg.center, pr.pos_b, pr.quat_b);
   if (dm_abs(normal_ws.x) > m.ccd_eps || dm_abs(normal_ws.y) > m.ccd_eps || dm_abs(normal_ws.z) > m.ccd_eps) {
-    V3 center_a_local = 0.5f * (A.aabb[7] + A.aabb[0]);
+    V3 center_a_local = A.aabb_mid;                                      // 0.5f * (aabb[7] + aabb[0]), k_build_geomk
     center_a = transform_by_trans_quat(center_a_local, pr.pos_a, pr.quat_a);
-    V3 center_b_local = 0.5f * (Bg.aabb[7] + Bg.aabb[0]);
+    V3 center_b_local = Bg.aabb_mid;
     center_b = transform_by_trans_quat(center_b_local, pr.pos_b, pr.quat_b);
     V3 delta = center_a - center_b;
     V3 normal = normalized(delta);
@@ -2336,7 +2353,7 @@ DEV void guess_geoms_center(const Model& m, const Pair& pr, V3 normal_ws, V3& ce
       if (offset_norm > m.eps) {
         V3 dir_offset = offset / offset_norm;
         V3 dla = inv_transform_by_quat(dir_offset, pr.quat_a), dlb = inv_transform_by_quat(dir_offset, pr.quat_b);
-        V3 box_size_a = A.aabb[7] - A.aabb[0], box_size_b = Bg.aabb[7] - Bg.aabb[0];
+        V3 box_size_a = A.aabb_size, box_size_b = Bg.aabb_size;           // aabb[7] - aabb[0], k_build_geomk
         float length_a = dot(box_size_a, v3(dm_abs(dla.x), dm_abs(dla.y), dm_abs(dla.z)));
         float length_b = dot(box_size_b, v3(dm_abs(dlb.x), dm_abs(dlb.y), dm_abs(dlb.z)));
         float offset_ratio = fmn(offset_norm / (length_a + length_b), 0.5f);
@@ -2361,26 +2378,29 @@ DEV void mpr_contact_from_centers(const Model& m, const Pair& pr, V3 center_a, V
     if (res >= 0) mpr_find_penetration(m, s, pr, is_col, normal, penetration, pos);
   }
 }
-DEV void mpr_contact(const Model& m, const Pair& pr, V3 normal_ws, bool& is_col, V3& normal, float& penetration, V3& pos) {
+DEV void mpr_contact(const Model& m, const GeomK* gk, const Pair& pr, V3 normal_ws, bool& is_col, V3& normal, float& penetration, V3& pos) {
   V3 center_a, center_b;
-  guess_geoms_center(m, pr, normal_ws, center_a, center_b);
+  guess_geoms_center(m, gk, pr, normal_ws, center_a, center_b);
   mpr_contact_from_centers(m, pr, center_a, center_b, is_col, normal, penetration, pos);
 }
 
 // func_compute_tolerance, contact.py:264-283
-DEV float compute_tolerance(const Model& m, int i_ga, int i_gb, float tolerance) {
-  float size_b = norm(m.geoms[i_gb].aabb[7] - m.geoms[i_gb].aabb[0]);
-  if (m.geoms[i_ga].type == GEOM_PLANE) return 0.5f * tolerance * size_b;   // the plane's (finite) box does not count
-  float size_a = norm(m.geoms[i_ga].aabb[7] - m.geoms[i_ga].aabb[0]);
+DEV float compute_tolerance(const GeomK* gk, int i_ga, int i_gb, float tolerance) {
+  float size_b = gk[i_gb].aabb_diag;                                     // norm(aabb[7] - aabb[0]), k_build_geomk
+  if (gk[i_ga].type == GEOM_PLANE) return 0.5f * tolerance * size_b;     // the plane's (finite) box does not count
+  float size_a = gk[i_ga].aabb_diag;
   return 0.5f * tolerance * fmn(size_a, size_b);
 }
-// func_contact_orthogonals (non-mujoco branch), contact.py:286-345
-DEV void contact_orthogonals(const Model& m, const E& e, int i_ga, int i_gb, V3 normal, V3& axis_0, V3& axis_1) {
-  V3 size_ga = m.geoms[i_ga].aabb[7], size_gb = m.geoms[i_gb].aabb[7];
+// func_contact_orthogonals (non-mujoco branch), contact.py:286-345.  The link whose frame gives the axes depends on the pair alone
+// (contact_orthogonals_link): its orientation is requested with the pair's other operands, in front of the query.
+DEV int contact_orthogonals_link(const GeomK* gk, int i_ga, int i_gb) {
+  V3 size_ga = gk[i_ga].aabb7, size_gb = gk[i_gb].aabb7;
   float volume_ga = size_ga.x * size_ga.y * size_ga.z, volume_gb = size_gb.x * size_gb.y * size_gb.z;
-  int i_g = (volume_ga < volume_gb && m.geoms[i_ga].type != GEOM_PLANE) ? i_ga : i_gb;   // against a plane, b is the reference geometry
-  int i_l = m.geoms[i_g].link;
-  M3 rot = quat_to_R(e.i_quat()[i_l], m.eps);
+  int i_g = (volume_ga < volume_gb && gk[i_ga].type != GEOM_PLANE) ? i_ga : i_gb;   // against a plane, b is the reference geometry
+  return gk[i_g].link;
+}
+DEV void contact_orthogonals(const Model& m, Q4 link_quat, V3 normal, V3& axis_0, V3& axis_1) {
+  M3 rot = quat_to_R(link_quat, m.eps);
   int axis_idx = 0; float axis_angle_max = 0.0f;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
@@ -2435,7 +2455,7 @@ struct CollideData {
     GjkStoreLds gjk[GJK_SLOTS];
     Terrain tr;
   };
-  unsigned short pair_sorted[MAXB];                   // the broad-phase list of this env (e.broad()): geom a | geom b << 8
+  unsigned pair_w[MAXB];                              // the broad-phase list of this env (e.broad()): geom a | geom b << 8 | pair index << 16 (broad_word)
   float stage[T][5][7];
   int cnt[T];
   unsigned gjk_slot_mask;                             // bit i set = gjk[i] is taken
@@ -2453,10 +2473,10 @@ DEV void stage_contact(ContactStage& cs, V3 normal, V3 pos, float pen) {
 // func_plane_box_contact, box_contact.py:25-93 (func_narrow_phase_convex_specializations): the deepest corner of the box, then its corners in vertex
 // order while the pair has fewer than n_contacts_per_pair contacts; a corner is kept if it penetrates and lies more than `tolerance` from the first
 // contact.  The box's vertices are its init-AABB corners (same order: x slowest, z fastest).  No perturbation, no cache.
-DEV void plane_box_contact_staged(const Model& m, const E& e, int i_ga, int i_gb, ContactStage& cs) {
+DEV void plane_box_contact_staged(const Model& m, const GeomK* gk, const E& e, int i_ga, int i_gb, ContactStage& cs) {
   const V3 ga_pos = e.g_pos()[i_ga], gb_pos = e.g_pos()[i_gb];
   const Q4 ga_quat = e.g_quat()[i_ga], gb_quat = e.g_quat()[i_gb];
-  const Geom& A = m.geoms[i_ga]; const Geom& Bg = m.geoms[i_gb];
+  const GeomK& A = gk[i_ga]; const GeomK& Bg = gk[i_gb];
   const V3 normal = -normalized(transform_by_quat(v3(A.data[0], A.data[1], A.data[2]), ga_quat));
   const V3 d_box = inv_transform_by_quat(normal, gb_quat);                            // _func_support_box, support_field.py:286-306
   const V3 v_ = v3((d_box.x < 0.0f ? -1.0f : 1.0f) * Bg.data[0] * 0.5f, (d_box.y < 0.0f ? -1.0f : 1.0f) * Bg.data[1] * 0.5f,
@@ -2466,11 +2486,11 @@ DEV void plane_box_contact_staged(const Model& m, const E& e, int i_ga, int i_gb
   if (!(pen0 > 0.0f)) return;
   const V3 contact_pos_0 = v1 - 0.5f * pen0 * normal;
   stage_contact(cs, normal, contact_pos_0, pen0);
-  const float tolerance = compute_tolerance(m, i_ga, i_gb, m.mc_tolerance);
+  const float tolerance = compute_tolerance(gk, i_ga, i_gb, m.mc_tolerance);
   const int n_max = imn(m.n_contacts_per_pair, 5);                                    // 5 = the staging slots of a lane
   for (int c = 0; c < 8; ++c) {
     if (cs.n >= n_max) break;
-    const V3 corner = transform_by_trans_quat(Bg.aabb[c], gb_pos, gb_quat);
+    const V3 corner = transform_by_trans_quat(m.geoms[i_gb].aabb[c], gb_pos, gb_quat);   // (all eight corners: these stay in the model)
     const float pen = dot(normal, corner - ga_pos);
     if (pen > 0.0f) {
       const V3 cpos = corner - 0.5f * pen * normal;
@@ -2487,11 +2507,21 @@ struct CcState {
   Pair pr; V3 ga_pos_o, gb_pos_o; Q4 ga_quat_o, gb_quat_o;
   int i_pair, type_a, type_b; bool multi_contact, want_gjk; float tolerance;
   bool is_col; float penetration; V3 normal, contact_pos;
+  Q4 link_quat;                                                 // orientation of the link of contact_orthogonals (multi_contact pairs)
 };
-DEV void cc_mpr_with_retry(const Model& m, CcState& c, int i_detection, unsigned* ncv, const Arr3& normal_cache, bool& guess_available) {
+// What a pair takes from the env's records in front of its first query, requested in one batch as soon as the pair is known (k_collide_team): the
+// two geom poses and the pair's entry of the normal cache (read unconditionally: the mask bit decides whether it is used).
+struct PairIn { V3 pos_a; Q4 quat_a; V3 pos_b; Q4 quat_b; V3 ncache; };
+DEV PairIn load_pair_in(const E& e, int i_ga, int i_gb, int i_pair) {
+  PairIn r;
+  r.pos_a = e.g_pos()[i_ga]; r.quat_a = e.g_quat()[i_ga]; r.pos_b = e.g_pos()[i_gb]; r.quat_b = e.g_quat()[i_gb]; r.ncache = e.normal_cache()[i_pair];
+  return r;
+}
+// normal_ws: the pair's normal-cache entry as the detection finds it -- the entry of the last narrow phase (masked by its valid bit) for detection 0,
+// and for a perturbed detection the normal detection 0 has just stored there (cc_rest)
+DEV void cc_mpr_with_retry(const Model& m, const GeomK* gk, CcState& c, int i_detection, V3 normal_ws, bool& guess_available) {
   const float EPS = m.eps;
   bool is_mpr_updated = false;
-  V3 normal_ws = ((ncv[c.i_pair >> 5] >> (c.i_pair & 31)) & 1u) ? (V3)normal_cache[c.i_pair] : v3(0, 0, 0);
   guess_available = (dm_abs(normal_ws.x) > EPS) || (dm_abs(normal_ws.y) > EPS) || (dm_abs(normal_ws.z) > EPS);
   for (int i_mpr = 0; i_mpr < 2; ++i_mpr) {
     if (i_mpr == 1) {
@@ -2499,7 +2529,7 @@ DEV void cc_mpr_with_retry(const Model& m, CcState& c, int i_detection, unsigned
     }
     if (!is_mpr_updated) {
       PHD_BEGIN
-      mpr_contact(m, c.pr, normal_ws, c.is_col, c.normal, c.penetration, c.contact_pos);
+      mpr_contact(m, gk, c.pr, normal_ws, c.is_col, c.normal, c.penetration, c.contact_pos);
       PHD(36)
       is_mpr_updated = true;
     }
@@ -2509,23 +2539,25 @@ DEV bool cc_prefer_gjk(const Model& m, const CcState& c, bool guess_available) {
   if (c.penetration > c.tolerance) return !guess_available || (m.mc_tolerance * c.penetration >= m.mpr_to_gjk_ratio * c.tolerance);
   return false;
 }
-DEV void cc_detect0(const Model& m, const E& e, int i_ga, int i_gb, unsigned* ncv, CcState& c) {
-  c.type_a = m.geoms[i_ga].type; c.type_b = m.geoms[i_gb].type;
+// i_pair = m.pair_idx of the pair (it travels with the broad-phase list); in = load_pair_in of (i_ga, i_gb, i_pair)
+DEV void cc_detect0(const Model& m, const GeomK* gk, const E& e, int i_ga, int i_gb, int i_pair, const PairIn& in, unsigned* ncv, CcState& c) {
+  c.type_a = gk[i_ga].type; c.type_b = gk[i_gb].type;
   c.multi_contact = (c.type_a != GEOM_SPHERE) && (c.type_b != GEOM_SPHERE);
-  c.tolerance = compute_tolerance(m, i_ga, i_gb, m.mc_tolerance);
-  c.ga_pos_o = e.g_pos()[i_ga]; c.gb_pos_o = e.g_pos()[i_gb]; c.ga_quat_o = e.g_quat()[i_ga]; c.gb_quat_o = e.g_quat()[i_gb];
+  c.link_quat = e.i_quat()[c.multi_contact ? contact_orthogonals_link(gk, i_ga, i_gb) : 0];   // in flight during the query
+  c.tolerance = compute_tolerance(gk, i_ga, i_gb, m.mc_tolerance);
+  c.ga_pos_o = in.pos_a; c.gb_pos_o = in.pos_b; c.ga_quat_o = in.quat_a; c.gb_quat_o = in.quat_b;
   Pair& pr = c.pr;
-  pr.i_ga = i_ga; pr.i_gb = i_gb; pr.pos_a = c.ga_pos_o; pr.quat_a = c.ga_quat_o; pr.pos_b = c.gb_pos_o; pr.quat_b = c.gb_quat_o; pr.prism = nullptr; pr.ga = geom_lite(m, i_ga); pr.gb = geom_lite(m, i_gb);
+  pr.i_ga = i_ga; pr.i_gb = i_gb; pr.pos_a = c.ga_pos_o; pr.quat_a = c.ga_quat_o; pr.pos_b = c.gb_pos_o; pr.quat_b = c.gb_quat_o; pr.prism = nullptr; pr.ga = geom_lite(gk, i_ga); pr.gb = geom_lite(gk, i_gb);
   pair_set_rots(pr);
   c.is_col = false; c.penetration = 0.0f; c.normal = v3(0, 0, 0); c.contact_pos = v3(0, 0, 0);
-  c.i_pair = (i_ga > i_gb) ? m.pair_idx[i_gb][i_ga] : m.pair_idx[i_ga][i_gb];
+  c.i_pair = i_pair;
   if (c.type_a == GEOM_PLANE) {                                  // plane pairs never vote for GJK / EPA
     plane_contact(m, pr, c.is_col, c.normal, c.penetration, c.contact_pos);
     c.want_gjk = false;
     return;
   }
   bool guess_available;
-  cc_mpr_with_retry(m, c, 0, ncv, e.normal_cache(), guess_available);
+  cc_mpr_with_retry(m, gk, c, 0, ((ncv[i_pair >> 5] >> (i_pair & 31)) & 1u) ? in.ncache : v3(0, 0, 0), guess_available);
   c.want_gjk = cc_prefer_gjk(m, c, guess_available);
 }
 // narrowphase.py:734-845: safe GJK + EPA replaces the MPR answer (one lane; LDS polytope slot when `gjk_slots` is given, else the global record)
@@ -2543,9 +2575,9 @@ DEV void cc_gjk_lane(const Model& m, const E& e, CcState& c, GjkStoreLds* gjk_sl
   c.penetration = gr.penetration;
   if (c.is_col) { c.contact_pos = gr.pos; c.normal = gr.normal; }
 }
-DEV void cc_rest(const Model& m, const E& e, CcState& c, ContactStage& cs, GjkStoreLds* gjk_slots, unsigned* gjk_slot_mask, GjkStoreFull* gjk_full, unsigned* ncv) {
+DEV void cc_rest(const Model& m, const GeomK* gk, const E& e, CcState& c, ContactStage& cs, GjkStoreLds* gjk_slots, unsigned* gjk_slot_mask, GjkStoreFull* gjk_full, unsigned* ncv) {
   const float EPS = m.eps;
-  const int i_ga = c.pr.i_ga, i_gb = c.pr.i_gb, i_pair = c.i_pair;
+  const int i_pair = c.i_pair;
   const bool multi_contact = c.multi_contact;
   const float tolerance = c.tolerance;
   Pair& pr = c.pr;
@@ -2566,7 +2598,7 @@ DEV void cc_rest(const Model& m, const E& e, CcState& c, ContactStage& cs, GjkSt
         plane_contact(m, pr, is_col, normal, penetration, contact_pos);
       } else {
         bool guess_available;
-        cc_mpr_with_retry(m, c, i_detection, ncv, normal_cache, guess_available);
+        cc_mpr_with_retry(m, gk, c, i_detection, normal_0, guess_available);   // normal_cache[i_pair] = normal_0, valid (detection 0 below)
         if (cc_prefer_gjk(m, c, guess_available)) cc_gjk_lane(m, e, c, gjk_slots, gjk_slot_mask, gjk_full);
       }
     }
@@ -2574,7 +2606,7 @@ DEV void cc_rest(const Model& m, const E& e, CcState& c, ContactStage& cs, GjkSt
       is_col_0 = is_col; normal_0 = normal; contact_pos_0 = contact_pos;
       if (is_col_0) {
         stage_contact(cs, normal, contact_pos, penetration);
-        if (multi_contact) contact_orthogonals(m, e, i_ga, i_gb, normal, axis_0, axis_1);
+        if (multi_contact) contact_orthogonals(m, c.link_quat, normal, axis_0, axis_1);
         normal_cache[i_pair] = normal; atomicOr(&ncv[i_pair >> 5], 1u << (i_pair & 31));
       } else {
         atomicAnd(&ncv[i_pair >> 5], ~(1u << (i_pair & 31)));          // normal_cache[i_pair] := 0
@@ -2602,11 +2634,11 @@ DEV void cc_rest(const Model& m, const E& e, CcState& c, ContactStage& cs, GjkSt
   }
   PHD(46)
 }
-DEV void convex_convex_contact_staged(const Model& m, const E& e, int i_ga, int i_gb, ContactStage& cs, GjkStoreLds* gjk_slots, unsigned* gjk_slot_mask, GjkStoreFull* gjk_full, unsigned* ncv) {
+DEV void convex_convex_contact_staged(const Model& m, const GeomK* gk, const E& e, int i_ga, int i_gb, int i_pair, const PairIn& in, ContactStage& cs, GjkStoreLds* gjk_slots, unsigned* gjk_slot_mask, GjkStoreFull* gjk_full, unsigned* ncv) {
   CcState c;
-  cc_detect0(m, e, i_ga, i_gb, ncv, c);
+  cc_detect0(m, gk, e, i_ga, i_gb, i_pair, in, ncv, c);
   if (c.want_gjk) cc_gjk_lane(m, e, c, gjk_slots, gjk_slot_mask, gjk_full);
-  cc_rest(m, e, c, cs, gjk_slots, gjk_slot_mask, gjk_full, ncv);
+  cc_rest(m, gk, e, c, cs, gjk_slots, gjk_slot_mask, gjk_full, ncv);
 }
 
 // Conservative reach test of a (geom, heightfield) pair before any support point is computed: every point of the geom lies within R (+ 1 mm for the
@@ -2639,13 +2671,13 @@ DEV bool terrain_pair_out_of_reach(const Model& m, const GeomLite& gl, V3 pos) {
 // func_contact_mpr_terrain, narrowphase.py:345-490, split for one-lane-per-prism execution.
 // (1) per pair: geom pose in the terrain frame, its bounding box from six support points, the cell range under it.
 template <class TP>
-DEV bool terrain_pair_setup(const Model& m, const E& e, int i_ga, int i_gb, TP& t) {
+DEV bool terrain_pair_setup(const Model& m, const GeomK* gk, const E& e, int i_ga, int i_gb, TP& t) {
   V3 ga_pos = e.g_pos()[i_ga], gb_pos = e.g_pos()[i_gb]; Q4 ga_quat = e.g_quat()[i_ga], gb_quat = e.g_quat()[i_gb];
   const float margin = 0.0f;
   transform_pos_quat_by_trans_quat(ga_pos - gb_pos, ga_quat, v3(0, 0, 0), inv_quat(gb_quat), t.pos_a, t.quat_a);
-  t.center_a = transform_by_trans_quat(m.geoms[i_ga].center, t.pos_a, t.quat_a);
+  t.center_a = transform_by_trans_quat(gk[i_ga].center, t.pos_a, t.quat_a);
   t.i_ga = i_ga;
-  GeomLite gl = geom_lite(m, i_ga);
+  GeomLite gl = geom_lite(gk, i_ga);
   const Rot t_rot = make_rot(t.quat_a);
   float xyz_max_min[6];
 #pragma unroll
@@ -2699,7 +2731,7 @@ DEV void terrain_desc_cell(const TP& t, int local, int& r, int& k) {
 //     cell per lane in k_collide_team
 // (3) MPR of the geom against that prism; the contact is returned in world coordinates
 template <class TP>
-DEV void terrain_prism_pair(const Model& m, const TP& t, int i_gb, int r, int k, V3 (&prism)[6], Pair& pr, V3& center_b) {
+DEV void terrain_prism_pair(const Model& m, const GeomK* gk, const TP& t, int i_gb, int r, int k, V3 (&prism)[6], Pair& pr, V3& center_b) {
   const float* tmm = m.terrain_xyz_maxmin;
   const float sh = m.terrain_hs;
 #pragma unroll
@@ -2710,22 +2742,22 @@ DEV void terrain_prism_pair(const Model& m, const TP& t, int i_gb, int r, int k,
     prism[3 + j] = v3(x, y, terrain_strip_z(m, r, t.c_min, kk) + 0.0f);
   }
   pr.i_ga = t.i_ga; pr.i_gb = i_gb; pr.prism = prism; pr.pos_a = t.pos_a; pr.quat_a = t.quat_a; pr.pos_b = v3(0, 0, 0); pr.quat_b = qident();
-  pr.ga = geom_lite(m, t.i_ga); pr.gb = geom_lite(m, i_gb);
+  pr.ga = geom_lite(gk, t.i_ga); pr.gb = geom_lite(gk, i_gb);
   pair_set_rots(pr);
   center_b = v3(0, 0, 0);
   for (int i_p = 0; i_p < 6; ++i_p) center_b = center_b + prism[i_p];
   center_b = center_b / 6.0f;
 }
 template <class TP>
-DEV bool terrain_prism_separated_at_once(const Model& m, const TP& t, int i_gb, int r, int k) {
+DEV bool terrain_prism_separated_at_once(const Model& m, const GeomK* gk, const TP& t, int i_gb, int r, int k) {
   V3 prism[6]; Pair pr; V3 center_b;
-  terrain_prism_pair(m, t, i_gb, r, k, prism, pr, center_b);
+  terrain_prism_pair(m, gk, t, i_gb, r, k, prism, pr, center_b);
   return mpr_first_support_separates(m, pr, t.center_a, center_b);
 }
 template <class TP>
-DEV bool terrain_prism_contact(const Model& m, const E& e, const TP& t, int i_gb, int r, int k, V3& normal, V3& contact_pos, float& penetration) {
+DEV bool terrain_prism_contact(const Model& m, const GeomK* gk, const E& e, const TP& t, int i_gb, int r, int k, V3& normal, V3& contact_pos, float& penetration) {
   V3 prism[6]; Pair pr; V3 center_b;
-  terrain_prism_pair(m, t, i_gb, r, k, prism, pr, center_b);
+  terrain_prism_pair(m, gk, t, i_gb, r, k, prism, pr, center_b);
   bool is_col;
   mpr_contact_from_centers(m, pr, t.center_a, center_b, is_col, normal, penetration, contact_pos);
   if (is_col) {
@@ -2738,23 +2770,43 @@ DEV bool terrain_prism_contact(const Model& m, const E& e, const TP& t, int i_gb
 }
 
 template <int T>
-__global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __restrict__ mp, GjkStoreFull* __restrict__ gjk_scratch, int* __restrict__ lpt_rec, int lpt_cap, int solver_epw) {
+__global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __restrict__ mp, const GeomK* __restrict__ gkp, GjkStoreFull* __restrict__ gjk_scratch, int* __restrict__ lpt_rec, int lpt_cap, int solver_epw) {
   STAMP(STK_COLLIDE)
   constexpr int EPW = 64 / T;                                           // environments per wavefront
   __shared__ CollideData<T> lds[EPW];
+  __shared__ alignas(16) char gk_raw[GEOMK_LDS_BYTES];                  // the geom table (GeomK[NG]): every per-geom constant of the narrow phase is read here
+  // four workgroups per CU (one wave per SIMD) at T = 16: a quarter of the CU's 160 KiB each
+  static_assert(T != 16 || NG != 28 || sizeof(CollideData<T>) * EPW + GEOMK_LDS_BYTES <= 40960, "k_collide_team<16>: four workgroups per CU");
+  // The kernel holds one wave per SIMD: nothing covers a memory round trip, so its operands are requested in two batches.  Batch 1, at entry, nothing
+  // waiting for the pair count: the geom table (all 64 lanes, before any lane retires), the count, the normal-cache mask and the lane's pairs of the
+  // first rounds.  Batch 2, per round: load_pair_in + the friction words, as soon as the lane has its pair.
+  wg_dma_to_lds<GEOMK_BYTES>(gk_raw, gkp);
+  const GeomK* gk = (const GeomK*)gk_raw;
   const int tl = threadIdx.x % T, slot = threadIdx.x / T;
   const int b = xcd_block() * EPW + slot;
   if (slot >= EPW || b >= P.B) return;
   const Model& m = *mp;
   E e(P, b);
   CollideData<T>* s = &lds[slot];
-  if (tl == 0) s->gjk_slot_mask = 0u;                                   // made visible by the barrier behind the pair-list load
-  for (int i = tl; i < NCV; i += T) s->ncv[i] = (unsigned)e.ncache_valid()[i];
   PH_BEGIN
   // ---- the pair list of the broad phase (tk_broadphase, run by the dynamics launch in front of this one) ----
-  const int n_broad = imn(imx(e.n_broad()[0], 0), MAXB);
-  for (int c = tl; c < n_broad; c += T) s->pair_sorted[c] = (unsigned short)(e.broad()[2 * c] | (e.broad()[2 * c + 1] << 8));
-  team_sync();
+  constexpr int NPRE = (T == 16) ? 2 : 1;                               // rounds whose pair words are requested up front (the walking robot: < 32 pairs)
+  static_assert(NPRE * T <= MAXB, "the unconditional pair-word loads stay inside e.broad()");
+  const int n_broad_ld = e.n_broad()[0];
+  unsigned ncv_ld[(NCV + T - 1) / T]; int pw_ld[NPRE];
+#pragma unroll
+  for (int q = 0; q < (NCV + T - 1) / T; ++q) { const int i = tl + q * T; ncv_ld[q] = (unsigned)e.ncache_valid()[i < NCV ? i : NCV - 1]; }
+#pragma unroll
+  for (int q = 0; q < NPRE; ++q) pw_ld[q] = e.broad()[tl + q * T];
+  if (tl == 0) s->gjk_slot_mask = 0u;                                   // made visible by the barrier behind the pair-list load
+  const int n_broad = imn(imx(n_broad_ld, 0), MAXB);
+#pragma unroll
+  for (int q = 0; q < (NCV + T - 1) / T; ++q) if (tl + q * T < NCV) s->ncv[tl + q * T] = ncv_ld[q];
+#pragma unroll
+  for (int q = 0; q < NPRE; ++q) if (tl + q * T < n_broad) s->pair_w[tl + q * T] = (unsigned)pw_ld[q];
+  for (int c = tl + NPRE * T; c < n_broad; c += T) s->pair_w[c] = (unsigned)e.broad()[c];
+  team_sync();                                                          // (also ends the DMA of the geom table)
+  PH(62)
   // ---- func_narrow_phase_convex_vs_convex (narrowphase.py:964-1068), then func_narrow_phase_any_vs_terrain (:1197-1244): one lane per
   //      pair, ordered compaction; the terrain pass appends after all convex-convex contacts, as the two reference kernels do ----
   int nc_run = 0;
@@ -2763,21 +2815,26 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
   // what a contact of the pair (i_ga, i_gb) takes from the model and the env's geom records: requested BEFORE the pair's narrow-phase query, so the
   // append behind the query does not start with a memory round trip (one wave per SIMD: nothing else would cover it)
   struct PairConst { float friction, sol[7]; int link_a, link_b; };
-  auto load_pair_const = [&](int i_ga, int i_gb) {
+  struct Fric { float gf_a, fr_a, gf_b, fr_b; };                         // geom_friction / friction_ratio of the two geoms (batch 2)
+  auto load_fric = [&](int i_ga, int i_gb) { Fric f = {e.geom_friction()[i_ga], e.friction_ratio()[i_ga], e.geom_friction()[i_gb], e.friction_ratio()[i_gb]}; return f; };
+  auto pair_const = [&](int i_ga, int i_gb, const Fric& f) {            // solver parameters and links: from the geom table
     PairConst pc;
-    float friction_a = e.geom_friction()[i_ga] * e.friction_ratio()[i_ga];
-    float friction_b = e.geom_friction()[i_gb] * e.friction_ratio()[i_gb];
+    float friction_a = f.gf_a * f.fr_a;
+    float friction_b = f.gf_b * f.fr_b;
     pc.friction = fmx(fmx(friction_a, friction_b), 1e-2f);
 #pragma unroll
-    for (int q = 0; q < 7; ++q) pc.sol[q] = 0.5f * (m.geoms[i_ga].sol_params[q] + m.geoms[i_gb].sol_params[q]);
-    pc.link_a = m.geoms[i_ga].link; pc.link_b = m.geoms[i_gb].link;
+    for (int q = 0; q < 7; ++q) pc.sol[q] = 0.5f * (gk[i_ga].sol_params[q] + gk[i_gb].sol_params[q]);
+    pc.link_a = gk[i_ga].link; pc.link_b = gk[i_gb].link;
     return pc;
   };
+  // The contact counts of the lanes (0 ... MAX_CONTACTS_PER_PAIR) are exchanged with one ballot per bit of the count: a lane's offset is the sum over
+  // the lanes below it, in lane order -- the order of the pairs.  A lane reads only its own staging slots: no ordering point.
+  static_assert(MAX_CONTACTS_PER_PAIR < 8, "append_staged: three bits of contact count");
   auto append_staged = [&](const ContactStage& cs, int i_ga, int i_gb, const PairConst& pc) {
-    s->cnt[tl] = cs.n;
-    team_sync();
-    int off = 0, tot = 0;
-    for (int l = 0; l < T; ++l) { int c = s->cnt[l]; off += (l < tl) ? c : 0; tot += c; }
+    const unsigned long long b0 = team_ballot<T>((cs.n & 1) != 0), b1 = team_ballot<T>((cs.n & 2) != 0), b2 = team_ballot<T>((cs.n & 4) != 0);
+    const unsigned long long below = (1ull << tl) - 1ull;
+    const int off = __popcll(b0 & below) + 2 * __popcll(b1 & below) + 4 * __popcll(b2 & below);
+    const int tot = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
     for (int k = 0; k < cs.n; ++k) {
       int i_c = nc_run + off + k;
       if (i_c < m.max_contact_pairs) {
@@ -2794,23 +2851,29 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
       }
     }
     nc_run += tot;
-    team_sync();
   };
   bool any_plane_box = false;                                          // team-uniform: a plane-box pair is in the broad-phase list
   for (int it = 0; it < n_np_iter; ++it) {
     int ip = it * T + tl;
     ContactStage cs; cs.st = &s->stage[tl][0][0]; cs.n = 0;
-    int i_ga = 0, i_gb = 0;
-    bool convex_pair = false, plane_box = false;
-    if (ip < n_broad) {
-      int pk = s->pair_sorted[ip];
-      i_ga = pk & 0xff; i_gb = pk >> 8;
-      if (m.geoms[i_ga].type > m.geoms[i_gb].type) { int t = i_ga; i_ga = i_gb; i_gb = t; }
-      plane_box = m.geoms[i_ga].type == GEOM_PLANE && m.geoms[i_gb].type == GEOM_BOX;   // skipped here (narrowphase.py:1040), own pass below
-      convex_pair = m.geoms[i_gb].type != GEOM_TERRAIN && !plane_box;
+    const bool have = ip < n_broad;                                     // lanes without a pair run (0, 0): their loads stay in bounds, nothing is used
+    const unsigned pw = have ? s->pair_w[ip] : 0u;
+    int i_ga = (int)(pw & 0xffu), i_gb = (int)((pw >> 8) & 0xffu);
+    const int i_pair = imn((int)(pw >> 16), NPAIR - 1);
+    // batch 2: requested for the pair as listed; the swap by type below (table in LDS) exchanges what has been requested
+    PairIn pin = load_pair_in(e, i_ga, i_gb, i_pair);
+    Fric fric = load_fric(i_ga, i_gb);
+    if (gk[i_ga].type > gk[i_gb].type) {
+      int t = i_ga; i_ga = i_gb; i_gb = t;
+      V3 tp = pin.pos_a; pin.pos_a = pin.pos_b; pin.pos_b = tp;
+      Q4 tq = pin.quat_a; pin.quat_a = pin.quat_b; pin.quat_b = tq;
+      Fric tf = {fric.gf_b, fric.fr_b, fric.gf_a, fric.fr_a}; fric = tf;
     }
+    const bool plane_box = have && gk[i_ga].type == GEOM_PLANE && gk[i_gb].type == GEOM_BOX;   // skipped here (narrowphase.py:1040), own pass below
+    const bool convex_pair = have && gk[i_gb].type != GEOM_TERRAIN && !plane_box;
     any_plane_box |= team_ballot<T>(plane_box) != 0ull;
-    const PairConst pc = load_pair_const(i_ga, i_gb);
+    const PairConst pc = pair_const(i_ga, i_gb, fric);
+    PH(62)
     if constexpr (T == 16) {
       // MPR of every pair on its own lane; then the pairs whose MPR answer has to be replaced by safe GJK + EPA (narrowphase.py:727-845) are
       // answered by QUADS: the four quads of the team take four flagged pairs at a time (the four feet of a landing robot), the four lanes of a
@@ -2818,7 +2881,7 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
       static_assert(GJK_SLOTS >= 4, "one LDS polytope slot per quad");
       CcState cst;
       cst.want_gjk = false;
-      if (convex_pair) cc_detect0(m, e, i_ga, i_gb, s->ncv, cst);
+      if (convex_pair) cc_detect0(m, gk, e, i_ga, i_gb, i_pair, pin, s->ncv, cst);
       const bool wants = convex_pair && cst.want_gjk;
       const unsigned want = dgc_ballot<16>(wants);
       const int n_want = __popc(want), quad = tl >> 2, ql = tl & 3;
@@ -2834,7 +2897,7 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
         dp.pos_b = v3(__shfl(cst.pr.pos_b.x, Ls, 16), __shfl(cst.pr.pos_b.y, Ls, 16), __shfl(cst.pr.pos_b.z, Ls, 16));
         dp.quat_b = q4(__shfl(cst.pr.quat_b.w, Ls, 16), __shfl(cst.pr.quat_b.x, Ls, 16), __shfl(cst.pr.quat_b.y, Ls, 16), __shfl(cst.pr.quat_b.z, Ls, 16));
         if (L >= 0) {
-          dp.ga = geom_lite(m, dp.i_ga); dp.gb = geom_lite(m, dp.i_gb); dp.ra = make_rot(dp.quat_a); dp.rb = make_rot(dp.quat_b);
+          dp.ga = geom_lite(gk, dp.i_ga); dp.gb = geom_lite(gk, dp.i_gb); dp.ra = make_rot(dp.quat_a); dp.rb = make_rot(dp.quat_b);
           dp.discrete = dp.ga.type == GEOM_BOX && dp.gb.type == GEOM_BOX;  // func_is_discrete_geoms, collider/utils.py:105-126
           PHD_BEGIN
           DgResult gr = dgc_contact<4>(dp, s->gjk[quad], m.eps, ql);
@@ -2854,10 +2917,14 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
         cst.penetration = o[1];
         if (cst.is_col) { cst.normal = v3(o[2], o[3], o[4]); cst.contact_pos = v3(o[5], o[6], o[7]); }
       }
-      if (convex_pair) cc_rest(m, e, cst, cs, nullptr, &s->gjk_slot_mask, &gjk_scratch[(size_t)b * T + tl], s->ncv);
-    } else if (convex_pair) convex_convex_contact_staged(m, e, i_ga, i_gb, cs, s->gjk, &s->gjk_slot_mask, &gjk_scratch[(size_t)b * T + tl], s->ncv);
+      if (convex_pair) cc_rest(m, gk, e, cst, cs, nullptr, &s->gjk_slot_mask, &gjk_scratch[(size_t)b * T + tl], s->ncv);
+    } else if (convex_pair) convex_convex_contact_staged(m, gk, e, i_ga, i_gb, i_pair, pin, cs, s->gjk, &s->gjk_slot_mask, &gjk_scratch[(size_t)b * T + tl], s->ncv);
+    PH(63)
     append_staged(cs, i_ga, i_gb, pc);
+    team_sync_lds();                                                    // gjk_res and the polytope slots are rewritten by the next round
+    PH(33)
   }
+  team_sync();                                                          // the terrain pass lays its pair slots over the polytope slots
   // ---- func_narrow_phase_convex_specializations (narrowphase.py:1146-1170; collider.py:486-498): plane-box pairs, after all convex-convex
   //      contacts and before the terrain pass; one lane per pair, same ordered compaction ----
   if (any_plane_box) {
@@ -2866,12 +2933,12 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
       ContactStage cs; cs.st = &s->stage[tl][0][0]; cs.n = 0;
       int i_ga = 0, i_gb = 0;
       if (ip < n_broad) {
-        int pk = s->pair_sorted[ip];
-        i_ga = pk & 0xff; i_gb = pk >> 8;
-        if (m.geoms[i_ga].type > m.geoms[i_gb].type) { int t = i_ga; i_ga = i_gb; i_gb = t; }
-        if (m.geoms[i_ga].type == GEOM_PLANE && m.geoms[i_gb].type == GEOM_BOX) plane_box_contact_staged(m, e, i_ga, i_gb, cs);
+        const unsigned pk = s->pair_w[ip];
+        i_ga = (int)(pk & 0xffu); i_gb = (int)((pk >> 8) & 0xffu);
+        if (gk[i_ga].type > gk[i_gb].type) { int t = i_ga; i_ga = i_gb; i_gb = t; }
+        if (gk[i_ga].type == GEOM_PLANE && gk[i_gb].type == GEOM_BOX) plane_box_contact_staged(m, gk, e, i_ga, i_gb, cs);
       }
-      append_staged(cs, i_ga, i_gb, load_pair_const(i_ga, i_gb));
+      append_staged(cs, i_ga, i_gb, pair_const(i_ga, i_gb, load_fric(i_ga, i_gb)));
     }
   }
   // ---- func_narrow_phase_any_vs_terrain (narrowphase.py:1197-1244): appended after all convex-convex contacts.  One lane per heightfield
@@ -2881,10 +2948,10 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
     PH(33)
     int n_list = 0, i_terrain = 0;                                      // terrain pairs, in broad-phase order
     for (int ip = 0; ip < n_broad; ++ip) {
-      int pk = s->pair_sorted[ip];
-      int i_ga = pk & 0xff, i_gb = pk >> 8;
-      if (m.geoms[i_ga].type == GEOM_TERRAIN) { int t = i_ga; i_ga = i_gb; i_gb = t; }
-      if (m.geoms[i_gb].type != GEOM_TERRAIN) continue;
+      const unsigned pk = s->pair_w[ip];
+      int i_ga = (int)(pk & 0xffu), i_gb = (int)((pk >> 8) & 0xffu);
+      if (gk[i_ga].type == GEOM_TERRAIN) { int t = i_ga; i_ga = i_gb; i_gb = t; }
+      if (gk[i_gb].type != GEOM_TERRAIN) continue;
       if (n_list < NG) { if (tl == 0) s->tr.tp[n_list].i_ga = i_ga; i_terrain = i_gb; n_list++; }
     }
     team_sync();
@@ -2898,7 +2965,7 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
         i_ga = s->tr.tp[p].i_ga;
         V3 pos_t; Q4 quat_t;
         transform_pos_quat_by_trans_quat((V3)e.g_pos()[i_ga] - (V3)e.g_pos()[i_terrain], e.g_quat()[i_ga], v3(0, 0, 0), inv_quat(e.g_quat()[i_terrain]), pos_t, quat_t);
-        keep = m.terrain_cmax == nullptr || !terrain_pair_out_of_reach(m, geom_lite(m, i_ga), pos_t);
+        keep = m.terrain_cmax == nullptr || !terrain_pair_out_of_reach(m, geom_lite(gk, i_ga), pos_t);
       }
       const unsigned long long mk = team_ballot<T>(keep);
       team_sync();
@@ -2908,9 +2975,9 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
     }
     for (int p = tl; p < n_tp; p += T) {                                // pair setup: pose in the terrain frame, cell range, dedupe tolerance
       auto& t = s->tr.tp[p];
-      terrain_pair_setup(m, e, t.i_ga, i_terrain, t);
+      terrain_pair_setup(m, gk, e, t.i_ga, i_terrain, t);
       t.n_items = imx(0, t.r_max - t.r_min) * imx(0, 2 * (t.c_max - t.c_min + 1) - 2);   // prisms under the geom's bounding box ("cells")
-      t.tol = compute_tolerance(m, t.i_ga, i_terrain, m.mc_tolerance);
+      t.tol = compute_tolerance(gk, t.i_ga, i_terrain, m.mc_tolerance);
     }
     team_sync();
     PH(26)
@@ -2975,7 +3042,7 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
             const auto& t = s->tr.tp[d & 31];
             int r, k;
             terrain_desc_cell(t, d >> 5, r, k);
-            keep = !terrain_prism_separated_at_once(m, t, i_terrain, r, k);
+            keep = !terrain_prism_separated_at_once(m, gk, t, i_terrain, r, k);
           }
           const unsigned long long mk = team_ballot<T>(keep);
           if (keep) items[n_keep + __popcll(mk & ((1ull << tl) - 1ull))] = d;
@@ -2995,7 +3062,7 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
           V3 normal, cpos; float pen;
           int r, k;
           terrain_desc_cell(t, d >> 5, r, k);
-          if (terrain_prism_contact(m, e, t, i_terrain, r, k, normal, cpos, pen)) {
+          if (terrain_prism_contact(m, gk, e, t, i_terrain, r, k, normal, cpos, pen)) {
             has = 1 + (d & 31);
             st[0] = normal.x; st[1] = normal.y; st[2] = normal.z; st[3] = cpos.x; st[4] = cpos.y; st[5] = cpos.z; st[6] = pen;
           }
@@ -3035,8 +3102,8 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
             e.c_normal()[i_c] = v3(pc[0], pc[1], pc[2]); e.c_pos()[i_c] = v3(pc[3], pc[4], pc[5]); e.c_pen()[i_c] = pc[6];
             e.c_friction()[i_c] = fmx(fmx(friction_a, friction_b), 1e-2f);
             auto sol = e.c_sol()[i_c];
-            for (int qq = 0; qq < 7; ++qq) sol[qq] = 0.5f * (m.geoms[i_ga].sol_params[qq] + m.geoms[i_terrain].sol_params[qq]);
-            e.c_link()[i_c] = m.geoms[i_ga].link; e.c_link()[MAXC + i_c] = m.geoms[i_terrain].link;
+            for (int qq = 0; qq < 7; ++qq) sol[qq] = 0.5f * (gk[i_ga].sol_params[qq] + gk[i_terrain].sol_params[qq]);
+            e.c_link()[i_c] = gk[i_ga].link; e.c_link()[MAXC + i_c] = gk[i_terrain].link;
           } else {
             atomicOr(&e.err()[0], GO2SIM_ERR_OVERFLOW_COLLISION_PAIRS);
           }
@@ -4517,7 +4584,7 @@ __global__ __launch_bounds__(64) void k_debug_narrowphase(const Model* __restric
   if (which >= 3) {
     if (threadIdx.x >= 16) return;
     DgPair dp; dp.m = mp; dp.i_ga = i_ga; dp.i_gb = i_gb; dp.pos_a = pa; dp.quat_a = qa; dp.pos_b = pb; dp.quat_b = qb;
-    dp.ga = geom_lite(m, i_ga); dp.gb = geom_lite(m, i_gb); dp.ra = make_rot(qa); dp.rb = make_rot(qb);
+    dp.ga = geom_lite(m.gk, i_ga); dp.gb = geom_lite(m.gk, i_gb); dp.ra = make_rot(qa); dp.rb = make_rot(qb);
     dp.discrete = m.geoms[i_ga].type == GEOM_BOX && m.geoms[i_gb].type == GEOM_BOX;
     DgResult r;
     if (which <= 4) {                                                   // the form the collision kernel runs: a quad per query, the quad's LDS slot
@@ -4535,12 +4602,12 @@ __global__ __launch_bounds__(64) void k_debug_narrowphase(const Model* __restric
   }
   if (threadIdx.x != 0) return;
   if (which == 0) {
-    Pair pr; pr.i_ga = i_ga; pr.i_gb = i_gb; pr.pos_a = pa; pr.quat_a = qa; pr.pos_b = pb; pr.quat_b = qb; pr.prism = nullptr; pr.ga = geom_lite(m, i_ga); pr.gb = geom_lite(m, i_gb);
+    Pair pr; pr.i_ga = i_ga; pr.i_gb = i_gb; pr.pos_a = pa; pr.quat_a = qa; pr.pos_b = pb; pr.quat_b = qb; pr.prism = nullptr; pr.ga = geom_lite(m.gk, i_ga); pr.gb = geom_lite(m.gk, i_gb);
     pair_set_rots(pr);
-    mpr_contact(m, pr, v3(0, 0, 0), is_col, normal, pen, pos);
+    mpr_contact(m, m.gk, pr, v3(0, 0, 0), is_col, normal, pen, pos);
   } else {
     DgPair dp; dp.m = mp; dp.i_ga = i_ga; dp.i_gb = i_gb; dp.pos_a = pa; dp.quat_a = qa; dp.pos_b = pb; dp.quat_b = qb;
-    dp.ga = geom_lite(m, i_ga); dp.gb = geom_lite(m, i_gb); dp.ra = make_rot(qa); dp.rb = make_rot(qb);
+    dp.ga = geom_lite(m.gk, i_ga); dp.gb = geom_lite(m.gk, i_gb); dp.ra = make_rot(qa); dp.rb = make_rot(qb);
     dp.discrete = m.geoms[i_ga].type == GEOM_BOX && m.geoms[i_gb].type == GEOM_BOX;
     const DgResult r = (which == 1) ? gjk_query(dp, slots, &mask, full, m.eps) : gjk_query(dp, nullptr, &mask, full, m.eps);
     is_col = r.is_col; pen = r.penetration; normal = r.normal; pos = r.pos;
@@ -4548,7 +4615,24 @@ __global__ __launch_bounds__(64) void k_debug_narrowphase(const Model* __restric
   out8[0] = is_col ? 1.0f : 0.0f; out8[1] = pen; out8[2] = normal.x; out8[3] = normal.y; out8[4] = normal.z; out8[5] = pos.x; out8[6] = pos.y; out8[7] = pos.z;
 }
 
-__global__ __launch_bounds__(WG) void k_clear_ext(Pool P) {             // kernel_clear_external_force, abd/misc.py:874
+// The compact geom table of the narrow phase from the model just uploaded (upload_model): one lane per geom.  The derived terms are formed here, on
+// the device, with the operations guess_geoms_center and compute_tolerance used to apply to the init-AABB corners on every launch.
+__global__ __launch_bounds__(64) void k_build_geomk(const Model* __restrict__ mp, GeomK* __restrict__ gk) {
+  for (int i_g = (int)threadIdx.x; i_g < NG; i_g += 64) {
+    const Geom& G = mp->geoms[i_g];
+    GeomK k;
+    k.type = G.type; k.link = G.link;
+    for (int q = 0; q < 3; ++q) k.data[q] = G.data[q];
+    for (int q = 0; q < 7; ++q) k.sol_params[q] = G.sol_params[q];
+    k.center = G.center; k.aabb7 = G.aabb[7];
+    k.aabb_mid = 0.5f * (G.aabb[7] + G.aabb[0]);
+    k.aabb_size = G.aabb[7] - G.aabb[0];
+    k.aabb_diag = norm(G.aabb[7] - G.aabb[0]);
+    gk[i_g] = k;
+  }
+}
+
+__global__ __launch_bounds__(WG) void k_clear_ext(Pool P) {            // kernel_clear_external_force, abd/misc.py:874
   int b = blockIdx.x * WG + threadIdx.x;
   if (b >= P.B) return;
   E e(P, b);
@@ -6204,6 +6288,7 @@ struct go2sim {
   Model hm;                 // host copy of the model
   Model* dm = nullptr;      // device copy
   ModelS* dms = nullptr;    // device copy of the compact tables (staged into LDS by the team kernels)
+  GeomK* dgk = nullptr;     // the compact geom table of the narrow phase (staged into LDS by k_collide_team), derived on the device: upload_model
   Pool P = {nullptr, nullptr, 0, nullptr, nullptr};
   DCfg hcfg; DCfg* dcfg = nullptr; bool cfg_set = false;
   Glob* dglob = nullptr; Acc* dacc = nullptr; int* derr = nullptr;      // derr[0]: go2sim_check_errno, derr[1]: asynchronous poll
@@ -6236,6 +6321,20 @@ struct go2sim {
 };
 
 static inline dim3 grid_for(int B) { return dim3((B + WG - 1) / WG); }
+
+// The host model to the device, with everything derived from it: Model, the compact tables ModelS and the geom table of the narrow phase.  The one
+// place where h->dm is written whole, so that no derived table outlives the model it was made from.  Synchronous (hipMemcpy; the kernel is waited for).
+static int upload_model(go2sim* h) {
+  ModelS hs;
+  if (!build_model_s(h->hm, hs)) return GO2SIM_E_BADMODEL;
+  h->hm.gk = h->dgk;
+  HIPCHK(hipMemcpy(h->dm, &h->hm, sizeof(Model), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->dms, &hs, sizeof(ModelS), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_build_geomk, dim3(1), dim3(64), 0, 0, h->dm, h->dgk);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  return GO2SIM_E_OK;
+}
 
 static void timing_flush(go2sim* h) {
   for (int i = 0; i < h->ev_n; ++i) {
@@ -6374,7 +6473,7 @@ static void build_launch_list(const go2sim* h, LaunchList& L, int n, const StepI
     const bool more = i + 1 < n;
     int* lpt_cur = lpt_on ? h->lpt + ((lpt0 + i) & 1) * lpt_record_ints(h) : nullptr;
     int* lpt_next = lpt_on ? h->lpt + ((lpt0 + i + 1) & 1) * lpt_record_ints(h) : nullptr;
-    add_launch(L, T_COLLIDE, collide_kernel(h->collide_team), team_grid(h, h->collide_team), b, h->P, h->dm, h->gjk_scratch, lpt_cur, h->lpt_cap, solver_epw(h));
+    add_launch(L, T_COLLIDE, collide_kernel(h->collide_team), team_grid(h, h->collide_team), b, h->P, h->dm, h->dgk, h->gjk_scratch, lpt_cur, h->lpt_cap, solver_epw(h));
     const int Ts = terrain ? h->terrain_solver_team : h->solver_team;
     add_launch(L, T_SOLVE, solve_kernel(terrain, Ts, fuse_solve(h) ? (more ? 1 : 2) : 0), team_grid(h, Ts), b, h->P, h->dm, h->dms, h->solver_ovf, lpt_cur, lpt_next, h->lpt_cap);
     if (fuse_solve(h)) continue;
@@ -6451,7 +6550,7 @@ static void handle_release(go2sim* h) {
   if (h->ev_created) for (int i = 0; i < TIMING_RING; ++i) { (void)hipEventDestroy(h->ev0[i]); (void)hipEventDestroy(h->ev1[i]); }
   (void)hipFree(h->P.f); (void)hipFree(h->P.i); (void)hipFree(h->P.fa); (void)hipFree(h->P.ia); (void)hipFree(h->dm); (void)hipFree(h->dcfg);
   (void)hipFree(h->dglob); (void)hipFree(h->dacc); (void)hipFree(h->derr); (void)hipFree(h->solver_ovf); (void)hipFree(h->gjk_scratch); (void)hipFree(h->lpt);
-  (void)hipFree(h->terrain_hf); (void)hipFree(h->terrain_cmax); (void)hipFree(h->dms); (void)hipFree(h->didx);
+  (void)hipFree(h->terrain_hf); (void)hipFree(h->terrain_cmax); (void)hipFree(h->dms); (void)hipFree(h->dgk); (void)hipFree(h->didx);
   if (h->herr_pinned) (void)hipHostFree(h->herr_pinned);
   if (h->ev_errno) (void)hipEventDestroy(h->ev_errno);
   delete h;
@@ -6498,14 +6597,11 @@ int go2sim_create(const void* blob, size_t nbytes, int n_envs, int device, uint6
     CK(hipMemset(h->P.fa, 0, (size_t)ASTRIDE * n_envs * sizeof(float)));
     CK(hipMemset(h->P.ia, 0, (size_t)AISTRIDE * n_envs * sizeof(int)));
     CK(hipMalloc((void**)&h->dm, sizeof(Model)));
-    CK(hipMemcpy(h->dm, &h->hm, sizeof(Model), hipMemcpyHostToDevice));
-    {
-      ModelS hs;
-      if (!build_model_s(h->hm, hs)) { rc = GO2SIM_E_BADMODEL; goto fail; }
-      CK(hipMalloc((void**)&h->dms, MODELS_LDS_BYTES));   // padded: the LDS DMA of the team kernels reads whole KiB
-      CK(hipMemset(h->dms, 0, MODELS_LDS_BYTES));
-      CK(hipMemcpy(h->dms, &hs, sizeof(ModelS), hipMemcpyHostToDevice));
-    }
+    CK(hipMalloc((void**)&h->dms, MODELS_LDS_BYTES));   // padded: the LDS DMA of the team kernels reads whole KiB
+    CK(hipMemset(h->dms, 0, MODELS_LDS_BYTES));
+    CK(hipMalloc((void**)&h->dgk, GEOMK_LDS_BYTES));    // (the same)
+    CK(hipMemset(h->dgk, 0, GEOMK_LDS_BYTES));
+    if ((rc = upload_model(h)) != GO2SIM_E_OK) goto fail;
     CK(hipMalloc((void**)&h->dcfg, sizeof(DCfg)));
     CK(hipMalloc((void**)&h->dglob, sizeof(Glob)));
     CK(hipMalloc((void**)&h->dacc, sizeof(Acc)));
@@ -6729,8 +6825,7 @@ int go2sim_set_terrain(go2sim_t* h, const int16_t* hf, int rows, int cols, float
   float x1 = (float)(rows - 1) * horizontal_scale, y1 = (float)(cols - 1) * horizontal_scale, z0 = hmin - 1.0f, z1 = hmax;
   for (int c = 0; c < 8; ++c) G.aabb[c] = v3h((c & 4) ? x1 : 0.0f, (c & 2) ? y1 : 0.0f, (c & 1) ? z1 : z0);
   m.links[0].pos = v3h(origin[0], origin[1], origin[2]); m.links[0].quat = {1.0f, 0.0f, 0.0f, 0.0f};
-  HIPCHK(hipMemcpy(h->dm, &h->hm, sizeof(Model), hipMemcpyHostToDevice));
-  { ModelS hs; if (!build_model_s(h->hm, hs)) return GO2SIM_E_BADMODEL; HIPCHK(hipMemcpy(h->dms, &hs, sizeof(ModelS), hipMemcpyHostToDevice)); }
+  { const int rc = upload_model(h); if (rc != GO2SIM_E_OK) return rc; }   // geoms[0] changed: the geom table of the narrow phase is rebuilt with it
   hipLaunchKernelGGL(k_set_link0_pose, dim3((h->B + 255) / 256), dim3(256), 0, s, h->P, m.links[0].pos);
   launch_fk_team(h, s, 1, nullptr);
   HIPCHK(hipGetLastError());
@@ -6793,9 +6888,7 @@ int go2sim_env_configure(go2sim_t* h, const double* f, int nf, const int* i, int
     int d = c.i[GO2SIM_IC_MOTOR_DOF0 + k];
     if (c.i[GO2SIM_IC_MANUAL_PD]) { h->hm.dofs[d].kp = 0.0f; h->hm.dofs[d].kv = 0.0f; } else { h->hm.dofs[d].kp = c.f[GO2SIM_FC_KP]; h->hm.dofs[d].kv = c.f[GO2SIM_FC_KD]; }
   }
-  HIPCHK(hipMemcpy(h->dm, &h->hm, sizeof(Model), hipMemcpyHostToDevice));
-  { ModelS hs; if (!build_model_s(h->hm, hs)) return GO2SIM_E_BADMODEL; HIPCHK(hipMemcpy(h->dms, &hs, sizeof(ModelS), hipMemcpyHostToDevice)); }
-  HIPCHK(hipDeviceSynchronize());
+  { const int rc = upload_model(h); if (rc != GO2SIM_E_OK) return rc; }
   h->step_count = 0; h->action_write_idx = 0; h->cfg_set = true;
   return GO2SIM_E_OK;
 }

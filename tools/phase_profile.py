@@ -35,7 +35,7 @@ out = (ctypes.c_ulonglong * (64 * PH_MAX_WG))()
 lib.lib.go2sim_debug_phases(sim.h, out, 1)
 # the broad phase (30 AABB + clear, 31 endpoint sort, 32 candidate pairs) runs at the end of every dynamics pass (tk_broadphase), not in k_collide_team
 BROAD = [30, 31, 32]
-GROUPS_ = {"post_a": [12, 13, 14, 15, 16, 17], "solver": [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11], "dynamics": list(range(20, 26)) + BROAD, "collide": [33, 26, 27, 28, 29], "integrate_fk": [40, 41, 18, 19, 55]}
+GROUPS_ = {"post_a": [12, 13, 14, 15, 16, 17], "solver": [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11], "dynamics": list(range(20, 26)) + BROAD, "collide": [62, 63, 33, 26, 27, 28, 29], "integrate_fk": [40, 41, 18, 19, 55]}
 def xcd_block(bid, n):
     """logical block of physical workgroup `bid` in a grid of n (xcd_block() of csrc/go2sim.hip)"""
     q, r, x, i = n >> 3, n & 7, bid & 7, bid >> 3
@@ -96,7 +96,7 @@ if len(sys.argv) > 3 and sys.argv[3] == "each":
             rows[g].append((srt.mean(), srt[int(0.99 * len(srt))], srt[int(0.999 * len(srt))], srt[-1]))
             i = int(np.argmax(tot))
             if worst[g] is None or tot[i] > worst[g][0]:
-                worst[g] = (tot[i], {k: a[i, k] / (1 if g == "post_a" else 2) for k in ids}, {k: a[i, k] for k in (range(50, 55) if g == "solver" else list(range(34, 50)) + list(range(56, 64)))})
+                worst[g] = (tot[i], {k: a[i, k] / (1 if g == "post_a" else 2) for k in ids}, {k: a[i, k] for k in (range(50, 55) if g == "solver" else list(range(34, 50)) + list(range(56, 62)))})
     for g, r in rows.items():
         if not r: continue
         r = np.array(r)
@@ -108,12 +108,12 @@ for s in range(W, W + N):
 lib.lib.go2sim_debug_phases(sim.h, out, 1)
 a = np.frombuffer(out, dtype=np.uint64).reshape(PH_MAX_WG, 64).astype(np.float64)
 launches = 2 * N                                   # substep kernels: two launches per env step
-GROUPS = {"solver": [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11], "dynamics": list(range(20, 26)) + BROAD, "collide": [33, 26, 27, 28, 29], "integrate_fk": [40, 41, 18, 19, 55]}   # (18 / 19 / 55: parts of 41; ids 34-39, 42-49: PHD sections, printed above)
+GROUPS = {"solver": [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11], "dynamics": list(range(20, 26)) + BROAD, "collide": [62, 63, 33, 26, 27, 28, 29], "integrate_fk": [40, 41, 18, 19, 55]}   # (18 / 19 / 55: parts of 41; ids 34-39, 42-49: PHD sections, printed above)
 NAMES = {0: "stage", 1: "rows", 2: "init Ma/Jaref/update", 3: "Hessian", 4: "Cholesky factor", 5: "gradient solve", 6: "line search", 7: "qacc/constraint update",
          8: "active-set change test (FAST ORDER) / incremental Cholesky", 9: "prologue", 11: "commit", 20: "staging (+ pre-physics)", 21: "composite bodies", 22: "mass matrix", 23: "factorisation", 24: "bias forces", 25: "solve + stores",
-         30: "broad: AABB + clear", 31: "broad: endpoint sort", 32: "broad: candidate pairs", 33: "pair list + narrow phase", 26: "terrain pair setup/count", 27: "terrain descriptors", 28: "terrain prism MPR", 29: "terrain replay"}
+         30: "broad: AABB + clear", 31: "broad: endpoint sort", 32: "broad: candidate pairs", 62: "narrow: head (staging, pair operands)", 63: "narrow: queries + cc_rest", 33: "narrow: append, plane-box, rest", 26: "terrain pair setup/count", 27: "terrain descriptors", 28: "terrain prism MPR", 29: "terrain replay"}
 # sections inside lane-divergent code (PHD): cycles at id, number of executions at id + 1
-for name, i in (("GJK / EPA query, cooperative (quad)", 34), ("GJK / EPA query, one lane (perturbed detections)", 62), ("  of which GJK", 38), ("  of which EPA + witness", 42), ("    EPA nearest-face scan", 56), ("    EPA horizon walk", 58), ("    EPA face attachment", 60), ("  support pair evaluations (GJK / EPA)", 48), ("MPR query", 36)):
+for name, i in (("GJK / EPA query, cooperative (quad)", 34), ("  of which GJK", 38), ("  of which EPA + witness", 42), ("    EPA nearest-face scan", 56), ("    EPA horizon walk", 58), ("    EPA face attachment", 60), ("  support pair evaluations (GJK / EPA)", 48), ("MPR query", 36)):
     cyc, cnt = a[:, i], a[:, i + 1]
     if cnt.sum() > 0:
         print(f"-- {name}: {cnt.sum() / launches:8.1f} executions per launch (wave level), {cyc.sum() / cnt.sum():9.0f} cycles each; per WG-launch mean {cyc.mean() * PH_MAX_WG / max(1, (cyc > 0).sum()) / launches:9.0f}, slowest 1% {np.sort(cyc)[-max(1, int((cyc > 0).sum()) // 100):].mean() / launches:9.0f}")
