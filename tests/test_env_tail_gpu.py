@@ -8,7 +8,7 @@ differ between envs, ...), so a configuration that stops reaching its path fails
 import numpy as np
 import pytest
 
-from util import CpuEnv, GpuEnv, bits_equal, make_actions
+from util import CpuEnv, GpuEnv, bits_equal, make_actions, outputs_differing
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +38,7 @@ def _max_ep(cpu):
 
 
 def _compare_step(cpu, gpu, oc, og, where):
-    bad = [n for n, x, y in zip(("obs", "priv", "rew", "reset", "timeout"), oc, og) if not bits_equal(x, y)]
+    bad = outputs_differing(oc, og)
     bad += [n for n, k, dt in ENV_BUFS if not bits_equal(cpu.env_buf(n, k, dt), gpu.env_buf(n, k, dt))]
     bad += [f for f in POOL_FIELDS if not bits_equal(cpu.field(f), gpu.field(f))]
     assert not bad, f"{where}: {bad} differ from the fast oracle"

@@ -5,7 +5,7 @@ arguments of three graph nodes)."""
 import numpy as np
 import pytest
 
-from util import GpuEnv, bits_equal, make_actions
+from util import GpuEnv, bits_equal, make_actions, outputs_differing, with_knobs
 
 pytestmark = pytest.mark.gpu
 
@@ -14,20 +14,18 @@ ENV_BUFS = [("COMMANDS", 3, np.float32), ("EPISODE_LENGTH", 1, np.int32), ("EPIS
             ("FEET_AIR_TIME", 4, np.float32), ("FOOT_CONTACT", 4, np.int32), ("BASE_EULER", 3, np.float32)]
 
 
-def _env(hip_lib, blob, n_envs, task, monkeypatch, graph):
-    monkeypatch.setenv("GO2SIM_GRAPH", "1" if graph else "0")
-    e = GpuEnv(hip_lib, blob, n_envs, seed=9, task=task)
-    monkeypatch.delenv("GO2SIM_GRAPH")
-    return e
+def _env(hip_lib, blob, n_envs, task, graph):
+    with with_knobs({"GO2SIM_GRAPH": "1" if graph else "0"}):
+        return GpuEnv(hip_lib, blob, n_envs, seed=9, task=task)
 
 
 @pytest.mark.parametrize("task,n_envs", [("walk", 130), ("walk", 4096), ("stairs", 70), ("jump_dr", 130)])
-def test_graph_and_plain_executors_bit_equal(hip_lib, blob, monkeypatch, task, n_envs):
+def test_graph_and_plain_executors_bit_equal(hip_lib, blob, task, n_envs):
     import torch
     from go2_sim2real_locomotion_rl_amd.capi import C
 
     steps = 10 if n_envs == 4096 else 24
-    g, p = _env(hip_lib, blob, n_envs, task, monkeypatch, True), _env(hip_lib, blob, n_envs, task, monkeypatch, False)
+    g, p = _env(hip_lib, blob, n_envs, task, True), _env(hip_lib, blob, n_envs, task, False)
     assert g.sim.graph_status() == (True, 0) and p.sim.graph_status()[0] is False, "each handle runs the executor it was asked for"
     g.reset(); p.reset()
     from util import task_cfg
@@ -40,7 +38,7 @@ def test_graph_and_plain_executors_bit_equal(hip_lib, blob, monkeypatch, task, n
             for e in (g, p):
                 e.obs = torch.zeros_like(e.obs); e.priv = torch.zeros_like(e.priv); e.rew = torch.zeros_like(e.rew)
         og, op = g.step(a), p.step(a)
-        bad = [n for n, x, y in zip(("obs", "priv", "rew", "reset", "timeout"), og, op) if not bits_equal(x, y)]
+        bad = outputs_differing(og, op)
         bad += [n for n, k, dt in ENV_BUFS if not bits_equal(g.env_buf(n, k, dt), p.env_buf(n, k, dt))]
         assert not bad, f"{task} step {s}: {bad} differ between the executors"
         resets += int(og[3].sum()); reset_steps += int(og[3].sum() > 0)

@@ -15,7 +15,7 @@ tolerance 0).  These tests bound what the change of order does to the results, a
 import numpy as np
 import pytest
 
-from util import CpuEnv, F, make_actions
+from util import CpuEnv, F, make_actions, with_knobs
 
 STATE = ["F_QPOS", "F_VEL", "F_QACC_WS", "F_CTRL_FORCE", "F_CTRL_POS", "F_CTRL_VEL", "F_EXT_FORCE", "F_MASS_SHIFT", "F_COM_SHIFT", "F_GEOM_FRICTION",
          "F_NORMAL_CACHE", "F_SORT_VALUE"]
@@ -98,15 +98,14 @@ def test_free_run_statistics_agree(oracle_strict_lib, oracle_fast_lib, blob, tas
     assert abs(c_s - c_f) <= 0.02 * c_s + 0.02, f"mean contacts {c_s:.4f} vs {c_f:.4f}"
 
 
-def test_arrow_form_against_row_form(oracle_fast_lib, blob, monkeypatch):
+def test_arrow_form_against_row_form(oracle_fast_lib, blob):
     """The FAST ORDER factorisation of the Newton Hessian has two forms: the arrow form (legs eliminated first, csrc/go2sim.hip ts_cholesky_factor_arrow /
     oracle cholesky_factor_arrow) whenever no Hessian entry couples two legs, and the dense row form otherwise.  GO2SIM_NO_ARROW=1 (read when a model is
     parsed) switches the arrow form off; both solve the same systems, so short free runs agree like fast against strict."""
     n, steps = 64, 4
     arrow = CpuEnv(oracle_fast_lib, blob, n, seed=9, task="walk")
-    monkeypatch.setenv("GO2SIM_NO_ARROW", "1")
-    rows = CpuEnv(oracle_fast_lib, blob, n, seed=9, task="walk")
-    monkeypatch.delenv("GO2SIM_NO_ARROW")
+    with with_knobs({"GO2SIM_NO_ARROW": "1"}):
+        rows = CpuEnv(oracle_fast_lib, blob, n, seed=9, task="walk")
     arrow.reset(); rows.reset()
     acts = make_actions(24, n, seed=9, kind="0.5", n_act=arrow.n_act)
     differ = False

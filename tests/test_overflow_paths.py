@@ -14,72 +14,46 @@ import pytest
 
 from go2_sim2real_locomotion_rl_amd.capi import C, Go2Sim
 from go2_sim2real_locomotion_rl_amd.model_blob import load_model_json, pack_model
-from util import bits_equal, install_stairs
+from util import Handle, Pair, install_stairs, random_poses
 
 FIELDS = ["F_QPOS", "F_VEL", "F_ACC", "F_CONTACT_FORCE", "F_QFRC_CONSTRAINT", "F_EFC_FORCE", "F_CONTACT_PEN", "F_CONTACT_POS", "F_CONTACT_NORMAL",
           "I_N_CONTACTS", "I_N_CONSTRAINTS", "I_SOLVER_ITERS", "I_N_BROAD", "I_ERRNO", "I_CONTACT_GEOMS"]
 
 
-def _random_poses(B, seed, terrain_info=None, z_range=(0.06, 0.2)):
-    model = load_model_json()
-    lim = np.array([d["limit"] for d in model["dofs"]], np.float32)[6:]
-    rng = np.random.default_rng(seed)
-    qpos = np.zeros((19, B), np.float32)
-    quat = rng.standard_normal((4, B)); quat /= np.linalg.norm(quat, axis=0)
-    qpos[3:7] = quat
-    qpos[7:] = lim[:, :1] + (lim[:, 1:] - lim[:, :1]) * rng.random((12, B), dtype=np.float32)
-    if terrain_info is not None:                         # across the step edges of the steepest row
-        c = np.asarray(terrain_info["row_centers"], np.float32)[12]
-        qpos[0] = c[0] + rng.uniform(1.0, 3.0, B); qpos[1] = c[1] + rng.uniform(-0.5, 0.5, B); qpos[2] = c[2] + rng.uniform(*z_range, B)
-    else:
-        qpos[0] = rng.uniform(-1, 1, B); qpos[1] = rng.uniform(-1, 1, B); qpos[2] = rng.uniform(*z_range, B)
-    return qpos
-
-
-class _Pair:
-    """the same scene on the oracle (numpy) and on the HIP library (torch), driven through the C ABI"""
+class _Pair(Pair):
+    """the scene pair of these tests: optionally on the stairs (`info`: their terrain), states uploaded as qpos, steps counted in rows and contacts"""
 
     def __init__(self, oracle_lib, hip_lib, blob, B, terrain=False):
-        import torch
-
-        self.torch, self.B = torch, B
-        self.dev = torch.device("cuda:0")
-        self.cpu, self.gpu = Go2Sim(oracle_lib, blob, B, 0, 1), Go2Sim(hip_lib, blob, B, 0, 1)
         self.info = None
-        if terrain:
-            _, self.info = install_stairs(self.cpu); install_stairs(self.gpu)
+
+        def make(lib, gpu):
+            h = Handle(lib, blob, B, gpu)
+            if terrain:
+                _, self.info = install_stairs(h.sim)
+            return h
+
+        super().__init__(oracle_lib, hip_lib, blob, B, make)
 
     def upload(self, qpos):
-        self.cpu.set_field_np(C["GO2SIM_F_QPOS"], qpos)
-        self.gpu.set_field(C["GO2SIM_F_QPOS"], self.torch.from_numpy(np.ascontiguousarray(qpos)).to(self.dev))
-        for s in (self.cpu, self.gpu):
-            s.reset_caches(None, 0); s.forward_kinematics()
-
-    def gfield(self, name):
-        k, is_int = self.gpu.field_size(C["GO2SIM_" + name])
-        t = self.torch.zeros(k, self.B, dtype=self.torch.int32 if is_int else self.torch.float32, device=self.dev)
-        self.gpu.get_field(C["GO2SIM_" + name], t)
-        self.torch.cuda.synchronize()
-        return t.cpu().numpy()
+        self.put("F_QPOS", qpos)
+        self.both(lambda s: (s.reset_caches(None, 0), s.forward_kinematics()))
 
     def step_and_compare(self, steps, fields=FIELDS):
         mx_rows = mx_con = 0; errs = 0
         for s in range(steps):
-            self.cpu.scene_step(1); self.gpu.scene_step(1)
-            for f in fields:
-                a, b = self.cpu.get_field_np(C["GO2SIM_" + f]), self.gfield(f)
-                assert bits_equal(a, b), f"step {s}: {f} differs (rows max {mx_rows})"
-            rows = self.cpu.get_field_np(C["GO2SIM_I_N_CONSTRAINTS"])[0]
-            mx_rows = max(mx_rows, int(rows.max())); mx_con = max(mx_con, int(self.cpu.get_field_np(C["GO2SIM_I_N_CONTACTS"]).max()))
-            errs |= int(np.bitwise_or.reduce(self.cpu.get_field_np(C["GO2SIM_I_ERRNO"])[0]))
-        assert self.cpu.check_errno() == self.gpu.check_errno()
+            self.both(lambda sim: sim.scene_step(1))
+            self.compare(fields, f"step {s} (rows max {mx_rows})")
+            rows = self.cget("I_N_CONSTRAINTS")[0]
+            mx_rows = max(mx_rows, int(rows.max())); mx_con = max(mx_con, int(self.cget("I_N_CONTACTS").max()))
+            errs |= int(np.bitwise_or.reduce(self.cget("I_ERRNO")[0]))
+        assert self.cpu.sim.check_errno() == self.gpu.sim.check_errno()       # (compared with each other: the cap tests mean them to be non-zero)
         return mx_rows, mx_con, errs
 
 
 @pytest.mark.gpu
 def test_flat_ground_more_rows_than_lds(oracle_lib, hip_lib, blob):
     p = _Pair(oracle_lib, hip_lib, blob, 96)
-    p.upload(_random_poses(96, 5))
+    p.upload(random_poses(96, 5))
     mx_rows, mx_con, errs = p.step_and_compare(25)
     assert mx_rows > 128 and mx_con > 32, (mx_rows, mx_con)        # far beyond the 32 LDS rows of the flat-ground solver
     assert errs == 0
@@ -88,7 +62,7 @@ def test_flat_ground_more_rows_than_lds(oracle_lib, hip_lib, blob):
 @pytest.mark.gpu
 def test_terrain_more_rows_than_lds(oracle_lib, hip_lib, blob):
     p = _Pair(oracle_lib, hip_lib, blob, 96, terrain=True)
-    p.upload(_random_poses(96, 5, p.info, z_range=(-0.25, 0.3)))
+    p.upload(random_poses(96, 5, p.info, z_range=(-0.25, 0.3)))
     mx_rows, mx_con, errs = p.step_and_compare(20)
     assert mx_rows > 400 and mx_con > 100, (mx_rows, mx_con)       # > 96 LDS rows of the terrain solver; close to the 150-contact cap
     assert errs == 0
@@ -102,7 +76,7 @@ def test_contact_cap_overflow_parity(oracle_lib, hip_lib, terrain):
     model = copy.deepcopy(load_model_json())
     model["collider"]["max_contact_pairs"] = 24
     p = _Pair(oracle_lib, hip_lib, pack_model(model), 64, terrain=terrain)
-    p.upload(_random_poses(64, 9, p.info, z_range=(-0.25, 0.3) if terrain else (0.06, 0.2)))
+    p.upload(random_poses(64, 9, p.info, z_range=(-0.25, 0.3) if terrain else (0.06, 0.2)))
     mx_rows, mx_con, errs = p.step_and_compare(12)
     assert mx_con == 24 and errs == C["GO2SIM_ERR_OVERFLOW_COLLISION_PAIRS"], (mx_con, errs)
 
@@ -116,19 +90,18 @@ def test_broad_pair_cap_overflow_flag_parity(oracle_lib, hip_lib):
     model = copy.deepcopy(load_model_json())
     model["collider"]["max_broad_pairs"] = 12
     p = _Pair(oracle_lib, hip_lib, pack_model(model), 64)
-    p.upload(_random_poses(64, 9))
-    p.cpu.scene_step(1); p.gpu.scene_step(1)
-    ec, eg = p.cpu.get_field_np(C["GO2SIM_I_ERRNO"]), p.gfield("I_ERRNO")
+    p.upload(random_poses(64, 9))
+    p.both(lambda sim: sim.scene_step(1))
+    ec, eg = p.cget("I_ERRNO"), p.gget("I_ERRNO")
     assert np.array_equal(ec, eg) and (ec & C["GO2SIM_ERR_OVERFLOW_CANDIDATE_CONTACTS"]).any()
-    for f in ("I_N_BROAD", "I_N_CONTACTS", "I_CONTACT_GEOMS", "F_CONTACT_PEN", "F_QPOS", "F_VEL"):
-        assert bits_equal(p.cpu.get_field_np(C["GO2SIM_" + f]), p.gfield(f)), f
-    assert p.cpu.get_field_np(C["GO2SIM_I_N_BROAD"]).max() == 12
+    p.compare(("I_N_BROAD", "I_N_CONTACTS", "I_CONTACT_GEOMS", "F_CONTACT_PEN", "F_QPOS", "F_VEL"), "first step")
+    assert p.cget("I_N_BROAD").max() == 12
 
 
 def test_overflow_states_on_the_oracle(oracle_lib, blob):
     """CPU-side twin of the GPU tests above (no GPU needed): the uploaded states do reach the row counts the GPU tests are about."""
     sim = Go2Sim(oracle_lib, blob, 48, 0, 1)
-    sim.set_field_np(C["GO2SIM_F_QPOS"], _random_poses(48, 5))
+    sim.set_field_np(C["GO2SIM_F_QPOS"], random_poses(48, 5))
     sim.reset_caches(None, 0); sim.forward_kinematics()
     sim.scene_step(1)
     rows = sim.get_field_np(C["GO2SIM_I_N_CONSTRAINTS"])[0]

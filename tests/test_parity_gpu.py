@@ -7,7 +7,7 @@ the only exception are the double-precision reset statistics (atomic accumulatio
 import numpy as np
 import pytest
 
-from util import CpuEnv, GpuEnv, F, bits_equal, gs_on_oracle, make_actions
+from util import CpuEnv, GpuEnv, F, bits_equal, gs_on_oracle, make_actions, with_knobs
 
 pytestmark = pytest.mark.gpu
 
@@ -113,7 +113,7 @@ def _assert_timing_counts(t, steps, row):
     assert tuple(cnt) == tuple(steps * c for c in TIMING_COUNTS[row]), (row, steps, cnt)
 
 
-def test_graph_and_plain_launch_paths_agree(hip_lib, blob, monkeypatch):
+def test_graph_and_plain_launch_paths_agree(hip_lib, blob):
     """go2sim_env_step launches its kernel sequence as one hipGraph (default) or kernel by kernel (GO2SIM_NO_GRAPH=1, timing mode): same bits.
     Also covers a change of the output buffers between steps (new arguments of a graph node) and of the action buffer (a node parameter), and the
     number of timed scopes per step that timing mode accounts."""
@@ -121,9 +121,8 @@ def test_graph_and_plain_launch_paths_agree(hip_lib, blob, monkeypatch):
 
     n_envs, steps = 70, 60
     g = GpuEnv(hip_lib, blob, n_envs, seed=4)
-    monkeypatch.setenv("GO2SIM_NO_GRAPH", "1")
-    p = GpuEnv(hip_lib, blob, n_envs, seed=4)
-    monkeypatch.delenv("GO2SIM_NO_GRAPH")
+    with with_knobs({"GO2SIM_NO_GRAPH": "1"}):
+        p = GpuEnv(hip_lib, blob, n_envs, seed=4)
     t = _timed_env(hip_lib, blob, n_envs, 4)
     g.reset(); p.reset(); t.reset()
     t.sim.read_timing(reset=True)                                  # (the reset is a MISC scope)
@@ -173,12 +172,8 @@ def test_scene_step_bit_exact_with_uploaded_state(oracle_lib, hip_lib, blob):
     v = rng.standard_normal((18, B)).astype(np.float32)
     ctrl = np.zeros((18, B), np.float32); ctrl[6:] = 8.0 * rng.standard_normal((12, B))
     for e in (cpu, gpu):
-        setter = e.sim.set_field_np if e is cpu else None
         for name, arr in (("F_QPOS", q.astype(np.float32)), ("F_VEL", v), ("F_CTRL_FORCE", ctrl)):
-            if e is cpu:
-                e.sim.set_field_np(F(name), arr)
-            else:
-                e.set_field(name, arr)
+            e.set_field(name, arr)
         e.sim.reset_caches()
         e.sim.forward_kinematics()
     for s in range(30):
@@ -464,13 +459,12 @@ def test_mass_matrix_field_semantics(oracle_lib, hip_lib, blob):
     assert bits_equal(gpu.field("F_MASS_MAT"), sym.reshape(18 * 18, n).astype(np.float32))
 
 
-def test_row_form_factorisation_bit_exact(oracle_lib, hip_lib, blob, monkeypatch):
+def test_row_form_factorisation_bit_exact(oracle_lib, hip_lib, blob):
     """GO2SIM_NO_ARROW=1 (read when a model is parsed, both libraries): the dense row-form factorisation and solves of the Newton Hessian, which the product
     takes only when a constraint row couples two legs, for every solve -- HIP against the fast oracle, bit for bit."""
-    monkeypatch.setenv("GO2SIM_NO_ARROW", "1")
     n_envs, steps = 64, 60
-    cpu, gpu = CpuEnv(oracle_lib, blob, n_envs, seed=5), GpuEnv(hip_lib, blob, n_envs, seed=5)
-    monkeypatch.delenv("GO2SIM_NO_ARROW")
+    with with_knobs({"GO2SIM_NO_ARROW": "1"}):
+        cpu, gpu = CpuEnv(oracle_lib, blob, n_envs, seed=5), GpuEnv(hip_lib, blob, n_envs, seed=5)
     cpu.reset(); gpu.reset()
     acts = make_actions(steps, n_envs, seed=5, kind="mixed")
     for s, a in enumerate(acts):

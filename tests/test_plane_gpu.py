@@ -16,51 +16,12 @@ import os
 import numpy as np
 import pytest
 
-from go2_sim2real_locomotion_rl_amd.capi import Go2Sim
 from go2_sim2real_locomotion_rl_amd.model_blob import MODEL_JSON, load_model_json, pack_model, with_plane_ground
 from plane_ref import PlaneRef
-from util import F, GpuEnv, bits_equal, make_actions
+from util import GpuEnv, Handle, bits_equal, draw_plane_qpos, make_actions, outputs_differing, with_knobs
 
 MODEL_DIR = os.path.dirname(MODEL_JSON)
 PLANES = [dict(), dict(pos=(0.3, -0.2, 0.05), normal=(np.sin(0.15), -np.sin(0.1), 1.0))]
-
-
-class Scene:
-    """scene-level handle on the HIP library (numpy in / out)"""
-
-    def __init__(self, lib, model, n_envs, seed=1):
-        import torch
-
-        self.torch, self.dev, self.B = torch, torch.device("cuda:0"), n_envs
-        self.sim = Go2Sim(lib, pack_model(model), n_envs, 0, seed)
-
-    def get(self, name):
-        k, is_int = self.sim.field_size(F(name))
-        t = self.torch.zeros(k, self.B, dtype=self.torch.int32 if is_int else self.torch.float32, device=self.dev)
-        self.sim.get_field(F(name), t)
-        self.torch.cuda.synchronize()
-        return t.cpu().numpy()
-
-    def put(self, name, a):
-        self.sim.set_field(F(name), self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev))
-        self.torch.cuda.synchronize()
-
-
-def draw_qpos(model, rng, B):
-    """Base 0.08-0.4 m above the plane's origin, tilted up to 0.7 rad, any yaw; joints anywhere inside their limits."""
-    q = np.tile(np.asarray(model["qpos0"], np.float64)[:, None], (1, B))
-    q[0:2] = rng.uniform(-0.3, 0.3, (2, B))
-    q[2] = rng.uniform(0.08, 0.4, B)
-    ax = rng.normal(size=(3, B)); ax /= np.linalg.norm(ax, axis=0)
-    ang = rng.uniform(-0.7, 0.7, B) * np.where(rng.random(B) < 0.3, 0.2, 1.0)
-    qt = np.concatenate([np.cos(0.5 * ang)[None], np.sin(0.5 * ang) * ax])
-    yaw = rng.uniform(-np.pi, np.pi, B)
-    qy = np.stack([np.cos(0.5 * yaw), 0 * yaw, 0 * yaw, np.sin(0.5 * yaw)])
-    w1, x1, y1, z1 = qt; w2, x2, y2, z2 = qy
-    q[3:7] = [w1 * w2 - z1 * z2, x1 * w2 + y1 * z2, y1 * w2 - x1 * z2, w1 * z2 + z1 * w2]
-    lim = np.array([d["limit"] for d in model["dofs"]])[6:]
-    q[7:] = lim[:, :1] + (lim[:, 1:] - lim[:, :1]) * rng.random((len(lim), B))
-    return q.astype(np.float32)
 
 
 @pytest.mark.gpu
@@ -73,10 +34,10 @@ def test_contact_sets_against_reference(hip_lib):
         model = with_plane_ground(base, **kw)
         ref = PlaneRef(model)
         robot_geoms = [i for i in range(1, len(model["geoms"])) if model["collision_pair_idx"][i] >= 0]   # geoms paired with the ground (row 0)
-        s = Scene(hip_lib, model, B, seed=5 + k)
+        s = Handle(hip_lib, pack_model(model), B, True, seed=5 + k)
         acc_here = 0
         for rnd in range(8):
-            s.put("F_QPOS", draw_qpos(base, np.random.default_rng(100 * k + rnd), B))
+            s.put("F_QPOS", draw_plane_qpos(base, np.random.default_rng(100 * k + rnd), B))
             s.put("F_VEL", np.zeros((18, B), np.float32))
             s.sim.reset_caches(None, 0); s.sim.forward_kinematics()
             lp, lq = s.get("F_LINK_POS").reshape(-1, 3, B), s.get("F_LINK_QUAT").reshape(-1, 4, B)
@@ -122,7 +83,7 @@ def test_cube_contact_force_on_plane(box_lib, shape):
     """test_contact_forces (test_rigid_physics.py:1749-1800): after 50 steps the cube's net contact force is its weight, atol 1e-5."""
     m = with_plane_ground(load_model_json(os.path.join(MODEL_DIR, f"{shape}_model.json")))
     B = 8
-    s = Scene(box_lib, m, B)
+    s = Handle(box_lib, pack_model(m), B, True)
     weight = -m["gravity"][2] * m["links"][1]["inertial_mass"]
     for _ in range(50):
         s.sim.scene_step(1)
@@ -140,7 +101,7 @@ def test_cube_on_tilted_plane_sticks(box_lib):
     th = np.deg2rad(10.0)
     m = with_plane_ground(load_model_json(os.path.join(MODEL_DIR, "box_model.json")), normal=(np.sin(th), 0.0, np.cos(th)))
     B = 4
-    s = Scene(box_lib, m, B)
+    s = Handle(box_lib, pack_model(m), B, True)
     s.sim.set_friction(1.0)
     a = 0.5 * m["geoms"][1]["data"][2]
     q = np.zeros((7, B), np.float32)
@@ -167,7 +128,7 @@ STAND = [0.0, 0.0, 0.0, 0.0, 0.8, 0.8, 1.0, 1.0, -1.5, -1.5, -1.5, -1.5]      # 
 
 def stand(lib, model, B=16, steps=200):
     """qpos0 with the standing joint angles, held by engine PD control (kp 100, kv 10); `steps` scene steps of 2 substeps."""
-    s = Scene(lib, model, B)
+    s = Handle(lib, pack_model(model), B, True)
     for d in range(6, 18):
         s.sim.set_dof_gains(d, 100.0, 10.0, -model["dofs"][d]["force_range"][1], model["dofs"][d]["force_range"][1])
     q = np.tile(np.asarray(model["qpos0"], np.float32)[:, None], (1, B)); q[7:] = np.asarray(STAND, np.float32)[:, None]
@@ -202,18 +163,16 @@ KNOBS = ["GO2SIM_COLLIDE_TEAM=32", "GO2SIM_COLLIDE_TEAM=64", "GO2SIM_NO_GRAPH=1"
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("knob", KNOBS)
-def test_plane_scheduling_knobs_bit_equal(hip_lib, knob, monkeypatch):
+def test_plane_scheduling_knobs_bit_equal(hip_lib, knob):
     blob = pack_model(with_plane_ground(load_model_json()))
     n_envs, steps = 128, 20
-    k, v = knob.split("=")
-    monkeypatch.setenv(k, v)
-    env_k = GpuEnv(hip_lib, blob, n_envs, seed=3)
-    monkeypatch.delenv(k)
+    with with_knobs(dict([knob.split("=")])):
+        env_k = GpuEnv(hip_lib, blob, n_envs, seed=3)
     env_d = GpuEnv(hip_lib, blob, n_envs, seed=3)
     env_k.reset(); env_d.reset()
     for s, a in enumerate(make_actions(steps, n_envs, seed=3, kind="mixed", n_act=env_d.n_act)):
         out_k, out_d = env_k.step(a), env_d.step(a)
-        bad = [n for n, x, y in zip(("obs", "priv", "rew", "reset", "timeout"), out_k, out_d) if not bits_equal(x, y)]
+        bad = outputs_differing(out_k, out_d)
         assert not bad, f"{knob} step {s}: {bad} differ from the default build"
     for name in ("F_QPOS", "F_VEL", "F_CONTACT_POS", "F_CONTACT_PEN", "I_N_CONTACTS", "I_CONTACT_GEOMS"):
         assert bits_equal(env_k.field(name), env_d.field(name)), f"{knob}: {name} after {steps} steps"

@@ -15,7 +15,7 @@ from go2_sim2real_locomotion_rl_amd.model_blob import load_model_json, pack_mode
 from test_parity_gpu import FIELDS as STATE_FIELDS
 from test_terrain_ref import FIELDS, STAND, draw_qpos, robot_geoms
 from terrain_ref import TerrainRef
-from util import CpuEnv, GpuEnv, F, bits_equal
+from util import CpuEnv, GpuEnv, F, bits_equal, with_knobs
 
 
 def run_pair(oracle_lib, hip_lib, field, q, steps, B, seed=2, contact_x=False):
@@ -28,7 +28,7 @@ def run_pair(oracle_lib, hip_lib, field, q, steps, B, seed=2, contact_x=False):
     v = (0.3 * rng.standard_normal((18, B))).astype(np.float32)
     ctrl = np.zeros((18, B), np.float32); ctrl[6:] = 4.0 * rng.standard_normal((12, B))
     for name, arr in (("F_QPOS", q.astype(np.float32)), ("F_VEL", v), ("F_CTRL_FORCE", ctrl)):
-        cpu.sim.set_field_np(F(name), arr); gpu.set_field(name, arr)
+        cpu.set_field(name, arr); gpu.set_field(name, arr)
     for e in (cpu, gpu):
         e.sim.reset_caches(); e.sim.forward_kinematics()
     total, xs = 0, []
@@ -114,15 +114,14 @@ def test_cell_size_with_too_many_prisms_per_pair_is_refused(hip_lib):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("team", ["32", "64"])
-def test_collide_team_bit_equal_on_heightfields(hip_lib, team, monkeypatch):
+def test_collide_team_bit_equal_on_heightfields(hip_lib, team):
     B = 64
     blob = pack_model()
     for name in ("random", "spikes"):
         field = FIELDS[name]
         q = draw_qpos(load_model_json(), field, np.random.default_rng(9), B)
-        monkeypatch.setenv("GO2SIM_COLLIDE_TEAM", team)
-        env_k = GpuEnv(hip_lib, blob, B, seed=3)
-        monkeypatch.delenv("GO2SIM_COLLIDE_TEAM")
+        with with_knobs({"GO2SIM_COLLIDE_TEAM": team}):
+            env_k = GpuEnv(hip_lib, blob, B, seed=3)
         env_d = GpuEnv(hip_lib, blob, B, seed=3)
         for e in (env_k, env_d):
             e.sim.set_terrain(*field[:4])

@@ -1,7 +1,13 @@
-"""Shared helpers for the parity tests."""
+"""Shared helpers for the parity tests: the task configurations, one handle with numpy access to a library's fields (Handle), the env wrappers
+built on it (CpuEnv / GpuEnv), the oracle and the HIP library side by side (Pair, env_pair, step_pair), the GO2SIM_* knobs of a handle's creation
+(with_knobs), bit comparisons and the seeded input generators.  Imports without torch: what needs torch or the benchmark imports it when called."""
+import contextlib
+import os
+
 import numpy as np
 
 from go2_sim2real_locomotion_rl_amd.capi import C, Go2Sim
+from go2_sim2real_locomotion_rl_amd.model_blob import load_model_json
 from go2_sim2real_locomotion_rl_amd.configs import (build_stair_terrain, flatten_base_cfg, flatten_walk_cfg, get_crouch_cfgs, get_jump_cfgs,
                                                     get_stair_cfgs, get_walk_cfgs, with_per_env_dr)
 
@@ -57,17 +63,66 @@ def make_actions(steps, n_envs, seed=0, kind="mixed", n_act=NACT):
     return a
 
 
-class CpuEnv:
+@contextlib.contextmanager
+def with_knobs(env):
+    """Sets the GO2SIM_* variables of `env` (name -> value; None: no knob) around the body, which creates the handle(s): the libraries read their knobs in
+    go2sim_create.  They are removed again on the way out (put back to what they were), also when the body raises, so no handle created later
+    sees them."""
+    env = dict(env or {})
+    assert all(k.startswith("GO2SIM_") for k in env), env
+    before = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        yield
+    finally:
+        for k, v in before.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+
+
+class Handle:
+    """One Go2Sim with numpy access to its fields: on the CPU oracle directly, on the HIP library (gpu=True) through torch tensors on cuda:0."""
+
+    def __init__(self, lib, blob, n_envs, gpu, seed=1):
+        self.gpu, self.B = gpu, n_envs
+        self.sim = Go2Sim(lib, blob, n_envs, 0, seed)
+
+    def get(self, name):
+        if not self.gpu:
+            return self.sim.get_field_np(F(name))
+        import torch
+
+        k, is_int = self.sim.field_size(F(name))
+        t = torch.zeros(k, self.B, dtype=torch.int32 if is_int else torch.float32, device="cuda:0")
+        self.sim.get_field(F(name), t)
+        torch.cuda.synchronize()
+        return t.cpu().numpy()
+
+    def put(self, name, arr):
+        if not self.gpu:
+            return self.sim.set_field_np(F(name), arr)
+        import torch
+
+        k, is_int = self.sim.field_size(F(name))              # the field's own type and size, as set_field_np has them
+        arr = np.ascontiguousarray(arr, dtype=np.int32 if is_int else np.float32).reshape(k, self.B)
+        self.sim.set_field(F(name), torch.from_numpy(arr).to("cuda:0"))
+        torch.cuda.synchronize()                              # the source tensor is a temporary
+
+    field, set_field = get, put                               # the names the env-level tests use
+
+
+class CpuEnv(Handle):
     """Go2Env on the CPU oracle with numpy buffers."""
 
     def __init__(self, lib, blob, n_envs, seed=1, task="walk", **cfg_kw):
-        self.sim = Go2Sim(lib, blob, n_envs, 0, seed)
+        super().__init__(lib, blob, n_envs, False, seed)
         f, i, self.reward_names, nobs, npriv, self.n_act = task_cfg(task, n_envs, **cfg_kw)
         self.fcfg, self.icfg = f, i
         if task == "stairs":
             install_stairs(self.sim)
         self.sim.env_configure(f, i)
-        self.B = n_envs
         self.obs = np.zeros((n_envs, nobs), np.float32); self.priv = np.zeros((n_envs, npriv), np.float32)
         self.rew = np.zeros(n_envs, np.float32); self.rst = np.zeros(n_envs, np.uint8); self.to = np.zeros(n_envs, np.float32)
 
@@ -78,16 +133,13 @@ class CpuEnv:
         self.sim.env_step(np.ascontiguousarray(act, np.float32), self.obs, self.priv, self.rew, self.rst, self.to)
         return self.obs, self.priv, self.rew, self.rst, self.to
 
-    def field(self, name):
-        return self.sim.get_field_np(F(name))
-
     def env_buf(self, name, k, dtype=np.float32):
         out = np.zeros((self.B, k), dtype)
         self.sim.env_get(C["GO2SIM_EB_" + name], out)
         return out
 
 
-class GpuEnv:
+class GpuEnv(Handle):
     """Go2Env on the HIP library with torch (ROCm) buffers; everything goes through the C ABI."""
 
     def __init__(self, lib, blob, n_envs, seed=1, task="walk", **cfg_kw):
@@ -95,12 +147,11 @@ class GpuEnv:
 
         self.torch = torch
         self.dev = torch.device("cuda:0")
-        self.sim = Go2Sim(lib, blob, n_envs, 0, seed)
+        super().__init__(lib, blob, n_envs, True, seed)
         f, i, self.reward_names, nobs, npriv, self.n_act = task_cfg(task, n_envs, **cfg_kw)
         if task == "stairs":
             install_stairs(self.sim)
         self.sim.env_configure(f, i)
-        self.B = n_envs
         self.obs = torch.zeros(n_envs, nobs, device=self.dev); self.priv = torch.zeros(n_envs, npriv, device=self.dev)
         self.rew = torch.zeros(n_envs, device=self.dev); self.rst = torch.zeros(n_envs, dtype=torch.uint8, device=self.dev)
         self.to = torch.zeros(n_envs, device=self.dev)
@@ -113,20 +164,6 @@ class GpuEnv:
         self.sim.env_step(a, self.obs, self.priv, self.rew, self.rst, self.to)
         self.torch.cuda.synchronize()
         return self.obs.cpu().numpy(), self.priv.cpu().numpy(), self.rew.cpu().numpy(), self.rst.cpu().numpy(), self.to.cpu().numpy()
-
-    def field(self, name):
-        torch = self.torch
-        k, is_int = self.sim.field_size(F(name))
-        t = torch.zeros(k, self.B, dtype=torch.int32 if is_int else torch.float32, device=self.dev)
-        self.sim.get_field(F(name), t)
-        torch.cuda.synchronize()
-        return t.cpu().numpy()
-
-    def set_field(self, name, arr):
-        torch = self.torch
-        t = torch.from_numpy(np.ascontiguousarray(arr)).to(self.dev)
-        self.sim.set_field(F(name), t)
-        torch.cuda.synchronize()
 
     def env_buf(self, name, k, dtype=np.float32):
         torch = self.torch
@@ -150,3 +187,100 @@ def bits_equal(a, b):
     if a.dtype == np.float32:
         return np.array_equal(a.view(np.int32), b.view(np.int32))
     return np.array_equal(a, b)
+
+
+def outputs_differing(out_a, out_b):
+    """The names among the five outputs of an env step that are not bit-equal between two sides."""
+    return [n for n, x, y in zip(("obs", "priv", "rew", "reset", "timeout"), out_a, out_b) if not bits_equal(x, y)]
+
+
+def compare_fields(cpu, gpu, fields, where):
+    """Every field of `fields` is bit-equal on the two handles (or envs); the message names the ones that are not, and the place."""
+    bad = [f for f in fields if not bits_equal(cpu.get(f), gpu.get(f))]
+    assert not bad, f"{where}: {bad} differ from the fast oracle"
+
+
+class Pair:
+    """The same scene on the oracle (`cpu`) and on the HIP library (`gpu`), two Handles, driven through scene_step / put / forward_kinematics.
+    make(lib, gpu) builds a side where it takes more than a Handle of `blob` (another model, gains, a terrain)."""
+
+    def __init__(self, oracle_lib, hip_lib, blob, n_envs, make=None):
+        make = make or (lambda lib, gpu: Handle(lib, blob, n_envs, gpu))
+        self.B = n_envs
+        self.cpu, self.gpu = make(oracle_lib, False), make(hip_lib, True)
+
+    def put(self, name, arr):
+        self.cpu.put(name, arr); self.gpu.put(name, arr)
+
+    def both(self, fn):
+        fn(self.cpu.sim); fn(self.gpu.sim)
+
+    def cget(self, name):
+        return self.cpu.get(name)
+
+    def gget(self, name):
+        return self.gpu.get(name)
+
+    def compare(self, fields, where):
+        compare_fields(self.cpu, self.gpu, fields, where)
+
+
+def env_pair(oracle_lib, hip_lib, blob, n_envs, task, knobs=None, seed=3, **kw):
+    """The same env on the oracle and on the HIP library, both created under `knobs` and reset."""
+    with with_knobs(knobs):
+        cpu, gpu = CpuEnv(oracle_lib, blob, n_envs, seed=seed, task=task, **kw), GpuEnv(hip_lib, blob, n_envs, seed=seed, task=task, **kw)
+    cpu.reset(); gpu.reset()
+    return cpu, gpu
+
+
+def step_pair(cpu, gpu, acts, fields, tag, first_step=0):
+    """Steps both envs through `acts`; after every step `fields` and the five outputs must be bit-equal.  Yields (step, oracle outputs, HIP
+    outputs) once the step has been compared: the caller's bookkeeping is the body of its for loop, the errno check follows the loop."""
+    for s, a in enumerate(acts, start=first_step):
+        oc = cpu.step(a); og = gpu.step(a)
+        compare_fields(cpu, gpu, fields, f"{tag} step {s}")
+        bad = outputs_differing(oc, og)
+        assert not bad, f"{tag} step {s}: {bad}"
+        yield s, oc, og
+
+
+def bench_actions(steps, n_envs, task):
+    """The benchmark's own action tape (set C: open-loop sine gait), as numpy."""
+    import torch
+
+    from bench import make_actions as bench_make_actions
+    return bench_make_actions(steps, n_envs, torch.device("cpu"), workload=task).numpy()
+
+
+def random_poses(B, seed, terrain_info=None, z_range=(0.06, 0.2)):
+    """Go2 qpos (19, B): robots in random orientations with random joint angles close to the ground, lying on their sides and backs, with self
+    collisions; with terrain_info (install_stairs) across the step edges of the steepest row of the stairs."""
+    lim = np.array([d["limit"] for d in load_model_json()["dofs"]], np.float32)[6:]
+    rng = np.random.default_rng(seed)
+    qpos = np.zeros((19, B), np.float32)
+    quat = rng.standard_normal((4, B)); quat /= np.linalg.norm(quat, axis=0)
+    qpos[3:7] = quat
+    qpos[7:] = lim[:, :1] + (lim[:, 1:] - lim[:, :1]) * rng.random((12, B), dtype=np.float32)
+    if terrain_info is not None:
+        c = np.asarray(terrain_info["row_centers"], np.float32)[12]
+        qpos[0] = c[0] + rng.uniform(1.0, 3.0, B); qpos[1] = c[1] + rng.uniform(-0.5, 0.5, B); qpos[2] = c[2] + rng.uniform(*z_range, B)
+    else:
+        qpos[0] = rng.uniform(-1, 1, B); qpos[1] = rng.uniform(-1, 1, B); qpos[2] = rng.uniform(*z_range, B)
+    return qpos
+
+
+def draw_plane_qpos(model, rng, B):
+    """Base 0.08-0.4 m above the plane's origin, tilted up to 0.7 rad, any yaw; joints anywhere inside their limits."""
+    q = np.tile(np.asarray(model["qpos0"], np.float64)[:, None], (1, B))
+    q[0:2] = rng.uniform(-0.3, 0.3, (2, B))
+    q[2] = rng.uniform(0.08, 0.4, B)
+    ax = rng.normal(size=(3, B)); ax /= np.linalg.norm(ax, axis=0)
+    ang = rng.uniform(-0.7, 0.7, B) * np.where(rng.random(B) < 0.3, 0.2, 1.0)
+    qt = np.concatenate([np.cos(0.5 * ang)[None], np.sin(0.5 * ang) * ax])
+    yaw = rng.uniform(-np.pi, np.pi, B)
+    qy = np.stack([np.cos(0.5 * yaw), 0 * yaw, 0 * yaw, np.sin(0.5 * yaw)])
+    w1, x1, y1, z1 = qt; w2, x2, y2, z2 = qy
+    q[3:7] = [w1 * w2 - z1 * z2, x1 * w2 + y1 * z2, y1 * w2 - x1 * z2, w1 * z2 + z1 * w2]
+    lim = np.array([d["limit"] for d in model["dofs"]])[6:]
+    q[7:] = lim[:, :1] + (lim[:, 1:] - lim[:, :1]) * rng.random((len(lim), B))
+    return q.astype(np.float32)
