@@ -1,7 +1,8 @@
-"""Shared helpers for the parity tests: the task configurations, one handle with numpy access to a library's fields (Handle), the env wrappers
+"""Shared helpers for the parity tests: the task configurations, one handle with numpy access to a library's fields (Handle), one narrow-phase query on explicit poses (make_query), the env wrappers
 built on it (CpuEnv / GpuEnv), the oracle and the HIP library side by side (Pair, env_pair, step_pair), the GO2SIM_* knobs of a handle's creation
 (with_knobs), bit comparisons and the seeded input generators.  Imports without torch: what needs torch or the benchmark imports it when called."""
 import contextlib
+import ctypes
 import os
 
 import numpy as np
@@ -80,6 +81,23 @@ def with_knobs(env):
                 del os.environ[k]
             else:
                 os.environ[k] = v
+
+
+def make_query(lib, blob, prefix, gjk_which=1):
+    """One narrow-phase query on explicit poses through `prefix`debug_narrowphase: q(which, a, b, pa, qa, pb, qb) with which = 0: MPR from a cold
+    start, 1: safe GJK + EPA (on the HIP library `gjk_which` selects the backend, tests/test_gjk_epa.py HIP_BACKENDS)."""
+    sim = Go2Sim(lib, blob, 1, 0, 1)
+    fn = getattr(lib.lib, prefix + "debug_narrowphase")
+
+    def q(which, a, b, pa, qa, pb, qb):
+        out = np.zeros(8, np.float32)
+        arrs = [np.ascontiguousarray(x, np.float32) for x in (pa, qa, pb, qb)]
+        rc = fn(sim.h, gjk_which if which else 0, a, b, *[x.ctypes.data_as(ctypes.c_void_p) for x in arrs], out.ctypes.data_as(ctypes.c_void_p))
+        assert rc == 0
+        return dict(is_col=bool(out[0]), pen=float(out[1]), normal=out[2:5].copy(), pos=out[5:8].copy(), raw=out.copy())
+
+    q.sim = sim
+    return q
 
 
 class Handle:
