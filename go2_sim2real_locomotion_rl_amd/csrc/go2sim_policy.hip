@@ -119,7 +119,8 @@ __device__ __forceinline__ void mlp_layer(const MlpDev& M, int l, const float (*
             const int gr = row0 + r;
             if (gr < B && n < dout) y[(size_t)gr * dout + n] = v;
           } else {
-            out[r][n] = elu1(v);
+            out[r][n] = n < dout ? elu1(v) : 0.0f;                       // the K padding of the next layer is zero whatever the inputs: a non-finite
+                                                                         // activation times the padded weight 0 would be NaN here and in every output after it
           }
         }
     }
@@ -190,12 +191,22 @@ __global__ __launch_bounds__(64) void k_rollout_add(float* __restrict__ rew, flo
   rew[b] = rr; val[b] = vv; don[b] = d[b];
 }
 constexpr int GAE_WG = 256;
-// one lane per env walks the rollout backwards; per-workgroup moments of the advantages in a fixed order
+// a workgroup's sum of one float64 per lane, in a fixed order (pairwise tree); the result is valid on lane 0
+__device__ __forceinline__ double wg_tree_sum(double* s, double v) {
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int k = GAE_WG / 2; k > 0; k >>= 1) {
+    if ((int)threadIdx.x < k) s[threadIdx.x] += s[threadIdx.x + k];
+    __syncthreads();
+  }
+  return s[0];
+}
+// one lane per env walks the rollout backwards; per-workgroup sum of the advantages in a fixed order
 __global__ __launch_bounds__(GAE_WG) void k_gae(const float* __restrict__ rew, const float* __restrict__ val, const uint8_t* __restrict__ don, const float* __restrict__ last_values,
                                                 int T, int B, float gamma, float lam, float* __restrict__ ret, float* __restrict__ adv, double* __restrict__ partial) {
-  __shared__ double s_sum[GAE_WG], s_sq[GAE_WG];
+  __shared__ double s_sum[GAE_WG];
   const int b = blockIdx.x * GAE_WG + threadIdx.x;
-  double sum = 0.0, sq = 0.0;
+  double sum = 0.0;
   if (b < B) {
     float advantage = 0.0f, next_v = last_values[b];
     for (int t = T - 1; t >= 0; --t) {
@@ -208,17 +219,31 @@ __global__ __launch_bounds__(GAE_WG) void k_gae(const float* __restrict__ rew, c
       ret[i] = r;
       const float a = r - v;
       adv[i] = a;
-      sum += (double)a; sq += (double)a * (double)a;
+      sum += (double)a;
       next_v = v;
     }
   }
-  s_sum[threadIdx.x] = sum; s_sq[threadIdx.x] = sq;
-  __syncthreads();
-  for (int s = GAE_WG / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) { s_sum[threadIdx.x] += s_sum[threadIdx.x + s]; s_sq[threadIdx.x] += s_sq[threadIdx.x + s]; }
-    __syncthreads();
+  const double s = wg_tree_sum(s_sum, sum);
+  if (threadIdx.x == 0) partial[2 * blockIdx.x] = s;
+}
+// second pass: per-workgroup sum of the squared deviations from the mean of ALL advantages of the handle.  (Sum and sum of squares in one pass lose
+// mean^2 / variance of the variance's digits: six of float64's sixteen at advantages = 1000 +- 0.01.)
+__global__ __launch_bounds__(GAE_WG) void k_gae_dev2(const float* __restrict__ adv, int T, int B, int n_wg, double count, double* __restrict__ partial) {
+  __shared__ double s_sq[GAE_WG];
+  __shared__ double s_mean;
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int i = 0; i < n_wg; ++i) s += partial[2 * i];                // the order of k_gae_moments: every workgroup gets the same bits
+    s_mean = s / count;
   }
-  if (threadIdx.x == 0) { partial[2 * blockIdx.x] = s_sum[0]; partial[2 * blockIdx.x + 1] = s_sq[0]; }
+  __syncthreads();
+  const double mean = s_mean;
+  const int b = blockIdx.x * GAE_WG + threadIdx.x;
+  double sq = 0.0;
+  if (b < B)
+    for (int t = T - 1; t >= 0; --t) { const double d = (double)adv[(size_t)t * B + b] - mean; sq += d * d; }
+  const double q = wg_tree_sum(s_sq, sq);
+  if (threadIdx.x == 0) partial[2 * blockIdx.x + 1] = q;
 }
 __global__ void k_gae_moments(const double* __restrict__ partial, int n_wg, double count, double* __restrict__ moments3) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
@@ -230,7 +255,7 @@ __global__ __launch_bounds__(256) void k_adv_normalize(float* __restrict__ adv, 
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const double N = moments3[2], mean = moments3[0] / N;
-  double var = (moments3[1] - N * mean * mean) / (N > 1.0 ? N - 1.0 : 1.0);   // torch.std: unbiased
+  double var = moments3[1] / (N > 1.0 ? N - 1.0 : 1.0);                       // torch.std: unbiased
   if (var < 0.0) var = 0.0;
   const float meanf = (float)mean, stdf = (float)sqrt(var);
   adv[i] = (adv[i] - meanf) / (stdf + 1e-8f);
@@ -255,7 +280,7 @@ struct go2sim_rollout {
   int T = 0, B = 0, n_wg = 0;
   float* f = nullptr;        // rewards | values | returns | advantages, each [T][B]
   uint8_t* dones = nullptr;  // [T][B]
-  double* partial = nullptr; // per-workgroup (sum, sum of squares)
+  double* partial = nullptr; // per-workgroup (sum, sum of squared deviations from the mean)
 };
 
 namespace {
@@ -396,6 +421,7 @@ int go2sim_rollout_compute_returns(go2sim_rollout_t* h, const float* last_values
   if (!h || !last_values || !moments3) return GO2SIM_E_BADARG;
   const size_t n = (size_t)h->T * h->B;
   hipLaunchKernelGGL(k_gae, dim3(h->n_wg), dim3(GAE_WG), 0, (hipStream_t)stream, h->f, h->f + n, h->dones, last_values, h->T, h->B, gamma, lam, h->f + 2 * n, h->f + 3 * n, h->partial);
+  hipLaunchKernelGGL(k_gae_dev2, dim3(h->n_wg), dim3(GAE_WG), 0, (hipStream_t)stream, h->f + 3 * n, h->T, h->B, h->n_wg, (double)n, h->partial);
   hipLaunchKernelGGL(k_gae_moments, dim3(1), dim3(1), 0, (hipStream_t)stream, h->partial, h->n_wg, (double)n, moments3);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;

@@ -6,7 +6,7 @@ curriculum counters (+ the friction-throttle counter), the same state machine on
 
 Environments are fully independent, so the hot path shards as contiguous blocks of envs per GPU with NO
 physics traffic.  The only collective the path needs is the rollout advantage-normalisation statistics:
-an all-gather of [sum, sum of squares, count] (3 floats per rank) over RCCL/xGMI (backend "nccl" on ROCm,
+an all-gather of [sum, sum of squared deviations from the rank's mean, count] (3 floats per rank) over RCCL/xGMI (backend "nccl" on ROCm,
 "gloo" in the CPU tests).  The reference has no distributed code on this path (its only multi-GPU artefact
 is examples/ddp_multi_gpu.py:36-90, one independent scene per rank with seed=local_rank)."""
 import torch
@@ -26,20 +26,39 @@ def shard_envs(total_envs: int, world_size: int, rank: int):
     return start, count
 
 
-def global_mean_std(x: torch.Tensor, group=None):
-    """Mean / unbiased std (``torch.std``) of `x` over all ranks, via ONE all-gather of 3 values per rank.  The moments are accumulated in
-    float64, as ``k_adv_normalize`` (csrc/go2sim_policy.hip) does, so that both advantage normalisations of the package agree."""
-    xd = x.reshape(-1).to(torch.float64)
-    m = torch.stack([xd.sum(), (xd * xd).sum(), torch.tensor(float(xd.numel()), device=x.device, dtype=torch.float64)])
+def merge_moments(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """[sum, M2, count] of the union of two sets from theirs, M2 the sum of squared deviations from the set's own mean (Chan et al.):
+    M2 = M2_a + M2_b + (mean_b - mean_a)^2 n_a n_b / (n_a + n_b).  Unlike a sum of squares, nothing here is of the size of mean^2."""
+    n = a[2] + b[2]
+    delta = b[0] / b[2] - a[0] / a[2]
+    return torch.stack([a[0] + b[0], a[1] + b[1] + delta * delta * (a[2] * b[2] / n), n])
+
+
+def _merge_ranks(m: torch.Tensor, group=None) -> torch.Tensor:
+    """One all-gather of 3 values per rank, merged in rank order so that every rank gets the same bits; identity for a single process."""
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
         world = dist.get_world_size(group)
         out = torch.empty(3 * world, device=m.device, dtype=m.dtype)
-        dist.all_gather_into_tensor(out, m, group=group)
-        m = out.view(world, 3).sum(0)
+        dist.all_gather_into_tensor(out, m.contiguous(), group=group)
+        out = out.view(world, 3)
+        g = out[0].clone()
+        for r in range(1, world):
+            g = merge_moments(g, out[r])
+        return g
+    return m
+
+
+def global_mean_std(x: torch.Tensor, group=None):
+    """Mean / unbiased std (``torch.std``) of `x` over all ranks, via ONE all-gather of 3 values per rank.  The moments are the library's
+    (go2sim_rollout_compute_returns): float64, the squared deviations taken in a second pass, so that both advantage normalisations of the
+    package agree."""
+    xd = x.reshape(-1).to(torch.float64)
+    s = xd.sum()
+    d = xd - s / xd.numel()
+    m = _merge_ranks(torch.stack([s, (d * d).sum(), torch.tensor(float(xd.numel()), device=x.device, dtype=torch.float64)]), group)
     n = m[2]
-    mean = m[0] / n
-    var = torch.clamp((m[1] - n * mean * mean) / torch.clamp(n - 1.0, min=1.0), min=0.0)
-    return mean.to(torch.float32), torch.sqrt(var).to(torch.float32)
+    var = torch.clamp(m[1] / torch.clamp(n - 1.0, min=1.0), min=0.0)
+    return (m[0] / n).to(torch.float32), torch.sqrt(var).to(torch.float32)
 
 
 def normalize_advantages(adv: torch.Tensor, group=None, eps: float = 1e-8) -> torch.Tensor:
@@ -50,18 +69,10 @@ def normalize_advantages(adv: torch.Tensor, group=None, eps: float = 1e-8) -> to
 
 
 def allgather_moments(moments3: torch.Tensor, group=None) -> torch.Tensor:
-    """Global [sum, sum of squares, count] from the per-rank moments of go2sim_rollout_compute_returns (float64[3]): one all-gather of
-    3 values per rank (RCCL over xGMI with backend "nccl", gloo in the CPU tests), summed in rank order so that every rank gets the same bits."""
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
-        world = dist.get_world_size(group)
-        out = torch.empty(3 * world, device=moments3.device, dtype=moments3.dtype)
-        dist.all_gather_into_tensor(out, moments3.contiguous(), group=group)
-        out = out.view(world, 3)
-        g = out[0].clone()
-        for r in range(1, world):
-            g = g + out[r]
-        return g
-    return moments3
+    """Global [sum, sum of squared deviations from the mean, count] from the per-rank moments of go2sim_rollout_compute_returns (float64[3]):
+    one all-gather of 3 values per rank (RCCL over xGMI with backend "nccl", gloo in the CPU tests), merged in rank order (merge_moments) so that
+    every rank gets the same bits."""
+    return _merge_ranks(moments3, group)
 
 
 def sync_env_globals(sim, group=None, stream=None, initial=False):

@@ -1,7 +1,7 @@
 """RolloutStorage -- the part of ``rsl_rl.storage.RolloutStorage`` (rsl-rl-lib==2.2.4) that sits between the env step and the PPO update:
 ``add_transitions`` (with PPO.process_env_step's time-out bootstrap) and ``compute_returns`` (GAE(lambda) + advantage normalisation), on the
 device through the C ABI (include/go2sim_policy.h).  In a multi-GPU job the normalisation statistics are global: the local moments
-[sum, sum of squares, count] are all-gathered over RCCL (one collective of 3 float64 per rank and rollout).
+[sum, sum of squared deviations from the mean, count] are all-gathered and merged over RCCL (one collective of 3 float64 per rank and rollout).
 
     storage = RolloutStorage(24, env.num_envs)
     for t in range(24):

@@ -99,6 +99,7 @@ int go2sim_cpu_policy_act(go2sim_mlp_t* actor, go2sim_mlp_t* critic, const float
   if (!mu) { mu_buf.resize((size_t)n_rows * A); mu = mu_buf.data(); }
   go2sim_cpu_mlp_forward(actor, obs, mu, n_rows, nullptr);
   if (critic) go2sim_cpu_mlp_forward(critic, critic_obs, values, n_rows, nullptr);
+#pragma omp parallel for schedule(static)
   for (int b = 0; b < n_rows; ++b) {
     float lp = 0.0f;
     for (int blk = 0; 4 * blk < A; ++blk) {
@@ -149,14 +150,16 @@ int go2sim_cpu_rollout_compute_returns(go2sim_rollout_t* h, const float* last_va
   const int T = h->T, B = h->B;
   const size_t n = (size_t)T * B;
   const float* rew = h->f.data(); const float* val = rew + n; float* ret = h->f.data() + 2 * n; float* adv = h->f.data() + 3 * n;
-  // same summation tree as the device kernel: 256-env workgroups, pairwise tree inside, workgroups in order
+  // same summation trees as the device kernels: 256-env workgroups, pairwise tree inside, workgroups in order; first the sum, then the squared
+  // deviations from the mean (two passes: see k_gae_dev2)
   const int WG = 256, n_wg = (B + WG - 1) / WG;
+  auto tree = [](double* s) { for (int k = 256 / 2; k > 0; k >>= 1) for (int l = 0; l < k; ++l) s[l] += s[l + k]; return s[0]; };
   double S = 0.0, Q = 0.0;
   for (int w = 0; w < n_wg; ++w) {
-    double s_sum[256], s_sq[256];
+    double s_sum[256];
     for (int l = 0; l < WG; ++l) {
       const int b = w * WG + l;
-      double sum = 0.0, sq = 0.0;
+      double sum = 0.0;
       if (b < B) {
         float advantage = 0.0f, next_v = last_values[b];
         for (int t = T - 1; t >= 0; --t) {
@@ -169,14 +172,25 @@ int go2sim_cpu_rollout_compute_returns(go2sim_rollout_t* h, const float* last_va
           ret[i] = r;
           const float a = r - v;
           adv[i] = a;
-          sum += (double)a; sq += (double)a * (double)a;
+          sum += (double)a;
           next_v = v;
         }
       }
-      s_sum[l] = sum; s_sq[l] = sq;
+      s_sum[l] = sum;
     }
-    for (int s = WG / 2; s > 0; s >>= 1) for (int l = 0; l < s; ++l) { s_sum[l] += s_sum[l + s]; s_sq[l] += s_sq[l + s]; }
-    S += s_sum[0]; Q += s_sq[0];
+    S += tree(s_sum);
+  }
+  const double mean = S / (double)n;
+  for (int w = 0; w < n_wg; ++w) {
+    double s_sq[256];
+    for (int l = 0; l < WG; ++l) {
+      const int b = w * WG + l;
+      double sq = 0.0;
+      if (b < B)
+        for (int t = T - 1; t >= 0; --t) { const double d = (double)adv[(size_t)t * B + b] - mean; sq += d * d; }
+      s_sq[l] = sq;
+    }
+    Q += tree(s_sq);
   }
   moments3[0] = S; moments3[1] = Q; moments3[2] = (double)n;
   return GO2SIM_E_OK;
@@ -186,7 +200,7 @@ int go2sim_cpu_rollout_normalize(go2sim_rollout_t* h, const double* moments3, vo
   const size_t n = (size_t)h->T * h->B;
   float* adv = h->f.data() + 3 * n;
   const double N = moments3[2], mean = moments3[0] / N;
-  double var = (moments3[1] - N * mean * mean) / (N > 1.0 ? N - 1.0 : 1.0);
+  double var = moments3[1] / (N > 1.0 ? N - 1.0 : 1.0);
   if (var < 0.0) var = 0.0;
   const float meanf = (float)mean, stdf = (float)sqrt(var);
   for (size_t i = 0; i < n; ++i) adv[i] = (adv[i] - meanf) / (stdf + 1e-8f);
