@@ -9,7 +9,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 REPO_ROOT = os.path.dirname(_HERE)
 HIP_SRC = os.path.join(_HERE, "csrc", "go2sim.hip")
 HIP_SRC_POLICY = os.path.join(_HERE, "csrc", "go2sim_policy.hip")
+HIP_SRC_TRAIN = os.path.join(_HERE, "csrc", "go2sim_train.hip")             # the PPO update (include/go2sim_train.h): product library only
 HIP_HDR_GJK = os.path.join(_HERE, "csrc", "go2sim_gjk_dev.h")
+HIP_HDR_MLP = os.path.join(_HERE, "csrc", "go2sim_mlp_dev.h")               # shared by go2sim_policy.hip and go2sim_train.hip
 HIP_LIB = os.path.join(_HERE, "csrc", "libgo2sim.so")
 ORACLE_SRC = os.path.join(REPO_ROOT, "oracle", "go2sim_cpu.cpp")
 ORACLE_SRC_POLICY = os.path.join(REPO_ROOT, "oracle", "policy_cpu.cpp")
@@ -36,10 +38,10 @@ def _headers():
 
 
 def build_hip(force=False, verbose=True):
-    if not force and _newer(HIP_LIB, HIP_SRC, HIP_SRC_POLICY, HIP_HDR_GJK, *_headers()):
+    if not force and _newer(HIP_LIB, HIP_SRC, HIP_SRC_POLICY, HIP_SRC_TRAIN, HIP_HDR_GJK, HIP_HDR_MLP, *_headers()):
         return HIP_LIB
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    cmd = [hipcc, *HIP_FLAGS, HIP_SRC, HIP_SRC_POLICY, "-o", HIP_LIB]
+    cmd = [hipcc, *HIP_FLAGS, HIP_SRC, HIP_SRC_POLICY, HIP_SRC_TRAIN, "-o", HIP_LIB]
     if verbose:
         print("[build]", " ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)
@@ -50,7 +52,7 @@ def build_hip_variant(name, extra_flags, force=False, verbose=True):
     """A diagnostic BUILD of the product library with extra -D flags (tools/lib_<name>.so); test infrastructure for builds the
     product does not ship -- e.g. ("bracket_inline", ["-DGO2SIM_BRACKET_INLINE"]), see DESIGN.md "update_bracket"."""
     out = os.path.join(REPO_ROOT, "tools", f"lib_{name}.so")
-    if not force and _newer(out, HIP_SRC, HIP_SRC_POLICY, HIP_HDR_GJK, *_headers()):
+    if not force and _newer(out, HIP_SRC, HIP_SRC_POLICY, HIP_HDR_GJK, HIP_HDR_MLP, *_headers()):
         return out
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     cmd = [hipcc, *HIP_FLAGS, *extra_flags, HIP_SRC, HIP_SRC_POLICY, "-o", out]

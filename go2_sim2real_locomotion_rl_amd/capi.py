@@ -48,6 +48,22 @@ C, DECLARED_FUNCS = _parse_header()
 _C_POLICY, _DECL_POLICY = _parse_header(os.path.join(REPO_ROOT, "include", "go2sim_policy.h"))
 C.update(_C_POLICY)
 DECLARED_FUNCS = DECLARED_FUNCS + _DECL_POLICY
+# the PPO update (include/go2sim_train.h) exists in the product library only: it has no go2sim_cpu_ twin, so its functions are a list of their own
+TRAIN_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_train.h")
+_C_TRAIN, DECLARED_TRAIN_FUNCS = _parse_header(TRAIN_HEADER)
+C.update(_C_TRAIN)
+
+
+class PpoCfg(ctypes.Structure):
+    """go2sim_ppo_cfg_t"""
+    _fields_ = [(n, ctypes.c_double) for n in ("clip_param", "desired_kl", "entropy_coef", "learning_rate", "max_grad_norm", "value_loss_coef",
+                                               "beta1", "beta2", "eps", "lr_min", "lr_max")] + [("use_clipped_value_loss", ctypes.c_int), ("adaptive", ctypes.c_int)]
+
+
+class PpoBatch(ctypes.Structure):
+    """go2sim_ppo_batch_t: device pointers of the rollout's flat row arrays"""
+    FIELDS = ("obs", "critic_obs", "actions", "target_values", "returns", "advantages", "old_log_prob", "old_mu", "old_sigma")
+    _fields_ = [(n, ctypes.c_void_p) for n in FIELDS]
 
 
 class EnvGlobals(ctypes.Structure):
@@ -112,6 +128,10 @@ class Go2SimLib:
         for name in DECLARED_FUNCS:
             fn = getattr(self.lib, prefix + name[len("go2sim_"):])
             fn.restype = ctypes.c_int
+        if self.is_device:
+            for name in DECLARED_TRAIN_FUNCS:       # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
+                if hasattr(self.lib, name):
+                    getattr(self.lib, name).restype = ctypes.c_int
 
     def fn(self, name):
         return getattr(self.lib, self.prefix + name)

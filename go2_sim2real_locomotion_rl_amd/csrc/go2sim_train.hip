@@ -1,0 +1,656 @@
+// go2sim_train.hip -- the PPO update next to the policy step (include/go2sim_train.h).  gfx950 only.
+//
+// One mini-batch is a fixed sequence of launches on the caller's stream, no host synchronisation and no floating-point atomics anywhere:
+//   k_train_forward   the layer loop of the inference kernel (go2sim_mlp_dev.h), rows read through the permutation index; every hidden layer's
+//                     post-activation [rows][npad] goes to the workspace, the outputs to mu [rows][A] / v [rows].  Actor and critic share the launch.
+//   k_ppo_head        one lane per row: logp, ratio, kl, the two losses, d loss / d mu and d loss / d v (these are the last layers' dZ), per-workgroup
+//                     float64 partial sums of surrogate, value loss, kl and d loss / d sigma[A].  Per-row scalars are evaluated in float64 and rounded once.
+//   k_ppo_finalize    adds the partials in workgroup order, applies the learning-rate rule to the device-side learning rate, writes the std gradient
+//                     and the running sums of the reported means.
+//   per layer, last to first (both networks per launch):
+//     k_bwd_dw        dW = dZ^T A_prev per row chunk of GO2SIM_PPO_ROW_CHUNK rows: a workgroup owns 2 x 4 output tiles of 16 x 16, its four wavefronts
+//                     take a quarter of the chunk's rows each (8 independent accumulators per wavefront, chains of 128 rows), their results are added
+//                     in wavefront order through LDS and written to the chunk's slab of partials.
+//     k_bwd_db        db = column sums of dZ per chunk (float64: 16 row slices per column, added in slice order), into the same slab.
+//     k_bwd_da        dZ_prev = (dZ W) * ELU'(A_prev), 32 rows per workgroup, 4 accumulators per wavefront.  W is read strided ([npad][kpad], the
+//                     reduction runs over its rows): no transposed copy of the weights is kept, the optimizer writes one array per layer.
+//                     Not launched for the first layer.
+//   k_reduce_partials adds the chunk slabs in chunk order in float64 and rounds once: the padded gradient vector.
+// The optimizer is two launches: k_sumsq (per-workgroup float64 sums of squares, pairwise tree) and k_adam (every workgroup adds those in the same
+// order, then clip coefficient and Adam in one pass over the padded parameters, written into the arrays go2sim_policy_act reads and into std).
+// Adam's per-element arithmetic is float64 on fp32 state, rounded once per stored value.
+// Padding: padded rows of dZ^T and padded columns of A_prev are exact zeros, so padded gradient entries are sums of exact zeros, and Adam leaves a
+// zero parameter with zero gradient, m and v at zero.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "go2sim_mlp_dev.h"
+#include "../../include/go2sim_train.h"
+
+namespace {
+
+#define HIPCHK(x)                                                                                   \
+  do {                                                                                              \
+    hipError_t e_ = (x);                                                                            \
+    if (e_ != hipSuccess) { fprintf(stderr, "go2sim_train: %s failed: %s\n", #x, hipGetErrorString(e_)); return GO2SIM_E_HIP; } \
+  } while (0)
+
+constexpr int RCH = GO2SIM_PPO_ROW_CHUNK, WGT = 256, NORM_WG = 256;
+constexpr int DW_TN = 2, DW_TK = 4;                       // output tiles of a k_bwd_dw workgroup: 32 rows of dW (n) x 64 columns (k)
+enum { S_LR = 0, S_KL, S_SUM_VL, S_SUM_SUR, S_SUM_ENT, S_COUNT, S_NORM, S_N };
+
+struct ActWs { float* a[MAXL]; };                        // post-activations of the hidden layers, [rows][npad[l]]
+
+// a workgroup's sum of one float64 per lane in a fixed order (pairwise tree), valid on every lane
+__device__ __forceinline__ double wg_sum(double* s, double v) {
+  __syncthreads();
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int k = WGT / 2; k > 0; k >>= 1) {
+    if ((int)threadIdx.x < k) s[threadIdx.x] += s[threadIdx.x + k];
+    __syncthreads();
+  }
+  return s[0];
+}
+
+__global__ __launch_bounds__(64 * NWAVE) void k_train_forward(MlpDev M0, const float* __restrict__ x0, float* __restrict__ y0, ActWs w0,
+                                                              MlpDev M1, const float* __restrict__ x1, float* __restrict__ y1, ActWs w1,
+                                                              const int32_t* __restrict__ idx, int B) {
+  __shared__ alignas(16) float act[2][TM][LDW];
+  const MlpDev& M = blockIdx.y == 0 ? M0 : M1;
+  const ActWs& ws = blockIdx.y == 0 ? w0 : w1;
+  const float* __restrict__ x = blockIdx.y == 0 ? x0 : x1;
+  float* __restrict__ y = blockIdx.y == 0 ? y0 : y1;
+  const int row0 = blockIdx.x * TM;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  {
+    const int K0 = M.kpad[0], d0 = M.din[0];
+    for (int i = tid; i < TM * K0; i += 64 * NWAVE) {
+      int r = i / K0, k = i - r * K0, gr = row0 + r;
+      act[0][r][k] = (gr < B && k < d0) ? x[(size_t)idx[gr] * d0 + k] : 0.0f;
+    }
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int l = 0; l < M.n_layers; ++l) {
+    const int tiles_per_wave = (M.npad[l] / 16 + NWAVE - 1) / NWAVE;
+    if (tiles_per_wave >= 4) mlp_layer<4>(M, l, act[cur], act[cur ^ 1], y, row0, B, wave, lane);
+    else if (tiles_per_wave >= 2) mlp_layer<2>(M, l, act[cur], act[cur ^ 1], y, row0, B, wave, lane);
+    else mlp_layer<1>(M, l, act[cur], act[cur ^ 1], y, row0, B, wave, lane);
+    __syncthreads();
+    cur ^= 1;
+    if (l < M.n_layers - 1) {                              // the next layer only reads this buffer: no barrier needed after the copy
+      const int N = M.npad[l];
+      float* __restrict__ dst = ws.a[l];
+      for (int i = tid; i < TM * N; i += 64 * NWAVE) {
+        int r = i / N, n = i - r * N, gr = row0 + r;
+        if (gr < B) dst[(size_t)gr * N + n] = act[cur][r][n];
+      }
+    }
+  }
+}
+
+struct HeadArgs {
+  const float *mu, *val;                                  // [n][A], [n]: this mini-batch's forward
+  go2sim_ppo_batch_t b;
+  const float* std_;
+  const int32_t* idx;
+  float *dz_actor, *dz_critic;                            // [n][Apad], [n][16]
+  double* part;                                           // [workgroups][3 + A]
+  int n, A, Apad, use_clipped;
+  double clip, vl_coef;
+};
+
+__global__ __launch_bounds__(WGT) void k_ppo_head(HeadArgs h) {
+  __shared__ double s_red[WGT];
+  const int r = blockIdx.x * WGT + threadIdx.x, A = h.A;
+  const bool on = r < h.n;
+  double sur = 0.0, vl = 0.0, kl = 0.0, dlogp = 0.0;
+  size_t src = 0;
+  if (on) {
+    src = (size_t)h.idx[r];
+    const double w = 1.0 / (double)h.n;
+    double lp = 0.0;
+    for (int a = 0; a < A; ++a) {
+      const double x = h.b.actions[src * A + a], m = h.mu[(size_t)r * A + a], s = h.std_[a];
+      const double os = h.b.old_sigma[src * A + a], om = h.b.old_mu[src * A + a];
+      const double d = x - m, dm = om - m;
+      lp += -(d * d) / (2.0 * (s * s)) - log(s) - 0.91893853320467274178;
+      kl += log(s / os + 1e-5) + (os * os + dm * dm) / (2.0 * (s * s)) - 0.5;
+    }
+    const double adv = h.b.advantages[src];
+    const double ratio = exp(lp - (double)h.b.old_log_prob[src]);
+    const double lo = 1.0 - h.clip, hi = 1.0 + h.clip;
+    const bool inside = ratio >= lo && ratio <= hi;
+    const double rc = ratio < lo ? lo : (ratio > hi ? hi : ratio);
+    const double s1 = -adv * ratio, s2 = -adv * rc;
+    sur = s1 > s2 ? s1 : s2;
+    // torch's max(): the larger arm takes the gradient, equal arms share it; clamp passes it inside its range only
+    const double g_ratio = inside ? -adv : (s1 > s2 ? -adv : (s1 == s2 ? -0.5 * adv : 0.0));
+    dlogp = g_ratio * ratio * w;
+    const double v = h.val[r], tv = h.b.target_values[src], ret = h.b.returns[src];
+    double dv;
+    if (h.use_clipped) {
+      const double dvt = v - tv;
+      const bool vin = dvt >= -h.clip && dvt <= h.clip;
+      const double vc = tv + (dvt < -h.clip ? -h.clip : (dvt > h.clip ? h.clip : dvt));
+      const double e1 = (v - ret) * (v - ret), e2 = (vc - ret) * (vc - ret);
+      vl = e1 > e2 ? e1 : e2;
+      dv = vin ? 2.0 * (v - ret) : (e1 > e2 ? 2.0 * (v - ret) : (e1 == e2 ? (v - ret) : 0.0));
+    } else {
+      vl = (ret - v) * (ret - v);
+      dv = 2.0 * (v - ret);
+    }
+    dv = dv * h.vl_coef * w;
+    for (int a = 0; a < h.Apad; ++a) {
+      float g = 0.0f;
+      if (a < A) {
+        const double x = h.b.actions[src * A + a], m = h.mu[(size_t)r * A + a], s = h.std_[a];
+        g = (float)(dlogp * (x - m) / (s * s));
+      }
+      h.dz_actor[(size_t)r * h.Apad + a] = g;
+    }
+    for (int c = 0; c < 16; ++c) h.dz_critic[(size_t)r * 16 + c] = c == 0 ? (float)dv : 0.0f;
+  }
+  double* part = h.part + (size_t)blockIdx.x * (3 + A);
+  double t;
+  t = wg_sum(s_red, sur); if (threadIdx.x == 0) part[0] = t;
+  t = wg_sum(s_red, vl);  if (threadIdx.x == 0) part[1] = t;
+  t = wg_sum(s_red, kl);  if (threadIdx.x == 0) part[2] = t;
+  for (int a = 0; a < A; ++a) {                           // d logp / d sigma_a = (a - mu)^2 / sigma^3 - 1 / sigma
+    double g = 0.0;
+    if (on) {
+      const double x = h.b.actions[src * A + a], m = h.mu[(size_t)r * A + a], s = h.std_[a];
+      const double d = x - m;
+      g = dlogp * ((d * d) / (s * s * s) - 1.0 / s);
+    }
+    t = wg_sum(s_red, g); if (threadIdx.x == 0) part[3 + a] = t;
+  }
+}
+
+// one workgroup: column q of the head's partials is added in workgroup order by lane q (q = 0 surrogate, 1 value loss, 2 kl, 3 + a d sigma_a)
+__global__ __launch_bounds__(64) void k_ppo_finalize(const double* __restrict__ part, int n_wg, int n, int A, const float* __restrict__ std_, double* __restrict__ scal,
+                                                     float* __restrict__ grad_std, double entropy_coef, double desired_kl, double lr_min, double lr_max, int adaptive) {
+  __shared__ double s3[3];
+  for (int q = threadIdx.x; q < 3 + A; q += 64) {
+    double s = 0.0;
+    for (int w = 0; w < n_wg; ++w) s += part[(size_t)w * (3 + A) + q];
+    if (q < 3) s3[q] = s / (double)n;
+    else grad_std[q - 3] = (float)(s - entropy_coef / (double)std_[q - 3]);     // the entropy bonus: - entropy_coef * d/d sigma sum_a log sigma
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double ent = 0.0;
+    for (int a = 0; a < A; ++a) ent += 0.5 + 0.5 * 1.8378770664093454836 + log((double)std_[a]);
+    const double kl_mean = s3[2];
+    if (adaptive) {
+      double lr = scal[S_LR];
+      if (kl_mean > 2.0 * desired_kl) lr = fmax(lr_min, lr / 1.5);
+      else if (kl_mean < desired_kl / 2.0 && kl_mean > 0.0) lr = fmin(lr_max, lr * 1.5);
+      scal[S_LR] = lr;
+    }
+    scal[S_KL] = kl_mean;
+    scal[S_SUM_SUR] += s3[0]; scal[S_SUM_VL] += s3[1]; scal[S_SUM_ENT] += ent; scal[S_COUNT] += 1.0;
+  }
+}
+
+// one layer of one network as the backward kernels see it
+struct BwdLayer {
+  const float* dz;      // [rows][N]  d loss / d pre-activation of this layer
+  const float* aprev;   // [rows][lda] input of this layer: the previous layer's post-activation (lda = K), or the observations (lda = din, rows through idx)
+  const float* W;       // [N][K]
+  float* dzprev;        // [rows][K], written by k_bwd_da (hidden layers only)
+  int N, K, lda, kmax;  // kmax: columns of aprev that exist (din for the input layer, K otherwise)
+  int gather;           // aprev rows are read through idx
+  int active;           // this network has this layer
+  size_t w_off, b_off;  // offsets of dW / db in a slab of partials (= in the padded gradient vector)
+};
+
+__global__ __launch_bounds__(WGT) void k_bwd_dw(BwdLayer L0, BwdLayer L1, const int32_t* __restrict__ idx, int n_rows, float* __restrict__ partial, size_t slab) {
+  __shared__ float red[NWAVE][DW_TN * DW_TK * 4][64];
+  const BwdLayer& L = blockIdx.z == 0 ? L0 : L1;
+  if (!L.active) return;
+  const int ntn = L.N / 16, ntk = L.K / 16, gk_n = (ntk + DW_TK - 1) / DW_TK, gn_n = (ntn + DW_TN - 1) / DW_TN;
+  if ((int)blockIdx.x >= gk_n * gn_n) return;
+  const int gn = blockIdx.x / gk_n, gk = blockIdx.x - gn * gk_n, c = blockIdx.y;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 15, kq = lane >> 4;
+  int ncol[DW_TN], kcol[DW_TK];
+#pragma unroll
+  for (int t = 0; t < DW_TN; ++t) { int nt = gn * DW_TN + t; if (nt >= ntn) nt = ntn - 1; ncol[t] = nt * 16 + col; }
+#pragma unroll
+  for (int t = 0; t < DW_TK; ++t) { int kt = gk * DW_TK + t; if (kt >= ntk) kt = ntk - 1; kcol[t] = kt * 16 + col; }
+  f32x4 acc[DW_TN][DW_TK];
+#pragma unroll
+  for (int a = 0; a < DW_TN; ++a)
+#pragma unroll
+    for (int b = 0; b < DW_TK; ++b) acc[a][b] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  const int rbeg = c * RCH + wave * (RCH / NWAVE);
+  int rend = rbeg + RCH / NWAVE;
+  if (rend > n_rows) rend = n_rows;
+  const gcfp dz = (gcfp)L.dz;
+  const gcfp ap = (gcfp)L.aprev;
+  for (int r0 = rbeg; r0 < rend; r0 += 4) {                // reduction index of the matrix instruction: row r0 + (lane >> 4)
+    const int r = r0 + kq;
+    const bool ron = r < rend;
+    const size_t rs = ron ? (L.gather ? (size_t)idx[r] : (size_t)r) : 0;
+    float av[DW_TN], bv[DW_TK];
+#pragma unroll
+    for (int t = 0; t < DW_TN; ++t) av[t] = ron ? dz[(size_t)r * L.N + ncol[t]] : 0.0f;
+#pragma unroll
+    for (int t = 0; t < DW_TK; ++t) bv[t] = (ron && kcol[t] < L.kmax) ? ap[rs * L.lda + kcol[t]] : 0.0f;
+#pragma unroll
+    for (int a = 0; a < DW_TN; ++a)
+#pragma unroll
+      for (int b = 0; b < DW_TK; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a], bv[b], acc[a][b], 0, 0, 0);
+  }
+#pragma unroll
+  for (int a = 0; a < DW_TN; ++a)
+#pragma unroll
+    for (int b = 0; b < DW_TK; ++b)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) red[wave][(a * DW_TK + b) * 4 + i][lane] = acc[a][b][i];
+  __syncthreads();
+  float* __restrict__ out = partial + (size_t)c * slab + L.w_off;
+  for (int e = tid; e < DW_TN * DW_TK * 4 * 64; e += WGT) {
+    const int q = e >> 6, ln = e & 63, t = q >> 2, i = q & 3, a = t / DW_TK, b = t - a * DW_TK;
+    const int nt = gn * DW_TN + a, kt = gk * DW_TK + b;
+    if (nt >= ntn || kt >= ntk) continue;
+    const float s = ((red[0][q][ln] + red[1][q][ln]) + red[2][q][ln]) + red[3][q][ln];
+    const int nrow = nt * 16 + 4 * (ln >> 4) + i, kc = kt * 16 + (ln & 15);   // accumulator element i: row 4 * (lane >> 4) + i, column lane & 15
+    out[(size_t)nrow * L.K + kc] = s;
+  }
+}
+
+// db of one chunk: a workgroup owns 16 columns; lane (slice, column) adds the 32 rows of its slice in float64, the 16 slices are added in slice order
+__global__ __launch_bounds__(WGT) void k_bwd_db(BwdLayer L0, BwdLayer L1, int n_rows, float* __restrict__ partial, size_t slab) {
+  __shared__ double s_part[16][16];
+  const BwdLayer& L = blockIdx.z == 0 ? L0 : L1;
+  if (!L.active || (int)blockIdx.x * 16 >= L.N) return;
+  const int col = threadIdx.x & 15, slice = threadIdx.x >> 4, ncol = blockIdx.x * 16 + col, c = blockIdx.y;
+  constexpr int SL = RCH / 16;
+  const int rbeg = c * RCH + slice * SL;
+  int rend = rbeg + SL;
+  if (rend > n_rows) rend = n_rows;
+  double s = 0.0;
+  for (int r = rbeg; r < rend; ++r) s += (double)L.dz[(size_t)r * L.N + ncol];
+  s_part[slice][col] = s;
+  __syncthreads();
+  if (slice == 0) {
+    double t = 0.0;
+    for (int k = 0; k < 16; ++k) t += s_part[k][col];
+    partial[(size_t)c * slab + L.b_off + ncol] = (float)t;
+  }
+}
+
+// dZ_prev[r][k] = (sum_n dZ[r][n] W[n][k]) * ELU'(A_prev[r][k]); ELU' from the stored post-activation a: 1 for a > 0, a + 1 otherwise
+__global__ __launch_bounds__(64 * NWAVE) void k_bwd_da(BwdLayer L0, BwdLayer L1, int n_rows) {
+  constexpr int TG = 2;
+  const BwdLayer& L = blockIdx.y == 0 ? L0 : L1;
+  if (!L.active) return;
+  const int row0 = blockIdx.x * TM, N = L.N, K = L.K, ktiles = K / 16;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 15, kq = lane >> 4;
+  const gcfp W = (gcfp)L.W;
+  const gcfp dz = (gcfp)L.dz;
+  bool ron[RT];
+  size_t roff[RT];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) { const int r = row0 + 16 * rt + col; ron[rt] = r < n_rows; roff[rt] = ron[rt] ? (size_t)r * N + 4 * kq : 0; }
+  for (int g0 = wave * TG; g0 < ktiles; g0 += NWAVE * TG) {
+    f32x4 acc[RT][TG];
+    int kc[TG];
+#pragma unroll
+    for (int t = 0; t < TG; ++t) {
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) acc[rt][t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      const int kt = (g0 + t < ktiles) ? g0 + t : ktiles - 1;
+      kc[t] = kt * 16 + col;
+    }
+    for (int j = 0; j < N; j += 16) {                      // reduction index: n = j + 4 (lane >> 4) + s
+      f32x4 av[RT];
+      float wv[TG][4];
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) av[rt] = ron[rt] ? *(gcf4p)(dz + roff[rt] + j) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int t = 0; t < TG; ++t)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) wv[t][s] = W[(size_t)(j + 4 * kq + s) * K + kc[t]];
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int t = 0; t < TG; ++t)
+#pragma unroll
+          for (int rt = 0; rt < RT; ++rt) acc[rt][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt][s], wv[t][s], acc[rt][t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < TG; ++t) {
+      if (g0 + t >= ktiles) break;
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int r = row0 + 16 * rt + 4 * kq + i;
+          if (r < n_rows) {
+            const float a = L.aprev[(size_t)r * K + kc[t]];
+            L.dzprev[(size_t)r * K + kc[t]] = acc[rt][t][i] * (a > 0.0f ? 1.0f : a + 1.0f);
+          }
+        }
+    }
+  }
+}
+
+__global__ __launch_bounds__(WGT) void k_reduce_partials(const float* __restrict__ partial, int n_chunks, size_t slab, float* __restrict__ grads) {
+  const size_t i = (size_t)blockIdx.x * WGT + threadIdx.x;
+  if (i >= slab) return;
+  double s = 0.0;
+  for (int c = 0; c < n_chunks; ++c) s += (double)partial[(size_t)c * slab + i];
+  grads[i] = (float)s;
+}
+
+__global__ __launch_bounds__(WGT) void k_sumsq(const float* __restrict__ g, size_t n, double* __restrict__ part) {
+  __shared__ double s_red[WGT];
+  double s = 0.0;
+  for (size_t i = (size_t)blockIdx.x * WGT + threadIdx.x; i < n; i += (size_t)NORM_WG * WGT) s += (double)g[i] * (double)g[i];
+  const double t = wg_sum(s_red, s);
+  if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+struct AdamArgs {
+  float *p_actor, *p_critic, *p_std, *g, *m, *v;
+  size_t nA, nC, n_tot;                                   // padded sizes; the std block follows the two networks
+  int A;
+  const double* sq_part;
+  double* scal;
+  double max_norm, b1, b2, eps, bc1, bc2_sqrt;            // bc1 = 1 - b1^t, bc2_sqrt = sqrt(1 - b2^t), from the step count in float64 on the host
+};
+
+__global__ __launch_bounds__(WGT) void k_adam(AdamArgs a) {
+  __shared__ double s_coef;
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int i = 0; i < NORM_WG; ++i) s += a.sq_part[i];   // every workgroup adds in the same order: the same bits everywhere
+    const double norm = sqrt(s);
+    double coef = a.max_norm / (norm + 1e-6);
+    if (coef > 1.0) coef = 1.0;
+    s_coef = coef;
+    if (blockIdx.x == 0) a.scal[S_NORM] = norm;
+  }
+  __syncthreads();
+  const size_t i = (size_t)blockIdx.x * WGT + threadIdx.x;
+  if (i >= a.n_tot) return;
+  float* p;
+  if (i < a.nA) p = a.p_actor + i;
+  else if (i < a.nA + a.nC) p = a.p_critic + (i - a.nA);
+  else { const size_t k = i - a.nA - a.nC; if (k >= (size_t)a.A) return; p = a.p_std + k; }
+  const double g = (double)a.g[i] * s_coef;
+  const double m = a.b1 * (double)a.m[i] + (1.0 - a.b1) * g;
+  const double v = a.b2 * (double)a.v[i] + (1.0 - a.b2) * (g * g);
+  a.g[i] = (float)g; a.m[i] = (float)m; a.v[i] = (float)v;
+  const double step_size = a.scal[S_LR] / a.bc1;
+  *p = (float)((double)*p - step_size * (m / (sqrt(v) / a.bc2_sqrt + a.eps)));
+}
+
+// flat [rows][cols] <-> padded [rows][ld]
+__global__ __launch_bounds__(WGT) void k_pack(int to_padded, float* __restrict__ padded, int ld, float* __restrict__ flat, int rows, int cols) {
+  const int i = blockIdx.x * WGT + threadIdx.x;
+  if (i >= rows * cols) return;
+  const int r = i / cols, c = i - r * cols;
+  if (to_padded) padded[(size_t)r * ld + c] = flat[i];
+  else flat[i] = padded[(size_t)r * ld + c];
+}
+__global__ void k_set_lr(double* scal, double lr) { if (blockIdx.x == 0 && threadIdx.x == 0) scal[S_LR] = lr; }
+__global__ void k_reset_stats(double* scal) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) { scal[S_SUM_VL] = 0.0; scal[S_SUM_SUR] = 0.0; scal[S_SUM_ENT] = 0.0; scal[S_COUNT] = 0.0; }
+}
+__global__ void k_stats(const double* __restrict__ scal, double step, double* __restrict__ out) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const double c = scal[S_COUNT] > 0.0 ? scal[S_COUNT] : 1.0;
+  out[GO2SIM_PPO_ST_VALUE_LOSS] = scal[S_SUM_VL] / c; out[GO2SIM_PPO_ST_SURROGATE] = scal[S_SUM_SUR] / c; out[GO2SIM_PPO_ST_ENTROPY] = scal[S_SUM_ENT] / c;
+  out[GO2SIM_PPO_ST_KL] = scal[S_KL]; out[GO2SIM_PPO_ST_LR] = scal[S_LR]; out[GO2SIM_PPO_ST_GRAD_NORM] = scal[S_NORM];
+  out[GO2SIM_PPO_ST_STEP] = step; out[GO2SIM_PPO_ST_COUNT] = scal[S_COUNT];
+}
+
+struct Seg { int base; size_t pad_off; int ld, rows, cols; size_t flat_off; };   // base 0 actor, 1 critic, 2 std
+
+}  // namespace
+
+struct go2sim_ppo {
+  go2sim_mlp *actor = nullptr, *critic = nullptr;
+  go2sim_ppo_cfg_t cfg{};
+  int A = 0, Apad = 0, max_rows = 0, max_chunks = 0, max_head_wg = 0;
+  size_t nA = 0, nC = 0, n_tot = 0, n_flat = 0;
+  float* fbuf = nullptr;      // one allocation: grads | m | v | mu | val | activations | dz ping-pong | partial slabs
+  float *grads = nullptr, *m = nullptr, *v = nullptr, *mu = nullptr, *val = nullptr, *partial = nullptr;
+  ActWs ws[2]{};
+  float* dz[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+  double* dbuf = nullptr;     // scal[S_N] | sq_part[NORM_WG] | head partials
+  double *scal = nullptr, *sq_part = nullptr, *head_part = nullptr;
+  long long step = 0;
+  std::vector<Seg> segs;
+};
+
+namespace {
+BwdLayer bwd_layer(const go2sim_ppo* h, int net, int lb, const go2sim_ppo_batch_t* batch) {
+  const go2sim_mlp* M = net == 0 ? h->actor : h->critic;
+  BwdLayer L{};
+  const int l = M->n_layers - 1 - lb;                      // lb counts from the last layer
+  if (l < 0) return L;
+  L.active = 1;
+  L.N = M->dev.npad[l]; L.K = M->dev.kpad[l];
+  L.dz = h->dz[net][l & 1];
+  L.W = M->dev.W[l];
+  if (l == 0) {
+    L.aprev = net == 0 ? batch->obs : batch->critic_obs; L.lda = M->dims[0]; L.kmax = M->dims[0]; L.gather = 1; L.dzprev = nullptr;
+  } else {
+    L.aprev = h->ws[net].a[l - 1]; L.lda = L.K; L.kmax = L.K; L.gather = 0; L.dzprev = h->dz[net][(l - 1) & 1];
+  }
+  L.w_off = (size_t)(M->dev.W[l] - M->dparams) + (net == 0 ? 0 : h->nA);
+  L.b_off = (size_t)(M->dev.b[l] - M->dparams) + (net == 0 ? 0 : h->nA);
+  return L;
+}
+float* vec_of(go2sim_ppo* h, int which) {
+  return which == GO2SIM_PPO_GRADS ? h->grads : which == GO2SIM_PPO_ADAM_M ? h->m : which == GO2SIM_PPO_ADAM_V ? h->v : nullptr;
+}
+int pack_all(go2sim_ppo* h, int which, int to_padded, float* flat, float* std_dev, hipStream_t st) {
+  if (!h || !flat || which < GO2SIM_PPO_PARAMS || which > GO2SIM_PPO_ADAM_V) return GO2SIM_E_BADARG;
+  if (which == GO2SIM_PPO_PARAMS && !std_dev) return GO2SIM_E_BADARG;
+  float* base[3];
+  if (which == GO2SIM_PPO_PARAMS) { base[0] = h->actor->dparams; base[1] = h->critic->dparams; base[2] = std_dev; }
+  else { float* v = vec_of(h, which); base[0] = v; base[1] = v + h->nA; base[2] = v + h->nA + h->nC; }
+  for (const Seg& s : h->segs)
+    hipLaunchKernelGGL(k_pack, dim3((s.rows * s.cols + WGT - 1) / WGT), dim3(WGT), 0, st, to_padded, base[s.base] + s.pad_off, s.ld, flat + s.flat_off, s.rows, s.cols);
+  HIPCHK(hipGetLastError());
+  return GO2SIM_E_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int go2sim_ppo_create(go2sim_mlp_t* actor, go2sim_mlp_t* critic, int n_actions, const go2sim_ppo_cfg_t* cfg, int max_rows, go2sim_ppo_t** out) {
+  if (!actor || !critic || !cfg || !out || max_rows < 1 || n_actions < 1) return GO2SIM_E_BADARG;
+  if (actor->dims[actor->n_layers] != n_actions || critic->dims[critic->n_layers] != 1 || actor->device != critic->device) return GO2SIM_E_BADARG;
+  if (!(cfg->learning_rate > 0.0) || !(cfg->clip_param >= 0.0)) return GO2SIM_E_BADARG;
+  HIPCHK(hipSetDevice(actor->device));
+  go2sim_ppo* h = new (std::nothrow) go2sim_ppo();
+  if (!h) return GO2SIM_E_NOMEM;
+  h->actor = actor; h->critic = critic; h->cfg = *cfg; h->A = n_actions; h->Apad = round16(n_actions); h->max_rows = max_rows;
+  h->max_chunks = (max_rows + RCH - 1) / RCH; h->max_head_wg = (max_rows + WGT - 1) / WGT;
+  h->nA = actor->padded; h->nC = critic->padded; h->n_tot = h->nA + h->nC + h->Apad;
+  // flat (state-dict) order: actor W0, b0, ..., critic W0, b0, ..., std
+  size_t flat = 0;
+  for (int net = 0; net < 2; ++net) {
+    const go2sim_mlp* M = net == 0 ? actor : critic;
+    for (int l = 0; l < M->n_layers; ++l) {
+      h->segs.push_back(Seg{net, (size_t)(M->dev.W[l] - M->dparams), M->dev.kpad[l], M->dims[l + 1], M->dims[l], flat}); flat += (size_t)M->dims[l] * M->dims[l + 1];
+      h->segs.push_back(Seg{net, (size_t)(M->dev.b[l] - M->dparams), M->dims[l + 1], 1, M->dims[l + 1], flat}); flat += M->dims[l + 1];
+    }
+  }
+  h->segs.push_back(Seg{2, 0, n_actions, 1, n_actions, flat}); flat += n_actions;
+  h->n_flat = flat;
+  // float workspace
+  const size_t R = (size_t)max_rows;
+  auto al16 = [](size_t n) { return (n + 15) / 16 * 16; };   // every region starts 64-byte aligned (float4 loads)
+  size_t need = 3 * h->n_tot + al16(R * n_actions) + al16(R);
+  size_t act_sz[2] = {0, 0}, dz_sz[2] = {0, 0};
+  for (int net = 0; net < 2; ++net) {
+    const go2sim_mlp* M = net == 0 ? actor : critic;
+    int wmax = 16;
+    for (int l = 0; l < M->n_layers; ++l) { if (l < M->n_layers - 1) act_sz[net] += R * M->dev.npad[l]; if (M->dev.npad[l] > wmax) wmax = M->dev.npad[l]; }
+    dz_sz[net] = R * wmax;
+    need += act_sz[net] + 2 * dz_sz[net];
+  }
+  const size_t slab = h->nA + h->nC;
+  need += (size_t)h->max_chunks * slab;
+  const size_t nd = S_N + NORM_WG + (size_t)h->max_head_wg * (3 + n_actions);
+  if (hipMalloc((void**)&h->fbuf, need * sizeof(float)) != hipSuccess || hipMalloc((void**)&h->dbuf, nd * sizeof(double)) != hipSuccess) {
+    go2sim_ppo_destroy(h);
+    return GO2SIM_E_NOMEM;
+  }
+  if (hipMemset(h->fbuf, 0, need * sizeof(float)) != hipSuccess || hipMemset(h->dbuf, 0, nd * sizeof(double)) != hipSuccess ||
+      hipMemcpy(h->dbuf + S_LR, &cfg->learning_rate, sizeof(double), hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    fprintf(stderr, "go2sim_train: initialising the workspaces failed: %s\n", hipGetErrorString(hipGetLastError()));
+    go2sim_ppo_destroy(h);
+    return GO2SIM_E_HIP;
+  }
+  float* p = h->fbuf;
+  h->grads = p; p += h->n_tot; h->m = p; p += h->n_tot; h->v = p; p += h->n_tot;
+  h->mu = p; p += al16(R * n_actions); h->val = p; p += al16(R);
+  for (int net = 0; net < 2; ++net) {
+    const go2sim_mlp* M = net == 0 ? actor : critic;
+    for (int l = 0; l < M->n_layers - 1; ++l) { h->ws[net].a[l] = p; p += R * M->dev.npad[l]; }
+    h->dz[net][0] = p; p += dz_sz[net]; h->dz[net][1] = p; p += dz_sz[net];
+  }
+  h->partial = p;
+  h->scal = h->dbuf; h->sq_part = h->dbuf + S_N; h->head_part = h->sq_part + NORM_WG;
+  *out = h;
+  return GO2SIM_E_OK;
+}
+
+int go2sim_ppo_destroy(go2sim_ppo_t* h) {
+  if (!h) return GO2SIM_E_BADARG;
+  if (h->fbuf) (void)hipFree(h->fbuf);
+  if (h->dbuf) (void)hipFree(h->dbuf);
+  delete h;
+  return GO2SIM_E_OK;
+}
+
+int go2sim_ppo_minibatch_grad(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const float* std_dev, const int32_t* idx, int n, void* stream) {
+  if (!h || !b || !std_dev || !idx || n < 1 || n > h->max_rows) return GO2SIM_E_BADARG;
+  if (!b->obs || !b->critic_obs || !b->actions || !b->target_values || !b->returns || !b->advantages || !b->old_log_prob || !b->old_mu || !b->old_sigma)
+    return GO2SIM_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  const go2sim_mlp *Ma = h->actor, *Mc = h->critic;
+  hipLaunchKernelGGL(k_train_forward, dim3((n + TM - 1) / TM, 2), dim3(64 * NWAVE), 0, st, Ma->dev, b->obs, h->mu, h->ws[0], Mc->dev, b->critic_obs, h->val, h->ws[1], idx, n);
+  const int n_wg = (n + WGT - 1) / WGT;
+  HeadArgs ha{};
+  ha.mu = h->mu; ha.val = h->val; ha.b = *b; ha.std_ = std_dev; ha.idx = idx;
+  ha.dz_actor = h->dz[0][(Ma->n_layers - 1) & 1]; ha.dz_critic = h->dz[1][(Mc->n_layers - 1) & 1];
+  ha.part = h->head_part; ha.n = n; ha.A = h->A; ha.Apad = h->Apad; ha.use_clipped = h->cfg.use_clipped_value_loss;
+  ha.clip = h->cfg.clip_param; ha.vl_coef = h->cfg.value_loss_coef;
+  hipLaunchKernelGGL(k_ppo_head, dim3(n_wg), dim3(WGT), 0, st, ha);
+  hipLaunchKernelGGL(k_ppo_finalize, dim3(1), dim3(64), 0, st, h->head_part, n_wg, n, h->A, std_dev, h->scal, h->grads + h->nA + h->nC, h->cfg.entropy_coef,
+                     h->cfg.desired_kl, h->cfg.lr_min, h->cfg.lr_max, h->cfg.adaptive);
+  const int n_chunks = (n + RCH - 1) / RCH;
+  const size_t slab = h->nA + h->nC;
+  const int depth = Ma->n_layers > Mc->n_layers ? Ma->n_layers : Mc->n_layers;
+  for (int lb = 0; lb < depth; ++lb) {
+    const BwdLayer L0 = bwd_layer(h, 0, lb, b), L1 = bwd_layer(h, 1, lb, b);
+    int groups = 1, nmax = 16, any_da = 0;
+    for (const BwdLayer* L : {&L0, &L1}) {
+      if (!L->active) continue;
+      const int g = ((L->N / 16 + DW_TN - 1) / DW_TN) * ((L->K / 16 + DW_TK - 1) / DW_TK);
+      if (g > groups) groups = g;
+      if (L->N > nmax) nmax = L->N;
+      if (L->dzprev) any_da = 1;
+    }
+    hipLaunchKernelGGL(k_bwd_dw, dim3(groups, n_chunks, 2), dim3(WGT), 0, st, L0, L1, idx, n, h->partial, slab);
+    hipLaunchKernelGGL(k_bwd_db, dim3(nmax / 16, n_chunks, 2), dim3(WGT), 0, st, L0, L1, n, h->partial, slab);
+    if (any_da) {
+      BwdLayer D0 = L0, D1 = L1;                           // a network at its first layer has no dA to compute
+      if (!D0.dzprev) D0.active = 0;
+      if (!D1.dzprev) D1.active = 0;
+      hipLaunchKernelGGL(k_bwd_da, dim3((n + TM - 1) / TM, 2), dim3(64 * NWAVE), 0, st, D0, D1, n);
+    }
+  }
+  hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((slab + WGT - 1) / WGT)), dim3(WGT), 0, st, h->partial, n_chunks, slab, h->grads);
+  HIPCHK(hipGetLastError());
+  return GO2SIM_E_OK;
+}
+
+int go2sim_ppo_apply(go2sim_ppo_t* h, float* std_dev, void* stream) {
+  if (!h || !std_dev) return GO2SIM_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  const double t = (double)(h->step + 1);                  // the handle's count moves once the launches are accepted
+  AdamArgs a{};
+  a.p_actor = h->actor->dparams; a.p_critic = h->critic->dparams; a.p_std = std_dev; a.g = h->grads; a.m = h->m; a.v = h->v;
+  a.nA = h->nA; a.nC = h->nC; a.n_tot = h->n_tot; a.A = h->A; a.sq_part = h->sq_part; a.scal = h->scal;
+  a.max_norm = h->cfg.max_grad_norm; a.b1 = h->cfg.beta1; a.b2 = h->cfg.beta2; a.eps = h->cfg.eps;
+  a.bc1 = 1.0 - std::pow(h->cfg.beta1, t); a.bc2_sqrt = std::sqrt(1.0 - std::pow(h->cfg.beta2, t));
+  hipLaunchKernelGGL(k_sumsq, dim3(NORM_WG), dim3(WGT), 0, st, h->grads, h->n_tot, h->sq_part);
+  hipLaunchKernelGGL(k_adam, dim3((unsigned)((h->n_tot + WGT - 1) / WGT)), dim3(WGT), 0, st, a);
+  HIPCHK(hipGetLastError());
+  h->step += 1;
+  return GO2SIM_E_OK;
+}
+
+int go2sim_ppo_update(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, float* std_dev, const int32_t* perm, int n_rows_total, int n_epochs, int n_mini_batches, void* stream) {
+  if (!h || !b || !std_dev || !perm || n_epochs < 1 || n_mini_batches < 1 || n_rows_total < n_mini_batches) return GO2SIM_E_BADARG;
+  const int mbs = n_rows_total / n_mini_batches;
+  if (mbs > h->max_rows) return GO2SIM_E_BADARG;
+  int rc = go2sim_ppo_reset_stats(h, stream);
+  for (int e = 0; e < n_epochs && rc == GO2SIM_E_OK; ++e)
+    for (int i = 0; i < n_mini_batches && rc == GO2SIM_E_OK; ++i) {
+      rc = go2sim_ppo_minibatch_grad(h, b, std_dev, perm + (size_t)i * mbs, mbs, stream);
+      if (rc == GO2SIM_E_OK) rc = go2sim_ppo_apply(h, std_dev, stream);
+    }
+  return rc;
+}
+
+int go2sim_ppo_n_params(go2sim_ppo_t* h, size_t* out) {
+  if (!h || !out) return GO2SIM_E_BADARG;
+  *out = h->n_flat;
+  return GO2SIM_E_OK;
+}
+int go2sim_ppo_export(go2sim_ppo_t* h, int which, float* flat_dev, const float* std_dev, void* stream) {
+  return pack_all(h, which, 0, flat_dev, const_cast<float*>(std_dev), (hipStream_t)stream);
+}
+int go2sim_ppo_import(go2sim_ppo_t* h, int which, const float* flat_dev, float* std_dev, void* stream) {
+  return pack_all(h, which, 1, const_cast<float*>(flat_dev), std_dev, (hipStream_t)stream);
+}
+int go2sim_ppo_n_padded(go2sim_ppo_t* h, size_t* out) {
+  if (!h || !out) return GO2SIM_E_BADARG;
+  *out = h->n_tot;
+  return GO2SIM_E_OK;
+}
+int go2sim_ppo_export_padded(go2sim_ppo_t* h, int which, float* padded_dev, void* stream) {
+  if (!h || !padded_dev || !vec_of(h, which)) return GO2SIM_E_BADARG;
+  HIPCHK(hipMemcpyAsync(padded_dev, vec_of(h, which), h->n_tot * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return GO2SIM_E_OK;
+}
+
+int go2sim_ppo_set_step(go2sim_ppo_t* h, long long step, double learning_rate, void* stream) {
+  if (!h || step < 0 || !(learning_rate > 0.0)) return GO2SIM_E_BADARG;
+  h->step = step;
+  hipLaunchKernelGGL(k_set_lr, dim3(1), dim3(1), 0, (hipStream_t)stream, h->scal, learning_rate);
+  HIPCHK(hipGetLastError());
+  return GO2SIM_E_OK;
+}
+int go2sim_ppo_reset_stats(go2sim_ppo_t* h, void* stream) {
+  if (!h) return GO2SIM_E_BADARG;
+  hipLaunchKernelGGL(k_reset_stats, dim3(1), dim3(1), 0, (hipStream_t)stream, h->scal);
+  HIPCHK(hipGetLastError());
+  return GO2SIM_E_OK;
+}
+int go2sim_ppo_stats(go2sim_ppo_t* h, double* out_dev, void* stream) {
+  if (!h || !out_dev) return GO2SIM_E_BADARG;
+  hipLaunchKernelGGL(k_stats, dim3(1), dim3(1), 0, (hipStream_t)stream, h->scal, (double)h->step, out_dev);
+  HIPCHK(hipGetLastError());
+  return GO2SIM_E_OK;
+}
+
+}  // extern "C"

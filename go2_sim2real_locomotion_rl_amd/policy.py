@@ -2,8 +2,9 @@
 ``examples/locomotion/final/go2_train_walk.py:12-15`` pins) on top of the policy entry points of the C ABI
 (include/go2sim_policy.h).  It covers the inference side that ``OnPolicyRunner`` / ``PPO.act`` call once per
 environment step -- ``act``, ``evaluate``, ``get_actions_log_prob``, ``act_inference``, ``action_mean``,
-``action_std`` -- with the reference's argument meaning; the PPO update itself (autograd) stays with the caller,
-who pushes new parameters with :meth:`load_state_dict`.
+``action_std`` -- with the reference's argument meaning.  The PPO update runs either in the library (ppo.PPO, include/go2sim_train.h: the
+optimizer writes the arrays ``act`` reads, :meth:`state_dict` exports them from the device) or with the caller in torch, who pushes new
+parameters with :meth:`load_state_dict`.
 
     policy = ActorCritic(49, 104, 16, actor_hidden_dims=[512, 256, 128], critic_hidden_dims=[512, 256, 128], activation="elu")
     policy.load_state_dict(torch.load("model_1000.pt", weights_only=True)["model_state_dict"])
@@ -107,7 +108,7 @@ class ActorCritic:
                 sd[f"{prefix}.{2 * l}.weight"] = (torch.rand(dims[l + 1], dims[l], generator=g) * 2 - 1) * bound
                 sd[f"{prefix}.{2 * l}.bias"] = (torch.rand(dims[l + 1], generator=g) * 2 - 1) * bound
         sd["std"] = init_noise_std * torch.ones(num_actions)
-        self._actor = self._critic = None
+        self._actor = self._critic = self._trainer = None
         self.std = torch.ones(num_actions, device=self.device)
         self.load_state_dict(sd)
         self._seed, self._step = int(seed), 0
@@ -124,12 +125,25 @@ class ActorCritic:
             self._actor, self._critic = Mlp(self._L, da, pa, dev), Mlp(self._L, dc, pc, dev)
         else:
             self._actor.set_params(pa); self._critic.set_params(pc)
-        self.std = state_dict["std"].detach().to(device=self.device, dtype=torch.float32).contiguous().clone()
+        self.std.copy_(state_dict["std"].detach().reshape(self.num_actions))     # in place: std stays the device tensor the update kernels write
         self._state = {k: (v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in state_dict.items()}
         return True
 
     def state_dict(self):
-        return dict(self._state)
+        """The parameters as they are on the device: once a trainer is attached the optimizer has written them there, and the host copy of the last
+        load_state_dict is stale."""
+        if self._trainer is None:
+            return dict(self._state)
+        from .ppo import unflatten
+
+        return unflatten(self._trainer.export("PARAMS", self.std).cpu(), self._adims, self._cdims)
+
+    def attach_trainer(self, max_rows_per_minibatch, **hyper):
+        """The go2sim_ppo handle (ppo.PpoHandle) that updates this policy's device parameters in place; the optimizer state lives in it."""
+        from .ppo import PpoHandle
+
+        self._trainer = PpoHandle(self._L, self._actor, self._critic, self.num_actions, max_rows_per_minibatch, device=self.device, **hyper)
+        return self._trainer
 
     def load_checkpoint(self, path, strict=False):
         """Load ``model_<it>.pt`` of a training run (rsl_rl 2.2.4 ``OnPolicyRunner.save`` layout), read with ``torch.load(weights_only=True)``.

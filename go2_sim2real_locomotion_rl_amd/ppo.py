@@ -1,0 +1,210 @@
+"""PPO -- host-side mirror of ``rsl_rl.algorithms.PPO`` (rsl-rl-lib==2.2.4) on top of the update entry points of the C ABI
+(include/go2sim_train.h): the fused MLP backward, the clipped losses, the adaptive learning rate, the gradient clip and Adam run as HIP
+kernels on the arrays ``ActorCritic.act`` reads; nothing of an update goes through the host.
+
+    policy = ActorCritic(49, 104, 16)
+    alg = PPO(policy, num_learning_epochs=5, num_mini_batches=4, schedule="adaptive", entropy_coef=0.003, gamma=0.99)
+    alg.init_storage(env.num_envs, 24, [49], [104], [16])
+    for t in range(24):
+        actions = alg.act(obs, critic_obs)
+        obs, rew, dones, infos = env.step(actions)
+        critic_obs = infos["observations"]["critic"]
+        alg.process_env_step(rew, dones, infos)
+    alg.compute_returns(critic_obs)
+    value_loss, surrogate_loss, entropy = alg.update()      # one host synchronisation, after the last mini-batch
+"""
+import ctypes
+
+import torch
+
+from .capi import C, Go2SimError, PpoBatch, PpoCfg, load_hip_lib
+from .rollout import RolloutStorage
+
+VECS = ("PARAMS", "GRADS", "ADAM_M", "ADAM_V")
+
+
+def _p(t):
+    return ctypes.c_void_p(0) if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def make_batch(**tensors):
+    """go2sim_ppo_batch_t of contiguous float32 device tensors (kept alive by the caller)."""
+    b = PpoBatch()
+    for name in PpoBatch.FIELDS:
+        t = tensors[name]
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise Go2SimError(f"{name} must be a contiguous float32 tensor")
+        setattr(b, name, t.data_ptr())
+    return b
+
+
+class PpoHandle:
+    """One go2sim_ppo handle: pointers only.  `actor` / `critic` are policy.Mlp objects of the product library."""
+
+    def __init__(self, lib, actor, critic, n_actions, max_rows, *, clip_param=0.2, desired_kl=0.01, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0,
+                 value_loss_coef=1.0, use_clipped_value_loss=True, adaptive=False, betas=(0.9, 0.999), eps=1e-8, lr_min=1e-5, lr_max=1e-2, device=None):
+        self.L, self.actor, self.critic = lib, actor, critic
+        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        cfg = PpoCfg(clip_param, desired_kl, entropy_coef, learning_rate, max_grad_norm, value_loss_coef, betas[0], betas[1], eps, lr_min, lr_max,
+                     int(bool(use_clipped_value_loss)), int(bool(adaptive)))
+        h = ctypes.c_void_p()
+        self.h = None
+        lib.check(lib.fn("ppo_create")(actor.h, critic.h, ctypes.c_int(n_actions), ctypes.byref(cfg), ctypes.c_int(max_rows), ctypes.byref(h)), "ppo_create")
+        self.h = h
+        n = ctypes.c_size_t()
+        lib.check(lib.fn("ppo_n_params")(self.h, ctypes.byref(n)), "ppo_n_params")
+        self.n_params = n.value
+        lib.check(lib.fn("ppo_n_padded")(self.h, ctypes.byref(n)), "ppo_n_padded")
+        self.n_padded = n.value
+        self._stats = torch.zeros(C["GO2SIM_PPO_N_STATS"], dtype=torch.float64, device=self.device)
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def minibatch_grad(self, batch, std, idx, n_rows=None):
+        n = idx.numel() if n_rows is None else n_rows
+        self.L.check(self.L.fn("ppo_minibatch_grad")(self.h, ctypes.byref(batch), _p(std), _p(idx), ctypes.c_int(n), self._stream()), "ppo_minibatch_grad")
+
+    def apply(self, std):
+        self.L.check(self.L.fn("ppo_apply")(self.h, _p(std), self._stream()), "ppo_apply")
+
+    def update(self, batch, std, perm, n_rows_total, n_epochs, n_mini_batches):
+        self.L.check(self.L.fn("ppo_update")(self.h, ctypes.byref(batch), _p(std), _p(perm), ctypes.c_int(n_rows_total), ctypes.c_int(n_epochs),
+                                             ctypes.c_int(n_mini_batches), self._stream()), "ppo_update")
+
+    def export(self, which, std=None):
+        """flat float32 device vector in state-dict order: actor W0, b0, ..., critic W0, b0, ..., std"""
+        out = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
+        self.L.check(self.L.fn("ppo_export")(self.h, ctypes.c_int(C["GO2SIM_PPO_" + which]), _p(out), _p(std), self._stream()), "ppo_export")
+        return out
+
+    def import_(self, which, flat, std=None):
+        flat = flat.to(device=self.device, dtype=torch.float32).contiguous()
+        if flat.numel() != self.n_params:
+            raise Go2SimError(f"flat vector has {flat.numel()} entries, expected {self.n_params}")
+        self.L.check(self.L.fn("ppo_import")(self.h, ctypes.c_int(C["GO2SIM_PPO_" + which]), _p(flat), _p(std), self._stream()), "ppo_import")
+        torch.cuda.current_stream(self.device).synchronize()          # `flat` may be a temporary
+
+    def export_padded(self, which):
+        out = torch.empty(self.n_padded, dtype=torch.float32, device=self.device)
+        self.L.check(self.L.fn("ppo_export_padded")(self.h, ctypes.c_int(C["GO2SIM_PPO_" + which]), _p(out), self._stream()), "ppo_export_padded")
+        return out
+
+    def set_step(self, step, learning_rate):
+        self.L.check(self.L.fn("ppo_set_step")(self.h, ctypes.c_longlong(int(step)), ctypes.c_double(float(learning_rate)), self._stream()), "ppo_set_step")
+
+    def reset_stats(self):
+        self.L.check(self.L.fn("ppo_reset_stats")(self.h, self._stream()), "ppo_reset_stats")
+
+    def stats(self):
+        """float64 device tensor [value loss, surrogate loss, entropy, kl_mean, learning rate, grad norm, step, mini-batches]; no synchronisation"""
+        self.L.check(self.L.fn("ppo_stats")(self.h, _p(self._stats), self._stream()), "ppo_stats")
+        return self._stats
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.fn("ppo_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def state_dict_keys(adims, cdims):
+    """[(key, shape)] in the flat order of go2sim_ppo_export"""
+    keys = []
+    for prefix, dims in (("actor", adims), ("critic", cdims)):
+        for l in range(len(dims) - 1):
+            keys += [(f"{prefix}.{2 * l}.weight", (dims[l + 1], dims[l])), (f"{prefix}.{2 * l}.bias", (dims[l + 1],))]
+    keys.append(("std", (adims[-1],)))
+    return keys
+
+
+def unflatten(flat, adims, cdims):
+    out, o = {}, 0
+    for k, shape in state_dict_keys(adims, cdims):
+        n = 1
+        for s in shape:
+            n *= s
+        out[k] = flat[o:o + n].reshape(shape).clone()
+        o += n
+    return out
+
+
+def flatten(sd, adims, cdims):
+    return torch.cat([sd[k].detach().reshape(-1).to(torch.float32).cpu() for k, _ in state_dict_keys(adims, cdims)])
+
+
+class PPO:
+    def __init__(self, policy, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95, value_loss_coef=1.0, entropy_coef=0.0,
+                 learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device=None, *, seed=1, **kwargs):
+        if schedule not in ("adaptive", "fixed"):
+            raise Go2SimError(f"schedule must be 'adaptive' or 'fixed', got {schedule!r}")
+        unknown = {k: v for k, v in kwargs.items() if k not in ("class_name", "normalize_advantage_per_mini_batch") and v is not None}
+        if unknown or kwargs.get("normalize_advantage_per_mini_batch"):
+            raise Go2SimError(f"go2sim's PPO does not implement {sorted(unknown) or ['normalize_advantage_per_mini_batch']} (RND, symmetry and multi-GPU are out of scope)")
+        self.policy = self.actor_critic = policy
+        self.device = policy.device if device is None else torch.device(device)
+        self.num_learning_epochs, self.num_mini_batches = int(num_learning_epochs), int(num_mini_batches)
+        self.gamma, self.lam = gamma, lam
+        self._hyper = dict(clip_param=clip_param, desired_kl=desired_kl, entropy_coef=entropy_coef, learning_rate=learning_rate, max_grad_norm=max_grad_norm,
+                           value_loss_coef=value_loss_coef, use_clipped_value_loss=use_clipped_value_loss, adaptive=schedule == "adaptive")
+        self.schedule, self.desired_kl = schedule, desired_kl
+        self.learning_rate = float(learning_rate)
+        self._gen = torch.Generator(device=self.device).manual_seed(int(seed))
+        self.storage = self._h = None
+        self.last_stats = None
+
+    def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
+        T, B, dev = int(num_transitions_per_env), int(num_envs), self.device
+        self.T, self.B, self.t = T, B, 0
+        self.storage = RolloutStorage(T, B, dev)
+        z = lambda *s: torch.zeros(T, B, *s, device=dev)
+        self.obs, self.critic_obs, self.actions = z(*actor_obs_shape), z(*critic_obs_shape), z(*action_shape)
+        self.old_log_prob, self.old_mu, self.old_sigma = z(), z(*action_shape), z(*action_shape)
+        self._mbs = T * B // self.num_mini_batches
+        if self._mbs < 1:
+            raise Go2SimError("fewer rows than mini-batches")
+        self._h = self.policy.attach_trainer(self._mbs, **self._hyper)
+        self._batch = make_batch(obs=self.obs, critic_obs=self.critic_obs, actions=self.actions, target_values=self.storage.values, returns=self.storage.returns,
+                                 advantages=self.storage.advantages, old_log_prob=self.old_log_prob, old_mu=self.old_mu, old_sigma=self.old_sigma)
+
+    def act(self, obs, critic_obs):
+        t = self.t
+        actions = self.policy.act(obs, critic_obs)
+        self.obs[t].copy_(obs); self.critic_obs[t].copy_(critic_obs); self.actions[t].copy_(actions)
+        self.old_log_prob[t].copy_(self.policy.actions_log_prob); self.old_mu[t].copy_(self.policy.action_mean); self.old_sigma[t].copy_(self.policy.action_std)
+        return actions
+
+    def process_env_step(self, rewards, dones, infos):
+        self.storage.add_transitions(self.t, rewards, dones, self.policy.values, infos.get("time_outs") if infos else None, gamma=self.gamma)
+        self.t += 1
+
+    def compute_returns(self, last_critic_obs):
+        self.storage.compute_returns(self.policy.evaluate(last_critic_obs), self.gamma, self.lam)
+
+    def update(self):
+        n = self.num_mini_batches * self._mbs
+        perm = torch.randperm(n, device=self.device, generator=self._gen).to(torch.int32)
+        self._h.update(self._batch, self.policy.std, perm, self.T * self.B, self.num_learning_epochs, self.num_mini_batches)
+        s = self._h.stats().cpu()                                          # the update's only host synchronisation
+        self.last_stats = s
+        self.learning_rate = float(s[C["GO2SIM_PPO_ST_LR"]])
+        self.t = 0
+        return float(s[C["GO2SIM_PPO_ST_VALUE_LOSS"]]), float(s[C["GO2SIM_PPO_ST_SURROGATE"]]), float(s[C["GO2SIM_PPO_ST_ENTROPY"]])
+
+    # ---- optimizer state (runner checkpoints) ----------------------------------------------------------
+    def optimizer_state_dict(self):
+        s = self._h.stats().cpu()
+        return {"exp_avg": self._h.export("ADAM_M").cpu(), "exp_avg_sq": self._h.export("ADAM_V").cpu(), "step": int(s[C["GO2SIM_PPO_ST_STEP"]]),
+                "lr": float(s[C["GO2SIM_PPO_ST_LR"]]), "perm_generator_state": self._gen.get_state().cpu()}
+
+    def load_optimizer_state_dict(self, sd):
+        self._h.import_("ADAM_M", sd["exp_avg"]); self._h.import_("ADAM_V", sd["exp_avg_sq"])
+        self._h.set_step(int(sd["step"]), float(sd["lr"]))
+        self.learning_rate = float(sd["lr"])
+        if sd.get("perm_generator_state") is not None:
+            self._gen.set_state(sd["perm_generator_state"].cpu())

@@ -1,0 +1,97 @@
+"""OnPolicyRunner -- the part of ``rsl_rl.runners.OnPolicyRunner`` (rsl-rl-lib==2.2.4) the train scripts use
+(examples/locomotion/final/go2_train_walk.py:475-476): it takes the reference's ``train_cfg`` dictionary unchanged and closes
+``Go2Env -> ActorCritic -> RolloutStorage -> PPO.update()`` into a training loop that stays on the device.
+
+    runner = OnPolicyRunner(env, get_train_cfg("go2-walk", 1000), log_dir="logs/go2-walk")
+    log = runner.learn(num_learning_iterations=1000, init_at_random_ep_len=True)
+    policy = runner.get_inference_policy()
+
+No TensorBoard: ``learn`` returns one dictionary per iteration.  The reward / episode-length means are taken over the episodes that ended
+during the iteration (the reference averages its last 100 finished episodes); they are counted on the device and read once per iteration,
+after the update's own read of its statistics.
+"""
+import os
+
+import torch
+
+from .capi import Go2SimError
+from .eval_io import read_checkpoint, save_checkpoint
+from .policy import ActorCritic
+from .ppo import PPO
+
+
+class OnPolicyRunner:
+    def __init__(self, env, train_cfg, log_dir=None, device=None):
+        self.cfg, self.env, self.log_dir = train_cfg, env, log_dir
+        self.device = torch.device(device) if device is not None else env.device
+        if train_cfg.get("empirical_normalization"):
+            raise Go2SimError("empirical_normalization is out of scope (the train scripts set it to None)")
+        alg_cfg, pol_cfg = dict(train_cfg["algorithm"]), dict(train_cfg["policy"])
+        if alg_cfg.pop("class_name", "PPO") != "PPO" or pol_cfg.pop("class_name", "ActorCritic") != "ActorCritic":
+            raise Go2SimError("go2sim implements class_name PPO / ActorCritic")
+        obs, extras = env.get_observations()
+        critic_obs = extras["observations"].get("critic", obs)
+        seed = int(train_cfg.get("seed", 1) or 1)
+        self.policy = ActorCritic(obs.shape[1], critic_obs.shape[1], env.num_actions, device=self.device, seed=seed, **pol_cfg)
+        self.alg = PPO(self.policy, device=self.device, seed=seed, **alg_cfg)
+        self.num_steps_per_env = int(train_cfg["num_steps_per_env"])
+        self.save_interval = int(train_cfg.get("save_interval", 0) or 0)
+        self.alg.init_storage(env.num_envs, self.num_steps_per_env, [obs.shape[1]], [critic_obs.shape[1]], [env.num_actions])
+        self.current_learning_iteration = 0
+        self._last_means = (0.0, 0.0)
+        self._cur_rew, self._cur_len = torch.zeros(env.num_envs, device=self.device), torch.zeros(env.num_envs, device=self.device)
+
+    def learn(self, num_learning_iterations, init_at_random_ep_len=False):
+        env, alg, dev = self.env, self.alg, self.device
+        if init_at_random_ep_len:
+            env.episode_length_buf = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
+        obs, extras = env.get_observations()
+        critic_obs = extras["observations"].get("critic", obs)
+        cur_rew, cur_len = self._cur_rew, self._cur_len                       # running episodes carry over from one learn() to the next
+        log = []
+        start = self.current_learning_iteration
+        for it in range(start, start + num_learning_iterations):
+            acc = torch.zeros(3, device=dev, dtype=torch.float64)            # finished episodes: count, sum of rewards, sum of lengths
+            for _ in range(self.num_steps_per_env):
+                actions = alg.act(obs, critic_obs)
+                obs, rewards, dones, infos = env.step(actions)
+                critic_obs = infos["observations"].get("critic", obs)
+                alg.process_env_step(rewards, dones, infos)
+                cur_rew += rewards; cur_len += 1
+                d = (dones > 0).to(torch.float64)
+                acc += torch.stack([d.sum(), (d * cur_rew).sum(), (d * cur_len).sum()])
+                keep = (dones == 0).to(cur_rew.dtype)
+                cur_rew *= keep; cur_len *= keep
+            alg.compute_returns(critic_obs)
+            value_loss, surrogate_loss, entropy = alg.update()
+            n, rs, ls = acc.tolist()
+            if n > 0:
+                self._last_means = (rs / n, ls / n)
+            self.current_learning_iteration = it + 1
+            log.append({"iteration": it, "mean_reward": self._last_means[0], "mean_episode_length": self._last_means[1], "value_loss": value_loss,
+                        "surrogate_loss": surrogate_loss, "entropy": entropy, "learning_rate": alg.learning_rate})
+            if self.log_dir is not None and self.save_interval > 0 and (it + 1) % self.save_interval == 0:
+                self.save(os.path.join(self.log_dir, f"model_{it + 1}.pt"))
+        if self.log_dir is not None:
+            self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
+        return log
+
+    def save(self, path, infos=None):
+        """rsl_rl 2.2.4 checkpoint layout (eval_io.read_checkpoint): model_state_dict, optimizer_state_dict (Adam's m, v, step, learning rate), iter, infos."""
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        opt = self.alg.optimizer_state_dict()
+        opt["policy_noise_step"] = int(self.policy._step)
+        save_checkpoint(path, self.policy.state_dict(), opt, self.current_learning_iteration, infos)
+
+    def load(self, path, load_optimizer=True):
+        ckpt = read_checkpoint(path)
+        self.policy.load_state_dict(ckpt["model_state_dict"])
+        opt = ckpt.get("optimizer_state_dict") or {}
+        if load_optimizer and "exp_avg" in opt:
+            self.alg.load_optimizer_state_dict(opt)
+            self.policy._step = int(opt.get("policy_noise_step", self.policy._step))
+        self.current_learning_iteration = int(ckpt.get("iter", 0) or 0)
+        return ckpt.get("infos")
+
+    def get_inference_policy(self, device=None):
+        return self.policy.act_inference

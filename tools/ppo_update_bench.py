@@ -1,0 +1,147 @@
+#!/usr/bin/env python
+"""Times PPO.update() of the library against an eager-torch fp32 restatement of the same update on the same GPU, at the training shape of the
+walk task: T = 24 steps x B = 4096 envs, 49 / 104 observations, 16 actions, two 512-256-128 MLPs, 5 epochs x 4 mini-batches of 24 576 rows.
+
+    python tools/ppo_update_bench.py [--updates 5] [--warmup 2] [--envs 4096] [--steps 24]
+
+Both sides update from the same rollout (collected once with the library's ActorCritic on random observations and rewards) and the same initial
+parameters.  Every shape is warmed up first; device events bracket `--updates` whole updates per side, the two sides alternating update by update so
+that other work on the machine hits both alike.  The HIP update ends in its one read of the statistics; the torch restatement reads kl_mean once per
+mini-batch, as rsl_rl's adaptive schedule does.  Prints one JSON line: both times per update, their ratio, the matrix work of an update computed
+from the shapes (forward, dW and dA of every layer, 2 x rows x in x out each; unpadded) and the fraction of the 157.3 TFLOPS fp32 matrix peak
+that the HIP update as a whole achieves (an end-to-end rate over peak, not a kernel's)."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+from torch import nn
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+PEAK_FP32_MATRIX = 157.3e12
+HP = dict(clip_param=0.2, desired_kl=0.01, entropy_coef=0.003, learning_rate=1e-3, max_grad_norm=1.0, value_loss_coef=1.0)
+EPOCHS, MINI_BATCHES = 5, 4
+
+
+def mlp(dims):
+    layers = []
+    for l in range(len(dims) - 1):
+        layers.append(nn.Linear(dims[l], dims[l + 1]))
+        if l < len(dims) - 2:
+            layers.append(nn.ELU())
+    return nn.Sequential(*layers)
+
+
+class TorchPPO:
+    """rsl_rl 2.2.4 PPO.update in eager torch (autograd, Normal, clip_grad_norm_, Adam)"""
+
+    def __init__(self, adims, cdims, state, device):
+        self.actor, self.critic = mlp(adims).to(device), mlp(cdims).to(device)
+        self.std = nn.Parameter(state["std"].to(device).clone())
+        with torch.no_grad():
+            for prefix, net in (("actor", self.actor), ("critic", self.critic)):
+                for k, p in net.named_parameters():
+                    p.copy_(state[f"{prefix}.{k}"])
+        self.params = [*self.actor.parameters(), *self.critic.parameters(), self.std]
+        self.lr = HP["learning_rate"]
+        self.opt = torch.optim.Adam(self.params, lr=self.lr)
+
+    def update(self, ro, perm):
+        mbs = perm.numel() // MINI_BATCHES
+        clip = HP["clip_param"]
+        for _ in range(EPOCHS):
+            for i in range(MINI_BATCHES):
+                idx = perm[i * mbs:(i + 1) * mbs].long()
+                mu = self.actor(ro["obs"][idx])
+                v = self.critic(ro["critic_obs"][idx]).squeeze(-1)
+                sigma = mu * 0.0 + self.std
+                dist = torch.distributions.Normal(mu, sigma)
+                logp = dist.log_prob(ro["actions"][idx]).sum(-1)
+                entropy = dist.entropy().sum(-1)
+                old_mu, old_sigma = ro["old_mu"][idx], ro["old_sigma"][idx]
+                with torch.inference_mode():
+                    kl = torch.sum(torch.log(sigma / old_sigma + 1.0e-5) + (old_sigma ** 2 + (old_mu - mu) ** 2) / (2.0 * sigma ** 2) - 0.5, dim=-1)
+                    kl_mean = float(kl.mean())                                      # the schedule's host read
+                if kl_mean > HP["desired_kl"] * 2.0:
+                    self.lr = max(1e-5, self.lr / 1.5)
+                elif 0.0 < kl_mean < HP["desired_kl"] / 2.0:
+                    self.lr = min(1e-2, self.lr * 1.5)
+                for g in self.opt.param_groups:
+                    g["lr"] = self.lr
+                adv, tv, ret = ro["advantages"][idx], ro["target_values"][idx], ro["returns"][idx]
+                ratio = torch.exp(logp - ro["old_log_prob"][idx])
+                surrogate = torch.max(-adv * ratio, -adv * torch.clamp(ratio, 1.0 - clip, 1.0 + clip)).mean()
+                v_clipped = tv + (v - tv).clamp(-clip, clip)
+                value_loss = torch.max((v - ret).pow(2), (v_clipped - ret).pow(2)).mean()
+                loss = surrogate + HP["value_loss_coef"] * value_loss - HP["entropy_coef"] * entropy.mean()
+                self.opt.zero_grad()
+                loss.backward()
+                nn.utils.clip_grad_norm_(self.params, HP["max_grad_norm"])
+                self.opt.step()
+
+
+def matrix_flop(adims, cdims, rows):
+    f = 0
+    for dims in (adims, cdims):
+        for l in range(len(dims) - 1):
+            f += 2 * rows * dims[l] * dims[l + 1] * (3 if l > 0 else 2)                  # forward, dW, and dA except for the first layer
+    return f
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--updates", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=24)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("ppo_update_bench needs a ROCm GPU: a time taken anywhere else says nothing")
+    from go2_sim2real_locomotion_rl_amd import PPO, ActorCritic
+
+    dev = torch.device("cuda", 0)
+    T, B, nobs, npriv, nact = args.steps, args.envs, 49, 104, 16
+    hidden = [512, 256, 128]
+    adims, cdims = [nobs, *hidden, nact], [npriv, *hidden, 1]
+    policy = ActorCritic(nobs, npriv, nact, hidden, hidden, device=dev, seed=1)
+    state = {k: v.clone() for k, v in policy.state_dict().items()}
+    alg = PPO(policy, num_learning_epochs=EPOCHS, num_mini_batches=MINI_BATCHES, schedule="adaptive", gamma=0.99, lam=0.95, seed=1, **HP)
+    alg.init_storage(B, T, [nobs], [npriv], [nact])
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def collect():
+        for _ in range(T):
+            obs, cobs = torch.randn(B, nobs, device=dev, generator=g), torch.randn(B, npriv, device=dev, generator=g)
+            alg.act(obs, cobs)
+            alg.process_env_step(torch.randn(B, device=dev, generator=g), (torch.rand(B, device=dev, generator=g) < 0.01).to(torch.uint8), {})
+        alg.compute_returns(torch.randn(B, npriv, device=dev, generator=g))
+
+    collect()
+    flat = lambda t: t.reshape(T * B, *t.shape[2:]).clone()
+    ro = dict(obs=flat(alg.obs), critic_obs=flat(alg.critic_obs), actions=flat(alg.actions), old_mu=flat(alg.old_mu), old_sigma=flat(alg.old_sigma),
+              old_log_prob=flat(alg.old_log_prob), target_values=flat(alg.storage.values), returns=flat(alg.storage.returns),
+              advantages=flat(alg.storage.advantages))
+    ref = TorchPPO(adims, cdims, state, dev)
+    perm_gen = torch.Generator(device=dev).manual_seed(1)
+    torch_update = lambda: ref.update(ro, torch.randperm(T * B // MINI_BATCHES * MINI_BATCHES, device=dev, generator=perm_gen))
+    for _ in range(args.warmup):
+        alg.update(); torch_update()
+    torch.cuda.synchronize()
+    ms = {"hip": 0.0, "torch": 0.0}
+    for _ in range(args.updates):                                                          # alternate the two sides update by update
+        for name, fn in (("hip", alg.update), ("torch", torch_update)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); fn(); e1.record()
+            torch.cuda.synchronize()
+            ms[name] += e0.elapsed_time(e1)
+    hip_ms, torch_ms = ms["hip"] / args.updates, ms["torch"] / args.updates
+    flop = matrix_flop(adims, cdims, T * B // MINI_BATCHES) * EPOCHS * MINI_BATCHES
+    print(json.dumps({"tool": "ppo_update_bench", "envs": B, "steps": T, "epochs": EPOCHS, "mini_batches": MINI_BATCHES, "updates_timed": args.updates,
+                      "hip_ms_per_update": round(hip_ms, 3), "torch_eager_ms_per_update": round(torch_ms, 3), "hip_over_torch": round(hip_ms / torch_ms, 3),
+                      "matrix_flop_per_update": flop, "hip_fraction_of_157.3_tflops": round(flop / (hip_ms * 1e-3) / PEAK_FP32_MATRIX, 4)}))
+
+
+if __name__ == "__main__":
+    main()
