@@ -16,6 +16,11 @@
 //                     reduction runs over its rows): no transposed copy of the weights is kept, the optimizer writes one array per layer.
 //                     Not launched for the first layer.
 //   k_reduce_partials adds the chunk slabs in chunk order in float64 and rounds once: the padded gradient vector.
+// A shard of a mini-batch that spans ranks (go2sim_ppo_shard_grad / go2sim_ppo_shard_reduce) runs the same launches with the global row weight and
+// replaces k_ppo_finalize and k_reduce_partials by
+//   k_shard_record    the same two sums (chunk slabs in chunk order, head partials in workgroup order) left in float64: the shard's record.
+//   k_shard_reduce    one pass over [records][padded vector]: adds the records in record order, rounds once into the gradient vector, the entropy term
+//                     on the std block.   k_shard_scalars: one workgroup, the three sums over the records' rows and the learning-rate rule.
 // The optimizer is two launches: k_sumsq (per-workgroup float64 sums of squares, pairwise tree) and k_adam (every workgroup adds those in the same
 // order, then clip coefficient and Adam in one pass over the padded parameters, written into the arrays go2sim_policy_act reads and into std).
 // Adam's per-element arithmetic is float64 on fp32 state, rounded once per stored value.
@@ -105,6 +110,7 @@ struct HeadArgs {
   double* part;                                           // [workgroups][3 + A]
   int n, A, Apad, use_clipped;
   double clip, vl_coef;
+  double w;                                               // weight of a row in the means: 1 / n, or 1 / (rows of all shards)
 };
 
 __global__ __launch_bounds__(WGT) void k_ppo_head(HeadArgs h) {
@@ -115,7 +121,7 @@ __global__ __launch_bounds__(WGT) void k_ppo_head(HeadArgs h) {
   size_t src = 0;
   if (on) {
     src = (size_t)h.idx[r];
-    const double w = 1.0 / (double)h.n;
+    const double w = h.w;
     double lp = 0.0;
     for (int a = 0; a < A; ++a) {
       const double x = h.b.actions[src * A + a], m = h.mu[(size_t)r * A + a], s = h.std_[a];
@@ -174,6 +180,21 @@ __global__ __launch_bounds__(WGT) void k_ppo_head(HeadArgs h) {
   }
 }
 
+// the mini-batch's means are known: entropy, the learning-rate rule on kl_mean, the running sums of the reported means (one thread)
+__device__ __forceinline__ void close_minibatch(double sur_mean, double vl_mean, double kl_mean, int A, const float* __restrict__ std_, double* __restrict__ scal,
+                                                double desired_kl, double lr_min, double lr_max, int adaptive) {
+  double ent = 0.0;
+  for (int a = 0; a < A; ++a) ent += 0.5 + 0.5 * 1.8378770664093454836 + log((double)std_[a]);
+  if (adaptive) {
+    double lr = scal[S_LR];
+    if (kl_mean > 2.0 * desired_kl) lr = fmax(lr_min, lr / 1.5);
+    else if (kl_mean < desired_kl / 2.0 && kl_mean > 0.0) lr = fmin(lr_max, lr * 1.5);
+    scal[S_LR] = lr;
+  }
+  scal[S_KL] = kl_mean;
+  scal[S_SUM_SUR] += sur_mean; scal[S_SUM_VL] += vl_mean; scal[S_SUM_ENT] += ent; scal[S_COUNT] += 1.0;
+}
+
 // one workgroup: column q of the head's partials is added in workgroup order by lane q (q = 0 surrogate, 1 value loss, 2 kl, 3 + a d sigma_a)
 __global__ __launch_bounds__(64) void k_ppo_finalize(const double* __restrict__ part, int n_wg, int n, int A, const float* __restrict__ std_, double* __restrict__ scal,
                                                      float* __restrict__ grad_std, double entropy_coef, double desired_kl, double lr_min, double lr_max, int adaptive) {
@@ -185,19 +206,7 @@ __global__ __launch_bounds__(64) void k_ppo_finalize(const double* __restrict__ 
     else grad_std[q - 3] = (float)(s - entropy_coef / (double)std_[q - 3]);     // the entropy bonus: - entropy_coef * d/d sigma sum_a log sigma
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double ent = 0.0;
-    for (int a = 0; a < A; ++a) ent += 0.5 + 0.5 * 1.8378770664093454836 + log((double)std_[a]);
-    const double kl_mean = s3[2];
-    if (adaptive) {
-      double lr = scal[S_LR];
-      if (kl_mean > 2.0 * desired_kl) lr = fmax(lr_min, lr / 1.5);
-      else if (kl_mean < desired_kl / 2.0 && kl_mean > 0.0) lr = fmin(lr_max, lr * 1.5);
-      scal[S_LR] = lr;
-    }
-    scal[S_KL] = kl_mean;
-    scal[S_SUM_SUR] += s3[0]; scal[S_SUM_VL] += s3[1]; scal[S_SUM_ENT] += ent; scal[S_COUNT] += 1.0;
-  }
+  if (threadIdx.x == 0) close_minibatch(s3[0], s3[1], s3[2], A, std_, scal, desired_kl, lr_min, lr_max, adaptive);
 }
 
 // one layer of one network as the backward kernels see it
@@ -350,6 +359,54 @@ __global__ __launch_bounds__(WGT) void k_reduce_partials(const float* __restrict
   double s = 0.0;
   for (int c = 0; c < n_chunks; ++c) s += (double)partial[(size_t)c * slab + i];
   grads[i] = (float)s;
+}
+
+// A shard's record (include/go2sim_train.h): entry i of [0, slab) is k_reduce_partials' sum without the rounding, the Apad entries after it are the
+// head's d loss / d sigma partials added in workgroup order (no entropy term), the last four the sums of surrogate, value loss, kl and the row count.
+__global__ __launch_bounds__(WGT) void k_shard_record(const float* __restrict__ partial, int n_chunks, size_t slab, const double* __restrict__ part, int n_wg,
+                                                      int A, int Apad, int n_rows, double* __restrict__ rec) {
+  const size_t i = (size_t)blockIdx.x * WGT + threadIdx.x;
+  if (i >= slab + (size_t)Apad + 4) return;
+  double s = 0.0;
+  if (i < slab) {
+    for (int c = 0; c < n_chunks; ++c) s += (double)partial[(size_t)c * slab + i];
+  } else {
+    const int k = (int)(i - slab);
+    int q = -1;                                            // column of the head's partials
+    if (k < Apad) { if (k < A) q = 3 + k; }
+    else if (k - Apad < 3) q = k - Apad;
+    else s = (double)n_rows;
+    if (q >= 0)
+      for (int w = 0; w < n_wg; ++w) s += part[(size_t)w * (3 + A) + q];
+  }
+  rec[i] = s;
+}
+
+// entry i of the padded gradient vector: the records' entries added in record order, rounded once; the std block takes the entropy bonus here
+__global__ __launch_bounds__(WGT) void k_shard_reduce(const double* __restrict__ rec, int n_rec, size_t len, size_t slab, int A, int Apad,
+                                                      const float* __restrict__ std_, double entropy_coef, float* __restrict__ grads) {
+  const size_t i = (size_t)blockIdx.x * WGT + threadIdx.x;
+  if (i >= slab + (size_t)Apad) return;
+  double s = 0.0;
+  for (int r = 0; r < n_rec; ++r) s += rec[(size_t)r * len + i];
+  if (i < slab) grads[i] = (float)s;
+  else {
+    const int a = (int)(i - slab);
+    grads[i] = a < A ? (float)(s - entropy_coef / (double)std_[a]) : 0.0f;
+  }
+}
+
+// one workgroup: lane q adds scalar q of the records in record order (surrogate, value loss, kl, rows)
+__global__ __launch_bounds__(64) void k_shard_scalars(const double* __restrict__ rec, int n_rec, size_t len, int A, const float* __restrict__ std_,
+                                                      double* __restrict__ scal, double desired_kl, double lr_min, double lr_max, int adaptive) {
+  __shared__ double s4[4];
+  if (threadIdx.x < 4) {
+    double s = 0.0;
+    for (int r = 0; r < n_rec; ++r) s += rec[(size_t)r * len + (len - 4) + threadIdx.x];
+    s4[threadIdx.x] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) close_minibatch(s4[0] / s4[3], s4[1] / s4[3], s4[2] / s4[3], A, std_, scal, desired_kl, lr_min, lr_max, adaptive);
 }
 
 __global__ __launch_bounds__(WGT) void k_sumsq(const float* __restrict__ g, size_t n, double* __restrict__ part) {
@@ -539,11 +596,9 @@ int go2sim_ppo_destroy(go2sim_ppo_t* h) {
   return GO2SIM_E_OK;
 }
 
-int go2sim_ppo_minibatch_grad(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const float* std_dev, const int32_t* idx, int n, void* stream) {
-  if (!h || !b || !std_dev || !idx || n < 1 || n > h->max_rows) return GO2SIM_E_BADARG;
-  if (!b->obs || !b->critic_obs || !b->actions || !b->target_values || !b->returns || !b->advantages || !b->old_log_prob || !b->old_mu || !b->old_sigma)
-    return GO2SIM_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
+// The launches of one mini-batch.  record == nullptr: the rows are the whole mini-batch (k_ppo_finalize, k_reduce_partials); otherwise they are a shard of it
+// and the sums stay in float64 in `record`.
+static int launch_grad(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const float* std_dev, const int32_t* idx, int n, double w, double* record, hipStream_t st) {
   const go2sim_mlp *Ma = h->actor, *Mc = h->critic;
   hipLaunchKernelGGL(k_train_forward, dim3((n + TM - 1) / TM, 2), dim3(64 * NWAVE), 0, st, Ma->dev, b->obs, h->mu, h->ws[0], Mc->dev, b->critic_obs, h->val, h->ws[1], idx, n);
   const int n_wg = (n + WGT - 1) / WGT;
@@ -551,10 +606,11 @@ int go2sim_ppo_minibatch_grad(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, cons
   ha.mu = h->mu; ha.val = h->val; ha.b = *b; ha.std_ = std_dev; ha.idx = idx;
   ha.dz_actor = h->dz[0][(Ma->n_layers - 1) & 1]; ha.dz_critic = h->dz[1][(Mc->n_layers - 1) & 1];
   ha.part = h->head_part; ha.n = n; ha.A = h->A; ha.Apad = h->Apad; ha.use_clipped = h->cfg.use_clipped_value_loss;
-  ha.clip = h->cfg.clip_param; ha.vl_coef = h->cfg.value_loss_coef;
+  ha.clip = h->cfg.clip_param; ha.vl_coef = h->cfg.value_loss_coef; ha.w = w;
   hipLaunchKernelGGL(k_ppo_head, dim3(n_wg), dim3(WGT), 0, st, ha);
-  hipLaunchKernelGGL(k_ppo_finalize, dim3(1), dim3(64), 0, st, h->head_part, n_wg, n, h->A, std_dev, h->scal, h->grads + h->nA + h->nC, h->cfg.entropy_coef,
-                     h->cfg.desired_kl, h->cfg.lr_min, h->cfg.lr_max, h->cfg.adaptive);
+  if (!record)
+    hipLaunchKernelGGL(k_ppo_finalize, dim3(1), dim3(64), 0, st, h->head_part, n_wg, n, h->A, std_dev, h->scal, h->grads + h->nA + h->nC, h->cfg.entropy_coef,
+                       h->cfg.desired_kl, h->cfg.lr_min, h->cfg.lr_max, h->cfg.adaptive);
   const int n_chunks = (n + RCH - 1) / RCH;
   const size_t slab = h->nA + h->nC;
   const int depth = Ma->n_layers > Mc->n_layers ? Ma->n_layers : Mc->n_layers;
@@ -577,7 +633,44 @@ int go2sim_ppo_minibatch_grad(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, cons
       hipLaunchKernelGGL(k_bwd_da, dim3((n + TM - 1) / TM, 2), dim3(64 * NWAVE), 0, st, D0, D1, n);
     }
   }
-  hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((slab + WGT - 1) / WGT)), dim3(WGT), 0, st, h->partial, n_chunks, slab, h->grads);
+  if (!record)
+    hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((slab + WGT - 1) / WGT)), dim3(WGT), 0, st, h->partial, n_chunks, slab, h->grads);
+  else
+    hipLaunchKernelGGL(k_shard_record, dim3((unsigned)((h->n_tot + 4 + WGT - 1) / WGT)), dim3(WGT), 0, st, h->partial, n_chunks, slab, h->head_part, n_wg, h->A,
+                       h->Apad, n, record);
+  HIPCHK(hipGetLastError());
+  return GO2SIM_E_OK;
+}
+
+static bool batch_ok(const go2sim_ppo_batch_t* b) {
+  return b && b->obs && b->critic_obs && b->actions && b->target_values && b->returns && b->advantages && b->old_log_prob && b->old_mu && b->old_sigma;
+}
+
+int go2sim_ppo_minibatch_grad(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const float* std_dev, const int32_t* idx, int n, void* stream) {
+  if (!h || !std_dev || !idx || n < 1 || n > h->max_rows || !batch_ok(b)) return GO2SIM_E_BADARG;
+  return launch_grad(h, b, std_dev, idx, n, 1.0 / (double)n, nullptr, (hipStream_t)stream);
+}
+
+int go2sim_ppo_shard_len(go2sim_ppo_t* h, size_t* out) {
+  if (!h || !out) return GO2SIM_E_BADARG;
+  *out = h->n_tot + 4;
+  return GO2SIM_E_OK;
+}
+
+int go2sim_ppo_shard_grad(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const float* std_dev, const int32_t* idx, int n, long long n_global, double* record,
+                          void* stream) {
+  if (!h || !std_dev || !idx || !record || n < 1 || n > h->max_rows || n_global < (long long)n || !batch_ok(b)) return GO2SIM_E_BADARG;
+  return launch_grad(h, b, std_dev, idx, n, 1.0 / (double)n_global, record, (hipStream_t)stream);
+}
+
+int go2sim_ppo_shard_reduce(go2sim_ppo_t* h, const double* records, int n_records, const float* std_dev, void* stream) {
+  if (!h || !records || !std_dev || n_records < 1) return GO2SIM_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t slab = h->nA + h->nC, len = h->n_tot + 4;
+  hipLaunchKernelGGL(k_shard_reduce, dim3((unsigned)((h->n_tot + WGT - 1) / WGT)), dim3(WGT), 0, st, records, n_records, len, slab, h->A, h->Apad, std_dev,
+                     h->cfg.entropy_coef, h->grads);
+  hipLaunchKernelGGL(k_shard_scalars, dim3(1), dim3(64), 0, st, records, n_records, len, h->A, std_dev, h->scal, h->cfg.desired_kl, h->cfg.lr_min, h->cfg.lr_max,
+                     h->cfg.adaptive);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;
 }

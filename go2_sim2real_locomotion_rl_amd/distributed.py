@@ -34,13 +34,52 @@ def merge_moments(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return torch.stack([a[0] + b[0], a[1] + b[1] + delta * delta * (a[2] * b[2] / n), n])
 
 
+def is_multi(group=None) -> bool:
+    """True inside a process group of more than one rank."""
+    return dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+
+
+def allgather_records(record: torch.Tensor, group=None) -> torch.Tensor:
+    """Every rank's `record` (a flat tensor of the same length on every rank) as [world][len] in rank order: ONE all-gather.  Under "nccl" the device
+    tensor goes through ``all_gather_into_tensor`` on torch's current stream (RCCL over xGMI; nothing is copied to the host); under "gloo" (CPU tests,
+    one-GPU rehearsal) a device tensor is staged through the host, as sync_env_globals does.  With a single process it is the record itself, [1][len]."""
+    record = record.reshape(-1)
+    if not is_multi(group):
+        return record.view(1, -1)
+    world = dist.get_world_size(group)
+    staged = record.is_cuda and dist.get_backend(group) != "nccl"
+    src = (record.cpu() if staged else record).contiguous()
+    out = torch.empty(world * src.numel(), device=src.device, dtype=src.dtype)
+    dist.all_gather_into_tensor(out, src, group=group)
+    out = out.view(world, src.numel())
+    return out.to(record.device) if staged else out
+
+
+def sum_in_rank_order(x: torch.Tensor, group=None) -> torch.Tensor:
+    """The ranks' `x` added in rank order (one all-gather): every rank gets the same bits.  Identity for a single process."""
+    parts = allgather_records(x, group)
+    s = parts[0].clone()
+    for r in range(1, parts.shape[0]):
+        s += parts[r]
+    return s.view(x.shape)
+
+
+def broadcast_from_rank0(x: torch.Tensor, group=None) -> torch.Tensor:
+    """Rank 0's `x` on every rank (a new tensor on x's device); staged through the host under "gloo".  Identity for a single process."""
+    if not is_multi(group):
+        return x
+    src = dist.get_global_rank(group, 0) if group is not None else 0
+    staged = x.is_cuda and dist.get_backend(group) != "nccl"
+    buf = (x.cpu() if staged else x.clone()).contiguous()
+    dist.broadcast(buf, src=src, group=group)
+    return buf.to(x.device) if staged else buf
+
+
 def _merge_ranks(m: torch.Tensor, group=None) -> torch.Tensor:
     """One all-gather of 3 values per rank, merged in rank order so that every rank gets the same bits; identity for a single process."""
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+    if is_multi(group):
         world = dist.get_world_size(group)
-        out = torch.empty(3 * world, device=m.device, dtype=m.dtype)
-        dist.all_gather_into_tensor(out, m.contiguous(), group=group)
-        out = out.view(world, 3)
+        out = allgather_records(m, group)
         g = out[0].clone()
         for r in range(1, world):
             g = merge_moments(g, out[r])

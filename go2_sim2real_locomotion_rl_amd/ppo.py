@@ -12,12 +12,18 @@ kernels on the arrays ``ActorCritic.act`` reads; nothing of an update goes throu
         alg.process_env_step(rew, dones, infos)
     alg.compute_returns(critic_obs)
     value_loss, surrogate_loss, entropy = alg.update()      # one host synchronisation, after the last mini-batch
+
+Under ``torchrun`` (``PPO(..., group=torch.distributed.group.WORLD)``) every rank holds a shard of the envs and all of them train ONE policy: per
+mini-batch each rank writes its shard's contribution as a float64 record (go2sim_ppo_shard_grad), the records are all-gathered
+(distributed.allgather_records) and every rank adds them in rank order (go2sim_ppo_shard_reduce) before the usual go2sim_ppo_apply, so the ranks'
+parameters stay bit-identical without ever being re-broadcast.
 """
 import ctypes
 
 import torch
 
 from .capi import C, Go2SimError, PpoBatch, PpoCfg, load_hip_lib
+from .distributed import allgather_records, broadcast_from_rank0, is_multi, shard_seed
 from .rollout import RolloutStorage
 
 VECS = ("PARAMS", "GRADS", "ADAM_M", "ADAM_V")
@@ -56,6 +62,8 @@ class PpoHandle:
         self.n_params = n.value
         lib.check(lib.fn("ppo_n_padded")(self.h, ctypes.byref(n)), "ppo_n_padded")
         self.n_padded = n.value
+        lib.check(lib.fn("ppo_shard_len")(self.h, ctypes.byref(n)), "ppo_shard_len")
+        self.shard_len = n.value
         self._stats = torch.zeros(C["GO2SIM_PPO_N_STATS"], dtype=torch.float64, device=self.device)
 
     def _stream(self):
@@ -64,6 +72,23 @@ class PpoHandle:
     def minibatch_grad(self, batch, std, idx, n_rows=None):
         n = idx.numel() if n_rows is None else n_rows
         self.L.check(self.L.fn("ppo_minibatch_grad")(self.h, ctypes.byref(batch), _p(std), _p(idx), ctypes.c_int(n), self._stream()), "ppo_minibatch_grad")
+
+    def shard_grad(self, batch, std, idx, n_rows_global, record=None, n_rows=None):
+        """This shard's contribution to a mini-batch of n_rows_global rows: a float64 device record of shard_len entries (include/go2sim_train.h)"""
+        n = idx.numel() if n_rows is None else n_rows
+        if record is None:
+            record = torch.empty(self.shard_len, dtype=torch.float64, device=self.device)
+        elif record.dtype != torch.float64 or record.numel() != self.shard_len or not record.is_contiguous():
+            raise Go2SimError(f"a record is a contiguous float64 tensor of {self.shard_len} entries")
+        self.L.check(self.L.fn("ppo_shard_grad")(self.h, ctypes.byref(batch), _p(std), _p(idx), ctypes.c_int(n), ctypes.c_longlong(int(n_rows_global)), _p(record),
+                                                 self._stream()), "ppo_shard_grad")
+        return record
+
+    def shard_reduce(self, records, std):
+        """records [n][shard_len] float64 on the device, added in the order given: gradients, learning-rate rule and running sums of the whole mini-batch"""
+        if records.dtype != torch.float64 or not records.is_contiguous() or records.numel() % self.shard_len or not records.is_cuda:
+            raise Go2SimError(f"records must be a contiguous float64 device tensor [n][{self.shard_len}]")
+        self.L.check(self.L.fn("ppo_shard_reduce")(self.h, _p(records), ctypes.c_int(records.numel() // self.shard_len), _p(std), self._stream()), "ppo_shard_reduce")
 
     def apply(self, std):
         self.L.check(self.L.fn("ppo_apply")(self.h, _p(std), self._stream()), "ppo_apply")
@@ -140,12 +165,12 @@ def flatten(sd, adims, cdims):
 
 class PPO:
     def __init__(self, policy, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95, value_loss_coef=1.0, entropy_coef=0.0,
-                 learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device=None, *, seed=1, **kwargs):
+                 learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device=None, *, seed=1, group=None, **kwargs):
         if schedule not in ("adaptive", "fixed"):
             raise Go2SimError(f"schedule must be 'adaptive' or 'fixed', got {schedule!r}")
         unknown = {k: v for k, v in kwargs.items() if k not in ("class_name", "normalize_advantage_per_mini_batch") and v is not None}
         if unknown or kwargs.get("normalize_advantage_per_mini_batch"):
-            raise Go2SimError(f"go2sim's PPO does not implement {sorted(unknown) or ['normalize_advantage_per_mini_batch']} (RND, symmetry and multi-GPU are out of scope)")
+            raise Go2SimError(f"go2sim's PPO does not implement {sorted(unknown) or ['normalize_advantage_per_mini_batch']} (RND and symmetry are out of scope)")
         self.policy = self.actor_critic = policy
         self.device = policy.device if device is None else torch.device(device)
         self.num_learning_epochs, self.num_mini_batches = int(num_learning_epochs), int(num_mini_batches)
@@ -154,7 +179,10 @@ class PPO:
                            value_loss_coef=value_loss_coef, use_clipped_value_loss=use_clipped_value_loss, adaptive=schedule == "adaptive")
         self.schedule, self.desired_kl = schedule, desired_kl
         self.learning_rate = float(learning_rate)
-        self._gen = torch.Generator(device=self.device).manual_seed(int(seed))
+        # a process group of more than one rank: the envs are sharded over the ranks and the update sums the shards' gradients in rank order
+        self.group = group if group is not None and is_multi(group) else None
+        self.rank = torch.distributed.get_rank(self.group) if self.group is not None else 0
+        self._gen = torch.Generator(device=self.device).manual_seed(shard_seed(seed, self.rank))
         self.storage = self._h = None
         self.last_stats = None
 
@@ -171,6 +199,20 @@ class PPO:
         self._h = self.policy.attach_trainer(self._mbs, **self._hyper)
         self._batch = make_batch(obs=self.obs, critic_obs=self.critic_obs, actions=self.actions, target_values=self.storage.values, returns=self.storage.returns,
                                  advantages=self.storage.advantages, old_log_prob=self.old_log_prob, old_mu=self.old_mu, old_sigma=self.old_sigma)
+        if self.group is not None:
+            # the ranks' mini-batch sizes, gathered once: a row weighs 1 / (their sum), so unequal shards are weighted by rows
+            sizes = allgather_records(torch.tensor([float(self._mbs)], dtype=torch.float64, device=dev), self.group)
+            self._mbs_global = int(sizes.sum().item())
+            self._record = torch.empty(self._h.shard_len, dtype=torch.float64, device=dev)
+            self.broadcast_parameters()
+
+    def broadcast_parameters(self):
+        """Every rank takes rank 0's parameters (network weights and std): the ranks start from the same bits, and keep them because they apply the
+        same gradients.  Nothing to do for a single process."""
+        if self.group is None:
+            return
+        flat = broadcast_from_rank0(self._h.export("PARAMS", self.policy.std), self.group)
+        self._h.import_("PARAMS", flat, self.policy.std)
 
     def act(self, obs, critic_obs):
         t = self.t
@@ -184,17 +226,30 @@ class PPO:
         self.t += 1
 
     def compute_returns(self, last_critic_obs):
-        self.storage.compute_returns(self.policy.evaluate(last_critic_obs), self.gamma, self.lam)
+        self.storage.compute_returns(self.policy.evaluate(last_critic_obs), self.gamma, self.lam, group=self.group)
 
     def update(self):
         n = self.num_mini_batches * self._mbs
         perm = torch.randperm(n, device=self.device, generator=self._gen).to(torch.int32)
-        self._h.update(self._batch, self.policy.std, perm, self.T * self.B, self.num_learning_epochs, self.num_mini_batches)
+        if self.group is None:
+            self._h.update(self._batch, self.policy.std, perm, self.T * self.B, self.num_learning_epochs, self.num_mini_batches)
+        else:
+            self._update_sharded(perm)
         s = self._h.stats().cpu()                                          # the update's only host synchronisation
         self.last_stats = s
         self.learning_rate = float(s[C["GO2SIM_PPO_ST_LR"]])
         self.t = 0
         return float(s[C["GO2SIM_PPO_ST_VALUE_LOSS"]]), float(s[C["GO2SIM_PPO_ST_SURROGATE"]]), float(s[C["GO2SIM_PPO_ST_ENTROPY"]])
+
+    def _update_sharded(self, perm):
+        """go2sim_ppo_update's loop on the host with the collective in it: per mini-batch this shard's record, one all-gather, the ordered reduction, Adam."""
+        h, std, mbs = self._h, self.policy.std, self._mbs
+        h.reset_stats()
+        for _ in range(self.num_learning_epochs):
+            for i in range(self.num_mini_batches):
+                rec = h.shard_grad(self._batch, std, perm[i * mbs:(i + 1) * mbs], self._mbs_global, self._record)
+                h.shard_reduce(allgather_records(rec, self.group), std)
+                h.apply(std)
 
     # ---- optimizer state (runner checkpoints) ----------------------------------------------------------
     def optimizer_state_dict(self):
@@ -206,5 +261,5 @@ class PPO:
         self._h.import_("ADAM_M", sd["exp_avg"]); self._h.import_("ADAM_V", sd["exp_avg_sq"])
         self._h.set_step(int(sd["step"]), float(sd["lr"]))
         self.learning_rate = float(sd["lr"])
-        if sd.get("perm_generator_state") is not None:
+        if sd.get("perm_generator_state") is not None and self.rank == 0:     # the file holds rank 0's stream; the other ranks keep their own
             self._gen.set_state(sd["perm_generator_state"].cpu())

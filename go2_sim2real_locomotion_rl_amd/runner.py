@@ -9,19 +9,24 @@
 No TensorBoard: ``learn`` returns one dictionary per iteration.  The reward / episode-length means are taken over the episodes that ended
 during the iteration (the reference averages its last 100 finished episodes); they are counted on the device and read once per iteration,
 after the update's own read of its statistics.
+
+Under ``torchrun`` every rank builds its shard of the envs (``Go2Env(n_local, ..., shared_globals=True)``) and a runner; the runners train one policy
+(ppo.PPO with the process group): rank 0's initial weights, per-rank noise and permutation streams, one curriculum, gradients summed in rank order,
+global means in every rank's log, checkpoints written by rank 0 (tools/train.py).
 """
 import os
 
 import torch
 
 from .capi import Go2SimError
+from .distributed import is_multi, shard_seed, sum_in_rank_order
 from .eval_io import read_checkpoint, save_checkpoint
 from .policy import ActorCritic
 from .ppo import PPO
 
 
 class OnPolicyRunner:
-    def __init__(self, env, train_cfg, log_dir=None, device=None):
+    def __init__(self, env, train_cfg, log_dir=None, device=None, group=None):
         self.cfg, self.env, self.log_dir = train_cfg, env, log_dir
         self.device = torch.device(device) if device is not None else env.device
         if train_cfg.get("empirical_normalization"):
@@ -32,8 +37,13 @@ class OnPolicyRunner:
         obs, extras = env.get_observations()
         critic_obs = extras["observations"].get("critic", obs)
         seed = int(train_cfg.get("seed", 1) or 1)
-        self.policy = ActorCritic(obs.shape[1], critic_obs.shape[1], env.num_actions, device=self.device, seed=seed, **pol_cfg)
-        self.alg = PPO(self.policy, device=self.device, seed=seed, **alg_cfg)
+        if group is None and is_multi():
+            group = torch.distributed.group.WORLD
+        self.group = group if group is not None and is_multi(group) else None
+        self.rank = torch.distributed.get_rank(self.group) if self.group is not None else 0
+        # the noise stream is the rank's own; the initial weights drawn from the same seed are replaced by rank 0's at the end of init_storage
+        self.policy = ActorCritic(obs.shape[1], critic_obs.shape[1], env.num_actions, device=self.device, seed=shard_seed(seed, self.rank), **pol_cfg)
+        self.alg = PPO(self.policy, device=self.device, seed=seed, group=self.group, **alg_cfg)
         self.num_steps_per_env = int(train_cfg["num_steps_per_env"])
         self.save_interval = int(train_cfg.get("save_interval", 0) or 0)
         self.alg.init_storage(env.num_envs, self.num_steps_per_env, [obs.shape[1]], [critic_obs.shape[1]], [env.num_actions])
@@ -62,9 +72,11 @@ class OnPolicyRunner:
                 acc += torch.stack([d.sum(), (d * cur_rew).sum(), (d * cur_len).sum()])
                 keep = (dones == 0).to(cur_rew.dtype)
                 cur_rew *= keep; cur_len *= keep
+            if getattr(env, "_shared_globals", False):
+                env.sync_globals(self.group)                                   # one curriculum and one set of global DR draws for all shards
             alg.compute_returns(critic_obs)
             value_loss, surrogate_loss, entropy = alg.update()
-            n, rs, ls = acc.tolist()
+            n, rs, ls = sum_in_rank_order(acc, self.group).tolist()            # every rank logs the global means
             if n > 0:
                 self._last_means = (rs / n, ls / n)
             self.current_learning_iteration = it + 1
@@ -78,6 +90,8 @@ class OnPolicyRunner:
 
     def save(self, path, infos=None):
         """rsl_rl 2.2.4 checkpoint layout (eval_io.read_checkpoint): model_state_dict, optimizer_state_dict (Adam's m, v, step, learning rate), iter, infos."""
+        if self.rank != 0:                                                     # the ranks hold the same bits: rank 0 writes them
+            return
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         opt = self.alg.optimizer_state_dict()
         opt["policy_noise_step"] = int(self.policy._step)
@@ -90,6 +104,7 @@ class OnPolicyRunner:
         if load_optimizer and "exp_avg" in opt:
             self.alg.load_optimizer_state_dict(opt)
             self.policy._step = int(opt.get("policy_noise_step", self.policy._step))
+        self.alg.broadcast_parameters()                                        # every rank read the file; rank 0's parameters are the ones in force
         self.current_learning_iteration = int(ckpt.get("iter", 0) or 0)
         return ckpt.get("infos")
 

@@ -81,6 +81,28 @@ int go2sim_ppo_destroy(go2sim_ppo_t* h);
 /* Forward, loss head and backward of one mini-batch: rows idx[0 .. n_rows) of `batch` (int32 device indices).  Leaves the gradients on the device,
  * applies the learning-rate rule to the device-side learning rate and adds this mini-batch to the running sums of the three reported means. */
 int go2sim_ppo_minibatch_grad(go2sim_ppo_t* h, const go2sim_ppo_batch_t* batch, const float* std_dev, const int32_t* idx_dev, int n_rows, void* stream);
+/* One policy trained across ranks (data parallel): every rank runs go2sim_ppo_shard_grad on its shard of the mini-batch, the ranks exchange the
+ * records (one all-gather, distributed.allgather_records), every rank runs go2sim_ppo_shard_reduce on the same records in the same order, then
+ * go2sim_ppo_apply.  All ranks add the same float64 numbers in the same (record) order and round once, so they hold bit-identical gradients,
+ * learning rates and, after the step, parameters; no parameter is ever re-broadcast.
+ *
+ * A record is go2sim_ppo_shard_len float64 (= go2sim_ppo_n_padded + 4), in the padded layout actor | critic | std of the gradient vector:
+ *   [0, nA + nC)             the shard's chunk slabs of dW / db added in chunk order, not rounded; every row weighted 1 / n_rows_global
+ *   [nA + nC, + Apad)        d loss / d sigma[a] summed over the head's workgroups in workgroup order, WITHOUT the entropy term (it does not depend on
+ *                            rows: the reduction adds it once); entries a >= n_actions are zero
+ *   [nA + nC + Apad, + 4)    the shard's unnormalised sums over rows of surrogate, value loss and kl, then n_rows as a double
+ * Padded entries are exact zeros.  With one record and n_rows_global = n_rows, shard_grad + shard_reduce leave the handle in the state of
+ * go2sim_ppo_minibatch_grad bit for bit.
+ *
+ * go2sim_ppo_shard_grad: forward, head and backward of rows idx[0 .. n_rows) with weight 1 / n_rows_global (n_rows <= n_rows_global); writes
+ * record_dev and nothing else the other calls read: the learning rate, kl_mean, the running sums and the gradient vector are left alone. */
+int go2sim_ppo_shard_len(go2sim_ppo_t* h, size_t* out);
+int go2sim_ppo_shard_grad(go2sim_ppo_t* h, const go2sim_ppo_batch_t* batch, const float* std_dev, const int32_t* idx_dev, int n_rows,
+                          long long n_rows_global, double* record_dev, void* stream);
+/* records_dev [n_records][shard_len], added entry by entry in record order in float64 and rounded once into the gradient vector; the std block gets
+ * - entropy_coef / std; the three sums are divided by the records' total row count, the learning-rate rule is applied to that global kl_mean, and the
+ * mini-batch is added to the running sums of the reported means, as go2sim_ppo_minibatch_grad does for its own rows. */
+int go2sim_ppo_shard_reduce(go2sim_ppo_t* h, const double* records_dev, int n_records, const float* std_dev, void* stream);
 /* Global-norm clip and one Adam step on the gradients the handle holds, written to the two networks' weights and to std_dev[A]. */
 int go2sim_ppo_apply(go2sim_ppo_t* h, float* std_dev, void* stream);
 /* The whole update: resets the running sums, then for every epoch and mini-batch i the two calls above on perm_dev[i * mbs .. (i + 1) * mbs),

@@ -1,0 +1,347 @@
+"""The sharded PPO update of the HIP library (go2sim_ppo_shard_grad / go2sim_ppo_shard_reduce, include/go2sim_train.h) in ONE process: several
+go2sim_ppo handles stand in for the ranks, each on its shard of a mini-batch's rows, and the "collective" is torch.cat of their records.  Inputs are
+the cases of tests/ppo_cases.py, the checker is tests/ppo_ref.py in float64 over the union of the shards' rows with its float32 evaluation as the
+yardstick, under the header's own bounds:
+  gradients, per tensor, the loss scalars and kl_mean:  max|g - g64| <= C_GRAD max(max|g32 - g64|, 2^-24 max|g64|),  C_GRAD = 16
+  whole updates, per tensor:                            max|p - p64| <= C_UPD max|p32 - p64|,                        C_UPD = 8
+A sharded sum differs from the unsharded one only in the association of float64 additions, so the bounds are the unsharded path's.  Every test prints
+its ratios before it asserts (worst values: DESIGN.md "PPO update")."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import ppo_cases as PC
+import ppo_ref as R
+
+pytestmark = pytest.mark.gpu
+
+C_GRAD = 16
+C_UPD = 8
+EPS = 2.0 ** -24
+DEV = "cuda:0"
+RCH = PC.ROW_CHUNK
+SMALL_NETS = ("one_layer", "small", "six_layers")
+
+
+def r16(v):
+    return (v + 15) // 16 * 16
+
+
+def real_entry_mask(adims, cdims):
+    """True where the padded layout (actor | critic | std) holds a real entry"""
+    parts = []
+    for dims in (adims, cdims):
+        for l in range(len(dims) - 1):
+            w = np.zeros((r16(dims[l + 1]), r16(dims[l])), bool); w[:dims[l + 1], :dims[l]] = True
+            b = np.zeros(r16(dims[l + 1]), bool); b[:dims[l + 1]] = True
+            parts += [w.reshape(-1), b]
+    s = np.zeros(r16(adims[-1]), bool); s[:adims[-1]] = True
+    return np.concatenate(parts + [s])
+
+
+def record_mask(adims, cdims):
+    """a record is the padded layout followed by its four scalars"""
+    return np.concatenate([real_entry_mask(adims, cdims), np.ones(4, bool)])
+
+
+def kl_of(net, n):
+    """the schedule case tests/ppo_cases.py gives (net, n): its references are computed once and shared with tests/test_ppo_gpu.py"""
+    return next(k for (m, r, k) in PC.GRAD_CASES if (m, r) == (net, n))
+
+
+class Side:
+    """One "rank": the two networks, std, a rollout and one go2sim_ppo handle on the GPU, and the rows `idx` of its shard"""
+
+    def __init__(self, lib, adims, cdims, state, rollout, max_rows, idx=None, **hyper):
+        from go2_sim2real_locomotion_rl_amd.policy import Mlp, flatten_sequential
+        from go2_sim2real_locomotion_rl_amd.ppo import PpoHandle, make_batch
+
+        self.adims, self.cdims = adims, cdims
+        self.actor = Mlp(lib, adims, flatten_sequential(state, "actor", len(adims) - 1)[0])
+        self.critic = Mlp(lib, cdims, flatten_sequential(state, "critic", len(cdims) - 1)[0])
+        self.std = state["std"].to(DEV).clone()
+        self.ro = {k: v.to(DEV).contiguous() for k, v in rollout.items()}
+        self.batch = make_batch(**self.ro)
+        hp = dict(clip_param=R.HP["clip_param"], desired_kl=R.HP["desired_kl"], entropy_coef=R.HP["entropy_coef"], learning_rate=R.HP["learning_rate"],
+                  max_grad_norm=R.HP["max_grad_norm"], value_loss_coef=R.HP["value_loss_coef"], use_clipped_value_loss=True, adaptive=True)
+        hp.update(hyper)
+        self.h = PpoHandle(lib, self.actor, self.critic, adims[-1], max_rows, **hp)
+        self.idx = None if idx is None else idx.to(torch.int32).to(DEV).contiguous()
+
+    def split(self, flat):
+        from go2_sim2real_locomotion_rl_amd.ppo import unflatten
+
+        return {k: v.double() for k, v in unflatten(flat.cpu(), self.adims, self.cdims).items()}
+
+    def stats(self):
+        s = self.h.stats().cpu()
+        return dict(value_loss=float(s[0]), surrogate=float(s[1]), entropy=float(s[2]), kl_mean=float(s[3]), lr=float(s[4]), grad_norm=float(s[5]),
+                    step=int(s[6]), count=int(s[7])), s
+
+    def bits(self, which):
+        return self.h.export(which, self.std).cpu().numpy().view(np.int32)
+
+
+def shard_sides(lib, c, split, rows=None, **hyper):
+    """one Side per entry of `split` on consecutive pieces of the case's index array (or of `rows`)"""
+    rows = c.idx if rows is None else rows
+    assert sum(split) == rows.numel()
+    offs = np.concatenate([[0], np.cumsum(split)])
+    return [Side(lib, c.adims, c.cdims, c.state, c.rollout, n, rows[o:o + n], **hyper) for n, o in zip(split, offs)]
+
+
+def sharded_grad(sides, n_global):
+    """shard_grad on every side, the records concatenated in side order (the all-gather), shard_reduce of all of them on every side"""
+    records = torch.cat([s.h.shard_grad(s.batch, s.std, s.idx, n_global) for s in sides]).view(len(sides), -1)
+    for s in sides:
+        s.h.shard_reduce(records, s.std)
+    return records
+
+
+def grad_ratios(side, tag, g64, s64, g32, s32, keys=None, scalars=("surrogate", "value_loss", "entropy", "kl_mean")):
+    got = side.split(side.h.export("GRADS"))
+    st, _ = side.stats()
+    worst = 0.0
+    for k in (g64 if keys is None else keys):
+        err, yard = float((got[k] - g64[k]).abs().max()), max(float((g32[k].double() - g64[k]).abs().max()), EPS * float(g64[k].abs().max()))
+        print(f"RATIO shard grad {tag} {k} {err / yard:.3f}")
+        worst = max(worst, err / yard)
+    for k in scalars:
+        err, yard = abs(st[k] - s64[k]), max(abs(s32[k] - s64[k]), EPS * abs(s64[k]))
+        print(f"RATIO shard scalar {tag} {k} {err / yard:.3f}")
+        worst = max(worst, err / yard)
+    print(f"RATIO shard worst {tag} {worst:.3f}")
+    return worst, st
+
+
+# ---- 1. one shard is the plain update, bit for bit ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("net,n", [("small", 37), ("six_layers", 2 * RCH + 37), ("full", 80)], ids=lambda v: str(v))
+def test_one_shard_equals_minibatch_grad_bit_for_bit(hip_lib, net, n):
+    c = PC.get_case(net, n, kl_of(net, n))
+    plain, shard = shard_sides(hip_lib, c, [n])[0], shard_sides(hip_lib, c, [n])[0]
+    plain.h.minibatch_grad(plain.batch, plain.std, plain.idx)
+    rec = shard.h.shard_grad(shard.batch, shard.std, shard.idx, n)
+    assert rec.numel() == shard.h.shard_len == shard.h.n_padded + 4
+    shard.h.shard_reduce(rec.view(1, -1), shard.std)
+    ga, gb = plain.h.export_padded("GRADS").cpu().numpy(), shard.h.export_padded("GRADS").cpu().numpy()
+    assert np.array_equal(ga.view(np.int32), gb.view(np.int32)) and np.abs(ga).max() > 0
+    sa, sb = plain.stats()[1].numpy(), shard.stats()[1].numpy()
+    assert np.array_equal(sa.view(np.int64), sb.view(np.int64)), (sa, sb)
+    assert sa[7] == 1 and sa[4] == pytest.approx(R.lr_rule(R.HP["learning_rate"], c.ref["f64"][1]["kl_mean"], R.HP["desired_kl"]), rel=1e-15)
+    plain.h.apply(plain.std); shard.h.apply(shard.std)
+    for which in ("PARAMS", "ADAM_M", "ADAM_V", "GRADS"):
+        assert np.array_equal(plain.bits(which), shard.bits(which)), which
+    assert torch.equal(plain.std, shard.std) and not torch.equal(plain.std.cpu(), c.state["std"])
+    assert np.array_equal(plain.stats()[1].numpy().view(np.int64), shard.stats()[1].numpy().view(np.int64))
+
+
+# ---- 2. shards against float64 -----------------------------------------------------------------------------------------------------------------
+SPLITS = [(17, (16, 1)), (37, (1, 36)), (2 * RCH + 37, (RCH + 5, RCH + 32)), (2 * RCH + 37, (RCH, RCH, 37))]
+
+
+@pytest.mark.parametrize("kl_case", ["down", "up", "keep"])
+@pytest.mark.parametrize("net", SMALL_NETS)
+@pytest.mark.parametrize("n,split", SPLITS, ids=lambda v: "+".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_sharded_gradients_and_scalars(hip_lib, net, n, split, kl_case):
+    c = PC.get_case(net, n, kl_case)                           # computed once per (net, n, kl_case): the two splits of 2R + 37 rows share it
+    g64, s64, _ = c.ref["f64"]
+    g32, s32, _ = c.ref["f32"]
+    sides = shard_sides(hip_lib, c, list(split))
+    records = sharded_grad(sides, n).cpu().numpy()
+    tag = f"{net}-{n}-{kl_case}-{'+'.join(map(str, split))}"
+    worst, st = grad_ratios(sides[0], tag, g64, s64, g32, s32)
+    assert worst <= C_GRAD
+    assert st["count"] == 1 and st["lr"] == pytest.approx(R.lr_rule(R.HP["learning_rate"], s64["kl_mean"], R.HP["desired_kl"]), rel=1e-15)
+    # every handle reduced the same records in the same order: the same bits everywhere
+    for s in sides[1:]:
+        assert np.array_equal(s.h.export_padded("GRADS").cpu().numpy().view(np.int32), sides[0].h.export_padded("GRADS").cpu().numpy().view(np.int32))
+        assert np.array_equal(s.stats()[1].numpy().view(np.int64), sides[0].stats()[1].numpy().view(np.int64))
+    # padding, and the records' row counts
+    assert np.isfinite(records).all() and not records[:, ~record_mask(c.adims, c.cdims)].any(), "padded record entries must be exactly zero"
+    assert records[:, -1].tolist() == [float(k) for k in split]
+    padded = sides[0].h.export_padded("GRADS").cpu().numpy()
+    assert np.isfinite(padded).all() and not padded[~real_entry_mask(c.adims, c.cdims)].any(), "padded gradient entries must be exactly zero"
+
+
+# ---- 3. the learning rate follows the global kl ------------------------------------------------------------------------------------------------
+def test_learning_rate_follows_the_global_kl(hip_lib):
+    """A "down" shard of 8 rows (kl_mean 0.05) and an "up" shard of 32 rows (0.002): alone they cut / raise the learning rate, their union
+    (8 x 0.05 + 32 x 0.002) / 40 = 0.0116 keeps it.  Every handle must take the union's outcome."""
+    adims, cdims = PC.NETS["small"]
+    state = PC.init_state(adims, cdims, torch.Generator().manual_seed(9001))
+    ro_a, ro_b = PC.make_rollout(adims, cdims, state, 8, "down", 9002), PC.make_rollout(adims, cdims, state, 32, "up", 9003)
+    union = {k: torch.cat([ro_a[k], ro_b[k]]) for k in ro_a}
+    lr0, dkl = R.HP["learning_rate"], R.HP["desired_kl"]
+    m64 = R.make_model(adims, cdims, state, torch.float64)
+    kl = {name: R.minibatch_grad(m64, {k: v.double() for k, v in ro.items()})[1]["kl_mean"] for name, ro in (("a", ro_a), ("b", ro_b), ("union", union))}
+    outcome = {name: R.lr_rule(lr0, v, dkl) for name, v in kl.items()}
+    print(f"KL {kl} LR {outcome}")
+    assert len({outcome["a"], outcome["b"], outcome["union"]}) == 3, "the test is vacuous unless the shards alone and the union disagree"
+    PC.check_margins(m64, union, "keep")                       # the union's kl_mean keeps its distance from both thresholds
+    sides = [Side(hip_lib, adims, cdims, state, union, n, idx) for n, idx in ((8, torch.arange(8)), (32, torch.arange(8, 40)))]
+    sharded_grad(sides, 40)
+    for s in sides:
+        st, _ = s.stats()
+        assert st["lr"] == outcome["union"] == lr0 and st["kl_mean"] == pytest.approx(kl["union"], rel=1e-4)
+    # and on its own each shard does what the float64 side says it would: the outcome above is the union's, not a shard's
+    for s, name in zip(sides, ("a", "b")):
+        s.h.set_step(0, lr0)
+        n = s.idx.numel()
+        s.h.shard_reduce(s.h.shard_grad(s.batch, s.std, s.idx, n).view(1, -1), s.std)
+        assert s.stats()[0]["lr"] == pytest.approx(outcome[name], rel=1e-15)
+
+
+# ---- 4. a chunk-aligned split ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("net", ["small", "six_layers"])
+def test_chunk_aligned_split_keeps_the_network_gradients_bit_for_bit(hip_lib, net):
+    """2R rows as [R, R] against one handle on the 2R rows: a chunk's slab depends on that chunk's rows only and (0 + c0) + c1 is the same sum both
+    ways, so the network block [0, nA + nC) of GRADS is bit-equal.  The std block and the scalars are sums over other groupings (the head's
+    workgroups of 256 rows): they are held to the float64 bound."""
+    n = 2 * RCH + 37
+    c = PC.get_case(net, n, kl_of(net, n))
+    rows = c.idx[:2 * RCH]
+    ref = {}
+    for name, dt in (("f64", torch.float64), ("f32", torch.float32)):
+        ref[name] = R.minibatch_grad(R.make_model(c.adims, c.cdims, c.state, dt), R.rows_of(c.rollout, rows.long(), dt))
+    whole = shard_sides(hip_lib, c, [2 * RCH], rows)[0]
+    whole.h.minibatch_grad(whole.batch, whole.std, whole.idx)
+    sides = shard_sides(hip_lib, c, [RCH, RCH], rows)
+    sharded_grad(sides, 2 * RCH)
+    n_net = whole.h.n_padded - r16(c.adims[-1])
+    ga, gb = whole.h.export_padded("GRADS").cpu().numpy(), sides[0].h.export_padded("GRADS").cpu().numpy()
+    differing = np.flatnonzero(ga[:n_net].view(np.int32) != gb[:n_net].view(np.int32))
+    assert differing.size == 0 and np.abs(ga[:n_net]).max() > 0, f"{differing.size} network gradient entries differ, first at {differing[:4]}"
+    worst, st = grad_ratios(sides[0], f"aligned-{net}", *ref["f64"], *ref["f32"], keys=["std"])
+    assert worst <= C_GRAD
+    assert st["lr"] == whole.stats()[0]["lr"]
+
+
+# ---- 5. padding --------------------------------------------------------------------------------------------------------------------------------
+def test_padded_entries_of_records_and_gradients_are_exact_zeros(hip_lib):
+    """six_layers has no width that is a multiple of 16; the record buffers start out as NaN, so an entry the kernel does not write is caught too"""
+    c = PC.get_case("six_layers", 37, kl_of("six_layers", 37))
+    sides = shard_sides(hip_lib, c, [1, 36])
+    recs = torch.full((2, sides[0].h.shard_len), float("nan"), dtype=torch.float64, device=DEV)
+    for k, s in enumerate(sides):
+        s.h.shard_grad(s.batch, s.std, s.idx, 37, recs[k])
+    mask = record_mask(c.adims, c.cdims)
+    assert mask.size == sides[0].h.shard_len
+    r = recs.cpu().numpy()
+    assert np.isfinite(r).all() and not r[:, ~mask].any()
+    assert (r[:, mask] != 0).mean() > 0.9, "the real entries are populated"
+    for s in sides:
+        s.h.shard_reduce(recs, s.std)
+        g = s.h.export_padded("GRADS").cpu().numpy()
+        assert np.isfinite(g).all() and not g[~mask[:-4]].any() and (g[mask[:-4]] != 0).mean() > 0.9
+
+
+# ---- 6. whole sharded updates ------------------------------------------------------------------------------------------------------------------
+def run_sharded_update(lib, adims, cdims, state, shards, perms, epochs, n_mb):
+    """PPO.update's sharded loop with torch.cat as the collective: shards = [rollout], perms = [permutation of the shard's used rows]"""
+    mbs = [p.numel() // n_mb for p in perms]
+    sides = [Side(lib, adims, cdims, state, ro, m) for ro, m in zip(shards, mbs)]
+    perms = [p.to(torch.int32).to(DEV) for p in perms]
+    for s in sides:
+        s.h.reset_stats()
+    for _ in range(epochs):
+        for i in range(n_mb):
+            recs = torch.cat([s.h.shard_grad(s.batch, s.std, p[i * m:(i + 1) * m], sum(mbs)) for s, p, m in zip(sides, perms, mbs)]).view(len(sides), -1)
+            for s in sides:
+                s.h.shard_reduce(recs, s.std)
+                s.h.apply(s.std)
+    return sides
+
+
+@pytest.mark.parametrize("rows", [(37, 43), (21, 28)], ids=lambda v: "+".join(map(str, v)))
+def test_whole_sharded_update(hip_lib, rows):
+    """Two handles, 2 epochs x 2 mini-batches, on shards of 37 and 43 rows, and of 7 x 3 and 7 x 4 rows: the shards' mini-batches are unequal
+    (18 + 21 and 10 + 14 rows, the odd shards drop their permutation's last row) and weighted by rows.  The union permutation puts mini-batch i of both
+    shards into mini-batch i of tests/ppo_ref.update."""
+    epochs, n_mb = 2, 2
+    adims, cdims = PC.NETS["small"]
+    g = torch.Generator().manual_seed(7000 + rows[0])
+    state = PC.init_state(adims, cdims, g)
+    shards, perms = [], []
+    for k, n in enumerate(rows):
+        ro = PC.make_rollout(adims, cdims, state, n, "keep", 7001 + rows[0] + k)
+        used = n_mb * (n // n_mb)
+        perms.append(torch.randperm(used, generator=g))
+        for key in ro:
+            ro[key][used:] = float("nan")                      # rows beyond the permutation are dropped: nothing may read them
+        shards.append(ro)
+    mbs = [p.numel() // n_mb for p in perms]
+    union = {k: torch.cat([ro[k][:p.numel()] for ro, p in zip(shards, perms)]) for k in shards[0]}
+    offs = [0, perms[0].numel()]
+    perm_u = torch.cat([perms[k][i * mbs[k]:(i + 1) * mbs[k]] + offs[k] for i in range(n_mb) for k in range(2)])
+    assert perm_u.numel() == union["obs"].shape[0] == n_mb * sum(mbs) and sorted(perm_u.tolist()) == list(range(perm_u.numel()))
+    ref = {}
+    for prec, dt in (("f64", torch.float64), ("f32", torch.float32)):
+        m = R.make_model(adims, cdims, state, dt)
+        means, lr, _ = R.update(m, union, perm_u, epochs, n_mb)
+        ref[prec] = dict(params={k: p.detach().clone() for k, p in R.ordered_params(m)}, means=means, lr=lr)
+    a, b = run_sharded_update(hip_lib, adims, cdims, state, shards, perms, epochs, n_mb)
+    for which in ("PARAMS", "ADAM_M", "ADAM_V", "GRADS"):
+        assert np.array_equal(a.bits(which), b.bits(which)), which
+    (sta, raw_a), (stb, raw_b) = a.stats(), b.stats()
+    assert np.array_equal(raw_a.numpy().view(np.int64), raw_b.numpy().view(np.int64))
+    assert sta["step"] == epochs * n_mb == sta["count"] and sta["lr"] == pytest.approx(ref["f64"]["lr"], rel=1e-15)
+    got = a.split(a.h.export("PARAMS", a.std))
+    worst = 0.0
+    for k, p64 in ref["f64"]["params"].items():
+        err, yard = float((got[k] - p64).abs().max()), float((ref["f32"]["params"][k].double() - p64).abs().max())
+        print(f"RATIO shard update {rows} {k} {err / yard:.3f}")
+        worst = max(worst, err / yard)
+    print(f"RATIO shard worst update {rows} {worst:.3f}")
+    assert worst <= C_UPD
+    for got_s, want in zip((sta["value_loss"], sta["surrogate"], sta["entropy"]), ref["f64"]["means"]):
+        assert got_s == pytest.approx(want, rel=1e-5)          # reported means: a sanity bound on fp32 forward passes, not a precision claim
+    mask = real_entry_mask(adims, cdims)
+    for which in ("GRADS", "ADAM_M", "ADAM_V"):
+        assert not a.h.export_padded(which).cpu().numpy()[~mask].any(), which
+
+
+# ---- 7. reproducibility and status codes -------------------------------------------------------------------------------------------------------
+def test_sharded_gradients_are_bit_reproducible(hip_lib):
+    n = 2 * RCH + 37
+    c = PC.get_case("small", n, kl_of("small", n))
+    outs = []
+    for _ in range(2):
+        sides = shard_sides(hip_lib, c, [RCH + 5, RCH + 32])
+        records = sharded_grad(sides, n)
+        sides[1].h.apply(sides[1].std)
+        outs.append([records.cpu().numpy().view(np.int64), sides[1].h.export_padded("GRADS").cpu().numpy().view(np.int32), sides[1].bits("PARAMS"),
+                     sides[1].stats()[1].numpy().view(np.int64)])
+    for name, x, y in zip(("records", "grads", "params", "stats"), *outs):
+        assert np.array_equal(x, y), name
+
+
+def test_bad_shard_arguments_return_a_status_and_launch_nothing(hip_lib):
+    from go2_sim2real_locomotion_rl_amd.capi import C
+
+    BAD, OK, null, st = C["GO2SIM_E_BADARG"], C["GO2SIM_E_OK"], ctypes.c_void_p(0), ctypes.c_void_p(0)
+    c = PC.get_case("small", 16, "down")
+    side = shard_sides(hip_lib, c, [16])[0]
+    L, h, p = hip_lib, side.h.h, lambda t: ctypes.c_void_p(t.data_ptr())
+    sharded_grad([side], 16)
+    side.h.apply(side.std)
+    rec = torch.full((side.h.shard_len,), 7.0, dtype=torch.float64, device=DEV)
+    before = [side.bits(w) for w in ("PARAMS", "GRADS", "ADAM_M", "ADAM_V")] + [side.stats()[1].numpy().view(np.int64)]
+    grad, red, ln = L.fn("ppo_shard_grad"), L.fn("ppo_shard_reduce"), L.fn("ppo_shard_len")
+    LL = ctypes.c_longlong
+    b, out = ctypes.byref(side.batch), ctypes.c_size_t()
+    assert grad(h, b, p(side.std), p(side.idx), 16, LL(16), null, st) == BAD                    # a null record
+    assert grad(h, b, p(side.std), p(side.idx), 16, LL(15), p(rec), st) == BAD                  # n_rows_global < n_rows
+    assert grad(h, b, p(side.std), p(side.idx), 17, LL(40), p(rec), st) == BAD                  # n_rows > max_rows
+    assert grad(h, b, p(side.std), p(side.idx), 0, LL(16), p(rec), st) == BAD
+    assert grad(null, b, p(side.std), p(side.idx), 16, LL(16), p(rec), st) == BAD and grad(h, b, null, p(side.idx), 16, LL(16), p(rec), st) == BAD
+    assert grad(h, b, p(side.std), null, 16, LL(16), p(rec), st) == BAD and grad(h, null, p(side.std), p(side.idx), 16, LL(16), p(rec), st) == BAD
+    assert red(h, p(rec), 0, p(side.std), st) == BAD and red(h, p(rec), -1, p(side.std), st) == BAD      # n_records < 1
+    assert red(h, null, 1, p(side.std), st) == BAD and red(null, p(rec), 1, p(side.std), st) == BAD and red(h, p(rec), 1, null, st) == BAD
+    assert ln(null, ctypes.byref(out)) == BAD and ln(h, null) == BAD
+    assert ln(h, ctypes.byref(out)) == OK and out.value == side.h.shard_len
+    after = [side.bits(w) for w in ("PARAMS", "GRADS", "ADAM_M", "ADAM_V")] + [side.stats()[1].numpy().view(np.int64)]
+    for name, x, y in zip(("params", "grads", "m", "v", "stats"), before, after):
+        assert np.array_equal(x, y), f"a refused call must not have launched anything: {name}"
+    assert bool((rec == 7.0).all()), "a refused call must not have written the record"

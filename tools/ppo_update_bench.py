@@ -2,14 +2,18 @@
 """Times PPO.update() of the library against an eager-torch fp32 restatement of the same update on the same GPU, at the training shape of the
 walk task: T = 24 steps x B = 4096 envs, 49 / 104 observations, 16 actions, two 512-256-128 MLPs, 5 epochs x 4 mini-batches of 24 576 rows.
 
-    python tools/ppo_update_bench.py [--updates 5] [--warmup 2] [--envs 4096] [--steps 24]
+    python tools/ppo_update_bench.py [--updates 5] [--warmup 2] [--envs 4096] [--steps 24] [--shards N]
 
 Both sides update from the same rollout (collected once with the library's ActorCritic on random observations and rewards) and the same initial
 parameters.  Every shape is warmed up first; device events bracket `--updates` whole updates per side, the two sides alternating update by update so
 that other work on the machine hits both alike.  The HIP update ends in its one read of the statistics; the torch restatement reads kl_mean once per
 mini-batch, as rsl_rl's adaptive schedule does.  Prints one JSON line: both times per update, their ratio, the matrix work of an update computed
 from the shapes (forward, dW and dA of every layer, 2 x rows x in x out each; unpadded) and the fraction of the 157.3 TFLOPS fp32 matrix peak
-that the HIP update as a whole achieves (an end-to-end rate over peak, not a kernel's)."""
+that the HIP update as a whole achieves (an end-to-end rate over peak, not a kernel's).
+
+--shards N adds the sharded form of the update as a rank of an N-rank job runs it, in this one process: per mini-batch go2sim_ppo_shard_grad, go2sim_ppo_shard_reduce
+of N copies of the record (what the all-gather would deliver; the collective itself is NOT in the time), go2sim_ppo_apply, alternating with the plain update.
+It reports `sharded_ms_per_update` and the difference to `hip_ms_per_update`."""
 import argparse
 import json
 import os
@@ -96,6 +100,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=24)
+    ap.add_argument("--shards", type=int, default=0, help="also time shard_grad + shard_reduce of N copies of the record + apply per mini-batch")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ppo_update_bench needs a ROCm GPU: a time taken anywhere else says nothing")
@@ -126,21 +131,44 @@ def main():
     ref = TorchPPO(adims, cdims, state, dev)
     perm_gen = torch.Generator(device=dev).manual_seed(1)
     torch_update = lambda: ref.update(ro, torch.randperm(T * B // MINI_BATCHES * MINI_BATCHES, device=dev, generator=perm_gen))
+    sides = [("hip", alg.update), ("torch", torch_update)]
+    if args.shards > 0:
+        h, mbs, n_sh = alg._h, alg._mbs, args.shards
+        records = torch.empty(n_sh, h.shard_len, dtype=torch.float64, device=dev)
+        shard_perm_gen = torch.Generator(device=dev).manual_seed(2)
+
+        def sharded_update():                                                              # PPO._update_sharded with copies in the collective's place
+            perm = torch.randperm(MINI_BATCHES * mbs, device=dev, generator=shard_perm_gen).to(torch.int32)
+            h.reset_stats()
+            for _ in range(EPOCHS):
+                for i in range(MINI_BATCHES):
+                    h.shard_grad(alg._batch, policy.std, perm[i * mbs:(i + 1) * mbs], n_sh * mbs, records[0])
+                    records[1:] = records[0]
+                    h.shard_reduce(records, policy.std)
+                    h.apply(policy.std)
+            h.stats().cpu()                                                                # the update's one read
+
+        sides.append(("sharded", sharded_update))
     for _ in range(args.warmup):
-        alg.update(); torch_update()
+        for _, fn in sides:
+            fn()
     torch.cuda.synchronize()
-    ms = {"hip": 0.0, "torch": 0.0}
-    for _ in range(args.updates):                                                          # alternate the two sides update by update
-        for name, fn in (("hip", alg.update), ("torch", torch_update)):
+    ms = {name: 0.0 for name, _ in sides}
+    for _ in range(args.updates):                                                          # alternate the sides update by update
+        for name, fn in sides:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(); fn(); e1.record()
             torch.cuda.synchronize()
             ms[name] += e0.elapsed_time(e1)
     hip_ms, torch_ms = ms["hip"] / args.updates, ms["torch"] / args.updates
     flop = matrix_flop(adims, cdims, T * B // MINI_BATCHES) * EPOCHS * MINI_BATCHES
+    extra = {}
+    if args.shards > 0:
+        sh_ms = ms["sharded"] / args.updates
+        extra = {"shards": args.shards, "sharded_ms_per_update": round(sh_ms, 3), "sharded_minus_hip_ms": round(sh_ms - hip_ms, 3)}
     print(json.dumps({"tool": "ppo_update_bench", "envs": B, "steps": T, "epochs": EPOCHS, "mini_batches": MINI_BATCHES, "updates_timed": args.updates,
                       "hip_ms_per_update": round(hip_ms, 3), "torch_eager_ms_per_update": round(torch_ms, 3), "hip_over_torch": round(hip_ms / torch_ms, 3),
-                      "matrix_flop_per_update": flop, "hip_fraction_of_157.3_tflops": round(flop / (hip_ms * 1e-3) / PEAK_FP32_MATRIX, 4)}))
+                      "matrix_flop_per_update": flop, "hip_fraction_of_157.3_tflops": round(flop / (hip_ms * 1e-3) / PEAK_FP32_MATRIX, 4), **extra}))
 
 
 if __name__ == "__main__":

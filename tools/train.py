@@ -1,0 +1,91 @@
+#!/usr/bin/env python
+"""Trains a Go2 policy with the library's runner, on one GPU or sharded over the ranks of a ``torchrun`` job.
+
+    python tools/train.py --task walk --envs 4096 --iterations 1000 --log-dir logs/go2-walk
+    torchrun --nproc-per-node 8 tools/train.py --task walk --envs 4096 --iterations 1000 --log-dir logs/go2-walk
+
+--envs is the env count PER RANK.  Under torchrun every rank builds its shard of the envs (``Go2Env(..., shared_globals=True)``: one curriculum, one
+set of global randomisation draws) and an OnPolicyRunner; the runners train ONE policy (gradients summed in rank order, DESIGN.md "(e) Multi-GPU"),
+rank 0 writes the checkpoints and prints one JSON line per iteration.  The train_cfg is the reference's for the task, read from the cfgs file of a
+reference run (--cfgs logs/<exp>/cfgs.pkl) or, by default, from the copy of it this repository keeps as a test fixture.
+GO2SIM_BENCH_REHEARSAL=1 puts all ranks on GPU 0 with a gloo group, as bench.py does: the call sequence on a one-GPU box, not the transport."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+TASKS = ("walk", "stairs", "crouch", "jump")
+
+
+def task_cfgs(task):
+    from go2_sim2real_locomotion_rl_amd import get_crouch_cfgs, get_jump_cfgs, get_stair_cfgs, get_walk_cfgs
+
+    return {"walk": get_walk_cfgs, "stairs": get_stair_cfgs, "crouch": get_crouch_cfgs, "jump": get_jump_cfgs}[task]()
+
+
+def train_cfg_of(task, cfgs_path=None):
+    if cfgs_path:
+        from go2_sim2real_locomotion_rl_amd import load_cfgs
+
+        return load_cfgs(cfgs_path)[4]
+    return json.load(open(os.path.join(ROOT, "tests", "golden", f"ref_cfgs_{task}.json")))["train_cfg"]
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--task", choices=TASKS, default="walk")
+    ap.add_argument("--envs", type=int, default=4096, help="environments per rank")
+    ap.add_argument("--iterations", type=int, default=1000)
+    ap.add_argument("--log-dir", default=None, help="checkpoints go here (rank 0); none are written without it")
+    ap.add_argument("--cfgs", default=None, help="cfgs.pkl of a reference run: its train_cfg replaces the task's default")
+    ap.add_argument("--steps-per-env", type=int, default=None, help="overrides train_cfg['num_steps_per_env']")
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--resume", default=None, help="checkpoint to load on every rank before training")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/train.py needs a ROCm GPU (the product has no CPU fallback)")
+
+    world, rank, local_rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
+    rehearsal = os.environ.get("GO2SIM_BENCH_REHEARSAL", "0") == "1"
+    if rehearsal:
+        local_rank = 0
+    torch.cuda.set_device(local_rank)
+    device = torch.device("cuda", local_rank)
+    if world > 1:
+        import torch.distributed as dist
+
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        if rehearsal:
+            dist.init_process_group(backend="gloo")
+        else:
+            dist.init_process_group(backend="nccl", device_id=device)
+    try:
+        from go2_sim2real_locomotion_rl_amd import Go2Env, OnPolicyRunner, init
+        from go2_sim2real_locomotion_rl_amd.distributed import shard_seed
+
+        seed = shard_seed(args.seed, rank)
+        init(seed=seed, device_index=local_rank)
+        env = Go2Env(args.envs, *task_cfgs(args.task), seed=seed, device=device, shared_globals=world > 1)
+        cfg = train_cfg_of(args.task, args.cfgs)
+        cfg["seed"] = args.seed
+        if args.steps_per_env:
+            cfg["num_steps_per_env"] = args.steps_per_env
+        runner = OnPolicyRunner(env, cfg, log_dir=args.log_dir, device=device)      # picks up the default process group
+        if args.resume:
+            runner.load(args.resume)
+        log = runner.learn(args.iterations, init_at_random_ep_len=True)
+        if rank == 0:
+            for entry in log:
+                print(json.dumps(dict(entry, world=world, envs=args.envs * world)), flush=True)
+    finally:
+        if world > 1:
+            dist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main()
