@@ -66,6 +66,13 @@ class PpoBatch(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in FIELDS]
 
 
+class PpoMirror(ctypes.Structure):
+    """go2sim_ppo_mirror_t: three signed permutations as device tables, the two flags and the mirror-loss coefficient"""
+    TABLES = ("obs_src", "obs_sign", "critic_src", "critic_sign", "action_src", "action_sign")
+    _fields_ = [(n, ctypes.c_void_p) for n in TABLES] + [("use_data_augmentation", ctypes.c_int), ("use_mirror_loss", ctypes.c_int),
+                                                         ("mirror_loss_coeff", ctypes.c_double)]
+
+
 class EnvGlobals(ctypes.Structure):
     _fields_ = [
         ("level", ctypes.c_double), ("timeout_rate_ema", ctypes.c_double), ("tracking_ema", ctypes.c_double), ("fall_rate_ema", ctypes.c_double),

@@ -69,6 +69,57 @@ def is_base_env_cfg(env_cfg, obs_cfg):
     return not walk_family and obs_cfg["num_obs"] == 45 and env_cfg["num_actions"] == 12
 
 
+def mirror_tables(env_cfg, obs_cfg):
+    """The left-right mirror (reflection in the robot's x-z plane) of the observation and action layout these cfg dicts give an env, as three signed
+    permutations ``{"policy": (src, sign), "critic": (src, sign), "actions": (src, sign)}`` with ``(M x)[j] = sign[j] * x[src[j]]`` (int32 / float32
+    CPU tensors).  Joints and legs are ordered FR, FL, RR, RL: the mirror swaps FR <-> FL and RR <-> RL and hip angles change sign; polar vectors
+    take (+, -, +), the angular velocity (-, +, -), the commands (vx, vy, wz) (+, -, -); scalars are fixed points; height-scan point
+    ix * ny + iy maps to ix * ny + (ny - 1 - iy)."""
+    num_actions, num_obs, num_priv = env_cfg["num_actions"], obs_cfg["num_obs"], obs_cfg.get("num_privileged_obs")
+    base = is_base_env_cfg(env_cfg, obs_cfg)
+    leg = [1, 0, 3, 2]
+    joints = ([3 * leg[j // 3] + j % 3 for j in range(12)], [-1.0 if j % 3 == 0 else 1.0 for j in range(12)])
+    joint_factors = (joints[0], [1.0] * 12)                              # kp / kd / motor strength: swap the legs, keep the sign
+    legs = (leg, [1.0] * 4)
+    polar, axial, cmd = ([0, 1, 2], [1.0, -1.0, 1.0]), ([0, 1, 2], [-1.0, 1.0, -1.0]), ([0, 1, 2], [1.0, -1.0, -1.0])
+    scalar = ([0], [1.0])
+
+    def cat(blocks):
+        src, sign = [], []
+        for b_src, b_sign in blocks:
+            src += [len(sign) + k for k in b_src]
+            sign += list(b_sign)
+        return src, sign
+
+    if num_actions not in (12, 16):
+        raise Go2SimError(f"no mirror for {num_actions} actions (12 joint targets, optionally 4 per-leg stiffness actions)")
+    actions = cat([joints] + ([legs] if num_actions == 16 else []))
+    obs = cat([axial, polar, cmd, joints, joints, actions])              # angular velocity, gravity, commands, dof pos, dof vel, actions
+    if base or num_priv is None:
+        critic = obs
+    else:
+        # base_lin_vel, friction, kp / kd / motor-strength factors, mass shift, com shift, leg mass shifts, gravity offset, push force, delay
+        blocks = [obs, polar, scalar, joint_factors, joint_factors, joint_factors, scalar, polar, legs, polar, polar, scalar]
+        extra = num_priv - (num_obs + 55)
+        terrain = env_cfg.get("terrain") or {}
+        if extra > 0 and terrain.get("enabled", False):                   # the stair layout: terrain row, then the height scan
+            hs = terrain.get("height_scan", {})
+            nx, ny = int(hs.get("num_x", 11)), int(hs.get("num_y", 7))
+            yr = hs.get("y_range", [-0.3, 0.3])
+            if float(yr[0]) != -float(yr[1]):
+                raise Go2SimError(f"the height scan's y_range {list(yr)} is not symmetric about 0: the scan has no mirror")
+            blocks += [scalar, ([ix * ny + (ny - 1 - iy) for ix in range(nx) for iy in range(ny)], [1.0] * (nx * ny))]
+        elif extra > 0:                                                    # a wider critic input without terrain holds zeros there
+            blocks.append((list(range(extra)), [1.0] * extra))
+        critic = cat(blocks)
+    out = {}
+    for key, (src, sign), width in zip(("policy", "critic", "actions"), (obs, critic, actions), (num_obs, num_obs if base or num_priv is None else num_priv, num_actions)):
+        if len(src) != width:
+            raise Go2SimError(f"mirror table {key!r} has {len(src)} entries, the layout's width is {width}")
+        out[key] = (torch.tensor(src, dtype=torch.int32), torch.tensor(sign, dtype=torch.float32))
+    return out
+
+
 class Go2Env:
     def __init__(self, num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg, show_viewer=False, *, seed=None, device=None,
                  freeze_curriculum=False, log_extras=True, errno_poll_every=5, shared_globals=False):
@@ -214,6 +265,11 @@ class Go2Env:
     def get_observations(self):
         self.extras["observations"]["critic"] = self.privileged_obs_buf if self.num_privileged_obs else self.obs_buf
         return self.obs_buf, self.extras
+
+    def mirror_tables(self):
+        """The left-right mirror of this env's observation and action layout (module function ``mirror_tables``), for
+        ``PPO(symmetry_cfg={"mirror_tables": env.mirror_tables(), ...})``."""
+        return mirror_tables(self.env_cfg, self.obs_cfg)
 
     def get_privileged_observations(self):
         return self.privileged_obs_buf if self.num_privileged_obs is not None else None

@@ -17,12 +17,16 @@ Under ``torchrun`` (``PPO(..., group=torch.distributed.group.WORLD)``) every ran
 mini-batch each rank writes its shard's contribution as a float64 record (go2sim_ppo_shard_grad), the records are all-gathered
 (distributed.allgather_records) and every rank adds them in rank order (go2sim_ppo_shard_reduce) before the usual go2sim_ppo_apply, so the ranks'
 parameters stay bit-identical without ever being re-broadcast.
+
+Left-right symmetry (rsl_rl's ``symmetry_cfg``): ``PPO(..., symmetry_cfg={"use_data_augmentation": True, "use_mirror_loss": True,
+"mirror_loss_coeff": 0.5, "mirror_tables": env.mirror_tables()})``.  The mirror is three signed permutations given as tables (Go2Env.mirror_tables);
+the kernels read every mini-batch row a second time through them, no mirrored copy is made (include/go2sim_train.h).
 """
 import ctypes
 
 import torch
 
-from .capi import C, Go2SimError, PpoBatch, PpoCfg, load_hip_lib
+from .capi import C, Go2SimError, PpoBatch, PpoCfg, PpoMirror, load_hip_lib
 from .distributed import allgather_records, broadcast_from_rank0, is_multi, shard_seed
 from .rollout import RolloutStorage
 
@@ -65,6 +69,8 @@ class PpoHandle:
         lib.check(lib.fn("ppo_shard_len")(self.h, ctypes.byref(n)), "ppo_shard_len")
         self.shard_len = n.value
         self._stats = torch.zeros(C["GO2SIM_PPO_N_STATS"], dtype=torch.float64, device=self.device)
+        self._sym = torch.zeros(1, dtype=torch.float64, device=self.device)
+        self.mirror = None
 
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -89,6 +95,37 @@ class PpoHandle:
         if records.dtype != torch.float64 or not records.is_contiguous() or records.numel() % self.shard_len or not records.is_cuda:
             raise Go2SimError(f"records must be a contiguous float64 device tensor [n][{self.shard_len}]")
         self.L.check(self.L.fn("ppo_shard_reduce")(self.h, _p(records), ctypes.c_int(records.numel() // self.shard_len), _p(std), self._stream()), "ppo_shard_reduce")
+
+    def set_mirror(self, tables, use_data_augmentation=False, use_mirror_loss=False, mirror_loss_coeff=0.0):
+        """tables: {"policy": (src, sign), "critic": (src, sign), "actions": (src, sign)}, each a signed permutation (M x)[j] = sign[j] x[src[j]], or None
+        to return to the plain update.  Waits for the device (the library validates the tables on the host); shard_len changes with it."""
+        if tables is None:
+            self.L.check(self.L.fn("ppo_set_mirror")(self.h, ctypes.c_void_p(0), self._stream()), "ppo_set_mirror")
+            self.mirror = None
+        else:
+            m, keep = PpoMirror(), []
+            for key, name in (("policy", "obs"), ("critic", "critic"), ("actions", "action")):
+                if key not in tables:
+                    raise Go2SimError(f"mirror_tables needs the entries 'policy', 'critic' and 'actions'; {key!r} is missing")
+                src, sign = tables[key]
+                src = torch.as_tensor(src).to(device=self.device, dtype=torch.int32).contiguous()
+                sign = torch.as_tensor(sign).to(device=self.device, dtype=torch.float32).contiguous()
+                width = {"policy": self.actor.dims[0], "critic": self.critic.dims[0], "actions": self.actor.dims[-1]}[key]
+                if src.numel() != width or sign.numel() != width:
+                    raise Go2SimError(f"mirror table {key!r} has {src.numel()} / {sign.numel()} entries, the network's width is {width}")
+                setattr(m, name + "_src", src.data_ptr()); setattr(m, name + "_sign", sign.data_ptr())
+                keep += [src, sign]
+            m.use_data_augmentation, m.use_mirror_loss, m.mirror_loss_coeff = int(bool(use_data_augmentation)), int(bool(use_mirror_loss)), float(mirror_loss_coeff)
+            self.L.check(self.L.fn("ppo_set_mirror")(self.h, ctypes.byref(m), self._stream()), "ppo_set_mirror")      # the library has its own copy on return
+            self.mirror = dict(use_data_augmentation=bool(use_data_augmentation), use_mirror_loss=bool(use_mirror_loss), mirror_loss_coeff=float(mirror_loss_coeff))
+        n = ctypes.c_size_t()
+        self.L.check(self.L.fn("ppo_shard_len")(self.h, ctypes.byref(n)), "ppo_shard_len")
+        self.shard_len = n.value
+
+    def symmetry_loss(self):
+        """float64 device tensor [1]: mean of the mirror loss L_sym over the mini-batches since the last reset; no synchronisation"""
+        self.L.check(self.L.fn("ppo_symmetry_loss")(self.h, _p(self._sym), self._stream()), "ppo_symmetry_loss")
+        return self._sym
 
     def apply(self, std):
         self.L.check(self.L.fn("ppo_apply")(self.h, _p(std), self._stream()), "ppo_apply")
@@ -165,12 +202,14 @@ def flatten(sd, adims, cdims):
 
 class PPO:
     def __init__(self, policy, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95, value_loss_coef=1.0, entropy_coef=0.0,
-                 learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device=None, *, seed=1, group=None, **kwargs):
+                 learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device=None, *, seed=1, group=None, symmetry_cfg=None,
+                 **kwargs):
         if schedule not in ("adaptive", "fixed"):
             raise Go2SimError(f"schedule must be 'adaptive' or 'fixed', got {schedule!r}")
         unknown = {k: v for k, v in kwargs.items() if k not in ("class_name", "normalize_advantage_per_mini_batch") and v is not None}
         if unknown or kwargs.get("normalize_advantage_per_mini_batch"):
-            raise Go2SimError(f"go2sim's PPO does not implement {sorted(unknown) or ['normalize_advantage_per_mini_batch']} (RND and symmetry are out of scope)")
+            raise Go2SimError(f"go2sim's PPO does not implement {sorted(unknown) or ['normalize_advantage_per_mini_batch']} (RND and symmetry are out of scope other than symmetry_cfg with mirror_tables)")
+        self.symmetry = self._check_symmetry_cfg(symmetry_cfg)
         self.policy = self.actor_critic = policy
         self.device = policy.device if device is None else torch.device(device)
         self.num_learning_epochs, self.num_mini_batches = int(num_learning_epochs), int(num_mini_batches)
@@ -185,6 +224,23 @@ class PPO:
         self._gen = torch.Generator(device=self.device).manual_seed(shard_seed(seed, self.rank))
         self.storage = self._h = None
         self.last_stats = None
+        self.symmetry_loss = None
+
+    @staticmethod
+    def _check_symmetry_cfg(cfg):
+        """rsl_rl's symmetry_cfg with the mirror as tables: -> dict(tables, use_data_augmentation, use_mirror_loss, mirror_loss_coeff) or None"""
+        if not cfg:
+            return None
+        known = {"use_data_augmentation", "use_mirror_loss", "mirror_loss_coeff", "data_augmentation_func", "mirror_tables"}
+        if set(cfg) - known:
+            raise Go2SimError(f"symmetry_cfg: unknown entries {sorted(set(cfg) - known)}")
+        if cfg.get("data_augmentation_func") is not None:
+            raise Go2SimError("symmetry_cfg['data_augmentation_func']: a Python callable cannot run inside the update's kernels; give the mirror as "
+                              "symmetry_cfg['mirror_tables'] = {'policy': (src, sign), 'critic': (src, sign), 'actions': (src, sign)} (Go2Env.mirror_tables())")
+        if cfg.get("mirror_tables") is None:
+            raise Go2SimError("symmetry_cfg needs 'mirror_tables' (Go2Env.mirror_tables())")
+        return dict(tables=cfg["mirror_tables"], use_data_augmentation=bool(cfg.get("use_data_augmentation", False)),
+                    use_mirror_loss=bool(cfg.get("use_mirror_loss", False)), mirror_loss_coeff=float(cfg.get("mirror_loss_coeff", 0.0)))
 
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
         T, B, dev = int(num_transitions_per_env), int(num_envs), self.device
@@ -197,6 +253,8 @@ class PPO:
         if self._mbs < 1:
             raise Go2SimError("fewer rows than mini-batches")
         self._h = self.policy.attach_trainer(self._mbs, **self._hyper)
+        if self.symmetry is not None:                                   # before the record below is sized: a record grows by the mirror-loss sum
+            self._h.set_mirror(**self.symmetry)
         self._batch = make_batch(obs=self.obs, critic_obs=self.critic_obs, actions=self.actions, target_values=self.storage.values, returns=self.storage.returns,
                                  advantages=self.storage.advantages, old_log_prob=self.old_log_prob, old_mu=self.old_mu, old_sigma=self.old_sigma)
         if self.group is not None:
@@ -235,7 +293,12 @@ class PPO:
             self._h.update(self._batch, self.policy.std, perm, self.T * self.B, self.num_learning_epochs, self.num_mini_batches)
         else:
             self._update_sharded(perm)
-        s = self._h.stats().cpu()                                          # the update's only host synchronisation
+        if self.symmetry is not None:                                      # rides along in the one read
+            s = torch.cat([self._h.stats(), self._h.symmetry_loss()]).cpu()
+            self.symmetry_loss = float(s[-1])
+            s = s[:-1]
+        else:
+            s = self._h.stats().cpu()                                      # the update's only host synchronisation
         self.last_stats = s
         self.learning_rate = float(s[C["GO2SIM_PPO_ST_LR"]])
         self.t = 0

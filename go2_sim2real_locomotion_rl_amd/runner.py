@@ -34,6 +34,9 @@ class OnPolicyRunner:
         alg_cfg, pol_cfg = dict(train_cfg["algorithm"]), dict(train_cfg["policy"])
         if alg_cfg.pop("class_name", "PPO") != "PPO" or pol_cfg.pop("class_name", "ActorCritic") != "ActorCritic":
             raise Go2SimError("go2sim implements class_name PPO / ActorCritic")
+        sym = alg_cfg.get("symmetry_cfg")
+        if sym and sym.get("mirror_tables") is None and sym.get("data_augmentation_func") is None:
+            alg_cfg["symmetry_cfg"] = dict(sym, mirror_tables=env.mirror_tables())     # the env knows its own observation layout
         obs, extras = env.get_observations()
         critic_obs = extras["observations"].get("critic", obs)
         seed = int(train_cfg.get("seed", 1) or 1)
@@ -82,6 +85,8 @@ class OnPolicyRunner:
             self.current_learning_iteration = it + 1
             log.append({"iteration": it, "mean_reward": self._last_means[0], "mean_episode_length": self._last_means[1], "value_loss": value_loss,
                         "surrogate_loss": surrogate_loss, "entropy": entropy, "learning_rate": alg.learning_rate})
+            if alg.symmetry is not None:
+                log[-1]["symmetry_loss"] = alg.symmetry_loss
             if self.log_dir is not None and self.save_interval > 0 and (it + 1) % self.save_interval == 0:
                 self.save(os.path.join(self.log_dir, f"model_{it + 1}.pt"))
         if self.log_dir is not None:

@@ -28,6 +28,23 @@
  *                  than one entry is at 2.79)
  *   C_UPD  = 8    (worst measured: 3.79, 2 epochs x 2 mini-batches of 37 rows)
  * Rows are reduced in chunks of GO2SIM_PPO_ROW_CHUNK: a chain of the matrix instruction never runs over more than a quarter of a chunk.
+ *
+ * Mirror symmetry (go2sim_ppo_set_mirror; rsl_rl 2.2.4's symmetry_cfg with the mirror given as tables).  A mirror is three signed permutations
+ * M_o, M_c, M_a for the actor input, the critic input and the actions, each acting as (M x)[j] = sign[j] x[src[j]].  A mini-batch of n rows read
+ * through idx becomes 2 n rows: rows 0 .. n-1 are the originals, row n + r is the mirror of row r: obs M_o obs_r, critic obs M_c cobs_r, actions
+ * M_a a_r, and old_log_prob, advantages, returns and target_values of row r unchanged.  The 2 n rows run through the row chunks as one sequence.
+ *   use_data_augmentation: surrogate and value_loss are means over all 2 n rows (row weight 1 / (2 n)), d loss / d sigma takes both halves;
+ *     kl_mean, and the learning-rate rule that reads it, over the n original rows only; entropy does not depend on rows.
+ *   use_mirror_loss: L_sym = mean over r < n, a < A of (mu(M_o obs_r)[a] - (M_a mu(obs_r))[a])^2;  loss += mirror_loss_coeff L_sym.  The target
+ *     M_a mu(obs_r) is detached: the gradient enters through the mirrored rows' mu only, coeff 2 (mu' - target) / (n A).
+ *   mirror loss without augmentation: forward and backward still run on 2 n rows, the mirrored rows carry no PPO weight, the originals weigh 1 / n;
+ *     surrogate, value_loss and kl are means over n.
+ *   both flags off: gradients, statistics and parameters have the bits of a handle without tables.
+ * L_sym is computed and reported (go2sim_ppo_symmetry_loss) whenever a mirror is set; it is added to the loss only under use_mirror_loss.
+ * No mirrored copy of a batch array is written anywhere and the batch arrays are never modified: the signed gather sits where rows are read
+ * through idx already.  All sums stay float64 in a fixed order.  The bounds above hold with the mirror on; worst measured over
+ * tests/test_ppo_sym_gpu.py on the MI355X: 1.77 against C_GRAD (17 rows, mirror loss only; sharded 1.29), 1.00 against C_UPD (2 epochs x 2 mini-batches of
+ * 37 rows, both flags).
  */
 #ifndef GO2SIM_TRAIN_H
 #define GO2SIM_TRAIN_H
@@ -66,6 +83,20 @@ typedef struct go2sim_ppo_batch {
   const float* old_sigma;      /* [rows][A] */
 } go2sim_ppo_batch_t;
 
+/* Three signed permutations as device tables (int32 src, float sign of +1 or -1) of the actor's input width, the critic's input width and
+ * n_actions entries, the two flags and the coefficient of the law above. */
+typedef struct go2sim_ppo_mirror {
+  const int32_t* obs_src;
+  const float* obs_sign;
+  const int32_t* critic_src;
+  const float* critic_sign;
+  const int32_t* action_src;
+  const float* action_sign;
+  int use_data_augmentation;
+  int use_mirror_loss;
+  double mirror_loss_coeff;
+} go2sim_ppo_mirror_t;
+
 enum go2sim_ppo_vec { GO2SIM_PPO_PARAMS = 0, GO2SIM_PPO_GRADS, GO2SIM_PPO_ADAM_M, GO2SIM_PPO_ADAM_V };
 /* go2sim_ppo_stats writes GO2SIM_PPO_N_STATS float64: means of value loss, surrogate loss and entropy over the mini-batches since the last reset,
  * kl_mean of the last mini-batch, learning rate, total gradient norm of the last apply, optimizer step count, mini-batches since the last reset */
@@ -77,6 +108,14 @@ enum go2sim_ppo_stat { GO2SIM_PPO_ST_VALUE_LOSS = 0, GO2SIM_PPO_ST_SURROGATE, GO
  * actor's last width, the critic's last width must be 1. */
 int go2sim_ppo_create(go2sim_mlp_t* actor, go2sim_mlp_t* critic, int n_actions, const go2sim_ppo_cfg_t* cfg, int max_rows_per_minibatch, go2sim_ppo_t** out);
 int go2sim_ppo_destroy(go2sim_ppo_t* h);
+
+/* Sets (or, with NULL, removes) the mirror.  A set-up call like go2sim_ppo_create: it reads the tables back to validate them on the host (indices in
+ * range, each src a permutation, signs +1 or -1; GO2SIM_E_BADARG otherwise, the handle unchanged), copies them into the handle and sizes the
+ * workspaces for 2 x max_rows_per_minibatch, so it waits for the device.  The optimizer state, the learning rate and the running sums are kept.
+ * Every call below honours the mirror.  With a mirror set a shard record grows by one entry (go2sim_ppo_shard_len). */
+int go2sim_ppo_set_mirror(go2sim_ppo_t* h, const go2sim_ppo_mirror_t* mirror, void* stream);
+/* out_dev: one float64 on the device, the mean of L_sym over the mini-batches since the last reset (0 without a mirror), written in stream order */
+int go2sim_ppo_symmetry_loss(go2sim_ppo_t* h, double* out_dev, void* stream);
 
 /* Forward, loss head and backward of one mini-batch: rows idx[0 .. n_rows) of `batch` (int32 device indices).  Leaves the gradients on the device,
  * applies the learning-rate rule to the device-side learning rate and adds this mini-batch to the running sums of the three reported means. */
@@ -91,6 +130,8 @@ int go2sim_ppo_minibatch_grad(go2sim_ppo_t* h, const go2sim_ppo_batch_t* batch, 
  *   [nA + nC, + Apad)        d loss / d sigma[a] summed over the head's workgroups in workgroup order, WITHOUT the entropy term (it does not depend on
  *                            rows: the reduction adds it once); entries a >= n_actions are zero
  *   [nA + nC + Apad, + 4)    the shard's unnormalised sums over rows of surrogate, value loss and kl, then n_rows as a double
+ *   with a mirror set, one more entry: the shard's unnormalised sum over mirrored rows and actions of (mu' - target)^2; under augmentation the sums
+ *   of surrogate and value loss run over originals and mirrors (divided by twice the row count), n_rows stays the count of original rows
  * Padded entries are exact zeros.  With one record and n_rows_global = n_rows, shard_grad + shard_reduce leave the handle in the state of
  * go2sim_ppo_minibatch_grad bit for bit.
  *

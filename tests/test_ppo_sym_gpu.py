@@ -1,0 +1,300 @@
+"""The HIP library's PPO update with a mirror set (go2sim_ppo_set_mirror, include/go2sim_train.h) against the torch float64 reference of
+tests/ppo_sym_ref.py over the cases of tests/ppo_sym_cases.py, with the float32 torch evaluation of the same expressions as the yardstick and under
+the header's own bounds:
+  gradients, per parameter tensor, the loss scalars, kl_mean and L_sym:  max|g - g64| <= C_GRAD max(max|g32 - g64|, 2^-24 max|g64|),  C_GRAD = 16
+  whole updates, per tensor:                                             max|p - p64| <= C_UPD max|p32 - p64|,                        C_UPD = 8
+Every test prints its ratios before it asserts (worst values: include/go2sim_train.h and DESIGN.md "PPO update").  Then the bit-level promises: both
+flags off is the plain update, the batch arrays are never written, the same update twice gives the same bits, one shard record reduced alone is
+go2sim_ppo_minibatch_grad; the status codes; the runner end to end."""
+import copy
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import ppo_cases as PC
+import ppo_ref as R
+import ppo_sym_cases as SC
+import ppo_sym_ref as SR
+
+pytestmark = pytest.mark.gpu
+
+C_GRAD = 16
+C_UPD = 8
+EPS = 2.0 ** -24
+DEV = "cuda:0"
+
+
+class Side:
+    """The two networks, std, the rollout and one go2sim_ppo handle on the GPU; `mirror`: None or (tables, augmentation, mirror loss, coefficient)"""
+
+    def __init__(self, lib, adims, cdims, state, rollout, max_rows, mirror=None, idx=None):
+        from go2_sim2real_locomotion_rl_amd.policy import Mlp, flatten_sequential
+        from go2_sim2real_locomotion_rl_amd.ppo import PpoHandle, make_batch
+
+        self.adims, self.cdims = adims, cdims
+        self.actor = Mlp(lib, adims, flatten_sequential(state, "actor", len(adims) - 1)[0])
+        self.critic = Mlp(lib, cdims, flatten_sequential(state, "critic", len(cdims) - 1)[0])
+        self.std = state["std"].to(DEV).clone()
+        self.ro = {k: v.to(DEV).contiguous() for k, v in rollout.items()}
+        self.batch = make_batch(**self.ro)
+        self.h = PpoHandle(lib, self.actor, self.critic, adims[-1], max_rows, clip_param=R.HP["clip_param"], desired_kl=R.HP["desired_kl"],
+                           entropy_coef=R.HP["entropy_coef"], learning_rate=R.HP["learning_rate"], max_grad_norm=R.HP["max_grad_norm"],
+                           value_loss_coef=R.HP["value_loss_coef"], use_clipped_value_loss=True, adaptive=True)
+        if mirror is not None:
+            self.h.set_mirror(mirror[0], *mirror[1:])
+        self.idx = None if idx is None else idx.to(torch.int32).to(DEV).contiguous()
+
+    def split(self, flat):
+        from go2_sim2real_locomotion_rl_amd.ppo import unflatten
+
+        return {k: v.double() for k, v in unflatten(flat.cpu(), self.adims, self.cdims).items()}
+
+    def scalars(self):
+        s = self.h.stats().cpu()
+        return dict(value_loss=float(s[0]), surrogate=float(s[1]), entropy=float(s[2]), kl_mean=float(s[3]), lr=float(s[4]), step=int(s[6]), count=int(s[7]),
+                    symmetry=float(self.h.symmetry_loss().cpu()[0]))
+
+    def bits(self):
+        out = [self.h.export(w, self.std).cpu().numpy().view(np.int32) for w in ("PARAMS", "ADAM_M", "ADAM_V", "GRADS")]
+        return out + [self.h.stats().cpu().numpy().view(np.int64)]
+
+
+def case_side(lib, c, flags, idx=None, max_rows=None):
+    mirror = None if flags is None else (c.tables,) + (SC.FLAGS[flags] if isinstance(flags, str) else flags)
+    idx = c.idx if idx is None else idx
+    return Side(lib, c.adims, c.cdims, c.state, c.rollout, idx.numel() if max_rows is None else max_rows, mirror, idx)
+
+
+def grad_ratios(side, tag, ref):
+    (g64, s64), (g32, s32) = ref["f64"], ref["f32"]
+    got, st = side.split(side.h.export("GRADS")), side.scalars()
+    worst = 0.0
+    for k in g64:
+        err, yard = float((got[k] - g64[k]).abs().max()), max(float((g32[k].double() - g64[k]).abs().max()), EPS * float(g64[k].abs().max()))
+        print(f"RATIO sym grad {tag} {k} {err / yard:.3f}")
+        worst = max(worst, err / yard)
+    for k in SR.SCALARS:
+        err, yard = abs(st[k] - s64[k]), max(abs(s32[k] - s64[k]), EPS * abs(s64[k]))
+        print(f"RATIO sym scalar {tag} {k} {err / yard:.3f}")
+        worst = max(worst, err / yard)
+    print(f"RATIO sym worst {tag} {worst:.3f}")
+    return worst, st
+
+
+# ---- 1. gradients and scalars under every flag combination ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("flags", sorted(SC.FLAGS))
+@pytest.mark.parametrize("shape", SC.SHAPES, ids=lambda s: f"{s[0]}-{s[1]}")
+def test_mirror_gradients_and_scalars(hip_lib, shape, flags):
+    c = SC.get_case(*shape)
+    ref = c.ref(flags)
+    side = case_side(hip_lib, c, flags)
+    side.h.minibatch_grad(side.batch, side.std, side.idx)
+    worst, st = grad_ratios(side, f"{shape[0]}-{shape[1]}-{flags}", ref)
+    assert worst <= C_GRAD
+    assert st["count"] == 1 and st["lr"] == pytest.approx(R.lr_rule(R.HP["learning_rate"], ref["f64"][1]["kl_mean"], R.HP["desired_kl"]), rel=1e-15)
+    padded = side.h.export_padded("GRADS").cpu().numpy()
+    assert np.isfinite(padded).all()
+    if flags == "both":                                        # the mirror loss moves the gradient: the flag is not a no-op
+        aug = c.ref("augment")["f64"][0]
+        assert any(not torch.equal(aug[k], ref["f64"][0][k]) for k in aug)
+
+
+def test_whole_update_with_mirror(hip_lib):
+    u = SC.get_update_case("both")
+    side = Side(hip_lib, u["adims"], u["cdims"], u["state"], u["rollout"], u["rows"] // u["n_mb"], (u["tables"],) + SC.FLAGS["both"])
+    side.h.update(side.batch, side.std, u["perm"].to(DEV), u["rows"], u["epochs"], u["n_mb"])
+    got, st = side.split(side.h.export("PARAMS", side.std)), side.scalars()
+    worst = 0.0
+    for k, p64 in u["f64"]["params"].items():
+        err, yard = float((got[k] - p64).abs().max()), float((u["f32"]["params"][k].double() - p64).abs().max())
+        print(f"RATIO sym update {k} {err / yard:.3f}")
+        worst = max(worst, err / yard)
+    print(f"RATIO sym worst update {worst:.3f}")
+    assert worst <= C_UPD
+    assert st["step"] == u["epochs"] * u["n_mb"] and st["count"] == st["step"] and st["lr"] == pytest.approx(u["f64"]["lr"], rel=1e-15)
+    for got_s, want in zip((st["value_loss"], st["surrogate"], st["entropy"], st["symmetry"]), u["f64"]["means"]):
+        assert got_s == pytest.approx(want, rel=1e-5)          # the reported means, as tests/test_ppo_gpu.py holds its three
+
+
+# ---- 2. the bit-level promises -------------------------------------------------------------------------------------------------------------------
+def update_2x2(lib, mirror):
+    u = SC.get_update_case("both")
+    side = Side(lib, u["adims"], u["cdims"], u["state"], u["rollout"], u["rows"] // u["n_mb"], mirror)
+    side.h.update(side.batch, side.std, u["perm"].to(DEV), u["rows"], u["epochs"], u["n_mb"])
+    return side
+
+
+def test_both_flags_off_is_the_plain_update_bit_for_bit(hip_lib):
+    u = SC.get_update_case("both")
+    plain, off = update_2x2(hip_lib, None), update_2x2(hip_lib, (u["tables"], False, False, 0.5))
+    for name, x, y in zip(("params", "m", "v", "grads", "stats"), plain.bits(), off.bits()):
+        assert np.array_equal(x, y), name
+    assert np.abs(plain.bits()[1].view(np.float32)).max() > 0
+    assert off.scalars()["symmetry"] > 0 and plain.scalars()["symmetry"] == 0.0     # reported, not added
+    # taking the mirror away again restores the plain path: a second update from the same state on both handles
+    on = update_2x2(hip_lib, (u["tables"],) + SC.FLAGS["both"])
+    assert not np.array_equal(on.bits()[0], plain.bits()[0])
+    on.h.set_mirror(None)
+    for side in (on, plain):
+        side.h.import_("PARAMS", PC_flat(u), side.std); side.h.import_("ADAM_M", torch.zeros(side.h.n_params)); side.h.import_("ADAM_V", torch.zeros(side.h.n_params))
+        side.h.set_step(0, R.HP["learning_rate"])
+        side.h.update(side.batch, side.std, u["perm"].to(DEV), u["rows"], u["epochs"], u["n_mb"])
+    for name, x, y in zip(("params", "m", "v", "grads", "stats"), plain.bits(), on.bits()):
+        assert np.array_equal(x, y), name
+
+
+def PC_flat(u):
+    m = R.make_model(u["adims"], u["cdims"], u["state"], torch.float32)
+    return torch.cat([u["state"][k].reshape(-1).float() for k, _ in R.ordered_params(m)])
+
+
+def test_batch_arrays_are_untouched_and_the_update_is_deterministic(hip_lib):
+    u = SC.get_update_case("both")
+    mirror = (u["tables"],) + SC.FLAGS["both"]
+    a = update_2x2(hip_lib, mirror)
+    for k, v in u["rollout"].items():                          # NaN rows included: compare the bits
+        assert np.array_equal(a.ro[k].cpu().numpy().view(np.int32), v.contiguous().numpy().view(np.int32)), k
+    b = update_2x2(hip_lib, mirror)
+    for name, x, y in zip(("params", "m", "v", "grads", "stats"), a.bits(), b.bits()):
+        assert np.array_equal(x, y), name
+    assert a.scalars()["symmetry"] == b.scalars()["symmetry"] > 0
+
+
+@pytest.mark.parametrize("shape", [("small", 300), ("walk", 37)], ids=lambda s: f"{s[0]}-{s[1]}")
+def test_minibatch_grad_with_mirror_is_bit_reproducible(hip_lib, shape):
+    c = SC.get_case(*shape)
+    outs = []
+    for _ in range(2):
+        side = case_side(hip_lib, c, "both")
+        side.h.minibatch_grad(side.batch, side.std, side.idx)
+        outs.append((side.h.export_padded("GRADS").cpu().numpy().view(np.int32), side.h.stats().cpu().numpy().view(np.int64), side.scalars()["symmetry"]))
+    assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1]) and outs[0][2] == outs[1][2]
+
+
+# ---- 3. the sharded path -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("flags", ["both", "mirror"])
+def test_one_record_with_mirror_equals_minibatch_grad_bit_for_bit(hip_lib, flags):
+    c = SC.get_case("small", 300)
+    plain, shard, bare = case_side(hip_lib, c, flags), case_side(hip_lib, c, flags), case_side(hip_lib, c, None)
+    assert shard.h.shard_len == shard.h.n_padded + 5 and bare.h.shard_len == bare.h.n_padded + 4
+    plain.h.minibatch_grad(plain.batch, plain.std, plain.idx)
+    rec = shard.h.shard_grad(shard.batch, shard.std, shard.idx, c.n)
+    assert rec.numel() == shard.h.n_padded + 5
+    shard.h.shard_reduce(rec.view(1, -1), shard.std)
+    ga, gb = plain.h.export_padded("GRADS").cpu().numpy(), shard.h.export_padded("GRADS").cpu().numpy()
+    assert np.array_equal(ga.view(np.int32), gb.view(np.int32)) and np.abs(ga).max() > 0
+    assert np.array_equal(plain.h.stats().cpu().numpy().view(np.int64), shard.h.stats().cpu().numpy().view(np.int64))
+    assert plain.scalars()["symmetry"] == shard.scalars()["symmetry"] > 0
+    plain.h.apply(plain.std); shard.h.apply(shard.std)
+    for name, x, y in zip(("params", "m", "v", "grads", "stats"), plain.bits(), shard.bits()):
+        assert np.array_equal(x, y), name
+    bare.h.set_mirror(c.tables, *SC.FLAGS[flags])
+    assert bare.h.shard_len == bare.h.n_padded + 5
+    bare.h.set_mirror(None)
+    assert bare.h.shard_len == bare.h.n_padded + 4
+
+
+@pytest.mark.parametrize("split", [(150, 150), (100, 200)], ids=lambda s: "+".join(map(str, s)))
+@pytest.mark.parametrize("flags", ["both", "mirror"])
+def test_shards_with_mirror_against_float64(hip_lib, split, flags):
+    c = SC.get_case("small", 300)
+    offs = np.concatenate([[0], np.cumsum(split)])
+    sides = [case_side(hip_lib, c, flags, idx=c.idx[o:o + n]) for n, o in zip(split, offs)]
+    records = torch.cat([s.h.shard_grad(s.batch, s.std, s.idx, c.n) for s in sides]).view(len(sides), -1)
+    for s in sides:
+        s.h.shard_reduce(records, s.std)
+    worst, st = grad_ratios(sides[0], f"shards-{split[0]}+{split[1]}-{flags}", c.ref(flags))
+    assert worst <= C_GRAD
+    a, b = sides[0].h.export_padded("GRADS").cpu().numpy(), sides[1].h.export_padded("GRADS").cpu().numpy()
+    assert np.array_equal(a.view(np.int32), b.view(np.int32))                      # every "rank" holds the same bits
+    assert sides[0].scalars() == sides[1].scalars()
+
+
+# ---- 4. status codes -----------------------------------------------------------------------------------------------------------------------------
+def test_set_mirror_rejects_bad_tables(hip_lib):
+    from go2_sim2real_locomotion_rl_amd.capi import C, Go2SimError, PpoMirror
+
+    c = SC.get_case("small", 17)
+    side, plain = case_side(hip_lib, c, None), case_side(hip_lib, c, None)
+    good = {k: (s.clone(), g.clone()) for k, (s, g) in c.tables.items()}
+
+    def broken(key, what, j, value):
+        t = {k: (s.clone(), g.clone()) for k, (s, g) in good.items()}
+        t[key][what][j] = value
+        return t
+
+    bad = [broken("policy", 0, 3, 2),                          # 2 twice: not a permutation
+           broken("critic", 0, 0, 9), broken("actions", 0, 1, -1),   # out of range
+           broken("actions", 1, 2, 0.5), broken("policy", 1, 0, 0.0)]  # signs other than +1 / -1
+    for t in bad:
+        with pytest.raises(Go2SimError, match=f"status {C['GO2SIM_E_BADARG']}"):
+            side.h.set_mirror(t, True, True, 0.5)
+    m = PpoMirror()                                            # null tables
+    assert hip_lib.fn("ppo_set_mirror")(side.h.h, ctypes.byref(m), ctypes.c_void_p(0)) == C["GO2SIM_E_BADARG"]
+    assert hip_lib.fn("ppo_set_mirror")(ctypes.c_void_p(0), ctypes.byref(m), ctypes.c_void_p(0)) == C["GO2SIM_E_BADARG"]
+    assert hip_lib.fn("ppo_symmetry_loss")(side.h.h, ctypes.c_void_p(0), ctypes.c_void_p(0)) == C["GO2SIM_E_BADARG"]
+    with pytest.raises(Go2SimError, match="entries"):
+        side.h.set_mirror(dict(good, policy=good["critic"]), True, True, 0.5)
+    # every refused call left the handle on the plain path
+    assert side.h.shard_len == side.h.n_padded + 4
+    side.h.minibatch_grad(side.batch, side.std, side.idx); plain.h.minibatch_grad(plain.batch, plain.std, plain.idx)
+    assert np.array_equal(side.h.export_padded("GRADS").cpu().numpy().view(np.int32), plain.h.export_padded("GRADS").cpu().numpy().view(np.int32))
+    # set, then removed: the plain path bit for bit
+    side.h.set_mirror(good, True, True, 0.5)
+    side.h.minibatch_grad(side.batch, side.std, side.idx)
+    assert not np.array_equal(side.h.export_padded("GRADS").cpu().numpy().view(np.int32), plain.h.export_padded("GRADS").cpu().numpy().view(np.int32))
+    side.h.set_mirror(None)
+    side.h.reset_stats(); plain.h.reset_stats()
+    side.h.set_step(0, R.HP["learning_rate"]); plain.h.set_step(0, R.HP["learning_rate"])
+    side.h.minibatch_grad(side.batch, side.std, side.idx); plain.h.minibatch_grad(plain.batch, plain.std, plain.idx)
+    assert np.array_equal(side.h.export_padded("GRADS").cpu().numpy().view(np.int32), plain.h.export_padded("GRADS").cpu().numpy().view(np.int32))
+    assert np.array_equal(side.h.stats().cpu().numpy().view(np.int64), plain.h.stats().cpu().numpy().view(np.int64))
+
+
+def test_ppo_class_refuses_a_callable_and_names_the_tables():
+    from go2_sim2real_locomotion_rl_amd import PPO, ActorCritic
+    from go2_sim2real_locomotion_rl_amd.capi import Go2SimError
+
+    policy = ActorCritic(49, 104, 16, [32], [32], seed=2)
+    with pytest.raises(Go2SimError, match="mirror_tables"):
+        PPO(policy, symmetry_cfg={"use_data_augmentation": True, "data_augmentation_func": lambda obs, actions, env, obs_type: (obs, actions)})
+    with pytest.raises(Go2SimError):
+        PPO(policy, symmetry_cfg={"use_data_augmentation": True, "mirror_tables": SC.ENV_TABLES["walk"]}, normalize_advantage_per_mini_batch=True)
+    with pytest.raises(Go2SimError):
+        PPO(policy, rnd_cfg={"weight": 1.0})
+    assert PPO(policy, symmetry_cfg=None).symmetry is None
+
+
+# ---- 5. end to end -------------------------------------------------------------------------------------------------------------------------------
+TRAIN_CFG = {
+    "algorithm": {"class_name": "PPO", "clip_param": 0.2, "desired_kl": 0.01, "entropy_coef": 0.003, "gamma": 0.99, "lam": 0.95, "learning_rate": 0.001,
+                  "max_grad_norm": 1.0, "num_learning_epochs": 2, "num_mini_batches": 4, "schedule": "adaptive", "use_clipped_value_loss": True,
+                  "value_loss_coef": 1.0},
+    "init_member_classes": {},
+    "policy": {"activation": "elu", "actor_hidden_dims": [64, 32], "critic_hidden_dims": [64, 32], "init_noise_std": 1.0, "class_name": "ActorCritic"},
+    "runner": {"checkpoint": -1, "experiment_name": "t", "load_run": -1, "log_interval": 1, "max_iterations": 2, "record_interval": -1, "resume": False,
+               "resume_path": None, "run_name": ""},
+    "runner_class_name": "OnPolicyRunner", "num_steps_per_env": 8, "save_interval": 1000, "empirical_normalization": None, "seed": 1,
+}
+
+
+def test_runner_trains_with_symmetry_and_reproduces():
+    from go2_sim2real_locomotion_rl_amd import Go2Env, OnPolicyRunner, get_walk_cfgs, init
+    cfg = copy.deepcopy(TRAIN_CFG)
+    cfg["algorithm"]["symmetry_cfg"] = {"use_data_augmentation": True, "use_mirror_loss": True, "mirror_loss_coeff": 0.5}
+    out = []
+    for _ in range(2):
+        init(seed=11)
+        env = Go2Env(64, *get_walk_cfgs(), seed=11)
+        tables = env.mirror_tables()
+        assert all(torch.equal(tables[k][0], SC.ENV_TABLES["walk"][k][0]) and torch.equal(tables[k][1], SC.ENV_TABLES["walk"][k][1]) for k in tables)
+        runner = OnPolicyRunner(env, cfg)
+        log = runner.learn(2)
+        assert all(np.isfinite(d["symmetry_loss"]) and d["symmetry_loss"] > 0 for d in log) and len(log) == 2
+        assert env.check_errno() == 0
+        out.append((log, runner.policy.state_dict()))
+    assert out[0][0] == out[1][0]
+    for k, v in out[0][1].items():
+        assert np.array_equal(v.numpy().view(np.int32), out[1][1][k].numpy().view(np.int32)), k

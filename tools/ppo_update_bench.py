@@ -2,7 +2,7 @@
 """Times PPO.update() of the library against an eager-torch fp32 restatement of the same update on the same GPU, at the training shape of the
 walk task: T = 24 steps x B = 4096 envs, 49 / 104 observations, 16 actions, two 512-256-128 MLPs, 5 epochs x 4 mini-batches of 24 576 rows.
 
-    python tools/ppo_update_bench.py [--updates 5] [--warmup 2] [--envs 4096] [--steps 24] [--shards N]
+    python tools/ppo_update_bench.py [--updates 5] [--warmup 2] [--envs 4096] [--steps 24] [--shards N] [--symmetry {off,augment,mirror,both}]
 
 Both sides update from the same rollout (collected once with the library's ActorCritic on random observations and rewards) and the same initial
 parameters.  Every shape is warmed up first; device events bracket `--updates` whole updates per side, the two sides alternating update by update so
@@ -13,7 +13,10 @@ that the HIP update as a whole achieves (an end-to-end rate over peak, not a ker
 
 --shards N adds the sharded form of the update as a rank of an N-rank job runs it, in this one process: per mini-batch go2sim_ppo_shard_grad, go2sim_ppo_shard_reduce
 of N copies of the record (what the all-gather would deliver; the collective itself is NOT in the time), go2sim_ppo_apply, alternating with the plain update.
-It reports `sharded_ms_per_update` and the difference to `hip_ms_per_update`."""
+It reports `sharded_ms_per_update` and the difference to `hip_ms_per_update`.
+
+--symmetry sets the walk env's mirror on the HIP side (symmetry_cfg with Go2Env's tables; mirror_loss_coeff 0.5): the update then handles twice the rows.  The
+torch side stays the plain update, so `hip_over_torch` compares unlike work; the time to hold `hip_ms_per_update` against is a plain run at --envs 8192."""
 import argparse
 import json
 import os
@@ -101,6 +104,7 @@ def main():
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--shards", type=int, default=0, help="also time shard_grad + shard_reduce of N copies of the record + apply per mini-batch")
+    ap.add_argument("--symmetry", choices=("off", "augment", "mirror", "both"), default="off", help="mirror symmetry on the HIP side (twice the rows)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ppo_update_bench needs a ROCm GPU: a time taken anywhere else says nothing")
@@ -112,7 +116,14 @@ def main():
     adims, cdims = [nobs, *hidden, nact], [npriv, *hidden, 1]
     policy = ActorCritic(nobs, npriv, nact, hidden, hidden, device=dev, seed=1)
     state = {k: v.clone() for k, v in policy.state_dict().items()}
-    alg = PPO(policy, num_learning_epochs=EPOCHS, num_mini_batches=MINI_BATCHES, schedule="adaptive", gamma=0.99, lam=0.95, seed=1, **HP)
+    sym = None
+    if args.symmetry != "off":
+        from go2_sim2real_locomotion_rl_amd import get_walk_cfgs
+        from go2_sim2real_locomotion_rl_amd.go2_env import mirror_tables
+
+        sym = {"use_data_augmentation": args.symmetry in ("augment", "both"), "use_mirror_loss": args.symmetry in ("mirror", "both"), "mirror_loss_coeff": 0.5,
+               "mirror_tables": mirror_tables(*get_walk_cfgs()[:2])}
+    alg = PPO(policy, num_learning_epochs=EPOCHS, num_mini_batches=MINI_BATCHES, schedule="adaptive", gamma=0.99, lam=0.95, seed=1, symmetry_cfg=sym, **HP)
     alg.init_storage(B, T, [nobs], [npriv], [nact])
     g = torch.Generator(device=dev).manual_seed(0)
 
@@ -166,6 +177,9 @@ def main():
     if args.shards > 0:
         sh_ms = ms["sharded"] / args.updates
         extra = {"shards": args.shards, "sharded_ms_per_update": round(sh_ms, 3), "sharded_minus_hip_ms": round(sh_ms - hip_ms, 3)}
+    if sym is not None:
+        extra["symmetry"] = args.symmetry
+        extra["symmetry_loss"] = alg.symmetry_loss
     print(json.dumps({"tool": "ppo_update_bench", "envs": B, "steps": T, "epochs": EPOCHS, "mini_batches": MINI_BATCHES, "updates_timed": args.updates,
                       "hip_ms_per_update": round(hip_ms, 3), "torch_eager_ms_per_update": round(torch_ms, 3), "hip_over_torch": round(hip_ms / torch_ms, 3),
                       "matrix_flop_per_update": flop, "hip_fraction_of_157.3_tflops": round(flop / (hip_ms * 1e-3) / PEAK_FP32_MATRIX, 4), **extra}))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Trains a Go2 policy with the library's runner, on one GPU or sharded over the ranks of a ``torchrun`` job.
 
-    python tools/train.py --task walk --envs 4096 --iterations 1000 --log-dir logs/go2-walk
+    python tools/train.py --task walk --envs 4096 --iterations 1000 --log-dir logs/go2-walk [--symmetry both --mirror-coeff 0.5]
     torchrun --nproc-per-node 8 tools/train.py --task walk --envs 4096 --iterations 1000 --log-dir logs/go2-walk
 
 --envs is the env count PER RANK.  Under torchrun every rank builds its shard of the envs (``Go2Env(..., shared_globals=True)``: one curriculum, one
@@ -45,6 +45,9 @@ def main():
     ap.add_argument("--cfgs", default=None, help="cfgs.pkl of a reference run: its train_cfg replaces the task's default")
     ap.add_argument("--steps-per-env", type=int, default=None, help="overrides train_cfg['num_steps_per_env']")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--symmetry", choices=("off", "augment", "mirror", "both"), default="off",
+                    help="left-right mirror symmetry in the update (rsl_rl's symmetry_cfg): augmentation with the mirrored rows, the mirror loss, or both")
+    ap.add_argument("--mirror-coeff", type=float, default=0.5, help="mirror_loss_coeff of --symmetry mirror / both")
     ap.add_argument("--resume", default=None, help="checkpoint to load on every rank before training")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -75,6 +78,9 @@ def main():
         cfg["seed"] = args.seed
         if args.steps_per_env:
             cfg["num_steps_per_env"] = args.steps_per_env
+        if args.symmetry != "off":                                                  # the runner fills in the env's own mirror tables
+            cfg["algorithm"]["symmetry_cfg"] = {"use_data_augmentation": args.symmetry in ("augment", "both"),
+                                                "use_mirror_loss": args.symmetry in ("mirror", "both"), "mirror_loss_coeff": args.mirror_coeff}
         runner = OnPolicyRunner(env, cfg, log_dir=args.log_dir, device=device)      # picks up the default process group
         if args.resume:
             runner.load(args.resume)
