@@ -52,6 +52,10 @@ DECLARED_FUNCS = DECLARED_FUNCS + _DECL_POLICY
 TRAIN_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_train.h")
 _C_TRAIN, DECLARED_TRAIN_FUNCS = _parse_header(TRAIN_HEADER)
 C.update(_C_TRAIN)
+# the recurrent (LSTM) policy (include/go2sim_rnn.h): the memory cell and the update through time; product library only, a list of its own as well
+RNN_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_rnn.h")
+_C_RNN, DECLARED_RNN_FUNCS = _parse_header(RNN_HEADER)
+C.update(_C_RNN)
 
 
 class PpoCfg(ctypes.Structure):
@@ -71,6 +75,12 @@ class PpoMirror(ctypes.Structure):
     TABLES = ("obs_src", "obs_sign", "critic_src", "critic_sign", "action_src", "action_sign")
     _fields_ = [(n, ctypes.c_void_p) for n in TABLES] + [("use_data_augmentation", ctypes.c_int), ("use_mirror_loss", ctypes.c_int),
                                                          ("mirror_loss_coeff", ctypes.c_double)]
+
+
+class PpoRnnState(ctypes.Structure):
+    """go2sim_ppo_rnn_state_t: the memories' state at the rollout's first act and the rollout's dones"""
+    FIELDS = ("h_a", "c_a", "h_c", "c_c", "dones")
+    _fields_ = [(n, ctypes.c_void_p) for n in FIELDS]
 
 
 class EnvGlobals(ctypes.Structure):
@@ -136,7 +146,7 @@ class Go2SimLib:
             fn = getattr(self.lib, prefix + name[len("go2sim_"):])
             fn.restype = ctypes.c_int
         if self.is_device:
-            for name in DECLARED_TRAIN_FUNCS:       # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
+            for name in DECLARED_TRAIN_FUNCS + DECLARED_RNN_FUNCS:       # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
                 if hasattr(self.lib, name):
                     getattr(self.lib, name).restype = ctypes.c_int
 

@@ -29,6 +29,10 @@
 // respectively in registers, once per workgroup); k_ppo_head permutes the actions the same way, reads row r's scalars, adds the mirror-loss term to
 // the mirrored rows' dZ and sums (mu' - target)^2 in one more float64 partial column.  The kernels that gather are templates on the mirror: a handle
 // without tables runs the code it ran before.
+// Recurrent policy (go2sim_ppo_create_recurrent, include/go2sim_rnn.h; the end of this file): an LSTM memory in front of each network.  A mini-batch is an env
+// block with all its steps: T launches of k_lstm_cell (go2sim_lstm_dev.h), the launches above on the T x block rows of h' (k_bwd_da<true> also writes the first
+// layer's d loss / d h'), T launches of k_lstm_bptt back through time, then k_bwd_dw / k_bwd_db for the memories' weights.  The memories' segments follow the two
+// networks in the padded vectors, so the chunk reduction, the norm and k_adam<true> cover them.  A handle without memories runs the plain instantiations.
 // Padding: padded rows of dZ^T and padded columns of A_prev are exact zeros, so padded gradient entries are sums of exact zeros, and Adam leaves a
 // zero parameter with zero gradient, m and v at zero.
 #include <hip/hip_runtime.h>
@@ -41,7 +45,9 @@
 #include <vector>
 
 #include "go2sim_mlp_dev.h"
+#include "go2sim_lstm_dev.h"   // the memories of a recurrent policy: LstmDev, struct go2sim_lstm, k_lstm_cell, k_lstm_bptt
 #include "../../include/go2sim_train.h"
+#include "../../include/go2sim_rnn.h"
 
 namespace {
 
@@ -287,6 +293,7 @@ struct BwdLayer {
   int gather;           // aprev rows are read through idx
   MirTab mir;           // gather layers under a mirror: rows >= n_orig read row idx[r - n_orig] through this table
   int active;           // this network has this layer
+  int lin;              // k_bwd_da<true>: the layer's input is a memory's h, not an ELU output: dzprev = dZ W without the ELU factor
   size_t w_off, b_off;  // offsets of dW / db in a slab of partials (= in the padded gradient vector)
 };
 
@@ -388,6 +395,8 @@ __global__ __launch_bounds__(WGT) void k_bwd_db(BwdLayer L0, BwdLayer L1, int n_
 }
 
 // dZ_prev[r][k] = (sum_n dZ[r][n] W[n][k]) * ELU'(A_prev[r][k]); ELU' from the stored post-activation a: 1 for a > 0, a + 1 otherwise
+// RNN: a first layer behind a memory (L.lin) writes d loss / d h; the plain instantiation is the kernel as it was
+template <bool RNN>
 __global__ __launch_bounds__(64 * NWAVE) void k_bwd_da(BwdLayer L0, BwdLayer L1, int n_rows) {
   constexpr int TG = 2;
   const BwdLayer& L = blockIdx.y == 0 ? L0 : L1;
@@ -435,6 +444,7 @@ __global__ __launch_bounds__(64 * NWAVE) void k_bwd_da(BwdLayer L0, BwdLayer L1,
         for (int i = 0; i < 4; ++i) {
           const int r = row0 + 16 * rt + 4 * kq + i;
           if (r < n_rows) {
+            if (RNN && L.lin) { L.dzprev[(size_t)r * K + kc[t]] = acc[rt][t][i]; continue; }
             const float a = L.aprev[(size_t)r * K + kc[t]];
             L.dzprev[(size_t)r * K + kc[t]] = acc[rt][t][i] * (a > 0.0f ? 1.0f : a + 1.0f);
           }
@@ -518,13 +528,16 @@ __global__ __launch_bounds__(WGT) void k_sumsq(const float* __restrict__ g, size
 
 struct AdamArgs {
   float *p_actor, *p_critic, *p_std, *g, *m, *v;
-  size_t nA, nC, n_tot;                                   // padded sizes; the std block follows the two networks
+  size_t nA, nC, n_tot;                                   // padded sizes; the std block follows the two networks (and the memories)
+  float *p_ma, *p_mc;                                     // k_adam<true>: the two memories' parameters, nMa + nMc entries after the networks
+  size_t nMa, nMc;
   int A;
   const double* sq_part;
   double* scal;
   double max_norm, b1, b2, eps, bc1, bc2_sqrt;            // bc1 = 1 - b1^t, bc2_sqrt = sqrt(1 - b2^t), from the step count in float64 on the host
 };
 
+template <bool RNN>
 __global__ __launch_bounds__(WGT) void k_adam(AdamArgs a) {
   __shared__ double s_coef;
   if (threadIdx.x == 0) {
@@ -542,7 +555,9 @@ __global__ __launch_bounds__(WGT) void k_adam(AdamArgs a) {
   float* p;
   if (i < a.nA) p = a.p_actor + i;
   else if (i < a.nA + a.nC) p = a.p_critic + (i - a.nA);
-  else { const size_t k = i - a.nA - a.nC; if (k >= (size_t)a.A) return; p = a.p_std + k; }
+  else if (RNN && i < a.nA + a.nC + a.nMa) p = a.p_ma + (i - a.nA - a.nC);
+  else if (RNN && i < a.nA + a.nC + a.nMa + a.nMc) p = a.p_mc + (i - a.nA - a.nC - a.nMa);
+  else { const size_t k = i - a.nA - a.nC - (RNN ? a.nMa + a.nMc : 0); if (k >= (size_t)a.A) return; p = a.p_std + k; }
   const double g = (double)a.g[i] * s_coef;
   const double m = a.b1 * (double)a.m[i] + (1.0 - a.b1) * g;
   const double v = a.b2 * (double)a.v[i] + (1.0 - a.b2) * (g * g);
@@ -574,7 +589,7 @@ __global__ void k_stats(const double* __restrict__ scal, double step, double* __
   out[GO2SIM_PPO_ST_STEP] = step; out[GO2SIM_PPO_ST_COUNT] = scal[S_COUNT];
 }
 
-struct Seg { int base; size_t pad_off; int ld, rows, cols; size_t flat_off; };   // base 0 actor, 1 critic, 2 std
+struct Seg { int base; size_t pad_off; int ld, rows, cols; size_t flat_off; };   // base 0 actor, 1 critic, 2 std, 3 memory_a, 4 memory_c
 
 }  // namespace
 
@@ -600,6 +615,15 @@ struct go2sim_ppo {
   int32_t* mir_src = nullptr;
   float* mir_sign = nullptr;
   MirTab tab[3]{};            // 0 actor input, 1 critic input, 2 actions
+  // recurrent policy (go2sim_ppo_create_recurrent): the two memories, their blocks after the networks in the padded vectors, the per-step workspaces
+  go2sim_lstm* mem[2] = {nullptr, nullptr};
+  size_t nM[2] = {0, 0};
+  size_t slab = 0;            // nA + nC + nM[0] + nM[1]: what the row chunks reduce; the std block follows
+  int rnn = 0, T = 0, nb_max = 0;
+  float* rbuf = nullptr;      // per memory: gates | dz [R][4 Hpad], hprev | cprev | hout | cout [R][H], dh_mlp [R][Hpad], dc [nb_max][Hpad]
+  int32_t* ibuf = nullptr;    // idx_b [R] (rows of the env block in the batch arrays) | idx_id [R] (0 .. R - 1)
+  float *r_gates[2]{}, *r_dz[2]{}, *r_hprev[2]{}, *r_cprev[2]{}, *r_hout[2]{}, *r_cout[2]{}, *r_dh[2]{}, *r_dc[2]{};
+  int32_t *idx_b = nullptr, *idx_id = nullptr;
 };
 
 namespace {
@@ -636,7 +660,7 @@ int alloc_workspaces(go2sim_ppo* h, size_t R) {
     need += 2 * dz_sz[net];
   }
   const int chunks = (int)((R + RCH - 1) / RCH), head_wg = (int)((R + WGT - 1) / WGT);
-  const size_t slab = h->nA + h->nC;
+  const size_t slab = h->slab;
   need += (size_t)chunks * slab;
   const size_t nd = (size_t)head_wg * (4 + h->A);
   float* wb = nullptr;
@@ -667,19 +691,58 @@ float* vec_of(go2sim_ppo* h, int which) {
 int pack_all(go2sim_ppo* h, int which, int to_padded, float* flat, float* std_dev, hipStream_t st) {
   if (!h || !flat || which < GO2SIM_PPO_PARAMS || which > GO2SIM_PPO_ADAM_V) return GO2SIM_E_BADARG;
   if (which == GO2SIM_PPO_PARAMS && !std_dev) return GO2SIM_E_BADARG;
-  float* base[3];
-  if (which == GO2SIM_PPO_PARAMS) { base[0] = h->actor->dparams; base[1] = h->critic->dparams; base[2] = std_dev; }
-  else { float* v = vec_of(h, which); base[0] = v; base[1] = v + h->nA; base[2] = v + h->nA + h->nC; }
+  float* base[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (which == GO2SIM_PPO_PARAMS) {
+    base[0] = h->actor->dparams; base[1] = h->critic->dparams; base[2] = std_dev;
+    if (h->rnn) { base[3] = h->mem[0]->dparams; base[4] = h->mem[1]->dparams; }
+  } else {
+    float* v = vec_of(h, which);
+    base[0] = v; base[1] = v + h->nA; base[2] = v + h->slab; base[3] = v + h->nA + h->nC; base[4] = base[3] + h->nM[0];
+  }
   for (const Seg& s : h->segs)
     hipLaunchKernelGGL(k_pack, dim3((s.rows * s.cols + WGT - 1) / WGT), dim3(WGT), 0, st, to_padded, base[s.base] + s.pad_off, s.ld, flat + s.flat_off, s.rows, s.cols);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;
 }
-}  // namespace
 
-extern "C" {
+// the row workspaces of a recurrent handle: R = T x nb_max rows per memory
+int alloc_rnn_workspaces(go2sim_ppo* h) {
+  auto al16 = [](size_t n) { return (n + 15) / 16 * 16; };
+  const size_t R = (size_t)h->T * h->nb_max;
+  size_t need = 0;
+  for (int net = 0; net < 2; ++net) {
+    const size_t H = h->mem[net]->H, Hp = h->mem[net]->dev.Hpad;
+    need += 2 * al16(R * 4 * Hp) + 4 * al16(R * H) + al16(R * Hp) + al16((size_t)h->nb_max * Hp);
+  }
+  if (hipMalloc((void**)&h->rbuf, need * sizeof(float)) != hipSuccess || hipMalloc((void**)&h->ibuf, 2 * R * sizeof(int32_t)) != hipSuccess) return GO2SIM_E_NOMEM;
+  HIPCHK(hipMemset(h->rbuf, 0, need * sizeof(float)));
+  float* p = h->rbuf;
+  for (int net = 0; net < 2; ++net) {
+    const size_t H = h->mem[net]->H, Hp = h->mem[net]->dev.Hpad;
+    h->r_gates[net] = p; p += al16(R * 4 * Hp); h->r_dz[net] = p; p += al16(R * 4 * Hp);
+    h->r_hprev[net] = p; p += al16(R * H); h->r_cprev[net] = p; p += al16(R * H); h->r_hout[net] = p; p += al16(R * H); h->r_cout[net] = p; p += al16(R * H);
+    h->r_dh[net] = p; p += al16(R * Hp); h->r_dc[net] = p; p += al16((size_t)h->nb_max * Hp);
+  }
+  h->idx_b = h->ibuf; h->idx_id = h->ibuf + R;
+  hipLaunchKernelGGL(k_iota, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, 0, h->idx_id, (int)R);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  return GO2SIM_E_OK;
+}
 
-int go2sim_ppo_create(go2sim_mlp_t* actor, go2sim_mlp_t* critic, int n_actions, const go2sim_ppo_cfg_t* cfg, int max_rows, go2sim_ppo_t** out) {
+// the segments of one memory in the flat (state-dict) order: weight_ih, weight_hh, bias_ih, bias_hh; a gate's block of H rows sits Hpad rows apart
+void lstm_segs(std::vector<Seg>& segs, int base, const go2sim_lstm* m, size_t& flat) {
+  const int H = m->H, I = m->I, Hp = m->dev.Hpad, Ip = m->dev.Ipad;
+  const size_t o_hh = (size_t)4 * Hp * Ip, o_bi = o_hh + (size_t)4 * Hp * Hp, o_bh = o_bi + (size_t)4 * Hp;
+  for (int q = 0; q < 4; ++q) { segs.push_back(Seg{base, (size_t)q * Hp * Ip, Ip, H, I, flat}); flat += (size_t)H * I; }
+  for (int q = 0; q < 4; ++q) { segs.push_back(Seg{base, o_hh + (size_t)q * Hp * Hp, Hp, H, H, flat}); flat += (size_t)H * H; }
+  for (int q = 0; q < 4; ++q) { segs.push_back(Seg{base, o_bi + (size_t)q * Hp, H, 1, H, flat}); flat += H; }
+  for (int q = 0; q < 4; ++q) { segs.push_back(Seg{base, o_bh + (size_t)q * Hp, H, 1, H, flat}); flat += H; }
+}
+
+// go2sim_ppo_create and go2sim_ppo_create_recurrent (ma, mc and n_steps set: max_rows = n_steps x the envs of a mini-batch)
+int create_impl(go2sim_mlp_t* actor, go2sim_mlp_t* critic, go2sim_lstm* ma, go2sim_lstm* mc, int n_steps, int n_actions, const go2sim_ppo_cfg_t* cfg, int max_rows,
+                go2sim_ppo_t** out) {
   if (!actor || !critic || !cfg || !out || max_rows < 1 || n_actions < 1) return GO2SIM_E_BADARG;
   if (actor->dims[actor->n_layers] != n_actions || critic->dims[critic->n_layers] != 1 || actor->device != critic->device) return GO2SIM_E_BADARG;
   if (!(cfg->learning_rate > 0.0) || !(cfg->clip_param >= 0.0)) return GO2SIM_E_BADARG;
@@ -687,7 +750,10 @@ int go2sim_ppo_create(go2sim_mlp_t* actor, go2sim_mlp_t* critic, int n_actions, 
   go2sim_ppo* h = new (std::nothrow) go2sim_ppo();
   if (!h) return GO2SIM_E_NOMEM;
   h->actor = actor; h->critic = critic; h->cfg = *cfg; h->A = n_actions; h->Apad = round16(n_actions); h->max_rows = max_rows;
-  h->nA = actor->padded; h->nC = critic->padded; h->n_tot = h->nA + h->nC + h->Apad;
+  h->nA = actor->padded; h->nC = critic->padded;
+  if (ma) { h->rnn = 1; h->mem[0] = ma; h->mem[1] = mc; h->nM[0] = ma->padded; h->nM[1] = mc->padded; h->T = n_steps; h->nb_max = max_rows / n_steps; }
+  h->slab = h->nA + h->nC + h->nM[0] + h->nM[1];
+  h->n_tot = h->slab + h->Apad;
   // flat (state-dict) order: actor W0, b0, ..., critic W0, b0, ..., std
   size_t flat = 0;
   for (int net = 0; net < 2; ++net) {
@@ -697,6 +763,7 @@ int go2sim_ppo_create(go2sim_mlp_t* actor, go2sim_mlp_t* critic, int n_actions, 
       h->segs.push_back(Seg{net, (size_t)(M->dev.b[l] - M->dparams), M->dims[l + 1], 1, M->dims[l + 1], flat}); flat += M->dims[l + 1];
     }
   }
+  if (h->rnn) { lstm_segs(h->segs, 3, ma, flat); lstm_segs(h->segs, 4, mc, flat); }
   h->segs.push_back(Seg{2, 0, n_actions, 1, n_actions, flat}); flat += n_actions;
   h->n_flat = flat;
   const size_t nd = S_N + NORM_WG;
@@ -712,7 +779,8 @@ int go2sim_ppo_create(go2sim_mlp_t* actor, go2sim_mlp_t* critic, int n_actions, 
   }
   h->grads = h->fbuf; h->m = h->grads + h->n_tot; h->v = h->m + h->n_tot;
   h->scal = h->dbuf; h->sq_part = h->dbuf + S_N;
-  const int rc = alloc_workspaces(h, (size_t)max_rows);
+  int rc = alloc_workspaces(h, (size_t)max_rows);
+  if (rc == GO2SIM_E_OK && h->rnn) rc = alloc_rnn_workspaces(h);
   if (rc != GO2SIM_E_OK) {
     go2sim_ppo_destroy(h);
     return rc;
@@ -720,9 +788,25 @@ int go2sim_ppo_create(go2sim_mlp_t* actor, go2sim_mlp_t* critic, int n_actions, 
   *out = h;
   return GO2SIM_E_OK;
 }
+}  // namespace
+
+extern "C" {
+
+int go2sim_ppo_create(go2sim_mlp_t* actor, go2sim_mlp_t* critic, int n_actions, const go2sim_ppo_cfg_t* cfg, int max_rows, go2sim_ppo_t** out) {
+  return create_impl(actor, critic, nullptr, nullptr, 0, n_actions, cfg, max_rows, out);
+}
+
+int go2sim_ppo_create_recurrent(go2sim_mlp_t* actor, go2sim_mlp_t* critic, go2sim_lstm_t* mem_a, go2sim_lstm_t* mem_c, int n_actions, const go2sim_ppo_cfg_t* cfg,
+                                int n_steps, int max_envs, go2sim_ppo_t** out) {
+  if (!actor || !critic || !mem_a || !mem_c || n_steps < 1 || max_envs < 1 || (long long)n_steps * max_envs > 0x7fffffffLL / 4 / MAXW) return GO2SIM_E_BADARG;
+  if (mem_a->H != actor->dims[0] || mem_c->H != critic->dims[0] || mem_a->device != actor->device || mem_c->device != actor->device) return GO2SIM_E_BADARG;
+  return create_impl(actor, critic, mem_a, mem_c, n_steps, n_actions, cfg, n_steps * max_envs, out);
+}
 
 int go2sim_ppo_destroy(go2sim_ppo_t* h) {
   if (!h) return GO2SIM_E_BADARG;
+  if (h->rbuf) (void)hipFree(h->rbuf);
+  if (h->ibuf) (void)hipFree(h->ibuf);
   if (h->fbuf) (void)hipFree(h->fbuf);
   if (h->wbuf) (void)hipFree(h->wbuf);
   if (h->dbuf) (void)hipFree(h->dbuf);
@@ -757,9 +841,9 @@ static int launch_grad_t(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const flo
   hipLaunchKernelGGL(k_ppo_head<MIR>, dim3(n_wg), dim3(WGT), 0, st, ha);
   if (!record)
     hipLaunchKernelGGL(k_ppo_finalize, dim3(1), dim3(64), 0, st, h->head_part, n_wg, ncol, n, (MIR && h->use_aug) ? 2 * n : n, h->A, std_dev, h->scal,
-                       h->grads + h->nA + h->nC, h->cfg.entropy_coef, h->cfg.desired_kl, h->cfg.lr_min, h->cfg.lr_max, h->cfg.adaptive);
+                       h->grads + h->slab, h->cfg.entropy_coef, h->cfg.desired_kl, h->cfg.lr_min, h->cfg.lr_max, h->cfg.adaptive);
   const int n_chunks = (n_bwd + RCH - 1) / RCH;
-  const size_t slab = h->nA + h->nC;
+  const size_t slab = h->slab;
   const int depth = Ma->n_layers > Mc->n_layers ? Ma->n_layers : Mc->n_layers;
   for (int lb = 0; lb < depth; ++lb) {
     const BwdLayer L0 = bwd_layer(h, 0, lb, b), L1 = bwd_layer(h, 1, lb, b);
@@ -781,7 +865,7 @@ static int launch_grad_t(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const flo
       BwdLayer D0 = L0, D1 = L1;                           // a network at its first layer has no dA to compute
       if (!D0.dzprev) D0.active = 0;
       if (!D1.dzprev) D1.active = 0;
-      hipLaunchKernelGGL(k_bwd_da, dim3((n_bwd + TM - 1) / TM, 2), dim3(64 * NWAVE), 0, st, D0, D1, n_bwd);
+      hipLaunchKernelGGL(k_bwd_da<false>, dim3((n_bwd + TM - 1) / TM, 2), dim3(64 * NWAVE), 0, st, D0, D1, n_bwd);
     }
   }
   if (!record)
@@ -803,7 +887,7 @@ static bool batch_ok(const go2sim_ppo_batch_t* b) {
 }
 
 int go2sim_ppo_minibatch_grad(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const float* std_dev, const int32_t* idx, int n, void* stream) {
-  if (!h || !std_dev || !idx || n < 1 || n > h->max_rows || !batch_ok(b)) return GO2SIM_E_BADARG;
+  if (!h || h->rnn || !std_dev || !idx || n < 1 || n > h->max_rows || !batch_ok(b)) return GO2SIM_E_BADARG;
   return launch_grad(h, b, std_dev, idx, n, 1.0 / (double)n, nullptr, (hipStream_t)stream);
 }
 
@@ -815,14 +899,14 @@ int go2sim_ppo_shard_len(go2sim_ppo_t* h, size_t* out) {
 
 int go2sim_ppo_shard_grad(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const float* std_dev, const int32_t* idx, int n, long long n_global, double* record,
                           void* stream) {
-  if (!h || !std_dev || !idx || !record || n < 1 || n > h->max_rows || n_global < (long long)n || !batch_ok(b)) return GO2SIM_E_BADARG;
+  if (!h || h->rnn || !std_dev || !idx || !record || n < 1 || n > h->max_rows || n_global < (long long)n || !batch_ok(b)) return GO2SIM_E_BADARG;
   return launch_grad(h, b, std_dev, idx, n, 1.0 / (double)n_global, record, (hipStream_t)stream);
 }
 
 int go2sim_ppo_shard_reduce(go2sim_ppo_t* h, const double* records, int n_records, const float* std_dev, void* stream) {
-  if (!h || !records || !std_dev || n_records < 1) return GO2SIM_E_BADARG;
+  if (!h || h->rnn || !records || !std_dev || n_records < 1) return GO2SIM_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
-  const size_t slab = h->nA + h->nC, len = h->n_tot + 4 + (h->mirror ? 1 : 0);
+  const size_t slab = h->slab, len = h->n_tot + 4 + (h->mirror ? 1 : 0);
   hipLaunchKernelGGL(k_shard_reduce, dim3((unsigned)((h->n_tot + WGT - 1) / WGT)), dim3(WGT), 0, st, records, n_records, len, slab, h->A, h->Apad, std_dev,
                      h->cfg.entropy_coef, h->grads);
   hipLaunchKernelGGL(k_shard_scalars, dim3(1), dim3(64), 0, st, records, n_records, len, h->n_tot, h->mirror ? 5 : 4, (h->mirror && h->use_aug) ? 2 : 1, h->A,
@@ -832,7 +916,7 @@ int go2sim_ppo_shard_reduce(go2sim_ppo_t* h, const double* records, int n_record
 }
 
 int go2sim_ppo_set_mirror(go2sim_ppo_t* h, const go2sim_ppo_mirror_t* m, void* stream) {
-  if (!h) return GO2SIM_E_BADARG;
+  if (!h || (h->rnn && m)) return GO2SIM_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
   if (!m) {                                                // back to the plain path; the larger workspaces stay
     h->mirror = h->use_aug = h->use_mloss = 0;
@@ -896,14 +980,19 @@ int go2sim_ppo_apply(go2sim_ppo_t* h, float* std_dev, void* stream) {
   a.max_norm = h->cfg.max_grad_norm; a.b1 = h->cfg.beta1; a.b2 = h->cfg.beta2; a.eps = h->cfg.eps;
   a.bc1 = 1.0 - std::pow(h->cfg.beta1, t); a.bc2_sqrt = std::sqrt(1.0 - std::pow(h->cfg.beta2, t));
   hipLaunchKernelGGL(k_sumsq, dim3(NORM_WG), dim3(WGT), 0, st, h->grads, h->n_tot, h->sq_part);
-  hipLaunchKernelGGL(k_adam, dim3((unsigned)((h->n_tot + WGT - 1) / WGT)), dim3(WGT), 0, st, a);
+  if (h->rnn) {
+    a.p_ma = h->mem[0]->dparams; a.p_mc = h->mem[1]->dparams; a.nMa = h->nM[0]; a.nMc = h->nM[1];
+    hipLaunchKernelGGL(k_adam<true>, dim3((unsigned)((h->n_tot + WGT - 1) / WGT)), dim3(WGT), 0, st, a);
+  } else {
+    hipLaunchKernelGGL(k_adam<false>, dim3((unsigned)((h->n_tot + WGT - 1) / WGT)), dim3(WGT), 0, st, a);
+  }
   HIPCHK(hipGetLastError());
   h->step += 1;
   return GO2SIM_E_OK;
 }
 
 int go2sim_ppo_update(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, float* std_dev, const int32_t* perm, int n_rows_total, int n_epochs, int n_mini_batches, void* stream) {
-  if (!h || !b || !std_dev || !perm || n_epochs < 1 || n_mini_batches < 1 || n_rows_total < n_mini_batches) return GO2SIM_E_BADARG;
+  if (!h || h->rnn || !b || !std_dev || !perm || n_epochs < 1 || n_mini_batches < 1 || n_rows_total < n_mini_batches) return GO2SIM_E_BADARG;
   const int mbs = n_rows_total / n_mini_batches;
   if (mbs > h->max_rows) return GO2SIM_E_BADARG;
   int rc = go2sim_ppo_reset_stats(h, stream);
@@ -955,6 +1044,205 @@ int go2sim_ppo_stats(go2sim_ppo_t* h, double* out_dev, void* stream) {
   hipLaunchKernelGGL(k_stats, dim3(1), dim3(1), 0, (hipStream_t)stream, h->scal, (double)h->step, out_dev);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;
+}
+
+}  // extern "C"
+
+// ---- recurrent policy (include/go2sim_rnn.h) ------------------------------------------------------------------------------------------------------
+namespace {
+size_t lstm_flat_size(int I, int H) { return (size_t)4 * H * ((size_t)I + H + 2); }
+// flat (weight_ih, weight_hh, bias_ih, bias_hh) <-> the zero-padded device layout, on the host
+void lstm_pack(const go2sim_lstm* h, const float* flat, float* padded, bool to_padded) {
+  const int I = h->I, H = h->H, Ip = h->dev.Ipad, Hp = h->dev.Hpad;
+  float* pd[4] = {padded, padded + (size_t)4 * Hp * Ip, padded + (size_t)4 * Hp * Ip + (size_t)4 * Hp * Hp, padded + (size_t)4 * Hp * Ip + (size_t)4 * Hp * Hp + (size_t)4 * Hp};
+  const size_t fo[4] = {0, (size_t)4 * H * I, (size_t)4 * H * I + (size_t)4 * H * H, (size_t)4 * H * I + (size_t)4 * H * H + (size_t)4 * H};
+  const int cols[4] = {I, H, 1, 1}, ld[4] = {Ip, Hp, 1, 1};
+  for (int m = 0; m < 4; ++m)
+    for (int q = 0; q < 4; ++q)
+      for (int j = 0; j < H; ++j) {
+        float* p = pd[m] + ((size_t)q * Hp + j) * ld[m];
+        float* f = const_cast<float*>(flat) + fo[m] + ((size_t)q * H + j) * cols[m];
+        if (to_padded) memcpy(p, f, sizeof(float) * cols[m]);
+        else memcpy(f, p, sizeof(float) * cols[m]);
+      }
+}
+bool state_ok(const go2sim_ppo_rnn_state_t* s) { return s && s->h_a && s->c_a && s->h_c && s->c_c && s->dones; }
+
+// The launches of one recurrent mini-batch: the env block [e0, e0 + nb) of a rollout of T x B rows; n = T nb rows, row t nb + j is batch row t B + e0 + j.
+int launch_grad_rnn(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const go2sim_ppo_rnn_state_t* s, const float* std_dev, int B, int e0, int nb, hipStream_t st) {
+  const go2sim_mlp *Ma = h->actor, *Mc = h->critic;
+  const int T = h->T, n = T * nb;
+  const float* x[2] = {b->obs, b->critic_obs};
+  const float *h0[2] = {s->h_a, s->h_c}, *c0[2] = {s->c_a, s->c_c};
+  int wmax = 1;                                            // column groups of the widest memory
+  for (int net = 0; net < 2; ++net) { const int g = (h->mem[net]->dev.Hpad / 16 + NWAVE - 1) / NWAVE; if (g > wmax) wmax = g; }
+  hipLaunchKernelGGL(k_rnn_idx, dim3((n + 255) / 256), dim3(256), 0, st, h->idx_b, n, nb, B, e0);
+  for (int t = 0; t < T; ++t) {
+    CellNet c[2];
+    for (int net = 0; net < 2; ++net) {
+      const go2sim_lstm* m = h->mem[net];
+      const size_t H = m->H, Hp = m->dev.Hpad, o = (size_t)t * nb;
+      CellNet& N = c[net];
+      N.M = m->dev; N.x = x[net] + ((size_t)t * B + e0) * m->I; N.ldx = m->I;
+      N.hin = t == 0 ? h0[net] + (size_t)e0 * H : h->r_hout[net] + (o - nb) * H;
+      N.cin = t == 0 ? c0[net] + (size_t)e0 * H : h->r_cout[net] + (o - nb) * H;
+      N.hout = h->r_hout[net] + o * H; N.cout = h->r_cout[net] + o * H;
+      N.gates = h->r_gates[net] + o * 4 * Hp; N.hprev = h->r_hprev[net] + o * H; N.cprev = h->r_cprev[net] + o * H;
+      N.active = 1;
+    }
+    hipLaunchKernelGGL(k_lstm_cell<true>, dim3((nb + TM - 1) / TM, wmax, 2), dim3(64 * NWAVE), 0, st, c[0], c[1],
+                       t == 0 ? (const uint8_t*)nullptr : s->dones + (size_t)(t - 1) * B + e0, nb);
+  }
+  hipLaunchKernelGGL(k_train_forward<false>, dim3((n + TM - 1) / TM, 2), dim3(64 * NWAVE), 0, st, Ma->dev, h->r_hout[0], h->mu, h->ws[0], Mc->dev, h->r_hout[1], h->val,
+                     h->ws[1], h->idx_id, n, n, h->tab[0], h->tab[1]);
+  const int n_wg = (n + WGT - 1) / WGT, ncol = 3 + h->A;
+  HeadArgs ha{};
+  ha.mu = h->mu; ha.val = h->val; ha.b = *b; ha.std_ = std_dev; ha.idx = h->idx_b;
+  ha.dz_actor = h->dz[0][(Ma->n_layers - 1) & 1]; ha.dz_critic = h->dz[1][(Mc->n_layers - 1) & 1];
+  ha.part = h->head_part; ha.n = n; ha.A = h->A; ha.Apad = h->Apad; ha.use_clipped = h->cfg.use_clipped_value_loss;
+  ha.clip = h->cfg.clip_param; ha.vl_coef = h->cfg.value_loss_coef; ha.w = 1.0 / (double)n; ha.n_rows = n;
+  hipLaunchKernelGGL(k_ppo_head<false>, dim3(n_wg), dim3(WGT), 0, st, ha);
+  hipLaunchKernelGGL(k_ppo_finalize, dim3(1), dim3(64), 0, st, h->head_part, n_wg, ncol, n, n, h->A, std_dev, h->scal, h->grads + h->slab, h->cfg.entropy_coef,
+                     h->cfg.desired_kl, h->cfg.lr_min, h->cfg.lr_max, h->cfg.adaptive);
+  const int n_chunks = (n + RCH - 1) / RCH;
+  const size_t slab = h->slab;
+  auto launch_dw_db = [&](const BwdLayer& L0, const BwdLayer& L1, const int32_t* idx) {
+    int groups = 1, nmax = 16;
+    for (const BwdLayer* L : {&L0, &L1}) {
+      if (!L->active) continue;
+      const int g = ((L->N / 16 + DW_TN - 1) / DW_TN) * ((L->K / 16 + DW_TK - 1) / DW_TK);
+      if (g > groups) groups = g;
+      if (L->N > nmax) nmax = L->N;
+    }
+    hipLaunchKernelGGL(k_bwd_dw<false>, dim3(groups, n_chunks, 2), dim3(WGT), 0, st, L0, L1, idx, n, n, h->partial, slab);
+    hipLaunchKernelGGL(k_bwd_db, dim3(nmax / 16, n_chunks, 2), dim3(WGT), 0, st, L0, L1, n, h->partial, slab);
+  };
+  const int depth = Ma->n_layers > Mc->n_layers ? Ma->n_layers : Mc->n_layers;
+  for (int lb = 0; lb < depth; ++lb) {
+    BwdLayer L[2] = {bwd_layer(h, 0, lb, b), bwd_layer(h, 1, lb, b)};
+    for (int net = 0; net < 2; ++net) {
+      const go2sim_mlp* M = net == 0 ? Ma : Mc;
+      if (!L[net].active || M->n_layers - 1 - lb != 0) continue;
+      // the first layer reads the memory's h' [n][H] and hands d loss / d h' back
+      L[net].aprev = h->r_hout[net]; L[net].lda = M->dims[0]; L[net].kmax = M->dims[0]; L[net].gather = 0; L[net].dzprev = h->r_dh[net]; L[net].lin = 1;
+    }
+    launch_dw_db(L[0], L[1], h->idx_id);
+    hipLaunchKernelGGL(k_bwd_da<true>, dim3((n + TM - 1) / TM, 2), dim3(64 * NWAVE), 0, st, L[0], L[1], n);
+  }
+  for (int t = T - 1; t >= 0; --t) {
+    BpttNet c[2];
+    for (int net = 0; net < 2; ++net) {
+      const go2sim_lstm* m = h->mem[net];
+      const size_t H = m->H, Hp = m->dev.Hpad, o = (size_t)t * nb;
+      BpttNet& N = c[net];
+      N.M = m->dev; N.dz_next = h->r_dz[net] + (o + nb) * 4 * Hp; N.dh_mlp = h->r_dh[net] + o * Hp; N.gates = h->r_gates[net] + o * 4 * Hp;
+      N.cprev = h->r_cprev[net] + o * H; N.cout = h->r_cout[net] + o * H; N.dc = h->r_dc[net]; N.dz = h->r_dz[net] + o * 4 * Hp; N.active = 1;
+    }
+    hipLaunchKernelGGL(k_lstm_bptt, dim3((nb + TM - 1) / TM, wmax, 2), dim3(64 * NWAVE), 0, st, c[0], c[1], s->dones + (size_t)t * B + e0, t < T - 1 ? 1 : 0, nb);
+  }
+  // the memories' weight gradients over all n rows: dW_ih = dz^T x (rows through idx_b), dW_hh = dz^T h_prev, db_ih = db_hh = column sums of dz
+  for (int part = 0; part < 2; ++part) {
+    BwdLayer L[2];
+    for (int net = 0; net < 2; ++net) {
+      const go2sim_lstm* m = h->mem[net];
+      const int Hp = m->dev.Hpad, Ip = m->dev.Ipad;
+      const size_t off = h->nA + h->nC + (net == 0 ? 0 : h->nM[0]), o_hh = (size_t)4 * Hp * Ip, o_bi = o_hh + (size_t)4 * Hp * Hp;
+      BwdLayer& Q = L[net];
+      Q = BwdLayer{};
+      Q.active = 1; Q.dz = h->r_dz[net]; Q.N = 4 * Hp;
+      if (part == 0) { Q.aprev = x[net]; Q.K = Ip; Q.lda = m->I; Q.kmax = m->I; Q.gather = 1; Q.W = m->dev.Wih; Q.w_off = off; Q.b_off = off + o_bi; }
+      else { Q.aprev = h->r_hprev[net]; Q.K = Hp; Q.lda = m->H; Q.kmax = m->H; Q.gather = 0; Q.W = m->dev.Whh; Q.w_off = off + o_hh; Q.b_off = off + o_bi + (size_t)4 * Hp; }
+    }
+    launch_dw_db(L[0], L[1], h->idx_b);
+  }
+  hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((slab + WGT - 1) / WGT)), dim3(WGT), 0, st, h->partial, n_chunks, slab, h->grads);
+  HIPCHK(hipGetLastError());
+  return GO2SIM_E_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int go2sim_lstm_create(int device, int n_in, int n_hidden, const float* params, size_t n_params, go2sim_lstm_t** out) {
+  if (!params || !out || n_in < 1 || n_in > MAXW || n_hidden < 1 || n_hidden > MAXW || n_params != lstm_flat_size(n_in, n_hidden)) return GO2SIM_E_BADARG;
+  HIPCHK(hipSetDevice(device));
+  go2sim_lstm* h = new (std::nothrow) go2sim_lstm();
+  if (!h) return GO2SIM_E_NOMEM;
+  h->device = device; h->I = n_in; h->H = n_hidden; h->n_params = n_params;
+  const int Ip = round16(n_in), Hp = round16(n_hidden);
+  h->padded = (size_t)4 * Hp * ((size_t)Ip + Hp + 2);
+  if (hipMalloc((void**)&h->dparams, h->padded * sizeof(float)) != hipSuccess) { delete h; return GO2SIM_E_NOMEM; }
+  h->dev.I = n_in; h->dev.H = n_hidden; h->dev.Ipad = Ip; h->dev.Hpad = Hp;
+  h->dev.Wih = h->dparams; h->dev.Whh = h->dev.Wih + (size_t)4 * Hp * Ip; h->dev.bih = h->dev.Whh + (size_t)4 * Hp * Hp; h->dev.bhh = h->dev.bih + (size_t)4 * Hp;
+  const int rc = go2sim_lstm_set_params(h, params, n_params, nullptr);
+  if (rc != GO2SIM_E_OK) { (void)hipFree(h->dparams); delete h; return rc; }
+  HIPCHK(hipDeviceSynchronize());
+  *out = h;
+  return GO2SIM_E_OK;
+}
+
+int go2sim_lstm_destroy(go2sim_lstm_t* h) {
+  if (!h) return GO2SIM_E_BADARG;
+  (void)hipFree(h->dparams);
+  delete h;
+  return GO2SIM_E_OK;
+}
+
+int go2sim_lstm_set_params(go2sim_lstm_t* h, const float* params, size_t n_params, void* stream) {
+  if (!h || !params || n_params != h->n_params) return GO2SIM_E_BADARG;
+  std::vector<float> packed(h->padded, 0.0f);
+  lstm_pack(h, params, packed.data(), true);
+  HIPCHK(hipMemcpyAsync(h->dparams, packed.data(), h->padded * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));      // `packed` is a temporary
+  return GO2SIM_E_OK;
+}
+
+int go2sim_lstm_get_params(go2sim_lstm_t* h, float* params, size_t n_params, void* stream) {
+  if (!h || !params || n_params != h->n_params) return GO2SIM_E_BADARG;
+  std::vector<float> packed(h->padded);
+  HIPCHK(hipMemcpyAsync(packed.data(), h->dparams, h->padded * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  lstm_pack(h, params, packed.data(), false);
+  return GO2SIM_E_OK;
+}
+
+int go2sim_lstm_step(go2sim_lstm_t* mem_a, const float* x_a, const float* h_in_a, const float* c_in_a, float* h_out_a, float* c_out_a, go2sim_lstm_t* mem_c,
+                     const float* x_c, const float* h_in_c, const float* c_in_c, float* h_out_c, float* c_out_c, const uint8_t* reset, int n_rows, void* stream) {
+  if (!mem_a || !x_a || !h_in_a || !c_in_a || !h_out_a || !c_out_a || h_out_a == h_in_a || n_rows < 0) return GO2SIM_E_BADARG;
+  if (mem_c && (!x_c || !h_in_c || !c_in_c || !h_out_c || !c_out_c || h_out_c == h_in_c)) return GO2SIM_E_BADARG;
+  if (n_rows == 0) return GO2SIM_E_OK;
+  CellNet c[2] = {};
+  c[0].M = mem_a->dev; c[0].x = x_a; c[0].ldx = mem_a->I; c[0].hin = h_in_a; c[0].cin = c_in_a; c[0].hout = h_out_a; c[0].cout = c_out_a; c[0].active = 1;
+  int groups = (mem_a->dev.Hpad / 16 + NWAVE - 1) / NWAVE;
+  if (mem_c) {
+    c[1].M = mem_c->dev; c[1].x = x_c; c[1].ldx = mem_c->I; c[1].hin = h_in_c; c[1].cin = c_in_c; c[1].hout = h_out_c; c[1].cout = c_out_c; c[1].active = 1;
+    const int g = (mem_c->dev.Hpad / 16 + NWAVE - 1) / NWAVE;
+    if (g > groups) groups = g;
+  }
+  hipLaunchKernelGGL(k_lstm_cell<false>, dim3((n_rows + TM - 1) / TM, groups, mem_c ? 2 : 1), dim3(64 * NWAVE), 0, (hipStream_t)stream, c[0], c[1], reset, n_rows);
+  HIPCHK(hipGetLastError());
+  return GO2SIM_E_OK;
+}
+
+int go2sim_ppo_rnn_minibatch_grad(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const go2sim_ppo_rnn_state_t* s, const float* std_dev, int n_envs, int env0, int n_block,
+                                  void* stream) {
+  if (!h || !h->rnn || !std_dev || !batch_ok(b) || !state_ok(s)) return GO2SIM_E_BADARG;
+  if (n_block < 1 || n_block > h->nb_max || env0 < 0 || n_envs < 1 || env0 > n_envs - n_block || (long long)h->T * n_envs > 0x7fffffffLL / MAXW) return GO2SIM_E_BADARG;
+  return launch_grad_rnn(h, b, s, std_dev, n_envs, env0, n_block, (hipStream_t)stream);
+}
+
+int go2sim_ppo_rnn_update(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const go2sim_ppo_rnn_state_t* s, float* std_dev, int n_envs, int n_epochs, int n_mini_batches,
+                          void* stream) {
+  if (!h || !h->rnn || !std_dev || !batch_ok(b) || !state_ok(s) || n_epochs < 1 || n_mini_batches < 1 || n_envs < n_mini_batches || n_envs % n_mini_batches) return GO2SIM_E_BADARG;
+  const int nb = n_envs / n_mini_batches;
+  if (nb > h->nb_max || (long long)h->T * n_envs > 0x7fffffffLL / MAXW) return GO2SIM_E_BADARG;
+  int rc = go2sim_ppo_reset_stats(h, stream);
+  for (int e = 0; e < n_epochs && rc == GO2SIM_E_OK; ++e)
+    for (int i = 0; i < n_mini_batches && rc == GO2SIM_E_OK; ++i) {
+      rc = go2sim_ppo_rnn_minibatch_grad(h, b, s, std_dev, n_envs, i * nb, nb, stream);
+      if (rc == GO2SIM_E_OK) rc = go2sim_ppo_apply(h, std_dev, stream);
+    }
+  return rc;
 }
 
 }  // extern "C"

@@ -13,6 +13,9 @@ parameters with :meth:`load_state_dict`.
 
 State-dict keys are those of the reference class: ``actor.{0,2,4,6}.{weight,bias}``, ``critic.{0,2,4,6}.{weight,bias}``, ``std``.
 Random numbers come from the library's counter-based Philox stream (seed, row, step), not from torch's global generator.
+
+``ActorCriticRecurrent`` (below) is ``rsl_rl.modules.ActorCriticRecurrent`` with one LSTM layer per network (include/go2sim_rnn.h): the same surface plus
+``reset(dones)`` / ``get_hidden_states()``, and the keys ``memory_{a,c}.rnn.{weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0}``.
 """
 import ctypes
 
@@ -221,3 +224,179 @@ class ActorCritic:
 
     def reset(self, dones=None):
         pass
+
+
+# ---- recurrent policy (include/go2sim_rnn.h) --------------------------------------------------------------------------------------------------
+LSTM_KEYS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+
+
+def lstm_shapes(n_in, n_hidden):
+    """[(key suffix, shape)] of one memory in state-dict (and flat) order"""
+    return [("weight_ih_l0", (4 * n_hidden, n_in)), ("weight_hh_l0", (4 * n_hidden, n_hidden)), ("bias_ih_l0", (4 * n_hidden,)), ("bias_hh_l0", (4 * n_hidden,))]
+
+
+def flatten_lstm(state_dict, prefix):
+    """[weight_ih, weight_hh, bias_ih, bias_hh] of ``prefix.rnn.*`` as one float32 vector (the layout go2sim_lstm_create takes) + (n_in, n_hidden)."""
+    ts = []
+    for k in LSTM_KEYS:
+        v = state_dict[f"{prefix}.rnn.{k}"]
+        ts.append(np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float32))
+    if ts[0].ndim != 2 or ts[0].shape[0] % 4 or ts[1].shape != (ts[0].shape[0], ts[0].shape[0] // 4) or ts[2].shape != (ts[0].shape[0],) or ts[3].shape != ts[2].shape:
+        raise Go2SimError(f"{prefix}: not the tensors of a one-layer nn.LSTM: {[t.shape for t in ts]}")
+    return np.concatenate([t.reshape(-1) for t in ts]), (ts[0].shape[1], ts[0].shape[0] // 4)
+
+
+class Lstm:
+    """One go2sim_lstm handle of the product library."""
+
+    def __init__(self, lib, n_in, n_hidden, params, device=0):
+        self.L, self.n_in, self.n_hidden = lib, int(n_in), int(n_hidden)
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        self.n_params = params.size
+        h = ctypes.c_void_p()
+        self.h = None
+        lib.check(lib.fn("lstm_create")(ctypes.c_int(device), ctypes.c_int(n_in), ctypes.c_int(n_hidden), params.ctypes.data_as(ctypes.c_void_p),
+                                        ctypes.c_size_t(params.size), ctypes.byref(h)), "lstm_create")
+        self.h = h
+
+    def set_params(self, params, stream=0):
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        self.L.check(self.L.fn("lstm_set_params")(self.h, params.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(params.size), ctypes.c_void_p(stream)),
+                     "lstm_set_params")
+
+    def get_params(self, stream=0):
+        out = np.empty(self.n_params, np.float32)
+        self.L.check(self.L.fn("lstm_get_params")(self.h, out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(out.size), ctypes.c_void_p(stream)), "lstm_get_params")
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.fn("lstm_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def lstm_step(lib, mem_a, x_a, h_in_a, c_in_a, h_out_a, c_out_a, mem_c=None, x_c=None, h_in_c=None, c_in_c=None, h_out_c=None, c_out_c=None, reset=None, n_rows=None,
+              stream=0):
+    """go2sim_lstm_step: one cell step of one or two memories in one launch (h_out must not be h_in)"""
+    n = x_a.shape[0] if n_rows is None else n_rows
+    rc = lib.fn("lstm_step")(mem_a.h, _ptr(x_a), _ptr(h_in_a), _ptr(c_in_a), _ptr(h_out_a), _ptr(c_out_a), mem_c.h if mem_c is not None else ctypes.c_void_p(0),
+                             _ptr(x_c), _ptr(h_in_c), _ptr(c_in_c), _ptr(h_out_c), _ptr(c_out_c), _ptr(reset), ctypes.c_int(n), ctypes.c_void_p(stream))
+    lib.check(rc, "lstm_step")
+
+
+class ActorCriticRecurrent(ActorCritic):
+    """``rsl_rl.modules.ActorCriticRecurrent`` (rsl-rl-lib==2.2.4) with ``rnn_type="lstm"`` and one layer: ``memory_a = LSTM(num_actor_obs -> H)`` in front of
+    the actor MLP, ``memory_c = LSTM(num_critic_obs -> H)`` in front of the critic MLP (include/go2sim_rnn.h).  ``act`` steps memory_a (and, given critic
+    observations, memory_c), ``evaluate`` steps memory_c, ``reset(dones)`` zeroes the state of the done envs.  State-dict keys beside the parent's:
+    ``memory_{a,c}.rnn.{weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0}``."""
+    is_recurrent = True
+
+    def __init__(self, num_actor_obs, num_critic_obs, num_actions, actor_hidden_dims=(256, 256, 256), critic_hidden_dims=(256, 256, 256), activation="elu",
+                 init_noise_std=1.0, rnn_type="lstm", rnn_hidden_size=256, rnn_num_layers=1, *, device=None, seed=1, **kwargs):
+        from .capi import C
+
+        if str(rnn_type).lower() != "lstm":
+            raise Go2SimError(f"go2sim's recurrent policy is an LSTM; rnn_type {rnn_type!r} is not implemented")
+        if int(rnn_num_layers) != 1:
+            raise Go2SimError(f"go2sim's recurrent policy has one LSTM layer, got rnn_num_layers = {rnn_num_layers}")
+        H = int(rnn_hidden_size)
+        if H < 1 or H > C["GO2SIM_MLP_MAX_WIDTH"]:
+            raise Go2SimError(f"rnn_hidden_size must be in 1 .. {C['GO2SIM_MLP_MAX_WIDTH']} (GO2SIM_MLP_MAX_WIDTH), got {H}")
+        self.rnn_hidden_size = H
+        self._mdims = ((int(num_actor_obs), H), (int(num_critic_obs), H))
+        g = torch.Generator().manual_seed(int(seed) + 0x5eed)              # nn.LSTM's default init: every tensor uniform(-1 / sqrt(H), 1 / sqrt(H))
+        self._mem_init = {}
+        for prefix, (n_in, _) in (("memory_a", self._mdims[0]), ("memory_c", self._mdims[1])):
+            for k, shape in lstm_shapes(n_in, H):
+                self._mem_init[f"{prefix}.rnn.{k}"] = (torch.rand(*shape, generator=g) * 2 - 1) / (H ** 0.5)
+        self._mem = None
+        self._hid = None
+        super().__init__(H, H, num_actions, actor_hidden_dims, critic_hidden_dims, activation, init_noise_std, device=device, seed=seed, **kwargs)
+
+    # ---- parameters ------------------------------------------------------------------------------
+    def load_state_dict(self, state_dict, strict=True):
+        if self._mem is None and not any(k.startswith("memory_") for k in state_dict):
+            state_dict = {**state_dict, **self._mem_init}                   # the constructor's own call: the MLPs' draws, the memories' draws
+        flats = []
+        for prefix, dims in (("memory_a", self._mdims[0]), ("memory_c", self._mdims[1])):
+            p, d = flatten_lstm(state_dict, prefix)
+            if d != dims:
+                raise Go2SimError(f"state dict has {prefix} sizes {d}, expected {dims}")
+            flats.append(p)
+        dev = self.device.index or 0
+        if self._mem is None:
+            self._mem = [Lstm(self._L, *self._mdims[0], flats[0], dev), Lstm(self._L, *self._mdims[1], flats[1], dev)]
+        else:
+            self._mem[0].set_params(flats[0]); self._mem[1].set_params(flats[1])
+        return super().load_state_dict(state_dict, strict)
+
+    def state_dict(self):
+        if self._trainer is None:
+            return dict(self._state)
+        from .ppo import unflatten
+
+        return unflatten(self._trainer.export("PARAMS", self.std).cpu(), self._adims, self._cdims, self._mdims)
+
+    def attach_trainer(self, n_steps, max_envs_per_minibatch, **hyper):
+        """The recurrent go2sim_ppo handle: workspaces for n_steps x max_envs_per_minibatch rows, the memories' parameters in the optimizer's vectors."""
+        from .ppo import PpoHandle
+
+        self._trainer = PpoHandle(self._L, self._actor, self._critic, self.num_actions, int(n_steps) * int(max_envs_per_minibatch), device=self.device,
+                                  memories=tuple(self._mem), n_steps=int(n_steps), **hyper)
+        return self._trainer
+
+    # ---- the memories' state ---------------------------------------------------------------------------
+    def _state_for(self, B):
+        """{"a": [h, c, spare h], "c": [...]} of [B][H] device tensors, zero at the start"""
+        if self._hid is None or self._hid["a"][0].shape[0] != B:
+            z = lambda: torch.zeros(B, self.rnn_hidden_size, device=self.device, dtype=torch.float32)
+            self._hid = {"a": [z(), z(), z()], "c": [z(), z(), z()]}
+        return self._hid
+
+    def _step_memories(self, obs, critic_obs):
+        """One launch for the memories whose observations are given; -> (h_a or None, h_c or None)"""
+        B = (obs if obs is not None else critic_obs).shape[0]
+        hid = self._state_for(B)
+        args, outs = [], []
+        for key, mem, x in (("a", self._mem[0], obs), ("c", self._mem[1], critic_obs)):
+            if x is None:
+                outs.append(None)
+                continue
+            x = x.to(device=self.device, dtype=torch.float32).contiguous()
+            h, c, spare = hid[key]
+            args += [mem, x, h, c, spare, c]
+            hid[key] = [spare, c, h]                                          # the step wrote the spare buffer: h' is the state now
+            outs.append(spare)
+        lstm_step(self._L, *args, n_rows=B, stream=torch.cuda.current_stream(self.device).cuda_stream)
+        return outs
+
+    def _run(self, obs, critic_obs, deterministic):
+        h_a, h_c = self._step_memories(obs, critic_obs)
+        return super()._run(h_a, h_c, deterministic)
+
+    def evaluate(self, critic_observations, **kwargs):
+        _, h_c = self._step_memories(None, critic_observations)
+        return super().evaluate(h_c)
+
+    def reset(self, dones=None, hidden_states=None):
+        """Zero h and c of the done envs (all envs without `dones`)."""
+        if self._hid is None:
+            return
+        for key in ("a", "c"):
+            for t in self._hid[key][:2]:
+                if dones is None:
+                    t.zero_()
+                else:
+                    t.masked_fill_((dones.reshape(-1, 1) != 0).to(t.device), 0.0)
+
+    def get_hidden_states(self):
+        """((h_a, c_a), (h_c, c_c)), each [1][B][H] as nn.LSTM shapes them; views of the live state (None before the first step)"""
+        if self._hid is None:
+            return None, None
+        return tuple((self._hid[k][0].unsqueeze(0), self._hid[k][1].unsqueeze(0)) for k in ("a", "c"))

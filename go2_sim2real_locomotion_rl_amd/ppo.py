@@ -21,12 +21,16 @@ parameters stay bit-identical without ever being re-broadcast.
 Left-right symmetry (rsl_rl's ``symmetry_cfg``): ``PPO(..., symmetry_cfg={"use_data_augmentation": True, "use_mirror_loss": True,
 "mirror_loss_coeff": 0.5, "mirror_tables": env.mirror_tables()})``.  The mirror is three signed permutations given as tables (Go2Env.mirror_tables);
 the kernels read every mini-batch row a second time through them, no mirrored copy is made (include/go2sim_train.h).
+
+A recurrent policy (policy.ActorCriticRecurrent, include/go2sim_rnn.h): ``act`` saves the memories' state at the rollout's first step, ``process_env_step``
+zeroes the state of the done envs, and ``update`` runs rsl_rl's recurrent mini-batches -- env blocks with all their steps, no permutation -- through the
+cell kernel forwards and backwards in time.  It needs ``num_envs`` divisible by ``num_mini_batches`` and refuses ``symmetry_cfg`` and a multi-rank group.
 """
 import ctypes
 
 import torch
 
-from .capi import C, Go2SimError, PpoBatch, PpoCfg, PpoMirror, load_hip_lib
+from .capi import C, Go2SimError, PpoBatch, PpoCfg, PpoMirror, PpoRnnState, load_hip_lib
 from .distributed import allgather_records, broadcast_from_rank0, is_multi, shard_seed
 from .rollout import RolloutStorage
 
@@ -52,14 +56,22 @@ class PpoHandle:
     """One go2sim_ppo handle: pointers only.  `actor` / `critic` are policy.Mlp objects of the product library."""
 
     def __init__(self, lib, actor, critic, n_actions, max_rows, *, clip_param=0.2, desired_kl=0.01, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0,
-                 value_loss_coef=1.0, use_clipped_value_loss=True, adaptive=False, betas=(0.9, 0.999), eps=1e-8, lr_min=1e-5, lr_max=1e-2, device=None):
-        self.L, self.actor, self.critic = lib, actor, critic
+                 value_loss_coef=1.0, use_clipped_value_loss=True, adaptive=False, betas=(0.9, 0.999), eps=1e-8, lr_min=1e-5, lr_max=1e-2, device=None,
+                 memories=None, n_steps=None):
+        """memories = (policy.Lstm of the actor, of the critic) and n_steps: the recurrent handle (include/go2sim_rnn.h), max_rows = n_steps x envs of a mini-batch"""
+        self.L, self.actor, self.critic, self.memories = lib, actor, critic, memories
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         cfg = PpoCfg(clip_param, desired_kl, entropy_coef, learning_rate, max_grad_norm, value_loss_coef, betas[0], betas[1], eps, lr_min, lr_max,
                      int(bool(use_clipped_value_loss)), int(bool(adaptive)))
         h = ctypes.c_void_p()
         self.h = None
-        lib.check(lib.fn("ppo_create")(actor.h, critic.h, ctypes.c_int(n_actions), ctypes.byref(cfg), ctypes.c_int(max_rows), ctypes.byref(h)), "ppo_create")
+        if memories is None:
+            lib.check(lib.fn("ppo_create")(actor.h, critic.h, ctypes.c_int(n_actions), ctypes.byref(cfg), ctypes.c_int(max_rows), ctypes.byref(h)), "ppo_create")
+        else:
+            if not n_steps or max_rows % int(n_steps):
+                raise Go2SimError("a recurrent handle is sized as n_steps x envs per mini-batch rows")
+            lib.check(lib.fn("ppo_create_recurrent")(actor.h, critic.h, memories[0].h, memories[1].h, ctypes.c_int(n_actions), ctypes.byref(cfg), ctypes.c_int(int(n_steps)),
+                                                     ctypes.c_int(max_rows // int(n_steps)), ctypes.byref(h)), "ppo_create_recurrent")
         self.h = h
         n = ctypes.c_size_t()
         lib.check(lib.fn("ppo_n_params")(self.h, ctypes.byref(n)), "ppo_n_params")
@@ -134,8 +146,17 @@ class PpoHandle:
         self.L.check(self.L.fn("ppo_update")(self.h, ctypes.byref(batch), _p(std), _p(perm), ctypes.c_int(n_rows_total), ctypes.c_int(n_epochs),
                                              ctypes.c_int(n_mini_batches), self._stream()), "ppo_update")
 
+    def rnn_minibatch_grad(self, batch, state, std, n_envs, env0, n_block):
+        """forward, head and backward through time of the env block [env0, env0 + n_block) of a rollout of n_steps x n_envs rows (recurrent handle)"""
+        self.L.check(self.L.fn("ppo_rnn_minibatch_grad")(self.h, ctypes.byref(batch), ctypes.byref(state), _p(std), ctypes.c_int(n_envs), ctypes.c_int(env0),
+                                                         ctypes.c_int(n_block), self._stream()), "ppo_rnn_minibatch_grad")
+
+    def rnn_update(self, batch, state, std, n_envs, n_epochs, n_mini_batches):
+        self.L.check(self.L.fn("ppo_rnn_update")(self.h, ctypes.byref(batch), ctypes.byref(state), _p(std), ctypes.c_int(n_envs), ctypes.c_int(n_epochs),
+                                                 ctypes.c_int(n_mini_batches), self._stream()), "ppo_rnn_update")
+
     def export(self, which, std=None):
-        """flat float32 device vector in state-dict order: actor W0, b0, ..., critic W0, b0, ..., std"""
+        """flat float32 device vector in state-dict order: actor W0, b0, ..., critic W0, b0, ..., (memory_a, memory_c: weight_ih, weight_hh, bias_ih, bias_hh,) std"""
         out = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
         self.L.check(self.L.fn("ppo_export")(self.h, ctypes.c_int(C["GO2SIM_PPO_" + which]), _p(out), _p(std), self._stream()), "ppo_export")
         return out
@@ -175,19 +196,33 @@ class PpoHandle:
             pass
 
 
-def state_dict_keys(adims, cdims):
-    """[(key, shape)] in the flat order of go2sim_ppo_export"""
+def make_rnn_state(h_a, c_a, h_c, c_c, dones):
+    """go2sim_ppo_rnn_state_t of contiguous device tensors (kept alive by the caller): four float32 [B][H] arrays and the uint8 dones [T][B]"""
+    s = PpoRnnState()
+    for name, t in zip(PpoRnnState.FIELDS, (h_a, c_a, h_c, c_c, dones)):
+        if t.dtype != (torch.uint8 if name == "dones" else torch.float32) or not t.is_contiguous():
+            raise Go2SimError(f"{name} must be a contiguous {'uint8' if name == 'dones' else 'float32'} tensor")
+        setattr(s, name, t.data_ptr())
+    return s
+
+
+def state_dict_keys(adims, cdims, mdims=None):
+    """[(key, shape)] in the flat order of go2sim_ppo_export; mdims = ((n_in, H) of memory_a, of memory_c) for a recurrent policy"""
     keys = []
     for prefix, dims in (("actor", adims), ("critic", cdims)):
         for l in range(len(dims) - 1):
             keys += [(f"{prefix}.{2 * l}.weight", (dims[l + 1], dims[l])), (f"{prefix}.{2 * l}.bias", (dims[l + 1],))]
+    if mdims is not None:
+        for prefix, (n_in, H) in zip(("memory_a", "memory_c"), mdims):
+            keys += [(f"{prefix}.rnn.weight_ih_l0", (4 * H, n_in)), (f"{prefix}.rnn.weight_hh_l0", (4 * H, H)), (f"{prefix}.rnn.bias_ih_l0", (4 * H,)),
+                     (f"{prefix}.rnn.bias_hh_l0", (4 * H,))]
     keys.append(("std", (adims[-1],)))
     return keys
 
 
-def unflatten(flat, adims, cdims):
+def unflatten(flat, adims, cdims, mdims=None):
     out, o = {}, 0
-    for k, shape in state_dict_keys(adims, cdims):
+    for k, shape in state_dict_keys(adims, cdims, mdims):
         n = 1
         for s in shape:
             n *= s
@@ -196,8 +231,8 @@ def unflatten(flat, adims, cdims):
     return out
 
 
-def flatten(sd, adims, cdims):
-    return torch.cat([sd[k].detach().reshape(-1).to(torch.float32).cpu() for k, _ in state_dict_keys(adims, cdims)])
+def flatten(sd, adims, cdims, mdims=None):
+    return torch.cat([sd[k].detach().reshape(-1).to(torch.float32).cpu() for k, _ in state_dict_keys(adims, cdims, mdims)])
 
 
 class PPO:
@@ -210,6 +245,11 @@ class PPO:
         if unknown or kwargs.get("normalize_advantage_per_mini_batch"):
             raise Go2SimError(f"go2sim's PPO does not implement {sorted(unknown) or ['normalize_advantage_per_mini_batch']} (RND and symmetry are out of scope other than symmetry_cfg with mirror_tables)")
         self.symmetry = self._check_symmetry_cfg(symmetry_cfg)
+        self.recurrent = bool(getattr(policy, "is_recurrent", False))
+        if self.recurrent and self.symmetry is not None:
+            raise Go2SimError("symmetry_cfg with a recurrent policy is not implemented (rsl_rl refuses it too)")
+        if self.recurrent and group is not None and is_multi(group):
+            raise Go2SimError("the sharded (multi-rank) update of a recurrent policy is not implemented")
         self.policy = self.actor_critic = policy
         self.device = policy.device if device is None else torch.device(device)
         self.num_learning_epochs, self.num_mini_batches = int(num_learning_epochs), int(num_mini_batches)
@@ -252,7 +292,15 @@ class PPO:
         self._mbs = T * B // self.num_mini_batches
         if self._mbs < 1:
             raise Go2SimError("fewer rows than mini-batches")
-        self._h = self.policy.attach_trainer(self._mbs, **self._hyper)
+        if self.recurrent:
+            # rsl_rl's recurrent generator: mini-batch m is the env block [m B / nmb, (m + 1) B / nmb) with all T steps
+            if B % self.num_mini_batches:
+                raise Go2SimError(f"a recurrent policy needs num_envs ({B}) divisible by num_mini_batches ({self.num_mini_batches})")
+            self._h = self.policy.attach_trainer(T, B // self.num_mini_batches, **self._hyper)
+            self._saved = [torch.zeros(B, self.policy.rnn_hidden_size, device=dev) for _ in range(4)]      # h_a, c_a, h_c, c_c at the rollout's first act
+            self._rnn_state = make_rnn_state(*self._saved, self.storage.dones)
+        else:
+            self._h = self.policy.attach_trainer(self._mbs, **self._hyper)
         if self.symmetry is not None:                                   # before the record below is sized: a record grows by the mirror-loss sum
             self._h.set_mirror(**self.symmetry)
         self._batch = make_batch(obs=self.obs, critic_obs=self.critic_obs, actions=self.actions, target_values=self.storage.values, returns=self.storage.returns,
@@ -274,6 +322,10 @@ class PPO:
 
     def act(self, obs, critic_obs):
         t = self.t
+        if self.recurrent and t == 0:                                      # the state the update's walk through time starts from
+            hid = self.policy._state_for(obs.shape[0])
+            for dst, src in zip(self._saved, (hid["a"][0], hid["a"][1], hid["c"][0], hid["c"][1])):
+                dst.copy_(src)
         actions = self.policy.act(obs, critic_obs)
         self.obs[t].copy_(obs); self.critic_obs[t].copy_(critic_obs); self.actions[t].copy_(actions)
         self.old_log_prob[t].copy_(self.policy.actions_log_prob); self.old_mu[t].copy_(self.policy.action_mean); self.old_sigma[t].copy_(self.policy.action_std)
@@ -282,14 +334,18 @@ class PPO:
     def process_env_step(self, rewards, dones, infos):
         self.storage.add_transitions(self.t, rewards, dones, self.policy.values, infos.get("time_outs") if infos else None, gamma=self.gamma)
         self.t += 1
+        if self.recurrent:
+            self.policy.reset(dones)
 
     def compute_returns(self, last_critic_obs):
         self.storage.compute_returns(self.policy.evaluate(last_critic_obs), self.gamma, self.lam, group=self.group)
 
     def update(self):
         n = self.num_mini_batches * self._mbs
-        perm = torch.randperm(n, device=self.device, generator=self._gen).to(torch.int32)
-        if self.group is None:
+        perm = None if self.recurrent else torch.randperm(n, device=self.device, generator=self._gen).to(torch.int32)
+        if self.recurrent:
+            self._h.rnn_update(self._batch, self._rnn_state, self.policy.std, self.B, self.num_learning_epochs, self.num_mini_batches)
+        elif self.group is None:
             self._h.update(self._batch, self.policy.std, perm, self.T * self.B, self.num_learning_epochs, self.num_mini_batches)
         else:
             self._update_sharded(perm)

@@ -21,7 +21,7 @@ import torch
 from .capi import Go2SimError
 from .distributed import is_multi, shard_seed, sum_in_rank_order
 from .eval_io import read_checkpoint, save_checkpoint
-from .policy import ActorCritic
+from .policy import ActorCritic, ActorCriticRecurrent
 from .ppo import PPO
 
 
@@ -32,8 +32,10 @@ class OnPolicyRunner:
         if train_cfg.get("empirical_normalization"):
             raise Go2SimError("empirical_normalization is out of scope (the train scripts set it to None)")
         alg_cfg, pol_cfg = dict(train_cfg["algorithm"]), dict(train_cfg["policy"])
-        if alg_cfg.pop("class_name", "PPO") != "PPO" or pol_cfg.pop("class_name", "ActorCritic") != "ActorCritic":
-            raise Go2SimError("go2sim implements class_name PPO / ActorCritic")
+        pol_class = pol_cfg.pop("class_name", "ActorCritic")
+        if alg_cfg.pop("class_name", "PPO") != "PPO" or pol_class not in ("ActorCritic", "ActorCriticRecurrent"):
+            raise Go2SimError("go2sim implements class_name PPO / ActorCritic / ActorCriticRecurrent")
+        pol_class = ActorCriticRecurrent if pol_class == "ActorCriticRecurrent" else ActorCritic
         sym = alg_cfg.get("symmetry_cfg")
         if sym and sym.get("mirror_tables") is None and sym.get("data_augmentation_func") is None:
             alg_cfg["symmetry_cfg"] = dict(sym, mirror_tables=env.mirror_tables())     # the env knows its own observation layout
@@ -45,7 +47,7 @@ class OnPolicyRunner:
         self.group = group if group is not None and is_multi(group) else None
         self.rank = torch.distributed.get_rank(self.group) if self.group is not None else 0
         # the noise stream is the rank's own; the initial weights drawn from the same seed are replaced by rank 0's at the end of init_storage
-        self.policy = ActorCritic(obs.shape[1], critic_obs.shape[1], env.num_actions, device=self.device, seed=shard_seed(seed, self.rank), **pol_cfg)
+        self.policy = pol_class(obs.shape[1], critic_obs.shape[1], env.num_actions, device=self.device, seed=shard_seed(seed, self.rank), **pol_cfg)
         self.alg = PPO(self.policy, device=self.device, seed=seed, group=self.group, **alg_cfg)
         self.num_steps_per_env = int(train_cfg["num_steps_per_env"])
         self.save_interval = int(train_cfg.get("save_interval", 0) or 0)
@@ -114,4 +116,6 @@ class OnPolicyRunner:
         return ckpt.get("infos")
 
     def get_inference_policy(self, device=None):
+        """The deterministic policy as a callable.  A recurrent policy keeps its memory between calls: the caller resets it through
+        ``runner.policy.reset(dones)`` after every env step, as the collection loop does."""
         return self.policy.act_inference

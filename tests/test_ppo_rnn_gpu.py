@@ -1,0 +1,399 @@
+"""The HIP library's recurrent policy (include/go2sim_rnn.h) against the torch float64 reference of tests/ppo_rnn_ref.py over the cases of
+tests/ppo_rnn_cases.py, with the float32 torch evaluation of the same expressions as the yardstick:
+  cell step and T-step unroll:      max|y - y64| <= C_MLP max(max|y32 - y64|, 2^-24 max|y64|)
+  gradients, per parameter tensor:  max|g - g64| <= C_GRAD max(max|g32 - g64|, 2^-24 max|g64|)      (the loss scalars and kl_mean the same way)
+  whole updates, per tensor:        max|p - p64| <= C_UPD max|p32 - p64|
+with the project's constants C_MLP = 7 (include/go2sim_policy.h), C_GRAD = 16 and C_UPD = 8 (include/go2sim_train.h).  Every test prints its ratios
+before it asserts.  Then the bit-level promises (reproducibility, the plain path against bits recorded from the parent build, padding), the refusals
+and the Python classes (ActorCriticRecurrent, PPO, OnPolicyRunner)."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import ppo_cases as PC
+import ppo_ref as R
+import ppo_rnn_cases as RC
+import ppo_rnn_ref as RR
+from test_ppo_gpu import TRAIN_CFG, case_side, walk_env
+
+pytestmark = pytest.mark.gpu
+
+C_MLP = 7
+C_GRAD = 16
+C_UPD = 8
+EPS = 2.0 ** -24
+DEV = "cuda:0"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ppo_plain_small_37_keep.npz")
+
+
+def r16(v):
+    return (v + 15) // 16 * 16
+
+
+def ratio(got, want64, want32):
+    """error over yardstick; a tensor that is exactly zero in float64 and float32 must be exactly zero"""
+    err = float((got - want64).abs().max())
+    yard = max(float((want32.double() - want64).abs().max()), EPS * float(want64.abs().max()))
+    if yard == 0.0:
+        assert err == 0.0
+        return 0.0
+    return err / yard
+
+
+class RnnSide:
+    """The two memories, the two networks, std, the rollout, the saved state and one recurrent go2sim_ppo handle on the GPU"""
+
+    def __init__(self, lib, H, Ia, Ic, adims, cdims, state, rollout, init, T, nb, **hyper):
+        from go2_sim2real_locomotion_rl_amd.policy import Lstm, Mlp, flatten_lstm, flatten_sequential
+        from go2_sim2real_locomotion_rl_amd.ppo import PpoHandle, make_batch, make_rnn_state
+
+        self.adims, self.cdims, self.mdims = adims, cdims, ((Ia, H), (Ic, H))
+        self.actor = Mlp(lib, adims, flatten_sequential(state, "actor", len(adims) - 1)[0])
+        self.critic = Mlp(lib, cdims, flatten_sequential(state, "critic", len(cdims) - 1)[0])
+        self.mem = (Lstm(lib, Ia, H, flatten_lstm(state, "memory_a")[0]), Lstm(lib, Ic, H, flatten_lstm(state, "memory_c")[0]))
+        self.std = state["std"].to(DEV).clone()
+        self.ro = {k: v.to(DEV).contiguous() for k, v in rollout.items()}
+        self.init = {k: v.to(DEV).contiguous() for k, v in init.items()}
+        self.batch = make_batch(**{k: self.ro[k].reshape((-1,) + tuple(self.ro[k].shape[2:])) for k in R.ROW_KEYS})
+        self.rstate = make_rnn_state(self.init["h_a"], self.init["c_a"], self.init["h_c"], self.init["c_c"], self.ro["dones"])
+        hp = dict(clip_param=R.HP["clip_param"], desired_kl=R.HP["desired_kl"], entropy_coef=R.HP["entropy_coef"], learning_rate=R.HP["learning_rate"],
+                  max_grad_norm=R.HP["max_grad_norm"], value_loss_coef=R.HP["value_loss_coef"], use_clipped_value_loss=True, adaptive=True)
+        hp.update(hyper)
+        self.h = PpoHandle(lib, self.actor, self.critic, adims[-1], T * nb, memories=self.mem, n_steps=T, **hp)
+
+    def split(self, flat):
+        from go2_sim2real_locomotion_rl_amd.ppo import unflatten
+
+        return {k: v.double() for k, v in unflatten(flat.cpu(), self.adims, self.cdims, self.mdims).items()}
+
+    def stats(self):
+        s = self.h.stats().cpu()
+        return dict(value_loss=float(s[0]), surrogate=float(s[1]), entropy=float(s[2]), kl_mean=float(s[3]), lr=float(s[4]), grad_norm=float(s[5]),
+                    step=int(s[6]), count=int(s[7])), s
+
+
+def side_of(lib, c, **hyper):
+    return RnnSide(lib, c.H, c.Ia, c.Ic, c.adims, c.cdims, c.state, c.rollout, c.init, c.T, c.nb, **hyper)
+
+
+def real_entry_mask(adims, cdims, mdims):
+    """True where the padded layout (actor | critic | memory_a | memory_c | std) holds a real entry"""
+    parts = []
+    for dims in (adims, cdims):
+        for l in range(len(dims) - 1):
+            w = np.zeros((r16(dims[l + 1]), r16(dims[l])), bool); w[:dims[l + 1], :dims[l]] = True
+            b = np.zeros(r16(dims[l + 1]), bool); b[:dims[l + 1]] = True
+            parts += [w.reshape(-1), b]
+    for n_in, H in mdims:
+        for cols in (n_in, H, None, None):
+            m = np.zeros((4, r16(H), r16(cols) if cols else 1), bool); m[:, :H, :(cols or 1)] = True
+            parts.append(m.reshape(-1))
+    s = np.zeros(r16(adims[-1]), bool); s[:adims[-1]] = True
+    return np.concatenate(parts + [s])
+
+
+# ---- 1. the cell step and the unroll -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(RC.GRAD_CASES))
+def test_cell_unroll_against_float64(hip_lib, name):
+    """T steps of go2sim_lstm_step, both memories per launch, the reset mask of step t + 1 = dones[t]: every h' and the last c"""
+    from go2_sim2real_locomotion_rl_amd.policy import Lstm, flatten_lstm, lstm_step
+
+    c = RC.get_case(name)
+    u64, u32 = c.unrolled(torch.float64), c.unrolled(torch.float32)
+    mems = {"a": Lstm(hip_lib, c.Ia, c.H, flatten_lstm(c.state, "memory_a")[0]), "c": Lstm(hip_lib, c.Ic, c.H, flatten_lstm(c.state, "memory_c")[0])}
+    sl = slice(c.e0, c.e0 + c.nb)
+    x = {"a": c.rollout["obs"][:, sl].contiguous().to(DEV), "c": c.rollout["critic_obs"][:, sl].contiguous().to(DEV)}
+    dones = c.rollout["dones"][:, sl].contiguous().to(DEV)
+    h = {k: [c.init["h_" + k][sl].contiguous().to(DEV), torch.empty(c.nb, c.H, device=DEV)] for k in "ac"}
+    cs = {k: c.init["c_" + k][sl].contiguous().to(DEV) for k in "ac"}
+    hs = {k: [] for k in "ac"}
+    for t in range(c.T):
+        lstm_step(hip_lib, mems["a"], x["a"][t], h["a"][0], cs["a"], h["a"][1], cs["a"], mems["c"], x["c"][t], h["c"][0], cs["c"], h["c"][1], cs["c"],
+                  reset=dones[t - 1] if t > 0 else None, n_rows=c.nb)
+        for k in "ac":
+            h[k] = [h[k][1], h[k][0]]
+            hs[k].append(h[k][0].clone())
+    worst = 0.0
+    for k in "ac":
+        got_h, got_c = torch.stack(hs[k]).cpu().double(), cs[k].cpu().double()
+        for what, got, i in (("h", got_h, 0), ("c", got_c, 1)):
+            q = ratio(got, u64[k][i], u32[k][i])
+            print(f"RATIO cell {name} memory_{k} {what} {q:.3f}")
+            worst = max(worst, q)
+    print(f"RATIO worst cell {name} {worst:.3f}")
+    assert worst <= C_MLP
+
+
+def test_cell_step_alone_and_reset_mask(hip_lib):
+    """One memory per launch (the evaluate path) equals the paired launch bit for bit; a reset row equals a row that enters with zero state."""
+    from go2_sim2real_locomotion_rl_amd.policy import Lstm, flatten_lstm, lstm_step
+
+    c = RC.get_case("h20-t8-n70-every")
+    sl = slice(c.e0, c.e0 + c.nb)
+    ma, mc = Lstm(hip_lib, c.Ia, c.H, flatten_lstm(c.state, "memory_a")[0]), Lstm(hip_lib, c.Ic, c.H, flatten_lstm(c.state, "memory_c")[0])
+    xa, xc = c.rollout["obs"][0, sl].contiguous().to(DEV), c.rollout["critic_obs"][0, sl].contiguous().to(DEV)
+    st = {k: c.init[k][sl].contiguous().to(DEV) for k in c.init}
+    mask = (torch.arange(c.nb) % 3 == 0).to(torch.uint8).to(DEV)
+    new = lambda: torch.full((c.nb, c.H), float("nan"), device=DEV)
+    pa, pc_, pca, pcc = new(), new(), new(), new()
+    lstm_step(hip_lib, ma, xa, st["h_a"], st["c_a"], pa, pca, mc, xc, st["h_c"], st["c_c"], pc_, pcc, reset=mask, n_rows=c.nb)
+    sa, sca, sc, scc = new(), new(), new(), new()
+    lstm_step(hip_lib, ma, xa, st["h_a"], st["c_a"], sa, sca, reset=mask, n_rows=c.nb)
+    lstm_step(hip_lib, mc, xc, st["h_c"], st["c_c"], sc, scc, reset=mask, n_rows=c.nb)
+    for x, y in ((pa, sa), (pca, sca), (pc_, sc), (pcc, scc)):
+        assert torch.isfinite(x).all() and torch.equal(x.view(torch.int32), y.view(torch.int32))
+    keep = (mask == 0).float().unsqueeze(1)
+    za, zca = new(), new()
+    lstm_step(hip_lib, ma, xa, st["h_a"] * keep, st["c_a"] * keep, za, zca, n_rows=c.nb)
+    assert torch.equal(za.view(torch.int32), pa.view(torch.int32)) and torch.equal(zca.view(torch.int32), pca.view(torch.int32))
+    ua = new()
+    lstm_step(hip_lib, ma, xa, st["h_a"], st["c_a"], ua, new(), n_rows=c.nb)
+    assert not torch.equal(ua[mask != 0], pa[mask != 0]) and torch.equal(ua[mask == 0], pa[mask == 0]), "the mask acts on its rows and on no other"
+    # a NaN state behind the mask does not leak
+    bad_h, bad_c = st["h_a"].clone(), st["c_a"].clone()
+    bad_h[mask != 0] = float("nan"); bad_c[mask != 0] = float("inf")
+    na, nca = new(), new()
+    lstm_step(hip_lib, ma, xa, bad_h, bad_c, na, nca, reset=mask, n_rows=c.nb)
+    assert torch.equal(na.view(torch.int32), pa.view(torch.int32)) and torch.equal(nca.view(torch.int32), pca.view(torch.int32))
+
+
+# ---- 2. gradients and scalars ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(RC.GRAD_CASES))
+def test_minibatch_gradients_and_scalars(hip_lib, name):
+    c = RC.get_case(name)
+    g64, s64, _ = c.ref["f64"]
+    g32, s32, _ = c.ref["f32"]
+    side = side_of(hip_lib, c)
+    side.h.rnn_minibatch_grad(side.batch, side.rstate, side.std, c.B, c.e0, c.nb)
+    got = side.split(side.h.export("GRADS"))
+    padded = side.h.export_padded("GRADS").cpu().numpy()
+    st, _ = side.stats()
+    worst, worst_lstm = 0.0, 0.0
+    for k in g64:
+        q = ratio(got[k], g64[k], g32[k])
+        print(f"RATIO grad {name} {k} {q:.3f}")
+        worst = max(worst, q)
+        if k.startswith("memory_"):
+            worst_lstm = max(worst_lstm, q)
+    for k in ("surrogate", "value_loss", "entropy", "kl_mean"):
+        err, yard = abs(st[k] - s64[k]), max(abs(s32[k] - s64[k]), EPS * abs(s64[k]))
+        print(f"RATIO scalar {name} {k} {err / yard:.3f}")
+        worst = max(worst, err / yard)
+    print(f"RATIO worst {name} {worst:.3f} lstm {worst_lstm:.3f}")
+    assert worst <= C_GRAD
+    assert np.isfinite(padded).all() and not padded[~real_entry_mask(c.adims, c.cdims, c.mdims)].any(), "padded gradient entries must be exactly zero"
+    for q in "ac":
+        assert torch.equal(got[f"memory_{q}.rnn.bias_ih_l0"], got[f"memory_{q}.rnn.bias_hh_l0"])
+    assert st["count"] == 1 and st["lr"] == pytest.approx(R.lr_rule(R.HP["learning_rate"], s64["kl_mean"], R.HP["desired_kl"]), rel=1e-15)
+
+
+def test_dones_at_the_last_step_change_no_bit(hip_lib):
+    out = []
+    for name in ("h20-t3-n17-last", "h20-t3-n17-none"):
+        c = RC.get_case(name)
+        side = side_of(hip_lib, c)
+        side.h.rnn_minibatch_grad(side.batch, side.rstate, side.std, c.B, c.e0, c.nb)
+        out.append((side.h.export_padded("GRADS").cpu().numpy().view(np.int32), side.stats()[1].numpy().view(np.int64)))
+    assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1])
+
+
+# ---- 3. whole updates --------------------------------------------------------------------------------------------------------------------------
+def run_update(lib):
+    u = RC.get_update_case()
+    side = RnnSide(lib, u["H"], u["Ia"], u["Ic"], u["adims"], u["cdims"], u["state"], u["rollout"], u["init"], u["T"], u["nb"])
+    side.h.rnn_update(side.batch, side.rstate, side.std, u["B"], u["epochs"], u["n_mb"])
+    return u, side
+
+
+def test_whole_update(hip_lib):
+    u, side = run_update(hip_lib)
+    got = side.split(side.h.export("PARAMS", side.std))
+    st, _ = side.stats()
+    worst = 0.0
+    for k, p64 in u["f64"]["params"].items():
+        err, yard = float((got[k] - p64).abs().max()), float((u["f32"]["params"][k].double() - p64).abs().max())
+        print(f"RATIO update {k} {err / yard:.3f}")
+        worst = max(worst, err / yard)
+    print(f"RATIO worst update {worst:.3f}")
+    assert worst <= C_UPD
+    assert st["step"] == u["epochs"] * u["n_mb"] and st["count"] == st["step"] and st["lr"] == pytest.approx(u["f64"]["lr"], rel=1e-15)
+    for got_s, want in zip((st["value_loss"], st["surrogate"], st["entropy"]), u["f64"]["means"]):
+        assert got_s == pytest.approx(want, rel=1e-5)
+    mask = real_entry_mask(u["adims"], u["cdims"], u["mdims"])
+    for which in ("GRADS", "ADAM_M", "ADAM_V"):
+        assert not side.h.export_padded(which).cpu().numpy()[~mask].any(), which
+    # the optimizer wrote the arrays the cell step reads
+    from go2_sim2real_locomotion_rl_amd.policy import flatten_lstm
+
+    sd = {k: v.float() for k, v in got.items()}
+    for mem, prefix in zip(side.mem, ("memory_a", "memory_c")):
+        assert np.array_equal(mem.get_params().view(np.int32), flatten_lstm(sd, prefix)[0].view(np.int32))
+
+
+def test_update_is_bit_reproducible(hip_lib):
+    outs = []
+    for _ in range(2):
+        _, side = run_update(hip_lib)
+        outs.append([side.h.export(w, side.std).cpu().numpy().view(np.int32) for w in ("PARAMS", "ADAM_M", "ADAM_V", "GRADS")] + [side.stats()[1].numpy().view(np.int64)])
+    for name, x, y in zip(("params", "m", "v", "grads", "stats"), *outs):
+        assert np.array_equal(x, y), name
+    assert np.abs(outs[0][1].view(np.float32)).max() > 0
+
+
+# ---- 4. the plain path -------------------------------------------------------------------------------------------------------------------------
+def test_plain_path_has_the_parent_builds_bits(hip_lib):
+    """A handle without memories: gradients, statistics and, after the step, parameters and Adam's moments equal the bits recorded from the build before the
+    recurrent policy was added (tests/golden/ppo_plain_small_37_keep.npz; go2sim_ppo_minibatch_grad + go2sim_ppo_apply on a tests/ppo_cases.py case)."""
+    c = PC.get_case("small", 37, "keep")
+    side = case_side(hip_lib, c)
+    side.h.minibatch_grad(side.batch, side.std, c.idx.to(DEV))
+    got = {"grads_padded": side.h.export_padded("GRADS").cpu().numpy().view(np.int32), "stats_grad": side.stats()[1].numpy().view(np.int64)}
+    side.h.apply(side.std)
+    got["params"] = side.h.export("PARAMS", side.std).cpu().numpy().view(np.int32)
+    got["adam_m"] = side.h.export_padded("ADAM_M").cpu().numpy().view(np.int32)
+    got["adam_v"] = side.h.export_padded("ADAM_V").cpu().numpy().view(np.int32)
+    got["stats_apply"] = side.stats()[1].numpy().view(np.int64)
+    want = np.load(GOLDEN)
+    assert set(want.files) == set(got)
+    for k in got:
+        assert np.array_equal(got[k], want[k]), k
+
+
+# ---- 5. refusals -------------------------------------------------------------------------------------------------------------------------------
+def test_refusals(hip_lib):
+    import ctypes
+
+    from go2_sim2real_locomotion_rl_amd import PPO, ActorCriticRecurrent, Go2SimError
+    from go2_sim2real_locomotion_rl_amd.capi import C
+
+    mk = lambda **kw: ActorCriticRecurrent(5, 7, 3, [8], [8], rnn_hidden_size=16, **kw)
+    with pytest.raises(Go2SimError, match="rnn_type"):
+        mk(rnn_type="gru")
+    with pytest.raises(Go2SimError, match="one LSTM layer"):
+        mk(rnn_num_layers=2)
+    with pytest.raises(Go2SimError, match="GO2SIM_MLP_MAX_WIDTH"):
+        ActorCriticRecurrent(5, 7, 3, [8], [8], rnn_hidden_size=C["GO2SIM_MLP_MAX_WIDTH"] + 1)
+    pol = mk()
+    tables = {"policy": (list(range(5)), [1.0] * 5), "critic": (list(range(7)), [1.0] * 7), "actions": (list(range(3)), [1.0] * 3)}
+    with pytest.raises(Go2SimError, match="symmetry_cfg"):
+        PPO(pol, symmetry_cfg={"use_mirror_loss": True, "mirror_loss_coeff": 0.5, "mirror_tables": tables})
+    alg = PPO(pol, num_mini_batches=4)
+    with pytest.raises(Go2SimError, match="divisible"):
+        alg.init_storage(10, 3, [5], [7], [3])
+    # the library refuses what the recurrent handle cannot run, and launches nothing
+    c = RC.get_case("h16-t3-n37-step0")
+    side = side_of(hip_lib, c)
+    BAD, st, p = C["GO2SIM_E_BADARG"], ctypes.c_void_p(0), lambda t: ctypes.c_void_p(t.data_ptr())
+    idx = torch.arange(8, dtype=torch.int32, device=DEV)
+    L, h = hip_lib, side.h.h
+    assert L.fn("ppo_minibatch_grad")(h, ctypes.byref(side.batch), p(side.std), p(idx), 8, st) == BAD
+    assert L.fn("ppo_update")(h, ctypes.byref(side.batch), p(side.std), p(idx), 8, 1, 1, st) == BAD
+    rec = torch.zeros(side.h.shard_len, dtype=torch.float64, device=DEV)
+    assert L.fn("ppo_shard_grad")(h, ctypes.byref(side.batch), p(side.std), p(idx), 8, ctypes.c_longlong(8), p(rec), st) == BAD
+    assert L.fn("ppo_shard_reduce")(h, p(rec), 1, p(side.std), st) == BAD
+    grad = L.fn("ppo_rnn_minibatch_grad")
+    assert grad(h, ctypes.byref(side.batch), ctypes.byref(side.rstate), p(side.std), c.B, c.e0, c.nb + 1, st) == BAD      # more envs than the handle was sized for
+    assert grad(h, ctypes.byref(side.batch), ctypes.byref(side.rstate), p(side.std), c.B, c.B - c.nb + 1, c.nb, st) == BAD  # the block leaves the rollout
+    assert grad(h, ctypes.byref(side.batch), None, p(side.std), c.B, c.e0, c.nb, st) == BAD
+    assert L.fn("ppo_rnn_update")(h, ctypes.byref(side.batch), ctypes.byref(side.rstate), p(side.std), c.B, 1, 3, st) == BAD    # 40 envs, 3 mini-batches
+    plain = case_side(hip_lib, PC.get_case("small", 16, "down"))
+    assert grad(plain.h.h, ctypes.byref(side.batch), ctypes.byref(side.rstate), p(side.std), c.B, c.e0, c.nb, st) == BAD          # a handle without memories
+    s, _ = side.stats()
+    assert s["count"] == 0 and s["step"] == 0 and not side.h.export_padded("GRADS").any()
+
+
+def _multi_rank_worker(rank, world, port, out_dir):
+    import torch.distributed as dist
+
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from go2_sim2real_locomotion_rl_amd import PPO, Go2SimError
+
+        class Stub:                                        # the refusal comes before anything touches the policy
+            is_recurrent, device = True, torch.device("cpu")
+
+        try:
+            PPO(Stub(), group=dist.group.WORLD)
+            msg = "accepted"
+        except Go2SimError as e:
+            msg = str(e)
+        open(os.path.join(out_dir, f"r{rank}.txt"), "w").write(msg)
+    finally:
+        dist.destroy_process_group()
+
+
+def test_multi_rank_group_is_refused(tmp_path):
+    import torch.multiprocessing as mp
+
+    from test_ppo_shard_capi import _free_port
+
+    mp.spawn(_multi_rank_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    for r in range(2):
+        assert "multi-rank" in open(tmp_path / f"r{r}.txt").read()
+
+
+# ---- 6. the classes ----------------------------------------------------------------------------------------------------------------------------
+RNN_CFG = dict(TRAIN_CFG, policy=dict(TRAIN_CFG["policy"], class_name="ActorCriticRecurrent", rnn_type="lstm", rnn_hidden_size=32, rnn_num_layers=1))
+MEM_KEYS = {f"memory_{q}.rnn.{k}" for q in "ac" for k in RR.LSTM_KEYS}
+
+
+def test_runner_end_to_end_twice(tmp_path):
+    from go2_sim2real_locomotion_rl_amd import ActorCriticRecurrent, OnPolicyRunner
+    from go2_sim2real_locomotion_rl_amd.eval_io import read_checkpoint
+
+    runs = []
+    for i in range(2):
+        runner = OnPolicyRunner(walk_env(), RNN_CFG)
+        assert isinstance(runner.policy, ActorCriticRecurrent) and runner.alg.recurrent
+        # the hidden state of an env that was done is zero after process_env_step
+        seen = []
+        orig = runner.alg.process_env_step
+
+        def spy(rewards, dones, infos, orig=orig, runner=runner, seen=seen):
+            orig(rewards, dones, infos)
+            (ha, ca), (hc, cc) = runner.policy.get_hidden_states()
+            d = dones != 0
+            seen.append(torch.stack([d.sum(), sum(x[0][d].ne(0).sum() for x in (ha, ca, hc, cc)), sum(x[0][~d].ne(0).sum() for x in (ha, ca, hc, cc))]))
+
+        runner.alg.process_env_step = spy
+        env = runner.env
+        ep = env.episode_length_buf.clone()
+        ep.view(-1)[:8] = int(env.max_episode_length) - 3                     # some envs time out inside the first rollout
+        env.episode_length_buf = ep
+        log = runner.learn(2)
+        seen = torch.stack(seen).cpu()
+        assert int(seen[:, 0].sum()) > 0, "no env was done: the check below would be empty"
+        assert int(seen[:, 1].sum()) == 0 and int(seen[:, 2].min()) > 0
+        assert all(np.isfinite(v) for d in log for v in d.values()) and env.check_errno() == 0
+        runs.append((log, {k: v.numpy().view(np.int32) for k, v in runner.policy.state_dict().items()}, runner))
+    assert runs[0][0] == runs[1][0]
+    assert set(runs[0][1]) == MEM_KEYS | {k for k in runs[0][1] if k.startswith(("actor.", "critic."))} | {"std"} and MEM_KEYS <= set(runs[0][1])
+    for k in runs[0][1]:
+        assert np.array_equal(runs[0][1][k], runs[1][1][k]), k
+    # checkpoint round trip through the runner
+    runner = runs[1][2]
+    path = str(tmp_path / "model_2.pt")
+    runner.save(path)
+    saved = read_checkpoint(path)["model_state_dict"]
+    assert saved["memory_a.rnn.weight_ih_l0"].shape == (4 * 32, 49) and saved["memory_c.rnn.weight_hh_l0"].shape == (4 * 32, 32)
+    fresh = OnPolicyRunner(walk_env(), RNN_CFG)
+    fresh.load(path)
+    back = fresh.policy.state_dict()
+    assert list(back) == list(runner.policy.state_dict())
+    for k, v in runner.policy.state_dict().items():
+        assert np.array_equal(v.numpy().view(np.int32), back[k].numpy().view(np.int32)), k
+    pol = ActorCriticRecurrent(49, 104, 16, [64, 32], [64, 32], rnn_hidden_size=32)
+    loaded, skipped, it = pol.load_checkpoint(path, strict=True)
+    assert it == 2 and not skipped and MEM_KEYS <= set(loaded)
+    # the loaded policies act alike from a reset memory, and the memory matters
+    act_a, act_b = fresh.get_inference_policy(), pol.act_inference
+    fresh.policy.reset(); pol.reset()
+    obs = torch.randn(64, 49, device=DEV, generator=torch.Generator(device=DEV).manual_seed(1))
+    a1, b1 = act_a(obs).clone(), act_b(obs).clone()
+    a2 = act_a(obs).clone()
+    assert a1.shape == (64, 16) and torch.equal(a1, b1) and not torch.equal(a1, a2)
+    fresh.policy.reset(torch.ones(64, device=DEV))
+    assert torch.equal(act_a(obs), a1)

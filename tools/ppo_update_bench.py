@@ -3,6 +3,7 @@
 walk task: T = 24 steps x B = 4096 envs, 49 / 104 observations, 16 actions, two 512-256-128 MLPs, 5 epochs x 4 mini-batches of 24 576 rows.
 
     python tools/ppo_update_bench.py [--updates 5] [--warmup 2] [--envs 4096] [--steps 24] [--shards N] [--symmetry {off,augment,mirror,both}]
+    python tools/ppo_update_bench.py --recurrent [--rnn-hidden 256] [--collection]
 
 Both sides update from the same rollout (collected once with the library's ActorCritic on random observations and rewards) and the same initial
 parameters.  Every shape is warmed up first; device events bracket `--updates` whole updates per side, the two sides alternating update by update so
@@ -16,7 +17,11 @@ of N copies of the record (what the all-gather would deliver; the collective its
 It reports `sharded_ms_per_update` and the difference to `hip_ms_per_update`.
 
 --symmetry sets the walk env's mirror on the HIP side (symmetry_cfg with Go2Env's tables; mirror_loss_coeff 0.5): the update then handles twice the rows.  The
-torch side stays the plain update, so `hip_over_torch` compares unlike work; the time to hold `hip_ms_per_update` against is a plain run at --envs 8192."""
+torch side stays the plain update, so `hip_over_torch` compares unlike work; the time to hold `hip_ms_per_update` against is a plain run at --envs 8192.
+
+--recurrent times the recurrent update (include/go2sim_rnn.h: an LSTM memory of --rnn-hidden units in front of each MLP, env-block mini-batches walked through
+time) against eager torch on the same GPU: nn.LSTM stepped over the [T][block] grid with the done mask between steps, plus the MLPs and the same losses.  --collection adds the closed collection loop (Go2Env walk task at --envs, `--steps` env steps of act / step / process_env_step, compute_returns)
+timed with the MLP policy and with the recurrent one: `collect_ms_mlp`, `collect_ms_recurrent`."""
 import argparse
 import json
 import os
@@ -89,6 +94,97 @@ class TorchPPO:
                 self.opt.step()
 
 
+class TorchRecurrentPPO(TorchPPO):
+    """The recurrent update in eager torch: two nn.LSTM stepped over the [T][block] grid with the done mask between steps, env-block mini-batches"""
+
+    def __init__(self, n_obs, n_cobs, H, adims, cdims, state, device):
+        super().__init__(adims, cdims, state, device)
+        self.mem = [nn.LSTM(n_obs, H).to(device), nn.LSTM(n_cobs, H).to(device)]
+        with torch.no_grad():
+            for prefix, m in zip(("memory_a", "memory_c"), self.mem):
+                for k, p in m.named_parameters():
+                    p.copy_(state[f"{prefix}.rnn.{k}"])
+        self.params = [*self.actor.parameters(), *self.critic.parameters(), *self.mem[0].parameters(), *self.mem[1].parameters(), self.std]
+        self.opt = torch.optim.Adam(self.params, lr=self.lr)
+
+    @staticmethod
+    def unroll(lstm, x, h, c, keep):
+        hs = []
+        for t in range(x.shape[0]):
+            if t > 0:
+                h, c = h * keep[t - 1], c * keep[t - 1]
+            out, (hn, cn) = lstm(x[t:t + 1], (h.unsqueeze(0), c.unsqueeze(0)))
+            h, c = hn[0], cn[0]
+            hs.append(out[0])
+        return torch.cat(hs)
+
+    def update(self, ro, saved, T, B):
+        clip, nb = HP["clip_param"], B // MINI_BATCHES
+        r3 = lambda k, sl: ro[k].reshape(T, B, *ro[k].shape[1:])[:, sl]
+        for _ in range(EPOCHS):
+            for i in range(MINI_BATCHES):
+                sl = slice(i * nb, (i + 1) * nb)
+                keep = (r3("dones", sl) == 0).float().unsqueeze(-1)
+                mu = self.actor(self.unroll(self.mem[0], r3("obs", sl), saved[0][sl], saved[1][sl], keep))
+                v = self.critic(self.unroll(self.mem[1], r3("critic_obs", sl), saved[2][sl], saved[3][sl], keep)).squeeze(-1)
+                row = lambda k: r3(k, sl).reshape(T * nb, *ro[k].shape[1:])
+                sigma = mu * 0.0 + self.std
+                dist = torch.distributions.Normal(mu, sigma)
+                logp = dist.log_prob(row("actions")).sum(-1)
+                entropy = dist.entropy().sum(-1)
+                old_mu, old_sigma = row("old_mu"), row("old_sigma")
+                with torch.inference_mode():
+                    kl = torch.sum(torch.log(sigma / old_sigma + 1.0e-5) + (old_sigma ** 2 + (old_mu - mu) ** 2) / (2.0 * sigma ** 2) - 0.5, dim=-1)
+                    kl_mean = float(kl.mean())
+                if kl_mean > HP["desired_kl"] * 2.0:
+                    self.lr = max(1e-5, self.lr / 1.5)
+                elif 0.0 < kl_mean < HP["desired_kl"] / 2.0:
+                    self.lr = min(1e-2, self.lr * 1.5)
+                for g in self.opt.param_groups:
+                    g["lr"] = self.lr
+                adv, tv, ret = row("advantages"), row("target_values"), row("returns")
+                ratio = torch.exp(logp - row("old_log_prob"))
+                surrogate = torch.max(-adv * ratio, -adv * torch.clamp(ratio, 1.0 - clip, 1.0 + clip)).mean()
+                v_clipped = tv + (v - tv).clamp(-clip, clip)
+                value_loss = torch.max((v - ret).pow(2), (v_clipped - ret).pow(2)).mean()
+                loss = surrogate + HP["value_loss_coef"] * value_loss - HP["entropy_coef"] * entropy.mean()
+                self.opt.zero_grad()
+                loss.backward()
+                nn.utils.clip_grad_norm_(self.params, HP["max_grad_norm"])
+                self.opt.step()
+
+
+def time_collection(dev, B, T, recurrent, H, reps=3):
+    """ms per rollout of the closed loop Go2Env -> policy -> storage (walk task), after one warm-up rollout"""
+    from go2_sim2real_locomotion_rl_amd import PPO, ActorCritic, ActorCriticRecurrent, Go2Env, get_walk_cfgs, init
+
+    init(seed=1)
+    env = Go2Env(B, *get_walk_cfgs(), seed=1, device=dev)
+    obs, extras = env.get_observations()
+    cobs = extras["observations"]["critic"]
+    hidden = [512, 256, 128]
+    pol = (ActorCriticRecurrent(obs.shape[1], cobs.shape[1], env.num_actions, hidden, hidden, rnn_hidden_size=H, device=dev) if recurrent
+           else ActorCritic(obs.shape[1], cobs.shape[1], env.num_actions, hidden, hidden, device=dev))
+    alg = PPO(pol, num_learning_epochs=EPOCHS, num_mini_batches=MINI_BATCHES, schedule="adaptive", gamma=0.99, lam=0.95, **HP)
+    alg.init_storage(B, T, [obs.shape[1]], [cobs.shape[1]], [env.num_actions])
+    total = 0.0
+    for rep in range(reps + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(T):
+            actions = alg.act(obs, cobs)
+            obs, rew, dones, infos = env.step(actions)
+            cobs = infos["observations"]["critic"]
+            alg.process_env_step(rew, dones, infos)
+        alg.compute_returns(cobs)
+        e1.record()
+        torch.cuda.synchronize()
+        alg.t = 0
+        if rep > 0:
+            total += e0.elapsed_time(e1)
+    return total / reps
+
+
 def matrix_flop(adims, cdims, rows):
     f = 0
     for dims in (adims, cdims):
@@ -105,12 +201,17 @@ def main():
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--shards", type=int, default=0, help="also time shard_grad + shard_reduce of N copies of the record + apply per mini-batch")
     ap.add_argument("--symmetry", choices=("off", "augment", "mirror", "both"), default="off", help="mirror symmetry on the HIP side (twice the rows)")
+    ap.add_argument("--recurrent", action="store_true", help="time the recurrent (LSTM) update against eager torch")
+    ap.add_argument("--rnn-hidden", type=int, default=256)
+    ap.add_argument("--collection", action="store_true", help="with --recurrent: also time the closed collection loop with the MLP and the recurrent policy")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ppo_update_bench needs a ROCm GPU: a time taken anywhere else says nothing")
     from go2_sim2real_locomotion_rl_amd import PPO, ActorCritic
 
     dev = torch.device("cuda", 0)
+    if args.recurrent:
+        return main_recurrent(args, dev)
     T, B, nobs, npriv, nact = args.steps, args.envs, 49, 104, 16
     hidden = [512, 256, 128]
     adims, cdims = [nobs, *hidden, nact], [npriv, *hidden, 1]
@@ -183,6 +284,56 @@ def main():
     print(json.dumps({"tool": "ppo_update_bench", "envs": B, "steps": T, "epochs": EPOCHS, "mini_batches": MINI_BATCHES, "updates_timed": args.updates,
                       "hip_ms_per_update": round(hip_ms, 3), "torch_eager_ms_per_update": round(torch_ms, 3), "hip_over_torch": round(hip_ms / torch_ms, 3),
                       "matrix_flop_per_update": flop, "hip_fraction_of_157.3_tflops": round(flop / (hip_ms * 1e-3) / PEAK_FP32_MATRIX, 4), **extra}))
+
+
+def main_recurrent(args, dev):
+    from go2_sim2real_locomotion_rl_amd import PPO, ActorCriticRecurrent
+
+    T, B, nobs, npriv, nact, H = args.steps, args.envs, 49, 104, 16, args.rnn_hidden
+    hidden = [512, 256, 128]
+    adims, cdims = [H, *hidden, nact], [H, *hidden, 1]
+    policy = ActorCriticRecurrent(nobs, npriv, nact, hidden, hidden, rnn_hidden_size=H, device=dev, seed=1)
+    state = {k: v.clone() for k, v in policy.state_dict().items()}
+    alg = PPO(policy, num_learning_epochs=EPOCHS, num_mini_batches=MINI_BATCHES, schedule="adaptive", gamma=0.99, lam=0.95, seed=1, **HP)
+    alg.init_storage(B, T, [nobs], [npriv], [nact])
+    g = torch.Generator(device=dev).manual_seed(0)
+    for _ in range(2):                                                                     # the second rollout starts from a non-zero saved state
+        for _ in range(T):
+            obs, cobs = torch.randn(B, nobs, device=dev, generator=g), torch.randn(B, npriv, device=dev, generator=g)
+            alg.act(obs, cobs)
+            alg.process_env_step(torch.randn(B, device=dev, generator=g), (torch.rand(B, device=dev, generator=g) < 0.01).to(torch.uint8), {})
+        alg.compute_returns(torch.randn(B, npriv, device=dev, generator=g))
+        alg.t = 0
+    flat = lambda t: t.reshape(T * B, *t.shape[2:]).clone()
+    ro = dict(obs=flat(alg.obs), critic_obs=flat(alg.critic_obs), actions=flat(alg.actions), old_mu=flat(alg.old_mu), old_sigma=flat(alg.old_sigma),
+              old_log_prob=flat(alg.old_log_prob), target_values=flat(alg.storage.values), returns=flat(alg.storage.returns),
+              advantages=flat(alg.storage.advantages), dones=flat(alg.storage.dones))
+    saved = [t.clone() for t in alg._saved]
+    ref = TorchRecurrentPPO(nobs, npriv, H, adims, cdims, state, dev)
+    sides = [("hip", alg.update), ("torch", lambda: ref.update(ro, saved, T, B))]
+    for _ in range(args.warmup):
+        for _, fn in sides:
+            fn()
+    torch.cuda.synchronize()
+    ms = {name: 0.0 for name, _ in sides}
+    for _ in range(args.updates):
+        for name, fn in sides:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); fn(); e1.record()
+            torch.cuda.synchronize()
+            ms[name] += e0.elapsed_time(e1)
+    hip_ms, torch_ms = ms["hip"] / args.updates, ms["torch"] / args.updates
+    rows = T * B // MINI_BATCHES
+    flop = (matrix_flop(adims, cdims, rows) + 2 * rows * H * (adims[1] + cdims[1])                     # the MLPs, with the first layers' dA
+            + sum(2 * rows * 4 * H * (n_in + H) * 2 + 2 * rows * 4 * H * H for n_in in (nobs, npriv))) * EPOCHS * MINI_BATCHES   # gates forward + dW, dh through W_hh
+    extra = {}
+    if args.collection:
+        del alg, policy, ref
+        extra = {"collect_ms_mlp": round(time_collection(dev, B, T, False, H), 3), "collect_ms_recurrent": round(time_collection(dev, B, T, True, H), 3)}
+    print(json.dumps({"tool": "ppo_update_bench", "recurrent": True, "rnn_hidden": H, "envs": B, "steps": T, "epochs": EPOCHS, "mini_batches": MINI_BATCHES,
+                      "updates_timed": args.updates, "hip_ms_per_update": round(hip_ms, 3), "torch_eager_ms_per_update": round(torch_ms, 3),
+                      "hip_over_torch": round(hip_ms / torch_ms, 3), "matrix_flop_per_update": flop,
+                      "hip_fraction_of_157.3_tflops": round(flop / (hip_ms * 1e-3) / PEAK_FP32_MATRIX, 4), **extra}))
 
 
 if __name__ == "__main__":

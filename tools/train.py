@@ -2,6 +2,7 @@
 """Trains a Go2 policy with the library's runner, on one GPU or sharded over the ranks of a ``torchrun`` job.
 
     python tools/train.py --task walk --envs 4096 --iterations 1000 --log-dir logs/go2-walk [--symmetry both --mirror-coeff 0.5]
+    python tools/train.py --task walk --envs 4096 --iterations 1000 --recurrent [--rnn-hidden 256]      # LSTM memories in front of both MLPs (one GPU)
     torchrun --nproc-per-node 8 tools/train.py --task walk --envs 4096 --iterations 1000 --log-dir logs/go2-walk
 
 --envs is the env count PER RANK.  Under torchrun every rank builds its shard of the envs (``Go2Env(..., shared_globals=True)``: one curriculum, one
@@ -48,6 +49,8 @@ def main():
     ap.add_argument("--symmetry", choices=("off", "augment", "mirror", "both"), default="off",
                     help="left-right mirror symmetry in the update (rsl_rl's symmetry_cfg): augmentation with the mirrored rows, the mirror loss, or both")
     ap.add_argument("--mirror-coeff", type=float, default=0.5, help="mirror_loss_coeff of --symmetry mirror / both")
+    ap.add_argument("--recurrent", action="store_true", help="train rsl_rl's ActorCriticRecurrent (one LSTM layer per network); one rank, no --symmetry")
+    ap.add_argument("--rnn-hidden", type=int, default=256, help="rnn_hidden_size of --recurrent")
     ap.add_argument("--resume", default=None, help="checkpoint to load on every rank before training")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -81,6 +84,8 @@ def main():
         if args.symmetry != "off":                                                  # the runner fills in the env's own mirror tables
             cfg["algorithm"]["symmetry_cfg"] = {"use_data_augmentation": args.symmetry in ("augment", "both"),
                                                 "use_mirror_loss": args.symmetry in ("mirror", "both"), "mirror_loss_coeff": args.mirror_coeff}
+        if args.recurrent:
+            cfg["policy"] = dict(cfg["policy"], class_name="ActorCriticRecurrent", rnn_type="lstm", rnn_hidden_size=args.rnn_hidden, rnn_num_layers=1)
         runner = OnPolicyRunner(env, cfg, log_dir=args.log_dir, device=device)      # picks up the default process group
         if args.resume:
             runner.load(args.resume)
