@@ -41,10 +41,13 @@
  * the gates' derivatives and of every gradient are exactly zero.  Bounds (tests/test_ppo_rnn_gpu.py), the forms of go2sim_policy.h and go2sim_train.h:
  *   cell step and T-step unroll:  max|y - y64| <= C_MLP max(max|y32 - y64|, 2^-24 max|y64|),  C_MLP = 7
  *   gradients per tensor (MLP, LSTM, std) with C_GRAD = 16, parameters after whole updates with C_UPD = 8.
- * Worst measured over tests/ppo_rnn_cases.py on the MI355X: 3.07 against C_MLP (the actor memory's c after 8 steps of one env, H = 16, random dones;
- * the worst h' is at 1.97); 4.25 against C_GRAD (the single entry of a one-layer critic's bias at T = 1 x 70 envs -- a sum of 70 signed d loss / d v,
- * the kind of entry go2sim_train.h records at 6.76), the worst tensor of a memory at 2.56 (memory_c's two biases, H = 48, 8 steps x 17 envs);
- * 2.65 against C_UPD (2 epochs x 2 mini-batches of 3 steps x 17 envs).  The LSTM tensors stay inside the project's constants: they have none of their own.
+ * Worst measured over tests/ppo_rnn_cases.py on the MI355X (H 16 .. 512, the further column groups of the two kernels included): 4.23 against C_MLP
+ * (the critic memory's c after 2 steps of one env at H = 512, case h512-t2-n1-none; the worst h' is at 3.22, the actor memory of the same case; within
+ * the first column group the worst stays 3.07, the actor memory's c after 8 steps of one env, H = 16, random dones; the product widths H = 256, I = 49 and
+ * 104 are at 1.30, two memories of unequal H in one launch at 2.10); 4.25 against C_GRAD (the single entry of a one-layer critic's bias at T = 1 x 70 envs
+ * -- a sum of 70 signed d loss / d v, the kind of entry go2sim_train.h records at 6.76), the worst tensor of a memory at 2.56 (memory_c's two biases,
+ * H = 48, 8 steps x 17 envs; 1.68 at H = 68, 1.54 at H = 80, 1.41 at H = 256, 1.25 at H = 512); 2.65 against C_UPD (2 epochs x 2 mini-batches of 3 steps x
+ * 17 envs, H = 20; 1.77 at H = 80, 2 steps x 17 envs, memory_c's bias_hh).  The LSTM tensors stay inside the project's constants: they have none of their own.
  *
  * Padded layout of the handle's vectors (gradients, Adam's m and v) with memories: actor | critic | memory_a | memory_c | std, a memory being
  * W_ih [4 Hpad][Ipad], W_hh [4 Hpad][Hpad], b_ih [4 Hpad], b_hh [4 Hpad] with gate q's unit j in row q Hpad + j.  Flat (state-dict) order of

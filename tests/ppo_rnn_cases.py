@@ -2,6 +2,9 @@
 patterns and saved states, at the smallest shapes where each piece can go wrong:
   H   16 (one tile), 20 (padding), 48          I   5, 49          T   1, 3, 8          envs per mini-batch   1, 17, 37, 70
   (T = 8 with 70 envs: 560 rows, across a 512-row chunk; 37 and 70 envs: more than one 32-row tile)
+  and, past the first column group of the LSTM kernels (a workgroup owns NWAVE x 16 = 64 hidden units, blockIdx.y walks the further groups):
+  H   80 (a second group with one live wavefront), 68 (the padded tile lies in the second group), 256 (the product width, four groups, with the
+  product's input widths 49 and 104), 512 (GO2SIM_MLP_MAX_WIDTH, eight groups);   I   64 (no input padding), 104;   envs per mini-batch   5, 33.
   dones: none | the last step only | step 0 | one env on every step | random at rate 0.2;   a zero and a non-zero saved state;   MLP depths 1 and 3.
 The observations are scaled so that the gate pre-activations have a standard deviation near 2: saturated and linear gate regimes both occur
 (check_regimes: at least a tenth of them on each side of +-2).  The per-row PPO inputs are built as in tests/ppo_cases.py, from the float64 forward, so
@@ -30,8 +33,23 @@ GRAD_CASES = {
     "h48-t8-n17-none": (48, 5, 5, 8, 17, "none", "zero", 3, "up"),
     "h20-t1-n70-random": (20, 49, 5, 1, 70, "random", "nonzero", 1, "keep"),
     "h16-t8-n1-random": (16, 49, 49, 8, 1, "random", "zero", 3, "down"),
+    # the further column groups
+    "h80-i64-t2-n33-step0": (80, 64, 49, 2, 33, "step0", "nonzero", 1, "keep"),
+    "h68-t3-n17-random": (68, 49, 5, 3, 17, "random", "nonzero", 3, "down"),
+    "h256-i104-t2-n5-step0": (256, 49, 104, 2, 5, "step0", "nonzero", 3, "up"),
+    "h512-t2-n1-none": (512, 5, 5, 2, 1, "none", "nonzero", 1, "keep"),
 }
-UPDATE_CASE = dict(H=20, Ia=5, Ic=49, T=3, nb=17, n_mb=2, epochs=2, depth=3)      # 2 epochs x 2 mini-batches of 51 rows, random dones, non-zero state
+# A case's seed comes from its position in one of these two lists, never from the table's size: a new name leaves every earlier case's inputs alone.
+SEED_NAMES_0 = ("h16-t1-n1", "h16-t3-n37-step0", "h16-t8-n1-random", "h20-t1-n70-random", "h20-t3-n17-last", "h20-t3-n17-none", "h20-t8-n70-every",
+                "h48-t8-n17-none", "h48-t8-n37-random")                       # the first nine, sorted: seed 5000 + 31 index
+SEED_NAMES_1 = ("h80-i64-t2-n33-step0", "h68-t3-n17-random", "h256-i104-t2-n5-step0", "h512-t2-n1-none")      # seed 9000 + 31 index; append only
+NWAVE = 4                                                   # wavefronts (16-unit column tiles) of a k_lstm_cell / k_lstm_bptt workgroup
+# name: 2 epochs x 2 mini-batches, random dones, non-zero state
+UPDATE_CASES = {
+    "h20-t3-n17": dict(H=20, Ia=5, Ic=49, T=3, nb=17, n_mb=2, epochs=2, depth=3, seed=777),      # mini-batches of 51 rows
+    "h80-i64-t2-n17": dict(H=80, Ia=64, Ic=49, T=2, nb=17, n_mb=2, epochs=2, depth=1, seed=877),  # the second column group through whole updates
+}
+UPDATE_CASE = UPDATE_CASES["h20-t3-n17"]
 
 
 def dims_of(H, depth):
@@ -181,18 +199,19 @@ class Case:
 @functools.lru_cache(maxsize=None)
 def get_case(name):
     # the "last" / "none" pair shares its seed: the dones at the last step must not change anything within the rollout
-    seed = 5000 + 31 * sorted(GRAD_CASES).index(name.replace("-last", "-none") if name.endswith("-last") else name)
+    key = name.replace("-last", "-none") if name.endswith("-last") else name
+    seed = 5000 + 31 * SEED_NAMES_0.index(key) if key in SEED_NAMES_0 else 9000 + 31 * SEED_NAMES_1.index(key)
     return Case(name, seed)
 
 
 @functools.lru_cache(maxsize=None)
-def get_update_case():
-    u = UPDATE_CASE
+def get_update_case(name="h20-t3-n17"):
+    u = UPDATE_CASES[name]
     H, Ia, Ic, T, nb, n_mb = u["H"], u["Ia"], u["Ic"], u["T"], u["nb"], u["n_mb"]
     adims, cdims = dims_of(H, u["depth"])
-    g = torch.Generator().manual_seed(777)
+    g = torch.Generator().manual_seed(u["seed"])
     state = init_state(H, Ia, Ic, adims, cdims, g)
-    ro, init = make_block(H, Ia, Ic, adims, cdims, state, T, nb * n_mb, "random", "nonzero", "keep", 778)
+    ro, init = make_block(H, Ia, Ic, adims, cdims, state, T, nb * n_mb, "random", "nonzero", "keep", u["seed"] + 1)
     m64 = RR.make_model(Ia, Ic, adims, cdims, state, torch.float64)
     for i in range(n_mb):
         check_margins(m64, ro, init, i * nb, nb, None)

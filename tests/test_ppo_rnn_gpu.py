@@ -4,7 +4,8 @@ tests/ppo_rnn_cases.py, with the float32 torch evaluation of the same expression
   gradients, per parameter tensor:  max|g - g64| <= C_GRAD max(max|g32 - g64|, 2^-24 max|g64|)      (the loss scalars and kl_mean the same way)
   whole updates, per tensor:        max|p - p64| <= C_UPD max|p32 - p64|
 with the project's constants C_MLP = 7 (include/go2sim_policy.h), C_GRAD = 16 and C_UPD = 8 (include/go2sim_train.h).  Every test prints its ratios
-before it asserts.  Then the bit-level promises (reproducibility, the plain path against bits recorded from the parent build, padding), the refusals
+before it asserts.  The cases reach past the first column group of k_lstm_cell / k_lstm_bptt (H = 68, 80, 256, 512; two memories of unequal H in one
+launch); what the classes hand to the update is in tests/test_ppo_rnn_collect_gpu.py.  Then the bit-level promises (reproducibility, the plain path against bits recorded from the parent build, padding), the refusals
 and the Python classes (ActorCriticRecurrent, PPO, OnPolicyRunner)."""
 import os
 
@@ -159,6 +160,68 @@ def test_cell_step_alone_and_reset_mask(hip_lib):
     assert torch.equal(na.view(torch.int32), pa.view(torch.int32)) and torch.equal(nca.view(torch.int32), pca.view(torch.int32))
 
 
+@pytest.mark.parametrize("Ha,Hc", [(16, 80), (80, 16)])
+def test_cell_unequal_hidden_sizes(hip_lib, Ha, Hc):
+    """The C ABI lets the two memories differ in H: go2sim_lstm_step sizes the grid by the wider one and the narrower one's further column groups
+    return early.  33 rows, 3 steps with a reset mask on steps 1 and 2: every h' and the last c of both memories against nn.LSTM in float64, and the
+    paired launch against the two single-memory launches bit for bit."""
+    from torch import nn
+
+    from go2_sim2real_locomotion_rl_amd.policy import Lstm, flatten_lstm, lstm_step
+
+    T, n, dims = 3, 33, {"a": (5, Ha), "c": (49, Hc)}
+    g = torch.Generator().manual_seed(4100 + Ha)
+    sd, x, h0, c0 = {}, {}, {}, {}
+    for k, (n_in, H) in dims.items():
+        for key, shape in (("weight_ih_l0", (4 * H, n_in)), ("weight_hh_l0", (4 * H, H)), ("bias_ih_l0", (4 * H,)), ("bias_hh_l0", (4 * H,))):
+            sd[f"memory_{k}.rnn.{key}"] = ((torch.rand(*shape, generator=g) * 2 - 1) / H ** 0.5).float()
+        x[k] = (RC.obs_scale(n_in, H) * torch.randn(T, n, n_in, generator=g)).float()
+        h0[k], c0[k] = (0.5 * torch.randn(n, H, generator=g)).float().clamp(-0.9, 0.9), (0.5 * torch.randn(n, H, generator=g)).float()
+    dones = torch.zeros(T, n, dtype=torch.uint8)
+    dones[0, ::2] = 1; dones[1, 1::3] = 1; dones[1, 32] = 1      # the masks of steps 1 and 2; row 32 is the one row of the second row tile
+    want = {}
+    for prec, dt in (("f64", torch.float64), ("f32", torch.float32)):
+        for k, (n_in, H) in dims.items():
+            lstm = nn.LSTM(n_in, H).to(dt)
+            with torch.no_grad():
+                for key in RR.LSTM_KEYS:
+                    getattr(lstm, key).copy_(sd[f"memory_{k}.rnn.{key}"].to(dt))
+                hs, (_, c), z = RR.unroll(lstm, x[k].to(dt), h0[k].to(dt), c0[k].to(dt), dones)
+            if prec == "f64":
+                RC.check_regimes(z)
+            want[prec, k] = (hs, c)
+    mems = {k: Lstm(hip_lib, n_in, H, flatten_lstm(sd, f"memory_{k}")[0]) for k, (n_in, H) in dims.items()}
+    xd, dd = {k: v.to(DEV) for k, v in x.items()}, dones.to(DEV)
+
+    def run(paired):
+        h = {k: [h0[k].to(DEV), torch.full((n, dims[k][1]), float("nan"), device=DEV)] for k in "ac"}
+        c = {k: c0[k].to(DEV) for k in "ac"}
+        hs = {k: [] for k in "ac"}
+        for t in range(T):
+            reset = dd[t - 1] if t > 0 else None
+            if paired:
+                lstm_step(hip_lib, mems["a"], xd["a"][t], h["a"][0], c["a"], h["a"][1], c["a"], mems["c"], xd["c"][t], h["c"][0], c["c"], h["c"][1], c["c"],
+                          reset=reset, n_rows=n)
+            else:
+                for k in "ac":
+                    lstm_step(hip_lib, mems[k], xd[k][t], h[k][0], c[k], h[k][1], c[k], reset=reset, n_rows=n)
+            for k in "ac":
+                h[k] = [h[k][1], h[k][0]]
+                hs[k].append(h[k][0].clone())
+        return {k: (torch.stack(hs[k]).cpu(), c[k].cpu()) for k in "ac"}
+
+    pair, single = run(True), run(False)
+    worst = 0.0
+    for k in "ac":
+        for what, i in (("h", 0), ("c", 1)):
+            assert torch.isfinite(pair[k][i]).all() and torch.equal(pair[k][i].view(torch.int32), single[k][i].view(torch.int32)), (k, what)
+            q = ratio(pair[k][i].double(), want["f64", k][i], want["f32", k][i])
+            print(f"RATIO cell unequal-{Ha}-{Hc} memory_{k} {what} {q:.3f}")
+            worst = max(worst, q)
+    print(f"RATIO worst cell unequal-{Ha}-{Hc} {worst:.3f}")
+    assert worst <= C_MLP
+
+
 # ---- 2. gradients and scalars ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", sorted(RC.GRAD_CASES))
 def test_minibatch_gradients_and_scalars(hip_lib, name):
@@ -200,23 +263,24 @@ def test_dones_at_the_last_step_change_no_bit(hip_lib):
 
 
 # ---- 3. whole updates --------------------------------------------------------------------------------------------------------------------------
-def run_update(lib):
-    u = RC.get_update_case()
+def run_update(lib, name="h20-t3-n17"):
+    u = RC.get_update_case(name)
     side = RnnSide(lib, u["H"], u["Ia"], u["Ic"], u["adims"], u["cdims"], u["state"], u["rollout"], u["init"], u["T"], u["nb"])
     side.h.rnn_update(side.batch, side.rstate, side.std, u["B"], u["epochs"], u["n_mb"])
     return u, side
 
 
-def test_whole_update(hip_lib):
-    u, side = run_update(hip_lib)
+@pytest.mark.parametrize("name", sorted(RC.UPDATE_CASES))
+def test_whole_update(hip_lib, name):
+    u, side = run_update(hip_lib, name)
     got = side.split(side.h.export("PARAMS", side.std))
     st, _ = side.stats()
     worst = 0.0
     for k, p64 in u["f64"]["params"].items():
         err, yard = float((got[k] - p64).abs().max()), float((u["f32"]["params"][k].double() - p64).abs().max())
-        print(f"RATIO update {k} {err / yard:.3f}")
+        print(f"RATIO update {name} {k} {err / yard:.3f}")
         worst = max(worst, err / yard)
-    print(f"RATIO worst update {worst:.3f}")
+    print(f"RATIO worst update {name} {worst:.3f}")
     assert worst <= C_UPD
     assert st["step"] == u["epochs"] * u["n_mb"] and st["count"] == st["step"] and st["lr"] == pytest.approx(u["f64"]["lr"], rel=1e-15)
     for got_s, want in zip((st["value_loss"], st["surrogate"], st["entropy"]), u["f64"]["means"]):
