@@ -56,6 +56,10 @@ C.update(_C_TRAIN)
 RNN_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_rnn.h")
 _C_RNN, DECLARED_RNN_FUNCS = _parse_header(RNN_HEADER)
 C.update(_C_RNN)
+# the empirical observation normaliser (include/go2sim_norm.h): product library only, a list of its own
+NORM_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_norm.h")
+_C_NORM, DECLARED_NORM_FUNCS = _parse_header(NORM_HEADER)
+C.update(_C_NORM)
 
 
 class PpoCfg(ctypes.Structure):
@@ -146,7 +150,7 @@ class Go2SimLib:
             fn = getattr(self.lib, prefix + name[len("go2sim_"):])
             fn.restype = ctypes.c_int
         if self.is_device:
-            for name in DECLARED_TRAIN_FUNCS + DECLARED_RNN_FUNCS:       # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
+            for name in DECLARED_TRAIN_FUNCS + DECLARED_RNN_FUNCS + DECLARED_NORM_FUNCS:       # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
                 if hasattr(self.lib, name):
                     getattr(self.lib, name).restype = ctypes.c_int
 

@@ -4,6 +4,7 @@
   numbers written by go2_train_walk.py:462-465 and read back by go2_eval_walk.py:500 / go2_eval_stairs.py:486.  ``load_cfgs`` reads it with an
   unpickler that refuses every global, i.e. nothing from the file is imported or executed; ``save_cfgs`` writes the same layout.
 * ``logs/<exp>/model_<it>.pt`` -- rsl_rl 2.2.4 ``OnPolicyRunner.save``: ``{"model_state_dict", "optimizer_state_dict", "iter", "infos"}``.
+  With ``empirical_normalization`` two more keys: ``obs_norm_state_dict`` / ``critic_obs_norm_state_dict`` (``_mean``, ``_var``, ``_std``, ``count``).
   ``read_checkpoint`` loads it with ``torch.load(weights_only=True)``; ``compatible_state_dict`` is the partial load of
   go2_eval_stairs.py:368-450 (``load_model_compat`` / ``_partial_load``): tensors whose shapes match are taken from the file, the rest (typically
   the first critic layer of a checkpoint trained with another privileged-observation width) keep their current values.
@@ -60,10 +61,15 @@ def read_checkpoint(path, map_location="cpu"):
     return ckpt
 
 
-def save_checkpoint(path, model_state_dict, optimizer_state_dict=None, it=0, infos=None):
-    """``OnPolicyRunner.save`` layout (rsl_rl 2.2.4 runners/on_policy_runner.py)."""
-    torch.save({"model_state_dict": {k: v.detach().cpu() for k, v in model_state_dict.items()},
-                "optimizer_state_dict": optimizer_state_dict if optimizer_state_dict is not None else {}, "iter": int(it), "infos": infos}, path)
+def save_checkpoint(path, model_state_dict, optimizer_state_dict=None, it=0, infos=None, *, obs_norm_state_dict=None, critic_obs_norm_state_dict=None):
+    """``OnPolicyRunner.save`` layout (rsl_rl 2.2.4 runners/on_policy_runner.py).  The two normaliser state dicts are written only when given (rsl_rl writes
+    them when ``empirical_normalization`` is on); without them the file has the four keys it always had."""
+    ckpt = {"model_state_dict": {k: v.detach().cpu() for k, v in model_state_dict.items()},
+            "optimizer_state_dict": optimizer_state_dict if optimizer_state_dict is not None else {}, "iter": int(it), "infos": infos}
+    for key, sd in (("obs_norm_state_dict", obs_norm_state_dict), ("critic_obs_norm_state_dict", critic_obs_norm_state_dict)):
+        if sd is not None:
+            ckpt[key] = {k: v.detach().cpu() for k, v in sd.items()}
+    torch.save(ckpt, path)
 
 
 def compatible_state_dict(current, saved):

@@ -3,6 +3,7 @@
 
     python tools/train.py --task walk --envs 4096 --iterations 1000 --log-dir logs/go2-walk [--symmetry both --mirror-coeff 0.5]
     python tools/train.py --task walk --envs 4096 --iterations 1000 --recurrent [--rnn-hidden 256]      # LSTM memories in front of both MLPs (one GPU)
+    python tools/train.py --task walk --envs 4096 --iterations 1000 --empirical-normalization           # running observation statistics in front of the policy
     torchrun --nproc-per-node 8 tools/train.py --task walk --envs 4096 --iterations 1000 --log-dir logs/go2-walk
 
 --envs is the env count PER RANK.  Under torchrun every rank builds its shard of the envs (``Go2Env(..., shared_globals=True)``: one curriculum, one
@@ -51,6 +52,8 @@ def main():
     ap.add_argument("--mirror-coeff", type=float, default=0.5, help="mirror_loss_coeff of --symmetry mirror / both")
     ap.add_argument("--recurrent", action="store_true", help="train rsl_rl's ActorCriticRecurrent (one LSTM layer per network); one rank, no --symmetry")
     ap.add_argument("--rnn-hidden", type=int, default=256, help="rnn_hidden_size of --recurrent")
+    ap.add_argument("--empirical-normalization", action="store_true",
+                    help="normalise both observation sets with running statistics (train_cfg['empirical_normalization']); the checkpoints carry them")
     ap.add_argument("--resume", default=None, help="checkpoint to load on every rank before training")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -86,6 +89,8 @@ def main():
                                                 "use_mirror_loss": args.symmetry in ("mirror", "both"), "mirror_loss_coeff": args.mirror_coeff}
         if args.recurrent:
             cfg["policy"] = dict(cfg["policy"], class_name="ActorCriticRecurrent", rnn_type="lstm", rnn_hidden_size=args.rnn_hidden, rnn_num_layers=1)
+        if args.empirical_normalization:
+            cfg["empirical_normalization"] = True
         runner = OnPolicyRunner(env, cfg, log_dir=args.log_dir, device=device)      # picks up the default process group
         if args.resume:
             runner.load(args.resume)
