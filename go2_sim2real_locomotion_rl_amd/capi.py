@@ -60,6 +60,10 @@ C.update(_C_RNN)
 NORM_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_norm.h")
 _C_NORM, DECLARED_NORM_FUNCS = _parse_header(NORM_HEADER)
 C.update(_C_NORM)
+# the LIDAR terrain scan (include/go2sim_lidar.h): product library only, a list of its own
+LIDAR_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_lidar.h")
+_C_LIDAR, DECLARED_LIDAR_FUNCS = _parse_header(LIDAR_HEADER)
+C.update(_C_LIDAR)
 
 
 class PpoCfg(ctypes.Structure):
@@ -150,7 +154,7 @@ class Go2SimLib:
             fn = getattr(self.lib, prefix + name[len("go2sim_"):])
             fn.restype = ctypes.c_int
         if self.is_device:
-            for name in DECLARED_TRAIN_FUNCS + DECLARED_RNN_FUNCS + DECLARED_NORM_FUNCS:       # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
+            for name in DECLARED_TRAIN_FUNCS + DECLARED_RNN_FUNCS + DECLARED_NORM_FUNCS + DECLARED_LIDAR_FUNCS:       # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
                 if hasattr(self.lib, name):
                     getattr(self.lib, name).restype = ctypes.c_int
 

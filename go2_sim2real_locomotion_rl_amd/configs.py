@@ -495,3 +495,26 @@ def get_stair_cfgs(pls_enable=True):
                         "rel_standing_envs": 0.05})
     command_cfg.pop("cmd_curriculum_start_frac", None)   # not a key of go2_train_stair.py's command_cfg (the env defaults it to 0.1, go2_env_stair.py:584)
     return env_cfg, obs_cfg, reward_cfg, command_cfg
+
+
+def get_lidar_cfg():
+    """`lidar` block of examples/locomotion/go2_stair_train_lidar.py:129-155 (values transcribed)."""
+    return {"enabled": True,
+            "actor_scan": {"x_points": [0.0, 0.15, 0.30, 0.50, 0.80], "y_points": [-0.15, 0.0, 0.15]},
+            "critic_scan": {"num_x": 9, "num_y": 5, "x_range": [-0.4, 0.8], "y_range": [-0.3, 0.3]},
+            "noise": {"height_noise_std": 0.02, "dropout_prob": 0.15, "full_blackout_prob": 0.05, "latency_prob": 0.1, "vertical_offset_std": 0.01},
+            "height_clip": 1.0, "height_scale": 1.0}
+
+
+def get_stair_lidar_cfgs(pls_enable=True, lidar=None):
+    """The stair configuration with the exteroceptive layout of go2_stair_train_lidar.py: its `lidar` block (or `lidar`), its 9 x 5 `height_scan`
+    and its widths (:342-360): 49 + 15 = 64 actor inputs, 64 + 55 + terrain row + 45 = 165 critic inputs (60 / 161 with `pls_enable` off).  Every
+    other value is get_stair_cfgs(): the step kernels are pinned to go2_env_stair.py with those values, and DESIGN.md "LIDAR scan" lists where
+    that script's own values differ."""
+    from .lidar import lidar_widths
+
+    env_cfg, obs_cfg, reward_cfg, command_cfg = get_stair_cfgs(pls_enable)
+    env_cfg["lidar"] = copy.deepcopy(lidar) if lidar is not None else get_lidar_cfg()
+    env_cfg["terrain"]["height_scan"] = {"num_x": 9, "num_y": 5, "x_range": [-0.4, 0.8], "y_range": [-0.3, 0.3]}
+    _, obs_cfg["num_obs"], obs_cfg["num_privileged_obs"] = lidar_widths(env_cfg)
+    return env_cfg, obs_cfg, reward_cfg, command_cfg

@@ -30,6 +30,7 @@
 
 #include "../../include/go2sim.h"
 #include "../../include/go2sim_detmath.h"
+#include "../../include/go2sim_lidar.h"
 
 #define DEV __device__ __forceinline__
 #define DEVN __device__ __noinline__
@@ -7068,6 +7069,14 @@ int go2sim_env_globals(go2sim_t* h, go2sim_env_globals_t* out, void* stream) {
 int go2sim_env_globals_ptr(go2sim_t* h, void** ptr_out) {
   if (!h || !ptr_out) return GO2SIM_E_BADARG;
   *ptr_out = h->dglob;
+  return GO2SIM_E_OK;
+}
+// include/go2sim_lidar.h: the base pose buffers for the LIDAR scan (csrc/go2sim_lidar.hip) to read in place
+int go2sim_lidar_env_pose(go2sim_t* h, const float** pos, const float** quat, long long* comp_stride) {
+  if (!h || !pos || !quat || !comp_stride) return GO2SIM_E_BADARG;
+  *pos = h->P.f + (size_t)FO(base_pos) * h->B;
+  *quat = h->P.f + (size_t)FO(base_quat) * h->B;
+  *comp_stride = (long long)h->B;
   return GO2SIM_E_OK;
 }
 int go2sim_env_set_level(go2sim_t* h, double level, void* stream) {

@@ -26,6 +26,7 @@ import torch
 
 from .capi import C, EnvGlobals, Go2Sim, Go2SimError, load_hip_lib
 from .configs import build_stair_terrain, flatten_base_cfg, flatten_walk_cfg
+from .lidar import LidarScan, check_lidar_widths, env_pose_ptrs, lidar_enabled, lidar_layout
 from .model_blob import pack_model
 
 _DEVICE = None
@@ -74,7 +75,8 @@ def mirror_tables(env_cfg, obs_cfg):
     permutations ``{"policy": (src, sign), "critic": (src, sign), "actions": (src, sign)}`` with ``(M x)[j] = sign[j] * x[src[j]]`` (int32 / float32
     CPU tensors).  Joints and legs are ordered FR, FL, RR, RL: the mirror swaps FR <-> FL and RR <-> RL and hip angles change sign; polar vectors
     take (+, -, +), the angular velocity (-, +, -), the commands (vx, vy, wz) (+, -, -); scalars are fixed points; height-scan point
-    ix * ny + iy maps to ix * ny + (ny - 1 - iy)."""
+    ix * ny + iy maps to ix * ny + (ny - 1 - iy), and so does a point of either grid of the LIDAR layout (the actor scan closes the actor row and
+    follows the observations in the critic row, the critic scan closes the critic row)."""
     num_actions, num_obs, num_priv = env_cfg["num_actions"], obs_cfg["num_obs"], obs_cfg.get("num_privileged_obs")
     base = is_base_env_cfg(env_cfg, obs_cfg)
     leg = [1, 0, 3, 2]
@@ -94,7 +96,21 @@ def mirror_tables(env_cfg, obs_cfg):
     if num_actions not in (12, 16):
         raise Go2SimError(f"no mirror for {num_actions} actions (12 joint targets, optionally 4 per-leg stiffness actions)")
     actions = cat([joints] + ([legs] if num_actions == 16 else []))
-    obs = cat([axial, polar, cmd, joints, joints, actions])              # angular velocity, gravity, commands, dof pos, dof vel, actions
+    obs_blocks = [axial, polar, cmd, joints, joints, actions]            # angular velocity, gravity, commands, dof pos, dof vel, actions
+    lidar = None
+    if not base and lidar_enabled(env_cfg):                              # the LIDAR layout: the actor scan closes the actor row, the critic scan the critic row
+        lidar = lidar_layout(env_cfg["lidar"])
+        for name in ("actor", "critic"):
+            ys = lidar[name + "_y"]
+            if any(ys[k] != -ys[len(ys) - 1 - k] for k in range(len(ys))):
+                raise Go2SimError(f"the lidar {name} scan's y points {ys} are not symmetric about 0: the scan has no mirror")
+
+        def scan_block(shape):
+            nx, ny = shape
+            return ([ix * ny + (ny - 1 - iy) for ix in range(nx) for iy in range(ny)], [1.0] * (nx * ny))
+
+        obs_blocks.append(scan_block(lidar["actor_shape"]))
+    obs = cat(obs_blocks)
     if base or num_priv is None:
         critic = obs
     else:
@@ -102,7 +118,9 @@ def mirror_tables(env_cfg, obs_cfg):
         blocks = [obs, polar, scalar, joint_factors, joint_factors, joint_factors, scalar, polar, legs, polar, polar, scalar]
         extra = num_priv - (num_obs + 55)
         terrain = env_cfg.get("terrain") or {}
-        if extra > 0 and terrain.get("enabled", False):                   # the stair layout: terrain row, then the height scan
+        if lidar is not None:                                              # terrain row, then the critic scan
+            blocks += [scalar, scan_block(lidar["critic_shape"])]
+        elif extra > 0 and terrain.get("enabled", False):                   # the stair layout: terrain row, then the height scan
             hs = terrain.get("height_scan", {})
             nx, ny = int(hs.get("num_x", 11)), int(hs.get("num_y", 7))
             yr = hs.get("y_range", [-0.3, 0.3])
@@ -145,16 +163,25 @@ class Go2Env:
         # stiffness, 12 and 45 / 100 / 178 without) and base (go2_env_base.py: 12 / 45).  The walk family's train scripts set `pls_enable` and
         # `num_privileged_obs`, the base env's set neither (go2_train_crouch.py / go2_train_jump.py)
         self.is_base_env = is_base_env_cfg(env_cfg, obs_cfg)
+        self._lidar = None
         if self.is_base_env:
             fcfg, icfg, self._reward_names = flatten_base_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg)
             self.num_privileged_obs = None
         else:
-            fcfg, icfg, self._reward_names = flatten_walk_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg,
+            # the LIDAR layout (go2_env_stair_lidar.py): the step kernels run the 49 / 105 (45 / 101) layout without a height scan into inner rows,
+            # the scan launch writes the wider rows (include/go2sim_lidar.h)
+            inner_obs_cfg = obs_cfg
+            if lidar_enabled(env_cfg):
+                self._lidar_n_in = n_in = check_lidar_widths(env_cfg, obs_cfg)
+                inner_obs_cfg = dict(obs_cfg, num_obs=n_in, num_privileged_obs=n_in + C["GO2SIM_LIDAR_PRIV_EXTRA"])
+            fcfg, icfg, self._reward_names = flatten_walk_cfg(num_envs, env_cfg, inner_obs_cfg, reward_cfg, command_cfg,
                                                               freeze_curriculum=freeze_curriculum, shared_globals=shared_globals)
             layouts = {(16, 49): (None, 104, 182)}
             if not env_cfg.get("pls_enable", False):
                 layouts[(12, 45)] = (None, 100, 178)
-            if self.num_privileged_obs not in layouts.get((self.num_actions, self.num_obs), ()):
+            if inner_obs_cfg is not obs_cfg:
+                icfg[C["GO2SIM_IC_SCAN_N"]] = 0                                  # the scans are the scan launch's
+            elif self.num_privileged_obs not in layouts.get((self.num_actions, self.num_obs), ()):
                 raise Go2SimError("go2sim implements the walk layout (16 actions, 49 / 104 obs; go2_train_walk.py:300-320), the stair layout "
                                   "(49 / 182 obs; go2_train_stair.py:282-300), both with pls_enable=False (12 actions, 45 / 100 and 45 / 178 obs) "
                                   "and the base layout (12 actions, 45 obs; go2_train_crouch.py / "
@@ -164,9 +191,20 @@ class Go2Env:
                 hf, info = build_stair_terrain(terrain_cfg)
                 self._terrain_info = info
                 self._sim.set_terrain(hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"])
+                if inner_obs_cfg is not obs_cfg:
+                    curr = env_cfg.get("curriculum", {}) or {}
+                    self._lidar = LidarScan(env_cfg["lidar"], num_envs, hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"],
+                                            seed=_SEED if seed is None else int(seed), dr_schedule=env_cfg.get("dr_schedule", None),
+                                            curriculum_enabled=bool(curr.get("enabled", False)), device=self.device)
         self._sim.env_configure(fcfg, icfg)
 
         B, dev = num_envs, self.device
+        if self._lidar is not None:
+            # the step kernels' rows, rewritten every step, and what the scan launch reads in place: the base pose buffers and the curriculum level
+            self._inner_obs = torch.zeros(B, self._lidar_n_in, device=dev)
+            self._inner_priv = torch.zeros(B, self._lidar_n_in + C["GO2SIM_LIDAR_PRIV_EXTRA"], device=dev)
+            self._lidar_pose = env_pose_ptrs(self._sim)
+            self._lidar_level = self._sim.env_globals_ptr() + EnvGlobals.level.offset
         self.obs_buf = torch.zeros(B, self.num_obs, device=dev)
         self.privileged_obs_buf = torch.zeros(B, 45 if self.is_base_env else (self.num_privileged_obs or self.num_obs + 55), device=dev)
         self.rew_buf = torch.zeros(B, device=dev)
@@ -211,7 +249,13 @@ class Go2Env:
         stream = torch.cuda.current_stream(self.device).cuda_stream
         self.obs_buf = torch.empty_like(self.obs_buf)                      # caching allocator: host-side only, no kernel
         self.privileged_obs_buf = torch.empty_like(self.privileged_obs_buf)
-        self._sim.env_step(a, self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self._time_outs, stream)
+        if self._lidar is None:
+            self._sim.env_step(a, self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self._time_outs, stream)
+        else:                                                              # one more launch: the scans and the wider rows, straight into the fresh tensors
+            self._sim.env_step(a, self._inner_obs, self._inner_priv, self.rew_buf, self.reset_buf, self._time_outs, stream)
+            pos, quat, cs = self._lidar_pose
+            self._lidar.step(pos, (cs, 1), quat, (cs, 1), self.reset_buf, self._lidar_level, self._inner_obs, self._inner_priv, self._lidar_n_in,
+                             self.obs_buf, self.privileged_obs_buf)
         self._steps_since_poll += 1
         poll = self._steps_since_poll >= self.errno_poll_every             # RATE_CHECK_ERRNO = 10 substeps, simulator.py:45,267
         if poll:
@@ -278,6 +322,8 @@ class Go2Env:
         """go2_env_walk.py:1242-1245 (reset_idx over all envs; obs_buf is not recomputed, as in the reference)."""
         stream = torch.cuda.current_stream(self.device).cuda_stream
         self._sim.env_reset(stream)
+        if self._lidar is not None:
+            self._lidar.clear()
         self.reset_buf.fill_(1)
         if self.log_extras:
             self._refresh_extras()
@@ -289,6 +335,8 @@ class Go2Env:
         if idx.numel() == 0:
             return
         self._sim.env_reset_idx(idx, idx.numel(), torch.cuda.current_stream(self.device).cuda_stream)
+        if self._lidar is not None:
+            self._lidar.clear(idx)
         self.reset_buf[idx.long()] = 1
         if self.log_extras:
             self._refresh_extras()
@@ -316,6 +364,8 @@ class Go2Env:
         p = torch.as_tensor(pos, device=self.device, dtype=torch.float32).reshape(idx.numel(), 3).contiguous()
         q = None if quat is None else torch.as_tensor(quat, device=self.device, dtype=torch.float32).reshape(idx.numel(), 4).contiguous()
         self._sim.env_respawn(idx, p, q, clear_buffers, idx.numel(), torch.cuda.current_stream(self.device).cuda_stream)
+        if self._lidar is not None and clear_buffers and idx.numel():
+            self._lidar.clear(idx)
 
     def respawn_at_start(self, envs_idx=(0,)):
         """go2_eval_stairs.py:314-361: back to the spawn point of the env's terrain row (or base_init_pos on flat ground)."""

@@ -1,0 +1,174 @@
+"""LidarScan -- the LIDAR terrain scan of the reference's exteroceptive stair env (examples/locomotion/go2_env_stair_lidar.py) on the scan entry points
+of the C ABI (include/go2sim_lidar.h): a noisy 5 x 3 body-frame height profile for the actor, a clean 9 x 5 one for the critic, and the wider rows.
+
+    scan = LidarScan(env_cfg["lidar"], n_envs, hf_int16, horizontal_scale, vertical_scale, origin, seed=1)
+    actor, critic = scan.scan(pos, quat, reset=reset_u8, level=level_f64)     # [n, 3] / [n, 4] device tensors -> [n, n_actor], [n, n_actor + n_critic]
+
+``lidar_layout(cfg)`` reads the dictionary as the reference's ``LidarScanConfig`` (:304) does and needs no GPU; ``Go2Env`` drives the handle through
+``LidarScan.step`` with the env's own pose buffers (one launch per env step)."""
+import ctypes
+
+import numpy as np
+import torch
+
+from .capi import C, Go2SimError, load_hip_lib
+
+
+class LidarCfg(ctypes.Structure):
+    """go2sim_lidar_cfg_t"""
+    DOUBLES = ("height_noise_std", "dropout_prob", "vertical_offset_std", "latency_prob", "full_blackout_prob", "height_clip", "height_scale",
+               "dr_phase1_level", "dr_terrain_gate", "origin_x", "origin_y", "horizontal_scale", "vertical_scale")
+    INTS = ("dr_schedule", "curriculum_enabled", "n_envs", "n_actor", "n_critic", "hf_rows", "hf_cols")
+    _fields_ = [(n, ctypes.c_double) for n in DOUBLES] + [(n, ctypes.c_int) for n in INTS]
+
+
+def lidar_enabled(env_cfg):
+    """True when the cfg selects the LIDAR layout: a ``lidar`` block that is enabled (LidarScanConfig's default) on an enabled terrain."""
+    lidar, terrain = env_cfg.get("lidar"), env_cfg.get("terrain")
+    return bool(lidar) and bool(lidar.get("enabled", True)) and bool(terrain) and bool(terrain.get("enabled", False))
+
+
+def lidar_layout(cfg):
+    """LidarScanConfig.__init__ (go2_env_stair_lidar.py:326-391) as data: the two grids as float32 arrays in point order ix * ny + iy, their shapes,
+    the noise constants, clip and scale.  The grids are formed by torch (linspace, meshgrid) as the reference forms them."""
+    a, c, nz = cfg.get("actor_scan", {}), cfg.get("critic_scan", {}), cfg.get("noise", {})
+    if "x_points" in a:
+        ax, ay = torch.tensor(a["x_points"], dtype=torch.float32), torch.tensor(a["y_points"], dtype=torch.float32)
+        actor_y = [float(v) for v in a["y_points"]]
+    else:
+        xr, yr = a.get("x_range", [0.0, 0.8]), a.get("y_range", [-0.15, 0.15])
+        actor_y = [float(yr[0]), float(yr[1])]
+        ax = torch.linspace(float(xr[0]), float(xr[1]), int(a.get("num_x", 5)))
+        ay = torch.linspace(float(yr[0]), float(yr[1]), int(a.get("num_y", 3)))
+    cxr, cyr = c.get("x_range", [-0.4, 0.8]), c.get("y_range", [-0.3, 0.3])
+    cx = torch.linspace(float(cxr[0]), float(cxr[1]), int(c.get("num_x", 9)))
+    cy = torch.linspace(float(cyr[0]), float(cyr[1]), int(c.get("num_y", 5)))
+
+    def grid(x, y):
+        gx, gy = torch.meshgrid(x, y, indexing="ij")
+        return np.ascontiguousarray(torch.stack([gx.reshape(-1), gy.reshape(-1)]).numpy(), dtype=np.float32)
+
+    return {"actor_xy": grid(ax, ay), "critic_xy": grid(cx, cy), "actor_shape": (len(ax), len(ay)), "critic_shape": (len(cx), len(cy)),
+            "actor_y": actor_y, "critic_y": [float(cyr[0]), float(cyr[1])],     # the cfg's own y points or y range: what a mirror needs symmetric
+            "height_noise_std": float(nz.get("height_noise_std", 0.02)), "dropout_prob": float(nz.get("dropout_prob", 0.15)),
+            "full_blackout_prob": float(nz.get("full_blackout_prob", 0.05)), "latency_prob": float(nz.get("latency_prob", 0.1)),
+            "vertical_offset_std": float(nz.get("vertical_offset_std", 0.01)),
+            "height_clip": float(cfg.get("height_clip", 1.0)), "height_scale": float(cfg.get("height_scale", 1.0))}
+
+
+def lidar_widths(env_cfg):
+    """(n_in, num_obs, num_privileged_obs) of the LIDAR layout these cfgs give: the proprioceptive width, then go2_stair_train_lidar.py:342-360."""
+    lay = lidar_layout(env_cfg["lidar"])
+    n_in = 33 + int(env_cfg["num_actions"])
+    n_actor, n_critic = lay["actor_xy"].shape[1], lay["critic_xy"].shape[1]
+    return n_in, n_in + n_actor, n_in + n_actor + C["GO2SIM_LIDAR_PRIV_EXTRA"] + n_critic
+
+
+def check_lidar_widths(env_cfg, obs_cfg):
+    """The proprioceptive width n_in of a LIDAR cfg whose obs_cfg carries the widths its grids give; Go2SimError (naming both) otherwise."""
+    n_in, want_obs, want_priv = lidar_widths(env_cfg)
+    num_actions, have = int(env_cfg["num_actions"]), (obs_cfg["num_obs"], obs_cfg.get("num_privileged_obs"))
+    if num_actions not in ((16,) if env_cfg.get("pls_enable", False) else (16, 12)):
+        raise Go2SimError(f"the LIDAR layout has 16 actions (12 with pls_enable=False), got {num_actions}")
+    if have != (want_obs, want_priv):
+        raise Go2SimError(f"obs_cfg gives num_obs / num_privileged_obs = {have[0]} / {have[1]}, the lidar cfg's grids give {want_obs} / {want_priv}")
+    return n_in
+
+
+def env_pose_ptrs(sim):
+    """(pos, quat, component stride): the device addresses of a Go2Sim handle's base pose buffers (go2sim_lidar_env_pose)."""
+    pos, quat, cs = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_longlong()
+    sim.L.check(sim.L.fn("lidar_env_pose")(sim.h, ctypes.byref(pos), ctypes.byref(quat), ctypes.byref(cs)), "lidar_env_pose")
+    return pos.value, quat.value, cs.value
+
+
+def _p(t):
+    return ctypes.c_void_p(0) if t is None else ctypes.c_void_p(t if isinstance(t, int) else t.data_ptr())
+
+
+class LidarScan:
+    def __init__(self, cfg, n_envs, hf_int16, horizontal_scale, vertical_scale, origin, *, seed=1, dr_schedule=None, curriculum_enabled=False, device=None):
+        if not torch.cuda.is_available():
+            raise Go2SimError("no ROCm GPU visible: the go2sim product path has no CPU fallback")
+        if not cfg.get("enabled", True):
+            raise Go2SimError("the lidar cfg is disabled: there is nothing to scan")
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.n_envs = int(n_envs)
+        self.layout = lay = lidar_layout(cfg)
+        self.n_actor, self.n_critic = lay["actor_xy"].shape[1], lay["critic_xy"].shape[1]
+        hf = np.ascontiguousarray(hf_int16, dtype=np.int16)
+        c = LidarCfg()
+        for name in ("height_noise_std", "dropout_prob", "vertical_offset_std", "latency_prob", "full_blackout_prob", "height_clip", "height_scale"):
+            setattr(c, name, lay[name])
+        c.dr_schedule = int(dr_schedule is not None)
+        if dr_schedule is not None:                                         # the defaults of flatten_walk_cfg
+            c.dr_phase1_level, c.dr_terrain_gate = float(dr_schedule.get("phase1_level", 0.15)), float(dr_schedule.get("terrain_gate", 0.50))
+        c.curriculum_enabled = int(bool(curriculum_enabled))
+        c.origin_x, c.origin_y = float(origin[0]), float(origin[1])
+        c.horizontal_scale, c.vertical_scale = float(horizontal_scale), float(vertical_scale)
+        c.n_envs, c.n_actor, c.n_critic, c.hf_rows, c.hf_cols = self.n_envs, self.n_actor, self.n_critic, hf.shape[0], hf.shape[1]
+        self._L = load_hip_lib()
+        self.h = None
+        h = ctypes.c_void_p()
+        self._L.check(self._L.fn("lidar_create")(ctypes.c_int(self.device.index or 0), ctypes.byref(c), hf.ctypes.data_as(ctypes.c_void_p),
+                                                 lay["actor_xy"].ctypes.data_as(ctypes.c_void_p), lay["critic_xy"].ctypes.data_as(ctypes.c_void_p),
+                                                 ctypes.c_uint64(int(seed)), ctypes.byref(h)), "lidar_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._L.fn("lidar_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    # ---- the step counter and the stored actor scan ---------------------------------------------------------------------------
+    @property
+    def step_count(self):
+        v = ctypes.c_uint32()
+        self._L.check(self._L.fn("lidar_get_step")(self.h, ctypes.byref(v)), "lidar_get_step")
+        return v.value
+
+    @step_count.setter
+    def step_count(self, value):
+        self._L.check(self._L.fn("lidar_set_step")(self.h, ctypes.c_uint32(int(value))), "lidar_set_step")
+
+    def stored_scan(self):
+        """float32 [n_envs, n_actor] CPU tensor; waits for the stream."""
+        out = np.zeros((self.n_envs, self.n_actor), np.float32)
+        self._L.check(self._L.fn("lidar_get_scan")(self.h, out.ctypes.data_as(ctypes.c_void_p), self._stream()), "lidar_get_scan")
+        return torch.from_numpy(out)
+
+    def set_stored_scan(self, scan):
+        a = np.ascontiguousarray(torch.as_tensor(scan).detach().cpu().to(torch.float32).numpy())
+        if a.shape != (self.n_envs, self.n_actor):
+            raise Go2SimError(f"the stored scan has shape {(self.n_envs, self.n_actor)}, got {a.shape}")
+        self._L.check(self._L.fn("lidar_set_scan")(self.h, a.ctypes.data_as(ctypes.c_void_p), self._stream()), "lidar_set_scan")
+
+    def clear(self, envs_idx=None):
+        """Stored actor scan := 0 for ``envs_idx`` (int32 device tensor) or for every env."""
+        n = 0 if envs_idx is None else envs_idx.numel()
+        self._L.check(self._L.fn("lidar_clear")(self.h, _p(envs_idx), ctypes.c_int(n), self._stream()), "lidar_clear")
+
+    # ---- the step ----------------------------------------------------------------------------------------------------------
+    def step(self, pos, pos_strides, quat, quat_strides, reset, level, obs, priv, n_in, obs_out, priv_out):
+        """go2sim_lidar_step with device tensors or raw device addresses; strides are (component, env) in elements."""
+        rc = self._L.fn("lidar_step")(self.h, ctypes.c_int(self.n_envs), _p(pos), ctypes.c_longlong(pos_strides[0]), ctypes.c_longlong(pos_strides[1]),
+                                      _p(quat), ctypes.c_longlong(quat_strides[0]), ctypes.c_longlong(quat_strides[1]), _p(reset), _p(level), _p(obs), _p(priv),
+                                      ctypes.c_int(n_in), _p(obs_out), _p(priv_out), self._stream())
+        self._L.check(rc, "lidar_step")
+
+    def scan(self, pos, quat, reset=None, level=None):
+        """The scans alone of poses given as [n, 3] / [n, 4] float32 device tensors: -> (actor [n, n_actor], actor | critic [n, n_actor + n_critic])."""
+        pos, quat = pos.contiguous(), quat.contiguous()
+        actor = torch.empty(self.n_envs, self.n_actor, device=self.device)
+        both = torch.empty(self.n_envs, self.n_actor + self.n_critic, device=self.device)
+        self.step(pos, (1, 3), quat, (1, 4), reset, level, None, None, 0, actor, both)
+        return actor, both
