@@ -64,6 +64,10 @@ C.update(_C_NORM)
 LIDAR_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_lidar.h")
 _C_LIDAR, DECLARED_LIDAR_FUNCS = _parse_header(LIDAR_HEADER)
 C.update(_C_LIDAR)
+# the four-value stair info (include/go2sim_stairinfo.h): product library only, a list of its own
+STAIRINFO_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_stairinfo.h")
+_C_STAIRINFO, DECLARED_STAIRINFO_FUNCS = _parse_header(STAIRINFO_HEADER)
+C.update(_C_STAIRINFO)
 
 
 class PpoCfg(ctypes.Structure):
@@ -154,7 +158,7 @@ class Go2SimLib:
             fn = getattr(self.lib, prefix + name[len("go2sim_"):])
             fn.restype = ctypes.c_int
         if self.is_device:
-            for name in DECLARED_TRAIN_FUNCS + DECLARED_RNN_FUNCS + DECLARED_NORM_FUNCS + DECLARED_LIDAR_FUNCS:       # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
+            for name in DECLARED_TRAIN_FUNCS + DECLARED_RNN_FUNCS + DECLARED_NORM_FUNCS + DECLARED_LIDAR_FUNCS + DECLARED_STAIRINFO_FUNCS:       # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
                 if hasattr(self.lib, name):
                     getattr(self.lib, name).restype = ctypes.c_int
 

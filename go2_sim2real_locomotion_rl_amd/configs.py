@@ -435,7 +435,10 @@ def get_stair_terrain_cfg():
 
 
 def build_stair_terrain(terrain_cfg):
-    """Heightfield (int16 [x cells, y cells]) and placement metadata, as go2_env_stair.py:47-186 builds them."""
+    """Heightfield (int16 [x cells, y cells]) and placement metadata, as go2_env_stair.py:47-186 builds them.  With `step_depth_range` or
+    `step_depths_m` every difficulty row has a tread depth of its own (go2_env_stair_lidar_2.py:83-216, `_build_stair_terrain_row_depths`)."""
+    if "step_depth_range" in terrain_cfg or "step_depths_m" in terrain_cfg:
+        return _build_stair_terrain_row_depths(terrain_cfg)
     g = terrain_cfg.get
     h_scale, v_scale = g("horizontal_scale", 0.05), g("vertical_scale", 0.005)
     num_rows, row_width_m = g("num_difficulty_rows", 10), g("row_width_m", 6.0)
@@ -470,6 +473,65 @@ def build_stair_terrain(terrain_cfg):
             "num_difficulty_rows": num_rows, "row_centers": [(cx + origin[0], cy + origin[1], cz + origin[2]) for cx, cy, cz in centers],
             "step_heights_m": step_heights_m.tolist(), "total_x_m": total_x * h_scale, "total_y_m": total_y * h_scale,
             "num_flights": num_flights, "num_steps": num_steps, "step_depth_m": g("step_depth_m", 0.30)}
+    return hf, info
+
+
+def stair_step_depths(terrain_cfg):
+    """Per-row tread depths in metres (float64 [rows]) of a terrain cfg with `step_depths_m` or `step_depth_range`.  An explicit `step_depths_m` (one
+    value per row) is taken as given.  Otherwise np.linspace(lo, hi, rows) is permuted -- the reference shuffles with the unseeded global generator
+    (go2_env_stair_lidar_2.py:105-106); here the permutation comes from np.random.default_rng(step_depth_seed, default 0), so that every call, from
+    whichever place, gives the same field."""
+    num_rows = terrain_cfg.get("num_difficulty_rows", 10)
+    if "step_depths_m" in terrain_cfg:
+        depths = np.asarray(terrain_cfg["step_depths_m"], np.float64)
+        if depths.shape != (num_rows,):
+            raise ValueError(f"terrain step_depths_m needs one value per difficulty row ({num_rows}), got shape {depths.shape}")
+        return depths.copy()
+    r = terrain_cfg.get("step_depth_range", [0.25, 0.25])
+    if isinstance(r, (int, float)):
+        r = [float(r), float(r)]
+    depths = np.linspace(r[0], r[1], num_rows)
+    return depths[np.random.default_rng(terrain_cfg.get("step_depth_seed", 0)).permutation(num_rows)]
+
+
+def _build_stair_terrain_row_depths(terrain_cfg):
+    """go2_env_stair_lidar_2.py:83-216: every flight section is as long as the deepest row's, a shallower row's ascent is padded at its top height
+    and its descent at 0.  The placement (origin, scales, row centres) does not depend on the depths."""
+    g = terrain_cfg.get
+    h_scale, v_scale = g("horizontal_scale", 0.05), g("vertical_scale", 0.005)
+    num_rows, row_width_m = g("num_difficulty_rows", 10), g("row_width_m", 6.0)
+    num_steps, num_flights = g("num_steps", 6), g("num_flights", 4)
+    depths_m = stair_step_depths(terrain_cfg)
+    depth_cells = np.maximum(1, np.round(depths_m / h_scale).astype(int))
+    cells = lambda metres: max(1, int(round(metres / h_scale)))
+    flat_before, flat_top = cells(g("flat_before_m", 2.0)), cells(g("flat_top_m", 1.5))
+    flat_gap, flat_after, row_width = cells(g("flat_gap_m", 1.5)), cells(g("flat_after_m", 2.0)), cells(row_width_m)
+    stair_section = num_steps * int(np.max(depth_cells))
+    total_x = flat_before + num_flights * (2 * stair_section + flat_top + flat_gap) + flat_after
+    total_y = num_rows * row_width
+    step_heights_m = np.linspace(g("step_height_min", 0.02), g("step_height_max", 0.15), num_rows)
+    step_units = np.round(step_heights_m / v_scale).astype(np.int16)
+    hf = np.zeros((total_x, total_y), dtype=np.int16)
+    centers = []
+    for row in range(num_rows):
+        y0, y1, sh, dc = row * row_width, (row + 1) * row_width, step_units[row], int(depth_cells[row])
+        x = flat_before
+        for _ in range(num_flights):
+            top = num_steps * sh
+            for s in range(num_steps):
+                hf[x + s * dc:x + (s + 1) * dc, y0:y1] = (s + 1) * sh
+            hf[x + num_steps * dc:x + stair_section + flat_top, y0:y1] = top          # the padding at the top height, then the flat top
+            x += stair_section + flat_top
+            for s in range(num_steps):
+                hf[x + s * dc:x + (s + 1) * dc, y0:y1] = top - (s + 1) * sh
+            hf[x + num_steps * dc:x + stair_section, y0:y1] = 0                        # the padding at ground level
+            x += stair_section + flat_gap
+        centers.append((flat_before * h_scale * 0.5, (y0 + row_width / 2.0) * h_scale, 0.0))
+    origin = (0.0, -total_y * h_scale / 2.0, 0.0)
+    info = {"heightfield": hf, "horizontal_scale": h_scale, "vertical_scale": v_scale, "terrain_origin": origin,
+            "num_difficulty_rows": num_rows, "row_centers": [(cx + origin[0], cy + origin[1], cz + origin[2]) for cx, cy, cz in centers],
+            "step_heights_m": step_heights_m.tolist(), "step_depths_m": depths_m.tolist(), "total_x_m": total_x * h_scale,
+            "total_y_m": total_y * h_scale, "num_flights": num_flights, "num_steps": num_steps}
     return hf, info
 
 
@@ -517,4 +579,34 @@ def get_stair_lidar_cfgs(pls_enable=True, lidar=None):
     env_cfg["lidar"] = copy.deepcopy(lidar) if lidar is not None else get_lidar_cfg()
     env_cfg["terrain"]["height_scan"] = {"num_x": 9, "num_y": 5, "x_range": [-0.4, 0.8], "y_range": [-0.3, 0.3]}
     _, obs_cfg["num_obs"], obs_cfg["num_privileged_obs"] = lidar_widths(env_cfg)
+    return env_cfg, obs_cfg, reward_cfg, command_cfg
+
+
+def get_stair_info_cfg():
+    """`stair_info` block of examples/locomotion/go2_stair_train_lidar_2.py:120-143 (values transcribed)."""
+    return {"enabled": True,
+            "edge_detection": {"max_range": 0.27, "threshold": 0.02, "num_samples": 14},
+            "edge_dist_scale": 3.7, "height_scale": 5.0, "depth_scale": 3.3, "direction_scale": 1.0,
+            "noise": {"edge_noise_std": 0.04, "height_noise_std": 0.01, "depth_noise_std": 0.01, "direction_flip_prob": 0.03,
+                      "full_blackout_prob": 0.05, "latency_prob": 0.10}}
+
+
+def get_stair_info_terrain_cfg():
+    """`terrain` block of go2_stair_train_lidar_2.py:150-165: a tread depth per difficulty row, risers up to 0.20 m."""
+    return {"enabled": True, "horizontal_scale": 0.05, "vertical_scale": 0.005, "num_difficulty_rows": 13, "row_width_m": 6.0,
+            "step_depth_range": [0.22, 0.30], "num_steps": 6, "num_flights": 4, "step_height_min": 0.02, "step_height_max": 0.20,
+            "flat_before_m": 2.0, "flat_top_m": 1.5, "flat_gap_m": 1.5, "flat_after_m": 2.0}
+
+
+def get_stair_info_cfgs(pls_enable=True, stair_info=None):
+    """The stair configuration with the four-value stair info of go2_stair_train_lidar_2.py: its `stair_info` block (or `stair_info`), its terrain
+    block (a tread depth per row; no height scan) and its widths (:318-327): 49 + 4 = 53 actor inputs, 53 + 55 + terrain row + 4 = 113 critic
+    inputs (49 / 109 with `pls_enable` off).  Every other value is get_stair_cfgs(): the step kernels are pinned to go2_env_stair.py with those
+    values, and DESIGN.md "Stair info" lists where that script's own values differ."""
+    from .stairinfo import stair_info_widths
+
+    env_cfg, obs_cfg, reward_cfg, command_cfg = get_stair_cfgs(pls_enable)
+    env_cfg["stair_info"] = copy.deepcopy(stair_info) if stair_info is not None else get_stair_info_cfg()
+    env_cfg["terrain"] = get_stair_info_terrain_cfg()
+    _, obs_cfg["num_obs"], obs_cfg["num_privileged_obs"] = stair_info_widths(env_cfg)
     return env_cfg, obs_cfg, reward_cfg, command_cfg

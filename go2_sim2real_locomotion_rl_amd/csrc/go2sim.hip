@@ -31,6 +31,7 @@
 #include "../../include/go2sim.h"
 #include "../../include/go2sim_detmath.h"
 #include "../../include/go2sim_lidar.h"
+#include "../../include/go2sim_stairinfo.h"
 
 #define DEV __device__ __forceinline__
 #define DEVN __device__ __noinline__
@@ -7077,6 +7078,12 @@ int go2sim_lidar_env_pose(go2sim_t* h, const float** pos, const float** quat, lo
   *pos = h->P.f + (size_t)FO(base_pos) * h->B;
   *quat = h->P.f + (size_t)FO(base_quat) * h->B;
   *comp_stride = (long long)h->B;
+  return GO2SIM_E_OK;
+}
+// include/go2sim_stairinfo.h: the terrain-row buffer for the stair info (csrc/go2sim_stairinfo.hip) to read in place
+int go2sim_stairinfo_env_rows(go2sim_t* h, const int** terrain_row) {
+  if (!h || !terrain_row) return GO2SIM_E_BADARG;
+  *terrain_row = h->P.i + (size_t)IO(terrain_row) * h->B;
   return GO2SIM_E_OK;
 }
 int go2sim_env_set_level(go2sim_t* h, double level, void* stream) {

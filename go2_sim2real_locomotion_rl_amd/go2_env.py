@@ -28,6 +28,7 @@ from .capi import C, EnvGlobals, Go2Sim, Go2SimError, load_hip_lib
 from .configs import build_stair_terrain, flatten_base_cfg, flatten_walk_cfg
 from .lidar import LidarScan, check_lidar_widths, env_pose_ptrs, lidar_enabled, lidar_layout
 from .model_blob import pack_model
+from .stairinfo import NUM_STAIR_INFO, StairInfo, check_one_exteroceptive_layout, check_stair_info_widths, env_rows_ptr, stair_info_enabled
 
 _DEVICE = None
 _SEED = 1
@@ -76,7 +77,8 @@ def mirror_tables(env_cfg, obs_cfg):
     CPU tensors).  Joints and legs are ordered FR, FL, RR, RL: the mirror swaps FR <-> FL and RR <-> RL and hip angles change sign; polar vectors
     take (+, -, +), the angular velocity (-, +, -), the commands (vx, vy, wz) (+, -, -); scalars are fixed points; height-scan point
     ix * ny + iy maps to ix * ny + (ny - 1 - iy), and so does a point of either grid of the LIDAR layout (the actor scan closes the actor row and
-    follows the observations in the critic row, the critic scan closes the critic row)."""
+    follows the observations in the critic row, the critic scan closes the critic row).  The four columns of the stair-info layout (edge distance, riser
+    height, tread depth, direction up / down along the forward axis) are fixed points with sign +1 in both rows."""
     num_actions, num_obs, num_priv = env_cfg["num_actions"], obs_cfg["num_obs"], obs_cfg.get("num_privileged_obs")
     base = is_base_env_cfg(env_cfg, obs_cfg)
     leg = [1, 0, 3, 2]
@@ -110,6 +112,10 @@ def mirror_tables(env_cfg, obs_cfg):
             return ([ix * ny + (ny - 1 - iy) for ix in range(nx) for iy in range(ny)], [1.0] * (nx * ny))
 
         obs_blocks.append(scan_block(lidar["actor_shape"]))
+    stair_info = not base and stair_info_enabled(env_cfg)
+    four = (list(range(NUM_STAIR_INFO)), [1.0] * NUM_STAIR_INFO)
+    if stair_info:                                                       # the stair-info layout: the actor four close the actor row, the clean four the critic row
+        obs_blocks.append(four)
     obs = cat(obs_blocks)
     if base or num_priv is None:
         critic = obs
@@ -120,6 +126,8 @@ def mirror_tables(env_cfg, obs_cfg):
         terrain = env_cfg.get("terrain") or {}
         if lidar is not None:                                              # terrain row, then the critic scan
             blocks += [scalar, scan_block(lidar["critic_shape"])]
+        elif stair_info:                                                   # terrain row, then the clean four
+            blocks += [scalar, four]
         elif extra > 0 and terrain.get("enabled", False):                   # the stair layout: terrain row, then the height scan
             hs = terrain.get("height_scan", {})
             nx, ny = int(hs.get("num_x", 11)), int(hs.get("num_y", 7))
@@ -143,6 +151,7 @@ class Go2Env:
                  freeze_curriculum=False, log_extras=True, errno_poll_every=5, shared_globals=False):
         if show_viewer:
             raise Go2SimError("the viewer is outside the accelerated path (SURVEY.md section 8f)")
+        check_one_exteroceptive_layout(env_cfg)
         self.device = device if device is not None else (_DEVICE if _DEVICE is not None else init())
         self.num_envs = num_envs
         self.num_obs = obs_cfg["num_obs"]
@@ -164,6 +173,7 @@ class Go2Env:
         # `num_privileged_obs`, the base env's set neither (go2_train_crouch.py / go2_train_jump.py)
         self.is_base_env = is_base_env_cfg(env_cfg, obs_cfg)
         self._lidar = None
+        self._stairinfo = None
         if self.is_base_env:
             fcfg, icfg, self._reward_names = flatten_base_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg)
             self.num_privileged_obs = None
@@ -171,7 +181,13 @@ class Go2Env:
             # the LIDAR layout (go2_env_stair_lidar.py): the step kernels run the 49 / 105 (45 / 101) layout without a height scan into inner rows,
             # the scan launch writes the wider rows (include/go2sim_lidar.h)
             inner_obs_cfg = obs_cfg
-            if lidar_enabled(env_cfg):
+            use_stair_info = stair_info_enabled(env_cfg)
+            if use_stair_info:
+                # the stair-info layout (go2_env_stair_lidar_2.py): inner rows as for the LIDAR layout, the stair-info launch writes the wider rows
+                # (include/go2sim_stairinfo.h)
+                self._lidar_n_in = n_in = check_stair_info_widths(env_cfg, obs_cfg)
+                inner_obs_cfg = dict(obs_cfg, num_obs=n_in, num_privileged_obs=n_in + C["GO2SIM_STAIRINFO_PRIV_EXTRA"])
+            elif lidar_enabled(env_cfg):
                 self._lidar_n_in = n_in = check_lidar_widths(env_cfg, obs_cfg)
                 inner_obs_cfg = dict(obs_cfg, num_obs=n_in, num_privileged_obs=n_in + C["GO2SIM_LIDAR_PRIV_EXTRA"])
             fcfg, icfg, self._reward_names = flatten_walk_cfg(num_envs, env_cfg, inner_obs_cfg, reward_cfg, command_cfg,
@@ -191,7 +207,14 @@ class Go2Env:
                 hf, info = build_stair_terrain(terrain_cfg)
                 self._terrain_info = info
                 self._sim.set_terrain(hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"])
-                if inner_obs_cfg is not obs_cfg:
+                if use_stair_info:
+                    curr = env_cfg.get("curriculum", {}) or {}
+                    depths = info.get("step_depths_m", [float(info.get("step_depth_m", 0.30))] * info["num_difficulty_rows"])
+                    self._stairinfo = StairInfo(env_cfg["stair_info"], num_envs, hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"],
+                                                info["step_heights_m"], depths, seed=_SEED if seed is None else int(seed),
+                                                dr_schedule=env_cfg.get("dr_schedule", None), curriculum_enabled=bool(curr.get("enabled", False)),
+                                                device=self.device)
+                elif inner_obs_cfg is not obs_cfg:
                     curr = env_cfg.get("curriculum", {}) or {}
                     self._lidar = LidarScan(env_cfg["lidar"], num_envs, hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"],
                                             seed=_SEED if seed is None else int(seed), dr_schedule=env_cfg.get("dr_schedule", None),
@@ -199,12 +222,14 @@ class Go2Env:
         self._sim.env_configure(fcfg, icfg)
 
         B, dev = num_envs, self.device
-        if self._lidar is not None:
+        if self._lidar is not None or self._stairinfo is not None:
             # the step kernels' rows, rewritten every step, and what the scan launch reads in place: the base pose buffers and the curriculum level
             self._inner_obs = torch.zeros(B, self._lidar_n_in, device=dev)
             self._inner_priv = torch.zeros(B, self._lidar_n_in + C["GO2SIM_LIDAR_PRIV_EXTRA"], device=dev)
             self._lidar_pose = env_pose_ptrs(self._sim)
             self._lidar_level = self._sim.env_globals_ptr() + EnvGlobals.level.offset
+        if self._stairinfo is not None:
+            self._stairinfo_rows = env_rows_ptr(self._sim)                 # the env's terrain rows, read on the device at step time
         self.obs_buf = torch.zeros(B, self.num_obs, device=dev)
         self.privileged_obs_buf = torch.zeros(B, 45 if self.is_base_env else (self.num_privileged_obs or self.num_obs + 55), device=dev)
         self.rew_buf = torch.zeros(B, device=dev)
@@ -249,7 +274,12 @@ class Go2Env:
         stream = torch.cuda.current_stream(self.device).cuda_stream
         self.obs_buf = torch.empty_like(self.obs_buf)                      # caching allocator: host-side only, no kernel
         self.privileged_obs_buf = torch.empty_like(self.privileged_obs_buf)
-        if self._lidar is None:
+        if self._stairinfo is not None:                                    # one more launch: both fours and the wider rows, straight into the fresh tensors
+            self._sim.env_step(a, self._inner_obs, self._inner_priv, self.rew_buf, self.reset_buf, self._time_outs, stream)
+            pos, quat, cs = self._lidar_pose
+            self._stairinfo.step(pos, (cs, 1), quat, (cs, 1), self._stairinfo_rows, self.reset_buf, self._lidar_level, self._inner_obs, self._inner_priv,
+                                 self._lidar_n_in, self.obs_buf, self.privileged_obs_buf)
+        elif self._lidar is None:
             self._sim.env_step(a, self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self._time_outs, stream)
         else:                                                              # one more launch: the scans and the wider rows, straight into the fresh tensors
             self._sim.env_step(a, self._inner_obs, self._inner_priv, self.rew_buf, self.reset_buf, self._time_outs, stream)
@@ -291,9 +321,21 @@ class Go2Env:
             "cmd_ranges": {"lin_vel_x_range": d[g["cmd_x_lo"]:g["cmd_x_lo"] + 2], "lin_vel_y_range": d[g["cmd_y_lo"]:g["cmd_y_lo"] + 2],
                            "ang_vel_range": d[g["cmd_yaw_lo"]:g["cmd_yaw_lo"] + 2]},
         }
+        if self._stairinfo is not None:                                     # go2_env_stair_lidar_2.py:1232: the DR level the stair-info noise scales with
+            self.extras["curriculum"]["stair_noise_level"] = self._dr_level_of(d[g["level"]])
         self.extras["domain_randomization"] = {"friction": f[g["friction"]], "mass_shift": f[g["mass_shift"]],
                                                "com_shift": f[g["com_shift"]:g["com_shift"] + 3],
                                                "leg_mass_shift": f[g["leg_mass_shift"]:g["leg_mass_shift"] + 4]}
+
+    def _dr_level_of(self, level):
+        """_get_dr_level (go2_env_stair_lidar_2.py) of the curriculum level, a 0-dim float64 device tensor: no synchronisation."""
+        curr, sched = self.env_cfg.get("curriculum", {}) or {}, self.env_cfg.get("dr_schedule", None)
+        t = level if curr.get("enabled", False) else torch.ones_like(level)
+        if sched is None:
+            return t
+        p1, gate = float(sched.get("phase1_level", 0.15)), float(sched.get("terrain_gate", 0.50))
+        pr = ((t - gate) / max(1e-6, 1.0 - gate)).clamp(0.0, 1.0)
+        return torch.where(t < gate, torch.full_like(t, p1), p1 + (1.0 - p1) * pr)
 
     def _raise_on_errno(self, v):
         """rigid_solver.py:1189-1213: the exceptions scene.step raises from its errno poll."""
@@ -324,6 +366,8 @@ class Go2Env:
         self._sim.env_reset(stream)
         if self._lidar is not None:
             self._lidar.clear()
+        if self._stairinfo is not None:
+            self._stairinfo.clear()
         self.reset_buf.fill_(1)
         if self.log_extras:
             self._refresh_extras()
@@ -337,6 +381,8 @@ class Go2Env:
         self._sim.env_reset_idx(idx, idx.numel(), torch.cuda.current_stream(self.device).cuda_stream)
         if self._lidar is not None:
             self._lidar.clear(idx)
+        if self._stairinfo is not None:
+            self._stairinfo.clear(idx)
         self.reset_buf[idx.long()] = 1
         if self.log_extras:
             self._refresh_extras()
@@ -366,6 +412,8 @@ class Go2Env:
         self._sim.env_respawn(idx, p, q, clear_buffers, idx.numel(), torch.cuda.current_stream(self.device).cuda_stream)
         if self._lidar is not None and clear_buffers and idx.numel():
             self._lidar.clear(idx)
+        if self._stairinfo is not None and clear_buffers and idx.numel():
+            self._stairinfo.clear(idx)
 
     def respawn_at_start(self, envs_idx=(0,)):
         """go2_eval_stairs.py:314-361: back to the spawn point of the env's terrain row (or base_init_pos on flat ground)."""

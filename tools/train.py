@@ -5,6 +5,7 @@
     python tools/train.py --task walk --envs 4096 --iterations 1000 --recurrent [--rnn-hidden 256]      # LSTM memories in front of both MLPs (one GPU)
     python tools/train.py --task walk --envs 4096 --iterations 1000 --empirical-normalization           # running observation statistics in front of the policy
     python tools/train.py --task stairs_lidar --envs 4096 --iterations 1000                             # the stair env with the actor's LIDAR terrain scan (64 / 165 inputs)
+    python tools/train.py --task stairs_info --envs 4096 --iterations 1000                              # the stair env with the four-value stair info (53 / 113 inputs)
     torchrun --nproc-per-node 8 tools/train.py --task walk --envs 4096 --iterations 1000 --log-dir logs/go2-walk
 
 --envs is the env count PER RANK.  Under torchrun every rank builds its shard of the envs (``Go2Env(..., shared_globals=True)``: one curriculum, one
@@ -22,13 +23,13 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-TASKS = ("walk", "stairs", "stairs_lidar", "crouch", "jump")
+TASKS = ("walk", "stairs", "stairs_lidar", "stairs_info", "crouch", "jump")
 
 
 def task_cfgs(task):
-    from go2_sim2real_locomotion_rl_amd import get_crouch_cfgs, get_jump_cfgs, get_stair_cfgs, get_stair_lidar_cfgs, get_walk_cfgs
+    from go2_sim2real_locomotion_rl_amd import get_crouch_cfgs, get_jump_cfgs, get_stair_cfgs, get_stair_info_cfgs, get_stair_lidar_cfgs, get_walk_cfgs
 
-    return {"walk": get_walk_cfgs, "stairs": get_stair_cfgs, "stairs_lidar": get_stair_lidar_cfgs, "crouch": get_crouch_cfgs, "jump": get_jump_cfgs}[task]()
+    return {"walk": get_walk_cfgs, "stairs": get_stair_cfgs, "stairs_lidar": get_stair_lidar_cfgs, "stairs_info": get_stair_info_cfgs, "crouch": get_crouch_cfgs, "jump": get_jump_cfgs}[task]()
 
 
 def train_cfg_of(task, cfgs_path=None):
@@ -36,7 +37,7 @@ def train_cfg_of(task, cfgs_path=None):
         from go2_sim2real_locomotion_rl_amd import load_cfgs
 
         return load_cfgs(cfgs_path)[4]
-    task = "stairs" if task == "stairs_lidar" else task        # go2_stair_train_lidar.py trains with go2_train_stair.py's train_cfg (only the experiment name differs)
+    task = "stairs" if task in ("stairs_lidar", "stairs_info") else task        # both lidar scripts train with go2_train_stair.py's train_cfg (only the experiment name differs)
     return json.load(open(os.path.join(ROOT, "tests", "golden", f"ref_cfgs_{task}.json")))["train_cfg"]
 
 
