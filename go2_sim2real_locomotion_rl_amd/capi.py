@@ -68,12 +68,21 @@ C.update(_C_LIDAR)
 STAIRINFO_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_stairinfo.h")
 _C_STAIRINFO, DECLARED_STAIRINFO_FUNCS = _parse_header(STAIRINFO_HEADER)
 C.update(_C_STAIRINFO)
+# teacher-student distillation (include/go2sim_distill.h): product library only, a list of its own
+DISTILL_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_distill.h")
+_C_DISTILL, DECLARED_DISTILL_FUNCS = _parse_header(DISTILL_HEADER)
+C.update(_C_DISTILL)
 
 
 class PpoCfg(ctypes.Structure):
     """go2sim_ppo_cfg_t"""
     _fields_ = [(n, ctypes.c_double) for n in ("clip_param", "desired_kl", "entropy_coef", "learning_rate", "max_grad_norm", "value_loss_coef",
                                                "beta1", "beta2", "eps", "lr_min", "lr_max")] + [("use_clipped_value_loss", ctypes.c_int), ("adaptive", ctypes.c_int)]
+
+
+class DistillCfg(ctypes.Structure):
+    """go2sim_distill_cfg_t"""
+    _fields_ = [(n, ctypes.c_double) for n in ("learning_rate", "max_grad_norm", "beta1", "beta2", "eps")] + [("loss_type", ctypes.c_int), ("sub_rows", ctypes.c_int)]
 
 
 class PpoBatch(ctypes.Structure):
@@ -158,7 +167,7 @@ class Go2SimLib:
             fn = getattr(self.lib, prefix + name[len("go2sim_"):])
             fn.restype = ctypes.c_int
         if self.is_device:
-            for name in DECLARED_TRAIN_FUNCS + DECLARED_RNN_FUNCS + DECLARED_NORM_FUNCS + DECLARED_LIDAR_FUNCS + DECLARED_STAIRINFO_FUNCS:       # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
+            for name in DECLARED_TRAIN_FUNCS + DECLARED_RNN_FUNCS + DECLARED_NORM_FUNCS + DECLARED_LIDAR_FUNCS + DECLARED_STAIRINFO_FUNCS + DECLARED_DISTILL_FUNCS:       # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
                 if hasattr(self.lib, name):
                     getattr(self.lib, name).restype = ctypes.c_int
 

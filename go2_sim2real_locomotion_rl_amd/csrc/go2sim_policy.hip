@@ -18,70 +18,16 @@
 #include <new>
 #include <vector>
 
-#include "go2sim_mlp_dev.h"   // MlpDev, struct go2sim_mlp, mlp_layer: shared with go2sim_train.hip
+#define GO2SIM_MLP_ACT_KERNELS
+#include "go2sim_mlp_dev.h"   // MlpDev, struct go2sim_mlp, mlp_layer, k_mlp_forward, k_policy_sample: shared with go2sim_train.hip and go2sim_distill.hip
 
 namespace {
-
-constexpr uint32_t RNG_POLICY_NOISE = 11;   // purposes 1..10 belong to the environment (csrc/go2sim.hip)
 
 #define HIPCHK(x)                                                                                   \
   do {                                                                                              \
     hipError_t e_ = (x);                                                                            \
     if (e_ != hipSuccess) { fprintf(stderr, "go2sim_policy: %s failed: %s\n", #x, hipGetErrorString(e_)); return GO2SIM_E_HIP; } \
   } while (0)
-
-// blockIdx.y selects the network: actor and critic of one policy step share a launch (2 x 128 workgroups of 32 rows at 4096 rows, one per CU)
-__global__ __launch_bounds__(64 * NWAVE) void k_mlp_forward(MlpDev M0, const float* __restrict__ x0, float* __restrict__ y0,
-                                                            MlpDev M1, const float* __restrict__ x1, float* __restrict__ y1, int B) {
-  __shared__ alignas(16) float act[2][TM][LDW];
-  const MlpDev& M = blockIdx.y == 0 ? M0 : M1;
-  const float* __restrict__ x = blockIdx.y == 0 ? x0 : x1;
-  float* __restrict__ y = blockIdx.y == 0 ? y0 : y1;
-  const int row0 = blockIdx.x * TM;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  {
-    const int K0 = M.kpad[0], d0 = M.din[0];
-    for (int idx = tid; idx < TM * K0; idx += 64 * NWAVE) {
-      int r = idx / K0, k = idx - r * K0, gr = row0 + r;
-      act[0][r][k] = (gr < B && k < d0) ? x[(size_t)gr * d0 + k] : 0.0f;
-    }
-  }
-  __syncthreads();
-  int cur = 0;
-  for (int l = 0; l < M.n_layers; ++l) {
-    const int tiles_per_wave = (M.npad[l] / 16 + NWAVE - 1) / NWAVE;
-    if (tiles_per_wave >= 4) mlp_layer<4>(M, l, act[cur], act[cur ^ 1], y, row0, B, wave, lane);
-    else if (tiles_per_wave >= 2) mlp_layer<2>(M, l, act[cur], act[cur ^ 1], y, row0, B, wave, lane);
-    else mlp_layer<1>(M, l, act[cur], act[cur ^ 1], y, row0, B, wave, lane);
-    __syncthreads();
-    cur ^= 1;
-  }
-}
-
-// Normal(mean, std).sample() + log_prob, one lane per row (A <= 16 actions)
-__global__ __launch_bounds__(64) void k_policy_sample(const float* __restrict__ mean, const float* __restrict__ std_, int B, int A, uint64_t seed, uint32_t step,
-                                                      int deterministic, float* __restrict__ actions, float* __restrict__ log_prob) {
-  const int b = blockIdx.x * 64 + threadIdx.x;
-  if (b >= B) return;
-  float lp = 0.0f;
-  for (int blk = 0; 4 * blk < A; ++blk) {
-    float n[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (!deterministic) {
-      dm_u4 r = dm_philox((uint32_t)b, step, RNG_POLICY_NOISE, (uint32_t)blk, (uint32_t)seed, (uint32_t)(seed >> 32));
-      dm_normal2(r.v[0], r.v[1], &n[0], &n[1]); dm_normal2(r.v[2], r.v[3], &n[2], &n[3]);
-    }
-    for (int k = 0; k < 4; ++k) {
-      const int a = 4 * blk + k;
-      if (a >= A) break;
-      const float mu = mean[(size_t)b * A + a], sd = std_[a];
-      const float act = mu + sd * n[k];
-      actions[(size_t)b * A + a] = act;
-      const float d = act - mu;
-      lp = lp + ((-(d * d) / (2.0f * (sd * sd)) - dm_log(sd)) - 0.91893853320467274178f);
-    }
-  }
-  if (log_prob) log_prob[b] = lp;
-}
 
 // ---- rollout storage (rsl_rl RolloutStorage.compute_returns) ----
 __global__ __launch_bounds__(64) void k_rollout_add(float* __restrict__ rew, float* __restrict__ val, uint8_t* __restrict__ don, int B, const float* __restrict__ r,

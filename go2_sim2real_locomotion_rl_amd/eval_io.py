@@ -61,12 +61,15 @@ def read_checkpoint(path, map_location="cpu"):
     return ckpt
 
 
-def save_checkpoint(path, model_state_dict, optimizer_state_dict=None, it=0, infos=None, *, obs_norm_state_dict=None, critic_obs_norm_state_dict=None):
+def save_checkpoint(path, model_state_dict, optimizer_state_dict=None, it=0, infos=None, *, obs_norm_state_dict=None, critic_obs_norm_state_dict=None,
+                    privileged_obs_norm_state_dict=None):
     """``OnPolicyRunner.save`` layout (rsl_rl 2.2.4 runners/on_policy_runner.py).  The two normaliser state dicts are written only when given (rsl_rl writes
-    them when ``empirical_normalization`` is on); without them the file has the four keys it always had."""
+    them when ``empirical_normalization`` is on); without them the file has the four keys it always had.  ``privileged_obs_norm_state_dict`` is a
+    distillation run's frozen teacher normaliser."""
     ckpt = {"model_state_dict": {k: v.detach().cpu() for k, v in model_state_dict.items()},
             "optimizer_state_dict": optimizer_state_dict if optimizer_state_dict is not None else {}, "iter": int(it), "infos": infos}
-    for key, sd in (("obs_norm_state_dict", obs_norm_state_dict), ("critic_obs_norm_state_dict", critic_obs_norm_state_dict)):
+    for key, sd in (("obs_norm_state_dict", obs_norm_state_dict), ("critic_obs_norm_state_dict", critic_obs_norm_state_dict),
+                    ("privileged_obs_norm_state_dict", privileged_obs_norm_state_dict)):
         if sd is not None:
             ckpt[key] = {k: v.detach().cpu() for k, v in sd.items()}
     torch.save(ckpt, path)

@@ -18,12 +18,20 @@ global means in every rank's log, checkpoints written by rank 0 (tools/train.py)
 does: ``obs_normalizer`` and ``critic_obs_normalizer`` (``until = 1e8``) step together after every ``env.step``, the policy sees and stores the normalised rows,
 the checkpoint gains ``obs_norm_state_dict`` / ``critic_obs_norm_state_dict`` and ``get_inference_policy()`` normalises before it acts.  The observations
 ``learn()`` starts from are normalised with the statistics as they are and are not counted (DESIGN.md "Empirical normalisation").
+
+``train_cfg["obs_groups"]`` (optional) maps the roles ``policy``, ``critic`` and ``teacher`` to the env's observation groups ``"policy"`` (what
+``get_observations()`` returns) or ``"critic"`` (``extras["observations"]["critic"]``).  ``{"policy": "critic"}`` on a PPO run trains an actor on the
+privileged rows -- a teacher.  ``algorithm.class_name == "Distillation"`` with ``policy.class_name == "StudentTeacher"`` (distillation.py) distils such a
+teacher into a student: ``load(teacher_checkpoint)`` fills the teacher, ``learn()`` collects with the student and regresses it onto the teacher's actions,
+the log carries ``behavior_loss``.  A teacher checkpoint's ``obs_norm_state_dict`` becomes a frozen teacher normaliser that is always applied (it is part of
+the teacher's function) and is saved as ``privileged_obs_norm_state_dict`` (DESIGN.md "Distillation").
 """
 import os
 
 import torch
 
 from .capi import Go2SimError
+from .distillation import Distillation, StudentTeacher
 from .distributed import is_multi, shard_seed, sum_in_rank_order
 from .eval_io import read_checkpoint, save_checkpoint
 from .normalization import EmpiricalNormalization, norm_step
@@ -38,33 +46,84 @@ class OnPolicyRunner:
         self.empirical_normalization = bool(train_cfg.get("empirical_normalization"))
         alg_cfg, pol_cfg = dict(train_cfg["algorithm"]), dict(train_cfg["policy"])
         pol_class = pol_cfg.pop("class_name", "ActorCritic")
-        if alg_cfg.pop("class_name", "PPO") != "PPO" or pol_class not in ("ActorCritic", "ActorCriticRecurrent"):
-            raise Go2SimError("go2sim implements class_name PPO / ActorCritic / ActorCriticRecurrent")
-        pol_class = ActorCriticRecurrent if pol_class == "ActorCriticRecurrent" else ActorCritic
+        alg_class = alg_cfg.pop("class_name", "PPO")
+        pairings = {"PPO": ("ActorCritic", "ActorCriticRecurrent"), "Distillation": ("StudentTeacher",)}
+        if alg_class not in pairings or pol_class not in pairings[alg_class]:
+            raise Go2SimError(f"go2sim implements class_name PPO with ActorCritic / ActorCriticRecurrent and Distillation with StudentTeacher; "
+                              f"algorithm {alg_class!r} with policy {pol_class!r} is not one of these pairings")
+        self.distill = alg_class == "Distillation"
+        self.obs_groups = self._check_obs_groups(train_cfg.get("obs_groups"))
+        obs, extras = env.get_observations()
+        self._roles(obs, extras["observations"])                              # an env without the group a role names is refused here
         sym = alg_cfg.get("symmetry_cfg")
         if sym and sym.get("mirror_tables") is None and sym.get("data_augmentation_func") is None:
-            alg_cfg["symmetry_cfg"] = dict(sym, mirror_tables=env.mirror_tables())     # the env knows its own observation layout
-        obs, extras = env.get_observations()
-        critic_obs = extras["observations"].get("critic", obs)
+            tables = dict(env.mirror_tables())                                 # the env knows its own observation layout
+            if self.obs_groups:                                                # a role that reads the other group mirrors with that group's table
+                env_tables = dict(tables)
+                for role in ("policy", "critic"):
+                    if role in self.obs_groups:
+                        tables[role] = env_tables[self.obs_groups[role]]
+            alg_cfg["symmetry_cfg"] = dict(sym, mirror_tables=tables)
         seed = int(train_cfg.get("seed", 1) or 1)
         if group is None and is_multi():
             group = torch.distributed.group.WORLD
         self.group = group if group is not None and is_multi(group) else None
         self.rank = torch.distributed.get_rank(self.group) if self.group is not None else 0
+        self.num_steps_per_env = int(train_cfg["num_steps_per_env"])
+        self.save_interval = int(train_cfg.get("save_interval", 0) or 0)
+        self.current_learning_iteration = 0
+        self._last_means = (0.0, 0.0)
+        self._cur_rew, self._cur_len = torch.zeros(env.num_envs, device=self.device), torch.zeros(env.num_envs, device=self.device)
+        self.obs_normalizer = self.critic_obs_normalizer = self.privileged_obs_normalizer = None
+        if self.distill:
+            if self.group is not None:
+                raise Go2SimError("Distillation over a multi-rank group is not implemented (the sharded distillation update is a follow-up)")
+            s_obs, _, t_obs = self._roles(obs, extras["observations"])
+            self.policy = StudentTeacher(s_obs.shape[1], t_obs.shape[1], env.num_actions, device=self.device, seed=seed, **pol_cfg)
+            self.alg = Distillation(self.policy, device=self.device, **alg_cfg)
+            self.alg.init_storage(env.num_envs, self.num_steps_per_env, [s_obs.shape[1]], [t_obs.shape[1]], [env.num_actions])
+            if self.empirical_normalization:                                  # the student's normaliser learns as the actor's does in a PPO run
+                self.obs_normalizer = EmpiricalNormalization([s_obs.shape[1]], until=1.0e8, device=self.device)
+            return
+        obs, critic_raw, _ = self._roles(obs, extras["observations"])
+        critic_obs = obs if critic_raw is None else critic_raw
+        pol_class = ActorCriticRecurrent if pol_class == "ActorCriticRecurrent" else ActorCritic
         # the noise stream is the rank's own; the initial weights drawn from the same seed are replaced by rank 0's at the end of init_storage
         self.policy = pol_class(obs.shape[1], critic_obs.shape[1], env.num_actions, device=self.device, seed=shard_seed(seed, self.rank), **pol_cfg)
         self.alg = PPO(self.policy, device=self.device, seed=seed, group=self.group, **alg_cfg)
-        self.num_steps_per_env = int(train_cfg["num_steps_per_env"])
-        self.save_interval = int(train_cfg.get("save_interval", 0) or 0)
         self.alg.init_storage(env.num_envs, self.num_steps_per_env, [obs.shape[1]], [critic_obs.shape[1]], [env.num_actions])
-        self.obs_normalizer = self.critic_obs_normalizer = None
         if self.empirical_normalization:
             # both exist even when the env gives no critic observations (the second then stays unused: the critic reads the normalised actor rows)
             self.obs_normalizer = EmpiricalNormalization([obs.shape[1]], until=1.0e8, device=self.device)
             self.critic_obs_normalizer = EmpiricalNormalization([critic_obs.shape[1]], until=1.0e8, device=self.device)
-        self.current_learning_iteration = 0
-        self._last_means = (0.0, 0.0)
-        self._cur_rew, self._cur_len = torch.zeros(env.num_envs, device=self.device), torch.zeros(env.num_envs, device=self.device)
+
+    ROLES, GROUPS = ("policy", "critic", "teacher"), ("policy", "critic")
+
+    @classmethod
+    def _check_obs_groups(cls, cfg):
+        """train_cfg["obs_groups"]: {role: env group}; -> dict (empty when absent: everything as without it)"""
+        if not cfg:
+            return {}
+        bad_roles = sorted(set(cfg) - set(cls.ROLES))
+        if bad_roles:
+            raise Go2SimError(f"obs_groups: unknown role(s) {bad_roles}; the roles are {list(cls.ROLES)}")
+        bad = {r: g for r, g in cfg.items() if g not in cls.GROUPS}
+        if bad:
+            raise Go2SimError(f"obs_groups: unknown observation group(s) {bad}; the env's groups are {list(cls.GROUPS)}")
+        return dict(cfg)
+
+    def _roles(self, obs, observations):
+        """The env's rows by role: -> (policy rows, critic rows or None, teacher rows).  Without obs_groups: the env's policy group, its critic group (None
+        when it has none: the critic then reads what the policy reads), and the policy group for the teacher."""
+        def group(name):
+            if name == "policy":
+                return obs
+            if "critic" not in observations:
+                raise Go2SimError("obs_groups names the group 'critic', but the env gives no critic observations")
+            return observations["critic"]
+        g = self.obs_groups
+        critic = group(g["critic"]) if "critic" in g else observations.get("critic")
+        return group(g.get("policy", "policy")), critic, group(g.get("teacher", "policy"))
 
     def _normalize(self, obs, critic, update):
         """Both observation sets through one norm_step call (`critic` is None when the env has no critic observations: the critic then reads the normalised
@@ -75,15 +134,17 @@ class OnPolicyRunner:
         return norm_step(self.obs_normalizer, obs, self.critic_obs_normalizer, critic, update=update, group=self.group)
 
     def learn(self, num_learning_iterations, init_at_random_ep_len=False):
+        if self.distill:
+            return self._learn_distill(num_learning_iterations, init_at_random_ep_len)
         env, alg, dev = self.env, self.alg, self.device
         if init_at_random_ep_len:
             env.episode_length_buf = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
         obs, extras = env.get_observations()
-        critic_obs = extras["observations"].get("critic", obs)
+        obs, critic_raw, _ = self._roles(obs, extras["observations"])
+        critic_obs = obs if critic_raw is None else critic_raw
         norm = self.empirical_normalization
         if norm:                                                              # the starting observations: current statistics, not counted
-            obs, critic_obs = self._normalize(obs, extras["observations"].get("critic"), update=False)
-        cur_rew, cur_len = self._cur_rew, self._cur_len                       # running episodes carry over from one learn() to the next
+            obs, critic_obs = self._normalize(obs, critic_raw, update=False)
         log = []
         start = self.current_learning_iteration
         for it in range(start, start + num_learning_iterations):
@@ -91,15 +152,12 @@ class OnPolicyRunner:
             for _ in range(self.num_steps_per_env):
                 actions = alg.act(obs, critic_obs)
                 obs, rewards, dones, infos = env.step(actions)
-                critic_obs = infos["observations"].get("critic", obs)
+                obs, critic_raw, _ = self._roles(obs, infos["observations"])
+                critic_obs = obs if critic_raw is None else critic_raw
                 if norm:
-                    obs, critic_obs = self._normalize(obs, infos["observations"].get("critic"), update=True)
+                    obs, critic_obs = self._normalize(obs, critic_raw, update=True)
                 alg.process_env_step(rewards, dones, infos)
-                cur_rew += rewards; cur_len += 1
-                d = (dones > 0).to(torch.float64)
-                acc += torch.stack([d.sum(), (d * cur_rew).sum(), (d * cur_len).sum()])
-                keep = (dones == 0).to(cur_rew.dtype)
-                cur_rew *= keep; cur_len *= keep
+                self._count_episodes(acc, rewards, dones)
             if getattr(env, "_shared_globals", False):
                 env.sync_globals(self.group)                                   # one curriculum and one set of global DR draws for all shards
             alg.compute_returns(critic_obs)
@@ -118,6 +176,84 @@ class OnPolicyRunner:
             self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
         return log
 
+    def _count_episodes(self, acc, rewards, dones):
+        """acc += (finished episodes, their reward sum, their length sum); running episodes carry over from one learn() to the next"""
+        cur_rew, cur_len = self._cur_rew, self._cur_len
+        cur_rew += rewards; cur_len += 1
+        d = (dones > 0).to(torch.float64)
+        acc += torch.stack([d.sum(), (d * cur_rew).sum(), (d * cur_len).sum()])
+        keep = (dones == 0).to(cur_rew.dtype)
+        cur_rew *= keep; cur_len *= keep
+
+    # ---- distillation ----------------------------------------------------------------------------------------
+    def _distill_rows(self, obs, observations, update):
+        """The student's and the teacher's rows of one env step, each through its normaliser where it has one: the student's learns (`update`), the
+        teacher's is frozen and always applied.  The results are the normalisers' own buffers or the env's tensors, which are not written."""
+        s_obs, _, t_obs = self._roles(obs, observations)
+        if self.obs_normalizer is not None:
+            s_obs = norm_step(self.obs_normalizer, s_obs, update=update)[0]
+        if self.privileged_obs_normalizer is not None:
+            t_obs = norm_step(self.privileged_obs_normalizer, t_obs, update=False)[0]
+        return s_obs, t_obs
+
+    def _learn_distill(self, num_learning_iterations, init_at_random_ep_len):
+        env, alg, dev = self.env, self.alg, self.device
+        if not self.policy.loaded_teacher:
+            raise Go2SimError("learn(): no teacher has been loaded; load a PPO checkpoint (the teacher) or a distillation checkpoint with runner.load(path) first")
+        if init_at_random_ep_len:
+            env.episode_length_buf = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
+        obs, extras = env.get_observations()
+        s_obs, t_obs = self._distill_rows(obs, extras["observations"], update=False)      # the starting observations are not counted
+        log = []
+        start = self.current_learning_iteration
+        for it in range(start, start + num_learning_iterations):
+            acc = torch.zeros(3, device=dev, dtype=torch.float64)
+            for _ in range(self.num_steps_per_env):
+                actions = alg.act(s_obs, t_obs)
+                obs, rewards, dones, infos = env.step(actions)
+                s_obs, t_obs = self._distill_rows(obs, infos["observations"], update=True)
+                alg.process_env_step(rewards, dones, infos)
+                self._count_episodes(acc, rewards, dones)
+            behavior_loss = alg.update()                                       # no returns to compute: the targets are the stored teacher actions
+            n, rs, ls = acc.tolist()
+            if n > 0:
+                self._last_means = (rs / n, ls / n)
+            self.current_learning_iteration = it + 1
+            log.append({"iteration": it, "mean_reward": self._last_means[0], "mean_episode_length": self._last_means[1], "behavior_loss": behavior_loss,
+                        "learning_rate": alg.learning_rate})
+            if self.log_dir is not None and self.save_interval > 0 and (it + 1) % self.save_interval == 0:
+                self.save(os.path.join(self.log_dir, f"model_{it + 1}.pt"))
+        if self.log_dir is not None:
+            self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
+        return log
+
+    def _load_distill(self, ckpt, path, load_optimizer):
+        """A PPO checkpoint is the teacher: teacher.* <- actor.*, its actor normaliser becomes the frozen teacher normaliser; the student, the iteration
+        and the optimizer are untouched.  A distillation checkpoint resumes: student, teacher, std, both normalisers, optimizer, iteration."""
+        resume = self.policy.load_state_dict(ckpt["model_state_dict"])
+        t_norm = ckpt.get("privileged_obs_norm_state_dict" if resume else "obs_norm_state_dict")
+        if t_norm is not None:
+            if self.privileged_obs_normalizer is None:
+                self.privileged_obs_normalizer = EmpiricalNormalization([self.policy._tdims[0]], until=1.0e8, device=self.device).eval()
+            self.privileged_obs_normalizer.load_state_dict(t_norm)
+        elif resume:
+            self.privileged_obs_normalizer = None
+        if not resume:
+            return ckpt.get("infos")
+        if self.empirical_normalization:
+            if ckpt.get("obs_norm_state_dict") is None:
+                raise Go2SimError(f"{path}: empirical_normalization is on, but the distillation checkpoint has no obs_norm_state_dict")
+            self.obs_normalizer.load_state_dict(ckpt["obs_norm_state_dict"])
+        elif ckpt.get("obs_norm_state_dict") is not None:
+            raise Go2SimError(f"{path}: the checkpoint's student was trained on normalised observations (obs_norm_state_dict), but empirical_normalization "
+                              "is off in this runner's train_cfg")
+        opt = ckpt.get("optimizer_state_dict") or {}
+        if load_optimizer and "exp_avg" in opt:
+            self.alg.load_optimizer_state_dict(opt)
+            self.policy._step = int(opt.get("policy_noise_step", self.policy._step))
+        self.current_learning_iteration = int(ckpt.get("iter", 0) or 0)
+        return ckpt.get("infos")
+
     def save(self, path, infos=None):
         """rsl_rl 2.2.4 checkpoint layout (eval_io.read_checkpoint): model_state_dict, optimizer_state_dict (Adam's m, v, step, learning rate), iter, infos."""
         if self.rank != 0:                                                     # the ranks hold the same bits: rank 0 writes them
@@ -125,6 +261,11 @@ class OnPolicyRunner:
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         opt = self.alg.optimizer_state_dict()
         opt["policy_noise_step"] = int(self.policy._step)
+        if self.distill:
+            save_checkpoint(path, self.policy.state_dict(), opt, self.current_learning_iteration, infos,
+                            obs_norm_state_dict=self.obs_normalizer.state_dict() if self.obs_normalizer is not None else None,
+                            privileged_obs_norm_state_dict=self.privileged_obs_normalizer.state_dict() if self.privileged_obs_normalizer is not None else None)
+            return
         if self.empirical_normalization:
             save_checkpoint(path, self.policy.state_dict(), opt, self.current_learning_iteration, infos, obs_norm_state_dict=self.obs_normalizer.state_dict(),
                             critic_obs_norm_state_dict=self.critic_obs_normalizer.state_dict())
@@ -133,6 +274,8 @@ class OnPolicyRunner:
 
     def load(self, path, load_optimizer=True):
         ckpt = read_checkpoint(path)
+        if self.distill:
+            return self._load_distill(ckpt, path, load_optimizer)
         has_norm = [k for k in ("obs_norm_state_dict", "critic_obs_norm_state_dict") if ckpt.get(k) is not None]
         if self.empirical_normalization and len(has_norm) != 2:
             raise Go2SimError(f"{path}: empirical_normalization is on, but the checkpoint has no obs_norm_state_dict / critic_obs_norm_state_dict")
@@ -155,7 +298,7 @@ class OnPolicyRunner:
         """The deterministic policy as a callable.  A recurrent policy keeps its memory between calls: the caller resets it through
         ``runner.policy.reset(dones)`` after every env step, as the collection loop does.  With empirical normalisation the callable first applies the actor
         normaliser without moving its statistics (rsl_rl puts it in eval mode here); the raw observations are not written."""
-        if not self.empirical_normalization:
+        if self.obs_normalizer is None:
             return self.policy.act_inference
         normalizer, act = self.obs_normalizer, self.policy.act_inference
         return lambda observations: act(norm_step(normalizer, observations, update=False)[0])

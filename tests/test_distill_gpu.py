@@ -1,0 +1,291 @@
+"""The HIP library's distillation (include/go2sim_distill.h) against the torch float64 reference of tests/distill_ref.py over the cases of
+tests/distill_cases.py, with the float32 torch evaluation of the same expressions as the yardstick:
+  (a) go2sim_distill_act:        bit-equal to go2sim_policy_act (actions, mean) and go2sim_mlp_forward (teacher_actions)
+  (b) window gradients, per parameter tensor:  max|g - g64| <= C_GRAD max(max|g32 - g64|, 2^-24 max|g64|)
+  (c) the loss statistic:        equal to a float64 evaluation on the library's own float32 means to 1e-12 relative; the means under C_MLP
+  (d) whole updates, per tensor: max|p - p64| <= C_UPD max|p32 - p64|
+  (e) bit reproducibility and the optimizer state's round trip, (f) the status codes.
+C_GRAD = 16, C_UPD = 8 (include/go2sim_train.h) and C_MLP = 7 (include/go2sim_policy.h) are the project's own constants.  Every test prints its ratios
+before it asserts.  Worst ratios measured on the MI355X: 5.00 (C_GRAD), 2.13 (C_UPD), 1.68 (C_MLP); include/go2sim_distill.h names the cases."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import distill_cases as DC
+
+pytestmark = pytest.mark.gpu
+
+C_GRAD = 16
+C_UPD = 8
+C_MLP = 7
+EPS = 2.0 ** -24
+DEV = "cuda:0"
+
+
+def r16(v):
+    return (v + 15) // 16 * 16
+
+
+def real_entry_mask(dims):
+    parts = []
+    for l in range(len(dims) - 1):
+        w = np.zeros((r16(dims[l + 1]), r16(dims[l])), bool); w[:dims[l + 1], :dims[l]] = True
+        b = np.zeros(r16(dims[l + 1]), bool); b[:dims[l + 1]] = True
+        parts += [w.reshape(-1), b]
+    return np.concatenate(parts)
+
+
+def bits(t):
+    return t.detach().cpu().contiguous().numpy().view(np.int32)
+
+
+class Side:
+    """Student, teacher, std, the storage and one go2sim_distill handle on the GPU"""
+
+    def __init__(self, lib, sdims, tdims, state, obs, ta, max_rows, **hyper):
+        from go2_sim2real_locomotion_rl_amd.distillation import DistillHandle
+        from go2_sim2real_locomotion_rl_amd.policy import Mlp, flatten_sequential
+
+        self.lib, self.sdims, self.tdims = lib, sdims, tdims
+        self.student = Mlp(lib, sdims, flatten_sequential(state, "student", len(sdims) - 1)[0])
+        self.teacher = Mlp(lib, tdims, flatten_sequential(state, "teacher", len(tdims) - 1)[0])
+        self.std = state["std"].to(DEV).clone()
+        self.obs, self.ta = obs.to(DEV).contiguous(), ta.to(DEV).contiguous()
+        self.h = DistillHandle(lib, self.student, sdims[-1], max_rows, **hyper)
+
+    def split(self, flat):
+        from go2_sim2real_locomotion_rl_amd.distillation import unflatten_student
+
+        return {k: v.double() for k, v in unflatten_student(flat.cpu(), self.sdims).items()}
+
+    def stats(self):
+        s = self.h.stats().cpu()
+        return dict(loss=float(s[0]), lr=float(s[1]), grad_norm=float(s[2]), step=int(s[3]), pairs=int(s[4]), windows=int(s[5])), s
+
+    def means(self, obs_rows):
+        """the library's own float32 student means of `obs_rows` [n][Ds], from a deterministic act"""
+        from go2_sim2real_locomotion_rl_amd.distillation import distill_act
+
+        n, A = obs_rows.shape[0], self.sdims[-1]
+        tobs = torch.zeros(n, self.tdims[0], device=DEV)
+        out = [torch.empty(n, A, device=DEV) for _ in range(3)]
+        distill_act(self.lib, self.student, self.teacher, obs_rows.contiguous(), tobs, self.std, n, 1, 0, True, *out)
+        return out[1]
+
+
+def case_side(lib, c, **hyper):
+    return Side(lib, c.sdims, c.tdims, c.state, c.obs, c.ta, c.G * c.N, loss_type=c.loss_type, **hyper)
+
+
+# ---- (a) the collection step ---------------------------------------------------------------------------------------------------------------------
+ACT_PAIRS = {                                               # student dims, teacher dims
+    "deeper_student": ([49, 32, 24, 16], [104, 40, 16]), "deeper_teacher": ([49, 32, 16], [104, 40, 24, 16]),
+    "wider_student_input": ([104, 32, 16], [49, 32, 16]), "wider_teacher_input": ([49, 32, 16], [104, 32, 16]),
+    "wider_student": ([49, 272, 12], [49, 20, 12]), "wider_teacher": ([49, 20, 12], [49, 272, 12]),
+}
+
+
+@pytest.mark.parametrize("deterministic", [False, True])
+@pytest.mark.parametrize("rows", [1, 17, 70])
+@pytest.mark.parametrize("pair", sorted(ACT_PAIRS))
+def test_act_equals_policy_act_and_mlp_forward(hip_lib, pair, rows, deterministic):
+    from go2_sim2real_locomotion_rl_amd.distillation import distill_act
+    from go2_sim2real_locomotion_rl_amd.policy import Mlp, flatten_sequential, policy_act
+
+    sdims, tdims = ACT_PAIRS[pair]
+    g = torch.Generator().manual_seed(11 + rows)
+    state = DC.init_state(sdims, tdims, g, std=0.3)
+    student = Mlp(hip_lib, sdims, flatten_sequential(state, "student", len(sdims) - 1)[0])
+    teacher = Mlp(hip_lib, tdims, flatten_sequential(state, "teacher", len(tdims) - 1)[0])
+    std = state["std"].to(DEV)
+    obs, tobs = torch.randn(rows, sdims[0], generator=g).to(DEV), torch.randn(rows, tdims[0], generator=g).to(DEV)
+    A, seed, step = sdims[-1], 0x1234567890, 5
+    new = lambda: torch.full((rows, A), float("nan"), device=DEV)
+    act, mean, tact, act_p, mean_p, tact_f = (new() for _ in range(6))
+    distill_act(hip_lib, student, teacher, obs, tobs, std, rows, seed, step, deterministic, act, mean, tact)
+    policy_act(hip_lib, student, None, obs, None, std, rows, seed, step, deterministic, act_p, mean_p, None, None)
+    teacher.forward(tobs, tact_f, rows)
+    torch.cuda.synchronize()
+    assert np.array_equal(bits(act), bits(act_p)) and np.array_equal(bits(mean), bits(mean_p)) and np.array_equal(bits(tact), bits(tact_f))
+    assert np.isfinite(act.cpu().numpy()).all() and np.isfinite(tact.cpu().numpy()).all()
+    assert np.array_equal(bits(act), bits(mean)) == bool(deterministic)
+
+
+# ---- (b), (c) one window -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", DC.GRAD_CASES, ids=DC.case_id)
+def test_window_gradients(hip_lib, case):
+    c = DC.get_case(*case)
+    g64, _, _ = c.ref["f64"]
+    g32, _, _ = c.ref["f32"]
+    side = case_side(hip_lib, c)
+    side.h.window_grad(side.obs, side.ta, c.idx.to(DEV), c.N)
+    got = side.split(side.h.export("GRADS"))
+    padded = side.h.export_padded("GRADS").cpu().numpy()
+    worst = 0.0
+    for k in g64:
+        err, yard = float((got[k] - g64[k]).abs().max()), max(float((g32[k].double() - g64[k]).abs().max()), EPS * float(g64[k].abs().max()))
+        print(f"RATIO grad {DC.case_id(case)} {k} {err / yard:.3f}")
+        worst = max(worst, err / yard)
+    print(f"RATIO worst grad {DC.case_id(case)} {worst:.3f}")
+    assert worst <= C_GRAD
+    assert np.isfinite(padded).all() and not padded[~real_entry_mask(c.sdims)].any(), "padded gradient entries must be exactly zero"
+    st, _ = side.stats()
+    assert st["pairs"] == c.G and st["windows"] == 0 and st["step"] == 0
+
+
+@pytest.mark.parametrize("case", [("small", 37, 3, "mse", "plain"), ("small", 37, 3, "huber", "plain"), ("six_layers", 37, 3, "huber", "dup"),
+                                  ("small", 2 * DC.ROW_CHUNK + 37, 1, "mse", "plain"), ("full", 16, 5, "huber", "plain")], ids=DC.case_id)
+def test_loss_statistic(hip_lib, case):
+    c = DC.get_case(*case)
+    _, l64, mu64 = c.ref["f64"]
+    _, _, mu32 = c.ref["f32"]
+    side = case_side(hip_lib, c)
+    side.h.window_grad(side.obs, side.ta, c.idx.to(DEV), c.N)
+    st, _ = side.stats()
+    rows = side.obs.reshape(-1, c.sdims[0])[c.idx.long().to(DEV)]
+    mu = side.means(rows).cpu().double()
+    err, yard = float((mu - mu64).abs().max()), max(float((mu32.double() - mu64).abs().max()), EPS * float(mu64.abs().max()))
+    print(f"RATIO mean {DC.case_id(case)} {err / yard:.3f}")
+    assert err / yard <= C_MLP
+    d = mu - c.ta.reshape(-1, c.sdims[-1])[c.idx.long()].double()
+    rho = d * d if c.loss_type == "mse" else torch.where(d.abs() <= 1, d * d / 2, d.abs() - 0.5)
+    want = float(rho.reshape(c.G, -1).mean(1).sum()) / c.G                 # a float64 sum in another order
+    print(f"RATIO loss {DC.case_id(case)} {abs(st['loss'] - want) / want:.3e}")
+    assert abs(st["loss"] - want) <= 1e-12 * want
+    assert st["loss"] == pytest.approx(sum(l64) / c.G, rel=1e-5)           # against the float64 law: fp32 forward passes, a sanity bound
+    side.h.loss_only(side.obs, side.ta, c.idx.to(DEV), c.N)                # the tail's pass: the same rows again double the sum and the count, no gradient
+    before = bits(side.h.export("GRADS"))
+    st2, _ = side.stats()
+    assert st2["pairs"] == 2 * c.G and abs(st2["loss"] - want) <= 1e-12 * want and np.array_equal(bits(side.h.export("GRADS")), before)
+
+
+def test_sub_batches_keep_the_bits(hip_lib):
+    """a window walked in sub-batches of one chunk holds the gradient bits of the same window in one piece"""
+    c = DC.get_case("small", 2 * DC.ROW_CHUNK + 37, 1, "mse", "plain")
+    out = []
+    for sub in (0, DC.ROW_CHUNK, 2 * DC.ROW_CHUNK):
+        side = case_side(hip_lib, c, sub_rows=sub)
+        side.h.window_grad(side.obs, side.ta, c.idx.to(DEV), c.N)
+        out.append((bits(side.h.export_padded("GRADS")), side.stats()[1].numpy().view(np.int64)))
+    for g, s in out[1:]:
+        assert np.array_equal(g, out[0][0]) and np.array_equal(s, out[0][1])
+    assert np.abs(out[0][0].view(np.float32)).max() > 0
+
+
+# ---- (d) whole updates -----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", DC.UPDATE_CASES, ids=DC.update_id)
+def test_whole_update(hip_lib, case):
+    u = DC.get_update_case(*case)
+    T, E, G, N = u["T"], u["E"], u["G"], u["N"]
+    side = Side(hip_lib, u["sdims"], u["tdims"], u["state"], u["obs"], u["ta"], G * N, learning_rate=u["hp"]["learning_rate"], max_grad_norm=u["hp"]["max_grad_norm"])
+    std0 = bits(side.std)
+    p0 = bits(side.h.export_padded("PARAMS"))
+    side.h.update(side.obs, side.ta, T, N, E, G)
+    got = side.split(side.h.export("PARAMS"))
+    st, _ = side.stats()
+    n_win = (E * T) // G
+    assert st["step"] == n_win and st["windows"] == n_win and st["pairs"] == E * T and st["lr"] == u["hp"]["learning_rate"]
+    assert st["loss"] == pytest.approx(u["f64"]["loss"], rel=1e-5)         # fp32 forward passes: a sanity bound, (c) is the precise statement
+    assert np.array_equal(bits(side.std), std0), "std is outside the optimizer"
+    if n_win == 0:                                                        # (2, 1, 5): nothing moves, bit for bit; the loss is still reported
+        assert np.array_equal(bits(side.h.export_padded("PARAMS")), p0) and st["loss"] > 0
+        for which in ("ADAM_M", "ADAM_V"):
+            assert not side.h.export_padded(which).cpu().numpy().any(), which
+        return
+    worst = 0.0
+    for k, p64 in u["f64"]["params"].items():
+        err, yard = float((got[k] - p64).abs().max()), float((u["f32"]["params"][k].double() - p64).abs().max())
+        print(f"RATIO update {DC.update_id(case)} {k} {err / yard:.3f}")
+        worst = max(worst, err / yard)
+    print(f"RATIO worst update {DC.update_id(case)} {worst:.3f}")
+    assert worst <= C_UPD
+    assert st["grad_norm"] == pytest.approx(u["f64"]["norms"][-1], rel=1e-4)
+    mask = real_entry_mask(u["sdims"])
+    for which in ("PARAMS", "GRADS", "ADAM_M", "ADAM_V"):
+        assert not side.h.export_padded(which).cpu().numpy()[~mask].any(), which
+
+
+# ---- (e) determinism and optimizer state -------------------------------------------------------------------------------------------------------------
+def run_update(lib, u, **hyper):
+    side = Side(lib, u["sdims"], u["tdims"], u["state"], u["obs"], u["ta"], u["G"] * u["N"], **hyper)
+    side.h.update(side.obs, side.ta, u["T"], u["N"], u["E"], u["G"])
+    return side, [bits(side.h.export(w)) for w in ("PARAMS", "ADAM_M", "ADAM_V", "GRADS")] + [side.stats()[1].numpy().view(np.int64)]
+
+
+def test_update_is_bit_reproducible(hip_lib):
+    u = DC.get_update_case((3, 2, 4), 37, "none")
+    (_, a), (_, b) = run_update(hip_lib, u), run_update(hip_lib, u)
+    for name, x, y in zip(("params", "m", "v", "grads", "stats"), a, b):
+        assert np.array_equal(x, y), name
+    assert np.abs(a[1].view(np.float32)).max() > 0
+
+
+def test_optimizer_state_round_trip(hip_lib):
+    """export, import and set_step carry the optimizer from one handle to another: the next update gives equal bits"""
+    u = DC.get_update_case((4, 1, 3), 37, "none")
+    a, _ = run_update(hip_lib, u)
+    b = Side(hip_lib, u["sdims"], u["tdims"], u["state"], u["obs"], u["ta"], u["G"] * u["N"])
+    for which in ("PARAMS", "ADAM_M", "ADAM_V"):
+        b.h.import_(which, a.h.export(which))
+    sa, _ = a.stats()
+    assert sa["step"] == 1
+    b.h.set_step(sa["step"], sa["lr"])
+    for side in (a, b):
+        side.h.update(side.obs, side.ta, u["T"], u["N"], u["E"], u["G"])
+    for which in ("PARAMS", "ADAM_M", "ADAM_V", "GRADS"):
+        assert np.array_equal(bits(a.h.export(which)), bits(b.h.export(which))), which
+    assert np.array_equal(a.stats()[1].numpy().view(np.int64), b.stats()[1].numpy().view(np.int64)) and a.stats()[0]["step"] == 2
+    a.h.reset_stats()
+    s, _ = a.stats()
+    assert s["loss"] == 0.0 and s["pairs"] == 0 and s["windows"] == 0 and s["step"] == 2
+
+
+# ---- (f) status codes ----------------------------------------------------------------------------------------------------------------------------------
+def test_bad_arguments_return_a_status_and_launch_nothing(hip_lib):
+    from go2_sim2real_locomotion_rl_amd.capi import C, DistillCfg
+
+    BAD, null, st = C["GO2SIM_E_BADARG"], ctypes.c_void_p(0), ctypes.c_void_p(0)
+    c = DC.get_case("small", 16, 1, "mse", "plain")
+    side = case_side(hip_lib, c)
+    L, h, p = hip_lib, side.h.h, lambda t: ctypes.c_void_p(t.data_ptr())
+    cfg = DistillCfg(1e-3, 0.0, 0.9, 0.999, 1e-8, 0, 0)
+    out = ctypes.c_void_p()
+    create = L.fn("distill_create")
+    assert create(null, 16, ctypes.byref(cfg), 16, ctypes.byref(out)) == BAD
+    assert create(side.student.h, 15, ctypes.byref(cfg), 16, ctypes.byref(out)) == BAD                      # the student's last width is 16
+    assert create(side.student.h, 16, ctypes.byref(cfg), 0, ctypes.byref(out)) == BAD
+    assert create(side.student.h, 16, ctypes.byref(DistillCfg(1e-3, 0.0, 0.9, 0.999, 1e-8, 2, 0)), 16, ctypes.byref(out)) == BAD     # no such loss
+    assert create(side.student.h, 16, ctypes.byref(DistillCfg(1e-3, 0.0, 0.9, 0.999, 1e-8, 0, 100)), 16, ctypes.byref(out)) == BAD   # not a multiple of the chunk
+    idx = c.idx.to(DEV)
+    side.h.window_grad(side.obs, side.ta, idx, c.N)
+    before = bits(side.h.export("GRADS"))
+    for name in ("distill_window_grad", "distill_loss_only"):
+        f = L.fn(name)
+        assert f(null, p(side.obs), p(side.ta), p(idx), 16, 16, st) == BAD
+        assert f(h, null, p(side.ta), p(idx), 16, 16, st) == BAD and f(h, p(side.obs), null, p(idx), 16, 16, st) == BAD and f(h, p(side.obs), p(side.ta), null, 16, 16, st) == BAD
+        assert f(h, p(side.obs), p(side.ta), p(idx), 0, 16, st) == BAD
+        assert f(h, p(side.obs), p(side.ta), p(idx), 32, 16, st) == BAD                                      # rows beyond the workspace
+        assert f(h, p(side.obs), p(side.ta), p(idx), 16, 5, st) == BAD                                       # not whole pairs
+    upd = L.fn("distill_update")
+    assert upd(null, p(side.obs), p(side.ta), 2, 16, 1, 1, st) == BAD and upd(h, null, p(side.ta), 2, 16, 1, 1, st) == BAD
+    assert upd(h, p(side.obs), p(side.ta), 2, 16, 1, 2, st) == BAD                                          # a window of 32 rows > 16
+    assert upd(h, p(side.obs), p(side.ta), 2, 16, 0, 1, st) == BAD and upd(h, p(side.obs), p(side.ta), 0, 16, 1, 1, st) == BAD
+    assert L.fn("distill_apply")(null, st) == BAD and L.fn("distill_stats")(null, p(side.std), st) == BAD and L.fn("distill_stats")(h, null, st) == BAD
+    assert L.fn("distill_export")(null, 1, p(side.std), st) == BAD and L.fn("distill_export")(h, 7, p(side.std), st) == BAD and L.fn("distill_import")(h, 1, null, st) == BAD
+    assert L.fn("distill_set_step")(h, ctypes.c_longlong(-1), ctypes.c_double(1e-3), st) == BAD and L.fn("distill_destroy")(null) == BAD
+    # the collection step: widths that do not match, NULL arrays
+    act = L.fn("distill_act")
+    wide = DC.get_case("one_layer", 1, 1, "mse", "plain")                                                   # a student that ends in 4 actions
+    other = case_side(hip_lib, wide)
+    a = [torch.zeros(16, 16, device=DEV) for _ in range(3)]
+    tobs = torch.zeros(16, c.tdims[0], device=DEV)
+    args = lambda **kw: [kw.get("s", side.student.h), kw.get("t", side.teacher.h), kw.get("obs", p(side.obs)), kw.get("tobs", p(tobs)), kw.get("std", p(side.std)), 16,
+                         ctypes.c_uint64(1), ctypes.c_uint32(0), 0, kw.get("a0", p(a[0])), kw.get("a1", p(a[1])), kw.get("a2", p(a[2])), st]
+    assert act(*args(t=other.teacher.h)) == BAD and act(*args(s=other.student.h)) == BAD                    # 16 actions against 4
+    for k in ("s", "t", "obs", "tobs", "std", "a0", "a1", "a2"):
+        assert act(*args(**{k: null})) == BAD, k
+    assert act(*args()) == 0
+    s, _ = side.stats()
+    assert np.array_equal(bits(side.h.export("GRADS")), before) and s["pairs"] == 1 and s["step"] == 0 and s["windows"] == 0, "a refused call must not have launched anything"

@@ -6,6 +6,8 @@
     python tools/train.py --task walk --envs 4096 --iterations 1000 --empirical-normalization           # running observation statistics in front of the policy
     python tools/train.py --task stairs_lidar --envs 4096 --iterations 1000                             # the stair env with the actor's LIDAR terrain scan (64 / 165 inputs)
     python tools/train.py --task stairs_info --envs 4096 --iterations 1000                              # the stair env with the four-value stair info (53 / 113 inputs)
+    python tools/train.py --task stairs_lidar --envs 4096 --iterations 1000 --actor-obs critic --log-dir logs/teacher   # a teacher: the actor reads the privileged rows
+    python tools/train.py --task stairs_lidar --envs 4096 --iterations 500 --distill logs/teacher/model_1000.pt --teacher-obs critic   # distil it into a student
     torchrun --nproc-per-node 8 tools/train.py --task walk --envs 4096 --iterations 1000 --log-dir logs/go2-walk
 
 --envs is the env count PER RANK.  Under torchrun every rank builds its shard of the envs (``Go2Env(..., shared_globals=True)``: one curriculum, one
@@ -57,6 +59,14 @@ def main():
     ap.add_argument("--rnn-hidden", type=int, default=256, help="rnn_hidden_size of --recurrent")
     ap.add_argument("--empirical-normalization", action="store_true",
                     help="normalise both observation sets with running statistics (train_cfg['empirical_normalization']); the checkpoints carry them")
+    ap.add_argument("--actor-obs", choices=("policy", "critic"), default="policy",
+                    help="the env observation group the PPO actor reads (train_cfg['obs_groups']['policy']); 'critic' trains a teacher on the privileged rows")
+    ap.add_argument("--distill", default=None, metavar="TEACHER_CKPT",
+                    help="distil the actor of this PPO checkpoint into a student (Distillation + StudentTeacher); one rank")
+    ap.add_argument("--student-hidden", type=int, nargs="+", default=[256, 256, 256], help="student_hidden_dims of --distill")
+    ap.add_argument("--gradient-length", type=int, default=15, help="steps per gradient window of --distill")
+    ap.add_argument("--loss-type", choices=("mse", "huber"), default="mse", help="behaviour loss of --distill")
+    ap.add_argument("--teacher-obs", choices=("policy", "critic"), default="policy", help="the env observation group the teacher of --distill reads")
     ap.add_argument("--resume", default=None, help="checkpoint to load on every rank before training")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -94,7 +104,24 @@ def main():
             cfg["policy"] = dict(cfg["policy"], class_name="ActorCriticRecurrent", rnn_type="lstm", rnn_hidden_size=args.rnn_hidden, rnn_num_layers=1)
         if args.empirical_normalization:
             cfg["empirical_normalization"] = True
+        if args.actor_obs != "policy":
+            cfg["obs_groups"] = {"policy": args.actor_obs}
+        if args.distill:
+            if world > 1 or args.recurrent or args.symmetry != "off" or args.actor_obs != "policy":
+                raise SystemExit("--distill runs on one rank, without --recurrent, --symmetry and --actor-obs")
+            from go2_sim2real_locomotion_rl_amd import read_checkpoint
+
+            sd = read_checkpoint(args.distill)["model_state_dict"]                 # the teacher's hidden sizes are the checkpoint's actor's
+            n_layers = len([k for k in sd if k.startswith("actor.") and k.endswith(".weight")])
+            teacher_hidden = [int(sd[f"actor.{2 * l}.weight"].shape[0]) for l in range(n_layers - 1)]
+            cfg["algorithm"] = {"class_name": "Distillation", "num_learning_epochs": 1, "gradient_length": args.gradient_length,
+                                "learning_rate": 1e-3, "max_grad_norm": None, "loss_type": args.loss_type}
+            cfg["policy"] = {"class_name": "StudentTeacher", "activation": "elu", "student_hidden_dims": list(args.student_hidden),
+                             "teacher_hidden_dims": teacher_hidden, "init_noise_std": 0.1}
+            cfg["obs_groups"] = {"teacher": args.teacher_obs}
         runner = OnPolicyRunner(env, cfg, log_dir=args.log_dir, device=device)      # picks up the default process group
+        if args.distill:
+            runner.load(args.distill)                                               # the teacher (and its normaliser, if the checkpoint has one)
         if args.resume:
             runner.load(args.resume)
         log = runner.learn(args.iterations, init_at_random_ep_len=True)
