@@ -72,6 +72,12 @@ C.update(_C_STAIRINFO)
 DISTILL_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_distill.h")
 _C_DISTILL, DECLARED_DISTILL_FUNCS = _parse_header(DISTILL_HEADER)
 C.update(_C_DISTILL)
+# the hidden-layer activation of an MLP (include/go2sim_activation.h): product library only, a list of its own
+ACT_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_activation.h")
+_C_ACT, DECLARED_ACT_FUNCS = _parse_header(ACT_HEADER)
+C.update(_C_ACT)
+# train_cfg["policy"]["activation"] as rsl_rl's resolve_nn_activation spells it -> GO2SIM_ACT_*
+ACTIVATIONS = {n: C["GO2SIM_ACT_" + n.upper()] for n in ("elu", "selu", "relu", "lrelu", "tanh", "sigmoid", "identity")}
 
 
 class PpoCfg(ctypes.Structure):
@@ -167,7 +173,7 @@ class Go2SimLib:
             fn = getattr(self.lib, prefix + name[len("go2sim_"):])
             fn.restype = ctypes.c_int
         if self.is_device:
-            for name in DECLARED_TRAIN_FUNCS + DECLARED_RNN_FUNCS + DECLARED_NORM_FUNCS + DECLARED_LIDAR_FUNCS + DECLARED_STAIRINFO_FUNCS + DECLARED_DISTILL_FUNCS:       # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
+            for name in DECLARED_TRAIN_FUNCS + DECLARED_RNN_FUNCS + DECLARED_NORM_FUNCS + DECLARED_LIDAR_FUNCS + DECLARED_STAIRINFO_FUNCS + DECLARED_DISTILL_FUNCS + DECLARED_ACT_FUNCS:       # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
                 if hasattr(self.lib, name):
                     getattr(self.lib, name).restype = ctypes.c_int
 

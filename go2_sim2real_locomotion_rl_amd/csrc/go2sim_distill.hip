@@ -142,7 +142,7 @@ BwdLayer student_layer(const go2sim_distill* h, int lb, const float* obs) {
   const int l = M->n_layers - 1 - lb;                      // lb counts from the last layer
   if (l < 0) return L;
   L.active = 1;
-  L.N = M->dev.npad[l]; L.K = M->dev.kpad[l];
+  L.N = M->dev.npad[l]; L.K = M->dev.kpad[l]; L.act = M->dev.act;
   L.dz = h->dz[l & 1];
   L.W = M->dev.W[l];
   if (l == 0) { L.aprev = obs; L.lda = M->dims[0]; L.kmax = M->dims[0]; L.gather = 1; L.dzprev = nullptr; }

@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "../../include/go2sim.h"
+#include "../../include/go2sim_activation.h"
 #include "../../include/go2sim_detmath.h"
 #include "../../include/go2sim_policy.h"
 
@@ -23,6 +24,7 @@ struct MlpDev {
   int din[GO2SIM_MLP_MAX_LAYERS], dout[GO2SIM_MLP_MAX_LAYERS], kpad[GO2SIM_MLP_MAX_LAYERS], npad[GO2SIM_MLP_MAX_LAYERS];
   const float* W[GO2SIM_MLP_MAX_LAYERS];   // [npad][kpad], zero padded
   const float* b[GO2SIM_MLP_MAX_LAYERS];   // [npad], zero padded
+  int act;                                 // GO2SIM_ACT_* of the hidden layers (include/go2sim_activation.h); 0 = ELU
 };
 
 struct go2sim_mlp {
@@ -48,6 +50,57 @@ typedef const __attribute__((address_space(1))) f32x4* gcf4p;
 inline int round16(int v) { return (v + 15) / 16 * 16; }
 
 __device__ __forceinline__ float elu1(float v) { return v > 0.0f ? v : dm_exp(v) - 1.0f; }   // nn.ELU(alpha=1)
+// The other activations of include/go2sim_activation.h (the table, the non-finite cases and the error bounds are derived there).  Every argument of
+// dm_exp is <= 0: no form overflows.  A NaN fails every comparison and reaches the arithmetic.
+constexpr float SELU_L = 1.0507009873554805f, SELU_LA = 1.7580993408473766f, LRELU_SLOPE = 0.01f;   // nn.SELU's scale and scale * alpha, nn.LeakyReLU's slope
+__device__ __forceinline__ float selu1(float v) { return v > 0.0f ? SELU_L * v : SELU_LA * (dm_exp(v) - 1.0f); }
+__device__ __forceinline__ float relu1(float v) { return v < 0.0f ? 0.0f : v; }                     // not v > 0 ? v : 0: relu(NaN) is NaN
+__device__ __forceinline__ float lrelu1(float v) { return v > 0.0f ? v : LRELU_SLOPE * v; }
+__device__ __forceinline__ float tanh1(float v) {
+  const float e = dm_exp(-2.0f * dm_abs(v)), t = (1.0f - e) / (1.0f + e);
+  return __builtin_copysignf(t, v);                                                                 // tanh(-0) = -0, as torch
+}
+__device__ __forceinline__ float sigmoid1(float v) {
+  const float e = dm_exp(-dm_abs(v)), d = 1.0f + e;
+  return v >= 0.0f ? 1.0f / d : e / d;
+}
+template <int ACT>
+__device__ __forceinline__ float act_fwd(float v) {
+  return ACT == GO2SIM_ACT_ELU ? elu1(v) : ACT == GO2SIM_ACT_SELU ? selu1(v) : ACT == GO2SIM_ACT_RELU ? relu1(v) : ACT == GO2SIM_ACT_LRELU ? lrelu1(v)
+         : ACT == GO2SIM_ACT_TANH ? tanh1(v) : ACT == GO2SIM_ACT_SIGMOID ? sigmoid1(v) : v;
+}
+// d activation / d pre-activation from the stored post-activation a
+template <int ACT>
+__device__ __forceinline__ float act_bwd(float a) {
+  return ACT == GO2SIM_ACT_ELU ? (a > 0.0f ? 1.0f : a + 1.0f) : ACT == GO2SIM_ACT_SELU ? (a > 0.0f ? SELU_L : a + SELU_LA) : ACT == GO2SIM_ACT_RELU ? (a > 0.0f ? 1.0f : 0.0f)
+         : ACT == GO2SIM_ACT_LRELU ? (a > 0.0f ? 1.0f : LRELU_SLOPE) : ACT == GO2SIM_ACT_TANH ? 1.0f - a * a : ACT == GO2SIM_ACT_SIGMOID ? a * (1.0f - a) : 1.0f;
+}
+// The activation is uniform over a launch's workgroup (a field of the MlpDev record): one scalar branch per epilogue selects the instantiation, so the
+// ELU epilogue's instruction stream is the one it was.
+#define GO2SIM_ACT_DISPATCH(act, CALL)                       \
+  switch (act) {                                             \
+    case GO2SIM_ACT_SELU: CALL(GO2SIM_ACT_SELU); break;      \
+    case GO2SIM_ACT_RELU: CALL(GO2SIM_ACT_RELU); break;      \
+    case GO2SIM_ACT_LRELU: CALL(GO2SIM_ACT_LRELU); break;    \
+    case GO2SIM_ACT_TANH: CALL(GO2SIM_ACT_TANH); break;      \
+    case GO2SIM_ACT_SIGMOID: CALL(GO2SIM_ACT_SIGMOID); break;  \
+    case GO2SIM_ACT_IDENTITY: CALL(GO2SIM_ACT_IDENTITY); break; \
+    default: CALL(GO2SIM_ACT_ELU); break;                    \
+  }
+
+// bias and activation of one accumulator tile of a hidden layer into the other LDS buffer
+template <int ACT>
+__device__ __forceinline__ void mlp_store_hidden(const f32x4 (&acc)[RT], float bv, float (*out)[LDW], int n, int dout, int kq) {
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float v = acc[rt][i] + bv;
+      out[16 * rt + 4 * kq + i][n] = n < dout ? act_fwd<ACT>(v) : 0.0f;   // the K padding of the next layer is zero whatever the inputs and the activation
+                                                                          // (sigmoid(0) = 0.5): a non-finite activation times the padded weight 0 would be
+                                                                          // NaN here and in every output after it
+    }
+}
 
 // One layer for the RT x 16 rows of the workgroup.  A wavefront works on TG output tiles (16 columns each) at a time: RT x TG independent accumulators
 // share one weight fragment per (tile, K step) over the row tiles and one A fragment per (row tile, K step) over the output tiles.
@@ -105,20 +158,23 @@ __device__ __forceinline__ void mlp_layer(const MlpDev& M, int l, const float (*
       if (g0 + t >= ntiles) break;
       const int n = (g0 + t) * 16 + arow;                              // accumulator element i of this lane: row 4 * (lane >> 4) + i, column lane & 15
       const float bv = bias[n];
+      if (last) {
 #pragma unroll
-      for (int rt = 0; rt < RT; ++rt)
+        for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int r = 16 * rt + 4 * kq + i;
-          const float v = acc[rt][t][i] + bv;
-          if (last) {
-            const int gr = row0 + r;
+          for (int i = 0; i < 4; ++i) {
+            const int gr = row0 + 16 * rt + 4 * kq + i;
+            const float v = acc[rt][t][i] + bv;
             if (gr < B && n < dout) y[(size_t)gr * dout + n] = v;
-          } else {
-            out[r][n] = n < dout ? elu1(v) : 0.0f;                       // the K padding of the next layer is zero whatever the inputs: a non-finite
-                                                                         // activation times the padded weight 0 would be NaN here and in every output after it
           }
-        }
+      } else {
+        f32x4 tile[RT];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) tile[rt] = acc[rt][t];
+#define GO2SIM_STORE_HIDDEN(A) mlp_store_hidden<A>(tile, bv, out, n, dout, kq)
+        GO2SIM_ACT_DISPATCH(M.act, GO2SIM_STORE_HIDDEN)
+#undef GO2SIM_STORE_HIDDEN
+      }
     }
   }
 }

@@ -2,8 +2,8 @@
 //
 // One kernel evaluates a whole MLP: a workgroup (4 wavefronts) owns RT x 16 rows of the batch and keeps their activations in LDS across all
 // layers; a layer is a [16 x K] x [K x N] product per row tile on the fp32 matrix cores (v_mfma_f32_16x16x4_f32, exact fp32: a k-ordered fma chain),
-// the four wavefronts take the 16-column output tiles round-robin, bias and ELU are applied on the accumulator and the result goes to the other
-// LDS buffer.  Weights stream from L2 (0.8 MB actor / 0.9 MB critic); every weight fragment a wavefront loads is used for RT row tiles (RT = 2: 32 rows
+// the four wavefronts take the 16-column output tiles round-robin, bias and the activation (ELU unless go2sim_act_set chose another:
+// include/go2sim_activation.h) are applied on the accumulator and the result goes to the other LDS buffer.  Weights stream from L2 (0.8 MB actor / 0.9 MB critic); every weight fragment a wavefront loads is used for RT row tiles (RT = 2: 32 rows
 // per workgroup, 132 KB of LDS, one workgroup per CU, 2 x 128 workgroups at 4096 rows; the accumulation chain of every output element is the one of
 // RT = 1).  Counters at 4096 rows (tools/policy_pmc.sh): 65 us per launch, the matrix pipe busy 38 % of the time (1.69 M matrix instructions = the
 // 3.3 GFLOP), 23 % in the 6.5 M other vector instructions (mostly the deterministic exp of the ELU epilogue, which a wavefront runs between its
@@ -183,6 +183,18 @@ int go2sim_mlp_set_params(go2sim_mlp_t* h, const float* params, size_t n_params,
   pack_padded(h, params, packed);
   HIPCHK(hipMemcpyAsync(h->dparams, packed.data(), h->padded * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream));
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));   // `packed` is a temporary
+  return GO2SIM_E_OK;
+}
+
+// include/go2sim_activation.h: a host-side field of the record every launch passes by value
+int go2sim_act_set(go2sim_mlp_t* h, int act) {
+  if (!h || act < 0 || act >= GO2SIM_ACT_COUNT) return GO2SIM_E_BADARG;
+  h->dev.act = act;
+  return GO2SIM_E_OK;
+}
+int go2sim_act_get(const go2sim_mlp_t* h, int* out) {
+  if (!h || !out) return GO2SIM_E_BADARG;
+  *out = h->dev.act;
   return GO2SIM_E_OK;
 }
 

@@ -12,7 +12,7 @@
 //                     take a quarter of the chunk's rows each (8 independent accumulators per wavefront, chains of 128 rows), their results are added
 //                     in wavefront order through LDS and written to the chunk's slab of partials.
 //     k_bwd_db        db = column sums of dZ per chunk (float64: 16 row slices per column, added in slice order), into the same slab.
-//     k_bwd_da        dZ_prev = (dZ W) * ELU'(A_prev), 32 rows per workgroup, 4 accumulators per wavefront.  W is read strided ([npad][kpad], the
+//     k_bwd_da        dZ_prev = (dZ W) * f'(A_prev) (f: the network's activation, ELU by default), 32 rows per workgroup, 4 accumulators per wavefront.  W is read strided ([npad][kpad], the
 //                     reduction runs over its rows): no transposed copy of the weights is kept, the optimizer writes one array per layer.
 //                     Not launched for the first layer.
 //   k_reduce_partials adds the chunk slabs in chunk order in float64 and rounds once: the padded gradient vector.
@@ -328,7 +328,7 @@ BwdLayer bwd_layer(const go2sim_ppo* h, int net, int lb, const go2sim_ppo_batch_
   const int l = M->n_layers - 1 - lb;                      // lb counts from the last layer
   if (l < 0) return L;
   L.active = 1;
-  L.N = M->dev.npad[l]; L.K = M->dev.kpad[l];
+  L.N = M->dev.npad[l]; L.K = M->dev.kpad[l]; L.act = M->dev.act;
   L.dz = h->dz[net][l & 1];
   L.W = M->dev.W[l];
   if (l == 0) {

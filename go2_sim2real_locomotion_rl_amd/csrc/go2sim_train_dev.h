@@ -100,7 +100,8 @@ struct BwdLayer {
   int gather;           // aprev rows are read through idx
   MirTab mir;           // gather layers under a mirror: rows >= n_orig read row idx[r - n_orig] through this table
   int active;           // this network has this layer
-  int lin;              // k_bwd_da<true>: the layer's input is a memory's h, not an ELU output: dzprev = dZ W without the ELU factor
+  int lin;              // k_bwd_da<true>: the layer's input is a memory's h, not an activation's output: dzprev = dZ W without the derivative's factor
+  int act;              // GO2SIM_ACT_* of the network (MlpDev::act): the derivative k_bwd_da multiplies by
   size_t w_off, b_off;  // offsets of dW / db in a slab of partials (= in the padded gradient vector)
 };
 
@@ -201,7 +202,23 @@ __global__ __launch_bounds__(WGT) void k_bwd_db(BwdLayer L0, BwdLayer L1, int n_
   }
 }
 
-// dZ_prev[r][k] = (sum_n dZ[r][n] W[n][k]) * ELU'(A_prev[r][k]); ELU' from the stored post-activation a: 1 for a > 0, a + 1 otherwise
+// one accumulator tile of k_bwd_da times the activation's derivative, from the stored post-activation (act_bwd, go2sim_mlp_dev.h)
+template <int ACT>
+__device__ __forceinline__ void bwd_store_dzprev(const f32x4 (&acc)[RT], const float* __restrict__ aprev, float* __restrict__ dzprev, int row0, int n_rows, int K, int kc, int kq) {
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = row0 + 16 * rt + 4 * kq + i;
+      if (r < n_rows) {
+        const float a = aprev[(size_t)r * K + kc];
+        dzprev[(size_t)r * K + kc] = acc[rt][i] * act_bwd<ACT>(a);
+      }
+    }
+}
+
+// dZ_prev[r][k] = (sum_n dZ[r][n] W[n][k]) * f'(A_prev[r][k]); f' of the network's activation (L.act) from the stored post-activation a: for ELU 1 for
+// a > 0, a + 1 otherwise
 // RNN: a first layer behind a memory (L.lin) writes d loss / d h; the plain instantiation is the kernel as it was
 template <bool RNN>
 __global__ __launch_bounds__(64 * NWAVE) void k_bwd_da(BwdLayer L0, BwdLayer L1, int n_rows) {
@@ -245,17 +262,22 @@ __global__ __launch_bounds__(64 * NWAVE) void k_bwd_da(BwdLayer L0, BwdLayer L1,
 #pragma unroll
     for (int t = 0; t < TG; ++t) {
       if (g0 + t >= ktiles) break;
+      f32x4 tile[RT];
 #pragma unroll
-      for (int rt = 0; rt < RT; ++rt)
+      for (int rt = 0; rt < RT; ++rt) tile[rt] = acc[rt][t];
+      if (RNN && L.lin) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int r = row0 + 16 * rt + 4 * kq + i;
-          if (r < n_rows) {
-            if (RNN && L.lin) { L.dzprev[(size_t)r * K + kc[t]] = acc[rt][t][i]; continue; }
-            const float a = L.aprev[(size_t)r * K + kc[t]];
-            L.dzprev[(size_t)r * K + kc[t]] = acc[rt][t][i] * (a > 0.0f ? 1.0f : a + 1.0f);
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int r = row0 + 16 * rt + 4 * kq + i;
+            if (r < n_rows) L.dzprev[(size_t)r * K + kc[t]] = tile[rt][i];
           }
-        }
+        continue;
+      }
+#define GO2SIM_STORE_DZPREV(A) bwd_store_dzprev<A>(tile, L.aprev, L.dzprev, row0, n_rows, K, kc[t], kq)
+      GO2SIM_ACT_DISPATCH(L.act, GO2SIM_STORE_DZPREV)
+#undef GO2SIM_STORE_DZPREV
     }
   }
 }

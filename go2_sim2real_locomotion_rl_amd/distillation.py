@@ -21,7 +21,7 @@ import torch
 
 from .capi import C, DistillCfg, Go2SimError, load_hip_lib
 from .distributed import is_multi
-from .policy import Mlp, _ptr, flatten_sequential, policy_act
+from .policy import Mlp, _ptr, flatten_sequential, policy_act, resolve_activation
 
 LOSS_TYPES = ("mse", "huber")
 
@@ -204,8 +204,7 @@ class StudentTeacher:
 
     def __init__(self, num_student_obs, num_teacher_obs, num_actions, student_hidden_dims=(256, 256, 256), teacher_hidden_dims=(256, 256, 256), activation="elu",
                  init_noise_std=0.1, *, device=None, seed=1, **kwargs):
-        if activation != "elu":
-            raise Go2SimError("go2sim implements the reference's activation ('elu')")
+        self.activation = resolve_activation(activation)                          # one name for student and teacher, as in rsl_rl; refused before the device is touched
         unknown = {k: v for k, v in kwargs.items() if k != "class_name" and v is not None}
         if unknown:
             raise Go2SimError(f"StudentTeacher does not implement {sorted(unknown)}")
@@ -241,7 +240,7 @@ class StudentTeacher:
             raise Go2SimError(f"state dict has {prefix} layer sizes {d}, this model's are {dims}")
         cur = self._student if which == "student" else self._teacher
         if cur is None:
-            net = Mlp(self._L, dims, flat, self.device.index or 0)
+            net = Mlp(self._L, dims, flat, self.device.index or 0, self.activation)
             if which == "student":
                 self._student = net
             else:
@@ -341,6 +340,10 @@ class StudentTeacher:
 
 # ---- the algorithm ---------------------------------------------------------------------------------------------------------------------------------
 class Distillation:
+    """rsl_rl's Distillation on a StudentTeacher.  The activation is the policy's (``train_cfg["policy"]["activation"]``, one name for student and teacher):
+    as in rsl_rl it lives in the config (``cfgs.pkl``), not in ``model_<it>.pt``, so a teacher checkpoint is interpreted with the student config's
+    activation -- a teacher trained with another one loads without complaint and computes something else."""
+
     def __init__(self, policy, num_learning_epochs=1, gradient_length=15, learning_rate=1e-3, max_grad_norm=None, loss_type="mse", device=None, *, group=None, **kwargs):
         unknown = {k: v for k, v in kwargs.items() if k != "class_name" and v is not None}
         if unknown:

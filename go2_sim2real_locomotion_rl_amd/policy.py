@@ -13,6 +13,8 @@ parameters with :meth:`load_state_dict`.
 
 State-dict keys are those of the reference class: ``actor.{0,2,4,6}.{weight,bias}``, ``critic.{0,2,4,6}.{weight,bias}``, ``std``.
 Random numbers come from the library's counter-based Philox stream (seed, row, step), not from torch's global generator.
+``activation`` is one of rsl_rl's ``elu``, ``selu``, ``relu``, ``lrelu``, ``tanh``, ``sigmoid``, ``identity`` (include/go2sim_activation.h); as in rsl_rl it is part of the
+config, not of the checkpoint.
 
 ``ActorCriticRecurrent`` (below) is ``rsl_rl.modules.ActorCriticRecurrent`` with one LSTM layer per network (include/go2sim_rnn.h): the same surface plus
 ``reset(dones)`` / ``get_hidden_states()``, and the keys ``memory_{a,c}.rnn.{weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0}``.
@@ -22,14 +24,29 @@ import ctypes
 import numpy as np
 import torch
 
-from .capi import Go2SimError, load_hip_lib
+from .capi import ACTIVATIONS, Go2SimError, load_hip_lib
+
+
+def resolve_activation(name):
+    """train_cfg["policy"]["activation"] -> one of the seven names of include/go2sim_activation.h (rsl_rl's resolve_nn_activation, each meaning the same torch
+    module).  Touches no device: a refusal is a Go2SimError before anything is allocated."""
+    key = str(name).lower()
+    if key == "crelu":
+        raise Go2SimError("activation 'crelu' is not implemented: it doubles the layer's width and is not a function of one value; "
+                          f"go2sim implements {sorted(ACTIVATIONS)}")
+    if key not in ACTIVATIONS:
+        raise Go2SimError(f"unknown activation {name!r}: go2sim implements {sorted(ACTIVATIONS)}")
+    return key
 
 
 class Mlp:
-    """One go2sim_mlp handle (works with either library: product or CPU oracle)."""
+    """One go2sim_mlp handle (works with either library: product or CPU oracle; the oracle's is ELU only)."""
 
-    def __init__(self, lib, dims, params, device=0):
+    def __init__(self, lib, dims, params, device=0, activation="elu"):
         self.L, self.dims = lib, [int(d) for d in dims]
+        activation = resolve_activation(activation)
+        if activation != "elu" and not lib.is_device:                              # before the handle exists: nothing to release on the refusal
+            raise Go2SimError("the CPU oracle's MLP is ELU only (include/go2sim_activation.h has no CPU twin)")
         params = np.ascontiguousarray(params, dtype=np.float32)
         self.n_params = params.size
         h = ctypes.c_void_p()
@@ -38,6 +55,23 @@ class Mlp:
                                   ctypes.c_size_t(params.size), ctypes.byref(h))
         lib.check(rc, "mlp_create")
         self.h = h
+        self.activation = "elu"
+        if activation != "elu":
+            self.set_activation(activation)
+
+    def set_activation(self, name):
+        """go2sim_act_set (include/go2sim_activation.h): to be called before the handle's first launch.  Product library only."""
+        name = resolve_activation(name)
+        if not self.L.is_device:
+            raise Go2SimError("the CPU oracle's MLP is ELU only (include/go2sim_activation.h has no CPU twin)")
+        self.L.check(self.L.lib.go2sim_act_set(self.h, ctypes.c_int(ACTIVATIONS[name])), "act_set")
+        self.activation = name
+
+    def get_activation(self):
+        """the name behind go2sim_act_get"""
+        out = ctypes.c_int(-1)
+        self.L.check(self.L.lib.go2sim_act_get(self.h, ctypes.byref(out)), "act_get")
+        return {v: k for k, v in ACTIVATIONS.items()}[out.value]
 
     def set_params(self, params, stream=0):
         params = np.ascontiguousarray(params, dtype=np.float32)
@@ -94,8 +128,7 @@ class ActorCritic:
 
     def __init__(self, num_actor_obs, num_critic_obs, num_actions, actor_hidden_dims=(512, 256, 128), critic_hidden_dims=(512, 256, 128),
                  activation="elu", init_noise_std=1.0, *, device=None, seed=1, **kwargs):
-        if activation != "elu":
-            raise Go2SimError("go2sim implements the reference's activation ('elu', go2_train_walk.py:42)")
+        self.activation = resolve_activation(activation)                          # before anything touches the device: a refusal needs no GPU
         if not torch.cuda.is_available():
             raise Go2SimError("no ROCm GPU visible: the go2sim product path has no CPU fallback")
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -125,7 +158,7 @@ class ActorCritic:
             raise Go2SimError(f"state dict has layer sizes {da} / {dc}, expected {self._adims} / {self._cdims}")
         dev = self.device.index or 0
         if self._actor is None:
-            self._actor, self._critic = Mlp(self._L, da, pa, dev), Mlp(self._L, dc, pc, dev)
+            self._actor, self._critic = Mlp(self._L, da, pa, dev, self.activation), Mlp(self._L, dc, pc, dev, self.activation)
         else:
             self._actor.set_params(pa); self._critic.set_params(pc)
         self.std.copy_(state_dict["std"].detach().reshape(self.num_actions))     # in place: std stays the device tensor the update kernels write

@@ -2,7 +2,7 @@
 """Times PPO.update() of the library against an eager-torch fp32 restatement of the same update on the same GPU, at the training shape of the
 walk task: T = 24 steps x B = 4096 envs, 49 / 104 observations, 16 actions, two 512-256-128 MLPs, 5 epochs x 4 mini-batches of 24 576 rows.
 
-    python tools/ppo_update_bench.py [--updates 5] [--warmup 2] [--envs 4096] [--steps 24] [--shards N] [--symmetry {off,augment,mirror,both}]
+    python tools/ppo_update_bench.py [--updates 5] [--warmup 2] [--envs 4096] [--steps 24] [--shards N] [--symmetry {off,augment,mirror,both}] [--activation NAME]
     python tools/ppo_update_bench.py --recurrent [--rnn-hidden 256] [--collection]
 
 Both sides update from the same rollout (collected once with the library's ActorCritic on random observations and rewards) and the same initial
@@ -37,12 +37,16 @@ HP = dict(clip_param=0.2, desired_kl=0.01, entropy_coef=0.003, learning_rate=1e-
 EPOCHS, MINI_BATCHES = 5, 4
 
 
+TORCH_ACT = {"elu": nn.ELU, "selu": nn.SELU, "relu": nn.ReLU, "lrelu": nn.LeakyReLU, "tanh": nn.Tanh, "sigmoid": nn.Sigmoid, "identity": nn.Identity}
+ACTIVATION = "elu"                                             # --activation: both sides' hidden layers (include/go2sim_activation.h)
+
+
 def mlp(dims):
     layers = []
     for l in range(len(dims) - 1):
         layers.append(nn.Linear(dims[l], dims[l + 1]))
         if l < len(dims) - 2:
-            layers.append(nn.ELU())
+            layers.append(TORCH_ACT[ACTIVATION]())
     return nn.Sequential(*layers)
 
 
@@ -204,7 +208,10 @@ def main():
     ap.add_argument("--recurrent", action="store_true", help="time the recurrent (LSTM) update against eager torch")
     ap.add_argument("--rnn-hidden", type=int, default=256)
     ap.add_argument("--collection", action="store_true", help="with --recurrent: also time the closed collection loop with the MLP and the recurrent policy")
+    ap.add_argument("--activation", choices=sorted(TORCH_ACT), default="elu", help="the hidden layers' activation on both sides")
     args = ap.parse_args()
+    global ACTIVATION
+    ACTIVATION = args.activation
     if not torch.cuda.is_available():
         raise SystemExit("ppo_update_bench needs a ROCm GPU: a time taken anywhere else says nothing")
     from go2_sim2real_locomotion_rl_amd import PPO, ActorCritic
@@ -215,7 +222,7 @@ def main():
     T, B, nobs, npriv, nact = args.steps, args.envs, 49, 104, 16
     hidden = [512, 256, 128]
     adims, cdims = [nobs, *hidden, nact], [npriv, *hidden, 1]
-    policy = ActorCritic(nobs, npriv, nact, hidden, hidden, device=dev, seed=1)
+    policy = ActorCritic(nobs, npriv, nact, hidden, hidden, activation=args.activation, device=dev, seed=1)
     state = {k: v.clone() for k, v in policy.state_dict().items()}
     sym = None
     if args.symmetry != "off":
@@ -281,7 +288,7 @@ def main():
     if sym is not None:
         extra["symmetry"] = args.symmetry
         extra["symmetry_loss"] = alg.symmetry_loss
-    print(json.dumps({"tool": "ppo_update_bench", "envs": B, "steps": T, "epochs": EPOCHS, "mini_batches": MINI_BATCHES, "updates_timed": args.updates,
+    print(json.dumps({"tool": "ppo_update_bench", "activation": args.activation, "envs": B, "steps": T, "epochs": EPOCHS, "mini_batches": MINI_BATCHES, "updates_timed": args.updates,
                       "hip_ms_per_update": round(hip_ms, 3), "torch_eager_ms_per_update": round(torch_ms, 3), "hip_over_torch": round(hip_ms / torch_ms, 3),
                       "matrix_flop_per_update": flop, "hip_fraction_of_157.3_tflops": round(flop / (hip_ms * 1e-3) / PEAK_FP32_MATRIX, 4), **extra}))
 
@@ -292,7 +299,7 @@ def main_recurrent(args, dev):
     T, B, nobs, npriv, nact, H = args.steps, args.envs, 49, 104, 16, args.rnn_hidden
     hidden = [512, 256, 128]
     adims, cdims = [H, *hidden, nact], [H, *hidden, 1]
-    policy = ActorCriticRecurrent(nobs, npriv, nact, hidden, hidden, rnn_hidden_size=H, device=dev, seed=1)
+    policy = ActorCriticRecurrent(nobs, npriv, nact, hidden, hidden, activation=args.activation, rnn_hidden_size=H, device=dev, seed=1)
     state = {k: v.clone() for k, v in policy.state_dict().items()}
     alg = PPO(policy, num_learning_epochs=EPOCHS, num_mini_batches=MINI_BATCHES, schedule="adaptive", gamma=0.99, lam=0.95, seed=1, **HP)
     alg.init_storage(B, T, [nobs], [npriv], [nact])
@@ -330,7 +337,7 @@ def main_recurrent(args, dev):
     if args.collection:
         del alg, policy, ref
         extra = {"collect_ms_mlp": round(time_collection(dev, B, T, False, H), 3), "collect_ms_recurrent": round(time_collection(dev, B, T, True, H), 3)}
-    print(json.dumps({"tool": "ppo_update_bench", "recurrent": True, "rnn_hidden": H, "envs": B, "steps": T, "epochs": EPOCHS, "mini_batches": MINI_BATCHES,
+    print(json.dumps({"tool": "ppo_update_bench", "activation": args.activation, "recurrent": True, "rnn_hidden": H, "envs": B, "steps": T, "epochs": EPOCHS, "mini_batches": MINI_BATCHES,
                       "updates_timed": args.updates, "hip_ms_per_update": round(hip_ms, 3), "torch_eager_ms_per_update": round(torch_ms, 3),
                       "hip_over_torch": round(hip_ms / torch_ms, 3), "matrix_flop_per_update": flop,
                       "hip_fraction_of_157.3_tflops": round(flop / (hip_ms * 1e-3) / PEAK_FP32_MATRIX, 4), **extra}))

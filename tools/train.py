@@ -67,6 +67,9 @@ def main():
     ap.add_argument("--gradient-length", type=int, default=15, help="steps per gradient window of --distill")
     ap.add_argument("--loss-type", choices=("mse", "huber"), default="mse", help="behaviour loss of --distill")
     ap.add_argument("--teacher-obs", choices=("policy", "critic"), default="policy", help="the env observation group the teacher of --distill reads")
+    ap.add_argument("--activation", default=None, metavar="NAME",
+                    help="train_cfg['policy']['activation']: elu, selu, relu, lrelu, tanh, sigmoid or identity (default: the config's own, 'elu'); "
+                         "with --distill the student's and the teacher's")
     ap.add_argument("--resume", default=None, help="checkpoint to load on every rank before training")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -100,6 +103,8 @@ def main():
         if args.symmetry != "off":                                                  # the runner fills in the env's own mirror tables
             cfg["algorithm"]["symmetry_cfg"] = {"use_data_augmentation": args.symmetry in ("augment", "both"),
                                                 "use_mirror_loss": args.symmetry in ("mirror", "both"), "mirror_loss_coeff": args.mirror_coeff}
+        if args.activation:
+            cfg["policy"] = dict(cfg["policy"], activation=args.activation)
         if args.recurrent:
             cfg["policy"] = dict(cfg["policy"], class_name="ActorCriticRecurrent", rnn_type="lstm", rnn_hidden_size=args.rnn_hidden, rnn_num_layers=1)
         if args.empirical_normalization:
@@ -116,7 +121,7 @@ def main():
             teacher_hidden = [int(sd[f"actor.{2 * l}.weight"].shape[0]) for l in range(n_layers - 1)]
             cfg["algorithm"] = {"class_name": "Distillation", "num_learning_epochs": 1, "gradient_length": args.gradient_length,
                                 "learning_rate": 1e-3, "max_grad_norm": None, "loss_type": args.loss_type}
-            cfg["policy"] = {"class_name": "StudentTeacher", "activation": "elu", "student_hidden_dims": list(args.student_hidden),
+            cfg["policy"] = {"class_name": "StudentTeacher", "activation": cfg["policy"].get("activation", "elu"), "student_hidden_dims": list(args.student_hidden),
                              "teacher_hidden_dims": teacher_hidden, "init_noise_std": 0.1}
             cfg["obs_groups"] = {"teacher": args.teacher_obs}
         runner = OnPolicyRunner(env, cfg, log_dir=args.log_dir, device=device)      # picks up the default process group
