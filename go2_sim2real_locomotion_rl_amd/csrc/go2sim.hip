@@ -768,6 +768,11 @@ __device__ unsigned long long g_phase_cycles[PH_MAX_WG * 64];
 // k_env_post_b_team: the 64 ids of a row are taken, so its marks go to the upper half of the rows (workgroup w: row PH_MAX_WG / 2 + w, ids from 0);
 // PH / PHD / PHC of the other kernels are confined to the lower half (they use at most 2048 rows at 4096 envs)
 #define PHB(i) { __builtin_amdgcn_s_waitcnt(0); unsigned long long ph_n = __builtin_readcyclecounter(); if (threadIdx.x == 0 && blockIdx.x < PH_MAX_WG / 2) g_phase_cycles[(PH_MAX_WG / 2 + blockIdx.x) * 64 + (i)] += ph_n - ph_t; ph_t = __builtin_readcyclecounter(); }
+// k_env_post_a, inside the term section: every wave accounts its own marks (its first lane), in rows of their own behind k_env_post_b_team's (row
+// PH_MAX_WG / 2 + PH_MAX_WG / 4 + workgroup; ids: the reward id of a term, PHA_REWK + wave for load_rew_k, PHA_WAIT + wave for the wait at the barrier)
+constexpr int PHA_REWK = 48, PHA_WAIT = 56;
+#define PHA_BEGIN unsigned long long pha_t = __builtin_readcyclecounter();
+#define PHA(i) { __builtin_amdgcn_s_waitcnt(0); unsigned long long pha_n = __builtin_readcyclecounter(); if (threadIdx.x % 64 == 0 && blockIdx.x < PH_MAX_WG / 4) g_phase_cycles[(PH_MAX_WG / 2 + PH_MAX_WG / 4 + blockIdx.x) * 64 + (i)] += pha_n - pha_t; pha_t = __builtin_readcyclecounter(); }
 #else
 #define PH_BEGIN
 #define PH(i)
@@ -775,6 +780,8 @@ __device__ unsigned long long g_phase_cycles[PH_MAX_WG * 64];
 #define PHD(i)
 #define PHC(i, n)
 #define PHB(i)
+#define PHA_BEGIN
+#define PHA(i)
 #endif
 
 // ---- optional wall-clock stamps per workgroup (build with -DGO2SIM_STAMP; tools/launch_overhead.py): every workgroup of the step kernels records
@@ -5116,18 +5123,21 @@ DEV RewGates reward_gates(const RewState& rs) {
 // The configuration words the walk / stairs terms read, fetched in one batch ahead of the term loop (load_rew_k): inside the loop every one of them
 // was a scalar round trip of its own -- the twelve force ranges two dependent ones (motor dof index, then the model's dof record).
 struct RewK { float dt, sigma, lin_vel_z_deadzone, base_height_target, feet_air_time_target, feet_height_target; float def[NM], force_lo[NM], force_hi[NM]; int na, use_terrain; };
-DEV RewK load_rew_k(const Model& m, const DCfg& c) {
+// motor_dof: the dof of motor i.  k_env_post_a gets the twelve from the host with its launch arguments (TermDeal), so the force ranges -- read from the
+// Model on the device every step: go2sim_set_dof_gains may change them -- are requested with the kernel's first loads.
+DEV RewK load_rew_k(const Model& m, const DCfg& c, const int* motor_dof) {
   RewK K;
   K.dt = c.f[GO2SIM_FC_DT]; K.sigma = c.f[GO2SIM_FC_TRACKING_SIGMA]; K.lin_vel_z_deadzone = c.f[GO2SIM_FC_LIN_VEL_Z_DEADZONE];
   K.base_height_target = c.f[GO2SIM_FC_BASE_HEIGHT_TARGET]; K.feet_air_time_target = c.f[GO2SIM_FC_FEET_AIR_TIME_TARGET]; K.feet_height_target = c.f[GO2SIM_FC_FEET_HEIGHT_TARGET];
   K.na = c.i[GO2SIM_IC_NUM_ACTIONS]; K.use_terrain = c.i[GO2SIM_IC_USE_TERRAIN];
 #pragma unroll
   for (int i = 0; i < NM; ++i) {
-    const int d = c.i[GO2SIM_IC_MOTOR_DOF0 + i];
+    const int d = motor_dof[i];
     K.def[i] = c.f[GO2SIM_FC_DEFAULT_DOF_POS0 + i]; K.force_lo[i] = m.dofs[d].force_range[0]; K.force_hi[i] = m.dofs[d].force_range[1];
   }
   return K;
 }
+DEV RewK load_rew_k(const Model& m, const DCfg& c) { return load_rew_k(m, c, &c.i[GO2SIM_IC_MOTOR_DOF0]); }
 DEV float reward_term(const Model& m, const DCfg& c, const RewK& K, RewState& rs, int id, const RewCtx& rc, const RewGates& gt) {
   const float dt = K.dt;
   const float* cmd = rs.cmd; const float* blv = rs.blv; const float* bav = rs.bav; const float* dof_pos = rs.dof_pos; const float* dof_vel = rs.dof_vel;
@@ -5272,25 +5282,73 @@ DEV float reward_term(const Model& m, const DCfg& c, const RewK& K, RewState& rs
 // One lane per env; the kernel is a single wave per 64 envs, so its duration is its dependency chain: every input is loaded before the
 // first store (one memory round trip instead of one per reward term) and the per-term episode sums sit in LDS for the dynamic term loop.
 DEV void env_globals_body(const DCfg& c, Glob& g, Acc* acc, uint64_t seed, int count_push);
-// Lane per env; the workgroup is POST_A_NWAVES wavefronts over the SAME 64 envs.  Every wave loads the state and forms the shared quantities (base frame
-// velocities, Euler angles, foot contacts, command gates) redundantly; the reward TERMS -- the long serial part: 19 independent functions of that state --
+// Lane per env; the workgroup is POST_A_NWAVES wavefronts over the SAME 64 envs.  Every wave loads the state and forms what the terms read (base frame
+// velocities, foot contacts, the command, its gates) redundantly -- the Euler angles, the termination test and every store are wave 0's alone, see the
+// split in the kernel; the reward TERMS -- the long serial part: 19 independent functions of that state --
 // are dealt to the waves (term k runs on one wave, its value goes to LDS), and wave 0 then adds them in the reference's order and makes every store.
 // The three terms that touch env state beyond their own value (feet_air_time writes and feet_stance reads _feet_air_time, go2_env_walk.py:1303-1314;
 // forward_progress moves _last_base_pos_x) stay together on wave 0, in order.  Same operations per value and the same sum order: results unchanged.
 // Which wave runs a term is decided on the host, once per configuration (deal_terms): wave 0 -- the wave that also makes every store and the sum -- keeps
-// only the stateful terms; the others go to the worker waves heaviest first, each to the least loaded worker, by the instruction counts of reward_term_cost.
+// only the stateful terms; the others go to the worker waves heaviest first, each to the least loaded worker, by the measured cycles of reward_term_cost.
 // (A wave runs its terms once, on cold code: what a term costs is roughly its length.  The former round-robin `(1 + j) % POST_A_NWAVES` gave wave 0 of the
 // walk's 19 terms dof_acc, foot_clearance, stand_still and base_height on top of its own two.)
 // (Wave count: eight wavefronts measured slower with the round-robin deal -- two 215-register wavefronts per SIMD get in each other's way; four, six and
 // eight were measured again with the deal by cost: DESIGN.md, round 7, profiles/r07_post_a_waves.txt.)
+// How a worker wave runs its terms (round 9): not as a loop over the list -- per term a dependent scalar load of the id, a switch into a case block that
+// was never fetched, a second scalar load for the scale -- but BY ID: the wave walks the ids of POST_A_TERMS in that one source order as straight-line
+// code, tests its own bit of the id (a scalar test on a kernel argument, no table load in front of it), and where the bit is set evaluates reward_term
+// with the id as a CONSTANT (the switch folds to that term's own expression: same operations, same order), multiplies by the id's scale and writes
+// s_r[slot of the id].  Masks, id -> slot and the scales by id are kernel arguments built with the launch list (deal_terms).  Wave 0 runs its (at most
+// three) stateful terms by id as well, in list order (POST_A_STATEFUL); a list that names an id twice or an id outside the two sets sends every wave
+// through the loop over the list (TermDeal::straight == 0, decided on the host).  Measured: a wave's first pass through that loop
+// stalls it for about 9 k cycles, whatever the term -- which is why no wave enters it on the shipped lists.
 constexpr int POST_A_NWAVES = 4;
-struct TermDeal { uint32_t w[NREW / 8]; uint32_t tracking; };       // owner wave of term k: four bits each; bit k of `tracking`: term k is a tracking term
+struct TermDeal {
+  uint32_t w[NREW / 8]; uint32_t tracking;                          // owner wave of term k: four bits each; bit k of `tracking`: term k is a tracking term
+  uint32_t straight;                                                // the workers run their terms by id (mask / slot / scale below); 0: every wave takes the loop
+  uint64_t mask[POST_A_NWAVES];                                     // bit id: the wave owns the term with that id
+  uint32_t slot[(GO2SIM_R_COUNT + 3) / 4];                          // id -> list position k, a byte each
+  float scale[GO2SIM_R_COUNT];                                      // by id, not by position: a constant offset into the kernel arguments for every term
+  uint32_t w0_ids;                                                  // wave 0's stateful terms in list order: an id per byte, 255: none
+  int motor_dof[NM];                                                // dof of motor i (load_rew_k)
+};
 static_assert(NREW == 32 && POST_A_NWAVES >= 2 && POST_A_NWAVES <= 16, "TermDeal holds four bits per term");
+static_assert(GO2SIM_R_COUNT <= 64, "TermDeal::mask holds one bit per reward id");
+// the ids the straight-line section knows: the terms of the walk and stairs lists (go2_env_walk.py, go2_env_stair.py) except the three stateful ones, which
+// are wave 0's.  (The base env's ids are not here: its terms run in k_env_post_b_team.)
+#define POST_A_TERMS(X) \
+  X(GO2SIM_R_DOF_ACC) X(GO2SIM_R_FOOT_CLEARANCE) X(GO2SIM_R_TRACKING_LIN_VEL) X(GO2SIM_R_TRACKING_ANG_VEL) X(GO2SIM_R_BASE_HEIGHT) X(GO2SIM_R_ENERGY) \
+  X(GO2SIM_R_TORQUE_LOAD) X(GO2SIM_R_ACTION_RATE) X(GO2SIM_R_SIMILAR_TO_DEFAULT) X(GO2SIM_R_STAND_STILL) X(GO2SIM_R_JOINT_TRACKING) X(GO2SIM_R_DOF_VEL) \
+  X(GO2SIM_R_FOOT_SLIP) X(GO2SIM_R_STAND_STILL_VEL) X(GO2SIM_R_LIN_VEL_Z) X(GO2SIM_R_ORIENTATION_PENALTY) X(GO2SIM_R_ANG_VEL_XY) X(GO2SIM_R_ORIENTATION_ROLL_ONLY)
+// the stateful ones (deal_terms): wave 0 runs them in LIST order -- TermDeal::w0_ids, three rounds of a three-way test on the id, each arm again
+// reward_term with a constant id
+#define POST_A_STATEFUL(X) X(GO2SIM_R_FEET_AIR_TIME) X(GO2SIM_R_FEET_STANCE) X(GO2SIM_R_FORWARD_PROGRESS)
+// One word of every part of the kernel arguments that k_env_post_a reads LATE -- behind a wait, or at an index it has to load first: the constants of the
+// frame math and the termination test, of the terms (RewK), the id / scale lists of the loop, the deal.  The kernel's scalar loads reach its 3 KB of
+// arguments cache line by cache line, each batch of them behind a wait of its own; requested together at the top of the kernel, ahead of the first wait,
+// the lines are on their way in one trip, and the later loads find them in the scalar cache.  Measured (phase profile, mean cycles per
+// workgroup-launch): 29.5 k with this request, 31.7 k without.  (The value returned only keeps the loads alive.)
+DEV uint32_t post_a_touch(const DCfg& c, const TermDeal& deal) {
+  uint32_t x = 0;
+  auto fi = [&](int k) { x ^= (uint32_t)c.i[k]; };
+  auto ff = [&](int k) { x ^= __float_as_uint(c.f[k]); };
+  fi(GO2SIM_IC_RESAMPLE_STEPS); fi(GO2SIM_IC_MAX_EPISODE_LENGTH); fi(GO2SIM_IC_COMPOUND_COMMANDS); fi(GO2SIM_IC_N_STANDING); fi(GO2SIM_IC_NUM_ACTIONS); fi(GO2SIM_IC_USE_TERRAIN);
+  fi(GO2SIM_IC_REWARD_ID0); fi(GO2SIM_IC_REWARD_ID0 + 16); fi(GO2SIM_IC_REWARD_ID0 + NREW - 1);
+  ff(GO2SIM_FC_BASE_INIT_QUAT0); ff(GO2SIM_FC_BASE_INIT_QUAT0 + 3); ff(GO2SIM_FC_FOOT_CONTACT_THRESHOLD);
+  ff(GO2SIM_FC_TERM_PITCH_DEG); ff(GO2SIM_FC_TERM_ROLL_DEG); ff(GO2SIM_FC_TERM_ZVEL); ff(GO2SIM_FC_TERM_YVEL);
+  ff(GO2SIM_FC_DT); ff(GO2SIM_FC_TRACKING_SIGMA); ff(GO2SIM_FC_LIN_VEL_Z_DEADZONE); ff(GO2SIM_FC_BASE_HEIGHT_TARGET); ff(GO2SIM_FC_FEET_AIR_TIME_TARGET); ff(GO2SIM_FC_FEET_HEIGHT_TARGET);
+  ff(GO2SIM_FC_DEFAULT_DOF_POS0); ff(GO2SIM_FC_DEFAULT_DOF_POS0 + NM - 1);
+  ff(GO2SIM_FC_REWARD_SCALE0); ff(GO2SIM_FC_REWARD_SCALE0 + 16); ff(GO2SIM_FC_REWARD_SCALE0 + NREW - 1);
+  x ^= deal.w[0] ^ deal.straight ^ deal.w0_ids ^ (uint32_t)deal.mask[POST_A_NWAVES - 1] ^ deal.slot[0] ^ deal.slot[(GO2SIM_R_COUNT + 3) / 4 - 1];
+  x ^= __float_as_uint(deal.scale[0]) ^ __float_as_uint(deal.scale[16]) ^ __float_as_uint(deal.scale[GO2SIM_R_COUNT - 1]) ^ (uint32_t)deal.motor_dof[0] ^ (uint32_t)deal.motor_dof[NM - 1];
+  return x;
+}
 __global__ __launch_bounds__(WG * POST_A_NWAVES) void k_env_post_a(Pool P, const Model* __restrict__ mp, const DCfg cv, Glob* gp,
                                                    Acc* acc, uint64_t seed, uint32_t step_count, const TermDeal deal) {
   STAMP(STK_POST_A)
+  { const uint32_t touched = post_a_touch(cv, deal); asm volatile("" :: "s"(touched)); }
   __shared__ float s_es[NREW][WG], s_r[NREW][WG];
-  const int ln = threadIdx.x % WG, wv = threadIdx.x / WG;
+  const int ln = threadIdx.x % WG, wv = __builtin_amdgcn_readfirstlane(threadIdx.x / WG);   // (the wave index as a scalar: what depends on it branches, not masks)
   const bool w0 = wv == 0;                                          // the wave that owns the env's stores
   int b = blockIdx.x * WG + ln;
   if (b >= P.B) return;
@@ -5305,13 +5363,13 @@ __global__ __launch_bounds__(WG * POST_A_NWAVES) void k_env_post_a(Pool P, const
   V3 bp = e.l_pos()[bl]; Q4 bq = e.l_quat()[bl];
   V3 rcom = e.root_com()[bl];
   V3 cda = e.cd_ang()[bl], cdv = e.cd_vel()[bl];
-  V3 f_cf[4], f_lp[4], f_cdv[4], f_cda[4]; int fc_old[4];
+  V3 f_cf[4], f_lp[4], f_cdv[4], f_cda[4]; int fc_old[4] = {0, 0, 0, 0};
   {
     auto fc = e.foot_contact();
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       int l = c.i[GO2SIM_IC_FOOT_LINK0 + i];
-      fc_old[i] = fc[i];
+      if (w0) fc_old[i] = fc[i];
       f_cf[i] = e.contact_force()[l]; f_lp[i] = e.l_pos()[l]; f_cdv[i] = e.cd_vel()[l]; f_cda[i] = e.cd_ang()[l];
     }
   }
@@ -5323,15 +5381,37 @@ __global__ __launch_bounds__(WG * POST_A_NWAVES) void k_env_post_a(Pool P, const
   }
   if (!base_env) load_rew_state(c, e, rs);
   else { auto cmd = e.commands(); for (int i = 0; i < 3; ++i) rs.cmd[i] = cmd[i]; }
-  {
+  // what the terms read of the configuration, of the Model (the force ranges, by the host's motor dofs) and of the deal -- the wave's mask, and for every id
+  // of the straight-line section its scale and the word that holds its slot -- is requested here, with the state: no term waits on a scalar load of its own
+  // (POST_A_HOLD: the value is in a scalar register from here on -- without it the compiler moves the load to the first use, into the term)
+#define POST_A_HOLD(x) asm volatile("" : "+s"(x))
+  RewK K{};
+  uint64_t mine = 0;
+  float t_scale[GO2SIM_R_COUNT] = {}; uint32_t t_slot[(GO2SIM_R_COUNT + 3) / 4] = {};
+  if (!base_env) {
+    K = load_rew_k(m, c, deal.motor_dof);
+    POST_A_HOLD(K.dt); POST_A_HOLD(K.sigma); POST_A_HOLD(K.lin_vel_z_deadzone); POST_A_HOLD(K.base_height_target); POST_A_HOLD(K.feet_air_time_target);
+    POST_A_HOLD(K.feet_height_target); POST_A_HOLD(K.na); POST_A_HOLD(K.use_terrain);
+#pragma unroll
+    for (int i = 0; i < NM; ++i) { POST_A_HOLD(K.def[i]); POST_A_HOLD(K.force_lo[i]); POST_A_HOLD(K.force_hi[i]); }
+#pragma unroll
+    for (int v = 1; v < POST_A_NWAVES; ++v) if (wv == v) mine = deal.mask[v];
+    if (!deal.straight) mine = 0;
+#define X(ID) t_scale[ID] = deal.scale[ID]; POST_A_HOLD(t_scale[ID]); t_slot[(ID) >> 2] = deal.slot[(ID) >> 2];
+    POST_A_TERMS(X)
+    POST_A_STATEFUL(X)
+#undef X
+#pragma unroll
+    for (int j = 0; j < (GO2SIM_R_COUNT + 3) / 4; ++j) POST_A_HOLD(t_slot[j]);
+  }
+#undef POST_A_HOLD
+  if (w0) {
     auto episode_sums = e.episode_sums();
     float es_[NREW];
 #pragma unroll
     for (int k = 0; k < NREW; ++k) es_[k] = episode_sums[k];           // all NREW rows exist; unconditional loads stay in flight together
-    if (w0) {
 #pragma unroll
-      for (int k = 0; k < NREW; ++k) s_es[k][ln] = es_[k];
-    }
+    for (int k = 0; k < NREW; ++k) s_es[k][ln] = es_[k];
   }
   PH(12)
   // ---- stores start here (wave 0 only) ----
@@ -5342,8 +5422,14 @@ __global__ __launch_bounds__(WG * POST_A_NWAVES) void k_env_post_a(Pool P, const
     base_pos[0] = bp.x; base_pos[1] = bp.y; base_pos[2] = bp.z;
     base_quat[0] = bq.w; base_quat[1] = bq.x; base_quat[2] = bq.y; base_quat[3] = bq.z;
   }
-  Q4 inv_init = inv_quat(q4(c.f[GO2SIM_FC_BASE_INIT_QUAT0], c.f[GO2SIM_FC_BASE_INIT_QUAT0 + 1], c.f[GO2SIM_FC_BASE_INIT_QUAT0 + 2], c.f[GO2SIM_FC_BASE_INIT_QUAT0 + 3]));
-  V3 eul = tc_quat_to_xyz_rpy_deg(tc_quat_mul(bq, inv_init), m.eps);
+  // The split between wave 0 and the workers: A QUANTITY IS FORMED ON A WORKER WAVE ONLY IF A REWARD TERM READS IT.  That is blv, bav, pg, the base
+  // position, the foot velocities / positions / contacts and the command (on a resample step with its Philox draw: the terms read the new command).  The
+  // Euler angles (two atan2, one asin), the termination test, the time-out flag and every store are wave 0's alone: no term of any list reads them.
+  V3 eul = v3(0.0f, 0.0f, 0.0f);
+  if (w0) {
+    Q4 inv_init = inv_quat(q4(c.f[GO2SIM_FC_BASE_INIT_QUAT0], c.f[GO2SIM_FC_BASE_INIT_QUAT0 + 1], c.f[GO2SIM_FC_BASE_INIT_QUAT0 + 2], c.f[GO2SIM_FC_BASE_INIT_QUAT0 + 3]));
+    eul = tc_quat_to_xyz_rpy_deg(tc_quat_mul(bq, inv_init), m.eps);
+  }
   Q4 inv_bq = inv_quat(bq);
   V3 velw = cdv + cross(cda, bp - rcom);
   V3 blv = tc_transform_by_quat(velw, inv_bq), bav = tc_transform_by_quat(cda, inv_bq);
@@ -5383,30 +5469,52 @@ __global__ __launch_bounds__(WG * POST_A_NWAVES) void k_env_post_a(Pool P, const
     if (w0) { cmd[0] = cx; cmd[1] = cy; cmd[2] = cz; }
     rs.cmd[0] = cx; rs.cmd[1] = cy; rs.cmd[2] = cz;
   }
-  int maxlen = c.i[GO2SIM_IC_MAX_EPISODE_LENGTH];
-  int rst = ep_len > maxlen;
-  rst |= dm_abs(eul.y) > c.f[GO2SIM_FC_TERM_PITCH_DEG];
-  rst |= dm_abs(eul.x) > c.f[GO2SIM_FC_TERM_ROLL_DEG];
-  rst |= dm_abs(blv.z) > c.f[GO2SIM_FC_TERM_ZVEL];
-  rst |= dm_abs(blv.y) > c.f[GO2SIM_FC_TERM_YVEL];
-  float time_out = (ep_len > maxlen) ? 1.0f : 0.0f;
-  if (w0) { e.reset_buf()[0] = rst; e.time_out()[0] = time_out; }
+  int rst = 0;
+  float time_out = 0.0f;
+  if (w0) {
+    int maxlen = c.i[GO2SIM_IC_MAX_EPISODE_LENGTH];
+    rst = ep_len > maxlen;
+    rst |= dm_abs(eul.y) > c.f[GO2SIM_FC_TERM_PITCH_DEG];
+    rst |= dm_abs(eul.x) > c.f[GO2SIM_FC_TERM_ROLL_DEG];
+    rst |= dm_abs(blv.z) > c.f[GO2SIM_FC_TERM_ZVEL];
+    rst |= dm_abs(blv.y) > c.f[GO2SIM_FC_TERM_YVEL];
+    time_out = (ep_len > maxlen) ? 1.0f : 0.0f;
+    e.reset_buf()[0] = rst; e.time_out()[0] = time_out;
+  }
   float rew = 0.0f;
   float tracking_int = 0.0f;
   PH(13)
   const float fat0[4] = {rs.fat[0], rs.fat[1], rs.fat[2], rs.fat[3]};
   const float last_x0 = rs.last_x;
   const RewGates gates = reward_gates(rs);
-  if (!base_env) {                                                   // the terms, dealt to the waves (deal_terms): stateful ones on wave 0, in list order
-    const RewK K = load_rew_k(m, c);
+  PHA_BEGIN
+#define POST_A_TERM(ID) { s_r[(t_slot[(ID) >> 2] >> (((ID) & 3) * 8)) & (uint32_t)(NREW - 1)][ln] = reward_term(m, c, K, rs, ID, rc, gates) * t_scale[ID]; PHA(ID) }
+  if (!base_env && !w0 && deal.straight) {                           // a worker's terms, by id: straight-line code, one scalar bit test per id
+    PHA(PHA_REWK + wv)
+#define X(ID) if ((mine >> (ID)) & 1ull) POST_A_TERM(ID)
+    POST_A_TERMS(X)
+#undef X
+  } else if (!base_env && deal.straight) {                           // wave 0's stateful terms, by id as well, in list order
+    PHA(PHA_REWK + wv)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const uint32_t id = (deal.w0_ids >> (8 * r)) & 255u;
+#define X(ID) if (id == (uint32_t)(ID)) POST_A_TERM(ID)
+      POST_A_STATEFUL(X)
+#undef X
+    }
+  } else if (!base_env) {                                            // a list that is not one for the sections above (deal_terms): every wave loops over the list
+    PHA(PHA_REWK + wv)
     const uint32_t dw[NREW / 8] = {deal.w[0], deal.w[1], deal.w[2], deal.w[3]};
     for (int k = 0; k < nrew; ++k) {
       const uint32_t word = (k < 16) ? ((k < 8) ? dw[0] : dw[1]) : ((k < 24) ? dw[2] : dw[3]);
       if (wv != (int)((word >> ((k & 7) * 4)) & 15u)) continue;       // (a wave reads the table entries of its own terms only)
       s_r[k][ln] = reward_term(m, c, K, rs, c.i[GO2SIM_IC_REWARD_ID0 + k], rc, gates) * c.f[GO2SIM_FC_REWARD_SCALE0 + k];
+      PHA(c.i[GO2SIM_IC_REWARD_ID0 + k])
     }
   }
   __syncthreads();
+  PHA(PHA_WAIT + wv)
   PH(14)
   if (!w0) return;                                                   // the rest is wave 0's: the sum in the reference's order, the statistics, the stores
   for (int k = 0; k < nrew; ++k) {
@@ -6403,39 +6511,63 @@ static void add_launch(LaunchList& L, int cat, void (*kernel)(P...), dim3 grid, 
   L.v.push_back(std::move(e));
 }
 // ---- which wave of k_env_post_a runs which reward term -----------------------------------------------------------------------------------------
-// Vector instructions of a term as reward_term writes it (counted from the source: an IEEE division ~12, a square root ~10, dm_exp ~25, a height lookup on
-// the heightfield ~150; the twelve-motor loops 3-5 per motor).  Only the proportions matter, and only for speed: no result depends on the deal.  Estimates, not
-// measured cycles; a term added to reward_term needs its line here (an id without one is taken as a handful of operations).
+// What a term costs its wave, in cycles: measured per term on the GPU with the marks of a -DGO2SIM_PHASE_PROFILE build (tools/phase_profile.py 100 100 each,
+// 4096 envs, mean over the workgroups; profiles/r09_phase_profile_env.txt, "post_a term section").  Step 0 of round 9 measured the list loop this way:
+// there every term carried 400-600 cycles of the loop itself and the first term of a wave some 9 k more, so its figures say little about the terms.  The
+// table is therefore the same measurement on the by-id section that runs now (walk; the two terrain figures: stairs); tracking_lin_vel, the first term of
+// its wave in that run (1.65 k with the wave's first fetch), is set beside tracking_ang_vel.  Only the proportions matter, and only for speed: no result
+// depends on the deal.  A term added to reward_term needs its line here (an id without one is taken as a small term).
 static int reward_term_cost(int id, bool terrain) {
   switch (id) {
-    case GO2SIM_R_TRACKING_LIN_VEL: return 45;
-    case GO2SIM_R_TRACKING_ANG_VEL: return 40;
-    case GO2SIM_R_LIN_VEL_Z: return 6;
-    case GO2SIM_R_BASE_HEIGHT: return terrain ? 160 : 6;
-    case GO2SIM_R_ACTION_RATE: return 50;
-    case GO2SIM_R_SIMILAR_TO_DEFAULT: case GO2SIM_R_STAND_STILL: case GO2SIM_R_JOINT_TRACKING: return 40;
-    case GO2SIM_R_DOF_ACC: return 200;                               // twelve divisions
-    case GO2SIM_R_DOF_VEL: return 25;
-    case GO2SIM_R_FOOT_SLIP: return 25;
-    case GO2SIM_R_FOOT_CLEARANCE: return terrain ? 700 : 90;         // four square roots (+ four height lookups)
-    case GO2SIM_R_ENERGY: return 65;
-    case GO2SIM_R_TORQUE_LOAD: return 50;
-    case GO2SIM_R_STAND_STILL_VEL: return 10;
-    default: return 5;                                               // a handful of operations
+    case GO2SIM_R_TRACKING_LIN_VEL: return 600;
+    case GO2SIM_R_TRACKING_ANG_VEL: return 496;
+    case GO2SIM_R_LIN_VEL_Z: return 246;
+    case GO2SIM_R_BASE_HEIGHT: return terrain ? 1656 : 297;
+    case GO2SIM_R_ACTION_RATE: return 990;
+    case GO2SIM_R_SIMILAR_TO_DEFAULT: return 342;
+    case GO2SIM_R_ORIENTATION_PENALTY: return 241;
+    case GO2SIM_R_DOF_ACC: return 828;                               // twelve divisions
+    case GO2SIM_R_DOF_VEL: return 250;
+    case GO2SIM_R_ANG_VEL_XY: return 234;
+    case GO2SIM_R_FOOT_SLIP: return 278;
+    case GO2SIM_R_FOOT_CLEARANCE: return terrain ? 5293 : 2296;      // four square roots (+ four height lookups)
+    case GO2SIM_R_JOINT_TRACKING: return 734;
+    case GO2SIM_R_ENERGY: return 1060;
+    case GO2SIM_R_TORQUE_LOAD: return 1276;
+    case GO2SIM_R_STAND_STILL: return 306;
+    case GO2SIM_R_STAND_STILL_VEL: return 319;
+    case GO2SIM_R_ORIENTATION_ROLL_ONLY: return 414;
+    default: return 300;
   }
 }
 // Stateful terms (feet_air_time, feet_stance, forward_progress: they read or move env state that another of them reads) stay on wave 0, which runs its
 // terms in list order.  The others: heaviest first (ties: list order), each to the worker wave 1 .. POST_A_NWAVES - 1 with the least work so far (ties:
 // the lowest wave).  Every term computes the same value on any wave, and wave 0 adds them in list order: the deal does not enter a result.
+// The same deal in the form the straight-line section of k_env_post_a reads (per wave a mask over ids, id -> slot, the scales by id), and whether the list
+// is one for that section at all: every id at most once, and every id that is not wave 0's among POST_A_TERMS.  Otherwise the kernel takes the loop.
 static TermDeal deal_terms(const DCfg& c) {
-  TermDeal d = {{0, 0, 0, 0}, 0};
+  TermDeal d;
+  memset(&d, 0, sizeof(d));
   const int n = c.i[GO2SIM_IC_N_REWARDS] < NREW ? c.i[GO2SIM_IC_N_REWARDS] : NREW;
   const bool terrain = c.i[GO2SIM_IC_USE_TERRAIN] != 0;
   int order[NREW], cost[NREW], m = 0, load[POST_A_NWAVES] = {0};
+  uint64_t known = 0, seen = 0;
+#define X(ID) known |= 1ull << (ID);
+  POST_A_TERMS(X)
+#undef X
+  d.straight = 1;
+  d.w0_ids = 0xffffffffu;
+  int n_w0 = 0;
   for (int k = 0; k < n; ++k) {
     const int id = c.i[GO2SIM_IC_REWARD_ID0 + k];
+    const bool stateful = id == GO2SIM_R_FEET_AIR_TIME || id == GO2SIM_R_FEET_STANCE || id == GO2SIM_R_FORWARD_PROGRESS;
+    if (id < 0 || id >= GO2SIM_R_COUNT || ((seen >> id) & 1ull) || !(stateful || ((known >> id) & 1ull))) d.straight = 0;
+    else { seen |= 1ull << id; d.slot[id >> 2] |= (uint32_t)k << ((id & 3) * 8); d.scale[id] = c.f[GO2SIM_FC_REWARD_SCALE0 + k]; }
     if (id == GO2SIM_R_TRACKING_LIN_VEL || id == GO2SIM_R_TRACKING_ANG_VEL) d.tracking |= 1u << k;
-    if (id == GO2SIM_R_FEET_AIR_TIME || id == GO2SIM_R_FEET_STANCE || id == GO2SIM_R_FORWARD_PROGRESS) continue;   // owner 0
+    if (stateful) {                                                  // owner 0
+      if (n_w0 < 3) { d.w0_ids = (d.w0_ids & ~(255u << (8 * n_w0))) | ((uint32_t)id << (8 * n_w0)); ++n_w0; }   // (a fourth: an id twice, the loop)
+      continue;
+    }
     cost[k] = reward_term_cost(id, terrain);
     order[m++] = k;
   }
@@ -6445,7 +6577,10 @@ static TermDeal deal_terms(const DCfg& c) {
     for (int v = 2; v < POST_A_NWAVES; ++v) if (load[v] < load[w]) w = v;
     load[w] += cost[order[t]];
     d.w[order[t] >> 3] |= (uint32_t)w << ((order[t] & 7) * 4);
+    const int id = c.i[GO2SIM_IC_REWARD_ID0 + order[t]];
+    if (id >= 0 && id < GO2SIM_R_COUNT) d.mask[w] |= 1ull << id;
   }
+  for (int i = 0; i < NM; ++i) d.motor_dof[i] = c.i[GO2SIM_IC_MOTOR_DOF0 + i];
   return d;
 }
 struct StepIO { const float* actions; float *obs, *priv, *rew; uint8_t* reset; float* timeout; };   // what go2sim_env_step is handed per step

@@ -10,7 +10,7 @@ from go2_sim2real_locomotion_rl_amd.configs import build_stair_terrain, flatten_
 from go2_sim2real_locomotion_rl_amd.model_blob import pack_model
 
 from go2_sim2real_locomotion_rl_amd import build
-so = build.build_hip_variant("prof", ["-DGO2SIM_PHASE_PROFILE"], verbose=False)     # tools/lib_prof.so, rebuilt when the sources are newer
+so = os.environ.get("GO2SIM_PROFILE_LIB") or build.build_hip_variant("prof", ["-DGO2SIM_PHASE_PROFILE"], verbose=False)     # tools/lib_prof.so, rebuilt when the sources are newer (GO2SIM_PROFILE_LIB: a -DGO2SIM_PHASE_PROFILE library built elsewhere, e.g. of another commit)
 lib = capi.Go2SimLib(so, "go2sim_")
 B = 4096
 dev = torch.device("cuda", 0)
@@ -76,11 +76,13 @@ if len(sys.argv) > 3 and sys.argv[3] == "each":
     # one read-out per env step: what a single launch waits for is its slowest workgroup, which per-run sums average away
     rows = {g: [] for g in list(GROUPS_) + ["post_b"]}
     worst = {g: None for g in list(GROUPS_) + ["post_b"]}
+    terms = []                                                     # k_env_post_a's term section (PHA in csrc/go2sim.hip): one row of marks per workgroup, every wave its own ids
     for s in range(W, W + N):
         sim.env_step(act[s], obs, priv, rew, rst, to)
         lib.lib.go2sim_debug_phases(sim.h, out, 1)
         a = np.frombuffer(out, dtype=np.uint64).reshape(PH_MAX_WG, 64).astype(np.float64)
-        ab, a = a[PH_MAX_WG // 2:], a[:PH_MAX_WG // 2]
+        terms.append(a[PH_MAX_WG // 2 + PH_MAX_WG // 4:][: (B + 63) // 64].copy())
+        ab, a = a[PH_MAX_WG // 2: PH_MAX_WG // 2 + PH_MAX_WG // 4], a[:PH_MAX_WG // 2]
         tot = ab[:, POST_B].sum(1)
         if (tot > 0).any():
             srt = np.sort(tot[tot > 0])
@@ -102,6 +104,23 @@ if len(sys.argv) > 3 and sys.argv[3] == "each":
         r = np.array(r)
         print(f"== {g}: cycles per WG-launch over {N} single steps: mean {r[:, 0].mean():9.0f}  p99 {r[:, 1].mean():9.0f}  p99.9 {r[:, 2].mean():9.0f}  max (mean over steps) {r[:, 3].mean():9.0f}  max (worst step) {r[:, 3].max():9.0f}")
         print("   worst workgroup: " + "  ".join(f"ph{k}={v:.0f}" for k, v in worst[g][1].items() if v > 0) + ("  | counters (both launches) " + " ".join(f"{k}:{v:.0f}" for k, v in worst[g][2].items()) if g in ("solver", "collide") else ""))
+    t = np.array(terms)                                            # [step][workgroup][id]
+    if t.sum() > 0:
+        from go2_sim2real_locomotion_rl_amd.capi import C
+        rid = {v: k[len("GO2SIM_R_"):].lower() for k, v in C.items() if k.startswith("GO2SIM_R_") and k != "GO2SIM_R_COUNT"}
+        PHA_REWK, PHA_WAIT = 48, 56
+        print(f"== post_a term section: cycles per workgroup-launch over {N} single steps, per mark (each between two s_waitcnt(0): the terms of a wave do not overlap here): mean | slowest workgroup (mean over steps) | max")
+        for w in range(8):
+            if t[:, :, PHA_REWK + w].sum() > 0 or t[:, :, PHA_WAIT + w].sum() > 0:
+                x, y = t[:, :, PHA_REWK + w], t[:, :, PHA_WAIT + w]
+                print(f"   wave {w}: load_rew_k {x.mean():7.0f} | {x.max(1).mean():7.0f} | {x.max():7.0f}    wait at the barrier {y.mean():7.0f} | {y.max(1).mean():7.0f} | {y.max():7.0f}")
+        tot = 0.0
+        for k in sorted(rid):
+            x = t[:, :, k]
+            if x.sum() > 0:
+                tot += x.mean()
+                print(f"   term {k:2d} {rid[k]:22s} {x.mean():7.0f} | {x.max(1).mean():7.0f} | {x.max():7.0f}")
+        print(f"   all terms, sum of the means: {tot:7.0f}")
     raise SystemExit(0)
 for s in range(W, W + N):
     sim.env_step(act[s], obs, priv, rew, rst, to)
