@@ -138,17 +138,18 @@ class EnvGlobals(ctypes.Structure):
         return out
 
 
-def _ptr(x):
-    """Accept raw addresses (int), None, numpy arrays, torch tensors or ctypes objects."""
+def _ptr(x, strided=False):
+    """The one pointer helper of the package: None (NULL), a raw address (int), a numpy array, a torch tensor or a ctypes object -> what ctypes passes.
+    Arrays and tensors must be contiguous unless `strided`: then the caller hands the strides over next to the base address."""
     if x is None:
-        return None
+        return ctypes.c_void_p(0)
     if isinstance(x, int):
         return ctypes.c_void_p(x)
     if isinstance(x, np.ndarray):
-        assert x.flags["C_CONTIGUOUS"]
+        assert strided or x.flags["C_CONTIGUOUS"]
         return ctypes.c_void_p(x.ctypes.data)
     if hasattr(x, "data_ptr"):
-        assert x.is_contiguous()
+        assert strided or x.is_contiguous()
         return ctypes.c_void_p(x.data_ptr())
     return x
 
@@ -185,10 +186,30 @@ class Go2SimLib:
             raise Go2SimError(f"{self.prefix}{what} failed with status {rc}")
 
 
-class Go2Sim:
+class Handle:
+    """Owns one handle of a library: (lib, h, the name of the entry that destroys it).  A subclass calls Handle.__init__ before its create call and sets
+    `h` after it, so a refused create leaves nothing to release; close() may be called any number of times."""
+
+    def __init__(self, lib, destroy):
+        self._owner, self._destroy, self.h = lib, destroy, None
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._owner.fn(self._destroy)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Go2Sim(Handle):
     """One simulator handle (n_envs environments on one device)."""
 
     def __init__(self, lib: Go2SimLib, model_blob: bytes, n_envs: int, device: int = 0, seed: int = 1):
+        Handle.__init__(self, lib, "destroy")
         self.L = lib
         self.n_envs = n_envs
         self._blob = model_blob
@@ -197,17 +218,6 @@ class Go2Sim:
                               ctypes.c_uint64(seed), ctypes.byref(h))
         lib.check(rc, "create")
         self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fn("destroy")(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- scene level ---------------------------------------------------------------------------
     def _call(self, name, *args):

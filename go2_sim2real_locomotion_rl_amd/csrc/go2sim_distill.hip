@@ -5,11 +5,13 @@
 // student's mean.  A window of the update is walked in sub-batches of sub_rows rows; one sub-batch is, on the caller's stream and without atomics,
 //   k_train_forward     (go2sim_train_dev.h) the student's forward with the hidden activations kept, rows read through the window's index list
 //   k_distill_head      one row per lane: residual, rho into a float64 per-workgroup partial, rho' / (N A) into dZ [rows][Apad] with zero padding
-//   per layer, last to first: k_bwd_dw, k_bwd_db, k_bwd_da   (go2sim_train_dev.h, one network per launch)
+//   per layer, last to first: k_bwd_dw, k_bwd_db, k_bwd_da   (launch_backward of go2sim_trainer_host.h, one network per launch)
 //   k_reduce_partials   (one sub-batch) or k_distill_accumulate (several): the chunk slabs added in chunk order in float64; the second keeps the float64 sum
 //                       across sub-batches and rounds after the last one, which is the same sequence of additions as one pass over all chunks
 // and after the last sub-batch k_distill_finalize adds the head's partials of the whole window in workgroup order.  The optimizer is k_sumsq + k_adam of
-// the PPO update over the student's padded parameters alone (no critic, no std block).
+// the PPO update over the student's padded parameters alone (no critic, no std block).  The host code that drives all of this but the head -- the
+// optimizer state and its step, the packing, the workspace carving, the backward schedule -- is the PPO update's too (go2sim_trainer_host.h); the float64
+// sum across sub-batches and the head's partials sit in the optimizer state's tail.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -22,15 +24,14 @@
 #define GO2SIM_MLP_ACT_KERNELS
 #include "go2sim_mlp_dev.h"
 #include "go2sim_train_dev.h"
+#define GO2SIM_HIPCHK_TAG "go2sim_distill"
+#include "go2sim_trainer_host.h"
 #include "../../include/go2sim_distill.h"
 
-namespace {
+static_assert((int)GO2SIM_DISTILL_GRADS == (int)GO2SIM_PPO_GRADS && (int)GO2SIM_DISTILL_ADAM_M == (int)GO2SIM_PPO_ADAM_M && (int)GO2SIM_DISTILL_ADAM_V == (int)GO2SIM_PPO_ADAM_V,
+              "opt_vec serves both enums");
 
-#define HIPCHK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) { fprintf(stderr, "go2sim_distill: %s failed: %s\n", #x, hipGetErrorString(e_)); return GO2SIM_E_HIP; } \
-  } while (0)
+namespace {
 
 // the handle's scalar block has the layout k_adam knows (S_LR, S_NORM); the running sum of the pairs' losses takes a slot the PPO sums use there
 constexpr int D_SUM_LOSS = S_SUM_VL;
@@ -111,8 +112,6 @@ __global__ void k_distill_stats(const double* __restrict__ scal, double step, do
   out[GO2SIM_DISTILL_ST_STEP] = step; out[GO2SIM_DISTILL_ST_PAIRS] = pairs; out[GO2SIM_DISTILL_ST_WINDOWS] = windows;
 }
 
-struct DSeg { size_t pad_off; int ld, rows, cols; size_t flat_off; };
-
 }  // namespace
 
 struct go2sim_distill {
@@ -120,42 +119,21 @@ struct go2sim_distill {
   go2sim_distill_cfg_t cfg{};
   int A = 0, Apad = 0, max_rows = 0, sub = 0, ws_rows = 0;
   size_t nP = 0, n_flat = 0;   // padded / flat size of the student's parameters
-  float* fbuf = nullptr;      // grads | m | v
+  OptState opt;               // over nP floats; its tail: acc[nP] | head partials
   float* wbuf = nullptr;      // mu | activations | dz ping-pong | partial slabs, for ws_rows rows
-  float *grads = nullptr, *m = nullptr, *v = nullptr, *mu = nullptr, *partial = nullptr;
-  ActWs ws{};
-  float* dz[2] = {nullptr, nullptr};
-  double* dbuf = nullptr;     // scal[S_N] | sq_part[NORM_WG] | acc[nP] | head partials
-  double *scal = nullptr, *sq_part = nullptr, *acc = nullptr, *head_part = nullptr;
+  float *mu = nullptr, *partial = nullptr;
+  NetWs nw{};
+  double *acc = nullptr, *head_part = nullptr;
   int max_head_wg = 0;
-  long long step = 0, pairs = 0, windows = 0;
+  long long pairs = 0, windows = 0;
   int32_t* rows = nullptr;    // the row-index list of go2sim_distill_update, for (rows_T, rows_N, rows_E)
   int rows_T = 0, rows_N = 0, rows_E = 0;
-  std::vector<DSeg> segs;
+  std::vector<Seg> segs;
 };
 
 namespace {
 
-BwdLayer student_layer(const go2sim_distill* h, int lb, const float* obs) {
-  const go2sim_mlp* M = h->student;
-  BwdLayer L{};
-  const int l = M->n_layers - 1 - lb;                      // lb counts from the last layer
-  if (l < 0) return L;
-  L.active = 1;
-  L.N = M->dev.npad[l]; L.K = M->dev.kpad[l]; L.act = M->dev.act;
-  L.dz = h->dz[l & 1];
-  L.W = M->dev.W[l];
-  if (l == 0) { L.aprev = obs; L.lda = M->dims[0]; L.kmax = M->dims[0]; L.gather = 1; L.dzprev = nullptr; }
-  else { L.aprev = h->ws.a[l - 1]; L.lda = L.K; L.kmax = L.K; L.gather = 0; L.dzprev = h->dz[(l - 1) & 1]; }
-  L.w_off = (size_t)(M->dev.W[l] - M->dparams);
-  L.b_off = (size_t)(M->dev.b[l] - M->dparams);
-  return L;
-}
-
-float* vec_of(go2sim_distill* h, int which) {
-  return which == GO2SIM_DISTILL_PARAMS ? h->student->dparams : which == GO2SIM_DISTILL_GRADS ? h->grads : which == GO2SIM_DISTILL_ADAM_M ? h->m
-         : which == GO2SIM_DISTILL_ADAM_V ? h->v : nullptr;
-}
+float* vec_of(go2sim_distill* h, int which) { return which == GO2SIM_DISTILL_PARAMS ? h->student->dparams : opt_vec(h->opt, which); }
 
 // forward and head of rows idx[0 .. n), with `backward` the gradient as well; the running loss sum moves by the rows' sum of rho / (N A)
 int launch_window(go2sim_distill* h, const float* obs, const float* teacher, const int32_t* idx, int n, int n_envs, bool backward, hipStream_t st) {
@@ -163,30 +141,25 @@ int launch_window(go2sim_distill* h, const float* obs, const float* teacher, con
   const double w = 1.0 / ((double)n_envs * (double)h->A);
   const int nsub = (n + h->sub - 1) / h->sub;
   const size_t slab = h->nP;
-  const BwdLayer off_layer{};                              // the second network's slot of the shared kernels stays empty
   for (int s = 0; s < nsub; ++s) {
     const int off = s * h->sub, m = n - off < h->sub ? n - off : h->sub;
     const int32_t* ix = idx + off;
-    hipLaunchKernelGGL(k_train_forward<false>, dim3((m + TM - 1) / TM, 1), dim3(64 * NWAVE), 0, st, M->dev, obs, h->mu, h->ws, M->dev, obs, h->mu, h->ws, ix, m, m,
+    hipLaunchKernelGGL(k_train_forward<false>, dim3((m + TM - 1) / TM, 1), dim3(64 * NWAVE), 0, st, M->dev, obs, h->mu, h->nw.a, M->dev, obs, h->mu, h->nw.a, ix, m, m,
                        MirTab{nullptr, nullptr}, MirTab{nullptr, nullptr});
     DistillHeadArgs ha{};
-    ha.mu = h->mu; ha.teacher = teacher; ha.idx = ix; ha.dz = h->dz[(M->n_layers - 1) & 1]; ha.part = h->head_part + off / WGT;
+    ha.mu = h->mu; ha.teacher = teacher; ha.idx = ix; ha.dz = h->nw.dz[(M->n_layers - 1) & 1]; ha.part = h->head_part + off / WGT;
     ha.n = m; ha.A = h->A; ha.Apad = h->Apad; ha.huber = h->cfg.loss_type == GO2SIM_DISTILL_HUBER; ha.w = w;
     hipLaunchKernelGGL(k_distill_head, dim3((m + WGT - 1) / WGT), dim3(WGT), 0, st, ha);
     if (!backward) continue;
     const int n_chunks = (m + RCH - 1) / RCH;
-    for (int lb = 0; lb < M->n_layers; ++lb) {
-      const BwdLayer L = student_layer(h, lb, obs);
-      const int groups = ((L.N / 16 + DW_TN - 1) / DW_TN) * ((L.K / 16 + DW_TK - 1) / DW_TK);
-      hipLaunchKernelGGL(k_bwd_dw<false>, dim3(groups, n_chunks, 1), dim3(WGT), 0, st, L, off_layer, ix, m, m, h->partial, slab);
-      hipLaunchKernelGGL(k_bwd_db, dim3(L.N / 16, n_chunks, 1), dim3(WGT), 0, st, L, off_layer, m, h->partial, slab);
-      if (L.dzprev) hipLaunchKernelGGL(k_bwd_da<false>, dim3((m + TM - 1) / TM, 1), dim3(64 * NWAVE), 0, st, L, off_layer, m);
-    }
+    BwdLayer L[MAXL][2] = {};                              // the second network's slot of the shared kernels stays empty
+    for (int lb = 0; lb < M->n_layers; ++lb) L[lb][0] = bwd_layer(M, h->nw, lb, obs, 1, MirTab{nullptr, nullptr}, 0);
+    launch_backward<false, false>(L, M->n_layers, BwdRun{1, ix, m, m, h->partial, slab, st});
     const dim3 grid((unsigned)((slab + WGT - 1) / WGT));
-    if (nsub == 1) hipLaunchKernelGGL(k_reduce_partials, grid, dim3(WGT), 0, st, h->partial, n_chunks, slab, h->grads);
-    else hipLaunchKernelGGL(k_distill_accumulate, grid, dim3(WGT), 0, st, h->partial, n_chunks, slab, h->acc, s == 0 ? 1 : 0, s == nsub - 1 ? 1 : 0, h->grads);
+    if (nsub == 1) hipLaunchKernelGGL(k_reduce_partials, grid, dim3(WGT), 0, st, h->partial, n_chunks, slab, h->opt.grads);
+    else hipLaunchKernelGGL(k_distill_accumulate, grid, dim3(WGT), 0, st, h->partial, n_chunks, slab, h->acc, s == 0 ? 1 : 0, s == nsub - 1 ? 1 : 0, h->opt.grads);
   }
-  hipLaunchKernelGGL(k_distill_finalize, dim3(1), dim3(1), 0, st, h->head_part, (n + WGT - 1) / WGT, w, h->scal);
+  hipLaunchKernelGGL(k_distill_finalize, dim3(1), dim3(1), 0, st, h->head_part, (n + WGT - 1) / WGT, w, h->opt.scal);
   HIPCHK(hipGetLastError());
   h->pairs += n / n_envs;
   return GO2SIM_E_OK;
@@ -198,11 +171,8 @@ bool window_ok(const go2sim_distill* h, const float* obs, const float* teacher, 
 
 int pack_all(go2sim_distill* h, int which, int to_padded, float* flat, hipStream_t st) {
   if (!h || !flat || !vec_of(h, which)) return GO2SIM_E_BADARG;
-  float* base = vec_of(h, which);
-  for (const DSeg& s : h->segs)
-    hipLaunchKernelGGL(k_pack, dim3((s.rows * s.cols + WGT - 1) / WGT), dim3(WGT), 0, st, to_padded, base + s.pad_off, s.ld, flat + s.flat_off, s.rows, s.cols);
-  HIPCHK(hipGetLastError());
-  return GO2SIM_E_OK;
+  float* base[1] = {vec_of(h, which)};
+  return pack_segs(h->segs, base, to_padded, flat, st);
 }
 
 }  // namespace
@@ -234,50 +204,31 @@ int go2sim_distill_create(go2sim_mlp_t* student, int n_actions, const go2sim_dis
   h->sub = cfg->sub_rows ? cfg->sub_rows : GO2SIM_DISTILL_SUB_ROWS;
   h->ws_rows = max_window_rows < h->sub ? max_window_rows : h->sub;
   h->nP = M->padded;
-  size_t flat = 0;
-  for (int l = 0; l < M->n_layers; ++l) {
-    h->segs.push_back(DSeg{(size_t)(M->dev.W[l] - M->dparams), M->dev.kpad[l], M->dims[l + 1], M->dims[l], flat}); flat += (size_t)M->dims[l] * M->dims[l + 1];
-    h->segs.push_back(DSeg{(size_t)(M->dev.b[l] - M->dparams), M->dims[l + 1], 1, M->dims[l + 1], flat}); flat += M->dims[l + 1];
-  }
-  h->n_flat = flat;
-  auto al16 = [](size_t n) { return (n + 15) / 16 * 16; };   // every region starts 64-byte aligned (float4 loads)
+  mlp_segs(h->segs, 0, M, h->n_flat);
   const size_t R = (size_t)h->ws_rows;
-  int wmax = 16;
-  size_t need = al16(R * h->A);
-  for (int l = 0; l < M->n_layers; ++l) { if (l < M->n_layers - 1) need += R * M->dev.npad[l]; if (M->dev.npad[l] > wmax) wmax = M->dev.npad[l]; }
-  const size_t dz_sz = R * wmax;
   const int chunks = (int)((R + RCH - 1) / RCH);
-  need += 2 * dz_sz + (size_t)chunks * h->nP;
+  const size_t need = al16(R * h->A) + net_ws_floats(M, R) + (size_t)chunks * h->nP;
   h->max_head_wg = (max_window_rows + WGT - 1) / WGT;
-  const size_t nd = S_N + NORM_WG + h->nP + (size_t)h->max_head_wg;
-  if (hipMalloc((void**)&h->fbuf, 3 * h->nP * sizeof(float)) != hipSuccess || hipMalloc((void**)&h->wbuf, need * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&h->dbuf, nd * sizeof(double)) != hipSuccess) {
+  if (!opt_alloc(h->opt, h->nP, h->nP + (size_t)h->max_head_wg) || hipMalloc((void**)&h->wbuf, need * sizeof(float)) != hipSuccess) {
     go2sim_distill_destroy(h);
     return GO2SIM_E_NOMEM;
   }
-  if (hipMemset(h->fbuf, 0, 3 * h->nP * sizeof(float)) != hipSuccess || hipMemset(h->wbuf, 0, need * sizeof(float)) != hipSuccess ||
-      hipMemset(h->dbuf, 0, nd * sizeof(double)) != hipSuccess || hipMemcpy(h->dbuf + S_LR, &cfg->learning_rate, sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-      hipDeviceSynchronize() != hipSuccess) {
+  if (!opt_zero(h->opt, cfg->learning_rate, h->wbuf, need)) {
     fprintf(stderr, "go2sim_distill: initialising the trainer failed: %s\n", hipGetErrorString(hipGetLastError()));
     go2sim_distill_destroy(h);
     return GO2SIM_E_HIP;
   }
-  h->grads = h->fbuf; h->m = h->grads + h->nP; h->v = h->m + h->nP;
-  h->scal = h->dbuf; h->sq_part = h->scal + S_N; h->acc = h->sq_part + NORM_WG; h->head_part = h->acc + h->nP;
-  float* p = h->wbuf;
-  h->mu = p; p += al16(R * h->A);
-  for (int l = 0; l < M->n_layers - 1; ++l) { h->ws.a[l] = p; p += R * M->dev.npad[l]; }
-  h->dz[0] = p; p += dz_sz; h->dz[1] = p; p += dz_sz;
-  h->partial = p;
+  h->acc = h->opt.tail; h->head_part = h->acc + h->nP;
+  h->mu = h->wbuf;
+  h->partial = net_ws_carve(M, R, h->mu + al16(R * h->A), h->nw);
   *out = h;
   return GO2SIM_E_OK;
 }
 
 int go2sim_distill_destroy(go2sim_distill_t* h) {
   if (!h) return GO2SIM_E_BADARG;
-  if (h->fbuf) (void)hipFree(h->fbuf);
+  opt_free(h->opt);
   if (h->wbuf) (void)hipFree(h->wbuf);
-  if (h->dbuf) (void)hipFree(h->dbuf);
   if (h->rows) (void)hipFree(h->rows);
   delete h;
   return GO2SIM_E_OK;
@@ -295,19 +246,13 @@ int go2sim_distill_loss_only(go2sim_distill_t* h, const float* obs, const float*
 
 int go2sim_distill_apply(go2sim_distill_t* h, void* stream) {
   if (!h) return GO2SIM_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  const double t = (double)(h->step + 1);                  // the handle's count moves once the launches are accepted
   AdamArgs a{};
-  a.p_actor = h->student->dparams; a.g = h->grads; a.m = h->m; a.v = h->v;
-  a.nA = h->nP; a.nC = 0; a.n_tot = h->nP; a.A = 0; a.sq_part = h->sq_part; a.scal = h->scal;
+  a.p_actor = h->student->dparams; a.nA = h->nP;
   a.max_norm = h->cfg.max_grad_norm > 0.0 ? h->cfg.max_grad_norm : std::numeric_limits<double>::infinity();   // no clip: the coefficient is min(1, inf) = 1, exact
   a.b1 = h->cfg.beta1; a.b2 = h->cfg.beta2; a.eps = h->cfg.eps;
-  a.bc1 = 1.0 - std::pow(h->cfg.beta1, t); a.bc2_sqrt = std::sqrt(1.0 - std::pow(h->cfg.beta2, t));
-  hipLaunchKernelGGL(k_sumsq, dim3(NORM_WG), dim3(WGT), 0, st, h->grads, h->nP, h->sq_part);
-  hipLaunchKernelGGL(k_adam<false>, dim3((unsigned)((h->nP + WGT - 1) / WGT)), dim3(WGT), 0, st, a);
-  HIPCHK(hipGetLastError());
-  h->step += 1; h->windows += 1;
-  return GO2SIM_E_OK;
+  const int rc = opt_apply<false>(h->opt, a, (hipStream_t)stream);
+  if (rc == GO2SIM_E_OK) h->windows += 1;
+  return rc;
 }
 
 int go2sim_distill_update(go2sim_distill_t* h, const float* obs, const float* teacher_actions, int T, int N, int E, int G, void* stream) {
@@ -347,28 +292,24 @@ int go2sim_distill_n_padded(go2sim_distill_t* h, size_t* out) {
   return GO2SIM_E_OK;
 }
 int go2sim_distill_export_padded(go2sim_distill_t* h, int which, float* padded_dev, void* stream) {
-  if (!h || !padded_dev || !vec_of(h, which)) return GO2SIM_E_BADARG;
-  HIPCHK(hipMemcpyAsync(padded_dev, vec_of(h, which), h->nP * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return GO2SIM_E_OK;
+  if (!h) return GO2SIM_E_BADARG;
+  return opt_export_padded(h->opt, vec_of(h, which), padded_dev, (hipStream_t)stream);
 }
 
 int go2sim_distill_set_step(go2sim_distill_t* h, long long step, double learning_rate, void* stream) {
-  if (!h || step < 0 || !(learning_rate > 0.0)) return GO2SIM_E_BADARG;
-  h->step = step;
-  hipLaunchKernelGGL(k_set_lr, dim3(1), dim3(1), 0, (hipStream_t)stream, h->scal, learning_rate);
-  HIPCHK(hipGetLastError());
-  return GO2SIM_E_OK;
+  if (!h) return GO2SIM_E_BADARG;
+  return opt_set_step(h->opt, step, learning_rate, (hipStream_t)stream);
 }
 int go2sim_distill_reset_stats(go2sim_distill_t* h, void* stream) {
   if (!h) return GO2SIM_E_BADARG;
-  hipLaunchKernelGGL(k_distill_reset, dim3(1), dim3(1), 0, (hipStream_t)stream, h->scal);
+  hipLaunchKernelGGL(k_distill_reset, dim3(1), dim3(1), 0, (hipStream_t)stream, h->opt.scal);
   HIPCHK(hipGetLastError());
   h->pairs = 0; h->windows = 0;
   return GO2SIM_E_OK;
 }
 int go2sim_distill_stats(go2sim_distill_t* h, double* out_dev, void* stream) {
   if (!h || !out_dev) return GO2SIM_E_BADARG;
-  hipLaunchKernelGGL(k_distill_stats, dim3(1), dim3(1), 0, (hipStream_t)stream, h->scal, (double)h->step, (double)h->pairs, (double)h->windows, out_dev);
+  hipLaunchKernelGGL(k_distill_stats, dim3(1), dim3(1), 0, (hipStream_t)stream, h->opt.scal, (double)h->opt.step, (double)h->pairs, (double)h->windows, out_dev);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;
 }

@@ -46,17 +46,13 @@
 
 #include "go2sim_mlp_dev.h"
 #include "go2sim_train_dev.h"  // the kernels shared with go2sim_distill.hip: k_train_forward, k_bwd_dw / db / da, k_reduce_partials, k_sumsq, k_adam, k_pack
+#define GO2SIM_HIPCHK_TAG "go2sim_train"
+#include "go2sim_trainer_host.h"  // the host side shared with go2sim_distill.hip: HIPCHK, the optimizer state, packing, workspaces, the backward schedule
 #include "go2sim_lstm_dev.h"   // the memories of a recurrent policy: LstmDev, struct go2sim_lstm, k_lstm_cell, k_lstm_bptt
 #include "../../include/go2sim_train.h"
 #include "../../include/go2sim_rnn.h"
 
 namespace {
-
-#define HIPCHK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) { fprintf(stderr, "go2sim_train: %s failed: %s\n", #x, hipGetErrorString(e_)); return GO2SIM_E_HIP; } \
-  } while (0)
 
 struct HeadArgs {
   const float *mu, *val;                                  // [n][A], [n]: this mini-batch's forward
@@ -284,26 +280,21 @@ __global__ void k_stats(const double* __restrict__ scal, double step, double* __
   out[GO2SIM_PPO_ST_STEP] = step; out[GO2SIM_PPO_ST_COUNT] = scal[S_COUNT];
 }
 
-struct Seg { int base; size_t pad_off; int ld, rows, cols; size_t flat_off; };   // base 0 actor, 1 critic, 2 std, 3 memory_a, 4 memory_c
-
 }  // namespace
 
 struct go2sim_ppo {
   go2sim_mlp *actor = nullptr, *critic = nullptr;
   go2sim_ppo_cfg_t cfg{};
   int A = 0, Apad = 0, max_rows = 0, max_chunks = 0, max_head_wg = 0;
-  size_t nA = 0, nC = 0, n_tot = 0, n_flat = 0;
-  float* fbuf = nullptr;      // the optimizer's vectors: grads | m | v
-  float* wbuf = nullptr;      // the workspaces of ws_rows rows: mu | val | activations | dz ping-pong | partial slabs
-  float *grads = nullptr, *m = nullptr, *v = nullptr, *mu = nullptr, *val = nullptr, *partial = nullptr;
-  ActWs ws[2]{};
-  float* dz[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-  double* dbuf = nullptr;     // scal[S_N] | sq_part[NORM_WG]
+  size_t nA = 0, nC = 0, n_flat = 0;
+  OptState opt;               // the optimizer's vectors over slab + Apad floats, the scalars, the step count
+  float* wbuf = nullptr;      // the workspaces of ws_rows rows: mu | val | per network activations, dz ping-pong | partial slabs
+  float *mu = nullptr, *val = nullptr, *partial = nullptr;
+  NetWs nw[2]{};
   double* hbuf = nullptr;     // head partials, [workgroups of ws_rows][4 + A]
-  double *scal = nullptr, *sq_part = nullptr, *head_part = nullptr;
+  double* head_part = nullptr;
   size_t ws_rows = 0;         // max_rows, twice that once a mirror has been set
-  long long step = 0;
-  std::vector<Seg> segs;
+  std::vector<Seg> segs;      // base 0 actor, 1 critic, 2 std, 3 memory_a, 4 memory_c
   // mirror symmetry (go2sim_ppo_set_mirror): the tables live in one device allocation each, obs | critic obs | actions
   int mirror = 0, use_aug = 0, use_mloss = 0;
   double mirror_coeff = 0.0;
@@ -323,37 +314,12 @@ struct go2sim_ppo {
 
 namespace {
 BwdLayer bwd_layer(const go2sim_ppo* h, int net, int lb, const go2sim_ppo_batch_t* batch) {
-  const go2sim_mlp* M = net == 0 ? h->actor : h->critic;
-  BwdLayer L{};
-  const int l = M->n_layers - 1 - lb;                      // lb counts from the last layer
-  if (l < 0) return L;
-  L.active = 1;
-  L.N = M->dev.npad[l]; L.K = M->dev.kpad[l]; L.act = M->dev.act;
-  L.dz = h->dz[net][l & 1];
-  L.W = M->dev.W[l];
-  if (l == 0) {
-    L.aprev = net == 0 ? batch->obs : batch->critic_obs; L.lda = M->dims[0]; L.kmax = M->dims[0]; L.gather = 1; L.dzprev = nullptr;
-    L.mir = h->tab[net];
-  } else {
-    L.aprev = h->ws[net].a[l - 1]; L.lda = L.K; L.kmax = L.K; L.gather = 0; L.dzprev = h->dz[net][(l - 1) & 1];
-  }
-  L.w_off = (size_t)(M->dev.W[l] - M->dparams) + (net == 0 ? 0 : h->nA);
-  L.b_off = (size_t)(M->dev.b[l] - M->dparams) + (net == 0 ? 0 : h->nA);
-  return L;
+  return bwd_layer(net == 0 ? h->actor : h->critic, h->nw[net], lb, net == 0 ? batch->obs : batch->critic_obs, 1, h->tab[net], net == 0 ? 0 : h->nA);
 }
 // (re)allocates the row workspaces for R rows; the optimizer's vectors and the scalars are not touched.  hipFree waits for the device.
 int alloc_workspaces(go2sim_ppo* h, size_t R) {
   const go2sim_mlp* nets[2] = {h->actor, h->critic};
-  auto al16 = [](size_t n) { return (n + 15) / 16 * 16; };   // every region starts 64-byte aligned (float4 loads)
-  size_t need = al16(R * h->A) + al16(R);
-  size_t dz_sz[2] = {0, 0};
-  for (int net = 0; net < 2; ++net) {
-    const go2sim_mlp* M = nets[net];
-    int wmax = 16;
-    for (int l = 0; l < M->n_layers; ++l) { if (l < M->n_layers - 1) need += R * M->dev.npad[l]; if (M->dev.npad[l] > wmax) wmax = M->dev.npad[l]; }
-    dz_sz[net] = R * wmax;
-    need += 2 * dz_sz[net];
-  }
+  size_t need = al16(R * h->A) + al16(R) + net_ws_floats(nets[0], R) + net_ws_floats(nets[1], R);
   const int chunks = (int)((R + RCH - 1) / RCH), head_wg = (int)((R + WGT - 1) / WGT);
   const size_t slab = h->slab;
   need += (size_t)chunks * slab;
@@ -372,16 +338,9 @@ int alloc_workspaces(go2sim_ppo* h, size_t R) {
   h->wbuf = wb; h->hbuf = hb; h->head_part = hb; h->ws_rows = R; h->max_chunks = chunks; h->max_head_wg = head_wg;
   float* p = wb;
   h->mu = p; p += al16(R * h->A); h->val = p; p += al16(R);
-  for (int net = 0; net < 2; ++net) {
-    const go2sim_mlp* M = nets[net];
-    for (int l = 0; l < M->n_layers - 1; ++l) { h->ws[net].a[l] = p; p += R * M->dev.npad[l]; }
-    h->dz[net][0] = p; p += dz_sz[net]; h->dz[net][1] = p; p += dz_sz[net];
-  }
+  for (int net = 0; net < 2; ++net) p = net_ws_carve(nets[net], R, p, h->nw[net]);
   h->partial = p;
   return GO2SIM_E_OK;
-}
-float* vec_of(go2sim_ppo* h, int which) {
-  return which == GO2SIM_PPO_GRADS ? h->grads : which == GO2SIM_PPO_ADAM_M ? h->m : which == GO2SIM_PPO_ADAM_V ? h->v : nullptr;
 }
 int pack_all(go2sim_ppo* h, int which, int to_padded, float* flat, float* std_dev, hipStream_t st) {
   if (!h || !flat || which < GO2SIM_PPO_PARAMS || which > GO2SIM_PPO_ADAM_V) return GO2SIM_E_BADARG;
@@ -391,18 +350,14 @@ int pack_all(go2sim_ppo* h, int which, int to_padded, float* flat, float* std_de
     base[0] = h->actor->dparams; base[1] = h->critic->dparams; base[2] = std_dev;
     if (h->rnn) { base[3] = h->mem[0]->dparams; base[4] = h->mem[1]->dparams; }
   } else {
-    float* v = vec_of(h, which);
+    float* v = opt_vec(h->opt, which);
     base[0] = v; base[1] = v + h->nA; base[2] = v + h->slab; base[3] = v + h->nA + h->nC; base[4] = base[3] + h->nM[0];
   }
-  for (const Seg& s : h->segs)
-    hipLaunchKernelGGL(k_pack, dim3((s.rows * s.cols + WGT - 1) / WGT), dim3(WGT), 0, st, to_padded, base[s.base] + s.pad_off, s.ld, flat + s.flat_off, s.rows, s.cols);
-  HIPCHK(hipGetLastError());
-  return GO2SIM_E_OK;
+  return pack_segs(h->segs, base, to_padded, flat, st);
 }
 
 // the row workspaces of a recurrent handle: R = T x nb_max rows per memory
 int alloc_rnn_workspaces(go2sim_ppo* h) {
-  auto al16 = [](size_t n) { return (n + 15) / 16 * 16; };
   const size_t R = (size_t)h->T * h->nb_max;
   size_t need = 0;
   for (int net = 0; net < 2; ++net) {
@@ -425,16 +380,6 @@ int alloc_rnn_workspaces(go2sim_ppo* h) {
   return GO2SIM_E_OK;
 }
 
-// the segments of one memory in the flat (state-dict) order: weight_ih, weight_hh, bias_ih, bias_hh; a gate's block of H rows sits Hpad rows apart
-void lstm_segs(std::vector<Seg>& segs, int base, const go2sim_lstm* m, size_t& flat) {
-  const int H = m->H, I = m->I, Hp = m->dev.Hpad, Ip = m->dev.Ipad;
-  const size_t o_hh = (size_t)4 * Hp * Ip, o_bi = o_hh + (size_t)4 * Hp * Hp, o_bh = o_bi + (size_t)4 * Hp;
-  for (int q = 0; q < 4; ++q) { segs.push_back(Seg{base, (size_t)q * Hp * Ip, Ip, H, I, flat}); flat += (size_t)H * I; }
-  for (int q = 0; q < 4; ++q) { segs.push_back(Seg{base, o_hh + (size_t)q * Hp * Hp, Hp, H, H, flat}); flat += (size_t)H * H; }
-  for (int q = 0; q < 4; ++q) { segs.push_back(Seg{base, o_bi + (size_t)q * Hp, H, 1, H, flat}); flat += H; }
-  for (int q = 0; q < 4; ++q) { segs.push_back(Seg{base, o_bh + (size_t)q * Hp, H, 1, H, flat}); flat += H; }
-}
-
 // go2sim_ppo_create and go2sim_ppo_create_recurrent (ma, mc and n_steps set: max_rows = n_steps x the envs of a mini-batch)
 int create_impl(go2sim_mlp_t* actor, go2sim_mlp_t* critic, go2sim_lstm* ma, go2sim_lstm* mc, int n_steps, int n_actions, const go2sim_ppo_cfg_t* cfg, int max_rows,
                 go2sim_ppo_t** out) {
@@ -448,32 +393,22 @@ int create_impl(go2sim_mlp_t* actor, go2sim_mlp_t* critic, go2sim_lstm* ma, go2s
   h->nA = actor->padded; h->nC = critic->padded;
   if (ma) { h->rnn = 1; h->mem[0] = ma; h->mem[1] = mc; h->nM[0] = ma->padded; h->nM[1] = mc->padded; h->T = n_steps; h->nb_max = max_rows / n_steps; }
   h->slab = h->nA + h->nC + h->nM[0] + h->nM[1];
-  h->n_tot = h->slab + h->Apad;
-  // flat (state-dict) order: actor W0, b0, ..., critic W0, b0, ..., std
+  // flat (state-dict) order: actor W0, b0, ..., critic W0, b0, ..., (the memories,) std
   size_t flat = 0;
-  for (int net = 0; net < 2; ++net) {
-    const go2sim_mlp* M = net == 0 ? actor : critic;
-    for (int l = 0; l < M->n_layers; ++l) {
-      h->segs.push_back(Seg{net, (size_t)(M->dev.W[l] - M->dparams), M->dev.kpad[l], M->dims[l + 1], M->dims[l], flat}); flat += (size_t)M->dims[l] * M->dims[l + 1];
-      h->segs.push_back(Seg{net, (size_t)(M->dev.b[l] - M->dparams), M->dims[l + 1], 1, M->dims[l + 1], flat}); flat += M->dims[l + 1];
-    }
-  }
+  mlp_segs(h->segs, 0, actor, flat);
+  mlp_segs(h->segs, 1, critic, flat);
   if (h->rnn) { lstm_segs(h->segs, 3, ma, flat); lstm_segs(h->segs, 4, mc, flat); }
   h->segs.push_back(Seg{2, 0, n_actions, 1, n_actions, flat}); flat += n_actions;
   h->n_flat = flat;
-  const size_t nd = S_N + NORM_WG;
-  if (hipMalloc((void**)&h->fbuf, 3 * h->n_tot * sizeof(float)) != hipSuccess || hipMalloc((void**)&h->dbuf, nd * sizeof(double)) != hipSuccess) {
+  if (!opt_alloc(h->opt, h->slab + h->Apad, 0)) {
     go2sim_ppo_destroy(h);
     return GO2SIM_E_NOMEM;
   }
-  if (hipMemset(h->fbuf, 0, 3 * h->n_tot * sizeof(float)) != hipSuccess || hipMemset(h->dbuf, 0, nd * sizeof(double)) != hipSuccess ||
-      hipMemcpy(h->dbuf + S_LR, &cfg->learning_rate, sizeof(double), hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+  if (!opt_zero(h->opt, cfg->learning_rate, nullptr, 0)) {
     fprintf(stderr, "go2sim_train: initialising the optimizer state failed: %s\n", hipGetErrorString(hipGetLastError()));
     go2sim_ppo_destroy(h);
     return GO2SIM_E_HIP;
   }
-  h->grads = h->fbuf; h->m = h->grads + h->n_tot; h->v = h->m + h->n_tot;
-  h->scal = h->dbuf; h->sq_part = h->dbuf + S_N;
   int rc = alloc_workspaces(h, (size_t)max_rows);
   if (rc == GO2SIM_E_OK && h->rnn) rc = alloc_rnn_workspaces(h);
   if (rc != GO2SIM_E_OK) {
@@ -502,9 +437,8 @@ int go2sim_ppo_destroy(go2sim_ppo_t* h) {
   if (!h) return GO2SIM_E_BADARG;
   if (h->rbuf) (void)hipFree(h->rbuf);
   if (h->ibuf) (void)hipFree(h->ibuf);
-  if (h->fbuf) (void)hipFree(h->fbuf);
+  opt_free(h->opt);
   if (h->wbuf) (void)hipFree(h->wbuf);
-  if (h->dbuf) (void)hipFree(h->dbuf);
   if (h->hbuf) (void)hipFree(h->hbuf);
   if (h->mir_src) (void)hipFree(h->mir_src);
   if (h->mir_sign) (void)hipFree(h->mir_sign);
@@ -514,6 +448,16 @@ int go2sim_ppo_destroy(go2sim_ppo_t* h) {
 
 }  // extern "C"
 
+// the head's arguments for n rows of this mini-batch's forward (n_rows with their mirrors), a row weighing w; no mirror terms
+static HeadArgs head_args(const go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const float* std_dev, const int32_t* idx, int n, int n_rows, double w) {
+  HeadArgs ha{};
+  ha.mu = h->mu; ha.val = h->val; ha.b = *b; ha.std_ = std_dev; ha.idx = idx;
+  ha.dz_actor = h->nw[0].dz[(h->actor->n_layers - 1) & 1]; ha.dz_critic = h->nw[1].dz[(h->critic->n_layers - 1) & 1];
+  ha.part = h->head_part; ha.n = n; ha.A = h->A; ha.Apad = h->Apad; ha.use_clipped = h->cfg.use_clipped_value_loss;
+  ha.clip = h->cfg.clip_param; ha.vl_coef = h->cfg.value_loss_coef; ha.w = w; ha.n_rows = n_rows;
+  return ha;
+}
+
 // The launches of one mini-batch.  record == nullptr: the rows are the whole mini-batch (k_ppo_finalize, k_reduce_partials); otherwise they are a shard of it
 // and the sums stay in float64 in `record`.  w: 1 / (rows of the mini-batch over all shards).  With a mirror the forward and the head run over 2 n rows
 // (the mirror loss is always reported), the backward too unless both flags are off: then no mirrored row carries a gradient.
@@ -522,51 +466,27 @@ static int launch_grad_t(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const flo
   const go2sim_mlp *Ma = h->actor, *Mc = h->critic;
   const int n_fwd = MIR ? 2 * n : n, n_bwd = (MIR && (h->use_aug || h->use_mloss)) ? 2 * n : n;
   const int ncol = (MIR ? 4 : 3) + h->A;
-  hipLaunchKernelGGL(k_train_forward<MIR>, dim3((n_fwd + TM - 1) / TM, 2), dim3(64 * NWAVE), 0, st, Ma->dev, b->obs, h->mu, h->ws[0], Mc->dev, b->critic_obs, h->val,
-                     h->ws[1], idx, n_fwd, n, h->tab[0], h->tab[1]);
+  hipLaunchKernelGGL(k_train_forward<MIR>, dim3((n_fwd + TM - 1) / TM, 2), dim3(64 * NWAVE), 0, st, Ma->dev, b->obs, h->mu, h->nw[0].a, Mc->dev, b->critic_obs, h->val,
+                     h->nw[1].a, idx, n_fwd, n, h->tab[0], h->tab[1]);
   const int n_wg = (n_fwd + WGT - 1) / WGT;
-  HeadArgs ha{};
-  ha.mu = h->mu; ha.val = h->val; ha.b = *b; ha.std_ = std_dev; ha.idx = idx;
-  ha.dz_actor = h->dz[0][(Ma->n_layers - 1) & 1]; ha.dz_critic = h->dz[1][(Mc->n_layers - 1) & 1];
-  ha.part = h->head_part; ha.n = n; ha.A = h->A; ha.Apad = h->Apad; ha.use_clipped = h->cfg.use_clipped_value_loss;
-  ha.clip = h->cfg.clip_param; ha.vl_coef = h->cfg.value_loss_coef;
-  ha.w = (MIR && h->use_aug) ? 0.5 * w : w;                // 1 / (2 n): halving is exact
-  ha.n_rows = n_fwd; ha.ppo_on_mirrors = MIR && h->use_aug; ha.use_mirror_loss = MIR && h->use_mloss; ha.ta = h->tab[2];
+  HeadArgs ha = head_args(h, b, std_dev, idx, n, n_fwd, (MIR && h->use_aug) ? 0.5 * w : w);      // 1 / (2 n): halving is exact
+  ha.ppo_on_mirrors = MIR && h->use_aug; ha.use_mirror_loss = MIR && h->use_mloss; ha.ta = h->tab[2];
   ha.w_sym = h->mirror_coeff * 2.0 * w / (double)h->A;
   hipLaunchKernelGGL(k_ppo_head<MIR>, dim3(n_wg), dim3(WGT), 0, st, ha);
   if (!record)
-    hipLaunchKernelGGL(k_ppo_finalize, dim3(1), dim3(64), 0, st, h->head_part, n_wg, ncol, n, (MIR && h->use_aug) ? 2 * n : n, h->A, std_dev, h->scal,
-                       h->grads + h->slab, h->cfg.entropy_coef, h->cfg.desired_kl, h->cfg.lr_min, h->cfg.lr_max, h->cfg.adaptive);
+    hipLaunchKernelGGL(k_ppo_finalize, dim3(1), dim3(64), 0, st, h->head_part, n_wg, ncol, n, (MIR && h->use_aug) ? 2 * n : n, h->A, std_dev, h->opt.scal,
+                       h->opt.grads + h->slab, h->cfg.entropy_coef, h->cfg.desired_kl, h->cfg.lr_min, h->cfg.lr_max, h->cfg.adaptive);
   const int n_chunks = (n_bwd + RCH - 1) / RCH;
   const size_t slab = h->slab;
   const int depth = Ma->n_layers > Mc->n_layers ? Ma->n_layers : Mc->n_layers;
-  for (int lb = 0; lb < depth; ++lb) {
-    const BwdLayer L0 = bwd_layer(h, 0, lb, b), L1 = bwd_layer(h, 1, lb, b);
-    int groups = 1, nmax = 16, any_da = 0;
-    for (const BwdLayer* L : {&L0, &L1}) {
-      if (!L->active) continue;
-      const int g = ((L->N / 16 + DW_TN - 1) / DW_TN) * ((L->K / 16 + DW_TK - 1) / DW_TK);
-      if (g > groups) groups = g;
-      if (L->N > nmax) nmax = L->N;
-      if (L->dzprev) any_da = 1;
-    }
-    // only a launch that holds a first layer gathers: the others run the instantiation without the table code in their row loop
-    if (MIR && ((L0.active && L0.gather) || (L1.active && L1.gather)))
-      hipLaunchKernelGGL(k_bwd_dw<true>, dim3(groups, n_chunks, 2), dim3(WGT), 0, st, L0, L1, idx, n_bwd, n, h->partial, slab);
-    else
-      hipLaunchKernelGGL(k_bwd_dw<false>, dim3(groups, n_chunks, 2), dim3(WGT), 0, st, L0, L1, idx, n_bwd, n, h->partial, slab);
-    hipLaunchKernelGGL(k_bwd_db, dim3(nmax / 16, n_chunks, 2), dim3(WGT), 0, st, L0, L1, n_bwd, h->partial, slab);
-    if (any_da) {
-      BwdLayer D0 = L0, D1 = L1;                           // a network at its first layer has no dA to compute
-      if (!D0.dzprev) D0.active = 0;
-      if (!D1.dzprev) D1.active = 0;
-      hipLaunchKernelGGL(k_bwd_da<false>, dim3((n_bwd + TM - 1) / TM, 2), dim3(64 * NWAVE), 0, st, D0, D1, n_bwd);
-    }
-  }
+  BwdLayer L[MAXL][2];
+  for (int lb = 0; lb < depth; ++lb)
+    for (int net = 0; net < 2; ++net) L[lb][net] = bwd_layer(h, net, lb, b);
+  launch_backward<MIR, false>(L, depth, BwdRun{2, idx, n_bwd, n, h->partial, slab, st});
   if (!record)
-    hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((slab + WGT - 1) / WGT)), dim3(WGT), 0, st, h->partial, n_chunks, slab, h->grads);
+    hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((slab + WGT - 1) / WGT)), dim3(WGT), 0, st, h->partial, n_chunks, slab, h->opt.grads);
   else
-    hipLaunchKernelGGL(k_shard_record, dim3((unsigned)((h->n_tot + 5 + WGT - 1) / WGT)), dim3(WGT), 0, st, h->partial, n_chunks, slab, h->head_part, n_wg, ncol, h->A,
+    hipLaunchKernelGGL(k_shard_record, dim3((unsigned)((h->opt.n_tot + 5 + WGT - 1) / WGT)), dim3(WGT), 0, st, h->partial, n_chunks, slab, h->head_part, n_wg, ncol, h->A,
                        h->Apad, n, record);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;
@@ -588,7 +508,7 @@ int go2sim_ppo_minibatch_grad(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, cons
 
 int go2sim_ppo_shard_len(go2sim_ppo_t* h, size_t* out) {
   if (!h || !out) return GO2SIM_E_BADARG;
-  *out = h->n_tot + 4 + (h->mirror ? 1 : 0);
+  *out = h->opt.n_tot + 4 + (h->mirror ? 1 : 0);
   return GO2SIM_E_OK;
 }
 
@@ -601,11 +521,11 @@ int go2sim_ppo_shard_grad(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const fl
 int go2sim_ppo_shard_reduce(go2sim_ppo_t* h, const double* records, int n_records, const float* std_dev, void* stream) {
   if (!h || h->rnn || !records || !std_dev || n_records < 1) return GO2SIM_E_BADARG;
   hipStream_t st = (hipStream_t)stream;
-  const size_t slab = h->slab, len = h->n_tot + 4 + (h->mirror ? 1 : 0);
-  hipLaunchKernelGGL(k_shard_reduce, dim3((unsigned)((h->n_tot + WGT - 1) / WGT)), dim3(WGT), 0, st, records, n_records, len, slab, h->A, h->Apad, std_dev,
-                     h->cfg.entropy_coef, h->grads);
-  hipLaunchKernelGGL(k_shard_scalars, dim3(1), dim3(64), 0, st, records, n_records, len, h->n_tot, h->mirror ? 5 : 4, (h->mirror && h->use_aug) ? 2 : 1, h->A,
-                     std_dev, h->scal, h->cfg.desired_kl, h->cfg.lr_min, h->cfg.lr_max, h->cfg.adaptive);
+  const size_t slab = h->slab, len = h->opt.n_tot + 4 + (h->mirror ? 1 : 0);
+  hipLaunchKernelGGL(k_shard_reduce, dim3((unsigned)((h->opt.n_tot + WGT - 1) / WGT)), dim3(WGT), 0, st, records, n_records, len, slab, h->A, h->Apad, std_dev,
+                     h->cfg.entropy_coef, h->opt.grads);
+  hipLaunchKernelGGL(k_shard_scalars, dim3(1), dim3(64), 0, st, records, n_records, len, h->opt.n_tot, h->mirror ? 5 : 4, (h->mirror && h->use_aug) ? 2 : 1, h->A,
+                     std_dev, h->opt.scal, h->cfg.desired_kl, h->cfg.lr_min, h->cfg.lr_max, h->cfg.adaptive);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;
 }
@@ -660,30 +580,18 @@ int go2sim_ppo_set_mirror(go2sim_ppo_t* h, const go2sim_ppo_mirror_t* m, void* s
 
 int go2sim_ppo_symmetry_loss(go2sim_ppo_t* h, double* out_dev, void* stream) {
   if (!h || !out_dev) return GO2SIM_E_BADARG;
-  hipLaunchKernelGGL(k_sym_loss, dim3(1), dim3(1), 0, (hipStream_t)stream, h->scal, out_dev);
+  hipLaunchKernelGGL(k_sym_loss, dim3(1), dim3(1), 0, (hipStream_t)stream, h->opt.scal, out_dev);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;
 }
 
 int go2sim_ppo_apply(go2sim_ppo_t* h, float* std_dev, void* stream) {
   if (!h || !std_dev) return GO2SIM_E_BADARG;
-  hipStream_t st = (hipStream_t)stream;
-  const double t = (double)(h->step + 1);                  // the handle's count moves once the launches are accepted
   AdamArgs a{};
-  a.p_actor = h->actor->dparams; a.p_critic = h->critic->dparams; a.p_std = std_dev; a.g = h->grads; a.m = h->m; a.v = h->v;
-  a.nA = h->nA; a.nC = h->nC; a.n_tot = h->n_tot; a.A = h->A; a.sq_part = h->sq_part; a.scal = h->scal;
+  a.p_actor = h->actor->dparams; a.p_critic = h->critic->dparams; a.p_std = std_dev; a.nA = h->nA; a.nC = h->nC; a.A = h->A;
+  if (h->rnn) { a.p_ma = h->mem[0]->dparams; a.p_mc = h->mem[1]->dparams; a.nMa = h->nM[0]; a.nMc = h->nM[1]; }
   a.max_norm = h->cfg.max_grad_norm; a.b1 = h->cfg.beta1; a.b2 = h->cfg.beta2; a.eps = h->cfg.eps;
-  a.bc1 = 1.0 - std::pow(h->cfg.beta1, t); a.bc2_sqrt = std::sqrt(1.0 - std::pow(h->cfg.beta2, t));
-  hipLaunchKernelGGL(k_sumsq, dim3(NORM_WG), dim3(WGT), 0, st, h->grads, h->n_tot, h->sq_part);
-  if (h->rnn) {
-    a.p_ma = h->mem[0]->dparams; a.p_mc = h->mem[1]->dparams; a.nMa = h->nM[0]; a.nMc = h->nM[1];
-    hipLaunchKernelGGL(k_adam<true>, dim3((unsigned)((h->n_tot + WGT - 1) / WGT)), dim3(WGT), 0, st, a);
-  } else {
-    hipLaunchKernelGGL(k_adam<false>, dim3((unsigned)((h->n_tot + WGT - 1) / WGT)), dim3(WGT), 0, st, a);
-  }
-  HIPCHK(hipGetLastError());
-  h->step += 1;
-  return GO2SIM_E_OK;
+  return h->rnn ? opt_apply<true>(h->opt, a, (hipStream_t)stream) : opt_apply<false>(h->opt, a, (hipStream_t)stream);
 }
 
 int go2sim_ppo_update(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, float* std_dev, const int32_t* perm, int n_rows_total, int n_epochs, int n_mini_batches, void* stream) {
@@ -712,31 +620,27 @@ int go2sim_ppo_import(go2sim_ppo_t* h, int which, const float* flat_dev, float* 
 }
 int go2sim_ppo_n_padded(go2sim_ppo_t* h, size_t* out) {
   if (!h || !out) return GO2SIM_E_BADARG;
-  *out = h->n_tot;
+  *out = h->opt.n_tot;
   return GO2SIM_E_OK;
 }
 int go2sim_ppo_export_padded(go2sim_ppo_t* h, int which, float* padded_dev, void* stream) {
-  if (!h || !padded_dev || !vec_of(h, which)) return GO2SIM_E_BADARG;
-  HIPCHK(hipMemcpyAsync(padded_dev, vec_of(h, which), h->n_tot * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return GO2SIM_E_OK;
+  if (!h) return GO2SIM_E_BADARG;
+  return opt_export_padded(h->opt, opt_vec(h->opt, which), padded_dev, (hipStream_t)stream);
 }
 
 int go2sim_ppo_set_step(go2sim_ppo_t* h, long long step, double learning_rate, void* stream) {
-  if (!h || step < 0 || !(learning_rate > 0.0)) return GO2SIM_E_BADARG;
-  h->step = step;
-  hipLaunchKernelGGL(k_set_lr, dim3(1), dim3(1), 0, (hipStream_t)stream, h->scal, learning_rate);
-  HIPCHK(hipGetLastError());
-  return GO2SIM_E_OK;
+  if (!h) return GO2SIM_E_BADARG;
+  return opt_set_step(h->opt, step, learning_rate, (hipStream_t)stream);
 }
 int go2sim_ppo_reset_stats(go2sim_ppo_t* h, void* stream) {
   if (!h) return GO2SIM_E_BADARG;
-  hipLaunchKernelGGL(k_reset_stats, dim3(1), dim3(1), 0, (hipStream_t)stream, h->scal);
+  hipLaunchKernelGGL(k_reset_stats, dim3(1), dim3(1), 0, (hipStream_t)stream, h->opt.scal);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;
 }
 int go2sim_ppo_stats(go2sim_ppo_t* h, double* out_dev, void* stream) {
   if (!h || !out_dev) return GO2SIM_E_BADARG;
-  hipLaunchKernelGGL(k_stats, dim3(1), dim3(1), 0, (hipStream_t)stream, h->scal, (double)h->step, out_dev);
+  hipLaunchKernelGGL(k_stats, dim3(1), dim3(1), 0, (hipStream_t)stream, h->opt.scal, (double)h->opt.step, out_dev);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;
 }
@@ -788,42 +692,26 @@ int launch_grad_rnn(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const go2sim_p
     hipLaunchKernelGGL(k_lstm_cell<true>, dim3((nb + TM - 1) / TM, wmax, 2), dim3(64 * NWAVE), 0, st, c[0], c[1],
                        t == 0 ? (const uint8_t*)nullptr : s->dones + (size_t)(t - 1) * B + e0, nb);
   }
-  hipLaunchKernelGGL(k_train_forward<false>, dim3((n + TM - 1) / TM, 2), dim3(64 * NWAVE), 0, st, Ma->dev, h->r_hout[0], h->mu, h->ws[0], Mc->dev, h->r_hout[1], h->val,
-                     h->ws[1], h->idx_id, n, n, h->tab[0], h->tab[1]);
+  hipLaunchKernelGGL(k_train_forward<false>, dim3((n + TM - 1) / TM, 2), dim3(64 * NWAVE), 0, st, Ma->dev, h->r_hout[0], h->mu, h->nw[0].a, Mc->dev, h->r_hout[1], h->val,
+                     h->nw[1].a, h->idx_id, n, n, h->tab[0], h->tab[1]);
   const int n_wg = (n + WGT - 1) / WGT, ncol = 3 + h->A;
-  HeadArgs ha{};
-  ha.mu = h->mu; ha.val = h->val; ha.b = *b; ha.std_ = std_dev; ha.idx = h->idx_b;
-  ha.dz_actor = h->dz[0][(Ma->n_layers - 1) & 1]; ha.dz_critic = h->dz[1][(Mc->n_layers - 1) & 1];
-  ha.part = h->head_part; ha.n = n; ha.A = h->A; ha.Apad = h->Apad; ha.use_clipped = h->cfg.use_clipped_value_loss;
-  ha.clip = h->cfg.clip_param; ha.vl_coef = h->cfg.value_loss_coef; ha.w = 1.0 / (double)n; ha.n_rows = n;
+  const HeadArgs ha = head_args(h, b, std_dev, h->idx_b, n, n, 1.0 / (double)n);
   hipLaunchKernelGGL(k_ppo_head<false>, dim3(n_wg), dim3(WGT), 0, st, ha);
-  hipLaunchKernelGGL(k_ppo_finalize, dim3(1), dim3(64), 0, st, h->head_part, n_wg, ncol, n, n, h->A, std_dev, h->scal, h->grads + h->slab, h->cfg.entropy_coef,
+  hipLaunchKernelGGL(k_ppo_finalize, dim3(1), dim3(64), 0, st, h->head_part, n_wg, ncol, n, n, h->A, std_dev, h->opt.scal, h->opt.grads + h->slab, h->cfg.entropy_coef,
                      h->cfg.desired_kl, h->cfg.lr_min, h->cfg.lr_max, h->cfg.adaptive);
   const int n_chunks = (n + RCH - 1) / RCH;
   const size_t slab = h->slab;
-  auto launch_dw_db = [&](const BwdLayer& L0, const BwdLayer& L1, const int32_t* idx) {
-    int groups = 1, nmax = 16;
-    for (const BwdLayer* L : {&L0, &L1}) {
-      if (!L->active) continue;
-      const int g = ((L->N / 16 + DW_TN - 1) / DW_TN) * ((L->K / 16 + DW_TK - 1) / DW_TK);
-      if (g > groups) groups = g;
-      if (L->N > nmax) nmax = L->N;
-    }
-    hipLaunchKernelGGL(k_bwd_dw<false>, dim3(groups, n_chunks, 2), dim3(WGT), 0, st, L0, L1, idx, n, n, h->partial, slab);
-    hipLaunchKernelGGL(k_bwd_db, dim3(nmax / 16, n_chunks, 2), dim3(WGT), 0, st, L0, L1, n, h->partial, slab);
-  };
   const int depth = Ma->n_layers > Mc->n_layers ? Ma->n_layers : Mc->n_layers;
-  for (int lb = 0; lb < depth; ++lb) {
-    BwdLayer L[2] = {bwd_layer(h, 0, lb, b), bwd_layer(h, 1, lb, b)};
+  BwdLayer L[MAXL][2];
+  for (int lb = 0; lb < depth; ++lb)
     for (int net = 0; net < 2; ++net) {
-      const go2sim_mlp* M = net == 0 ? Ma : Mc;
-      if (!L[net].active || M->n_layers - 1 - lb != 0) continue;
+      BwdLayer& Q = L[lb][net];
+      Q = bwd_layer(h, net, lb, b);
+      if (!Q.active || (net == 0 ? Ma : Mc)->n_layers - 1 - lb != 0) continue;
       // the first layer reads the memory's h' [n][H] and hands d loss / d h' back
-      L[net].aprev = h->r_hout[net]; L[net].lda = M->dims[0]; L[net].kmax = M->dims[0]; L[net].gather = 0; L[net].dzprev = h->r_dh[net]; L[net].lin = 1;
+      Q.aprev = h->r_hout[net]; Q.gather = 0; Q.dzprev = h->r_dh[net]; Q.lin = 1;
     }
-    launch_dw_db(L[0], L[1], h->idx_id);
-    hipLaunchKernelGGL(k_bwd_da<true>, dim3((n + TM - 1) / TM, 2), dim3(64 * NWAVE), 0, st, L[0], L[1], n);
-  }
+  launch_backward<false, true>(L, depth, BwdRun{2, h->idx_id, n, n, h->partial, slab, st});
   for (int t = T - 1; t >= 0; --t) {
     BpttNet c[2];
     for (int net = 0; net < 2; ++net) {
@@ -848,9 +736,9 @@ int launch_grad_rnn(go2sim_ppo_t* h, const go2sim_ppo_batch_t* b, const go2sim_p
       if (part == 0) { Q.aprev = x[net]; Q.K = Ip; Q.lda = m->I; Q.kmax = m->I; Q.gather = 1; Q.W = m->dev.Wih; Q.w_off = off; Q.b_off = off + o_bi; }
       else { Q.aprev = h->r_hprev[net]; Q.K = Hp; Q.lda = m->H; Q.kmax = m->H; Q.gather = 0; Q.W = m->dev.Whh; Q.w_off = off + o_hh; Q.b_off = off + o_bi + (size_t)4 * Hp; }
     }
-    launch_dw_db(L[0], L[1], h->idx_b);
+    launch_dw_db<false>(L[0], L[1], BwdRun{2, h->idx_b, n, n, h->partial, slab, st});
   }
-  hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((slab + WGT - 1) / WGT)), dim3(WGT), 0, st, h->partial, n_chunks, slab, h->grads);
+  hipLaunchKernelGGL(k_reduce_partials, dim3((unsigned)((slab + WGT - 1) / WGT)), dim3(WGT), 0, st, h->partial, n_chunks, slab, h->opt.grads);
   HIPCHK(hipGetLastError());
   return GO2SIM_E_OK;
 }

@@ -19,15 +19,12 @@ import ctypes
 
 import torch
 
-from .capi import C, DistillCfg, Go2SimError, load_hip_lib
+from .capi import C, DistillCfg, Go2SimError, _ptr, load_hip_lib
 from .distributed import is_multi
-from .policy import Mlp, _ptr, flatten_sequential, policy_act, resolve_activation
+from .policy import Mlp, flatten_sequential, policy_act, resolve_activation
+from .trainer import OptimizerState, TrainerHandle, mlp_keys, unflatten_keys
 
 LOSS_TYPES = ("mse", "huber")
-
-
-def _p(t):
-    return ctypes.c_void_p(0) if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 # ---- pure functions (no GPU) ---------------------------------------------------------------------------------------------------------------------
@@ -46,14 +43,6 @@ def distill_windows(T, E, G):
                 windows.append(cur)
                 cur = []
     return windows, cur
-
-
-def mlp_keys(prefix, dims):
-    """[(key, shape)] of one network in state-dict (and flat) order"""
-    keys = []
-    for l in range(len(dims) - 1):
-        keys += [(f"{prefix}.{2 * l}.weight", (dims[l + 1], dims[l])), (f"{prefix}.{2 * l}.bias", (dims[l + 1],))]
-    return keys
 
 
 def _check_shapes(sd, prefix, dims, what):
@@ -100,96 +89,46 @@ def teacher_state_from_checkpoint(state_dict, student_dims=None, teacher_dims=No
 
 
 def unflatten_student(flat, dims):
-    out, o = {}, 0
-    for k, shape in mlp_keys("student", dims):
-        n = 1
-        for s in shape:
-            n *= s
-        out[k] = flat[o:o + n].reshape(shape).clone()
-        o += n
-    return out
+    return unflatten_keys(flat, mlp_keys("student", dims))
 
 
 # ---- the trainer handle --------------------------------------------------------------------------------------------------------------------------
-class DistillHandle:
+class DistillHandle(TrainerHandle):
     """One go2sim_distill handle: pointers only.  `student` is a policy.Mlp of the product library."""
 
     def __init__(self, lib, student, n_actions, max_window_rows, *, learning_rate=1e-3, max_grad_norm=None, loss_type="mse", betas=(0.9, 0.999), eps=1e-8, sub_rows=0,
                  device=None):
         if loss_type not in LOSS_TYPES:
             raise Go2SimError(f"loss_type must be one of {LOSS_TYPES}, got {loss_type!r}")
-        self.L, self.student = lib, student
-        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        TrainerHandle.__init__(self, lib, "distill", device)
+        self.student = student
         cfg = DistillCfg(float(learning_rate), float(max_grad_norm) if max_grad_norm is not None else 0.0, betas[0], betas[1], eps,
                          C["GO2SIM_DISTILL_" + loss_type.upper()], int(sub_rows))
         h = ctypes.c_void_p()
-        self.h = None
         lib.check(lib.fn("distill_create")(student.h, ctypes.c_int(n_actions), ctypes.byref(cfg), ctypes.c_int(int(max_window_rows)), ctypes.byref(h)), "distill_create")
-        self.h = h
-        n = ctypes.c_size_t()
-        lib.check(lib.fn("distill_n_params")(self.h, ctypes.byref(n)), "distill_n_params")
-        self.n_params = n.value
-        lib.check(lib.fn("distill_n_padded")(self.h, ctypes.byref(n)), "distill_n_padded")
-        self.n_padded = n.value
-        self._stats = torch.zeros(C["GO2SIM_DISTILL_N_STATS"], dtype=torch.float64, device=self.device)
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._created(h)
 
     def window_grad(self, obs, teacher_actions, idx, n_envs, n_rows=None):
         n = idx.numel() if n_rows is None else n_rows
-        self.L.check(self.L.fn("distill_window_grad")(self.h, _p(obs), _p(teacher_actions), _p(idx), ctypes.c_int(n), ctypes.c_int(n_envs), self._stream()), "distill_window_grad")
+        self._call("window_grad", _ptr(obs), _ptr(teacher_actions), _ptr(idx), ctypes.c_int(n), ctypes.c_int(n_envs))
 
     def loss_only(self, obs, teacher_actions, idx, n_envs, n_rows=None):
         n = idx.numel() if n_rows is None else n_rows
-        self.L.check(self.L.fn("distill_loss_only")(self.h, _p(obs), _p(teacher_actions), _p(idx), ctypes.c_int(n), ctypes.c_int(n_envs), self._stream()), "distill_loss_only")
+        self._call("loss_only", _ptr(obs), _ptr(teacher_actions), _ptr(idx), ctypes.c_int(n), ctypes.c_int(n_envs))
 
     def apply(self):
-        self.L.check(self.L.fn("distill_apply")(self.h, self._stream()), "distill_apply")
+        self._call("apply")
 
     def update(self, obs, teacher_actions, n_steps, n_envs, n_epochs, gradient_length):
-        self.L.check(self.L.fn("distill_update")(self.h, _p(obs), _p(teacher_actions), ctypes.c_int(n_steps), ctypes.c_int(n_envs), ctypes.c_int(n_epochs),
-                                                 ctypes.c_int(gradient_length), self._stream()), "distill_update")
+        self._call("update", _ptr(obs), _ptr(teacher_actions), ctypes.c_int(n_steps), ctypes.c_int(n_envs), ctypes.c_int(n_epochs), ctypes.c_int(gradient_length))
 
     def export(self, which):
         """flat float32 device vector in state-dict order: student W0, b0, W1, b1, ..."""
-        out = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-        self.L.check(self.L.fn("distill_export")(self.h, ctypes.c_int(C["GO2SIM_DISTILL_" + which]), _p(out), self._stream()), "distill_export")
-        return out
-
-    def import_(self, which, flat):
-        flat = flat.to(device=self.device, dtype=torch.float32).contiguous()
-        if flat.numel() != self.n_params:
-            raise Go2SimError(f"flat vector has {flat.numel()} entries, expected {self.n_params}")
-        self.L.check(self.L.fn("distill_import")(self.h, ctypes.c_int(C["GO2SIM_DISTILL_" + which]), _p(flat), self._stream()), "distill_import")
-        torch.cuda.current_stream(self.device).synchronize()          # `flat` may be a temporary
-
-    def export_padded(self, which):
-        out = torch.empty(self.n_padded, dtype=torch.float32, device=self.device)
-        self.L.check(self.L.fn("distill_export_padded")(self.h, ctypes.c_int(C["GO2SIM_DISTILL_" + which]), _p(out), self._stream()), "distill_export_padded")
-        return out
-
-    def set_step(self, step, learning_rate):
-        self.L.check(self.L.fn("distill_set_step")(self.h, ctypes.c_longlong(int(step)), ctypes.c_double(float(learning_rate)), self._stream()), "distill_set_step")
-
-    def reset_stats(self):
-        self.L.check(self.L.fn("distill_reset_stats")(self.h, self._stream()), "distill_reset_stats")
+        return TrainerHandle.export(self, which)
 
     def stats(self):
         """float64 device tensor [mean behaviour loss, learning rate, grad norm, step, pairs, windows]; no synchronisation"""
-        self.L.check(self.L.fn("distill_stats")(self.h, _p(self._stats), self._stream()), "distill_stats")
-        return self._stats
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fn("distill_destroy")(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return TrainerHandle.stats(self)
 
 
 def distill_act(lib, student, teacher, obs, teacher_obs, std, n_rows, seed, step, deterministic, actions, mean, teacher_actions, stream=0):
@@ -339,7 +278,7 @@ class StudentTeacher:
 
 
 # ---- the algorithm ---------------------------------------------------------------------------------------------------------------------------------
-class Distillation:
+class Distillation(OptimizerState):
     """rsl_rl's Distillation on a StudentTeacher.  The activation is the policy's (``train_cfg["policy"]["activation"]``, one name for student and teacher):
     as in rsl_rl it lives in the config (``cfgs.pkl``), not in ``model_<it>.pt``, so a teacher checkpoint is interpreted with the student config's
     activation -- a teacher trained with another one loads without complaint and computes something else."""
@@ -388,14 +327,3 @@ class Distillation:
         self.last_stats = s
         self.t = 0
         return float(s[C["GO2SIM_DISTILL_ST_LOSS"]])
-
-    # ---- optimizer state (runner checkpoints) ----------------------------------------------------------
-    def optimizer_state_dict(self):
-        s = self._h.stats().cpu()
-        return {"exp_avg": self._h.export("ADAM_M").cpu(), "exp_avg_sq": self._h.export("ADAM_V").cpu(), "step": int(s[C["GO2SIM_DISTILL_ST_STEP"]]),
-                "lr": float(s[C["GO2SIM_DISTILL_ST_LR"]])}
-
-    def load_optimizer_state_dict(self, sd):
-        self._h.import_("ADAM_M", sd["exp_avg"]); self._h.import_("ADAM_V", sd["exp_avg_sq"])
-        self._h.set_step(int(sd["step"]), float(sd["lr"]))
-        self.learning_rate = float(sd["lr"])

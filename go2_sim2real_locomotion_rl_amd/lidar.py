@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 import torch
 
-from .capi import C, Go2SimError, load_hip_lib
+from .capi import C, Go2SimError, Handle, _ptr, load_hip_lib
 
 
 class LidarCfg(ctypes.Structure):
@@ -82,11 +82,7 @@ def env_pose_ptrs(sim):
     return pos.value, quat.value, cs.value
 
 
-def _p(t):
-    return ctypes.c_void_p(0) if t is None else ctypes.c_void_p(t if isinstance(t, int) else t.data_ptr())
-
-
-class LidarScan:
+class LidarScan(Handle):
     def __init__(self, cfg, n_envs, hf_int16, horizontal_scale, vertical_scale, origin, *, seed=1, dr_schedule=None, curriculum_enabled=False, device=None):
         if not torch.cuda.is_available():
             raise Go2SimError("no ROCm GPU visible: the go2sim product path has no CPU fallback")
@@ -108,23 +104,12 @@ class LidarScan:
         c.horizontal_scale, c.vertical_scale = float(horizontal_scale), float(vertical_scale)
         c.n_envs, c.n_actor, c.n_critic, c.hf_rows, c.hf_cols = self.n_envs, self.n_actor, self.n_critic, hf.shape[0], hf.shape[1]
         self._L = load_hip_lib()
-        self.h = None
+        Handle.__init__(self, self._L, "lidar_destroy")
         h = ctypes.c_void_p()
         self._L.check(self._L.fn("lidar_create")(ctypes.c_int(self.device.index or 0), ctypes.byref(c), hf.ctypes.data_as(ctypes.c_void_p),
                                                  lay["actor_xy"].ctypes.data_as(ctypes.c_void_p), lay["critic_xy"].ctypes.data_as(ctypes.c_void_p),
                                                  ctypes.c_uint64(int(seed)), ctypes.byref(h)), "lidar_create")
         self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._L.fn("lidar_destroy")(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -155,14 +140,14 @@ class LidarScan:
     def clear(self, envs_idx=None):
         """Stored actor scan := 0 for ``envs_idx`` (int32 device tensor) or for every env."""
         n = 0 if envs_idx is None else envs_idx.numel()
-        self._L.check(self._L.fn("lidar_clear")(self.h, _p(envs_idx), ctypes.c_int(n), self._stream()), "lidar_clear")
+        self._L.check(self._L.fn("lidar_clear")(self.h, _ptr(envs_idx), ctypes.c_int(n), self._stream()), "lidar_clear")
 
     # ---- the step ----------------------------------------------------------------------------------------------------------
     def step(self, pos, pos_strides, quat, quat_strides, reset, level, obs, priv, n_in, obs_out, priv_out):
         """go2sim_lidar_step with device tensors or raw device addresses; strides are (component, env) in elements."""
-        rc = self._L.fn("lidar_step")(self.h, ctypes.c_int(self.n_envs), _p(pos), ctypes.c_longlong(pos_strides[0]), ctypes.c_longlong(pos_strides[1]),
-                                      _p(quat), ctypes.c_longlong(quat_strides[0]), ctypes.c_longlong(quat_strides[1]), _p(reset), _p(level), _p(obs), _p(priv),
-                                      ctypes.c_int(n_in), _p(obs_out), _p(priv_out), self._stream())
+        rc = self._L.fn("lidar_step")(self.h, ctypes.c_int(self.n_envs), _ptr(pos, True), ctypes.c_longlong(pos_strides[0]), ctypes.c_longlong(pos_strides[1]),
+                                      _ptr(quat, True), ctypes.c_longlong(quat_strides[0]), ctypes.c_longlong(quat_strides[1]), _ptr(reset), _ptr(level), _ptr(obs), _ptr(priv),
+                                      ctypes.c_int(n_in), _ptr(obs_out), _ptr(priv_out), self._stream())
         self._L.check(rc, "lidar_step")
 
     def scan(self, pos, quat, reset=None, level=None):

@@ -16,15 +16,11 @@ import ctypes
 import numpy as np
 import torch
 
-from .capi import Go2SimError, load_hip_lib
+from .capi import Go2SimError, Handle, _ptr, load_hip_lib
 from .distributed import allgather_records, is_multi
 
 
-def _p(t):
-    return ctypes.c_void_p(0) if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-class EmpiricalNormalization:
+class EmpiricalNormalization(Handle):
     def __init__(self, shape, eps=1e-2, until=None, *, device=None):
         if not torch.cuda.is_available():
             raise Go2SimError("no ROCm GPU visible: the go2sim product path has no CPU fallback")
@@ -34,23 +30,12 @@ class EmpiricalNormalization:
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.training = True
         self._L = load_hip_lib()
+        Handle.__init__(self, self._L, "norm_destroy")
         self._bufs = {}
         h = ctypes.c_void_p()
-        self.h = None
         self._L.check(self._L.fn("norm_create")(ctypes.c_int(self.device.index or 0), ctypes.c_int(self.d), ctypes.c_double(self.eps),
                                                 ctypes.c_double(0.0 if until is None else float(until)), ctypes.byref(h)), "norm_create")
         self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._L.fn("norm_destroy")(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- rsl_rl's module surface -----------------------------------------------------------------------
     def train(self, mode=True):
@@ -83,7 +68,7 @@ class EmpiricalNormalization:
     def update(self, x):
         """Fold the batch into the statistics (unless ``count >= until``); the normalised rows go to a scratch buffer."""
         x = self._in(x)
-        self._L.check(self._L.fn("norm_step")(self.h, _p(x), _p(self._out(x.shape[0], "scratch")), None, None, None, ctypes.c_int(x.shape[0]), ctypes.c_int(1),
+        self._L.check(self._L.fn("norm_step")(self.h, _ptr(x), _ptr(self._out(x.shape[0], "scratch")), None, None, None, ctypes.c_int(x.shape[0]), ctypes.c_int(1),
                                               self._stream()), "norm_step")
 
     def inverse(self, y):
@@ -151,10 +136,10 @@ def norm_step(norm_a, x_a, norm_b=None, x_b=None, update=None, group=None):
         ln = ctypes.c_int()
         L.check(L.fn("norm_record_len")(norm_a.h, hb, ctypes.byref(ln)), "norm_record_len")
         rec = torch.empty(ln.value, dtype=torch.float64, device=norm_a.device)
-        L.check(L.fn("norm_moments")(norm_a.h, _p(xa), hb, _p(xb), ctypes.c_int(n), _p(rec), stream), "norm_moments")
+        L.check(L.fn("norm_moments")(norm_a.h, _ptr(xa), hb, _ptr(xb), ctypes.c_int(n), _ptr(rec), stream), "norm_moments")
         recs = allgather_records(rec, group).contiguous()
-        L.check(L.fn("norm_merge_step")(norm_a.h, _p(xa), _p(ya), hb, _p(xb), _p(yb), ctypes.c_int(n), _p(recs), ctypes.c_int(recs.shape[0]), ctypes.c_int(1), stream),
+        L.check(L.fn("norm_merge_step")(norm_a.h, _ptr(xa), _ptr(ya), hb, _ptr(xb), _ptr(yb), ctypes.c_int(n), _ptr(recs), ctypes.c_int(recs.shape[0]), ctypes.c_int(1), stream),
                 "norm_merge_step")
     else:
-        L.check(L.fn("norm_step")(norm_a.h, _p(xa), _p(ya), hb, _p(xb), _p(yb), ctypes.c_int(n), ctypes.c_int(int(update)), stream), "norm_step")
+        L.check(L.fn("norm_step")(norm_a.h, _ptr(xa), _ptr(ya), hb, _ptr(xb), _ptr(yb), ctypes.c_int(n), ctypes.c_int(int(update)), stream), "norm_step")
     return ya, yb

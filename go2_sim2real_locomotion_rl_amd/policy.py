@@ -24,7 +24,7 @@ import ctypes
 import numpy as np
 import torch
 
-from .capi import ACTIVATIONS, Go2SimError, load_hip_lib
+from .capi import ACTIVATIONS, Go2SimError, Handle, _ptr, load_hip_lib
 
 
 def resolve_activation(name):
@@ -39,10 +39,11 @@ def resolve_activation(name):
     return key
 
 
-class Mlp:
+class Mlp(Handle):
     """One go2sim_mlp handle (works with either library: product or CPU oracle; the oracle's is ELU only)."""
 
     def __init__(self, lib, dims, params, device=0, activation="elu"):
+        Handle.__init__(self, lib, "mlp_destroy")
         self.L, self.dims = lib, [int(d) for d in dims]
         activation = resolve_activation(activation)
         if activation != "elu" and not lib.is_device:                              # before the handle exists: nothing to release on the refusal
@@ -80,26 +81,6 @@ class Mlp:
 
     def forward(self, x, y, n_rows, stream=0):
         self.L.check(self.L.fn("mlp_forward")(self.h, _ptr(x), _ptr(y), ctypes.c_int(n_rows), ctypes.c_void_p(stream)), "mlp_forward")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fn("mlp_destroy")(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _ptr(a):
-    if a is None:
-        return ctypes.c_void_p(0)
-    if isinstance(a, torch.Tensor):
-        return ctypes.c_void_p(a.data_ptr())
-    return a.ctypes.data_as(ctypes.c_void_p)
-
 
 def flatten_sequential(state_dict, prefix, n_layers):
     """[W0, b0, W1, b1, ...] of ``prefix.{0,2,4,...}`` as one float32 vector (the layout go2sim_mlp_create takes) + the layer sizes."""
@@ -279,15 +260,15 @@ def flatten_lstm(state_dict, prefix):
     return np.concatenate([t.reshape(-1) for t in ts]), (ts[0].shape[1], ts[0].shape[0] // 4)
 
 
-class Lstm:
+class Lstm(Handle):
     """One go2sim_lstm handle of the product library."""
 
     def __init__(self, lib, n_in, n_hidden, params, device=0):
+        Handle.__init__(self, lib, "lstm_destroy")
         self.L, self.n_in, self.n_hidden = lib, int(n_in), int(n_hidden)
         params = np.ascontiguousarray(params, dtype=np.float32)
         self.n_params = params.size
         h = ctypes.c_void_p()
-        self.h = None
         lib.check(lib.fn("lstm_create")(ctypes.c_int(device), ctypes.c_int(n_in), ctypes.c_int(n_hidden), params.ctypes.data_as(ctypes.c_void_p),
                                         ctypes.c_size_t(params.size), ctypes.byref(h)), "lstm_create")
         self.h = h
@@ -301,18 +282,6 @@ class Lstm:
         out = np.empty(self.n_params, np.float32)
         self.L.check(self.L.fn("lstm_get_params")(self.h, out.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(out.size), ctypes.c_void_p(stream)), "lstm_get_params")
         return out
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fn("lstm_destroy")(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def lstm_step(lib, mem_a, x_a, h_in_a, c_in_a, h_out_a, c_out_a, mem_c=None, x_c=None, h_in_c=None, c_in_c=None, h_out_c=None, c_out_c=None, reset=None, n_rows=None,
               stream=0):

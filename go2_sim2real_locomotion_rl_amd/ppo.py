@@ -30,15 +30,12 @@ import ctypes
 
 import torch
 
-from .capi import C, Go2SimError, PpoBatch, PpoCfg, PpoMirror, PpoRnnState, load_hip_lib
+from .capi import C, Go2SimError, PpoBatch, PpoCfg, PpoMirror, PpoRnnState, _ptr, load_hip_lib
 from .distributed import allgather_records, broadcast_from_rank0, is_multi, shard_seed
 from .rollout import RolloutStorage
+from .trainer import OptimizerState, TrainerHandle, mlp_keys, unflatten_keys
 
 VECS = ("PARAMS", "GRADS", "ADAM_M", "ADAM_V")
-
-
-def _p(t):
-    return ctypes.c_void_p(0) if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def make_batch(**tensors):
@@ -52,19 +49,18 @@ def make_batch(**tensors):
     return b
 
 
-class PpoHandle:
+class PpoHandle(TrainerHandle):
     """One go2sim_ppo handle: pointers only.  `actor` / `critic` are policy.Mlp objects of the product library."""
 
     def __init__(self, lib, actor, critic, n_actions, max_rows, *, clip_param=0.2, desired_kl=0.01, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0,
                  value_loss_coef=1.0, use_clipped_value_loss=True, adaptive=False, betas=(0.9, 0.999), eps=1e-8, lr_min=1e-5, lr_max=1e-2, device=None,
                  memories=None, n_steps=None):
         """memories = (policy.Lstm of the actor, of the critic) and n_steps: the recurrent handle (include/go2sim_rnn.h), max_rows = n_steps x envs of a mini-batch"""
-        self.L, self.actor, self.critic, self.memories = lib, actor, critic, memories
-        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+        TrainerHandle.__init__(self, lib, "ppo", device)
+        self.actor, self.critic, self.memories = actor, critic, memories
         cfg = PpoCfg(clip_param, desired_kl, entropy_coef, learning_rate, max_grad_norm, value_loss_coef, betas[0], betas[1], eps, lr_min, lr_max,
                      int(bool(use_clipped_value_loss)), int(bool(adaptive)))
         h = ctypes.c_void_p()
-        self.h = None
         if memories is None:
             lib.check(lib.fn("ppo_create")(actor.h, critic.h, ctypes.c_int(n_actions), ctypes.byref(cfg), ctypes.c_int(max_rows), ctypes.byref(h)), "ppo_create")
         else:
@@ -72,24 +68,16 @@ class PpoHandle:
                 raise Go2SimError("a recurrent handle is sized as n_steps x envs per mini-batch rows")
             lib.check(lib.fn("ppo_create_recurrent")(actor.h, critic.h, memories[0].h, memories[1].h, ctypes.c_int(n_actions), ctypes.byref(cfg), ctypes.c_int(int(n_steps)),
                                                      ctypes.c_int(max_rows // int(n_steps)), ctypes.byref(h)), "ppo_create_recurrent")
-        self.h = h
+        self._created(h)
         n = ctypes.c_size_t()
-        lib.check(lib.fn("ppo_n_params")(self.h, ctypes.byref(n)), "ppo_n_params")
-        self.n_params = n.value
-        lib.check(lib.fn("ppo_n_padded")(self.h, ctypes.byref(n)), "ppo_n_padded")
-        self.n_padded = n.value
         lib.check(lib.fn("ppo_shard_len")(self.h, ctypes.byref(n)), "ppo_shard_len")
         self.shard_len = n.value
-        self._stats = torch.zeros(C["GO2SIM_PPO_N_STATS"], dtype=torch.float64, device=self.device)
         self._sym = torch.zeros(1, dtype=torch.float64, device=self.device)
         self.mirror = None
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def minibatch_grad(self, batch, std, idx, n_rows=None):
         n = idx.numel() if n_rows is None else n_rows
-        self.L.check(self.L.fn("ppo_minibatch_grad")(self.h, ctypes.byref(batch), _p(std), _p(idx), ctypes.c_int(n), self._stream()), "ppo_minibatch_grad")
+        self._call("minibatch_grad", ctypes.byref(batch), _ptr(std), _ptr(idx), ctypes.c_int(n))
 
     def shard_grad(self, batch, std, idx, n_rows_global, record=None, n_rows=None):
         """This shard's contribution to a mini-batch of n_rows_global rows: a float64 device record of shard_len entries (include/go2sim_train.h)"""
@@ -98,21 +86,20 @@ class PpoHandle:
             record = torch.empty(self.shard_len, dtype=torch.float64, device=self.device)
         elif record.dtype != torch.float64 or record.numel() != self.shard_len or not record.is_contiguous():
             raise Go2SimError(f"a record is a contiguous float64 tensor of {self.shard_len} entries")
-        self.L.check(self.L.fn("ppo_shard_grad")(self.h, ctypes.byref(batch), _p(std), _p(idx), ctypes.c_int(n), ctypes.c_longlong(int(n_rows_global)), _p(record),
-                                                 self._stream()), "ppo_shard_grad")
+        self._call("shard_grad", ctypes.byref(batch), _ptr(std), _ptr(idx), ctypes.c_int(n), ctypes.c_longlong(int(n_rows_global)), _ptr(record))
         return record
 
     def shard_reduce(self, records, std):
         """records [n][shard_len] float64 on the device, added in the order given: gradients, learning-rate rule and running sums of the whole mini-batch"""
         if records.dtype != torch.float64 or not records.is_contiguous() or records.numel() % self.shard_len or not records.is_cuda:
             raise Go2SimError(f"records must be a contiguous float64 device tensor [n][{self.shard_len}]")
-        self.L.check(self.L.fn("ppo_shard_reduce")(self.h, _p(records), ctypes.c_int(records.numel() // self.shard_len), _p(std), self._stream()), "ppo_shard_reduce")
+        self._call("shard_reduce", _ptr(records), ctypes.c_int(records.numel() // self.shard_len), _ptr(std))
 
     def set_mirror(self, tables, use_data_augmentation=False, use_mirror_loss=False, mirror_loss_coeff=0.0):
         """tables: {"policy": (src, sign), "critic": (src, sign), "actions": (src, sign)}, each a signed permutation (M x)[j] = sign[j] x[src[j]], or None
         to return to the plain update.  Waits for the device (the library validates the tables on the host); shard_len changes with it."""
         if tables is None:
-            self.L.check(self.L.fn("ppo_set_mirror")(self.h, ctypes.c_void_p(0), self._stream()), "ppo_set_mirror")
+            self._call("set_mirror", ctypes.c_void_p(0))
             self.mirror = None
         else:
             m, keep = PpoMirror(), []
@@ -128,7 +115,7 @@ class PpoHandle:
                 setattr(m, name + "_src", src.data_ptr()); setattr(m, name + "_sign", sign.data_ptr())
                 keep += [src, sign]
             m.use_data_augmentation, m.use_mirror_loss, m.mirror_loss_coeff = int(bool(use_data_augmentation)), int(bool(use_mirror_loss)), float(mirror_loss_coeff)
-            self.L.check(self.L.fn("ppo_set_mirror")(self.h, ctypes.byref(m), self._stream()), "ppo_set_mirror")      # the library has its own copy on return
+            self._call("set_mirror", ctypes.byref(m))      # the library has its own copy on return
             self.mirror = dict(use_data_augmentation=bool(use_data_augmentation), use_mirror_loss=bool(use_mirror_loss), mirror_loss_coeff=float(mirror_loss_coeff))
         n = ctypes.c_size_t()
         self.L.check(self.L.fn("ppo_shard_len")(self.h, ctypes.byref(n)), "ppo_shard_len")
@@ -136,64 +123,32 @@ class PpoHandle:
 
     def symmetry_loss(self):
         """float64 device tensor [1]: mean of the mirror loss L_sym over the mini-batches since the last reset; no synchronisation"""
-        self.L.check(self.L.fn("ppo_symmetry_loss")(self.h, _p(self._sym), self._stream()), "ppo_symmetry_loss")
+        self._call("symmetry_loss", _ptr(self._sym))
         return self._sym
 
     def apply(self, std):
-        self.L.check(self.L.fn("ppo_apply")(self.h, _p(std), self._stream()), "ppo_apply")
+        self._call("apply", _ptr(std))
 
     def update(self, batch, std, perm, n_rows_total, n_epochs, n_mini_batches):
-        self.L.check(self.L.fn("ppo_update")(self.h, ctypes.byref(batch), _p(std), _p(perm), ctypes.c_int(n_rows_total), ctypes.c_int(n_epochs),
-                                             ctypes.c_int(n_mini_batches), self._stream()), "ppo_update")
+        self._call("update", ctypes.byref(batch), _ptr(std), _ptr(perm), ctypes.c_int(n_rows_total), ctypes.c_int(n_epochs), ctypes.c_int(n_mini_batches))
 
     def rnn_minibatch_grad(self, batch, state, std, n_envs, env0, n_block):
         """forward, head and backward through time of the env block [env0, env0 + n_block) of a rollout of n_steps x n_envs rows (recurrent handle)"""
-        self.L.check(self.L.fn("ppo_rnn_minibatch_grad")(self.h, ctypes.byref(batch), ctypes.byref(state), _p(std), ctypes.c_int(n_envs), ctypes.c_int(env0),
-                                                         ctypes.c_int(n_block), self._stream()), "ppo_rnn_minibatch_grad")
+        self._call("rnn_minibatch_grad", ctypes.byref(batch), ctypes.byref(state), _ptr(std), ctypes.c_int(n_envs), ctypes.c_int(env0), ctypes.c_int(n_block))
 
     def rnn_update(self, batch, state, std, n_envs, n_epochs, n_mini_batches):
-        self.L.check(self.L.fn("ppo_rnn_update")(self.h, ctypes.byref(batch), ctypes.byref(state), _p(std), ctypes.c_int(n_envs), ctypes.c_int(n_epochs),
-                                                 ctypes.c_int(n_mini_batches), self._stream()), "ppo_rnn_update")
+        self._call("rnn_update", ctypes.byref(batch), ctypes.byref(state), _ptr(std), ctypes.c_int(n_envs), ctypes.c_int(n_epochs), ctypes.c_int(n_mini_batches))
 
     def export(self, which, std=None):
         """flat float32 device vector in state-dict order: actor W0, b0, ..., critic W0, b0, ..., (memory_a, memory_c: weight_ih, weight_hh, bias_ih, bias_hh,) std"""
-        out = torch.empty(self.n_params, dtype=torch.float32, device=self.device)
-        self.L.check(self.L.fn("ppo_export")(self.h, ctypes.c_int(C["GO2SIM_PPO_" + which]), _p(out), _p(std), self._stream()), "ppo_export")
-        return out
+        return TrainerHandle.export(self, which, std)
 
     def import_(self, which, flat, std=None):
-        flat = flat.to(device=self.device, dtype=torch.float32).contiguous()
-        if flat.numel() != self.n_params:
-            raise Go2SimError(f"flat vector has {flat.numel()} entries, expected {self.n_params}")
-        self.L.check(self.L.fn("ppo_import")(self.h, ctypes.c_int(C["GO2SIM_PPO_" + which]), _p(flat), _p(std), self._stream()), "ppo_import")
-        torch.cuda.current_stream(self.device).synchronize()          # `flat` may be a temporary
-
-    def export_padded(self, which):
-        out = torch.empty(self.n_padded, dtype=torch.float32, device=self.device)
-        self.L.check(self.L.fn("ppo_export_padded")(self.h, ctypes.c_int(C["GO2SIM_PPO_" + which]), _p(out), self._stream()), "ppo_export_padded")
-        return out
-
-    def set_step(self, step, learning_rate):
-        self.L.check(self.L.fn("ppo_set_step")(self.h, ctypes.c_longlong(int(step)), ctypes.c_double(float(learning_rate)), self._stream()), "ppo_set_step")
-
-    def reset_stats(self):
-        self.L.check(self.L.fn("ppo_reset_stats")(self.h, self._stream()), "ppo_reset_stats")
+        TrainerHandle.import_(self, which, flat, std)
 
     def stats(self):
         """float64 device tensor [value loss, surrogate loss, entropy, kl_mean, learning rate, grad norm, step, mini-batches]; no synchronisation"""
-        self.L.check(self.L.fn("ppo_stats")(self.h, _p(self._stats), self._stream()), "ppo_stats")
-        return self._stats
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fn("ppo_destroy")(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return TrainerHandle.stats(self)
 
 
 def make_rnn_state(h_a, c_a, h_c, c_c, dones):
@@ -208,10 +163,7 @@ def make_rnn_state(h_a, c_a, h_c, c_c, dones):
 
 def state_dict_keys(adims, cdims, mdims=None):
     """[(key, shape)] in the flat order of go2sim_ppo_export; mdims = ((n_in, H) of memory_a, of memory_c) for a recurrent policy"""
-    keys = []
-    for prefix, dims in (("actor", adims), ("critic", cdims)):
-        for l in range(len(dims) - 1):
-            keys += [(f"{prefix}.{2 * l}.weight", (dims[l + 1], dims[l])), (f"{prefix}.{2 * l}.bias", (dims[l + 1],))]
+    keys = mlp_keys("actor", adims) + mlp_keys("critic", cdims)
     if mdims is not None:
         for prefix, (n_in, H) in zip(("memory_a", "memory_c"), mdims):
             keys += [(f"{prefix}.rnn.weight_ih_l0", (4 * H, n_in)), (f"{prefix}.rnn.weight_hh_l0", (4 * H, H)), (f"{prefix}.rnn.bias_ih_l0", (4 * H,)),
@@ -221,21 +173,14 @@ def state_dict_keys(adims, cdims, mdims=None):
 
 
 def unflatten(flat, adims, cdims, mdims=None):
-    out, o = {}, 0
-    for k, shape in state_dict_keys(adims, cdims, mdims):
-        n = 1
-        for s in shape:
-            n *= s
-        out[k] = flat[o:o + n].reshape(shape).clone()
-        o += n
-    return out
+    return unflatten_keys(flat, state_dict_keys(adims, cdims, mdims))
 
 
 def flatten(sd, adims, cdims, mdims=None):
     return torch.cat([sd[k].detach().reshape(-1).to(torch.float32).cpu() for k, _ in state_dict_keys(adims, cdims, mdims)])
 
 
-class PPO:
+class PPO(OptimizerState):
     def __init__(self, policy, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95, value_loss_coef=1.0, entropy_coef=0.0,
                  learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device=None, *, seed=1, group=None, symmetry_cfg=None,
                  **kwargs):
@@ -372,13 +317,9 @@ class PPO:
 
     # ---- optimizer state (runner checkpoints) ----------------------------------------------------------
     def optimizer_state_dict(self):
-        s = self._h.stats().cpu()
-        return {"exp_avg": self._h.export("ADAM_M").cpu(), "exp_avg_sq": self._h.export("ADAM_V").cpu(), "step": int(s[C["GO2SIM_PPO_ST_STEP"]]),
-                "lr": float(s[C["GO2SIM_PPO_ST_LR"]]), "perm_generator_state": self._gen.get_state().cpu()}
+        return dict(OptimizerState.optimizer_state_dict(self), perm_generator_state=self._gen.get_state().cpu())
 
     def load_optimizer_state_dict(self, sd):
-        self._h.import_("ADAM_M", sd["exp_avg"]); self._h.import_("ADAM_V", sd["exp_avg_sq"])
-        self._h.set_step(int(sd["step"]), float(sd["lr"]))
-        self.learning_rate = float(sd["lr"])
+        OptimizerState.load_optimizer_state_dict(self, sd)
         if sd.get("perm_generator_state") is not None and self.rank == 0:     # the file holds rank 0's stream; the other ranks keep their own
             self._gen.set_state(sd["perm_generator_state"].cpu())

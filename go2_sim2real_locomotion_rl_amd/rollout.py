@@ -15,50 +15,35 @@ import ctypes
 
 import torch
 
-from .capi import C, Go2SimError, load_hip_lib
+from .capi import C, Go2SimError, Handle, _ptr, load_hip_lib
 from .distributed import allgather_moments
 
 
-def _p(t):
-    return ctypes.c_void_p(0) if t is None else ctypes.c_void_p(t.data_ptr() if isinstance(t, torch.Tensor) else t.ctypes.data)
-
-
-class RolloutBuffers:
+class RolloutBuffers(Handle):
     """One go2sim_rollout handle (either library); pointers only, no torch arithmetic."""
 
     def __init__(self, lib, n_steps, n_envs, device=0):
+        Handle.__init__(self, lib, "rollout_destroy")
         self.L, self.T, self.B = lib, int(n_steps), int(n_envs)
         h = ctypes.c_void_p()
         lib.check(lib.fn("rollout_create")(ctypes.c_int(device), ctypes.c_int(n_steps), ctypes.c_int(n_envs), ctypes.byref(h)), "rollout_create")
         self.h = h
 
     def add(self, t, rewards, dones, values, time_outs, gamma, stream=0):
-        self.L.check(self.L.fn("rollout_add")(self.h, ctypes.c_int(t), _p(rewards), _p(dones), _p(values), _p(time_outs), ctypes.c_float(gamma),
+        self.L.check(self.L.fn("rollout_add")(self.h, ctypes.c_int(t), _ptr(rewards), _ptr(dones), _ptr(values), _ptr(time_outs), ctypes.c_float(gamma),
                                               ctypes.c_void_p(stream)), "rollout_add")
 
     def compute_returns(self, last_values, gamma, lam, moments3, stream=0):
-        self.L.check(self.L.fn("rollout_compute_returns")(self.h, _p(last_values), ctypes.c_float(gamma), ctypes.c_float(lam), _p(moments3),
+        self.L.check(self.L.fn("rollout_compute_returns")(self.h, _ptr(last_values), ctypes.c_float(gamma), ctypes.c_float(lam), _ptr(moments3),
                                                           ctypes.c_void_p(stream)), "rollout_compute_returns")
 
     def normalize(self, moments3, stream=0):
-        self.L.check(self.L.fn("rollout_normalize")(self.h, _p(moments3), ctypes.c_void_p(stream)), "rollout_normalize")
+        self.L.check(self.L.fn("rollout_normalize")(self.h, _ptr(moments3), ctypes.c_void_p(stream)), "rollout_normalize")
 
     def ptr(self, which):
         p = ctypes.c_void_p()
         self.L.check(self.L.fn("rollout_ptr")(self.h, ctypes.c_int(C["GO2SIM_RB_" + which]), ctypes.byref(p)), "rollout_ptr")
         return p.value
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fn("rollout_destroy")(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class RolloutStorage:
     def __init__(self, num_transitions_per_env, num_envs, device=None):

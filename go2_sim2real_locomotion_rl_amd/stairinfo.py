@@ -13,7 +13,7 @@ import math
 import numpy as np
 import torch
 
-from .capi import C, Go2SimError, load_hip_lib
+from .capi import C, Go2SimError, Handle, _ptr, load_hip_lib
 
 
 class StairInfoCfg(ctypes.Structure):
@@ -86,11 +86,7 @@ def env_rows_ptr(sim):
     return rows.value
 
 
-def _p(t):
-    return ctypes.c_void_p(0) if t is None else ctypes.c_void_p(t if isinstance(t, int) else t.data_ptr())
-
-
-class StairInfo:
+class StairInfo(Handle):
     def __init__(self, cfg, n_envs, hf_int16, horizontal_scale, vertical_scale, origin, step_heights_m, step_depths_m, *, seed=1, dr_schedule=None,
                  curriculum_enabled=False, device=None):
         if not torch.cuda.is_available():
@@ -120,24 +116,13 @@ class StairInfo:
         c.horizontal_scale, c.vertical_scale = float(horizontal_scale), float(vertical_scale)
         c.n_envs, c.n_samples, c.n_rows, c.hf_rows, c.hf_cols = self.n_envs, len(lay["sample_x"]), self.n_rows, hf.shape[0], hf.shape[1]
         self._L = load_hip_lib()
-        self.h = None
+        Handle.__init__(self, self._L, "stairinfo_destroy")
         h = ctypes.c_void_p()
         self._L.check(self._L.fn("stairinfo_create")(ctypes.c_int(self.device.index or 0), ctypes.byref(c), hf.ctypes.data_as(ctypes.c_void_p),
                                                      lay["sample_x"].ctypes.data_as(ctypes.c_void_p), self.row_heights.ctypes.data_as(ctypes.c_void_p),
                                                      self.row_depths.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(int(seed)), ctypes.byref(h)),
                       "stairinfo_create")
         self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._L.fn("stairinfo_destroy")(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -168,14 +153,14 @@ class StairInfo:
     def clear(self, envs_idx=None):
         """Stored actor row := 0 for ``envs_idx`` (int32 device tensor) or for every env."""
         n = 0 if envs_idx is None else envs_idx.numel()
-        self._L.check(self._L.fn("stairinfo_clear")(self.h, _p(envs_idx), ctypes.c_int(n), self._stream()), "stairinfo_clear")
+        self._L.check(self._L.fn("stairinfo_clear")(self.h, _ptr(envs_idx), ctypes.c_int(n), self._stream()), "stairinfo_clear")
 
     # ---- the step ----------------------------------------------------------------------------------------------------------
     def step(self, pos, pos_strides, quat, quat_strides, rows, reset, level, obs, priv, n_in, obs_out, priv_out):
         """go2sim_stairinfo_step with device tensors or raw device addresses; strides are (component, env) in elements."""
-        rc = self._L.fn("stairinfo_step")(self.h, ctypes.c_int(self.n_envs), _p(pos), ctypes.c_longlong(pos_strides[0]), ctypes.c_longlong(pos_strides[1]),
-                                          _p(quat), ctypes.c_longlong(quat_strides[0]), ctypes.c_longlong(quat_strides[1]), _p(rows), _p(reset), _p(level),
-                                          _p(obs), _p(priv), ctypes.c_int(n_in), _p(obs_out), _p(priv_out), self._stream())
+        rc = self._L.fn("stairinfo_step")(self.h, ctypes.c_int(self.n_envs), _ptr(pos, True), ctypes.c_longlong(pos_strides[0]), ctypes.c_longlong(pos_strides[1]),
+                                          _ptr(quat, True), ctypes.c_longlong(quat_strides[0]), ctypes.c_longlong(quat_strides[1]), _ptr(rows), _ptr(reset), _ptr(level),
+                                          _ptr(obs), _ptr(priv), ctypes.c_int(n_in), _ptr(obs_out), _ptr(priv_out), self._stream())
         self._L.check(rc, "stairinfo_step")
 
     def info(self, pos, quat, rows=None, reset=None, level=None):

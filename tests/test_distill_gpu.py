@@ -289,3 +289,40 @@ def test_bad_arguments_return_a_status_and_launch_nothing(hip_lib):
     assert act(*args()) == 0
     s, _ = side.stats()
     assert np.array_equal(bits(side.h.export("GRADS")), before) and s["pairs"] == 1 and s["step"] == 0 and s["windows"] == 0, "a refused call must not have launched anything"
+
+
+# ---- the bits of the build before the trainers' host code was shared (tools/record_ppo_plain_golden.py) --------------------------------------------
+def golden_window(lib, case):
+    from test_ppo_gpu import grad_and_apply_bits
+
+    c = DC.get_case(*case)
+    side = case_side(lib, c)
+    side.h.window_grad(side.obs, side.ta, c.idx.to(DEV), c.N)
+    return grad_and_apply_bits(side.h)
+
+
+def golden_window_across_chunks(lib):
+    """one window of three row chunks, in one piece and in sub-batches of one chunk"""
+    c = DC.get_case("small", 2 * DC.ROW_CHUNK + 37, 1, "mse", "plain")
+    out = {}
+    for tag, sub in (("one_piece", 0), ("sub_batches", DC.ROW_CHUNK)):
+        side = case_side(lib, c, sub_rows=sub)
+        side.h.window_grad(side.obs, side.ta, c.idx.to(DEV), c.N)
+        out["grads_padded_" + tag], out["stats_" + tag] = bits(side.h.export_padded("GRADS")), side.stats()[1].numpy().view(np.int64).copy()
+    return out
+
+
+GOLDEN_WINDOWS = {"distill_small_37_3_mse_plain": ("small", 37, 3, "mse", "plain"), "distill_six_layers_37_3_huber_dup": ("six_layers", 37, 3, "huber", "dup")}
+
+
+@pytest.mark.parametrize("name", sorted(GOLDEN_WINDOWS))
+def test_window_and_step_have_the_parent_builds_bits(hip_lib, name):
+    from test_ppo_gpu import check_golden
+
+    check_golden(name, golden_window(hip_lib, GOLDEN_WINDOWS[name]))
+
+
+def test_window_across_chunks_has_the_parent_builds_bits(hip_lib):
+    from test_ppo_gpu import check_golden
+
+    check_golden("distill_small_1061_chunks", golden_window_across_chunks(hip_lib))

@@ -7,6 +7,7 @@ C_GRAD and C_UPD: the smallest of 4, 8, 16, 32 that is at least twice the worst 
 include/go2sim_train.h and DESIGN.md "PPO update").  Every test prints its ratios before it asserts.  Then bit reproducibility, the Python
 classes (PPO, OnPolicyRunner, ActorCritic.state_dict) and the status codes."""
 import ctypes
+import os
 
 import numpy as np
 import pytest
@@ -21,6 +22,7 @@ C_GRAD = 16
 C_UPD = 8
 EPS = 2.0 ** -24
 DEV = "cuda:0"
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def r16(v):
@@ -387,3 +389,55 @@ def test_bad_arguments_return_a_status_and_launch_nothing(hip_lib):
     assert L.fn("ppo_destroy")(null) == BAD
     s, _ = side.stats()
     assert torch.equal(side.h.export("GRADS").cpu(), before) and s["count"] == 1 and s["step"] == 0, "a refused call must not have launched anything"
+
+
+# ---- the bits of the build before the trainers' host code was shared (tools/record_ppo_plain_golden.py) --------------------------------------------
+def bits32(t):
+    return t.detach().cpu().contiguous().numpy().view(np.int32)
+
+
+def grad_and_apply_bits(h, std=None):
+    """After a gradient call on handle `h`: the padded gradient and the statistics, then the step and the parameters, Adam's moments and the statistics.
+    std = None: a handle whose apply / export take no std (distillation)."""
+    stats = lambda: h.stats().cpu().numpy().view(np.int64).copy()
+    out = {"grads_padded": bits32(h.export_padded("GRADS")), "stats_grad": stats()}
+    if std is None:
+        h.apply()
+        out["params"] = bits32(h.export("PARAMS"))
+    else:
+        h.apply(std)
+        out["params"] = bits32(h.export("PARAMS", std))
+    out["adam_m"], out["adam_v"], out["stats_apply"] = bits32(h.export_padded("ADAM_M")), bits32(h.export_padded("ADAM_V")), stats()
+    return out
+
+
+def check_golden(name, got):
+    want = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
+    assert set(want.files) == set(got)
+    for k in got:
+        assert np.array_equal(got[k], want[k]), k
+    assert any(np.abs(got[k].view(np.float32)).max() > 0 for k in got if k.startswith("grads"))
+
+
+def golden_plain_unequal_depth(lib):
+    """actor [5, 8, 4] over critic [7, 1]: the critic has no layer left when the actor's first one runs"""
+    adims, cdims, n = [5, 8, 4], [7, 1], 17
+    state = PC.init_state(adims, cdims, torch.Generator().manual_seed(4100))
+    side = Side(lib, adims, cdims, state, PC.make_rollout(adims, cdims, state, n, "keep", 4101), n)
+    side.h.minibatch_grad(side.batch, side.std, torch.arange(n, dtype=torch.int32, device=DEV))
+    return grad_and_apply_bits(side.h, side.std)
+
+
+def golden_plain_row_chunks(lib):
+    c = PC.get_case("small", 2 * PC.ROW_CHUNK + 37, "down")
+    side = case_side(lib, c)
+    side.h.minibatch_grad(side.batch, side.std, c.idx.to(DEV))
+    return grad_and_apply_bits(side.h, side.std)
+
+
+def test_unequal_depths_have_the_parent_builds_bits(hip_lib):
+    check_golden("ppo_plain_unequal_depth_17", golden_plain_unequal_depth(hip_lib))
+
+
+def test_several_row_chunks_have_the_parent_builds_bits(hip_lib):
+    check_golden("ppo_plain_small_1061_down", golden_plain_row_chunks(hip_lib))

@@ -17,7 +17,7 @@ import ppo_cases as PC
 import ppo_ref as R
 import ppo_rnn_cases as RC
 import ppo_rnn_ref as RR
-from test_ppo_gpu import TRAIN_CFG, case_side, walk_env
+from test_ppo_gpu import TRAIN_CFG, case_side, check_golden, grad_and_apply_bits, walk_env
 
 pytestmark = pytest.mark.gpu
 
@@ -323,6 +323,18 @@ def test_plain_path_has_the_parent_builds_bits(hip_lib):
     assert set(want.files) == set(got)
     for k in got:
         assert np.array_equal(got[k], want[k]), k
+
+
+def golden_recurrent(lib):
+    c = RC.get_case("h20-t3-n17-last")
+    side = side_of(lib, c)
+    side.h.rnn_minibatch_grad(side.batch, side.rstate, side.std, c.B, c.e0, c.nb)
+    return grad_and_apply_bits(side.h, side.std)
+
+
+def test_recurrent_path_has_the_parent_builds_bits(hip_lib):
+    """The same for a handle with memories, recorded from the build before the trainers' host code was shared; the memories' blocks are in every vector."""
+    check_golden("ppo_rnn_h20_t3_n17_last", golden_recurrent(hip_lib))
 
 
 # ---- 5. refusals -------------------------------------------------------------------------------------------------------------------------------

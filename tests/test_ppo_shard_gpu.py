@@ -345,3 +345,23 @@ def test_bad_shard_arguments_return_a_status_and_launch_nothing(hip_lib):
     for name, x, y in zip(("params", "grads", "m", "v", "stats"), before, after):
         assert np.array_equal(x, y), f"a refused call must not have launched anything: {name}"
     assert bool((rec == 7.0).all()), "a refused call must not have written the record"
+
+
+# ---- the bits of the build before the trainers' host code was shared (tools/record_ppo_plain_golden.py) --------------------------------------------
+def golden_two_shard_records(lib):
+    from test_ppo_gpu import bits32
+
+    sides = shard_sides(lib, PC.get_case("small", 37, "keep"), [17, 20])
+    records = sharded_grad(sides, 37)
+    side = sides[0]
+    out = {"records": records.cpu().numpy().view(np.int64).copy(), "grads_padded": bits32(side.h.export_padded("GRADS")),
+           "stats_reduce": side.stats()[1].numpy().view(np.int64).copy()}
+    side.h.apply(side.std)
+    out["params"] = bits32(side.h.export("PARAMS", side.std))
+    return out
+
+
+def test_two_shard_records_have_the_parent_builds_bits(hip_lib):
+    from test_ppo_gpu import check_golden
+
+    check_golden("ppo_shard_small_37_17_20", golden_two_shard_records(hip_lib))

@@ -298,3 +298,19 @@ def test_runner_trains_with_symmetry_and_reproduces():
     assert out[0][0] == out[1][0]
     for k, v in out[0][1].items():
         assert np.array_equal(v.numpy().view(np.int32), out[1][1][k].numpy().view(np.int32)), k
+
+
+# ---- the bits of the build before the trainers' host code was shared (tools/record_ppo_plain_golden.py) --------------------------------------------
+def golden_mirror_both(lib):
+    from test_ppo_gpu import grad_and_apply_bits
+
+    side = case_side(lib, SC.get_case("small", 17), "both")
+    side.h.minibatch_grad(side.batch, side.std, side.idx)
+    sym = side.h.symmetry_loss().cpu().numpy().view(np.int64).copy()
+    return dict(grad_and_apply_bits(side.h, side.std), symmetry_loss=sym)
+
+
+def test_mirror_path_has_the_parent_builds_bits(hip_lib):
+    from test_ppo_gpu import check_golden
+
+    check_golden("ppo_mirror_small_17_both", golden_mirror_both(hip_lib))

@@ -1,10 +1,14 @@
-"""Records the bits tests/test_ppo_rnn_gpu.py::test_plain_path_has_the_parent_builds_bits compares against: one go2sim_ppo_minibatch_grad and one
-go2sim_ppo_apply of a handle WITHOUT memories on the tests/ppo_cases.py case ("small", 37, "keep"), run against a given build of the library.
+"""Records the bits the "... has_the_parent_builds_bits" GPU tests compare against, run against a given build of the library.
 
-    python tools/record_ppo_plain_golden.py --lib path/to/libgo2sim.so [--out tests/golden/ppo_plain_small_37_keep.npz]
+    python tools/record_ppo_plain_golden.py --lib path/to/libgo2sim.so [--case NAME | --case all] [--out FILE | --out-dir DIR]
 
-The file in tests/golden/ was recorded from the build of the commit before the recurrent policy was added."""
+Without --case: the first fixture, tests/golden/ppo_plain_small_37_keep.npz (one go2sim_ppo_minibatch_grad and one go2sim_ppo_apply of a handle WITHOUT
+memories on the tests/ppo_cases.py case ("small", 37, "keep")); the file in tests/golden/ was recorded from the build of the commit before the recurrent
+policy was added.  The other cases are one small update per path of the PPO and the distillation trainers; each is the function of the GPU test file of
+its path that the test itself calls (public handle API and the generators of tests/*_cases.py only).  Their files were recorded from the build of the
+commit before the two trainers' host code was put on one shared core.  With --check the arrays are compared with the existing file instead of written."""
 import argparse
+import importlib
 import os
 import sys
 
@@ -13,18 +17,24 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
+# case (the fixture's file name) -> (test module, function(lib) -> {name: integer view})
+CASES = {
+    "ppo_plain_small_37_keep": (None, None),
+    "ppo_plain_unequal_depth_17": ("test_ppo_gpu", "golden_plain_unequal_depth"),
+    "ppo_plain_small_1061_down": ("test_ppo_gpu", "golden_plain_row_chunks"),
+    "ppo_mirror_small_17_both": ("test_ppo_sym_gpu", "golden_mirror_both"),
+    "ppo_shard_small_37_17_20": ("test_ppo_shard_gpu", "golden_two_shard_records"),
+    "ppo_rnn_h20_t3_n17_last": ("test_ppo_rnn_gpu", "golden_recurrent"),
+    "distill_small_37_3_mse_plain": ("test_distill_gpu", "golden_window"),
+    "distill_six_layers_37_3_huber_dup": ("test_distill_gpu", "golden_window"),
+    "distill_small_1061_chunks": ("test_distill_gpu", "golden_window_across_chunks"),
+}
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--lib", required=True)
-    ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "ppo_plain_small_37_keep.npz"))
-    args = ap.parse_args()
+
+def record_first(lib):
     import ppo_cases as PC
     from test_ppo_gpu import DEV, case_side
 
-    from go2_sim2real_locomotion_rl_amd.capi import Go2SimLib
-
-    lib = Go2SimLib(os.path.abspath(args.lib), "go2sim_")
     c = PC.get_case("small", 37, "keep")
     side = case_side(lib, c)
     side.h.minibatch_grad(side.batch, side.std, c.idx.to(DEV))
@@ -34,9 +44,47 @@ def main():
     out["adam_m"] = side.h.export_padded("ADAM_M").cpu().numpy().view(np.int32)
     out["adam_v"] = side.h.export_padded("ADAM_V").cpu().numpy().view(np.int32)
     out["stats_apply"] = side.stats()[1].numpy().view(np.int64)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    np.savez_compressed(args.out, **out)
-    print("recorded", {k: v.shape for k, v in out.items()}, "->", args.out)
+    return out
+
+
+def record(lib, case):
+    module, fn = CASES[case]
+    if module is None:
+        return record_first(lib)
+    mod = importlib.import_module(module)
+    if fn == "golden_window":
+        return mod.golden_window(lib, mod.GOLDEN_WINDOWS[case])
+    return getattr(mod, fn)(lib)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lib", required=True)
+    ap.add_argument("--case", default="ppo_plain_small_37_keep", choices=sorted(CASES) + ["all"])
+    ap.add_argument("--out", default=None, help="file of a single case (default: <out-dir>/<case>.npz)")
+    ap.add_argument("--out-dir", default=os.path.join(ROOT, "tests", "golden"))
+    ap.add_argument("--check", action="store_true", help="compare with the existing file, array for array, and write nothing")
+    args = ap.parse_args()
+    from go2_sim2real_locomotion_rl_amd.capi import Go2SimLib
+
+    lib = Go2SimLib(os.path.abspath(args.lib), "go2sim_")
+    cases = list(CASES) if args.case == "all" else [args.case]
+    if args.out and len(cases) > 1:
+        ap.error("--out names one file; use --out-dir with --case all")
+    bad = 0
+    for case in cases:
+        out = record(lib, case)
+        path = args.out or os.path.join(args.out_dir, case + ".npz")
+        if args.check:
+            want = np.load(path)
+            same = set(want.files) == set(out) and all(np.array_equal(out[k], want[k]) for k in out)
+            print("check", case, "identical" if same else "DIFFERENT", path)
+            bad += not same
+            continue
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        np.savez_compressed(path, **out)
+        print("recorded", case, {k: v.shape for k, v in out.items()}, "->", path)
+    sys.exit(1 if bad else 0)
 
 
 if __name__ == "__main__":
