@@ -2120,11 +2120,27 @@ DEV V3 support_prism(const V3* prism, V3 d) {
 // type and size of a geom, read once per pair so that the MPR iterations do not go back to the model in global memory
 struct GeomLite { int type; float d0, d1, d2; };
 DEV GeomLite geom_lite(const GeomK* gk, int i_g) { const GeomK& G = gk[i_g]; GeomLite r = {G.type, G.data[0], G.data[1], G.data[2]}; return r; }   // gk: the geom table, in LDS (k_collide_team) or global (m.gk)
+// The class of a pair: what the narrow-phase query code is compiled for.  PC_GENERIC is the run-time switch over the geom types.  A sphere against a
+// box -- every query of the walking robot: a foot on the ground box -- has its own instantiation of the same source, in which the two sides' support
+// functions are known at compile time: nothing of the other types is compiled in, no branch stands between the two supports of a pair, and the sphere
+// keeps no rotation.  The operands stay in the pair's order, so the class comes in two values, by the side the sphere is on (k_collide_team sorts a
+// pair by type, its sphere is operand a; go2sim_debug_narrowphase takes either order).  The expressions are the generic ones (conditions that are
+// constants of the instantiation select among them, none exists twice), so the answer is the same bit for bit.
+enum PairClass { PC_GENERIC = 0, PC_SPHERE_BOX = 1, PC_BOX_SPHERE = 2 };
+DEV constexpr bool pc_side_is_sphere(PairClass pc, int side) { return (pc == PC_SPHERE_BOX && side == 0) || (pc == PC_BOX_SPHERE && side == 1); }
+DEV constexpr bool pc_side_is_box(PairClass pc, int side) { return (pc == PC_SPHERE_BOX && side == 1) || (pc == PC_BOX_SPHERE && side == 0); }
+DEV PairClass pair_class(int type_a, int type_b) {
+  if (type_a == GEOM_SPHERE && type_b == GEOM_BOX) return PC_SPHERE_BOX;
+  if (type_a == GEOM_BOX && type_b == GEOM_SPHERE) return PC_BOX_SPHERE;
+  return PC_GENERIC;                                                    // terrain prisms, planes, cylinders, sphere - sphere, box - box
+}
+// SIDE: 0 = operand a of the pair, 1 = operand b
+template <PairClass PC = PC_GENERIC, int SIDE = 0>
 DEV V3 support_driver(const Model& m, V3 direction, int i_g, const GeomLite& gl, V3 pos, const Rot& rot, const V3* prism = nullptr) {
-  if (gl.type == GEOM_TERRAIN) return support_prism(prism, direction);
-  if (gl.type == GEOM_SPHERE) {
+  if constexpr (PC == PC_GENERIC) { if (gl.type == GEOM_TERRAIN) return support_prism(prism, direction); }
+  if (pc_side_is_sphere(PC, SIDE) || (PC == PC_GENERIC && gl.type == GEOM_SPHERE)) {
     return pos + direction * gl.d0;
-  } else if (gl.type == GEOM_BOX) {
+  } else if (pc_side_is_box(PC, SIDE) || (PC == PC_GENERIC && gl.type == GEOM_BOX)) {
     V3 d_box = rot_apply_inv(rot, direction);
     V3 v_ = v3((d_box.x < 0.0f ? -1.0f : 1.0f) * gl.d0 * 0.5f, (d_box.y < 0.0f ? -1.0f : 1.0f) * gl.d1 * 0.5f,
                (d_box.z < 0.0f ? -1.0f : 1.0f) * gl.d2 * 0.5f);
@@ -2137,11 +2153,16 @@ DEV V3 support_driver(const Model& m, V3 direction, int i_g, const GeomLite& gl,
   return pos;   // a plane has no support point: its pairs never reach MPR or GJK (plane_contact, plane_box_contact_staged)
 }
 struct Pair { int i_ga, i_gb; V3 pos_a; Q4 quat_a; V3 pos_b; Q4 quat_b; const V3* prism; GeomLite ga, gb; Rot ra, rb; };   // ra / rb = make_rot(quat_a / quat_b)
-DEV void pair_set_rots(Pair& pr) { pr.ra = make_rot(pr.quat_a); pr.rb = make_rot(pr.quat_b); }
+template <PairClass PC = PC_GENERIC>
+DEV void pair_set_rots(Pair& pr) {                                      // (a side known to be a sphere keeps no rotation: no expression of a sphere reads it)
+  if constexpr (!pc_side_is_sphere(PC, 0)) pr.ra = make_rot(pr.quat_a);
+  if constexpr (!pc_side_is_sphere(PC, 1)) pr.rb = make_rot(pr.quat_b);
+}
 // compute_support, collider/mpr.py:179-202
+template <PairClass PC = PC_GENERIC>
 DEV void compute_support(const Model& m, V3 direction, const Pair& pr, V3& v, V3& v1, V3& v2) {
-  v1 = support_driver(m, direction, pr.i_ga, pr.ga, pr.pos_a, pr.ra);
-  v2 = support_driver(m, -direction, pr.i_gb, pr.gb, pr.pos_b, pr.rb, pr.prism);
+  v1 = support_driver<PC, 0>(m, direction, pr.i_ga, pr.ga, pr.pos_a, pr.ra);
+  v2 = support_driver<PC, 1>(m, -direction, pr.i_gb, pr.gb, pr.pos_b, pr.rb, pr.prism);
   v = v1 - v2;
 }
 
@@ -2150,11 +2171,12 @@ DEV void compute_support(const Model& m, V3 direction, const Pair& pr, V3& v, V3
 //      gjk.py:1652-1700,1854-1907.  Vertex ids only need to be unique per (geom, vertex): 64 ids are reserved per geom. ----
 // (type and size of the geom come from the per-pair GeomLite record: a GJK / EPA query makes some sixty support calls, and fetching them from
 //  the model in global memory every time put a dependent load in front of each one)
+template <PairClass PC = PC_GENERIC, int SIDE = 0>
 DEV V3 gjk_support_driver(const Model& m, V3 direction, int i_g, const GeomLite& gl, V3 pos, const Rot& rot, int& vid) {
-  if (gl.type == GEOM_SPHERE) {
+  if (pc_side_is_sphere(PC, SIDE) || (PC == PC_GENERIC && gl.type == GEOM_SPHERE)) {
     vid = -1;
     return pos + direction * gl.d0;
-  } else if (gl.type == GEOM_BOX) {
+  } else if (pc_side_is_box(PC, SIDE) || (PC == PC_GENERIC && gl.type == GEOM_BOX)) {
     V3 d_box = rot_apply_inv(rot, direction);
     V3 v_ = v3((d_box.x < 0.0f ? -1.0f : 1.0f) * gl.d0 * 0.5f, (d_box.y < 0.0f ? -1.0f : 1.0f) * gl.d1 * 0.5f,
                (d_box.z < 0.0f ? -1.0f : 1.0f) * gl.d2 * 0.5f);
@@ -2230,6 +2252,7 @@ DEV bool mpr_first_support_separates(const Model& m, const Pair& pr, V3 center_a
   return dot(v, direction) < EPSC;
 }
 // mpr_discover_portal, mpr.py:445-598
+template <PairClass PC = PC_GENERIC>
 DEV int mpr_discover_portal(const Model& m, Simplex& s, const Pair& pr, V3 center_a, V3 center_b) {
   const float EPSC = m.ccd_eps;
   s.v1[0] = center_a; s.v2[0] = center_b; s.v[0] = center_a - center_b;
@@ -2237,7 +2260,7 @@ DEV int mpr_discover_portal(const Model& m, Simplex& s, const Pair& pr, V3 cente
   if (dm_abs(s.v[0].x) < EPSC && dm_abs(s.v[0].y) < EPSC && dm_abs(s.v[0].z) < EPSC) s.v[0].x += 10.0f * EPSC;
   V3 direction = -normalized(s.v[0]);
   V3 v, v1, v2;
-  compute_support(m, direction, pr, v, v1, v2);
+  compute_support<PC>(m, direction, pr, v, v1, v2);
   s.v1[1] = v1; s.v2[1] = v2; s.v[1] = v;
   simplex_size = 2;
   float d = dot(v, direction);
@@ -2250,7 +2273,7 @@ DEV int mpr_discover_portal(const Model& m, Simplex& s, const Pair& pr, V3 cente
       if (dm_abs(s.v[1].x) < EPSC && dm_abs(s.v[1].y) < EPSC && dm_abs(s.v[1].z) < EPSC) ret = 1; else ret = 2;
     } else {
       direction = normalized(direction);
-      compute_support(m, direction, pr, v, v1, v2);
+      compute_support<PC>(m, direction, pr, v, v1, v2);
       d = dot(v, direction);
       if (d < EPSC) {
         ret = -1;
@@ -2267,7 +2290,7 @@ DEV int mpr_discover_portal(const Model& m, Simplex& s, const Pair& pr, V3 cente
         }
         int num_trials = 0;
         while (simplex_size < 4) {
-          compute_support(m, direction, pr, v, v1, v2);
+          compute_support<PC>(m, direction, pr, v, v1, v2);
           d = dot(v, direction);
           if (d < EPSC) { ret = -1; break; }
           bool cont = false;
@@ -2295,13 +2318,14 @@ DEV int mpr_discover_portal(const Model& m, Simplex& s, const Pair& pr, V3 cente
   return ret;
 }
 // mpr_refine_portal, mpr.py:232-278
+template <PairClass PC = PC_GENERIC>
 DEV int mpr_refine_portal(const Model& m, Simplex& s, const Pair& pr) {
   int ret = 1;
   while (true) {
     V3 direction = mpr_portal_dir(s);
     if (dot(s.v[1], direction) > -m.ccd_eps) { ret = 0; break; }
     V3 v, v1, v2;
-    compute_support(m, direction, pr, v, v1, v2);
+    compute_support<PC>(m, direction, pr, v, v1, v2);
     if (!(dot(v, direction) > -m.ccd_eps) || mpr_portal_reach_tolerance(m, s, v, direction)) { ret = -1; break; }
     mpr_expand_portal(s, v, v1, v2);
   }
@@ -2327,12 +2351,13 @@ DEV V3 mpr_find_pos(const Model& m, const Simplex& s) {
   return (0.5f / sum_) * (p1 + p2);
 }
 // mpr_find_penetration, mpr.py:338-423
+template <PairClass PC = PC_GENERIC>
 DEV void mpr_find_penetration(const Model& m, Simplex& s, const Pair& pr, bool& is_col, V3& normal, float& penetration, V3& pos) {
   int iterations = 0;
   while (true) {
     V3 direction = mpr_portal_dir(s);
     V3 v, v1, v2;
-    compute_support(m, direction, pr, v, v1, v2);
+    compute_support<PC>(m, direction, pr, v, v1, v2);
     if (mpr_portal_reach_tolerance(m, s, v, direction) || iterations > m.ccd_iterations) {
       penetration = dot(direction, s.v[1]);
       normal = -direction;
@@ -2374,23 +2399,25 @@ DEV void guess_geoms_center(const Model& m, const GeomK* gk, const Pair& pr, V3 
 }
 // func_mpr_contact -> func_mpr_contact_from_centers, mpr.py:686-819
 // func_mpr_contact_from_centers, mpr.py:686-760
+template <PairClass PC = PC_GENERIC>
 DEV void mpr_contact_from_centers(const Model& m, const Pair& pr, V3 center_a, V3 center_b, bool& is_col, V3& normal, float& penetration, V3& pos) {
   Simplex s;
-  int res = mpr_discover_portal(m, s, pr, center_a, center_b);
+  int res = mpr_discover_portal<PC>(m, s, pr, center_a, center_b);
   is_col = false; pos = v3(0, 0, 0); normal = v3(0, 0, 0); penetration = 0.0f;
   if (res == 1) {
     is_col = true; penetration = 0.0f; normal = -normalized(s.v[0]); pos = (s.v1[1] + s.v2[1]) * 0.5f;
   } else if (res == 2) {
     is_col = true; penetration = norm(s.v[1]); normal = -normalized(s.v[1]); pos = (s.v1[1] + s.v2[1]) * 0.5f;
   } else if (res == 0) {
-    res = mpr_refine_portal(m, s, pr);
-    if (res >= 0) mpr_find_penetration(m, s, pr, is_col, normal, penetration, pos);
+    res = mpr_refine_portal<PC>(m, s, pr);
+    if (res >= 0) mpr_find_penetration<PC>(m, s, pr, is_col, normal, penetration, pos);
   }
 }
+template <PairClass PC = PC_GENERIC>
 DEV void mpr_contact(const Model& m, const GeomK* gk, const Pair& pr, V3 normal_ws, bool& is_col, V3& normal, float& penetration, V3& pos) {
   V3 center_a, center_b;
   guess_geoms_center(m, gk, pr, normal_ws, center_a, center_b);
-  mpr_contact_from_centers(m, pr, center_a, center_b, is_col, normal, penetration, pos);
+  mpr_contact_from_centers<PC>(m, pr, center_a, center_b, is_col, normal, penetration, pos);
 }
 
 // func_compute_tolerance, contact.py:264-283
@@ -2528,6 +2555,7 @@ DEV PairIn load_pair_in(const E& e, int i_ga, int i_gb, int i_pair) {
 }
 // normal_ws: the pair's normal-cache entry as the detection finds it -- the entry of the last narrow phase (masked by its valid bit) for detection 0,
 // and for a perturbed detection the normal detection 0 has just stored there (cc_rest)
+template <PairClass PC = PC_GENERIC>
 DEV void cc_mpr_with_retry(const Model& m, const GeomK* gk, CcState& c, int i_detection, V3 normal_ws, bool& guess_available) {
   const float EPS = m.eps;
   bool is_mpr_updated = false;
@@ -2538,7 +2566,7 @@ DEV void cc_mpr_with_retry(const Model& m, const GeomK* gk, CcState& c, int i_de
     }
     if (!is_mpr_updated) {
       PHD_BEGIN
-      mpr_contact(m, gk, c.pr, normal_ws, c.is_col, c.normal, c.penetration, c.contact_pos);
+      mpr_contact<PC>(m, gk, c.pr, normal_ws, c.is_col, c.normal, c.penetration, c.contact_pos);
       PHD(36)
       is_mpr_updated = true;
     }
@@ -2549,6 +2577,7 @@ DEV bool cc_prefer_gjk(const Model& m, const CcState& c, bool guess_available) {
   return false;
 }
 // i_pair = m.pair_idx of the pair (it travels with the broad-phase list); in = load_pair_in of (i_ga, i_gb, i_pair)
+template <PairClass PC = PC_GENERIC>
 DEV void cc_detect0(const Model& m, const GeomK* gk, const E& e, int i_ga, int i_gb, int i_pair, const PairIn& in, unsigned* ncv, CcState& c) {
   c.type_a = gk[i_ga].type; c.type_b = gk[i_gb].type;
   c.multi_contact = (c.type_a != GEOM_SPHERE) && (c.type_b != GEOM_SPHERE);
@@ -2557,16 +2586,18 @@ DEV void cc_detect0(const Model& m, const GeomK* gk, const E& e, int i_ga, int i
   c.ga_pos_o = in.pos_a; c.gb_pos_o = in.pos_b; c.ga_quat_o = in.quat_a; c.gb_quat_o = in.quat_b;
   Pair& pr = c.pr;
   pr.i_ga = i_ga; pr.i_gb = i_gb; pr.pos_a = c.ga_pos_o; pr.quat_a = c.ga_quat_o; pr.pos_b = c.gb_pos_o; pr.quat_b = c.gb_quat_o; pr.prism = nullptr; pr.ga = geom_lite(gk, i_ga); pr.gb = geom_lite(gk, i_gb);
-  pair_set_rots(pr);
+  pair_set_rots<PC>(pr);
   c.is_col = false; c.penetration = 0.0f; c.normal = v3(0, 0, 0); c.contact_pos = v3(0, 0, 0);
   c.i_pair = i_pair;
-  if (c.type_a == GEOM_PLANE) {                                  // plane pairs never vote for GJK / EPA
-    plane_contact(m, pr, c.is_col, c.normal, c.penetration, c.contact_pos);
-    c.want_gjk = false;
-    return;
+  if constexpr (PC == PC_GENERIC) {
+    if (c.type_a == GEOM_PLANE) {                                // plane pairs never vote for GJK / EPA
+      plane_contact(m, pr, c.is_col, c.normal, c.penetration, c.contact_pos);
+      c.want_gjk = false;
+      return;
+    }
   }
   bool guess_available;
-  cc_mpr_with_retry(m, gk, c, 0, ((ncv[i_pair >> 5] >> (i_pair & 31)) & 1u) ? in.ncache : v3(0, 0, 0), guess_available);
+  cc_mpr_with_retry<PC>(m, gk, c, 0, ((ncv[i_pair >> 5] >> (i_pair & 31)) & 1u) ? in.ncache : v3(0, 0, 0), guess_available);
   c.want_gjk = cc_prefer_gjk(m, c, guess_available);
 }
 // narrowphase.py:734-845: safe GJK + EPA replaces the MPR answer (one lane; LDS polytope slot when `gjk_slots` is given, else the global record)
@@ -2778,8 +2809,27 @@ DEV bool terrain_prism_contact(const Model& m, const GeomK* gk, const E& e, cons
   return is_col;
 }
 
+// One safe GJK + EPA query answered by the four lanes of a quad (ql = lane within the quad) on the quad's LDS polytope slot; a query that outgrows the
+// slot is repeated on the full-capacity record in global memory.  gk: the geom table (LDS in k_collide_team, global in k_debug_narrowphase).
+template <PairClass PC, class SLOT>
+DEV DgResult quad_gjk_query(const Model* mp, const GeomK* gk, int i_ga, int i_gb, V3 pos_a, Q4 quat_a, V3 pos_b, Q4 quat_b, SLOT& slot, GjkStoreFull& full, int ql) {
+  DgPairT<PC> dp;
+  dp.m = mp; dp.i_ga = i_ga; dp.i_gb = i_gb; dp.pos_a = pos_a; dp.quat_a = quat_a; dp.pos_b = pos_b; dp.quat_b = quat_b;
+  dp.ga = geom_lite(gk, i_ga); dp.gb = geom_lite(gk, i_gb);
+  if constexpr (!pc_side_is_sphere(PC, 0)) dp.ra = make_rot(quat_a);
+  if constexpr (!pc_side_is_sphere(PC, 1)) dp.rb = make_rot(quat_b);
+  dp.discrete = dp.ga.type == GEOM_BOX && dp.gb.type == GEOM_BOX;        // func_is_discrete_geoms, collider/utils.py:105-126
+  PHD_BEGIN
+  DgResult gr = dgc_contact<4>(dp, slot, mp->eps, ql);
+  if (gr.overflow) gr = dgc_contact<4>(dp, full, mp->eps, ql);           // outgrew the slot: the same query on the full-capacity record
+  PHD(34)
+  return gr;
+}
+
+// collide_flags: COLLIDE_GENERIC = every wave takes the PC_GENERIC instantiation (GO2SIM_COLLIDE_GENERIC=1: one binary compared with itself)
+constexpr int COLLIDE_GENERIC = 1;
 template <int T>
-__global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __restrict__ mp, const GeomK* __restrict__ gkp, GjkStoreFull* __restrict__ gjk_scratch, int* __restrict__ lpt_rec, int lpt_cap, int solver_epw) {
+__global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __restrict__ mp, const GeomK* __restrict__ gkp, GjkStoreFull* __restrict__ gjk_scratch, int* __restrict__ lpt_rec, int lpt_cap, int solver_epw, int collide_flags) {
   STAMP(STK_COLLIDE)
   constexpr int EPW = 64 / T;                                           // environments per wavefront
   __shared__ CollideData<T> lds[EPW];
@@ -2890,7 +2940,13 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
       static_assert(GJK_SLOTS >= 4, "one LDS polytope slot per quad");
       CcState cst;
       cst.want_gjk = false;
-      if (convex_pair) cc_detect0(m, gk, e, i_ga, i_gb, i_pair, pin, s->ncv, cst);
+      // The class of the round, one per WAVE: when every pair of the wave's (up to four) teams is a sphere against a box -- the walking robot: feet on
+      // the ground -- the wave runs the PC_SPHERE_BOX instantiation of the MPR queries and of the fallback quads, otherwise (one pair of another class
+      // is enough) the generic one, as a whole: never both one after the other, which would lengthen the wave everything waits for.
+      const bool other_class = convex_pair && pair_class(gk[i_ga].type, gk[i_gb].type) != PC_SPHERE_BOX;
+      const bool wave_sphere_box = !(collide_flags & COLLIDE_GENERIC) && __ballot(other_class) == 0ull;
+      if (wave_sphere_box) { if (convex_pair) cc_detect0<PC_SPHERE_BOX>(m, gk, e, i_ga, i_gb, i_pair, pin, s->ncv, cst); }
+      else if (convex_pair) cc_detect0<PC_GENERIC>(m, gk, e, i_ga, i_gb, i_pair, pin, s->ncv, cst);
       const bool wants = convex_pair && cst.want_gjk;
       const unsigned want = dgc_ballot<16>(wants);
       const int n_want = __popc(want), quad = tl >> 2, ql = tl & 3;
@@ -2899,19 +2955,15 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
         for (int k = 0; k < r0 + quad; ++k) rest &= rest - 1u;           // drop the pairs taken by earlier rounds / lower quads
         const int L = rest ? __ffs((int)rest) - 1 : -1;                  // the lane whose pair my quad answers in this round
         const int Ls = L < 0 ? tl : L;
-        DgPair dp;                                                       // (all 16 lanes shuffle: the source lanes have to be active)
-        dp.m = mp; dp.i_ga = __shfl(i_ga, Ls, 16); dp.i_gb = __shfl(i_gb, Ls, 16);
-        dp.pos_a = v3(__shfl(cst.pr.pos_a.x, Ls, 16), __shfl(cst.pr.pos_a.y, Ls, 16), __shfl(cst.pr.pos_a.z, Ls, 16));
-        dp.quat_a = q4(__shfl(cst.pr.quat_a.w, Ls, 16), __shfl(cst.pr.quat_a.x, Ls, 16), __shfl(cst.pr.quat_a.y, Ls, 16), __shfl(cst.pr.quat_a.z, Ls, 16));
-        dp.pos_b = v3(__shfl(cst.pr.pos_b.x, Ls, 16), __shfl(cst.pr.pos_b.y, Ls, 16), __shfl(cst.pr.pos_b.z, Ls, 16));
-        dp.quat_b = q4(__shfl(cst.pr.quat_b.w, Ls, 16), __shfl(cst.pr.quat_b.x, Ls, 16), __shfl(cst.pr.quat_b.y, Ls, 16), __shfl(cst.pr.quat_b.z, Ls, 16));
+        const int q_ga = __shfl(i_ga, Ls, 16), q_gb = __shfl(i_gb, Ls, 16);   // (all 16 lanes shuffle: the source lanes have to be active)
+        const V3 q_pos_a = v3(__shfl(cst.pr.pos_a.x, Ls, 16), __shfl(cst.pr.pos_a.y, Ls, 16), __shfl(cst.pr.pos_a.z, Ls, 16));
+        const Q4 q_quat_a = q4(__shfl(cst.pr.quat_a.w, Ls, 16), __shfl(cst.pr.quat_a.x, Ls, 16), __shfl(cst.pr.quat_a.y, Ls, 16), __shfl(cst.pr.quat_a.z, Ls, 16));
+        const V3 q_pos_b = v3(__shfl(cst.pr.pos_b.x, Ls, 16), __shfl(cst.pr.pos_b.y, Ls, 16), __shfl(cst.pr.pos_b.z, Ls, 16));
+        const Q4 q_quat_b = q4(__shfl(cst.pr.quat_b.w, Ls, 16), __shfl(cst.pr.quat_b.x, Ls, 16), __shfl(cst.pr.quat_b.y, Ls, 16), __shfl(cst.pr.quat_b.z, Ls, 16));
         if (L >= 0) {
-          dp.ga = geom_lite(gk, dp.i_ga); dp.gb = geom_lite(gk, dp.i_gb); dp.ra = make_rot(dp.quat_a); dp.rb = make_rot(dp.quat_b);
-          dp.discrete = dp.ga.type == GEOM_BOX && dp.gb.type == GEOM_BOX;  // func_is_discrete_geoms, collider/utils.py:105-126
-          PHD_BEGIN
-          DgResult gr = dgc_contact<4>(dp, s->gjk[quad], m.eps, ql);
-          if (gr.overflow) gr = dgc_contact<4>(dp, gjk_scratch[(size_t)b * T + L], m.eps, ql);   // outgrew the LDS slot: the same query on the full-capacity record
-          PHD(34)
+          GjkStoreFull& q_full = gjk_scratch[(size_t)b * T + L];
+          const DgResult gr = wave_sphere_box ? quad_gjk_query<PC_SPHERE_BOX>(mp, gk, q_ga, q_gb, q_pos_a, q_quat_a, q_pos_b, q_quat_b, s->gjk[quad], q_full, ql)
+                                              : quad_gjk_query<PC_GENERIC>(mp, gk, q_ga, q_gb, q_pos_a, q_quat_a, q_pos_b, q_quat_b, s->gjk[quad], q_full, ql);
           if (ql == 0) {
             float* o = s->gjk_res[L];
             o[0] = gr.is_col ? 1.0f : 0.0f; o[1] = gr.penetration; o[2] = gr.normal.x; o[3] = gr.normal.y; o[4] = gr.normal.z; o[5] = gr.pos.x; o[6] = gr.pos.y; o[7] = gr.pos.z;
@@ -4580,7 +4632,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 // diagnostics (go2sim_debug_narrowphase): one narrow-phase query on explicit poses, by one lane.  which = 0: MPR from a cold start
 // (func_mpr_contact, mpr.py:763-819); 1: safe GJK + EPA the way k_collide_team runs it (LDS polytope slot, global record on overflow);
 // 2: safe GJK + EPA on the full-capacity global record only; 3 / 4: the cooperative form k_collide_team<16> runs (the 4 lanes of a quad answer the
-// query together) on an LDS slot / on the global record; 5 / 6: the same with 16 lanes per query.  out = {is_col, penetration, normal[3], pos[3]}
+// query together) on an LDS slot / on the global record; 5 / 6: the same with 16 lanes per query; 7 / 8: which = 0 / which = 3 in the pair's own class
+// instantiation (PC_SPHERE_BOX or PC_BOX_SPHERE by the operand order; the host refuses any other pair): the code a wave of sphere-box pairs runs in
+// k_collide_team, to be compared with the generic answer on the same poses.  out = {is_col, penetration, normal[3], pos[3]}
 __global__ __launch_bounds__(64) void k_debug_narrowphase(const Model* __restrict__ mp, int which, int i_ga, int i_gb, V3 pa, Q4 qa, V3 pb, Q4 qb,
                                                           GjkStoreFull* __restrict__ full, float* __restrict__ out8) {
   __shared__ GjkStoreLds slots[GJK_SLOTS_MAX];
@@ -4590,7 +4644,15 @@ __global__ __launch_bounds__(64) void k_debug_narrowphase(const Model* __restric
   __syncthreads();
   const Model& m = *mp;
   bool is_col = false; V3 normal = v3(0, 0, 0), pos = v3(0, 0, 0); float pen = 0.0f;
-  if (which >= 3) {
+  if (which == 8) {
+    if (threadIdx.x >= 4) return;
+    const DgResult r = pair_class(m.gk[i_ga].type, m.gk[i_gb].type) == PC_SPHERE_BOX ? quad_gjk_query<PC_SPHERE_BOX>(mp, m.gk, i_ga, i_gb, pa, qa, pb, qb, slots[0], *full, (int)threadIdx.x)
+                                                                                     : quad_gjk_query<PC_BOX_SPHERE>(mp, m.gk, i_ga, i_gb, pa, qa, pb, qb, slots[0], *full, (int)threadIdx.x);
+    if (threadIdx.x != 0) return;
+    out8[0] = r.is_col ? 1.0f : 0.0f; out8[1] = r.penetration; out8[2] = r.normal.x; out8[3] = r.normal.y; out8[4] = r.normal.z; out8[5] = r.pos.x; out8[6] = r.pos.y; out8[7] = r.pos.z;
+    return;
+  }
+  if (which >= 3 && which <= 6) {
     if (threadIdx.x >= 16) return;
     DgPair dp; dp.m = mp; dp.i_ga = i_ga; dp.i_gb = i_gb; dp.pos_a = pa; dp.quat_a = qa; dp.pos_b = pb; dp.quat_b = qb;
     dp.ga = geom_lite(m.gk, i_ga); dp.gb = geom_lite(m.gk, i_gb); dp.ra = make_rot(qa); dp.rb = make_rot(qb);
@@ -4610,10 +4672,18 @@ __global__ __launch_bounds__(64) void k_debug_narrowphase(const Model* __restric
     return;
   }
   if (threadIdx.x != 0) return;
-  if (which == 0) {
+  if (which == 0 || which == 7) {
     Pair pr; pr.i_ga = i_ga; pr.i_gb = i_gb; pr.pos_a = pa; pr.quat_a = qa; pr.pos_b = pb; pr.quat_b = qb; pr.prism = nullptr; pr.ga = geom_lite(m.gk, i_ga); pr.gb = geom_lite(m.gk, i_gb);
-    pair_set_rots(pr);
-    mpr_contact(m, m.gk, pr, v3(0, 0, 0), is_col, normal, pen, pos);
+    if (which == 0) {
+      pair_set_rots(pr);
+      mpr_contact(m, m.gk, pr, v3(0, 0, 0), is_col, normal, pen, pos);
+    } else if (pair_class(pr.ga.type, pr.gb.type) == PC_SPHERE_BOX) {
+      pair_set_rots<PC_SPHERE_BOX>(pr);
+      mpr_contact<PC_SPHERE_BOX>(m, m.gk, pr, v3(0, 0, 0), is_col, normal, pen, pos);
+    } else {
+      pair_set_rots<PC_BOX_SPHERE>(pr);
+      mpr_contact<PC_BOX_SPHERE>(m, m.gk, pr, v3(0, 0, 0), is_col, normal, pen, pos);
+    }
   } else {
     DgPair dp; dp.m = mp; dp.i_ga = i_ga; dp.i_gb = i_gb; dp.pos_a = pa; dp.quat_a = qa; dp.pos_b = pb; dp.quat_b = qb;
     dp.ga = geom_lite(m.gk, i_ga); dp.gb = geom_lite(m.gk, i_gb); dp.ra = make_rot(qa); dp.rb = make_rot(qb);
@@ -6421,6 +6491,7 @@ struct go2sim {
   int dyn_team = 32;                        // lanes per environment in k_dynamics_team
   int fk_team = 16;                         // lanes per environment in k_integrate_fk_team / k_fk_team
   int collide_team = 16;                    // lanes per environment in k_collide_team
+  bool collide_generic = false;             // GO2SIM_COLLIDE_GENERIC=1: k_collide_team takes the generic narrow-phase instantiation for every wave (diagnostic: one binary against itself)
   int solver_team = 32;                     // lanes per environment in k_constraint_solve_team
   int terrain_solver_team = 64;             // ... on heightfield terrain (96 LDS rows)
   uint32_t step_count = 0; int action_write_idx = 0;
@@ -6610,7 +6681,7 @@ static void build_launch_list(const go2sim* h, LaunchList& L, int n, const StepI
     const bool more = i + 1 < n;
     int* lpt_cur = lpt_on ? h->lpt + ((lpt0 + i) & 1) * lpt_record_ints(h) : nullptr;
     int* lpt_next = lpt_on ? h->lpt + ((lpt0 + i + 1) & 1) * lpt_record_ints(h) : nullptr;
-    add_launch(L, T_COLLIDE, collide_kernel(h->collide_team), team_grid(h, h->collide_team), b, h->P, h->dm, h->dgk, h->gjk_scratch, lpt_cur, h->lpt_cap, solver_epw(h));
+    add_launch(L, T_COLLIDE, collide_kernel(h->collide_team), team_grid(h, h->collide_team), b, h->P, h->dm, h->dgk, h->gjk_scratch, lpt_cur, h->lpt_cap, solver_epw(h), h->collide_generic ? COLLIDE_GENERIC : 0);
     const int Ts = terrain ? h->terrain_solver_team : h->solver_team;
     add_launch(L, T_SOLVE, solve_kernel(terrain, Ts, fuse_solve(h) ? (more ? 1 : 2) : 0), team_grid(h, Ts), b, h->P, h->dm, h->dms, h->solver_ovf, lpt_cur, lpt_next, h->lpt_cap);
     if (fuse_solve(h)) continue;
@@ -6707,6 +6778,7 @@ static void read_knobs(go2sim* h) {
   if (env_int("GO2SIM_NO_FUSE", 0)) h->fuse_fk_dyn = false;
   if (env_int("GO2SIM_NO_FUSE_SOLVE", 0)) h->fuse_solve_int = false;
   if (env_int("GO2SIM_NO_LPT", 0)) h->use_lpt = false;
+  if (env_int("GO2SIM_COLLIDE_GENERIC", 0)) h->collide_generic = true;
 }
 
 int go2sim_create(const void* blob, size_t nbytes, int n_envs, int device, uint64_t seed, go2sim_t** out) {
@@ -7324,7 +7396,11 @@ int go2sim_read_timing(go2sim_t* h, float* ms_out8, int* cnt_out8, int reset) {
 }
 
 int go2sim_debug_narrowphase(go2sim_t* h, int which, int i_ga, int i_gb, const float* pa, const float* qa, const float* pb, const float* qb, float* out8) {
-  if (!h || !out8 || !pa || !qa || !pb || !qb || i_ga < 0 || i_gb < 0 || i_ga >= NG || i_gb >= NG || which < 0 || which > 6) return GO2SIM_E_BADARG;
+  if (!h || !out8 || !pa || !qa || !pb || !qb || i_ga < 0 || i_gb < 0 || i_ga >= NG || i_gb >= NG || which < 0 || which > 8) return GO2SIM_E_BADARG;
+  if (which >= 7) {                                                      // the sphere-box instantiations: a sphere against a box, in either order
+    const int ta = h->hm.geoms[i_ga].type, tb = h->hm.geoms[i_gb].type;
+    if (!((ta == GEOM_SPHERE && tb == GEOM_BOX) || (ta == GEOM_BOX && tb == GEOM_SPHERE))) return GO2SIM_E_BADARG;
+  }
   float* dout = nullptr;
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipMalloc((void**)&dout, 8 * sizeof(float)));

@@ -48,26 +48,31 @@ struct GjkCtl { int nv, nf, nmap, hz_n, ns, last_searched; bool overflow; };
 struct DgResult { bool is_col, overflow; float penetration; V3 normal, pos; };
 
 // ---- geometry of the pair: world-frame support points with vertex ids (gjk_support.py:62-186, support_field.py:183-306) ----
-struct DgPair {
+// PC: the pair's class (go2sim.hip, PairClass).  PC_GENERIC carries the run-time type switch; a sphere-box class names the sphere's and the box's
+// side at compile time (its sphere side keeps no rotation: `ra` / `rb` of that side is never read).
+template <PairClass PC>
+struct DgPairT {
   const Model* m; int i_ga, i_gb; V3 pos_a; Q4 quat_a; V3 pos_b; Q4 quat_b; bool discrete; GeomLite ga, gb; Rot ra, rb;   // type / size of the two geoms and the rotation coefficients of their poses, set up once
-  DEV V3 support_one(V3 d, int i_g, const GeomLite& gl, V3 pos, const Rot& rot, int& vid) const { return gjk_support_driver(*m, d, i_g, gl, pos, rot, vid); }
+  DEV bool disc() const { if constexpr (PC == PC_GENERIC) return discrete; else return false; }   // func_is_discrete_geoms: box - box only
   DEV void support_into(V3 d, DgVert* out) const {                   // the one copy of the support code of a query
     PHD_BEGIN
     DgVert r;
-    r.o1 = support_one(d, i_ga, ga, pos_a, ra, r.id1);
-    r.o2 = support_one(-d, i_gb, gb, pos_b, rb, r.id2);
+    r.o1 = gjk_support_driver<PC, 0>(*m, d, i_ga, ga, pos_a, ra, r.id1);
+    r.o2 = gjk_support_driver<PC, 1>(*m, -d, i_gb, gb, pos_b, rb, r.id2);
     r.mk = r.o1 - r.o2;
     *out = r;
     PHD(48)
   }
   DEV DgVert support(V3 d) const { DgVert r; support_into(d, &r); return r; }
   // count_support_driver, gjk.py:1854-1877: only a box can have several support points (a face / edge exactly normal to the direction)
+  template <int SIDE>
   DEV int count_one(V3 d, const GeomLite& gl, const Rot& rot) const {
-    if (gl.type != GEOM_BOX) return 1;
+    if constexpr (pc_side_is_sphere(PC, SIDE)) return 1;
+    if constexpr (PC == PC_GENERIC) { if (gl.type != GEOM_BOX) return 1; }
     V3 db = rot_apply_inv(rot, d);
     return 1 << ((db.x == 0.0f) + (db.y == 0.0f) + (db.z == 0.0f));
   }
-  DEV int count(V3 d) const { return count_one(d, ga, ra) * count_one(-d, gb, rb); }
+  DEV int count(V3 d) const { return count_one<0>(d, ga, ra) * count_one<1>(-d, gb, rb); }
   // func_get_discrete_geom_vertex (BOX), gjk.py:1666-1700
   DEV void box_vertex(bool second, int i_v, V3& obj, int& id) const {
     const int i_g = second ? i_gb : i_ga;
@@ -77,6 +82,7 @@ struct DgPair {
     id = 64 * i_g + i_v;
   }
 };
+typedef DgPairT<PC_GENERIC> DgPair;
 
 // ---- simplex vertex admission tests (gjk.py:1420-1539) ----
 template <class S>
@@ -109,8 +115,8 @@ DEV bool dg_valid(const S& st, int ns, const DgVert& w) { return !dg_duplicate(s
 
 // func_safe_gjk_support, gjk.py:1737-1850: when the plain direction hits a face / edge of a box (several support points), the direction is
 // nudged towards one of the 8 octants until the support point is unique and admissible
-template <class S>
-DEV DgVert dg_safe_support(const DgPair& pr, const S& st, int ns, V3 dir, float eps) {
+template <class PR, class S>
+DEV DgVert dg_safe_support(const PR& pr, const S& st, int ns, V3 dir, float eps) {
   DgVert w; w.o1 = v3(0, 0, 0); w.o2 = v3(0, 0, 0); w.mk = v3(0, 0, 0); w.id1 = -1; w.id2 = -1;
   for (int i = 0; i < 9; ++i) {
     V3 nd = dir;
@@ -132,10 +138,10 @@ DEV DgVert dg_safe_support(const DgPair& pr, const S& st, int ns, V3 dir, float 
 }
 
 // func_search_valid_simplex_vertex, gjk.py:1543-1649
-template <class S>
-DEV bool dg_search_vertex(const DgPair& pr, const S& st, GjkCtl& c, DgVert& w, float eps) {
+template <class PR, class S>
+DEV bool dg_search_vertex(const PR& pr, const S& st, GjkCtl& c, DgVert& w, float eps) {
   w.o1 = v3(0, 0, 0); w.o2 = v3(0, 0, 0); w.mk = v3(0, 0, 0); w.id1 = -1; w.id2 = -1;
-  if (pr.discrete) {                                                    // box - box: walk the 8 x 8 vertex pairs from where the last search stopped
+  if (pr.disc()) {                                                    // box - box: walk the 8 x 8 vertex pairs from where the last search stopped
     for (int k = 0; k < 64; ++k) {
       const int mth = (k + c.last_searched) % 64;
       pr.box_vertex(false, mth / 8, w.o1, w.id1);
@@ -160,8 +166,8 @@ DEV bool dg_search_vertex(const DgPair& pr, const S& st, GjkCtl& c, DgVert& w, f
 // func_safe_gjk, gjk.py:1200-1416: true when the tetrahedron v[0..3] contains the origin.  One loop serves both stages (steps 0..3 build
 // the initial tetrahedron from the directions +-z, +-y, the later steps replace the vertex opposite to the worst face), so the safe-support
 // code has a single call site.
-template <class S>
-DEV bool dg_gjk(const DgPair& pr, S& st, GjkCtl& c, float eps) {
+template <class PR, class S>
+DEV bool dg_gjk(const PR& pr, S& st, GjkCtl& c, float eps) {
   c.ns = 0;
   V3 best_n = v3(0, 0, 0);
   for (int step = 0; step < 4 + DG_GJK_MAX_IT; ++step) {
@@ -343,8 +349,8 @@ DEV V3 dg_project_origin(V3 p1, V3 p2, V3 p3) {
 
 // func_safe_epa, epa.py:970-1181 + func_safe_epa_init :1245-1295 + func_safe_epa_witness :1184-1242.
 // Returns the distance (negative = penetration) and the two witness points; 0 distance = no contact found.
-template <class S>
-DEV float dg_epa(const DgPair& pr, S& st, GjkCtl& c, float eps, V3& w1, V3& w2, bool& has_witness) {
+template <class PR, class S>
+DEV float dg_epa(const PR& pr, S& st, GjkCtl& c, float eps, V3& w1, V3& w2, bool& has_witness) {
   has_witness = false;
   // polytope = the GJK tetrahedron (its vertices already sit in v[0..3])
   c.nv = 4; c.nf = 0; c.nmap = 0; c.hz_n = 0;
@@ -356,7 +362,7 @@ DEV float dg_epa(const DgPair& pr, S& st, GjkCtl& c, float eps, V3& w1, V3& w2, 
   for (int i = 0; i < 4; ++i) { st.map[i] = (short)i; st.f[i].map_idx = (short)i; }
   c.nmap = 4;
   float upper = DG_FLOAT_MAX, upper2 = DG_FLOAT_MAX * DG_FLOAT_MAX, lower = 0.0f;
-  const float tol = pr.discrete ? eps : DG_TOLERANCE;
+  const float tol = pr.disc() ? eps : DG_TOLERANCE;
   int nearest = -1;
   for (int k = 0; k < DG_EPA_MAX_IT; ++k) {
     const int prev = nearest;
@@ -379,7 +385,7 @@ DEV float dg_epa(const DgPair& pr, S& st, GjkCtl& c, float eps, V3& w1, V3& w2, 
     const float upper_k = dot(w, dir);
     if (upper_k < upper) { upper = upper_k; upper2 = upper * upper; }
     if ((upper - lower) < tol) break;
-    if (pr.discrete) {
+    if (pr.disc()) {
       bool repeated = false;
       for (int i = 0; i < c.nv && !repeated; ++i) repeated = (i != wi) && st.v[i].id1 == st.v[wi].id1 && st.v[i].id2 == st.v[wi].id2;
       if (repeated) break;
@@ -428,8 +434,8 @@ DEV float dg_epa(const DgPair& pr, S& st, GjkCtl& c, float eps, V3& w1, V3& w2, 
 }
 
 // func_gjk_contact (non-MuJoCo branch), gjk.py:161-437
-template <class S>
-DEV DgResult dg_contact(const DgPair& pr, S& st, float eps) {
+template <class PR, class S>
+DEV DgResult dg_contact(const PR& pr, S& st, float eps) {
   GjkCtl c; c.nv = c.nf = c.nmap = c.hz_n = c.ns = 0; c.last_searched = 0; c.overflow = false;
   DgResult r; r.is_col = false; r.overflow = false; r.penetration = 0.0f; r.normal = v3(0, 0, 0); r.pos = v3(0, 0, 0);
   PHD_BEGIN
@@ -489,8 +495,8 @@ DEV void dgc_store_vert(S& st, int idx, const DgVert& w, int tl) { if (tl == 0) 
 
 // func_safe_gjk_support: the plain direction and its 8 nudged variants, W candidates at a time (lane l of round r = candidate r W + l); the rounds
 // stop as soon as the serial loop's choice is known.  `valid` = dg_valid of the returned vertex
-template <int W, class S>
-DEV DgVert dgc_safe_support(const DgPair& pr, const S& st, int ns, V3 dir, float eps, int tl, bool& valid) {
+template <int W, class PR, class S>
+DEV DgVert dgc_safe_support(const PR& pr, const S& st, int ns, V3 dir, float eps, int tl, bool& valid) {
   DgVert w_last; w_last.o1 = v3(0, 0, 0); w_last.o2 = v3(0, 0, 0); w_last.mk = v3(0, 0, 0); w_last.id1 = -1; w_last.id2 = -1;
   bool valid_last = false;
   for (int i0 = 0; i0 < 9; i0 += W) {
@@ -520,9 +526,9 @@ DEV DgVert dgc_safe_support(const DgPair& pr, const S& st, int ns, V3 dir, float
 }
 
 // func_search_valid_simplex_vertex: rare (the plain safe support was not admissible); the triangle case uses the cooperative safe support
-template <int W, class S>
-DEV bool dgc_search_vertex(const DgPair& pr, const S& st, GjkCtl& c, DgVert& w, float eps, int tl) {
-  if (pr.discrete) return dg_search_vertex(pr, st, c, w, eps);           // box - box vertex walk: executed redundantly by all lanes
+template <int W, class PR, class S>
+DEV bool dgc_search_vertex(const PR& pr, const S& st, GjkCtl& c, DgVert& w, float eps, int tl) {
+  if (pr.disc()) return dg_search_vertex(pr, st, c, w, eps);           // box - box vertex walk: executed redundantly by all lanes
   w.o1 = v3(0, 0, 0); w.o2 = v3(0, 0, 0); w.mk = v3(0, 0, 0); w.id1 = -1; w.id2 = -1;
   if (c.ns == 3) {
     V3 a = st.v[0].mk, b = st.v[1].mk, cc = st.v[2].mk;
@@ -538,8 +544,8 @@ DEV bool dgc_search_vertex(const DgPair& pr, const S& st, GjkCtl& c, DgVert& w, 
 }
 
 // func_safe_gjk
-template <int W, class S>
-DEV bool dgc_gjk(const DgPair& pr, S& st, GjkCtl& c, float eps, int tl) {
+template <int W, class PR, class S>
+DEV bool dgc_gjk(const PR& pr, S& st, GjkCtl& c, float eps, int tl) {
   c.ns = 0;
   V3 best_n = v3(0, 0, 0);
   for (int step = 0; step < 4 + DG_GJK_MAX_IT; ++step) {
@@ -631,8 +637,8 @@ DEV void dgc_horizon(S& st, GjkCtl& c, int nearest) {
 }
 
 // func_safe_epa + _init + _witness
-template <int W, class S>
-DEV float dgc_epa(const DgPair& pr, S& st, GjkCtl& c, float eps, V3& w1, V3& w2, bool& has_witness, int tl) {
+template <int W, class PR, class S>
+DEV float dgc_epa(const PR& pr, S& st, GjkCtl& c, float eps, V3& w1, V3& w2, bool& has_witness, int tl) {
   has_witness = false;
   c.nv = 4; c.nf = 0; c.nmap = 0; c.hz_n = 0;
   {                                                                      // the four faces of the tetrahedron, one per lane
@@ -646,7 +652,7 @@ DEV float dgc_epa(const DgPair& pr, S& st, GjkCtl& c, float eps, V3& w1, V3& w2,
   }
   team_sync();
   float upper = DG_FLOAT_MAX, upper2 = DG_FLOAT_MAX * DG_FLOAT_MAX, lower = 0.0f;
-  const float tol = pr.discrete ? eps : DG_TOLERANCE;
+  const float tol = pr.disc() ? eps : DG_TOLERANCE;
   int nearest = -1;
   for (int k = 0; k < DG_EPA_MAX_IT; ++k) {
     const int prev = nearest;
@@ -668,7 +674,7 @@ DEV float dgc_epa(const DgPair& pr, S& st, GjkCtl& c, float eps, V3& w1, V3& w2,
     const float upper_k = dot(w, dir);
     if (upper_k < upper) { upper = upper_k; upper2 = upper * upper; }
     if ((upper - lower) < tol) { team_sync(); break; }
-    if (pr.discrete) {
+    if (pr.disc()) {
       bool repeated = false;
       for (int i = 0; i < wi && !repeated; ++i) repeated = st.v[i].id1 == wv.id1 && st.v[i].id2 == wv.id2;
       if (repeated) { team_sync(); break; }
@@ -730,8 +736,8 @@ DEV float dgc_epa(const DgPair& pr, S& st, GjkCtl& c, float eps, V3& w1, V3& w2,
 }
 
 // func_gjk_contact, executed by the W lanes of a group together (tl = lane within the group); every lane returns the same result
-template <int W, class S>
-DEV DgResult dgc_contact(const DgPair& pr, S& st, float eps, int tl) {
+template <int W, class PR, class S>
+DEV DgResult dgc_contact(const PR& pr, S& st, float eps, int tl) {
   GjkCtl c; c.nv = c.nf = c.nmap = c.hz_n = c.ns = 0; c.last_searched = 0; c.overflow = false;
   DgResult r; r.is_col = false; r.overflow = false; r.penetration = 0.0f; r.normal = v3(0, 0, 0); r.pos = v3(0, 0, 0);
   PHD_BEGIN

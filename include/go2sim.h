@@ -418,7 +418,8 @@ int go2sim_env_globals_ptr(go2sim_t* h, void** ptr_out);
  * penetration, normal[3], pos[3]}), evaluated by the library's own narrow-phase code: which = 0 MPR from a cold start (collider/mpr.py:763-819),
  * 1 safe GJK + EPA by one lane with the LDS polytope slot (collider/gjk.py:161-437), 2 the same on the full-capacity polytope record, 3 / 4 the
  * cooperative query the collision kernel runs (the 4 lanes of a quad on one query) with an LDS slot / on the full-capacity record, 5 / 6 the same
- * with 16 lanes per query.  Synchronous.
+ * with 16 lanes per query, 7 / 8 = 0 / 3 compiled for the pair's class (a sphere against a box in either operand order, the code the collision
+ * kernel runs for a wave of such pairs; GO2SIM_E_BADARG for any other pair): bit-equal to 0 / 3 on the same poses.  Synchronous.
  * Lets the closed-form checks of tests/test_gjk_epa.py run against the HIP implementation, not only against the oracle. */
 int go2sim_debug_narrowphase(go2sim_t* h, int which, int i_ga, int i_gb, const float* pos_a, const float* quat_a, const float* pos_b,
                              const float* quat_b, float* out8);
