@@ -72,6 +72,10 @@ C.update(_C_STAIRINFO)
 DISTILL_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_distill.h")
 _C_DISTILL, DECLARED_DISTILL_FUNCS = _parse_header(DISTILL_HEADER)
 C.update(_C_DISTILL)
+# distillation with a recurrent student (include/go2sim_rdistill.h): product library only, a list of its own
+RDISTILL_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_rdistill.h")
+_C_RDISTILL, DECLARED_RDISTILL_FUNCS = _parse_header(RDISTILL_HEADER)
+C.update(_C_RDISTILL)
 # the hidden-layer activation of an MLP (include/go2sim_activation.h): product library only, a list of its own
 ACT_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_activation.h")
 _C_ACT, DECLARED_ACT_FUNCS = _parse_header(ACT_HEADER)
@@ -89,6 +93,22 @@ class PpoCfg(ctypes.Structure):
 class DistillCfg(ctypes.Structure):
     """go2sim_distill_cfg_t"""
     _fields_ = [(n, ctypes.c_double) for n in ("learning_rate", "max_grad_norm", "beta1", "beta2", "eps")] + [("loss_type", ctypes.c_int), ("sub_rows", ctypes.c_int)]
+
+
+class RDistillCfg(ctypes.Structure):
+    """go2sim_rdistill_cfg_t"""
+    _fields_ = [(n, ctypes.c_double) for n in ("learning_rate", "max_grad_norm", "beta1", "beta2", "eps")] + [("loss_type", ctypes.c_int), ("sub_envs", ctypes.c_int)]
+
+
+class RDistillRoll(ctypes.Structure):
+    """go2sim_rdistill_roll_t: device pointers of one rollout, the state S at its first act and the carried state"""
+    FIELDS = ("obs", "teacher_actions", "dones", "h0", "c0", "h", "c")
+    _fields_ = [(n, ctypes.c_void_p) for n in FIELDS] + [("n_steps", ctypes.c_int), ("n_envs", ctypes.c_int)]
+
+
+class RDistillSeg(ctypes.Structure):
+    """go2sim_rdistill_seg_t"""
+    _fields_ = [("t0", ctypes.c_int), ("n_steps", ctypes.c_int)]
 
 
 class PpoBatch(ctypes.Structure):
@@ -174,7 +194,7 @@ class Go2SimLib:
             fn = getattr(self.lib, prefix + name[len("go2sim_"):])
             fn.restype = ctypes.c_int
         if self.is_device:
-            for name in DECLARED_TRAIN_FUNCS + DECLARED_RNN_FUNCS + DECLARED_NORM_FUNCS + DECLARED_LIDAR_FUNCS + DECLARED_STAIRINFO_FUNCS + DECLARED_DISTILL_FUNCS + DECLARED_ACT_FUNCS:       # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
+            for name in DECLARED_TRAIN_FUNCS + DECLARED_RNN_FUNCS + DECLARED_NORM_FUNCS + DECLARED_LIDAR_FUNCS + DECLARED_STAIRINFO_FUNCS + DECLARED_DISTILL_FUNCS + DECLARED_RDISTILL_FUNCS + DECLARED_ACT_FUNCS:     # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
                 if hasattr(self.lib, name):
                     getattr(self.lib, name).restype = ctypes.c_int
 

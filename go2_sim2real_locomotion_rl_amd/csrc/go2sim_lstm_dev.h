@@ -1,5 +1,5 @@
 // go2sim_lstm_dev.h -- private to csrc/: the device-side record of one LSTM memory, the handle behind go2sim_lstm_t and the two kernels that walk
-// through time (include/go2sim_rnn.h): the cell step and the backward-through-time step.  Included by go2sim_train.hip.  Not part of the C ABI.
+// through time (include/go2sim_rnn.h): the cell step and the backward-through-time step.  Included by go2sim_train.hip and go2sim_rdistill.hip.  Not part of the C ABI.
 //
 // Both kernels tile the hidden units, never the 4 H gate columns as one row: a workgroup owns TM = 32 rows and NWAVE x 16 hidden units, a wavefront one
 // 16-unit column tile.  In the cell step the wavefront holds the four gate accumulators of its units for both row tiles (8 accumulators), so i, f, g, o

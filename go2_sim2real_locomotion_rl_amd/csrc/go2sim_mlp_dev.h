@@ -1,5 +1,5 @@
 // go2sim_mlp_dev.h -- private to csrc/: the device-side record of one MLP, the handle behind go2sim_mlp_t and the fused layer loop, shared by the
-// inference source (go2sim_policy.hip) and the training sources (go2sim_train.hip, go2sim_distill.hip).  Not part of the C ABI.
+// inference source (go2sim_policy.hip) and the training sources (go2sim_train.hip, go2sim_distill.hip, go2sim_rdistill.hip).  Not part of the C ABI.
 #ifndef GO2SIM_MLP_DEV_H
 #define GO2SIM_MLP_DEV_H
 #include <hip/hip_runtime.h>
@@ -179,7 +179,7 @@ __device__ __forceinline__ void mlp_layer(const MlpDev& M, int l, const float (*
   }
 }
 
-// The two kernels of a policy step, for the sources that act (go2sim_policy.hip, go2sim_distill.hip): they define GO2SIM_MLP_ACT_KERNELS before the include, so
+// The two kernels of a policy step, for the sources that act (go2sim_policy.hip, go2sim_distill.hip, go2sim_rdistill.hip): they define GO2SIM_MLP_ACT_KERNELS before the include, so
 // that a source that only trains does not carry a copy.
 #ifdef GO2SIM_MLP_ACT_KERNELS
 constexpr uint32_t RNG_POLICY_NOISE = 11;   // purposes 1..10 belong to the environment (csrc/go2sim.hip)

@@ -1,5 +1,5 @@
 // go2sim_train_dev.h -- private to csrc/: the kernels every update shares, next to go2sim_mlp_dev.h.  The PPO update (go2sim_train.hip) and the
-// distillation update (go2sim_distill.hip) include it; each keeps its own loss head, and both drive these kernels through the host code of
+// distillation updates (go2sim_distill.hip, go2sim_rdistill.hip) include it; each keeps its own loss head, and both drive these kernels through the host code of
 // go2sim_trainer_host.h (optimizer state, packing, workspaces, the backward schedule).  Not part of the C ABI.
 //   k_train_forward   the layer loop of the inference kernel with every hidden layer's post-activation kept in the workspace
 //   k_bwd_dw / k_bwd_db / k_bwd_da   the chunked backward of one layer of one or two networks (go2sim_train.hip describes them)

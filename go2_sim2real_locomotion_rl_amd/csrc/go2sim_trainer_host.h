@@ -1,5 +1,5 @@
 // go2sim_trainer_host.h -- private to csrc/: the host side every update shares, next to the kernels of go2sim_train_dev.h.  The PPO update
-// (go2sim_train.hip) and the distillation update (go2sim_distill.hip) are handles that own an OptState and call these pieces; each keeps its own loss
+// (go2sim_train.hip) and the distillation updates (go2sim_distill.hip, go2sim_rdistill.hip) are handles that own an OptState and call these pieces; each keeps its own loss
 // head, statistics, argument checks and (PPO) mirror tables, shard records and recurrent workspaces.  Not part of the C ABI.
 //   HIPCHK            the status check, tagged with the including file's GO2SIM_HIPCHK_TAG
 //   OptState          grads | m | v and scal | sq_part | tail, the step count; opt_apply = k_sumsq + k_adam

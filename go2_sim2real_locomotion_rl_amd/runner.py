@@ -21,8 +21,8 @@ the checkpoint gains ``obs_norm_state_dict`` / ``critic_obs_norm_state_dict`` an
 
 ``train_cfg["obs_groups"]`` (optional) maps the roles ``policy``, ``critic`` and ``teacher`` to the env's observation groups ``"policy"`` (what
 ``get_observations()`` returns) or ``"critic"`` (``extras["observations"]["critic"]``).  ``{"policy": "critic"}`` on a PPO run trains an actor on the
-privileged rows -- a teacher.  ``algorithm.class_name == "Distillation"`` with ``policy.class_name == "StudentTeacher"`` (distillation.py) distils such a
-teacher into a student: ``load(teacher_checkpoint)`` fills the teacher, ``learn()`` collects with the student and regresses it onto the teacher's actions,
+privileged rows -- a teacher.  ``algorithm.class_name == "Distillation"`` with ``policy.class_name == "StudentTeacher"`` or ``"StudentTeacherRecurrent"``
+(distillation.py; the second puts an LSTM memory in front of the student and needs ``rnn_hidden_dim``) distils such a teacher into a student: ``load(teacher_checkpoint)`` fills the teacher, ``learn()`` collects with the student and regresses it onto the teacher's actions,
 the log carries ``behavior_loss``.  A teacher checkpoint's ``obs_norm_state_dict`` becomes a frozen teacher normaliser that is always applied (it is part of
 the teacher's function) and is saved as ``privileged_obs_norm_state_dict`` (DESIGN.md "Distillation").
 """
@@ -31,7 +31,7 @@ import os
 import torch
 
 from .capi import Go2SimError
-from .distillation import Distillation, StudentTeacher
+from .distillation import Distillation, StudentTeacher, StudentTeacherRecurrent
 from .distributed import is_multi, shard_seed, sum_in_rank_order
 from .eval_io import read_checkpoint, save_checkpoint
 from .normalization import EmpiricalNormalization, norm_step
@@ -47,10 +47,10 @@ class OnPolicyRunner:
         alg_cfg, pol_cfg = dict(train_cfg["algorithm"]), dict(train_cfg["policy"])
         pol_class = pol_cfg.pop("class_name", "ActorCritic")
         alg_class = alg_cfg.pop("class_name", "PPO")
-        pairings = {"PPO": ("ActorCritic", "ActorCriticRecurrent"), "Distillation": ("StudentTeacher",)}
+        pairings = {"PPO": ("ActorCritic", "ActorCriticRecurrent"), "Distillation": ("StudentTeacher", "StudentTeacherRecurrent")}
         if alg_class not in pairings or pol_class not in pairings[alg_class]:
-            raise Go2SimError(f"go2sim implements class_name PPO with ActorCritic / ActorCriticRecurrent and Distillation with StudentTeacher; "
-                              f"algorithm {alg_class!r} with policy {pol_class!r} is not one of these pairings")
+            raise Go2SimError(f"go2sim implements class_name PPO with ActorCritic / ActorCriticRecurrent and Distillation with StudentTeacher / "
+                              f"StudentTeacherRecurrent; algorithm {alg_class!r} with policy {pol_class!r} is not one of these pairings")
         self.distill = alg_class == "Distillation"
         self.obs_groups = self._check_obs_groups(train_cfg.get("obs_groups"))
         obs, extras = env.get_observations()
@@ -79,7 +79,8 @@ class OnPolicyRunner:
             if self.group is not None:
                 raise Go2SimError("Distillation over a multi-rank group is not implemented (the sharded distillation update is a follow-up)")
             s_obs, _, t_obs = self._roles(obs, extras["observations"])
-            self.policy = StudentTeacher(s_obs.shape[1], t_obs.shape[1], env.num_actions, device=self.device, seed=seed, **pol_cfg)
+            st_class = StudentTeacherRecurrent if pol_class == "StudentTeacherRecurrent" else StudentTeacher   # the recurrent class refuses a config without rnn_hidden_dim
+            self.policy = st_class(s_obs.shape[1], t_obs.shape[1], env.num_actions, device=self.device, seed=seed, **pol_cfg)
             self.alg = Distillation(self.policy, device=self.device, **alg_cfg)
             self.alg.init_storage(env.num_envs, self.num_steps_per_env, [s_obs.shape[1]], [t_obs.shape[1]], [env.num_actions])
             if self.empirical_normalization:                                  # the student's normaliser learns as the actor's does in a PPO run
@@ -228,13 +229,15 @@ class OnPolicyRunner:
         return log
 
     def _load_distill(self, ckpt, path, load_optimizer):
-        """A PPO checkpoint is the teacher: teacher.* <- actor.*, its actor normaliser becomes the frozen teacher normaliser; the student, the iteration
-        and the optimizer are untouched.  A distillation checkpoint resumes: student, teacher, std, both normalisers, optimizer, iteration."""
+        """A PPO checkpoint is the teacher: teacher.* <- actor.* (for a StudentTeacherRecurrent with a recurrent teacher also memory_t.* <- memory_a.*), its
+        actor normaliser becomes the frozen teacher normaliser; the student, the iteration and the optimizer are untouched.  A distillation checkpoint
+        resumes: student, teacher, (the memories,) std, both normalisers, optimizer, iteration."""
         resume = self.policy.load_state_dict(ckpt["model_state_dict"])
         t_norm = ckpt.get("privileged_obs_norm_state_dict" if resume else "obs_norm_state_dict")
         if t_norm is not None:
             if self.privileged_obs_normalizer is None:
-                self.privileged_obs_normalizer = EmpiricalNormalization([self.policy._tdims[0]], until=1.0e8, device=self.device).eval()
+                n_teacher_obs = self.policy._tmem[0] if getattr(self.policy, "_tmem", None) else self.policy._tdims[0]   # a recurrent teacher's memory reads the rows
+                self.privileged_obs_normalizer = EmpiricalNormalization([n_teacher_obs], until=1.0e8, device=self.device).eval()
             self.privileged_obs_normalizer.load_state_dict(t_norm)
         elif resume:
             self.privileged_obs_normalizer = None

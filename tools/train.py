@@ -8,6 +8,7 @@
     python tools/train.py --task stairs_info --envs 4096 --iterations 1000                              # the stair env with the four-value stair info (53 / 113 inputs)
     python tools/train.py --task stairs_lidar --envs 4096 --iterations 1000 --actor-obs critic --log-dir logs/teacher   # a teacher: the actor reads the privileged rows
     python tools/train.py --task stairs_lidar --envs 4096 --iterations 500 --distill logs/teacher/model_1000.pt --teacher-obs critic   # distil it into a student
+    python tools/train.py --task stairs_lidar --distill logs/teacher/model_1000.pt --teacher-obs critic --student-recurrent --rnn-hidden 256   # ... a student with an LSTM memory
     torchrun --nproc-per-node 8 tools/train.py --task walk --envs 4096 --iterations 1000 --log-dir logs/go2-walk
 
 --envs is the env count PER RANK.  Under torchrun every rank builds its shard of the envs (``Go2Env(..., shared_globals=True)``: one curriculum, one
@@ -56,13 +57,17 @@ def main():
                     help="left-right mirror symmetry in the update (rsl_rl's symmetry_cfg): augmentation with the mirrored rows, the mirror loss, or both")
     ap.add_argument("--mirror-coeff", type=float, default=0.5, help="mirror_loss_coeff of --symmetry mirror / both")
     ap.add_argument("--recurrent", action="store_true", help="train rsl_rl's ActorCriticRecurrent (one LSTM layer per network); one rank, no --symmetry")
-    ap.add_argument("--rnn-hidden", type=int, default=256, help="rnn_hidden_size of --recurrent")
+    ap.add_argument("--rnn-hidden", type=int, default=256, help="rnn_hidden_size of --recurrent, rnn_hidden_dim of --student-recurrent")
     ap.add_argument("--empirical-normalization", action="store_true",
                     help="normalise both observation sets with running statistics (train_cfg['empirical_normalization']); the checkpoints carry them")
     ap.add_argument("--actor-obs", choices=("policy", "critic"), default="policy",
                     help="the env observation group the PPO actor reads (train_cfg['obs_groups']['policy']); 'critic' trains a teacher on the privileged rows")
     ap.add_argument("--distill", default=None, metavar="TEACHER_CKPT",
                     help="distil the actor of this PPO checkpoint into a student (Distillation + StudentTeacher); one rank")
+    ap.add_argument("--student-recurrent", action="store_true",
+                    help="with --distill: an LSTM memory of --rnn-hidden units in front of the student (Distillation + StudentTeacherRecurrent)")
+    ap.add_argument("--teacher-recurrent", action="store_true",
+                    help="with --student-recurrent: the teacher checkpoint is an ActorCriticRecurrent's (tools/train.py --recurrent); its memory_a becomes memory_t")
     ap.add_argument("--student-hidden", type=int, nargs="+", default=[256, 256, 256], help="student_hidden_dims of --distill")
     ap.add_argument("--gradient-length", type=int, default=15, help="steps per gradient window of --distill")
     ap.add_argument("--loss-type", choices=("mse", "huber"), default="mse", help="behaviour loss of --distill")
@@ -111,6 +116,8 @@ def main():
             cfg["empirical_normalization"] = True
         if args.actor_obs != "policy":
             cfg["obs_groups"] = {"policy": args.actor_obs}
+        if (args.student_recurrent or args.teacher_recurrent) and not (args.distill and args.student_recurrent):
+            raise SystemExit("--student-recurrent belongs to --distill, --teacher-recurrent to --student-recurrent")
         if args.distill:
             if world > 1 or args.recurrent or args.symmetry != "off" or args.actor_obs != "policy":
                 raise SystemExit("--distill runs on one rank, without --recurrent, --symmetry and --actor-obs")
@@ -123,6 +130,13 @@ def main():
                                 "learning_rate": 1e-3, "max_grad_norm": None, "loss_type": args.loss_type}
             cfg["policy"] = {"class_name": "StudentTeacher", "activation": cfg["policy"].get("activation", "elu"), "student_hidden_dims": list(args.student_hidden),
                              "teacher_hidden_dims": teacher_hidden, "init_noise_std": 0.1}
+            if args.student_recurrent:
+                cfg["policy"].update(class_name="StudentTeacherRecurrent", rnn_type="lstm", rnn_hidden_dim=args.rnn_hidden, rnn_num_layers=1,
+                                     teacher_recurrent=args.teacher_recurrent)
+                if args.teacher_recurrent:                                          # the teacher's memory width is the checkpoint's
+                    if "memory_a.rnn.weight_hh_l0" not in sd:
+                        raise SystemExit(f"--teacher-recurrent: {args.distill} has no memory_a.* keys (it was not trained with --recurrent)")
+                    cfg["policy"]["teacher_rnn_hidden_dim"] = int(sd["memory_a.rnn.weight_hh_l0"].shape[1])
             cfg["obs_groups"] = {"teacher": args.teacher_obs}
         runner = OnPolicyRunner(env, cfg, log_dir=args.log_dir, device=device)      # picks up the default process group
         if args.distill:
