@@ -773,6 +773,12 @@ __device__ unsigned long long g_phase_cycles[PH_MAX_WG * 64];
 constexpr int PHA_REWK = 48, PHA_WAIT = 56;
 #define PHA_BEGIN unsigned long long pha_t = __builtin_readcyclecounter();
 #define PHA(i) { __builtin_amdgcn_s_waitcnt(0); unsigned long long pha_n = __builtin_readcyclecounter(); if (threadIdx.x % 64 == 0 && blockIdx.x < PH_MAX_WG / 4) g_phase_cycles[(PH_MAX_WG / 2 + PH_MAX_WG / 4 + blockIdx.x) * 64 + (i)] += pha_n - pha_t; pha_t = __builtin_readcyclecounter(); }
+// k_collide_team, the fixed part of a launch split finer (ids PHK_* below): a timer of its own next to PH's, rows of their own in the last eighth
+// (row PH_MAX_WG - PH_MAX_WG / 8 + workgroup: 1024 workgroups at 4096 envs).  A PHK mark does NOT wait for memory: what a sync point waits for is
+// what it measures, so a mark in front of one must leave the stores in flight.  PHW: PH without the wait, for the same reason.
+#define PHK_BEGIN unsigned long long phk_t = __builtin_readcyclecounter();
+#define PHK(i) { unsigned long long phk_n = __builtin_readcyclecounter(); if (threadIdx.x == 0 && blockIdx.x < PH_MAX_WG / 8) g_phase_cycles[(PH_MAX_WG - PH_MAX_WG / 8 + blockIdx.x) * 64 + (i)] += phk_n - phk_t; phk_t = __builtin_readcyclecounter(); }
+#define PHW(i) { unsigned long long ph_n = __builtin_readcyclecounter(); if (threadIdx.x == 0 && blockIdx.x < PH_MAX_WG / 2) g_phase_cycles[blockIdx.x * 64 + (i)] += ph_n - ph_t; ph_t = __builtin_readcyclecounter(); }
 #else
 #define PH_BEGIN
 #define PH(i)
@@ -782,7 +788,14 @@ constexpr int PHA_REWK = 48, PHA_WAIT = 56;
 #define PHB(i)
 #define PHA_BEGIN
 #define PHA(i)
+#define PHK_BEGIN
+#define PHK(i)
+#define PHW(i)
 #endif
+// PHK ids (tools/phase_profile.py): the head until the pair words are in LDS / until batch 2 has arrived; cc_detect0 (set-up + MPR round: section 36
+// is inside), the fallback quads, the sync behind them, cc_rest; the append (issue of the stores), the round's LDS sync, the sync behind the pair
+// loop, plane-box + terrain + the count, the sync behind the count, LPT key + mask stores
+enum { PHK_HEAD_WORDS = 0, PHK_HEAD_BATCH2, PHK_DETECT0, PHK_QUADS, PHK_QUAD_SYNC, PHK_REST, PHK_APPEND, PHK_ROUND_SYNC, PHK_TAIL_SYNC1, PHK_PASSES, PHK_TAIL_SYNC2, PHK_TAIL_END };
 
 // ---- optional wall-clock stamps per workgroup (build with -DGO2SIM_STAMP; tools/launch_overhead.py): every workgroup of the step kernels records
 // s_memrealtime (the 100 MHz constant clock shared by all CUs) at entry and after its last memory operation has retired.  From one step's stamps the
@@ -2579,9 +2592,13 @@ DEV bool cc_prefer_gjk(const Model& m, const CcState& c, bool guess_available) {
 // i_pair = m.pair_idx of the pair (it travels with the broad-phase list); in = load_pair_in of (i_ga, i_gb, i_pair)
 template <PairClass PC = PC_GENERIC>
 DEV void cc_detect0(const Model& m, const GeomK* gk, const E& e, int i_ga, int i_gb, int i_pair, const PairIn& in, unsigned* ncv, CcState& c) {
-  c.type_a = gk[i_ga].type; c.type_b = gk[i_gb].type;
-  c.multi_contact = (c.type_a != GEOM_SPHERE) && (c.type_b != GEOM_SPHERE);
-  c.link_quat = e.i_quat()[c.multi_contact ? contact_orthogonals_link(gk, i_ga, i_gb) : 0];   // in flight during the query
+  if constexpr (PC == PC_SPHERE_BOX) {                           // the class says it all: a sphere pair takes no perturbed detection, no link orientation is fetched
+    c.type_a = GEOM_SPHERE; c.type_b = GEOM_BOX; c.multi_contact = false; c.link_quat = q4(0, 0, 0, 0);
+  } else {
+    c.type_a = gk[i_ga].type; c.type_b = gk[i_gb].type;
+    c.multi_contact = (c.type_a != GEOM_SPHERE) && (c.type_b != GEOM_SPHERE);
+    c.link_quat = e.i_quat()[c.multi_contact ? contact_orthogonals_link(gk, i_ga, i_gb) : 0];   // in flight during the query
+  }
   c.tolerance = compute_tolerance(gk, i_ga, i_gb, m.mc_tolerance);
   c.ga_pos_o = in.pos_a; c.gb_pos_o = in.pos_b; c.ga_quat_o = in.quat_a; c.gb_quat_o = in.quat_b;
   Pair& pr = c.pr;
@@ -2615,10 +2632,12 @@ DEV void cc_gjk_lane(const Model& m, const E& e, CcState& c, GjkStoreLds* gjk_sl
   c.penetration = gr.penetration;
   if (c.is_col) { c.contact_pos = gr.pos; c.normal = gr.normal; }
 }
+// PC_SPHERE_BOX: multi_contact is the constant false, so the loop folds to the bookkeeping of detection 0 (no perturbed detection, no contact_orthogonals)
+template <PairClass PC = PC_GENERIC>
 DEV void cc_rest(const Model& m, const GeomK* gk, const E& e, CcState& c, ContactStage& cs, GjkStoreLds* gjk_slots, unsigned* gjk_slot_mask, GjkStoreFull* gjk_full, unsigned* ncv) {
   const float EPS = m.eps;
   const int i_pair = c.i_pair;
-  const bool multi_contact = c.multi_contact;
+  const bool multi_contact = PC == PC_SPHERE_BOX ? false : c.multi_contact;
   const float tolerance = c.tolerance;
   Pair& pr = c.pr;
   bool is_col_0 = false; V3 normal_0 = v3(0, 0, 0), contact_pos_0 = v3(0, 0, 0);
@@ -2848,6 +2867,7 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
   E e(P, b);
   CollideData<T>* s = &lds[slot];
   PH_BEGIN
+  PHK_BEGIN
   // ---- the pair list of the broad phase (tk_broadphase, run by the dynamics launch in front of this one) ----
   constexpr int NPRE = (T == 16) ? 2 : 1;                               // rounds whose pair words are requested up front (the walking robot: < 32 pairs)
   static_assert(NPRE * T <= MAXB, "the unconditional pair-word loads stay inside e.broad()");
@@ -2866,6 +2886,7 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
   for (int c = tl + NPRE * T; c < n_broad; c += T) s->pair_w[c] = (unsigned)e.broad()[c];
   team_sync();                                                          // (also ends the DMA of the geom table)
   PH(62)
+  PHK(PHK_HEAD_WORDS)
   // ---- func_narrow_phase_convex_vs_convex (narrowphase.py:964-1068), then func_narrow_phase_any_vs_terrain (:1197-1244): one lane per
   //      pair, ordered compaction; the terrain pass appends after all convex-convex contacts, as the two reference kernels do ----
   int nc_run = 0;
@@ -2933,6 +2954,7 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
     any_plane_box |= team_ballot<T>(plane_box) != 0ull;
     const PairConst pc = pair_const(i_ga, i_gb, fric);
     PH(62)
+    PHK(PHK_HEAD_BATCH2)
     if constexpr (T == 16) {
       // MPR of every pair on its own lane; then the pairs whose MPR answer has to be replaced by safe GJK + EPA (narrowphase.py:727-845) are
       // answered by QUADS: the four quads of the team take four flagged pairs at a time (the four feet of a landing robot), the four lanes of a
@@ -2941,12 +2963,13 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
       CcState cst;
       cst.want_gjk = false;
       // The class of the round, one per WAVE: when every pair of the wave's (up to four) teams is a sphere against a box -- the walking robot: feet on
-      // the ground -- the wave runs the PC_SPHERE_BOX instantiation of the MPR queries and of the fallback quads, otherwise (one pair of another class
+      // the ground -- the wave runs the PC_SPHERE_BOX instantiation of the MPR queries, of the fallback quads and of cc_rest, otherwise (one pair of another class
       // is enough) the generic one, as a whole: never both one after the other, which would lengthen the wave everything waits for.
       const bool other_class = convex_pair && pair_class(gk[i_ga].type, gk[i_gb].type) != PC_SPHERE_BOX;
       const bool wave_sphere_box = !(collide_flags & COLLIDE_GENERIC) && __ballot(other_class) == 0ull;
       if (wave_sphere_box) { if (convex_pair) cc_detect0<PC_SPHERE_BOX>(m, gk, e, i_ga, i_gb, i_pair, pin, s->ncv, cst); }
       else if (convex_pair) cc_detect0<PC_GENERIC>(m, gk, e, i_ga, i_gb, i_pair, pin, s->ncv, cst);
+      PHK(PHK_DETECT0)
       const bool wants = convex_pair && cst.want_gjk;
       const unsigned want = dgc_ballot<16>(wants);
       const int n_want = __popc(want), quad = tl >> 2, ql = tl & 3;
@@ -2970,7 +2993,9 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
           }
         }
       }
+      PHK(PHK_QUADS)
       team_sync();
+      PHK(PHK_QUAD_SYNC)
       if (wants) {
         atomicAdd(&e.gjk_fallback()[0], 1);
         const float* o = s->gjk_res[tl];
@@ -2978,14 +3003,19 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
         cst.penetration = o[1];
         if (cst.is_col) { cst.normal = v3(o[2], o[3], o[4]); cst.contact_pos = v3(o[5], o[6], o[7]); }
       }
-      if (convex_pair) cc_rest(m, gk, e, cst, cs, nullptr, &s->gjk_slot_mask, &gjk_scratch[(size_t)b * T + tl], s->ncv);
+      if (wave_sphere_box) { if (convex_pair) cc_rest<PC_SPHERE_BOX>(m, gk, e, cst, cs, nullptr, &s->gjk_slot_mask, &gjk_scratch[(size_t)b * T + tl], s->ncv); }
+      else if (convex_pair) cc_rest<PC_GENERIC>(m, gk, e, cst, cs, nullptr, &s->gjk_slot_mask, &gjk_scratch[(size_t)b * T + tl], s->ncv);
     } else if (convex_pair) convex_convex_contact_staged(m, gk, e, i_ga, i_gb, i_pair, pin, cs, s->gjk, &s->gjk_slot_mask, &gjk_scratch[(size_t)b * T + tl], s->ncv);
     PH(63)
+    PHK(PHK_REST)
     append_staged(cs, i_ga, i_gb, pc);
+    PHK(PHK_APPEND)
     team_sync_lds();                                                    // gjk_res and the polytope slots are rewritten by the next round
-    PH(33)
+    PHW(33)
+    PHK(PHK_ROUND_SYNC)
   }
   team_sync();                                                          // the terrain pass lays its pair slots over the polytope slots
+  PHK(PHK_TAIL_SYNC1)
   // ---- func_narrow_phase_convex_specializations (narrowphase.py:1146-1170; collider.py:486-498): plane-box pairs, after all convex-convex
   //      contacts and before the terrain pass; one lane per pair, same ordered compaction ----
   if (any_plane_box) {
@@ -3178,7 +3208,9 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
     e.n_contacts()[0] = imn(nc_run, m.max_contact_pairs);
     s->cnt[0] = imn(nc_run, m.max_contact_pairs);
   }
+  PHK(PHK_PASSES)
   team_sync();
+  PHK(PHK_TAIL_SYNC2)
   if (lpt_rec && tl == 0 && b % solver_epw == 0) {                       // the first env of a solver block files it (the block's envs sit in this wavefront)
     int key = s->cnt[0];
     for (int k = 1; k < solver_epw; ++k) if (b + k < P.B && slot + k < EPW) key = imx(key, lds[slot + k].cnt[0]);
@@ -3186,6 +3218,7 @@ __global__ __launch_bounds__(64) void k_collide_team(Pool P, const Model* __rest
   }
   for (int i = tl; i < NCV; i += T) e.ncache_valid()[i] = (int)s->ncv[i];
   PH(33)
+  PHK(PHK_TAIL_END)
 }
 
 // ---------------------------------------------------------------------------------------------

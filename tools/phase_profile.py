@@ -71,6 +71,20 @@ if len(sys.argv) > 3 and sys.argv[3] == "decouple":
     print(f"  collide + solver only    : sum of slowest workgroups {S2_all.mean():9.0f}   longest per-env chain {C2_all.mean():9.0f}   gap {100 * (1 - C2_all.mean() / S2_all.mean()):5.1f} %")
     print("  (integrate_fk: the T = 16 launch of the second substep is attributed with the T = 32 map; it is constant-time, so the gap is unaffected)")
     raise SystemExit(0)
+# k_collide_team's fixed part, split finer (PHK_* in csrc/go2sim.hip): rows of their own in the last eighth, marks that do not wait for memory
+PHK_ROW0 = PH_MAX_WG - PH_MAX_WG // 8
+PHK_NAMES = ["head: until the pair words are in LDS", "head: until batch 2 has arrived", "cc_detect0: set-up + MPR round (section 36 inside)", "fallback quads", "sync behind the quads",
+             "cc_rest", "append (stores issued)", "round's LDS sync", "tail sync 1 (behind the pair loop)", "plane-box + terrain + count", "tail sync 2 (behind the count)", "LPT key + mask stores"]
+def print_phk(a, launches):
+    k = a[PHK_ROW0:PHK_ROW0 + PH_MAX_WG // 8, :len(PHK_NAMES)]
+    used = k.sum(1) > 0
+    if not used.any(): return
+    print(f"== collide, fixed part split (marks without a memory wait): mean cycles per WG-launch over {int(used.sum())} workgroups")
+    for i, n in enumerate(PHK_NAMES):
+        print(f"   phk {i:2d} {n:52s} {k[used, i].mean() / launches:9.0f}")
+    print(f"   sum {k[used].sum(1).mean() / launches:9.0f}")
+
+
 POST_B = [0, 1, 2, 3, 4]     # k_env_post_b_team keeps its own rows (the upper half, PHB in csrc/go2sim.hip): 0 reset, 1 staging + draws, 2 observations, 3 privileged tail, 4 copies
 if len(sys.argv) > 3 and sys.argv[3] == "each":
     # one read-out per env step: what a single launch waits for is its slowest workgroup, which per-run sums average away
@@ -159,3 +173,4 @@ for g, ids in GROUPS.items():
         if sub[:, k].sum() == 0:
             continue
         print(f"   phase {i:2d} {NAMES.get(i, ''):24s} mean {sub[used, k].mean() / launches:9.0f} ({100 * sub[used, k].sum() / tot[used].sum():5.1f}%)   slowest 1% {sub[top, k].mean() / launches:9.0f} ({100 * sub[top, k].sum() / tot[top].sum():5.1f}%)")
+print_phk(a, launches)
