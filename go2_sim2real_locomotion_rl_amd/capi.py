@@ -44,42 +44,28 @@ def _parse_header(path=HEADER):
 
 
 C, DECLARED_FUNCS = _parse_header()
-# the policy-inference entry points (include/go2sim_policy.h) live in the same two libraries
-_C_POLICY, _DECL_POLICY = _parse_header(os.path.join(REPO_ROOT, "include", "go2sim_policy.h"))
-C.update(_C_POLICY)
-DECLARED_FUNCS = DECLARED_FUNCS + _DECL_POLICY
-# the PPO update (include/go2sim_train.h) exists in the product library only: it has no go2sim_cpu_ twin, so its functions are a list of their own
-TRAIN_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_train.h")
-_C_TRAIN, DECLARED_TRAIN_FUNCS = _parse_header(TRAIN_HEADER)
-C.update(_C_TRAIN)
-# the recurrent (LSTM) policy (include/go2sim_rnn.h): the memory cell and the update through time; product library only, a list of its own as well
-RNN_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_rnn.h")
-_C_RNN, DECLARED_RNN_FUNCS = _parse_header(RNN_HEADER)
-C.update(_C_RNN)
-# the empirical observation normaliser (include/go2sim_norm.h): product library only, a list of its own
-NORM_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_norm.h")
-_C_NORM, DECLARED_NORM_FUNCS = _parse_header(NORM_HEADER)
-C.update(_C_NORM)
-# the LIDAR terrain scan (include/go2sim_lidar.h): product library only, a list of its own
-LIDAR_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_lidar.h")
-_C_LIDAR, DECLARED_LIDAR_FUNCS = _parse_header(LIDAR_HEADER)
-C.update(_C_LIDAR)
-# the four-value stair info (include/go2sim_stairinfo.h): product library only, a list of its own
-STAIRINFO_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_stairinfo.h")
-_C_STAIRINFO, DECLARED_STAIRINFO_FUNCS = _parse_header(STAIRINFO_HEADER)
-C.update(_C_STAIRINFO)
-# teacher-student distillation (include/go2sim_distill.h): product library only, a list of its own
-DISTILL_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_distill.h")
-_C_DISTILL, DECLARED_DISTILL_FUNCS = _parse_header(DISTILL_HEADER)
-C.update(_C_DISTILL)
-# distillation with a recurrent student (include/go2sim_rdistill.h): product library only, a list of its own
-RDISTILL_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_rdistill.h")
-_C_RDISTILL, DECLARED_RDISTILL_FUNCS = _parse_header(RDISTILL_HEADER)
-C.update(_C_RDISTILL)
-# the hidden-layer activation of an MLP (include/go2sim_activation.h): product library only, a list of its own
-ACT_HEADER = os.path.join(REPO_ROOT, "include", "go2sim_activation.h")
-_C_ACT, DECLARED_ACT_FUNCS = _parse_header(ACT_HEADER)
-C.update(_C_ACT)
+PRODUCT_ONLY_FUNCS = []
+
+
+def _product_header(name, funcs=PRODUCT_ONLY_FUNCS):
+    """include/go2sim_<name>.h: its constants go into C, its functions onto `funcs` -- by default the list of what only the product library has (no
+    go2sim_cpu_ twin; the diagnostic and shape builds do not carry it either).  -> (path, the header's declared functions)"""
+    path = os.path.join(REPO_ROOT, "include", f"go2sim_{name}.h")
+    consts, decls = _parse_header(path)
+    C.update(consts)
+    funcs.extend(decls)
+    return path, decls
+
+
+_product_header("policy", DECLARED_FUNCS)                                      # policy inference lives in both libraries
+TRAIN_HEADER, DECLARED_TRAIN_FUNCS = _product_header("train")                  # the PPO update
+RNN_HEADER, DECLARED_RNN_FUNCS = _product_header("rnn")                        # the recurrent (LSTM) policy: the memory cell and the update through time
+NORM_HEADER, DECLARED_NORM_FUNCS = _product_header("norm")                     # the empirical observation normaliser
+LIDAR_HEADER, DECLARED_LIDAR_FUNCS = _product_header("lidar")                  # the LIDAR terrain scan
+STAIRINFO_HEADER, DECLARED_STAIRINFO_FUNCS = _product_header("stairinfo")      # the four-value stair info
+DISTILL_HEADER, DECLARED_DISTILL_FUNCS = _product_header("distill")            # teacher-student distillation
+RDISTILL_HEADER, DECLARED_RDISTILL_FUNCS = _product_header("rdistill")         # distillation with a recurrent student
+ACT_HEADER, DECLARED_ACT_FUNCS = _product_header("activation")                 # the hidden-layer activation of an MLP
 # train_cfg["policy"]["activation"] as rsl_rl's resolve_nn_activation spells it -> GO2SIM_ACT_*
 ACTIVATIONS = {n: C["GO2SIM_ACT_" + n.upper()] for n in ("elu", "selu", "relu", "lrelu", "tanh", "sigmoid", "identity")}
 
@@ -194,7 +180,7 @@ class Go2SimLib:
             fn = getattr(self.lib, prefix + name[len("go2sim_"):])
             fn.restype = ctypes.c_int
         if self.is_device:
-            for name in DECLARED_TRAIN_FUNCS + DECLARED_RNN_FUNCS + DECLARED_NORM_FUNCS + DECLARED_LIDAR_FUNCS + DECLARED_STAIRINFO_FUNCS + DECLARED_DISTILL_FUNCS + DECLARED_RDISTILL_FUNCS + DECLARED_ACT_FUNCS:     # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
+            for name in PRODUCT_ONLY_FUNCS:                                    # the diagnostic and shape builds (build.build_hip_variant) do not carry the update
                 if hasattr(self.lib, name):
                     getattr(self.lib, name).restype = ctypes.c_int
 

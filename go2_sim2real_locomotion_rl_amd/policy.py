@@ -17,14 +17,20 @@ Random numbers come from the library's counter-based Philox stream (seed, row, s
 config, not of the checkpoint.
 
 ``ActorCriticRecurrent`` (below) is ``rsl_rl.modules.ActorCriticRecurrent`` with one LSTM layer per network (include/go2sim_rnn.h): the same surface plus
-``reset(dones)`` / ``get_hidden_states()``, and the keys ``memory_{a,c}.rnn.{weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0}``.
+``reset(dones)`` / ``get_hidden_states()``, and the four ``nn.LSTM`` keys of ``memory_{a,c}.rnn.`` (module_core.lstm_shapes).
+
+What the two classes share with distillation's modules -- the initial draws, the key lists, the memories' state, the device set-up and the create-or-set of a
+network -- is module_core.py; this file keeps the handles (``Mlp``, ``Lstm``), the launches and what is particular to the two classes.
 """
 import ctypes
 
 import numpy as np
 import torch
 
-from .capi import ACTIVATIONS, Go2SimError, Handle, _ptr, load_hip_lib
+from .capi import ACTIVATIONS, Go2SimError, Handle, _ptr
+from .module_core import (LSTM_KEYS, MemoryState, PolicyModule, actor_critic_init, actor_critic_recurrent_init, check_lstm_config, hidden_state_views,  # noqa: F401
+                          lstm_shapes)
+from .ppo import PpoHandle, unflatten
 
 
 def resolve_activation(name):
@@ -104,61 +110,38 @@ def policy_act(lib, actor, critic, obs, critic_obs, std, n_rows, seed, step, det
     lib.check(rc, "policy_act")
 
 
-class ActorCritic:
-    is_recurrent = False
+class ActorCritic(PolicyModule):
+    _mdims = None                                                              # the memories' ((n_in, H), (n_in, H)): the recurrent subclass's
 
     def __init__(self, num_actor_obs, num_critic_obs, num_actions, actor_hidden_dims=(512, 256, 128), critic_hidden_dims=(512, 256, 128),
                  activation="elu", init_noise_std=1.0, *, device=None, seed=1, **kwargs):
         self.activation = resolve_activation(activation)                          # before anything touches the device: a refusal needs no GPU
-        if not torch.cuda.is_available():
-            raise Go2SimError("no ROCm GPU visible: the go2sim product path has no CPU fallback")
-        self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.num_actions = num_actions
-        self._L = load_hip_lib()
+        PolicyModule.__init__(self, num_actions, device, seed)
         self._adims = [num_actor_obs, *actor_hidden_dims, num_actions]
         self._cdims = [num_critic_obs, *critic_hidden_dims, 1]
-        g = torch.Generator().manual_seed(seed)
-        sd = {}
-        for prefix, dims in (("actor", self._adims), ("critic", self._cdims)):      # nn.Linear default init (kaiming_uniform(a=sqrt 5))
-            for l in range(len(dims) - 1):
-                bound = 1.0 / (dims[l] ** 0.5)
-                sd[f"{prefix}.{2 * l}.weight"] = (torch.rand(dims[l + 1], dims[l], generator=g) * 2 - 1) * bound
-                sd[f"{prefix}.{2 * l}.bias"] = (torch.rand(dims[l + 1], generator=g) * 2 - 1) * bound
-        sd["std"] = init_noise_std * torch.ones(num_actions)
-        self._actor = self._critic = self._trainer = None
-        self.std = torch.ones(num_actions, device=self.device)
-        self.load_state_dict(sd)
-        self._seed, self._step = int(seed), 0
-        self._bufs = {}
+        self.load_state_dict(self._initial_state(init_noise_std, seed))
 
     # ---- parameters ------------------------------------------------------------------------------
+    def _initial_state(self, init_noise_std, seed):
+        return actor_critic_init(self._adims, self._cdims, init_noise_std, seed)
+
+    def _parts(self):
+        return [("_actor", "mlp", "actor", self._adims), ("_critic", "mlp", "critic", self._cdims)]
+
     def load_state_dict(self, state_dict, strict=True):
-        pa, da = flatten_sequential(state_dict, "actor", len(self._adims) - 1)
-        pc, dc = flatten_sequential(state_dict, "critic", len(self._cdims) - 1)
-        if da != self._adims or dc != self._cdims:
-            raise Go2SimError(f"state dict has layer sizes {da} / {dc}, expected {self._adims} / {self._cdims}")
-        dev = self.device.index or 0
-        if self._actor is None:
-            self._actor, self._critic = Mlp(self._L, da, pa, dev, self.activation), Mlp(self._L, dc, pc, dev, self.activation)
-        else:
-            self._actor.set_params(pa); self._critic.set_params(pc)
-        self.std.copy_(state_dict["std"].detach().reshape(self.num_actions))     # in place: std stays the device tensor the update kernels write
-        self._state = {k: (v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in state_dict.items()}
+        self._set_parts(self._parts(), state_dict)
+        self._set_std(state_dict)
         return True
 
     def state_dict(self):
         """The parameters as they are on the device: once a trainer is attached the optimizer has written them there, and the host copy of the last
         load_state_dict is stale."""
         if self._trainer is None:
-            return dict(self._state)
-        from .ppo import unflatten
-
-        return unflatten(self._trainer.export("PARAMS", self.std).cpu(), self._adims, self._cdims)
+            return self._host_state()
+        return unflatten(self._trainer.export("PARAMS", self.std).cpu(), self._adims, self._cdims, self._mdims)
 
     def attach_trainer(self, max_rows_per_minibatch, **hyper):
         """The go2sim_ppo handle (ppo.PpoHandle) that updates this policy's device parameters in place; the optimizer state lives in it."""
-        from .ppo import PpoHandle
-
         self._trainer = PpoHandle(self._L, self._actor, self._critic, self.num_actions, max_rows_per_minibatch, device=self.device, **hyper)
         return self._trainer
 
@@ -179,13 +162,6 @@ class ActorCritic:
         return loaded, skipped, int(ckpt.get("iter", 0) or 0)
 
     # ---- rsl_rl ActorCritic surface (inference side) ---------------------------------------------------
-    def _buf(self, name, shape):
-        t = self._bufs.get(name)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = torch.empty(*shape, device=self.device, dtype=torch.float32)
-            self._bufs[name] = t
-        return t
-
     def _run(self, obs, critic_obs, deterministic):
         B = obs.shape[0]
         obs = obs.to(device=self.device, dtype=torch.float32).contiguous()
@@ -221,14 +197,6 @@ class ActorCritic:
         return (-((actions - self._mean) ** 2) / (2 * var) - torch.log(self.std) - 0.9189385332046727).sum(-1)
 
     @property
-    def action_mean(self):
-        return self._mean
-
-    @property
-    def action_std(self):
-        return self.std.expand_as(self._mean)
-
-    @property
     def values(self):
         return None if self._values is None else self._values.unsqueeze(-1)
 
@@ -236,19 +204,8 @@ class ActorCritic:
     def actions_log_prob(self):
         return self._logp
 
-    def reset(self, dones=None):
-        pass
-
 
 # ---- recurrent policy (include/go2sim_rnn.h) --------------------------------------------------------------------------------------------------
-LSTM_KEYS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
-
-
-def lstm_shapes(n_in, n_hidden):
-    """[(key suffix, shape)] of one memory in state-dict (and flat) order"""
-    return [("weight_ih_l0", (4 * n_hidden, n_in)), ("weight_hh_l0", (4 * n_hidden, n_hidden)), ("bias_ih_l0", (4 * n_hidden,)), ("bias_hh_l0", (4 * n_hidden,))]
-
-
 def flatten_lstm(state_dict, prefix):
     """[weight_ih, weight_hh, bias_ih, bias_hh] of ``prefix.rnn.*`` as one float32 vector (the layout go2sim_lstm_create takes) + (n_in, n_hidden)."""
     ts = []
@@ -295,86 +252,42 @@ def lstm_step(lib, mem_a, x_a, h_in_a, c_in_a, h_out_a, c_out_a, mem_c=None, x_c
 class ActorCriticRecurrent(ActorCritic):
     """``rsl_rl.modules.ActorCriticRecurrent`` (rsl-rl-lib==2.2.4) with ``rnn_type="lstm"`` and one layer: ``memory_a = LSTM(num_actor_obs -> H)`` in front of
     the actor MLP, ``memory_c = LSTM(num_critic_obs -> H)`` in front of the critic MLP (include/go2sim_rnn.h).  ``act`` steps memory_a (and, given critic
-    observations, memory_c), ``evaluate`` steps memory_c, ``reset(dones)`` zeroes the state of the done envs.  State-dict keys beside the parent's:
-    ``memory_{a,c}.rnn.{weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0}``."""
+    observations, memory_c), ``evaluate`` steps memory_c, ``reset(dones)`` zeroes the state of the done envs at once.  State-dict keys beside the parent's:
+    the four ``nn.LSTM`` keys under ``memory_{a,c}.rnn.``."""
     is_recurrent = True
 
     def __init__(self, num_actor_obs, num_critic_obs, num_actions, actor_hidden_dims=(256, 256, 256), critic_hidden_dims=(256, 256, 256), activation="elu",
                  init_noise_std=1.0, rnn_type="lstm", rnn_hidden_size=256, rnn_num_layers=1, *, device=None, seed=1, **kwargs):
-        from .capi import C
-
-        if str(rnn_type).lower() != "lstm":
-            raise Go2SimError(f"go2sim's recurrent policy is an LSTM; rnn_type {rnn_type!r} is not implemented")
-        if int(rnn_num_layers) != 1:
-            raise Go2SimError(f"go2sim's recurrent policy has one LSTM layer, got rnn_num_layers = {rnn_num_layers}")
-        H = int(rnn_hidden_size)
-        if H < 1 or H > C["GO2SIM_MLP_MAX_WIDTH"]:
-            raise Go2SimError(f"rnn_hidden_size must be in 1 .. {C['GO2SIM_MLP_MAX_WIDTH']} (GO2SIM_MLP_MAX_WIDTH), got {H}")
-        self.rnn_hidden_size = H
+        H = self.rnn_hidden_size = check_lstm_config("ActorCriticRecurrent", rnn_type, rnn_num_layers, rnn_hidden_size, "rnn_hidden_size")
         self._mdims = ((int(num_actor_obs), H), (int(num_critic_obs), H))
-        g = torch.Generator().manual_seed(int(seed) + 0x5eed)              # nn.LSTM's default init: every tensor uniform(-1 / sqrt(H), 1 / sqrt(H))
-        self._mem_init = {}
-        for prefix, (n_in, _) in (("memory_a", self._mdims[0]), ("memory_c", self._mdims[1])):
-            for k, shape in lstm_shapes(n_in, H):
-                self._mem_init[f"{prefix}.rnn.{k}"] = (torch.rand(*shape, generator=g) * 2 - 1) / (H ** 0.5)
-        self._mem = None
-        self._hid = None
         super().__init__(H, H, num_actions, actor_hidden_dims, critic_hidden_dims, activation, init_noise_std, device=device, seed=seed, **kwargs)
+        self._hid = (MemoryState(H, self.device), MemoryState(H, self.device))      # memory_a's, memory_c's
 
     # ---- parameters ------------------------------------------------------------------------------
-    def load_state_dict(self, state_dict, strict=True):
-        if self._mem is None and not any(k.startswith("memory_") for k in state_dict):
-            state_dict = {**state_dict, **self._mem_init}                   # the constructor's own call: the MLPs' draws, the memories' draws
-        flats = []
-        for prefix, dims in (("memory_a", self._mdims[0]), ("memory_c", self._mdims[1])):
-            p, d = flatten_lstm(state_dict, prefix)
-            if d != dims:
-                raise Go2SimError(f"state dict has {prefix} sizes {d}, expected {dims}")
-            flats.append(p)
-        dev = self.device.index or 0
-        if self._mem is None:
-            self._mem = [Lstm(self._L, *self._mdims[0], flats[0], dev), Lstm(self._L, *self._mdims[1], flats[1], dev)]
-        else:
-            self._mem[0].set_params(flats[0]); self._mem[1].set_params(flats[1])
-        return super().load_state_dict(state_dict, strict)
+    def _initial_state(self, init_noise_std, seed):
+        return actor_critic_recurrent_init(self._adims, self._cdims, self._mdims, init_noise_std, seed)
 
-    def state_dict(self):
-        if self._trainer is None:
-            return dict(self._state)
-        from .ppo import unflatten
-
-        return unflatten(self._trainer.export("PARAMS", self.std).cpu(), self._adims, self._cdims, self._mdims)
+    def _parts(self):
+        return super()._parts() + [("_mem_a", "lstm", "memory_a", self._mdims[0]), ("_mem_c", "lstm", "memory_c", self._mdims[1])]
 
     def attach_trainer(self, n_steps, max_envs_per_minibatch, **hyper):
         """The recurrent go2sim_ppo handle: workspaces for n_steps x max_envs_per_minibatch rows, the memories' parameters in the optimizer's vectors."""
-        from .ppo import PpoHandle
-
         self._trainer = PpoHandle(self._L, self._actor, self._critic, self.num_actions, int(n_steps) * int(max_envs_per_minibatch), device=self.device,
-                                  memories=tuple(self._mem), n_steps=int(n_steps), **hyper)
+                                  memories=(self._mem_a, self._mem_c), n_steps=int(n_steps), **hyper)
         return self._trainer
 
     # ---- the memories' state ---------------------------------------------------------------------------
-    def _state_for(self, B):
-        """{"a": [h, c, spare h], "c": [...]} of [B][H] device tensors, zero at the start"""
-        if self._hid is None or self._hid["a"][0].shape[0] != B:
-            z = lambda: torch.zeros(B, self.rnn_hidden_size, device=self.device, dtype=torch.float32)
-            self._hid = {"a": [z(), z(), z()], "c": [z(), z(), z()]}
-        return self._hid
-
     def _step_memories(self, obs, critic_obs):
         """One launch for the memories whose observations are given; -> (h_a or None, h_c or None)"""
         B = (obs if obs is not None else critic_obs).shape[0]
-        hid = self._state_for(B)
         args, outs = [], []
-        for key, mem, x in (("a", self._mem[0], obs), ("c", self._mem[1], critic_obs)):
+        for state, mem, x in ((self._hid[0].rows(B), self._mem_a, obs), (self._hid[1].rows(B), self._mem_c, critic_obs)):
             if x is None:
                 outs.append(None)
                 continue
-            x = x.to(device=self.device, dtype=torch.float32).contiguous()
-            h, c, spare = hid[key]
-            args += [mem, x, h, c, spare, c]
-            hid[key] = [spare, c, h]                                          # the step wrote the spare buffer: h' is the state now
-            outs.append(spare)
+            step = state.advance()
+            args += [mem, x.to(device=self.device, dtype=torch.float32).contiguous(), *step]
+            outs.append(step[2])
         lstm_step(self._L, *args, n_rows=B, stream=torch.cuda.current_stream(self.device).cuda_stream)
         return outs
 
@@ -386,19 +299,16 @@ class ActorCriticRecurrent(ActorCritic):
         _, h_c = self._step_memories(None, critic_observations)
         return super().evaluate(h_c)
 
+    def save_memory_state(self, h_a, c_a, h_c, c_c):
+        """The memories' state as the next step enters it, copied into the caller's [B][H] arrays: what PPO keeps of a rollout's first act."""
+        B = h_a.shape[0]
+        self._hid[0].rows(B).copy_entering(h_a, c_a); self._hid[1].rows(B).copy_entering(h_c, c_c)
+
     def reset(self, dones=None, hidden_states=None):
-        """Zero h and c of the done envs (all envs without `dones`)."""
-        if self._hid is None:
-            return
-        for key in ("a", "c"):
-            for t in self._hid[key][:2]:
-                if dones is None:
-                    t.zero_()
-                else:
-                    t.masked_fill_((dones.reshape(-1, 1) != 0).to(t.device), 0.0)
+        """Zero h and c of the done envs (all envs without `dones`), now."""
+        for state in self._hid:
+            state.zero(dones)
 
     def get_hidden_states(self):
-        """((h_a, c_a), (h_c, c_c)), each [1][B][H] as nn.LSTM shapes them; views of the live state (None before the first step)"""
-        if self._hid is None:
-            return None, None
-        return tuple((self._hid[k][0].unsqueeze(0), self._hid[k][1].unsqueeze(0)) for k in ("a", "c"))
+        """((h_a, c_a), (h_c, c_c)), each [1][B][H] as nn.LSTM shapes them; views of the live state (None, None before the first step)"""
+        return hidden_state_views(self._hid)

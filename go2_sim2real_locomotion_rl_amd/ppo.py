@@ -32,8 +32,9 @@ import torch
 
 from .capi import C, Go2SimError, PpoBatch, PpoCfg, PpoMirror, PpoRnnState, _ptr, load_hip_lib
 from .distributed import allgather_records, broadcast_from_rank0, is_multi, shard_seed
+from .module_core import memory_keys, mlp_keys, unflatten_keys
 from .rollout import RolloutStorage
-from .trainer import OptimizerState, TrainerHandle, mlp_keys, unflatten_keys
+from .trainer import OptimizerState, TrainerHandle
 
 VECS = ("PARAMS", "GRADS", "ADAM_M", "ADAM_V")
 
@@ -165,9 +166,7 @@ def state_dict_keys(adims, cdims, mdims=None):
     """[(key, shape)] in the flat order of go2sim_ppo_export; mdims = ((n_in, H) of memory_a, of memory_c) for a recurrent policy"""
     keys = mlp_keys("actor", adims) + mlp_keys("critic", cdims)
     if mdims is not None:
-        for prefix, (n_in, H) in zip(("memory_a", "memory_c"), mdims):
-            keys += [(f"{prefix}.rnn.weight_ih_l0", (4 * H, n_in)), (f"{prefix}.rnn.weight_hh_l0", (4 * H, H)), (f"{prefix}.rnn.bias_ih_l0", (4 * H,)),
-                     (f"{prefix}.rnn.bias_hh_l0", (4 * H,))]
+        keys += memory_keys("memory_a", *mdims[0]) + memory_keys("memory_c", *mdims[1])
     keys.append(("std", (adims[-1],)))
     return keys
 
@@ -181,6 +180,8 @@ def flatten(sd, adims, cdims, mdims=None):
 
 
 class PPO(OptimizerState):
+    result_names = ("value_loss", "surrogate_loss", "entropy")                # of what update() returns, as the runner logs them
+
     def __init__(self, policy, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95, value_loss_coef=1.0, entropy_coef=0.0,
                  learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device=None, *, seed=1, group=None, symmetry_cfg=None,
                  **kwargs):
@@ -268,9 +269,7 @@ class PPO(OptimizerState):
     def act(self, obs, critic_obs):
         t = self.t
         if self.recurrent and t == 0:                                      # the state the update's walk through time starts from
-            hid = self.policy._state_for(obs.shape[0])
-            for dst, src in zip(self._saved, (hid["a"][0], hid["a"][1], hid["c"][0], hid["c"][1])):
-                dst.copy_(src)
+            self.policy.save_memory_state(*self._saved)
         actions = self.policy.act(obs, critic_obs)
         self.obs[t].copy_(obs); self.critic_obs[t].copy_(critic_obs); self.actions[t].copy_(actions)
         self.old_log_prob[t].copy_(self.policy.actions_log_prob); self.old_mu[t].copy_(self.policy.action_mean); self.old_sigma[t].copy_(self.policy.action_std)

@@ -134,41 +134,44 @@ class OnPolicyRunner:
             return y, y
         return norm_step(self.obs_normalizer, obs, self.critic_obs_normalizer, critic, update=update, group=self.group)
 
-    def learn(self, num_learning_iterations, init_at_random_ep_len=False):
+    def _rows(self, obs, observations, update):
+        """The env's rows of one step as the pair ``alg.act`` takes, normalised where a normaliser exists (`update`: the learning ones count the rows):
+        (actor rows, critic rows) for PPO, (student rows, teacher rows) for distillation."""
         if self.distill:
-            return self._learn_distill(num_learning_iterations, init_at_random_ep_len)
+            return self._distill_rows(obs, observations, update)
+        obs, critic_raw, _ = self._roles(obs, observations)
+        if self.empirical_normalization:
+            return self._normalize(obs, critic_raw, update=update)
+        return obs, (obs if critic_raw is None else critic_raw)
+
+    def learn(self, num_learning_iterations, init_at_random_ep_len=False):
         env, alg, dev = self.env, self.alg, self.device
+        if self.distill and not self.policy.loaded_teacher:
+            raise Go2SimError("learn(): no teacher has been loaded; load a PPO checkpoint (the teacher) or a distillation checkpoint with runner.load(path) first")
         if init_at_random_ep_len:
             env.episode_length_buf = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
         obs, extras = env.get_observations()
-        obs, critic_raw, _ = self._roles(obs, extras["observations"])
-        critic_obs = obs if critic_raw is None else critic_raw
-        norm = self.empirical_normalization
-        if norm:                                                              # the starting observations: current statistics, not counted
-            obs, critic_obs = self._normalize(obs, critic_raw, update=False)
+        rows = self._rows(obs, extras["observations"], update=False)          # the starting observations: current statistics, not counted
         log = []
         start = self.current_learning_iteration
         for it in range(start, start + num_learning_iterations):
             acc = torch.zeros(3, device=dev, dtype=torch.float64)            # finished episodes: count, sum of rewards, sum of lengths
             for _ in range(self.num_steps_per_env):
-                actions = alg.act(obs, critic_obs)
+                actions = alg.act(*rows)
                 obs, rewards, dones, infos = env.step(actions)
-                obs, critic_raw, _ = self._roles(obs, infos["observations"])
-                critic_obs = obs if critic_raw is None else critic_raw
-                if norm:
-                    obs, critic_obs = self._normalize(obs, critic_raw, update=True)
+                rows = self._rows(obs, infos["observations"], update=True)
                 alg.process_env_step(rewards, dones, infos)
                 self._count_episodes(acc, rewards, dones)
-            if getattr(env, "_shared_globals", False):
+            if not self.distill and getattr(env, "_shared_globals", False):
                 env.sync_globals(self.group)                                   # one curriculum and one set of global DR draws for all shards
-            alg.compute_returns(critic_obs)
-            value_loss, surrogate_loss, entropy = alg.update()
-            n, rs, ls = sum_in_rank_order(acc, self.group).tolist()            # every rank logs the global means
+            alg.compute_returns(rows[1])                                       # nothing for distillation: the targets are the stored teacher actions
+            results = alg.update()
+            n, rs, ls = (acc if self.distill else sum_in_rank_order(acc, self.group)).tolist()      # every rank logs the global means; distillation is one rank
             if n > 0:
                 self._last_means = (rs / n, ls / n)
             self.current_learning_iteration = it + 1
-            log.append({"iteration": it, "mean_reward": self._last_means[0], "mean_episode_length": self._last_means[1], "value_loss": value_loss,
-                        "surrogate_loss": surrogate_loss, "entropy": entropy, "learning_rate": alg.learning_rate})
+            log.append({"iteration": it, "mean_reward": self._last_means[0], "mean_episode_length": self._last_means[1],
+                        **dict(zip(alg.result_names, results if isinstance(results, tuple) else (results,))), "learning_rate": alg.learning_rate})
             if alg.symmetry is not None:
                 log[-1]["symmetry_loss"] = alg.symmetry_loss
             if self.log_dir is not None and self.save_interval > 0 and (it + 1) % self.save_interval == 0:
@@ -197,88 +200,28 @@ class OnPolicyRunner:
             t_obs = norm_step(self.privileged_obs_normalizer, t_obs, update=False)[0]
         return s_obs, t_obs
 
-    def _learn_distill(self, num_learning_iterations, init_at_random_ep_len):
-        env, alg, dev = self.env, self.alg, self.device
-        if not self.policy.loaded_teacher:
-            raise Go2SimError("learn(): no teacher has been loaded; load a PPO checkpoint (the teacher) or a distillation checkpoint with runner.load(path) first")
-        if init_at_random_ep_len:
-            env.episode_length_buf = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
-        obs, extras = env.get_observations()
-        s_obs, t_obs = self._distill_rows(obs, extras["observations"], update=False)      # the starting observations are not counted
-        log = []
-        start = self.current_learning_iteration
-        for it in range(start, start + num_learning_iterations):
-            acc = torch.zeros(3, device=dev, dtype=torch.float64)
-            for _ in range(self.num_steps_per_env):
-                actions = alg.act(s_obs, t_obs)
-                obs, rewards, dones, infos = env.step(actions)
-                s_obs, t_obs = self._distill_rows(obs, infos["observations"], update=True)
-                alg.process_env_step(rewards, dones, infos)
-                self._count_episodes(acc, rewards, dones)
-            behavior_loss = alg.update()                                       # no returns to compute: the targets are the stored teacher actions
-            n, rs, ls = acc.tolist()
-            if n > 0:
-                self._last_means = (rs / n, ls / n)
-            self.current_learning_iteration = it + 1
-            log.append({"iteration": it, "mean_reward": self._last_means[0], "mean_episode_length": self._last_means[1], "behavior_loss": behavior_loss,
-                        "learning_rate": alg.learning_rate})
-            if self.log_dir is not None and self.save_interval > 0 and (it + 1) % self.save_interval == 0:
-                self.save(os.path.join(self.log_dir, f"model_{it + 1}.pt"))
-        if self.log_dir is not None:
-            self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
-        return log
-
-    def _load_distill(self, ckpt, path, load_optimizer):
+    def _load_distill(self, ckpt, path):
         """A PPO checkpoint is the teacher: teacher.* <- actor.* (for a StudentTeacherRecurrent with a recurrent teacher also memory_t.* <- memory_a.*), its
         actor normaliser becomes the frozen teacher normaliser; the student, the iteration and the optimizer are untouched.  A distillation checkpoint
-        resumes: student, teacher, (the memories,) std, both normalisers, optimizer, iteration."""
+        resumes: student, teacher, (the memories,) std and both normalisers.  -> resume"""
         resume = self.policy.load_state_dict(ckpt["model_state_dict"])
         t_norm = ckpt.get("privileged_obs_norm_state_dict" if resume else "obs_norm_state_dict")
         if t_norm is not None:
             if self.privileged_obs_normalizer is None:
-                n_teacher_obs = self.policy._tmem[0] if getattr(self.policy, "_tmem", None) else self.policy._tdims[0]   # a recurrent teacher's memory reads the rows
-                self.privileged_obs_normalizer = EmpiricalNormalization([n_teacher_obs], until=1.0e8, device=self.device).eval()
+                self.privileged_obs_normalizer = EmpiricalNormalization([self.policy.num_teacher_obs], until=1.0e8, device=self.device).eval()
             self.privileged_obs_normalizer.load_state_dict(t_norm)
         elif resume:
             self.privileged_obs_normalizer = None
-        if not resume:
-            return ckpt.get("infos")
-        if self.empirical_normalization:
+        if resume and self.empirical_normalization:
             if ckpt.get("obs_norm_state_dict") is None:
                 raise Go2SimError(f"{path}: empirical_normalization is on, but the distillation checkpoint has no obs_norm_state_dict")
             self.obs_normalizer.load_state_dict(ckpt["obs_norm_state_dict"])
-        elif ckpt.get("obs_norm_state_dict") is not None:
+        elif resume and ckpt.get("obs_norm_state_dict") is not None:
             raise Go2SimError(f"{path}: the checkpoint's student was trained on normalised observations (obs_norm_state_dict), but empirical_normalization "
                               "is off in this runner's train_cfg")
-        opt = ckpt.get("optimizer_state_dict") or {}
-        if load_optimizer and "exp_avg" in opt:
-            self.alg.load_optimizer_state_dict(opt)
-            self.policy._step = int(opt.get("policy_noise_step", self.policy._step))
-        self.current_learning_iteration = int(ckpt.get("iter", 0) or 0)
-        return ckpt.get("infos")
+        return resume
 
-    def save(self, path, infos=None):
-        """rsl_rl 2.2.4 checkpoint layout (eval_io.read_checkpoint): model_state_dict, optimizer_state_dict (Adam's m, v, step, learning rate), iter, infos."""
-        if self.rank != 0:                                                     # the ranks hold the same bits: rank 0 writes them
-            return
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        opt = self.alg.optimizer_state_dict()
-        opt["policy_noise_step"] = int(self.policy._step)
-        if self.distill:
-            save_checkpoint(path, self.policy.state_dict(), opt, self.current_learning_iteration, infos,
-                            obs_norm_state_dict=self.obs_normalizer.state_dict() if self.obs_normalizer is not None else None,
-                            privileged_obs_norm_state_dict=self.privileged_obs_normalizer.state_dict() if self.privileged_obs_normalizer is not None else None)
-            return
-        if self.empirical_normalization:
-            save_checkpoint(path, self.policy.state_dict(), opt, self.current_learning_iteration, infos, obs_norm_state_dict=self.obs_normalizer.state_dict(),
-                            critic_obs_norm_state_dict=self.critic_obs_normalizer.state_dict())
-        else:
-            save_checkpoint(path, self.policy.state_dict(), opt, self.current_learning_iteration, infos)
-
-    def load(self, path, load_optimizer=True):
-        ckpt = read_checkpoint(path)
-        if self.distill:
-            return self._load_distill(ckpt, path, load_optimizer)
+    def _load_ppo(self, ckpt, path):
         has_norm = [k for k in ("obs_norm_state_dict", "critic_obs_norm_state_dict") if ckpt.get(k) is not None]
         if self.empirical_normalization and len(has_norm) != 2:
             raise Go2SimError(f"{path}: empirical_normalization is on, but the checkpoint has no obs_norm_state_dict / critic_obs_norm_state_dict")
@@ -286,15 +229,34 @@ class OnPolicyRunner:
             raise Go2SimError(f"{path}: the checkpoint carries {has_norm} (its policy was trained on normalised observations), but empirical_normalization "
                               "is off in this runner's train_cfg")
         self.policy.load_state_dict(ckpt["model_state_dict"])
-        opt = ckpt.get("optimizer_state_dict") or {}
-        if load_optimizer and "exp_avg" in opt:
-            self.alg.load_optimizer_state_dict(opt)
-            self.policy._step = int(opt.get("policy_noise_step", self.policy._step))
         self.alg.broadcast_parameters()                                        # every rank read the file; rank 0's parameters are the ones in force
         if self.empirical_normalization:                                      # every rank read the same file: nothing to broadcast
             self.obs_normalizer.load_state_dict(ckpt["obs_norm_state_dict"])
             self.critic_obs_normalizer.load_state_dict(ckpt["critic_obs_norm_state_dict"])
-        self.current_learning_iteration = int(ckpt.get("iter", 0) or 0)
+        return True
+
+    def save(self, path, infos=None):
+        """rsl_rl 2.2.4 checkpoint layout (eval_io.read_checkpoint): model_state_dict, optimizer_state_dict (Adam's m, v, step, learning rate), iter, infos,
+        and the state of the normalisers that exist."""
+        if self.rank != 0:                                                     # the ranks hold the same bits: rank 0 writes them
+            return
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        opt = self.alg.optimizer_state_dict()
+        opt["policy_noise_step"] = int(self.policy.noise_step)
+        norm_state = lambda normalizer: None if normalizer is None else normalizer.state_dict()
+        save_checkpoint(path, self.policy.state_dict(), opt, self.current_learning_iteration, infos, obs_norm_state_dict=norm_state(self.obs_normalizer),
+                        critic_obs_norm_state_dict=norm_state(self.critic_obs_normalizer), privileged_obs_norm_state_dict=norm_state(self.privileged_obs_normalizer))
+
+    def load(self, path, load_optimizer=True):
+        """A checkpoint of this runner's own kind resumes the run: model, normalisers, optimizer, the policy's noise step, iteration.  A distillation runner
+        also takes a PPO checkpoint, as its teacher (_load_distill); that is no resume and leaves the rest alone."""
+        ckpt = read_checkpoint(path)
+        if (self._load_distill if self.distill else self._load_ppo)(ckpt, path):
+            opt = ckpt.get("optimizer_state_dict") or {}
+            if load_optimizer and "exp_avg" in opt:
+                self.alg.load_optimizer_state_dict(opt)
+                self.policy.noise_step = int(opt.get("policy_noise_step", self.policy.noise_step))
+            self.current_learning_iteration = int(ckpt.get("iter", 0) or 0)
         return ckpt.get("infos")
 
     def get_inference_policy(self, device=None):

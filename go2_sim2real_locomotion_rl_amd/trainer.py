@@ -1,6 +1,6 @@
 """What the update handles and algorithms of ppo.py and distillation.py share on the host: the handle surface that include/go2sim_train.h and
-include/go2sim_distill.h spell alike (sizes, flat and padded exports, the step count, the statistics), the state-dict key lists of the flat vectors and
-the optimizer-state checkpoint entries.  The device side of the same sharing is csrc/go2sim_trainer_host.h."""
+include/go2sim_distill.h spell alike (sizes, flat and padded exports, the step count, the statistics) and the optimizer-state checkpoint entries.  The
+state-dict key lists of the flat vectors are module_core.py's.  The device side of the same sharing is csrc/go2sim_trainer_host.h."""
 import ctypes
 
 import torch
@@ -62,26 +62,6 @@ class TrainerHandle(Handle):
         """float64 device tensor of the handle's statistics (GO2SIM_<PREFIX>_ST_*); no synchronisation"""
         self._call("stats", _ptr(self._stats))
         return self._stats
-
-
-def mlp_keys(prefix, dims):
-    """[(key, shape)] of one network in state-dict (and flat) order"""
-    keys = []
-    for l in range(len(dims) - 1):
-        keys += [(f"{prefix}.{2 * l}.weight", (dims[l + 1], dims[l])), (f"{prefix}.{2 * l}.bias", (dims[l + 1],))]
-    return keys
-
-
-def unflatten_keys(flat, keys):
-    """a flat vector sliced by a [(key, shape)] list -> {key: tensor}"""
-    out, o = {}, 0
-    for k, shape in keys:
-        n = 1
-        for s in shape:
-            n *= s
-        out[k] = flat[o:o + n].reshape(shape).clone()
-        o += n
-    return out
 
 
 class OptimizerState:
