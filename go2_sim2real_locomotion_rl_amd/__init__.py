@@ -15,9 +15,10 @@ from .model_blob import load_model_json, pack_model  # noqa: F401
 from .normalization import EmpiricalNormalization  # noqa: F401
 from .policy import ActorCritic, ActorCriticRecurrent  # noqa: F401
 from .ppo import PPO  # noqa: F401
+from .rnd import RandomNetworkDistillation  # noqa: F401
 from .rollout import RolloutStorage  # noqa: F401
 from .runner import OnPolicyRunner  # noqa: F401
 from .stairinfo import StairInfo  # noqa: F401
 
-__all__ = ["Go2Env", "ActorCritic", "ActorCriticRecurrent", "RolloutStorage", "PPO", "Distillation", "StudentTeacher", "StudentTeacherRecurrent", "distill_windows", "rdistill_schedule", "teacher_state_from_checkpoint", "OnPolicyRunner", "EmpiricalNormalization", "LidarScan", "StairInfo", "init", "C", "Go2Sim", "Go2SimError", "load_hip_lib", "flatten_walk_cfg", "flatten_base_cfg", "get_walk_cfgs", "get_stair_cfgs", "get_stair_lidar_cfgs", "get_stair_info_cfg", "get_stair_info_cfgs",
+__all__ = ["Go2Env", "ActorCritic", "ActorCriticRecurrent", "RolloutStorage", "PPO", "RandomNetworkDistillation", "Distillation", "StudentTeacher", "StudentTeacherRecurrent", "distill_windows", "rdistill_schedule", "teacher_state_from_checkpoint", "OnPolicyRunner", "EmpiricalNormalization", "LidarScan", "StairInfo", "init", "C", "Go2Sim", "Go2SimError", "load_hip_lib", "flatten_walk_cfg", "flatten_base_cfg", "get_walk_cfgs", "get_stair_cfgs", "get_stair_lidar_cfgs", "get_stair_info_cfg", "get_stair_info_cfgs",
            "get_crouch_cfgs", "get_jump_cfgs", "load_model_json", "pack_model", "load_cfgs", "save_cfgs", "read_checkpoint", "save_checkpoint", "allgather_records", "shard_envs", "shard_seed"]

@@ -15,12 +15,14 @@ HIP_SRC_LIDAR = os.path.join(_HERE, "csrc", "go2sim_lidar.hip")             # th
 HIP_SRC_STAIRINFO = os.path.join(_HERE, "csrc", "go2sim_stairinfo.hip")     # the four-value stair info (include/go2sim_stairinfo.h): product library only
 HIP_SRC_DISTILL = os.path.join(_HERE, "csrc", "go2sim_distill.hip")         # teacher-student distillation (include/go2sim_distill.h): product library only
 HIP_SRC_RDISTILL = os.path.join(_HERE, "csrc", "go2sim_rdistill.hip")       # distillation with a recurrent student (include/go2sim_rdistill.h): product library only
+HIP_SRC_RND = os.path.join(_HERE, "csrc", "go2sim_rnd.hip")                 # random network distillation (include/go2sim_rnd.h): product library only
 HIP_HDR_GJK = os.path.join(_HERE, "csrc", "go2sim_gjk_dev.h")
 HIP_HDR_MLP = os.path.join(_HERE, "csrc", "go2sim_mlp_dev.h")               # shared by go2sim_policy.hip and go2sim_train.hip
 HIP_HDR_LSTM = os.path.join(_HERE, "csrc", "go2sim_lstm_dev.h")             # the recurrent policy's kernels (include/go2sim_rnn.h), included by go2sim_train.hip
 HIP_HDR_TRAIN = os.path.join(_HERE, "csrc", "go2sim_train_dev.h")           # the forward-with-activations, backward and optimizer kernels go2sim_train.hip and go2sim_distill.hip share
 HIP_HDR_TRAINER = os.path.join(_HERE, "csrc", "go2sim_trainer_host.h")      # the host side the two share: optimizer state, packing, workspaces, the backward schedule
 HIP_HDR_DISTILL = os.path.join(_HERE, "csrc", "go2sim_distill_dev.h")       # the loss head and float64 sums go2sim_distill.hip and go2sim_rdistill.hip share
+HIP_HDR_NORM = os.path.join(_HERE, "csrc", "go2sim_norm_dev.h")             # the float64 moment code go2sim_norm.hip and go2sim_rnd.hip share
 HIP_LIB = os.path.join(_HERE, "csrc", "libgo2sim.so")
 ORACLE_SRC = os.path.join(REPO_ROOT, "oracle", "go2sim_cpu.cpp")
 ORACLE_SRC_POLICY = os.path.join(REPO_ROOT, "oracle", "policy_cpu.cpp")
@@ -47,11 +49,11 @@ def _headers():
 
 
 def build_hip(force=False, verbose=True):
-    if not force and _newer(HIP_LIB, HIP_SRC, HIP_SRC_POLICY, HIP_SRC_TRAIN, HIP_SRC_NORM, HIP_SRC_LIDAR, HIP_SRC_STAIRINFO, HIP_SRC_DISTILL, HIP_SRC_RDISTILL, HIP_HDR_GJK, HIP_HDR_MLP, HIP_HDR_LSTM, HIP_HDR_TRAIN, HIP_HDR_TRAINER,
-                            HIP_HDR_DISTILL, *_headers()):
+    if not force and _newer(HIP_LIB, HIP_SRC, HIP_SRC_POLICY, HIP_SRC_TRAIN, HIP_SRC_NORM, HIP_SRC_LIDAR, HIP_SRC_STAIRINFO, HIP_SRC_DISTILL, HIP_SRC_RDISTILL, HIP_SRC_RND, HIP_HDR_GJK, HIP_HDR_MLP, HIP_HDR_LSTM, HIP_HDR_TRAIN, HIP_HDR_TRAINER,
+                            HIP_HDR_DISTILL, HIP_HDR_NORM, *_headers()):
         return HIP_LIB
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    cmd = [hipcc, *HIP_FLAGS, HIP_SRC, HIP_SRC_POLICY, HIP_SRC_TRAIN, HIP_SRC_NORM, HIP_SRC_LIDAR, HIP_SRC_STAIRINFO, HIP_SRC_DISTILL, HIP_SRC_RDISTILL, "-o", HIP_LIB]
+    cmd = [hipcc, *HIP_FLAGS, HIP_SRC, HIP_SRC_POLICY, HIP_SRC_TRAIN, HIP_SRC_NORM, HIP_SRC_LIDAR, HIP_SRC_STAIRINFO, HIP_SRC_DISTILL, HIP_SRC_RDISTILL, HIP_SRC_RND, "-o", HIP_LIB]
     if verbose:
         print("[build]", " ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)

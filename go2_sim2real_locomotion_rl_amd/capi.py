@@ -66,6 +66,7 @@ STAIRINFO_HEADER, DECLARED_STAIRINFO_FUNCS = _product_header("stairinfo")      #
 DISTILL_HEADER, DECLARED_DISTILL_FUNCS = _product_header("distill")            # teacher-student distillation
 RDISTILL_HEADER, DECLARED_RDISTILL_FUNCS = _product_header("rdistill")         # distillation with a recurrent student
 ACT_HEADER, DECLARED_ACT_FUNCS = _product_header("activation")                 # the hidden-layer activation of an MLP
+RND_HEADER, DECLARED_RND_FUNCS = _product_header("rnd")                        # random network distillation: the intrinsic reward and the predictor's update
 # train_cfg["policy"]["activation"] as rsl_rl's resolve_nn_activation spells it -> GO2SIM_ACT_*
 ACTIVATIONS = {n: C["GO2SIM_ACT_" + n.upper()] for n in ("elu", "selu", "relu", "lrelu", "tanh", "sigmoid", "identity")}
 
@@ -79,6 +80,11 @@ class PpoCfg(ctypes.Structure):
 class DistillCfg(ctypes.Structure):
     """go2sim_distill_cfg_t"""
     _fields_ = [(n, ctypes.c_double) for n in ("learning_rate", "max_grad_norm", "beta1", "beta2", "eps")] + [("loss_type", ctypes.c_int), ("sub_rows", ctypes.c_int)]
+
+
+class RndCfg(ctypes.Structure):
+    """go2sim_rnd_cfg_t"""
+    _fields_ = [(n, ctypes.c_double) for n in ("learning_rate", "beta1", "beta2", "eps")] + [("reward_normalization", ctypes.c_int)]
 
 
 class RDistillCfg(ctypes.Structure):

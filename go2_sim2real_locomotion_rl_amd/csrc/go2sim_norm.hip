@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/go2sim_norm.h"
+#include "go2sim_norm_dev.h"   // Mom, mom_merge, fold_chunks, norm_law: shared with go2sim_rnd.hip
 
 namespace {
 
@@ -18,7 +19,6 @@ namespace {
     if (e_ != hipSuccess) { fprintf(stderr, "go2sim_norm: %s failed: %s\n", #x, hipGetErrorString(e_)); return GO2SIM_E_HIP; } \
   } while (0)
 
-constexpr int CH = GO2SIM_NORM_ROW_CHUNK;   // rows of one k_norm_moments workgroup: the unit of the fixed fold order
 constexpr int MOM_WG = 1024;                // its lanes
 constexpr int APPLY_WG = 256, APPLY_ROWS = 32;
 enum { MODE_PLAIN = 0, MODE_CHUNKS = 1, MODE_RECORDS = 2 };
@@ -39,50 +39,6 @@ struct NormJob {
   const float* x;
   float* y;
 };
-
-struct Mom { double n, mean, M2; };
-
-// Chan et al.: the moments of the union from those of two sets
-__device__ __forceinline__ void mom_merge(Mom& a, double nb, double mb, double M2b) {
-  const double n = a.n + nb, delta = mb - a.mean;
-  a.mean = a.mean + delta * (nb / n);
-  a.M2 = a.M2 + M2b + delta * delta * (a.n * nb / n);
-  a.n = n;
-}
-
-__device__ __forceinline__ int chunk_rows(int i, int n_rows) { return min(CH, n_rows - i * CH); }
-
-// column c's moments over all chunks of the call, in chunk order: the batch mean as the weighted mean of the chunk means, then the chunks' centred squares
-// moved to it, M2 = sum_i (M2_i + n_i (mean_i - mean)^2) -- two passes over the chunk moments, one division per column, nothing of the size of mean^2
-__device__ __forceinline__ Mom fold_chunks(const double* __restrict__ part, int d, int c, int n_rows) {
-  const int nch = (n_rows + CH - 1) / CH;
-  if (nch == 1) return Mom{(double)n_rows, part[c], part[(size_t)d + c]};
-  // FB chunks' loads are issued together, the sums stay in chunk order: the 16 chunks of 4096 rows cost two round trips to memory, not sixteen
-  constexpr int FB = 8;
-  double s = 0.0;
-  for (int i0 = 0; i0 < nch; i0 += FB) {
-    double m[FB];
-#pragma unroll
-    for (int k = 0; k < FB; ++k) m[k] = i0 + k < nch ? part[(size_t)(2 * (i0 + k)) * d + c] : 0.0;
-#pragma unroll
-    for (int k = 0; k < FB; ++k)
-      if (i0 + k < nch) s += (double)chunk_rows(i0 + k, n_rows) * m[k];
-  }
-  const double mean = s / (double)n_rows;
-  double q = 0.0;
-  for (int i0 = 0; i0 < nch; i0 += FB) {
-    double m[FB], m2[FB];
-#pragma unroll
-    for (int k = 0; k < FB; ++k) {
-      m[k] = i0 + k < nch ? part[(size_t)(2 * (i0 + k)) * d + c] : 0.0;
-      m2[k] = i0 + k < nch ? part[(size_t)(2 * (i0 + k) + 1) * d + c] : 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < FB; ++k)
-      if (i0 + k < nch) { const double e = m[k] - mean; q += m2[k] + (double)chunk_rows(i0 + k, n_rows) * (e * e); }
-  }
-  return Mom{(double)n_rows, mean, q};
-}
 
 // column c's moments over the records (rec points at this normaliser's part of record 0), folded in record order; empty records are passed over
 __device__ __forceinline__ Mom fold_records(const double* __restrict__ rec, int n_rec, int rec_len, int d, int c) {
@@ -190,11 +146,8 @@ __global__ __launch_bounds__(APPLY_WG) void k_norm_apply(NormJob j0, NormJob j1,
     if (move) b = mode == MODE_CHUNKS ? fold_chunks(J.N.part, d, c, n_rows) : fold_records(rec, n_rec, rec_len, d, c);
     if (move && b.n > 0.0) {                                   // b.n is the same in every column
       const double m = (double)J.N.pmean[c], v = (double)J.N.pvar[c];
-      const double cnt1 = (double)cnt + b.n, rate = b.n / cnt1;
-      const double dm = b.mean - m;
-      const double m1 = m + rate * dm;
-      double v1 = v + rate * (b.M2 / b.n - v + dm * (b.mean - m1));
-      if (v1 < 0.0) v1 = 0.0;
+      double m1, v1;
+      norm_law(m, v, cnt, b, m1, v1);
       m32 = (float)m1;
       s32 = (float)sqrt(v1);
       if (blockIdx.x == 0 && rl == 0) {

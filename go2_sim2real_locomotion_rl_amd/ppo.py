@@ -25,6 +25,11 @@ the kernels read every mini-batch row a second time through them, no mirrored co
 A recurrent policy (policy.ActorCriticRecurrent, include/go2sim_rnn.h): ``act`` saves the memories' state at the rollout's first step, ``process_env_step``
 zeroes the state of the done envs, and ``update`` runs rsl_rl's recurrent mini-batches -- env blocks with all their steps, no permutation -- through the
 cell kernel forwards and backwards in time.  It needs ``num_envs`` divisible by ``num_mini_batches`` and refuses ``symmetry_cfg`` and a multi-rank group.
+
+Random network distillation (rsl_rl's ``rnd_cfg``; rnd.py, include/go2sim_rnd.h): ``PPO(..., rnd_cfg={"num_states": 49, "weight": 0.1 * env.dt, ...})`` builds a
+``RandomNetworkDistillation``; ``process_env_step(rewards, dones, infos, rnd_state)`` adds the curiosity bonus to the reward the storage takes (the env's tensor is
+not written) and keeps the state rows, and ``update`` trains the predictor on the policy's own mini-batch row lists and returns ``rnd_loss`` as a fourth value.
+One rank only.
 """
 import ctypes
 
@@ -33,6 +38,7 @@ import torch
 from .capi import C, Go2SimError, PpoBatch, PpoCfg, PpoMirror, PpoRnnState, _ptr, load_hip_lib
 from .distributed import allgather_records, broadcast_from_rank0, is_multi, shard_seed
 from .module_core import memory_keys, mlp_keys, unflatten_keys
+from .rnd import RandomNetworkDistillation, check_rnd_cfg
 from .rollout import RolloutStorage
 from .trainer import OptimizerState, TrainerHandle
 
@@ -184,13 +190,19 @@ class PPO(OptimizerState):
 
     def __init__(self, policy, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95, value_loss_coef=1.0, entropy_coef=0.0,
                  learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device=None, *, seed=1, group=None, symmetry_cfg=None,
-                 **kwargs):
+                 rnd_cfg=None, **kwargs):
         if schedule not in ("adaptive", "fixed"):
             raise Go2SimError(f"schedule must be 'adaptive' or 'fixed', got {schedule!r}")
         unknown = {k: v for k, v in kwargs.items() if k not in ("class_name", "normalize_advantage_per_mini_batch") and v is not None}
         if unknown or kwargs.get("normalize_advantage_per_mini_batch"):
-            raise Go2SimError(f"go2sim's PPO does not implement {sorted(unknown) or ['normalize_advantage_per_mini_batch']} (RND and symmetry are out of scope other than symmetry_cfg with mirror_tables)")
+            raise Go2SimError(f"go2sim's PPO does not implement {sorted(unknown) or ['normalize_advantage_per_mini_batch']} (beyond rnd_cfg and symmetry_cfg with mirror_tables, RND and symmetry are out of scope)")
         self.symmetry = self._check_symmetry_cfg(symmetry_cfg)
+        self.rnd_cfg = check_rnd_cfg(rnd_cfg)                                   # None for None / {}: everything as without it
+        if self.rnd_cfg is not None:
+            if group is not None and is_multi(group):
+                raise Go2SimError("rnd_cfg over a multi-rank group is not implemented (the sharded predictor update is a follow-up)")
+            if "num_states" not in self.rnd_cfg:
+                raise Go2SimError("rnd_cfg needs 'num_states', the width of the rnd_state rows (the runner fills it from obs_groups['rnd_state'])")
         self.recurrent = bool(getattr(policy, "is_recurrent", False))
         if self.recurrent and self.symmetry is not None:
             raise Go2SimError("symmetry_cfg with a recurrent policy is not implemented (rsl_rl refuses it too)")
@@ -211,6 +223,11 @@ class PPO(OptimizerState):
         self.storage = self._h = None
         self.last_stats = None
         self.symmetry_loss = None
+        self.rnd = None
+        if self.rnd_cfg is not None:
+            self.rnd = RandomNetworkDistillation(device=self.device, seed=seed, **self.rnd_cfg)
+            self.result_names = PPO.result_names + ("rnd_loss",)
+            self.rnd_loss = None
 
     @staticmethod
     def _check_symmetry_cfg(cfg):
@@ -228,7 +245,7 @@ class PPO(OptimizerState):
         return dict(tables=cfg["mirror_tables"], use_data_augmentation=bool(cfg.get("use_data_augmentation", False)),
                     use_mirror_loss=bool(cfg.get("use_mirror_loss", False)), mirror_loss_coeff=float(cfg.get("mirror_loss_coeff", 0.0)))
 
-    def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
+    def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, rnd_state_shape=None):
         T, B, dev = int(num_transitions_per_env), int(num_envs), self.device
         self.T, self.B, self.t = T, B, 0
         self.storage = RolloutStorage(T, B, dev)
@@ -251,6 +268,15 @@ class PPO(OptimizerState):
             self._h.set_mirror(**self.symmetry)
         self._batch = make_batch(obs=self.obs, critic_obs=self.critic_obs, actions=self.actions, target_values=self.storage.values, returns=self.storage.returns,
                                  advantages=self.storage.advantages, old_log_prob=self.old_log_prob, old_mu=self.old_mu, old_sigma=self.old_sigma)
+        if self.rnd is not None:
+            if rnd_state_shape is not None and list(rnd_state_shape) != [self.rnd.num_states]:
+                raise Go2SimError(f"rnd_state_shape {list(rnd_state_shape)} is not rnd_cfg's num_states [{self.rnd.num_states}]")
+            self.rnd_states = z(self.rnd.num_states)                      # the rows the predictor's update reads, as the step's networks saw them
+            self.rnd.attach(max(B, self._mbs))
+            if self.recurrent:                                            # the env blocks with all their steps, t-major: mini-batch m is entries [m mbs, (m + 1) mbs)
+                blk = B // self.num_mini_batches
+                rows = torch.arange(T, device=dev).view(1, T, 1) * B + torch.arange(B, device=dev).view(self.num_mini_batches, 1, blk)
+                self._rnd_idx = rows.reshape(-1).to(torch.int32).contiguous()
         if self.group is not None:
             # the ranks' mini-batch sizes, gathered once: a row weighs 1 / (their sum), so unequal shards are weighted by rows
             sizes = allgather_records(torch.tensor([float(self._mbs)], dtype=torch.float64, device=dev), self.group)
@@ -275,7 +301,12 @@ class PPO(OptimizerState):
         self.old_log_prob[t].copy_(self.policy.actions_log_prob); self.old_mu[t].copy_(self.policy.action_mean); self.old_sigma[t].copy_(self.policy.action_std)
         return actions
 
-    def process_env_step(self, rewards, dones, infos):
+    def process_env_step(self, rewards, dones, infos, rnd_state=None):
+        if self.rnd is not None:
+            if rnd_state is None:
+                raise Go2SimError("process_env_step: a PPO with rnd_cfg needs the rnd_state rows of this step")
+            self.intrinsic_rewards, rewards = self.rnd.get_intrinsic_reward(rnd_state, rewards)      # the env's reward tensor is not written
+            self.rnd_states[self.t].copy_(self.rnd.last_state)
         self.storage.add_transitions(self.t, rewards, dones, self.policy.values, infos.get("time_outs") if infos else None, gamma=self.gamma)
         self.t += 1
         if self.recurrent:
@@ -293,16 +324,23 @@ class PPO(OptimizerState):
             self._h.update(self._batch, self.policy.std, perm, self.T * self.B, self.num_learning_epochs, self.num_mini_batches)
         else:
             self._update_sharded(perm)
-        if self.symmetry is not None:                                      # rides along in the one read
-            s = torch.cat([self._h.stats(), self._h.symmetry_loss()]).cpu()
+        extra = []
+        if self.rnd is not None:                                           # the predictor's loop on the same row lists, after the policy's
+            idx, n_rnd = (self._rnd_idx, self.T * self.B) if self.recurrent else (perm, n)
+            extra.append(self.rnd.update(self.rnd_states, idx, n_rnd, self.num_learning_epochs, self.num_mini_batches)[:1])
+        if self.symmetry is not None:
+            extra.append(self._h.symmetry_loss())
+        s = (torch.cat([self._h.stats(), *extra]) if extra else self._h.stats()).cpu()      # the update's only host synchronisation; the extras ride along
+        if self.symmetry is not None:
             self.symmetry_loss = float(s[-1])
-            s = s[:-1]
-        else:
-            s = self._h.stats().cpu()                                      # the update's only host synchronisation
+        if self.rnd is not None:
+            self.rnd_loss = float(s[C["GO2SIM_PPO_N_STATS"]])
+        s = s[:C["GO2SIM_PPO_N_STATS"]]
         self.last_stats = s
         self.learning_rate = float(s[C["GO2SIM_PPO_ST_LR"]])
         self.t = 0
-        return float(s[C["GO2SIM_PPO_ST_VALUE_LOSS"]]), float(s[C["GO2SIM_PPO_ST_SURROGATE"]]), float(s[C["GO2SIM_PPO_ST_ENTROPY"]])
+        out = float(s[C["GO2SIM_PPO_ST_VALUE_LOSS"]]), float(s[C["GO2SIM_PPO_ST_SURROGATE"]]), float(s[C["GO2SIM_PPO_ST_ENTROPY"]])
+        return out + (self.rnd_loss,) if self.rnd is not None else out
 
     def _update_sharded(self, perm):
         """go2sim_ppo_update's loop on the host with the collective in it: per mini-batch this shard's record, one all-gather, the ordered reduction, Adam."""

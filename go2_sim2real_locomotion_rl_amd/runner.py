@@ -25,6 +25,11 @@ privileged rows -- a teacher.  ``algorithm.class_name == "Distillation"`` with `
 (distillation.py; the second puts an LSTM memory in front of the student and needs ``rnn_hidden_dim``) distils such a teacher into a student: ``load(teacher_checkpoint)`` fills the teacher, ``learn()`` collects with the student and regresses it onto the teacher's actions,
 the log carries ``behavior_loss``.  A teacher checkpoint's ``obs_norm_state_dict`` becomes a frozen teacher normaliser that is always applied (it is part of
 the teacher's function) and is saved as ``privileged_obs_norm_state_dict`` (DESIGN.md "Distillation").
+
+``train_cfg["algorithm"]["rnd_cfg"]`` (rsl_rl's random network distillation; rnd.py, DESIGN.md "RND") adds a curiosity bonus to the reward: the role ``rnd_state`` of
+``obs_groups`` (default ``"policy"``) names the rows the two networks embed and sizes them (``num_states``), ``weight`` is multiplied by ``env.dt`` on a copy of
+the cfg, the log gains ``rnd_loss``, ``mean_intrinsic_reward``, ``mean_extrinsic_reward`` and ``rnd_weight``, and a checkpoint ``rnd_state_dict`` /
+``rnd_optimizer_state_dict``.  One rank only.
 """
 import os
 
@@ -75,6 +80,7 @@ class OnPolicyRunner:
         self._last_means = (0.0, 0.0)
         self._cur_rew, self._cur_len = torch.zeros(env.num_envs, device=self.device), torch.zeros(env.num_envs, device=self.device)
         self.obs_normalizer = self.critic_obs_normalizer = self.privileged_obs_normalizer = None
+        self.rnd = None
         if self.distill:
             if self.group is not None:
                 raise Go2SimError("Distillation over a multi-rank group is not implemented (the sharded distillation update is a follow-up)")
@@ -91,14 +97,25 @@ class OnPolicyRunner:
         pol_class = ActorCriticRecurrent if pol_class == "ActorCriticRecurrent" else ActorCritic
         # the noise stream is the rank's own; the initial weights drawn from the same seed are replaced by rank 0's at the end of init_storage
         self.policy = pol_class(obs.shape[1], critic_obs.shape[1], env.num_actions, device=self.device, seed=shard_seed(seed, self.rank), **pol_cfg)
+        if alg_cfg.get("rnd_cfg"):
+            if self.group is not None:
+                raise Go2SimError("rnd_cfg over a multi-rank group is not implemented (the sharded predictor update is a follow-up)")
+            # on a copy: the width of the rows the role reads, and the weight per env step scaled by the step's length as rsl_rl's runner does
+            rnd_cfg = dict(alg_cfg["rnd_cfg"], num_states=int(self._rnd_rows(*env.get_observations()).shape[1]))
+            rnd_cfg["weight"] = float(rnd_cfg.get("weight", 0.0)) * float(env.dt)
+            alg_cfg["rnd_cfg"] = rnd_cfg
         self.alg = PPO(self.policy, device=self.device, seed=seed, group=self.group, **alg_cfg)
         self.alg.init_storage(env.num_envs, self.num_steps_per_env, [obs.shape[1]], [critic_obs.shape[1]], [env.num_actions])
+        self.rnd = self.alg.rnd
+        if self.rnd is not None:                                              # running episodes' two reward parts, counted as _count_episodes counts the sum
+            self._cur_int, self._cur_ext = torch.zeros(env.num_envs, device=self.device), torch.zeros(env.num_envs, device=self.device)
+            self._last_rnd_means = (0.0, 0.0)
         if self.empirical_normalization:
             # both exist even when the env gives no critic observations (the second then stays unused: the critic reads the normalised actor rows)
             self.obs_normalizer = EmpiricalNormalization([obs.shape[1]], until=1.0e8, device=self.device)
             self.critic_obs_normalizer = EmpiricalNormalization([critic_obs.shape[1]], until=1.0e8, device=self.device)
 
-    ROLES, GROUPS = ("policy", "critic", "teacher"), ("policy", "critic")
+    ROLES, GROUPS = ("policy", "critic", "teacher", "rnd_state"), ("policy", "critic")
 
     @classmethod
     def _check_obs_groups(cls, cfg):
@@ -125,6 +142,14 @@ class OnPolicyRunner:
         g = self.obs_groups
         critic = group(g["critic"]) if "critic" in g else observations.get("critic")
         return group(g.get("policy", "policy")), critic, group(g.get("teacher", "policy"))
+
+    def _rnd_rows(self, obs, extras):
+        """the env's raw rows of the role rnd_state (default: the policy group); `extras` is what the env returned next to obs"""
+        if self.obs_groups.get("rnd_state", "policy") == "policy":
+            return obs
+        if "critic" not in extras["observations"]:
+            raise Go2SimError("obs_groups names the group 'critic', but the env gives no critic observations")
+        return extras["observations"]["critic"]
 
     def _normalize(self, obs, critic, update):
         """Both observation sets through one norm_step call (`critic` is None when the env has no critic observations: the critic then reads the normalised
@@ -156,17 +181,27 @@ class OnPolicyRunner:
         start = self.current_learning_iteration
         for it in range(start, start + num_learning_iterations):
             acc = torch.zeros(3, device=dev, dtype=torch.float64)            # finished episodes: count, sum of rewards, sum of lengths
+            acc_rnd = torch.zeros(2, device=dev, dtype=torch.float64) if self.rnd is not None else None      # their intrinsic and extrinsic reward sums
             for _ in range(self.num_steps_per_env):
                 actions = alg.act(*rows)
                 obs, rewards, dones, infos = env.step(actions)
                 rows = self._rows(obs, infos["observations"], update=True)
-                alg.process_env_step(rewards, dones, infos)
+                if self.rnd is not None:
+                    alg.process_env_step(rewards, dones, infos, self._rnd_rows(obs, infos))
+                    self._count_rnd(acc_rnd, alg.intrinsic_rewards, rewards, dones)
+                else:
+                    alg.process_env_step(rewards, dones, infos)
                 self._count_episodes(acc, rewards, dones)
             if not self.distill and getattr(env, "_shared_globals", False):
                 env.sync_globals(self.group)                                   # one curriculum and one set of global DR draws for all shards
             alg.compute_returns(rows[1])                                       # nothing for distillation: the targets are the stored teacher actions
             results = alg.update()
-            n, rs, ls = (acc if self.distill else sum_in_rank_order(acc, self.group)).tolist()      # every rank logs the global means; distillation is one rank
+            if self.rnd is not None:                                           # one rank: the two extra sums ride in the same read
+                n, rs, ls, ri, re = torch.cat([acc, acc_rnd]).tolist()
+                if n > 0:
+                    self._last_rnd_means = (ri / n, re / n)
+            else:
+                n, rs, ls = (acc if self.distill else sum_in_rank_order(acc, self.group)).tolist()      # every rank logs the global means; distillation is one rank
             if n > 0:
                 self._last_means = (rs / n, ls / n)
             self.current_learning_iteration = it + 1
@@ -174,6 +209,8 @@ class OnPolicyRunner:
                         **dict(zip(alg.result_names, results if isinstance(results, tuple) else (results,))), "learning_rate": alg.learning_rate})
             if alg.symmetry is not None:
                 log[-1]["symmetry_loss"] = alg.symmetry_loss
+            if self.rnd is not None:
+                log[-1].update(mean_intrinsic_reward=self._last_rnd_means[0], mean_extrinsic_reward=self._last_rnd_means[1], rnd_weight=self.rnd.weight)
             if self.log_dir is not None and self.save_interval > 0 and (it + 1) % self.save_interval == 0:
                 self.save(os.path.join(self.log_dir, f"model_{it + 1}.pt"))
         if self.log_dir is not None:
@@ -188,6 +225,14 @@ class OnPolicyRunner:
         acc += torch.stack([d.sum(), (d * cur_rew).sum(), (d * cur_len).sum()])
         keep = (dones == 0).to(cur_rew.dtype)
         cur_rew *= keep; cur_len *= keep
+
+    def _count_rnd(self, acc_rnd, intrinsic, rewards, dones):
+        """acc_rnd += (intrinsic, extrinsic) reward sums of the episodes that ended in this step, with _count_episodes's accounting"""
+        self._cur_int += intrinsic; self._cur_ext += rewards
+        d = (dones > 0).to(torch.float64)
+        acc_rnd += torch.stack([(d * self._cur_int).sum(), (d * self._cur_ext).sum()])
+        keep = (dones == 0).to(self._cur_int.dtype)
+        self._cur_int *= keep; self._cur_ext *= keep
 
     # ---- distillation ----------------------------------------------------------------------------------------
     def _distill_rows(self, obs, observations, update):
@@ -228,11 +273,18 @@ class OnPolicyRunner:
         if not self.empirical_normalization and has_norm:
             raise Go2SimError(f"{path}: the checkpoint carries {has_norm} (its policy was trained on normalised observations), but empirical_normalization "
                               "is off in this runner's train_cfg")
+        has_rnd = [k for k in ("rnd_state_dict", "rnd_optimizer_state_dict") if ckpt.get(k) is not None]
+        if self.rnd is not None and len(has_rnd) != 2:
+            raise Go2SimError(f"{path}: rnd_cfg is set, but the checkpoint has no rnd_state_dict / rnd_optimizer_state_dict")
+        if self.rnd is None and has_rnd:
+            raise Go2SimError(f"{path}: the checkpoint carries {has_rnd} (it was trained with random network distillation), but this runner's train_cfg has no rnd_cfg")
         self.policy.load_state_dict(ckpt["model_state_dict"])
         self.alg.broadcast_parameters()                                        # every rank read the file; rank 0's parameters are the ones in force
         if self.empirical_normalization:                                      # every rank read the same file: nothing to broadcast
             self.obs_normalizer.load_state_dict(ckpt["obs_norm_state_dict"])
             self.critic_obs_normalizer.load_state_dict(ckpt["critic_obs_norm_state_dict"])
+        if self.rnd is not None:
+            self.rnd.load_state_dict(ckpt["rnd_state_dict"])
         return True
 
     def save(self, path, infos=None):
@@ -245,7 +297,8 @@ class OnPolicyRunner:
         opt["policy_noise_step"] = int(self.policy.noise_step)
         norm_state = lambda normalizer: None if normalizer is None else normalizer.state_dict()
         save_checkpoint(path, self.policy.state_dict(), opt, self.current_learning_iteration, infos, obs_norm_state_dict=norm_state(self.obs_normalizer),
-                        critic_obs_norm_state_dict=norm_state(self.critic_obs_normalizer), privileged_obs_norm_state_dict=norm_state(self.privileged_obs_normalizer))
+                        critic_obs_norm_state_dict=norm_state(self.critic_obs_normalizer), privileged_obs_norm_state_dict=norm_state(self.privileged_obs_normalizer),
+                        rnd_state_dict=norm_state(self.rnd), rnd_optimizer_state_dict=None if self.rnd is None else self.rnd.optimizer_state_dict())
 
     def load(self, path, load_optimizer=True):
         """A checkpoint of this runner's own kind resumes the run: model, normalisers, optimizer, the policy's noise step, iteration.  A distillation runner
@@ -256,6 +309,8 @@ class OnPolicyRunner:
             if load_optimizer and "exp_avg" in opt:
                 self.alg.load_optimizer_state_dict(opt)
                 self.policy.noise_step = int(opt.get("policy_noise_step", self.policy.noise_step))
+                if self.rnd is not None:
+                    self.rnd.load_optimizer_state_dict(ckpt["rnd_optimizer_state_dict"])
             self.current_learning_iteration = int(ckpt.get("iter", 0) or 0)
         return ckpt.get("infos")
 

@@ -9,6 +9,7 @@
     python tools/train.py --task stairs_lidar --envs 4096 --iterations 1000 --actor-obs critic --log-dir logs/teacher   # a teacher: the actor reads the privileged rows
     python tools/train.py --task stairs_lidar --envs 4096 --iterations 500 --distill logs/teacher/model_1000.pt --teacher-obs critic   # distil it into a student
     python tools/train.py --task stairs_lidar --distill logs/teacher/model_1000.pt --teacher-obs critic --student-recurrent --rnn-hidden 256   # ... a student with an LSTM memory
+    python tools/train.py --task jump --envs 4096 --iterations 1000 --rnd-weight 1.0 --rnd-reward-normalization       # a curiosity bonus (random network distillation; one GPU)
     torchrun --nproc-per-node 8 tools/train.py --task walk --envs 4096 --iterations 1000 --log-dir logs/go2-walk
 
 --envs is the env count PER RANK.  Under torchrun every rank builds its shard of the envs (``Go2Env(..., shared_globals=True)``: one curriculum, one
@@ -75,6 +76,14 @@ def main():
     ap.add_argument("--activation", default=None, metavar="NAME",
                     help="train_cfg['policy']['activation']: elu, selu, relu, lrelu, tanh, sigmoid or identity (default: the config's own, 'elu'); "
                          "with --distill the student's and the teacher's")
+    ap.add_argument("--rnd-weight", type=float, default=None, metavar="W",
+                    help="random network distillation (rsl_rl's rnd_cfg): weight of the curiosity bonus per second (the runner multiplies it by env.dt); one rank")
+    ap.add_argument("--rnd-outputs", type=int, default=1, help="num_outputs of --rnd-weight: the embedding width")
+    ap.add_argument("--rnd-hidden", type=int, nargs="+", default=[-1], help="predictor_hidden_dims and target_hidden_dims of --rnd-weight (-1: the state width)")
+    ap.add_argument("--rnd-state-normalization", action="store_true", help="normalise the rnd_state rows with running statistics")
+    ap.add_argument("--rnd-reward-normalization", action="store_true", help="divide the bonus by the running std of its discounted sum")
+    ap.add_argument("--rnd-schedule", default=None, metavar="linear:a:b:v", help="weight_schedule of --rnd-weight: linear:initial_step:final_step:final_value or step:final_step:final_value")
+    ap.add_argument("--rnd-obs", choices=("policy", "critic"), default="policy", help="the env observation group the two RND networks embed (obs_groups['rnd_state'])")
     ap.add_argument("--resume", default=None, help="checkpoint to load on every rank before training")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -116,6 +125,20 @@ def main():
             cfg["empirical_normalization"] = True
         if args.actor_obs != "policy":
             cfg["obs_groups"] = {"policy": args.actor_obs}
+        if args.rnd_weight is not None:
+            if world > 1 or args.distill:
+                raise SystemExit("--rnd-weight runs on one rank and belongs to PPO, not to --distill")
+            rnd_cfg = {"weight": args.rnd_weight, "num_outputs": args.rnd_outputs, "predictor_hidden_dims": list(args.rnd_hidden), "target_hidden_dims": list(args.rnd_hidden),
+                       "state_normalization": args.rnd_state_normalization, "reward_normalization": args.rnd_reward_normalization}
+            if args.rnd_schedule:
+                mode, *vals = args.rnd_schedule.split(":")
+                names = {"linear": ("initial_step", "final_step", "final_value"), "step": ("final_step", "final_value")}.get(mode)
+                if names is None or len(vals) != len(names):
+                    raise SystemExit("--rnd-schedule is linear:initial_step:final_step:final_value or step:final_step:final_value")
+                rnd_cfg["weight_schedule"] = {"mode": mode, **{n: (float(v) if n == "final_value" else int(v)) for n, v in zip(names, vals)}}
+            cfg["algorithm"] = dict(cfg["algorithm"], rnd_cfg=rnd_cfg)
+            if args.rnd_obs != "policy":
+                cfg["obs_groups"] = dict(cfg.get("obs_groups") or {}, rnd_state=args.rnd_obs)
         if (args.student_recurrent or args.teacher_recurrent) and not (args.distill and args.student_recurrent):
             raise SystemExit("--student-recurrent belongs to --distill, --teacher-recurrent to --student-recurrent")
         if args.distill:
