@@ -67,6 +67,7 @@ DISTILL_HEADER, DECLARED_DISTILL_FUNCS = _product_header("distill")            #
 RDISTILL_HEADER, DECLARED_RDISTILL_FUNCS = _product_header("rdistill")         # distillation with a recurrent student
 ACT_HEADER, DECLARED_ACT_FUNCS = _product_header("activation")                 # the hidden-layer activation of an MLP
 RND_HEADER, DECLARED_RND_FUNCS = _product_header("rnd")                        # random network distillation: the intrinsic reward and the predictor's update
+TILES_HEADER, DECLARED_TILES_FUNCS = _product_header("tiles")                  # the rough-terrain walk env: float heightfield, ground query
 # train_cfg["policy"]["activation"] as rsl_rl's resolve_nn_activation spells it -> GO2SIM_ACT_*
 ACTIVATIONS = {n: C["GO2SIM_ACT_" + n.upper()] for n in ("elu", "selu", "relu", "lrelu", "tanh", "sigmoid", "identity")}
 
@@ -275,6 +276,25 @@ class Go2Sim(Handle):
         self._terrain_keepalive = (hf, org)
         self._call("set_terrain", _ptr(hf), ctypes.c_int(hf.shape[0]), ctypes.c_int(hf.shape[1]), ctypes.c_float(horizontal_scale),
                    ctypes.c_float(vertical_scale), _ptr(org), _ptr(stream))
+
+    def _tiles_call(self, name, *args):
+        """An entry of include/go2sim_tiles.h: the product library alone has it."""
+        if not self.L.is_device or not hasattr(self.L.lib, name):
+            raise Go2SimError(f"{name} is an entry of the HIP product library (include/go2sim_tiles.h); {self.L.path} does not have it")
+        self.L.check(getattr(self.L.lib, name)(self.h, *args), name)
+
+    def set_terrain_f32(self, hf_metres, horizontal_scale, origin, stream=None):
+        """go2sim_set_terrain_f32: heights as float32 metres [rows][cols]"""
+        hf = np.ascontiguousarray(hf_metres, dtype=np.float32)
+        org = np.ascontiguousarray(origin, dtype=np.float32)
+        assert hf.ndim == 2 and org.size == 3
+        self._terrain_keepalive = (hf, org)
+        self._tiles_call("go2sim_set_terrain_f32", _ptr(hf), ctypes.c_int(hf.shape[0]), ctypes.c_int(hf.shape[1]), ctypes.c_float(horizontal_scale),
+                         _ptr(org), _ptr(stream))
+
+    def tiles_query(self, xy, out, n=None, stream=None):
+        """go2sim_tiles_query: xy float32 [n][2] -> out float32 [n], device memory"""
+        self._tiles_call("go2sim_tiles_query", _ptr(xy), ctypes.c_int(len(xy) if n is None else n), _ptr(out), _ptr(stream))
 
     def set_dof_gains(self, dof, kp, kv, flo, fhi):
         self._call("set_dof_gains", ctypes.c_int(dof), ctypes.c_float(kp), ctypes.c_float(kv), ctypes.c_float(flo), ctypes.c_float(fhi))

@@ -11,6 +11,7 @@ import numpy as np
 
 from .capi import C, Go2SimError
 from .model_blob import load_model_json
+from .terrain_tiles import is_tile_terrain_cfg, tile_layout
 
 REWARD_IDS = {
     "tracking_lin_vel": "GO2SIM_R_TRACKING_LIN_VEL", "tracking_ang_vel": "GO2SIM_R_TRACKING_ANG_VEL",
@@ -265,7 +266,14 @@ def flatten_walk_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg, *, mod
     if dr_sched is not None:
         f[F("DR_PHASE1_LEVEL")], f[F("DR_TERRAIN_GATE")] = dr_sched.get("phase1_level", 0.15), dr_sched.get("terrain_gate", 0.50)
     tcfg = env_cfg.get("terrain", None)
-    if tcfg is not None and tcfg.get("enabled", False):
+    if is_tile_terrain_cfg(tcfg):
+        # ---- rough-terrain env (go2_env_Omni_kplearn_varied_terrain.py + terrain_manager.py; include/go2sim_tiles.h): the stair extras stay off ----
+        L = tile_layout(tcfg)
+        i[I("TILE_MODE")], i[I("TILE_N_ROWS")], i[I("TILE_N_COLS")] = 1, L["n_rows"], L["n_cols"]
+        f[F("TILE_SIZE_X")], f[F("TILE_SIZE_Y")] = L["subterrain_size"]
+        f[F("TILE_JITTER_X")], f[F("TILE_JITTER_Y")] = L["jitter"]
+        f[F("TILE_MAX_WANDER")], f[F("TILE_SPAWN_OFFSET")] = L["max_wander"], L["spawn_height_offset"]
+    elif tcfg is not None and tcfg.get("enabled", False):
         import torch
 
         _, info = build_stair_terrain(tcfg)
@@ -609,4 +617,53 @@ def get_stair_info_cfgs(pls_enable=True, stair_info=None):
     env_cfg["stair_info"] = copy.deepcopy(stair_info) if stair_info is not None else get_stair_info_cfg()
     env_cfg["terrain"] = get_stair_info_terrain_cfg()
     _, obs_cfg["num_obs"], obs_cfg["num_privileged_obs"] = stair_info_widths(env_cfg)
+    return env_cfg, obs_cfg, reward_cfg, command_cfg
+
+
+# ---------------------------------------------------------------------------------------------
+# rough-terrain fine-tuning env: examples/locomotion/go2_train_Omni_kplearn_varied_terrain.py + terrain_manager.py (include/go2sim_tiles.h)
+# ---------------------------------------------------------------------------------------------
+ROUGH_HEIGHTMAP = {"size_x": 15.0, "size_y": 15.0, "h_scale": 0.05, "min_h": -0.08, "max_h": 0.08, "smoothing": 3}   # the script's HEIGHTMAP_* constants
+
+
+def rough_heightmap(seed=0):
+    """`make_terrain_cfg_heightmap` of the train script: float32 metres [300][300], the left half (columns below 150) flat, the right half
+    uniform bumps in [-0.08, 0.08] smoothed with a 3 x 3 box filter.  The script draws from numpy's global generator; here the draw comes from
+    ``RandomState(seed)``, which gives the values the script gives after ``np.random.seed(seed)``."""
+    from scipy.ndimage import uniform_filter
+
+    H = ROUGH_HEIGHTMAP
+    res_x, res_y = int(H["size_x"] / H["h_scale"]), int(H["size_y"] / H["h_scale"])
+    hf = np.zeros((res_y, res_x), dtype=np.float32)
+    half_x = res_x // 2
+    bumpy = np.random.RandomState(seed).uniform(H["min_h"], H["max_h"], (res_y, res_x - half_x)).astype(np.float32)
+    if H["smoothing"] > 1:
+        bumpy = uniform_filter(bumpy, size=H["smoothing"]).astype(np.float32)
+    hf[:, half_x:] = bumpy
+    return hf
+
+
+def get_rough_terrain_cfg(mode="heightmap", seed=0):
+    """`make_terrain_cfg_heightmap` / `make_terrain_cfg_grid` of the train script (:131-198)."""
+    if mode == "heightmap":
+        return {"enabled": True, "height_field": rough_heightmap(seed), "horizontal_scale": ROUGH_HEIGHTMAP["h_scale"], "vertical_scale": 1.0,
+                "spawn_height_offset": 0.05, "boundary_margin": 1.0}
+    if mode == "grid":
+        return {"enabled": True, "subterrain_types": [["flat_terrain", "random_uniform_terrain"], ["random_uniform_terrain", "flat_terrain"]],
+                "subterrain_size": (8.0, 8.0), "horizontal_scale": 0.25, "vertical_scale": 0.005, "randomize": True, "spawn_height_offset": 0.05,
+                "boundary_margin": 1.0, "subterrain_parameters": {"random_uniform_terrain": {"min_height": -0.08, "max_height": 0.08}}}
+    raise ValueError(f"terrain mode {mode!r}: 'heightmap' or 'grid'")
+
+
+def get_rough_cfgs(mode="heightmap", seed=0):
+    """go2_train_Omni_kplearn_varied_terrain.py:201-488 (values transcribed): the 16-action walk configuration with the script's five changes -- spawn
+    height range [0.43, 0.48] and base_init_pos z 0.45 for the bumps, curriculum level_init 0.20, feet_air_time 0.3, foot_clearance -0.3 -- and its
+    terrain block.  `mode` is the script's TERRAIN_MODE ("heightmap", its default, or "grid"); `seed` makes the heightmap's bumps (rough_heightmap)."""
+    env_cfg, obs_cfg, reward_cfg, command_cfg = get_walk_cfgs(pls_enable=True)
+    env_cfg["init_pos_z_range"] = [0.43, 0.48]
+    env_cfg["base_init_pos"] = [0.0, 0.0, 0.45]
+    env_cfg["curriculum"]["level_init"] = 0.20
+    env_cfg["terrain"] = get_rough_terrain_cfg(mode, seed)
+    reward_cfg["reward_scales"]["feet_air_time"] = 0.3
+    reward_cfg["reward_scales"]["foot_clearance"] = -0.3
     return env_cfg, obs_cfg, reward_cfg, command_cfg

@@ -32,6 +32,8 @@
 #include "../../include/go2sim_detmath.h"
 #include "../../include/go2sim_lidar.h"
 #include "../../include/go2sim_stairinfo.h"
+#include "../../include/go2sim_tiles.h"
+#include "go2sim_tiles_dev.h"
 
 #define DEV __device__ __forceinline__
 #define DEVN __device__ __noinline__
@@ -568,12 +570,12 @@ constexpr int GEOMK_BYTES = NG * (int)sizeof(GeomK), GEOMK_LDS_BYTES = lds_dma_b
   X(base_ang_vel, 3) X(projected_gravity, 3) X(base_euler, 3) X(commands, 3) X(time_out, 1) X(kp_factors, NM)          \
   X(kd_factors, NM) X(motor_strength, NM) X(gravity_offset, 3) X(current_push_force, 3) X(push_stored_force, 3)       \
   X(feet_air_time, 4) X(base_vel_world, 3) X(last_base_pos_x, 1) X(episode_sums, NREW) X(rew_terms, NREW) X(rew, 1) X(obs, NOBS_MAX) X(priv, NPRIV_MAX) \
-  X(base_kp, 1) X(base_kd, 1)
+  X(base_kp, 1) X(base_kd, 1) X(ground_height, 1) X(spawn_pos, 3)
 
 #define GO2SIM_INT_FIELDS(X)                                                                                         \
   X(n_contacts, 1) X(n_con, 1) X(err, 1) X(is_warmstart, 1) X(first_time, 1) X(n_broad, 1) X(solver_iters, 1) X(ctrl_mode, ND) \
   X(gjk_fallback, 1) X(delay_steps, 1) X(episode_length, 1) X(reset_buf, 1) X(push_remaining, 1) X(foot_contact, 4)    \
-  X(last_foot_contact, 4) X(terrain_row, 1) X(terrain_key, 1)
+  X(last_foot_contact, 4) X(terrain_row, 1) X(terrain_key, 1) X(tile_row, 1) X(tile_col, 1)
 
 #define GO2SIM_AOS_FLOAT_FIELDS(X)                                                                                   \
   X(acc, ND) X(qacc_ws, ND) X(force, ND) X(qf_smooth, ND) X(acc_smooth, ND) X(qfrc_constraint, ND) X(mass_mat, NTRI)  \
@@ -679,9 +681,9 @@ struct E {
   FA(actions) FA(last_actions) FA(applied_actions) FA2(action_history, NA) FA(target_dof_pos) FA(e_dof_pos) FA(e_dof_vel) FA(last_dof_vel)
   FA(torque) FA(base_pos) FA(base_quat) FA(base_lin_vel) FA(base_ang_vel) FA(projected_gravity) FA(base_euler) FA(commands) FA(time_out)
   FA(kp_factors) FA(kd_factors) FA(motor_strength) FA(gravity_offset) FA(current_push_force) FA(push_stored_force) FA(feet_air_time) FA(base_vel_world) FA(last_base_pos_x)
-  FA(episode_sums) FA(rew_terms) FA(rew) FA(obs) FA(priv) FA(base_kp) FA(base_kd)
+  FA(episode_sums) FA(rew_terms) FA(rew) FA(obs) FA(priv) FA(base_kp) FA(base_kd) FA(ground_height) FA(spawn_pos)
   IA(n_contacts) IA(n_con) IA(err) IA(is_warmstart) IA(first_time) IA(n_broad) IA(solver_iters) IA(ctrl_mode)
-  IA(gjk_fallback) IA(delay_steps) IA(episode_length) IA(reset_buf) IA(push_remaining) IA(foot_contact) IA(last_foot_contact) IA(terrain_row) IA(terrain_key)
+  IA(gjk_fallback) IA(delay_steps) IA(episode_length) IA(reset_buf) IA(push_remaining) IA(foot_contact) IA(last_foot_contact) IA(terrain_row) IA(terrain_key) IA(tile_row) IA(tile_col)
   AA(acc) AA(qacc_ws) AA(force) AA(qf_smooth) AA(acc_smooth) AA(qfrc_constraint) AA3(cdof_ang) AA3(cdof_vel) AA3(cdofd_ang)
   AA3(cdofd_vel) AA9(cinr_inertial) AA3(cinr_pos) AA(cinr_mass) AA3(i_pos) AA4(i_quat) AA3(g_pos) AA4(g_quat) AA(sort_value) AA3(c_pos) AA3(c_normal)
   AA(c_pen) AA(c_friction) AA2(c_sol, 7) AA3(c_force) AA(efc_force) AA3(normal_cache)
@@ -4847,6 +4849,10 @@ DEV float terrain_height(const Model& m, const DCfg& c, float x, float y) {
   row = row < 0 ? 0 : (row > m.terrain_cols - 1 ? m.terrain_cols - 1 : row);
   return m.terrain_hf[(size_t)col * m.terrain_cols + row];
 }
+// the heightfield as the tile mode's device functions read it (csrc/go2sim_tiles_dev.h): link 0 carries the origin go2sim_set_terrain[_f32] was handed
+__host__ __device__ inline TileField tile_field(const Model& m) {
+  return TileField{m.terrain_hf, m.terrain_rows, m.terrain_cols, m.links[0].pos.x, m.links[0].pos.y, m.terrain_hs};
+}
 __host__ __device__ inline void apply_curriculum_level(const DCfg& c, Glob& g) {
   double lvl_terrain = c.i[GO2SIM_IC_CURR_ENABLED] ? g.level : 1.0;
   double lvl = dr_level(c, lvl_terrain);   // noise / pushes / delay follow the DR level; the command ranges follow the curriculum level
@@ -5188,6 +5194,7 @@ struct RewState {
   float actions[NA], last_actions[NA];
   float fat[4]; int fc[4];
   float last_x;
+  float ground = 0.0f;                                               // tile mode: bilinear ground height under the base (include/go2sim_tiles.h)
   float ctrl_pos[NM], ctrl_vel[NM], s_vel[NM], s_dof_pos[NM]; int ctrl_mode[NM];   // base env only (engine PD, accessor.py:848-875)
 };
 // the part of RewState that is plain env-buffer content (the caller fills blv, bav, pg, base_pos, dof_pos, dof_vel, fc)
@@ -5225,14 +5232,14 @@ DEV RewGates reward_gates(const RewState& rs) {
 }
 // The configuration words the walk / stairs terms read, fetched in one batch ahead of the term loop (load_rew_k): inside the loop every one of them
 // was a scalar round trip of its own -- the twelve force ranges two dependent ones (motor dof index, then the model's dof record).
-struct RewK { float dt, sigma, lin_vel_z_deadzone, base_height_target, feet_air_time_target, feet_height_target; float def[NM], force_lo[NM], force_hi[NM]; int na, use_terrain; };
+struct RewK { float dt, sigma, lin_vel_z_deadzone, base_height_target, feet_air_time_target, feet_height_target; float def[NM], force_lo[NM], force_hi[NM]; int na, use_terrain, tile; };
 // motor_dof: the dof of motor i.  k_env_post_a gets the twelve from the host with its launch arguments (TermDeal), so the force ranges -- read from the
 // Model on the device every step: go2sim_set_dof_gains may change them -- are requested with the kernel's first loads.
 DEV RewK load_rew_k(const Model& m, const DCfg& c, const int* motor_dof) {
   RewK K;
   K.dt = c.f[GO2SIM_FC_DT]; K.sigma = c.f[GO2SIM_FC_TRACKING_SIGMA]; K.lin_vel_z_deadzone = c.f[GO2SIM_FC_LIN_VEL_Z_DEADZONE];
   K.base_height_target = c.f[GO2SIM_FC_BASE_HEIGHT_TARGET]; K.feet_air_time_target = c.f[GO2SIM_FC_FEET_AIR_TIME_TARGET]; K.feet_height_target = c.f[GO2SIM_FC_FEET_HEIGHT_TARGET];
-  K.na = c.i[GO2SIM_IC_NUM_ACTIONS]; K.use_terrain = c.i[GO2SIM_IC_USE_TERRAIN];
+  K.na = c.i[GO2SIM_IC_NUM_ACTIONS]; K.use_terrain = c.i[GO2SIM_IC_USE_TERRAIN]; K.tile = c.i[GO2SIM_IC_TILE_MODE];
 #pragma unroll
   for (int i = 0; i < NM; ++i) {
     const int d = motor_dof[i];
@@ -5268,6 +5275,8 @@ DEV float reward_term(const Model& m, const DCfg& c, const RewK& K, RewState& rs
     }
     case GO2SIM_R_BASE_HEIGHT: {                                     // go2_env_stair.py:1634-1648: height above the local terrain
       float hgt = rs.base_pos[2];
+      if (K.tile) hgt = rs.base_pos[2] - rs.ground;                  // tile mode (include/go2sim_tiles.h): above the bilinear ground height
+      else
       if (K.use_terrain) hgt = rs.base_pos[2] - terrain_height(m, c, rs.base_pos[0], rs.base_pos[1]);
       float d = hgt - K.base_height_target; return d * d;
     }
@@ -5494,7 +5503,7 @@ __global__ __launch_bounds__(WG * POST_A_NWAVES) void k_env_post_a(Pool P, const
   if (!base_env) {
     K = load_rew_k(m, c, deal.motor_dof);
     POST_A_HOLD(K.dt); POST_A_HOLD(K.sigma); POST_A_HOLD(K.lin_vel_z_deadzone); POST_A_HOLD(K.base_height_target); POST_A_HOLD(K.feet_air_time_target);
-    POST_A_HOLD(K.feet_height_target); POST_A_HOLD(K.na); POST_A_HOLD(K.use_terrain);
+    POST_A_HOLD(K.feet_height_target); POST_A_HOLD(K.na); POST_A_HOLD(K.use_terrain); POST_A_HOLD(K.tile);
 #pragma unroll
     for (int i = 0; i < NM; ++i) { POST_A_HOLD(K.def[i]); POST_A_HOLD(K.force_lo[i]); POST_A_HOLD(K.force_hi[i]); }
 #pragma unroll
@@ -5548,6 +5557,13 @@ __global__ __launch_bounds__(WG * POST_A_NWAVES) void k_env_post_a(Pool P, const
   }
   rs.blv[0] = blv.x; rs.blv[1] = blv.y; rs.blv[2] = blv.z; rs.bav[0] = bav.x; rs.bav[1] = bav.y; rs.bav[2] = bav.z;
   rs.pg[0] = pg.x; rs.pg[1] = pg.y; rs.pg[2] = pg.z; rs.base_pos[0] = bp.x; rs.base_pos[1] = bp.y; rs.base_pos[2] = bp.z;
+  // tile mode (include/go2sim_tiles.h; a branch uniform over the launch): the bilinear ground height under the base, formed by wave 0, which keeps it
+  // and runs the boundary test, and by the wave that owns the base-height term
+  const bool tile = K.tile && m.terrain_enabled;
+  if (tile && (w0 || !deal.straight || ((mine >> GO2SIM_R_BASE_HEIGHT) & 1ull))) {
+    rs.ground = tile_ground_height(tile_field(m), bp.x, bp.y);
+    if (w0) e.ground_height()[0] = rs.ground;
+  }
   if (w0) {
     auto dof_pos = e.e_dof_pos(); auto dof_vel = e.e_dof_vel();
 #pragma unroll
@@ -5581,6 +5597,7 @@ __global__ __launch_bounds__(WG * POST_A_NWAVES) void k_env_post_a(Pool P, const
     rst |= dm_abs(eul.x) > c.f[GO2SIM_FC_TERM_ROLL_DEG];
     rst |= dm_abs(blv.z) > c.f[GO2SIM_FC_TERM_ZVEL];
     rst |= dm_abs(blv.y) > c.f[GO2SIM_FC_TERM_YVEL];
+    if (tile) { auto sp = e.spawn_pos(); rst |= tile_out_of_bounds(bp.x, bp.y, sp[0], sp[1], c.f[GO2SIM_FC_TILE_MAX_WANDER]); }   // not a time-out
     time_out = (ep_len > maxlen) ? 1.0f : 0.0f;
     e.reset_buf()[0] = rst; e.time_out()[0] = time_out;
   }
@@ -5948,6 +5965,10 @@ DEV void env_reset_one(const Model& m, const DCfg& c, const Glob& g, const E& e,
   { auto ncv = e.ncache_valid(); for (int p = 0; p < NCV; ++p) ncv[p] = 0; }   // normal cache := zeros
   float bpx = c.f[GO2SIM_FC_BASE_INIT_POS0], bpy = c.f[GO2SIM_FC_BASE_INIT_POS0 + 1], bpz = c.f[GO2SIM_FC_BASE_INIT_POS0 + 2];
   float bq[4] = {c.f[GO2SIM_FC_BASE_INIT_QUAT0], c.f[GO2SIM_FC_BASE_INIT_QUAT0 + 1], c.f[GO2SIM_FC_BASE_INIT_QUAT0 + 2], c.f[GO2SIM_FC_BASE_INIT_QUAT0 + 3]};
+  if (c.i[GO2SIM_IC_TILE_MODE]) {                                      // tile mode: the spawn record k_env_tile_spawn wrote ahead of this reset; init_pos_z_range is ignored
+    auto sp = e.spawn_pos();
+    bpx = sp[0]; bpy = sp[1]; bpz = sp[2];
+  } else
   if (c.i[GO2SIM_IC_USE_TERRAIN]) {                                    // _get_terrain_spawn_pos, go2_env_stair.py:856-871, :1531-1540
     const float* rcn = &c.f[GO2SIM_FC_ROW_CENTER0 + 3 * e.terrain_row()[0]];
     float init_z = c.f[GO2SIM_FC_BASE_INIT_POS0 + 2];
@@ -6036,6 +6057,27 @@ __global__ __launch_bounds__(256) void k_env_terrain_rows(Pool P, const DCfg* __
     e.terrain_row()[0] = row;
   }
   atomicAdd(&g.terrain_row_sum, row);
+}
+
+// Tile mode (include/go2sim_tiles.h, "Spawn"; TerrainManager.sample_spawn): every env whose reset flag is set draws its tile and jitter, looks up the
+// ground there and records spawn position and tile; the reset that follows (env_reset_one) puts the base there.  One lane per env, one Philox block
+// per reset env, keyed like the other draws of a reset.  Gated on g.n_reset_now.  Envs that are not reset keep their record.
+__global__ __launch_bounds__(256) void k_env_tile_spawn(Pool P, const Model* __restrict__ mp, const DCfg* __restrict__ cp, const Glob* __restrict__ gp, uint64_t seed) {
+  const DCfg& c = *cp; const Glob& g = *gp; const Model& m = *mp;
+  if (!c.i[GO2SIM_IC_TILE_MODE] || !m.terrain_enabled || g.n_reset_now <= 0) return;
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= P.B) return;
+  E e(P, b);
+  if (!e.reset_buf()[0]) return;
+  TileGrid G;
+  G.n_rows = imx(1, c.i[GO2SIM_IC_TILE_N_ROWS]); G.n_cols = imx(1, c.i[GO2SIM_IC_TILE_N_COLS]);
+  G.size_x = c.f[GO2SIM_FC_TILE_SIZE_X]; G.size_y = c.f[GO2SIM_FC_TILE_SIZE_Y];
+  G.jitter_x = c.f[GO2SIM_FC_TILE_JITTER_X]; G.jitter_y = c.f[GO2SIM_FC_TILE_JITTER_Y];
+  G.base_z = c.f[GO2SIM_FC_BASE_INIT_POS0 + 2]; G.spawn_offset = c.f[GO2SIM_FC_TILE_SPAWN_OFFSET];
+  const TileSpawn s = tile_spawn(tile_field(m), G, rng4(seed, GO2SIM_TILES_RNG_PURPOSE, (uint32_t)b, g.reset_calls - 1, 0));
+  auto sp = e.spawn_pos();
+  sp[0] = s.x; sp[1] = s.y; sp[2] = s.z;
+  e.tile_row()[0] = s.row; e.tile_col()[0] = s.col;
 }
 
 __global__ __launch_bounds__(WG) void k_env_reset_tail(Pool P, const Model* __restrict__ mp, const DCfg* __restrict__ cp, const Glob* __restrict__ gp, uint64_t seed) {
@@ -6730,6 +6772,7 @@ static void build_launch_list(const go2sim* h, LaunchList& L, int n, const StepI
   L.post_a = (int)L.v.size();
   add_launch(L, T_ENV_POST, k_env_post_a, ge, dim3(WG * POST_A_NWAVES), h->P, h->dm, h->hcfg, h->dglob, h->dacc, h->seed, h->step_count, deal_terms(h->hcfg));
   if (h->hcfg.i[GO2SIM_IC_USE_TERRAIN]) add_launch(L, T_ENV_POST, k_env_terrain_rows, dim3((h->B + 255) / 256), dim3(256), h->P, h->dcfg, h->dglob, h->seed);
+  if (h->hcfg.i[GO2SIM_IC_TILE_MODE]) add_launch(L, T_ENV_POST, k_env_tile_spawn, dim3((h->B + 255) / 256), dim3(256), h->P, h->dm, h->dcfg, h->dglob, h->seed);
   L.post_b = (int)L.v.size();
   add_launch(L, T_ENV_POST, k_env_post_b_team<16>, dim3((h->B + 3) / 4), dim3(128), h->P, h->dm, h->dms, h->dcfg, h->dglob, h->seed, h->step_count, io->obs, io->priv, io->rew, io->reset, io->timeout);
   if (h->hcfg.i[GO2SIM_IC_ENGINE_BATCH_GAIN]) add_launch(L, T_ENV_POST, k_env_engine_gains, dim3(1), dim3(GAIN_WG), h->P, h->dm, h->dms, h->dcfg, h->dglob);
@@ -7036,16 +7079,13 @@ __global__ void k_set_link0_pose(Pool P, V3 pos) {
   auto ncv = e.ncache_valid();
   for (int p = 0; p < NCV; ++p) ncv[p] = 0;
 }
-int go2sim_set_terrain(go2sim_t* h, const int16_t* hf, int rows, int cols, float horizontal_scale, float vertical_scale, const float* origin, void* stream) {
-  if (!h || !hf || rows < 2 || cols < 2 || !origin || !(horizontal_scale > 0.0f)) return GO2SIM_E_BADARG;
-  if (!terrain_cells_fit(h->hm, horizontal_scale)) return GO2SIM_E_BADARG;
-  hipStream_t s = (hipStream_t)stream;
+// what go2sim_set_terrain and go2sim_set_terrain_f32 share: the heights in metres become the handle's heightfield
+static int set_terrain_metres(go2sim_t* h, const std::vector<float>& hfm, int rows, int cols, float horizontal_scale, const float* origin, hipStream_t s) {
   HIPCHK(hipStreamSynchronize(s));
   h->step.clear();         // the solver kernel of the env step's list depends on the terrain flag
   Model& m = h->hm;
-  std::vector<float> hfm((size_t)rows * cols);
   float hmax = -1e30f, hmin = 1e30f;
-  for (size_t k = 0; k < hfm.size(); ++k) { float v = (float)hf[k] * vertical_scale; hfm[k] = v; hmax = (hmax < v) ? v : hmax; hmin = (v < hmin) ? v : hmin; }
+  for (size_t k = 0; k < hfm.size(); ++k) { float v = hfm[k]; hmax = (hmax < v) ? v : hmax; hmin = (v < hmin) ? v : hmin; }
   if (h->terrain_hf) (void)hipFree(h->terrain_hf);
   HIPCHK(hipMalloc((void**)&h->terrain_hf, hfm.size() * sizeof(float)));
   HIPCHK(hipMemcpy(h->terrain_hf, hfm.data(), hfm.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -7072,6 +7112,28 @@ int go2sim_set_terrain(go2sim_t* h, const int16_t* hf, int rows, int cols, float
   launch_fk_team(h, s, 1, nullptr);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(s));
+  return GO2SIM_E_OK;
+}
+int go2sim_set_terrain(go2sim_t* h, const int16_t* hf, int rows, int cols, float horizontal_scale, float vertical_scale, const float* origin, void* stream) {
+  if (!h || !hf || rows < 2 || cols < 2 || !origin || !(horizontal_scale > 0.0f)) return GO2SIM_E_BADARG;
+  if (!terrain_cells_fit(h->hm, horizontal_scale)) return GO2SIM_E_BADARG;
+  std::vector<float> hfm((size_t)rows * cols);
+  for (size_t k = 0; k < hfm.size(); ++k) hfm[k] = (float)hf[k] * vertical_scale;
+  return set_terrain_metres(h, hfm, rows, cols, horizontal_scale, origin, (hipStream_t)stream);
+}
+// include/go2sim_tiles.h: the heights as float32 metres
+int go2sim_set_terrain_f32(go2sim_t* h, const float* hf, int rows, int cols, float horizontal_scale, const float* origin, void* stream) {
+  if (!h || !hf || rows < 2 || cols < 2 || !origin || !(horizontal_scale > 0.0f)) return GO2SIM_E_BADARG;
+  if (!terrain_cells_fit(h->hm, horizontal_scale)) return GO2SIM_E_BADARG;
+  std::vector<float> hfm(hf, hf + (size_t)rows * cols);
+  for (float v : hfm) if (!(v - v == 0.0f)) return GO2SIM_E_BADARG;     // NaN or infinite
+  return set_terrain_metres(h, hfm, rows, cols, horizontal_scale, origin, (hipStream_t)stream);
+}
+// include/go2sim_tiles.h: the heightfield for the query on arbitrary points (csrc/go2sim_tiles.hip)
+int go2sim_tiles_env_field(go2sim_t* h, const float** hf, int* rows, int* cols, float* origin_xy2, float* horizontal_scale) {
+  if (!h || !hf || !rows || !cols || !origin_xy2 || !horizontal_scale || !h->hm.terrain_enabled) return GO2SIM_E_BADARG;
+  const TileField T = tile_field(h->hm);
+  *hf = T.hf; *rows = T.rows; *cols = T.cols; origin_xy2[0] = T.ox; origin_xy2[1] = T.oy; *horizontal_scale = T.hs;
   return GO2SIM_E_OK;
 }
 int go2sim_set_dof_gains(go2sim_t* h, int d, float kp, float kv, float flo, float fhi) {
@@ -7109,6 +7171,8 @@ int go2sim_env_configure(go2sim_t* h, const double* f, int nf, const int* i, int
     for (int k = 0; k < c.i[GO2SIM_IC_N_REWARDS]; ++k) { int id = c.i[GO2SIM_IC_REWARD_ID0 + k]; if (id < 0 || id >= GO2SIM_R_COUNT) return GO2SIM_E_BADARG; }
     if (c.i[GO2SIM_IC_ENGINE_BATCH_GAIN] && (c.i[GO2SIM_IC_ENV_KIND] != 0 || c.i[GO2SIM_IC_MANUAL_PD] || c.i[GO2SIM_IC_SHARED_GLOBALS] || P_B_MAX_GAIN < h->B))
       return GO2SIM_E_BADARG;                                             // (one batch gain: not sharded; k_env_engine_gains: exact float64 sum up to 2^23 / 12 envs)
+    if (c.i[GO2SIM_IC_TILE_MODE] && (c.i[GO2SIM_IC_ENV_KIND] != 0 || c.i[GO2SIM_IC_USE_TERRAIN] || c.i[GO2SIM_IC_TILE_N_ROWS] < 1 || c.i[GO2SIM_IC_TILE_N_COLS] < 1))
+      return GO2SIM_E_BADARG;                                             // (tile mode, include/go2sim_tiles.h: the walk env, without the stair env's terrain terms)
     h->step.clear();         // the configuration is baked into the kernel arguments of the env step's list
     h->hcfg = c;
   }
@@ -7135,8 +7199,11 @@ int go2sim_env_configure(go2sim_t* h, const double* f, int nf, const int* i, int
   return GO2SIM_E_OK;
 }
 
+// tile mode reads the heightfield: a handle configured for it steps and resets only once go2sim_set_terrain[_f32] has installed one
+static bool tile_mode_without_field(const go2sim* h) { return h->hcfg.i[GO2SIM_IC_TILE_MODE] && !h->hm.terrain_enabled; }
 int go2sim_env_step(go2sim_t* h, const float* actions, float* obs, float* priv, float* rew, uint8_t* reset, float* timeout, void* stream) {
   if (!h || !h->cfg_set || !actions) return GO2SIM_E_BADARG;
+  if (tile_mode_without_field(h)) return GO2SIM_E_BADARG;
   hipStream_t s = (hipStream_t)stream;
   LaunchList& L = h->step;
   const StepIO io{actions, obs, priv, rew, reset, timeout};
@@ -7168,12 +7235,13 @@ static void launch_reset_marked(go2sim* h, hipStream_t s) {
   const dim3 g = grid_for(h->B), b(WG);
   hipLaunchKernelGGL(k_env_globals, dim3(1), dim3(1), 0, s, h->dcfg, h->dglob, h->dacc, h->seed, 0);
   if (h->hcfg.i[GO2SIM_IC_USE_TERRAIN]) hipLaunchKernelGGL(k_env_terrain_rows, dim3((h->B + 255) / 256), dim3(256), 0, s, h->P, h->dcfg, h->dglob, h->seed);
+  if (h->hcfg.i[GO2SIM_IC_TILE_MODE]) hipLaunchKernelGGL(k_env_tile_spawn, dim3((h->B + 255) / 256), dim3(256), 0, s, h->P, h->dm, h->dcfg, h->dglob, h->seed);
   hipLaunchKernelGGL(k_env_reset_tail, g, b, 0, s, h->P, h->dm, h->dcfg, h->dglob, h->seed);
   if (h->hcfg.i[GO2SIM_IC_ENGINE_BATCH_GAIN]) hipLaunchKernelGGL(k_env_engine_gains, dim3(1), dim3(GAIN_WG), 0, s, h->P, h->dm, h->dms, h->dcfg, h->dglob);
   launch_fk_team(h, s, 1, &h->dglob->n_reset_now);
 }
 int go2sim_env_reset(go2sim_t* h, void* stream) {
-  if (!h || !h->cfg_set) return GO2SIM_E_BADARG;
+  if (!h || !h->cfg_set || tile_mode_without_field(h)) return GO2SIM_E_BADARG;
   hipStream_t s = (hipStream_t)stream;
   ScopedTimer t(h, s, T_MISC);
   HIPCHK(hipMemsetAsync(h->dacc, 0, sizeof(Acc), s));
@@ -7183,7 +7251,7 @@ int go2sim_env_reset(go2sim_t* h, void* stream) {
   return GO2SIM_E_OK;
 }
 int go2sim_env_reset_idx(go2sim_t* h, const int* envs_idx, int n_sel, void* stream) {
-  if (!h || !h->cfg_set || (n_sel > 0 && !envs_idx) || n_sel < 0) return GO2SIM_E_BADARG;
+  if (!h || !h->cfg_set || (n_sel > 0 && !envs_idx) || n_sel < 0 || tile_mode_without_field(h)) return GO2SIM_E_BADARG;
   if (n_sel == 0) return GO2SIM_E_OK;                                  // `if len(envs_idx) == 0: return`, go2_env_walk.py:1157
   hipStream_t s = (hipStream_t)stream;
   ScopedTimer t(h, s, T_MISC);
@@ -7279,6 +7347,10 @@ int go2sim_env_get(go2sim_t* h, int buf, void* dst, void* stream) {
     case GO2SIM_EB_REW_TERMS: k = NREW; src = F + FO(rew_terms) * B; break;
     case GO2SIM_EB_TORQUE: k = 12; src = F + FO(torque) * B; break;
     case GO2SIM_EB_TERRAIN_ROW: k = 1; src = I + IO(terrain_row) * B; break;
+    case GO2SIM_EB_GROUND_HEIGHT: k = 1; src = F + FO(ground_height) * B; break;
+    case GO2SIM_EB_SPAWN_POS: k = 3; src = F + FO(spawn_pos) * B; break;
+    case GO2SIM_EB_TILE_ROW: k = 1; src = I + IO(tile_row) * B; break;
+    case GO2SIM_EB_TILE_COL: k = 1; src = I + IO(tile_col) * B; break;
     default: return GO2SIM_E_BADARG;
   }
   int n = k * h->B;

@@ -20,7 +20,9 @@ import types
 import numpy as np
 import torch
 
+from . import terrain_tiles
 from .capi import C, Go2Sim, Go2SimError, load_hip_lib
+from .terrain_tiles import install_terrain
 from .model_blob import MODEL_JSON, load_model_json, pack_model, with_plane_ground
 
 gpu, cpu = "gpu", "cpu"
@@ -68,7 +70,31 @@ def _plane(pos=(0.0, 0.0, 0.0), normal=(0.0, 0.0, 1.0), plane_size=(1e3, 1e3), *
     return _Opt(kind="plane", pos=tuple(pos), normal=tuple(n / np.linalg.norm(n)), plane_size=tuple(plane_size), **kw)
 
 
-morphs = types.SimpleNamespace(URDF=lambda **kw: _Opt(kind="urdf", **kw), Terrain=lambda **kw: _Opt(kind="terrain", **kw), Plane=_plane)
+def _terrain(height_field=None, horizontal_scale=0.25, vertical_scale=0.005, pos=(0.0, 0.0, 0.0), n_subterrains=(3, 3), subterrain_size=(12.0, 12.0),
+             subterrain_types=None, subterrain_parameters=None, randomize=False, **kw):
+    """gs.morphs.Terrain (options/morphs.py): a ready `height_field` (int16 raw units, or a float array: heights = field x vertical_scale), or the
+    grid form -- `n_subterrains` tiles of `subterrain_size` whose field terrain_tiles.generate_tiles makes when the morph is created (numpy's global
+    generator, as in the reference), for `flat_terrain` and `random_uniform_terrain`; every other subterrain name is refused by name."""
+    if height_field is not None:
+        hf = np.asarray(height_field)
+        if hf.ndim != 2:
+            raise GenesisException("`height_field` should be a 2D array.")
+        if not np.issubdtype(hf.dtype, np.integer):
+            hf = hf.astype(np.float32)
+    else:
+        if subterrain_types is None:
+            raise GenesisException("go2sim generates no default subterrain grid: pass `subterrain_types` (flat_terrain / random_uniform_terrain) or a `height_field`")
+        try:
+            subterrain_types = terrain_tiles.check_subterrain_types(subterrain_types, n_subterrains)     # (the shape must be `n_subterrains`, as in the reference)
+            hf = terrain_tiles.generate_tiles(subterrain_types, subterrain_size, float(horizontal_scale), float(vertical_scale), randomize=bool(randomize),
+                                              subterrain_parameters=subterrain_parameters)
+        except terrain_tiles.TerrainError as e:
+            raise GenesisException(str(e)) from None
+    return _Opt(kind="terrain", height_field=hf, horizontal_scale=float(horizontal_scale), vertical_scale=float(vertical_scale), pos=tuple(pos),
+                n_subterrains=tuple(n_subterrains), subterrain_size=tuple(subterrain_size), subterrain_types=subterrain_types, randomize=bool(randomize), **kw)
+
+
+morphs = types.SimpleNamespace(URDF=lambda **kw: _Opt(kind="urdf", **kw), Terrain=_terrain, Plane=_plane)
 # robot URDF (file name stem) -> compiled model (tools/compile_go2_model.py --robot ...)
 ROBOT_MODELS = {"go2": MODEL_JSON, "anymal_c": os.path.join(os.path.dirname(MODEL_JSON), "anymal_c_model.json")}
 GROUND_RANGE = (0, 1, 0, 0)     # link_start, link_end, dof_start, dof_end of the ground entity (entity 0 of every compiled model)
@@ -457,6 +483,8 @@ class Scene:
                 raise GenesisException("the compiled scene has exactly one ground entity")
             self._ground_morph = morph
             ent = RigidEntity(self, morph, *GROUND_RANGE)
+            if kind == "terrain":
+                ent.height_field = morph.height_field                    # raw units; TerrainManager.post_build looks for it (terrain_manager.py:233)
         elif kind == "urdf" and stem in ROBOT_MODELS:
             if self._robot is not None:
                 raise GenesisException("the compiled scene has exactly one robot")
@@ -482,8 +510,7 @@ class Scene:
             model = with_plane_ground(model, pos=g.pos, normal=g.normal, plane_size=g.plane_size)
         self._sim = Go2Sim(_lib, pack_model(model), int(n_envs), device.index or 0, _seed)
         if getattr(g, "kind", None) == "terrain":
-            self._sim.set_terrain(np.asarray(g.height_field, np.int16), float(g.horizontal_scale), float(g.vertical_scale),
-                                  list(getattr(g, "pos", (0.0, 0.0, 0.0))))
+            install_terrain(self._sim, g.height_field, float(g.horizontal_scale), float(g.vertical_scale), list(getattr(g, "pos", (0.0, 0.0, 0.0))))
         m = self._robot.morph
         if getattr(m, "pos", None) is not None or getattr(m, "quat", None) is not None:     # initial base pose of the URDF morph
             q = self._robot._get("F_QPOS")

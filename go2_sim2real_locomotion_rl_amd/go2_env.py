@@ -29,6 +29,8 @@ from .configs import build_stair_terrain, flatten_base_cfg, flatten_walk_cfg
 from .lidar import LidarScan, check_lidar_widths, env_pose_ptrs, lidar_enabled, lidar_layout
 from .model_blob import pack_model
 from .stairinfo import NUM_STAIR_INFO, StairInfo, check_one_exteroceptive_layout, check_stair_info_widths, env_rows_ptr, stair_info_enabled
+from .terrain_manager import TerrainManager
+from .terrain_tiles import install_terrain, is_tile_terrain_cfg
 
 _DEVICE = None
 _SEED = 1
@@ -174,6 +176,7 @@ class Go2Env:
         self.is_base_env = is_base_env_cfg(env_cfg, obs_cfg)
         self._lidar = None
         self._stairinfo = None
+        self.terrain = None                                                # the TerrainManager of the rough-terrain env
         if self.is_base_env:
             fcfg, icfg, self._reward_names = flatten_base_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg)
             self.num_privileged_obs = None
@@ -203,7 +206,17 @@ class Go2Env:
                                   "and the base layout (12 actions, 45 obs; go2_train_crouch.py / "
                                   "go2_train_jump.py)")
             terrain_cfg = env_cfg.get("terrain", None)
-            if terrain_cfg is not None and terrain_cfg.get("enabled", False):     # go2_env_stair.py:352-433: gs.morphs.Terrain instead of the plane
+            if is_tile_terrain_cfg(terrain_cfg):
+                # the rough-terrain env (go2_env_Omni_kplearn_varied_terrain.py:  a terrain dictionary with `subterrain_types` or a `height_field`):
+                # the manager makes the morph, the library takes its field and runs ground height, boundary and spawn itself (include/go2sim_tiles.h)
+                if inner_obs_cfg is not obs_cfg:
+                    raise Go2SimError("the LIDAR / stair-info layouts belong to the stair terrain, not to a tile terrain")
+                self.terrain = TerrainManager(terrain_cfg, num_envs, device=self.device)
+                morph = self.terrain.build_terrain_morph()
+                install_terrain(self._sim, morph.height_field, morph.horizontal_scale, morph.vertical_scale, list(morph.pos))
+                self.terrain.post_build(morph)
+                self.terrain.bind(self)
+            elif terrain_cfg is not None and terrain_cfg.get("enabled", False):   # go2_env_stair.py:352-433: gs.morphs.Terrain instead of the plane
                 hf, info = build_stair_terrain(terrain_cfg)
                 self._terrain_info = info
                 self._sim.set_terrain(hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"])
@@ -455,6 +468,8 @@ class Go2Env:
     base_pos = property(lambda self: self._env_view("BASE_POS", 3))
     base_quat = property(lambda self: self._env_view("BASE_QUAT", 4))
     base_euler = property(lambda self: self._env_view("BASE_EULER", 3))
+    # rough-terrain env (go2_env_Omni_kplearn_varied_terrain.py `_ground_height`): the bilinear ground height under the base at the last step
+    _ground_height = property(lambda self: self._env_view("GROUND_HEIGHT", 1))
 
     @property
     def episode_sums(self):

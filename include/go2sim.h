@@ -188,7 +188,14 @@ enum go2sim_fcfg {
   GO2SIM_FC_ROW_CENTER0,                                   /* 16 x (x, y, z) spawn centres of the difficulty rows */
   GO2SIM_FC_SCAN_X0 = GO2SIM_FC_ROW_CENTER0 + 48,          /* 80 body-frame x offsets of the height-scan grid (row-major nx x ny) */
   GO2SIM_FC_SCAN_Y0 = GO2SIM_FC_SCAN_X0 + 80,              /* 80 body-frame y offsets */
-  GO2SIM_FC_COUNT = GO2SIM_FC_SCAN_Y0 + 80
+  GO2SIM_FC_COUNT = GO2SIM_FC_SCAN_Y0 + 80,
+  /* rough-terrain walk env (include/go2sim_tiles.h; go2_env_Omni_kplearn_varied_terrain.py + terrain_manager.py): the tile size, the spawn
+     jitter (size / 2 - boundary_margin - 0.5 per axis; <= 0: none), max_wander and spawn_height_offset.  All float32 constants of the per-env
+     arithmetic; the placement of the heightfield (origin, cell size) is the one go2sim_set_terrain[_f32] installed.
+     The length of the float array is unchanged: these six are NAMES FOR THE FIRST SIX WORDS OF THE STAIR ENV'S ROW-CENTRE TABLE, which only
+     GO2SIM_IC_USE_TERRAIN reads and GO2SIM_IC_TILE_MODE excludes (go2sim_env_configure refuses both at once). */
+  GO2SIM_FC_TILE_SIZE_X = GO2SIM_FC_ROW_CENTER0, GO2SIM_FC_TILE_SIZE_Y,
+  GO2SIM_FC_TILE_JITTER_X, GO2SIM_FC_TILE_JITTER_Y, GO2SIM_FC_TILE_MAX_WANDER, GO2SIM_FC_TILE_SPAWN_OFFSET
 };
 enum go2sim_icfg {
   GO2SIM_IC_ENV_KIND = 0, /* 0 = walk (go2_env_walk.py), 1 = base (go2_env_base.py: crouch / jump; engine PD, reset before reward, 45 obs) */
@@ -219,6 +226,10 @@ enum go2sim_icfg {
                                   shards with go2sim_env_sync_counters / _sync_apply / _set_global_dr (distributed.sync_env_globals) */
   GO2SIM_IC_ENGINE_BATCH_GAIN, /* walk / stair env with PLS off, no kp_factor_range, kp_range set (go2_env_walk.py:797-801): engine PD whose
                                   motor-dof kp / kv become the mean of the effective gains drawn in each reset call (go2sim_env_globals_t.engine_kp / _kd) */
+  /* rough-terrain walk env (include/go2sim_tiles.h): the walk env on a heightfield with a bilinear ground height under the base, a boundary
+     termination and a random spawn tile per reset.  Independent of GO2SIM_IC_USE_TERRAIN (the stair env's rows, scan and foot terms stay off);
+     the heightfield itself is installed with go2sim_set_terrain / go2sim_set_terrain_f32.  A 1 x 1 grid is the heightmap mode. */
+  GO2SIM_IC_TILE_MODE, GO2SIM_IC_TILE_N_ROWS, GO2SIM_IC_TILE_N_COLS,
   GO2SIM_IC_COUNT
 };
 /* reward terms of go2_env_walk.py:1251-1366 */
@@ -255,6 +266,10 @@ enum go2sim_env_buf {
   GO2SIM_EB_REW_TERMS,        /* f32 k=32 per-term reward of the last step (already x scale) */
   GO2SIM_EB_TORQUE,           /* f32 k=12 last commanded torque */
   GO2SIM_EB_TERRAIN_ROW,      /* i32 k=1  difficulty row of the env (go2_env_stair.py:_env_terrain_row) */
+  GO2SIM_EB_GROUND_HEIGHT,    /* f32 k=1  tile mode: bilinear ground height under the base at the last step (env._ground_height) */
+  GO2SIM_EB_SPAWN_POS,        /* f32 k=3  tile mode: spawn position of the env's last reset (TerrainManager._env_spawn_pos) */
+  GO2SIM_EB_TILE_ROW,         /* i32 k=1  tile mode: spawn tile of the env's last reset (TerrainManager._env_tile_row) */
+  GO2SIM_EB_TILE_COL,         /* i32 k=1  (TerrainManager._env_tile_col) */
   GO2SIM_EB_COUNT
 };
 

@@ -6,6 +6,7 @@
     python tools/train.py --task walk --envs 4096 --iterations 1000 --empirical-normalization           # running observation statistics in front of the policy
     python tools/train.py --task stairs_lidar --envs 4096 --iterations 1000                             # the stair env with the actor's LIDAR terrain scan (64 / 165 inputs)
     python tools/train.py --task stairs_info --envs 4096 --iterations 1000                              # the stair env with the four-value stair info (53 / 113 inputs)
+    python tools/train.py --task rough --terrain-mode grid --envs 4096 --iterations 1000                # the walk env on rough ground (heightmap or tile grid)
     python tools/train.py --task stairs_lidar --envs 4096 --iterations 1000 --actor-obs critic --log-dir logs/teacher   # a teacher: the actor reads the privileged rows
     python tools/train.py --task stairs_lidar --envs 4096 --iterations 500 --distill logs/teacher/model_1000.pt --teacher-obs critic   # distil it into a student
     python tools/train.py --task stairs_lidar --distill logs/teacher/model_1000.pt --teacher-obs critic --student-recurrent --rnn-hidden 256   # ... a student with an LSTM memory
@@ -27,12 +28,15 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-TASKS = ("walk", "stairs", "stairs_lidar", "stairs_info", "crouch", "jump")
+TASKS = ("walk", "stairs", "stairs_lidar", "stairs_info", "rough", "crouch", "jump")
 
 
-def task_cfgs(task):
-    from go2_sim2real_locomotion_rl_amd import get_crouch_cfgs, get_jump_cfgs, get_stair_cfgs, get_stair_info_cfgs, get_stair_lidar_cfgs, get_walk_cfgs
+def task_cfgs(task, terrain_mode="heightmap", terrain_seed=0):
+    from go2_sim2real_locomotion_rl_amd import (get_crouch_cfgs, get_jump_cfgs, get_rough_cfgs, get_stair_cfgs, get_stair_info_cfgs, get_stair_lidar_cfgs,
+                                                get_walk_cfgs)
 
+    if task == "rough":                                        # go2_train_Omni_kplearn_varied_terrain.py: the walk env on a heightmap or a tile grid
+        return get_rough_cfgs(terrain_mode, seed=terrain_seed)
     return {"walk": get_walk_cfgs, "stairs": get_stair_cfgs, "stairs_lidar": get_stair_lidar_cfgs, "stairs_info": get_stair_info_cfgs, "crouch": get_crouch_cfgs, "jump": get_jump_cfgs}[task]()
 
 
@@ -41,6 +45,7 @@ def train_cfg_of(task, cfgs_path=None):
         from go2_sim2real_locomotion_rl_amd import load_cfgs
 
         return load_cfgs(cfgs_path)[4]
+    task = "rough_heightmap" if task == "rough" else task                      # (both terrain modes train with the same train_cfg)
     task = "stairs" if task in ("stairs_lidar", "stairs_info") else task        # both lidar scripts train with go2_train_stair.py's train_cfg (only the experiment name differs)
     return json.load(open(os.path.join(ROOT, "tests", "golden", f"ref_cfgs_{task}.json")))["train_cfg"]
 
@@ -48,6 +53,8 @@ def train_cfg_of(task, cfgs_path=None):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--task", choices=TASKS, default="walk")
+    ap.add_argument("--terrain-mode", choices=("heightmap", "grid"), default="heightmap", help="--task rough: the train script's TERRAIN_MODE")
+    ap.add_argument("--terrain-seed", type=int, default=0, help="--task rough: seeds the heightmap's bumps and, through numpy's global generator, the grid's tiles")
     ap.add_argument("--envs", type=int, default=4096, help="environments per rank")
     ap.add_argument("--iterations", type=int, default=1000)
     ap.add_argument("--log-dir", default=None, help="checkpoints go here (rank 0); none are written without it")
@@ -109,7 +116,11 @@ def main():
 
         seed = shard_seed(args.seed, rank)
         init(seed=seed, device_index=local_rank)
-        env = Go2Env(args.envs, *task_cfgs(args.task), seed=seed, device=device, shared_globals=world > 1)
+        if args.task == "rough":
+            import numpy as np
+
+            np.random.seed(args.terrain_seed)                  # every rank generates the same tiles
+        env = Go2Env(args.envs, *task_cfgs(args.task, args.terrain_mode, args.terrain_seed), seed=seed, device=device, shared_globals=world > 1)
         cfg = train_cfg_of(args.task, args.cfgs)
         cfg["seed"] = args.seed
         if args.steps_per_env:
