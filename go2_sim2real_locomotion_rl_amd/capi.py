@@ -68,6 +68,7 @@ RDISTILL_HEADER, DECLARED_RDISTILL_FUNCS = _product_header("rdistill")         #
 ACT_HEADER, DECLARED_ACT_FUNCS = _product_header("activation")                 # the hidden-layer activation of an MLP
 RND_HEADER, DECLARED_RND_FUNCS = _product_header("rnd")                        # random network distillation: the intrinsic reward and the predictor's update
 TILES_HEADER, DECLARED_TILES_FUNCS = _product_header("tiles")                  # the rough-terrain walk env: float heightfield, ground query
+WELLS_HEADER, DECLARED_WELLS_FUNCS = _product_header("wells")                  # the stairwell env: 11 x 11 scan, alive term
 # train_cfg["policy"]["activation"] as rsl_rl's resolve_nn_activation spells it -> GO2SIM_ACT_*
 ACTIVATIONS = {n: C["GO2SIM_ACT_" + n.upper()] for n in ("elu", "selu", "relu", "lrelu", "tanh", "sigmoid", "identity")}
 

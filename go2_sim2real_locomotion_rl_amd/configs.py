@@ -12,6 +12,7 @@ import numpy as np
 from .capi import C, Go2SimError
 from .model_blob import load_model_json
 from .terrain_tiles import is_tile_terrain_cfg, tile_layout
+from .terrain_wells import build_stairwell_terrain, is_well_terrain_cfg, well_centers
 
 REWARD_IDS = {
     "tracking_lin_vel": "GO2SIM_R_TRACKING_LIN_VEL", "tracking_ang_vel": "GO2SIM_R_TRACKING_ANG_VEL",
@@ -156,6 +157,8 @@ def flatten_walk_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg, *, mod
     f[F("FEET_AIR_TIME_TARGET")] = reward_cfg.get("feet_air_time_target", 0.1)
     f[F("FOOT_CONTACT_THRESHOLD")] = env_cfg.get("foot_contact_threshold", 1.0)
     names = list(reward_cfg["reward_scales"].keys())
+    if is_well_terrain_cfg(env_cfg.get("terrain")) and "alive" in names:
+        names.remove("alive")                                # the stairwell env's alive term is the wells launch's (include/go2sim_wells.h), not a core term
     assert len(names) <= 32
     for k, name in enumerate(names):
         if name not in REWARD_IDS:
@@ -273,6 +276,20 @@ def flatten_walk_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg, *, mod
         f[F("TILE_SIZE_X")], f[F("TILE_SIZE_Y")] = L["subterrain_size"]
         f[F("TILE_JITTER_X")], f[F("TILE_JITTER_Y")] = L["jitter"]
         f[F("TILE_MAX_WANDER")], f[F("TILE_SPAWN_OFFSET")] = L["max_wander"], L["spawn_height_offset"]
+    elif is_well_terrain_cfg(tcfg):
+        # ---- stairwell env (go2_env_stair6_Omni.py; include/go2sim_wells.h): the stair env's rows are the well levels, the row centres the well
+        # centres (kept as doubles: the spawn law adds the offset in float64), the scan is the wells launch's ----
+        from .wells import check_well_scan_shape
+
+        _, info = build_stairwell_terrain(tcfg)
+        n_levels = info["num_difficulty_levels"]
+        if n_levels > C["GO2SIM_WELLS_LEVELS_MAX"]:
+            raise Go2SimError(f"the stairwell env holds at most {C['GO2SIM_WELLS_LEVELS_MAX']} difficulty levels, got {n_levels}")
+        check_well_scan_shape(tcfg)
+        i[I("USE_TERRAIN")], i[I("N_TERRAIN_ROWS")], i[I("WELL_SPAWN")], i[I("SCAN_N")] = 1, n_levels, 1, 0
+        f[F("TERRAIN_ORIGIN_X")], f[F("TERRAIN_ORIGIN_Y")] = info["terrain_origin"][0], info["terrain_origin"][1]
+        f[F("TERRAIN_H_SCALE")] = info["horizontal_scale"]
+        f[F("ROW_CENTER0"):F("ROW_CENTER0") + 3 * n_levels] = np.asarray(well_centers(info), np.float64).reshape(-1)
     elif tcfg is not None and tcfg.get("enabled", False):
         import torch
 
@@ -666,4 +683,36 @@ def get_rough_cfgs(mode="heightmap", seed=0):
     env_cfg["terrain"] = get_rough_terrain_cfg(mode, seed)
     reward_cfg["reward_scales"]["feet_air_time"] = 0.3
     reward_cfg["reward_scales"]["foot_clearance"] = -0.3
+    return env_cfg, obs_cfg, reward_cfg, command_cfg
+
+
+# ---------------------------------------------------------------------------------------------
+# stairwell env: examples/locomotion/go2_stair_train6_Omni.py + go2_env_stair6_Omni.py (include/go2sim_wells.h)
+# ---------------------------------------------------------------------------------------------
+def get_stairwell_terrain_cfg():
+    """`terrain` block of go2_stair_train6_Omni.py:97-116 with its 11 x 11 `height_scan`."""
+    return {"enabled": True, "horizontal_scale": 0.05, "vertical_scale": 0.005, "step_depth_m": 0.39, "steps_per_flight": 10,
+            "num_flights_per_side": 2, "flat_landing_m": 1.5, "flat_bottom_m": 2.0, "flat_surround_m": 4.0, "step_height_min": 0.02,
+            "step_height_max": 0.135, "num_difficulty_levels": 9, "wells_per_row": 3,
+            "height_scan": {"num_x": 11, "num_y": 11, "x_range": [-0.5, 0.5], "y_range": [-0.5, 0.5]}}
+
+
+def get_stairwell_cfgs(pls_enable=True):
+    """go2_stair_train6_Omni.py:60-322 (values transcribed): the stair configuration on the grid of stairwells -- omnidirectional commands, termination
+    at 50 degrees, 30 s episodes, curriculum from level 0, no forward_progress, the alive term, and the 226-wide privileged observation (49 + 55 +
+    well level + 121 height-scan points; 45 + ... = 222 with `pls_enable` off)."""
+    env_cfg, obs_cfg, reward_cfg, command_cfg = get_stair_cfgs(pls_enable)
+    env_cfg["curriculum"]["level_init"] = 0.0
+    env_cfg.update({"termination_if_roll_greater_than": 50, "termination_if_pitch_greater_than": 50, "episode_length_s": 30.0,
+                    "terrain": get_stairwell_terrain_cfg()})
+    obs_cfg["num_privileged_obs"] = obs_cfg["num_obs"] + 55 + 1 + 121
+    reward_cfg["feet_height_target"] = 0.15
+    # `alive` is third in the script's dictionary.  Here it is last: the wells launch adds it after the core's sum (include/go2sim_wells.h), and with
+    # alive last the float32 sum of the terms in dictionary order is that sum to the bit.  test_wells_ref compares the dictionaries as sets of items.
+    reward_cfg["reward_scales"] = {
+        "tracking_lin_vel": 2.0, "tracking_ang_vel": 1.0, "lin_vel_z": -1.0, "base_height": -0.1, "action_rate": -0.01,
+        "similar_to_default": -0.05, "orientation_roll_only": -5.0, "dof_acc": -2.5e-7, "dof_vel": -5e-4, "ang_vel_xy": -0.05,
+        "feet_air_time": 0.2, "foot_slip": -0.15, "foot_clearance": -0.5, "joint_tracking": -0.1, "energy": 0.0, "torque_load": 0.0,
+        "stand_still": -0.5, "stand_still_vel": -2.0, "feet_stance": -0.3, "alive": 0.2}
+    command_cfg.update({"lin_vel_x_range": [-0.3, 0.8], "lin_vel_y_range": [-0.4, 0.4], "ang_vel_range": [-0.5, 0.5]})
     return env_cfg, obs_cfg, reward_cfg, command_cfg

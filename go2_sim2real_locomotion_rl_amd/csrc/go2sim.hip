@@ -34,6 +34,8 @@
 #include "../../include/go2sim_stairinfo.h"
 #include "../../include/go2sim_tiles.h"
 #include "go2sim_tiles_dev.h"
+#include "../../include/go2sim_wells.h"
+#include "go2sim_wells_dev.h"
 
 #define DEV __device__ __forceinline__
 #define DEVN __device__ __noinline__
@@ -6080,6 +6082,46 @@ __global__ __launch_bounds__(256) void k_env_tile_spawn(Pool P, const Model* __r
   e.tile_row()[0] = s.row; e.tile_col()[0] = s.col;
 }
 
+// Stairwell env (include/go2sim_wells.h, "The well spawn"; _get_spawn_pos and the yaw line of reset_idx).  It runs AFTER the reset of the flagged envs
+// (env_reset_one, which has put them on the centre of their well -- the level k_env_terrain_rows assigned -- with yaw 0) and before their kinematics are
+// refreshed for the next step: every env whose reset flag is set draws its offset from the centre and its yaw, and base position, base quaternion and the
+// spawn record (x, y, yaw) are rewritten.  env_reset_one itself is not touched: its code sits in the middle of k_env_post_b_team, where a longer reset
+// path measurably slowed the walk env's step (DESIGN.md "Stairwell env").  One lane per env, one Philox block per reset env, keyed like the other draws
+// of a reset; roll and pitch are formed again from their words of the pose block, by env_reset_one's own expressions.  Gated on g.n_reset_now.
+struct WellCentres { double xy[2 * GO2SIM_WELLS_LEVELS_MAX]; };       // (x, y) of every level as configured: the row-centre table keeps float32 only
+__global__ __launch_bounds__(256) void k_env_well_spawn(Pool P, const DCfg* __restrict__ cp, const Glob* __restrict__ gp, uint64_t seed, WellCentres W) {
+  const DCfg& c = *cp; const Glob& g = *gp;
+  if (!c.i[GO2SIM_IC_WELL_SPAWN] || !c.i[GO2SIM_IC_USE_TERRAIN] || g.n_reset_now <= 0) return;
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= P.B) return;
+  E e(P, b);
+  if (!e.reset_buf()[0]) return;
+  const uint32_t rc = g.reset_calls - 1;
+  const int lvl = imx(0, imn(e.terrain_row()[0], GO2SIM_WELLS_LEVELS_MAX - 1));
+  const dm_u4 r = rng4(seed, GO2SIM_WELLS_RNG_PURPOSE, (uint32_t)b, rc, 0);
+  double cx = W.xy[0], cy = W.xy[1];                                   // (a scan over the table: no dynamically indexed kernel argument)
+#pragma unroll
+  for (int k = 1; k < GO2SIM_WELLS_LEVELS_MAX; ++k) if (k == lvl) { cx = W.xy[2 * k]; cy = W.xy[2 * k + 1]; }
+  const float x = well_spawn_coord(cx, dm_u01(r.v[0])), y = well_spawn_coord(cy, dm_u01(r.v[1]));
+  auto base_pos = e.base_pos(); auto base_quat = e.base_quat(); auto qpos = e.qpos();
+  base_pos[0] = x; base_pos[1] = y; qpos[0] = x; qpos[1] = y;
+  e.last_base_pos_x()[0] = x;
+  float yaw = 0.0f;
+  if (c.i[GO2SIM_IC_HAS_INIT_EULER]) {                                 // euler_to_quat_wxyz with the reset's roll and pitch and this yaw
+    const dm_u4 rp = rng4(seed, RNG_RESET_POSE, (uint32_t)b, rc, 0);
+    const double D2R = 3.141592653589793 / 180.0;
+    const double lo = c.d[GO2SIM_FC_INIT_EULER_LO_DEG] * D2R, hi = c.d[GO2SIM_FC_INIT_EULER_HI_DEG] * D2R;
+    const float roll = rand_float(lo, hi, rp.v[1]), pitch = rand_float(lo, hi, rp.v[2]);
+    yaw = rand_float(lo, hi, r.v[2]);
+    float sr, cr, sp, cpp, sy, cy2;
+    dm_sincos(roll / 2.0f, &sr, &cr); dm_sincos(pitch / 2.0f, &sp, &cpp); dm_sincos(yaw / 2.0f, &sy, &cy2);
+    const float bq[4] = {cr * cpp * cy2 + sr * sp * sy, sr * cpp * cy2 - cr * sp * sy, cr * sp * cy2 + sr * cpp * sy, cr * cpp * sy - sr * sp * cy2};
+    for (int k = 0; k < 4; ++k) { base_quat[k] = bq[k]; qpos[3 + k] = bq[k]; }
+  }
+  auto sp3 = e.spawn_pos();
+  sp3[0] = x; sp3[1] = y; sp3[2] = yaw;
+}
+
 __global__ __launch_bounds__(WG) void k_env_reset_tail(Pool P, const Model* __restrict__ mp, const DCfg* __restrict__ cp, const Glob* __restrict__ gp, uint64_t seed) {
   int b = blockIdx.x * WG + threadIdx.x;
   if (b >= P.B) return;
@@ -6550,6 +6592,7 @@ struct go2sim {
   int* herr_pinned = nullptr; hipEvent_t ev_errno = nullptr; bool errno_poll_pending = false;   // go2sim_errno_poll_*
   int* didx = nullptr; int didx_cap = 0;    // scratch for index lists (go2sim_env_reset_idx)
   float* terrain_hf = nullptr;              // device copy of the heightfield in metres (go2sim_set_terrain)
+  WellCentres well_xy = {};                 // stairwell env: the well centres in double (go2sim_env_configure), an argument of k_env_well_spawn
   float* terrain_cmax = nullptr;            // ... and its coarse maximum map
   GjkStoreFull* gjk_scratch = nullptr;      // full-capacity polytope records of the GJK / EPA fallback (queries that outgrow their LDS slot) and
                                             // prism descriptors of the terrain pass: one block per (env, narrow-phase lane)
@@ -6776,6 +6819,10 @@ static void build_launch_list(const go2sim* h, LaunchList& L, int n, const StepI
   L.post_b = (int)L.v.size();
   add_launch(L, T_ENV_POST, k_env_post_b_team<16>, dim3((h->B + 3) / 4), dim3(128), h->P, h->dm, h->dms, h->dcfg, h->dglob, h->seed, h->step_count, io->obs, io->priv, io->rew, io->reset, io->timeout);
   if (h->hcfg.i[GO2SIM_IC_ENGINE_BATCH_GAIN]) add_launch(L, T_ENV_POST, k_env_engine_gains, dim3(1), dim3(GAIN_WG), h->P, h->dm, h->dms, h->dcfg, h->dglob);
+  if (h->hcfg.i[GO2SIM_IC_WELL_SPAWN]) {   // stairwell env: the reset envs move off their well's centre, then the kinematics follow (both gated on g.n_reset_now)
+    add_launch(L, T_ENV_POST, k_env_well_spawn, dim3((h->B + 255) / 256), dim3(256), h->P, h->dcfg, h->dglob, h->seed, h->well_xy);
+    add_launch(L, T_ENV_POST, fk_kernel(h->fk_team), team_grid(h, h->fk_team), dim3(64), h->P, h->dms, 1, &h->dglob->n_reset_now);
+  }
 }
 // the per-step arguments of the env step's list (argument positions: k_env_pre / k_pre_dynamics_team, k_env_post_a, k_env_post_b_team)
 template <class T> static void set_arg(Launch& e, int k, T value) { *(T*)e.args[k] = value; }
@@ -7173,8 +7220,11 @@ int go2sim_env_configure(go2sim_t* h, const double* f, int nf, const int* i, int
       return GO2SIM_E_BADARG;                                             // (one batch gain: not sharded; k_env_engine_gains: exact float64 sum up to 2^23 / 12 envs)
     if (c.i[GO2SIM_IC_TILE_MODE] && (c.i[GO2SIM_IC_ENV_KIND] != 0 || c.i[GO2SIM_IC_USE_TERRAIN] || c.i[GO2SIM_IC_TILE_N_ROWS] < 1 || c.i[GO2SIM_IC_TILE_N_COLS] < 1))
       return GO2SIM_E_BADARG;                                             // (tile mode, include/go2sim_tiles.h: the walk env, without the stair env's terrain terms)
+    if (c.i[GO2SIM_IC_WELL_SPAWN] && (c.i[GO2SIM_IC_TILE_MODE] || !c.i[GO2SIM_IC_USE_TERRAIN] || c.i[GO2SIM_IC_ENV_KIND] != 0))
+      return GO2SIM_E_BADARG;                                             // (stairwell env, include/go2sim_wells.h: the stair env's rows are the well levels)
     h->step.clear();         // the configuration is baked into the kernel arguments of the env step's list
     h->hcfg = c;
+    for (int k = 0; k < GO2SIM_WELLS_LEVELS_MAX; ++k) { h->well_xy.xy[2 * k] = f[GO2SIM_FC_ROW_CENTER0 + 3 * k]; h->well_xy.xy[2 * k + 1] = f[GO2SIM_FC_ROW_CENTER0 + 3 * k + 1]; }
   }
   const DCfg& c = h->hcfg;
   HIPCHK(hipSetDevice(h->device));
@@ -7237,6 +7287,7 @@ static void launch_reset_marked(go2sim* h, hipStream_t s) {
   if (h->hcfg.i[GO2SIM_IC_USE_TERRAIN]) hipLaunchKernelGGL(k_env_terrain_rows, dim3((h->B + 255) / 256), dim3(256), 0, s, h->P, h->dcfg, h->dglob, h->seed);
   if (h->hcfg.i[GO2SIM_IC_TILE_MODE]) hipLaunchKernelGGL(k_env_tile_spawn, dim3((h->B + 255) / 256), dim3(256), 0, s, h->P, h->dm, h->dcfg, h->dglob, h->seed);
   hipLaunchKernelGGL(k_env_reset_tail, g, b, 0, s, h->P, h->dm, h->dcfg, h->dglob, h->seed);
+  if (h->hcfg.i[GO2SIM_IC_WELL_SPAWN]) hipLaunchKernelGGL(k_env_well_spawn, dim3((h->B + 255) / 256), dim3(256), 0, s, h->P, h->dcfg, h->dglob, h->seed, h->well_xy);
   if (h->hcfg.i[GO2SIM_IC_ENGINE_BATCH_GAIN]) hipLaunchKernelGGL(k_env_engine_gains, dim3(1), dim3(GAIN_WG), 0, s, h->P, h->dm, h->dms, h->dcfg, h->dglob);
   launch_fk_team(h, s, 1, &h->dglob->n_reset_now);
 }

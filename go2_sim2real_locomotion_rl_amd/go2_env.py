@@ -31,6 +31,8 @@ from .model_blob import pack_model
 from .stairinfo import NUM_STAIR_INFO, StairInfo, check_one_exteroceptive_layout, check_stair_info_widths, env_rows_ptr, stair_info_enabled
 from .terrain_manager import TerrainManager
 from .terrain_tiles import install_terrain, is_tile_terrain_cfg
+from .terrain_wells import build_stairwell_terrain, is_well_terrain_cfg, well_centers
+from .wells import WellScan, check_well_widths, well_scan_shape
 
 _DEVICE = None
 _SEED = 1
@@ -79,7 +81,7 @@ def mirror_tables(env_cfg, obs_cfg):
     CPU tensors).  Joints and legs are ordered FR, FL, RR, RL: the mirror swaps FR <-> FL and RR <-> RL and hip angles change sign; polar vectors
     take (+, -, +), the angular velocity (-, +, -), the commands (vx, vy, wz) (+, -, -); scalars are fixed points; height-scan point
     ix * ny + iy maps to ix * ny + (ny - 1 - iy), and so does a point of either grid of the LIDAR layout (the actor scan closes the actor row and
-    follows the observations in the critic row, the critic scan closes the critic row).  The four columns of the stair-info layout (edge distance, riser
+    follows the observations in the critic row, the critic scan closes the critic row) and of the stairwell env's 11 x 11 scan.  The four columns of the stair-info layout (edge distance, riser
     height, tread depth, direction up / down along the forward axis) are fixed points with sign +1 in both rows."""
     num_actions, num_obs, num_priv = env_cfg["num_actions"], obs_cfg["num_obs"], obs_cfg.get("num_privileged_obs")
     base = is_base_env_cfg(env_cfg, obs_cfg)
@@ -132,8 +134,9 @@ def mirror_tables(env_cfg, obs_cfg):
             blocks += [scalar, four]
         elif extra > 0 and terrain.get("enabled", False):                   # the stair layout: terrain row, then the height scan
             hs = terrain.get("height_scan", {})
-            nx, ny = int(hs.get("num_x", 11)), int(hs.get("num_y", 7))
-            yr = hs.get("y_range", [-0.3, 0.3])
+            well = is_well_terrain_cfg(terrain)                             # the stairwell layout: well level, then the square scan (its defaults)
+            nx, ny = (well_scan_shape(terrain) if well else (int(hs.get("num_x", 11)), int(hs.get("num_y", 7))))
+            yr = hs.get("y_range", [-0.5, 0.5] if well else [-0.3, 0.3])
             if float(yr[0]) != -float(yr[1]):
                 raise Go2SimError(f"the height scan's y_range {list(yr)} is not symmetric about 0: the scan has no mirror")
             blocks += [scalar, ([ix * ny + (ny - 1 - iy) for ix in range(nx) for iy in range(ny)], [1.0] * (nx * ny))]
@@ -154,6 +157,11 @@ class Go2Env:
         if show_viewer:
             raise Go2SimError("the viewer is outside the accelerated path (SURVEY.md section 8f)")
         check_one_exteroceptive_layout(env_cfg)
+        use_wells = is_well_terrain_cfg(env_cfg.get("terrain")) and not is_base_env_cfg(env_cfg, obs_cfg)
+        if use_wells and (env_cfg.get("lidar") or env_cfg.get("stair_info")):
+            raise Go2SimError("the stairwell terrain has its own 11 x 11 scan: it does not combine with env_cfg['lidar'] or env_cfg['stair_info']")
+        if use_wells:
+            check_well_widths(env_cfg, obs_cfg)                             # (before anything touches the device)
         self.device = device if device is not None else (_DEVICE if _DEVICE is not None else init())
         self.num_envs = num_envs
         self.num_obs = obs_cfg["num_obs"]
@@ -176,6 +184,7 @@ class Go2Env:
         self.is_base_env = is_base_env_cfg(env_cfg, obs_cfg)
         self._lidar = None
         self._stairinfo = None
+        self._wells = None
         self.terrain = None                                                # the TerrainManager of the rough-terrain env
         if self.is_base_env:
             fcfg, icfg, self._reward_names = flatten_base_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg)
@@ -193,6 +202,11 @@ class Go2Env:
             elif lidar_enabled(env_cfg):
                 self._lidar_n_in = n_in = check_lidar_widths(env_cfg, obs_cfg)
                 inner_obs_cfg = dict(obs_cfg, num_obs=n_in, num_privileged_obs=n_in + C["GO2SIM_LIDAR_PRIV_EXTRA"])
+            elif use_wells:
+                # the stairwell layout (go2_env_stair6_Omni.py): the actor row is the step kernels' own, the privileged row is an inner row without a
+                # height scan, the wells launch writes the wider one and adds the alive term (include/go2sim_wells.h)
+                self._lidar_n_in = n_in = check_well_widths(env_cfg, obs_cfg)
+                inner_obs_cfg = dict(obs_cfg, num_obs=n_in, num_privileged_obs=n_in + C["GO2SIM_WELLS_PRIV_EXTRA"])
             fcfg, icfg, self._reward_names = flatten_walk_cfg(num_envs, env_cfg, inner_obs_cfg, reward_cfg, command_cfg,
                                                               freeze_curriculum=freeze_curriculum, shared_globals=shared_globals)
             layouts = {(16, 49): (None, 104, 182)}
@@ -216,6 +230,13 @@ class Go2Env:
                 install_terrain(self._sim, morph.height_field, morph.horizontal_scale, morph.vertical_scale, list(morph.pos))
                 self.terrain.post_build(morph)
                 self.terrain.bind(self)
+            elif use_wells:                                                       # go2_env_stair6_Omni.py:371-397: the grid of stairwells
+                hf, info = build_stairwell_terrain(terrain_cfg)
+                self._terrain_info = dict(info, row_centers=well_centers(info), num_difficulty_rows=info["num_difficulty_levels"])
+                self._sim.set_terrain(hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"])
+                self._wells = WellScan(terrain_cfg, num_envs, hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"],
+                                       n_levels=info["num_difficulty_levels"], alive_scale=float(self.reward_scales.get("alive", 0.0)), dt=self.dt,
+                                       device=self.device)
             elif terrain_cfg is not None and terrain_cfg.get("enabled", False):   # go2_env_stair.py:352-433: gs.morphs.Terrain instead of the plane
                 hf, info = build_stair_terrain(terrain_cfg)
                 self._terrain_info = info
@@ -243,6 +264,12 @@ class Go2Env:
             self._lidar_level = self._sim.env_globals_ptr() + EnvGlobals.level.offset
         if self._stairinfo is not None:
             self._stairinfo_rows = env_rows_ptr(self._sim)                 # the env's terrain rows, read on the device at step time
+        if self._wells is not None:
+            self._inner_priv = torch.zeros(B, self._lidar_n_in + C["GO2SIM_WELLS_PRIV_EXTRA"], device=dev)
+            self._lidar_pose = env_pose_ptrs(self._sim)
+            self._alive_ep = _as_device_tensor(self._wells.alive_ep_ptr, (B,), torch.float32, dev)   # per-env record of the last finished episode's alive term
+            self._alive_log = torch.zeros((), device=dev)
+            self._has_alive = "alive" in self.reward_scales
         self.obs_buf = torch.zeros(B, self.num_obs, device=dev)
         self.privileged_obs_buf = torch.zeros(B, 45 if self.is_base_env else (self.num_privileged_obs or self.num_obs + 55), device=dev)
         self.rew_buf = torch.zeros(B, device=dev)
@@ -292,6 +319,13 @@ class Go2Env:
             pos, quat, cs = self._lidar_pose
             self._stairinfo.step(pos, (cs, 1), quat, (cs, 1), self._stairinfo_rows, self.reset_buf, self._lidar_level, self._inner_obs, self._inner_priv,
                                  self._lidar_n_in, self.obs_buf, self.privileged_obs_buf)
+        elif self._wells is not None:                                      # one more launch: the 11 x 11 scan into the wider privileged row, and the alive term
+            self._sim.env_step(a, self.obs_buf, self._inner_priv, self.rew_buf, self.reset_buf, self._time_outs, stream)
+            pos, quat, cs = self._lidar_pose
+            self._wells.step(pos, (cs, 1), quat, (cs, 1), self.reset_buf, self._inner_priv, self._lidar_n_in, self.privileged_obs_buf,
+                             self.rew_buf if self._has_alive else None)
+            if self.log_extras and self._has_alive:
+                self._log_alive(self.reset_buf)
         elif self._lidar is None:
             self._sim.env_step(a, self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self._time_outs, stream)
         else:                                                              # one more launch: the scans and the wider rows, straight into the fresh tensors
@@ -318,6 +352,8 @@ class Go2Env:
         snap = self._glob_f32.clone()
         n = len(self._reward_names)
         self.extras["episode"] = dict(zip(self._episode_keys, snap[self._ep_off:self._ep_off + n].unbind(0)))
+        if self._wells is not None and self._has_alive:
+            self.extras["episode"]["rew_alive"] = self._alive_log
         if self._use_terrain:
             rows = snap.view(torch.int32)
             self.extras["episode"]["terrain_mean_row"] = rows[self._goff["terrain_row_sum"]].float() / rows[self._goff["last_reset_count"]].clamp(min=1).float()
@@ -339,6 +375,13 @@ class Go2Env:
         self.extras["domain_randomization"] = {"friction": f[g["friction"]], "mass_shift": f[g["mass_shift"]],
                                                "com_shift": f[g["com_shift"]:g["com_shift"] + 3],
                                                "leg_mass_shift": f[g["leg_mass_shift"]:g["leg_mass_shift"] + 4]}
+
+    def _log_alive(self, mask):
+        """extras["episode"]["rew_alive"] as the core reports its terms: the mean, over the envs of the last reset, of episode sum / episode seconds
+        (the wells launch left each env's value in alive_ep); kept while no env is reset.  Device arithmetic on [n_envs] values, no synchronisation."""
+        m = mask.to(torch.float32)
+        n = m.sum()
+        self._alive_log = torch.where(n > 0, (self._alive_ep * m).sum() / n.clamp(min=1.0), self._alive_log)
 
     def _dr_level_of(self, level):
         """_get_dr_level (go2_env_stair_lidar_2.py) of the curriculum level, a 0-dim float64 device tensor: no synchronisation."""
@@ -382,6 +425,10 @@ class Go2Env:
         if self._stairinfo is not None:
             self._stairinfo.clear()
         self.reset_buf.fill_(1)
+        if self._wells is not None:
+            self._wells.clear()
+            if self.log_extras and self._has_alive:
+                self._log_alive(self.reset_buf)
         if self.log_extras:
             self._refresh_extras()
         return self.obs_buf, None
@@ -397,6 +444,12 @@ class Go2Env:
         if self._stairinfo is not None:
             self._stairinfo.clear(idx)
         self.reset_buf[idx.long()] = 1
+        if self._wells is not None:
+            self._wells.clear(idx)
+            if self.log_extras and self._has_alive:
+                sel = torch.zeros(self.num_envs, device=self.device)
+                sel[idx.long()] = 1.0
+                self._log_alive(sel)
         if self.log_extras:
             self._refresh_extras()
 
@@ -427,6 +480,8 @@ class Go2Env:
             self._lidar.clear(idx)
         if self._stairinfo is not None and clear_buffers and idx.numel():
             self._stairinfo.clear(idx)
+        if self._wells is not None and clear_buffers and idx.numel():
+            self._wells.clear(idx)
 
     def respawn_at_start(self, envs_idx=(0,)):
         """go2_eval_stairs.py:314-361: back to the spawn point of the env's terrain row (or base_init_pos on flat ground)."""

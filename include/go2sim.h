@@ -230,6 +230,10 @@ enum go2sim_icfg {
      termination and a random spawn tile per reset.  Independent of GO2SIM_IC_USE_TERRAIN (the stair env's rows, scan and foot terms stay off);
      the heightfield itself is installed with go2sim_set_terrain / go2sim_set_terrain_f32.  A 1 x 1 grid is the heightmap mode. */
   GO2SIM_IC_TILE_MODE, GO2SIM_IC_TILE_N_ROWS, GO2SIM_IC_TILE_N_COLS,
+  /* stairwell env (include/go2sim_wells.h): with GO2SIM_IC_USE_TERRAIN, the row-centre table holds well centres (x, y, bottom_z), the terrain
+     row is the well level, and every reset env gets a uniform offset of +-0.3 m in x and in y and, with init_euler_range, a yaw from that range
+     (k_env_well_spawn, Philox purpose 15).  Refused together with GO2SIM_IC_TILE_MODE or without GO2SIM_IC_USE_TERRAIN. */
+  GO2SIM_IC_WELL_SPAWN,
   GO2SIM_IC_COUNT
 };
 /* reward terms of go2_env_walk.py:1251-1366 */

@@ -6,6 +6,7 @@
     python tools/train.py --task walk --envs 4096 --iterations 1000 --empirical-normalization           # running observation statistics in front of the policy
     python tools/train.py --task stairs_lidar --envs 4096 --iterations 1000                             # the stair env with the actor's LIDAR terrain scan (64 / 165 inputs)
     python tools/train.py --task stairs_info --envs 4096 --iterations 1000                              # the stair env with the four-value stair info (53 / 113 inputs)
+    python tools/train.py --task stairwell --envs 4096 --iterations 1000                                # the omnidirectional stair env on the grid of stairwells (49 / 226 inputs)
     python tools/train.py --task rough --terrain-mode grid --envs 4096 --iterations 1000                # the walk env on rough ground (heightmap or tile grid)
     python tools/train.py --task stairs_lidar --envs 4096 --iterations 1000 --actor-obs critic --log-dir logs/teacher   # a teacher: the actor reads the privileged rows
     python tools/train.py --task stairs_lidar --envs 4096 --iterations 500 --distill logs/teacher/model_1000.pt --teacher-obs critic   # distil it into a student
@@ -28,16 +29,16 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-TASKS = ("walk", "stairs", "stairs_lidar", "stairs_info", "rough", "crouch", "jump")
+TASKS = ("walk", "stairs", "stairs_lidar", "stairs_info", "stairwell", "rough", "crouch", "jump")
 
 
 def task_cfgs(task, terrain_mode="heightmap", terrain_seed=0):
     from go2_sim2real_locomotion_rl_amd import (get_crouch_cfgs, get_jump_cfgs, get_rough_cfgs, get_stair_cfgs, get_stair_info_cfgs, get_stair_lidar_cfgs,
-                                                get_walk_cfgs)
+                                                get_stairwell_cfgs, get_walk_cfgs)
 
     if task == "rough":                                        # go2_train_Omni_kplearn_varied_terrain.py: the walk env on a heightmap or a tile grid
         return get_rough_cfgs(terrain_mode, seed=terrain_seed)
-    return {"walk": get_walk_cfgs, "stairs": get_stair_cfgs, "stairs_lidar": get_stair_lidar_cfgs, "stairs_info": get_stair_info_cfgs, "crouch": get_crouch_cfgs, "jump": get_jump_cfgs}[task]()
+    return {"walk": get_walk_cfgs, "stairs": get_stair_cfgs, "stairs_lidar": get_stair_lidar_cfgs, "stairs_info": get_stair_info_cfgs, "stairwell": get_stairwell_cfgs, "crouch": get_crouch_cfgs, "jump": get_jump_cfgs}[task]()
 
 
 def train_cfg_of(task, cfgs_path=None):
