@@ -69,6 +69,7 @@ ACT_HEADER, DECLARED_ACT_FUNCS = _product_header("activation")                 #
 RND_HEADER, DECLARED_RND_FUNCS = _product_header("rnd")                        # random network distillation: the intrinsic reward and the predictor's update
 TILES_HEADER, DECLARED_TILES_FUNCS = _product_header("tiles")                  # the rough-terrain walk env: float heightfield, ground query
 WELLS_HEADER, DECLARED_WELLS_FUNCS = _product_header("wells")                  # the stairwell env: 11 x 11 scan, alive term
+RNG_HEADER, _ = _product_header("rng", [])                                     # the purposes of the random stream (constants only; both libraries)
 # train_cfg["policy"]["activation"] as rsl_rl's resolve_nn_activation spells it -> GO2SIM_ACT_*
 ACTIVATIONS = {n: C["GO2SIM_ACT_" + n.upper()] for n in ("elu", "selu", "relu", "lrelu", "tanh", "sigmoid", "identity")}
 

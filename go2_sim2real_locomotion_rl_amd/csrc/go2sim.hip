@@ -31,6 +31,7 @@
 #include "../../include/go2sim.h"
 #include "../../include/go2sim_detmath.h"
 #include "../../include/go2sim_lidar.h"
+#include "../../include/go2sim_rng.h"
 #include "../../include/go2sim_stairinfo.h"
 #include "../../include/go2sim_tiles.h"
 #include "go2sim_tiles_dev.h"
@@ -4766,7 +4767,6 @@ struct DCfg { double d[GO2SIM_FC_N_HOST]; float f[GO2SIM_FC_COUNT]; int i[GO2SIM
 struct Acc { double timeouts, tracking, ep[NREW]; int n_reset_now; int done; };   // done: workgroups of k_env_post_a that have finished
 typedef go2sim_env_globals_t Glob;
 
-enum { RNG_ACTION_NOISE = 1, RNG_PUSH = 2, RNG_CMD = 3, RNG_OBS_NOISE = 4, RNG_RESET_DR = 5, RNG_GLOBAL_DR = 6, RNG_RESET_CMD = 7, RNG_RESET_POSE = 8, RNG_TERRAIN_ROW = 9, RNG_TERRAIN_PERM = 10, RNG_RESET_KPKD = 11 };
 __host__ __device__ inline dm_u4 rng4(uint64_t seed, uint32_t purpose, uint32_t env, uint32_t step, uint32_t idx) {
 #ifdef GO2SIM_RNG_CONST   // diagnostic build (include/go2sim_detmath.h): every word of a draw is its stream key
   dm_u4 o; o.v[0] = o.v[1] = o.v[2] = o.v[3] = step; (void)purpose; (void)env; (void)idx; (void)seed; return o;
@@ -4979,7 +4979,7 @@ __global__ __launch_bounds__(WG) void k_env_pre(Pool P, const Model* __restrict_
   if (g.action_noise_std_cur > 0.0) {
 #pragma unroll
     for (int blk = 0; blk < 3; ++blk) {
-      dm_u4 r = rng4(seed, RNG_ACTION_NOISE, b, step_count, blk);
+      dm_u4 r = rng4(seed, GO2SIM_RNG_ACTION_NOISE, b, step_count, blk);
       float n0, n1, n2, n3;
       dm_normal2(r.v[0], r.v[1], &n0, &n1); dm_normal2(r.v[2], r.v[3], &n2, &n3);
       target[4 * blk + 0] = target[4 * blk + 0] + n0 * (float)g.action_noise_std_cur;
@@ -5024,7 +5024,7 @@ __global__ __launch_bounds__(WG) void k_env_pre(Pool P, const Model* __restrict_
     cpf[0] = 0.0f; cpf[1] = 0.0f; cpf[2] = 0.0f;
   } else {
     if (g.push_counter % g.push_interval == 0) {
-      dm_u4 r = rng4(seed, RNG_PUSH, b, step_count, 0);
+      dm_u4 r = rng4(seed, GO2SIM_RNG_PUSH, b, step_count, 0);
       psf_[0] = rand_float(g.push_force_lo, g.push_force_hi, r.v[0]);
       psf_[1] = rand_float(g.push_force_lo, g.push_force_hi, r.v[1]);
       psf_[2] = 0.0f;
@@ -5126,7 +5126,7 @@ __global__ __launch_bounds__(64) void k_pre_dynamics_team(Pool P, const ModelS* 
     if (tl < NM) {
       float target = delayed * c.f[GO2SIM_FC_ACTION_SCALE] + c.f[GO2SIM_FC_DEFAULT_DOF_POS0 + tl];
       if (g.action_noise_std_cur > 0.0) {
-        dm_u4 r = rng4(seed, RNG_ACTION_NOISE, b, step_count, tl / 4);
+        dm_u4 r = rng4(seed, GO2SIM_RNG_ACTION_NOISE, b, step_count, tl / 4);
         float n0, n1;
         if ((tl & 2) == 0) dm_normal2(r.v[0], r.v[1], &n0, &n1); else dm_normal2(r.v[2], r.v[3], &n0, &n1);
         target = target + ((tl & 1) ? n1 : n0) * (float)g.action_noise_std_cur;
@@ -5162,7 +5162,7 @@ __global__ __launch_bounds__(64) void k_pre_dynamics_team(Pool P, const ModelS* 
         cpf[0] = 0.0f; cpf[1] = 0.0f; cpf[2] = 0.0f;
       } else {
         if (g.push_counter % g.push_interval == 0) {
-          dm_u4 r = rng4(seed, RNG_PUSH, b, step_count, 0);
+          dm_u4 r = rng4(seed, GO2SIM_RNG_PUSH, b, step_count, 0);
           psf_[0] = rand_float(g.push_force_lo, g.push_force_hi, r.v[0]);
           psf_[1] = rand_float(g.push_force_lo, g.push_force_hi, r.v[1]);
           psf_[2] = 0.0f;
@@ -5584,7 +5584,7 @@ __global__ __launch_bounds__(WG * POST_A_NWAVES) void k_env_post_a(Pool P, const
   }
   if (ep_len % c.i[GO2SIM_IC_RESAMPLE_STEPS] == 0) {
     auto cmd = e.commands();
-    dm_u4 r = rng4(seed, RNG_CMD, b, step_count, 0);
+    dm_u4 r = rng4(seed, GO2SIM_RNG_CMD, b, step_count, 0);
     float cx, cy, cz;
     sample_commands(c, g, r, b, cx, cy, cz);
     if (w0) { cmd[0] = cx; cmd[1] = cy; cmd[2] = cz; }
@@ -5794,9 +5794,9 @@ __host__ __device__ inline void globals_curriculum_check(const DCfg& c, Glob& g)
 // t_sample (CurriculumManager.sample_level :85-93) and the "global" DR draws (:737-756, 803-848) of one reset call; `n_throttle` resets are counted
 // for the friction throttle, `key` numbers the call in the Philox stream
 __host__ __device__ inline void globals_draws(const DCfg& c, Glob& g, uint64_t seed, int n_throttle, uint32_t key) {
-  dm_u4 r0 = rng4(seed, RNG_GLOBAL_DR, 0xffffffffu, key, 0);
-  dm_u4 r1 = rng4(seed, RNG_GLOBAL_DR, 0xffffffffu, key, 1);
-  dm_u4 r2 = rng4(seed, RNG_GLOBAL_DR, 0xffffffffu, key, 2);
+  dm_u4 r0 = rng4(seed, GO2SIM_RNG_GLOBAL_DR, 0xffffffffu, key, 0);
+  dm_u4 r1 = rng4(seed, GO2SIM_RNG_GLOBAL_DR, 0xffffffffu, key, 1);
+  dm_u4 r2 = rng4(seed, GO2SIM_RNG_GLOBAL_DR, 0xffffffffu, key, 2);
   double t;
   if (c.i[GO2SIM_IC_DR_SCHEDULE]) t = dr_level(c, c.i[GO2SIM_IC_CURR_ENABLED] ? g.level : 1.0);   // go2_env_stair.py:1506-1507
   else if (!c.i[GO2SIM_IC_CURR_ENABLED]) t = 1.0;
@@ -5897,7 +5897,7 @@ DEV ResetDraws env_reset_draws_team(const DCfg& c, const Glob& g, const E& e, in
   const uint32_t rc = g.reset_calls - 1;
   const double ts = g.t_sample;
   const int k = tl < 13 ? tl : 12;
-  const uint32_t purpose = k < 11 ? RNG_RESET_DR : (k == 11 ? RNG_RESET_POSE : RNG_RESET_CMD);
+  const uint32_t purpose = k < 11 ? GO2SIM_RNG_RESET_DR : (k == 11 ? GO2SIM_RNG_RESET_POSE : GO2SIM_RNG_RESET_CMD);
   const dm_u4 r = rng4(seed, purpose, b, rc, k < 11 ? k : 0);
   // the per-env DR blocks: kp factors 0..2, kd factors 3..5, gravity offset 6 (three values), motor strength 7..9
   const int has = k < 3 ? GO2SIM_IC_HAS_KPF_DR : (k < 6 ? GO2SIM_IC_HAS_KDF_DR : (k == 6 ? GO2SIM_IC_HAS_GOFF_DR : GO2SIM_IC_HAS_MSTR_DR));
@@ -5923,23 +5923,23 @@ DEV void env_reset_one(const Model& m, const DCfg& c, const Glob& g, const E& e,
   auto kp_factors = e.kp_factors(); auto kd_factors = e.kd_factors(); auto motor_strength = e.motor_strength(); auto gravity_offset = e.gravity_offset();
   if (!pre) {
   if (c.i[GO2SIM_IC_HAS_KPF_DR])
-    for (int blk = 0; blk < 3; ++blk) { dm_u4 r = rng4(seed, RNG_RESET_DR, b, rc, blk); for (int k = 0; k < 4; ++k) kp_factors[4 * blk + k] = rand_float(lerp_lo(c, GO2SIM_FC_KPF_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_KPF_EASY_LO, ts), r.v[k]); }
+    for (int blk = 0; blk < 3; ++blk) { dm_u4 r = rng4(seed, GO2SIM_RNG_RESET_DR, b, rc, blk); for (int k = 0; k < 4; ++k) kp_factors[4 * blk + k] = rand_float(lerp_lo(c, GO2SIM_FC_KPF_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_KPF_EASY_LO, ts), r.v[k]); }
   if (c.i[GO2SIM_IC_HAS_KDF_DR])
-    for (int blk = 0; blk < 3; ++blk) { dm_u4 r = rng4(seed, RNG_RESET_DR, b, rc, 3 + blk); for (int k = 0; k < 4; ++k) kd_factors[4 * blk + k] = rand_float(lerp_lo(c, GO2SIM_FC_KDF_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_KDF_EASY_LO, ts), r.v[k]); }
+    for (int blk = 0; blk < 3; ++blk) { dm_u4 r = rng4(seed, GO2SIM_RNG_RESET_DR, b, rc, 3 + blk); for (int k = 0; k < 4; ++k) kd_factors[4 * blk + k] = rand_float(lerp_lo(c, GO2SIM_FC_KDF_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_KDF_EASY_LO, ts), r.v[k]); }
   if (c.i[GO2SIM_IC_HAS_GOFF_DR]) {
-    dm_u4 r = rng4(seed, RNG_RESET_DR, b, rc, 6);
+    dm_u4 r = rng4(seed, GO2SIM_RNG_RESET_DR, b, rc, 6);
     for (int k = 0; k < 3; ++k) gravity_offset[k] = rand_float(lerp_lo(c, GO2SIM_FC_GOFF_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_GOFF_EASY_LO, ts), r.v[k]);
   }
   if (c.i[GO2SIM_IC_HAS_MSTR_DR])
-    for (int blk = 0; blk < 3; ++blk) { dm_u4 r = rng4(seed, RNG_RESET_DR, b, rc, 7 + blk); for (int k = 0; k < 4; ++k) motor_strength[4 * blk + k] = rand_float(lerp_lo(c, GO2SIM_FC_MSTR_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_MSTR_EASY_LO, ts), r.v[k]); }
+    for (int blk = 0; blk < 3; ++blk) { dm_u4 r = rng4(seed, GO2SIM_RNG_RESET_DR, b, rc, 7 + blk); for (int k = 0; k < 4; ++k) motor_strength[4 * blk + k] = rand_float(lerp_lo(c, GO2SIM_FC_MSTR_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_MSTR_EASY_LO, ts), r.v[k]); }
   }
   if (!c.i[GO2SIM_IC_PLS_ENABLE] && c.i[GO2SIM_IC_HAS_KP_RANGE]) {   // _randomize_kp_kd with PLS off (go2_env_walk.py:776-781): kp_val, then kd_val, one per env;
-    dm_u4 r = rng4(seed, RNG_RESET_KPKD, b, rc, 0);                   // a stream of its own, so that no draw of a PLS-on configuration moves
+    dm_u4 r = rng4(seed, GO2SIM_RNG_RESET_KPKD, b, rc, 0);                   // a stream of its own, so that no draw of a PLS-on configuration moves
     e.base_kp()[0] = rand_float(lerp_lo(c, GO2SIM_FC_KPR_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_KPR_EASY_LO, ts), r.v[0]);
     e.base_kd()[0] = rand_float(lerp_lo(c, GO2SIM_FC_KDR_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_KDR_EASY_LO, ts), r.v[1]);
   }
   if (c.i[GO2SIM_IC_PER_ENV_GLOBAL_DR]) {   // extension (BASELINE configs[4], not in the reference): the friction / base-mass scalars are drawn per env
-    dm_u4 r = pre ? pre->per_env : rng4(seed, RNG_RESET_DR, b, rc, 10);
+    dm_u4 r = pre ? pre->per_env : rng4(seed, GO2SIM_RNG_RESET_DR, b, rc, 10);
     if (c.i[GO2SIM_IC_HAS_FRICTION_DR]) {
       float mu = rand_float(lerp_lo(c, GO2SIM_FC_FRICTION_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_FRICTION_EASY_LO, ts), r.v[0]);
       auto gf = e.geom_friction();
@@ -5948,7 +5948,7 @@ DEV void env_reset_one(const Model& m, const DCfg& c, const Glob& g, const E& e,
     if (c.i[GO2SIM_IC_HAS_MASS_DR])
       e.mass_shift()[c.i[GO2SIM_IC_BASE_LINK]] = rand_float(lerp_lo(c, GO2SIM_FC_MASS_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_MASS_EASY_LO, ts), r.v[1]);
   }
-  dm_u4 rp = pre ? pre->pose : rng4(seed, RNG_RESET_POSE, b, rc, 0);
+  dm_u4 rp = pre ? pre->pose : rng4(seed, GO2SIM_RNG_RESET_POSE, b, rc, 0);
   {
     int max_d = imx(c.i[GO2SIM_IC_MIN_DELAY], imn(g.delay_max_cur, c.i[GO2SIM_IC_MAX_DELAY]));
     e.delay_steps()[0] = rand_int(c.i[GO2SIM_IC_MIN_DELAY], max_d, rp.v[3]);
@@ -6003,7 +6003,7 @@ DEV void env_reset_one(const Model& m, const DCfg& c, const Glob& g, const E& e,
   { auto fat = e.feet_air_time(); auto fc = e.foot_contact(); auto lfc = e.last_foot_contact(); for (int i = 0; i < 4; ++i) { fat[i] = 0.0f; fc[i] = 0; lfc[i] = 0; } }
   { auto es = e.episode_sums(); for (int k = 0; k < NREW; ++k) es[k] = 0.0f; }
   e.episode_length()[0] = 0; e.reset_buf()[0] = 1;
-  dm_u4 r = pre ? pre->cmd : rng4(seed, RNG_RESET_CMD, b, rc, 0);
+  dm_u4 r = pre ? pre->cmd : rng4(seed, GO2SIM_RNG_RESET_CMD, b, rc, 0);
   float cx, cy, cz;
   sample_commands(c, g, r, b, cx, cy, cz);
   auto cmd = e.commands();
@@ -6044,15 +6044,15 @@ __global__ __launch_bounds__(256) void k_env_terrain_rows(Pool P, const DCfg* __
     int max_row = (int)(level * (double)(n_rows - 1));
     max_row = imx(0, imn(max_row, n_rows - 1));
     int n_frontier = (int)((double)n * 0.40), n_near = (int)((double)n * 0.30);
-    const unsigned kj = rng4(seed, RNG_TERRAIN_PERM, b, rc, 0).v[0];
+    const unsigned kj = rng4(seed, GO2SIM_RNG_TERRAIN_PERM, b, rc, 0).v[0];
     int p = 0;
     const int* rb = P.i + (size_t)IO(reset_buf) * P.B;
     for (int b2 = 0; b2 < P.B; ++b2) {
       if (!rb[b2] || b2 == b) continue;
-      unsigned k2 = rng4(seed, RNG_TERRAIN_PERM, b2, rc, 0).v[0];
+      unsigned k2 = rng4(seed, GO2SIM_RNG_TERRAIN_PERM, b2, rc, 0).v[0];
       p += (k2 < kj) || (k2 == kj && b2 < b);
     }
-    dm_u4 r = rng4(seed, RNG_TERRAIN_ROW, (uint32_t)p, rc, 0);
+    dm_u4 r = rng4(seed, GO2SIM_RNG_TERRAIN_ROW, (uint32_t)p, rc, 0);
     if (p < n_frontier) row = max_row;
     else if (p < n_frontier + n_near) row = (max_row >= 2) ? rand_int(imx(0, max_row - 2), imx(0, max_row - 1), r.v[0]) : max_row;
     else row = rand_int(0, (max_row >= 3) ? max_row - 3 : 0, r.v[1]);
@@ -6108,7 +6108,7 @@ __global__ __launch_bounds__(256) void k_env_well_spawn(Pool P, const DCfg* __re
   e.last_base_pos_x()[0] = x;
   float yaw = 0.0f;
   if (c.i[GO2SIM_IC_HAS_INIT_EULER]) {                                 // euler_to_quat_wxyz with the reset's roll and pitch and this yaw
-    const dm_u4 rp = rng4(seed, RNG_RESET_POSE, (uint32_t)b, rc, 0);
+    const dm_u4 rp = rng4(seed, GO2SIM_RNG_RESET_POSE, (uint32_t)b, rc, 0);
     const double D2R = 3.141592653589793 / 180.0;
     const double lo = c.d[GO2SIM_FC_INIT_EULER_LO_DEG] * D2R, hi = c.d[GO2SIM_FC_INIT_EULER_HI_DEG] * D2R;
     const float roll = rand_float(lo, hi, rp.v[1]), pitch = rand_float(lo, hi, rp.v[2]);
@@ -6335,7 +6335,7 @@ __global__ __launch_bounds__(128) void k_env_post_b_team(Pool P, const Model* __
   const bool per_env_dr = c.i[GO2SIM_IC_PER_ENV_GLOBAL_DR] != 0;
   float n0[4] = {0.0f, 0.0f, 0.0f, 0.0f};              // the draws of block `tl` (the only block of this lane unless nobs > 4 T)
   if (noisy && tl * 4 < nobs) {
-    dm_u4 r = rng4(seed, RNG_OBS_NOISE, b, step_count, tl);
+    dm_u4 r = rng4(seed, GO2SIM_RNG_OBS_NOISE, b, step_count, tl);
     dm_normal2(r.v[0], r.v[1], &n0[0], &n0[1]); dm_normal2(r.v[2], r.v[3], &n0[2], &n0[3]);
   }
 #pragma unroll
@@ -6347,7 +6347,7 @@ __global__ __launch_bounds__(128) void k_env_post_b_team(Pool P, const Model* __
   for (int blk = tl; blk * 4 < nobs; blk += T) {
     float n[4] = {n0[0], n0[1], n0[2], n0[3]};
     if (noisy && blk != tl) {
-      dm_u4 r = rng4(seed, RNG_OBS_NOISE, b, step_count, blk);
+      dm_u4 r = rng4(seed, GO2SIM_RNG_OBS_NOISE, b, step_count, blk);
       dm_normal2(r.v[0], r.v[1], &n[0], &n[1]); dm_normal2(r.v[2], r.v[3], &n[2], &n[3]);
     }
 #pragma unroll

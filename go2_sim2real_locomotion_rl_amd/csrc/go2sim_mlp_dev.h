@@ -11,6 +11,7 @@
 #include "../../include/go2sim_activation.h"
 #include "../../include/go2sim_detmath.h"
 #include "../../include/go2sim_policy.h"
+#include "../../include/go2sim_rng.h"   // GO2SIM_RNG_POLICY_NOISE: the env holds purposes 1..10 and 16, the sensors 12..15
 
 #ifndef MLP_KU
 #define MLP_KU 1
@@ -182,8 +183,6 @@ __device__ __forceinline__ void mlp_layer(const MlpDev& M, int l, const float (*
 // The two kernels of a policy step, for the sources that act (go2sim_policy.hip, go2sim_distill.hip, go2sim_rdistill.hip): they define GO2SIM_MLP_ACT_KERNELS before the include, so
 // that a source that only trains does not carry a copy.
 #ifdef GO2SIM_MLP_ACT_KERNELS
-constexpr uint32_t RNG_POLICY_NOISE = 11;   // purposes 1..10 belong to the environment (csrc/go2sim.hip)
-
 // blockIdx.y selects the network: actor and critic of one policy step (student and teacher of one distillation step) share a launch (2 x 128
 // workgroups of 32 rows at 4096 rows, one per CU)
 __global__ __launch_bounds__(64 * NWAVE) void k_mlp_forward(MlpDev M0, const float* __restrict__ x0, float* __restrict__ y0,
@@ -222,7 +221,7 @@ __global__ __launch_bounds__(64) void k_policy_sample(const float* __restrict__ 
   for (int blk = 0; 4 * blk < A; ++blk) {
     float n[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (!deterministic) {
-      dm_u4 r = dm_philox((uint32_t)b, step, RNG_POLICY_NOISE, (uint32_t)blk, (uint32_t)seed, (uint32_t)(seed >> 32));
+      dm_u4 r = dm_philox((uint32_t)b, step, GO2SIM_RNG_POLICY_NOISE, (uint32_t)blk, (uint32_t)seed, (uint32_t)(seed >> 32));
       dm_normal2(r.v[0], r.v[1], &n[0], &n[1]); dm_normal2(r.v[2], r.v[3], &n[2], &n[3]);
     }
     for (int k = 0; k < 4; ++k) {

@@ -25,6 +25,7 @@
 
 #include "../include/go2sim.h"
 #include "../include/go2sim_detmath.h"
+#include "../include/go2sim_rng.h"
 #include "gjk_epa_cpu.h"
 
 namespace {
@@ -2097,7 +2098,6 @@ inline dm_u4 rng4(const go2sim* h, uint32_t purpose, uint32_t env, uint32_t step
   return dm_philox(env, step, purpose, idx, (uint32_t)h->seed, (uint32_t)(h->seed >> 32));
 #endif
 }
-enum { RNG_ACTION_NOISE = 1, RNG_PUSH = 2, RNG_CMD = 3, RNG_OBS_NOISE = 4, RNG_RESET_DR = 5, RNG_GLOBAL_DR = 6, RNG_RESET_CMD = 7, RNG_RESET_POSE = 8, RNG_TERRAIN_ROW = 9, RNG_TERRAIN_PERM = 10 };
 // gs_rand_float, go2_env_walk.py:7-8: `(upper - lower) * torch.rand(...) + lower` with python-float bounds: the difference is formed in float64 and
 // both scalars are rounded to float32 where they meet the float32 tensor
 inline real rand_float(double lower, double upper, uint32_t r) { return (real)(upper - lower) * dm_u01(r) + (real)lower; }
@@ -2225,7 +2225,7 @@ void env_pre(go2sim* h, int b, const real* actions) {
   for (int i = 0; i < NM; ++i) target[i] = delayed[i] * c.f[GO2SIM_FC_ACTION_SCALE] + c.f[GO2SIM_FC_DEFAULT_DOF_POS0 + i];
   if (g.action_noise_std_cur > 0.0) {                                                  // randn_like(target) * python float: the scalar meets the tensor as float32
     for (int blk = 0; blk < 3; ++blk) {
-      dm_u4 r = rng4(h, RNG_ACTION_NOISE, b, g.step_count, blk);
+      dm_u4 r = rng4(h, GO2SIM_RNG_ACTION_NOISE, b, g.step_count, blk);
       real n0, n1, n2, n3;
       dm_normal2(r.v[0], r.v[1], &n0, &n1); dm_normal2(r.v[2], r.v[3], &n2, &n3);
       real nn[4] = {n0, n1, n2, n3};
@@ -2269,7 +2269,7 @@ void env_pre(go2sim* h, int b, const real* actions) {
     x.current_push_force[0] = x.current_push_force[1] = x.current_push_force[2] = 0.0f;
   } else {
     if (g.push_counter % g.push_interval == 0) {
-      dm_u4 r = rng4(h, RNG_PUSH, b, g.step_count, 0);
+      dm_u4 r = rng4(h, GO2SIM_RNG_PUSH, b, g.step_count, 0);
       x.push_stored_force[0] = rand_float(g.push_force_lo, g.push_force_hi, r.v[0]);
       x.push_stored_force[1] = rand_float(g.push_force_lo, g.push_force_hi, r.v[1]);
       x.push_stored_force[2] = 0.0f;
@@ -2426,7 +2426,7 @@ void env_post_a(go2sim* h, int b) {
     link_vel_xy[2 * i] = lv.x; link_vel_xy[2 * i + 1] = lv.y; foot_z[i] = e.l_pos[l].z; foot_xy[2 * i] = e.l_pos[l].x; foot_xy[2 * i + 1] = e.l_pos[l].y;
   }
   if (x.episode_length % c.i[GO2SIM_IC_RESAMPLE_STEPS] == 0) {                          // _resample_commands :927-963
-    dm_u4 r = rng4(h, RNG_CMD, b, g.step_count, 0);
+    dm_u4 r = rng4(h, GO2SIM_RNG_CMD, b, g.step_count, 0);
     sample_commands(c, g, r, b, x.commands);
   }
   int maxlen = c.i[GO2SIM_IC_MAX_EPISODE_LENGTH];
@@ -2478,9 +2478,9 @@ void globals_curriculum_check(go2sim* h) {
 // for the friction throttle, `key` numbers the call in the Philox stream
 void globals_draws(go2sim* h, int n_throttle, uint32_t key) {
   const Cfg& c = h->cfg; go2sim_env_globals_t& g = h->g;
-  dm_u4 r0 = rng4(h, RNG_GLOBAL_DR, 0xffffffffu, key, 0);
-  dm_u4 r1 = rng4(h, RNG_GLOBAL_DR, 0xffffffffu, key, 1);
-  dm_u4 r2 = rng4(h, RNG_GLOBAL_DR, 0xffffffffu, key, 2);
+  dm_u4 r0 = rng4(h, GO2SIM_RNG_GLOBAL_DR, 0xffffffffu, key, 0);
+  dm_u4 r1 = rng4(h, GO2SIM_RNG_GLOBAL_DR, 0xffffffffu, key, 1);
+  dm_u4 r2 = rng4(h, GO2SIM_RNG_GLOBAL_DR, 0xffffffffu, key, 2);
   double t;                                                                             // CurriculumManager.sample_level :85-93
   if (c.i[GO2SIM_IC_DR_SCHEDULE]) t = dr_level(c, c.i[GO2SIM_IC_CURR_ENABLED] ? g.level : 1.0);   // go2_env_stair.py:1506-1507
   else if (!c.i[GO2SIM_IC_CURR_ENABLED]) t = 1.0;
@@ -2539,17 +2539,17 @@ void env_reset_one(go2sim* h, int b) {
   uint32_t rc = g.reset_calls - 1;  // id of the current reset call (already advanced by env_globals_update)
   double ts = g.t_sample;
   if (c.i[GO2SIM_IC_HAS_KPF_DR])                                                          // _randomize_kp_kd (PLS branch) :763-773
-    for (int blk = 0; blk < 3; ++blk) { dm_u4 r = rng4(h, RNG_RESET_DR, b, rc, blk); for (int k = 0; k < 4; ++k) x.kp_factors[4 * blk + k] = rand_float(lerp_lo(c, GO2SIM_FC_KPF_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_KPF_EASY_LO, ts), r.v[k]); }
+    for (int blk = 0; blk < 3; ++blk) { dm_u4 r = rng4(h, GO2SIM_RNG_RESET_DR, b, rc, blk); for (int k = 0; k < 4; ++k) x.kp_factors[4 * blk + k] = rand_float(lerp_lo(c, GO2SIM_FC_KPF_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_KPF_EASY_LO, ts), r.v[k]); }
   if (c.i[GO2SIM_IC_HAS_KDF_DR])
-    for (int blk = 0; blk < 3; ++blk) { dm_u4 r = rng4(h, RNG_RESET_DR, b, rc, 3 + blk); for (int k = 0; k < 4; ++k) x.kd_factors[4 * blk + k] = rand_float(lerp_lo(c, GO2SIM_FC_KDF_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_KDF_EASY_LO, ts), r.v[k]); }
+    for (int blk = 0; blk < 3; ++blk) { dm_u4 r = rng4(h, GO2SIM_RNG_RESET_DR, b, rc, 3 + blk); for (int k = 0; k < 4; ++k) x.kd_factors[4 * blk + k] = rand_float(lerp_lo(c, GO2SIM_FC_KDF_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_KDF_EASY_LO, ts), r.v[k]); }
   if (c.i[GO2SIM_IC_HAS_GOFF_DR]) {                                                        // _randomize_gravity_offset :824-832
-    dm_u4 r = rng4(h, RNG_RESET_DR, b, rc, 6);
+    dm_u4 r = rng4(h, GO2SIM_RNG_RESET_DR, b, rc, 6);
     for (int k = 0; k < 3; ++k) x.gravity_offset[k] = rand_float(lerp_lo(c, GO2SIM_FC_GOFF_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_GOFF_EASY_LO, ts), r.v[k]);
   }
   if (c.i[GO2SIM_IC_HAS_MSTR_DR])                                                          // _randomize_motor_strength :850-858
-    for (int blk = 0; blk < 3; ++blk) { dm_u4 r = rng4(h, RNG_RESET_DR, b, rc, 7 + blk); for (int k = 0; k < 4; ++k) x.motor_strength[4 * blk + k] = rand_float(lerp_lo(c, GO2SIM_FC_MSTR_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_MSTR_EASY_LO, ts), r.v[k]); }
+    for (int blk = 0; blk < 3; ++blk) { dm_u4 r = rng4(h, GO2SIM_RNG_RESET_DR, b, rc, 7 + blk); for (int k = 0; k < 4; ++k) x.motor_strength[4 * blk + k] = rand_float(lerp_lo(c, GO2SIM_FC_MSTR_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_MSTR_EASY_LO, ts), r.v[k]); }
   if (c.i[GO2SIM_IC_PER_ENV_GLOBAL_DR]) {   // extension (BASELINE configs[4], not in the reference): the friction / base-mass scalars are drawn per env
-    dm_u4 r = rng4(h, RNG_RESET_DR, b, rc, 10);
+    dm_u4 r = rng4(h, GO2SIM_RNG_RESET_DR, b, rc, 10);
     if (c.i[GO2SIM_IC_HAS_FRICTION_DR]) {
       real mu = rand_float(lerp_lo(c, GO2SIM_FC_FRICTION_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_FRICTION_EASY_LO, ts), r.v[0]);
       for (int i = 0; i < NG; ++i) e.geom_friction[i] = mu;
@@ -2557,7 +2557,7 @@ void env_reset_one(go2sim* h, int b) {
     if (c.i[GO2SIM_IC_HAS_MASS_DR])
       e.mass_shift[c.i[GO2SIM_IC_BASE_LINK]] = rand_float(lerp_lo(c, GO2SIM_FC_MASS_EASY_LO, ts), lerp_hi(c, GO2SIM_FC_MASS_EASY_LO, ts), r.v[1]);
   }
-  dm_u4 rp = rng4(h, RNG_RESET_POSE, b, rc, 0);
+  dm_u4 rp = rng4(h, GO2SIM_RNG_RESET_POSE, b, rc, 0);
   {                                                                                        // _randomize_delay :860-866
     int max_d = std::max(c.i[GO2SIM_IC_MIN_DELAY], std::min(g.delay_max_cur, c.i[GO2SIM_IC_MAX_DELAY]));
     x.delay_steps = rand_int(c.i[GO2SIM_IC_MIN_DELAY], max_d, rp.v[3]);
@@ -2603,7 +2603,7 @@ void env_reset_one(go2sim* h, int b) {
   for (int i = 0; i < 4; ++i) { x.feet_air_time[i] = 0.0f; x.foot_contact[i] = 0; x.last_foot_contact[i] = 0; }
   for (int k = 0; k < NREW; ++k) x.episode_sums[k] = 0.0f;
   x.episode_length = 0; x.reset_buf = 1;
-  dm_u4 r = rng4(h, RNG_RESET_CMD, b, rc, 0);                                              // _resample_commands(envs_idx) :1240
+  dm_u4 r = rng4(h, GO2SIM_RNG_RESET_CMD, b, rc, 0);                                              // _resample_commands(envs_idx) :1240
   sample_commands(c, g, r, b, x.commands);
 }
 
@@ -2660,7 +2660,7 @@ void env_post_b(go2sim* h, int b, real* obs, real* priv) {
   if (c.i[GO2SIM_IC_HAS_OBS_NOISE] && c.d[GO2SIM_FC_OBS_NOISE_LEVEL_MAX] > 0.0) {          // _add_obs_noise :908-910, _rebuild_obs_noise_vec :611-626
     double lvl = g.obs_noise_level_cur;                                                     // python-float products, rounded on assignment into the float32 vector
     for (int blk = 0; blk * 4 < nobs; ++blk) {
-      dm_u4 r = rng4(h, RNG_OBS_NOISE, b, g.step_count, blk);
+      dm_u4 r = rng4(h, GO2SIM_RNG_OBS_NOISE, b, g.step_count, blk);
       real n[4];
       dm_normal2(r.v[0], r.v[1], &n[0], &n[1]); dm_normal2(r.v[2], r.v[3], &n[2], &n[3]);
       for (int k = 0; k < 4; ++k) {
@@ -2972,12 +2972,12 @@ static void assign_terrain_rows(go2sim* h) {
     int max_row = (int)(level * (double)(n_rows - 1));
     max_row = std::max(0, std::min(max_row, n_rows - 1));
     int n_frontier = (int)((double)n * 0.40), n_near = (int)((double)n * 0.30);
-    for (int j = 0; j < n; ++j) h->eb[idx[j]].terrain_key = rng4(h, RNG_TERRAIN_PERM, idx[j], rc, 0).v[0];
+    for (int j = 0; j < n; ++j) h->eb[idx[j]].terrain_key = rng4(h, GO2SIM_RNG_TERRAIN_PERM, idx[j], rc, 0).v[0];
     for (int j = 0; j < n; ++j) {
       unsigned kj = h->eb[idx[j]].terrain_key;
       int p = 0;
       for (int j2 = 0; j2 < n; ++j2) { unsigned k2 = h->eb[idx[j2]].terrain_key; p += (k2 < kj) || (k2 == kj && j2 < j); }
-      dm_u4 r = rng4(h, RNG_TERRAIN_ROW, (uint32_t)p, rc, 0);
+      dm_u4 r = rng4(h, GO2SIM_RNG_TERRAIN_ROW, (uint32_t)p, rc, 0);
       int row;
       if (p < n_frontier) row = max_row;
       else if (p < n_frontier + n_near) row = (max_row >= 2) ? rand_int(std::max(0, max_row - 2), std::max(0, max_row - 1), r.v[0]) : max_row;

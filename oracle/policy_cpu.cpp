@@ -17,6 +17,7 @@
 #include "../include/go2sim.h"
 #include "../include/go2sim_detmath.h"
 #include "../include/go2sim_policy.h"
+#include "../include/go2sim_rng.h"
 
 struct go2sim_mlp {
   int n_layers = 0;
@@ -105,7 +106,7 @@ int go2sim_cpu_policy_act(go2sim_mlp_t* actor, go2sim_mlp_t* critic, const float
     for (int blk = 0; 4 * blk < A; ++blk) {
       float n[4] = {0.0f, 0.0f, 0.0f, 0.0f};
       if (!deterministic) {
-        dm_u4 r = dm_philox((uint32_t)b, step, 11u, (uint32_t)blk, (uint32_t)seed, (uint32_t)(seed >> 32));
+        dm_u4 r = dm_philox((uint32_t)b, step, GO2SIM_RNG_POLICY_NOISE, (uint32_t)blk, (uint32_t)seed, (uint32_t)(seed >> 32));
         dm_normal2(r.v[0], r.v[1], &n[0], &n[1]); dm_normal2(r.v[2], r.v[3], &n[2], &n[3]);
       }
       for (int k = 0; k < 4; ++k) {

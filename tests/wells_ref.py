@@ -11,7 +11,7 @@ import lidar_ref as LR
 import policy_ref as PR
 
 PURPOSE = 15            # GO2SIM_WELLS_RNG_PURPOSE
-PURPOSE_POSE = 8        # RNG_RESET_POSE of csrc/go2sim.hip: word 0 the z offset, words 1, 2 roll and pitch
+PURPOSE_POSE = 8        # GO2SIM_RNG_RESET_POSE (include/go2sim_rng.h): word 0 the z offset, words 1, 2 roll and pitch
 JITTER = 0.3            # GO2SIM_WELLS_SPAWN_JITTER
 f32 = np.float32
 
