@@ -432,7 +432,11 @@ struct alignas(16) ModelS {
   // leg form of the tree (build_leg_form): links of leg l at leg_links[LEG_D * l + 0 .. LEG_D - 1], root -> leaf, legs in the child_list order of
   // the root; leg_form = 0 when the tree does not have that shape.  (Bytes: the table fills the tail of the last 16-byte granule.)
   unsigned char leg_links[LEG_K * LEG_D], leg_root, leg_form;
+  // the links whose pose the kinematics read but never write (parent == -1 && is_fixed: the ground), bit i = link i < 15; FIXED_ROOTS_ALL: such a link lies
+  // beyond the mask, every link counts (tk_stage_links).  (The last two bytes of that granule: sizeof(ModelS) decides the LDS footprint of the step kernels.)
+  unsigned short fixed_roots;
 };
+constexpr unsigned FIXED_ROOTS_ALL = 0x8000u;
 constexpr int SOLVER_BLOCK_BYTES = (int)(sizeof(LinkS) * NL + 2 * (NTRI + 1) + sizeof(JLim) * NJ);
 static_assert(sizeof(ModelS) % 16 == 0 && (2 * (NTRI + 1)) % 4 == 0 && offsetof(ModelS, links) % 16 == 0 && offsetof(ModelS, jlim) == offsetof(ModelS, links) + sizeof(LinkS) * NL + 2 * (NTRI + 1), "ModelS is copied in 16-byte granules");
 
@@ -514,6 +518,10 @@ bool build_model_s(const Model& m, ModelS& o) {
     o.jlim[i].lo = rev ? m.dofs[J.dof_start].limit[0] : 0.0f; o.jlim[i].hi = rev ? m.dofs[J.dof_start].limit[1] : 0.0f;
   }
   o.leg_form = build_leg_form(m, o) ? 1 : 0;
+  unsigned fixed_roots = 0u;
+  for (int i = 0; i < NL; ++i)
+    if (m.links[i].parent == -1 && m.links[i].is_fixed) fixed_roots |= (i < 15) ? (1u << i) : FIXED_ROOTS_ALL;
+  o.fixed_roots = (unsigned short)fixed_roots;
   return true;
 }
 DEV float mass_mask(const ModelS& m, int i, int j) { return (float)((m.mass_mask_bits[i] >> j) & 1u); }
@@ -524,20 +532,20 @@ struct ModelView {
   int n_levels, iterations, ls_iterations, arrow_mode, leg_form; float substep_dt; V3 gravity; float eps, tolerance, ls_tolerance, meaninertia;
   const LinkS* links; const Joint* joints; const Dof* dofs; const GeomS* geoms; const Entity* entities; const float* qpos0;
   const unsigned* mass_mask_bits; const int *level_start, *level_links, *child_start, *child_list, *dof_link; const unsigned char *tri_i, *tri_j;
-  const unsigned char* leg_links; int leg_root;
+  const unsigned char* leg_links; int leg_root; unsigned fixed_roots;
   DEV ModelView(const ModelS* t, const ModelS* __restrict__ g)
       : n_levels(g->n_levels), iterations(g->iterations), ls_iterations(g->ls_iterations), arrow_mode(g->arrow_mode), leg_form(g->leg_form), substep_dt(g->substep_dt), gravity(g->gravity), eps(g->eps),
         tolerance(g->tolerance), ls_tolerance(g->ls_tolerance), meaninertia(g->meaninertia), links(t->links), joints(t->joints), dofs(t->dofs),
         geoms(t->geoms), entities(t->entities), qpos0(t->qpos0), mass_mask_bits(t->mass_mask_bits), level_start(t->level_start),
         level_links(t->level_links), child_start(t->child_start), child_list(t->child_list), dof_link(t->dof_link), tri_i(t->tri_i), tri_j(t->tri_j),
-        leg_links(t->leg_links), leg_root(g->leg_root) {}
+        leg_links(t->leg_links), leg_root(g->leg_root), fixed_roots(g->fixed_roots) {}
   // solver flavour: only the link table and the triangle LUT are staged in LDS; joint / dof constants are read with uniform indices and stay
   // behind scalar loads of the global model
   DEV ModelView(const LinkS* lds_links, const unsigned char* lds_tri_i, const unsigned char* lds_tri_j, const Model* __restrict__ g)
       : n_levels(g->n_levels), iterations(g->iterations), ls_iterations(g->ls_iterations), arrow_mode(g->arrow_mode), leg_form(0), substep_dt(g->substep_dt), gravity(g->gravity), eps(g->eps),
         tolerance(g->tolerance), ls_tolerance(g->ls_tolerance), meaninertia(g->meaninertia), links(lds_links), joints(g->joints), dofs(g->dofs),
         geoms(nullptr), entities(g->entities), qpos0(g->qpos0), mass_mask_bits(nullptr), level_start(nullptr), level_links(nullptr), child_start(nullptr),
-        child_list(nullptr), dof_link(nullptr), tri_i(lds_tri_i), tri_j(lds_tri_j), leg_links(nullptr), leg_root(-1) {}
+        child_list(nullptr), dof_link(nullptr), tri_i(lds_tri_i), tri_j(lds_tri_j), leg_links(nullptr), leg_root(-1), fixed_roots(0u) {}
 };
 DEV float mass_mask(const ModelView& m, int i, int j) { return (float)((m.mass_mask_bits[i] >> j) & 1u); }
 DEV void tri_index(const ModelView& m, int idx, int& i, int& j) { i = m.tri_i[idx]; j = m.tri_j[idx]; }
@@ -784,6 +792,11 @@ constexpr int PHA_REWK = 48, PHA_WAIT = 56;
 #define PHK_BEGIN unsigned long long phk_t = __builtin_readcyclecounter();
 #define PHK(i) { unsigned long long phk_n = __builtin_readcyclecounter(); if (threadIdx.x == 0 && blockIdx.x < PH_MAX_WG / 8) g_phase_cycles[(PH_MAX_WG - PH_MAX_WG / 8 + blockIdx.x) * 64 + (i)] += phk_n - phk_t; phk_t = __builtin_readcyclecounter(); }
 #define PHW(i) { unsigned long long ph_n = __builtin_readcyclecounter(); if (threadIdx.x == 0 && blockIdx.x < PH_MAX_WG / 2) g_phase_cycles[blockIdx.x * 64 + (i)] += ph_n - ph_t; ph_t = __builtin_readcyclecounter(); }
+// the integrate / kinematics half of the step kernels (phases 40 / 41) split finer (ids PHI_* below): a timer of its own, the rows of PHK (k_collide_team
+// uses ids 0-11 there) at ids from PHI_ID0.  Like PHK a PHI mark does not wait for memory; the marks stand BEHIND the sync points, whose wait they account.
+constexpr int PHI_ID0 = 16;
+#define PHI_BEGIN unsigned long long phi_t = __builtin_readcyclecounter();
+#define PHI(i) { unsigned long long phi_n = __builtin_readcyclecounter(); if (threadIdx.x == 0 && blockIdx.x < PH_MAX_WG / 8) g_phase_cycles[(PH_MAX_WG - PH_MAX_WG / 8 + blockIdx.x) * 64 + PHI_ID0 + (i)] += phi_n - phi_t; phi_t = __builtin_readcyclecounter(); }
 #else
 #define PH_BEGIN
 #define PH(i)
@@ -796,7 +809,12 @@ constexpr int PHA_REWK = 48, PHA_WAIT = 56;
 #define PHK_BEGIN
 #define PHK(i)
 #define PHW(i)
+#define PHI_BEGIN
+#define PHI(i)
 #endif
+// PHI ids (tools/phase_profile.py): the staging until its sync; tk_integrate: the new coordinates, the NaN verdict, current state + stores; tk_kinematics: the
+// link walk, the inertial frames (phase 19 until i_pos / i_quat are in LDS), the centre-of-mass reduction, inertia + cdof, geoms + the closing sync, velocities
+enum { PHI_STAGE = 0, PHI_INT_NEXT, PHI_INT_NAN, PHI_INT_COPY, PHI_WALK, PHI_IFRAME, PHI_COM, PHI_INERTIA, PHI_GEOMS, PHI_VEL };
 // PHK ids (tools/phase_profile.py): the head until the pair words are in LDS / until batch 2 has arrived; cc_detect0 (set-up + MPR round: section 36
 // is inside), the fallback quads, the sync behind them, cc_rest; the append (issue of the stores), the round's LDS sync, the sync behind the pair
 // loop, plane-box + terrain + the count, the sync behind the count, LPT key + mask stores
@@ -1064,9 +1082,35 @@ struct DynData {
 static_assert(!ARROW_SHAPE || (offsetof(DynData, Dinv) % 8 == 0 && sizeof(DynData) % 8 == 0), "arrow_solve reads DynData::Dinv with 8-byte LDS loads");
 #endif
 
+// The link poses the kinematics take from memory: those of the fixed roots (ModelS::fixed_roots; `fixed_roots` comes from the global copy of the model, the
+// LDS tables are still in flight here).  No other pose is read before tk_kinematics has written it:
+//  - leg form (build_leg_form: the tree is ONE free root, its LEG_K * LEG_D chain links, and fixed roots without joints or children): lane 0 writes the root,
+//    the leg lanes every chain link, all in front of the sync that closes the walk; the walk itself reads no pose from LDS;
+//  - level walk: every link but a fixed root is written at its level (fixed links below a parent included), a parent's pose is read one level -- one sync --
+//    after it was written, and a root reads none;
+//  - everything behind the walk (inertial frames, free-joint cdof, geoms -- those on fixed links too, with force_update_fixed or without) reads after that sync.
 template <int T>
-DEV void tk_stage_links(const E& e, KinData* s, int tl) {
-  team_for<NL, T>(tl, [&](int i_l) { st3(s->l_pos, i_l, e.l_pos()[i_l]); st4(s->l_quat, i_l, e.l_quat()[i_l]); });
+DEV void tk_stage_links(unsigned fixed_roots, const E& e, KinData* s, int tl) {
+  team_for<NL, T>(tl, [&](int i_l) {
+    if ((fixed_roots & FIXED_ROOTS_ALL) || (i_l < 15 && ((fixed_roots >> i_l) & 1u))) { st3(s->l_pos, i_l, e.l_pos()[i_l]); st4(s->l_quat, i_l, e.l_quat()[i_l]); }
+  });
+}
+// mass_shift / com_shift of the links of my lane (link r * T + tl in round r), requested with the staging batch of the kernel and consumed by tk_kinematics
+// behind the link walk -- where the request used to stand, a full memory round trip in the middle of the chain.  Nothing writes the two fields while a
+// kernel of the substep sequence or k_fk_team runs: their writers are the reset / randomisation code of the env kernels (reset_tail in k_env_post_b_team,
+// whose FK wavefront loads behind the workgroup barrier that follows it; the reset kernels) and go2sim_set_field, all of them launches of their own.
+template <int T>
+struct LinkShift { static constexpr int R = (NL + T - 1) / T; float mass[R]; V3 com[R]; };
+template <int T>
+DEV LinkShift<T> tk_load_shifts(const E& e, int tl) {
+  LinkShift<T> o;
+#pragma unroll
+  for (int r = 0; r < LinkShift<T>::R; ++r) {
+    int i_l = r * T + tl;
+    i_l = i_l < NL ? i_l : NL - 1;
+    o.mass[r] = gload(e, FO(mass_shift), i_l); o.com[r] = (V3)e.com_shift()[i_l];
+  }
+  return o;
 }
 // update_cartesian_space + forward_velocity of the state held in s->qpos / s->vel
 // (func_forward_kinematics_entity :463-618, func_COM_links_entity :224-459, func_update_geoms_entity :709-744,
@@ -1076,14 +1120,15 @@ DEV void tk_stage_links(const E& e, KinData* s, int tl) {
 // (with `dk`, i.e. between the substeps of an env step, the outputs that only the forward dynamics reads -- cinr_*, cdofd_*, cd_vel / cd_ang, i_pos --
 //  are not written to HBM at all: the dynamics half of the same kernel takes them from LDS, and the FK that closes the step writes them all)
 template <int T, class MT>
-DEV void tk_kinematics(const MT& m, const E& e, KinData* s, int tl, bool force_update_fixed, DynData* dk = nullptr) {
-  // s->l_pos / s->l_quat hold the current link poses (tk_stage_links, issued with the kernel's other staging loads)
+DEV void tk_kinematics(const MT& m, const E& e, KinData* s, int tl, bool force_update_fixed, const LinkShift<T>& sh, DynData* dk = nullptr) {
+  // s->l_pos / s->l_quat hold the poses of the fixed roots (tk_stage_links, issued with the kernel's other staging loads), `sh` my links' shifts
   PH_BEGIN                                                             // (profiling builds: 18 = link poses by level, 19 = COM / inertia / cdof / geoms, 55 = velocities by level)
+  PHI_BEGIN
   const bool legs = (T == 32 || T == 64) && m.leg_form;
   if (legs) {
     // leg form: every lane evaluates the root pose (redundantly: the same operations, no LDS round trip), lane l < LEG_K then walks leg l root -> leaf
-    // in registers.  The joint-local terms (dp, the local rotation) do not depend on the parent: they are formed before the walk, side by side on
-    // LEG_K * LEG_D lanes.  Per link the operations and their order are those of the level walk below.
+    // in registers (in three stages, below).  The joint-local terms (dp, the local rotation) do not depend on the parent: they are formed before the walk,
+    // side by side on LEG_K * LEG_D lanes.  Per link the operations and their order are those of the level walk below.
     const int r = m.leg_root;
     const int rq = m.joints[m.links[r].joint_start].q_start;
     const V3 rpos = v3(s->qpos[rq], s->qpos[rq + 1], s->qpos[rq + 2]);
@@ -1114,29 +1159,60 @@ DEV void tk_kinematics(const MT& m, const E& e, KinData* s, int tl, bool force_u
       const int src = tl < LEG_K ? LEG_D * tl + d : 0;
       qloc[d] = q4(__shfl(ql.w, src, T), __shfl(ql.x, src, T), __shfl(ql.y, src, T), __shfl(ql.z, src, T));
     }
-    if (tl < LEG_K) {
-      int lk[LEG_D], jk[LEG_D];
-      V3 lpos[LEG_D], jpos[LEG_D], axis[LEG_D]; Q4 lquat[LEG_D];
+    // The walk of a leg in three stages.  Only the orientations form a chain of rotations: per link qa = the link's frame in its parent's (before the joint),
+    // qf = the joint's rotation applied to it.  The four rotated vectors of a link (link offset by the parent's orientation, joint position and axis by qa,
+    // joint position by qf) depend on orientations alone, so once stage 1 has them they are formed side by side on the LEG_K * LEG_D chain-link lanes; what
+    // is left of the position chain in stage 3 is three vector additions per link.  Every expression is the one of the level walk, operands in its order:
+    // the stages change which lane evaluates it, not what is evaluated.  (Lanes outside a stage shadow lane 0's work and store nothing.)
+    const int lg = tl < LEG_K ? tl : 0;
+    int lk[LEG_D], jk[LEG_D]; Q4 qa[LEG_D], qf[LEG_D];
+    {                                                                  // stage 1, lane l < LEG_K: the orientations of leg l, root -> leaf
+      Q4 quat = rquat;
 #pragma unroll
       for (int d = 0; d < LEG_D; ++d) {
-        lk[d] = m.leg_links[LEG_D * tl + d];
+        lk[d] = m.leg_links[LEG_D * lg + d];
         const auto& L = m.links[lk[d]];
         jk[d] = L.joint_start;
-        const Joint& J = m.joints[jk[d]];
-        lpos[d] = L.pos; lquat[d] = L.quat; jpos[d] = J.pos; axis[d] = m.dofs[J.dof_start].motion_ang;
+        qa[d] = transform_quat_by_quat(L.quat, quat);
+        qf[d] = transform_quat_by_quat(qloc[d], qa[d]);
+        quat = qf[d];
       }
-      V3 pos = rpos; Q4 quat = rquat;
+    }
+    const int cj = tl < LEG_K * LEG_D ? tl : 0, cl = cj / LEG_D, cd = cj % LEG_D;
+    Q4 pq = rquat, cqa = rquat, cqf = rquat;                           // stage 2, lane LEG_D * l + d: link d of leg l; its parent's orientation, its qa and qf
+#pragma unroll
+    for (int d = 0; d < LEG_D; ++d) {
+      const Q4 a = q4(__shfl(qa[d].w, cl, T), __shfl(qa[d].x, cl, T), __shfl(qa[d].y, cl, T), __shfl(qa[d].z, cl, T));
+      const Q4 f = q4(__shfl(qf[d].w, cl, T), __shfl(qf[d].x, cl, T), __shfl(qf[d].y, cl, T), __shfl(qf[d].z, cl, T));
+      if (cd == d) { cqa = a; cqf = f; }
+      if (cd == d + 1) pq = f;
+    }
+    V3 t_lp, t_ja, t_jf;
+    {
+      const auto& L = m.links[m.leg_links[cj]];
+      const int i_j = L.joint_start;
+      const Joint& J = m.joints[i_j];
+      t_lp = transform_by_quat(L.pos, pq);
+      t_ja = transform_by_quat(J.pos, cqa);
+      const V3 t_ax = transform_by_quat(m.dofs[J.dof_start].motion_ang, cqa);
+      t_jf = transform_by_quat(J.pos, cqf);
+      if (tl < LEG_K * LEG_D) st3(s->xaxis, i_j, t_ax);
+    }
+    {                                                                  // stage 3, lane l < LEG_K: the positions of leg l, root -> leaf
+      V3 pos = rpos;
 #pragma unroll
       for (int d = 0; d < LEG_D; ++d) {
-        const Q4 pq = quat;
-        pos = pos + transform_by_quat(lpos[d], pq);
-        quat = transform_quat_by_quat(lquat[d], pq);
-        const V3 anchor = transform_by_quat(jpos[d], quat) + pos;
-        st3(s->xanchor, jk[d], anchor);
-        st3(s->xaxis, jk[d], transform_by_quat(axis[d], quat));
-        quat = transform_quat_by_quat(qloc[d], quat);
-        pos = anchor - transform_by_quat(jpos[d], quat);
-        st3(s->l_pos, lk[d], pos); st4(s->l_quat, lk[d], quat); e.l_pos()[lk[d]] = pos; e.l_quat()[lk[d]] = quat;
+        const int src = LEG_D * lg + d;
+        const V3 lp = v3(__shfl(t_lp.x, src, T), __shfl(t_lp.y, src, T), __shfl(t_lp.z, src, T));
+        const V3 ja = v3(__shfl(t_ja.x, src, T), __shfl(t_ja.y, src, T), __shfl(t_ja.z, src, T));
+        const V3 jf = v3(__shfl(t_jf.x, src, T), __shfl(t_jf.y, src, T), __shfl(t_jf.z, src, T));
+        pos = pos + lp;
+        const V3 anchor = ja + pos;
+        pos = anchor - jf;
+        if (tl < LEG_K) {
+          st3(s->xanchor, jk[d], anchor);
+          st3(s->l_pos, lk[d], pos); st4(s->l_quat, lk[d], qf[d]); e.l_pos()[lk[d]] = pos; e.l_quat()[lk[d]] = qf[d];
+        }
       }
     }
     team_sync();
@@ -1182,15 +1258,20 @@ DEV void tk_kinematics(const MT& m, const E& e, KinData* s, int tl, bool force_u
     team_sync();
   }
   PH(18)
+  PHI(PHI_WALK)
   // centre of mass of each kinematic tree
-  for (int i_l = tl; i_l < NL; i_l += T) {
+#pragma unroll
+  for (int r = 0; r < LinkShift<T>::R; ++r) {
+    const int i_l = r * T + tl;
+    if (i_l >= NL) continue;
     const auto& L = m.links[i_l];
-    s->mass[i_l] = L.mass + gload(e, FO(mass_shift), i_l);
+    s->mass[i_l] = L.mass + sh.mass[r];
     V3 ipbw; Q4 iq;
-    transform_pos_quat_by_trans_quat(L.inertial_pos + (V3)e.com_shift()[i_l], L.inertial_quat, ld3(s->l_pos, i_l), ld4(s->l_quat, i_l), ipbw, iq);
+    transform_pos_quat_by_trans_quat(L.inertial_pos + sh.com[r], L.inertial_quat, ld3(s->l_pos, i_l), ld4(s->l_quat, i_l), ipbw, iq);
     st3(s->i_pos, i_l, ipbw); st4(s->i_quat, i_l, iq);
   }
   team_sync();
+  PHI(PHI_IFRAME)
   V3 rc[2];
 #pragma unroll
   for (int i_e = 0; i_e < 2; ++i_e) {
@@ -1204,6 +1285,7 @@ DEV void tk_kinematics(const MT& m, const E& e, KinData* s, int tl, bool force_u
     rc[i_e] = root_com_bw / mass_sum;
   }
   team_sync();
+  PHI(PHI_COM)
   for (int i_l = tl; i_l < NL; i_l += T) {
     const auto& L = m.links[i_l];
     V3 r = (L.entity == 0) ? rc[0] : rc[1];
@@ -1250,6 +1332,7 @@ DEV void tk_kinematics(const MT& m, const E& e, KinData* s, int tl, bool force_u
       }
     }
   }
+  PHI(PHI_INERTIA)
   for (int i_g = tl; i_g < NG; i_g += T) {
     const auto& G = m.geoms[i_g];
     bool is_fixed = m.links[G.link].is_fixed;
@@ -1260,6 +1343,7 @@ DEV void tk_kinematics(const MT& m, const E& e, KinData* s, int tl, bool force_u
     }
   }
   team_sync();
+  PHI(PHI_GEOMS)
   PH(19)
   // forward velocity
   if (legs) {
@@ -1368,11 +1452,13 @@ DEV void tk_kinematics(const MT& m, const E& e, KinData* s, int tl, bool force_u
     team_sync();
   }
   PH(55)
+  PHI(PHI_VEL)
 }
 
 // func_integrate (forward_dynamics.py:1558-1699) + func_copy_next_to_curr (abd/diff.py:25-54) on the staged state: s->vel_next holds v + a dt
 template <int T, class MT>
 DEV void tk_integrate(const MT& m, const E& e, KinData* s, int tl) {
+  PHI_BEGIN
   for (int i_l = tl; i_l < NL; i_l += T) {
     const auto& L = m.links[i_l];
     if (L.n_dofs == 0) continue;
@@ -1393,11 +1479,13 @@ DEV void tk_integrate(const MT& m, const E& e, KinData* s, int tl) {
     }
   }
   team_sync();
+  PHI(PHI_INT_NEXT)
   bool bad = false;
   for (int d = tl; d < ND; d += T) bad |= isnan_(s->vel_next[d]);
   for (int q = tl; q < NQ; q += T) bad |= isnan_(s->qpos_next[q]);
   if (bad) s->valid = 0;
   team_sync();
+  PHI(PHI_INT_NAN)
   if (s->valid) {
     for (int d = tl; d < ND; d += T) { float v = s->vel_next[d]; s->vel[d] = v; gstore(e, FO(vel), d, v); }
     for (int q = tl; q < NQ; q += T) { float v = s->qpos_next[q]; s->qpos[q] = v; gstore(e, FO(qpos), q, v); }
@@ -1405,6 +1493,7 @@ DEV void tk_integrate(const MT& m, const E& e, KinData* s, int tl) {
     atomicOr(&e.err()[0], GO2SIM_ERR_INVALID_ACC_NAN);
   }
   team_sync();
+  PHI(PHI_INT_COPY)
 }
 
 // kernel_step_2 (rigid_solver.py:3072-3180): func_integrate (forward_dynamics.py:1558-1699) + func_copy_next_to_curr
@@ -1420,6 +1509,7 @@ DEV void integrate_fk_body(const Pool& P, const ModelS* __restrict__ mp, int b, 
   E e(P, b < P.B ? b : P.B - 1);
   KinData* s = &lds[slot];
   PH_BEGIN
+  PHI_BEGIN
   if (pre) { if (tl < ND) { s->vel[tl] = pre_vel; s->vel_next[tl] = pre_acc; } }
   else {
     team_stage<ND, T>(tl, [&](int d) { return gload(e, FO(vel), d); }, [&](int d, float v) { s->vel[d] = v; });
@@ -1428,12 +1518,14 @@ DEV void integrate_fk_body(const Pool& P, const ModelS* __restrict__ mp, int b, 
   team_stage<NQ, T>(tl, [&](int q) { return gload(e, FO(qpos), q); }, [&](int q, float v) { s->qpos[q] = v; });
   team_for<ND, T>(tl, [&](int d) { s->vel_next[d] = s->vel[d] + s->vel_next[d] * m.substep_dt; });
   if (tl == 0) s->valid = 1;
-  tk_stage_links<T>(e, s, tl);
+  tk_stage_links<T>(m.fixed_roots, e, s, tl);
+  const LinkShift<T> sh = tk_load_shifts<T>(e, tl);
   team_sync();
+  PHI(PHI_STAGE)
   if (b >= P.B) return;
   tk_integrate<T>(m, e, s, tl);
   PH(40)
-  tk_kinematics<T>(m, e, s, tl, false);
+  tk_kinematics<T>(m, e, s, tl, false, sh);
   PH(41)
 }
 template <int T>
@@ -1461,10 +1553,11 @@ __global__ __launch_bounds__(64) void k_fk_team(Pool P, const ModelS* __restrict
   KinData* s = &lds[slot];
   team_stage<ND, T>(tl, [&](int d) { return gload(e, FO(vel), d); }, [&](int d, float v) { s->vel[d] = v; });
   team_stage<NQ, T>(tl, [&](int q) { return gload(e, FO(qpos), q); }, [&](int q, float v) { s->qpos[q] = v; });
-  tk_stage_links<T>(e, s, tl);
+  tk_stage_links<T>(m.fixed_roots, e, s, tl);
+  const LinkShift<T> sh = tk_load_shifts<T>(e, tl);
   team_sync();
   if (b >= P.B) return;
-  tk_kinematics<T>(m, e, s, tl, force_update_fixed != 0);
+  tk_kinematics<T>(m, e, s, tl, force_update_fixed != 0, sh);
 }
 
 // kernel_step_1 without the (already fresh) FK, rigid_solver.py:3008-3069: func_compute_mass_matrix (forward_dynamics.py:291-541),
@@ -2036,6 +2129,7 @@ DEV void integrate_fk_dynamics_body(const Pool& P, const ModelS* __restrict__ mp
   static_assert(offsetof(DynData, L) == offsetof(DynData, M) + sizeof(float) * ND * ND, "KinData overlay");
   KinData* s = lds_k.at(slot, d->M);
   PH_BEGIN
+  PHI_BEGIN
   if (pre) { if (tl < ND) { s->vel[tl] = pre_vel; s->vel_next[tl] = pre_acc; } }     // (k_solve_integrate_team: taken from the solver's LDS block)
   else {
     team_stage<ND, T>(tl, [&](int i) { return gload(e, FO(vel), i); }, [&](int i, float v) { s->vel[i] = v; });
@@ -2051,12 +2145,14 @@ DEV void integrate_fk_dynamics_body(const Pool& P, const ModelS* __restrict__ mp
                         [&](int k, float v) { int i_l = k / 6, c = k % 6; if (c < 3) d->cfrc_ang[3 * i_l + c] = v; else d->cfrc_vel[3 * i_l + c - 3] = v; });
   team_for<ND, T>(tl, [&](int i) { s->vel_next[i] = s->vel[i] + s->vel_next[i] * m.substep_dt; });
   if (tl == 0) s->valid = 1;
-  tk_stage_links<T>(e, s, tl);
+  tk_stage_links<T>(m.fixed_roots, e, s, tl);
+  const LinkShift<T> sh = tk_load_shifts<T>(e, tl);
   team_sync();
+  PHI(PHI_STAGE)
   if (b >= P.B) return;                                               // (team_sync is a fence, not a barrier: a team may leave early)
   tk_integrate<T>(m, e, s, tl);
   PH(40)
-  tk_kinematics<T>(m, e, s, tl, false, d);
+  tk_kinematics<T>(m, e, s, tl, false, sh, d);
   team_for<ND, T>(tl, [&](int i) { d->vel[i] = s->vel[i]; });
   team_sync();
   PH(41)
@@ -6234,10 +6330,11 @@ __global__ __launch_bounds__(128) void k_env_post_b_team(Pool P, const Model* __
     KinData* ks = &fk_lds[slot];
     team_stage<ND, T>(tl, [&](int d) { return gload(e, FO(vel), d); }, [&](int d, float v) { ks->vel[d] = v; });
     team_stage<NQ, T>(tl, [&](int q) { return gload(e, FO(qpos), q); }, [&](int q, float v) { ks->qpos[q] = v; });
-    tk_stage_links<T>(e, ks, tl);
+    tk_stage_links<T>(msp->fixed_roots, e, ks, tl);
+    const LinkShift<T> sh = tk_load_shifts<T>(e, tl);
     team_sync();
     const ModelView mv((const ModelS*)ms_raw, msp);
-    tk_kinematics<T>(mv, e, ks, tl, true);
+    tk_kinematics<T>(mv, e, ks, tl, true, sh);
     return;
   }
   const bool valid = b < P.B;                                          // (lanes beyond the batch stay with their wavefront up to its ONE barrier)

@@ -85,17 +85,35 @@ def print_phk(a, launches):
     print(f"   sum {k[used].sum(1).mean() / launches:9.0f}")
 
 
+# the integrate / kinematics half of the step kernels (phases 40 / 41) split finer (PHI_* in csrc/go2sim.hip): the rows of PHK at ids from PHI_ID0, marks that do not wait for
+# memory and stand behind the sync points whose wait they account
+PHI_ID0 = 16
+PHI_NAMES = ["staging until its sync", "tk_integrate: new coordinates", "tk_integrate: NaN verdict", "tk_integrate: current state + stores", "link walk (phase 18)",
+             "inertial frames: phase 19 until i_pos / i_quat are in LDS", "centre-of-mass reduction", "inertia + cdof", "geoms + closing sync", "velocities (phase 55)"]
+def phi_rows(a):
+    return a[PHK_ROW0:PHK_ROW0 + PH_MAX_WG // 8, PHI_ID0:PHI_ID0 + len(PHI_NAMES)]
+def print_phi(k, launches):
+    used = k.sum(1) > 0
+    if not used.any(): return
+    print(f"== integrate + kinematics split (marks without a memory wait, behind the sync points): mean cycles per WG-launch over {int(used.sum())} workgroups")
+    for i, n in enumerate(PHI_NAMES):
+        print(f"   phi {i:2d} {n:58s} {k[used, i].mean() / launches:9.0f}")
+    print(f"   sum {k[used].sum(1).mean() / launches:9.0f}")
+
+
 POST_B = [0, 1, 2, 3, 4]     # k_env_post_b_team keeps its own rows (the upper half, PHB in csrc/go2sim.hip): 0 reset, 1 staging + draws, 2 observations, 3 privileged tail, 4 copies
 if len(sys.argv) > 3 and sys.argv[3] == "each":
     # one read-out per env step: what a single launch waits for is its slowest workgroup, which per-run sums average away
     rows = {g: [] for g in list(GROUPS_) + ["post_b"]}
     worst = {g: None for g in list(GROUPS_) + ["post_b"]}
+    phi = 0.0
     terms = []                                                     # k_env_post_a's term section (PHA in csrc/go2sim.hip): one row of marks per workgroup, every wave its own ids
     for s in range(W, W + N):
         sim.env_step(act[s], obs, priv, rew, rst, to)
         lib.lib.go2sim_debug_phases(sim.h, out, 1)
         a = np.frombuffer(out, dtype=np.uint64).reshape(PH_MAX_WG, 64).astype(np.float64)
         terms.append(a[PH_MAX_WG // 2 + PH_MAX_WG // 4:][: (B + 63) // 64].copy())
+        phi = phi + phi_rows(a)
         ab, a = a[PH_MAX_WG // 2: PH_MAX_WG // 2 + PH_MAX_WG // 4], a[:PH_MAX_WG // 2]
         tot = ab[:, POST_B].sum(1)
         if (tot > 0).any():
@@ -118,6 +136,7 @@ if len(sys.argv) > 3 and sys.argv[3] == "each":
         r = np.array(r)
         print(f"== {g}: cycles per WG-launch over {N} single steps: mean {r[:, 0].mean():9.0f}  p99 {r[:, 1].mean():9.0f}  p99.9 {r[:, 2].mean():9.0f}  max (mean over steps) {r[:, 3].mean():9.0f}  max (worst step) {r[:, 3].max():9.0f}")
         print("   worst workgroup: " + "  ".join(f"ph{k}={v:.0f}" for k, v in worst[g][1].items() if v > 0) + ("  | counters (both launches) " + " ".join(f"{k}:{v:.0f}" for k, v in worst[g][2].items()) if g in ("solver", "collide") else ""))
+    print_phi(phi, 2 * N)
     t = np.array(terms)                                            # [step][workgroup][id]
     if t.sum() > 0:
         from go2_sim2real_locomotion_rl_amd.capi import C
@@ -174,3 +193,4 @@ for g, ids in GROUPS.items():
             continue
         print(f"   phase {i:2d} {NAMES.get(i, ''):24s} mean {sub[used, k].mean() / launches:9.0f} ({100 * sub[used, k].sum() / tot[used].sum():5.1f}%)   slowest 1% {sub[top, k].mean() / launches:9.0f} ({100 * sub[top, k].sum() / tot[top].sum():5.1f}%)")
 print_phk(a, launches)
+print_phi(phi_rows(a), launches)
