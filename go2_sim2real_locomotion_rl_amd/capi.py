@@ -69,6 +69,7 @@ ACT_HEADER, DECLARED_ACT_FUNCS = _product_header("activation")                 #
 RND_HEADER, DECLARED_RND_FUNCS = _product_header("rnd")                        # random network distillation: the intrinsic reward and the predictor's update
 TILES_HEADER, DECLARED_TILES_FUNCS = _product_header("tiles")                  # the rough-terrain walk env: float heightfield, ground query
 WELLS_HEADER, DECLARED_WELLS_FUNCS = _product_header("wells")                  # the stairwell env: 11 x 11 scan, alive term
+STATE_HEADER, DECLARED_STATE_FUNCS = _product_header("state")                  # env snapshots: the record's size, save, load
 RNG_HEADER, _ = _product_header("rng", [])                                     # the purposes of the random stream (constants only; both libraries)
 # train_cfg["policy"]["activation"] as rsl_rl's resolve_nn_activation spells it -> GO2SIM_ACT_*
 ACTIVATIONS = {n: C["GO2SIM_ACT_" + n.upper()] for n in ("elu", "selu", "relu", "lrelu", "tanh", "sigmoid", "identity")}
@@ -395,6 +396,27 @@ class Go2Sim(Handle):
     def env_set_level(self, level, stream=None):
         self._call("env_set_level", ctypes.c_double(level), _ptr(stream))
 
+    # ---- snapshots (include/go2sim_state.h; the product library alone has them) ------------------
+    def _state_call(self, name, *args):
+        if not self.L.is_device or not hasattr(self.L.lib, name):
+            raise Go2SimError(f"{name} is an entry of the HIP product library (include/go2sim_state.h); {self.L.path} does not have it")
+        return getattr(self.L.lib, name)(self.h, *args)
+
+    def state_size(self):
+        n = ctypes.c_size_t()
+        self.L.check(self._state_call("go2sim_state_size", ctypes.byref(n)), "state_size")
+        return n.value
+
+    def state_save(self, dst, nbytes=None, stream=None):
+        """go2sim_state_save into `dst`: a contiguous uint8 / int32 device tensor (or a raw device address with `nbytes`); stream-ordered"""
+        n = dst.numel() * dst.element_size() if nbytes is None else int(nbytes)
+        self.L.check(self._state_call("go2sim_state_save", _ptr(dst), ctypes.c_size_t(n), _ptr(stream)), "state_save")
+
+    def state_load(self, src, nbytes=None, stream=None):
+        """go2sim_state_load from `src`; -> the status (GO2SIM_E_OK, or GO2SIM_E_BADARG for a refused record: the handle is then untouched)"""
+        n = src.numel() * src.element_size() if nbytes is None else int(nbytes)
+        return self._state_call("go2sim_state_load", _ptr(src), ctypes.c_size_t(n), _ptr(stream))
+
     def enable_timing(self, enable=True):
         self._call("enable_timing", ctypes.c_int(int(enable)))
 
@@ -417,6 +439,31 @@ class Go2Sim(Handle):
         k, is_int = self.field_size(field)
         arr = np.ascontiguousarray(arr, dtype=np.int32 if is_int else np.float32).reshape(k, self.n_envs)
         self.set_field(field, arr)
+
+
+# the words of a snapshot's header that go2sim_state_load compares, by name (include/go2sim_state.h): (first word, words, name)
+STATE_HEADER_FIELDS = [(C["GO2SIM_STATE_W_MAGIC"], 1, "magic"), (C["GO2SIM_STATE_W_VERSION"], 1, "format version"), (C["GO2SIM_STATE_W_N_ENVS"], 1, "n_envs"),
+                       (C["GO2SIM_STATE_W_NQ"], C["GO2SIM_STATE_W_SEED"] - C["GO2SIM_STATE_W_NQ"], "layout constants"), (C["GO2SIM_STATE_W_SEED"], 2, "seed"),
+                       (C["GO2SIM_STATE_W_MODEL_DIGEST"], 2, "model digest"), (C["GO2SIM_STATE_W_CFG_DIGEST"], 2, "configuration digest"),
+                       (C["GO2SIM_STATE_W_BYTES"], 2, "record size")]
+
+
+def state_header_mismatch(words_a, words_b):
+    """Names of the compared header fields in which two snapshot headers (sequences of uint32 words) differ."""
+    return [name for w0, n, name in STATE_HEADER_FIELDS if [int(v) for v in words_a[w0:w0 + n]] != [int(v) for v in words_b[w0:w0 + n]]]
+
+
+def state_record_parts(words):
+    """[(name, first byte, bytes)] of the parts of a snapshot's body, from its header's words (include/go2sim_state.h): for telling where two records differ."""
+    W = lambda name: int(words[C["GO2SIM_STATE_W_" + name]]) & 0xFFFFFFFF
+    B = W("N_ENVS")
+    sizes = [("globals", W("GLOB_BYTES")), ("accumulator", W("ACC_BYTES")), ("soa_float", 4 * W("F_CARRIED") * B), ("soa_int", 4 * W("I_CARRIED") * B),
+             ("aos_float", 16 * W("AF_CARRIED") * B), ("aos_int", 16 * W("AI_CARRIED") * B)]
+    at, parts = 4 * C["GO2SIM_STATE_HDR_WORDS"], []
+    for name, n in sizes:
+        parts.append((name, at, n))
+        at += (n + 15) // 16 * 16
+    return parts
 
 
 def load_hip_lib():

@@ -33,6 +33,7 @@
 #include "../../include/go2sim_lidar.h"
 #include "../../include/go2sim_rng.h"
 #include "../../include/go2sim_stairinfo.h"
+#include "../../include/go2sim_state.h"
 #include "../../include/go2sim_tiles.h"
 #include "go2sim_tiles_dev.h"
 #include "../../include/go2sim_wells.h"
@@ -571,55 +572,65 @@ constexpr int GEOMK_BYTES = NG * (int)sizeof(GeomK), GEOMK_LDS_BYTES = lds_dma_b
 // Two pools.  SoA rows [feature][n_envs] hold what the lane-per-env Go2Env kernels touch (coalesced across envs); the AoS records
 // [n_envs][record] hold the physics-internal arrays that only the team kernels (and the field API) touch: the lanes of a team then
 // read / write consecutive words of one record (coalesced across the team) instead of one 64-byte sector per word.
+// The third argument marks what a snapshot carries (include/go2sim_state.h, DESIGN.md "Env state"): CARRIED = a step may read the field before it writes
+// it, or the field API shows values an earlier step left there; REWRITTEN = every word a step reads has been written earlier in the same step and
+// nothing else shows it.  These tables are the one place that knows the carried set.
+constexpr int CARRIED = 1, REWRITTEN = 0;
 #define GO2SIM_FLOAT_FIELDS(X)                                                                                       \
-  X(qpos, NQ) X(vel, ND) X(ctrl_force, ND) X(ext, NL * 6) X(mass_shift, NL) X(com_shift, NL * 3)                        \
-  X(friction_ratio, NG) X(l_pos, NL * 3) X(l_quat, NL * 4) X(cd_vel, NL * 3) X(cd_ang, NL * 3) X(root_com, NL * 3)     \
-  X(contact_force, NL * 3) X(geom_friction, NG) X(ctrl_pos, ND) X(ctrl_vel, ND) X(dof_pos, ND) \
+  X(qpos, NQ, CARRIED) X(vel, ND, CARRIED) X(ctrl_force, ND, CARRIED) X(ext, NL * 6, CARRIED) X(mass_shift, NL, CARRIED) X(com_shift, NL * 3, CARRIED) \
+  X(friction_ratio, NG, CARRIED) X(l_pos, NL * 3, CARRIED) X(l_quat, NL * 4, CARRIED) X(cd_vel, NL * 3, CARRIED) X(cd_ang, NL * 3, CARRIED) X(root_com, NL * 3, CARRIED) \
+  X(contact_force, NL * 3, CARRIED) X(geom_friction, NG, CARRIED) X(ctrl_pos, ND, CARRIED) X(ctrl_vel, ND, CARRIED) X(dof_pos, ND, CARRIED) \
   /* ---- Go2Env buffers ---- */                                                                                     \
-  X(actions, NA) X(last_actions, NA) X(applied_actions, NA) X(action_history, GO2SIM_ACTION_RING_MAX * NA) X(target_dof_pos, NM)            \
-  X(e_dof_pos, NM) X(e_dof_vel, NM) X(last_dof_vel, NM) X(torque, NM) X(base_pos, 3) X(base_quat, 4) X(base_lin_vel, 3) \
-  X(base_ang_vel, 3) X(projected_gravity, 3) X(base_euler, 3) X(commands, 3) X(time_out, 1) X(kp_factors, NM)          \
-  X(kd_factors, NM) X(motor_strength, NM) X(gravity_offset, 3) X(current_push_force, 3) X(push_stored_force, 3)       \
-  X(feet_air_time, 4) X(base_vel_world, 3) X(last_base_pos_x, 1) X(episode_sums, NREW) X(rew_terms, NREW) X(rew, 1) X(obs, NOBS_MAX) X(priv, NPRIV_MAX) \
-  X(base_kp, 1) X(base_kd, 1) X(ground_height, 1) X(spawn_pos, 3)
+  X(actions, NA, CARRIED) X(last_actions, NA, CARRIED) X(applied_actions, NA, CARRIED) X(action_history, GO2SIM_ACTION_RING_MAX * NA, CARRIED) X(target_dof_pos, NM, CARRIED) \
+  X(e_dof_pos, NM, CARRIED) X(e_dof_vel, NM, CARRIED) X(last_dof_vel, NM, CARRIED) X(torque, NM, CARRIED) X(base_pos, 3, CARRIED) X(base_quat, 4, CARRIED) X(base_lin_vel, 3, CARRIED) \
+  X(base_ang_vel, 3, CARRIED) X(projected_gravity, 3, CARRIED) X(base_euler, 3, CARRIED) X(commands, 3, CARRIED) X(time_out, 1, CARRIED) X(kp_factors, NM, CARRIED) \
+  X(kd_factors, NM, CARRIED) X(motor_strength, NM, CARRIED) X(gravity_offset, 3, CARRIED) X(current_push_force, 3, CARRIED) X(push_stored_force, 3, CARRIED) \
+  X(feet_air_time, 4, CARRIED) X(base_vel_world, 3, CARRIED) X(last_base_pos_x, 1, CARRIED) X(episode_sums, NREW, CARRIED) X(rew_terms, NREW, CARRIED) X(rew, 1, CARRIED) X(obs, NOBS_MAX, CARRIED) X(priv, NPRIV_MAX, CARRIED) \
+  X(base_kp, 1, CARRIED) X(base_kd, 1, CARRIED) X(ground_height, 1, CARRIED) X(spawn_pos, 3, CARRIED)
 
 #define GO2SIM_INT_FIELDS(X)                                                                                         \
-  X(n_contacts, 1) X(n_con, 1) X(err, 1) X(is_warmstart, 1) X(first_time, 1) X(n_broad, 1) X(solver_iters, 1) X(ctrl_mode, ND) \
-  X(gjk_fallback, 1) X(delay_steps, 1) X(episode_length, 1) X(reset_buf, 1) X(push_remaining, 1) X(foot_contact, 4)    \
-  X(last_foot_contact, 4) X(terrain_row, 1) X(terrain_key, 1) X(tile_row, 1) X(tile_col, 1)
+  X(n_contacts, 1, CARRIED) X(n_con, 1, CARRIED) X(err, 1, CARRIED) X(is_warmstart, 1, CARRIED) X(first_time, 1, CARRIED) X(n_broad, 1, CARRIED) X(solver_iters, 1, CARRIED) X(ctrl_mode, ND, CARRIED) \
+  X(gjk_fallback, 1, CARRIED) X(delay_steps, 1, CARRIED) X(episode_length, 1, CARRIED) X(reset_buf, 1, CARRIED) X(push_remaining, 1, CARRIED) X(foot_contact, 4, CARRIED)    \
+  X(last_foot_contact, 4, CARRIED) X(terrain_row, 1, CARRIED) X(terrain_key, 1, CARRIED) X(tile_row, 1, CARRIED) X(tile_col, 1, CARRIED)
 
+// REWRITTEN here: c_friction / c_sol (k_collide_team writes them for every contact below n_contacts; the solver's row build and commit read those and no others; the
+// broad phase's clear leaves them alone) and c_force (written by the solver's commit, zeroed by the clear, read by no kernel).  The other contact
+// arrays and efc_force are written and read the same way, but the field API shows their whole extent, the tails an earlier step left included; so it
+// does mass_mat (GO2SIM_F_MASS_MAT), which tk_dynamics rewrites whole before the solver's staging reads it.
 #define GO2SIM_AOS_FLOAT_FIELDS(X)                                                                                   \
-  X(acc, ND) X(qacc_ws, ND) X(force, ND) X(qf_smooth, ND) X(acc_smooth, ND) X(qfrc_constraint, ND) X(mass_mat, NTRI)  \
-  X(cdof_ang, ND * 3) X(cdof_vel, ND * 3) X(cdofd_ang, ND * 3) X(cdofd_vel, ND * 3) X(cinr_inertial, NL * 9)            \
-  X(cinr_pos, NL * 3) X(cinr_mass, NL) X(i_pos, NL * 3) X(i_quat, NL * 4) X(g_pos, NG * 3) X(g_quat, NG * 4)              \
-  X(sort_value, 2 * NG) X(c_pos, MAXC * 3) X(c_normal, MAXC * 3) X(c_pen, MAXC) X(c_friction, MAXC) X(c_sol, MAXC * 7)    \
-  X(c_force, MAXC * 3) X(efc_force, MAXR) X(normal_cache, NPAIR * 3)
+  X(acc, ND, CARRIED) X(qacc_ws, ND, CARRIED) X(force, ND, CARRIED) X(qf_smooth, ND, CARRIED) X(acc_smooth, ND, CARRIED) X(qfrc_constraint, ND, CARRIED) X(mass_mat, NTRI, CARRIED)  \
+  X(cdof_ang, ND * 3, CARRIED) X(cdof_vel, ND * 3, CARRIED) X(cdofd_ang, ND * 3, CARRIED) X(cdofd_vel, ND * 3, CARRIED) X(cinr_inertial, NL * 9, CARRIED)            \
+  X(cinr_pos, NL * 3, CARRIED) X(cinr_mass, NL, CARRIED) X(i_pos, NL * 3, CARRIED) X(i_quat, NL * 4, CARRIED) X(g_pos, NG * 3, CARRIED) X(g_quat, NG * 4, CARRIED)              \
+  X(sort_value, 2 * NG, CARRIED) X(c_pos, MAXC * 3, CARRIED) X(c_normal, MAXC * 3, CARRIED) X(c_pen, MAXC, CARRIED) X(c_friction, MAXC, REWRITTEN) X(c_sol, MAXC * 7, REWRITTEN)    \
+  X(c_force, MAXC * 3, REWRITTEN) X(efc_force, MAXR, CARRIED) X(normal_cache, NPAIR * 3, CARRIED)
 
 // ncache_valid: one bit per geom pair, set = normal_cache[pair] holds the contact normal of the last narrow phase; clear = the cache entry reads as the
 // zero vector (func_broad_phase / func_convex_convex_contact write zeros there: here they clear a bit of a mask the kernel keeps in LDS)
 constexpr int NCV = (NPAIR + 31) / 32;
-#define GO2SIM_AOS_INT_FIELDS(X) X(sort_ig, 2 * NG) X(broad, MAXB * 2) X(c_geom, 2 * MAXC) X(c_link, 2 * MAXC) X(ncache_valid, NCV)
+// REWRITTEN here: broad (tk_broadphase writes the words below n_broad, k_collide_team behind it uses those; the words it requests beyond them are
+// dropped unread) and c_link (as c_friction: written per contact by k_collide_team, read below n_contacts by the solver, not shown by the field API)
+#define GO2SIM_AOS_INT_FIELDS(X) X(sort_ig, 2 * NG, CARRIED) X(broad, MAXB * 2, REWRITTEN) X(c_geom, 2 * MAXC, CARRIED) X(c_link, 2 * MAXC, REWRITTEN) X(ncache_valid, NCV, CARRIED)
 
 enum FOff : int {
-#define X(n, c) FO_##n##_, FO_##n##_end = FO_##n##_ + (c) - 1,
+#define X(n, c, k) FO_##n##_, FO_##n##_end = FO_##n##_ + (c) - 1,
   GO2SIM_FLOAT_FIELDS(X)
 #undef X
   FO_TOTAL
 };
 enum IOff : int {
-#define X(n, c) IO_##n##_, IO_##n##_end = IO_##n##_ + (c) - 1,
+#define X(n, c, k) IO_##n##_, IO_##n##_end = IO_##n##_ + (c) - 1,
   GO2SIM_INT_FIELDS(X)
 #undef X
   IO_TOTAL
 };
 enum AOff : int {
-#define X(n, c) AO_##n##_, AO_##n##_end = AO_##n##_ + (c) - 1,
+#define X(n, c, k) AO_##n##_, AO_##n##_end = AO_##n##_ + (c) - 1,
   GO2SIM_AOS_FLOAT_FIELDS(X)
 #undef X
   AO_TOTAL
 };
 enum AIOff : int {
-#define X(n, c) AIO_##n##_, AIO_##n##_end = AIO_##n##_ + (c) - 1,
+#define X(n, c, k) AIO_##n##_, AIO_##n##_end = AIO_##n##_ + (c) - 1,
   GO2SIM_AOS_INT_FIELDS(X)
 #undef X
   AIO_TOTAL
@@ -6710,6 +6721,10 @@ struct go2sim {
   int solver_team = 32;                     // lanes per environment in k_constraint_solve_team
   int terrain_solver_team = 64;             // ... on heightfield terrain (96 LDS rows)
   uint32_t step_count = 0; int action_write_idx = 0;
+  bool state_whole = false;                 // GO2SIM_STATE_WHOLE=1: snapshots carry the whole pools, not the carried fields alone (include/go2sim_state.h)
+  uint64_t terrain_digest = 0;              // FNV-1a of the installed heightfield in metres, its shape, cell size and origin; 0 without one
+  uint64_t model_digest = 0;                // FNV-1a of the model blob (include/go2sim_state.h)
+  uint32_t* dverdict = nullptr; uint32_t* hverdict_pinned = nullptr;   // go2sim_state_load: the header's verdict and the record's host scalars
   // timing
   bool timing = false;
   hipEvent_t ev0[TIMING_RING], ev1[TIMING_RING]; int ev_cat[TIMING_RING]; int ev_n = 0; bool ev_created = false;
@@ -6980,10 +6995,18 @@ static void handle_release(go2sim* h) {
   (void)hipFree(h->dglob); (void)hipFree(h->dacc); (void)hipFree(h->derr); (void)hipFree(h->solver_ovf); (void)hipFree(h->gjk_scratch); (void)hipFree(h->lpt);
   (void)hipFree(h->terrain_hf); (void)hipFree(h->terrain_cmax); (void)hipFree(h->dms); (void)hipFree(h->dgk); (void)hipFree(h->didx);
   if (h->herr_pinned) (void)hipHostFree(h->herr_pinned);
+  (void)hipFree(h->dverdict);
+  if (h->hverdict_pinned) (void)hipHostFree(h->hverdict_pinned);
   if (h->ev_errno) (void)hipEventDestroy(h->ev_errno);
   delete h;
 }
 
+constexpr uint64_t FNV64_BASIS = 0xcbf29ce484222325ull;
+static uint64_t fnv1a64(const void* p, size_t n, uint64_t hash) {
+  const unsigned char* b = (const unsigned char*)p;
+  for (size_t k = 0; k < n; ++k) { hash ^= b[k]; hash *= 0x100000001b3ull; }
+  return hash;
+}
 // the GO2SIM_* environment knobs of a handle (README.md); an unset or unaccepted value leaves the default
 static int env_int(const char* name, int unset) { const char* t = getenv(name); return t ? atoi(t) : unset; }
 static void read_knobs(go2sim* h) {
@@ -6999,6 +7022,7 @@ static void read_knobs(go2sim* h) {
   if (env_int("GO2SIM_NO_FUSE_SOLVE", 0)) h->fuse_solve_int = false;
   if (env_int("GO2SIM_NO_LPT", 0)) h->use_lpt = false;
   if (env_int("GO2SIM_COLLIDE_GENERIC", 0)) h->collide_generic = true;
+  if (env_int("GO2SIM_STATE_WHOLE", 0)) h->state_whole = true;
 }
 
 int go2sim_create(const void* blob, size_t nbytes, int n_envs, int device, uint64_t seed, go2sim_t** out) {
@@ -7010,6 +7034,7 @@ int go2sim_create(const void* blob, size_t nbytes, int n_envs, int device, uint6
   if (!h) return GO2SIM_E_NOMEM;
   if (!parse_model(blob, nbytes, h->hm)) { delete h; return GO2SIM_E_BADMODEL; }
   h->B = n_envs; h->device = device; h->seed = seed;
+  h->model_digest = fnv1a64(blob, nbytes, FNV64_BASIS);
   // every failure below releases what was allocated so far (one exit path)
   int rc = GO2SIM_E_OK;
 #define CK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { fprintf(stderr, "go2sim: HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); rc = GO2SIM_E_HIP; goto fail; } } while (0)
@@ -7039,6 +7064,9 @@ int go2sim_create(const void* blob, size_t nbytes, int n_envs, int device, uint6
     CK(hipHostMalloc((void**)&h->herr_pinned, 2 * sizeof(int), hipHostMallocDefault));
     h->herr_pinned[0] = h->herr_pinned[1] = 0;
     CK(hipEventCreateWithFlags(&h->ev_errno, hipEventDisableTiming));
+    CK(hipMalloc((void**)&h->dverdict, 4 * sizeof(uint32_t)));
+    CK(hipMemset(h->dverdict, 0, 4 * sizeof(uint32_t)));
+    CK(hipHostMalloc((void**)&h->hverdict_pinned, 4 * sizeof(uint32_t), hipHostMallocDefault));
     CK(hipMalloc((void**)&h->solver_ovf, (size_t)n_envs * sizeof(SolverData<MAXR>)));
     read_knobs(h);
     CK(hipMalloc((void**)&h->gjk_scratch, (size_t)n_envs * h->collide_team * sizeof(GjkStoreFull)));   // ~20 KB per narrow-phase lane (after GO2SIM_COLLIDE_TEAM)
@@ -7256,6 +7284,10 @@ static int set_terrain_metres(go2sim_t* h, const std::vector<float>& hfm, int ro
   launch_fk_team(h, s, 1, nullptr);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(s));
+  {                                                                     // include/go2sim_state.h: the heightfield is part of the model digest of a snapshot
+    const float geo[4] = {horizontal_scale, origin[0], origin[1], origin[2]}; const int shape[2] = {rows, cols};
+    h->terrain_digest = fnv1a64(hfm.data(), hfm.size() * sizeof(float), fnv1a64(geo, sizeof(geo), fnv1a64(shape, sizeof(shape), FNV64_BASIS)));
+  }
   return GO2SIM_E_OK;
 }
 int go2sim_set_terrain(go2sim_t* h, const int16_t* hf, int rows, int cols, float horizontal_scale, float vertical_scale, const float* origin, void* stream) {
@@ -7687,13 +7719,91 @@ int go2sim_debug_phases(go2sim_t* h, unsigned long long* out64, int reset) {
 #endif
 int go2sim_debug_field(go2sim_t* h, const char* name, void** ptr, int* k, int* is_int) {
   if (!h || !name || !ptr) return GO2SIM_E_BADARG;
-#define X(n, c) if (!strcmp(name, #n)) { *ptr = h->P.f + (size_t)FO(n) * h->B; if (k) *k = (c); if (is_int) *is_int = 0; return GO2SIM_E_OK; }
+#define X(n, c, k_) if (!strcmp(name, #n)) { *ptr = h->P.f + (size_t)FO(n) * h->B; if (k) *k = (c); if (is_int) *is_int = 0; return GO2SIM_E_OK; }
   GO2SIM_FLOAT_FIELDS(X)
 #undef X
-#define X(n, c) if (!strcmp(name, #n)) { *ptr = h->P.i + (size_t)IO(n) * h->B; if (k) *k = (c); if (is_int) *is_int = 1; return GO2SIM_E_OK; }
+#define X(n, c, k_) if (!strcmp(name, #n)) { *ptr = h->P.i + (size_t)IO(n) * h->B; if (k) *k = (c); if (is_int) *is_int = 1; return GO2SIM_E_OK; }
   GO2SIM_INT_FIELDS(X)
 #undef X
   return GO2SIM_E_BADARG;
+}
+// include/go2sim_state.h: the carried state of a handle as csrc/go2sim_state.hip packs it.  The spans come from the flags of the four field tables:
+// rows of the SoA pools (unit = 1 word of a record column), 16-byte chunks of the AoS records (unit = 4 words; a chunk is carried when a word of
+// a carried field lies in it).  `whole` (GO2SIM_STATE_WHOLE=1) carries every unit of the stride.
+struct FieldMark { int off, count, carried; };
+static bool carried_spans(const FieldMark* marks, int n_marks, int stride_words, int unit, bool whole, go2sim_state_spans_t* out) {
+  std::vector<char> keep((size_t)(stride_words / unit), whole ? 1 : 0);
+  for (int k = 0; k < n_marks && !whole; ++k)
+    if (marks[k].carried) for (int u = marks[k].off / unit; u <= (marks[k].off + marks[k].count - 1) / unit; ++u) keep[(size_t)u] = 1;
+  out->n = 0; out->carried = 0;
+  for (int u = 0; u < (int)keep.size(); ++u) {
+    if (!keep[(size_t)u]) continue;
+    if (u == 0 || !keep[(size_t)u - 1]) { if (out->n == GO2SIM_STATE_MAX_SPANS) return false; out->first[out->n] = u; out->count[out->n] = 0; out->n += 1; }
+    out->count[out->n - 1] += 1; out->carried += 1;
+  }
+  return true;
+}
+int go2sim_state_view(go2sim_t* h, go2sim_state_view_t* out) {
+  if (!h || !out) return GO2SIM_E_BADARG;
+  memset(out, 0, sizeof(*out));
+#define X(n, c, k) {FO(n), (c), (k)},
+  static const FieldMark f_marks[] = {GO2SIM_FLOAT_FIELDS(X)};
+#undef X
+#define X(n, c, k) {IO(n), (c), (k)},
+  static const FieldMark i_marks[] = {GO2SIM_INT_FIELDS(X)};
+#undef X
+#define X(n, c, k) {AO(n), (c), (k)},
+  static const FieldMark af_marks[] = {GO2SIM_AOS_FLOAT_FIELDS(X)};
+#undef X
+#define X(n, c, k) {AIO(n), (c), (k)},
+  static const FieldMark ai_marks[] = {GO2SIM_AOS_INT_FIELDS(X)};
+#undef X
+  static_assert(ASTRIDE % 4 == 0 && AISTRIDE % 4 == 0, "AoS records are whole 16-byte chunks");
+  const size_t B = (size_t)h->B;
+  out->device = h->device; out->n_envs = h->B;
+  out->glob = h->dglob; out->glob_bytes = sizeof(Glob); out->acc = h->dacc; out->acc_bytes = sizeof(Acc);
+  void* pool[GO2SIM_STATE_N_POOLS] = {h->P.f, h->P.i, h->P.fa, h->P.ia};
+  const int words[GO2SIM_STATE_N_POOLS] = {FO_TOTAL, IO_TOTAL, ASTRIDE, AISTRIDE}, unit[GO2SIM_STATE_N_POOLS] = {1, 1, 4, 4};
+  const FieldMark* marks[GO2SIM_STATE_N_POOLS] = {f_marks, i_marks, af_marks, ai_marks};
+  const int n_marks[GO2SIM_STATE_N_POOLS] = {(int)(sizeof(f_marks) / sizeof(FieldMark)), (int)(sizeof(i_marks) / sizeof(FieldMark)),
+                                             (int)(sizeof(af_marks) / sizeof(FieldMark)), (int)(sizeof(ai_marks) / sizeof(FieldMark))};
+  size_t total = (size_t)GO2SIM_STATE_HDR_WORDS * 4 + (sizeof(Glob) + 15) / 16 * 16 + (sizeof(Acc) + 15) / 16 * 16;
+  for (int k = 0; k < GO2SIM_STATE_N_POOLS; ++k) {
+    out->pool[k] = pool[k]; out->stride[k] = words[k] / unit[k];
+    if (!carried_spans(marks[k], n_marks[k], words[k], unit[k], h->state_whole, &out->spans[k])) return GO2SIM_E_BADARG;
+    total += ((size_t)out->spans[k].carried * unit[k] * 4 * B + 15) / 16 * 16;
+  }
+  // the one piece of state that lives in the model tables: with the batch gain k_env_engine_gains rewrites the motor dofs' kp / kv after a step with resets
+  static_assert(2 * NM <= GO2SIM_STATE_MAX_GAIN_WORDS, "the gains part holds kp and kv of every motor dof");
+  if (h->cfg_set && h->hcfg.i[GO2SIM_IC_ENGINE_BATCH_GAIN]) {
+    out->n_gain = 2 * NM;
+    for (int k = 0; k < NM; ++k) {
+      const size_t d = (size_t)h->hcfg.i[GO2SIM_IC_MOTOR_DOF0 + k];
+      out->gain_dev[0][2 * k] = (char*)h->dm + offsetof(Model, dofs) + d * sizeof(Dof) + offsetof(Dof, kp);
+      out->gain_dev[0][2 * k + 1] = (char*)h->dm + offsetof(Model, dofs) + d * sizeof(Dof) + offsetof(Dof, kv);
+      out->gain_dev[1][2 * k] = (char*)h->dms + offsetof(ModelS, dofs) + d * sizeof(Dof) + offsetof(Dof, kp);
+      out->gain_dev[1][2 * k + 1] = (char*)h->dms + offsetof(ModelS, dofs) + d * sizeof(Dof) + offsetof(Dof, kv);
+    }
+    total += ((size_t)out->n_gain * 4 + 15) / 16 * 16;
+  }
+  uint64_t cfg_digest = fnv1a64(h->hcfg.d, sizeof(h->hcfg.d), FNV64_BASIS);
+  cfg_digest = fnv1a64(h->hcfg.f, sizeof(h->hcfg.f), cfg_digest);
+  cfg_digest = fnv1a64(h->hcfg.i, sizeof(h->hcfg.i), cfg_digest);
+  uint32_t* w = out->hdr;
+  auto put64 = [&](int at, uint64_t v) { w[at] = (uint32_t)v; w[at + 1] = (uint32_t)(v >> 32); };
+  w[GO2SIM_STATE_W_MAGIC] = GO2SIM_STATE_MAGIC; w[GO2SIM_STATE_W_VERSION] = GO2SIM_STATE_VERSION; w[GO2SIM_STATE_W_N_ENVS] = (uint32_t)h->B;
+  w[GO2SIM_STATE_W_NQ] = NQ; w[GO2SIM_STATE_W_ND] = ND; w[GO2SIM_STATE_W_NL] = NL; w[GO2SIM_STATE_W_NG] = NG; w[GO2SIM_STATE_W_NA] = NA; w[GO2SIM_STATE_W_NM] = NM;
+  w[GO2SIM_STATE_W_NOBS_MAX] = NOBS_MAX; w[GO2SIM_STATE_W_NPRIV_MAX] = NPRIV_MAX; w[GO2SIM_STATE_W_NREW] = NREW;
+  w[GO2SIM_STATE_W_MAX_CONTACTS] = MAXC; w[GO2SIM_STATE_W_MAX_ROWS] = MAXR;
+  w[GO2SIM_STATE_W_F_ROWS] = FO_TOTAL; w[GO2SIM_STATE_W_I_ROWS] = IO_TOTAL; w[GO2SIM_STATE_W_AF_STRIDE] = ASTRIDE; w[GO2SIM_STATE_W_AI_STRIDE] = AISTRIDE;
+  w[GO2SIM_STATE_W_GLOB_BYTES] = (uint32_t)sizeof(Glob); w[GO2SIM_STATE_W_ACC_BYTES] = (uint32_t)sizeof(Acc);
+  for (int k = 0; k < GO2SIM_STATE_N_POOLS; ++k) w[GO2SIM_STATE_W_F_CARRIED + k] = (uint32_t)out->spans[k].carried;
+  put64(GO2SIM_STATE_W_SEED, h->seed); put64(GO2SIM_STATE_W_MODEL_DIGEST, h->hm.terrain_enabled ? fnv1a64(&h->terrain_digest, sizeof(uint64_t), h->model_digest) : h->model_digest); put64(GO2SIM_STATE_W_CFG_DIGEST, cfg_digest);
+  put64(GO2SIM_STATE_W_BYTES, (uint64_t)total);
+  w[GO2SIM_STATE_W_STEP_COUNT] = h->step_count; w[GO2SIM_STATE_W_ACTION_WRITE_IDX] = (uint32_t)h->action_write_idx;
+  out->verdict_dev = h->dverdict; out->verdict_host = h->hverdict_pinned;
+  out->step_count = &h->step_count; out->action_write_idx = &h->action_write_idx;
+  return GO2SIM_E_OK;
 }
 
 }  // extern "C"

@@ -62,11 +62,13 @@ def read_checkpoint(path, map_location="cpu"):
 
 
 def save_checkpoint(path, model_state_dict, optimizer_state_dict=None, it=0, infos=None, *, obs_norm_state_dict=None, critic_obs_norm_state_dict=None,
-                    privileged_obs_norm_state_dict=None, rnd_state_dict=None, rnd_optimizer_state_dict=None):
+                    privileged_obs_norm_state_dict=None, rnd_state_dict=None, rnd_optimizer_state_dict=None, env_state_dict=None,
+                    runner_state_dict=None):
     """``OnPolicyRunner.save`` layout (rsl_rl 2.2.4 runners/on_policy_runner.py).  The two normaliser state dicts are written only when given (rsl_rl writes
     them when ``empirical_normalization`` is on); without them the file has the four keys it always had.  ``privileged_obs_norm_state_dict`` is a
     distillation run's frozen teacher normaliser; ``rnd_state_dict`` / ``rnd_optimizer_state_dict`` are a run with random network distillation's
-    (rnd.py: the two networks and the normalisers; Adam's m, v, step, learning rate and the module's counter)."""
+    (rnd.py: the two networks and the normalisers; Adam's m, v, step, learning rate and the module's counter).  ``env_state_dict`` / ``runner_state_dict``
+    (Go2Env.state_dict(), OnPolicyRunner.runner_state_dict(): CPU tensors and plain numbers) make the file an exact resume point."""
     ckpt = {"model_state_dict": {k: v.detach().cpu() for k, v in model_state_dict.items()},
             "optimizer_state_dict": optimizer_state_dict if optimizer_state_dict is not None else {}, "iter": int(it), "infos": infos}
     for key, sd in (("obs_norm_state_dict", obs_norm_state_dict), ("critic_obs_norm_state_dict", critic_obs_norm_state_dict),
@@ -77,6 +79,10 @@ def save_checkpoint(path, model_state_dict, optimizer_state_dict=None, it=0, inf
         ckpt["rnd_state_dict"] = {k: v.detach().cpu() for k, v in rnd_state_dict.items()}
     if rnd_optimizer_state_dict is not None:
         ckpt["rnd_optimizer_state_dict"] = rnd_optimizer_state_dict
+    if env_state_dict is not None:
+        ckpt["env_state_dict"] = env_state_dict
+    if runner_state_dict is not None:
+        ckpt["runner_state_dict"] = runner_state_dict
     torch.save(ckpt, path)
 
 

@@ -24,7 +24,7 @@ import math
 
 import torch
 
-from .capi import C, EnvGlobals, Go2Sim, Go2SimError, load_hip_lib
+from .capi import C, EnvGlobals, Go2Sim, Go2SimError, load_hip_lib, state_header_mismatch
 from .configs import build_stair_terrain, flatten_base_cfg, flatten_walk_cfg
 from .lidar import LidarScan, check_lidar_widths, env_pose_ptrs, lidar_enabled, lidar_layout
 from .model_blob import pack_model
@@ -149,6 +149,50 @@ def mirror_tables(env_cfg, obs_cfg):
             raise Go2SimError(f"mirror table {key!r} has {len(src)} entries, the layout's width is {width}")
         out[key] = (torch.tensor(src, dtype=torch.int32), torch.tensor(sign, dtype=torch.float32))
     return out
+
+
+ENV_STATE_VERSION = 1
+
+
+def env_state_schema(family, num_envs, num_obs, num_critic_obs, core_bytes=None, lidar_points=None, n_globals=None):
+    """What ``Go2Env.state_dict()`` of such an env holds: {key: int | str | (dtype, shape)}; a shape entry None is not checked.  `family` is one of
+    base, walk, stairs, stairs_lidar, stairs_info, rough, stairwell; `num_critic_obs` the width of the privileged rows as the env keeps them."""
+    B, f32 = int(num_envs), torch.float32
+    schema = {"version": int, "family": str, "num_envs": int, "num_obs": int, "num_critic_obs": int, "terrain_rows_locked": int, "steps_since_poll": int,
+              "core": (torch.uint8, (core_bytes,)), "obs_buf": (f32, (B, int(num_obs))), "privileged_obs_buf": (f32, (B, int(num_critic_obs))),
+              "rew_buf": (f32, (B,)), "reset_buf": (torch.uint8, (B,)), "time_outs": (f32, (B,)),
+              "extras_snapshot": (f32, (None,)), "extras_full_snapshot": (f32, (None,))}
+    if family == "stairs_lidar":
+        schema.update(lidar_step=int, lidar_scan=(f32, (B, lidar_points)))
+    if family == "stairs_info":
+        schema.update(stairinfo_step=int, stairinfo_rows=(f32, (B, NUM_STAIR_INFO)))
+    if family == "stairwell":
+        schema.update(wells_alive_sum=(f32, (B,)), wells_alive_steps=(torch.int32, (B,)), wells_alive_ep=(f32, (B,)), wells_alive_log=(f32, ()))
+    return schema
+
+
+def check_env_state(state, schema, expect):
+    """Go2SimError unless `state` has every key of `schema` with its type, dtype and shape, and its scalars equal `expect` (a dict: version, family,
+    num_envs, num_obs, num_critic_obs).  Nothing is written anywhere: load_state_dict calls this before it touches the env."""
+    if not isinstance(state, dict):
+        raise Go2SimError(f"an env state is a dictionary, got {type(state).__name__}")
+    missing = sorted(k for k in schema if k not in state)
+    if missing:
+        raise Go2SimError(f"the env state lacks the key(s) {missing}")
+    for key, want in expect.items():
+        if state[key] != want:
+            raise Go2SimError(f"the env state was saved with {key} = {state[key]!r}, this env has {key} = {want!r}")
+    for key, kind in schema.items():
+        v = state[key]
+        if isinstance(kind, type):
+            if not isinstance(v, kind) or isinstance(v, bool):
+                raise Go2SimError(f"the env state's {key!r} must be a plain {kind.__name__}, got {type(v).__name__}")
+            continue
+        dtype, shape = kind
+        if not torch.is_tensor(v) or v.dtype != dtype:
+            raise Go2SimError(f"the env state's {key!r} must be a {dtype} tensor, got {getattr(v, 'dtype', type(v).__name__)}")
+        if v.dim() != len(shape) or any(w is not None and int(n) != int(w) for n, w in zip(v.shape, shape)):
+            raise Go2SimError(f"the env state's {key!r} has shape {tuple(v.shape)}, this env's is {tuple('*' if w is None else w for w in shape)}")
 
 
 class Go2Env:
@@ -291,6 +335,7 @@ class Go2Env:
         self.errno_poll_every = int(errno_poll_every)  # env steps between errno polls (simulator.py:267: every 10 substeps)
         self._steps_since_poll = 0
         self._views = {}
+        self._extras_snapshot = self._extras_full_snapshot = None
         self._shared_globals = bool(shared_globals) and not self.is_base_env
         if self._shared_globals:
             # one batch sharded over ranks: the first sync (before the constructor's reset) puts every shard at the single-process starting point -- rank 0's
@@ -349,7 +394,11 @@ class Go2Env:
         """extras["episode"] (go2_env_walk.py:1228-1235) every step, extras["curriculum"] (:674-686) and extras["domain_randomization"]
         (:756,813) every ``errno_poll_every`` steps, from ONE snapshot of the device globals: a single small device copy, no synchronisation;
         the values are 0-dim views of that snapshot (the reference stores python floats obtained with ``.item()``)."""
-        snap = self._glob_f32.clone()
+        self._set_extras(self._glob_f32.clone(), full)
+
+    def _set_extras(self, snap, full):
+        """the extras of one snapshot of the device globals (kept: state_dict() saves the last one and the last full one)"""
+        self._extras_snapshot = snap
         n = len(self._reward_names)
         self.extras["episode"] = dict(zip(self._episode_keys, snap[self._ep_off:self._ep_off + n].unbind(0)))
         if self._wells is not None and self._has_alive:
@@ -359,6 +408,7 @@ class Go2Env:
             self.extras["episode"]["terrain_mean_row"] = rows[self._goff["terrain_row_sum"]].float() / rows[self._goff["last_reset_count"]].clamp(min=1).float()
         if self.is_base_env or not full:
             return
+        self._extras_full_snapshot = snap
         f, i, d = snap, snap.view(torch.int32), snap.view(torch.float64)
         g = self._goff
         self.extras["curriculum"] = {
@@ -452,6 +502,87 @@ class Go2Env:
                 self._log_alive(sel)
         if self.log_extras:
             self._refresh_extras()
+
+    # ---- snapshots (include/go2sim_state.h, ENV_STATE.md) ---------------------------------
+    @property
+    def state_family(self):
+        if self.is_base_env:
+            return "base"
+        if self._lidar is not None:
+            return "stairs_lidar"
+        if self._stairinfo is not None:
+            return "stairs_info"
+        if self._wells is not None:
+            return "stairwell"
+        if self.terrain is not None:
+            return "rough"
+        return "stairs" if self._use_terrain else "walk"
+
+    def _state_schema(self):
+        schema = env_state_schema(self.state_family, self.num_envs, self.num_obs, self.privileged_obs_buf.shape[1], self._sim.state_size(),
+                                  None if self._lidar is None else self._lidar.n_actor)
+        expect = {"version": ENV_STATE_VERSION, "family": self.state_family, "num_envs": self.num_envs, "num_obs": self.num_obs,
+                  "num_critic_obs": int(self.privileged_obs_buf.shape[1])}
+        return schema, expect
+
+    def state_dict(self):
+        """Everything of this env that outlives a step, as CPU tensors and plain numbers (eval_io.read_checkpoint reads them without executing
+        anything): the core's record (go2sim_state_save), the LIDAR / stair-info / wells handles' state, and the env's own tensors -- the rows
+        get_observations() returns, the reset flags and time-outs, the terrain-row lock, the poll cadence and the snapshots behind ``extras``.
+        Static inputs (heightfield, tiles, well centres, model, cfgs, seed) are not state: the caller builds the env from them.  Waits for the stream."""
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rec = torch.empty(self._sim.state_size(), dtype=torch.uint8, device=self.device)
+        self._sim.state_save(rec, stream=stream)
+        _, sd = self._state_schema()
+        sd = dict(sd, terrain_rows_locked=int(self._terrain_rows_locked), steps_since_poll=int(self._steps_since_poll), core=rec.cpu())
+        for key, t in (("obs_buf", self.obs_buf), ("privileged_obs_buf", self.privileged_obs_buf), ("rew_buf", self.rew_buf), ("reset_buf", self.reset_buf),
+                       ("time_outs", self._time_outs), ("extras_snapshot", self._extras_snapshot), ("extras_full_snapshot", self._extras_full_snapshot)):
+            sd[key] = torch.zeros(0) if t is None else t.detach().cpu().clone()
+        if self._lidar is not None:
+            sd.update(lidar_step=int(self._lidar.step_count), lidar_scan=self._lidar.stored_scan())
+        if self._stairinfo is not None:
+            sd.update(stairinfo_step=int(self._stairinfo.step_count), stairinfo_rows=self._stairinfo.stored_rows())
+        if self._wells is not None:
+            alive_sum, alive_steps = self._wells.alive_state()
+            sd.update(wells_alive_sum=alive_sum, wells_alive_steps=alive_steps, wells_alive_ep=self._alive_ep.cpu().clone(), wells_alive_log=self._alive_log.cpu().clone())
+        return sd
+
+    def load_state_dict(self, state):
+        """Put a ``state_dict()`` back into an env built from the same cfgs, num_envs and seed: ``get_observations()`` then returns the saved rows and
+        the next ``step(a)`` returns what the saved env's next ``step(a)`` returned, bit for bit.  The dictionary is validated before anything is
+        written (keys, family, widths, num_envs), and the core compares the record's header with its own (seed, model and configuration digests)
+        before it writes: a Go2SimError names the mismatch and leaves the env as it was."""
+        schema, expect = self._state_schema()
+        check_env_state(state, schema, expect)
+        dev, stream = self.device, torch.cuda.current_stream(self.device).cuda_stream
+        rec = state["core"].to(dev)
+        if self._sim.state_load(rec, stream=stream) != C["GO2SIM_E_OK"]:
+            mine = torch.empty_like(rec)
+            self._sim.state_save(mine, stream=stream)
+            n = 4 * C["GO2SIM_STATE_HDR_WORDS"]
+            names = state_header_mismatch(rec[:n].cpu().view(torch.int32).tolist(), mine[:n].cpu().view(torch.int32).tolist())
+            raise Go2SimError(f"go2sim_state_load refused the record: its {' and '.join(names) or 'header'} differ(s) from this env's "
+                              "(build the env from the cfgs, num_envs and seed the state was saved with)")
+        self.obs_buf, self.privileged_obs_buf = state["obs_buf"].to(dev), state["privileged_obs_buf"].to(dev)
+        self.rew_buf.copy_(state["rew_buf"]); self.reset_buf.copy_(state["reset_buf"]); self._time_outs.copy_(state["time_outs"])
+        self._terrain_rows_locked, self._steps_since_poll = bool(state["terrain_rows_locked"]), int(state["steps_since_poll"])
+        if self._lidar is not None:
+            self._lidar.step_count = state["lidar_step"]
+            self._lidar.set_stored_scan(state["lidar_scan"])
+        if self._stairinfo is not None:
+            self._stairinfo.step_count = state["stairinfo_step"]
+            self._stairinfo.set_stored_rows(state["stairinfo_rows"])
+        if self._wells is not None:
+            self._wells.set_alive_state(state["wells_alive_sum"], state["wells_alive_steps"])
+            self._alive_ep.copy_(state["wells_alive_ep"])
+            self._alive_log = state["wells_alive_log"].to(dev)
+        self.extras = {"observations": {"critic": self.privileged_obs_buf if self.num_privileged_obs else self.obs_buf}, "time_outs": self._time_outs}
+        self._extras_snapshot = self._extras_full_snapshot = None
+        n_glob = self._glob_f32.numel()
+        for key, full in (("extras_full_snapshot", True), ("extras_snapshot", False)):      # the last full one first: the per-step entries come from the later one
+            if state[key].numel() == n_glob:
+                self._set_extras(state[key].to(dev), full)
+        torch.cuda.current_stream(self.device).synchronize()                   # the handles' setters read host copies of the state's tensors
 
     # ---- eval / teleop surface (go2_eval_walk.py, go2_eval_stairs.py) ------------------------------
     @property

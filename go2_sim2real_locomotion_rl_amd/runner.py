@@ -32,6 +32,7 @@ the cfg, the log gains ``rnd_loss``, ``mean_intrinsic_reward``, ``mean_extrinsic
 ``rnd_optimizer_state_dict``.  One rank only.
 """
 import os
+import sys
 
 import torch
 
@@ -78,6 +79,10 @@ class OnPolicyRunner:
         self.save_interval = int(train_cfg.get("save_interval", 0) or 0)
         self.current_learning_iteration = 0
         self._last_means = (0.0, 0.0)
+        self._kind = f"{alg_class}/{pol_class}"                                # what a checkpoint's runner_state_dict must come from
+        self.save_env_state = False                                            # learn()'s own checkpoints: with the env's and the loop's state (save(env_state=True))
+        self._resumed = False                                                  # load() put an env state back: the next learn() re-randomises nothing
+        self._last_rows = self._resume_rows = None                             # the rows the next act reads: as learn() left them / as load() restored them
         self._cur_rew, self._cur_len = torch.zeros(env.num_envs, device=self.device), torch.zeros(env.num_envs, device=self.device)
         self.obs_normalizer = self.critic_obs_normalizer = self.privileged_obs_normalizer = None
         self.rnd = None
@@ -173,10 +178,16 @@ class OnPolicyRunner:
         env, alg, dev = self.env, self.alg, self.device
         if self.distill and not self.policy.loaded_teacher:
             raise Go2SimError("learn(): no teacher has been loaded; load a PPO checkpoint (the teacher) or a distillation checkpoint with runner.load(path) first")
-        if init_at_random_ep_len:
-            env.episode_length_buf = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
-        obs, extras = env.get_observations()
-        rows = self._rows(obs, extras["observations"], update=False)          # the starting observations: current statistics, not counted
+        resumed, self._resumed = self._resumed, False
+        if self._resume_rows is not None:
+            # a checkpoint with the env's state was loaded: the episode lengths, the observations and the rows the interrupted loop was about to act on
+            # are the saved ones; nothing the state carries is read again or drawn again
+            rows, self._resume_rows = self._resume_rows, None
+        else:
+            if init_at_random_ep_len and not resumed:
+                env.episode_length_buf = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))
+            obs, extras = env.get_observations()
+            rows = self._rows(obs, extras["observations"], update=False)      # the starting observations: current statistics, not counted
         log = []
         start = self.current_learning_iteration
         for it in range(start, start + num_learning_iterations):
@@ -205,6 +216,7 @@ class OnPolicyRunner:
             if n > 0:
                 self._last_means = (rs / n, ls / n)
             self.current_learning_iteration = it + 1
+            self._last_rows = rows
             log.append({"iteration": it, "mean_reward": self._last_means[0], "mean_episode_length": self._last_means[1],
                         **dict(zip(alg.result_names, results if isinstance(results, tuple) else (results,))), "learning_rate": alg.learning_rate})
             if alg.symmetry is not None:
@@ -212,9 +224,9 @@ class OnPolicyRunner:
             if self.rnd is not None:
                 log[-1].update(mean_intrinsic_reward=self._last_rnd_means[0], mean_extrinsic_reward=self._last_rnd_means[1], rnd_weight=self.rnd.weight)
             if self.log_dir is not None and self.save_interval > 0 and (it + 1) % self.save_interval == 0:
-                self.save(os.path.join(self.log_dir, f"model_{it + 1}.pt"))
+                self.save(os.path.join(self.log_dir, f"model_{it + 1}.pt"), env_state=self.save_env_state)
         if self.log_dir is not None:
-            self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
+            self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"), env_state=self.save_env_state)
         return log
 
     def _count_episodes(self, acc, rewards, dones):
@@ -287,9 +299,56 @@ class OnPolicyRunner:
             self.rnd.load_state_dict(ckpt["rnd_state_dict"])
         return True
 
-    def save(self, path, infos=None):
+    # ---- the collection loop's own state (checkpoints with env_state) ---------------------------------------------
+    def _memories(self):
+        """the policy's memory states that exist and have stepped (module_core.MemoryState)"""
+        return [(k, st) for k, st in enumerate(getattr(self.policy, "_hid", ())) if st is not None and st.B > 0]
+
+    def runner_state_dict(self):
+        """What the collection loop carries from one iteration to the next, as CPU tensors and plain numbers: the rows the next act reads, the running
+        episodes' sums behind mean_reward / mean_episode_length (and RND's pair), the last means, and every memory's (h, c) as the next step enters it."""
+        cpu = lambda t: t.detach().cpu().clone()
+        sd = {"kind": self._kind, "num_envs": int(self.env.num_envs), "cur_rew": cpu(self._cur_rew), "cur_len": cpu(self._cur_len),
+              "last_means": [float(v) for v in self._last_means]}
+        if self._last_rows is not None:
+            sd["rows"] = [cpu(r) for r in self._last_rows]
+        if self.rnd is not None:
+            sd.update(cur_int=cpu(self._cur_int), cur_ext=cpu(self._cur_ext), last_rnd_means=[float(v) for v in self._last_rnd_means])
+        for k, st in self._memories():
+            h, c = torch.empty_like(st.h), torch.empty_like(st.c)
+            st.copy_entering(h, c)
+            sd[f"memory_{k}_h"], sd[f"memory_{k}_c"] = h.cpu(), c.cpu()
+        return sd
+
+    def load_runner_state_dict(self, sd):
+        """puts back a runner_state_dict() of a runner of this kind and size (runner_state_matches)"""
+        if not self.runner_state_matches(sd):
+            raise Go2SimError(f"the runner state was saved by a {sd.get('kind')!r} runner with {sd.get('num_envs')} envs, this one is {self._kind!r} with {self.env.num_envs}")
+        dev = self.device
+        self._cur_rew.copy_(sd["cur_rew"]); self._cur_len.copy_(sd["cur_len"])
+        self._last_means = tuple(float(v) for v in sd["last_means"])
+        if self.rnd is not None:
+            self._cur_int.copy_(sd["cur_int"]); self._cur_ext.copy_(sd["cur_ext"])
+            self._last_rnd_means = tuple(float(v) for v in sd["last_rnd_means"])
+        for k, st in enumerate(getattr(self.policy, "_hid", ())):
+            if st is not None and f"memory_{k}_h" in sd:
+                h = sd[f"memory_{k}_h"].to(dev)
+                st.rows(h.shape[0])
+                st.zero()                                                      # (drops a pending mask: the saved state is the entering one)
+                st.h.copy_(h); st.c.copy_(sd[f"memory_{k}_c"].to(dev))
+        self._resume_rows = self._last_rows = tuple(r.to(dev) for r in sd["rows"]) if "rows" in sd else None
+        self._resumed = True
+
+    def runner_state_matches(self, sd):
+        return sd.get("kind") == self._kind and int(sd.get("num_envs", -1)) == int(self.env.num_envs)
+
+    def save(self, path, infos=None, env_state=False):
         """rsl_rl 2.2.4 checkpoint layout (eval_io.read_checkpoint): model_state_dict, optimizer_state_dict (Adam's m, v, step, learning rate), iter, infos,
-        and the state of the normalisers that exist."""
+        and the state of the normalisers that exist.  With `env_state` two more keys make the file an exact resume point: ``env_state_dict``
+        (Go2Env.state_dict()) and ``runner_state_dict`` (runner_state_dict()).  One rank only: each rank of a group owns its shard of the envs."""
+        if env_state and self.group is not None:
+            raise Go2SimError("save(env_state=True) over a multi-rank group is not implemented: each rank owns its shard of the envs "
+                              "(per-rank env-state sidecar files are a follow-up)")
         if self.rank != 0:                                                     # the ranks hold the same bits: rank 0 writes them
             return
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -298,7 +357,8 @@ class OnPolicyRunner:
         norm_state = lambda normalizer: None if normalizer is None else normalizer.state_dict()
         save_checkpoint(path, self.policy.state_dict(), opt, self.current_learning_iteration, infos, obs_norm_state_dict=norm_state(self.obs_normalizer),
                         critic_obs_norm_state_dict=norm_state(self.critic_obs_normalizer), privileged_obs_norm_state_dict=norm_state(self.privileged_obs_normalizer),
-                        rnd_state_dict=norm_state(self.rnd), rnd_optimizer_state_dict=None if self.rnd is None else self.rnd.optimizer_state_dict())
+                        rnd_state_dict=norm_state(self.rnd), rnd_optimizer_state_dict=None if self.rnd is None else self.rnd.optimizer_state_dict(),
+                        env_state_dict=self.env.state_dict() if env_state else None, runner_state_dict=self.runner_state_dict() if env_state else None)
 
     def load(self, path, load_optimizer=True):
         """A checkpoint of this runner's own kind resumes the run: model, normalisers, optimizer, the policy's noise step, iteration.  A distillation runner
@@ -312,6 +372,20 @@ class OnPolicyRunner:
                 if self.rnd is not None:
                     self.rnd.load_optimizer_state_dict(ckpt["rnd_optimizer_state_dict"])
             self.current_learning_iteration = int(ckpt.get("iter", 0) or 0)
+            ignored = None
+            # an exact resume point, taken when it comes from a runner of this kind: the env's state first (it validates before it writes), then the loop's
+            if ckpt.get("env_state_dict") is not None and ckpt.get("runner_state_dict") is not None and self.group is None:
+                if self.runner_state_matches(ckpt["runner_state_dict"]):
+                    self.env.load_state_dict(ckpt["env_state_dict"])
+                    self.load_runner_state_dict(ckpt["runner_state_dict"])
+                else:
+                    ignored = (f"it was saved by a {ckpt['runner_state_dict'].get('kind')!r} runner with {ckpt['runner_state_dict'].get('num_envs')} envs, "
+                               f"this one is {self._kind!r} with {self.env.num_envs}")
+            elif ckpt.get("env_state_dict") is not None and self.group is not None:
+                ignored = "this runner is one rank of a group, and each rank owns its shard of the envs"
+            if ignored:
+                print(f"OnPolicyRunner.load: {path} carries an env state that is NOT restored ({ignored}); training continues in front of this env as it is, "
+                      "curriculum and episode counters included", file=sys.stderr, flush=True)
         return ckpt.get("infos")
 
     def get_inference_policy(self, device=None):

@@ -92,7 +92,10 @@ def main():
     ap.add_argument("--rnd-reward-normalization", action="store_true", help="divide the bonus by the running std of its discounted sum")
     ap.add_argument("--rnd-schedule", default=None, metavar="linear:a:b:v", help="weight_schedule of --rnd-weight: linear:initial_step:final_step:final_value or step:final_step:final_value")
     ap.add_argument("--rnd-obs", choices=("policy", "critic"), default="policy", help="the env observation group the two RND networks embed (obs_groups['rnd_state'])")
-    ap.add_argument("--resume", default=None, help="checkpoint to load on every rank before training")
+    ap.add_argument("--resume", default=None, help="checkpoint to load on every rank before training; one written with --save-env-state continues "
+                                                   "the interrupted run exactly (env, curriculum, episode sums, memories)")
+    ap.add_argument("--save-env-state", action="store_true",
+                    help="the checkpoints also carry the env's and the collection loop's state (OnPolicyRunner.save(env_state=True)); one rank")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/train.py needs a ROCm GPU (the product has no CPU fallback)")
@@ -174,6 +177,10 @@ def main():
                     cfg["policy"]["teacher_rnn_hidden_dim"] = int(sd["memory_a.rnn.weight_hh_l0"].shape[1])
             cfg["obs_groups"] = {"teacher": args.teacher_obs}
         runner = OnPolicyRunner(env, cfg, log_dir=args.log_dir, device=device)      # picks up the default process group
+        if args.save_env_state:
+            if world > 1:
+                raise SystemExit("--save-env-state runs on one rank: each rank owns its shard of the envs")
+            runner.save_env_state = True
         if args.distill:
             runner.load(args.distill)                                               # the teacher (and its normaliser, if the checkpoint has one)
         if args.resume:
