@@ -21,6 +21,7 @@ HIP_HDR_TILES = os.path.join(_HERE, "csrc", "go2sim_tiles_dev.h")           # th
 HIP_SRC_WELLS = os.path.join(_HERE, "csrc", "go2sim_wells.hip")             # the stairwell env's scan handle (include/go2sim_wells.h): product library only
 HIP_HDR_WELLS = os.path.join(_HERE, "csrc", "go2sim_wells_dev.h")           # the stairwell env's device functions go2sim.hip and go2sim_wells.hip share
 HIP_SRC_STATE = os.path.join(_HERE, "csrc", "go2sim_state.hip")             # env snapshots: save, load (include/go2sim_state.h): product library only
+HIP_SRC_CTERMS = os.path.join(_HERE, "csrc", "go2sim_cterms.hip")           # the contact terms body_contact and stumble (include/go2sim_cterms.h): product library only
 HIP_HDR_GJK = os.path.join(_HERE, "csrc", "go2sim_gjk_dev.h")
 HIP_HDR_MLP = os.path.join(_HERE, "csrc", "go2sim_mlp_dev.h")               # shared by go2sim_policy.hip and go2sim_train.hip
 HIP_HDR_LSTM = os.path.join(_HERE, "csrc", "go2sim_lstm_dev.h")             # the recurrent policy's kernels (include/go2sim_rnn.h), included by go2sim_train.hip
@@ -54,11 +55,11 @@ def _headers():
 
 
 def build_hip(force=False, verbose=True):
-    if not force and _newer(HIP_LIB, HIP_SRC, HIP_SRC_POLICY, HIP_SRC_TRAIN, HIP_SRC_NORM, HIP_SRC_LIDAR, HIP_SRC_STAIRINFO, HIP_SRC_DISTILL, HIP_SRC_RDISTILL, HIP_SRC_RND, HIP_SRC_TILES, HIP_HDR_TILES, HIP_SRC_WELLS, HIP_HDR_WELLS, HIP_SRC_STATE, HIP_HDR_GJK, HIP_HDR_MLP, HIP_HDR_LSTM, HIP_HDR_TRAIN, HIP_HDR_TRAINER,
+    if not force and _newer(HIP_LIB, HIP_SRC, HIP_SRC_POLICY, HIP_SRC_TRAIN, HIP_SRC_NORM, HIP_SRC_LIDAR, HIP_SRC_STAIRINFO, HIP_SRC_DISTILL, HIP_SRC_RDISTILL, HIP_SRC_RND, HIP_SRC_TILES, HIP_HDR_TILES, HIP_SRC_WELLS, HIP_HDR_WELLS, HIP_SRC_STATE, HIP_SRC_CTERMS, HIP_HDR_GJK, HIP_HDR_MLP, HIP_HDR_LSTM, HIP_HDR_TRAIN, HIP_HDR_TRAINER,
                             HIP_HDR_DISTILL, HIP_HDR_NORM, *_headers()):
         return HIP_LIB
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    cmd = [hipcc, *HIP_FLAGS, HIP_SRC, HIP_SRC_POLICY, HIP_SRC_TRAIN, HIP_SRC_NORM, HIP_SRC_LIDAR, HIP_SRC_STAIRINFO, HIP_SRC_DISTILL, HIP_SRC_RDISTILL, HIP_SRC_RND, HIP_SRC_TILES, HIP_SRC_WELLS, HIP_SRC_STATE, "-o", HIP_LIB]
+    cmd = [hipcc, *HIP_FLAGS, HIP_SRC, HIP_SRC_POLICY, HIP_SRC_TRAIN, HIP_SRC_NORM, HIP_SRC_LIDAR, HIP_SRC_STAIRINFO, HIP_SRC_DISTILL, HIP_SRC_RDISTILL, HIP_SRC_RND, HIP_SRC_TILES, HIP_SRC_WELLS, HIP_SRC_STATE, HIP_SRC_CTERMS, "-o", HIP_LIB]
     if verbose:
         print("[build]", " ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)

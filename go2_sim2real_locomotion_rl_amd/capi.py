@@ -70,6 +70,7 @@ RND_HEADER, DECLARED_RND_FUNCS = _product_header("rnd")                        #
 TILES_HEADER, DECLARED_TILES_FUNCS = _product_header("tiles")                  # the rough-terrain walk env: float heightfield, ground query
 WELLS_HEADER, DECLARED_WELLS_FUNCS = _product_header("wells")                  # the stairwell env: 11 x 11 scan, alive term
 STATE_HEADER, DECLARED_STATE_FUNCS = _product_header("state")                  # env snapshots: the record's size, save, load
+CTERMS_HEADER, DECLARED_CTERMS_FUNCS = _product_header("cterms")                # the contact terms: body_contact, stumble
 RNG_HEADER, _ = _product_header("rng", [])                                     # the purposes of the random stream (constants only; both libraries)
 # train_cfg["policy"]["activation"] as rsl_rl's resolve_nn_activation spells it -> GO2SIM_ACT_*
 ACTIVATIONS = {n: C["GO2SIM_ACT_" + n.upper()] for n in ("elu", "selu", "relu", "lrelu", "tanh", "sigmoid", "identity")}

@@ -24,6 +24,8 @@ REWARD_IDS = {
     "stand_still": "GO2SIM_R_STAND_STILL", "stand_still_vel": "GO2SIM_R_STAND_STILL_VEL", "feet_stance": "GO2SIM_R_FEET_STANCE",
     "orientation_roll_only": "GO2SIM_R_ORIENTATION_ROLL_ONLY", "forward_progress": "GO2SIM_R_FORWARD_PROGRESS",   # go2_env_stair.py
 }
+# the reward terms of the contact-terms launch (include/go2sim_cterms.h), in the order it applies them: not core terms
+CONTACT_TERM_NAMES = ("body_contact", "stumble")
 
 
 def get_walk_cfgs(pls_enable=True):
@@ -159,6 +161,7 @@ def flatten_walk_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg, *, mod
     names = list(reward_cfg["reward_scales"].keys())
     if is_well_terrain_cfg(env_cfg.get("terrain")) and "alive" in names:
         names.remove("alive")                                # the stairwell env's alive term is the wells launch's (include/go2sim_wells.h), not a core term
+    names = [n for n in names if n not in CONTACT_TERM_NAMES]  # body_contact and stumble are the contact-terms launch's (include/go2sim_cterms.h)
     assert len(names) <= 32
     for k, name in enumerate(names):
         if name not in REWARD_IDS:
@@ -623,17 +626,25 @@ def get_stair_info_terrain_cfg():
             "flat_before_m": 2.0, "flat_top_m": 1.5, "flat_gap_m": 1.5, "flat_after_m": 2.0}
 
 
-def get_stair_info_cfgs(pls_enable=True, stair_info=None):
+def get_stair_info_cfgs(pls_enable=True, stair_info=None, script_values=False):
     """The stair configuration with the four-value stair info of go2_stair_train_lidar_2.py: its `stair_info` block (or `stair_info`), its terrain
     block (a tread depth per row; no height scan) and its widths (:318-327): 49 + 4 = 53 actor inputs, 53 + 55 + terrain row + 4 = 113 critic
-    inputs (49 / 109 with `pls_enable` off).  Every other value is get_stair_cfgs(): the step kernels are pinned to go2_env_stair.py with those
-    values, and DESIGN.md "Stair info" lists where that script's own values differ."""
+    inputs (49 / 109 with `pls_enable` off).  By default every other value is get_stair_cfgs(): the step kernels are pinned to go2_env_stair.py
+    with those values, and DESIGN.md "Stair info" lists where that script's own values differ.  `script_values` takes those over as well --
+    curriculum level_init 0.2, feet_height_target 0.15, and the front-thigh contact penalty (`body_contact_names`, `body_contact_threshold`,
+    reward `body_contact` -2.0, last in the dictionary as in the script: include/go2sim_cterms.h) -- and so gives the script's own dictionaries
+    (tests/golden/ref_cfgs_stair_info.json)."""
     from .stairinfo import stair_info_widths
 
     env_cfg, obs_cfg, reward_cfg, command_cfg = get_stair_cfgs(pls_enable)
     env_cfg["stair_info"] = copy.deepcopy(stair_info) if stair_info is not None else get_stair_info_cfg()
     env_cfg["terrain"] = get_stair_info_terrain_cfg()
     _, obs_cfg["num_obs"], obs_cfg["num_privileged_obs"] = stair_info_widths(env_cfg)
+    if script_values:
+        env_cfg["curriculum"]["level_init"] = 0.2
+        env_cfg.update({"body_contact_names": ["FR_thigh", "FL_thigh"], "body_contact_threshold": 1.0})
+        reward_cfg["feet_height_target"] = 0.15
+        reward_cfg["reward_scales"]["body_contact"] = -2.0
     return env_cfg, obs_cfg, reward_cfg, command_cfg
 
 

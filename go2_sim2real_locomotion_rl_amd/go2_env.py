@@ -25,7 +25,8 @@ import math
 import torch
 
 from .capi import C, EnvGlobals, Go2Sim, Go2SimError, load_hip_lib, state_header_mismatch
-from .configs import build_stair_terrain, flatten_base_cfg, flatten_walk_cfg
+from .configs import CONTACT_TERM_NAMES, build_stair_terrain, flatten_base_cfg, flatten_walk_cfg
+from .contact_terms import DEFAULT_BODY_CONTACT_NAMES, ContactTerms, contact_term_scales, resolve_body_links
 from .lidar import LidarScan, check_lidar_widths, env_pose_ptrs, lidar_enabled, lidar_layout
 from .model_blob import pack_model
 from .stairinfo import NUM_STAIR_INFO, StairInfo, check_one_exteroceptive_layout, check_stair_info_widths, env_rows_ptr, stair_info_enabled
@@ -154,9 +155,10 @@ def mirror_tables(env_cfg, obs_cfg):
 ENV_STATE_VERSION = 1
 
 
-def env_state_schema(family, num_envs, num_obs, num_critic_obs, core_bytes=None, lidar_points=None, n_globals=None):
+def env_state_schema(family, num_envs, num_obs, num_critic_obs, core_bytes=None, lidar_points=None, n_globals=None, cterms=False):
     """What ``Go2Env.state_dict()`` of such an env holds: {key: int | str | (dtype, shape)}; a shape entry None is not checked.  `family` is one of
-    base, walk, stairs, stairs_lidar, stairs_info, rough, stairwell; `num_critic_obs` the width of the privileged rows as the env keeps them."""
+    base, walk, stairs, stairs_lidar, stairs_info, rough, stairwell; `num_critic_obs` the width of the privileged rows as the env keeps them;
+    `cterms`: the env runs the contact-terms launch (a non-zero body_contact or stumble scale)."""
     B, f32 = int(num_envs), torch.float32
     schema = {"version": int, "family": str, "num_envs": int, "num_obs": int, "num_critic_obs": int, "terrain_rows_locked": int, "steps_since_poll": int,
               "core": (torch.uint8, (core_bytes,)), "obs_buf": (f32, (B, int(num_obs))), "privileged_obs_buf": (f32, (B, int(num_critic_obs))),
@@ -168,6 +170,9 @@ def env_state_schema(family, num_envs, num_obs, num_critic_obs, core_bytes=None,
         schema.update(stairinfo_step=int, stairinfo_rows=(f32, (B, NUM_STAIR_INFO)))
     if family == "stairwell":
         schema.update(wells_alive_sum=(f32, (B,)), wells_alive_steps=(torch.int32, (B,)), wells_alive_ep=(f32, (B,)), wells_alive_log=(f32, ()))
+    if cterms:                                                          # body_contact, then stumble (include/go2sim_cterms.h)
+        schema.update(cterms_sum=(f32, (2, B)), cterms_steps=(torch.int32, (2, B)), cterms_ep=(f32, (2, B)), cterms_log=(f32, (2,)),
+                      cterms_count=(f32, (B,)))
     return schema
 
 
@@ -206,6 +211,9 @@ class Go2Env:
             raise Go2SimError("the stairwell terrain has its own 11 x 11 scan: it does not combine with env_cfg['lidar'] or env_cfg['stair_info']")
         if use_wells:
             check_well_widths(env_cfg, obs_cfg)                             # (before anything touches the device)
+        cterm_scales = (0.0, 0.0) if is_base_env_cfg(env_cfg, obs_cfg) else contact_term_scales(reward_cfg)
+        if any(cterm_scales):                                               # an unknown link name is refused; the reference warns and drops the term
+            cterm_body_links = resolve_body_links(env_cfg.get("body_contact_names", list(DEFAULT_BODY_CONTACT_NAMES)))
         self.device = device if device is not None else (_DEVICE if _DEVICE is not None else init())
         self.num_envs = num_envs
         self.num_obs = obs_cfg["num_obs"]
@@ -229,6 +237,7 @@ class Go2Env:
         self._lidar = None
         self._stairinfo = None
         self._wells = None
+        self._cterms = None
         self.terrain = None                                                # the TerrainManager of the rough-terrain env
         if self.is_base_env:
             fcfg, icfg, self._reward_names = flatten_base_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg)
@@ -300,6 +309,18 @@ class Go2Env:
         self._sim.env_configure(fcfg, icfg)
 
         B, dev = num_envs, self.device
+        if any(cterm_scales):
+            # body_contact (go2_env_stair_lidar_2.py) and stumble (go2_env_terrain.py): one launch after the step's own reads the links' contact forces
+            # where the solve left them and adds both terms (include/go2sim_cterms.h)
+            self._cterms = ContactTerms(B, body_links=cterm_body_links, body_contact_scale=cterm_scales[0], stumble_scale=cterm_scales[1],
+                                        body_contact_threshold=float(env_cfg.get("body_contact_threshold", 1.0)),
+                                        stumble_threshold=float(reward_cfg.get("stumble_threshold", 5.0)), dt=self.dt, device=dev)
+            self._cterms_cf = self._sim.field_ptr(C["GO2SIM_F_CONTACT_FORCE"])   # SoA [link * 3 + comp][B]
+            self._cterms_ep = _as_device_tensor(self._cterms.ep_ptrs[0], (2, B), torch.float32, dev)   # per-env records of the last finished episode, one row per term
+            self._cterms_log = torch.zeros(2, device=dev)                   # the logged means, body_contact then stumble
+        self._cterm_keys = [] if self.is_base_env else [n for n in CONTACT_TERM_NAMES if n in self.reward_scales]
+        self._cterm_zero = torch.zeros((), device=dev)
+        self.body_contact_count = torch.zeros(B, device=dev)               # links of body_contact_names in contact at the last step, per env
         if self._lidar is not None or self._stairinfo is not None:
             # the step kernels' rows, rewritten every step, and what the scan launch reads in place: the base pose buffers and the curriculum level
             self._inner_obs = torch.zeros(B, self._lidar_n_in, device=dev)
@@ -378,6 +399,11 @@ class Go2Env:
             pos, quat, cs = self._lidar_pose
             self._lidar.step(pos, (cs, 1), quat, (cs, 1), self.reset_buf, self._lidar_level, self._inner_obs, self._inner_priv, self._lidar_n_in,
                              self.obs_buf, self.privileged_obs_buf)
+        if self._cterms is not None:                                       # one more launch: body_contact and stumble, after the alive term
+            n = self.num_envs
+            self._cterms.step(self._cterms_cf, (n, 3 * n, 1), self.reset_buf, self.rew_buf, self.body_contact_count)
+            if self.log_extras:
+                self._log_cterms(self.reset_buf)
         self._steps_since_poll += 1
         poll = self._steps_since_poll >= self.errno_poll_every             # RATE_CHECK_ERRNO = 10 substeps, simulator.py:45,267
         if poll:
@@ -403,6 +429,9 @@ class Go2Env:
         self.extras["episode"] = dict(zip(self._episode_keys, snap[self._ep_off:self._ep_off + n].unbind(0)))
         if self._wells is not None and self._has_alive:
             self.extras["episode"]["rew_alive"] = self._alive_log
+        for name in self._cterm_keys:                                       # a zero scale: the key is accepted, nothing runs, the entry is zero
+            t = CONTACT_TERM_NAMES.index(name)
+            self.extras["episode"]["rew_" + name] = self._cterms_log[t] if self._cterms is not None and self._cterms.active[t] else self._cterm_zero
         if self._use_terrain:
             rows = snap.view(torch.int32)
             self.extras["episode"]["terrain_mean_row"] = rows[self._goff["terrain_row_sum"]].float() / rows[self._goff["last_reset_count"]].clamp(min=1).float()
@@ -432,6 +461,14 @@ class Go2Env:
         m = mask.to(torch.float32)
         n = m.sum()
         self._alive_log = torch.where(n > 0, (self._alive_ep * m).sum() / n.clamp(min=1.0), self._alive_log)
+
+    def _log_cterms(self, mask):
+        """extras["episode"]["rew_body_contact"] / ["rew_stumble"], as _log_alive reports rew_alive: the means of the launch's ep records over the envs
+        of the last reset; kept while no env is reset.  Device arithmetic, no synchronisation."""
+        m = mask.to(torch.float32)
+        n = m.sum()
+        means = (self._cterms_ep * m).sum(1) / n.clamp(min=1.0)
+        self._cterms_log = torch.where(n > 0, means, self._cterms_log)
 
     def _dr_level_of(self, level):
         """_get_dr_level (go2_env_stair_lidar_2.py) of the curriculum level, a 0-dim float64 device tensor: no synchronisation."""
@@ -479,6 +516,10 @@ class Go2Env:
             self._wells.clear()
             if self.log_extras and self._has_alive:
                 self._log_alive(self.reset_buf)
+        if self._cterms is not None:
+            self._cterms.clear()
+            if self.log_extras:
+                self._log_cterms(self.reset_buf)
         if self.log_extras:
             self._refresh_extras()
         return self.obs_buf, None
@@ -500,6 +541,12 @@ class Go2Env:
                 sel = torch.zeros(self.num_envs, device=self.device)
                 sel[idx.long()] = 1.0
                 self._log_alive(sel)
+        if self._cterms is not None:
+            self._cterms.clear(idx)
+            if self.log_extras:
+                sel = torch.zeros(self.num_envs, device=self.device)
+                sel[idx.long()] = 1.0
+                self._log_cterms(sel)
         if self.log_extras:
             self._refresh_extras()
 
@@ -520,7 +567,7 @@ class Go2Env:
 
     def _state_schema(self):
         schema = env_state_schema(self.state_family, self.num_envs, self.num_obs, self.privileged_obs_buf.shape[1], self._sim.state_size(),
-                                  None if self._lidar is None else self._lidar.n_actor)
+                                  None if self._lidar is None else self._lidar.n_actor, cterms=self._cterms is not None)
         expect = {"version": ENV_STATE_VERSION, "family": self.state_family, "num_envs": self.num_envs, "num_obs": self.num_obs,
                   "num_critic_obs": int(self.privileged_obs_buf.shape[1])}
         return schema, expect
@@ -545,6 +592,10 @@ class Go2Env:
         if self._wells is not None:
             alive_sum, alive_steps = self._wells.alive_state()
             sd.update(wells_alive_sum=alive_sum, wells_alive_steps=alive_steps, wells_alive_ep=self._alive_ep.cpu().clone(), wells_alive_log=self._alive_log.cpu().clone())
+        if self._cterms is not None:
+            sums, steps, ep = self._cterms.state()
+            sd.update(cterms_sum=sums, cterms_steps=steps, cterms_ep=ep, cterms_log=self._cterms_log.cpu().clone(),
+                      cterms_count=self.body_contact_count.cpu().clone())
         return sd
 
     def load_state_dict(self, state):
@@ -576,6 +627,10 @@ class Go2Env:
             self._wells.set_alive_state(state["wells_alive_sum"], state["wells_alive_steps"])
             self._alive_ep.copy_(state["wells_alive_ep"])
             self._alive_log = state["wells_alive_log"].to(dev)
+        if self._cterms is not None:
+            self._cterms.set_state(state["cterms_sum"], state["cterms_steps"], state["cterms_ep"])
+            self._cterms_log = state["cterms_log"].to(dev)
+            self.body_contact_count.copy_(state["cterms_count"])
         self.extras = {"observations": {"critic": self.privileged_obs_buf if self.num_privileged_obs else self.obs_buf}, "time_outs": self._time_outs}
         self._extras_snapshot = self._extras_full_snapshot = None
         n_glob = self._glob_f32.numel()
@@ -613,6 +668,8 @@ class Go2Env:
             self._stairinfo.clear(idx)
         if self._wells is not None and clear_buffers and idx.numel():
             self._wells.clear(idx)
+        if self._cterms is not None and clear_buffers and idx.numel():
+            self._cterms.clear(idx)
 
     def respawn_at_start(self, envs_idx=(0,)):
         """go2_eval_stairs.py:314-361: back to the spawn point of the env's terrain row (or base_init_pos on flat ground)."""

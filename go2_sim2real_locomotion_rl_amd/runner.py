@@ -8,7 +8,8 @@
 
 No TensorBoard: ``learn`` returns one dictionary per iteration.  The reward / episode-length means are taken over the episodes that ended
 during the iteration (the reference averages its last 100 finished episodes); they are counted on the device and read once per iteration,
-after the update's own read of its statistics.
+after the update's own read of its statistics.  The env's ``extras["episode"]`` means of the iteration's last step (``rew_<term>``, rsl_rl's
+"Episode/rew_<term>") ride in the same entry, read in one stacked copy.
 
 Under ``torchrun`` every rank builds its shard of the envs (``Go2Env(n_local, ..., shared_globals=True)``) and a runner; the runners train one policy
 (ppo.PPO with the process group): rank 0's initial weights, per-rank noise and permutation streams, one curriculum, gradients summed in rank order,
@@ -219,6 +220,10 @@ class OnPolicyRunner:
             self._last_rows = rows
             log.append({"iteration": it, "mean_reward": self._last_means[0], "mean_episode_length": self._last_means[1],
                         **dict(zip(alg.result_names, results if isinstance(results, tuple) else (results,))), "learning_rate": alg.learning_rate})
+            episode = infos.get("episode") if isinstance(infos, dict) else None
+            if episode:                                                        # the env's per-term episode means (rsl_rl's "Episode/rew_*"), one read
+                keys = [k for k in episode if k not in log[-1]]
+                log[-1].update(zip(keys, torch.stack([torch.as_tensor(episode[k], device=dev).detach().to(torch.float32).reshape(()) for k in keys]).tolist()))
             if alg.symmetry is not None:
                 log[-1]["symmetry_loss"] = alg.symmetry_loss
             if self.rnd is not None:

@@ -32,12 +32,30 @@ sys.path.insert(0, ROOT)
 TASKS = ("walk", "stairs", "stairs_lidar", "stairs_info", "stairwell", "rough", "crouch", "jump")
 
 
-def task_cfgs(task, terrain_mode="heightmap", terrain_seed=0):
+def task_cfgs(task, terrain_mode="heightmap", terrain_seed=0, script_values=False, body_contact=None, stumble=None):
+    """The task's four cfg dictionaries.  `script_values` (stairs_info): go2_stair_train_lidar_2.py's own values, its body_contact penalty among them;
+    `body_contact` / `stumble`: scales of the two contact terms (include/go2sim_cterms.h) for any walk or stair task, appended to reward_scales."""
+    cfgs = _task_cfgs(task, terrain_mode, terrain_seed, script_values)
+    for name, scale in (("body_contact", body_contact), ("stumble", stumble)):
+        if scale is not None:
+            if task in ("crouch", "jump"):
+                raise SystemExit(f"--{name.replace('_', '-')} belongs to the walk and stair tasks: the base env has no contact terms")
+            scales = cfgs[2]["reward_scales"]
+            scales.pop(name, None)                             # last in the dictionary: the launch adds the term after the core's sum
+            scales[name] = float(scale)
+    return cfgs
+
+
+def _task_cfgs(task, terrain_mode, terrain_seed, script_values):
     from go2_sim2real_locomotion_rl_amd import (get_crouch_cfgs, get_jump_cfgs, get_rough_cfgs, get_stair_cfgs, get_stair_info_cfgs, get_stair_lidar_cfgs,
                                                 get_stairwell_cfgs, get_walk_cfgs)
 
     if task == "rough":                                        # go2_train_Omni_kplearn_varied_terrain.py: the walk env on a heightmap or a tile grid
         return get_rough_cfgs(terrain_mode, seed=terrain_seed)
+    if script_values:
+        if task != "stairs_info":
+            raise SystemExit("--script-values belongs to --task stairs_info")
+        return get_stair_info_cfgs(script_values=True)
     return {"walk": get_walk_cfgs, "stairs": get_stair_cfgs, "stairs_lidar": get_stair_lidar_cfgs, "stairs_info": get_stair_info_cfgs, "stairwell": get_stairwell_cfgs, "crouch": get_crouch_cfgs, "jump": get_jump_cfgs}[task]()
 
 
@@ -56,6 +74,12 @@ def main():
     ap.add_argument("--task", choices=TASKS, default="walk")
     ap.add_argument("--terrain-mode", choices=("heightmap", "grid"), default="heightmap", help="--task rough: the train script's TERRAIN_MODE")
     ap.add_argument("--terrain-seed", type=int, default=0, help="--task rough: seeds the heightmap's bumps and, through numpy's global generator, the grid's tiles")
+    ap.add_argument("--script-values", action="store_true",
+                    help="--task stairs_info: go2_stair_train_lidar_2.py's own values (level_init 0.2, feet_height_target 0.15, body_contact -2.0 on the front thighs)")
+    ap.add_argument("--body-contact", type=float, default=None, metavar="SCALE",
+                    help="walk and stair tasks: reward scale of the body_contact term (links of env_cfg['body_contact_names'], default the front thighs, in contact)")
+    ap.add_argument("--stumble", type=float, default=None, metavar="SCALE",
+                    help="walk and stair tasks: reward scale of the stumble term (contact force above reward_cfg['stumble_threshold'] on the links that are no feet)")
     ap.add_argument("--envs", type=int, default=4096, help="environments per rank")
     ap.add_argument("--iterations", type=int, default=1000)
     ap.add_argument("--log-dir", default=None, help="checkpoints go here (rank 0); none are written without it")
@@ -124,7 +148,7 @@ def main():
             import numpy as np
 
             np.random.seed(args.terrain_seed)                  # every rank generates the same tiles
-        env = Go2Env(args.envs, *task_cfgs(args.task, args.terrain_mode, args.terrain_seed), seed=seed, device=device, shared_globals=world > 1)
+        env = Go2Env(args.envs, *task_cfgs(args.task, args.terrain_mode, args.terrain_seed, args.script_values, args.body_contact, args.stumble), seed=seed, device=device, shared_globals=world > 1)
         cfg = train_cfg_of(args.task, args.cfgs)
         cfg["seed"] = args.seed
         if args.steps_per_env:
