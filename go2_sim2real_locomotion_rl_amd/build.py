@@ -7,28 +7,17 @@ import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 REPO_ROOT = os.path.dirname(_HERE)
-HIP_SRC = os.path.join(_HERE, "csrc", "go2sim.hip")
-HIP_SRC_POLICY = os.path.join(_HERE, "csrc", "go2sim_policy.hip")
-HIP_SRC_TRAIN = os.path.join(_HERE, "csrc", "go2sim_train.hip")             # the PPO update (include/go2sim_train.h): product library only
-HIP_SRC_NORM = os.path.join(_HERE, "csrc", "go2sim_norm.hip")               # the observation normaliser (include/go2sim_norm.h): product library only
-HIP_SRC_LIDAR = os.path.join(_HERE, "csrc", "go2sim_lidar.hip")             # the LIDAR terrain scan (include/go2sim_lidar.h): product library only
-HIP_SRC_STAIRINFO = os.path.join(_HERE, "csrc", "go2sim_stairinfo.hip")     # the four-value stair info (include/go2sim_stairinfo.h): product library only
-HIP_SRC_DISTILL = os.path.join(_HERE, "csrc", "go2sim_distill.hip")         # teacher-student distillation (include/go2sim_distill.h): product library only
-HIP_SRC_RDISTILL = os.path.join(_HERE, "csrc", "go2sim_rdistill.hip")       # distillation with a recurrent student (include/go2sim_rdistill.h): product library only
-HIP_SRC_RND = os.path.join(_HERE, "csrc", "go2sim_rnd.hip")                 # random network distillation (include/go2sim_rnd.h): product library only
-HIP_SRC_TILES = os.path.join(_HERE, "csrc", "go2sim_tiles.hip")             # the rough-terrain env's ground query (include/go2sim_tiles.h): product library only
-HIP_HDR_TILES = os.path.join(_HERE, "csrc", "go2sim_tiles_dev.h")           # the tile mode's device functions go2sim.hip and go2sim_tiles.hip share
-HIP_SRC_WELLS = os.path.join(_HERE, "csrc", "go2sim_wells.hip")             # the stairwell env's scan handle (include/go2sim_wells.h): product library only
-HIP_HDR_WELLS = os.path.join(_HERE, "csrc", "go2sim_wells_dev.h")           # the stairwell env's device functions go2sim.hip and go2sim_wells.hip share
-HIP_SRC_STATE = os.path.join(_HERE, "csrc", "go2sim_state.hip")             # env snapshots: save, load (include/go2sim_state.h): product library only
-HIP_SRC_CTERMS = os.path.join(_HERE, "csrc", "go2sim_cterms.hip")           # the contact terms body_contact and stumble (include/go2sim_cterms.h): product library only
-HIP_HDR_GJK = os.path.join(_HERE, "csrc", "go2sim_gjk_dev.h")
-HIP_HDR_MLP = os.path.join(_HERE, "csrc", "go2sim_mlp_dev.h")               # shared by go2sim_policy.hip and go2sim_train.hip
-HIP_HDR_LSTM = os.path.join(_HERE, "csrc", "go2sim_lstm_dev.h")             # the recurrent policy's kernels (include/go2sim_rnn.h), included by go2sim_train.hip
-HIP_HDR_TRAIN = os.path.join(_HERE, "csrc", "go2sim_train_dev.h")           # the forward-with-activations, backward and optimizer kernels go2sim_train.hip and go2sim_distill.hip share
-HIP_HDR_TRAINER = os.path.join(_HERE, "csrc", "go2sim_trainer_host.h")      # the host side the two share: optimizer state, packing, workspaces, the backward schedule
-HIP_HDR_DISTILL = os.path.join(_HERE, "csrc", "go2sim_distill_dev.h")       # the loss head and float64 sums go2sim_distill.hip and go2sim_rdistill.hip share
-HIP_HDR_NORM = os.path.join(_HERE, "csrc", "go2sim_norm_dev.h")             # the float64 moment code go2sim_norm.hip and go2sim_rnd.hip share
+_CSRC = os.path.join(_HERE, "csrc")
+# The product's sources, csrc/go2sim<suffix>.hip: the simulator with the env, policy inference, and what the product library alone has (include/go2sim_<name>.h
+# states each one's ABI): the PPO update, the observation normaliser, the LIDAR scan, the stair info, distillation (feed-forward, recurrent), RND, the
+# rough-terrain ground query, the stairwell scan, env snapshots, the contact terms.
+HIP_SOURCES = tuple(os.path.join(_CSRC, f"go2sim{s}.hip") for s in ("", "_policy", "_train", "_norm", "_lidar", "_stairinfo", "_distill", "_rdistill", "_rnd",
+                                                                    "_tiles", "_wells", "_state", "_cterms"))
+# The device and host headers they share, csrc/go2sim_<name>.h (each one's first lines say between which sources).
+HIP_DEV_HEADERS = tuple(os.path.join(_CSRC, f"go2sim_{n}.h") for n in ("gjk_dev", "mlp_dev", "lstm_dev", "train_dev", "trainer_host", "distill_dev", "norm_dev",
+                                                                       "tiles_dev", "wells_dev", "envlaunch_dev"))
+HIP_SRC, HIP_SRC_POLICY = HIP_SOURCES[:2]                                  # what the diagnostic and shape builds compile
+HIP_SRC_NORM = HIP_SOURCES[3]
 HIP_LIB = os.path.join(_HERE, "csrc", "libgo2sim.so")
 ORACLE_SRC = os.path.join(REPO_ROOT, "oracle", "go2sim_cpu.cpp")
 ORACLE_SRC_POLICY = os.path.join(REPO_ROOT, "oracle", "policy_cpu.cpp")
@@ -55,11 +44,10 @@ def _headers():
 
 
 def build_hip(force=False, verbose=True):
-    if not force and _newer(HIP_LIB, HIP_SRC, HIP_SRC_POLICY, HIP_SRC_TRAIN, HIP_SRC_NORM, HIP_SRC_LIDAR, HIP_SRC_STAIRINFO, HIP_SRC_DISTILL, HIP_SRC_RDISTILL, HIP_SRC_RND, HIP_SRC_TILES, HIP_HDR_TILES, HIP_SRC_WELLS, HIP_HDR_WELLS, HIP_SRC_STATE, HIP_SRC_CTERMS, HIP_HDR_GJK, HIP_HDR_MLP, HIP_HDR_LSTM, HIP_HDR_TRAIN, HIP_HDR_TRAINER,
-                            HIP_HDR_DISTILL, HIP_HDR_NORM, *_headers()):
+    if not force and _newer(HIP_LIB, *HIP_SOURCES, *HIP_DEV_HEADERS, *_headers()):
         return HIP_LIB
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    cmd = [hipcc, *HIP_FLAGS, HIP_SRC, HIP_SRC_POLICY, HIP_SRC_TRAIN, HIP_SRC_NORM, HIP_SRC_LIDAR, HIP_SRC_STAIRINFO, HIP_SRC_DISTILL, HIP_SRC_RDISTILL, HIP_SRC_RND, HIP_SRC_TILES, HIP_SRC_WELLS, HIP_SRC_STATE, HIP_SRC_CTERMS, "-o", HIP_LIB]
+    cmd = [hipcc, *HIP_FLAGS, *HIP_SOURCES, "-o", HIP_LIB]
     if verbose:
         print("[build]", " ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)
@@ -70,7 +58,7 @@ def build_hip_variant(name, extra_flags, force=False, verbose=True):
     """A diagnostic BUILD of the product library with extra -D flags (tools/lib_<name>.so); test infrastructure for builds the
     product does not ship -- e.g. ("bracket_inline", ["-DGO2SIM_BRACKET_INLINE"]), see DESIGN.md "update_bracket"."""
     out = os.path.join(REPO_ROOT, "tools", f"lib_{name}.so")
-    if not force and _newer(out, HIP_SRC, HIP_SRC_POLICY, HIP_HDR_GJK, HIP_HDR_MLP, HIP_HDR_TILES, HIP_HDR_WELLS, *_headers()):
+    if not force and _newer(out, HIP_SRC, HIP_SRC_POLICY, *HIP_DEV_HEADERS, *_headers()):
         return out
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     cmd = [hipcc, *HIP_FLAGS, *extra_flags, HIP_SRC, HIP_SRC_POLICY, "-o", out]

@@ -12,6 +12,7 @@ import os
 import re
 
 import numpy as np
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 REPO_ROOT = os.path.dirname(_HERE)
@@ -220,6 +221,110 @@ class Handle:
             self.close()
         except Exception:
             pass
+
+
+def _as_device_tensor(ptr, shape, dtype, device):
+    """Zero-copy torch view of library-owned device memory (no ownership transfer, include/go2sim.h)."""
+    itemsize = torch.empty((), dtype=dtype).element_size()
+    n = 1
+    for s in shape:
+        n *= s
+
+    class _Mem:
+        __cuda_array_interface__ = {
+            "shape": tuple(shape), "typestr": {torch.float32: "<f4", torch.int32: "<i4", torch.uint8: "|u1"}[dtype],
+            "data": (int(ptr), False), "version": 2, "strides": None,
+        }
+
+    assert n * itemsize > 0
+    return torch.as_tensor(_Mem(), device=device)
+
+
+def check_layout_widths(name, env_cfg, obs_cfg, widths):
+    """The proprioceptive width n_in of a cfg whose obs_cfg carries `widths` = (n_in, num_obs, num_privileged_obs), what the `name` layout gives;
+    Go2SimError (naming both pairs) otherwise."""
+    n_in, want_obs, want_priv = widths
+    num_actions, have = int(env_cfg["num_actions"]), (obs_cfg["num_obs"], obs_cfg.get("num_privileged_obs"))
+    if num_actions not in ((16,) if env_cfg.get("pls_enable", False) else (16, 12)):
+        raise Go2SimError(f"the {name} layout has 16 actions (12 with pls_enable=False), got {num_actions}")
+    if have != (want_obs, want_priv):
+        raise Go2SimError(f"obs_cfg gives num_obs / num_privileged_obs = {have[0]} / {have[1]}, the {name} layout gives {want_obs} / {want_priv}")
+    return n_in
+
+
+class EnvLaunch(Handle):
+    """One of the launches Go2Env runs after the step's own (LidarScan, StairInfo, WellScan, ContactTerms): the handle of go2sim_<NAME>_create with its
+    device, stream, clear and host-array state, and what Go2Env asks of every launch:
+
+        inner_widths(env_cfg, obs_cfg)   (num_obs, num_privileged_obs) of the rows the step kernels write for it (a layout launch; checks obs_cfg)
+        launch(env, inner_obs, inner_priv), clear(idx), log(mask), episode_entries(), curriculum_entries(level)
+        state_schema(B), state_dict(), load_state_dict(state)      its keys of Go2Env.state_dict() (ENV_STATE.md)
+
+    An episode term keeps `ep`, the device view [..., n_envs] of the per-env records of the last finished episode, and `ep_log`, their logged means."""
+    NAME = STATE_FAMILY = None
+    WIDENS_OBS = True                  # the launch writes the actor row as well: the step kernels write an inner one
+    logs, ep, ep_log = False, None, None
+
+    def __init__(self, n_envs, device=None):
+        if not torch.cuda.is_available():
+            raise Go2SimError("no ROCm GPU visible: the go2sim product path has no CPU fallback")
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.n_envs = int(n_envs)
+        self._L = load_hip_lib()
+        Handle.__init__(self, self._L, self.NAME + "_destroy")
+
+    def _call(self, entry, *args):
+        self._L.check(self._L.fn(f"{self.NAME}_{entry}")(self.h, *args), f"{self.NAME}_{entry}")
+
+    def _create(self, cfg, *arrays):
+        h = ctypes.c_void_p()
+        self._L.check(self._L.fn(self.NAME + "_create")(ctypes.c_int(self.device.index or 0), ctypes.byref(cfg), *arrays, ctypes.byref(h)), self.NAME + "_create")
+        self.h = h
+        self._step_fn = self._L.fn(self.NAME + "_step")                    # looked up once: step() runs every env step
+
+    def _step(self, *args):
+        rc = self._step_fn(self.h, *args, self._stream())
+        if rc:
+            self._L.check(rc, self.NAME + "_step")
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def clear(self, envs_idx=None):
+        """For ``envs_idx`` (int32 device tensor) or for every env: stored rows := 0; an episode term's hand-over without a step (record the per-second
+        value, zero sum and count)."""
+        self._call("clear", _ptr(envs_idx), ctypes.c_int(0 if envs_idx is None else envs_idx.numel()), self._stream())
+
+    def _get_host(self, entry, shape, *dtypes):
+        """CPU tensors of `shape`, one per dtype, filled by go2sim_<NAME>_<entry>; waits for the stream."""
+        out = [np.zeros(shape, t) for t in dtypes]
+        self._call(entry, *(_ptr(a) for a in out), self._stream())
+        return tuple(torch.from_numpy(a) for a in out)
+
+    def _set_host(self, entry, what, shape, *values):
+        """go2sim_<NAME>_<entry> with `values` = (tensor, torch dtype) ..., each of `shape`; Go2SimError "<what> shape ..., got ..." otherwise."""
+        arrs = [np.ascontiguousarray(torch.as_tensor(v).detach().cpu().to(t).numpy()) for v, t in values]
+        if any(a.shape != shape for a in arrs):
+            got = [str(a.shape) for a in arrs]
+            raise Go2SimError(f"{what} shape {shape}, got {' and '.join([', '.join(got[:-1])] * (len(got) > 1) + got[-1:])}")
+        self._call(entry, *(_ptr(a) for a in arrs), self._stream())
+
+    def log(self, mask):
+        """ep_log := the means of `ep` over the envs of `mask`, as the core reports its terms (the mean, over the envs of the last reset, of episode sum /
+        episode seconds); kept while no env is reset.  Device arithmetic on [n_envs] values, no synchronisation."""
+        if self.logs:
+            m = mask.to(torch.float32)
+            n = m.sum()
+            self.ep_log = torch.where(n > 0, (self.ep * m).sum(-1) / n.clamp(min=1.0), self.ep_log)
+
+    def episode_entries(self):
+        return {}
+
+    def curriculum_entries(self, level):
+        return {}
+
+    def state_schema(self, B):
+        return self.schema_of(B)
 
 
 class Go2Sim(Handle):

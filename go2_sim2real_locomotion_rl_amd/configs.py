@@ -110,6 +110,14 @@ def _name_maps(model):
     return links, joints
 
 
+def dr_schedule_params(dr_schedule):
+    """(scheduled, phase1_level, terrain_gate) of env_cfg["dr_schedule"], a dictionary or None (no schedule: the DR level is the curriculum level), with
+    the defaults of go2_env_stair.py:972-988 -- for the env kernels, the LIDAR and stair-info launches and extras["curriculum"]."""
+    if dr_schedule is None:
+        return 0, 0.0, 0.0
+    return 1, float(dr_schedule.get("phase1_level", 0.15)), float(dr_schedule.get("terrain_gate", 0.50))
+
+
 def flatten_walk_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg, *, model=None, per_env_global_dr=False,
                      freeze_curriculum=False, shared_globals=False):
     """Go2Env.__init__ (go2_env_walk.py:155-525) as data: returns (fcfg float32[FC_COUNT], icfg int32[IC_COUNT],
@@ -267,10 +275,7 @@ def flatten_walk_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg, *, mod
 
     # ---- stair env extras (go2_env_stair.py:352-398, 972-988, 1615-1626) ----
     f[F("LIN_VEL_Z_DEADZONE")] = float(reward_cfg.get("lin_vel_z_deadzone", 0.0))
-    dr_sched = env_cfg.get("dr_schedule", None)
-    i[I("DR_SCHEDULE")] = int(dr_sched is not None)
-    if dr_sched is not None:
-        f[F("DR_PHASE1_LEVEL")], f[F("DR_TERRAIN_GATE")] = dr_sched.get("phase1_level", 0.15), dr_sched.get("terrain_gate", 0.50)
+    i[I("DR_SCHEDULE")], f[F("DR_PHASE1_LEVEL")], f[F("DR_TERRAIN_GATE")] = dr_schedule_params(env_cfg.get("dr_schedule", None))
     tcfg = env_cfg.get("terrain", None)
     if is_tile_terrain_cfg(tcfg):
         # ---- rough-terrain env (go2_env_Omni_kplearn_varied_terrain.py + terrain_manager.py; include/go2sim_tiles.h): the stair extras stay off ----

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 import torch
 
-from .capi import C, Go2SimError, Handle, _ptr, load_hip_lib
+from .capi import C, EnvLaunch, Go2SimError, _as_device_tensor, _ptr
 from .configs import CONTACT_TERM_NAMES                              # ("body_contact", "stumble"): the order the launch applies them in
 from .model_blob import load_model_json
 
@@ -64,13 +64,15 @@ def contact_term_scales(reward_cfg):
     return tuple(float(scales.get(n, 0.0)) for n in CONTACT_TERM_NAMES)
 
 
-class ContactTerms(Handle):
+class ContactTerms(EnvLaunch):
+    NAME, logs = "cterms", True
+
     def __init__(self, n_envs, *, body_links=(), stumble_links=None, body_contact_scale=0.0, stumble_scale=0.0, body_contact_threshold=1.0,
-                 stumble_threshold=5.0, n_links=None, dt=0.02, device=None, body_mask=None, stumble_mask=None):
-        if not torch.cuda.is_available():
-            raise Go2SimError("no ROCm GPU visible: the go2sim product path has no CPU fallback")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.n_envs, self.n_links = int(n_envs), int(C["GO2SIM_NL"] if n_links is None else n_links)
+                 stumble_threshold=5.0, n_links=None, dt=0.02, device=None, body_mask=None, stumble_mask=None, report=CONTACT_TERM_NAMES, count_out=None):
+        """``report``: the terms whose reward_cfg key exists, the ones episode_entries() lists (zero for a zero scale); ``count_out``: where launch() leaves
+        the per-env count of body links in contact (Go2Env.body_contact_count)."""
+        EnvLaunch.__init__(self, n_envs, device)
+        self.n_links = int(C["GO2SIM_NL"] if n_links is None else n_links)
         c = CtermsCfg()
         c.dt, c.body_contact_scale, c.stumble_scale = float(dt), float(body_contact_scale), float(stumble_scale)
         c.body_contact_threshold, c.stumble_threshold = float(body_contact_threshold), float(stumble_threshold)
@@ -78,45 +80,52 @@ class ContactTerms(Handle):
         c.body_mask = link_mask(body_links) if body_mask is None else int(body_mask)
         c.stumble_mask = (link_mask(non_foot_links() if stumble_links is None else stumble_links)) if stumble_mask is None else int(stumble_mask)
         self.body_mask, self.stumble_mask = int(c.body_mask), int(c.stumble_mask)
-        self._L = load_hip_lib()
-        Handle.__init__(self, self._L, "cterms_destroy")
-        h = ctypes.c_void_p()
-        self._L.check(self._L.fn("cterms_create")(ctypes.c_int(self.device.index or 0), ctypes.byref(c), ctypes.byref(h)), "cterms_create")
-        self.h = h
+        self._create(c)
         ep_b, ep_s, inc_b, inc_s = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_float(), ctypes.c_float()
-        self._L.check(self._L.fn("cterms_ep")(self.h, ctypes.byref(ep_b), ctypes.byref(ep_s), ctypes.byref(inc_b), ctypes.byref(inc_s)), "cterms_ep")
+        self._call("ep", ctypes.byref(ep_b), ctypes.byref(ep_s), ctypes.byref(inc_b), ctypes.byref(inc_s))
         self.ep_ptrs = (ep_b.value, ep_s.value)                        # per-env records of the last finished episode, body_contact then stumble
-        if ep_s.value != ep_b.value + 4 * self.n_envs:                 # the library keeps them as one [2][n_envs] array; Go2Env reduces both in one view
+        if ep_s.value != ep_b.value + 4 * self.n_envs:                 # the library keeps them as one [2][n_envs] array: both are reduced in one view
             raise Go2SimError("go2sim_cterms_ep: the two records are not adjacent")
         self.incs = (inc_b.value, inc_s.value)                         # f32(scale * dt) of each
         self.active = (float(body_contact_scale) != 0.0, float(stumble_scale) != 0.0)
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self.ep = _as_device_tensor(ep_b.value, (2, self.n_envs), torch.float32, self.device)
+        self.ep_log = torch.zeros(2, device=self.device)              # the logged means, body_contact then stumble
+        self.count = torch.zeros(self.n_envs, device=self.device) if count_out is None else count_out
+        self._report, self._zero = tuple(report), torch.zeros((), device=self.device)
 
     # ---- the sums --------------------------------------------------------------------------------------------------------------
     def state(self):
         """(sum float32 [2, n_envs], steps int32 [2, n_envs], ep float32 [2, n_envs]) CPU tensors, body_contact then stumble; waits for the stream."""
-        s, k, e = (np.zeros((2, self.n_envs), t) for t in (np.float32, np.int32, np.float32))
-        self._L.check(self._L.fn("cterms_get_state")(self.h, _ptr(s), _ptr(k), _ptr(e), self._stream()), "cterms_get_state")
-        return torch.from_numpy(s), torch.from_numpy(k), torch.from_numpy(e)
+        return self._get_host("get_state", (2, self.n_envs), np.float32, np.int32, np.float32)
 
     def set_state(self, sums, steps, ep):
-        s = np.ascontiguousarray(torch.as_tensor(sums).detach().cpu().to(torch.float32).numpy())
-        k = np.ascontiguousarray(torch.as_tensor(steps).detach().cpu().to(torch.int32).numpy())
-        e = np.ascontiguousarray(torch.as_tensor(ep).detach().cpu().to(torch.float32).numpy())
-        if not (s.shape == k.shape == e.shape == (2, self.n_envs)):
-            raise Go2SimError(f"the contact terms' state has shape {(2, self.n_envs)}, got {s.shape}, {k.shape} and {e.shape}")
-        self._L.check(self._L.fn("cterms_set_state")(self.h, _ptr(s), _ptr(k), _ptr(e), self._stream()), "cterms_set_state")
-
-    def clear(self, envs_idx=None):
-        """The episode hand-over without a step for ``envs_idx`` (int32 device tensor) or for every env: record the per-second values, zero sums and counts."""
-        n = 0 if envs_idx is None else envs_idx.numel()
-        self._L.check(self._L.fn("cterms_clear")(self.h, _ptr(envs_idx), ctypes.c_int(n), self._stream()), "cterms_clear")
+        self._set_host("set_state", "the contact terms' state has", (2, self.n_envs), (sums, torch.float32), (steps, torch.int32), (ep, torch.float32))
 
     # ---- the step ----------------------------------------------------------------------------------------------------------
     def step(self, cf, strides, reset, rew, count_out):
         """go2sim_cterms_step with device tensors or raw device addresses; strides are (component, link, env) in elements."""
-        rc = self._L.fn("cterms_step")(self.h, ctypes.c_int(self.n_envs), _ptr(cf, True), ctypes.c_longlong(strides[0]), ctypes.c_longlong(strides[1]),
-                                       ctypes.c_longlong(strides[2]), _ptr(reset), _ptr(rew), _ptr(count_out), self._stream())
-        self._L.check(rc, "cterms_step")
+        self._step(ctypes.c_int(self.n_envs), _ptr(cf, True), ctypes.c_longlong(strides[0]), ctypes.c_longlong(strides[1]),
+                   ctypes.c_longlong(strides[2]), _ptr(reset), _ptr(rew), _ptr(count_out))
+
+    # ---- for Go2Env (capi.EnvLaunch) -------------------------------------------------------------------------------------------
+    def launch(self, env, inner_obs, inner_priv):
+        """Both terms onto the env's reward, from the links' contact forces where the solve left them (SoA [link * 3 + comp][n_envs])."""
+        n = self.n_envs
+        self.step(env._contact_force_ptr, (n, 3 * n, 1), env.reset_buf, env.rew_buf, self.count)
+
+    def episode_entries(self):
+        return {"rew_" + name: self.ep_log[t] if self.active[t] else self._zero for t, name in enumerate(CONTACT_TERM_NAMES) if name in self._report}
+
+    @staticmethod
+    def schema_of(B, _=None):                                                    # body_contact, then stumble (include/go2sim_cterms.h)
+        f32 = torch.float32
+        return {"cterms_sum": (f32, (2, B)), "cterms_steps": (torch.int32, (2, B)), "cterms_ep": (f32, (2, B)), "cterms_log": (f32, (2,)), "cterms_count": (f32, (B,))}
+
+    def state_dict(self):
+        sums, steps, ep = self.state()
+        return {"cterms_sum": sums, "cterms_steps": steps, "cterms_ep": ep, "cterms_log": self.ep_log.cpu().clone(), "cterms_count": self.count.cpu().clone()}
+
+    def load_state_dict(self, state):
+        self.set_state(state["cterms_sum"], state["cterms_steps"], state["cterms_ep"])
+        self.ep_log = state["cterms_log"].to(self.device)
+        self.count.copy_(state["cterms_count"])

@@ -2,69 +2,28 @@
 // clean one, and the assembly of the wider observation rows, on gfx950.  The header states the law, the draw layout and the launch; this file follows its names.
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
-#include <cstdio>
 #include <new>
-#include <vector>
 
-#include "../../include/go2sim_detmath.h"
 #include "../../include/go2sim_lidar.h"
+#include "go2sim_envlaunch_dev.h"
 
 namespace {
 
-#define HIPCHK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) { fprintf(stderr, "go2sim_lidar: %s failed: %s\n", #x, hipGetErrorString(e_)); return GO2SIM_E_HIP; } \
-  } while (0)
-
-constexpr int WAVE = 64, WG = 256, ENVS_PER_WG = WG / WAVE;
+constexpr char TAG[] = "go2sim_lidar";
 constexpr int EXTRA = GO2SIM_LIDAR_PRIV_EXTRA;
 
 // what the kernels see of one handle
 struct LidarDev {
-  const float* hf;                 // [rows][cols] metres
-  const float *ax, *ay, *cx, *cy;  // the sample points
+  const float* hf;                 // Field's members are this one, rows, cols, ox, oy and hs
+  const float *ax, *ay, *cx, *cy;  // the sample points: one allocation, in this order
   float* stored;                   // [n_envs][n_actor]
   int rows, cols, n_envs, n_actor, n_critic;
   float ox, oy, hs, clip, scale;
   float noise_std, offset_std;
   double dropout_prob, latency_prob, blackout_prob;     // multiplied with L in float64, then rounded (the header's thresholds)
-  double phase1, gate;
-  int dr_schedule, curriculum_enabled;
+  DrSched dr;
   uint32_t k0, k1;                 // the seed's words
 };
-
-struct Pose {
-  const float *pos, *quat;
-  long long pcs, pes, qcs, qes;
-};
-
-// _get_dr_level, go2_env_stair_lidar.py:1197-1220
-__device__ __forceinline__ double dr_level(const LidarDev& D, double t) {
-  if (!D.dr_schedule) return t;
-  if (t < D.gate) return D.phase1;
-  double den = 1.0 - D.gate;
-  if (den < 1e-6) den = 1e-6;
-  double pr = (t - D.gate) / den;
-  pr = pr < 0.0 ? 0.0 : (pr > 1.0 ? 1.0 : pr);
-  return D.phase1 + (1.0 - D.phase1) * pr;
-}
-
-// trunc toward zero, then clamp to [0, n - 1], by comparisons a NaN fails (it selects 0): never an index outside the field
-__device__ __forceinline__ int cell_index(float q, int n) {
-  if (!(q >= 1.0f)) return 0;                    // negatives, [0, 1) and NaN
-  if (q >= (float)(n - 1)) return n - 1;         // +inf included
-  return (int)q;
-}
-
-__device__ __forceinline__ float raw_height(const LidarDev& D, float px, float py, float pz, float s, float c, float lx, float ly) {
-  const float wx = px + c * lx - s * ly;
-  const float wy = py + s * lx + c * ly;
-  const int col = cell_index((wx - D.ox) / D.hs, D.rows);
-  const int row = cell_index((wy - D.oy) / D.hs, D.cols);
-  return D.hf[(size_t)col * D.cols + row] - pz;
-}
 
 __device__ __forceinline__ float clip_scale(const LidarDev& D, float v) {
   v = v < -D.clip ? -D.clip : (v > D.clip ? D.clip : v);     // a NaN stays a NaN, as torch.clamp leaves it
@@ -95,15 +54,10 @@ __global__ __launch_bounds__(WG) void k_lidar_step(LidarDev D, Pose P, const uin
     for (int k = t; k < nc; k += WAVE) prow[n_in + na + extra + k] = 0.0f;
     return;
   }
-  const float px = P.pos[(size_t)b * P.pes], py = P.pos[P.pcs + (size_t)b * P.pes], pz = P.pos[2 * P.pcs + (size_t)b * P.pes];
-  const float qw = P.quat[(size_t)b * P.qes], qx = P.quat[P.qcs + (size_t)b * P.qes], qy = P.quat[2 * P.qcs + (size_t)b * P.qes],
-              qz = P.quat[3 * P.qcs + (size_t)b * P.qes];
-  const float yaw = dm_atan2(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz));
-  float s, c;
-  dm_sincos(yaw, &s, &c);
-  for (int k = t; k < nc; k += WAVE) prow[n_in + na + extra + k] = clip_scale(D, raw_height(D, px, py, pz, s, c, D.cx[k], D.cy[k]));
+  const Base B = load_base(P, b);
+  for (int k = t; k < nc; k += WAVE) prow[n_in + na + extra + k] = clip_scale(D, scan_point(D, B.px, B.py, B.pz, B.s, B.c, D.cx[k], D.cy[k]));
   if (na == 0) return;
-  const double L = dr_level(D, D.curriculum_enabled ? *level : 1.0);
+  const double L = dr_level(D.dr, level);
   const bool on = L > 0.0;
   const float Lf = (float)L;
   const bool do_noise = on && D.noise_std > 0.0f, do_drop = on && D.dropout_prob > 0.0, do_off = on && D.offset_std > 0.0f;
@@ -120,7 +74,7 @@ __global__ __launch_bounds__(WG) void k_lidar_step(LidarDev D, Pose P, const uin
   }
   const float drop_thr = (float)(D.dropout_prob * L);
   for (int k = t; k < na; k += WAVE) {
-    float v = raw_height(D, px, py, pz, s, c, D.ax[k], D.ay[k]);
+    float v = scan_point(D, B.px, B.py, B.pz, B.s, B.c, D.ax[k], D.ay[k]);
     if (do_noise || do_drop) {
       const dm_u4 r = dm_philox((uint32_t)b, step, GO2SIM_LIDAR_RNG_PURPOSE, 1u + (uint32_t)(k >> 1), D.k0, D.k1);
       if (do_noise) {
@@ -139,22 +93,11 @@ __global__ __launch_bounds__(WG) void k_lidar_step(LidarDev D, Pose P, const uin
   }
 }
 
-__global__ __launch_bounds__(WG) void k_lidar_clear(float* __restrict__ stored, int n_envs, int n_actor, const int* __restrict__ idx, int n_sel) {
-  const long long i = (long long)blockIdx.x * WG + threadIdx.x, total = (long long)(idx ? n_sel : n_envs) * n_actor;
-  if (i >= total) return;
-  const int r = (int)(i / n_actor), k = (int)(i - (long long)r * n_actor);
-  const int b = idx ? idx[r] : r;
-  if (b >= 0 && b < n_envs) stored[(size_t)b * n_actor + k] = 0.0f;
-}
-
 }  // namespace
 
 struct go2sim_lidar {
   int device = 0;
   LidarDev dev = {};
-  float* hf = nullptr;
-  float* pts = nullptr;     // ax | ay | cx | cy
-  float* stored = nullptr;
   uint32_t step = 0;
 };
 
@@ -165,39 +108,34 @@ int go2sim_lidar_create(int device, const go2sim_lidar_cfg_t* cfg, const int16_t
   if (!out || !cfg || !hf) return GO2SIM_E_BADARG;
   const go2sim_lidar_cfg_t& c = *cfg;
   if (c.n_envs < 1 || c.n_actor < 0 || c.n_critic < 0 || c.n_actor + c.n_critic == 0 || c.n_actor > (1 << 16) || c.n_critic > (1 << 16)) return GO2SIM_E_BADARG;
-  if (c.hf_rows < 1 || c.hf_cols < 1 || (long long)c.hf_rows * c.hf_cols > (1LL << 30) || !(c.horizontal_scale > 0.0) || !(c.height_clip >= 0.0)) return GO2SIM_E_BADARG;
+  if (!field_args_ok(c.hf_rows, c.hf_cols, c.horizontal_scale) || !(c.height_clip >= 0.0)) return GO2SIM_E_BADARG;
   if ((c.n_actor > 0 && !actor_xy) || (c.n_critic > 0 && !critic_xy)) return GO2SIM_E_BADARG;
-  const double all[] = {c.height_noise_std, c.dropout_prob, c.vertical_offset_std, c.latency_prob, c.full_blackout_prob, c.height_scale, c.dr_phase1_level,
-                        c.dr_terrain_gate, c.origin_x, c.origin_y, c.vertical_scale};
-  for (double v : all)
-    if (v != v) return GO2SIM_E_BADARG;
-  HIPCHK(hipSetDevice(device));
+  if (nan_in({c.height_noise_std, c.dropout_prob, c.vertical_offset_std, c.latency_prob, c.full_blackout_prob, c.height_scale, c.dr_phase1_level,
+              c.dr_terrain_gate, c.origin_x, c.origin_y, c.vertical_scale}))
+    return GO2SIM_E_BADARG;
+  HIPCHK(TAG, hipSetDevice(device));
   go2sim_lidar* h = new (std::nothrow) go2sim_lidar();
   if (!h) return GO2SIM_E_NOMEM;
   h->device = device;
-  const size_t cells = (size_t)c.hf_rows * c.hf_cols, npts = 2 * ((size_t)c.n_actor + c.n_critic), nst = (size_t)c.n_envs * (c.n_actor > 0 ? c.n_actor : 1);
-  if (hipMalloc((void**)&h->hf, cells * sizeof(float)) != hipSuccess || hipMalloc((void**)&h->pts, npts * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&h->stored, nst * sizeof(float)) != hipSuccess) {
-    go2sim_lidar_destroy(h);
-    return GO2SIM_E_NOMEM;
-  }
-  std::vector<float> hfm(cells), pts(npts);
-  for (size_t k = 0; k < cells; ++k) hfm[k] = (float)hf[k] * (float)c.vertical_scale;      // as go2sim_set_terrain forms the env's own copy
+  LidarDev& D = h->dev;
+  const size_t npts = 2 * ((size_t)c.n_actor + c.n_critic), nst = (size_t)c.n_envs * (c.n_actor > 0 ? c.n_actor : 1);
+  std::vector<float> pts(npts);
   for (int k = 0; k < 2 * c.n_actor; ++k) pts[k] = actor_xy[k];
   for (int k = 0; k < 2 * c.n_critic; ++k) pts[2 * (size_t)c.n_actor + k] = critic_xy[k];
-  if (hipMemcpy(h->hf, hfm.data(), cells * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(h->pts, pts.data(), npts * sizeof(float), hipMemcpyHostToDevice) != hipSuccess || hipMemset(h->stored, 0, nst * sizeof(float)) != hipSuccess ||
-      hipDeviceSynchronize() != hipSuccess) {
+  int rc = upload_field(&D, hf, c.hf_rows, c.hf_cols, c.origin_x, c.origin_y, c.horizontal_scale, c.vertical_scale);
+  if (rc == GO2SIM_E_OK) rc = dev_array((float**)&D.ax, pts.data(), npts);
+  if (rc == GO2SIM_E_OK) rc = dev_array(&D.stored, (const float*)nullptr, nst);
+  if (rc == GO2SIM_E_OK && hipDeviceSynchronize() != hipSuccess) rc = GO2SIM_E_HIP;
+  if (rc != GO2SIM_E_OK) {
     go2sim_lidar_destroy(h);
-    return GO2SIM_E_HIP;
+    return rc;
   }
-  LidarDev& D = h->dev;
-  D.hf = h->hf; D.ax = h->pts; D.ay = D.ax + c.n_actor; D.cx = D.ay + c.n_actor; D.cy = D.cx + c.n_critic; D.stored = h->stored;
-  D.rows = c.hf_rows; D.cols = c.hf_cols; D.n_envs = c.n_envs; D.n_actor = c.n_actor; D.n_critic = c.n_critic;
-  D.ox = (float)c.origin_x; D.oy = (float)c.origin_y; D.hs = (float)c.horizontal_scale; D.clip = (float)c.height_clip; D.scale = (float)c.height_scale;
+  D.ay = D.ax + c.n_actor; D.cx = D.ay + c.n_actor; D.cy = D.cx + c.n_critic;
+  D.n_envs = c.n_envs; D.n_actor = c.n_actor; D.n_critic = c.n_critic;
+  D.clip = (float)c.height_clip; D.scale = (float)c.height_scale;
   D.noise_std = (float)c.height_noise_std; D.offset_std = (float)c.vertical_offset_std;
   D.dropout_prob = c.dropout_prob; D.latency_prob = c.latency_prob; D.blackout_prob = c.full_blackout_prob;
-  D.phase1 = c.dr_phase1_level; D.gate = c.dr_terrain_gate; D.dr_schedule = c.dr_schedule != 0; D.curriculum_enabled = c.curriculum_enabled != 0;
+  D.dr = DrSched{c.dr_phase1_level, c.dr_terrain_gate, c.dr_schedule != 0, c.curriculum_enabled != 0};
   D.k0 = (uint32_t)seed; D.k1 = (uint32_t)(seed >> 32);
   *out = h;
   return GO2SIM_E_OK;
@@ -205,7 +143,7 @@ int go2sim_lidar_create(int device, const go2sim_lidar_cfg_t* cfg, const int16_t
 
 int go2sim_lidar_destroy(go2sim_lidar_t* h) {
   if (!h) return GO2SIM_E_BADARG;
-  (void)hipFree(h->hf); (void)hipFree(h->pts); (void)hipFree(h->stored);
+  (void)hipFree((void*)h->dev.hf); (void)hipFree((void*)h->dev.ax); (void)hipFree(h->dev.stored);
   delete h;
   return GO2SIM_E_OK;
 }
@@ -223,43 +161,28 @@ int go2sim_lidar_set_step(go2sim_lidar_t* h, uint32_t step) {
 }
 
 int go2sim_lidar_clear(go2sim_lidar_t* h, const int* envs_idx, int n_sel, void* stream) {
-  if (!h || (envs_idx && n_sel < 0)) return GO2SIM_E_BADARG;
-  const long long total = (long long)(envs_idx ? n_sel : h->dev.n_envs) * h->dev.n_actor;
-  if (total == 0) return GO2SIM_E_OK;
-  hipLaunchKernelGGL(k_lidar_clear, dim3((unsigned)((total + WG - 1) / WG)), dim3(WG), 0, (hipStream_t)stream, h->stored, h->dev.n_envs, h->dev.n_actor, envs_idx, n_sel);
-  HIPCHK(hipGetLastError());
-  return GO2SIM_E_OK;
+  return h ? clear_rows(TAG, h->dev.stored, h->dev.n_envs, h->dev.n_actor, envs_idx, n_sel, stream) : GO2SIM_E_BADARG;
 }
 
 int go2sim_lidar_get_scan(go2sim_lidar_t* h, float* scan, void* stream) {
   if (!h || !scan) return GO2SIM_E_BADARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (h->dev.n_actor > 0) HIPCHK(hipMemcpyAsync(scan, h->stored, (size_t)h->dev.n_envs * h->dev.n_actor * sizeof(float), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return GO2SIM_E_OK;
+  return copy_wait(TAG, hipMemcpyDeviceToHost, stream, {{scan, h->dev.stored, (size_t)h->dev.n_envs * h->dev.n_actor * sizeof(float)}});
 }
 
 int go2sim_lidar_set_scan(go2sim_lidar_t* h, const float* scan, void* stream) {
   if (!h || !scan) return GO2SIM_E_BADARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (h->dev.n_actor > 0) HIPCHK(hipMemcpyAsync(h->stored, scan, (size_t)h->dev.n_envs * h->dev.n_actor * sizeof(float), hipMemcpyHostToDevice, s));
-  HIPCHK(hipStreamSynchronize(s));                          // the source is the caller's host memory
-  return GO2SIM_E_OK;
+  return copy_wait(TAG, hipMemcpyHostToDevice, stream, {{h->dev.stored, scan, (size_t)h->dev.n_envs * h->dev.n_actor * sizeof(float)}});
 }
 
 int go2sim_lidar_step(go2sim_lidar_t* h, int n, const float* pos, long long pos_comp_stride, long long pos_env_stride, const float* quat,
                       long long quat_comp_stride, long long quat_env_stride, const uint8_t* reset, const double* level, const float* obs, const float* priv,
                       int n_in, float* obs_out, float* priv_out, void* stream) {
-  if (!h || n != h->dev.n_envs || !pos || !quat || !obs_out || !priv_out || n_in < 0 || n_in > (1 << 20)) return GO2SIM_E_BADARG;
-  if (pos_comp_stride < 0 || pos_env_stride < 0 || quat_comp_stride < 0 || quat_env_stride < 0) return GO2SIM_E_BADARG;
-  if (h->dev.curriculum_enabled && !level) return GO2SIM_E_BADARG;
-  if ((obs == nullptr) != (priv == nullptr) || (obs == nullptr) != (n_in == 0)) return GO2SIM_E_BADARG;
-  if (obs_out == priv_out || (obs && ((const float*)obs_out == obs || (const float*)obs_out == priv || (const float*)priv_out == obs || (const float*)priv_out == priv)))
-    return GO2SIM_E_BADARG;
+  if (!h || n != h->dev.n_envs || !pose_args_ok(pos, pos_comp_stride, pos_env_stride, quat, quat_comp_stride, quat_env_stride)) return GO2SIM_E_BADARG;
+  if ((h->dev.dr.curriculum_enabled && !level) || !rows_args_ok(obs, priv, n_in, obs_out, priv_out)) return GO2SIM_E_BADARG;
   const Pose P = {pos, quat, pos_comp_stride, pos_env_stride, quat_comp_stride, quat_env_stride};
   hipLaunchKernelGGL(k_lidar_step, dim3((n + ENVS_PER_WG - 1) / ENVS_PER_WG), dim3(WG), 0, (hipStream_t)stream, h->dev, P, reset, level, h->step, obs, priv, n_in,
                      obs_out, priv_out);
-  HIPCHK(hipGetLastError());
+  HIPCHK(TAG, hipGetLastError());
   h->step += 1u;
   return GO2SIM_E_OK;
 }

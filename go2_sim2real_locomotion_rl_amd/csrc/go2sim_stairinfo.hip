@@ -4,31 +4,22 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
 #include <new>
-#include <vector>
 
-#include "../../include/go2sim_detmath.h"
 #include "../../include/go2sim_stairinfo.h"
+#include "go2sim_envlaunch_dev.h"
 
 namespace {
 
-#define HIPCHK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) { fprintf(stderr, "go2sim_stairinfo: %s failed: %s\n", #x, hipGetErrorString(e_)); return GO2SIM_E_HIP; } \
-  } while (0)
-
-constexpr int WAVE = 64, WG = 256, ENVS_PER_WG = WG / WAVE;
+constexpr char TAG[] = "go2sim_stairinfo";
 constexpr int NV = GO2SIM_STAIRINFO_N, EXTRA = GO2SIM_STAIRINFO_PRIV_EXTRA;
 constexpr int MAX_SAMPLES = GO2SIM_STAIRINFO_MAX_SAMPLES, MAX_ROWS = GO2SIM_STAIRINFO_MAX_ROWS;
 static_assert(MAX_SAMPLES <= WAVE, "one lane per pair of neighbouring samples");
 
 // what the kernels see of one handle
 struct StairDev {
-  const float* hf;                  // [rows][cols] metres
-  const float* xs;                  // [n_samples]
+  const float* hf;                  // Field's members are this one, rows, cols, ox, oy and hs
+  const float* xs;                  // [n_samples]; one allocation with the two below, in this order
   const float *row_h, *row_d;       // [n_rows]
   float* stored;                    // [n_envs][4]
   int rows, cols, n_envs, n_samples, n_rows;
@@ -36,41 +27,9 @@ struct StairDev {
   float s_e, s_h, s_d, s_dir;
   float std_e, std_h, std_d;
   double flip_prob, latency_prob, blackout_prob;     // multiplied with L in float64, then rounded (the header's thresholds)
-  double phase1, gate;
-  int dr_schedule, curriculum_enabled;
+  DrSched dr;
   uint32_t k0, k1;                  // the seed's words
 };
-
-struct Pose {
-  const float *pos, *quat;
-  long long pcs, pes, qcs, qes;
-};
-
-// _get_dr_level, go2_env_stair_lidar_2.py (the mapping of go2sim_lidar.hip)
-__device__ __forceinline__ double dr_level(const StairDev& D, double t) {
-  if (!D.dr_schedule) return t;
-  if (t < D.gate) return D.phase1;
-  double den = 1.0 - D.gate;
-  if (den < 1e-6) den = 1e-6;
-  double pr = (t - D.gate) / den;
-  pr = pr < 0.0 ? 0.0 : (pr > 1.0 ? 1.0 : pr);
-  return D.phase1 + (1.0 - D.phase1) * pr;
-}
-
-// trunc toward zero, then clamp to [0, n - 1], by comparisons a NaN fails (it selects 0): never an index outside the field
-__device__ __forceinline__ int cell_index(float q, int n) {
-  if (!(q >= 1.0f)) return 0;                    // negatives, [0, 1) and NaN
-  if (q >= (float)(n - 1)) return n - 1;         // +inf included
-  return (int)q;
-}
-
-__device__ __forceinline__ float height_at(const StairDev& D, float px, float py, float s, float c, float lx) {
-  const float wx = px + c * lx;
-  const float wy = py + s * lx;
-  const int col = cell_index((wx - D.ox) / D.hs, D.rows);
-  const int row = cell_index((wy - D.oy) / D.hs, D.cols);
-  return D.hf[(size_t)col * D.cols + row];
-}
 
 // One wavefront per env.  Every lane holds the env's pose, yaw, sine, cosine, level and draws (wave-uniform values); lane t owns the neighbouring samples
 // (t, t + 1), lane j < 4 entry j of the stored row, and lane t the columns t, t + 64, ... of the copied inner rows, so that consecutive lanes write
@@ -95,17 +54,12 @@ __global__ __launch_bounds__(WG) void k_stairinfo_step(StairDev D, Pose P, const
     if (t < NV) { *st = 0.0f; orow[n_in + t] = 0.0f; prow[n_in + t] = 0.0f; prow[n_in + NV + extra + t] = 0.0f; }
     return;
   }
-  const float px = P.pos[(size_t)b * P.pes], py = P.pos[P.pcs + (size_t)b * P.pes];
-  const float qw = P.quat[(size_t)b * P.qes], qx = P.quat[P.qcs + (size_t)b * P.qes], qy = P.quat[2 * P.qcs + (size_t)b * P.qes],
-              qz = P.quat[3 * P.qcs + (size_t)b * P.qes];
-  const float yaw = dm_atan2(2.0f * (qw * qz + qx * qy), 1.0f - 2.0f * (qy * qy + qz * qz));
-  float s, c;
-  dm_sincos(yaw, &s, &c);
+  const Base B = load_base(P, b);
   // the edge detector: lane t < n_samples - 1 forms dh_t; the first edge is the lowest set bit of the ballot
   const int np = D.n_samples - 1;
   const int k = t < np ? t : np - 1;                                // lanes beyond the pairs repeat the last one and do not vote
   const float x0 = D.xs[k], x1 = D.xs[k + 1];
-  const float dh = height_at(D, px, py, s, c, x1) - height_at(D, px, py, s, c, x0);
+  const float dh = height_ahead(D, B.px, B.py, B.s, B.c, x1) - height_ahead(D, B.px, B.py, B.s, B.c, x0);
   const unsigned long long sig = __ballot(t < np && fabsf(dh) > D.thr);
   const unsigned long long up = __ballot(dh > 0.0f);
   const int first = sig ? __ffsll((unsigned long long)sig) - 1 : 0;
@@ -119,7 +73,7 @@ __global__ __launch_bounds__(WG) void k_stairinfo_step(StairDev D, Pose P, const
   float height = D.row_h[r], depth = D.row_d[r];
   const float c0 = edge * D.s_e, c1 = height * D.s_h, c2 = depth * D.s_d, c3 = dir * D.s_dir;
   // the actor's copy
-  const double L = dr_level(D, D.curriculum_enabled ? *level : 1.0);
+  const double L = dr_level(D.dr, level);
   const bool on = L > 0.0;
   const float Lf = (float)L;
   if (on) {
@@ -155,22 +109,11 @@ __global__ __launch_bounds__(WG) void k_stairinfo_step(StairDev D, Pose P, const
   }
 }
 
-__global__ __launch_bounds__(WG) void k_stairinfo_clear(float* __restrict__ stored, int n_envs, const int* __restrict__ idx, int n_sel) {
-  const long long i = (long long)blockIdx.x * WG + threadIdx.x, total = (long long)(idx ? n_sel : n_envs) * NV;
-  if (i >= total) return;
-  const int r = (int)(i / NV), k = (int)(i - (long long)r * NV);
-  const int b = idx ? idx[r] : r;
-  if (b >= 0 && b < n_envs) stored[(size_t)b * NV + k] = 0.0f;
-}
-
 }  // namespace
 
 struct go2sim_stairinfo {
   int device = 0;
   StairDev dev = {};
-  float* hf = nullptr;
-  float* tab = nullptr;     // xs | row_h | row_d
-  float* stored = nullptr;
   uint32_t step = 0;
 };
 
@@ -181,41 +124,35 @@ int go2sim_stairinfo_create(int device, const go2sim_stairinfo_cfg_t* cfg, const
   if (!out || !cfg || !hf || !sample_x || !row_heights || !row_depths) return GO2SIM_E_BADARG;
   const go2sim_stairinfo_cfg_t& c = *cfg;
   if (c.n_envs < 1 || c.n_samples < 2 || c.n_samples > MAX_SAMPLES || c.n_rows < 1 || c.n_rows > MAX_ROWS) return GO2SIM_E_BADARG;
-  if (c.hf_rows < 1 || c.hf_cols < 1 || (long long)c.hf_rows * c.hf_cols > (1LL << 30) || !(c.horizontal_scale > 0.0)) return GO2SIM_E_BADARG;
+  if (!field_args_ok(c.hf_rows, c.hf_cols, c.horizontal_scale)) return GO2SIM_E_BADARG;
   if (!(c.max_range >= 0.0) || !(c.threshold >= 0.0) || !std::isfinite(c.max_range) || !std::isfinite(c.threshold)) return GO2SIM_E_BADARG;
-  const double all[] = {c.edge_dist_scale, c.height_scale, c.depth_scale, c.direction_scale, c.edge_noise_std, c.height_noise_std, c.depth_noise_std,
-                        c.direction_flip_prob, c.latency_prob, c.full_blackout_prob, c.dr_phase1_level, c.dr_terrain_gate, c.origin_x, c.origin_y,
-                        c.horizontal_scale, c.vertical_scale};
-  for (double v : all)
-    if (v != v) return GO2SIM_E_BADARG;
-  HIPCHK(hipSetDevice(device));
+  if (nan_in({c.edge_dist_scale, c.height_scale, c.depth_scale, c.direction_scale, c.edge_noise_std, c.height_noise_std, c.depth_noise_std,
+              c.direction_flip_prob, c.latency_prob, c.full_blackout_prob, c.dr_phase1_level, c.dr_terrain_gate, c.origin_x, c.origin_y, c.horizontal_scale,
+              c.vertical_scale}))
+    return GO2SIM_E_BADARG;
+  HIPCHK(TAG, hipSetDevice(device));
   go2sim_stairinfo* h = new (std::nothrow) go2sim_stairinfo();
   if (!h) return GO2SIM_E_NOMEM;
   h->device = device;
-  const size_t cells = (size_t)c.hf_rows * c.hf_cols, ntab = (size_t)c.n_samples + 2 * (size_t)c.n_rows, nst = (size_t)c.n_envs * NV;
-  if (hipMalloc((void**)&h->hf, cells * sizeof(float)) != hipSuccess || hipMalloc((void**)&h->tab, ntab * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&h->stored, nst * sizeof(float)) != hipSuccess) {
-    go2sim_stairinfo_destroy(h);
-    return GO2SIM_E_NOMEM;
-  }
-  std::vector<float> hfm(cells), tab(ntab);
-  for (size_t k = 0; k < cells; ++k) hfm[k] = (float)hf[k] * (float)c.vertical_scale;      // as go2sim_set_terrain forms the env's own copy
+  StairDev& D = h->dev;
+  std::vector<float> tab((size_t)c.n_samples + 2 * (size_t)c.n_rows);
   for (int k = 0; k < c.n_samples; ++k) tab[k] = sample_x[k];
   for (int k = 0; k < c.n_rows; ++k) { tab[c.n_samples + k] = row_heights[k]; tab[c.n_samples + c.n_rows + k] = row_depths[k]; }
-  if (hipMemcpy(h->hf, hfm.data(), cells * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(h->tab, tab.data(), ntab * sizeof(float), hipMemcpyHostToDevice) != hipSuccess || hipMemset(h->stored, 0, nst * sizeof(float)) != hipSuccess ||
-      hipDeviceSynchronize() != hipSuccess) {
+  int rc = upload_field(&D, hf, c.hf_rows, c.hf_cols, c.origin_x, c.origin_y, c.horizontal_scale, c.vertical_scale);
+  if (rc == GO2SIM_E_OK) rc = dev_array((float**)&D.xs, tab.data(), tab.size());
+  if (rc == GO2SIM_E_OK) rc = dev_array(&D.stored, (const float*)nullptr, (size_t)c.n_envs * NV);
+  if (rc == GO2SIM_E_OK && hipDeviceSynchronize() != hipSuccess) rc = GO2SIM_E_HIP;
+  if (rc != GO2SIM_E_OK) {
     go2sim_stairinfo_destroy(h);
-    return GO2SIM_E_HIP;
+    return rc;
   }
-  StairDev& D = h->dev;
-  D.hf = h->hf; D.xs = h->tab; D.row_h = D.xs + c.n_samples; D.row_d = D.row_h + c.n_rows; D.stored = h->stored;
-  D.rows = c.hf_rows; D.cols = c.hf_cols; D.n_envs = c.n_envs; D.n_samples = c.n_samples; D.n_rows = c.n_rows;
-  D.ox = (float)c.origin_x; D.oy = (float)c.origin_y; D.hs = (float)c.horizontal_scale; D.max_range = (float)c.max_range; D.thr = (float)c.threshold;
+  D.row_h = D.xs + c.n_samples; D.row_d = D.row_h + c.n_rows;
+  D.n_envs = c.n_envs; D.n_samples = c.n_samples; D.n_rows = c.n_rows;
+  D.max_range = (float)c.max_range; D.thr = (float)c.threshold;
   D.s_e = (float)c.edge_dist_scale; D.s_h = (float)c.height_scale; D.s_d = (float)c.depth_scale; D.s_dir = (float)c.direction_scale;
   D.std_e = (float)c.edge_noise_std; D.std_h = (float)c.height_noise_std; D.std_d = (float)c.depth_noise_std;
   D.flip_prob = c.direction_flip_prob; D.latency_prob = c.latency_prob; D.blackout_prob = c.full_blackout_prob;
-  D.phase1 = c.dr_phase1_level; D.gate = c.dr_terrain_gate; D.dr_schedule = c.dr_schedule != 0; D.curriculum_enabled = c.curriculum_enabled != 0;
+  D.dr = DrSched{c.dr_phase1_level, c.dr_terrain_gate, c.dr_schedule != 0, c.curriculum_enabled != 0};
   D.k0 = (uint32_t)seed; D.k1 = (uint32_t)(seed >> 32);
   *out = h;
   return GO2SIM_E_OK;
@@ -223,7 +160,7 @@ int go2sim_stairinfo_create(int device, const go2sim_stairinfo_cfg_t* cfg, const
 
 int go2sim_stairinfo_destroy(go2sim_stairinfo_t* h) {
   if (!h) return GO2SIM_E_BADARG;
-  (void)hipFree(h->hf); (void)hipFree(h->tab); (void)hipFree(h->stored);
+  (void)hipFree((void*)h->dev.hf); (void)hipFree((void*)h->dev.xs); (void)hipFree(h->dev.stored);
   delete h;
   return GO2SIM_E_OK;
 }
@@ -241,44 +178,29 @@ int go2sim_stairinfo_set_step(go2sim_stairinfo_t* h, uint32_t step) {
 }
 
 int go2sim_stairinfo_clear(go2sim_stairinfo_t* h, const int* envs_idx, int n_sel, void* stream) {
-  if (!h || (envs_idx && n_sel < 0)) return GO2SIM_E_BADARG;
-  const long long total = (long long)(envs_idx ? n_sel : h->dev.n_envs) * NV;
-  if (total == 0) return GO2SIM_E_OK;
-  hipLaunchKernelGGL(k_stairinfo_clear, dim3((unsigned)((total + WG - 1) / WG)), dim3(WG), 0, (hipStream_t)stream, h->stored, h->dev.n_envs, envs_idx, n_sel);
-  HIPCHK(hipGetLastError());
-  return GO2SIM_E_OK;
+  return h ? clear_rows(TAG, h->dev.stored, h->dev.n_envs, NV, envs_idx, n_sel, stream) : GO2SIM_E_BADARG;
 }
 
 int go2sim_stairinfo_get_state(go2sim_stairinfo_t* h, float* rows4, void* stream) {
   if (!h || !rows4) return GO2SIM_E_BADARG;
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(hipMemcpyAsync(rows4, h->stored, (size_t)h->dev.n_envs * NV * sizeof(float), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return GO2SIM_E_OK;
+  return copy_wait(TAG, hipMemcpyDeviceToHost, stream, {{rows4, h->dev.stored, (size_t)h->dev.n_envs * NV * sizeof(float)}});
 }
 
 int go2sim_stairinfo_set_state(go2sim_stairinfo_t* h, const float* rows4, void* stream) {
   if (!h || !rows4) return GO2SIM_E_BADARG;
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(hipMemcpyAsync(h->stored, rows4, (size_t)h->dev.n_envs * NV * sizeof(float), hipMemcpyHostToDevice, s));
-  HIPCHK(hipStreamSynchronize(s));                          // the source is the caller's host memory
-  return GO2SIM_E_OK;
+  return copy_wait(TAG, hipMemcpyHostToDevice, stream, {{h->dev.stored, rows4, (size_t)h->dev.n_envs * NV * sizeof(float)}});
 }
 
 int go2sim_stairinfo_step(go2sim_stairinfo_t* h, int n, const float* pos, long long pos_comp_stride, long long pos_env_stride, const float* quat,
                           long long quat_comp_stride, long long quat_env_stride, const int* terrain_row, const uint8_t* reset, const double* level,
                           const float* obs, const float* priv, int n_in, float* obs_out, float* priv_out, void* stream) {
-  if (!h || n != h->dev.n_envs || !pos || !quat || !obs_out || !priv_out || n_in < 0 || n_in > (1 << 20)) return GO2SIM_E_BADARG;
-  if (pos_comp_stride < 0 || pos_env_stride < 0 || quat_comp_stride < 0 || quat_env_stride < 0) return GO2SIM_E_BADARG;
+  if (!h || n != h->dev.n_envs || !pose_args_ok(pos, pos_comp_stride, pos_env_stride, quat, quat_comp_stride, quat_env_stride)) return GO2SIM_E_BADARG;
   if (!terrain_row && h->dev.n_rows > 1) return GO2SIM_E_BADARG;
-  if (h->dev.curriculum_enabled && !level) return GO2SIM_E_BADARG;
-  if ((obs == nullptr) != (priv == nullptr) || (obs == nullptr) != (n_in == 0)) return GO2SIM_E_BADARG;
-  if (obs_out == priv_out || (obs && ((const float*)obs_out == obs || (const float*)obs_out == priv || (const float*)priv_out == obs || (const float*)priv_out == priv)))
-    return GO2SIM_E_BADARG;
+  if ((h->dev.dr.curriculum_enabled && !level) || !rows_args_ok(obs, priv, n_in, obs_out, priv_out)) return GO2SIM_E_BADARG;
   const Pose P = {pos, quat, pos_comp_stride, pos_env_stride, quat_comp_stride, quat_env_stride};
   hipLaunchKernelGGL(k_stairinfo_step, dim3((n + ENVS_PER_WG - 1) / ENVS_PER_WG), dim3(WG), 0, (hipStream_t)stream, h->dev, P, terrain_row, reset, level, h->step,
                      obs, priv, n_in, obs_out, priv_out);
-  HIPCHK(hipGetLastError());
+  HIPCHK(TAG, hipGetLastError());
   h->step += 1u;
   return GO2SIM_E_OK;
 }

@@ -24,16 +24,16 @@ import math
 
 import torch
 
-from .capi import C, EnvGlobals, Go2Sim, Go2SimError, load_hip_lib, state_header_mismatch
+from .capi import C, EnvGlobals, Go2Sim, Go2SimError, _as_device_tensor, load_hip_lib, state_header_mismatch
 from .configs import CONTACT_TERM_NAMES, build_stair_terrain, flatten_base_cfg, flatten_walk_cfg
 from .contact_terms import DEFAULT_BODY_CONTACT_NAMES, ContactTerms, contact_term_scales, resolve_body_links
-from .lidar import LidarScan, check_lidar_widths, env_pose_ptrs, lidar_enabled, lidar_layout
+from .lidar import LidarScan, env_pose_ptrs, lidar_enabled, lidar_layout
 from .model_blob import pack_model
-from .stairinfo import NUM_STAIR_INFO, StairInfo, check_one_exteroceptive_layout, check_stair_info_widths, env_rows_ptr, stair_info_enabled
+from .stairinfo import NUM_STAIR_INFO, StairInfo, check_one_exteroceptive_layout, env_rows_ptr, stair_info_enabled
 from .terrain_manager import TerrainManager
 from .terrain_tiles import install_terrain, is_tile_terrain_cfg
 from .terrain_wells import build_stairwell_terrain, is_well_terrain_cfg, well_centers
-from .wells import WellScan, check_well_widths, well_scan_shape
+from .wells import WellScan, well_scan_shape
 
 _DEVICE = None
 _SEED = 1
@@ -51,23 +51,6 @@ def init(backend=None, precision="32", logging_level=None, performance_mode=True
     if seed is not None:
         _SEED = int(seed)
     return _DEVICE
-
-
-def _as_device_tensor(ptr, shape, dtype, device):
-    """Zero-copy torch view of library-owned device memory (no ownership transfer, include/go2sim.h)."""
-    itemsize = torch.empty((), dtype=dtype).element_size()
-    n = 1
-    for s in shape:
-        n *= s
-
-    class _Mem:
-        __cuda_array_interface__ = {
-            "shape": tuple(shape), "typestr": {torch.float32: "<f4", torch.int32: "<i4", torch.uint8: "|u1"}[dtype],
-            "data": (int(ptr), False), "version": 2, "strides": None,
-        }
-
-    assert n * itemsize > 0
-    return torch.as_tensor(_Mem(), device=device)
 
 
 def is_base_env_cfg(env_cfg, obs_cfg):
@@ -153,26 +136,23 @@ def mirror_tables(env_cfg, obs_cfg):
 
 
 ENV_STATE_VERSION = 1
+LAYOUT_LAUNCHES = (StairInfo, LidarScan, WellScan)       # the launches that widen the observation rows: an env has at most one
 
 
-def env_state_schema(family, num_envs, num_obs, num_critic_obs, core_bytes=None, lidar_points=None, n_globals=None, cterms=False):
+def env_state_schema(family, num_envs, num_obs, num_critic_obs, core_bytes=None, lidar_points=None, n_globals=None, cterms=False, launches=None):
     """What ``Go2Env.state_dict()`` of such an env holds: {key: int | str | (dtype, shape)}; a shape entry None is not checked.  `family` is one of
     base, walk, stairs, stairs_lidar, stairs_info, rough, stairwell; `num_critic_obs` the width of the privileged rows as the env keeps them;
-    `cterms`: the env runs the contact-terms launch (a non-zero body_contact or stumble scale)."""
+    `cterms`: the env runs the contact-terms launch (a non-zero body_contact or stumble scale); `launches`: an env's own list, in place of both."""
     B, f32 = int(num_envs), torch.float32
     schema = {"version": int, "family": str, "num_envs": int, "num_obs": int, "num_critic_obs": int, "terrain_rows_locked": int, "steps_since_poll": int,
               "core": (torch.uint8, (core_bytes,)), "obs_buf": (f32, (B, int(num_obs))), "privileged_obs_buf": (f32, (B, int(num_critic_obs))),
               "rew_buf": (f32, (B,)), "reset_buf": (torch.uint8, (B,)), "time_outs": (f32, (B,)),
               "extras_snapshot": (f32, (None,)), "extras_full_snapshot": (f32, (None,))}
-    if family == "stairs_lidar":
-        schema.update(lidar_step=int, lidar_scan=(f32, (B, lidar_points)))
-    if family == "stairs_info":
-        schema.update(stairinfo_step=int, stairinfo_rows=(f32, (B, NUM_STAIR_INFO)))
-    if family == "stairwell":
-        schema.update(wells_alive_sum=(f32, (B,)), wells_alive_steps=(torch.int32, (B,)), wells_alive_ep=(f32, (B,)), wells_alive_log=(f32, ()))
-    if cterms:                                                          # body_contact, then stumble (include/go2sim_cterms.h)
-        schema.update(cterms_sum=(f32, (2, B)), cterms_steps=(torch.int32, (2, B)), cterms_ep=(f32, (2, B)), cterms_log=(f32, (2,)),
-                      cterms_count=(f32, (B,)))
+    if launches is None:                                                # each launch owns its keys
+        for kind in [k for k in LAYOUT_LAUNCHES if k.STATE_FAMILY == family] + [ContactTerms] * bool(cterms):
+            schema.update(kind.schema_of(B, lidar_points))
+    for launch in launches or ():
+        schema.update(launch.state_schema(B))
     return schema
 
 
@@ -206,12 +186,19 @@ class Go2Env:
         if show_viewer:
             raise Go2SimError("the viewer is outside the accelerated path (SURVEY.md section 8f)")
         check_one_exteroceptive_layout(env_cfg)
-        use_wells = is_well_terrain_cfg(env_cfg.get("terrain")) and not is_base_env_cfg(env_cfg, obs_cfg)
+        base = is_base_env_cfg(env_cfg, obs_cfg)
+        use_wells = is_well_terrain_cfg(env_cfg.get("terrain")) and not base
         if use_wells and (env_cfg.get("lidar") or env_cfg.get("stair_info")):
             raise Go2SimError("the stairwell terrain has its own 11 x 11 scan: it does not combine with env_cfg['lidar'] or env_cfg['stair_info']")
-        if use_wells:
-            check_well_widths(env_cfg, obs_cfg)                             # (before anything touches the device)
-        cterm_scales = (0.0, 0.0) if is_base_env_cfg(env_cfg, obs_cfg) else contact_term_scales(reward_cfg)
+        # The layout launch: the step kernels write inner rows without a height scan (49 / 105, 45 / 101 with pls_enable=False), one more launch writes
+        # the wider rows -- the stair info (go2_env_stair_lidar_2.py; include/go2sim_stairinfo.h), the LIDAR scans (go2_env_stair_lidar.py;
+        # include/go2sim_lidar.h), or the stairwell's scan with its alive term (go2_env_stair6_Omni.py; include/go2sim_wells.h)
+        layout = None if base else StairInfo if stair_info_enabled(env_cfg) else LidarScan if lidar_enabled(env_cfg) else WellScan if use_wells else None
+        inner_obs_cfg = obs_cfg
+        if layout is not None:                                              # obs_cfg must carry the layout's widths (before anything touches the device)
+            inner_widths = layout.inner_widths(env_cfg, obs_cfg)
+            inner_obs_cfg = dict(obs_cfg, num_obs=inner_widths[0], num_privileged_obs=inner_widths[1])
+        cterm_scales = (0.0, 0.0) if base else contact_term_scales(reward_cfg)
         if any(cterm_scales):                                               # an unknown link name is refused; the reference warns and drops the term
             cterm_body_links = resolve_body_links(env_cfg.get("body_contact_names", list(DEFAULT_BODY_CONTACT_NAMES)))
         self.device = device if device is not None else (_DEVICE if _DEVICE is not None else init())
@@ -233,33 +220,14 @@ class Go2Env:
         # the two env families of the reference: walk / stairs (go2_env_walk.py / go2_env_stair.py: 16 actions and 49 / 104 / 182 obs with per-leg
         # stiffness, 12 and 45 / 100 / 178 without) and base (go2_env_base.py: 12 / 45).  The walk family's train scripts set `pls_enable` and
         # `num_privileged_obs`, the base env's set neither (go2_train_crouch.py / go2_train_jump.py)
-        self.is_base_env = is_base_env_cfg(env_cfg, obs_cfg)
-        self._lidar = None
-        self._stairinfo = None
-        self._wells = None
-        self._cterms = None
+        self.is_base_env = base
+        self._lidar = self._stairinfo = self._wells = self._cterms = None    # the launch handles by name; self._launches is what the env runs
         self.terrain = None                                                # the TerrainManager of the rough-terrain env
+        B, dev, handle_seed = num_envs, self.device, _SEED if seed is None else int(seed)
         if self.is_base_env:
             fcfg, icfg, self._reward_names = flatten_base_cfg(num_envs, env_cfg, obs_cfg, reward_cfg, command_cfg)
             self.num_privileged_obs = None
         else:
-            # the LIDAR layout (go2_env_stair_lidar.py): the step kernels run the 49 / 105 (45 / 101) layout without a height scan into inner rows,
-            # the scan launch writes the wider rows (include/go2sim_lidar.h)
-            inner_obs_cfg = obs_cfg
-            use_stair_info = stair_info_enabled(env_cfg)
-            if use_stair_info:
-                # the stair-info layout (go2_env_stair_lidar_2.py): inner rows as for the LIDAR layout, the stair-info launch writes the wider rows
-                # (include/go2sim_stairinfo.h)
-                self._lidar_n_in = n_in = check_stair_info_widths(env_cfg, obs_cfg)
-                inner_obs_cfg = dict(obs_cfg, num_obs=n_in, num_privileged_obs=n_in + C["GO2SIM_STAIRINFO_PRIV_EXTRA"])
-            elif lidar_enabled(env_cfg):
-                self._lidar_n_in = n_in = check_lidar_widths(env_cfg, obs_cfg)
-                inner_obs_cfg = dict(obs_cfg, num_obs=n_in, num_privileged_obs=n_in + C["GO2SIM_LIDAR_PRIV_EXTRA"])
-            elif use_wells:
-                # the stairwell layout (go2_env_stair6_Omni.py): the actor row is the step kernels' own, the privileged row is an inner row without a
-                # height scan, the wells launch writes the wider one and adds the alive term (include/go2sim_wells.h)
-                self._lidar_n_in = n_in = check_well_widths(env_cfg, obs_cfg)
-                inner_obs_cfg = dict(obs_cfg, num_obs=n_in, num_privileged_obs=n_in + C["GO2SIM_WELLS_PRIV_EXTRA"])
             fcfg, icfg, self._reward_names = flatten_walk_cfg(num_envs, env_cfg, inner_obs_cfg, reward_cfg, command_cfg,
                                                               freeze_curriculum=freeze_curriculum, shared_globals=shared_globals)
             layouts = {(16, 49): (None, 104, 182)}
@@ -276,65 +244,60 @@ class Go2Env:
             if is_tile_terrain_cfg(terrain_cfg):
                 # the rough-terrain env (go2_env_Omni_kplearn_varied_terrain.py:  a terrain dictionary with `subterrain_types` or a `height_field`):
                 # the manager makes the morph, the library takes its field and runs ground height, boundary and spawn itself (include/go2sim_tiles.h)
-                if inner_obs_cfg is not obs_cfg:
+                if layout is not None:
                     raise Go2SimError("the LIDAR / stair-info layouts belong to the stair terrain, not to a tile terrain")
                 self.terrain = TerrainManager(terrain_cfg, num_envs, device=self.device)
                 morph = self.terrain.build_terrain_morph()
                 install_terrain(self._sim, morph.height_field, morph.horizontal_scale, morph.vertical_scale, list(morph.pos))
                 self.terrain.post_build(morph)
                 self.terrain.bind(self)
-            elif use_wells:                                                       # go2_env_stair6_Omni.py:371-397: the grid of stairwells
-                hf, info = build_stairwell_terrain(terrain_cfg)
-                self._terrain_info = dict(info, row_centers=well_centers(info), num_difficulty_rows=info["num_difficulty_levels"])
-                self._sim.set_terrain(hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"])
-                self._wells = WellScan(terrain_cfg, num_envs, hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"],
-                                       n_levels=info["num_difficulty_levels"], alive_scale=float(self.reward_scales.get("alive", 0.0)), dt=self.dt,
-                                       device=self.device)
-            elif terrain_cfg is not None and terrain_cfg.get("enabled", False):   # go2_env_stair.py:352-433: gs.morphs.Terrain instead of the plane
-                hf, info = build_stair_terrain(terrain_cfg)
+            elif terrain_cfg is not None and terrain_cfg.get("enabled", False):
+                if use_wells:                                                     # go2_env_stair6_Omni.py:371-397: the grid of stairwells
+                    hf, info = build_stairwell_terrain(terrain_cfg)
+                    info = dict(info, row_centers=well_centers(info), num_difficulty_rows=info["num_difficulty_levels"])
+                else:                                                             # go2_env_stair.py:352-433: gs.morphs.Terrain instead of the plane
+                    hf, info = build_stair_terrain(terrain_cfg)
                 self._terrain_info = info
                 self._sim.set_terrain(hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"])
-                if use_stair_info:
-                    curr = env_cfg.get("curriculum", {}) or {}
+                field = (B, hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"])
+                noise = dict(seed=handle_seed, dr_schedule=env_cfg.get("dr_schedule", None),
+                             curriculum_enabled=bool((env_cfg.get("curriculum", {}) or {}).get("enabled", False)), device=dev)
+                if layout is StairInfo:
                     depths = info.get("step_depths_m", [float(info.get("step_depth_m", 0.30))] * info["num_difficulty_rows"])
-                    self._stairinfo = StairInfo(env_cfg["stair_info"], num_envs, hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"],
-                                                info["step_heights_m"], depths, seed=_SEED if seed is None else int(seed),
-                                                dr_schedule=env_cfg.get("dr_schedule", None), curriculum_enabled=bool(curr.get("enabled", False)),
-                                                device=self.device)
-                elif inner_obs_cfg is not obs_cfg:
-                    curr = env_cfg.get("curriculum", {}) or {}
-                    self._lidar = LidarScan(env_cfg["lidar"], num_envs, hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"],
-                                            seed=_SEED if seed is None else int(seed), dr_schedule=env_cfg.get("dr_schedule", None),
-                                            curriculum_enabled=bool(curr.get("enabled", False)), device=self.device)
+                    self._stairinfo = StairInfo(env_cfg["stair_info"], *field, info["step_heights_m"], depths, **noise)
+                elif layout is LidarScan:
+                    self._lidar = LidarScan(env_cfg["lidar"], *field, **noise)
+                elif layout is WellScan:
+                    self._wells = WellScan(terrain_cfg, *field, n_levels=info["num_difficulty_levels"], alive_scale=self.reward_scales.get("alive"), dt=self.dt,
+                                           device=dev)
         self._sim.env_configure(fcfg, icfg)
 
-        B, dev = num_envs, self.device
+        self.body_contact_count = torch.zeros(B, device=dev)               # links of body_contact_names in contact at the last step, per env
+        cterm_keys = [] if self.is_base_env else [n for n in CONTACT_TERM_NAMES if n in self.reward_scales]
         if any(cterm_scales):
             # body_contact (go2_env_stair_lidar_2.py) and stumble (go2_env_terrain.py): one launch after the step's own reads the links' contact forces
             # where the solve left them and adds both terms (include/go2sim_cterms.h)
             self._cterms = ContactTerms(B, body_links=cterm_body_links, body_contact_scale=cterm_scales[0], stumble_scale=cterm_scales[1],
                                         body_contact_threshold=float(env_cfg.get("body_contact_threshold", 1.0)),
-                                        stumble_threshold=float(reward_cfg.get("stumble_threshold", 5.0)), dt=self.dt, device=dev)
-            self._cterms_cf = self._sim.field_ptr(C["GO2SIM_F_CONTACT_FORCE"])   # SoA [link * 3 + comp][B]
-            self._cterms_ep = _as_device_tensor(self._cterms.ep_ptrs[0], (2, B), torch.float32, dev)   # per-env records of the last finished episode, one row per term
-            self._cterms_log = torch.zeros(2, device=dev)                   # the logged means, body_contact then stumble
-        self._cterm_keys = [] if self.is_base_env else [n for n in CONTACT_TERM_NAMES if n in self.reward_scales]
-        self._cterm_zero = torch.zeros((), device=dev)
-        self.body_contact_count = torch.zeros(B, device=dev)               # links of body_contact_names in contact at the last step, per env
-        if self._lidar is not None or self._stairinfo is not None:
-            # the step kernels' rows, rewritten every step, and what the scan launch reads in place: the base pose buffers and the curriculum level
-            self._inner_obs = torch.zeros(B, self._lidar_n_in, device=dev)
-            self._inner_priv = torch.zeros(B, self._lidar_n_in + C["GO2SIM_LIDAR_PRIV_EXTRA"], device=dev)
-            self._lidar_pose = env_pose_ptrs(self._sim)
-            self._lidar_level = self._sim.env_globals_ptr() + EnvGlobals.level.offset
-        if self._stairinfo is not None:
-            self._stairinfo_rows = env_rows_ptr(self._sim)                 # the env's terrain rows, read on the device at step time
-        if self._wells is not None:
-            self._inner_priv = torch.zeros(B, self._lidar_n_in + C["GO2SIM_WELLS_PRIV_EXTRA"], device=dev)
-            self._lidar_pose = env_pose_ptrs(self._sim)
-            self._alive_ep = _as_device_tensor(self._wells.alive_ep_ptr, (B,), torch.float32, dev)   # per-env record of the last finished episode's alive term
-            self._alive_log = torch.zeros((), device=dev)
-            self._has_alive = "alive" in self.reward_scales
+                                        stumble_threshold=float(reward_cfg.get("stumble_threshold", 5.0)), dt=self.dt, device=dev, report=cterm_keys,
+                                        count_out=self.body_contact_count)
+        # In the order the rewards are added: at most one layout launch (alive), then the contact terms (body_contact, stumble)
+        self._launches = [h for h in (self._stairinfo, self._lidar, self._wells, self._cterms) if h is not None]
+        # a zero scale without the launch: the key is accepted, nothing runs, the entry is zero
+        self._episode_zeros = {} if self._cterms is not None else dict.fromkeys(["rew_" + n for n in cterm_keys], torch.zeros((), device=dev))
+        # what the launches read in place: the base pose buffers, the curriculum level, the terrain rows, the links' contact forces (SoA [link * 3 + comp][B])
+        self._base_pose = env_pose_ptrs(self._sim)
+        self._level_ptr = self._sim.env_globals_ptr() + EnvGlobals.level.offset
+        self._terrain_rows_ptr = env_rows_ptr(self._sim)
+        self._contact_force_ptr = self._sim.field_ptr(C["GO2SIM_F_CONTACT_FORCE"])
+        # the step kernels' inner rows, rewritten every step (None: the step kernels write the env's own row)
+        self._inner_obs = torch.zeros(B, inner_widths[0], device=dev) if layout is not None and layout.WIDENS_OBS else None
+        self._inner_priv = torch.zeros(B, inner_widths[1], device=dev) if layout is not None else None
+        # names the env tests read: the inner rows' proprioceptive width (only with a layout launch) and the contact terms' per-env episode records
+        if layout is not None:
+            self._lidar_n_in = inner_widths[0]
+        if self._cterms is not None:
+            self._cterms_ep = self._cterms.ep
         self.obs_buf = torch.zeros(B, self.num_obs, device=dev)
         self.privileged_obs_buf = torch.zeros(B, 45 if self.is_base_env else (self.num_privileged_obs or self.num_obs + 55), device=dev)
         self.rew_buf = torch.zeros(B, device=dev)
@@ -380,30 +343,12 @@ class Go2Env:
         stream = torch.cuda.current_stream(self.device).cuda_stream
         self.obs_buf = torch.empty_like(self.obs_buf)                      # caching allocator: host-side only, no kernel
         self.privileged_obs_buf = torch.empty_like(self.privileged_obs_buf)
-        if self._stairinfo is not None:                                    # one more launch: both fours and the wider rows, straight into the fresh tensors
-            self._sim.env_step(a, self._inner_obs, self._inner_priv, self.rew_buf, self.reset_buf, self._time_outs, stream)
-            pos, quat, cs = self._lidar_pose
-            self._stairinfo.step(pos, (cs, 1), quat, (cs, 1), self._stairinfo_rows, self.reset_buf, self._lidar_level, self._inner_obs, self._inner_priv,
-                                 self._lidar_n_in, self.obs_buf, self.privileged_obs_buf)
-        elif self._wells is not None:                                      # one more launch: the 11 x 11 scan into the wider privileged row, and the alive term
-            self._sim.env_step(a, self.obs_buf, self._inner_priv, self.rew_buf, self.reset_buf, self._time_outs, stream)
-            pos, quat, cs = self._lidar_pose
-            self._wells.step(pos, (cs, 1), quat, (cs, 1), self.reset_buf, self._inner_priv, self._lidar_n_in, self.privileged_obs_buf,
-                             self.rew_buf if self._has_alive else None)
-            if self.log_extras and self._has_alive:
-                self._log_alive(self.reset_buf)
-        elif self._lidar is None:
-            self._sim.env_step(a, self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self._time_outs, stream)
-        else:                                                              # one more launch: the scans and the wider rows, straight into the fresh tensors
-            self._sim.env_step(a, self._inner_obs, self._inner_priv, self.rew_buf, self.reset_buf, self._time_outs, stream)
-            pos, quat, cs = self._lidar_pose
-            self._lidar.step(pos, (cs, 1), quat, (cs, 1), self.reset_buf, self._lidar_level, self._inner_obs, self._inner_priv, self._lidar_n_in,
-                             self.obs_buf, self.privileged_obs_buf)
-        if self._cterms is not None:                                       # one more launch: body_contact and stumble, after the alive term
-            n = self.num_envs
-            self._cterms.step(self._cterms_cf, (n, 3 * n, 1), self.reset_buf, self.rew_buf, self.body_contact_count)
+        self._sim.env_step(a, self.obs_buf if self._inner_obs is None else self._inner_obs,
+                           self.privileged_obs_buf if self._inner_priv is None else self._inner_priv, self.rew_buf, self.reset_buf, self._time_outs, stream)
+        for launch in self._launches:                                      # one more launch each, straight into the fresh tensors and onto the reward
+            launch.launch(self, self._inner_obs, self._inner_priv)
             if self.log_extras:
-                self._log_cterms(self.reset_buf)
+                launch.log(self.reset_buf)
         self._steps_since_poll += 1
         poll = self._steps_since_poll >= self.errno_poll_every             # RATE_CHECK_ERRNO = 10 substeps, simulator.py:45,267
         if poll:
@@ -427,11 +372,9 @@ class Go2Env:
         self._extras_snapshot = snap
         n = len(self._reward_names)
         self.extras["episode"] = dict(zip(self._episode_keys, snap[self._ep_off:self._ep_off + n].unbind(0)))
-        if self._wells is not None and self._has_alive:
-            self.extras["episode"]["rew_alive"] = self._alive_log
-        for name in self._cterm_keys:                                       # a zero scale: the key is accepted, nothing runs, the entry is zero
-            t = CONTACT_TERM_NAMES.index(name)
-            self.extras["episode"]["rew_" + name] = self._cterms_log[t] if self._cterms is not None and self._cterms.active[t] else self._cterm_zero
+        for launch in self._launches:
+            self.extras["episode"].update(launch.episode_entries())
+        self.extras["episode"].update(self._episode_zeros)
         if self._use_terrain:
             rows = snap.view(torch.int32)
             self.extras["episode"]["terrain_mean_row"] = rows[self._goff["terrain_row_sum"]].float() / rows[self._goff["last_reset_count"]].clamp(min=1).float()
@@ -449,36 +392,11 @@ class Go2Env:
             "cmd_ranges": {"lin_vel_x_range": d[g["cmd_x_lo"]:g["cmd_x_lo"] + 2], "lin_vel_y_range": d[g["cmd_y_lo"]:g["cmd_y_lo"] + 2],
                            "ang_vel_range": d[g["cmd_yaw_lo"]:g["cmd_yaw_lo"] + 2]},
         }
-        if self._stairinfo is not None:                                     # go2_env_stair_lidar_2.py:1232: the DR level the stair-info noise scales with
-            self.extras["curriculum"]["stair_noise_level"] = self._dr_level_of(d[g["level"]])
+        for launch in self._launches:
+            self.extras["curriculum"].update(launch.curriculum_entries(d[g["level"]]))
         self.extras["domain_randomization"] = {"friction": f[g["friction"]], "mass_shift": f[g["mass_shift"]],
                                                "com_shift": f[g["com_shift"]:g["com_shift"] + 3],
                                                "leg_mass_shift": f[g["leg_mass_shift"]:g["leg_mass_shift"] + 4]}
-
-    def _log_alive(self, mask):
-        """extras["episode"]["rew_alive"] as the core reports its terms: the mean, over the envs of the last reset, of episode sum / episode seconds
-        (the wells launch left each env's value in alive_ep); kept while no env is reset.  Device arithmetic on [n_envs] values, no synchronisation."""
-        m = mask.to(torch.float32)
-        n = m.sum()
-        self._alive_log = torch.where(n > 0, (self._alive_ep * m).sum() / n.clamp(min=1.0), self._alive_log)
-
-    def _log_cterms(self, mask):
-        """extras["episode"]["rew_body_contact"] / ["rew_stumble"], as _log_alive reports rew_alive: the means of the launch's ep records over the envs
-        of the last reset; kept while no env is reset.  Device arithmetic, no synchronisation."""
-        m = mask.to(torch.float32)
-        n = m.sum()
-        means = (self._cterms_ep * m).sum(1) / n.clamp(min=1.0)
-        self._cterms_log = torch.where(n > 0, means, self._cterms_log)
-
-    def _dr_level_of(self, level):
-        """_get_dr_level (go2_env_stair_lidar_2.py) of the curriculum level, a 0-dim float64 device tensor: no synchronisation."""
-        curr, sched = self.env_cfg.get("curriculum", {}) or {}, self.env_cfg.get("dr_schedule", None)
-        t = level if curr.get("enabled", False) else torch.ones_like(level)
-        if sched is None:
-            return t
-        p1, gate = float(sched.get("phase1_level", 0.15)), float(sched.get("terrain_gate", 0.50))
-        pr = ((t - gate) / max(1e-6, 1.0 - gate)).clamp(0.0, 1.0)
-        return torch.where(t < gate, torch.full_like(t, p1), p1 + (1.0 - p1) * pr)
 
     def _raise_on_errno(self, v):
         """rigid_solver.py:1189-1213: the exceptions scene.step raises from its errno poll."""
@@ -507,22 +425,22 @@ class Go2Env:
         """go2_env_walk.py:1242-1245 (reset_idx over all envs; obs_buf is not recomputed, as in the reference)."""
         stream = torch.cuda.current_stream(self.device).cuda_stream
         self._sim.env_reset(stream)
-        if self._lidar is not None:
-            self._lidar.clear()
-        if self._stairinfo is not None:
-            self._stairinfo.clear()
         self.reset_buf.fill_(1)
-        if self._wells is not None:
-            self._wells.clear()
-            if self.log_extras and self._has_alive:
-                self._log_alive(self.reset_buf)
-        if self._cterms is not None:
-            self._cterms.clear()
-            if self.log_extras:
-                self._log_cterms(self.reset_buf)
+        self._clear_launches()
         if self.log_extras:
             self._refresh_extras()
         return self.obs_buf, None
+
+    def _clear_launches(self, idx=None):
+        """the launches' share of a reset of the envs `idx` (None: all): stored rows := 0, episode terms handed over and their records logged"""
+        mask = self.reset_buf
+        if idx is not None and self.log_extras and any(launch.logs for launch in self._launches):
+            mask = torch.zeros(self.num_envs, device=self.device)
+            mask[idx.long()] = 1.0
+        for launch in self._launches:
+            launch.clear(idx)
+            if self.log_extras:
+                launch.log(mask)
 
     def reset_idx(self, envs_idx):
         """go2_env_walk.py:1156-1240: curriculum bookkeeping, "global" DR draws and per-env reset of ``envs_idx`` (index tensor / list)."""
@@ -530,44 +448,28 @@ class Go2Env:
         if idx.numel() == 0:
             return
         self._sim.env_reset_idx(idx, idx.numel(), torch.cuda.current_stream(self.device).cuda_stream)
-        if self._lidar is not None:
-            self._lidar.clear(idx)
-        if self._stairinfo is not None:
-            self._stairinfo.clear(idx)
         self.reset_buf[idx.long()] = 1
-        if self._wells is not None:
-            self._wells.clear(idx)
-            if self.log_extras and self._has_alive:
-                sel = torch.zeros(self.num_envs, device=self.device)
-                sel[idx.long()] = 1.0
-                self._log_alive(sel)
-        if self._cterms is not None:
-            self._cterms.clear(idx)
-            if self.log_extras:
-                sel = torch.zeros(self.num_envs, device=self.device)
-                sel[idx.long()] = 1.0
-                self._log_cterms(sel)
+        self._clear_launches(idx)
         if self.log_extras:
             self._refresh_extras()
+
+    _cterms_log = property(lambda self: self._cterms.ep_log)               # the contact terms' logged means, under the name the env tests read
 
     # ---- snapshots (include/go2sim_state.h, ENV_STATE.md) ---------------------------------
     @property
     def state_family(self):
         if self.is_base_env:
             return "base"
-        if self._lidar is not None:
-            return "stairs_lidar"
-        if self._stairinfo is not None:
-            return "stairs_info"
-        if self._wells is not None:
-            return "stairwell"
+        for launch in self._launches:
+            if launch.STATE_FAMILY:
+                return launch.STATE_FAMILY
         if self.terrain is not None:
             return "rough"
         return "stairs" if self._use_terrain else "walk"
 
     def _state_schema(self):
         schema = env_state_schema(self.state_family, self.num_envs, self.num_obs, self.privileged_obs_buf.shape[1], self._sim.state_size(),
-                                  None if self._lidar is None else self._lidar.n_actor, cterms=self._cterms is not None)
+                                  launches=self._launches)
         expect = {"version": ENV_STATE_VERSION, "family": self.state_family, "num_envs": self.num_envs, "num_obs": self.num_obs,
                   "num_critic_obs": int(self.privileged_obs_buf.shape[1])}
         return schema, expect
@@ -585,17 +487,8 @@ class Go2Env:
         for key, t in (("obs_buf", self.obs_buf), ("privileged_obs_buf", self.privileged_obs_buf), ("rew_buf", self.rew_buf), ("reset_buf", self.reset_buf),
                        ("time_outs", self._time_outs), ("extras_snapshot", self._extras_snapshot), ("extras_full_snapshot", self._extras_full_snapshot)):
             sd[key] = torch.zeros(0) if t is None else t.detach().cpu().clone()
-        if self._lidar is not None:
-            sd.update(lidar_step=int(self._lidar.step_count), lidar_scan=self._lidar.stored_scan())
-        if self._stairinfo is not None:
-            sd.update(stairinfo_step=int(self._stairinfo.step_count), stairinfo_rows=self._stairinfo.stored_rows())
-        if self._wells is not None:
-            alive_sum, alive_steps = self._wells.alive_state()
-            sd.update(wells_alive_sum=alive_sum, wells_alive_steps=alive_steps, wells_alive_ep=self._alive_ep.cpu().clone(), wells_alive_log=self._alive_log.cpu().clone())
-        if self._cterms is not None:
-            sums, steps, ep = self._cterms.state()
-            sd.update(cterms_sum=sums, cterms_steps=steps, cterms_ep=ep, cterms_log=self._cterms_log.cpu().clone(),
-                      cterms_count=self.body_contact_count.cpu().clone())
+        for launch in self._launches:
+            sd.update(launch.state_dict())
         return sd
 
     def load_state_dict(self, state):
@@ -617,20 +510,8 @@ class Go2Env:
         self.obs_buf, self.privileged_obs_buf = state["obs_buf"].to(dev), state["privileged_obs_buf"].to(dev)
         self.rew_buf.copy_(state["rew_buf"]); self.reset_buf.copy_(state["reset_buf"]); self._time_outs.copy_(state["time_outs"])
         self._terrain_rows_locked, self._steps_since_poll = bool(state["terrain_rows_locked"]), int(state["steps_since_poll"])
-        if self._lidar is not None:
-            self._lidar.step_count = state["lidar_step"]
-            self._lidar.set_stored_scan(state["lidar_scan"])
-        if self._stairinfo is not None:
-            self._stairinfo.step_count = state["stairinfo_step"]
-            self._stairinfo.set_stored_rows(state["stairinfo_rows"])
-        if self._wells is not None:
-            self._wells.set_alive_state(state["wells_alive_sum"], state["wells_alive_steps"])
-            self._alive_ep.copy_(state["wells_alive_ep"])
-            self._alive_log = state["wells_alive_log"].to(dev)
-        if self._cterms is not None:
-            self._cterms.set_state(state["cterms_sum"], state["cterms_steps"], state["cterms_ep"])
-            self._cterms_log = state["cterms_log"].to(dev)
-            self.body_contact_count.copy_(state["cterms_count"])
+        for launch in self._launches:
+            launch.load_state_dict(state)
         self.extras = {"observations": {"critic": self.privileged_obs_buf if self.num_privileged_obs else self.obs_buf}, "time_outs": self._time_outs}
         self._extras_snapshot = self._extras_full_snapshot = None
         n_glob = self._glob_f32.numel()
@@ -662,14 +543,9 @@ class Go2Env:
         p = torch.as_tensor(pos, device=self.device, dtype=torch.float32).reshape(idx.numel(), 3).contiguous()
         q = None if quat is None else torch.as_tensor(quat, device=self.device, dtype=torch.float32).reshape(idx.numel(), 4).contiguous()
         self._sim.env_respawn(idx, p, q, clear_buffers, idx.numel(), torch.cuda.current_stream(self.device).cuda_stream)
-        if self._lidar is not None and clear_buffers and idx.numel():
-            self._lidar.clear(idx)
-        if self._stairinfo is not None and clear_buffers and idx.numel():
-            self._stairinfo.clear(idx)
-        if self._wells is not None and clear_buffers and idx.numel():
-            self._wells.clear(idx)
-        if self._cterms is not None and clear_buffers and idx.numel():
-            self._cterms.clear(idx)
+        if clear_buffers and idx.numel():
+            for launch in self._launches:
+                launch.clear(idx)
 
     def respawn_at_start(self, envs_idx=(0,)):
         """go2_eval_stairs.py:314-361: back to the spawn point of the env's terrain row (or base_init_pos on flat ground)."""

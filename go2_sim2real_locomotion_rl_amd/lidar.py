@@ -11,7 +11,8 @@ import ctypes
 import numpy as np
 import torch
 
-from .capi import C, Go2SimError, Handle, _ptr, load_hip_lib
+from .capi import C, EnvLaunch, Go2SimError, _ptr, check_layout_widths
+from .configs import dr_schedule_params
 
 
 class LidarCfg(ctypes.Structure):
@@ -66,13 +67,7 @@ def lidar_widths(env_cfg):
 
 def check_lidar_widths(env_cfg, obs_cfg):
     """The proprioceptive width n_in of a LIDAR cfg whose obs_cfg carries the widths its grids give; Go2SimError (naming both) otherwise."""
-    n_in, want_obs, want_priv = lidar_widths(env_cfg)
-    num_actions, have = int(env_cfg["num_actions"]), (obs_cfg["num_obs"], obs_cfg.get("num_privileged_obs"))
-    if num_actions not in ((16,) if env_cfg.get("pls_enable", False) else (16, 12)):
-        raise Go2SimError(f"the LIDAR layout has 16 actions (12 with pls_enable=False), got {num_actions}")
-    if have != (want_obs, want_priv):
-        raise Go2SimError(f"obs_cfg gives num_obs / num_privileged_obs = {have[0]} / {have[1]}, the lidar cfg's grids give {want_obs} / {want_priv}")
-    return n_in
+    return check_layout_widths("LIDAR", env_cfg, obs_cfg, lidar_widths(env_cfg))
 
 
 def env_pose_ptrs(sim):
@@ -82,73 +77,50 @@ def env_pose_ptrs(sim):
     return pos.value, quat.value, cs.value
 
 
-class LidarScan(Handle):
+class LidarScan(EnvLaunch):
+    NAME, STATE_FAMILY = "lidar", "stairs_lidar"
+
     def __init__(self, cfg, n_envs, hf_int16, horizontal_scale, vertical_scale, origin, *, seed=1, dr_schedule=None, curriculum_enabled=False, device=None):
-        if not torch.cuda.is_available():
-            raise Go2SimError("no ROCm GPU visible: the go2sim product path has no CPU fallback")
+        EnvLaunch.__init__(self, n_envs, device)
         if not cfg.get("enabled", True):
             raise Go2SimError("the lidar cfg is disabled: there is nothing to scan")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.n_envs = int(n_envs)
         self.layout = lay = lidar_layout(cfg)
         self.n_actor, self.n_critic = lay["actor_xy"].shape[1], lay["critic_xy"].shape[1]
         hf = np.ascontiguousarray(hf_int16, dtype=np.int16)
         c = LidarCfg()
         for name in ("height_noise_std", "dropout_prob", "vertical_offset_std", "latency_prob", "full_blackout_prob", "height_clip", "height_scale"):
             setattr(c, name, lay[name])
-        c.dr_schedule = int(dr_schedule is not None)
-        if dr_schedule is not None:                                         # the defaults of flatten_walk_cfg
-            c.dr_phase1_level, c.dr_terrain_gate = float(dr_schedule.get("phase1_level", 0.15)), float(dr_schedule.get("terrain_gate", 0.50))
+        c.dr_schedule, c.dr_phase1_level, c.dr_terrain_gate = dr_schedule_params(dr_schedule)
         c.curriculum_enabled = int(bool(curriculum_enabled))
         c.origin_x, c.origin_y = float(origin[0]), float(origin[1])
         c.horizontal_scale, c.vertical_scale = float(horizontal_scale), float(vertical_scale)
         c.n_envs, c.n_actor, c.n_critic, c.hf_rows, c.hf_cols = self.n_envs, self.n_actor, self.n_critic, hf.shape[0], hf.shape[1]
-        self._L = load_hip_lib()
-        Handle.__init__(self, self._L, "lidar_destroy")
-        h = ctypes.c_void_p()
-        self._L.check(self._L.fn("lidar_create")(ctypes.c_int(self.device.index or 0), ctypes.byref(c), hf.ctypes.data_as(ctypes.c_void_p),
-                                                 lay["actor_xy"].ctypes.data_as(ctypes.c_void_p), lay["critic_xy"].ctypes.data_as(ctypes.c_void_p),
-                                                 ctypes.c_uint64(int(seed)), ctypes.byref(h)), "lidar_create")
-        self.h = h
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._create(c, _ptr(hf), _ptr(lay["actor_xy"]), _ptr(lay["critic_xy"]), ctypes.c_uint64(int(seed)))
 
     # ---- the step counter and the stored actor scan ---------------------------------------------------------------------------
     @property
     def step_count(self):
         v = ctypes.c_uint32()
-        self._L.check(self._L.fn("lidar_get_step")(self.h, ctypes.byref(v)), "lidar_get_step")
+        self._call("get_step", ctypes.byref(v))
         return v.value
 
     @step_count.setter
     def step_count(self, value):
-        self._L.check(self._L.fn("lidar_set_step")(self.h, ctypes.c_uint32(int(value))), "lidar_set_step")
+        self._call("set_step", ctypes.c_uint32(int(value)))
 
     def stored_scan(self):
         """float32 [n_envs, n_actor] CPU tensor; waits for the stream."""
-        out = np.zeros((self.n_envs, self.n_actor), np.float32)
-        self._L.check(self._L.fn("lidar_get_scan")(self.h, out.ctypes.data_as(ctypes.c_void_p), self._stream()), "lidar_get_scan")
-        return torch.from_numpy(out)
+        return self._get_host("get_scan", (self.n_envs, self.n_actor), np.float32)[0]
 
     def set_stored_scan(self, scan):
-        a = np.ascontiguousarray(torch.as_tensor(scan).detach().cpu().to(torch.float32).numpy())
-        if a.shape != (self.n_envs, self.n_actor):
-            raise Go2SimError(f"the stored scan has shape {(self.n_envs, self.n_actor)}, got {a.shape}")
-        self._L.check(self._L.fn("lidar_set_scan")(self.h, a.ctypes.data_as(ctypes.c_void_p), self._stream()), "lidar_set_scan")
-
-    def clear(self, envs_idx=None):
-        """Stored actor scan := 0 for ``envs_idx`` (int32 device tensor) or for every env."""
-        n = 0 if envs_idx is None else envs_idx.numel()
-        self._L.check(self._L.fn("lidar_clear")(self.h, _ptr(envs_idx), ctypes.c_int(n), self._stream()), "lidar_clear")
+        self._set_host("set_scan", "the stored scan has", (self.n_envs, self.n_actor), (scan, torch.float32))
 
     # ---- the step ----------------------------------------------------------------------------------------------------------
     def step(self, pos, pos_strides, quat, quat_strides, reset, level, obs, priv, n_in, obs_out, priv_out):
         """go2sim_lidar_step with device tensors or raw device addresses; strides are (component, env) in elements."""
-        rc = self._L.fn("lidar_step")(self.h, ctypes.c_int(self.n_envs), _ptr(pos, True), ctypes.c_longlong(pos_strides[0]), ctypes.c_longlong(pos_strides[1]),
-                                      _ptr(quat, True), ctypes.c_longlong(quat_strides[0]), ctypes.c_longlong(quat_strides[1]), _ptr(reset), _ptr(level), _ptr(obs), _ptr(priv),
-                                      ctypes.c_int(n_in), _ptr(obs_out), _ptr(priv_out), self._stream())
-        self._L.check(rc, "lidar_step")
+        self._step(ctypes.c_int(self.n_envs), _ptr(pos, True), ctypes.c_longlong(pos_strides[0]), ctypes.c_longlong(pos_strides[1]), _ptr(quat, True),
+                   ctypes.c_longlong(quat_strides[0]), ctypes.c_longlong(quat_strides[1]), _ptr(reset), _ptr(level), _ptr(obs), _ptr(priv), ctypes.c_int(n_in),
+                   _ptr(obs_out), _ptr(priv_out))
 
     def scan(self, pos, quat, reset=None, level=None):
         """The scans alone of poses given as [n, 3] / [n, 4] float32 device tensors: -> (actor [n, n_actor], actor | critic [n, n_actor + n_critic])."""
@@ -157,3 +129,28 @@ class LidarScan(Handle):
         both = torch.empty(self.n_envs, self.n_actor + self.n_critic, device=self.device)
         self.step(pos, (1, 3), quat, (1, 4), reset, level, None, None, 0, actor, both)
         return actor, both
+
+    # ---- for Go2Env (capi.EnvLaunch) -------------------------------------------------------------------------------------------
+    @staticmethod
+    def inner_widths(env_cfg, obs_cfg):
+        n_in = check_lidar_widths(env_cfg, obs_cfg)
+        return n_in, n_in + C["GO2SIM_LIDAR_PRIV_EXTRA"]
+
+    def launch(self, env, inner_obs, inner_priv):
+        """The scans and the wider rows, straight into the env's fresh tensors; pose and level are read where the step left them."""
+        pos, quat, cs = env._base_pose
+        self.step(pos, (cs, 1), quat, (cs, 1), env.reset_buf, env._level_ptr, inner_obs, inner_priv, inner_obs.shape[1], env.obs_buf, env.privileged_obs_buf)
+
+    @staticmethod
+    def schema_of(B, n_points=None):
+        return {"lidar_step": int, "lidar_scan": (torch.float32, (B, n_points))}
+
+    def state_schema(self, B):
+        return self.schema_of(B, self.n_actor)
+
+    def state_dict(self):
+        return {"lidar_step": int(self.step_count), "lidar_scan": self.stored_scan()}
+
+    def load_state_dict(self, state):
+        self.step_count = state["lidar_step"]
+        self.set_stored_scan(state["lidar_scan"])

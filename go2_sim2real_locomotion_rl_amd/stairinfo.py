@@ -13,7 +13,8 @@ import math
 import numpy as np
 import torch
 
-from .capi import C, Go2SimError, Handle, _ptr, load_hip_lib
+from .capi import C, EnvLaunch, Go2SimError, _ptr, check_layout_widths
+from .configs import dr_schedule_params
 
 
 class StairInfoCfg(ctypes.Structure):
@@ -70,13 +71,7 @@ def stair_info_widths(env_cfg):
 
 def check_stair_info_widths(env_cfg, obs_cfg):
     """The proprioceptive width n_in of a stair-info cfg whose obs_cfg carries the layout's widths; Go2SimError (naming both pairs) otherwise."""
-    n_in, want_obs, want_priv = stair_info_widths(env_cfg)
-    num_actions, have = int(env_cfg["num_actions"]), (obs_cfg["num_obs"], obs_cfg.get("num_privileged_obs"))
-    if num_actions not in ((16,) if env_cfg.get("pls_enable", False) else (16, 12)):
-        raise Go2SimError(f"the stair-info layout has 16 actions (12 with pls_enable=False), got {num_actions}")
-    if have != (want_obs, want_priv):
-        raise Go2SimError(f"obs_cfg gives num_obs / num_privileged_obs = {have[0]} / {have[1]}, the stair_info layout gives {want_obs} / {want_priv}")
-    return n_in
+    return check_layout_widths("stair-info", env_cfg, obs_cfg, stair_info_widths(env_cfg))
 
 
 def env_rows_ptr(sim):
@@ -86,15 +81,14 @@ def env_rows_ptr(sim):
     return rows.value
 
 
-class StairInfo(Handle):
+class StairInfo(EnvLaunch):
+    NAME, STATE_FAMILY = "stairinfo", "stairs_info"
+
     def __init__(self, cfg, n_envs, hf_int16, horizontal_scale, vertical_scale, origin, step_heights_m, step_depths_m, *, seed=1, dr_schedule=None,
                  curriculum_enabled=False, device=None):
-        if not torch.cuda.is_available():
-            raise Go2SimError("no ROCm GPU visible: the go2sim product path has no CPU fallback")
+        EnvLaunch.__init__(self, n_envs, device)
         if not cfg.get("enabled", True):
             raise Go2SimError("the stair_info cfg is disabled: there is nothing to detect")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.n_envs = int(n_envs)
         self.layout = lay = stair_info_layout(cfg)
         # torch.tensor(list, dtype=float32), as go2_env_stair_lidar_2.py:470-473 forms the two tables
         self.row_heights = np.ascontiguousarray(np.asarray(step_heights_m, np.float64).astype(np.float32))
@@ -103,65 +97,43 @@ class StairInfo(Handle):
             raise Go2SimError(f"the per-row step heights and depths must be two lists of one length, 1 .. {C['GO2SIM_STAIRINFO_MAX_ROWS']} rows, "
                               f"got {self.row_heights.shape} and {self.row_depths.shape}")
         self.n_rows = len(self.row_heights)
+        self._sched, self._curriculum = dr_schedule_params(dr_schedule), bool(curriculum_enabled)
         hf = np.ascontiguousarray(hf_int16, dtype=np.int16)
         c = StairInfoCfg()
         for name in ("max_range", "threshold", "edge_dist_scale", "height_scale", "depth_scale", "direction_scale", "edge_noise_std", "height_noise_std",
                      "depth_noise_std", "direction_flip_prob", "latency_prob", "full_blackout_prob"):
             setattr(c, name, lay[name])
-        c.dr_schedule = int(dr_schedule is not None)
-        if dr_schedule is not None:                                         # the defaults of flatten_walk_cfg
-            c.dr_phase1_level, c.dr_terrain_gate = float(dr_schedule.get("phase1_level", 0.15)), float(dr_schedule.get("terrain_gate", 0.50))
-        c.curriculum_enabled = int(bool(curriculum_enabled))
+        c.dr_schedule, c.dr_phase1_level, c.dr_terrain_gate = self._sched
+        c.curriculum_enabled = int(self._curriculum)
         c.origin_x, c.origin_y = float(origin[0]), float(origin[1])
         c.horizontal_scale, c.vertical_scale = float(horizontal_scale), float(vertical_scale)
         c.n_envs, c.n_samples, c.n_rows, c.hf_rows, c.hf_cols = self.n_envs, len(lay["sample_x"]), self.n_rows, hf.shape[0], hf.shape[1]
-        self._L = load_hip_lib()
-        Handle.__init__(self, self._L, "stairinfo_destroy")
-        h = ctypes.c_void_p()
-        self._L.check(self._L.fn("stairinfo_create")(ctypes.c_int(self.device.index or 0), ctypes.byref(c), hf.ctypes.data_as(ctypes.c_void_p),
-                                                     lay["sample_x"].ctypes.data_as(ctypes.c_void_p), self.row_heights.ctypes.data_as(ctypes.c_void_p),
-                                                     self.row_depths.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(int(seed)), ctypes.byref(h)),
-                      "stairinfo_create")
-        self.h = h
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._create(c, _ptr(hf), _ptr(lay["sample_x"]), _ptr(self.row_heights), _ptr(self.row_depths), ctypes.c_uint64(int(seed)))
 
     # ---- the step counter and the stored actor rows ---------------------------------------------------------------------------
     @property
     def step_count(self):
         v = ctypes.c_uint32()
-        self._L.check(self._L.fn("stairinfo_get_step")(self.h, ctypes.byref(v)), "stairinfo_get_step")
+        self._call("get_step", ctypes.byref(v))
         return v.value
 
     @step_count.setter
     def step_count(self, value):
-        self._L.check(self._L.fn("stairinfo_set_step")(self.h, ctypes.c_uint32(int(value))), "stairinfo_set_step")
+        self._call("set_step", ctypes.c_uint32(int(value)))
 
     def stored_rows(self):
         """float32 [n_envs, 4] CPU tensor; waits for the stream."""
-        out = np.zeros((self.n_envs, NUM_STAIR_INFO), np.float32)
-        self._L.check(self._L.fn("stairinfo_get_state")(self.h, out.ctypes.data_as(ctypes.c_void_p), self._stream()), "stairinfo_get_state")
-        return torch.from_numpy(out)
+        return self._get_host("get_state", (self.n_envs, NUM_STAIR_INFO), np.float32)[0]
 
     def set_stored_rows(self, rows4):
-        a = np.ascontiguousarray(torch.as_tensor(rows4).detach().cpu().to(torch.float32).numpy())
-        if a.shape != (self.n_envs, NUM_STAIR_INFO):
-            raise Go2SimError(f"the stored rows have shape {(self.n_envs, NUM_STAIR_INFO)}, got {a.shape}")
-        self._L.check(self._L.fn("stairinfo_set_state")(self.h, a.ctypes.data_as(ctypes.c_void_p), self._stream()), "stairinfo_set_state")
-
-    def clear(self, envs_idx=None):
-        """Stored actor row := 0 for ``envs_idx`` (int32 device tensor) or for every env."""
-        n = 0 if envs_idx is None else envs_idx.numel()
-        self._L.check(self._L.fn("stairinfo_clear")(self.h, _ptr(envs_idx), ctypes.c_int(n), self._stream()), "stairinfo_clear")
+        self._set_host("set_state", "the stored rows have", (self.n_envs, NUM_STAIR_INFO), (rows4, torch.float32))
 
     # ---- the step ----------------------------------------------------------------------------------------------------------
     def step(self, pos, pos_strides, quat, quat_strides, rows, reset, level, obs, priv, n_in, obs_out, priv_out):
         """go2sim_stairinfo_step with device tensors or raw device addresses; strides are (component, env) in elements."""
-        rc = self._L.fn("stairinfo_step")(self.h, ctypes.c_int(self.n_envs), _ptr(pos, True), ctypes.c_longlong(pos_strides[0]), ctypes.c_longlong(pos_strides[1]),
-                                          _ptr(quat, True), ctypes.c_longlong(quat_strides[0]), ctypes.c_longlong(quat_strides[1]), _ptr(rows), _ptr(reset), _ptr(level),
-                                          _ptr(obs), _ptr(priv), ctypes.c_int(n_in), _ptr(obs_out), _ptr(priv_out), self._stream())
-        self._L.check(rc, "stairinfo_step")
+        self._step(ctypes.c_int(self.n_envs), _ptr(pos, True), ctypes.c_longlong(pos_strides[0]), ctypes.c_longlong(pos_strides[1]), _ptr(quat, True),
+                   ctypes.c_longlong(quat_strides[0]), ctypes.c_longlong(quat_strides[1]), _ptr(rows), _ptr(reset), _ptr(level), _ptr(obs), _ptr(priv),
+                   ctypes.c_int(n_in), _ptr(obs_out), _ptr(priv_out))
 
     def info(self, pos, quat, rows=None, reset=None, level=None):
         """The fours alone of poses given as [n, 3] / [n, 4] float32 device tensors and rows as an int32 [n] device tensor:
@@ -171,3 +143,35 @@ class StairInfo(Handle):
         both = torch.empty(self.n_envs, 2 * NUM_STAIR_INFO, device=self.device)
         self.step(pos, (1, 3), quat, (1, 4), rows, reset, level, None, None, 0, actor, both)
         return actor, both
+
+    # ---- for Go2Env (capi.EnvLaunch) -------------------------------------------------------------------------------------------
+    @staticmethod
+    def inner_widths(env_cfg, obs_cfg):
+        n_in = check_stair_info_widths(env_cfg, obs_cfg)
+        return n_in, n_in + C["GO2SIM_STAIRINFO_PRIV_EXTRA"]
+
+    def launch(self, env, inner_obs, inner_priv):
+        """Both fours and the wider rows, straight into the env's fresh tensors; pose, terrain rows and level are read where the step left them."""
+        pos, quat, cs = env._base_pose
+        self.step(pos, (cs, 1), quat, (cs, 1), env._terrain_rows_ptr, env.reset_buf, env._level_ptr, inner_obs, inner_priv, inner_obs.shape[1], env.obs_buf,
+                  env.privileged_obs_buf)
+
+    def curriculum_entries(self, level):
+        """go2_env_stair_lidar_2.py:1232: the DR level the noise scales with, _get_dr_level of the curriculum level (a 0-dim float64 device tensor)."""
+        scheduled, p1, gate = self._sched
+        t = level if self._curriculum else torch.ones_like(level)
+        if scheduled:
+            pr = ((t - gate) / max(1e-6, 1.0 - gate)).clamp(0.0, 1.0)
+            t = torch.where(t < gate, torch.full_like(t, p1), p1 + (1.0 - p1) * pr)
+        return {"stair_noise_level": t}
+
+    @staticmethod
+    def schema_of(B, _=None):
+        return {"stairinfo_step": int, "stairinfo_rows": (torch.float32, (B, NUM_STAIR_INFO))}
+
+    def state_dict(self):
+        return {"stairinfo_step": int(self.step_count), "stairinfo_rows": self.stored_rows()}
+
+    def load_state_dict(self, state):
+        self.step_count = state["stairinfo_step"]
+        self.set_stored_rows(state["stairinfo_rows"])

@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 import torch
 
-from .capi import C, Go2SimError, Handle, _ptr, load_hip_lib
+from .capi import C, EnvLaunch, Go2SimError, _as_device_tensor, _ptr, check_layout_widths
 from .terrain_wells import well_scan_axes
 
 
@@ -44,68 +44,45 @@ def well_widths(env_cfg):
 def check_well_widths(env_cfg, obs_cfg):
     """The proprioceptive width n_in of a stairwell cfg whose obs_cfg carries the widths its scan grid gives; Go2SimError (naming both) otherwise."""
     check_well_scan_shape(env_cfg["terrain"])
-    n_in, want_obs, want_priv = well_widths(env_cfg)
-    num_actions, have = int(env_cfg["num_actions"]), (obs_cfg["num_obs"], obs_cfg.get("num_privileged_obs"))
-    if num_actions not in ((16,) if env_cfg.get("pls_enable", False) else (16, 12)):
-        raise Go2SimError(f"the stairwell layout has 16 actions (12 with pls_enable=False), got {num_actions}")
-    if have != (want_obs, want_priv):
-        raise Go2SimError(f"obs_cfg gives num_obs / num_privileged_obs = {have[0]} / {have[1]}, the stairwell cfg's scan grid gives {want_obs} / {want_priv}")
-    return n_in
+    return check_layout_widths("stairwell", env_cfg, obs_cfg, well_widths(env_cfg))
 
 
-class WellScan(Handle):
+class WellScan(EnvLaunch):
+    NAME, STATE_FAMILY, WIDENS_OBS = "wells", "stairwell", False         # the actor row is the step kernels' own
+
     def __init__(self, terrain_cfg, n_envs, hf_int16, horizontal_scale, vertical_scale, origin, *, n_levels=1, alive_scale=0.0, dt=0.02, device=None):
-        if not torch.cuda.is_available():
-            raise Go2SimError("no ROCm GPU visible: the go2sim product path has no CPU fallback")
+        """``alive_scale=None``: a reward_cfg without the `alive` key -- Go2Env hands no reward over and reports no rew_alive."""
+        EnvLaunch.__init__(self, n_envs, device)
         self.nx, self.ny = check_well_scan_shape(terrain_cfg)
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.n_envs, self.n_points = int(n_envs), self.nx * self.ny
+        self.n_points, self.logs = self.nx * self.ny, alive_scale is not None
         self.xs, self.ys = well_scan_axes(terrain_cfg)
         hf = np.ascontiguousarray(hf_int16, dtype=np.int16)
         c = WellsCfg()
         c.origin_x, c.origin_y = float(origin[0]), float(origin[1])
         c.horizontal_scale, c.vertical_scale = float(horizontal_scale), float(vertical_scale)
-        c.alive_scale, c.dt = float(alive_scale), float(dt)
+        c.alive_scale, c.dt = float(alive_scale or 0.0), float(dt)
         c.n_envs, c.nx, c.ny, c.hf_rows, c.hf_cols, c.n_levels = self.n_envs, self.nx, self.ny, hf.shape[0], hf.shape[1], int(n_levels)
-        self._L = load_hip_lib()
-        Handle.__init__(self, self._L, "wells_destroy")
-        h = ctypes.c_void_p()
-        self._L.check(self._L.fn("wells_create")(ctypes.c_int(self.device.index or 0), ctypes.byref(c), hf.ctypes.data_as(ctypes.c_void_p),
-                                                 self.xs.ctypes.data_as(ctypes.c_void_p), self.ys.ctypes.data_as(ctypes.c_void_p), ctypes.byref(h)), "wells_create")
-        self.h = h
+        self._create(c, _ptr(hf), _ptr(self.xs), _ptr(self.ys))
         ep, inc = ctypes.c_void_p(), ctypes.c_float()
-        self._L.check(self._L.fn("wells_alive_ep")(self.h, ctypes.byref(ep), ctypes.byref(inc)), "wells_alive_ep")
+        self._call("alive_ep", ctypes.byref(ep), ctypes.byref(inc))
         self.alive_ep_ptr, self.inc = ep.value, inc.value                  # the per-env record of the last finished episode; f32(alive_scale * dt)
-
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self.ep = _as_device_tensor(ep.value, (self.n_envs,), torch.float32, self.device)
+        self.ep_log = torch.zeros((), device=self.device)
 
     # ---- the alive sums ---------------------------------------------------------------------------------------------------------
     def alive_state(self):
         """(alive sum float32 [n_envs], step count int32 [n_envs]) CPU tensors; waits for the stream."""
-        s, k = np.zeros(self.n_envs, np.float32), np.zeros(self.n_envs, np.int32)
-        self._L.check(self._L.fn("wells_get_alive")(self.h, s.ctypes.data_as(ctypes.c_void_p), k.ctypes.data_as(ctypes.c_void_p), self._stream()), "wells_get_alive")
-        return torch.from_numpy(s), torch.from_numpy(k)
+        return self._get_host("get_alive", (self.n_envs,), np.float32, np.int32)
 
     def set_alive_state(self, alive_sum, steps):
-        s = np.ascontiguousarray(torch.as_tensor(alive_sum).detach().cpu().to(torch.float32).numpy())
-        k = np.ascontiguousarray(torch.as_tensor(steps).detach().cpu().to(torch.int32).numpy())
-        if s.shape != (self.n_envs,) or k.shape != (self.n_envs,):
-            raise Go2SimError(f"the alive state has shape {(self.n_envs,)}, got {s.shape} and {k.shape}")
-        self._L.check(self._L.fn("wells_set_alive")(self.h, s.ctypes.data_as(ctypes.c_void_p), k.ctypes.data_as(ctypes.c_void_p), self._stream()), "wells_set_alive")
-
-    def clear(self, envs_idx=None):
-        """The episode hand-over without a step for ``envs_idx`` (int32 device tensor) or for every env: record the per-second value, zero sum and count."""
-        n = 0 if envs_idx is None else envs_idx.numel()
-        self._L.check(self._L.fn("wells_clear")(self.h, _ptr(envs_idx), ctypes.c_int(n), self._stream()), "wells_clear")
+        self._set_host("set_alive", "the alive state has", (self.n_envs,), (alive_sum, torch.float32), (steps, torch.int32))
 
     # ---- the step ----------------------------------------------------------------------------------------------------------
     def step(self, pos, pos_strides, quat, quat_strides, reset, priv, n_in, priv_out, rew):
         """go2sim_wells_step with device tensors or raw device addresses; strides are (component, env) in elements."""
-        rc = self._L.fn("wells_step")(self.h, ctypes.c_int(self.n_envs), _ptr(pos, True), ctypes.c_longlong(pos_strides[0]), ctypes.c_longlong(pos_strides[1]),
-                                      _ptr(quat, True), ctypes.c_longlong(quat_strides[0]), ctypes.c_longlong(quat_strides[1]), _ptr(reset), _ptr(priv),
-                                      ctypes.c_int(n_in), _ptr(priv_out), _ptr(rew), self._stream())
-        self._L.check(rc, "wells_step")
+        self._step(ctypes.c_int(self.n_envs), _ptr(pos, True), ctypes.c_longlong(pos_strides[0]), ctypes.c_longlong(pos_strides[1]), _ptr(quat, True),
+                   ctypes.c_longlong(quat_strides[0]), ctypes.c_longlong(quat_strides[1]), _ptr(reset), _ptr(priv), ctypes.c_int(n_in), _ptr(priv_out),
+                   _ptr(rew))
 
     def scan(self, pos, quat):
         """The scan alone of poses given as [n, 3] / [n, 4] float32 device tensors -> [n, nx * ny]."""
@@ -113,3 +90,31 @@ class WellScan(Handle):
         out = torch.empty(self.n_envs, self.n_points, device=self.device)
         self.step(pos, (1, 3), quat, (1, 4), None, None, 0, out, None)
         return out
+
+    # ---- for Go2Env (capi.EnvLaunch) -------------------------------------------------------------------------------------------
+    @staticmethod
+    def inner_widths(env_cfg, obs_cfg):
+        n_in = check_well_widths(env_cfg, obs_cfg)
+        return n_in, n_in + C["GO2SIM_WELLS_PRIV_EXTRA"]
+
+    def launch(self, env, inner_obs, inner_priv):
+        """The 11 x 11 scan into the env's wider privileged row, and the alive term onto its reward."""
+        pos, quat, cs = env._base_pose
+        self.step(pos, (cs, 1), quat, (cs, 1), env.reset_buf, inner_priv, env.num_obs, env.privileged_obs_buf, env.rew_buf if self.logs else None)
+
+    def episode_entries(self):
+        return {"rew_alive": self.ep_log} if self.logs else {}
+
+    @staticmethod
+    def schema_of(B, _=None):
+        f32 = torch.float32
+        return {"wells_alive_sum": (f32, (B,)), "wells_alive_steps": (torch.int32, (B,)), "wells_alive_ep": (f32, (B,)), "wells_alive_log": (f32, ())}
+
+    def state_dict(self):
+        alive_sum, alive_steps = self.alive_state()
+        return {"wells_alive_sum": alive_sum, "wells_alive_steps": alive_steps, "wells_alive_ep": self.ep.cpu().clone(), "wells_alive_log": self.ep_log.cpu().clone()}
+
+    def load_state_dict(self, state):
+        self.set_alive_state(state["wells_alive_sum"], state["wells_alive_steps"])
+        self.ep.copy_(state["wells_alive_ep"])
+        self.ep_log = state["wells_alive_log"].to(self.device)

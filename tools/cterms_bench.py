@@ -71,7 +71,7 @@ def main():
     env = runners["on"].env
     both = ContactTerms(B, body_links=resolve_body_links(), body_contact_scale=-2.0, stumble_scale=-1.0, device=env.device)
     rew, count = torch.zeros(B, device=env.device), torch.zeros(B, device=env.device)
-    a = (env._cterms_cf, (B, 3 * B, 1), env.reset_buf, rew, count)
+    a = (env._contact_force_ptr, (B, 3 * B, 1), env.reset_buf, rew, count)
     sides = {"body": lambda: env._cterms.step(*a), "both": lambda: both.step(*a)}
     us = {k: [] for k in sides}
     for fn in sides.values():

@@ -18,6 +18,8 @@ import json
 import os
 import sys
 
+import types
+
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,13 +74,21 @@ class EagerScan:
         torch.cat([priv[:, :n_in], actor, priv[:, n_in:], critic], dim=1, out=priv_out)
 
 
+def swap_in(env, hip, eager):
+    """Run `eager` (a `step` with the handle's signature) in the env's launch list in the place of the handle `hip`; nothing is cleared or logged."""
+    eager.launch = types.MethodType(type(hip).launch, eager)
+    eager.clear = eager.log = lambda *a: None
+    eager.episode_entries, eager.curriculum_entries = hip.episode_entries, hip.curriculum_entries
+    env._launches[env._launches.index(hip)] = eager
+
+
 def eager_for(env):
     """The eager scan on an LIDAR Go2Env's own buffers: the pose fields, the level word of the globals, the heightfield the env was built with."""
     from go2_sim2real_locomotion_rl_amd.configs import build_stair_terrain
-    from go2_sim2real_locomotion_rl_amd.go2_env import _as_device_tensor
+    from go2_sim2real_locomotion_rl_amd.capi import _as_device_tensor
 
     hf, info = build_stair_terrain(env.env_cfg["terrain"])
-    pos_ptr, quat_ptr, cs = env._lidar_pose
+    pos_ptr, quat_ptr, cs = env._base_pose
     pos = _as_device_tensor(pos_ptr, (3, cs), torch.float32, env.device)
     quat = _as_device_tensor(quat_ptr, (4, cs), torch.float32, env.device)
     return EagerScan(env._lidar.layout, hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"], env.num_envs, pos, quat,
@@ -158,8 +168,7 @@ def main():
 
     # (a) the closed collection loop
     runners = {"stairs": make_runner("stairs", B, T), "lidar": make_runner("lidar", B, T), "lidar_eager": make_runner("lidar", B, T)}
-    runners["lidar_eager"].env._lidar_hip, runners["lidar_eager"].env._lidar = runners["lidar_eager"].env._lidar, eager_for(runners["lidar_eager"].env)
-    runners["lidar_eager"].env._lidar.clear = lambda idx=None: None
+    swap_in(runners["lidar_eager"].env, runners["lidar_eager"].env._lidar, eager_for(runners["lidar_eager"].env))
     ms = {k: [] for k in runners}
     for r in runners.values():
         collect(r, T)
@@ -172,9 +181,9 @@ def main():
     # (b) the scan call of one env step, on the LIDAR env's own buffers
     env = runners["lidar"].env
     hip, eager = env._lidar, eager_for(env)
-    pos, quat, cs = env._lidar_pose
+    pos, quat, cs = env._base_pose
     obs_out, priv_out = torch.empty_like(env.obs_buf), torch.empty_like(env.privileged_obs_buf)
-    a = (pos, (cs, 1), quat, (cs, 1), env.reset_buf, env._lidar_level, env._inner_obs, env._inner_priv, env._lidar_n_in, obs_out, priv_out)
+    a = (pos, (cs, 1), quat, (cs, 1), env.reset_buf, env._level_ptr, env._inner_obs, env._inner_priv, env._inner_obs.shape[1], obs_out, priv_out)
     sides = {"hip": lambda: hip.step(*a), "torch": lambda: eager.step(*a)}
     us = {k: [] for k in sides}
     for fn in sides.values():

@@ -23,6 +23,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from lidar_bench import swap_in  # noqa: E402
 
 
 class EagerStairInfo:
@@ -95,13 +96,13 @@ class EagerStairInfo:
 def eager_for(env):
     """The eager form on a stair-info Go2Env's own buffers: the pose fields, the terrain rows, the level word, the heightfield the env was built with."""
     from go2_sim2real_locomotion_rl_amd.configs import build_stair_terrain
-    from go2_sim2real_locomotion_rl_amd.go2_env import _as_device_tensor
+    from go2_sim2real_locomotion_rl_amd.capi import _as_device_tensor
 
     hf, info = build_stair_terrain(env.env_cfg["terrain"])
-    pos_ptr, quat_ptr, cs = env._lidar_pose
+    pos_ptr, quat_ptr, cs = env._base_pose
     pos = _as_device_tensor(pos_ptr, (3, cs), torch.float32, env.device)
     quat = _as_device_tensor(quat_ptr, (4, cs), torch.float32, env.device)
-    rows = _as_device_tensor(env._stairinfo_rows, (cs,), torch.int32, env.device)
+    rows = _as_device_tensor(env._terrain_rows_ptr, (cs,), torch.int32, env.device)
     return EagerStairInfo(env._stairinfo.layout, hf, info["horizontal_scale"], info["vertical_scale"], info["terrain_origin"], info["step_heights_m"],
                           info["step_depths_m"], env.num_envs, pos, quat, rows, env._glob_f64[env._level_off], env.env_cfg.get("dr_schedule"), env.device)
 
@@ -184,8 +185,7 @@ def main():
     runners = {"stairs": make_runner("stairs", B, T), "lidar": make_runner("lidar", B, T), "stair_info": make_runner("stair_info", B, T),
                "stair_info_eager": make_runner("stair_info", B, T)}
     eenv = runners["stair_info_eager"].env
-    eenv._stairinfo_hip, eenv._stairinfo = eenv._stairinfo, eager_for(eenv)
-    eenv._stairinfo.clear = lambda idx=None: None
+    swap_in(eenv, eenv._stairinfo, eager_for(eenv))
     ms = {k: [] for k in runners}
     for r in runners.values():
         collect(r, T)
@@ -198,9 +198,9 @@ def main():
     # (b) the call of one env step, on the stair-info env's own buffers
     env = runners["stair_info"].env
     hip, eager = env._stairinfo, eager_for(env)
-    pos, quat, cs = env._lidar_pose
+    pos, quat, cs = env._base_pose
     obs_out, priv_out = torch.empty_like(env.obs_buf), torch.empty_like(env.privileged_obs_buf)
-    a = (pos, (cs, 1), quat, (cs, 1), env._stairinfo_rows, env.reset_buf, env._lidar_level, env._inner_obs, env._inner_priv, env._lidar_n_in, obs_out, priv_out)
+    a = (pos, (cs, 1), quat, (cs, 1), env._terrain_rows_ptr, env.reset_buf, env._level_ptr, env._inner_obs, env._inner_priv, env._inner_obs.shape[1], obs_out, priv_out)
     sides = {"hip": lambda: hip.step(*a), "torch": lambda: eager.step(*a)}
     us = {k: [] for k in sides}
     for fn in sides.values():

@@ -74,12 +74,13 @@ def timed(fn):
 
 def scan_launch_us(env, reps=200):
     """one scan launch of `env` on its own pose buffers, back to back: microseconds per launch"""
-    pos, quat, cs = env._lidar_pose
+    pos, quat, cs = env._base_pose
     if env._wells is not None:
         rew = torch.zeros(env.num_envs, device=env.device)
-        one = lambda: env._wells.step(pos, (cs, 1), quat, (cs, 1), env.reset_buf, env._inner_priv, env._lidar_n_in, env.privileged_obs_buf, rew)
+        one = lambda: env._wells.step(pos, (cs, 1), quat, (cs, 1), env.reset_buf, env._inner_priv, env.num_obs, env.privileged_obs_buf, rew)
     else:
-        one = lambda: env._lidar.step(pos, (cs, 1), quat, (cs, 1), env.reset_buf, env._lidar_level, env._inner_obs, env._inner_priv, env._lidar_n_in,
+        n_in = env._inner_obs.shape[1]
+        one = lambda: env._lidar.step(pos, (cs, 1), quat, (cs, 1), env.reset_buf, env._level_ptr, env._inner_obs, env._inner_priv, n_in,
                                       env.obs_buf, env.privileged_obs_buf)
     many = lambda: [one() for _ in range(reps)]
     many()
