@@ -10,9 +10,9 @@ REPO_ROOT = os.path.dirname(_HERE)
 _CSRC = os.path.join(_HERE, "csrc")
 # The product's sources, csrc/go2sim<suffix>.hip: the simulator with the env, policy inference, and what the product library alone has (include/go2sim_<name>.h
 # states each one's ABI): the PPO update, the observation normaliser, the LIDAR scan, the stair info, distillation (feed-forward, recurrent), RND, the
-# rough-terrain ground query, the stairwell scan, env snapshots, the contact terms.
+# rough-terrain ground query, the stairwell scan, env snapshots, the contact terms, the evaluation statistics.
 HIP_SOURCES = tuple(os.path.join(_CSRC, f"go2sim{s}.hip") for s in ("", "_policy", "_train", "_norm", "_lidar", "_stairinfo", "_distill", "_rdistill", "_rnd",
-                                                                    "_tiles", "_wells", "_state", "_cterms"))
+                                                                    "_tiles", "_wells", "_state", "_cterms", "_evalstats"))
 # The device and host headers they share, csrc/go2sim_<name>.h (each one's first lines say between which sources).
 HIP_DEV_HEADERS = tuple(os.path.join(_CSRC, f"go2sim_{n}.h") for n in ("gjk_dev", "mlp_dev", "lstm_dev", "train_dev", "trainer_host", "distill_dev", "norm_dev",
                                                                        "tiles_dev", "wells_dev", "envlaunch_dev"))

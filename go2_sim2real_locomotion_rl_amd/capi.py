@@ -72,6 +72,7 @@ TILES_HEADER, DECLARED_TILES_FUNCS = _product_header("tiles")                  #
 WELLS_HEADER, DECLARED_WELLS_FUNCS = _product_header("wells")                  # the stairwell env: 11 x 11 scan, alive term
 STATE_HEADER, DECLARED_STATE_FUNCS = _product_header("state")                  # env snapshots: the record's size, save, load
 CTERMS_HEADER, DECLARED_CTERMS_FUNCS = _product_header("cterms")                # the contact terms: body_contact, stumble
+EVALSTATS_HEADER, DECLARED_EVALSTATS_FUNCS = _product_header("evalstats")       # the evaluation statistics: per-env and per-bin records
 RNG_HEADER, _ = _product_header("rng", [])                                     # the purposes of the random stream (constants only; both libraries)
 # train_cfg["policy"]["activation"] as rsl_rl's resolve_nn_activation spells it -> GO2SIM_ACT_*
 ACTIVATIONS = {n: C["GO2SIM_ACT_" + n.upper()] for n in ("elu", "selu", "relu", "lrelu", "tanh", "sigmoid", "identity")}

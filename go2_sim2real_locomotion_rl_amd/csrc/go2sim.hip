@@ -30,6 +30,7 @@
 
 #include "../../include/go2sim.h"
 #include "../../include/go2sim_detmath.h"
+#include "../../include/go2sim_evalstats.h"
 #include "../../include/go2sim_lidar.h"
 #include "../../include/go2sim_rng.h"
 #include "../../include/go2sim_stairinfo.h"
@@ -7576,6 +7577,24 @@ int go2sim_lidar_env_pose(go2sim_t* h, const float** pos, const float** quat, lo
 int go2sim_stairinfo_env_rows(go2sim_t* h, const int** terrain_row) {
   if (!h || !terrain_row) return GO2SIM_E_BADARG;
   *terrain_row = h->P.i + (size_t)IO(terrain_row) * h->B;
+  return GO2SIM_E_OK;
+}
+// include/go2sim_evalstats.h: the env buffers the evaluation statistics (csrc/go2sim_evalstats.hip) read in place -- SoA [k][n_envs] in the pool
+int go2sim_env_buffer_dev(go2sim_t* h, int buf, const float** ptr, long long* comp_stride, long long* env_stride) {
+  if (!h || !ptr || !comp_stride || !env_stride) return GO2SIM_E_BADARG;
+  size_t off;
+  switch (buf) {
+    case GO2SIM_EB_COMMANDS: off = FO(commands); break;
+    case GO2SIM_EB_BASE_LIN_VEL: off = FO(base_lin_vel); break;
+    case GO2SIM_EB_BASE_ANG_VEL: off = FO(base_ang_vel); break;
+    case GO2SIM_EB_PROJECTED_GRAVITY: off = FO(projected_gravity); break;
+    case GO2SIM_EB_DOF_VEL: off = FO(e_dof_vel); break;
+    case GO2SIM_EB_TORQUE: off = FO(torque); break;
+    default: return GO2SIM_E_BADARG;
+  }
+  *ptr = h->P.f + off * h->B;
+  *comp_stride = (long long)h->B;
+  *env_stride = 1;
   return GO2SIM_E_OK;
 }
 int go2sim_env_set_level(go2sim_t* h, double level, void* stream) {

@@ -317,6 +317,7 @@ class Go2Env:
         self._terrain_rows_locked = False
         self.log_extras = bool(log_extras)            # per-step snapshot of the episode / curriculum / DR logs (one small device copy)
         self.errno_poll_every = int(errno_poll_every)  # env steps between errno polls (simulator.py:267: every 10 substeps)
+        self.freeze_curriculum = bool(freeze_curriculum)  # what evaluation.Evaluator asks for
         self._steps_since_poll = 0
         self._views = {}
         self._extras_snapshot = self._extras_full_snapshot = None
